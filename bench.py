@@ -92,6 +92,31 @@ def rocprof_avg_ms(kernel_class, n, mb, conv=False):
     return total / calls * 1e-6 if calls else None
 
 
+DUMP_VOXELS = 1 << 21          # --dump-outputs: voxels per volume array at most (4 arrays x 8 MiB float32)
+DUMP_SEED = 0
+
+
+def dump_outputs(out_dir, solver, write):
+    """--dump-outputs: what the last timed step computed, as a caller of FullfieldSolver.step receives it — the minibatch's
+    loss (float64), the updated volume (delta, beta) and the volume gradient the update was taken from (float32, (Y, X, Z)) —
+    as out_dir/<name>.npy.  A volume of more than DUMP_VOXELS voxels is sampled at DUMP_VOXELS fixed voxels (flat (Y, X, Z)
+    indices drawn with DUMP_SEED, ascending), the same in every array and every run.  Every rank calls this (reading the
+    gradient back after a sharded step is a collective); the rank with `write` set writes."""
+    nvox = solver.dim_y * solver.dim_x * solver.dim_z
+    idx = None
+    if nvox > DUMP_VOXELS:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(nvox, DUMP_VOXELS, replace=False))
+    out = {'loss': np.asarray(solver._get_loss(), dtype=np.float64)}     # what step(want_loss=True) returns, still on the device
+    for names, pair in ((('delta', 'beta'), solver.get_volume), (('grad_delta', 'grad_beta'), solver.gradient_to_host)):
+        for name, a in zip(names, pair()):
+            out[name] = a if idx is None else a.reshape(-1)[idx]
+    if write:
+        os.makedirs(out_dir, exist_ok=True)
+        for name, a in out.items():
+            np.save(os.path.join(out_dir, name + '.npy'), a)
+        print('[bench] outputs of the last timed step: {} in {}'.format(', '.join(sorted(out)), out_dir), file=sys.stderr)
+
+
 def make_phantom(n, seed=3):
     """'charcoal-like': U(0, 2e-6) box-smoothed over 3 voxels, beta = 0.1 delta."""
     from scipy.ndimage import uniform_filter
@@ -230,11 +255,13 @@ def rehearse_cpu(args, out):
         allmax = lambda v: float(np.max(grp.allgather(np.array([v]))))
         allsum = lambda a: np.sum(grp.allgather(np.asarray(a)), axis=0)
         barrier, close = grp.barrier, grp.close
+    g = np.zeros(1 << 16)
+    for i in range(args.warmup):
+        g = allsum(np.full(1 << 16, float(rank + i)))              # stands in for the gradient exchange
     barrier()
     t0 = time.perf_counter()
-    g = np.zeros(1 << 16)
-    for i in range(args.warmup + args.steps):
-        g = allsum(np.full(1 << 16, float(rank + i)))              # stands in for the gradient exchange
+    for i in range(args.warmup, args.warmup + args.steps):
+        g = allsum(np.full(1 << 16, float(rank + i)))
     barrier()
     elapsed = allmax(time.perf_counter() - t0)
     seen = allsum(np.bincount(np.concatenate(mine), minlength=args.n_theta).astype(np.float64))
@@ -340,7 +367,10 @@ def main():
     ap.add_argument('--propagator', default='fft', choices=['fft', 'conv'],
                     help="'conv': the reference entry points' truncated real-space kernel (17 taps), for comparison")
     ap.add_argument('--rehearse-cpu', action='store_true', help='launch, rendezvous, schedule and timing path of an N-rank run without GPU work')
+    ap.add_argument('--dump-outputs', metavar='DIR', help='write what the last timed step computed to DIR/<name>.npy (dump_outputs)')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         return self_launch(args.gpus)
@@ -412,6 +442,8 @@ def main():
     elapsed = time.perf_counter() - t0
     if comm.size > 1:
         elapsed = float(comm.allreduce_max_host(np.array([elapsed]))[0])
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, solver, rank == 0)
     # where the tail of a step goes (rotation adjoint, gradient exchange, Adam, all-gather), from stream-ordered time stamps in
     # two extra steps after the timed region; max over ranks
     solver.time_tail = True

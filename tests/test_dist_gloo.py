@@ -116,10 +116,18 @@ def _socket_worker(rank, world, path, out_dir):
 
 @pytest.mark.timeout(120)
 def test_socket_rendezvous_and_host_collectives(tmp_path):
+    from beyond_dof_amd.comm import rendezvous_dir
     world = 3
-    path = str(tmp_path / 'rdzv.sock')
+    # the socket goes where the library puts its own: a unix socket address holds ~107 bytes, which pytest's tmp_path
+    # (base directory, user name, test name) can exceed
+    path = os.path.join(rendezvous_dir(), 'test_rdzv_{}.sock'.format(os.getpid()))
     open(path, 'w').close()                       # a stale file of a dead job must not be in the way
-    mp.spawn(_socket_worker, args=(world, path, str(tmp_path)), nprocs=world, join=True)
+    try:
+        mp.spawn(_socket_worker, args=(world, path, str(tmp_path)), nprocs=world, join=True)
+    except BaseException:
+        if os.path.exists(path):
+            os.unlink(path)
+        raise
     for r in range(world):
         d = np.load(str(tmp_path / 'sock{}.npz'.format(r)))
         assert np.array_equal(d['tot'], [6.0, 60.0]) and np.array_equal(d['mx'], [2.0, 0.0])

@@ -32,7 +32,9 @@ def _launch_two(worker, *args, **kw):
         env = dict(os.environ, MASTER_ADDR='127.0.0.1', MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE='2',
                    LOCAL_RANK='0' if stub else str(rank), BDOF_COMM_BACKEND=backend)
         if backend == 'rccl':
-            env['BDOF_RDZV'] = os.path.join(str(args[0]), 'rdzv_{}.sock'.format(port))
+            # in the library's own rendezvous directory: tmp_path can be longer than a unix socket address (~107 bytes)
+            from beyond_dof_amd.comm import rendezvous_dir
+            env['BDOF_RDZV'] = os.path.join(rendezvous_dir(), 'test_rdzv_{}.sock'.format(port))
             env.setdefault('HSA_ENABLE_IPC_MODE_LEGACY', '0')
         if stub:
             env['BDOF_RCCL_LIB'] = stub
@@ -261,6 +263,33 @@ def test_bench_py_single_rank_matches_contract():
     assert ro['bound'] == 'hbm' and abs(ro['frac'] - ro['achieved'] / ro['peak']) < 1e-12
     assert abs(ro['achieved'] * 1e9 - ro['algorithmic_bytes_per_launch'] / (ro['avg_launch_ms_events'] * 1e-3)) <= 1e-6 * ro['achieved'] * 1e9
     assert d['cpu_baseline']['kind'] == 'port' and d['cpu_baseline']['value'] > 0
+
+
+def test_bench_py_dump_outputs(tmp_path):
+    """`python bench.py --dump-outputs DIR`: the last timed step's loss, volume and gradient as .npy files (float32 / float64,
+    at most 64 MB in all; a 256^3 volume is sampled at fixed voxels), the same in two runs of the same command."""
+    import json
+    env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK')}
+    dumps = []
+    for run in ('a', 'b'):
+        out = tmp_path / run
+        r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--size', '256', '--angles-per-gpu', '4', '--n-theta', '16',
+                            '--steps', '2', '--warmup', '1', '--no-cpu-baseline', '--no-profile', '--dump-outputs', str(out)],
+                           env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+        assert r.returncode == 0, r.stderr.decode()[-3000:]
+        lines = [ln for ln in r.stdout.decode().splitlines() if ln.strip()]
+        assert len(lines) == 1 and json.loads(lines[0])['steps'] == 2
+        names = sorted(os.listdir(str(out)))
+        assert names == ['beta.npy', 'delta.npy', 'grad_beta.npy', 'grad_delta.npy', 'loss.npy'], names
+        assert sum(os.path.getsize(str(out / n)) for n in names) <= 64 * 2 ** 20
+        dumps.append({n[:-4]: np.load(str(out / n)) for n in names})
+    a, b = dumps
+    assert a['loss'].dtype == np.float64 and a['loss'].shape == () and np.isfinite(a['loss']) and a['loss'] > 0
+    for k in ('delta', 'beta', 'grad_delta', 'grad_beta'):
+        assert a[k].dtype == np.float32 and a[k].shape == (1 << 21,) and np.all(np.isfinite(a[k])), k
+    assert np.any(a['grad_delta'] != 0) and np.any(a['delta'] != 0)
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k
 
 
 def test_two_rank_tiled_propagation(tmp_path):
