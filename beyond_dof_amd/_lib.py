@@ -11,6 +11,7 @@ LIB_PATH = os.environ.get('BDOF_LIB') or os.path.join(_HERE, 'libbdof.so')      
 
 DET_NONE, DET_NEAR, DET_FAR = 0, 1, 2
 VARIANT_NUMPY_SKIP_LAST, VARIANT_TF_ALL = 0, 1
+CFG_GRAD, CFG_GENERIC, CFG_NO_RESIDENT, CFG_ALWAYS_RESIDENT, CFG_RECOMPUTE, CFG_NO_GROT, CFG_ADJOINT64 = 1, 2, 4, 8, 16, 32, 64
 K_ROW_FWD, K_COL_PROP, K_ROW_BWD, K_LOSS, K_ROT_ADJ, K_ADAM = range(6)
 KERNEL_CLASS_NAMES = ['row_fwd', 'col_prop', 'row_bwd', 'loss', 'rot_adjoint', 'adam']
 

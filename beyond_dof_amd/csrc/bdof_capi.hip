@@ -45,7 +45,7 @@ struct bdof_ctx {
     int ncu = 256;
     int NY = 0, NX = 0, S = 0, Bmax = 0;
     bool with_grad = false;
-    bool recompute = false;                      // tape-free adjoint (bdof_configure flag 16): the tape holds 3 fields, not S
+    bool recompute = false;                      // tape-free adjoint (BDOF_CFG_RECOMPUTE): the tape holds 3 fields, not S
     cf *twY = nullptr, *twX = nullptr;
     // dithered twiddle tables (bdof_fft.h; BDOF_TW_DITHER=D, default 64): D copies of each table, entry j of copy d rounded up or
     // down so that the mean over the D copies is the float64 value to ulp / D; the launches of slice z take copy z mod D
@@ -110,7 +110,7 @@ struct bdof_ctx {
     // generic-size engine (rocFFT): one plan pair per batch size
     bool generic = false;
     std::map<int, std::pair<rocfft_plan, rocfft_plan>> gplans;
-    // float64 adjoint sweep (bdof_configure flag 64; generic engine)
+    // float64 adjoint sweep (BDOF_CFG_ADJOINT64; generic engine)
     bool adj64 = false, have_h64 = false;
     std::map<int, std::pair<rocfft_plan, rocfft_plan>> gplans64;
     std::map<std::array<int, 4>, std::pair<rocfft_plan, rocfft_plan>> fplans;      // bdof_fields_free_step: (NX, NY, B, double)
@@ -159,6 +159,31 @@ static int fail(bdof_ctx* c, int code, const std::string& msg) {
         }                                                                                          \
     } while (0)
 
+// ---- argument checks shared by the entry points (0 = passed, else the code of the failure) -------------------------------------
+// the status of the launches just queued
+static int launched(bdof_ctx* c) {
+    HIPC(c, hipGetLastError());
+    return 0;
+}
+static int need_configured(bdof_ctx* c) {
+    return c->NY ? 0 : fail(c, BDOF_ERR_STATE, "bdof_configure has not been called");
+}
+static int need_angles(bdof_ctx* c, const int* angle_of_b) {
+    return c->obj.tab && !angle_of_b ? fail(c, BDOF_ERR_ARG, "angle_of_b required with a rotation table") : 0;
+}
+static int check_batch(bdof_ctx* c, int B) {
+    return B < 1 || B > c->Bmax ? fail(c, BDOF_ERR_ARG, "batch size outside [1, Bmax]") : 0;
+}
+static int check_range(bdof_ctx* c, int z0, int nz) {
+    return z0 < 0 || nz < 1 || z0 + nz > c->S ? fail(c, BDOF_ERR_ARG, "slice range outside [0, S)") : 0;
+}
+static int check_taper(bdof_ctx* c, int TX, int TY, int taper) {
+    return taper < 0 || 2 * taper > TX || 2 * taper > TY ? fail(c, BDOF_ERR_ARG, "taper must fit the tile") : 0;
+}
+static int check_halo(bdof_ctx* c, int TX, int TY, int halo_x, int halo_y) {
+    return halo_x < 0 || halo_y < 0 || 2 * halo_x >= TX || 2 * halo_y >= TY ? fail(c, BDOF_ERR_ARG, "halo must leave a core") : 0;
+}
+
 // Mean-refraction carrier (modulate_eps_s): constant part of the wave entering slice z, a_z = a_0 (cbar H00)^z
 // (H00 = DC value of the transfer function, cbar = mean modulation factor of the object)
 static std::complex<double> carrier_z(const bdof_ctx* c, int z) { return c->a0 * std::pow((1.0 + c->cbm1) * c->h00, z); }
@@ -181,15 +206,11 @@ static cf carrier_det(const bdof_ctx* c) {
 // bdof_set_meas_mode(1): the host subtracted |a_0| from the amplitudes; the detector carrier has modulus |a_0| |cbar|^S
 static float meas_dref(const bdof_ctx* c) { return (float)(std::abs(carrier_end(c)) - std::abs(c->a0)); }
 // the object's mean modulation factor rides on the carrier when the carrier is a scalar of the transfer-function path
-static bool want_cbar(const bdof_ctx* c) {
-    static const bool off = std::getenv("BDOF_NO_MEAN_CARRIER") != nullptr;
-    return !off && std::abs(c->a0) > 0.0 && !c->pstack && !c->have_conv;
-}
+static bool want_cbar(const bdof_ctx* c) { return std::abs(c->a0) > 0.0 && !c->pstack && !c->have_conv; }
 
 // far-field detector + plane-wave carrier: the DC seed of the adjoint is carried as a float64 scalar (AdjCarrier)
 static bool use_adj_carrier(const bdof_ctx* c) {
-    static const bool off = std::getenv("BDOF_NO_ADJ_CARRIER") != nullptr;
-    return !off && c->det_mode == BDOF_DET_FAR && !c->pstack && c->gcar && std::abs(c->a0) > 0.0;
+    return c->det_mode == BDOF_DET_FAR && !c->pstack && c->gcar && std::abs(c->a0) > 0.0;
 }
 static double2 d2(std::complex<double> v) { return make_double2(v.real(), v.imag()); }
 // conj(H00)^n: what the adjoint carrier picks up in n adjoint transfer-function steps
@@ -260,15 +281,23 @@ template <int N> static int rows_grid(const bdof_ctx* c, int B, int R) {
     return balanced_grid(c, B * R / RowCfg<N>::TILE, N >= 1024 ? 1 : 2);
 }
 
-#define DISPATCH_N(n, EXPR)                                    \
-    switch (n) {                                               \
-        case 64: { constexpr int N_ = 64; EXPR; } break;       \
-        case 128: { constexpr int N_ = 128; EXPR; } break;     \
-        case 256: { constexpr int N_ = 256; EXPR; } break;     \
-        case 512: { constexpr int N_ = 512; EXPR; } break;     \
-        case 1024: { constexpr int N_ = 1024; EXPR; } break;   \
-        default: break;                                        \
+#define DISPATCH_N(n, ...)                                            \
+    switch (n) {                                                      \
+        case 64: { constexpr int N_ = 64; __VA_ARGS__; } break;       \
+        case 128: { constexpr int N_ = 128; __VA_ARGS__; } break;     \
+        case 256: { constexpr int N_ = 256; __VA_ARGS__; } break;     \
+        case 512: { constexpr int N_ = 512; __VA_ARGS__; } break;     \
+        case 1024: { constexpr int N_ = 1024; __VA_ARGS__; } break;   \
+        default: break;                                               \
     }
+
+// Runtime choice -> template argument: f(std::integral_constant<int, v>) for v in [0, N) (values from N - 1 up take N - 1),
+// f(std::true_type / false_type) for a bool; the constant converts to its value where a template argument is expected.
+template <int N, int I = 0, class F> static auto with_int(int v, F&& f) {
+    if constexpr (I + 1 < N) { if (v != I) return with_int<N, I + 1>(v, f); }
+    return f(std::integral_constant<int, I>{});
+}
+template <class F> static auto with_bool(bool v, F&& f) { return v ? f(std::true_type{}) : f(std::false_type{}); }
 
 // ---- sub-batches --------------------------------------------------------------------------------
 // A batch whose tile count fills the chip's workgroup slots badly (25 wavefields of 512 rows = 800 tiles on 512 slots:
@@ -416,26 +445,9 @@ static void launch_row_fwd(bdof_ctx* c, int B, int z, const cf* in, cf* out, boo
         a.pz_b = c->NX;
     }
     c->tw_tick = (unsigned)z;
-    const bool pf = a.pz != nullptr;
-    DISPATCH_N(c->NY, {
-        const dim3 grid(rows_grid<N_>(c, B, c->NX));
-        const dim3 blk(BDOF_THREADS);
-        if (z == 0 || start) {
-            if (pf) {
-                if (tstore) BDOF_LAUNCH(ps, (k_row_fwd<N_, true, true, true>), grid, blk, 0, c->sub_stream, a);
-                else BDOF_LAUNCH(ps, (k_row_fwd<N_, true, false, true>), grid, blk, 0, c->sub_stream, a);
-            } else {
-                if (tstore) BDOF_LAUNCH(ps, (k_row_fwd<N_, true, true>), grid, blk, 0, c->sub_stream, a);
-                else BDOF_LAUNCH(ps, (k_row_fwd<N_, true, false>), grid, blk, 0, c->sub_stream, a);
-            }
-        } else if (pf) {
-            if (tstore) BDOF_LAUNCH(ps, (k_row_fwd<N_, false, true, true>), grid, blk, 0, c->sub_stream, a);
-            else BDOF_LAUNCH(ps, (k_row_fwd<N_, false, false, true>), grid, blk, 0, c->sub_stream, a);
-        } else {
-            if (tstore) BDOF_LAUNCH(ps, (k_row_fwd<N_, false, true>), grid, blk, 0, c->sub_stream, a);
-            else BDOF_LAUNCH(ps, (k_row_fwd<N_, false, false>), grid, blk, 0, c->sub_stream, a);
-        }
-    });
+    DISPATCH_N(c->NY, with_bool(z == 0 || start, [&](auto FIRST) { with_bool(tstore, [&](auto TSTORE) { with_bool(a.pz != nullptr, [&](auto PF) {
+        BDOF_LAUNCH(ps, (k_row_fwd<N_, FIRST, TSTORE, PF>), dim3(rows_grid<N_>(c, B, c->NX)), dim3(BDOF_THREADS), 0, c->sub_stream, a);
+    }); }); }));
 }
 
 // A_z^-1 (tape-free adjoint): scattered part of phi_z (L1 hybrid, or real space) -> R eps(psi_z) in L2
@@ -446,12 +458,9 @@ static void launch_row_unmod(bdof_ctx* c, int B, int z, const cf* in, cf* out, b
     a.pz_b = 0;
     sq_of(c, (unsigned)z, a.sq);
     c->tw_tick = (unsigned)z;
-    DISPATCH_N(c->NY, {
-        const dim3 grid(rows_grid<N_>(c, B, c->NX));
-        const dim3 blk(BDOF_THREADS);
-        if (a.pz) BDOF_LAUNCH(ps, (k_row_fwd<N_, false, true, true, true>), grid, blk, 0, c->sub_stream, a);
-        else BDOF_LAUNCH(ps, (k_row_fwd<N_, false, true, false, true>), grid, blk, 0, c->sub_stream, a);
-    });
+    DISPATCH_N(c->NY, with_bool(a.pz != nullptr, [&](auto PF) {
+        BDOF_LAUNCH(ps, (k_row_fwd<N_, false, true, PF, true>), dim3(rows_grid<N_>(c, B, c->NX)), dim3(BDOF_THREADS), 0, c->sub_stream, a);
+    }));
 }
 
 // B: L2 -> L1
@@ -467,11 +476,10 @@ static void launch_row_prop(bdof_ctx* c, int B, const cf* in, cf* out, const cf*
     }
     RowPropArgs a{sub_field(c, in), sub_field(c, out), h, B, c->NY, scale, conj_h, tw_of(c, c->twX, c->NX, tick)};
     sq_of(c, tick, a.sq);
-    DISPATCH_N(c->NX, {
-        // the adjoint step runs the instance with exact transform constants (bdof_fft.h: that is where the gradient's error is made)
-        if (conj_h ? BDOF_EX_ADJ : BDOF_EX_FWD_B) BDOF_LAUNCH(ps, (k_row_prop<N_, true>), dim3(rows_grid<N_>(c, B, c->NY)), dim3(BDOF_THREADS), 0, c->sub_stream, a);
-        else BDOF_LAUNCH(ps, (k_row_prop<N_, false>), dim3(rows_grid<N_>(c, B, c->NY)), dim3(BDOF_THREADS), 0, c->sub_stream, a);
-    });
+    // the adjoint step runs the instance with exact transform constants (bdof_fft.h: that is where the gradient's error is made)
+    DISPATCH_N(c->NX, with_bool(conj_h ? BDOF_EX_ADJ : BDOF_EX_FWD_B, [&](auto EX) {
+        BDOF_LAUNCH(ps, (k_row_prop<N_, EX>), dim3(rows_grid<N_>(c, B, c->NY)), dim3(BDOF_THREADS), 0, c->sub_stream, a);
+    }));
 }
 
 // A'_z: L1 (g) + phi tape -> L2 (g)
@@ -492,27 +500,11 @@ static void launch_row_bwd(bdof_ctx* c, int B, int z, const cf* gin, const cf* t
                  gt && gt->grot ? gt->S_ : c->S, gt && gt->grot ? gt->z_ : z};
     sq_of(c, (unsigned)z, a.sq);
     c->tw_tick = (unsigned)z;
-    const bool pf = a.pz != nullptr;
-    DISPATCH_N(c->NY, {
-        const dim3 grid(rows_grid<N_>(c, B, c->NX));
-        const dim3 blk(BDOF_THREADS);
-        if (a.ac.gcar) {         // far field + plane-wave carrier (never together with a carrier field)
-            if (hist == 0) BDOF_LAUNCH(ps, (k_row_bwd<N_, 0, false, true>), grid, blk, 0, c->sub_stream, a);
-            else if (hist == 1) BDOF_LAUNCH(ps, (k_row_bwd<N_, 1, false, true>), grid, blk, 0, c->sub_stream, a);
-            else if (hist == 2) BDOF_LAUNCH(ps, (k_row_bwd<N_, 2, false, true>), grid, blk, 0, c->sub_stream, a);
-            else BDOF_LAUNCH(ps, (k_row_bwd<N_, 3, false, true>), grid, blk, 0, c->sub_stream, a);
-        } else if (pf) {
-            if (hist == 0) BDOF_LAUNCH(ps, (k_row_bwd<N_, 0, true>), grid, blk, 0, c->sub_stream, a);
-            else if (hist == 1) BDOF_LAUNCH(ps, (k_row_bwd<N_, 1, true>), grid, blk, 0, c->sub_stream, a);
-            else if (hist == 2) BDOF_LAUNCH(ps, (k_row_bwd<N_, 2, true>), grid, blk, 0, c->sub_stream, a);
-            else BDOF_LAUNCH(ps, (k_row_bwd<N_, 3, true>), grid, blk, 0, c->sub_stream, a);
-        } else {
-            if (hist == 0) BDOF_LAUNCH(ps, (k_row_bwd<N_, 0>), grid, blk, 0, c->sub_stream, a);
-            else if (hist == 1) BDOF_LAUNCH(ps, (k_row_bwd<N_, 1>), grid, blk, 0, c->sub_stream, a);
-            else if (hist == 2) BDOF_LAUNCH(ps, (k_row_bwd<N_, 2>), grid, blk, 0, c->sub_stream, a);
-            else BDOF_LAUNCH(ps, (k_row_bwd<N_, 3>), grid, blk, 0, c->sub_stream, a);
-        }
-    });
+    // carrier form: 0 scalar, 1 field (PF), 2 far field + plane-wave carrier (GC; never together with a carrier field)
+    const int form = a.ac.gcar ? 2 : a.pz ? 1 : 0;
+    DISPATCH_N(c->NY, with_int<4>(hist, [&](auto HIST) { with_int<3>(form, [&](auto FORM) {
+        BDOF_LAUNCH(ps, (k_row_bwd<N_, HIST, FORM == 1, FORM == 2>), dim3(rows_grid<N_>(c, B, c->NX)), dim3(BDOF_THREADS), 0, c->sub_stream, a);
+    }); }));
 }
 
 // Real-space detector on L1 rows.  Returns the grid (= number of partial sums when meas != null).
@@ -528,11 +520,9 @@ static int launch_loss_real(bdof_ctx* c, int B, const cf* in, cf* out_hyb, bool 
                c->meas_dev ? (dref_override ? *dref_override : meas_dref(c)) : 0.f,
                pf64 ? pf64 : (pfield && pfield == c->pdet ? c->pdet64 : nullptr), pscale};
     int grid = 0;
-    DISPATCH_N(c->NY, {
-        grid = rows_grid<N_>(c, B, c->NX);
-        if (tstore) hipLaunchKernelGGL((k_row_loss<N_, false, true>), dim3(grid), dim3(BDOF_THREADS), 0, c->sub_stream, a);
-        else hipLaunchKernelGGL((k_row_loss<N_, false, false>), dim3(grid), dim3(BDOF_THREADS), 0, c->sub_stream, a);
-    });
+    DISPATCH_N(c->NY, grid = rows_grid<N_>(c, B, c->NX); with_bool(tstore, [&](auto TSTORE) {
+        hipLaunchKernelGGL((k_row_loss<N_, false, TSTORE>), dim3(grid), dim3(BDOF_THREADS), 0, c->sub_stream, a);
+    }));
     return grid;
 }
 
@@ -562,10 +552,9 @@ static int launch_loss_far(bdof_ctx* c, int B, const cf* in, cf* out_hyb, cf* ou
 //   DET_NEAR                  : bufB = d_hat (L1)    (tf_all: one step with the combined transfer function)
 //   DET_FAR                   : bufA = R phi_{S-1} in L2 order, un-normalised (|fft2| is unchanged by the
 //                               unit-modulus transfer function, so tf_all needs no extra step here)
-enum { TAPE_NONE = 0, TAPE_HISTORY = 1, TAPE_PHI = 2, TAPE_LAST = 3 };
+enum { TAPE_NONE = 0, TAPE_HISTORY = 1, TAPE_LAST = 2 };
 // TAPE_LAST (tape-free adjoint): only the real-space phi_{S-1} is kept (tape slot 0); the adjoint sweep marches it back.
 // TAPE_HISTORY keeps psi_hat_{z+1} (the transfer-function step's output) per slice: probe_array of np_funcs.py:43.
-// TAPE_PHI keeps the real-space phi_z written by A_z: what the adjoint needs, without a third transform in A'_z.
 static void forward_sweep(bdof_ctx* c, const Group* groups, int ngroups, int tape_mode) {
     const size_t fld = (size_t)c->Bmax * c->NX * c->NY;
     const bool tf_all = c->variant == BDOF_VARIANT_TF_ALL;
@@ -573,7 +562,7 @@ static void forward_sweep(bdof_ctx* c, const Group* groups, int ngroups, int tap
         const cf* in = nullptr;
         if (z > 0) in = tape_mode == TAPE_HISTORY ? c->tape + (size_t)(z - 1) * fld : c->bufB;
         const bool last = z == c->S - 1;
-        cf* phi = tape_mode == TAPE_PHI ? c->tape + (size_t)z * fld : (tape_mode == TAPE_LAST && last ? c->tape : nullptr);
+        cf* phi = tape_mode == TAPE_LAST && last ? c->tape : nullptr;
         for (int gi = 0; gi < ngroups; ++gi) {
             const int B = groups[gi].B;
             use_group(c, groups[gi]);
@@ -823,15 +812,21 @@ static int generic_loss_grad(bdof_ctx* c, int B, const float* meas, void* out_wa
     return 0;
 }
 
+// the dynamic LDS limit of kernel K, raised once per device (the attribute is per device: a process may hold ctxs on several)
+template <auto K> static int max_lds_once(bdof_ctx* c, int bytes) {
+    static bool attr_set[BDOF_MAX_DEVICES] = {};
+    if (!attr_set[c->device % BDOF_MAX_DEVICES]) {
+        HIPC(c, hipFuncSetAttribute((const void*)K, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+        attr_set[c->device % BDOF_MAX_DEVICES] = true;
+    }
+    return 0;
+}
+
 // ---- LDS-resident engine ---------------------------------------------------------------------------
 template <int N, int T, int WPE> static int resident_launch_t(bdof_ctx* c, const ResArgs& a, int grid, int* waves) {
     *waves = T / 64;
     const size_t lds = sizeof(cf) * ((size_t)N * (N | 1) + 2 * N) + sizeof(long long) * 3 * N;
-    static bool attr_set[BDOF_MAX_DEVICES] = {};      // the attribute is per device (a process may hold ctxs on several)
-    if (!attr_set[c->device % BDOF_MAX_DEVICES]) {
-        HIPC(c, hipFuncSetAttribute((const void*)k_resident<N, T, WPE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr_set[c->device % BDOF_MAX_DEVICES] = true;
-    }
+    if (int r = max_lds_once<k_resident<N, T, WPE>>(c, (int)lds)) return r;
     hipLaunchKernelGGL((k_resident<N, T, WPE>), dim3(grid), dim3(T), lds, c->stream, a);
     return 0;
 }
@@ -846,7 +841,7 @@ static bool use_resident(const bdof_ctx* c, int B) {
     if (!c->resident || c->recompute) return false;
     // far field + plane-wave carrier needs the adjoint carrier (AdjCarrier), which the resident kernel does not carry: the
     // streaming / generic engines take that case (plane-wave full-field at a resident-plan size)
-    if (c->det_mode == BDOF_DET_FAR && !c->pstack && std::abs(c->a0) > 0.0 && !std::getenv("BDOF_NO_ADJ_CARRIER")) return false;
+    if (c->det_mode == BDOF_DET_FAR && !c->pstack && std::abs(c->a0) > 0.0) return false;
     return c->generic || c->res_always || B * 4 >= c->ncu;
 }
 
@@ -882,18 +877,35 @@ static int resident_run(bdof_ctx* c, int B, const float* meas, void* out_wave, b
     if (meas)
         hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, c->stream, c->partial, grid * waves, 1.0 / ((double)B * c->NX * c->NY),
                            c->loss_dev);
-    HIPC(c, hipGetLastError());
-    return 0;
+    return launched(c);
 }
 
 static int check_ready(bdof_ctx* c, int B) {
     if (!c) return BDOF_ERR_ARG;
-    if (c->NY == 0) return fail(c, BDOF_ERR_STATE, "bdof_configure has not been called");
+    if (int r = need_configured(c)) return r;
     if (!c->have_physics) return fail(c, BDOF_ERR_STATE, "bdof_set_physics has not been called");
     if (!c->have_probe) return fail(c, BDOF_ERR_STATE, "bdof_set_probe has not been called");
     if (!c->obj_src && !c->obj_bound_mod) return fail(c, BDOF_ERR_STATE, "bdof_set_object has not been called");
-    if (B < 1 || B > c->Bmax) return fail(c, BDOF_ERR_ARG, "batch size outside [1, Bmax]");
-    return 0;
+    return check_batch(c, B);
+}
+
+// ---- the tile family: tiles cut out of a field / written back into it, and the adjoints ---------------------------------------
+// Every entry point fills its argument struct and hands it to launch_tiles: shapes, taper (gathers) and halo (scatters) are
+// checked — the one an entry point does not take is 0 and passes — then one launch of 256-thread workgroups on the ctx stream,
+// over the tiles' rows (TILE_GRID: y blocks of 256, up to 64 workgroups along x, one z per tile) or over the field's rows
+// (FIELD_GRID: the adjoints that sum the tiles into the field).
+enum TileGrid { TILE_GRID, FIELD_GRID };
+template <class Args, class... Rest>
+static int launch_tiles(bdof_ctx* c, const void* field, const void* tiles, TileGrid shape, void (*kernel)(Args, Rest...), const Args& a,
+                        Rest... rest) {
+    if (!c || !field || !tiles || !a.x0 || !a.y0) return BDOF_ERR_ARG;
+    if (a.B < 1 || a.FX < 1 || a.FY < 1 || a.TX < 1 || a.TY < 1) return fail(c, BDOF_ERR_ARG, "bad tile / field shape");
+    int r;
+    if ((r = check_taper(c, a.TX, a.TY, a.taper)) || (r = check_halo(c, a.TX, a.TY, a.hx, a.hy))) return r;
+    HIPC(c, hipSetDevice(c->device));
+    const dim3 grid = shape == TILE_GRID ? dim3((a.TY + 255) / 256, std::min(a.TX, 64), a.B) : dim3(std::min(a.FX, c->ncu * 8));
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, c->stream, a, rest...);
+    return launched(c);
 }
 
 extern "C" {
@@ -1085,19 +1097,19 @@ static int upload_twiddle(bdof_ctx* c, int N, cf** dst, bool dither = true) {
 int bdof_configure(bdof_ctx* c, int NY, int NX, int S, int Bmax, int with_grad) {
     if (!c) return BDOF_ERR_ARG;
     if (NY < 1 || NX < 1 || S < 1 || Bmax < 1) return fail(c, BDOF_ERR_ARG, "NY, NX, S and Bmax must be >= 1");
-    const bool generic = (with_grad & (2 | 64)) != 0 || !supported_n(NY) || !supported_n(NX);
+    const bool generic = (with_grad & (BDOF_CFG_GENERIC | BDOF_CFG_ADJOINT64)) != 0 || !supported_n(NY) || !supported_n(NX);
     if (generic && (size_t)NY * NX > ((size_t)1 << 26)) return fail(c, BDOF_ERR_SIZE, "wavefield too large");
     HIPC(c, hipSetDevice(c->device));
     HIPC(c, hipStreamSynchronize(c->stream));
     free_workspace(c);
-    c->NY = NY; c->NX = NX; c->S = S; c->Bmax = Bmax; c->with_grad = (with_grad & 1) != 0;
+    c->NY = NY; c->NX = NX; c->S = S; c->Bmax = Bmax; c->with_grad = (with_grad & BDOF_CFG_GRAD) != 0;
     c->generic = generic;
     // dithered transform constants (bdof_fft.h): 64 copies of each table by default, BDOF_TW_DITHER=0 for one plain table
     { const char* e = std::getenv("BDOF_TW_DITHER"); c->tw_dither = e ? std::max(0, std::min(256, atoi(e))) : 64; if (c->tw_dither == 1) c->tw_dither = 0; }
-    c->recompute = (with_grad & 16) != 0 && !generic;      // the streaming engine's option; the others keep their tapes
-    c->adj64 = (with_grad & 64) != 0 && (with_grad & 1) != 0;
-    c->resident = (with_grad & (6 | 64)) == 0 && NX == NY && resident_supported(NX) && !std::getenv("BDOF_NO_RESIDENT");
-    c->res_always = (with_grad & 8) != 0 || std::getenv("BDOF_FORCE_RESIDENT");
+    c->recompute = (with_grad & BDOF_CFG_RECOMPUTE) != 0 && !generic;      // the streaming engine's option; the others keep their tapes
+    c->adj64 = (with_grad & BDOF_CFG_ADJOINT64) != 0 && c->with_grad;
+    c->resident = (with_grad & (BDOF_CFG_GENERIC | BDOF_CFG_NO_RESIDENT | BDOF_CFG_ADJOINT64)) == 0 && NX == NY && resident_supported(NX) && !std::getenv("BDOF_NO_RESIDENT");
+    c->res_always = (with_grad & BDOF_CFG_ALWAYS_RESIDENT) != 0 || std::getenv("BDOF_FORCE_RESIDENT");
     c->res_dirty = true;
     c->have_physics = c->have_probe = c->tape_valid = false;
     int r;
@@ -1120,12 +1132,12 @@ int bdof_configure(bdof_ctx* c, int NY, int NX, int S, int Bmax, int with_grad) 
     HIPC(c, hipMalloc((void**)&c->bufB, sizeof(cf) * fld));
     if (c->with_grad) {
         // tape-free adjoint: phi_{S-1} (real space) + the two fields the marched-back wave alternates between
-        const bool small_tape = c->recompute && !(c->resident && ((with_grad & 8) != 0 || std::getenv("BDOF_FORCE_RESIDENT")));
+        const bool small_tape = c->recompute && !(c->resident && c->res_always);
         c->recompute = small_tape;
         HIPC(c, hipMalloc((void**)&c->tape, sizeof(cf) * fld * (size_t)(small_tape ? std::min(S, 3) : S)));
-        // flag 32: the caller sweeps slice ranges into gradient buffers of its own (bdof_adjoint_range, the tiled path), where
-        // [Bmax][S] rows would not fit — 260 GB for 121 tiles of 512^2 x 1024 slices
-        if ((with_grad & 32) == 0) HIPC(c, hipMalloc((void**)&c->grot, sizeof(float2) * fld * (size_t)S));
+        // BDOF_CFG_NO_GROT: the caller sweeps slice ranges into gradient buffers of its own (bdof_adjoint_range, the tiled path),
+        // where [Bmax][S] rows would not fit — 260 GB for 121 tiles of 512^2 x 1024 slices
+        if ((with_grad & BDOF_CFG_NO_GROT) == 0) HIPC(c, hipMalloc((void**)&c->grot, sizeof(float2) * fld * (size_t)S));
         HIPC(c, hipMalloc((void**)&c->gcar, sizeof(double2) * (size_t)Bmax));
         HIPC(c, hipMalloc((void**)&c->gt0, sizeof(double2) * (size_t)Bmax));
     }
@@ -1145,7 +1157,7 @@ int bdof_configure(bdof_ctx* c, int NY, int NX, int S, int Bmax, int with_grad) 
 int bdof_set_physics(bdof_ctx* c, double k, const float* hs, const float* hs_det, const double* h00, const double* hdet00,
                      int det_mode, int variant) {
     if (!c || !hs || !h00) return BDOF_ERR_ARG;
-    if (c->NY == 0) return fail(c, BDOF_ERR_STATE, "bdof_configure has not been called");
+    if (int r = need_configured(c)) return r;
     if (det_mode < 0 || det_mode > 2 || variant < 0 || variant > 1) return fail(c, BDOF_ERR_ARG, "bad det_mode / variant");
     if (det_mode == BDOF_DET_NEAR && !hs_det) return fail(c, BDOF_ERR_ARG, "hs_det required for BDOF_DET_NEAR");
     const size_t bytes = sizeof(cf) * c->NX * c->NY;
@@ -1257,7 +1269,7 @@ int bdof_set_physics_f64(bdof_ctx* c, const double* hs, const double* hs_det) {
 
 int bdof_set_probe(bdof_ctx* c, const float* probe, double a0_re, double a0_im) {
     if (!c || !probe) return BDOF_ERR_ARG;
-    if (c->NY == 0) return fail(c, BDOF_ERR_STATE, "bdof_configure has not been called");
+    if (int r = need_configured(c)) return r;
     HIPC(c, hipMemcpyAsync(c->probe, probe, sizeof(cf) * c->NX * c->NY, hipMemcpyHostToDevice, c->stream));
     c->c64_tf = false; c->c64_ks = 0;     // a float64 twin handed over before (bdof_set_tf_f64 / bdof_set_conv_f64) held the previous model
     HIPC(c, hipStreamSynchronize(c->stream));
@@ -1282,7 +1294,7 @@ int bdof_probe_stack_supported(bdof_ctx* c) {
 
 int bdof_set_probe_stack(bdof_ctx* c, const float* stack, const float* det) {
     if (!c) return BDOF_ERR_ARG;
-    if (c->NY == 0) return fail(c, BDOF_ERR_STATE, "bdof_configure has not been called");
+    if (int r = need_configured(c)) return r;
     HIPC(c, hipSetDevice(c->device));
     HIPC(c, hipStreamSynchronize(c->stream));
     if (c->pstack) { (void)hipFree(c->pstack); c->pstack = nullptr; }
@@ -1364,11 +1376,8 @@ int bdof_set_probe_field(bdof_ctx* c, const double* probe, const double* hT, con
     PF_HIP(hipMalloc((void**)&c->pstack, fld * (size_t)c->S));
     PF_HIP(hipMalloc((void**)&c->pdet, fld));
     PF_HIP(hipMalloc((void**)&c->pdetT, fld));
-    static const bool no_f64_det = std::getenv("BDOF_NO_F64_DET") != nullptr;      // A/B switch: residual from float32 planes as before
-    if (!no_f64_det) {
-        PF_HIP(hipMalloc((void**)&c->pdet64, dbytes));
-        PF_HIP(hipMalloc((void**)&c->pdetT64, dbytes));
-    }
+    PF_HIP(hipMalloc((void**)&c->pdet64, dbytes));
+    PF_HIP(hipMalloc((void**)&c->pdetT64, dbytes));
     const int grid = g_elem_grid(c, n);
     void* buf[1] = {dp};
     auto step = [&](const double2* h) -> int {
@@ -1390,10 +1399,8 @@ int bdof_set_probe_field(bdof_ctx* c, const double* probe, const double* hT, con
     hipLaunchKernelGGL(k_d_to_f, dim3(grid), dim3(256), 0, c->stream, dp, c->pdet, c->NX, c->NY, 0);
     hipLaunchKernelGGL(k_d_to_f, dim3(grid), dim3(256), 0, c->stream, dp, c->pdetT, c->NX, c->NY, 1);
     // ... and unrounded: the detector kernels add the scattered wave to these and take |d| - m in float64 (loss_seed_f64)
-    if (c->pdet64) {
-        hipLaunchKernelGGL(k_d_copy, dim3(grid), dim3(256), 0, c->stream, dp, c->pdet64, c->NX, c->NY, 0);
-        hipLaunchKernelGGL(k_d_copy, dim3(grid), dim3(256), 0, c->stream, dp, c->pdetT64, c->NX, c->NY, 1);
-    }
+    hipLaunchKernelGGL(k_d_copy, dim3(grid), dim3(256), 0, c->stream, dp, c->pdet64, c->NX, c->NY, 0);
+    hipLaunchKernelGGL(k_d_copy, dim3(grid), dim3(256), 0, c->stream, dp, c->pdetT64, c->NX, c->NY, 1);
     PF_HIP(hipGetLastError());
     PF_HIP(hipStreamSynchronize(c->stream));
 #undef PF_TRY
@@ -1411,7 +1418,7 @@ int bdof_set_probe_field(bdof_ctx* c, const double* probe, const double* hT, con
 
 int bdof_set_object(bdof_ctx* c, const void* vol, long long n_rows, int volNY, const int* tab, int volNX, int n_angles) {
     if (!c || !vol || n_rows < 1) return BDOF_ERR_ARG;
-    if (c->NY == 0) return fail(c, BDOF_ERR_STATE, "bdof_configure has not been called");
+    if (int r = need_configured(c)) return r;
     if (volNY < 1) return fail(c, BDOF_ERR_ARG, "volNY must be >= 1");
     if (tab && (volNX < 1 || n_angles < 1)) return fail(c, BDOF_ERR_ARG, "volNX and n_angles must be >= 1 with a table");
     if (!tab && volNY != c->NY) return fail(c, BDOF_ERR_ARG, "without a rotation table volNY must equal NY");
@@ -1443,11 +1450,19 @@ static void set_batch_views(bdof_ctx* c, const int* angle_of_b, const int* xoff,
     c->obj.xoff = xoff;
     c->obj.yoff = yoff;
 }
+// the batch's view of the caller's (delta, beta) rows: the float64 paths modulate from the rows, not from the table c->mod
+static ObjView rows_view(const bdof_ctx* c, const int* angle_of_b, const int* xoff, const int* yoff) {
+    ObjView o = c->obj;
+    o.vol = c->obj_src;
+    o.angle_of_b = angle_of_b;
+    o.xoff = xoff;
+    o.yoff = yoff;
+    return o;
+}
 
 int bdof_forward(bdof_ctx* c, int B, const int* angle_of_b, const int* xoff, const int* yoff, void* out_wave, int keep_tape) {
-    int r = check_ready(c, B);
-    if (r) return r;
-    if (c->obj.tab && !angle_of_b) return fail(c, BDOF_ERR_ARG, "angle_of_b required with a rotation table");
+    int r;
+    if ((r = check_ready(c, B)) || (r = need_angles(c, angle_of_b))) return r;
     if (keep_tape && !c->with_grad) return fail(c, BDOF_ERR_STATE, "keep_tape needs bdof_configure(with_grad=1)");
     if (keep_tape && c->recompute) return fail(c, BDOF_ERR_STATE, "the per-slice history is not kept in tape-free (recompute) mode");
     HIPC(c, hipSetDevice(c->device));
@@ -1462,8 +1477,7 @@ int bdof_forward(bdof_ctx* c, int B, const int* angle_of_b, const int* xoff, con
         if (keep_tape) return fail(c, BDOF_ERR_STATE, "the per-slice history is not kept by the generic-size engine");
         if ((r = generic_forward(c, B, out_wave, false))) return r;
         c->tape_valid = c->last_valid = false;
-        HIPC(c, hipGetLastError());
-        return 0;
+        return launched(c);
     }
     const bool tf_all = c->variant == BDOF_VARIANT_TF_ALL;
     Group groups[BDOF_MAX_GROUPS];
@@ -1490,8 +1504,7 @@ int bdof_forward(bdof_ctx* c, int B, const int* angle_of_b, const int* xoff, con
         }
         c->last_valid = true;
     }
-    HIPC(c, hipGetLastError());
-    return 0;
+    return launched(c);
 }
 
 int bdof_forward_range(bdof_ctx* c, int B, const int* angle_of_b, const int* xoff, const int* yoff, int z0, int nz,
@@ -1499,9 +1512,9 @@ int bdof_forward_range(bdof_ctx* c, int B, const int* angle_of_b, const int* xof
     int r = check_ready(c, B);
     if (r) return r;
     if (!in_real || !out_real) return BDOF_ERR_ARG;
-    if (z0 < 0 || nz < 1 || z0 + nz > c->S) return fail(c, BDOF_ERR_ARG, "slice range outside [0, S)");
+    if ((r = check_range(c, z0, nz))) return r;
     if (c->generic) return fail(c, BDOF_ERR_SIZE, "bdof_forward_range runs on the fused streaming kernels (NY, NX powers of two in 64..1024)");
-    if (c->obj.tab && !angle_of_b) return fail(c, BDOF_ERR_ARG, "angle_of_b required with a rotation table");
+    if ((r = need_angles(c, angle_of_b))) return r;
     if (c->range_car && (B != c->range_car_B || z0 != c->range_car_z0))
         return fail(c, BDOF_ERR_ARG, "the range carriers (bdof_set_range_carrier) were handed over for another batch / first slice");
     HIPC(c, hipSetDevice(c->device));
@@ -1537,8 +1550,7 @@ int bdof_forward_range(bdof_ctx* c, int B, const int* angle_of_b, const int* xof
     }
     if ((r = join_streams(c, ng))) return r;
     c->tape_valid = c->last_valid = false;
-    HIPC(c, hipGetLastError());
-    return 0;
+    return launched(c);
 }
 
 // Carrier fields for the NEXT bdof_forward_range calls over slices z0 .. z0 + nz - 1 of B wavefields: stack [nz][B][NX][NY] complex64
@@ -1549,7 +1561,7 @@ int bdof_forward_range(bdof_ctx* c, int B, const int* angle_of_b, const int* xof
 int bdof_set_range_carrier(bdof_ctx* c, const void* stack, int B, int z0, int nz) {
     if (!c) return BDOF_ERR_ARG;
     if (!stack) { c->range_car = nullptr; c->range_car_B = 0; return 0; }
-    if (c->NY == 0) return fail(c, BDOF_ERR_STATE, "bdof_configure has not been called");
+    if (int r = need_configured(c)) return r;
     if (c->pstack || c->a0 != std::complex<double>(0.0, 0.0))
         return fail(c, BDOF_ERR_STATE, "range carriers replace the ctx's own probe carrier: bind a zero probe (bdof_set_probe, a0 = 0) and no probe stack");
     if (B < 1 || B > c->Bmax || z0 < 0 || nz < 1 || z0 + nz > c->S) return fail(c, BDOF_ERR_ARG, "batch / slice range outside the configuration");
@@ -1576,11 +1588,11 @@ int bdof_adjoint_range(bdof_ctx* c, int B, const int* angle_of_b, const int* xof
     int r = check_ready(c, B);
     if (r) return r;
     if (!end_real || !g_end_real || !g_start_real || !grot_range) return BDOF_ERR_ARG;
-    if (z0 < 0 || nz < 1 || z0 + nz > c->S) return fail(c, BDOF_ERR_ARG, "slice range outside [0, S)");
+    if ((r = check_range(c, z0, nz))) return r;
     if (c->generic) return fail(c, BDOF_ERR_SIZE, "bdof_adjoint_range runs on the fused streaming kernels");
     if (!c->with_grad || !c->tape) return fail(c, BDOF_ERR_STATE, "bdof_adjoint_range needs bdof_configure(with_grad=1)");
     if (c->S < 2) return fail(c, BDOF_ERR_SIZE, "bdof_adjoint_range needs at least two tape fields (S >= 2)");
-    if (c->obj.tab && !angle_of_b) return fail(c, BDOF_ERR_ARG, "angle_of_b required with a rotation table");
+    if ((r = need_angles(c, angle_of_b))) return r;
     HIPC(c, hipSetDevice(c->device));
     set_batch_views(c, angle_of_b, xoff, yoff);
     if ((r = ensure_modulation_k(c, c->k_fft))) return r;
@@ -1620,8 +1632,7 @@ int bdof_adjoint_range(bdof_ctx* c, int B, const int* angle_of_b, const int* xof
     if ((r = join_streams(c, ng))) return r;
     c->tape_valid = c->last_valid = false;
     c->gpsi_src = nullptr;
-    HIPC(c, hipGetLastError());
-    return 0;
+    return launched(c);
 }
 
 // loss = mean((|field| - meas)^2) over n = FX * FY pixels (left on the device, bdof_get_loss) and, in place of the field,
@@ -1636,76 +1647,40 @@ int bdof_field_loss_seed(bdof_ctx* c, void* field, const float* meas, int FX, in
                  nullptr, nullptr, make_double2(0.0, 0.0), make_double2(0.0, 0.0), nullptr, nullptr, 0.0, make_double2(0.0, 0.0)};
     hipLaunchKernelGGL(k_g_loss, dim3(egrid), dim3(256), 0, c->stream, la);
     hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, c->stream, c->partial, egrid, 1.0 / (double)n, c->loss_dev);
-    HIPC(c, hipGetLastError());
-    return 0;
-}
-
-static int tiles_check(bdof_ctx* c, const void* field, const void* tiles, int B, int FX, int FY, int TX, int TY, const int* x0, const int* y0) {
-    if (!c || !field || !tiles || !x0 || !y0) return BDOF_ERR_ARG;
-    if (B < 1 || FX < 1 || FY < 1 || TX < 1 || TY < 1) return fail(c, BDOF_ERR_ARG, "bad tile / field shape");
-    return 0;
+    return launched(c);
 }
 
 int bdof_tiles_gather(bdof_ctx* c, const void* field, int FX, int FY, void* tiles, int B, int TX, int TY, const int* x0, const int* y0,
                       int taper) {
-    int r = tiles_check(c, field, tiles, B, FX, FY, TX, TY, x0, y0);
-    if (r) return r;
-    HIPC(c, hipSetDevice(c->device));
-    if (taper < 0 || 2 * taper > TX || 2 * taper > TY) return fail(c, BDOF_ERR_ARG, "taper must fit the tile");
-    TileArgs a{(cf*)field, (cf*)tiles, x0, y0, B, FX, FY, TX, TY, 0, 0, taper};
-    hipLaunchKernelGGL(k_tiles_gather, dim3((TY + 255) / 256, std::min(TX, 64), B), dim3(256), 0, c->stream, a, 0);
-    HIPC(c, hipGetLastError());
-    return 0;
+    return launch_tiles(c, field, tiles, TILE_GRID, k_tiles_gather, TileArgs{(cf*)field, (cf*)tiles, x0, y0, B, FX, FY, TX, TY, 0, 0, taper}, 0);
 }
 
 int bdof_tiles_scatter(bdof_ctx* c, const void* tiles, void* field, int FX, int FY, int B, int TX, int TY, const int* x0, const int* y0,
                        int halo_x, int halo_y) {
-    int r = tiles_check(c, field, tiles, B, FX, FY, TX, TY, x0, y0);
-    if (r) return r;
-    if (halo_x < 0 || halo_y < 0 || 2 * halo_x >= TX || 2 * halo_y >= TY) return fail(c, BDOF_ERR_ARG, "halo must leave a core");
-    HIPC(c, hipSetDevice(c->device));
-    TileArgs a{(cf*)field, (cf*)tiles, x0, y0, B, FX, FY, TX, TY, halo_x, halo_y, 0};
-    hipLaunchKernelGGL(k_tiles_scatter, dim3((TY + 255) / 256, std::min(TX, 64), B), dim3(256), 0, c->stream, a);
-    HIPC(c, hipGetLastError());
-    return 0;
+    return launch_tiles(c, field, tiles, TILE_GRID, k_tiles_scatter, TileArgs{(cf*)field, (cf*)tiles, x0, y0, B, FX, FY, TX, TY, halo_x, halo_y, 0});
 }
 
 // adjoint of bdof_tiles_scatter: tiles = the field on every tile's core, zero elsewhere
 int bdof_tiles_scatter_adjoint(bdof_ctx* c, const void* field, int FX, int FY, void* tiles, int B, int TX, int TY, const int* x0, const int* y0,
                                int halo_x, int halo_y) {
-    int r = tiles_check(c, field, tiles, B, FX, FY, TX, TY, x0, y0);
-    if (r) return r;
-    if (halo_x < 0 || halo_y < 0 || 2 * halo_x >= TX || 2 * halo_y >= TY) return fail(c, BDOF_ERR_ARG, "halo must leave a core");
-    HIPC(c, hipSetDevice(c->device));
-    TileArgs a{(cf*)field, (cf*)tiles, x0, y0, B, FX, FY, TX, TY, halo_x, halo_y, 0};
-    hipLaunchKernelGGL(k_tiles_gather, dim3((TY + 255) / 256, std::min(TX, 64), B), dim3(256), 0, c->stream, a, 1);
-    HIPC(c, hipGetLastError());
-    return 0;
+    return launch_tiles(c, field, tiles, TILE_GRID, k_tiles_gather, TileArgs{(cf*)field, (cf*)tiles, x0, y0, B, FX, FY, TX, TY, halo_x, halo_y, 0}, 1);
 }
 
 // adjoint of bdof_tiles_gather: field = sum of the tiles' pixels, weighted with the taper, at the positions they were cut from
 int bdof_tiles_gather_adjoint(bdof_ctx* c, const void* tiles, void* field, int FX, int FY, int B, int TX, int TY, const int* x0, const int* y0,
                               int taper) {
-    int r = tiles_check(c, field, tiles, B, FX, FY, TX, TY, x0, y0);
-    if (r) return r;
-    if (taper < 0 || 2 * taper > TX || 2 * taper > TY) return fail(c, BDOF_ERR_ARG, "taper must fit the tile");
-    HIPC(c, hipSetDevice(c->device));
-    TileArgs a{(cf*)field, (cf*)tiles, x0, y0, B, FX, FY, TX, TY, 0, 0, taper};
-    hipLaunchKernelGGL(k_tiles_gather_adjoint, dim3(std::min(FX, c->ncu * 8)), dim3(256), 0, c->stream, a);
-    HIPC(c, hipGetLastError());
-    return 0;
+    return launch_tiles(c, field, tiles, FIELD_GRID, k_tiles_gather_adjoint, TileArgs{(cf*)field, (cf*)tiles, x0, y0, B, FX, FY, TX, TY, 0, 0, taper});
 }
 
 // object gradient of a slice range of tiles, added into the volume gradient rows (see k_tiles_grad_add)
 int bdof_tiles_grad_add(bdof_ctx* c, const void* grot_range, void* gvol, int B, int TX, int TY, const int* x0, const int* y0, int z0, int nz) {
     if (!c || !grot_range || !gvol || !x0 || !y0 || B < 1) return BDOF_ERR_ARG;
     if (!c->obj.tab) return fail(c, BDOF_ERR_STATE, "bdof_set_object with a table has not been called");
-    if (z0 < 0 || nz < 1 || z0 + nz > c->S) return fail(c, BDOF_ERR_ARG, "slice range outside [0, S)");
+    if (int r = check_range(c, z0, nz)) return r;
     HIPC(c, hipSetDevice(c->device));
     TileGradArgs a{(const float2*)grot_range, (float2*)gvol, c->obj.tab, x0, y0, B, TX, TY, c->obj.volNX, c->obj.volNY, z0, nz, 1};
     hipLaunchKernelGGL(k_tiles_grad_add, dim3(std::min(c->obj.volNX, c->ncu * 8)), dim3(256), 0, c->stream, a);
-    HIPC(c, hipGetLastError());
-    return 0;
+    return launched(c);
 }
 
 // ---- whole-field / tile-batch operations in either precision (bdof_field.h) ------------------------------------------------
@@ -1757,8 +1732,7 @@ int bdof_fields_free_step(bdof_ctx* c, void* fields, int B, int NX, int NY, cons
     if (is_double) hipLaunchKernelGGL(k_f_hmul<double2>, dim3(g_elem_grid(c, n)), dim3(256), 0, c->stream, (double2*)fields, (const double2*)h, per, n, conj_h);
     else hipLaunchKernelGGL(k_f_hmul<float2>, dim3(g_elem_grid(c, n)), dim3(256), 0, c->stream, (float2*)fields, (const float2*)h, per, n, conj_h);
     RFC(c, rocfft_execute(pi, buf, nullptr, c->ginfo));
-    HIPC(c, hipGetLastError());
-    return 0;
+    return launched(c);
 }
 
 // The same step on an AUXILIARY stream: it starts after everything queued on the ctx's stream so far (first copying `src` into
@@ -1801,8 +1775,7 @@ int bdof_fields_free_step_aux(bdof_ctx* c, void* fields, const void* src, int B,
     if (is_double) hipLaunchKernelGGL(k_f_hmul<double2>, dim3(g_elem_grid(c, n)), dim3(256), 0, c->aux, (double2*)fields, (const double2*)h, per, n, conj_h);
     else hipLaunchKernelGGL(k_f_hmul<float2>, dim3(g_elem_grid(c, n)), dim3(256), 0, c->aux, (float2*)fields, (const float2*)h, per, n, conj_h);
     RFC(c, rocfft_execute(pi, buf, nullptr, c->ginfo_aux));
-    HIPC(c, hipGetLastError());
-    return 0;
+    return launched(c);
 }
 
 // The carrier stack of a stitch range (bdof_set_range_carrier) in one call: p0 [B][NX][NY] complex128 (device; overwritten) are
@@ -1837,8 +1810,7 @@ int bdof_range_carrier_build(bdof_ctx* c, void* p0, void* stack, int B, int NX, 
         RFC(c, rocfft_execute(qi, b1, nullptr, c->ginfo));
         hipLaunchKernelGGL(k_f_to_float, dim3(g_elem_grid(c, need)), dim3(256), 0, c->stream, (const double2*)c->car_scratch, (cf*)stack + n, need);
     }
-    HIPC(c, hipGetLastError());
-    return 0;
+    return launched(c);
 }
 
 int bdof_aux_join(bdof_ctx* c) {
@@ -1857,8 +1829,7 @@ int bdof_caxpy(bdof_ctx* c, void* y, const void* x, double alpha, size_t n, int 
     HIPC(c, hipSetDevice(c->device));
     if (is_double) hipLaunchKernelGGL(k_f_axpy<double>, dim3(g_elem_grid(c, 2 * n)), dim3(256), 0, c->stream, (double*)y, (const double*)x, alpha, 2 * n);
     else hipLaunchKernelGGL(k_f_axpy<float>, dim3(g_elem_grid(c, 2 * n)), dim3(256), 0, c->stream, (float*)y, (const float*)x, (float)alpha, 2 * n);
-    HIPC(c, hipGetLastError());
-    return 0;
+    return launched(c);
 }
 
 // complex64 <-> complex128 copies of n numbers
@@ -1867,85 +1838,47 @@ int bdof_c_convert(bdof_ctx* c, void* dst, const void* src, size_t n, int to_dou
     HIPC(c, hipSetDevice(c->device));
     if (to_double) hipLaunchKernelGGL(k_f_to_double, dim3(g_elem_grid(c, n)), dim3(256), 0, c->stream, (const cf*)src, (double2*)dst, n);
     else hipLaunchKernelGGL(k_f_to_float, dim3(g_elem_grid(c, n)), dim3(256), 0, c->stream, (const double2*)src, (cf*)dst, n);
-    HIPC(c, hipGetLastError());
-    return 0;
+    return launched(c);
 }
 
 int bdof_tiles_gather_f64(bdof_ctx* c, const void* field, int FX, int FY, void* tiles, int B, int TX, int TY, const int* x0, const int* y0,
                           int taper) {
-    int r = tiles_check(c, field, tiles, B, FX, FY, TX, TY, x0, y0);
-    if (r) return r;
-    if (taper < 0 || 2 * taper > TX || 2 * taper > TY) return fail(c, BDOF_ERR_ARG, "taper must fit the tile");
-    HIPC(c, hipSetDevice(c->device));
-    Tile64Args a{(double2*)field, (double2*)tiles, x0, y0, B, FX, FY, TX, TY, 0, 0, taper};
-    hipLaunchKernelGGL(k_tiles_gather64, dim3((TY + 255) / 256, std::min(TX, 64), B), dim3(256), 0, c->stream, a);
-    HIPC(c, hipGetLastError());
-    return 0;
+    return launch_tiles(c, field, tiles, TILE_GRID, k_tiles_gather64, Tile64Args{(double2*)field, (double2*)tiles, x0, y0, B, FX, FY, TX, TY, 0, 0, taper});
 }
 
 int bdof_tiles_scatter_f64(bdof_ctx* c, const void* tiles, void* field, int FX, int FY, int B, int TX, int TY, const int* x0, const int* y0,
                            int halo_x, int halo_y) {
-    int r = tiles_check(c, field, tiles, B, FX, FY, TX, TY, x0, y0);
-    if (r) return r;
-    if (halo_x < 0 || halo_y < 0 || 2 * halo_x >= TX || 2 * halo_y >= TY) return fail(c, BDOF_ERR_ARG, "halo must leave a core");
-    HIPC(c, hipSetDevice(c->device));
-    Tile64Args a{(double2*)field, (double2*)tiles, x0, y0, B, FX, FY, TX, TY, halo_x, halo_y, 0};
-    hipLaunchKernelGGL(k_tiles_scatter64, dim3((TY + 255) / 256, std::min(TX, 64), B), dim3(256), 0, c->stream, a);
-    HIPC(c, hipGetLastError());
-    return 0;
+    return launch_tiles(c, field, tiles, TILE_GRID, k_tiles_scatter64,
+                        Tile64Args{(double2*)field, (double2*)tiles, x0, y0, B, FX, FY, TX, TY, halo_x, halo_y, 0});
 }
 
 // complex64 tiles cut out of a complex128 field (tapered, periodic) / written back into it:
 // field[core] = (accumulate ? field[core] : 0) + tiles_a - tiles_b (tiles_b nullable), the sum formed in float64
 int bdof_tiles_gather_mixed(bdof_ctx* c, const void* field64, int FX, int FY, void* tiles, int B, int TX, int TY, const int* x0, const int* y0,
                             int taper) {
-    int r = tiles_check(c, field64, tiles, B, FX, FY, TX, TY, x0, y0);
-    if (r) return r;
-    if (taper < 0 || 2 * taper > TX || 2 * taper > TY) return fail(c, BDOF_ERR_ARG, "taper must fit the tile");
-    HIPC(c, hipSetDevice(c->device));
-    TileMixArgs a{(double2*)field64, nullptr, nullptr, (cf*)tiles, x0, y0, B, FX, FY, TX, TY, 0, 0, taper, 0};
-    hipLaunchKernelGGL(k_tiles_gather_mixed, dim3((TY + 255) / 256, std::min(TX, 64), B), dim3(256), 0, c->stream, a, 0);
-    HIPC(c, hipGetLastError());
-    return 0;
+    return launch_tiles(c, field64, tiles, TILE_GRID, k_tiles_gather_mixed,
+                        TileMixArgs{(double2*)field64, nullptr, nullptr, (cf*)tiles, x0, y0, B, FX, FY, TX, TY, 0, 0, taper, 0}, 0);
 }
 
 // adjoint of bdof_tiles_scatter_diff64 w.r.t. tiles_a: complex64 tiles = the complex128 field on every tile's core, zero elsewhere
 int bdof_tiles_scatter_adjoint_mixed(bdof_ctx* c, const void* field64, int FX, int FY, void* tiles, int B, int TX, int TY, const int* x0,
                                      const int* y0, int halo_x, int halo_y) {
-    int r = tiles_check(c, field64, tiles, B, FX, FY, TX, TY, x0, y0);
-    if (r) return r;
-    if (halo_x < 0 || halo_y < 0 || 2 * halo_x >= TX || 2 * halo_y >= TY) return fail(c, BDOF_ERR_ARG, "halo must leave a core");
-    HIPC(c, hipSetDevice(c->device));
-    TileMixArgs a{(double2*)field64, nullptr, nullptr, (cf*)tiles, x0, y0, B, FX, FY, TX, TY, halo_x, halo_y, 0, 0};
-    hipLaunchKernelGGL(k_tiles_gather_mixed, dim3((TY + 255) / 256, std::min(TX, 64), B), dim3(256), 0, c->stream, a, 1);
-    HIPC(c, hipGetLastError());
-    return 0;
+    return launch_tiles(c, field64, tiles, TILE_GRID, k_tiles_gather_mixed,
+                        TileMixArgs{(double2*)field64, nullptr, nullptr, (cf*)tiles, x0, y0, B, FX, FY, TX, TY, halo_x, halo_y, 0, 0}, 1);
 }
 
 // adjoint of bdof_tiles_gather_mixed, on a difference of tiles: field64 (+)= sum of the tapered (tiles_a - tiles_b) pixels at the
 // positions they were cut from (periodically); tiles_b nullable
 int bdof_tiles_gather_adjoint_diff64(bdof_ctx* c, const void* tiles_a, const void* tiles_b, void* field64, int FX, int FY, int B, int TX, int TY,
                                      const int* x0, const int* y0, int taper, int accumulate) {
-    int r = tiles_check(c, field64, tiles_a, B, FX, FY, TX, TY, x0, y0);
-    if (r) return r;
-    if (taper < 0 || 2 * taper > TX || 2 * taper > TY) return fail(c, BDOF_ERR_ARG, "taper must fit the tile");
-    HIPC(c, hipSetDevice(c->device));
-    TileMixArgs a{(double2*)field64, (const cf*)tiles_a, (const cf*)tiles_b, nullptr, x0, y0, B, FX, FY, TX, TY, 0, 0, taper, accumulate};
-    hipLaunchKernelGGL(k_tiles_gather_adjoint_diff64, dim3(std::min(FX, c->ncu * 8)), dim3(256), 0, c->stream, a);
-    HIPC(c, hipGetLastError());
-    return 0;
+    return launch_tiles(c, field64, tiles_a, FIELD_GRID, k_tiles_gather_adjoint_diff64,
+                        TileMixArgs{(double2*)field64, (const cf*)tiles_a, (const cf*)tiles_b, nullptr, x0, y0, B, FX, FY, TX, TY, 0, 0, taper, accumulate});
 }
 
 int bdof_tiles_scatter_diff64(bdof_ctx* c, const void* tiles_a, const void* tiles_b, void* field64, int FX, int FY, int B, int TX, int TY,
                               const int* x0, const int* y0, int halo_x, int halo_y, int accumulate) {
-    int r = tiles_check(c, field64, tiles_a, B, FX, FY, TX, TY, x0, y0);
-    if (r) return r;
-    if (halo_x < 0 || halo_y < 0 || 2 * halo_x >= TX || 2 * halo_y >= TY) return fail(c, BDOF_ERR_ARG, "halo must leave a core");
-    HIPC(c, hipSetDevice(c->device));
-    TileMixArgs a{(double2*)field64, (const cf*)tiles_a, (const cf*)tiles_b, nullptr, x0, y0, B, FX, FY, TX, TY, halo_x, halo_y, 0, accumulate};
-    hipLaunchKernelGGL(k_tiles_scatter_diff64, dim3((TY + 255) / 256, std::min(TX, 64), B), dim3(256), 0, c->stream, a);
-    HIPC(c, hipGetLastError());
-    return 0;
+    return launch_tiles(c, field64, tiles_a, TILE_GRID, k_tiles_scatter_diff64,
+                        TileMixArgs{(double2*)field64, (const cf*)tiles_a, (const cf*)tiles_b, nullptr, x0, y0, B, FX, FY, TX, TY, halo_x, halo_y, 0, accumulate});
 }
 
 // bdof_forward_range in float64 on caller-owned complex128 fields [B][NX][NY], in place: slices z0 .. z0+nz-1 of the bound object
@@ -1954,20 +1887,15 @@ int bdof_tiles_scatter_diff64(bdof_ctx* c, const void* tiles_a, const void* tile
 int bdof_forward_range_f64(bdof_ctx* c, int B, const int* angle_of_b, const int* xoff, const int* yoff, int z0, int nz, void* fields,
                            const void* h, double k, int prop_last) {
     if (!c || !fields || !h) return BDOF_ERR_ARG;
-    if (c->NY == 0) return fail(c, BDOF_ERR_STATE, "bdof_configure has not been called");
+    if (int r = need_configured(c)) return r;
     if (!c->obj_src) return fail(c, BDOF_ERR_STATE, "bdof_set_object (with (delta, beta) rows) has not been called");
     if (B < 1) return fail(c, BDOF_ERR_ARG, "batch size must be positive");
-    if (z0 < 0 || nz < 1 || z0 + nz > c->S) return fail(c, BDOF_ERR_ARG, "slice range outside [0, S)");
-    if (c->obj.tab && !angle_of_b) return fail(c, BDOF_ERR_ARG, "angle_of_b required with a rotation table");
+    int r;
+    if ((r = check_range(c, z0, nz)) || (r = need_angles(c, angle_of_b))) return r;
     HIPC(c, hipSetDevice(c->device));
     rocfft_plan pf, pi;
-    int r = field_plans(c, c->NX, c->NY, B, true, &pf, &pi);
-    if (r) return r;
-    ObjView o = c->obj;
-    o.vol = c->obj_src;
-    o.angle_of_b = angle_of_b;
-    o.xoff = xoff;
-    o.yoff = yoff;
+    if ((r = field_plans(c, c->NX, c->NY, B, true, &pf, &pi))) return r;
+    const ObjView o = rows_view(c, angle_of_b, xoff, yoff);
     const size_t per = (size_t)c->NX * c->NY, n = per * B;
     void* buf[1] = {fields};
     for (int z = z0; z < z0 + nz; ++z) {
@@ -1979,8 +1907,7 @@ int bdof_forward_range_f64(bdof_ctx* c, int B, const int* angle_of_b, const int*
             RFC(c, rocfft_execute(pi, buf, nullptr, c->ginfo));
         }
     }
-    HIPC(c, hipGetLastError());
-    return 0;
+    return launched(c);
 }
 
 // ---- the real-space propagator in float64 (bdof_conv64.h) -------------------------------------------------------------------
@@ -2009,7 +1936,7 @@ static int c64_room(bdof_ctx* c, int B, bool tf, size_t M) {
 // recursion, propagation.py:91,99); k = 2 pi dz / lambda with numpy's pi (propagation.py:25)
 int bdof_set_conv_f64(bdof_ctx* c, const double* probe, const double* khat, int ks, double ksum_re, double ksum_im, double k) {
     if (!c || !probe || !khat) return BDOF_ERR_ARG;
-    if (c->NY == 0) return fail(c, BDOF_ERR_STATE, "bdof_configure has not been called");
+    if (int r = need_configured(c)) return r;
     if (c->NX != c->NY) return fail(c, BDOF_ERR_SIZE, "the float64 real-space path takes square wavefields");
     if (ks < 1 || ks % 2 == 0 || ks >= c->NX) return fail(c, BDOF_ERR_ARG, "kernel_size must be odd and smaller than the field");
     HIPC(c, hipSetDevice(c->device));
@@ -2036,7 +1963,7 @@ int bdof_set_conv_f64(bdof_ctx* c, const double* probe, const double* khat, int 
 // step of the renormalised exit wave): hdetT host complex128 [kx][ky], ifftshift(H_det) / (NX NY); NULL removes it
 int bdof_set_conv_f64_detector(bdof_ctx* c, const double* hdetT) {
     if (!c) return BDOF_ERR_ARG;
-    if (c->NY == 0) return fail(c, BDOF_ERR_STATE, "bdof_configure has not been called");
+    if (int r = need_configured(c)) return r;
     HIPC(c, hipSetDevice(c->device));
     HIPC(c, hipStreamSynchronize(c->stream));
     const size_t n = (size_t)c->NX * c->NY;
@@ -2056,22 +1983,17 @@ int bdof_loss_grad_conv_f64(bdof_ctx* c, int B, const int* angle_of_b, const int
     if (!c->c64_ks || c->c64_tf) return fail(c, BDOF_ERR_STATE, "bdof_set_conv_f64 has not been called");
     if (!c->obj_src) return fail(c, BDOF_ERR_STATE, "bdof_set_object (with (delta, beta) rows) has not been called");
     if (!c->grot || !c->partial) return fail(c, BDOF_ERR_STATE, "bdof_configure(with_grad = 1) needed");
-    if (B < 1 || B > c->Bmax) return fail(c, BDOF_ERR_ARG, "batch size outside [1, Bmax]");
+    int r;
+    if ((r = check_batch(c, B)) || (r = need_angles(c, angle_of_b))) return r;
     if (c->det_mode == BDOF_DET_NEAR && !c->c64_hdet)
         return fail(c, BDOF_ERR_STATE, "near-field detector: bdof_set_conv_f64_detector has not been called");
-    if (c->obj.tab && !angle_of_b) return fail(c, BDOF_ERR_ARG, "angle_of_b required with a rotation table");
     HIPC(c, hipSetDevice(c->device));
     const int N = c->NX, ks = c->c64_ks, p = (ks - 1) / 2, M = N + ks - 1, S = c->S;
     const size_t per = (size_t)N * N, n = per * B, nbig = (size_t)M * M * B;
-    int r;
     if ((r = c64_room(c, B, false, (size_t)M))) return r;
     rocfft_plan pf, pi;
     if ((r = field_plans(c, N, N, B, true, &pf, &pi))) return r;           // detector transforms
-    ObjView o = c->obj;
-    o.vol = c->obj_src;
-    o.angle_of_b = angle_of_b;
-    o.xoff = xoff;
-    o.yoff = yoff;
+    const ObjView o = rows_view(c, angle_of_b, xoff, yoff);
     const int eg = g_elem_grid(c, n), egb = g_elem_grid(c, nbig);
     double2 *psi = c->c64_psi, *big = c->c64_big;
     hipLaunchKernelGGL(k_c64_bcast, dim3(eg), dim3(256), 0, c->stream, c->c64_probe, psi, B, per);
@@ -2116,8 +2038,7 @@ int bdof_loss_grad_conv_f64(bdof_ctx* c, int B, const int* angle_of_b, const int
     }
     c->tape_valid = c->last_valid = false;
     c->gpsi_src = nullptr;
-    HIPC(c, hipGetLastError());
-    return 0;
+    return launched(c);
 }
 
 // ---- the transfer-function model in float64 on the same context -------------------------------------------------------------
@@ -2125,7 +2046,7 @@ int bdof_loss_grad_conv_f64(bdof_ctx* c, int B, const int* angle_of_b, const int
 // ifftshift-ed transfer functions / (NX NY); k = 2 pi dz / lambda as bdof_set_physics has it
 int bdof_set_tf_f64(bdof_ctx* c, const double* probe, const double* hT, const double* hdetT, double k) {
     if (!c || !probe || !hT) return BDOF_ERR_ARG;
-    if (c->NY == 0) return fail(c, BDOF_ERR_STATE, "bdof_configure has not been called");
+    if (int r = need_configured(c)) return r;
     if (c->det_mode == BDOF_DET_NEAR && !hdetT) return fail(c, BDOF_ERR_ARG, "a near-field detector needs its transfer function in float64 too");
     HIPC(c, hipSetDevice(c->device));
     HIPC(c, hipStreamSynchronize(c->stream));
@@ -2151,20 +2072,15 @@ int bdof_loss_grad_tf_f64(bdof_ctx* c, int B, const int* angle_of_b, const int* 
     if (!c->c64_tf) return fail(c, BDOF_ERR_STATE, "bdof_set_tf_f64 has not been called");
     if (!c->obj_src) return fail(c, BDOF_ERR_STATE, "bdof_set_object (with (delta, beta) rows) has not been called");
     if (!c->grot || !c->partial) return fail(c, BDOF_ERR_STATE, "bdof_configure(with_grad = 1) needed");
-    if (B < 1 || B > c->Bmax) return fail(c, BDOF_ERR_ARG, "batch size outside [1, Bmax]");
-    if (c->obj.tab && !angle_of_b) return fail(c, BDOF_ERR_ARG, "angle_of_b required with a rotation table");
+    int r;
+    if ((r = check_batch(c, B)) || (r = need_angles(c, angle_of_b))) return r;
     HIPC(c, hipSetDevice(c->device));
     const int NX = c->NX, NY = c->NY, S = c->S;
     const size_t per = (size_t)NX * NY, n = per * B;
-    int r;
     if ((r = c64_room(c, B, true, 0))) return r;
     rocfft_plan pf, pi;
     if ((r = field_plans(c, NX, NY, B, true, &pf, &pi))) return r;
-    ObjView o = c->obj;
-    o.vol = c->obj_src;
-    o.angle_of_b = angle_of_b;
-    o.xoff = xoff;
-    o.yoff = yoff;
+    const ObjView o = rows_view(c, angle_of_b, xoff, yoff);
     const int eg = g_elem_grid(c, n);
     const bool far = c->det_mode == BDOF_DET_FAR;
     // a step after the last slice: variant tf_all, except in front of a far-field detector (|F P phi| = |H F phi| = |F phi|)
@@ -2193,8 +2109,7 @@ int bdof_loss_grad_tf_f64(bdof_ctx* c, int B, const int* angle_of_b, const int* 
     }
     c->tape_valid = c->last_valid = false;
     c->gpsi_src = nullptr;
-    HIPC(c, hipGetLastError());
-    return 0;
+    return launched(c);
 }
 
 int bdof_tape_to_real(bdof_ctx* c, int i, int B, void* out) {
@@ -2213,8 +2128,7 @@ int bdof_tape_to_real(bdof_ctx* c, int i, int B, void* out) {
         launch_loss_real(c, B, c->bufA, nullptr, false, (cf*)out, nullptr, 1.f / c->NY, 1.f, 0.f, carrier_phi_at(c, c->S - 1),
                          slice_carrier_field(c, c->S - 1));
     }
-    HIPC(c, hipGetLastError());
-    return 0;
+    return launched(c);
 }
 
 int bdof_loss_grad(bdof_ctx* c, int B, const int* angle_of_b, const int* xoff, const int* yoff, const float* meas, void* out_wave) {
@@ -2224,7 +2138,7 @@ int bdof_loss_grad(bdof_ctx* c, int B, const int* angle_of_b, const int* xoff, c
     if (c->meas_dev && (c->det_mode == BDOF_DET_FAR || c->pstack))
         return fail(c, BDOF_ERR_STATE, "bdof_set_meas_mode(1) needs a real-space detector and a scalar carrier");
     if (!c->with_grad || !c->grot) return fail(c, BDOF_ERR_STATE, "bdof_loss_grad needs bdof_configure(with_grad=1) with the gradient workspace (not flag 32)");
-    if (c->obj.tab && !angle_of_b) return fail(c, BDOF_ERR_ARG, "angle_of_b required with a rotation table");
+    if ((r = need_angles(c, angle_of_b))) return r;
     HIPC(c, hipSetDevice(c->device));
     set_batch_views(c, angle_of_b, xoff, yoff);
     if ((r = ensure_modulation_k(c, c->k_fft))) return r;
@@ -2239,8 +2153,7 @@ int bdof_loss_grad(bdof_ctx* c, int B, const int* angle_of_b, const int* xoff, c
         if ((r = generic_loss_grad(c, B, meas, out_wave))) return r;
         c->tape_valid = c->last_valid = false;
         c->gpsi_src = c->bufA;                  // the adjoint sweep ends with G(psi_0) in the field buffer, [b][x][y]
-        HIPC(c, hipGetLastError());
-        return 0;
+        return launched(c);
     }
     const size_t fld = (size_t)c->Bmax * c->NX * c->NY;
     const float NYf = (float)c->NY;
@@ -2250,12 +2163,10 @@ int bdof_loss_grad(bdof_ctx* c, int B, const int* angle_of_b, const int* xoff, c
     if ((r = fork_streams(c, ng))) return r;
     // The tape is the per-slice history psi_hat_z that the transfer-function kernel writes anyway; A'_z recomputes phi_z from
     // it (one more transform per launch, no tape write in A_z: 104 instead of 112 B per pixel per slice-step, 67.6 -> 65.3 ms
-    // per step at 512^3 x 25).  BDOF_TAPE_PHI=1 selects the older form (A_z stores phi_z) for comparison; same bits.
-    static const bool hist_env = std::getenv("BDOF_TAPE_PHI") == nullptr;
+    // per step at 512^3 x 25).
     const bool recompute = c->recompute;
-    const bool hist_tape = hist_env && !recompute;
-    forward_sweep(c, groups, ng, recompute ? TAPE_LAST : (hist_tape ? TAPE_HISTORY : TAPE_PHI));
-    c->tape_valid = false;      // the tape holds phi_z (or an incomplete history), not what bdof_tape_to_real expects
+    forward_sweep(c, groups, ng, recompute ? TAPE_LAST : TAPE_HISTORY);
+    c->tape_valid = false;      // the tape holds an incomplete history (or phi_{S-1} alone), not what bdof_tape_to_real expects
     c->last_valid = false;
     const float seed_scale = 2.f / ((float)B * (float)c->NX * (float)c->NY);
     int npart = 0;
@@ -2275,7 +2186,7 @@ int bdof_loss_grad(bdof_ctx* c, int B, const int* angle_of_b, const int* xoff, c
         }
     }
     // backward sweep: A'_z (L1 -> L2), then the adjoint transfer-function step (L2 -> L1)
-    // Tape-free form (bdof_configure flag 16): P is unitary and c_z is invertible, so the forward wave is marched
+    // Tape-free form (BDOF_CFG_RECOMPUTE): P is unitary and c_z is invertible, so the forward wave is marched
     // BACK beside the adjoint field instead of being stored per slice: phi_{z-1} = P^H (phi_z / c_z) — one A_z^-1 launch and
     // one more adjoint transfer-function launch per slice (+40 B per pixel per slice-step), S - 3 fields per wavefield less
     // memory.  phi_{S-1} is kept by the forward sweep (real space, tape slot 0); slots 1 / 2 hold the marched-back wave in L1 /
@@ -2298,19 +2209,15 @@ int bdof_loss_grad(bdof_ctx* c, int B, const int* angle_of_b, const int* xoff, c
                 }
                 continue;
             }
-            if (hist_tape)
-                launch_row_bwd(c, groups[gi].B, z, c->bufB, z > 0 ? c->tape + (size_t)(z - 1) * fld : nullptr, z > 0 ? c->bufA : nullptr,
-                               z > 0 ? 1 : 2);
-            else
-                launch_row_bwd(c, groups[gi].B, z, c->bufB, c->tape + (size_t)z * fld, z > 0 ? c->bufA : nullptr);
+            launch_row_bwd(c, groups[gi].B, z, c->bufB, z > 0 ? c->tape + (size_t)(z - 1) * fld : nullptr, z > 0 ? c->bufA : nullptr,
+                           z > 0 ? 1 : 2);
             if (z > 0) launch_row_prop(c, groups[gi].B, c->bufA, c->bufB, c->hs, 1.f, 1, z - 1);
         }
     }
     if ((r = join_streams(c, ng))) return r;
     hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, c->stream, c->partial, npart,
                        1.0 / ((double)B * c->NX * c->NY), c->loss_dev);
-    HIPC(c, hipGetLastError());
-    return 0;
+    return launched(c);
 }
 
 
@@ -2320,7 +2227,7 @@ int bdof_loss_grad(bdof_ctx* c, int B, const int* angle_of_b, const int* xoff, c
 int bdof_set_conv(bdof_ctx* c, const float* ky, const float* kx, int ks, double e_re, double e_im, double ksum_re,
                   double ksum_im, double k) {
     if (!c || !ky || !kx) return BDOF_ERR_ARG;
-    if (c->NY == 0) return fail(c, BDOF_ERR_STATE, "bdof_configure has not been called");
+    if (int r = need_configured(c)) return r;
     if (ks < 1 || ks > BDOF_CONV_MAXK || ks % 2 == 0) return fail(c, BDOF_ERR_ARG, "kernel_size must be odd and <= 33");
     if (c->generic || c->NX % BDOF_CONV_TX || c->NY % BDOF_CONV_TY)
         return fail(c, BDOF_ERR_SIZE, "the conv propagator needs power-of-two wavefields (tiles are 32 x 64)");
@@ -2415,30 +2322,21 @@ template <bool BWD, int H, bool PF> static int launch_conv_hp(bdof_ctx* c, ConvA
             return 0;
         }
     }
-    const int lds = conv_lds_bytes(c);
-    static bool attr_set[BDOF_MAX_DEVICES] = {};
-    if (!attr_set[c->device % BDOF_MAX_DEVICES]) {
-        HIPC(c, hipFuncSetAttribute((const void*)k_conv<BWD, H, PF>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024));
-        attr_set[c->device % BDOF_MAX_DEVICES] = true;
-    }
+    if (int r = max_lds_once<k_conv<BWD, H, PF>>(c, 160 * 1024 - 1024)) return r;
     const int tiles = a.B * (a.NX / BDOF_CONV_TX) * (a.NY / BDOF_CONV_TY);
     const int grid = balanced_grid(c, tiles, 2);
-    BDOF_LAUNCH(ps, (k_conv<BWD, H, PF>), dim3(grid), dim3(BDOF_CONV_THREADS), lds, c->sub_stream, a);
+    BDOF_LAUNCH(ps, (k_conv<BWD, H, PF>), dim3(grid), dim3(BDOF_CONV_THREADS), conv_lds_bytes(c), c->sub_stream, a);
     return 0;
-}
-template <bool BWD, int H> static int launch_conv_h(bdof_ctx* c, ConvArgs& a, ProfScope& ps) {
-    return a.pfield ? launch_conv_hp<BWD, H, true>(c, a, ps) : launch_conv_hp<BWD, H, false>(c, a, ps);
 }
 
 template <bool BWD> static int launch_conv(bdof_ctx* c, ConvArgs& a) {
     ProfScope ps(c, BWD ? BDOF_K_ROW_BWD : BDOF_K_ROW_FWD, true);
-    switch ((c->taps.ks - 1) / 2) {           // register-window fast paths for the common kernel sizes 5, 9, 17, 33
-        case 2: return launch_conv_h<BWD, 2>(c, a, ps);
-        case 4: return launch_conv_h<BWD, 4>(c, a, ps);
-        case 8: return launch_conv_h<BWD, 8>(c, a, ps);
-        case 16: return launch_conv_h<BWD, 16>(c, a, ps);
-        default: return launch_conv_h<BWD, 0>(c, a, ps);
-    }
+    // register-window fast paths for the common kernel sizes 5, 9, 17, 33 (H = 2, 4, 8, 16 = 2^L), the generic window H = 0 otherwise
+    const int h = (c->taps.ks - 1) / 2;
+    const int log_h = h == 2 ? 1 : h == 4 ? 2 : h == 8 ? 3 : h == 16 ? 4 : 0;
+    return with_int<5>(log_h, [&](auto L) { return with_bool(a.pfield != nullptr, [&](auto PF) {
+        return launch_conv_hp<BWD, (L ? 1 << L : 0), PF>(c, a, ps);
+    }); });
 }
 
 // forward sweep of the conv propagator; leaves psi_S (eps part) in bufB and the scalars in conv_scal
@@ -2494,8 +2392,7 @@ static int conv_check(bdof_ctx* c, int B, const int* angle_of_b) {
     int r = check_ready(c, B);
     if (r) return r;
     if (!c->have_conv) return fail(c, BDOF_ERR_STATE, "bdof_set_conv has not been called");
-    if (c->obj.tab && !angle_of_b) return fail(c, BDOF_ERR_ARG, "angle_of_b required with a rotation table");
-    return 0;
+    return need_angles(c, angle_of_b);
 }
 
 
@@ -2503,7 +2400,7 @@ extern "C" {
 
 int bdof_set_conv_probe_stack(bdof_ctx* c, const float* stack, const double* det64, double p0_re, double p0_im, double pS_re, double pS_im) {
     if (!c) return BDOF_ERR_ARG;
-    if (c->NY == 0) return fail(c, BDOF_ERR_STATE, "bdof_configure has not been called");
+    if (int r = need_configured(c)) return r;
     HIPC(c, hipSetDevice(c->device));
     HIPC(c, hipStreamSynchronize(c->stream));
     if (c->cstack) { (void)hipFree(c->cstack); c->cstack = nullptr; }
@@ -2558,8 +2455,7 @@ int bdof_forward_conv(bdof_ctx* c, int B, const int* angle_of_b, const int* xoff
             c->a0 = keep;
         }
     }
-    HIPC(c, hipGetLastError());
-    return 0;
+    return launched(c);
 }
 
 int bdof_loss_grad_conv(bdof_ctx* c, int B, const int* angle_of_b, const int* xoff, const int* yoff, const float* meas, void* out_wave) {
@@ -2662,13 +2558,12 @@ int bdof_loss_grad_conv(bdof_ctx* c, int B, const int* angle_of_b, const int* xo
         }
     }
     if ((r = join_streams(c, ng))) return r;
-    HIPC(c, hipGetLastError());
-    return 0;
+    return launched(c);
 }
 
 int bdof_enable_probe_grad(bdof_ctx* c, int enable) {
     if (!c) return BDOF_ERR_ARG;
-    if (c->NY == 0) return fail(c, BDOF_ERR_STATE, "bdof_configure has not been called");
+    if (int r = need_configured(c)) return r;
     HIPC(c, hipSetDevice(c->device));
     if (enable && !c->gpsi0) {
         if (!c->with_grad) return fail(c, BDOF_ERR_STATE, "the probe gradient needs bdof_configure(with_grad=1)");
@@ -2690,8 +2585,7 @@ int bdof_probe_grad(bdof_ctx* c, void* out, int accumulate) {
     const size_t n = (size_t)c->NX * c->NY;
     hipLaunchKernelGGL(k_sum_fields, dim3((unsigned)std::min<size_t>((n + 255) / 256, (size_t)c->ncu * 8)), dim3(256), 0, c->stream, c->gpsi_src,
                        (cf*)out, c->gpsi_B, n, accumulate);
-    HIPC(c, hipGetLastError());
-    return 0;
+    return launched(c);
 }
 
 int bdof_get_loss(bdof_ctx* c, double* loss) {
@@ -2708,7 +2602,7 @@ int bdof_rotation_adjoint_rows(bdof_ctx* c, int B, const int* angle_of_b, void* 
     if (!c || !gvol || !angle_of_b) return BDOF_ERR_ARG;
     if (!c->grot) return fail(c, BDOF_ERR_STATE, "no gradient workspace (configure with_grad=1)");
     if (!c->adj_off) return fail(c, BDOF_ERR_STATE, "bdof_set_rotation_adjoint has not been called");
-    if (B < 1 || B > c->Bmax) return fail(c, BDOF_ERR_ARG, "batch size outside [1, Bmax]");
+    if (int r = check_batch(c, B)) return r;
     if (c->NY % 2) return fail(c, BDOF_ERR_SIZE, "the rotation adjoint needs an even NY");
     if (row0 < 0 || n_rows < 0 || (long long)row0 + n_rows > c->adj_ndest) return fail(c, BDOF_ERR_ARG, "destination rows outside the volume");
     if (n_rows == 0) return 0;
@@ -2721,8 +2615,7 @@ int bdof_rotation_adjoint_rows(bdof_ctx* c, int B, const int* angle_of_b, void* 
     int grid = need < c->ncu * 8 ? need : c->ncu * 8;
     hipLaunchKernelGGL(k_rot_adjoint, dim3(grid), dim3(256), 0, c->stream, a);
     hipLaunchKernelGGL(k_rot_adjoint_heavy, dim3(c->ncu * 8), dim3(256), 0, c->stream, a);
-    HIPC(c, hipGetLastError());
-    return 0;
+    return launched(c);
 }
 
 int bdof_rotation_adjoint(bdof_ctx* c, int B, const int* angle_of_b, void* gvol, int accumulate, float scale) {
@@ -2735,7 +2628,7 @@ int bdof_window_rotation_adjoint(bdof_ctx* c, int B, int angle, const int* xoff,
     if (!c || !gvol || !xoff || !yoff) return BDOF_ERR_ARG;
     if (!c->grot) return fail(c, BDOF_ERR_STATE, "no gradient workspace (configure with_grad=1)");
     if (!c->adj_off || !c->obj.tab) return fail(c, BDOF_ERR_STATE, "rotation tables have not been set");
-    if (B < 1 || B > c->Bmax) return fail(c, BDOF_ERR_ARG, "batch size outside [1, Bmax]");
+    if (int r = check_batch(c, B)) return r;
     if (angle < 0 || angle >= c->n_angles) return fail(c, BDOF_ERR_ARG, "angle index outside the rotation tables");
     HIPC(c, hipSetDevice(c->device));
     if (c->obj.volNY % 2) return fail(c, BDOF_ERR_SIZE, "the rotation adjoint needs an even volume NY");
@@ -2747,8 +2640,7 @@ int bdof_window_rotation_adjoint(bdof_ctx* c, int B, int angle, const int* xoff,
         // more windows than the overlap-add kernel lists per column: direct (slow) gather
         int grid = c->adj_ndest < c->ncu * 16 ? c->adj_ndest : c->ncu * 16;
         hipLaunchKernelGGL(k_window_rot_adjoint, dim3(grid), dim3(256), 0, c->stream, a);
-        HIPC(c, hipGetLastError());
-        return 0;
+        return launched(c);
     }
     const size_t need = sizeof(float2) * (size_t)n_src * c->obj.volNY;
     if (c->winpad_sz < need) {
@@ -2771,8 +2663,7 @@ int bdof_window_rotation_adjoint(bdof_ctx* c, int B, int angle, const int* xoff,
     const int needwg = (c->adj_ndest + 3) / 4;
     hipLaunchKernelGGL(k_rot_adjoint, dim3(needwg < c->ncu * 8 ? needwg : c->ncu * 8), dim3(256), 0, c->stream, r);
     hipLaunchKernelGGL(k_rot_adjoint_heavy, dim3(c->ncu * 8), dim3(256), 0, c->stream, r);
-    HIPC(c, hipGetLastError());
-    return 0;
+    return launched(c);
 }
 
 int bdof_adam_step_slab(bdof_ctx* c, const void* x_old, void* x_new, const void* g, void* m, void* v, const float* mask,
@@ -2798,8 +2689,7 @@ int bdof_adam_step_slab(bdof_ctx* c, const void* x_old, void* x_new, const void*
     int grid = need < (size_t)c->ncu * 16 ? (int)need : c->ncu * 16;
     grid = (grid + 7) / 8 * 8;                       // k_adam deals the range to the 8 XCDs by blockIdx % 8
     hipLaunchKernelGGL(k_adam, dim3(grid), dim3(256), 0, c->stream, a);
-    HIPC(c, hipGetLastError());
-    return 0;
+    return launched(c);
 }
 
 int bdof_adam_step(bdof_ctx* c, const void* x_old, void* x_new, const void* g, void* m, void* v, const float* mask,
@@ -2817,15 +2707,14 @@ int bdof_rotate_bilinear(bdof_ctx* c, const void* vol, int NXv, int NZv, int NYv
     const size_t nrows = (size_t)B * NZv * NXv;
     const int grid = (int)std::min<size_t>((nrows + 3) / 4, (size_t)c->ncu * 16);
     hipLaunchKernelGGL((k_rot_bilinear<false>), dim3(grid), dim3(256), 0, c->stream, a, 0.f, (double2*)nullptr);
-    HIPC(c, hipGetLastError());
-    return 0;
+    return launched(c);
 }
 
 // bdof_rotate_bilinear + bdof_set_object in one pass: the B rotated objects are written straight into the ctx's modulation
 // table as factors c - 1 (no rotated (delta, beta) copy, no second pass over B volumes) and bound as the batch's objects.
 int bdof_set_object_bilinear(bdof_ctx* c, const void* vol, int NXv, int NZv, int NYv, const double* prm, int B, int conv) {
     if (!c || !vol || !prm || B < 1) return BDOF_ERR_ARG;
-    if (c->NY == 0) return fail(c, BDOF_ERR_STATE, "bdof_configure has not been called");
+    if (int r = need_configured(c)) return r;
     if (NXv < 1 || NZv < 1 || NYv < 2 || NYv % 2) return fail(c, BDOF_ERR_SIZE, "bdof_set_object_bilinear needs an even NY");
     if (NYv != c->NY || NXv != c->NX || NZv != c->S) return fail(c, BDOF_ERR_ARG, "the volume must be (NX, S, NY) of the configured wavefields");
     if (B > c->Bmax) return fail(c, BDOF_ERR_ARG, "batch size outside [1, Bmax]");
@@ -2867,8 +2756,7 @@ int bdof_rotate_bilinear_adjoint(bdof_ctx* c, const void* grot, int NXv, int NZv
     else if (nv4 <= 4) hipLaunchKernelGGL((k_rot_bilinear_adjoint<4>), dim3(grid), dim3(256), 0, c->stream, a);
     else if (nv4 <= 8) hipLaunchKernelGGL((k_rot_bilinear_adjoint<8>), dim3(grid), dim3(256), 0, c->stream, a);
     else return fail(c, BDOF_ERR_SIZE, "bdof_rotate_bilinear_adjoint: NY <= 1024");
-    HIPC(c, hipGetLastError());
-    return 0;
+    return launched(c);
 }
 
 int bdof_regularizer_value(bdof_ctx* c, const void* x, int NXv, int NZv, int NYv, double* sums) {
@@ -2896,8 +2784,7 @@ int bdof_mask_shrink(bdof_ctx* c, const void* x, float* mask, size_t n, float th
     size_t need = (n + 255) / 256;
     int grid = need < (size_t)c->ncu * 16 ? (int)need : c->ncu * 16;
     hipLaunchKernelGGL(k_mask_shrink, dim3(grid), dim3(256), 0, c->stream, (const float2*)x, mask, n, thresh);
-    HIPC(c, hipGetLastError());
-    return 0;
+    return launched(c);
 }
 
 int bdof_gather_fields(bdof_ctx* c, void* dst, const void* src, const int* idx, int B, size_t bytes_per_field) {
@@ -2908,14 +2795,12 @@ int bdof_gather_fields(bdof_ctx* c, void* dst, const void* src, const int* idx, 
         const size_t n4 = bytes_per_field / 4;
         const int gx4 = (int)std::min<size_t>((n4 + 255) / 256, 64);
         hipLaunchKernelGGL(k_gather_fields4, dim3(gx4, B < 1024 ? B : 1024), dim3(256), 0, c->stream, (float*)dst, (const float*)src, idx, B, n4);
-        HIPC(c, hipGetLastError());
-        return 0;
+        return launched(c);
     }
     const size_t n16 = bytes_per_field / 16;
     const int gx = (int)std::min<size_t>((n16 + 255) / 256, 64);
     hipLaunchKernelGGL(k_gather_fields, dim3(gx, B < 1024 ? B : 1024), dim3(256), 0, c->stream, (float4*)dst, (const float4*)src, idx, B, n16);
-    HIPC(c, hipGetLastError());
-    return 0;
+    return launched(c);
 }
 
 int bdof_set_streams(bdof_ctx* c, int n) {

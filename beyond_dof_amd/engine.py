@@ -46,10 +46,10 @@ class MultisliceEngine(object):
         self.h = self.ctx.handle
         self.ny, self.nx, self.n_slice, self.batch_max = int(ny), int(nx), int(n_slice), int(batch_max)
         self.with_grad = bool(with_grad)
-        self.ctx.check(self.lib.bdof_configure(self.h, self.ny, self.nx, self.n_slice, self.batch_max,
-                                               int(bool(with_grad)) | (2 if (force_generic or os.environ.get('BDOF_FORCE_GENERIC')) else 0)
-                                               | (4 if engine == 'streaming' else 0) | (8 if engine == 'resident' else 0)
-                                               | (16 if self.recompute else 0) | (32 if no_grot else 0) | (64 if self.adjoint64 else 0)))
+        flags = (_lib.CFG_GRAD if with_grad else 0) | (_lib.CFG_GENERIC if (force_generic or os.environ.get('BDOF_FORCE_GENERIC')) else 0) \
+            | (_lib.CFG_NO_RESIDENT if engine == 'streaming' else 0) | (_lib.CFG_ALWAYS_RESIDENT if engine == 'resident' else 0) \
+            | (_lib.CFG_RECOMPUTE if self.recompute else 0) | (_lib.CFG_NO_GROT if no_grot else 0) | (_lib.CFG_ADJOINT64 if self.adjoint64 else 0)
+        self.ctx.check(self.lib.bdof_configure(self.h, self.ny, self.nx, self.n_slice, self.batch_max, flags))
         self._engine_arg = 'generic' if force_generic else engine
         self._device = device
         self.det_mode = _lib.DET_NONE

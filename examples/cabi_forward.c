@@ -47,7 +47,7 @@ int main(int argc, char** argv) {
 
     if (bdof_device_count() < 1) { fprintf(stderr, "no GPU\n"); return 4; }
     CHECK(bdof_ctx_create(&ctx, 0, NULL));
-    CHECK(bdof_configure(ctx, NY, NX, S, B, 1));
+    CHECK(bdof_configure(ctx, NY, NX, S, B, BDOF_CFG_GRAD));
     CHECK(bdof_set_physics(ctx, dbl[0], hs, hdet, &dbl[1], &dbl[3], det, variant));
     CHECK(bdof_set_transfer_f64(ctx, hs64));         /* the slice step's H in float64: the kernels use dithered float32 copies of it */
     CHECK(bdof_set_probe(ctx, probe, dbl[5], dbl[6]));

@@ -30,6 +30,8 @@ typedef struct bdof_ctx bdof_ctx;
 enum { BDOF_DET_NONE = 0, BDOF_DET_NEAR = 1, BDOF_DET_FAR = 2 };      /* free_prop_cm None / float / 'inf'  (np_funcs.py:45-61) */
 enum { BDOF_VARIANT_NUMPY_SKIP_LAST = 0, BDOF_VARIANT_TF_ALL = 1 };   /* np_funcs.py:41 vs tensorflow_recon/util.py:465-483 */
 enum { BDOF_K_ROW_FWD = 0, BDOF_K_COL_PROP = 1, BDOF_K_ROW_BWD = 2, BDOF_K_LOSS = 3, BDOF_K_ROT_ADJ = 4, BDOF_K_ADAM = 5, BDOF_K_COUNT = 6 };
+enum { BDOF_CFG_GRAD = 1, BDOF_CFG_GENERIC = 2, BDOF_CFG_NO_RESIDENT = 4, BDOF_CFG_ALWAYS_RESIDENT = 8, BDOF_CFG_RECOMPUTE = 16,
+       BDOF_CFG_NO_GROT = 32, BDOF_CFG_ADJOINT64 = 64 };                /* bdof_configure's with_grad flags */
 
 /* lifecycle.  `stream` is a hipStream_t (NULL: the library creates its own). */
 int bdof_ctx_create(bdof_ctx** out, int device, void* stream);
@@ -57,14 +59,15 @@ int bdof_timer_elapsed(bdof_ctx* ctx, int slot_a, int slot_b, double* ms);
  *     fields of 32, 36, 48, 64, 72, 80, 96 or 128 pixels — the probes of the ptychography drivers
  *     (cnn_propagator/reconstruct_ptycho.py:106); chosen when no fused plan exists or the batch has >= CUs/4 wavefields;
  *   - generic-size engine (rocFFT + point-wise kernels): every other size.
- * with_grad bits: 0 allocate the tape (S fields per wavefield) and the rotated-frame gradient; 1 force the generic-size
- * engine (cross-checks); 2 never use the resident engine; 3 use it for every batch size; 4 (value 16) tape-free adjoint of the
- * streaming engine: 3 tape fields instead of S, the forward wave is marched back beside the adjoint field;
- * 5 (value 32) no rotated-frame gradient workspace (range sweeps with caller-owned buffers, bdof_adjoint_range);
- * 6 (value 64) float64 adjoint sweep (accuracy option; runs on the generic-size engine whatever the size): seed, adjoint
- * transforms (rocFFT double precision), transfer function and the products conj(phi) G in float64, forward sweep and tape in
- * float32 — what autograd's float64 tape gives the reference (cnn_propagator/fullfield.py:329, ptychography.py:248);
- * follow bdof_set_physics with bdof_set_physics_f64.
+ * with_grad: an OR of BDOF_CFG_* flags.  BDOF_CFG_GRAD allocate the tape (S fields per wavefield) and the rotated-frame
+ * gradient; BDOF_CFG_GENERIC force the generic-size engine (cross-checks); BDOF_CFG_NO_RESIDENT never use the resident engine;
+ * BDOF_CFG_ALWAYS_RESIDENT use it for every batch size; BDOF_CFG_RECOMPUTE tape-free adjoint of the streaming engine: 3 tape
+ * fields instead of S, the forward wave is marched back beside the adjoint field; BDOF_CFG_NO_GROT no
+ * rotated-frame gradient workspace (range sweeps with caller-owned buffers, bdof_adjoint_range); BDOF_CFG_ADJOINT64 float64
+ * adjoint sweep (accuracy option; runs on the generic-size engine whatever the size): seed, adjoint transforms (rocFFT double
+ * precision), transfer function and the products conj(phi) G in float64, forward sweep and tape in float32 — what autograd's
+ * float64 tape gives the reference (cnn_propagator/fullfield.py:329, ptychography.py:248); follow bdof_set_physics with
+ * bdof_set_physics_f64.
  * Environment read here: BDOF_TW_DITHER=D — number of dithered copies of the transform constants the per-slice kernels walk
  * (default 64; 0: one plain float32 table, round 2's behaviour; DESIGN §5 "Dithered transform constants").
  * Replaces the per-call allocations of multislice_propagate_batch_numpy

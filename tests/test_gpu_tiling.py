@@ -465,3 +465,48 @@ def test_range_carrier_stack_in_one_call_equals_the_step_by_step_one():
     e = (rel(s1, s2), rel(s1, ref), rel(s2, ref))
     print('carrier stack: one call vs step by step', e[0], ' vs numpy float64:', e[1:])
     assert e[0] <= 2e-7 and e[1] <= 1e-7 and e[2] <= 1e-7, e        # complex64 storage: 6e-8
+
+
+def test_tile_entry_points_refuse_bad_taper_halo_and_batch():
+    """Each of the ten bdof_tiles_* entry points refuses a taper that does not fit the tile (gathers) or a halo that leaves no
+    core (scatters), and a batch of no tiles, before it launches; the valid call next to them runs."""
+    from beyond_dof_amd import _lib
+    ctx = _lib.Context(0)
+    lib, h = ctx.lib, ctx.handle
+    FX = FY = 64
+    TX = TY = 32
+    f32 = _lib.DeviceBuffer.zeros(ctx, (FX, FY), np.complex64)
+    f64 = _lib.DeviceBuffer.zeros(ctx, (FX, FY), np.complex128)
+    t32 = _lib.DeviceBuffer.zeros(ctx, (1, TX, TY), np.complex64)
+    t64 = _lib.DeviceBuffer.zeros(ctx, (1, TX, TY), np.complex128)
+    pos = _lib.DeviceBuffer.zeros(ctx, (1,), np.int32)
+    p = (pos.ptr, pos.ptr)
+    gathers = {          # (taper, B) -> return code
+        'bdof_tiles_gather': lambda t, B: lib.bdof_tiles_gather(h, f32.ptr, FX, FY, t32.ptr, B, TX, TY, *p, t),
+        'bdof_tiles_gather_adjoint': lambda t, B: lib.bdof_tiles_gather_adjoint(h, t32.ptr, f32.ptr, FX, FY, B, TX, TY, *p, t),
+        'bdof_tiles_gather_f64': lambda t, B: lib.bdof_tiles_gather_f64(h, f64.ptr, FX, FY, t64.ptr, B, TX, TY, *p, t),
+        'bdof_tiles_gather_mixed': lambda t, B: lib.bdof_tiles_gather_mixed(h, f64.ptr, FX, FY, t32.ptr, B, TX, TY, *p, t),
+        'bdof_tiles_gather_adjoint_diff64': lambda t, B: lib.bdof_tiles_gather_adjoint_diff64(h, t32.ptr, None, f64.ptr, FX, FY, B, TX, TY,
+                                                                                           *p, t, 0),
+    }
+    scatters = {         # (halo, B) -> return code
+        'bdof_tiles_scatter': lambda o, B: lib.bdof_tiles_scatter(h, t32.ptr, f32.ptr, FX, FY, B, TX, TY, *p, o, o),
+        'bdof_tiles_scatter_adjoint': lambda o, B: lib.bdof_tiles_scatter_adjoint(h, f32.ptr, FX, FY, t32.ptr, B, TX, TY, *p, o, o),
+        'bdof_tiles_scatter_f64': lambda o, B: lib.bdof_tiles_scatter_f64(h, t64.ptr, f64.ptr, FX, FY, B, TX, TY, *p, o, o),
+        'bdof_tiles_scatter_adjoint_mixed': lambda o, B: lib.bdof_tiles_scatter_adjoint_mixed(h, f64.ptr, FX, FY, t32.ptr, B, TX, TY, *p, o, o),
+        'bdof_tiles_scatter_diff64': lambda o, B: lib.bdof_tiles_scatter_diff64(h, t32.ptr, None, f64.ptr, FX, FY, B, TX, TY, *p, o, o, 0),
+    }
+    for name, call in gathers.items():
+        for taper in (-1, TX // 2 + 1):
+            assert call(taper, 1) != 0 and b'taper' in lib.bdof_last_error(h), name
+        assert call(4, 0) != 0 and b'shape' in lib.bdof_last_error(h), name
+        assert call(4, 1) == 0, name
+    for name, call in scatters.items():
+        for halo in (-1, TX // 2):
+            assert call(halo, 1) != 0 and b'halo' in lib.bdof_last_error(h), name
+        assert call(4, 0) != 0 and b'shape' in lib.bdof_last_error(h), name
+        assert call(4, 1) == 0, name
+    ctx.sync()
+    for b in (f32, f64, t32, t64, pos):
+        b.free()
+    ctx.close()

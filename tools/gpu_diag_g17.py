@@ -32,7 +32,7 @@ def main():
     engines = (('conv', {}),) if conv else (('resident', {}), ('streaming', {'BDOF_NO_RESIDENT_PIN': '1'}),
                                             ('generic', {'BDOF_NO_RESIDENT_PIN': '1', 'BDOF_FORCE_GENERIC': '1'}),
                                             ('adjoint64', {'BDOF_ADJOINT64': '1'}))
-    print('lib', os.environ.get('BDOF_LIB', 'default'), 'BDOF_NO_F64_DET' if os.environ.get('BDOF_NO_F64_DET') else '')
+    print('lib', os.environ.get('BDOF_LIB', 'default'))
     ind0 = np.array([0, 1])
     _, rgd, rgb = orc.ptycho_loss_and_grad(init_d, init_b, coords[0], pos, pos[ind0], g['prj'][0, ind0], pr, pi_, psz, 5000., 1e-7,
                                            propagator='conv' if conv else 'fft')
