@@ -476,10 +476,9 @@ static void launch_row_prop(bdof_ctx* c, int B, const cf* in, cf* out, const cf*
     }
     RowPropArgs a{sub_field(c, in), sub_field(c, out), h, B, c->NY, scale, conj_h, tw_of(c, c->twX, c->NX, tick)};
     sq_of(c, tick, a.sq);
-    // the adjoint step runs the instance with exact transform constants (bdof_fft.h: that is where the gradient's error is made)
-    DISPATCH_N(c->NX, with_bool(conj_h ? BDOF_EX_ADJ : BDOF_EX_FWD_B, [&](auto EX) {
-        BDOF_LAUNCH(ps, (k_row_prop<N_, EX>), dim3(rows_grid<N_>(c, B, c->NY)), dim3(BDOF_THREADS), 0, c->sub_stream, a);
-    }));
+    DISPATCH_N(c->NX, {
+        BDOF_LAUNCH(ps, (k_row_prop<N_, false>), dim3(rows_grid<N_>(c, B, c->NY)), dim3(BDOF_THREADS), 0, c->sub_stream, a);
+    });
 }
 
 // A'_z: L1 (g) + phi tape -> L2 (g)
@@ -1108,8 +1107,8 @@ int bdof_configure(bdof_ctx* c, int NY, int NX, int S, int Bmax, int with_grad) 
     { const char* e = std::getenv("BDOF_TW_DITHER"); c->tw_dither = e ? std::max(0, std::min(256, atoi(e))) : 64; if (c->tw_dither == 1) c->tw_dither = 0; }
     c->recompute = (with_grad & BDOF_CFG_RECOMPUTE) != 0 && !generic;      // the streaming engine's option; the others keep their tapes
     c->adj64 = (with_grad & BDOF_CFG_ADJOINT64) != 0 && c->with_grad;
-    c->resident = (with_grad & (BDOF_CFG_GENERIC | BDOF_CFG_NO_RESIDENT | BDOF_CFG_ADJOINT64)) == 0 && NX == NY && resident_supported(NX) && !std::getenv("BDOF_NO_RESIDENT");
-    c->res_always = (with_grad & BDOF_CFG_ALWAYS_RESIDENT) != 0 || std::getenv("BDOF_FORCE_RESIDENT");
+    c->resident = (with_grad & (BDOF_CFG_GENERIC | BDOF_CFG_NO_RESIDENT | BDOF_CFG_ADJOINT64)) == 0 && NX == NY && resident_supported(NX);
+    c->res_always = (with_grad & BDOF_CFG_ALWAYS_RESIDENT) != 0;
     c->res_dirty = true;
     c->have_physics = c->have_probe = c->tape_valid = false;
     int r;

@@ -11,7 +11,7 @@
 //   * windows of 4 outputs in both passes: 8 (64 + 2H) y-pass windows in two rounds, 512 x-pass windows — every wave
 //     issues the same FMA count in the x pass and the y pass's second round is 2H / 8 waves;
 //   * 53.9 KB of LDS in two static objects, 97-117 VGPRs: two workgroups per CU (three need <= 80 registers: 64-112 bytes of
-//     scratch per lane, 59.9 / 94.9 us against 54.0 / 57.8 us forward / backward in tools/kbench_conv2.hip);
+//     scratch per lane, 59.9 / 94.9 us against 54.0 / 57.8 us forward / backward, MEASUREMENTS.md round 3);
 //   * XCD-aware tile order (runs of strips per blockIdx % 8) so that the halos neighbouring tiles share are L2 hits;
 //   * the DMA and the loads carried into the next tile are issued by asm, with one counted wait per tile (below).
 // Reference: cnn_propagator/propagation.py:80-107 (the convolution of one slice), :109-110 (renormalisation, k_conv_final).
@@ -47,24 +47,10 @@ template <int H, int TXV = 64> struct Conv2Cfg {
     static constexpr int TXH = TX + 2 * H, TYH = TY + 2 * H, NP = TYH / 2, RU = NP | 1;
     static constexpr int UNITS = TXH * RU, NLOADS = (UNITS + 63) / 64, MP = (NLOADS + NW - 1) / NW;
     static constexpr int A_BYTES = NLOADS * 1024, M_BYTES = TXH * SM * 8, LDS = A_BYTES + M_BYTES;
-#ifdef BDOF_CONV2_MINW
-    static constexpr int MINW = BDOF_CONV2_MINW; // timing experiment (tools/kbench_conv2.hip)
-#else
     static constexpr int MINW = 4;               // waves per SIMD asked of the register allocator: two workgroups of 8 waves per CU
-#endif
     static_assert(H % 2 == 0 && NP % 2 == 0, "halo of even width: 16-byte units must not straddle the field's edge");
     static_assert(TX * TY == THREADS * R, "one x-pass window per thread");
 };
-
-// In-kernel phase stamps (tools/kbench_conv2.hip builds with -DBDOF_CONV2_STAMP): wave 0 of every workgroup adds the
-// cycles (s_memtime) it spent in each phase of its tiles to g_conv2_stamp[phase]; compiled out of the library.
-#ifdef BDOF_CONV2_STAMP
-__device__ unsigned long long g_conv2_stamp[8];
-#define CONV2_STAMP(k) do { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); const unsigned long long t_ = __builtin_amdgcn_s_memtime(); \
-                            st_acc[k] += t_ - st_t; st_t = t_; } while (0)
-#else
-#define CONV2_STAMP(k) do { } while (0)
-#endif
 
 template <bool BWD, int H, bool PF = false, int TXV = 64>
 __global__ __launch_bounds__((Conv2Cfg<H, TXV>::THREADS), (Conv2Cfg<H, TXV>::MINW)) void k_conv2(ConvArgs a) {
@@ -101,11 +87,7 @@ __global__ __launch_bounds__((Conv2Cfg<H, TXV>::THREADS), (Conv2Cfg<H, TXV>::MIN
     for (int m = 0; m < MP; ++m) {
         const int u = (wave + NW * m) * 64 + lane;
         const int i = u / RU, c = u - i * RU;
-#if defined(BDOF_CONV2_WHATIF) && (BDOF_CONV2_WHATIF & 4)
-        rel[m] = (unsigned)(min(i, TXH - 1) * a.NY + 2 * (min(c, NP - 1) % 16) + H) * 8u;    // timing experiment: every row's units from
-#else                                                                                          // TWO aligned 128-byte lines
         rel[m] = (unsigned)(min(i, TXH - 1) * a.NY + 2 * min(c, NP - 1)) * 8u;
-#endif
         act |= (wave + NW * m < C::NLOADS && i < TXH && c < NP) ? 1u << m : 0u;
     }
     unsigned oob = 0;            // bit m: the unit of load m lies outside the field (padding constant after landing)
@@ -126,11 +108,7 @@ __global__ __launch_bounds__((Conv2Cfg<H, TXV>::THREADS), (Conv2Cfg<H, TXV>::MIN
             for (int m = 0; m < MP; ++m) {
                 const int u = (wave + NW * m) * 64 + lane;
                 const int i = u / RU, c = u - i * RU;
-#if defined(BDOF_CONV2_WHATIF) && (BDOF_CONV2_WHATIF & 4)
-                const int x = x0 - H + i, y = y0 + 2 * (c % 16);
-#else
                 const int x = x0 - H + i, y = y0 - H + 2 * c;
-#endif
                 const bool in = (unsigned)x < (unsigned)a.NX && (unsigned)y < (unsigned)a.NY;
                 const unsigned off = (__umul24(min(max(x, 0), a.NX - 1), a.NY) + min(max(y, 0), a.NY - 2)) * 8u;
                 if ((act >> m) & 1u) {
@@ -190,11 +168,7 @@ __global__ __launch_bounds__((Conv2Cfg<H, TXV>::THREADS), (Conv2Cfg<H, TXV>::MIN
         for (int q = 0; q < R; ++q) {
             if (sraw[q] < 0) e.xin &= ~(1u << q);                          // a table entry that points nowhere
             const unsigned off = __umul24(x0 + i0 + q, a.NY) + y;
-#if defined(BDOF_CONV2_WHATIF) && (BDOF_CONV2_WHATIF & 1)
-            e.m1[q] = make_float2(1e-3f * (float)q, 0.f);                 // timing experiment (tools/kbench_conv2.hip): no operand loads
-#else
             e.m1[q] = a.obj.vol[(size_t)max(sraw[q], 0) * a.obj.volNY + yc];
-#endif
             if constexpr (BWD) e.tp[q] = tape_b[off];
             if constexpr (PF) e.pf[q] = a.pfield[off];                   // L2-resident plane shared by all wavefields
         }
@@ -215,9 +189,6 @@ __global__ __launch_bounds__((Conv2Cfg<H, TXV>::THREADS), (Conv2Cfg<H, TXV>::MIN
 #pragma unroll
     for (int q = 0; q < R; ++q) asm volatile("" : "+v"(sraw[q]));           // no use of these moves above the wait
     asm volatile("" : "+v"(yo));
-#ifdef BDOF_CONV2_STAMP
-    unsigned long long st_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, st_t = __builtin_amdgcn_s_memtime();
-#endif
     for (int tile = wg; tile < ntiles; tile += nwg) {
         const TilePos tp_ = tile_pos(tile);
         const int b = tp_.b, x0 = tp_.x0, y0 = tp_.y0;
@@ -231,9 +202,7 @@ __global__ __launch_bounds__((Conv2Cfg<H, TXV>::THREADS), (Conv2Cfg<H, TXV>::MIN
             for (int m = 0; m < MP; ++m)
                 if ((oob >> m) & 1u) A4[(wave + NW * m) * 64 + lane] = pp;
         }
-        CONV2_STAMP(0);          // operand requests, padding patch
         conv_sync();
-        CONV2_STAMP(1);          // barrier: the other waves' DMA pieces
         TapsPtr kt = (TapsPtr)a.taps;
         asm volatile("" : "+s"(kt));
         // pass along y: lanes = 8 windows of 4 outputs along a row, then rows.  forward: o[y] = sum_d K[h+d] f[y-d]
@@ -244,23 +213,14 @@ __global__ __launch_bounds__((Conv2Cfg<H, TXV>::THREADS), (Conv2Cfg<H, TXV>::MIN
             cf win[R + 2 * H], o[R];
 #pragma unroll
             for (int q = 0; q < (R + 2 * H) / 2; ++q) {
-#if defined(BDOF_CONV2_WHATIF) && (BDOF_CONV2_WHATIF & 8)
-                const float4 v = make_float4(1e-3f * (float)(lane + q), 0.5f, (float)w, 1.f);     // timing experiment: no LDS reads in the passes
-#else
                 const float4 v = p[q];
-#endif
                 win[2 * q] = make_float2(v.x, v.y);
                 win[2 * q + 1] = make_float2(v.z, v.w);
             }
-#if defined(BDOF_CONV2_WHATIF) && (BDOF_CONV2_WHATIF & 16)
-            for (int q = 0; q < R; ++q) o[q] = cadd(win[q], win[q + 2 * H]);                       // timing experiment: no tap sums
-#else
             conv_window<BWD, H, R>(win, kt->ky, o);
-#endif
 #pragma unroll
             for (int q = 0; q < R; ++q) M[i * SM + R * w + q] = o[q];
         }
-        CONV2_STAMP(2);          // y pass
         // the epilogue's operands are in registers before the next DMA is queued behind them
 #pragma unroll
         for (int q = 0; q < R; ++q) {
@@ -268,15 +228,12 @@ __global__ __launch_bounds__((Conv2Cfg<H, TXV>::THREADS), (Conv2Cfg<H, TXV>::MIN
             if constexpr (BWD) asm volatile("" : "+v"(cur.tp[q].x), "+v"(cur.tp[q].y));
             if constexpr (PF) asm volatile("" : "+v"(cur.pf[q].x), "+v"(cur.pf[q].y));
         }
-        CONV2_STAMP(3);          // wait for the epilogue's operands
         conv_sync();
-        CONV2_STAMP(4);          // barrier: M complete
         const int next = tile + nwg;
         if (next < ntiles) {
             issue(next);                 // A is free: in flight during the x pass and the epilogue
             request_rows(next);
         }
-        CONV2_STAMP(5);          // DMA issue
         asm volatile("" : "+s"(kt));
         // pass along x (window of R consecutive x for one y), then the pointwise physics
         {
@@ -286,16 +243,8 @@ __global__ __launch_bounds__((Conv2Cfg<H, TXV>::THREADS), (Conv2Cfg<H, TXV>::MIN
             float2* grot_b = BWD ? a.grot + ((size_t)b * a.obj.S + a.zmod) * a.NX * a.NY : nullptr;
             cf win[R + 2 * H];
 #pragma unroll
-#if defined(BDOF_CONV2_WHATIF) && (BDOF_CONV2_WHATIF & 8)
-            for (int q = 0; q < R + 2 * H; ++q) win[q] = make_float2(1e-3f * (float)(lane + q), 0.5f);
-#else
             for (int q = 0; q < R + 2 * H; ++q) win[q] = M[(i0 + q) * SM + j];
-#endif
-#if defined(BDOF_CONV2_WHATIF) && (BDOF_CONV2_WHATIF & 16)
-            for (int q = 0; q < R; ++q) o[q] = cadd(win[q], win[q + 2 * H]);
-#else
             conv_window<BWD, H, R>(win, kt->kx, o);
-#endif
             const int y = y0 + j;
 #pragma unroll
             for (int q = 0; q < R; ++q) {
@@ -307,12 +256,7 @@ __global__ __launch_bounds__((Conv2Cfg<H, TXV>::THREADS), (Conv2Cfg<H, TXV>::MIN
                 cf car = a.carrier;
                 if constexpr (PF) car = cur.pf[q];
                 if constexpr (!BWD) {
-#if defined(BDOF_CONV2_WHATIF) && (BDOF_CONV2_WHATIF & 2)
-                    const cf res = modulate_eps(acc, car, mm);             // timing experiment: no stores (kept alive by a test
-                    if (res.x == 123.456f) out_b[off] = res;               // that practically never passes)
-#else
                     out_b[off] = modulate_eps(acc, car, mm);
-#endif
                 } else {
                     const cf phi = cadd(cur.tp[q], car);
                     const cf tt = cmulc(acc, phi);
@@ -321,16 +265,10 @@ __global__ __launch_bounds__((Conv2Cfg<H, TXV>::THREADS), (Conv2Cfg<H, TXV>::MIN
                 }
             }
         }
-        CONV2_STAMP(6);          // x pass, epilogue, stores issued
         // everything queued before this tile's NS stores has retired: the next halo tile and its table rows
         asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NS) : "memory");
-        CONV2_STAMP(7);          // wait for the next halo tile
 #pragma unroll
         for (int q = 0; q < R; ++q) asm volatile("" : "+v"(sraw[q]));
         asm volatile("" : "+v"(yo));
     }
-#ifdef BDOF_CONV2_STAMP
-    if (tid == 64 * BDOF_CONV2_STAMP)          // -DBDOF_CONV2_STAMP=w: the stamps of wave w
-        for (int k = 0; k < 8; ++k) atomicAdd(&g_conv2_stamp[k], st_acc[k]);
-#endif
 }

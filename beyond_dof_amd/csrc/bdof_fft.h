@@ -21,32 +21,20 @@ __device__ __forceinline__ cf cscale(cf a, float s) { return make_float2(a.x * s
 
 // Transform constants.  float32-rounded twiddle tables and float32(sqrt(1/2)) are the SAME small perturbation of every transform
 // of a multislice stack: their errors add up coherently along hundreds of slices (gradient error at 512 slices 1.61e-5,
-// reconstructed delta against the reference's loop at 256^3 2.1e-5).  Two remedies are built in:
+// reconstructed delta against the reference's loop at 256^3 2.1e-5).  Two remedies, one per kind of kernel (template
+// parameter EX of the transforms below):
 //
-//  * dithered constants (the streaming engine's per-slice kernels, default): the host uploads D = 64 copies of each table in which
-//    entry j is rounded DOWN or UP so that the mean over the copies is the float64 value to ulp / D, slice z runs with copy
-//    z mod D, and sqrt(1/2) arrives per launch the same way (mul_sqrt_half's `sq`).  Plain float32 arithmetic, no extra
-//    instruction — and the table errors of neighbouring slices cancel instead of adding up: gradient error at 512 slices 6.0e-6,
-//    reconstructed delta 6.6e-6 (G18) / 3.4e-6 (G15) / 7.4e-6 (G19).  BDOF_TW_DITHER=0 in the environment switches it off.
-//  * hi + lo pairs (EX = true: table[N + j] = the float32 rounding error of table[j], sqrt(1/2) likewise): every product with a
-//    constant is exact to 1e-15 for 2 more FMAs — 6.1e-6 / 5.8e-6 / 3.7e-6 / 7.0e-6 on the same four numbers for +3.2 ms (4.8 %)
-//    of the cfg3 step.  The kernels that run once per step (detector plane, loss) use it; -DBDOF_EXACT_TRANSFORMS builds the
-//    per-slice kernels with it too (round 3's first default, kept for comparison).
-#if defined(BDOF_EXACT_TWIDDLES) || defined(BDOF_FAST_ADJOINT) || defined(BDOF_FAST_FORWARD)
-#error "BDOF_EXACT_TWIDDLES / BDOF_FAST_ADJOINT / BDOF_FAST_FORWARD (rounds 2-3) no longer exist: the per-slice kernels run with dithered constants; -DBDOF_EXACT_TRANSFORMS builds them with hi + lo tables"
-#endif
-#ifndef BDOF_EXACT_CONSTANTS
-#define BDOF_EXACT_CONSTANTS 1          // sqrt(1/2) as a hi + lo pair wherever no dithered value is handed in (mul_sqrt_half)
-#endif
-#ifdef BDOF_EXACT_TRANSFORMS
-constexpr bool BDOF_EX_ALL = true;
-#else
-constexpr bool BDOF_EX_ALL = false;
-#endif
-constexpr bool BDOF_EX_ADJ = BDOF_EX_ALL;       // adjoint sweep (A', B')
-constexpr bool BDOF_EX_FWD_A = BDOF_EX_ALL;     // forward sweep
-constexpr bool BDOF_EX_FWD_B = BDOF_EX_ALL;
-constexpr bool BDOF_EX_DET = true;              // once per step: detector plane, loss, seed
+//  * EX = false, dithered constants (the per-slice kernels of the streaming engine): the host uploads D = 64 copies of each
+//    table in which entry j is rounded DOWN or UP so that the mean over the copies is the float64 value to ulp / D, slice z
+//    runs with copy z mod D, and sqrt(1/2) arrives per launch the same way (mul_sqrt_half's `sq`).  Plain float32 arithmetic,
+//    no extra instruction — and the table errors of neighbouring slices cancel instead of adding up: gradient error at 512
+//    slices 6.0e-6, reconstructed delta 6.6e-6 (G18) / 3.4e-6 (G15) / 7.4e-6 (G19).  BDOF_TW_DITHER=0 in the environment
+//    switches the dither off.
+//  * EX = true, hi + lo pairs (the kernels that run once per step: detector plane, loss, seed): table[N + j] = the float32
+//    rounding error of table[j], sqrt(1/2) likewise; every product with a constant is exact to 1e-15 for 2 more FMAs.  In
+//    the per-slice kernels it buys nothing over the dither (6.1e-6 / 5.8e-6 / 3.7e-6 / 7.0e-6 on the same four numbers) and
+//    costs 4.8 % of the cfg3 step (MEASUREMENTS.md).
+
 // u * (w + wl), the twiddle conjugated for the inverse transform
 template <int SIGN, bool EX> __device__ __forceinline__ cf tw_mul(cf u, cf w, cf wl) {
     if (SIGN > 0) { w.y = -w.y; wl.y = -wl.y; }
@@ -83,21 +71,12 @@ template <int SIGN> __device__ __forceinline__ void dft4(cf& a0, cf& a1, cf& a2,
 //   sq != nullptr (the per-slice kernels of the streaming engine): the constant of THIS launch comes from the host, sq[0] for the
 //      transforms instantiated with ROUND 1 and sq[1] for those with ROUND 2 — the host walks the two neighbouring float32 values
 //      over the slices so that their mean is sqrt(1/2) (dithered constants, above), at no cost in instructions;
-//   ROUND 0, or BDOF_EXACT_CONSTANTS (the default) without sq: hi + lo pair, one more FMA per product, exact to 1e-15;
-//   without BDOF_EXACT_CONSTANTS (-UBDOF_EXACT_CONSTANTS is not offered; round 2's scheme, kept for the record): ROUND 1 = the
-//      nearest float32 (rounds DOWN), ROUND 2 = its upper neighbour; a kernel whose propagation step runs four line transforms uses
-//      2 in one of them and 1 in the other three: (3 x -1.71 + 6.72)e-8 — the defects cancel to a quarter.
+//   ROUND 0, or no sq: hi + lo pair, one more FMA per product, exact to 1e-15.
 template <int ROUND_> __device__ __forceinline__ float mul_sqrt_half(float t, const float* sq = nullptr) {
-    if constexpr (ROUND_ == 0) return fmaf(t, 0.70710678118654752f, t * 1.2101617e-8f);
-    else if (sq) return t * sq[ROUND_ - 1];
-    else {
-#ifdef BDOF_EXACT_CONSTANTS
-        return fmaf(t, 0.70710678118654752f, t * 1.2101617e-8f);
-#else
-        if constexpr (ROUND_ == 1) return t * 0.70710678118654752f;
-        else return t * 0.70710682868957520f;
-#endif
+    if constexpr (ROUND_ != 0) {
+        if (sq) return t * sq[ROUND_ - 1];
     }
+    return fmaf(t, 0.70710678118654752f, t * 1.2101617e-8f);
 }
 
 template <int SIGN, int ROUND = 1>
@@ -150,7 +129,7 @@ template <int N> struct FftTw {
     // lds_mid: LDS_CNT slots; lds_tail: 7*N/8 slots laid out [m-1][j] = table[m*j] (also the tail stage's twiddles):
     // one cooperative fill, one barrier, and the per-lane last-stage factors are read back from LDS instead of being
     // gathered from global memory by every wave (kernel start-up is amortised over only ~2 tiles per workgroup).
-    template <bool LO = BDOF_EX_ALL>
+    template <bool LO = false>
     __device__ __forceinline__ void load(const cf* __restrict__ table, int tid, cf* lds_mid, cf* lds_tail) {
         constexpr int T = N / 8;
         for (int e = threadIdx.x; e < 7 * T; e += blockDim.x) {
@@ -198,7 +177,7 @@ template <int N, int R, class L> __device__ __forceinline__ void stage_read(cf (
 }
 
 // WHICH: 0 = first stage (no twiddles), 1 / 2 = middle stage (LDS table), 3 = last stage (registers)
-template <int N, int SIGN, int R, int PP, int WHICH, int ROUND = 1, bool EX = BDOF_EX_ALL>
+template <int N, int SIGN, int R, int PP, int WHICH, int ROUND = 1, bool EX = false>
 __device__ __forceinline__ void stage_compute(cf (&u)[8], const FftTw<N>& tw, int tid) {
     constexpr int T = N / 8, NB = 8 / R;
     typedef FftTw<N> TW;
@@ -233,7 +212,7 @@ template <int N, int R, int PP, class L> __device__ __forceinline__ void stage_w
 // Full transform of one line.  u[m] <-> position tid + m*T on entry and on exit.
 // Unnormalised; SIGN = -1 forward DFT, +1 inverse.  lds.sync_w2r() orders a stage's stores
 // before the next stage's loads; lds.sync_r2w() orders loads before the stores that reuse the image.
-template <int N, int SIGN, int ROUND = 1, bool EX = BDOF_EX_ALL, class L>
+template <int N, int SIGN, int ROUND = 1, bool EX = false, class L>
 __device__ __forceinline__ void line_fft(cf (&u)[8], const FftTw<N>& tw, int tid, L& lds) {
     typedef FftPlan<N> P;
     stage_compute<N, SIGN, P::R0, 1, 0, ROUND, EX>(u, tw, tid);
@@ -260,7 +239,7 @@ __device__ __forceinline__ void line_fft(cf (&u)[8], const FftTw<N>& tw, int tid
 
 // All stages but the last; the last stage's inputs are left in the line's LDS image (no sync after the
 // final store: the caller's workgroup barrier orders it before the transposed readers).
-template <int N, int SIGN, int ROUND = 1, bool EX = BDOF_EX_ALL, class L>
+template <int N, int SIGN, int ROUND = 1, bool EX = false, class L>
 __device__ __forceinline__ void line_fft_partial(cf (&u)[8], const FftTw<N>& tw, int tid, L& lds) {
     typedef FftPlan<N> P;
     stage_compute<N, SIGN, P::R0, 1, 0, ROUND, EX>(u, tw, tid);
@@ -284,7 +263,7 @@ __device__ __forceinline__ void line_fft_partial(cf (&u)[8], const FftTw<N>& tw,
 
 // The last stage (radix 8, p = N/8) for butterfly j of a line whose image is `lds`; `tail` is the LDS copy
 // [m-1][j] of the twiddles exp(-2 pi i m j / N) (fill_tail_table).  On exit u[q] is the output at position j + q*N/8.
-template <int N, int SIGN, int ROUND = 1, bool EX = BDOF_EX_ALL, class L>
+template <int N, int SIGN, int ROUND = 1, bool EX = false, class L>
 __device__ __forceinline__ void last_stage(cf (&u)[8], int j, L& lds, const cf* tail, const float* sq = nullptr) {
     constexpr int T = N / 8;
     cf w[7], wl[7];

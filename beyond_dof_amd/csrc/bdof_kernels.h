@@ -56,7 +56,7 @@ template <int T> struct RowLds {
 //   dst[(pos) * ld + r] = scale * out(row r, position pos),  pos = j + q*T
 // Called by all threads between two workgroup barriers.
 // ---------------------------------------------------------------------------------------------
-template <int N, int SIGN, int ROUND = 1, bool EX = BDOF_EX_ALL>
+template <int N, int SIGN, int ROUND = 1, bool EX = false>
 __device__ __forceinline__ void transposed_tail(cf* smem, cf* __restrict__ dst, size_t ld, float scale, const cf* tail, const float* sq = nullptr) {
     typedef RowCfg<N> C;
 #pragma nounroll
@@ -238,7 +238,7 @@ __global__ __launch_bounds__(BDOF_THREADS, RowCfg<NY>::MIN_WAVES) void k_row_fwd
     typedef RowCfg<NY> C;
     __shared__ cf smem[C::LDS_CF];
     const int tid = threadIdx.x % C::T, rl = threadIdx.x / C::T;
-    constexpr bool EX = BDOF_EX_FWD_A;
+    constexpr bool EX = false;            // per-slice kernel: dithered transform constants (bdof_fft.h)
     __shared__ cf smem_tw[FftTw<NY>::LDS_CNT * (EX ? 2 : 1)];
     FftTw<NY> tw;
     __shared__ cf smem_tail[7 * C::T * (EX ? 2 : 1)];
@@ -318,8 +318,8 @@ struct RowPropArgs {
     float sq[2];     // sqrt(1/2) of this launch (RowFwdArgs)
 };
 
-// EX: exact transform constants (hi + lo twiddles, bdof_fft.h) — the instance the adjoint sweep launches
-template <int NX, bool EX = BDOF_EX_ALL>
+// EX: hi + lo transform constants (bdof_fft.h).  The library launches EX = false (dithered constants, like every per-slice kernel)
+template <int NX, bool EX = false>
 __global__ __launch_bounds__(BDOF_THREADS, RowCfg<NX>::MIN_WAVES) void k_row_prop(RowPropArgs a) {
     typedef RowCfg<NX> C;
     __shared__ cf smem[C::LDS_CF];
@@ -487,7 +487,7 @@ __global__ __launch_bounds__(BDOF_THREADS, RowCfg<N>::MIN_WAVES) void k_row_loss
     constexpr int S1 = FAR ? -1 : +1;     // direction of the first transform; the second is the opposite
     __shared__ cf smem[C::LDS_CF];
     const int tid = threadIdx.x % C::T, rl = threadIdx.x / C::T;
-    constexpr bool EX = BDOF_EX_DET;
+    constexpr bool EX = true;             // once per step: hi + lo transform constants (bdof_fft.h)
     __shared__ cf smem_tw[FftTw<N>::LDS_CNT * (EX ? 2 : 1)];
     FftTw<N> tw;
     __shared__ cf smem_tail[7 * C::T * (EX ? 2 : 1)];
@@ -639,17 +639,11 @@ __global__ __launch_bounds__(BDOF_THREADS, RowCfg<NY>::MIN_WAVES) void k_row_bwd
     typedef RowCfg<NY> C;
     __shared__ cf smem[C::LDS_CF];
     const int tid = threadIdx.x % C::T, rl = threadIdx.x / C::T;
-    // the transforms of the ADJOINT field run with exact constants (EX, bdof_fft.h); re-deriving phi from the tape does not
-    constexpr bool EX = BDOF_EX_ADJ;
-    // phi_z is re-derived from the tape with plain float32 tables: it is ONE transform of the scattered part (no chain for a
-    // table error to add up along, and phi = carrier + scattered part enters the gradient only through conj(phi) G), so the
-    // exact constants of A_z's own inverse transform buy nothing here and cost 2.4 us per launch (1.2 ms per cfg3 step)
-    constexpr bool EXP = false;
-    constexpr bool LO = EX || EXP;
-    __shared__ cf smem_tw[FftTw<NY>::LDS_CNT * (LO ? 2 : 1)];
+    constexpr bool EX = false;            // per-slice kernel: dithered transform constants (bdof_fft.h)
+    __shared__ cf smem_tw[FftTw<NY>::LDS_CNT * (EX ? 2 : 1)];
     FftTw<NY> tw;
-    __shared__ cf smem_tail[7 * C::T * (LO ? 2 : 1)];
-    tw.template load<LO>(a.twiddle, tid, smem_tw, smem_tail);
+    __shared__ cf smem_tail[7 * C::T * (EX ? 2 : 1)];
+    tw.template load<EX>(a.twiddle, tid, smem_tw, smem_tail);
     tw.sq = a.sq;
     const int ntiles = a.B * a.NX / C::TILE;
     for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
@@ -677,7 +671,7 @@ __global__ __launch_bounds__(BDOF_THREADS, RowCfg<NY>::MIN_WAVES) void k_row_bwd
 #pragma unroll
                 for (int m = 0; m < 8; ++m) pc[m] = a.pz[(size_t)x * NY + tid + m * C::T];
             }
-            if constexpr (HIST == 1 || HIST == 3) line_fft<NY, +1, 1, EXP>(p, tw, tid, lds);   // psi_hat_z -> psi_z (scattered part)
+            if constexpr (HIST == 1 || HIST == 3) line_fft<NY, +1, 1, EX>(p, tw, tid, lds);   // psi_hat_z -> psi_z (scattered part)
             if constexpr (HIST == 3) {
 #pragma unroll
                 for (int m = 0; m < 8; ++m) p[m] = cscale(p[m], a.tape_scale);
@@ -1827,7 +1821,7 @@ __global__ __launch_bounds__(BDOF_THREADS, RowCfg<NY>::MIN_WAVES) void k_row_rea
     typedef RowCfg<NY> C;
     __shared__ cf smem[C::LDS_CF];
     const int tid = threadIdx.x % C::T, rl = threadIdx.x / C::T;
-    constexpr bool EX = BDOF_EX_DET;
+    constexpr bool EX = true;             // once per step: hi + lo transform constants (bdof_fft.h)
     __shared__ cf smem_tw[FftTw<NY>::LDS_CNT * (EX ? 2 : 1)];
     FftTw<NY> tw;
     __shared__ cf smem_tail[7 * C::T * (EX ? 2 : 1)];

@@ -12,15 +12,9 @@
 #pragma once
 #include "bdof_generic.h"
 
-// Exact twiddles (hi + lo pairs) in the ADJOINT passes of this kernel (what -DBDOF_EXACT_TRANSFORMS gives the streaming kernels): measured in
-// round 3 on far-field ptychography (golden vector G17's configuration, 64^2 x 64 slices): gradient error 1.86e-6 -> 1.70e-6 for
-// +2.3 % (72^2) / +3.3 % (64^2) kernel time — the float32 rounding of the transforms themselves is the floor here, not the
-// tables (tools/precision_model.py).  Off by default; -DBDOF_RES_EXACT_ADJOINT switches it on.
-#ifdef BDOF_RES_EXACT_ADJOINT
-constexpr bool BDOF_EX_RES = true;
-#else
-constexpr bool BDOF_EX_RES = false;
-#endif
+// The passes use plain float32 twiddles.  Hi + lo pairs (bdof_fft.h) in the adjoint passes took the gradient error of far-field
+// ptychography (G17's configuration, 64^2 x 64 slices) only from 1.86e-6 to 1.70e-6 for +2-3 % kernel time: the float32
+// rounding of the transforms themselves is the floor here, not the tables (tools/precision_model.py).
 
 template <int N> struct ResPlan;      // radices of the Stockham passes of one line, and the workgroup size
 template <> struct ResPlan<32> { static constexpr int n = 2, R0 = 8, R1 = 4, R2 = 1, T = 64, WPE = 2; static constexpr bool FUSE = true; };
@@ -149,9 +143,7 @@ struct EpiNone {
     __device__ __forceinline__ cf post(int, int, int, int, cf v) { return v; }
 };
 
-// EX: exact transform constants — the twiddle table's lo parts (tw[N + j], bdof_fft.h) are multiplied in as well; the passes of
-// the ADJOINT sweep run with it (the gradient's error is made there, the forward sweep rides on its carrier).
-template <int N, int R, int NS, int SIGN, bool ALONG_Y, int T, bool EX = false, class Epi>
+template <int N, int R, int NS, int SIGN, bool ALONG_Y, int T, class Epi>
 __device__ __forceinline__ void res_pass(cf* f, const cf* tw, int tid, Epi& epi) {
     // every index below is invariant across slices: without this the compiler hoists the address math of all 16 passes
     // out of the slice loop and keeps it in registers (250+ VGPRs, spills).  Recomputing it per pass is a few VALU ops.
@@ -179,7 +171,7 @@ __device__ __forceinline__ void res_pass(cf* f, const cf* tw, int tid, Epi& epi)
 #pragma unroll
                 for (int m = 1; m < R; ++m) {
                     const int ti = k * m * (N / (NS * R));
-                    u[c][m] = tw_mul<SIGN, EX>(u[c][m], tw[ti], tw[(EX ? N : 0) + ti]);
+                    u[c][m] = tw_mul<SIGN, false>(u[c][m], tw[ti], tw[ti]);
                 }
             }
             res_dft<R, SIGN, 0>(u[c]);
@@ -203,7 +195,7 @@ __device__ __forceinline__ void res_pass(cf* f, const cf* tw, int tid, Epi& epi)
 // Wave-local Stockham pass: lane (li, j) of wave w holds butterfly j of line w * LPW + li.  In place without a barrier: every
 // lane of the wave has issued its reads before any lane's write (one instruction stream), and only this wave touches
 // these lines while the line direction does not change.
-template <int N, int R, int NS, int SIGN, bool ALONG_Y, int L, int LPW, bool EX = false, class Epi>
+template <int N, int R, int NS, int SIGN, bool ALONG_Y, int L, int LPW, class Epi>
 __device__ __forceinline__ void res_wpass(cf* f, const cf* tw, int tid, Epi& epi) {
     asm volatile("" : "+v"(tid));
     constexpr int P = N | 1, ES = ALONG_Y ? 1 : P, NBL = N / R;
@@ -226,7 +218,7 @@ __device__ __forceinline__ void res_wpass(cf* f, const cf* tw, int tid, Epi& epi
 #pragma unroll
             for (int m = 1; m < R; ++m) {
                 const int ti = k * m * (N / (NS * R));
-                u[m] = tw_mul<SIGN, EX>(u[m], tw[ti], tw[(EX ? N : 0) + ti]);
+                u[m] = tw_mul<SIGN, false>(u[m], tw[ti], tw[ti]);
             }
         }
         res_dft<R, SIGN, 0>(u);
@@ -244,14 +236,14 @@ __device__ __forceinline__ void res_wpass(cf* f, const cf* tw, int tid, Epi& epi
 }
 
 // both passes of every line of one direction (two-pass plans only); no workgroup barrier inside
-template <int N, int SIGN, bool ALONG_Y, bool EX = false, class Epi> __device__ __forceinline__ void res_wlines(cf* f, const cf* tw, int tid, Epi& epi) {
+template <int N, int SIGN, bool ALONG_Y, class Epi> __device__ __forceinline__ void res_wlines(cf* f, const cf* tw, int tid, Epi& epi) {
     typedef ResPlan<N> Pl;
     static_assert(Pl::n == 2, "wave-local lines are written for two-pass plans");
     constexpr int L = ResWave<N>::L, LPW = ResWave<N>::LPW;
     static_assert(L >= N / Pl::R0 && L >= N / Pl::R1 && L * LPW <= 64, "lanes per line");
     EpiNone none;
-    res_wpass<N, Pl::R0, 1, SIGN, ALONG_Y, L, LPW, EX>(f, tw, tid, none);
-    res_wpass<N, Pl::R1, Pl::R0, SIGN, ALONG_Y, L, LPW, EX>(f, tw, tid, epi);
+    res_wpass<N, Pl::R0, 1, SIGN, ALONG_Y, L, LPW>(f, tw, tid, none);
+    res_wpass<N, Pl::R1, Pl::R0, SIGN, ALONG_Y, L, LPW>(f, tw, tid, epi);
 }
 
 // radix and butterflies per thread of the LAST pass of a line (the one that carries an epilogue)
@@ -261,36 +253,36 @@ template <int N, int T> struct ResLast {
     static constexpr int CNT = (N * (N / R) + T - 1) / T;
 };
 
-template <int N, int T, int SIGN, bool ALONG_Y, bool EX = false, class Epi>
+template <int N, int T, int SIGN, bool ALONG_Y, class Epi>
 __device__ __forceinline__ void res_lines(cf* f, const cf* tw, int tid, Epi& epi) {
     typedef ResPlan<N> Pl;
     EpiNone none;
-    res_pass<N, Pl::R0, 1, SIGN, ALONG_Y, T, EX>(f, tw, tid, none);
+    res_pass<N, Pl::R0, 1, SIGN, ALONG_Y, T>(f, tw, tid, none);
     if constexpr (Pl::n > 2) {
-        res_pass<N, Pl::R1, Pl::R0, SIGN, ALONG_Y, T, EX>(f, tw, tid, none);
-        res_pass<N, Pl::R2, Pl::R0 * Pl::R1, SIGN, ALONG_Y, T, EX>(f, tw, tid, epi);
+        res_pass<N, Pl::R1, Pl::R0, SIGN, ALONG_Y, T>(f, tw, tid, none);
+        res_pass<N, Pl::R2, Pl::R0 * Pl::R1, SIGN, ALONG_Y, T>(f, tw, tid, epi);
     } else {
-        res_pass<N, Pl::R1, Pl::R0, SIGN, ALONG_Y, T, EX>(f, tw, tid, epi);
+        res_pass<N, Pl::R1, Pl::R0, SIGN, ALONG_Y, T>(f, tw, tid, epi);
     }
 }
 
 // un-normalised 2-D DFT of the field image f[x * P + y], SIGN = -1 forward, +1 inverse; `epi` rides on the last pass
-template <int N, int T, int SIGN, bool EX = false, class Epi> __device__ __forceinline__ void res_fft2(cf* f, const cf* tw, int tid, Epi& epi) {
+template <int N, int T, int SIGN, class Epi> __device__ __forceinline__ void res_fft2(cf* f, const cf* tw, int tid, Epi& epi) {
     EpiNone none;
     if constexpr (ResWave<N>::L > 0) {
         static_assert(T >= 64 * ((N + ResWave<N>::LPW - 1) / ResWave<N>::LPW), "not enough waves for the lines");
-        res_wlines<N, SIGN, true, EX>(f, tw, tid, none);
+        res_wlines<N, SIGN, true>(f, tw, tid, none);
         res_sync();
-        res_wlines<N, SIGN, false, EX>(f, tw, tid, epi);
+        res_wlines<N, SIGN, false>(f, tw, tid, epi);
         res_sync();
     } else {
-        res_lines<N, T, SIGN, true, EX>(f, tw, tid, none);
-        res_lines<N, T, SIGN, false, EX>(f, tw, tid, epi);
+        res_lines<N, T, SIGN, true>(f, tw, tid, none);
+        res_lines<N, T, SIGN, false>(f, tw, tid, epi);
     }
 }
-template <int N, int T, int SIGN, bool EX = false> __device__ __forceinline__ void res_fft2(cf* f, const cf* tw, int tid) {
+template <int N, int T, int SIGN> __device__ __forceinline__ void res_fft2(cf* f, const cf* tw, int tid) {
     EpiNone none;
-    res_fft2<N, T, SIGN, EX>(f, tw, tid, none);
+    res_fft2<N, T, SIGN>(f, tw, tid, none);
 }
 
 struct ResArgs {
@@ -366,31 +358,30 @@ template <int N, int T, bool CONJ, class Epi, class Mid>
 __device__ __forceinline__ void res_prop(cf* f, const cf* hT, const cf* tw, int tid, Epi& epi, Mid&& mid) {
     EpiH<N, T, CONJ> eh;
     eh.hT = hT;
-    constexpr bool EX = CONJ && BDOF_EX_RES;        // the adjoint step's transforms are exact (bdof_fft.h)
     if constexpr (ResWave<N>::L > 0) {
         // wave-local lines: the inverse transform runs x first, so that a column goes forward, x h, and back in one wave
         static_assert(!Epi::active, "the wave-local form carries no point-wise epilogue");
         EpiNone none;
-        res_wlines<N, -1, true, EX>(f, tw, tid, none);
+        res_wlines<N, -1, true>(f, tw, tid, none);
         res_sync();
-        res_wlines<N, -1, false, EX>(f, tw, tid, eh);
-        res_wlines<N, +1, false, EX>(f, tw, tid, none);
+        res_wlines<N, -1, false>(f, tw, tid, eh);
+        res_wlines<N, +1, false>(f, tw, tid, none);
         res_sync();
         {   // the last line set, its two passes written out so that `mid` sits before the lighter (radix R1) one
             typedef ResPlan<N> Pl;
             constexpr int L = ResWave<N>::L, LPW = ResWave<N>::LPW;
-            res_wpass<N, Pl::R0, 1, +1, true, L, LPW, EX>(f, tw, tid, none);
+            res_wpass<N, Pl::R0, 1, +1, true, L, LPW>(f, tw, tid, none);
             mid();
-            res_wpass<N, Pl::R1, Pl::R0, +1, true, L, LPW, EX>(f, tw, tid, none);
+            res_wpass<N, Pl::R1, Pl::R0, +1, true, L, LPW>(f, tw, tid, none);
         }
         res_sync();
     } else {
-        res_fft2<N, T, -1, EX>(f, tw, tid, eh);
+        res_fft2<N, T, -1>(f, tw, tid, eh);
         res_epi_prefetch<N, T>(tid, epi);
         EpiNone none;
-        res_lines<N, T, +1, true, EX>(f, tw, tid, none);
+        res_lines<N, T, +1, true>(f, tw, tid, none);
         mid();
-        res_lines<N, T, +1, false, EX>(f, tw, tid, epi);
+        res_lines<N, T, +1, false>(f, tw, tid, epi);
     }
 }
 template <int N, int T, bool CONJ, class Epi>
@@ -682,7 +673,7 @@ __global__ __launch_bounds__(T, WPE) void k_resident(ResArgs a) {
             Pipe::load_field(tape0 + (size_t)(a.S - 1) * a.tape_stride, tid, t);
         }
         if (a.det_mode == BDOF_DET_NEAR) res_prop<N, T, true>(f, a.hdetT, tw, tid);
-        else if (far) res_fft2<N, T, +1, BDOF_EX_RES>(f, tw, tid);     // F^H = un-normalised inverse
+        else if (far) res_fft2<N, T, +1>(f, tw, tid);     // F^H = un-normalised inverse
         for (int z = a.S - 1; z >= 0; --z) {
             const long long r2 = Pipe::row_of(a, b, z - 2, tid);
             const bool prop_after = z < a.S - 1 || (a.tf_all && !far);

@@ -25,28 +25,24 @@ class MultisliceEngine(object):
     """One wavefield geometry (NY x NX x S) on one GPU."""
 
     def __init__(self, ny, nx, n_slice, batch_max, with_grad=True, device=0, stream=None, force_generic=False, engine='auto',
-                 recompute=None, no_grot=False, adjoint64=None):
+                 recompute=False, no_grot=False, adjoint64=False):
         """Engines (include/bdof.h, bdof_configure): powers of two in 64..1024 run on the fused streaming kernels; small
         square fields (32..128, e.g. the 72 x 72 ptychography probe) on the LDS-resident kernel when there is no fused plan
         or the batch is large; every other size on the generic engine (rocFFT).  engine='generic' (= force_generic=True),
         'streaming' (never resident) or 'resident' (resident for every batch size) pin the choice for cross-checks.
-        adjoint64=True (env BDOF_ADJOINT64=1): the adjoint sweep in float64 (bdof_configure flag 64; generic engine) — the
+        adjoint64=True: the adjoint sweep in float64 (bdof_configure flag 64; generic engine) — the
         accuracy option for reconstructions that must follow the reference's float64 loop voxel by voxel."""
         if engine not in ('auto', 'generic', 'streaming', 'resident'):
             raise ValueError('engine must be auto, generic, streaming or resident')
         force_generic = force_generic or engine == 'generic'
-        if recompute is None:
-            recompute = bool(int(os.environ.get('BDOF_RECOMPUTE', '0')))
         self.recompute = bool(recompute)
-        if adjoint64 is None:
-            adjoint64 = bool(int(os.environ.get('BDOF_ADJOINT64', '0')))
         self.adjoint64 = bool(adjoint64) and bool(with_grad)
         self.ctx = _lib.Context(device, stream)
         self.lib = self.ctx.lib
         self.h = self.ctx.handle
         self.ny, self.nx, self.n_slice, self.batch_max = int(ny), int(nx), int(n_slice), int(batch_max)
         self.with_grad = bool(with_grad)
-        flags = (_lib.CFG_GRAD if with_grad else 0) | (_lib.CFG_GENERIC if (force_generic or os.environ.get('BDOF_FORCE_GENERIC')) else 0) \
+        flags = (_lib.CFG_GRAD if with_grad else 0) | (_lib.CFG_GENERIC if force_generic else 0) \
             | (_lib.CFG_NO_RESIDENT if engine == 'streaming' else 0) | (_lib.CFG_ALWAYS_RESIDENT if engine == 'resident' else 0) \
             | (_lib.CFG_RECOMPUTE if self.recompute else 0) | (_lib.CFG_NO_GROT if no_grot else 0) | (_lib.CFG_ADJOINT64 if self.adjoint64 else 0)
         self.ctx.check(self.lib.bdof_configure(self.h, self.ny, self.nx, self.n_slice, self.batch_max, flags))
@@ -254,7 +250,7 @@ class MultisliceEngine(object):
         steps (probe_type='optimizable') must not move it: the solvers switch the splitting off for that case
         (residual_split = False) before they upload."""
         self.meas_ref = 0.0
-        if a0 != 0 and self.det_mode != _lib.DET_FAR and self.residual_split and not os.environ.get('BDOF_NO_RESIDUAL_SPLIT'):
+        if a0 != 0 and self.det_mode != _lib.DET_FAR and self.residual_split:
             self.meas_ref = abs(a0)
         self.ctx.check(self.lib.bdof_set_meas_mode(self.h, 1 if self.meas_ref else 0))
 

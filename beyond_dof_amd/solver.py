@@ -22,7 +22,7 @@ from . import _lib
 from ._lib import DeviceBuffer
 from . import util
 from .comm import PseudoComm
-from .engine import MultisliceEngine
+from .engine import MultisliceEngine, RESIDENT_SIZES
 
 
 class _VolumeSolver(object):
@@ -333,7 +333,7 @@ class _VolumeSolver(object):
 class FullfieldSolver(_VolumeSolver):
     def __init__(self, dim_y, dim_x, dim_z, n_theta, minibatch_size, energy_ev, psize_cm, free_prop_cm=None,
                  probe_real=None, probe_imag=None, variant='numpy_skip_last', comm=None, device=0, stream=None,
-                 coord_ls=None, propagator='fft', kernel_size=17, recompute=None, rotation='nearest', theta=None, adjoint64=None,
+                 coord_ls=None, propagator='fft', kernel_size=17, recompute=False, rotation='nearest', theta=None, adjoint64=None,
                  detector_kernel='TF'):
         """propagator='fft': the transfer-function step of np_funcs.py (north-star path); 'conv': the truncated real-space
         kernel of propagation.py, what cnn_propagator/fullfield.py:87,102 calls (kernel_size taps per axis).
@@ -530,7 +530,9 @@ class PtychoSolver(_VolumeSolver):
 
     def __init__(self, obj_size, probe_size, probe_pos, n_theta, minibatch_size, energy_ev, psize_cm, probe_real, probe_imag,
                  variant='numpy_skip_last', comm=None, device=0, stream=None, coord_ls=None, propagator='fft', kernel_size=17,
-                 adjoint64=None):
+                 adjoint64=None, engine=None):
+        """engine: None picks the LDS-resident engine for small square probes (below) and the automatic choice otherwise; 'auto',
+        'generic', 'streaming' or 'resident' go to MultisliceEngine(engine=...) as they are."""
         self.conv = propagator == 'conv'
         self.dim_y, self.dim_x, self.dim_z = [int(s) for s in obj_size]
         self.py, self.px = int(probe_size[0]), int(probe_size[1])
@@ -540,10 +542,9 @@ class PtychoSolver(_VolumeSolver):
         self.half = (np.array(probe_size) / 2).astype('int')            # ptychography.py:138
         # small square probes: the LDS-resident engine (one launch per minibatch) also for the minibatches of ~20 positions the
         # drivers use, where the automatic choice would take the launch-bound streaming kernels for 64^2 / 128^2
-        from .engine import RESIDENT_SIZES
-        pin = 'resident' if (self.py == self.px and self.py in RESIDENT_SIZES and not self.conv
-                             and not os.environ.get('BDOF_NO_RESIDENT_PIN')) else 'auto'
-        self.eng = MultisliceEngine(self.py, self.px, self.dim_z, self.mb, with_grad=True, device=device, stream=stream, engine=pin,
+        if engine is None:
+            engine = 'resident' if self.py == self.px and self.py in RESIDENT_SIZES and not self.conv else 'auto'
+        self.eng = MultisliceEngine(self.py, self.px, self.dim_z, self.mb, with_grad=True, device=device, stream=stream, engine=engine,
                                     adjoint64=adjoint64 is True and not self.conv)
         self.ctx = self.eng.ctx
         self.eng.set_physics(energy_ev, psize_cm, 'inf', variant=variant)   # free_prop_cm='inf', ptychography.py:76

@@ -317,8 +317,8 @@ def test_reconstruct_fullfield_vs_the_reference_loop_at_cfg2_size(tmp_path, monk
     stats = (np.abs(d - g['delta_sub']).max() / lr, rel(d, g['delta_sub']), np.abs(b - g['beta_sub']).max() / lr, rel(b, g['beta_sub']))
     print('G18 stats' if not noise else 'G19 stats', adjoint_precision, stats)
     # measured (round 3, dithered transform constants — the default): G18 (noise-free data) delta 6.6e-6, beta 4.3e-5; G19 (2 % noise)
-    # delta 7.4e-6, beta 2.7e-5 — both inside the north star's 1e-5 (hi + lo tables in every transform, -DBDOF_EXACT_TRANSFORMS:
-    # 5.8e-6 / 7.0e-6; one plain table, BDOF_TW_DITHER=0: 2.1e-5 / 1.68e-5).  Round 4 (dithered transfer function): 2.0e-6 /
+    # delta 7.4e-6, beta 2.7e-5 — both inside the north star's 1e-5 (hi + lo tables in every transform, a build option
+    # until round 4: 5.8e-6 / 7.0e-6; one plain table, BDOF_TW_DITHER=0: 2.1e-5 / 1.68e-5).  Round 4 (dithered transfer function): 2.0e-6 /
     # 4.2e-6; adjoint_precision='first-step' (the first minibatch of each epoch through bdof_loss_grad_tf_f64) is offered as well
     assert stats[0] <= 0.05 and stats[1] <= 1e-5 and stats[3] <= 1e-4, stats
 

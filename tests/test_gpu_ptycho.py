@@ -27,20 +27,17 @@ def _setup(psz=(64, 64)):
     return rng, n, n_theta, psz, pos, od, ob, coords, prr, pii
 
 
-@pytest.mark.parametrize('psz,force_resident', [((64, 64), False), ((64, 64), True), ((72, 72), False), ((60, 60), False)],
+# engine=None: PtychoSolver's own choice (the resident engine where it exists); 'auto' un-pins it (streaming for 64^2)
+@pytest.mark.parametrize('psz,engine', [((64, 64), 'auto'), ((64, 64), 'resident'), ((72, 72), None), ((60, 60), None)],
                          ids=['64-streaming', '64-resident', '72-resident', '60-rocfft'])
-def test_ptycho_forward_and_gradient_vs_oracle(psz, force_resident, monkeypatch):
+def test_ptycho_forward_and_gradient_vs_oracle(psz, engine):
     """Rotation table + per-position windows (zero padding beyond the volume) through each of the three device engines."""
     import __graft_entry__ as entry
     entry.build()
     from beyond_dof_amd.solver import PtychoSolver
-    if force_resident:
-        monkeypatch.setenv('BDOF_FORCE_RESIDENT', '1')
-    elif psz == (64, 64):
-        monkeypatch.setenv('BDOF_NO_RESIDENT_PIN', '1')      # PtychoSolver pins the resident engine where it exists: not here
     rng, n, n_theta, psz, pos, od, ob, coords, prr, pii = _setup(psz)
     mb = 6
-    s = PtychoSolver((n, n, n), psz, pos, n_theta, mb, 5000., 1e-7, prr, pii, coord_ls=coords)
+    s = PtychoSolver((n, n, n), psz, pos, n_theta, mb, 5000., 1e-7, prr, pii, coord_ls=coords, engine=engine)
     s.set_volume(od, ob)
     sel = np.array([0, 3, 5, 6, 10, 11])
     i_theta = 2

@@ -72,7 +72,7 @@ __host__ __device__ __forceinline__ int fft512_perm(int lane, int m) { return (l
 
 // natural order in (u[m] <-> position lane + 64 m), digit-permuted spectrum out (fft512_perm).  tw: the row kernels' tables
 // (w[m-1] = W512^(m lane) in registers; the middle stage's LDS table [k][m-1] = W64^(m k)).  Un-normalised, forward sign.
-template <int ROUND = 1, bool EX = BDOF_EX_ALL>
+template <int ROUND = 1, bool EX = false>
 __device__ __forceinline__ void fft512_reg_forward(cf (&u)[8], const FftTw<512>& tw, int lane) {
     typedef FftTw<512> TW;
     dft8<-1, EX ? 0 : ROUND>(u[0], u[1], u[2], u[3], u[4], u[5], u[6], u[7], tw.sq);
@@ -89,7 +89,7 @@ __device__ __forceinline__ void fft512_reg_forward(cf (&u)[8], const FftTw<512>&
 
 // digit-permuted order in, the first two inverse stages in registers; the LAST stage's inputs are left in the line's LDS image
 // exactly where line_fft_partial<512, +1> leaves them (position j + 64 m for input m of butterfly j), for transposed_tail.
-template <int ROUND = 1, bool EX = BDOF_EX_ALL, class L>
+template <int ROUND = 1, bool EX = false, class L>
 __device__ __forceinline__ void fft512_reg_inverse_partial(cf (&u)[8], const FftTw<512>& tw, int lane, L& lds) {
     typedef FftTw<512> TW;
     dft8<+1, EX ? 0 : ROUND>(u[0], u[1], u[2], u[3], u[4], u[5], u[6], u[7], tw.sq);

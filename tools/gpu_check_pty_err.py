@@ -10,13 +10,10 @@ from oracle import bdof_oracle as orc  # noqa: E402
 import test_gpu_ptycho as t  # noqa: E402
 from beyond_dof_amd.solver import PtychoSolver  # noqa: E402
 
-for psz, env in [((64, 64), {}), ((64, 64), {'BDOF_FORCE_RESIDENT': '1'}), ((72, 72), {}), ((72, 72), {'BDOF_NO_RESIDENT': '1'}),
-                 ((96, 96), {}), ((96, 96), {'BDOF_NO_RESIDENT': '1'}), ((60, 60), {})]:
-    for k in ('BDOF_FORCE_RESIDENT', 'BDOF_NO_RESIDENT'):
-        os.environ.pop(k, None)
-    os.environ.update(env)
+for psz, engine in [((64, 64), None), ((64, 64), 'resident'), ((72, 72), None), ((72, 72), 'streaming'),
+                    ((96, 96), None), ((96, 96), 'streaming'), ((60, 60), None)]:
     rng, n, n_theta, psz, pos, od, ob, coords, prr, pii = t._setup(psz)
-    s = PtychoSolver((n, n, n), psz, pos, n_theta, 6, 5000., 1e-7, prr, pii, coord_ls=coords)
+    s = PtychoSolver((n, n, n), psz, pos, n_theta, 6, 5000., 1e-7, prr, pii, coord_ls=coords, engine=engine)
     s.set_volume(od, ob)
     sel = np.array([0, 3, 5, 6, 10, 11])
     pad, half = orc.ptycho_pad_amounts(pos, psz, (n, n, n))
@@ -27,4 +24,4 @@ for psz, env in [((64, 64), {}), ((64, 64), {'BDOF_FORCE_RESIDENT': '1'}), ((72,
     ref, _ = orc.multislice_propagate_batch_numpy(subs[..., 0], subs[..., 1], prr, pii, 5000., 1e-7, 'inf', subs[..., 0].shape,
                                                   return_probe_array=False)
     w = s.forward(2, sel)
-    print(psz, env, 'intensity rel err %.3e  wave rel err %.3e' % (t.rel(np.abs(w) ** 2, np.abs(ref) ** 2), t.rel(w, ref)))
+    print(psz, engine, 'intensity rel err %.3e  wave rel err %.3e' % (t.rel(np.abs(w) ** 2, np.abs(ref) ** 2), t.rel(w, ref)))

@@ -29,18 +29,16 @@ def main():
     coords = orc.rotation_lookup(list(obj_size), n_theta)
     pr, pi_ = orc.gaussian_probe(psz, sigma, sigma, 0.5)
     init_d, init_b = g13_inputs.initial_guess(obj_size)
-    engines = (('conv', {}),) if conv else (('resident', {}), ('streaming', {'BDOF_NO_RESIDENT_PIN': '1'}),
-                                            ('generic', {'BDOF_NO_RESIDENT_PIN': '1', 'BDOF_FORCE_GENERIC': '1'}),
-                                            ('adjoint64', {'BDOF_ADJOINT64': '1'}))
+    # (name, PtychoSolver keyword arguments)
+    engines = (('conv', {}),) if conv else (('resident', {}), ('streaming', {'engine': 'auto'}), ('generic', {'engine': 'generic'}),
+                                            ('adjoint64', {'adjoint64': True}))
     print('lib', os.environ.get('BDOF_LIB', 'default'))
     ind0 = np.array([0, 1])
     _, rgd, rgb = orc.ptycho_loss_and_grad(init_d, init_b, coords[0], pos, pos[ind0], g['prj'][0, ind0], pr, pi_, psz, 5000., 1e-7,
                                            propagator='conv' if conv else 'fft')
-    for name, env in engines:
-        for k in ('BDOF_NO_RESIDENT_PIN', 'BDOF_FORCE_GENERIC', 'BDOF_ADJOINT64'):
-            os.environ.pop(k, None)
-        os.environ.update(env)
-        s = PtychoSolver(obj_size, psz, pos, n_theta, mb, 5000., 1e-7, pr, pi_, coord_ls=coords, propagator='conv' if conv else 'fft')
+    for name, kw in engines:
+        s = PtychoSolver(obj_size, psz, pos, n_theta, mb, 5000., 1e-7, pr, pi_, coord_ls=coords, propagator='conv' if conv else 'fft',
+                         **kw)
         s.set_volume(init_d, init_b)
         s.loss_and_grad(0, ind0, np.abs(g['prj'][0, ind0]))
         gd, gb = s.gradient_to_host()
