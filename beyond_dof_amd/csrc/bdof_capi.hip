@@ -29,9 +29,95 @@
 #define BDOF_MAX_GROUPS 4
 #define BDOF_N_TIMERS 16
 #define BDOF_MAX_DEVICES 64
-struct bdof_ctx {
+// ---- ownership: a member's type says who releases it ------------------------------------------------------------------------
+// device memory that its holder owns: n elements of T, released when the holder goes
+template <typename T>
+class DevBuf {
+    T* p_ = nullptr;
+    size_t n_ = 0;
+public:
+    DevBuf() = default;
+    DevBuf(DevBuf&& o) noexcept { *this = std::move(o); }
+    DevBuf& operator=(DevBuf&& o) noexcept { std::swap(p_, o.p_); std::swap(n_, o.n_); return *this; }     // o releases what this held
+    ~DevBuf() { reset(); }
+    void reset() { if (p_) (void)hipFree(p_); p_ = nullptr; n_ = 0; }
+    // what is held goes BEFORE its replacement is allocated: the large buffers do not fit twice
+    hipError_t alloc(size_t n) {
+        reset();
+        const hipError_t e = hipMalloc((void**)&p_, n * sizeof(T));
+        if (e == hipSuccess) n_ = n; else p_ = nullptr;
+        return e;
+    }
+    hipError_t room(size_t n) { return n_ >= n ? hipSuccess : alloc(n); }      // grow only
+    size_t size() const { return n_; }
+    explicit operator bool() const { return p_ != nullptr; }
+    operator T*() const { return p_; }
+};
+
+// the forward and the inverse rocFFT plan of one (shape, batch, precision)
+struct PlanPair {
+    rocfft_plan fwd = nullptr, inv = nullptr;
+    PlanPair() = default;
+    PlanPair(PlanPair&& o) noexcept : fwd(o.fwd), inv(o.inv) { o.fwd = o.inv = nullptr; }
+    ~PlanPair() {
+        if (fwd) (void)rocfft_plan_destroy(fwd);
+        if (inv) (void)rocfft_plan_destroy(inv);
+    }
+};
+
+// what rocFFT executes with on one stream: the execution info and the work area bound to it (fft_exec_room)
+struct FftExec {
+    rocfft_execution_info info = nullptr;
+    DevBuf<char> work;
+    FftExec() = default;
+    FftExec(FftExec&& o) noexcept { *this = std::move(o); }
+    FftExec& operator=(FftExec&& o) noexcept { std::swap(info, o.info); work = std::move(o.work); return *this; }
+    ~FftExec() { if (info) (void)rocfft_execution_info_destroy(info); }
+};
+
+// Everything bdof_configure sizes, with the flags that say what the buffers hold: a re-configure assigns a fresh Workspace, so a
+// member placed here is released and reset by its type.  Members of bdof_ctx itself survive a re-configure.
+struct Workspace {
+    DevBuf<cf> twY, twX;
+    DevBuf<cf> hs, hdet, hcomb, probe;
+    // float64 real-space propagator (bdof_set_conv_f64 / bdof_loss_grad_conv_f64, bdof_conv64.h)
+    DevBuf<double2> c64_probe, c64_khat, c64_psi, c64_q, c64_big, c64_tape, c64_scal, c64_part;
+    int c64_ks = 0, c64_B = 0;
+    DevBuf<double2> c64_h, c64_hdet;             // the transfer-function model of the float64 path (bdof_set_tf_f64)
+    DevBuf<cf> hsT_d;              // the same copies in the LDS-resident kernel's [kx][ky] order
+    DevBuf<cf> hs_d;               // bdof_set_transfer_f64: hs_copies dithered float32 copies of the slice step's table (bdof_field.h)
+    int hs_copies = 0;
+    DevBuf<cf> bufA, bufB, tape;
+    DevBuf<float2> grot;
+    DevBuf<double2> gcar, gt0;                   // adjoint carrier per wavefield (AdjCarrier, bdof_kernels.h)
+    DevBuf<cf> gpsi0;                            // [Bmax][NX][NY] G(psi_0) per wavefield (bdof_enable_probe_grad)
+    const cf* gpsi_src = nullptr;                // borrowed from this workspace: where the last bdof_loss_grad left it (gpsi0, or the generic engine's field)
+    DevBuf<double> partial, loss_dev;
+    // real-space truncated-kernel propagator (bdof_set_conv)
+    bool have_conv = false;
+    DevBuf<ConvTaps> taps_dev;
+    int taps_copies = 1;          // dithered copies of the taps in taps_dev (bdof_set_conv_taps_f64), slice z takes copy z mod taps_copies
+    DevBuf<cf> bufC, conv_scal;
+    // carrier field of the real-space propagator (bdof_set_conv_probe_stack): p_0 .. p_S, float32 planes [S + 1][NX][NY]; the
+    // detector plane of p_S in float64; corner pixels of p_0 and p_S (the renormalisation s = p_0[0,0] / psi_S[0,0,0])
+    DevBuf<cf> cstack;
+    DevBuf<double2> cdet64;
+    // LDS-resident engine (small square fields, bdof_resident.h)
+    bool resident = false;
+    DevBuf<cf> hsT, hdetT, twR, res_carrier;
+    DevBuf<cf> pstack, pdet, pdetT;              // carrier field of a localised probe (bdof_set_probe_stack); pdetT = det transposed
+    DevBuf<double2> pdet64, pdetT64;             // the same planes in float64 (bdof_set_probe_field): the residual |d| - m is formed in float64
+    // rocFFT (generic-size engine, float64 paths, whole-field steps): one plan pair per (NX, NY, B, double)
+    std::map<std::array<int, 4>, PlanPair> plans;
+    FftExec fft;                                 // of the ctx's stream
+    // float64 adjoint sweep (BDOF_CFG_ADJOINT64; generic engine)
+    bool have_h64 = false;
+    DevBuf<double2> g64, hs64, hdet64;
+};
+
+struct bdof_ctx : Workspace {
     int device = 0;
-    hipStream_t stream = nullptr;
+    hipStream_t stream = nullptr;               // borrowed from the caller unless own_stream
     bool own_stream = false;
     // dual-stream split of a batch (see batch_groups): the sub-batch the launchers currently work on
     hipStream_t side[BDOF_MAX_GROUPS - 1] = {};   // side streams PROVEN to run concurrently with the ctx stream (probe_side_streams)
@@ -46,94 +132,52 @@ struct bdof_ctx {
     int NY = 0, NX = 0, S = 0, Bmax = 0;
     bool with_grad = false;
     bool recompute = false;                      // tape-free adjoint (BDOF_CFG_RECOMPUTE): the tape holds 3 fields, not S
-    cf *twY = nullptr, *twX = nullptr;
     // dithered twiddle tables (bdof_fft.h; BDOF_TW_DITHER=D, default 64): D copies of each table, entry j of copy d rounded up or
     // down so that the mean over the D copies is the float64 value to ulp / D; the launches of slice z take copy z mod D
     int tw_dither = 0;
     unsigned tw_tick = 0;          // the slice of the last A / A' launch: the transfer-function launch that follows takes the same copy
-    cf *hs = nullptr, *hdet = nullptr, *hcomb = nullptr, *probe = nullptr;
-    // float64 real-space propagator (bdof_set_conv_f64 / bdof_loss_grad_conv_f64, bdof_conv64.h)
-    double2 *c64_probe = nullptr, *c64_khat = nullptr, *c64_psi = nullptr, *c64_q = nullptr, *c64_big = nullptr, *c64_tape = nullptr,
-            *c64_scal = nullptr, *c64_part = nullptr;
-    int c64_ks = 0, c64_B = 0;
-    double2* car_scratch = nullptr;             // bdof_range_carrier_build: [nz - 1][B][NX][NY] complex128
-    size_t car_scratch_n = 0;
-    hipStream_t aux = nullptr;                  // bdof_fields_free_step_aux: the whole-field step of a stitch range beside the tiles' sweeps
-    hipEvent_t ev_aux_fork = nullptr, ev_aux_join = nullptr;
-    rocfft_execution_info ginfo_aux = nullptr;
-    void* gwork_aux = nullptr;
-    size_t gwork_aux_sz = 0;
-    bool aux_pending = false;
+    // borrowed: the caller's memory, which the caller keeps alive and releases (with the caller's stream above, and gpsi_src,
+    // which points into the Workspace and is reset with it)
+    const float2* obj_src = nullptr;            // caller's (delta, beta) rows
+    const int *adj_off = nullptr, *adj_order = nullptr;
+    const cf* hs_override = nullptr;            // bdof_forward_range_h: the table of this call's transfer-function steps
     const cf* range_car = nullptr;              // bdof_set_range_carrier: [nz][B][NX][NY] carrier fields of the range being swept
     int range_car_B = 0, range_car_z0 = 0;
+    DevBuf<double2> car_scratch;                // bdof_range_carrier_build: [nz - 1][B][NX][NY] complex128
+    hipStream_t aux = nullptr;                  // bdof_fields_free_step_aux: the whole-field step of a stitch range beside the tiles' sweeps
+    hipEvent_t ev_aux_fork = nullptr, ev_aux_join = nullptr;
+    FftExec fft_aux;
+    bool aux_pending = false;
     bool c64_tf = false;                        // the float64 path holds the transfer-function model (bdof_set_tf_f64), not the real-space one
-    double2 *c64_h = nullptr, *c64_hdet = nullptr;
     std::complex<double> c64_ksum{1.0, 0.0};
     double c64_k = 0.0;
-    cf* hsT_d = nullptr;           // the same copies in the LDS-resident kernel's [kx][ky] order
-    cf* hs_d = nullptr;            // bdof_set_transfer_f64: hs_copies dithered float32 copies of the slice step's table (bdof_field.h)
-    int hs_copies = 0;
-    const cf* hs_override = nullptr;   // bdof_forward_range_h: the table of this call's transfer-function steps
-    cf *bufA = nullptr, *bufB = nullptr, *tape = nullptr;
-    float2* grot = nullptr;
-    double2 *gcar = nullptr, *gt0 = nullptr;     // adjoint carrier per wavefield (AdjCarrier, bdof_kernels.h)
-    cf* gpsi0 = nullptr;                         // [Bmax][NX][NY] G(psi_0) per wavefield (bdof_enable_probe_grad)
-    const cf* gpsi_src = nullptr;                // where the last bdof_loss_grad left it (gpsi0, or the generic engine's field)
     int gpsi_B = 0;
-    double *partial = nullptr, *loss_dev = nullptr;
     int npartial = 0;
     float k = 0.f;                              // the k the modulation table in c->mod was built with
     float k_fft = 0.f;                          // bdof_set_physics' k (the reference's PI literal, quirk Q1)
     std::complex<double> h00{1.0, 0.0}, hdet00{1.0, 0.0}, a0{0.0, 0.0};   // carrier splitting (bdof_kernels.h)
     std::complex<double> cbm1{0.0, 0.0};        // cbar - 1: mean modulation factor of the object minus one (modulate_eps_s)
-    double2* cbar_dev = nullptr;                // [npartial_cb + 1] per-workgroup sums of the modulation table, then the mean
-    int ncb = 0;
-    // real-space truncated-kernel propagator (bdof_set_conv)
-    bool have_conv = false;
-    ConvTaps taps{};
-    ConvTaps* taps_dev = nullptr;
-    int taps_copies = 1;          // dithered copies of the taps in taps_dev (bdof_set_conv_taps_f64), slice z takes copy z mod taps_copies
+    DevBuf<double2> cbar_dev;                   // [ncu * 16 + 1] per-workgroup sums of the modulation table, then the mean
+    ConvTaps taps{};                            // bdof_set_conv
     std::complex<double> ksum{1.0, 0.0};
     float k_conv = 0.f;
-    cf *bufC = nullptr, *conv_scal = nullptr;
-    // carrier field of the real-space propagator (bdof_set_conv_probe_stack): p_0 .. p_S, float32 planes [S + 1][NX][NY]; the
-    // detector plane of p_S in float64; corner pixels of p_0 and p_S (the renormalisation s = p_0[0,0] / psi_S[0,0,0])
-    cf* cstack = nullptr;
-    double2* cdet64 = nullptr;
-    std::complex<double> c_p0{0.0, 0.0}, c_pS{0.0, 0.0};
-    // LDS-resident engine (small square fields, bdof_resident.h)
-    bool resident = false, res_dirty = true, res_always = false;
-    cf *hsT = nullptr, *hdetT = nullptr, *twR = nullptr, *res_carrier = nullptr;
+    std::complex<double> c_p0{0.0, 0.0}, c_pS{0.0, 0.0};   // bdof_set_conv_probe_stack
+    bool res_dirty = true, res_always = false;
     int meas_dev = 0;                           // bdof_set_meas_mode
-    cf *pstack = nullptr, *pdet = nullptr, *pdetT = nullptr;      // carrier field of a localised probe (bdof_set_probe_stack); pdetT = det transposed
-    double2 *pdet64 = nullptr, *pdetT64 = nullptr;                // the same planes in float64 (bdof_set_probe_field): the residual |d| - m is formed in float64
-    // generic-size engine (rocFFT): one plan pair per batch size
-    bool generic = false;
-    std::map<int, std::pair<rocfft_plan, rocfft_plan>> gplans;
-    // float64 adjoint sweep (BDOF_CFG_ADJOINT64; generic engine)
-    bool adj64 = false, have_h64 = false;
-    std::map<int, std::pair<rocfft_plan, rocfft_plan>> gplans64;
-    std::map<std::array<int, 4>, std::pair<rocfft_plan, rocfft_plan>> fplans;      // bdof_fields_free_step: (NX, NY, B, double)
-    double2 *g64 = nullptr, *hs64 = nullptr, *hdet64 = nullptr;
-    rocfft_execution_info ginfo = nullptr;
-    void* gwork = nullptr;
-    size_t gwork_sz = 0;
+    bool generic = false;                       // generic-size engine (rocFFT)
+    bool adj64 = false;                         // float64 adjoint sweep (BDOF_CFG_ADJOINT64; generic engine)
     int det_mode = BDOF_DET_NONE, variant = BDOF_VARIANT_NUMPY_SKIP_LAST;
     bool have_physics = false, have_probe = false, tape_valid = false, last_valid = false;
     ObjView obj{};
-    const float2* obj_src = nullptr;            // caller's (delta, beta) rows
     bool obj_bound_mod = false;                 // bdof_set_object_bilinear: c->mod was written directly, there is no obj_src
     size_t obj_rows = 0;
-    float2* mod = nullptr;                      // c - 1 table of those rows (k_modulation_table)
-    size_t mod_cap = 0;
+    DevBuf<float2> mod;                         // c - 1 table of those rows (k_modulation_table)
     bool mod_dirty = true;
     int n_angles = 0;
-    const int *adj_off = nullptr, *adj_order = nullptr;
     int adj_ndest = 0;
-    float2* winpad = nullptr;                   // [S][volNX][volNY] rotated-frame gradient of the ptychography windows
-    size_t winpad_sz = 0;
-    int* win_angle = nullptr;                   // device copy of the batch's angle index
-    int* heavy = nullptr;                       // [1 + n_dest]: counter + deferred rows of the rotation adjoint
+    DevBuf<float2> winpad;                      // [S][volNX][volNY] rotated-frame gradient of the ptychography windows
+    DevBuf<int> win_angle;                      // device copy of the batch's angle index
+    DevBuf<int> heavy;                          // [1 + n_dest]: counter + deferred rows of the rotation adjoint
     // profiling
     bool prof = false;
     int prof_stride = 1;                        // time every prof_stride-th launch of a class
@@ -582,18 +626,8 @@ static void forward_sweep(bdof_ctx* c, const Group* groups, int ngroups, int tap
 // (Re)build the modulation table c - 1 = exp(i k delta - k beta) - 1 of the object rows when the object or k changed.
 // room for n modulation factors and, if the mean-refraction carrier is in use, for the per-workgroup sums of a pass
 static int modulation_room(bdof_ctx* c, size_t n, bool mean) {
-    if (n > c->mod_cap) {
-        if (c->mod) (void)hipFree(c->mod);
-        c->mod = nullptr; c->mod_cap = 0;
-        HIPC(c, hipMalloc((void**)&c->mod, sizeof(float2) * n));
-        c->mod_cap = n;
-    }
-    if (mean && c->ncb < c->ncu * 16 + 1) {
-        if (c->cbar_dev) (void)hipFree(c->cbar_dev);
-        c->cbar_dev = nullptr; c->ncb = 0;
-        HIPC(c, hipMalloc((void**)&c->cbar_dev, sizeof(double2) * (size_t)(c->ncu * 16 + 1)));
-        c->ncb = c->ncu * 16 + 1;
-    }
+    HIPC(c, c->mod.room(n));
+    if (mean) HIPC(c, c->cbar_dev.room((size_t)c->ncu * 16 + 1));
     return 0;
 }
 // after a pass that left c - 1 in c->mod (and `grid` partial sums in cbar_dev if mean): mean to the host, object bound
@@ -644,36 +678,43 @@ static bool g_rocfft_ready = false;
         if (s_ != rocfft_status_success) return fail((c), BDOF_ERR_STATE, std::string(#call) + ": rocfft status " + std::to_string((int)s_)); \
     } while (0)
 
-static int generic_plans(bdof_ctx* c, int B, rocfft_plan* fwd, rocfft_plan* inv, bool dbl = false) {
+// rocFFT's execution info of stream `st`, with a work area of at least `need` bytes bound to it.  The area only grows, and the
+// stream drains before the old one goes: queued transforms may still use it.
+static int fft_exec_room(bdof_ctx* c, FftExec& x, hipStream_t st, size_t need) {
+    if (!x.info) {
+        RFC(c, rocfft_execution_info_create(&x.info));
+        RFC(c, rocfft_execution_info_set_stream(x.info, (void*)st));
+    }
+    if (x.work.size() < need) {
+        HIPC(c, hipStreamSynchronize(st));
+        HIPC(c, x.work.alloc(need));
+    }
+    if (x.work.size()) RFC(c, rocfft_execution_info_set_work_buffer(x.info, x.work, x.work.size()));
+    return 0;
+}
+
+// the cached in-place 2-D plans of B fields [NX][NY] (the cache keeps them), created at first use; c->fft is ready to execute them
+// on the ctx's stream
+static int field_plans(bdof_ctx* c, int NX, int NY, int B, bool dbl, rocfft_plan* fwd, rocfft_plan* inv) {
     if (!g_rocfft_ready) { RFC(c, rocfft_setup()); g_rocfft_ready = true; }
-    auto& plans = dbl ? c->gplans64 : c->gplans;
-    const rocfft_precision prec = dbl ? rocfft_precision_double : rocfft_precision_single;
-    auto it = plans.find(B);
-    if (it == plans.end()) {
-        const size_t lengths[2] = {(size_t)c->NY, (size_t)c->NX};      // fastest dimension first
-        rocfft_plan pf = nullptr, pi = nullptr;
-        RFC(c, rocfft_plan_create(&pf, rocfft_placement_inplace, rocfft_transform_type_complex_forward, prec, 2, lengths, (size_t)B, nullptr));
-        RFC(c, rocfft_plan_create(&pi, rocfft_placement_inplace, rocfft_transform_type_complex_inverse, prec, 2, lengths, (size_t)B, nullptr));
+    const std::array<int, 4> key{NX, NY, B, dbl ? 1 : 0};
+    auto it = c->plans.find(key);
+    size_t need = 0;                                                    // a cached pair's work area is there already
+    if (it == c->plans.end()) {
+        const size_t lengths[2] = {(size_t)NY, (size_t)NX};             // fastest dimension first
+        const rocfft_precision prec = dbl ? rocfft_precision_double : rocfft_precision_single;
+        PlanPair p;
+        RFC(c, rocfft_plan_create(&p.fwd, rocfft_placement_inplace, rocfft_transform_type_complex_forward, prec, 2, lengths, (size_t)B, nullptr));
+        RFC(c, rocfft_plan_create(&p.inv, rocfft_placement_inplace, rocfft_transform_type_complex_inverse, prec, 2, lengths, (size_t)B, nullptr));
         size_t w1 = 0, w2 = 0;
-        RFC(c, rocfft_plan_get_work_buffer_size(pf, &w1));
-        RFC(c, rocfft_plan_get_work_buffer_size(pi, &w2));
-        const size_t need = std::max(w1, w2);
-        if (need > c->gwork_sz) {
-            HIPC(c, hipStreamSynchronize(c->stream));
-            if (c->gwork) (void)hipFree(c->gwork);
-            c->gwork = nullptr;
-            HIPC(c, hipMalloc(&c->gwork, need));
-            c->gwork_sz = need;
-        }
-        it = plans.emplace(B, std::make_pair(pf, pi)).first;
+        RFC(c, rocfft_plan_get_work_buffer_size(p.fwd, &w1));
+        RFC(c, rocfft_plan_get_work_buffer_size(p.inv, &w2));
+        need = std::max(w1, w2);
+        it = c->plans.emplace(key, std::move(p)).first;
     }
-    if (!c->ginfo) {
-        RFC(c, rocfft_execution_info_create(&c->ginfo));
-        RFC(c, rocfft_execution_info_set_stream(c->ginfo, (void*)c->stream));
-    }
-    if (c->gwork_sz) RFC(c, rocfft_execution_info_set_work_buffer(c->ginfo, c->gwork, c->gwork_sz));
-    *fwd = it->second.first;
-    *inv = it->second.second;
+    if (int r = fft_exec_room(c, c->fft, c->stream, need)) return r;
+    *fwd = it->second.fwd;
+    *inv = it->second.inv;
     return 0;
 }
 
@@ -688,10 +729,10 @@ static int g_elem_grid(const bdof_ctx* c, size_t n) { return (int)std::min<size_
 static int generic_prop(bdof_ctx* c, int B, rocfft_plan pf, rocfft_plan pi, cf* field, const cf* h, int conj_h) {
     ProfScope ps(c, BDOF_K_COL_PROP);
     void* buf[1] = {field};
-    RFC(c, rocfft_execute(pf, buf, nullptr, c->ginfo));
+    RFC(c, rocfft_execute(pf, buf, nullptr, c->fft.info));
     const size_t n = (size_t)B * c->NX * c->NY;
     hipLaunchKernelGGL(k_g_hmul, dim3(g_elem_grid(c, n)), dim3(256), 0, c->stream, field, h, B, c->NX, c->NY, conj_h);
-    RFC(c, rocfft_execute(pi, buf, nullptr, c->ginfo));
+    RFC(c, rocfft_execute(pi, buf, nullptr, c->fft.info));
     return 0;
 }
 
@@ -722,7 +763,7 @@ static int generic_forward_sweep(bdof_ctx* c, int B, bool tape, rocfft_plan pf, 
         a *= c->hdet00;
     } else if (c->det_mode == BDOF_DET_FAR) {
         void* buf[1] = {c->bufA};
-        RFC(c, rocfft_execute(pf, buf, nullptr, c->ginfo));
+        RFC(c, rocfft_execute(pf, buf, nullptr, c->fft.info));
         a *= (double)c->NX * (double)c->NY;
     }
     *carrier_out = a;
@@ -731,7 +772,7 @@ static int generic_forward_sweep(bdof_ctx* c, int B, bool tape, rocfft_plan pf, 
 
 static int generic_forward(bdof_ctx* c, int B, void* out_wave, bool keep_tape) {
     rocfft_plan pf, pi;
-    int r = generic_plans(c, B, &pf, &pi);
+    int r = field_plans(c, c->NX, c->NY, B, false, &pf, &pi);
     if (r) return r;
     std::complex<double> a;
     if ((r = generic_forward_sweep(c, B, keep_tape, pf, pi, &a))) return r;
@@ -747,7 +788,7 @@ static int generic_forward(bdof_ctx* c, int B, void* out_wave, bool keep_tape) {
 
 static int generic_loss_grad(bdof_ctx* c, int B, const float* meas, void* out_wave) {
     rocfft_plan pf, pi;
-    int r = generic_plans(c, B, &pf, &pi);
+    int r = field_plans(c, c->NX, c->NY, B, false, &pf, &pi);
     if (r) return r;
     const size_t fld = (size_t)c->Bmax * c->NX * c->NY;
     const size_t n = (size_t)B * c->NX * c->NY;
@@ -770,17 +811,17 @@ static int generic_loss_grad(bdof_ctx* c, int B, const float* meas, void* out_wa
     if (f64) {
         // float64 adjoint sweep: g64 holds the seed G(d)
         rocfft_plan pf64, pi64;
-        if ((r = generic_plans(c, B, &pf64, &pi64, true))) return r;
+        if ((r = field_plans(c, c->NX, c->NY, B, true, &pf64, &pi64))) return r;
         void* b64[1] = {c->g64};
         auto prop64 = [&](const double2* h) -> int {
             ProfScope ps(c, BDOF_K_COL_PROP);
-            RFC(c, rocfft_execute(pf64, b64, nullptr, c->ginfo));
+            RFC(c, rocfft_execute(pf64, b64, nullptr, c->fft.info));
             hipLaunchKernelGGL(k_g_hmul64, dim3(egrid), dim3(256), 0, c->stream, c->g64, h, B, c->NX, c->NY, 1);
-            RFC(c, rocfft_execute(pi64, b64, nullptr, c->ginfo));
+            RFC(c, rocfft_execute(pi64, b64, nullptr, c->fft.info));
             return 0;
         };
         if (c->det_mode == BDOF_DET_NEAR) { if ((r = prop64(c->hdet64))) return r; }
-        else if (c->det_mode == BDOF_DET_FAR) RFC(c, rocfft_execute(pi64, b64, nullptr, c->ginfo));
+        else if (c->det_mode == BDOF_DET_FAR) RFC(c, rocfft_execute(pi64, b64, nullptr, c->fft.info));
         for (int z = c->S - 1; z >= 0; --z) {
             const bool prop_after = z < c->S - 1 || (tf_all && c->det_mode != BDOF_DET_FAR);
             if (prop_after && (r = prop64(c->hs64))) return r;
@@ -798,7 +839,7 @@ static int generic_loss_grad(bdof_ctx* c, int B, const float* meas, void* out_wa
     if (c->det_mode == BDOF_DET_NEAR) {
         if ((r = generic_prop(c, B, pf, pi, c->bufA, c->hdet, 1))) return r;
     } else if (c->det_mode == BDOF_DET_FAR) {
-        RFC(c, rocfft_execute(pi, buf, nullptr, c->ginfo));            // F^H = unnormalised inverse
+        RFC(c, rocfft_execute(pi, buf, nullptr, c->fft.info));            // F^H = unnormalised inverse
     }
     for (int z = c->S - 1; z >= 0; --z) {
         const bool prop_after = z < c->S - 1 || (tf_all && c->det_mode != BDOF_DET_FAR);
@@ -966,70 +1007,21 @@ int bdof_ctx_create(bdof_ctx** out, int device, void* stream) {
     return 0;
 }
 
-static void free_generic(bdof_ctx* c) {
-    for (auto& kv : c->gplans) { (void)rocfft_plan_destroy(kv.second.first); (void)rocfft_plan_destroy(kv.second.second); }
-    c->gplans.clear();
-    for (auto& kv : c->gplans64) { (void)rocfft_plan_destroy(kv.second.first); (void)rocfft_plan_destroy(kv.second.second); }
-    c->gplans64.clear();
-    for (auto& kv : c->fplans) { (void)rocfft_plan_destroy(kv.second.first); (void)rocfft_plan_destroy(kv.second.second); }
-    c->fplans.clear();
-    for (double2** q : {&c->g64, &c->hs64, &c->hdet64}) { if (*q) (void)hipFree(*q); *q = nullptr; }
-    c->have_h64 = false;
-    if (c->ginfo) { (void)rocfft_execution_info_destroy(c->ginfo); c->ginfo = nullptr; }
-    if (c->gwork) { (void)hipFree(c->gwork); c->gwork = nullptr; c->gwork_sz = 0; }
-}
-
-static void free_workspace(bdof_ctx* c) {
-    free_generic(c);
-    if (c->hs_d) { (void)hipFree(c->hs_d); c->hs_d = nullptr; c->hs_copies = 0; }
-    if (c->hsT_d) { (void)hipFree(c->hsT_d); c->hsT_d = nullptr; }
-    for (double2** q : {&c->c64_probe, &c->c64_khat, &c->c64_psi, &c->c64_q, &c->c64_big, &c->c64_tape, &c->c64_scal, &c->c64_part, &c->c64_h, &c->c64_hdet}) {
-        if (*q) (void)hipFree(*q);
-        *q = nullptr;
-    }
-    c->c64_ks = c->c64_B = 0;
-    void* ptrs[] = {c->cstack, c->cdet64, c->pdet64, c->pdetT64, c->pstack, c->pdet, c->pdetT, c->hsT, c->hdetT, c->twR, c->res_carrier, c->bufC, c->conv_scal, c->taps_dev, c->twY, c->twX, c->hs, c->hdet, c->hcomb, c->probe, c->bufA, c->bufB, c->tape, c->grot, c->gcar, c->gt0, c->gpsi0, c->partial, c->loss_dev};
-    for (void* p : ptrs) if (p) (void)hipFree(p);
-    c->hsT = c->hdetT = c->twR = c->res_carrier = nullptr;
-    c->pstack = c->pdet = c->pdetT = nullptr;
-    c->pdet64 = c->pdetT64 = nullptr;
-    c->resident = false;
-    c->bufC = c->conv_scal = nullptr;
-    c->cstack = nullptr; c->cdet64 = nullptr;
-    c->taps_dev = nullptr;
-    c->taps_copies = 1;
-    c->have_conv = false;
-    c->twY = c->twX = c->hs = c->hdet = c->hcomb = c->probe = c->bufA = c->bufB = c->tape = nullptr;
-    c->grot = nullptr;
-    c->gcar = c->gt0 = nullptr;
-    c->gpsi0 = nullptr; c->gpsi_src = nullptr;
-    c->partial = c->loss_dev = nullptr;
-}
-
 void bdof_ctx_destroy(bdof_ctx* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
-    free_workspace(c);
-    if (c->heavy) (void)hipFree(c->heavy);
-    if (c->winpad) (void)hipFree(c->winpad);
-    if (c->win_angle) (void)hipFree(c->win_angle);
-    if (c->mod) (void)hipFree(c->mod);
-    if (c->cbar_dev) (void)hipFree(c->cbar_dev);
     for (auto& e : c->ev_pool) (void)hipEventDestroy(e);
     for (auto& e : c->timer) if (e) (void)hipEventDestroy(e);
     for (hipStream_t s : c->side_all) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); }
     if (c->aux) { (void)hipStreamSynchronize(c->aux); (void)hipStreamDestroy(c->aux); }
     if (c->ev_aux_fork) (void)hipEventDestroy(c->ev_aux_fork);
     if (c->ev_aux_join) (void)hipEventDestroy(c->ev_aux_join);
-    if (c->ginfo_aux) (void)rocfft_execution_info_destroy(c->ginfo_aux);
-    if (c->gwork_aux) (void)hipFree(c->gwork_aux);
-    if (c->car_scratch) (void)hipFree(c->car_scratch);
     for (int i = 0; i < BDOF_MAX_GROUPS - 1; ++i)
         if (c->ev_join[i]) (void)hipEventDestroy(c->ev_join[i]);
     if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
     if (c->own_stream) (void)hipStreamDestroy(c->stream);
-    delete c;
+    delete c;                                    // every stream has drained: the owning members release the device memory and the plans
 }
 
 const char* bdof_last_error(const bdof_ctx* c) { return c ? c->err.c_str() : "null ctx"; }
@@ -1083,12 +1075,12 @@ int bdof_twiddle_tables(int N, int D, float* out) {
     return 0;
 }
 
-static int upload_twiddle(bdof_ctx* c, int N, cf** dst, bool dither = true) {
+static int upload_twiddle(bdof_ctx* c, int N, DevBuf<cf>& dst, bool dither = true) {
     const int D = dither && c->tw_dither > 1 ? c->tw_dither : 1;
     std::vector<cf> t((size_t)N * 2 * D);
     fill_twiddle_tables(N, D, t.data());
-    HIPC(c, hipMalloc((void**)dst, sizeof(cf) * t.size()));
-    HIPC(c, hipMemcpyAsync(*dst, t.data(), sizeof(cf) * t.size(), hipMemcpyHostToDevice, c->stream));
+    HIPC(c, dst.alloc(t.size()));
+    HIPC(c, hipMemcpyAsync(dst, t.data(), sizeof(cf) * t.size(), hipMemcpyHostToDevice, c->stream));
     HIPC(c, hipStreamSynchronize(c->stream));
     return 0;
 }
@@ -1100,7 +1092,7 @@ int bdof_configure(bdof_ctx* c, int NY, int NX, int S, int Bmax, int with_grad) 
     if (generic && (size_t)NY * NX > ((size_t)1 << 26)) return fail(c, BDOF_ERR_SIZE, "wavefield too large");
     HIPC(c, hipSetDevice(c->device));
     HIPC(c, hipStreamSynchronize(c->stream));
-    free_workspace(c);
+    static_cast<Workspace&>(*c) = Workspace{};       // the previous configuration's buffers, plans and flags go before the new ones come
     c->NY = NY; c->NX = NX; c->S = S; c->Bmax = Bmax; c->with_grad = (with_grad & BDOF_CFG_GRAD) != 0;
     c->generic = generic;
     // dithered transform constants (bdof_fft.h): 64 copies of each table by default, BDOF_TW_DITHER=0 for one plain table
@@ -1113,42 +1105,42 @@ int bdof_configure(bdof_ctx* c, int NY, int NX, int S, int Bmax, int with_grad) 
     c->have_physics = c->have_probe = c->tape_valid = false;
     int r;
     if (c->resident) {
-        if ((r = upload_twiddle(c, NX, &c->twR, false))) return r;       // one launch runs all slices: one table
-        HIPC(c, hipMalloc((void**)&c->hsT, sizeof(cf) * NX * NY));
-        HIPC(c, hipMalloc((void**)&c->hdetT, sizeof(cf) * NX * NY));
-        HIPC(c, hipMalloc((void**)&c->res_carrier, sizeof(cf) * 2 * (size_t)S));
+        if ((r = upload_twiddle(c, NX, c->twR, false))) return r;       // one launch runs all slices: one table
+        HIPC(c, c->hsT.alloc((size_t)NX * NY));
+        HIPC(c, c->hdetT.alloc((size_t)NX * NY));
+        HIPC(c, c->res_carrier.alloc(2 * (size_t)S));
     }
     if (!generic) {
-        if ((r = upload_twiddle(c, NY, &c->twY))) return r;
-        if ((r = upload_twiddle(c, NX, &c->twX))) return r;
+        if ((r = upload_twiddle(c, NY, c->twY))) return r;
+        if ((r = upload_twiddle(c, NX, c->twX))) return r;
     }
     const size_t fld = (size_t)Bmax * NX * NY;
-    HIPC(c, hipMalloc((void**)&c->hs, sizeof(cf) * NX * NY));
-    HIPC(c, hipMalloc((void**)&c->hdet, sizeof(cf) * NX * NY));
-    HIPC(c, hipMalloc((void**)&c->hcomb, sizeof(cf) * NX * NY));
-    HIPC(c, hipMalloc((void**)&c->probe, sizeof(cf) * NX * NY));
-    HIPC(c, hipMalloc((void**)&c->bufA, sizeof(cf) * fld));
-    HIPC(c, hipMalloc((void**)&c->bufB, sizeof(cf) * fld));
+    HIPC(c, c->hs.alloc((size_t)NX * NY));
+    HIPC(c, c->hdet.alloc((size_t)NX * NY));
+    HIPC(c, c->hcomb.alloc((size_t)NX * NY));
+    HIPC(c, c->probe.alloc((size_t)NX * NY));
+    HIPC(c, c->bufA.alloc(fld));
+    HIPC(c, c->bufB.alloc(fld));
     if (c->with_grad) {
         // tape-free adjoint: phi_{S-1} (real space) + the two fields the marched-back wave alternates between
         const bool small_tape = c->recompute && !(c->resident && c->res_always);
         c->recompute = small_tape;
-        HIPC(c, hipMalloc((void**)&c->tape, sizeof(cf) * fld * (size_t)(small_tape ? std::min(S, 3) : S)));
+        HIPC(c, c->tape.alloc(fld * (size_t)(small_tape ? std::min(S, 3) : S)));
         // BDOF_CFG_NO_GROT: the caller sweeps slice ranges into gradient buffers of its own (bdof_adjoint_range, the tiled path),
         // where [Bmax][S] rows would not fit — 260 GB for 121 tiles of 512^2 x 1024 slices
-        if ((with_grad & BDOF_CFG_NO_GROT) == 0) HIPC(c, hipMalloc((void**)&c->grot, sizeof(float2) * fld * (size_t)S));
-        HIPC(c, hipMalloc((void**)&c->gcar, sizeof(double2) * (size_t)Bmax));
-        HIPC(c, hipMalloc((void**)&c->gt0, sizeof(double2) * (size_t)Bmax));
+        if ((with_grad & BDOF_CFG_NO_GROT) == 0) HIPC(c, c->grot.alloc(fld * (size_t)S));
+        HIPC(c, c->gcar.alloc((size_t)Bmax));
+        HIPC(c, c->gt0.alloc((size_t)Bmax));
     }
     if (c->adj64) {
-        HIPC(c, hipMalloc((void**)&c->g64, sizeof(double2) * fld));
-        HIPC(c, hipMalloc((void**)&c->hs64, sizeof(double2) * NX * NY));
-        HIPC(c, hipMalloc((void**)&c->hdet64, sizeof(double2) * NX * NY));
+        HIPC(c, c->g64.alloc(fld));
+        HIPC(c, c->hs64.alloc((size_t)NX * NY));
+        HIPC(c, c->hdet64.alloc((size_t)NX * NY));
     }
     c->npartial = c->ncu * 16 + 64;
     // the resident kernel leaves one pair per workgroup AND wave (up to 16 waves)
-    HIPC(c, hipMalloc((void**)&c->partial, sizeof(double) * 2 * c->npartial * (c->resident ? 16 : 1)));
-    HIPC(c, hipMalloc((void**)&c->loss_dev, sizeof(double)));
+    HIPC(c, c->partial.alloc((size_t)2 * c->npartial * (c->resident ? 16 : 1)));
+    HIPC(c, c->loss_dev.alloc(1));
     HIPC(c, hipMemsetAsync(c->loss_dev, 0, sizeof(double), c->stream));
     return 0;
 }
@@ -1218,13 +1210,13 @@ int bdof_set_transfer_f64(bdof_ctx* c, const double* hs64) {
     if (D < 2) { c->hs_copies = 0; return 0; }
     HIPC(c, hipSetDevice(c->device));
     HIPC(c, hipStreamSynchronize(c->stream));
-    if (c->hs_d) { (void)hipFree(c->hs_d); c->hs_d = nullptr; }
-    if (c->hsT_d) { (void)hipFree(c->hsT_d); c->hsT_d = nullptr; }
+    c->hs_d.reset();
+    c->hsT_d.reset();
     c->hs_copies = 0;
-    double2* tmp = nullptr;
-    HIPC(c, hipMalloc(&tmp, n * sizeof(double2)));
-    hipError_t e = hipMalloc(&c->hs_d, (size_t)D * n * sizeof(cf));
-    if (e != hipSuccess) { (void)hipFree(tmp); c->hs_d = nullptr; return fail(c, (int)e, "hipMalloc of the dithered transfer-function copies failed"); }
+    DevBuf<double2> tmp;
+    HIPC(c, tmp.alloc(n));
+    hipError_t e = c->hs_d.alloc((size_t)D * n);
+    if (e != hipSuccess) return fail(c, (int)e, "hipMalloc of the dithered transfer-function copies failed");
     e = hipMemcpy(tmp, hs64, n * sizeof(double2), hipMemcpyHostToDevice);
     if (e == hipSuccess) {
         hipLaunchKernelGGL(k_dither_copies, dim3(g_elem_grid(c, n)), dim3(256), 0, c->stream, tmp, c->hs_d, n, D);
@@ -1238,7 +1230,7 @@ int bdof_set_transfer_f64(bdof_ctx* c, const double* hs64) {
                 t[2 * ((size_t)kx * c->NY + ky)] = hs64[2 * ((size_t)ky * c->NX + kx)];
                 t[2 * ((size_t)kx * c->NY + ky) + 1] = hs64[2 * ((size_t)ky * c->NX + kx) + 1];
             }
-        e = hipMalloc(&c->hsT_d, (size_t)D * n * sizeof(cf));
+        e = c->hsT_d.alloc((size_t)D * n);
         if (e == hipSuccess) e = hipMemcpy(tmp, t.data(), n * sizeof(double2), hipMemcpyHostToDevice);
         if (e == hipSuccess) {
             hipLaunchKernelGGL(k_dither_copies, dim3(g_elem_grid(c, n)), dim3(256), 0, c->stream, tmp, c->hsT_d, n, D);
@@ -1246,7 +1238,6 @@ int bdof_set_transfer_f64(bdof_ctx* c, const double* hs64) {
         }
         c->res_dirty = true;
     }
-    (void)hipFree(tmp);
     if (e != hipSuccess) return fail(c, (int)e, "building the dithered transfer-function copies failed");
     c->hs_copies = D;
     return 0;
@@ -1296,17 +1287,14 @@ int bdof_set_probe_stack(bdof_ctx* c, const float* stack, const float* det) {
     if (int r = need_configured(c)) return r;
     HIPC(c, hipSetDevice(c->device));
     HIPC(c, hipStreamSynchronize(c->stream));
-    if (c->pstack) { (void)hipFree(c->pstack); c->pstack = nullptr; }
-    if (c->pdet) { (void)hipFree(c->pdet); c->pdet = nullptr; }
-    if (c->pdetT) { (void)hipFree(c->pdetT); c->pdetT = nullptr; }
-    if (c->pdet64) { (void)hipFree(c->pdet64); c->pdet64 = nullptr; }          // a host-supplied stack comes in float32 only
-    if (c->pdetT64) { (void)hipFree(c->pdetT64); c->pdetT64 = nullptr; }
+    c->pstack.reset(); c->pdet.reset(); c->pdetT.reset();
+    c->pdet64.reset(); c->pdetT64.reset();                     // a host-supplied stack comes in float32 only
     c->mod_dirty = true;
     if (!stack && !det) return 0;
     if (!stack || !det) return fail(c, BDOF_ERR_ARG, "bdof_set_probe_stack: both arrays or neither");
-    const size_t fld = sizeof(cf) * (size_t)c->NX * c->NY;
-    HIPC(c, hipMalloc((void**)&c->pstack, fld * (size_t)c->S));
-    HIPC(c, hipMalloc((void**)&c->pdet, fld));
+    const size_t n = (size_t)c->NX * c->NY, fld = sizeof(cf) * n;
+    HIPC(c, c->pstack.alloc(n * (size_t)c->S));
+    HIPC(c, c->pdet.alloc(n));
     HIPC(c, hipMemcpy(c->pstack, stack, fld * (size_t)c->S, hipMemcpyHostToDevice));
     HIPC(c, hipMemcpy(c->pdet, det, fld, hipMemcpyHostToDevice));
     // the streaming far-field detector works on rows [ky][kx]: the same field transposed
@@ -1316,7 +1304,7 @@ int bdof_set_probe_stack(bdof_ctx* c, const float* stack, const float* det) {
             t[2 * ((size_t)j * c->NX + i)] = det[2 * ((size_t)i * c->NY + j)];
             t[2 * ((size_t)j * c->NX + i) + 1] = det[2 * ((size_t)i * c->NY + j) + 1];
         }
-    HIPC(c, hipMalloc((void**)&c->pdetT, fld));
+    HIPC(c, c->pdetT.alloc(n));
     HIPC(c, hipMemcpy(c->pdetT, t.data(), fld, hipMemcpyHostToDevice));
     return 0;
 }
@@ -1331,81 +1319,51 @@ int bdof_set_probe_field(bdof_ctx* c, const double* probe, const double* hT, con
     if (c->det_mode == BDOF_DET_NEAR && !hdetT) return fail(c, BDOF_ERR_ARG, "hdetT required for BDOF_DET_NEAR");
     HIPC(c, hipSetDevice(c->device));
     HIPC(c, hipStreamSynchronize(c->stream));
-    if (!g_rocfft_ready) { RFC(c, rocfft_setup()); g_rocfft_ready = true; }
     const size_t n = (size_t)c->NX * c->NY, fld = sizeof(cf) * n, dbytes = sizeof(double2) * n;
-    rocfft_plan pf = nullptr, pi = nullptr;
-    rocfft_execution_info info = nullptr;
-    double2 *dp = nullptr, *dh = nullptr, *dhd = nullptr;
-    void* work = nullptr;
-    int rc = 0;
-    auto cleanup = [&]() {
-        if (pf) (void)rocfft_plan_destroy(pf);
-        if (pi) (void)rocfft_plan_destroy(pi);
-        if (info) (void)rocfft_execution_info_destroy(info);
-        for (void* q : {(void*)dp, (void*)dh, (void*)dhd, work}) if (q) (void)hipFree(q);
-    };
-#define PF_TRY(expr) do { rc = (expr); if (rc) { cleanup(); return rc; } } while (0)
-#define PF_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { cleanup(); return fail(c, (int)e_, std::string(#call) + ": " + hipGetErrorString(e_)); } } while (0)
-#define PF_RF(call) do { rocfft_status s_ = (call); if (s_ != rocfft_status_success) { cleanup(); return fail(c, BDOF_ERR_STATE, std::string(#call) + ": rocfft status " + std::to_string((int)s_)); } } while (0)
-    const size_t lengths[2] = {(size_t)c->NY, (size_t)c->NX};      // fastest dimension first: fields are [x][y]
-    PF_RF(rocfft_plan_create(&pf, rocfft_placement_inplace, rocfft_transform_type_complex_forward, rocfft_precision_double, 2, lengths, 1, nullptr));
-    PF_RF(rocfft_plan_create(&pi, rocfft_placement_inplace, rocfft_transform_type_complex_inverse, rocfft_precision_double, 2, lengths, 1, nullptr));
-    size_t w1 = 0, w2 = 0;
-    PF_RF(rocfft_plan_get_work_buffer_size(pf, &w1));
-    PF_RF(rocfft_plan_get_work_buffer_size(pi, &w2));
-    PF_RF(rocfft_execution_info_create(&info));
-    PF_RF(rocfft_execution_info_set_stream(info, (void*)c->stream));
-    if (std::max(w1, w2)) {
-        PF_HIP(hipMalloc(&work, std::max(w1, w2)));
-        PF_RF(rocfft_execution_info_set_work_buffer(info, work, std::max(w1, w2)));
-    }
-    PF_HIP(hipMalloc((void**)&dp, dbytes));
-    PF_HIP(hipMalloc((void**)&dh, dbytes));
-    PF_HIP(hipMemcpy(dp, probe, dbytes, hipMemcpyHostToDevice));
-    PF_HIP(hipMemcpy(dh, hT, dbytes, hipMemcpyHostToDevice));
+    rocfft_plan pf, pi;
+    int r = field_plans(c, c->NX, c->NY, 1, true, &pf, &pi);       // fields are [x][y]
+    if (r) return r;
+    DevBuf<double2> dp, dh, dhd;
+    HIPC(c, dp.alloc(n));
+    HIPC(c, dh.alloc(n));
+    HIPC(c, hipMemcpy(dp, probe, dbytes, hipMemcpyHostToDevice));
+    HIPC(c, hipMemcpy(dh, hT, dbytes, hipMemcpyHostToDevice));
     if (hdetT) {
-        PF_HIP(hipMalloc((void**)&dhd, dbytes));
-        PF_HIP(hipMemcpy(dhd, hdetT, dbytes, hipMemcpyHostToDevice));
+        HIPC(c, dhd.alloc(n));
+        HIPC(c, hipMemcpy(dhd, hdetT, dbytes, hipMemcpyHostToDevice));
     }
-    if (c->pstack) { (void)hipFree(c->pstack); c->pstack = nullptr; }
-    if (c->pdet) { (void)hipFree(c->pdet); c->pdet = nullptr; }
-    if (c->pdetT) { (void)hipFree(c->pdetT); c->pdetT = nullptr; }
-    if (c->pdet64) { (void)hipFree(c->pdet64); c->pdet64 = nullptr; }
-    if (c->pdetT64) { (void)hipFree(c->pdetT64); c->pdetT64 = nullptr; }
-    PF_HIP(hipMalloc((void**)&c->pstack, fld * (size_t)c->S));
-    PF_HIP(hipMalloc((void**)&c->pdet, fld));
-    PF_HIP(hipMalloc((void**)&c->pdetT, fld));
-    PF_HIP(hipMalloc((void**)&c->pdet64, dbytes));
-    PF_HIP(hipMalloc((void**)&c->pdetT64, dbytes));
+    c->pstack.reset(); c->pdet.reset(); c->pdetT.reset();
+    c->pdet64.reset(); c->pdetT64.reset();
+    HIPC(c, c->pstack.alloc(n * (size_t)c->S));
+    HIPC(c, c->pdet.alloc(n));
+    HIPC(c, c->pdetT.alloc(n));
+    HIPC(c, c->pdet64.alloc(n));
+    HIPC(c, c->pdetT64.alloc(n));
     const int grid = g_elem_grid(c, n);
     void* buf[1] = {dp};
     auto step = [&](const double2* h) -> int {
-        if (rocfft_execute(pf, buf, nullptr, info) != rocfft_status_success) return fail(c, BDOF_ERR_STATE, "rocfft_execute (double) failed");
+        if (rocfft_execute(pf, buf, nullptr, c->fft.info) != rocfft_status_success) return fail(c, BDOF_ERR_STATE, "rocfft_execute (double) failed");
         hipLaunchKernelGGL(k_d_mul, dim3(grid), dim3(256), 0, c->stream, dp, h, n, 1.0 / (double)n);
-        if (rocfft_execute(pi, buf, nullptr, info) != rocfft_status_success) return fail(c, BDOF_ERR_STATE, "rocfft_execute (double) failed");
+        if (rocfft_execute(pi, buf, nullptr, c->fft.info) != rocfft_status_success) return fail(c, BDOF_ERR_STATE, "rocfft_execute (double) failed");
         return 0;
     };
     for (int z = 0; z < c->S; ++z) {
         hipLaunchKernelGGL(k_d_to_f, dim3(grid), dim3(256), 0, c->stream, dp, c->pstack + (size_t)z * n, c->NX, c->NY, 0);
-        if (z < c->S - 1) PF_TRY(step(dh));
+        if (z < c->S - 1 && (r = step(dh))) return r;
     }
     if (c->det_mode == BDOF_DET_FAR) {
-        if (rocfft_execute(pf, buf, nullptr, info) != rocfft_status_success) { cleanup(); return fail(c, BDOF_ERR_STATE, "rocfft_execute (double) failed"); }
+        if (rocfft_execute(pf, buf, nullptr, c->fft.info) != rocfft_status_success) return fail(c, BDOF_ERR_STATE, "rocfft_execute (double) failed");
     } else {
-        if (c->variant == BDOF_VARIANT_TF_ALL) PF_TRY(step(dh));
-        if (c->det_mode == BDOF_DET_NEAR) PF_TRY(step(dhd));
+        if (c->variant == BDOF_VARIANT_TF_ALL && (r = step(dh))) return r;
+        if (c->det_mode == BDOF_DET_NEAR && (r = step(dhd))) return r;
     }
     hipLaunchKernelGGL(k_d_to_f, dim3(grid), dim3(256), 0, c->stream, dp, c->pdet, c->NX, c->NY, 0);
     hipLaunchKernelGGL(k_d_to_f, dim3(grid), dim3(256), 0, c->stream, dp, c->pdetT, c->NX, c->NY, 1);
     // ... and unrounded: the detector kernels add the scattered wave to these and take |d| - m in float64 (loss_seed_f64)
     hipLaunchKernelGGL(k_d_copy, dim3(grid), dim3(256), 0, c->stream, dp, c->pdet64, c->NX, c->NY, 0);
     hipLaunchKernelGGL(k_d_copy, dim3(grid), dim3(256), 0, c->stream, dp, c->pdetT64, c->NX, c->NY, 1);
-    PF_HIP(hipGetLastError());
-    PF_HIP(hipStreamSynchronize(c->stream));
-#undef PF_TRY
-#undef PF_HIP
-#undef PF_RF
-    cleanup();
+    HIPC(c, hipGetLastError());
+    HIPC(c, hipStreamSynchronize(c->stream));         // the temporaries go when this returns: nothing queued may still read them
     // the wave is carried as p_z + eps_z with eps_0 = 0: no probe of its own, no scalar carrier
     HIPC(c, hipMemsetAsync(c->probe, 0, fld, c->stream));
     c->a0 = 0.0;
@@ -1438,9 +1396,7 @@ int bdof_set_rotation_adjoint(bdof_ctx* c, const int* off, const int* order, int
     if (!c || !off || !order || n_dest < 1) return BDOF_ERR_ARG;
     c->adj_off = off; c->adj_order = order; c->adj_ndest = n_dest;
     HIPC(c, hipSetDevice(c->device));
-    if (c->heavy) (void)hipFree(c->heavy);
-    c->heavy = nullptr;
-    HIPC(c, hipMalloc((void**)&c->heavy, sizeof(int) * ((size_t)n_dest + 1)));
+    HIPC(c, c->heavy.alloc((size_t)n_dest + 1));
     return 0;
 }
 
@@ -1606,10 +1562,10 @@ int bdof_adjoint_range(bdof_ctx* c, int B, const int* angle_of_b, const int* xof
         const int Bg = groups[gi].B;
         use_group(c, groups[gi]);
         // phi_{zt} = P^H psi_{zt+1} and G(phi_{zt}) = P^H G(psi_{zt+1}): real space -> R (transposed) -> adjoint step
-        RealToHybArgs ra{sub_field(c, (const cf*)end_real), sub_field(c, c->bufA), Bg, c->NX, c->twY};
+        RealToHybArgs ra{sub_field(c, (const cf*)end_real), sub_field<cf>(c, c->bufA), Bg, c->NX, c->twY};
         DISPATCH_N(c->NY, { hipLaunchKernelGGL((k_row_real_to_hyb<N_>), dim3(rows_grid<N_>(c, Bg, c->NX)), dim3(BDOF_THREADS), 0, c->sub_stream, ra); });
         launch_row_prop(c, Bg, c->bufA, rc1, c->hs, 1.f, 1, zt);
-        RealToHybArgs rg{sub_field(c, (const cf*)g_end_real), sub_field(c, c->bufA), Bg, c->NX, c->twY};
+        RealToHybArgs rg{sub_field(c, (const cf*)g_end_real), sub_field<cf>(c, c->bufA), Bg, c->NX, c->twY};
         DISPATCH_N(c->NY, { hipLaunchKernelGGL((k_row_real_to_hyb<N_>), dim3(rows_grid<N_>(c, Bg, c->NX)), dim3(BDOF_THREADS), 0, c->sub_stream, rg); });
         launch_row_prop(c, Bg, c->bufA, c->bufB, c->hs, 1.f, 1, zt);
     }
@@ -1683,40 +1639,6 @@ int bdof_tiles_grad_add(bdof_ctx* c, const void* grot_range, void* gvol, int B, 
 }
 
 // ---- whole-field / tile-batch operations in either precision (bdof_field.h) ------------------------------------------------
-static int field_plans(bdof_ctx* c, int NX, int NY, int B, bool dbl, rocfft_plan* fwd, rocfft_plan* inv) {
-    if (!g_rocfft_ready) { RFC(c, rocfft_setup()); g_rocfft_ready = true; }
-    const std::array<int, 4> key{NX, NY, B, dbl ? 1 : 0};
-    auto it = c->fplans.find(key);
-    if (it == c->fplans.end()) {
-        const size_t lengths[2] = {(size_t)NY, (size_t)NX};             // fastest dimension first
-        const rocfft_precision prec = dbl ? rocfft_precision_double : rocfft_precision_single;
-        rocfft_plan pf = nullptr, pi = nullptr;
-        RFC(c, rocfft_plan_create(&pf, rocfft_placement_inplace, rocfft_transform_type_complex_forward, prec, 2, lengths, (size_t)B, nullptr));
-        RFC(c, rocfft_plan_create(&pi, rocfft_placement_inplace, rocfft_transform_type_complex_inverse, prec, 2, lengths, (size_t)B, nullptr));
-        size_t w1 = 0, w2 = 0;
-        RFC(c, rocfft_plan_get_work_buffer_size(pf, &w1));
-        RFC(c, rocfft_plan_get_work_buffer_size(pi, &w2));
-        const size_t need = std::max(w1, w2);
-        if (need > c->gwork_sz) {
-            HIPC(c, hipStreamSynchronize(c->stream));
-            if (c->gwork) (void)hipFree(c->gwork);
-            c->gwork = nullptr;
-            c->gwork_sz = 0;
-            HIPC(c, hipMalloc(&c->gwork, need));
-            c->gwork_sz = need;
-        }
-        it = c->fplans.emplace(key, std::make_pair(pf, pi)).first;
-    }
-    if (!c->ginfo) {
-        RFC(c, rocfft_execution_info_create(&c->ginfo));
-        RFC(c, rocfft_execution_info_set_stream(c->ginfo, (void*)c->stream));
-    }
-    if (c->gwork_sz) RFC(c, rocfft_execution_info_set_work_buffer(c->ginfo, c->gwork, c->gwork_sz));
-    *fwd = it->second.first;
-    *inv = it->second.second;
-    return 0;
-}
-
 // fields[b] <- F^-1 ( h * F fields[b] ) for B fields [NX][NY] in place; h[kx][ky] carries 1 / (NX NY) (and any power of the
 // transfer function: np_funcs.py:42 composes in free space); is_double: complex128 fields and table, else complex64
 int bdof_fields_free_step(bdof_ctx* c, void* fields, int B, int NX, int NY, const void* h, int conj_h, int is_double) {
@@ -1727,10 +1649,10 @@ int bdof_fields_free_step(bdof_ctx* c, void* fields, int B, int NX, int NY, cons
     if (r) return r;
     void* buf[1] = {fields};
     const size_t per = (size_t)NX * NY, n = per * B;
-    RFC(c, rocfft_execute(pf, buf, nullptr, c->ginfo));
+    RFC(c, rocfft_execute(pf, buf, nullptr, c->fft.info));
     if (is_double) hipLaunchKernelGGL(k_f_hmul<double2>, dim3(g_elem_grid(c, n)), dim3(256), 0, c->stream, (double2*)fields, (const double2*)h, per, n, conj_h);
     else hipLaunchKernelGGL(k_f_hmul<float2>, dim3(g_elem_grid(c, n)), dim3(256), 0, c->stream, (float2*)fields, (const float2*)h, per, n, conj_h);
-    RFC(c, rocfft_execute(pi, buf, nullptr, c->ginfo));
+    RFC(c, rocfft_execute(pi, buf, nullptr, c->fft.info));
     return launched(c);
 }
 
@@ -1749,31 +1671,21 @@ int bdof_fields_free_step_aux(bdof_ctx* c, void* fields, const void* src, int B,
         HIPC(c, hipStreamCreateWithFlags(&c->aux, hipStreamNonBlocking));
         HIPC(c, hipEventCreateWithFlags(&c->ev_aux_fork, hipEventDisableTiming));
         HIPC(c, hipEventCreateWithFlags(&c->ev_aux_join, hipEventDisableTiming));
-        RFC(c, rocfft_execution_info_create(&c->ginfo_aux));
-        RFC(c, rocfft_execution_info_set_stream(c->ginfo_aux, (void*)c->aux));
     }
     size_t w1 = 0, w2 = 0;
     RFC(c, rocfft_plan_get_work_buffer_size(pf, &w1));
     RFC(c, rocfft_plan_get_work_buffer_size(pi, &w2));
-    const size_t need = std::max(w1, w2);
-    if (need > c->gwork_aux_sz) {
-        HIPC(c, hipStreamSynchronize(c->aux));
-        if (c->gwork_aux) (void)hipFree(c->gwork_aux);
-        c->gwork_aux = nullptr; c->gwork_aux_sz = 0;
-        HIPC(c, hipMalloc(&c->gwork_aux, need));
-        c->gwork_aux_sz = need;
-    }
-    if (c->gwork_aux_sz) RFC(c, rocfft_execution_info_set_work_buffer(c->ginfo_aux, c->gwork_aux, c->gwork_aux_sz));
+    if ((r = fft_exec_room(c, c->fft_aux, c->aux, std::max(w1, w2)))) return r;
     const size_t per = (size_t)NX * NY, n = per * B, esz = is_double ? sizeof(double2) : sizeof(float2);
     HIPC(c, hipEventRecord(c->ev_aux_fork, c->stream));
     HIPC(c, hipStreamWaitEvent(c->aux, c->ev_aux_fork, 0));
     c->aux_pending = true;
     if (src) HIPC(c, hipMemcpyAsync(fields, src, n * esz, hipMemcpyDeviceToDevice, c->aux));
     void* buf[1] = {fields};
-    RFC(c, rocfft_execute(pf, buf, nullptr, c->ginfo_aux));
+    RFC(c, rocfft_execute(pf, buf, nullptr, c->fft_aux.info));
     if (is_double) hipLaunchKernelGGL(k_f_hmul<double2>, dim3(g_elem_grid(c, n)), dim3(256), 0, c->aux, (double2*)fields, (const double2*)h, per, n, conj_h);
     else hipLaunchKernelGGL(k_f_hmul<float2>, dim3(g_elem_grid(c, n)), dim3(256), 0, c->aux, (float2*)fields, (const float2*)h, per, n, conj_h);
-    RFC(c, rocfft_execute(pi, buf, nullptr, c->ginfo_aux));
+    RFC(c, rocfft_execute(pi, buf, nullptr, c->fft_aux.info));
     return launched(c);
 }
 
@@ -1789,12 +1701,9 @@ int bdof_range_carrier_build(bdof_ctx* c, void* p0, void* stack, int B, int NX, 
     hipLaunchKernelGGL(k_f_to_float, dim3(g_elem_grid(c, n)), dim3(256), 0, c->stream, (const double2*)p0, (cf*)stack, n);
     if (nz > 1) {
         const size_t need = n * (size_t)(nz - 1);
-        if (need > c->car_scratch_n) {
+        if (c->car_scratch.size() < need) {
             HIPC(c, hipStreamSynchronize(c->stream));
-            if (c->car_scratch) (void)hipFree(c->car_scratch);
-            c->car_scratch = nullptr; c->car_scratch_n = 0;
-            HIPC(c, hipMalloc(&c->car_scratch, need * sizeof(double2)));
-            c->car_scratch_n = need;
+            HIPC(c, c->car_scratch.alloc(need));
         }
         rocfft_plan pf, pi, qf, qi;
         int r = field_plans(c, NX, NY, B, true, &pf, &pi);
@@ -1802,11 +1711,11 @@ int bdof_range_carrier_build(bdof_ctx* c, void* p0, void* stack, int B, int NX, 
         if ((r = field_plans(c, NX, NY, B * (nz - 1), true, &qf, &qi))) return r;       // (sizes the shared work buffer for both)
         if ((r = field_plans(c, NX, NY, B, true, &pf, &pi))) return r;
         void* b0[1] = {p0};
-        RFC(c, rocfft_execute(pf, b0, nullptr, c->ginfo));
+        RFC(c, rocfft_execute(pf, b0, nullptr, c->fft.info));
         hipLaunchKernelGGL(k_carrier_spectra, dim3(g_elem_grid(c, n)), dim3(256), 0, c->stream, (const double2*)p0, (const double2*)h, c->car_scratch,
                            per, B, nz, (double)NX * (double)NY);
         void* b1[1] = {c->car_scratch};
-        RFC(c, rocfft_execute(qi, b1, nullptr, c->ginfo));
+        RFC(c, rocfft_execute(qi, b1, nullptr, c->fft.info));
         hipLaunchKernelGGL(k_f_to_float, dim3(g_elem_grid(c, need)), dim3(256), 0, c->stream, (const double2*)c->car_scratch, (cf*)stack + n, need);
     }
     return launched(c);
@@ -1901,9 +1810,9 @@ int bdof_forward_range_f64(bdof_ctx* c, int B, const int* angle_of_b, const int*
         Mod64Args m{(double2*)fields, o, B, c->NX, c->NY, z, k, nullptr};
         hipLaunchKernelGGL(k_f64_modulate, dim3(g_elem_grid(c, n)), dim3(256), 0, c->stream, m);
         if (z < z0 + nz - 1 || prop_last) {
-            RFC(c, rocfft_execute(pf, buf, nullptr, c->ginfo));
+            RFC(c, rocfft_execute(pf, buf, nullptr, c->fft.info));
             hipLaunchKernelGGL(k_f_hmul<double2>, dim3(g_elem_grid(c, n)), dim3(256), 0, c->stream, (double2*)fields, (const double2*)h, per, n, 0);
-            RFC(c, rocfft_execute(pi, buf, nullptr, c->ginfo));
+            RFC(c, rocfft_execute(pi, buf, nullptr, c->fft.info));
         }
     }
     return launched(c);
@@ -1918,13 +1827,13 @@ static int c64_room(bdof_ctx* c, int B, bool tf, size_t M) {
     const bool have = c->c64_B >= B && c->c64_psi && c->c64_tape && (tf || (c->c64_q && c->c64_big));
     if (have) return 0;
     HIPC(c, hipStreamSynchronize(c->stream));
-    for (double2** q : {&c->c64_psi, &c->c64_q, &c->c64_big, &c->c64_tape}) { if (*q) (void)hipFree(*q); *q = nullptr; }
+    c->c64_psi.reset(); c->c64_q.reset(); c->c64_big.reset(); c->c64_tape.reset();      // all four go before any comes back
     c->c64_B = 0;
-    HIPC(c, hipMalloc(&c->c64_psi, n * sizeof(double2)));
-    HIPC(c, hipMalloc(&c->c64_tape, (size_t)c->S * n * sizeof(double2)));
+    HIPC(c, c->c64_psi.alloc(n));
+    HIPC(c, c->c64_tape.alloc((size_t)c->S * n));
     if (!tf) {
-        HIPC(c, hipMalloc(&c->c64_q, n * sizeof(double2)));
-        HIPC(c, hipMalloc(&c->c64_big, M * M * (size_t)B * sizeof(double2)));
+        HIPC(c, c->c64_q.alloc(n));
+        HIPC(c, c->c64_big.alloc(M * M * (size_t)B));
     }
     c->c64_B = B;
     return 0;
@@ -1942,13 +1851,13 @@ int bdof_set_conv_f64(bdof_ctx* c, const double* probe, const double* khat, int 
     HIPC(c, hipStreamSynchronize(c->stream));
     const size_t n = (size_t)c->NX * c->NY, M = (size_t)c->NX + ks - 1;
     if (c->c64_ks != ks) {
-        for (double2** q : {&c->c64_khat, &c->c64_big}) { if (*q) (void)hipFree(*q); *q = nullptr; }
+        c->c64_khat.reset(); c->c64_big.reset();
         c->c64_B = 0;
     }
-    if (!c->c64_probe) HIPC(c, hipMalloc(&c->c64_probe, n * sizeof(double2)));
-    if (!c->c64_khat) HIPC(c, hipMalloc(&c->c64_khat, M * M * sizeof(double2)));
-    if (!c->c64_scal) HIPC(c, hipMalloc(&c->c64_scal, 2 * sizeof(double2)));
-    if (!c->c64_part) HIPC(c, hipMalloc(&c->c64_part, (size_t)c->ncu * 16 * sizeof(double2)));
+    if (!c->c64_probe) HIPC(c, c->c64_probe.alloc(n));
+    if (!c->c64_khat) HIPC(c, c->c64_khat.alloc(M * M));
+    if (!c->c64_scal) HIPC(c, c->c64_scal.alloc(2));
+    if (!c->c64_part) HIPC(c, c->c64_part.alloc((size_t)c->ncu * 16));
     HIPC(c, hipMemcpy(c->c64_probe, probe, n * sizeof(double2), hipMemcpyHostToDevice));
     HIPC(c, hipMemcpy(c->c64_khat, khat, M * M * sizeof(double2), hipMemcpyHostToDevice));
     c->c64_ks = ks;
@@ -1966,8 +1875,8 @@ int bdof_set_conv_f64_detector(bdof_ctx* c, const double* hdetT) {
     HIPC(c, hipSetDevice(c->device));
     HIPC(c, hipStreamSynchronize(c->stream));
     const size_t n = (size_t)c->NX * c->NY;
-    if (!hdetT) { if (c->c64_hdet) (void)hipFree(c->c64_hdet); c->c64_hdet = nullptr; return 0; }
-    if (!c->c64_hdet) HIPC(c, hipMalloc(&c->c64_hdet, n * sizeof(double2)));
+    if (!hdetT) { c->c64_hdet.reset(); return 0; }
+    if (!c->c64_hdet) HIPC(c, c->c64_hdet.alloc(n));
     HIPC(c, hipMemcpy(c->c64_hdet, hdetT, n * sizeof(double2), hipMemcpyHostToDevice));
     return 0;
 }
@@ -2015,12 +1924,12 @@ int bdof_loss_grad_conv_f64(bdof_ctx* c, int B, const int* angle_of_b, const int
     const bool far = c->det_mode == BDOF_DET_FAR;
     void* buf[1] = {psi};
     const bool near = c->det_mode == BDOF_DET_NEAR;
-    if (far) RFC(c, rocfft_execute(pf, buf, nullptr, c->ginfo));           // un-shifted, un-normalised fft2 (propagation.py:114-115)
+    if (far) RFC(c, rocfft_execute(pf, buf, nullptr, c->fft.info));           // un-shifted, un-normalised fft2 (propagation.py:114-115)
     else if (near) { if ((r = bdof_fields_free_step(c, psi, B, N, N, c->c64_hdet, 0, 1))) return r; }      // propagation.py:122-124
     const int lgrid = std::min(eg, c->npartial);
     hipLaunchKernelGGL(k_c64_loss, dim3(lgrid), dim3(256), 0, c->stream, psi, meas, c->partial, B, N, N, far ? 1 : 0, meas_ref, 2.0 / (double)n);
     hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, c->stream, c->partial, lgrid, 1.0 / (double)n, c->loss_dev);
-    if (far) RFC(c, rocfft_execute(pi, buf, nullptr, c->ginfo));           // G(q) = N^2 ifft2(G(d)): the un-normalised inverse
+    if (far) RFC(c, rocfft_execute(pi, buf, nullptr, c->fft.info));           // G(q) = N^2 ifft2(G(d)): the un-normalised inverse
     else if (near) { if ((r = bdof_fields_free_step(c, psi, B, N, N, c->c64_hdet, 1, 1))) return r; }
     // adjoint of the renormalisation through the corner pixel
     const int dgrid = std::min(eg, c->ncu * 16);
@@ -2050,9 +1959,9 @@ int bdof_set_tf_f64(bdof_ctx* c, const double* probe, const double* hT, const do
     HIPC(c, hipSetDevice(c->device));
     HIPC(c, hipStreamSynchronize(c->stream));
     const size_t n = (size_t)c->NX * c->NY;
-    if (!c->c64_probe) HIPC(c, hipMalloc(&c->c64_probe, n * sizeof(double2)));
-    if (!c->c64_h) HIPC(c, hipMalloc(&c->c64_h, n * sizeof(double2)));
-    if (hdetT && !c->c64_hdet) HIPC(c, hipMalloc(&c->c64_hdet, n * sizeof(double2)));
+    if (!c->c64_probe) HIPC(c, c->c64_probe.alloc(n));
+    if (!c->c64_h) HIPC(c, c->c64_h.alloc(n));
+    if (hdetT && !c->c64_hdet) HIPC(c, c->c64_hdet.alloc(n));
     HIPC(c, hipMemcpy(c->c64_probe, probe, n * sizeof(double2), hipMemcpyHostToDevice));
     HIPC(c, hipMemcpy(c->c64_h, hT, n * sizeof(double2), hipMemcpyHostToDevice));
     if (hdetT) HIPC(c, hipMemcpy(c->c64_hdet, hdetT, n * sizeof(double2), hipMemcpyHostToDevice));
@@ -2094,12 +2003,12 @@ int bdof_loss_grad_tf_f64(bdof_ctx* c, int B, const int* angle_of_b, const int* 
     }
     void* buf[1] = {psi};
     if (c->det_mode == BDOF_DET_NEAR) { if ((r = bdof_fields_free_step(c, psi, B, NX, NY, c->c64_hdet, 0, 1))) return r; }
-    else if (far) RFC(c, rocfft_execute(pf, buf, nullptr, c->ginfo));       // un-shifted, un-normalised fft2
+    else if (far) RFC(c, rocfft_execute(pf, buf, nullptr, c->fft.info));       // un-shifted, un-normalised fft2
     const int lgrid = std::min(eg, c->npartial);
     hipLaunchKernelGGL(k_c64_loss, dim3(lgrid), dim3(256), 0, c->stream, psi, meas, c->partial, B, NX, NY, far ? 1 : 0, meas_ref, 2.0 / (double)n);
     hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, c->stream, c->partial, lgrid, 1.0 / (double)n, c->loss_dev);
     if (c->det_mode == BDOF_DET_NEAR) { if ((r = bdof_fields_free_step(c, psi, B, NX, NY, c->c64_hdet, 1, 1))) return r; }
-    else if (far) RFC(c, rocfft_execute(pi, buf, nullptr, c->ginfo));       // F^H: the un-normalised inverse
+    else if (far) RFC(c, rocfft_execute(pi, buf, nullptr, c->fft.info));       // F^H: the un-normalised inverse
     for (int z = S - 1; z >= 0; --z) {
         if (z < S - 1 || prop_last)
             if ((r = bdof_fields_free_step(c, psi, B, NX, NY, c->c64_h, 1, 1))) return r;
@@ -2241,11 +2150,11 @@ int bdof_set_conv(bdof_ctx* c, const float* ky, const float* kx, int ks, double 
     c->ksum = std::complex<double>(ksum_re, ksum_im);
     c->k_conv = (float)k;
     const size_t fld = (size_t)c->Bmax * c->NX * c->NY;
-    if (!c->bufC) HIPC(c, hipMalloc((void**)&c->bufC, sizeof(cf) * fld));
-    if (!c->conv_scal) HIPC(c, hipMalloc((void**)&c->conv_scal, sizeof(cf) * 4));
+    if (!c->bufC) HIPC(c, c->bufC.alloc(fld));
+    if (!c->conv_scal) HIPC(c, c->conv_scal.alloc(4));
     HIPC(c, hipStreamSynchronize(c->stream));                  // a sweep still in flight reads the previous taps
-    if (c->taps_dev && c->taps_copies != 1) { (void)hipFree(c->taps_dev); c->taps_dev = nullptr; }
-    if (!c->taps_dev) HIPC(c, hipMalloc((void**)&c->taps_dev, sizeof(ConvTaps)));
+    if (c->taps_copies != 1) c->taps_dev.reset();
+    if (!c->taps_dev) HIPC(c, c->taps_dev.alloc(1));
     c->taps_copies = 1;
     HIPC(c, hipMemcpy(c->taps_dev, &c->taps, sizeof(ConvTaps), hipMemcpyHostToDevice));
     c->have_conv = true;
@@ -2272,9 +2181,7 @@ int bdof_set_conv_taps_f64(bdof_ctx* c, const double* ky, const double* kx, doub
         t[d].e = make_float2(dither_pick(e_re, d, 0.25), dither_pick(e_im, d, 0.75));
     }
     HIPC(c, hipStreamSynchronize(c->stream));
-    if (c->taps_dev) (void)hipFree(c->taps_dev);
-    c->taps_dev = nullptr;
-    HIPC(c, hipMalloc((void**)&c->taps_dev, sizeof(ConvTaps) * D));
+    HIPC(c, c->taps_dev.alloc((size_t)D));
     HIPC(c, hipMemcpy(c->taps_dev, t.data(), sizeof(ConvTaps) * D, hipMemcpyHostToDevice));
     c->taps_copies = D;
     return 0;
@@ -2402,14 +2309,14 @@ int bdof_set_conv_probe_stack(bdof_ctx* c, const float* stack, const double* det
     if (int r = need_configured(c)) return r;
     HIPC(c, hipSetDevice(c->device));
     HIPC(c, hipStreamSynchronize(c->stream));
-    if (c->cstack) { (void)hipFree(c->cstack); c->cstack = nullptr; }
-    if (c->cdet64) { (void)hipFree(c->cdet64); c->cdet64 = nullptr; }
+    c->cstack.reset();
+    c->cdet64.reset();
     if (!stack && !det64) return 0;
     if (!stack || !det64) return fail(c, BDOF_ERR_ARG, "bdof_set_conv_probe_stack: both arrays or neither");
     if (!c->have_conv) return fail(c, BDOF_ERR_STATE, "bdof_set_conv has not been called");
     const size_t plane = (size_t)c->NX * c->NY;
-    HIPC(c, hipMalloc((void**)&c->cstack, sizeof(cf) * plane * (size_t)(c->S + 1)));
-    HIPC(c, hipMalloc((void**)&c->cdet64, sizeof(double2) * plane));
+    HIPC(c, c->cstack.alloc(plane * (size_t)(c->S + 1)));
+    HIPC(c, c->cdet64.alloc(plane));
     HIPC(c, hipMemcpy(c->cstack, stack, sizeof(cf) * plane * (size_t)(c->S + 1), hipMemcpyHostToDevice));
     HIPC(c, hipMemcpy(c->cdet64, det64, sizeof(double2) * plane, hipMemcpyHostToDevice));
     c->c_p0 = std::complex<double>(p0_re, p0_im);
@@ -2566,11 +2473,10 @@ int bdof_enable_probe_grad(bdof_ctx* c, int enable) {
     HIPC(c, hipSetDevice(c->device));
     if (enable && !c->gpsi0) {
         if (!c->with_grad) return fail(c, BDOF_ERR_STATE, "the probe gradient needs bdof_configure(with_grad=1)");
-        HIPC(c, hipMalloc((void**)&c->gpsi0, sizeof(cf) * (size_t)c->Bmax * c->NX * c->NY));
+        HIPC(c, c->gpsi0.alloc((size_t)c->Bmax * c->NX * c->NY));
     } else if (!enable && c->gpsi0) {
         HIPC(c, hipStreamSynchronize(c->stream));
-        (void)hipFree(c->gpsi0);
-        c->gpsi0 = nullptr;
+        c->gpsi0.reset();
     }
     c->gpsi_src = nullptr;
     return 0;
@@ -2641,15 +2547,12 @@ int bdof_window_rotation_adjoint(bdof_ctx* c, int B, int angle, const int* xoff,
         hipLaunchKernelGGL(k_window_rot_adjoint, dim3(grid), dim3(256), 0, c->stream, a);
         return launched(c);
     }
-    const size_t need = sizeof(float2) * (size_t)n_src * c->obj.volNY;
-    if (c->winpad_sz < need) {
+    const size_t need = (size_t)n_src * c->obj.volNY;
+    if (c->winpad.size() < need) {
         HIPC(c, hipStreamSynchronize(c->stream));
-        if (c->winpad) (void)hipFree(c->winpad);
-        c->winpad = nullptr; c->winpad_sz = 0;
-        HIPC(c, hipMalloc((void**)&c->winpad, need));
-        c->winpad_sz = need;
+        HIPC(c, c->winpad.alloc(need));
     }
-    if (!c->win_angle) HIPC(c, hipMalloc((void**)&c->win_angle, sizeof(int)));
+    if (!c->win_angle) HIPC(c, c->win_angle.alloc(1));
     HIPC(c, hipMemsetD32Async((hipDeviceptr_t)c->win_angle, angle, 1, c->stream));
     // stage 1: windows -> rotated frame
     const int z_per_wg = 8;
