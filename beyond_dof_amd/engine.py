@@ -10,12 +10,12 @@ from . import _lib
 from ._lib import DeviceBuffer
 from . import util
 
-_DET = {None: _lib.DET_NONE, 'inf': _lib.DET_FAR}
 _VARIANT = {'numpy_skip_last': _lib.VARIANT_NUMPY_SKIP_LAST, 'tf_all': _lib.VARIANT_TF_ALL}
 
 
-def _idx_buf(ctx, values):
-    return DeviceBuffer.from_host(ctx, np.asarray(values, dtype=np.int32))
+def _hp(arr):
+    """Host pointer of a numpy array for a library call (None stays None)."""
+    return None if arr is None else arr.ctypes.data
 
 
 RESIDENT_SIZES = (32, 36, 48, 64, 72, 80, 96, 128)      # square fields with an LDS-resident plan (csrc/bdof_resident.h)
@@ -38,19 +38,33 @@ class MultisliceEngine(object):
         self.recompute = bool(recompute)
         self.adjoint64 = bool(adjoint64) and bool(with_grad)
         self.ctx = _lib.Context(device, stream)
-        self.lib = self.ctx.lib
-        self.h = self.ctx.handle
+        self.lib, self.h = self.ctx.lib, self.ctx.handle
         self.ny, self.nx, self.n_slice, self.batch_max = int(ny), int(nx), int(n_slice), int(batch_max)
         self.with_grad = bool(with_grad)
         flags = (_lib.CFG_GRAD if with_grad else 0) | (_lib.CFG_GENERIC if force_generic else 0) \
             | (_lib.CFG_NO_RESIDENT if engine == 'streaming' else 0) | (_lib.CFG_ALWAYS_RESIDENT if engine == 'resident' else 0) \
             | (_lib.CFG_RECOMPUTE if self.recompute else 0) | (_lib.CFG_NO_GROT if no_grot else 0) | (_lib.CFG_ADJOINT64 if self.adjoint64 else 0)
         self.ctx.check(self.lib.bdof_configure(self.h, self.ny, self.nx, self.n_slice, self.batch_max, flags))
-        self._engine_arg = 'generic' if force_generic else engine
-        self._device = device
-        self.det_mode = _lib.DET_NONE
-        self._keep = {}          # device buffers that must outlive the calls that registered them
-        self._tables = None
+        self._reset_host_state()
+
+    # Host state: what the setters below record on the instance; before that, and after _reset_host_state(), as declared here.
+    optics = None               # util.Optics of set_physics
+    variant = k = None
+    det_mode, det_kernel = _lib.DET_NONE, 'TF'
+    _far_phase = None
+    _conv_kernel = None         # (ky, kx, e) of set_conv; None: the transfer-function propagator only
+    _conv_k64 = None
+    _probe_args = None          # (real, imag) of set_probe: re-issued when the physics or the propagator change
+    probe_stack, probe_gain = False, 1.0
+    meas_ref = 0.0
+    tf_f64 = conv_f64 = False
+    _gprobe = None              # enable_probe_grad
+    residual_split = True       # False: amplitudes go to the device as they are (a probe that changes between steps)
+
+    def _reset_host_state(self):
+        for name in set(vars(self)) & set(vars(MultisliceEngine)):
+            delattr(self, name)
+        self._keep = {}         # device buffers that must outlive the calls that registered them
 
     # ---- physics -------------------------------------------------------------------------------
     def set_physics(self, energy_ev, psize_cm, free_prop_cm=None, variant='numpy_skip_last', pi=util.PI, field_shape=None,
@@ -59,59 +73,55 @@ class MultisliceEngine(object):
         engine's wavefields are tiles of a (FY, FX) field and apply that field's propagator (util.get_kernel_tile).
         detector_kernel: 'TF' (what np_funcs.py:55 forces), 'IR' (get_kernel_ir, np_funcs.py:59-61) or 'auto' (the sampling
         criterion of np_funcs.py:51-53) for the step to a detector at a finite distance."""
-        voxel_nm = np.array([psize_cm] * 3) * 1.e7 if np.isscalar(psize_cm) else np.array(psize_cm) * 1.e7
-        lmbda_nm = 1240. / energy_ev
-        delta_nm = voxel_nm[-1]
-        k = 2. * pi * delta_nm / lmbda_nm
-        hs64 = util.device_transfer_function(delta_nm, lmbda_nm, voxel_nm, self.ny, self.nx, pi=pi, field_shape=field_shape, dtype=np.complex128)
+        o = util.Optics(energy_ev, psize_cm, free_prop_cm, pi, self.ny, self.nx, field_shape)
+        det_mode = _lib.DET_NONE if free_prop_cm is None else _lib.DET_FAR if o.det_nm is None else _lib.DET_NEAR
+        det_kernel = 'TF'
+        if det_mode == _lib.DET_NEAR:
+            det_kernel = util.detector_kernel_kind(detector_kernel, o.det_nm, o.lmbda_nm, o.voxel_nm, (self.ny, self.nx))
+        self.optics, self.variant, self.k = o, variant, o.k       # (a refused argument has raised by now: the old physics stay whole)
+        self.det_mode, self.det_kernel = det_mode, det_kernel
+        hs64 = o.table(o.delta_nm, tiled=True, dtype=np.complex128)       # the slice step honours field_shape ...
         hs = hs64.astype(np.complex64)
-        h00 = np.array(util.transfer_function_dc(delta_nm, lmbda_nm, voxel_nm, self.ny, self.nx, pi=pi, field_shape=field_shape))
-        hdet = hdet00 = None
-        self.det_kernel = 'TF'
-        if free_prop_cm is None:
-            det = _lib.DET_NONE
-        elif isinstance(free_prop_cm, str):
-            if free_prop_cm != 'inf':
-                raise ValueError("free_prop_cm must be None, a distance in cm or 'inf'")
-            det = _lib.DET_FAR
-        else:
-            det = _lib.DET_NEAR
-            self.det_kernel = util.detector_kernel_kind(detector_kernel, free_prop_cm * 1e7, lmbda_nm, voxel_nm, (self.ny, self.nx))
-            hdet = util.device_transfer_function(free_prop_cm * 1e7, lmbda_nm, voxel_nm, self.ny, self.nx, pi=pi, kernel=self.det_kernel)
-            hdet00 = np.array(util.transfer_function_dc(free_prop_cm * 1e7, lmbda_nm, voxel_nm, self.ny, self.nx, pi=pi, kernel=self.det_kernel))
-        self.det_mode = det
-        self.variant = variant
-        self.k = k
-        self._physics_args = (energy_ev, psize_cm, free_prop_cm, variant, pi)
-        self._field_shape = field_shape
-        self._tf64_args = (hs64, free_prop_cm, lmbda_nm, voxel_nm, pi, float(k))
+        h00 = o.dc(o.delta_nm, tiled=True)
+        hdet00 = o.dc(o.det_nm, det_kernel) if det_mode == _lib.DET_NEAR else None
+        hdet = self._detector_table(np.complex64)                          # ... the detector step does not
         self.tf_f64 = self.conv_f64 = False     # a float64 twin bound before this call held the previous tables
         # tf_all + far field: the last transfer-function step only multiplies the far field by the
         # unit-modulus H (F P phi = H . F phi); libbdof skips it and the host applies it to returned waves
         self._far_phase = None
-        if det == _lib.DET_FAR and variant == 'tf_all':
+        if self.det_mode == _lib.DET_FAR and variant == 'tf_all':
             self._far_phase = (hs.astype(np.complex128) * (self.nx * self.ny)).astype(np.complex64)
-        self.ctx.check(self.lib.bdof_set_physics(self.h, k, hs.ctypes.data, hdet.ctypes.data if hdet is not None else None,
-                                                 h00.ctypes.data, hdet00.ctypes.data if hdet00 is not None else None,
-                                                 det, _VARIANT[variant]))
+        self.ctx.check(self.lib.bdof_set_physics(self.h, o.k, hs.ctypes.data, _hp(hdet), h00.ctypes.data, _hp(hdet00),
+                                                 self.det_mode, _VARIANT[variant]))
         # the same table in float64: the streaming kernels multiply by dithered float32 copies of it (bdof_set_transfer_f64)
         self.ctx.check(self.lib.bdof_set_transfer_f64(self.h, hs64.ctypes.data))
         if self.adjoint64:
-            hd64 = None
-            if det == _lib.DET_NEAR:
-                hd64 = util.device_transfer_function(free_prop_cm * 1e7, lmbda_nm, voxel_nm, self.ny, self.nx, pi=pi, dtype=np.complex128,
-                                                     kernel=self.det_kernel)
-            self.ctx.check(self.lib.bdof_set_physics_f64(self.h, hs64.ctypes.data, hd64.ctypes.data if hd64 is not None else None))
-        if getattr(self, '_probe_args', None) is not None:
+            hd64 = self._detector_table(np.complex128)
+            self.ctx.check(self.lib.bdof_set_physics_f64(self.h, hs64.ctypes.data, _hp(hd64)))
+        if self._probe_args is not None:
             self.set_probe(*self._probe_args)      # the carrier (field, calibration) of the probe depends on the physics
+
+    def _detector_table(self, dtype, fold=True, transpose=False, tiled=False):
+        """The un-shifted multiplier of the step to a near-field detector (None without one): the one place it is built.
+        fold: 1/(nx*ny) folded in (the sweeps' tables) or not (the carrier fields').  tiled: honour field_shape, which only
+        bdof_set_probe_field's table does, and only as 'TF'; every other caller takes the (ny, nx) mesh's own."""
+        if self.det_mode != _lib.DET_NEAR:
+            return None
+        o = self.optics
+        return o.table(o.det_nm, self.det_kernel, tiled and self.det_kernel == 'TF', fold, transpose, dtype)
+
+    def _probe_field(self, round_c64=True):
+        """The (ny, nx) probe of set_probe.  round_c64: rounded to complex64 as the reference's wavefront is (np_funcs.py:20-21)
+        — set_probe and enable_tf_f64; enable_conv_f64 hands the float64 values over as they are."""
+        pr, pi = self._probe_args
+        probe = (np.asarray(pr) + 1j * np.asarray(pi)) * np.ones((self.ny, self.nx))
+        return probe.astype(np.complex64) if round_c64 else probe
 
     def _probe_stack(self, probe_c64):
         """The probe propagated through free space to the entrance of every slice and to the detector, in float64 on the
         host (np_funcs.py:42-61 without an object) — the carrier field of bdof_set_probe_stack (include/bdof.h)."""
-        energy_ev, psize_cm, free_prop_cm, variant, pi = self._physics_args
-        voxel_nm = np.array([psize_cm] * 3) * 1.e7 if np.isscalar(psize_cm) else np.array(psize_cm) * 1.e7
-        lmbda_nm = 1240. / energy_ev
-        h = np.fft.ifftshift(util.get_kernel(voxel_nm[-1], lmbda_nm, voxel_nm, (self.ny, self.nx), pi=pi))
+        o = self.optics
+        h = o.table(o.delta_nm, tiled=False, fold=False, dtype=np.complex128)      # this cross-check: the (ny, nx) mesh's own get_kernel
         p = probe_c64.astype(np.complex128)
         stack = np.empty((self.n_slice, self.nx, self.ny), dtype=np.complex64)
         for z in range(self.n_slice):
@@ -121,37 +131,26 @@ class MultisliceEngine(object):
         if self.det_mode == _lib.DET_FAR:
             det = np.fft.fft2(p)                      # un-shifted, un-normalised; a tf_all step before it is applied on the host
         else:
-            if variant == 'tf_all':
+            if self.variant == 'tf_all':
                 p = np.fft.ifft2(np.fft.fft2(p) * h)
             if self.det_mode == _lib.DET_NEAR:
-                hd = np.fft.ifftshift(util.centred_kernel(free_prop_cm * 1e7, lmbda_nm, voxel_nm, self.ny, self.nx, pi=pi, kernel=self.det_kernel))
-                p = np.fft.ifft2(np.fft.fft2(p) * hd)
+                p = np.fft.ifft2(np.fft.fft2(p) * self._detector_table(np.complex128, fold=False))
             det = p
         return np.ascontiguousarray(stack), np.ascontiguousarray(det.T.astype(np.complex64))
 
     def _probe_field_device(self, probe_c64):
         """The same carrier field computed by the library on the device in float64 (bdof_set_probe_field): the host only forms
-        the two transfer functions (float64, transposed to [kx][ky])."""
-        energy_ev, psize_cm, free_prop_cm, variant, pi = self._physics_args
-        voxel_nm = np.array([psize_cm] * 3) * 1.e7 if np.isscalar(psize_cm) else np.array(psize_cm) * 1.e7
-        lmbda_nm = 1240. / energy_ev
-        fs = getattr(self, '_field_shape', None)
-        kern = (lambda d: util.get_kernel_tile(d, lmbda_nm, voxel_nm, (self.ny, self.nx), fs, pi=pi)) if fs is not None else \
-            (lambda d: util.get_kernel(d, lmbda_nm, voxel_nm, (self.ny, self.nx), pi=pi))
-        hT = np.ascontiguousarray(np.fft.ifftshift(kern(voxel_nm[-1])).T.astype(np.complex128))
-        hdT = None
-        if self.det_mode == _lib.DET_NEAR:
-            kd = kern(free_prop_cm * 1e7) if self.det_kernel == 'TF' else \
-                util.centred_kernel(free_prop_cm * 1e7, lmbda_nm, voxel_nm, self.ny, self.nx, pi=pi, kernel='IR')
-            hdT = np.ascontiguousarray(np.fft.ifftshift(kd).T.astype(np.complex128))
+        the two transfer functions (float64, transposed to [kx][ky]); both honour field_shape."""
+        o = self.optics
+        hT = o.table(o.delta_nm, tiled=True, fold=False, transpose=True, dtype=np.complex128)
+        hdT = self._detector_table(np.complex128, fold=False, transpose=True, tiled=True)
         p = np.ascontiguousarray(probe_c64.T.astype(np.complex128))
-        self.ctx.check(self.lib.bdof_set_probe_field(self.h, p.ctypes.data, hT.ctypes.data, hdT.ctypes.data if hdT is not None else None))
+        self.ctx.check(self.lib.bdof_set_probe_field(self.h, p.ctypes.data, hT.ctypes.data, _hp(hdT)))
 
     def set_probe(self, probe_real, probe_imag):
         self._probe_args = (np.array(probe_real, copy=True), np.array(probe_imag, copy=True))
         self.tf_f64 = self.conv_f64 = False     # the float64 twins (enable_tf_f64 / enable_conv_f64) hold the previous probe
-        probe = (np.asarray(probe_real) + 1j * np.asarray(probe_imag)) * np.ones((self.ny, self.nx))
-        probe = probe.astype(np.complex64)                         # the reference rounds to complex64 too (np_funcs.py:20)
+        probe = self._probe_field()
         # Carrier splitting: the wave is held as carrier + eps and only eps runs through the float32 transforms.
         #  - a (nearly) uniform probe rides on its mean a0, propagated exactly as a scalar inside the library;
         #  - a localised probe rides on its own free-space propagation, a carrier FIELD per slice, which the library computes
@@ -160,18 +159,17 @@ class MultisliceEngine(object):
         mean = complex(probe.astype(np.complex128).mean())
         a0 = mean if np.abs(probe - mean).max() <= 0.25 * abs(mean) else 0j
         self.probe_stack = False
-        if getattr(self, '_conv_set', False) and hasattr(self, '_physics_args'):
+        if self._conv_kernel is not None and self.optics is not None:
             if self._set_conv_probe_stack(probe, a0):
                 return
-        use_stack = (a0 == 0 and hasattr(self, '_physics_args') and not os.environ.get('BDOF_NO_PROBE_STACK')
-                     and not getattr(self, '_conv_set', False)              # the real-space propagator has its own carrier
+        use_stack = (a0 == 0 and self.optics is not None and not os.environ.get('BDOF_NO_PROBE_STACK')
+                     and self._conv_kernel is None                          # the real-space propagator has its own carrier
                      and self.n_slice * self.nx * self.ny <= (1 << 32)      # 32 GiB of stack at most
                      and self.lib.bdof_probe_stack_supported(self.h) == 1)
         if use_stack:
             if os.environ.get('BDOF_HOST_PROBE_STACK'):                     # cross-check: the float64 propagation on the host
                 stack, det = self._probe_stack(probe)
-                zero = np.zeros((self.nx, self.ny), dtype=np.complex64)
-                self.ctx.check(self.lib.bdof_set_probe(self.h, zero.ctypes.data, 0.0, 0.0))
+                self._set_zero_probe()
                 self.ctx.check(self.lib.bdof_set_probe_stack(self.h, stack.ctypes.data, det.ctypes.data))
             else:
                 self._probe_field_device(probe)
@@ -185,6 +183,11 @@ class MultisliceEngine(object):
         self.ctx.check(self.lib.bdof_set_probe(self.h, eps.ctypes.data, a0.real, a0.imag))
         self._set_meas_mode(a0)
 
+    def _set_zero_probe(self):
+        """bdof_set_probe with nothing in it: the wave is a carrier field's, or a caller's."""
+        zero = np.zeros((self.nx, self.ny), dtype=np.complex64)
+        self.ctx.check(self.lib.bdof_set_probe(self.h, zero.ctypes.data, 0.0, 0.0))
+
     def _set_conv_probe_stack(self, probe, a0):
         """Real-space propagator with a probe that has no dominant constant part (a0 == 0, e.g. a ptychography probe): the
         carrier FIELD of bdof_set_conv_probe_stack — the probe carried through empty space by the padded convolution itself,
@@ -195,24 +198,19 @@ class MultisliceEngine(object):
         if a0 != 0 or not small or os.environ.get('BDOF_NO_PROBE_STACK'):
             self.ctx.check(lib.bdof_set_conv_probe_stack(h, None, None, 0., 0., 0., 0.))
             return False
-        energy_ev, psize_cm, free_prop_cm, variant, pi = self._physics_args
-        ky, kx, e = self._conv_kernel
-        planes = util.conv_probe_stack(probe.astype(np.complex128), ky, kx, e, self.n_slice)          # (S + 1, Y, X)
+        planes = util.conv_probe_stack(probe.astype(np.complex128), *self._conv_kernel, self.n_slice)     # (S + 1, Y, X)
         p_end = planes[-1]
         if self.det_mode == _lib.DET_FAR:
             det = np.fft.fft2(p_end)                                                                   # [ky][kx], un-shifted
         elif self.det_mode == _lib.DET_NEAR:
-            voxel_nm = np.array([psize_cm] * 3) * 1.e7 if np.isscalar(psize_cm) else np.array(psize_cm) * 1.e7
-            hd = np.fft.ifftshift(util.centred_kernel(free_prop_cm * 1e7, 1240. / energy_ev, voxel_nm, self.ny, self.nx, pi=pi, kernel=self.det_kernel))
-            det = np.fft.ifft2(np.fft.fft2(p_end) * hd).T                                              # [x][y]
+            det = np.fft.ifft2(np.fft.fft2(p_end) * self._detector_table(np.complex128, fold=False)).T    # [x][y]
         else:
             det = p_end.T
         stack = np.ascontiguousarray(planes.transpose(0, 2, 1).astype(np.complex64))                   # [S + 1][x][y]
         det = np.ascontiguousarray(det.astype(np.complex128))
-        zero = np.zeros((self.nx, self.ny), dtype=np.complex64)
         if lib.bdof_probe_stack_supported(h) == 1:
             self.ctx.check(lib.bdof_set_probe_stack(h, None, None))
-        self.ctx.check(lib.bdof_set_probe(h, zero.ctypes.data, 0.0, 0.0))
+        self._set_zero_probe()
         p0, ps = complex(planes[0][0, 0]), complex(p_end[0, 0])
         self.ctx.check(lib.bdof_set_conv_probe_stack(h, stack.ctypes.data, det.ctypes.data, p0.real, p0.imag, ps.real, ps.imag))
         self.probe_stack, self.probe_gain = False, 1.0
@@ -225,7 +223,8 @@ class MultisliceEngine(object):
         self._gprobe = DeviceBuffer.zeros(self.ctx, (self.nx, self.ny), np.complex64) if on else None
 
     def probe_grad(self, accumulate=False, to_host=True):
-        """dL/d(probe_real) + i dL/d(probe_imag) of the last loss_grad, summed over its wavefields: (Y, X) complex."""
+        """dL/d(probe_real) + i dL/d(probe_imag) of the last loss_grad, summed over its wavefields: (Y, X) complex.
+        to_host=False: the device accumulator itself, [x][y]."""
         self.ctx.check(self.lib.bdof_probe_grad(self.h, self._gprobe.ptr, int(bool(accumulate))))
         if not to_host:
             return self._gprobe
@@ -235,13 +234,10 @@ class MultisliceEngine(object):
     def set_probe_none(self):
         """No probe of the ctx's own: every wavefield starts from a caller-supplied field (bdof_forward_range), no carrier."""
         self._probe_args = None
-        zero = np.zeros((self.nx, self.ny), dtype=np.complex64)
-        self.ctx.check(self.lib.bdof_set_probe(self.h, zero.ctypes.data, 0.0, 0.0))
+        self._set_zero_probe()
         self.ctx.check(self.lib.bdof_set_probe_stack(self.h, None, None))
         self.probe_stack, self.probe_gain = False, 1.0
         self._set_meas_mode(0j)
-
-    residual_split = True      # False: amplitudes go to the device as they are (a probe that changes between steps)
 
     def _set_meas_mode(self, a0):
         """Residual splitting at the detector (include/bdof.h, bdof_set_meas_mode): with a plane-wave carrier and a real-space
@@ -257,24 +253,18 @@ class MultisliceEngine(object):
     def set_conv(self, energy_ev, psize_cm, kernel_size=17):
         """Switch the slice-to-slice step to the truncated real-space kernel of multislice_propagate_cnn
         (cnn_propagator/propagation.py:18-44): k uses numpy's pi there (:25), the kernel the reference's PI literal."""
-        voxel_nm = np.array([psize_cm] * 3) * 1.e7 if np.isscalar(psize_cm) else np.array(psize_cm) * 1.e7
-        lmbda_nm = 1240. / energy_ev
-        delta_nm = voxel_nm[-1]
-        ky, kx, e = util.conv_kernel_separable(delta_nm, lmbda_nm, voxel_nm, (self.ny, self.nx), kernel_size)
+        o = util.Optics(energy_ev, psize_cm, None, np.pi, self.ny, self.nx)         # o.k: numpy's pi, unlike set_physics
+        ky, kx, e = util.conv_kernel_separable(o.delta_nm, o.lmbda_nm, o.voxel_nm, (self.ny, self.nx), kernel_size)   # pi=util.PI
         ksum = e * ky.sum() * kx.sum()
-        self._conv_set = True
         self._conv_kernel = (ky, kx, e)
-        k = 2. * np.pi * delta_nm / lmbda_nm
-        kyf = np.ascontiguousarray(ky.astype(np.complex64))
-        kxf = np.ascontiguousarray(kx.astype(np.complex64))
+        kyf, kxf = [np.ascontiguousarray(t.astype(np.complex64)) for t in (ky, kx)]
         self.ctx.check(self.lib.bdof_set_conv(self.h, kyf.ctypes.data, kxf.ctypes.data, int(kernel_size), e.real, e.imag,
-                                              ksum.real, ksum.imag, k))
+                                              ksum.real, ksum.imag, o.k))
         # the taps in float64 as well: dithered copies, one per slice (include/bdof.h)
-        ky64 = np.ascontiguousarray(ky.astype(np.complex128))
-        kx64 = np.ascontiguousarray(kx.astype(np.complex128))
+        ky64, kx64 = [np.ascontiguousarray(t.astype(np.complex128)) for t in (ky, kx)]
         self.ctx.check(self.lib.bdof_set_conv_taps_f64(self.h, ky64.ctypes.data, kx64.ctypes.data, float(e.real), float(e.imag)))
-        self._conv_k64 = k
-        if getattr(self, '_probe_args', None) is not None:
+        self._conv_k64 = o.k
+        if self._probe_args is not None:
             self.set_probe(*self._probe_args)      # the carrier (scalar or field) of the probe follows the propagator
 
     def enable_tf_f64(self):
@@ -283,20 +273,14 @@ class MultisliceEngine(object):
         accuracy path of the first minibatch of an epoch (adjoint_precision='first-step') — no second engine — and a float64 twin
         of the fused kernels for tests.  Hands the probe and the transfer function(s) over in float64; call again after
         set_physics / set_probe."""
-        if getattr(self, '_tf64_args', None) is None or getattr(self, '_probe_args', None) is None:
+        if self.optics is None or self._probe_args is None:
             raise RuntimeError('set_physics and set_probe first')
-        hs64, free_prop_cm, lmbda_nm, voxel_nm, pi, k = self._tf64_args
-        hd = None
-        if self.det_mode == _lib.DET_NEAR:
-            hd64 = util.device_transfer_function(free_prop_cm * 1e7, lmbda_nm, voxel_nm, self.ny, self.nx, pi=pi, dtype=np.complex128,
-                                                 kernel=self.det_kernel)
-            hd = np.ascontiguousarray(hd64.T)
-        ht = np.ascontiguousarray(hs64.T)                                       # [kx][ky]
-        pr, pi_ = self._probe_args
+        o = self.optics
+        ht = o.table(o.delta_nm, tiled=True, transpose=True, dtype=np.complex128)       # set_physics' float64 table as [kx][ky]
+        hd = self._detector_table(np.complex128, transpose=True)
         # the reference's wavefront starts as complex64 (np_funcs.py:20-21) and becomes complex128 at the first product
-        probe = np.ascontiguousarray(((np.asarray(pr) + 1j * np.asarray(pi_)) * np.ones((self.ny, self.nx))).T.astype(np.complex64)
-                                     .astype(np.complex128))
-        self.ctx.check(self.lib.bdof_set_tf_f64(self.h, probe.ctypes.data, ht.ctypes.data, hd.ctypes.data if hd is not None else None, k))
+        probe = np.ascontiguousarray(self._probe_field().T.astype(np.complex128))
+        self.ctx.check(self.lib.bdof_set_tf_f64(self.h, probe.ctypes.data, ht.ctypes.data, _hp(hd), float(o.k)))
         self.tf_f64 = True
 
     def enable_conv_f64(self):
@@ -304,7 +288,7 @@ class MultisliceEngine(object):
         f64=True)): the accuracy path for the first minibatch of an epoch (adjoint_precision='first-step' / 'float64' with
         propagator='conv').  Square fields.  Hands the probe and the transform of the zero-padded
         ks x ks kernel over in float64 (overlap-save on the padded (N + ks - 1)^2 grid)."""
-        if not getattr(self, '_conv_set', False) or getattr(self, '_probe_args', None) is None:
+        if self._conv_kernel is None or self._probe_args is None:
             raise RuntimeError('set_conv and set_probe first')
         if self.nx != self.ny:
             raise ValueError('the float64 real-space path takes square wavefields')
@@ -315,16 +299,11 @@ class MultisliceEngine(object):
         kpad[:ks, :ks] = e * np.outer(ky, kx)                                    # K[p][q] = e ky[p] kx[q]   (numpy (Y, X) order)
         khat = np.ascontiguousarray((np.fft.fft2(kpad) / float(m * m)).T)       # [kx][ky]
         ksum = e * ky.sum() * kx.sum()
-        pr, pi = self._probe_args
-        probe = np.ascontiguousarray(((np.asarray(pr) + 1j * np.asarray(pi)) * np.ones((self.ny, self.nx))).T.astype(np.complex128))
+        probe = np.ascontiguousarray(self._probe_field(round_c64=False).T.astype(np.complex128))
         self.ctx.check(self.lib.bdof_set_conv_f64(self.h, probe.ctypes.data, khat.ctypes.data, ks, float(ksum.real), float(ksum.imag),
                                                   float(self._conv_k64)))
-        hd = None
-        if self.det_mode == _lib.DET_NEAR:                                       # propagation.py:122-124: one transfer-function step
-            _, free_prop_cm, lmbda_nm, voxel_nm, pi64, _ = self._tf64_args
-            hd = np.ascontiguousarray(util.device_transfer_function(free_prop_cm * 1e7, lmbda_nm, voxel_nm, self.ny, self.nx, pi=pi64,
-                                                                    dtype=np.complex128, kernel=self.det_kernel).T)
-        self.ctx.check(self.lib.bdof_set_conv_f64_detector(self.h, hd.ctypes.data if hd is not None else None))
+        hd = self._detector_table(np.complex128, transpose=True)                 # propagation.py:122-124: one transfer-function step
+        self.ctx.check(self.lib.bdof_set_conv_f64_detector(self.h, _hp(hd)))
         self.conv_f64 = True
 
     # ---- object --------------------------------------------------------------------------------
@@ -359,9 +338,8 @@ class MultisliceEngine(object):
 
     def meas_layout(self, meas_abs):
         """|measured| (n, Y, X) in the index order libbdof's loss kernels read it."""
-        ref = getattr(self, 'meas_ref', 0.0)
-        if ref:
-            m = (np.asarray(meas_abs, dtype=np.float64) - ref).astype(np.float32)      # subtract in float64, round once
+        if self.meas_ref:
+            m = (np.asarray(meas_abs, dtype=np.float64) - self.meas_ref).astype(np.float32)      # subtract in float64, round once
         else:
             m = np.asarray(meas_abs, dtype=np.float32)
         if self.det_mode == _lib.DET_FAR:
@@ -371,11 +349,13 @@ class MultisliceEngine(object):
     def _meas_to_device(self, meas_abs):
         return DeviceBuffer.from_host(self.ctx, self.meas_layout(meas_abs))
 
+    def _idx_bufs(self, *lists):
+        """Per-wavefield index lists (angle, xoff, yoff) as int32 on the device (None stays None)."""
+        return [None if v is None else DeviceBuffer.from_host(self.ctx, np.asarray(v, dtype=np.int32)) for v in lists]
+
     def forward(self, B, angle_idx=None, xoff=None, yoff=None, keep_tape=False, to_host=True, conv=False):
         out = DeviceBuffer(self.ctx, B * self.nx * self.ny * 8, np.complex64, (B, self.nx, self.ny))
-        a = _idx_buf(self.ctx, angle_idx) if angle_idx is not None else None
-        xo = _idx_buf(self.ctx, xoff) if xoff is not None else None
-        yo = _idx_buf(self.ctx, yoff) if yoff is not None else None
+        a, xo, yo = self._idx_bufs(angle_idx, xoff, yoff)
         if conv:
             self.ctx.check(self.lib.bdof_forward_conv(self.h, B, _lib._ptr(a), _lib._ptr(xo), _lib._ptr(yo), out.ptr))
         else:
@@ -393,27 +373,35 @@ class MultisliceEngine(object):
         return res
 
     # ---- loss + gradient -----------------------------------------------------------------------
+    def loss_grad_device(self, B, angle, xoff, yoff, meas, conv=False, f64=False):
+        """Enqueue forward + loss + adjoint of B wavefields; every array argument is a device pointer (or None).  The one
+        place that picks among the four entry points: conv — the real-space propagator; f64 — the model's float64 path on
+        this context, which takes the residual-splitting reference as a number."""
+        if f64:
+            if conv and not self.conv_f64:
+                raise RuntimeError('the real-space propagator\'s float64 path: enable_conv_f64() first')
+            if not conv and not self.tf_f64:
+                raise RuntimeError('the transfer-function model\'s float64 path: enable_tf_f64() first')
+            fn, last = (self.lib.bdof_loss_grad_conv_f64 if conv else self.lib.bdof_loss_grad_tf_f64), float(self.meas_ref)
+        else:
+            fn, last = (self.lib.bdof_loss_grad_conv if conv else self.lib.bdof_loss_grad), None
+        self.ctx.check(fn(self.h, B, angle, xoff, yoff, meas, last))
+
+    def get_loss(self):
+        """The loss of the last loss_grad_device (waits for it)."""
+        loss = ctypes.c_double(0)
+        self.ctx.check(self.lib.bdof_get_loss(self.h, ctypes.byref(loss)))
+        return loss.value
+
     def loss_grad(self, B, meas_abs, angle_idx=None, xoff=None, yoff=None, meas_on_device=False, conv=False, f64=False):
         """Runs forward + loss + adjoint; returns the loss.  The gradient stays on the device.  f64: the float64 path of the
         model on the same context (enable_tf_f64 / with conv: enable_conv_f64)."""
         m = meas_abs if meas_on_device else self._meas_to_device(meas_abs)
-        a = _idx_buf(self.ctx, angle_idx) if angle_idx is not None else None
-        xo = _idx_buf(self.ctx, xoff) if xoff is not None else None
-        yo = _idx_buf(self.ctx, yoff) if yoff is not None else None
-        if f64:
-            if conv and not getattr(self, 'conv_f64', False):
-                raise RuntimeError('the real-space propagator\'s float64 path: enable_conv_f64() first')
-            if not conv and not getattr(self, 'tf_f64', False):
-                raise RuntimeError('the transfer-function model\'s float64 path: enable_tf_f64() first')
-            fn = self.lib.bdof_loss_grad_conv_f64 if conv else self.lib.bdof_loss_grad_tf_f64
-            self.ctx.check(fn(self.h, B, _lib._ptr(a), _lib._ptr(xo), _lib._ptr(yo), _lib._ptr(m), float(getattr(self, 'meas_ref', 0.0))))
-        else:
-            fn = self.lib.bdof_loss_grad_conv if conv else self.lib.bdof_loss_grad
-            self.ctx.check(fn(self.h, B, _lib._ptr(a), _lib._ptr(xo), _lib._ptr(yo), _lib._ptr(m), None))
-        loss = ctypes.c_double(0)
-        self.ctx.check(self.lib.bdof_get_loss(self.h, ctypes.byref(loss)))
+        a, xo, yo = self._idx_bufs(angle_idx, xoff, yoff)
+        self.loss_grad_device(B, _lib._ptr(a), _lib._ptr(xo), _lib._ptr(yo), _lib._ptr(m), conv=conv, f64=f64)
+        loss = self.get_loss()
         self._keep['last_idx'] = (a, xo, yo, m)
-        return loss.value
+        return loss
 
     def grad_batch_to_host(self, B):
         """Gradient w.r.t. the rotated object batch: (g_delta, g_beta), each (B, Y, X, S)."""
@@ -423,7 +411,7 @@ class MultisliceEngine(object):
         return util.rows_to_batch(out)
 
     def rotation_adjoint(self, B, angle_idx, gvol_buf, accumulate=False, scale=1.0):
-        a = _idx_buf(self.ctx, angle_idx)
+        a, = self._idx_bufs(angle_idx)
         self.ctx.check(self.lib.bdof_rotation_adjoint(self.h, B, a.ptr, _lib._ptr(gvol_buf), int(accumulate), float(scale)))
         self.ctx.sync()
 

@@ -45,7 +45,16 @@ class _VolumeSolver(object):
         self._epoch_plan = None    # shard layout of the Adam moments since the last reset_moments (None: none taken yet)
         self._g_shards = None      # slabs whose gradient is reduced on this rank's 1/size only (after a sharded step)
         self.probe = None          # enable_probe_optimization
+        self._pgrad = None         # the engine's device accumulator of the probe gradient (_probe_collect)
+        self.meas = None           # FullfieldSolver.set_measurements
+        self.meas_all = None       # PtychoSolver.set_measurements
         self.comm.attach(self.ctx)
+
+    def _upload_rotation_tables(self, coord_ls):
+        if coord_ls is None:
+            coord_ls = util.rotation_lookup([self.dim_y, self.dim_x, self.dim_z], self.n_theta)
+        tables = util.device_rotation_tables(coord_ls, self.dim_x, self.dim_z)
+        self.tab, self.off, self.order = [DeviceBuffer.from_host(self.ctx, t) for t in tables]
 
     def _bind_volume(self):
         self.eng.set_volume(self.x[self.cur], self.dim_x * self.dim_z, self.dim_y, self.tab, self.dim_x, self.n_theta)
@@ -78,9 +87,15 @@ class _VolumeSolver(object):
             self._bind_volume()
 
     def _get_loss(self):
-        loss = ctypes.c_double(0)
-        self.ctx.check(self.ctx.lib.bdof_get_loss(self.ctx.handle, ctypes.byref(loss)))
-        return loss.value
+        return self.eng.get_loss()
+
+    def _enable_f64(self):
+        """Bind the model's float64 twin in the constructor: it allocates the float64 wave + tape for the minibatch, so a run
+        fails here, not mid-way; a probe the float64 path does not take is the caller's to decide about (BdofError)."""
+        try:
+            (self.eng.enable_conv_f64 if self.conv else self.eng.enable_tf_f64)()
+        except ValueError as err:
+            raise _lib.BdofError(str(err))
 
     def _g_is_local(self):
         """self.g is about to be rewritten whole with this rank's own, unreduced gradient: the shard layout a sharded step
@@ -285,29 +300,29 @@ class _VolumeSolver(object):
         self._pacc = 0
         self.eng.enable_probe_grad(True)
         # The resident amplitudes were laid out as m - |a0| for the probe in force at set_measurements (residual splitting,
-        # engine._set_meas_mode).  A probe that moves every step would leave that reference behind — every residual biased by
+        # MultisliceEngine.meas_layout).  A probe that moves every step would leave that reference behind — every residual biased by
         # |a0_new| - |a0_old|, or by |a0| itself once the carrier changes kind — so the splitting is switched off here and
         # amplitudes that are already resident are put back to plain m.
-        old_ref = getattr(self.eng, 'meas_ref', 0.0)
+        old_ref = self.eng.meas_ref
         self.eng.residual_split = False
         self.eng.set_probe(self.probe.real, self.probe.imag)
-        if old_ref and getattr(self, 'meas', None) is not None:
+        if old_ref and self.meas is not None:
             self.ctx.sync()
             self.meas.upload((self.meas.download().astype(np.float64) + old_ref).astype(np.float32))
 
     def _probe_collect(self):
         """Add this minibatch's probe gradient to the device accumulator (call after every loss_grad)."""
-        if getattr(self, 'probe', None) is None:
+        if self.probe is None:
             return
-        self.eng.probe_grad(accumulate=self._pacc > 0, to_host=False)
+        self._pgrad = self.eng.probe_grad(accumulate=self._pacc > 0, to_host=False)
         self._pacc += 1
 
     def _probe_apply(self, b1=0.9, b2=0.999, eps=1e-8):
         """Adam on (probe_real, probe_imag) with the accumulated gradient (mean over accumulated minibatches and ranks)."""
-        if getattr(self, 'probe', None) is None or self._pacc == 0:
+        if self.probe is None or self._pacc == 0:
             return
         self.ctx.sync()
-        g = np.ascontiguousarray(self.eng._gprobe.download().T).astype(np.complex128) / self._pacc
+        g = np.ascontiguousarray(self._pgrad.download().T).astype(np.complex128) / self._pacc
         self._pacc = 0
         if self.comm.size > 1:
             g = self.comm.allreduce_sum_host(g) / self.comm.size
@@ -368,15 +383,8 @@ class FullfieldSolver(_VolumeSolver):
         if probe_real is None:
             probe_real, probe_imag = np.ones((dim_y, dim_x)), np.zeros((dim_y, dim_x))   # 'plane', fullfield.py:276-278
         self.eng.set_probe(probe_real, probe_imag)
-        if self.f64:                                 # allocates the float64 wave + tape for the minibatch: fails here, not mid-run
-            try:
-                if self.conv:
-                    self.eng.enable_conv_f64()
-                else:
-                    self.eng.enable_tf_f64()
-            except ValueError as err:
-                from ._lib import BdofError
-                raise BdofError(str(err))
+        if self.f64:
+            self._enable_f64()
         if self.bilinear:
             # per-angle projective transform of tf.contrib.image.rotate for images of height X and width Z, in float64
             th = np.asarray(theta, dtype=np.float64)
@@ -388,14 +396,8 @@ class FullfieldSolver(_VolumeSolver):
             self.tab = self.off = self.order = None
         else:
             # rotation lookup tables (cnn_propagator/util.py:294-347), uploaded once
-            if coord_ls is None:
-                coord_ls = util.rotation_lookup([dim_y, dim_x, dim_z], n_theta)
-            tab, off, order = util.device_rotation_tables(coord_ls, self.dim_x, self.dim_z)
-            self.tab = DeviceBuffer.from_host(self.ctx, tab)
-            self.off = DeviceBuffer.from_host(self.ctx, off)
-            self.order = DeviceBuffer.from_host(self.ctx, order)
+            self._upload_rotation_tables(coord_ls)
         self._init_volume()
-        self.meas = None
         self.meas_stage = DeviceBuffer(self.ctx, self.mb * self.dim_x * self.dim_y * 4, np.float32,
                                        (self.mb, self.dim_x, self.dim_y))
         self.angle_buf = DeviceBuffer(self.ctx, self.mb * 4, np.int32, (self.mb,))
@@ -404,9 +406,8 @@ class FullfieldSolver(_VolumeSolver):
             self.eng.set_rotation_adjoint(self.off, self.order, self.dim_x * self.dim_z)
 
     def _bind_volume(self):
-        if self.bilinear:
-            return                   # the engine's object is the minibatch's rotated copy, rebuilt at every step (_rotate_batch)
-        self.eng.set_volume(self.x[self.cur], self.dim_x * self.dim_z, self.dim_y, self.tab, self.dim_x, self.n_theta)
+        if not self.bilinear:        # (else the engine's object is the minibatch's rotated copy, rebuilt at every step: _rotate_batch)
+            _VolumeSolver._bind_volume(self)
 
     def _rotate_batch(self, idx, B):
         """Bilinear rotation of the current volume to the B angles idx, bound as a batch of rotated objects: one pass that
@@ -435,22 +436,18 @@ class FullfieldSolver(_VolumeSolver):
     def _rot_loss_grad(self, angle_idx, f64=False):
         """Forward + adjoint sweeps of this rank's angles: the gradient w.r.t. the rotated objects stays in the ctx.
         f64: through the transfer-function model's float64 path on the same context (bdof_loss_grad_tf_f64)."""
-        lib, h = self.ctx.lib, self.ctx.handle
         self._stage_batch(angle_idx)
         if f64:
             if self.bilinear:
                 raise ValueError("f64: the float64 paths run with the lookup-table rotation")
-            if self.conv and not getattr(self.eng, 'conv_f64', False):
+            if self.conv and not self.eng.conv_f64:      # (a probe or physics set since the last call unbound the twin)
                 self.eng.enable_conv_f64()
-            if not self.conv and not getattr(self.eng, 'tf_f64', False):
+            if not self.conv and not self.eng.tf_f64:
                 self.eng.enable_tf_f64()
-            fn = lib.bdof_loss_grad_conv_f64 if self.conv else lib.bdof_loss_grad_tf_f64
-            self.ctx.check(fn(h, self.mb, self.angle_buf.ptr, None, None, self.meas_stage.ptr, float(getattr(self.eng, 'meas_ref', 0.0))))
-            return
-        fn = lib.bdof_loss_grad_conv if self.conv else lib.bdof_loss_grad
-        if self.bilinear:
+        elif self.bilinear:
             self._rotate_batch(angle_idx, self.mb)
-        self.ctx.check(fn(h, self.mb, None if self.bilinear else self.angle_buf.ptr, None, None, self.meas_stage.ptr, None))
+        self.eng.loss_grad_device(self.mb, None if self.bilinear else self.angle_buf.ptr, None, None, self.meas_stage.ptr,
+                                  conv=self.conv, f64=f64)
 
     def _produce(self, accumulate=False):
         lib, h = self.ctx.lib, self.ctx.handle
@@ -493,7 +490,7 @@ class FullfieldSolver(_VolumeSolver):
         n_batch_per_update > 1 (tensorflow_recon/fullfield.py:413-425,512-530): the volume gradient of consecutive
         minibatches is accumulated and applied (averaged) every n-th minibatch or at the last one of the epoch; the Adam
         bias-correction exponent then counts updates, not minibatches."""
-        self._rot_loss_grad(angle_idx, f64=self.f64 is True or (self.f64 == 'first' and i_batch == 0 and getattr(self, 'probe', None) is None))
+        self._rot_loss_grad(angle_idx, f64=self.f64 is True or (self.f64 == 'first' and i_batch == 0 and self.probe is None))
         self._probe_collect()
         nb = max(1, int(n_batch_per_update))
         if nb > 1:
@@ -557,23 +554,11 @@ class PtychoSolver(_VolumeSolver):
         # whole step; every later step runs on the fast engine.  f64 = 'first' / True says when it runs.
         self.f64 = None
         if adjoint64 == 'first' or (self.conv and adjoint64 is True):
-            try:
-                if self.conv:
-                    self.eng.enable_conv_f64()
-                else:
-                    self.eng.enable_tf_f64()
-            except ValueError as err:                      # a probe the float64 path does not take: let the caller decide
-                from ._lib import BdofError
-                raise BdofError(str(err))
+            self._enable_f64()
             self.f64 = adjoint64
         elif adjoint64 not in (None, False, True):
             raise ValueError("adjoint64 must be None, False, True or 'first'")
-        if coord_ls is None:
-            coord_ls = util.rotation_lookup([self.dim_y, self.dim_x, self.dim_z], n_theta)
-        tab, off, order = util.device_rotation_tables(coord_ls, self.dim_x, self.dim_z)
-        self.tab = DeviceBuffer.from_host(self.ctx, tab)
-        self.off = DeviceBuffer.from_host(self.ctx, off)
-        self.order = DeviceBuffer.from_host(self.ctx, order)
+        self._upload_rotation_tables(coord_ls)
         self._init_volume()
         self.meas_stage = DeviceBuffer(self.ctx, self.mb * self.py * self.px * 4, np.float32, (self.mb, self.py, self.px))
         self.idx_buf = DeviceBuffer(self.ctx, 4 * self.mb * 4, np.int32, (4, self.mb))
@@ -598,7 +583,7 @@ class PtychoSolver(_VolumeSolver):
         idx[3] = 0
         p = self.idx_buf.ptr
         if prj_abs_batch is None:
-            if getattr(self, 'meas_all', None) is None:
+            if self.meas_all is None:
                 raise ValueError('no measurements: pass prj_abs_batch or call set_measurements first')
             idx[3] = int(i_theta) * self.n_pos_all + np.asarray(pos_idx)
             self.idx_buf.upload(idx)
@@ -611,24 +596,14 @@ class PtychoSolver(_VolumeSolver):
 
     def _win_loss_grad(self, i_theta, pos_idx, prj_abs_batch, use64=False):
         a, xo, yo = self._stage(i_theta, pos_idx, prj_abs_batch)
-        ctx = self.ctx
-        if self.f64 is True or (use64 and self.f64 == 'first'):
-            fn = ctx.lib.bdof_loss_grad_conv_f64 if self.conv else ctx.lib.bdof_loss_grad_tf_f64
-            ctx.check(fn(ctx.handle, self.mb, a, xo, yo, self.meas_stage.ptr, float(getattr(self.eng, 'meas_ref', 0.0))))
-        else:
-            fn = ctx.lib.bdof_loss_grad_conv if self.conv else ctx.lib.bdof_loss_grad
-            ctx.check(fn(ctx.handle, self.mb, a, xo, yo, self.meas_stage.ptr, None))
+        f64 = self.f64 is True or (use64 and self.f64 == 'first')
+        self.eng.loss_grad_device(self.mb, a, xo, yo, self.meas_stage.ptr, conv=self.conv, f64=f64)
         self._last = (int(i_theta), xo, yo)
 
     def _produce_all(self):
         i_theta, xo, yo = self._last
         self._g_is_local()
         self.ctx.check(self.ctx.lib.bdof_window_rotation_adjoint(self.ctx.handle, self.mb, i_theta, xo, yo, self.g.ptr, 0, 1.0))
-
-    def _get_loss(self):
-        loss = ctypes.c_double(0)
-        self.ctx.check(self.ctx.lib.bdof_get_loss(self.ctx.handle, ctypes.byref(loss)))
-        return loss.value
 
     def loss_and_grad(self, i_theta, pos_idx, prj_abs_batch=None, want_loss=True, f64=False):
         """prj_abs_batch: |this_prj_batch| (mb, py, px) for probe positions pos_idx at angle i_theta (None: from the resident

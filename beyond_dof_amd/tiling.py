@@ -65,6 +65,10 @@ class TiledPropagator(object):
         transform pair per slice and tile: cheap for a padded field, 4 x the sweep's time for a field full of object)."""
         self.fy, self.fx = int(field_shape[0]), int(field_shape[1])
         self.n_slice, self.tile = int(n_slice), int(tile)
+        # the tiles' optics (they apply the field's propagator) and the whole field's own
+        self._optics = o = util.Optics(energy_ev, psize_cm, None, pi, self.tile, self.tile, (self.fy, self.fx))
+        self._field_optics = util.Optics(energy_ev, psize_cm, None, pi, self.fy, self.fx)
+        self.spread_px, self.winding = self._reach(o)
         if isinstance(halo, str):
             if halo != 'auto':
                 raise ValueError("halo: a number of pixels or 'auto'")
@@ -76,9 +80,6 @@ class TiledPropagator(object):
         self.core = self.tile - 2 * self.halo
         self.taper = self.halo // 2 if taper is None else int(taper)
         self.variant = variant
-        voxel_nm = np.array([psize_cm] * 3) * 1.e7 if np.isscalar(psize_cm) else np.array(psize_cm) * 1.e7
-        lmbda_nm = 1240. / energy_ev
-        self.spread_px = lmbda_nm * voxel_nm[2] / (2. * voxel_nm[0] ** 2)      # lateral reach of the band-edge ray per slice
         geometric = max(1, int(safety * (self.halo - self.taper) / self.spread_px)) if self.halo > 0 else self.n_slice
         self.with_grad = bool(with_grad)
         if long_range == 'auto':
@@ -96,8 +97,6 @@ class TiledPropagator(object):
         if precision == 'float64' and (self.with_grad or (comm is not None and comm.size > 1)):
             raise ValueError("precision='float64' is implemented for the forward model on one rank")
         self.precision = precision
-        # slices in which the band edge's phase pi lambda dz / (2 dx)^2 winds by pi: beyond it the first-order correction degrades
-        self.winding = max(1, int(4. * voxel_nm[0] ** 2 / (lmbda_nm * voxel_nm[2])))
         if slices_per_exchange is None:
             slices_per_exchange = min(geometric, self.winding) if self.long_range else geometric
         self.seg = max(1, int(slices_per_exchange))
@@ -127,6 +126,8 @@ class TiledPropagator(object):
         self._carrier_arg = carrier
         self._active = None               # per stitch range: indices of the tiles whose window holds any object (set_object*)
         self._active_bufs = {}
+        self._ends = self._grot = self._gvol = None      # the gradient's per-range buffers (_range_buffers)
+        self._obj_shape = None            # row layout of the object the engine holds (set_object*)
         n = self.n_tiles * self.tile * self.tile
         self.dbl = precision == 'float64'
         ctype = np.complex128 if self.dbl else np.complex64
@@ -134,8 +135,7 @@ class TiledPropagator(object):
         self.tiles_in = DeviceBuffer(self.ctx, n * cb, ctype, (self.n_tiles, self.tile, self.tile))
         self.tiles_out = None if self.dbl else DeviceBuffer(self.ctx, n * 8, np.complex64, (self.n_tiles, self.tile, self.tile))
         self.field = DeviceBuffer(self.ctx, self.fx * self.fy * cb, ctype, (self.fx, self.fy))
-        self._phys = (voxel_nm[2], lmbda_nm, voxel_nm, pi)
-        self.k64 = 2. * pi * voxel_nm[2] / lmbda_nm
+        self.k64 = o.k
         self.h64 = DeviceBuffer.from_host(self.ctx, self._free_table(1, (self.tile, self.tile), np.complex128)) if self.dbl else None
         self._pow_tables = {}
         if self.long_range:
@@ -159,14 +159,8 @@ class TiledPropagator(object):
         """The `power`-th power of one slice step's transfer function on a (ny, nx) grid of this field, un-shifted, 1 / (NX NY)
         folded in, formed in float64 (H is exp(i phase): the power is taken on the phase, i.e. on the distance).
         [kx][ky] for bdof_fields_free_step / bdof_forward_range_f64; fused_layout: [ky][kx], the row kernels' order."""
-        dist_nm, lmbda_nm, voxel_nm, pi = self._phys
-        ny, nx = shape
-        if tuple(shape) == (self.fy, self.fx):
-            h = util.get_kernel(dist_nm * power, lmbda_nm, voxel_nm, (ny, nx), pi=pi)
-        else:
-            h = util.get_kernel_tile(dist_nm * power, lmbda_nm, voxel_nm, (ny, nx), (self.fy, self.fx), pi=pi)
-        h = np.fft.ifftshift(h) / float(nx * ny)
-        return np.ascontiguousarray((h if fused_layout else h.T).astype(ctype))
+        o = self._field_optics if tuple(shape) == (self.fy, self.fx) else self._optics      # (get_kernel / get_kernel_tile)
+        return o.table(o.delta_nm * power, tiled=True, transpose=not fused_layout, dtype=ctype)
 
     def _tables(self, power):
         """(tile table, field table) of `power` consecutive free-space steps, on the device; built once per distinct power.
@@ -185,7 +179,8 @@ class TiledPropagator(object):
         vol = DeviceBuffer.from_host(self.ctx, rows)
         tab = np.ascontiguousarray(np.tile(np.arange(self.fx, dtype=np.int32), (1, self.n_slice, 1)))             # [1][S][x] -> row x
         self.eng.set_volume(vol, self.fx, self.fy, DeviceBuffer.from_host(self.ctx, tab), self.fx, 1)
-        if getattr(self, 'skip_vacuum', False):             # (WholeFieldPropagator borrows this method: it has no tiles)
+        self._obj_shape = rows.shape
+        if self.skip_vacuum:                                # (WholeFieldPropagator borrows this method: it has no tiles)
             act = self._tiles_with_object((np.asarray(delta2d) != 0) | (np.asarray(beta2d) != 0))
             self._active = [act] * len(self.segments())
 
@@ -208,7 +203,8 @@ class TiledPropagator(object):
         z = np.arange(self.n_slice, dtype=np.int32)
         tab = np.ascontiguousarray((x[None, :] * self.n_slice + z[:, None])[None].astype(np.int32))               # [1][S][X]
         self.eng.set_volume(vol, self.fx * self.n_slice, self.fy, DeviceBuffer.from_host(self.ctx, tab), self.fx, 1)
-        if getattr(self, 'skip_vacuum', False):
+        self._obj_shape = rows.shape
+        if self.skip_vacuum:
             d, b = np.asarray(delta), np.asarray(beta)
             self._active = [self._tiles_with_object(np.any(d[:, :, z0:z0 + nz] != 0, axis=2) | np.any(b[:, :, z0:z0 + nz] != 0, axis=2))
                             for z0, nz in self.segments()]
@@ -260,10 +256,14 @@ class TiledPropagator(object):
         return (n, ib.ptr, ib.ptr + 4 * n, ib.ptr + 8 * n, vb.ptr, vb.ptr + 4 * n, vb.ptr + 8 * n)
 
     # ---- forward -------------------------------------------------------------------------------
+    @staticmethod
+    def _reach(o):
+        """(spread_px, winding) of the optics o: the lateral reach of the band-edge ray per slice in pixels, and the slices in
+        which the band edge's phase pi lambda dz / (2 dx)^2 winds by pi (beyond it the first-order correction degrades)."""
+        return o.lmbda_nm * o.delta_nm / (2. * o.voxel_nm[0] ** 2), max(1, int(4. * o.voxel_nm[0] ** 2 / (o.lmbda_nm * o.delta_nm)))
+
     def _auto_halo(self, energy_ev, psize_cm, safety, slices_per_exchange, long_range, comm, carriers=False):
-        voxel_nm = np.array([psize_cm] * 3) * 1.e7 if np.isscalar(psize_cm) else np.array(psize_cm) * 1.e7
-        lmbda_nm = 1240. / energy_ev
-        spread = lmbda_nm * voxel_nm[2] / (2. * voxel_nm[0] ** 2)
+        spread, winding = self._reach(util.Optics(energy_ev, psize_cm, None, util.PI, self.tile, self.tile))
         plain = min(64, self.tile // 4)
         geometric = max(1, int(safety * (plain - plain // 2) / spread))
         if long_range == 'auto':
@@ -271,7 +271,6 @@ class TiledPropagator(object):
                 (slices_per_exchange is None or slices_per_exchange < self.n_slice)
         if not long_range:
             return plain
-        winding = max(1, int(4. * voxel_nm[0] ** 2 / (lmbda_nm * voxel_nm[2])))
         seg = winding if slices_per_exchange is None else int(slices_per_exchange)
         # without per-tile carriers the float32 round-off of the sweeps (6e-6 at cfg4's depth) hides what a wider ramp would buy;
         # with them the tiling error is what is left, and 40 pixels of ramp and margin bring it under 1e-6
@@ -401,15 +400,11 @@ class TiledPropagator(object):
             raise RuntimeError('TiledPropagator(with_grad=True) needed')
         if self.long_range:
             return self._loss_and_grad_long_range(meas_dev)
-        import ctypes
         lib, h, p = self.lib, self.h, self.idx.ptr
         a, xo, yo = p, p + 4 * self.n_tiles, p + 8 * self.n_tiles
         T, B = self.tile, self.n_tiles
         segs = self.segments()
-        if getattr(self, '_ends', None) is None or len(self._ends) != len(segs):
-            self._ends = [DeviceBuffer(self.ctx, B * T * T * 8, np.complex64, (B, T, T)) for _ in segs]
-            self._grot = DeviceBuffer(self.ctx, B * max(nz for _, nz in segs) * T * T * 8, np.float32)
-            self._gvol = DeviceBuffer.zeros(self.ctx, self.eng._keep['obj'].shape, np.float32)
+        self._range_buffers(segs)
         for (z0, nz), end in zip(segs, self._ends):
             self.ctx.check(lib.bdof_tiles_gather(h, self.field.ptr, self.fx, self.fy, self.tiles_in.ptr, B, T, T, xo, yo, self.taper))
             self.ctx.check(lib.bdof_forward_range(h, B, a, xo, yo, z0, nz, self.tiles_in.ptr, end.ptr, 1))
@@ -424,9 +419,15 @@ class TiledPropagator(object):
             self.ctx.check(lib.bdof_tiles_gather_adjoint(h, self.tiles_out.ptr, self.field.ptr, self.fx, self.fy, B, T, T, xo, yo, self.taper))
             self._sum_over_ranks(self.field)
         self._sum_over_ranks(gvol)
-        loss = ctypes.c_double(0)
-        self.ctx.check(lib.bdof_get_loss(h, ctypes.byref(loss)))
-        return loss.value, gvol
+        return self.eng.get_loss(), gvol
+
+    def _range_buffers(self, segs):
+        """The gradient sweeps' buffers: every range's end state, one range's gradient rows, the volume gradient."""
+        B, T = self.n_tiles, self.tile
+        if self._ends is None or len(self._ends) != len(segs):
+            self._ends = [DeviceBuffer(self.ctx, B * T * T * 8, np.complex64, (B, T, T)) for _ in segs]
+            self._grot = DeviceBuffer(self.ctx, B * max(nz for _, nz in segs) * T * T * 8, np.float32)
+            self._gvol = DeviceBuffer.zeros(self.ctx, self._obj_shape, np.float32)
 
     def _conj_table(self, power):
         """conj(H^power) for the tiles, in the fused kernels' layout: the adjoint of their free-space step over a range."""
@@ -442,17 +443,13 @@ class TiledPropagator(object):
             G_in = W^H G_out + Cut^H ( T^H - F^H ) Stitch^H G_out ,
         T^H by bdof_adjoint_range (which also leaves the object-gradient rows), F^H the fused free-space step with conj(H^n),
         W^H bdof_fields_free_step(conj_h = 1); the field-level adjoint stays in complex128 like the field."""
-        import ctypes
         lib, h, p = self.lib, self.h, self.idx.ptr
         a, xo, yo = p, p + 4 * self.n_tiles, p + 8 * self.n_tiles
         v = self.vac.ptr
         va, vx, vy = v, v + 4 * self.n_tiles, v + 8 * self.n_tiles
         T, B, npx = self.tile, self.n_tiles, self.fx * self.fy
         segs = self.segments()
-        if getattr(self, '_ends', None) is None or len(self._ends) != len(segs):
-            self._ends = [DeviceBuffer(self.ctx, B * T * T * 8, np.complex64, (B, T, T)) for _ in segs]
-            self._grot = DeviceBuffer(self.ctx, B * max(nz for _, nz in segs) * T * T * 8, np.float32)
-            self._gvol = DeviceBuffer.zeros(self.ctx, self.eng._keep['obj'].shape, np.float32)
+        self._range_buffers(segs)
         f, w = self.field64, self.whole64
         self.ctx.check(lib.bdof_c_convert(h, f.ptr, self.field.ptr, npx, 1))
         for (z0, nz), end in zip(segs, self._ends):
@@ -484,9 +481,7 @@ class TiledPropagator(object):
             self.ctx.check(lib.bdof_tiles_gather_adjoint_diff64(h, self.tiles_out.ptr, self.tiles_free.ptr, g.ptr, self.fx, self.fy, B, T, T, xo, yo,
                                                                 self.taper, 1))
         self.ctx.check(lib.bdof_c_convert(h, self.field.ptr, g.ptr, npx, 0))            # G(probe), as the plain path leaves it
-        loss = ctypes.c_double(0)
-        self.ctx.check(lib.bdof_get_loss(h, ctypes.byref(loss)))
-        return loss.value, gvol
+        return self.eng.get_loss(), gvol
 
     def loss_and_grad(self, probe_real, probe_imag, meas_abs):
         """loss = mean((|exit wave| - meas_abs)^2) over the field (fullfield.py:106, no detector step) and its gradient w.r.t.
@@ -515,13 +510,12 @@ class WholeFieldPropagator(object):
 
     def __init__(self, field_shape, n_slice, energy_ev, psize_cm, variant='numpy_skip_last', device=0, pi=util.PI):
         self.fy, self.fx, self.n_slice, self.variant = int(field_shape[0]), int(field_shape[1]), int(n_slice), variant
-        voxel_nm = np.array([psize_cm] * 3) * 1.e7 if np.isscalar(psize_cm) else np.array(psize_cm) * 1.e7
-        lmbda_nm = 1240. / energy_ev
+        o = util.Optics(energy_ev, psize_cm, None, pi, self.fy, self.fx)
         self.eng = MultisliceEngine(self.fy, self.fx, self.n_slice, 1, with_grad=False, device=device, engine='generic')
         self.ctx, self.lib, self.h = self.eng.ctx, self.eng.lib, self.eng.h
-        self.k64 = 2. * pi * voxel_nm[2] / lmbda_nm
-        hk = np.fft.ifftshift(util.get_kernel(voxel_nm[2], lmbda_nm, voxel_nm, (self.fy, self.fx), pi=pi)) / float(self.fx * self.fy)
-        self.h64 = DeviceBuffer.from_host(self.ctx, np.ascontiguousarray(hk.T.astype(np.complex128)))      # [kx][ky]
+        self.k64 = o.k
+        self.h64 = DeviceBuffer.from_host(self.ctx, o.table(o.delta_nm, transpose=True, dtype=np.complex128))      # [kx][ky]
+        self.skip_vacuum, self._obj_shape = False, None      # (set_object* are TiledPropagator's: no tiles here to leave out)
         self.field = DeviceBuffer(self.ctx, self.fx * self.fy * 16, np.complex128, (self.fx, self.fy))
         self.idx = DeviceBuffer.from_host(self.ctx, np.zeros(3, dtype=np.int32))
 

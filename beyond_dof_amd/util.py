@@ -112,6 +112,48 @@ def transfer_function_dc(dist_nm, lmbda_nm, voxel_nm, ny, nx, pi=PI, field_shape
     return v.real, v.imag
 
 
+class Optics(object):
+    """Units and propagation multipliers of one (ny, nx) wavefield geometry: what the engine and the tiled propagator take
+    every wavelength, voxel size, k and transfer-function table from.  free_prop_cm: None (no detector step), a distance in cm
+    or 'inf' (far field); field_shape: the wavefield is a tile of a (FY, FX) field (get_kernel_tile)."""
+
+    def __init__(self, energy_ev, psize_cm, free_prop_cm, pi, ny, nx, field_shape=None):
+        if isinstance(free_prop_cm, str) and free_prop_cm != 'inf':
+            raise ValueError("free_prop_cm must be None, a distance in cm or 'inf'")
+        self.voxel_nm = np.array([psize_cm] * 3) * 1.e7 if np.isscalar(psize_cm) else np.array(psize_cm) * 1.e7
+        self.lmbda_nm = 1240. / energy_ev
+        self.delta_nm = self.voxel_nm[-1]                      # slice thickness
+        self.pi = pi                                           # enters k and H: the reference's literal, or numpy's (set_conv)
+        self.k = 2. * pi * self.delta_nm / self.lmbda_nm
+        self.det_nm = None if free_prop_cm is None or isinstance(free_prop_cm, str) else free_prop_cm * 1e7
+        self.ny, self.nx, self.field_shape = int(ny), int(nx), field_shape
+
+    def _args(self, tiled, kernel='TF'):
+        return self.lmbda_nm, self.voxel_nm, self.ny, self.nx, self.pi, self.field_shape if tiled else None, kernel
+
+    def slice_kernel(self, tiled):
+        """Centred multiplier of one slice step.  tiled=False: the (ny, nx) mesh's own even for a tile of a larger field."""
+        return centred_kernel(self.delta_nm, *self._args(tiled))
+
+    def detector_kernel(self, kind, tiled=False):
+        """Centred multiplier of the step to the detector, kind 'TF' or 'IR' (whole fields only)."""
+        return centred_kernel(self.det_nm, *self._args(tiled, kind))
+
+    def table(self, dist_nm, kernel='TF', tiled=False, fold=True, transpose=False, dtype=np.complex64):
+        """The multiplier of a step over dist_nm in device layout: un-shifted, [ky][kx] or, if transpose, [kx][ky].  fold: 1/(nx*ny)
+        folded in (device_transfer_function: the sweeps' tables) or not (the carrier fields' and the host's)."""
+        lmbda_nm, voxel_nm, ny, nx, pi, fs, kernel = self._args(tiled, kernel)
+        if fold:
+            h = device_transfer_function(dist_nm, lmbda_nm, voxel_nm, ny, nx, pi, fs, dtype, kernel)
+        else:
+            h = np.fft.ifftshift(centred_kernel(dist_nm, lmbda_nm, voxel_nm, ny, nx, pi, fs, kernel)).astype(dtype)
+        return np.ascontiguousarray(h.T) if transpose else h
+
+    def dc(self, dist_nm, kernel='TF', tiled=False):
+        """(re, im) array of the factor a constant wave picks up over dist_nm (transfer_function_dc)."""
+        return np.array(transfer_function_dc(dist_nm, *self._args(tiled, kernel)))
+
+
 def conv_kernel_separable(delta_nm, lmbda_nm, voxel_nm, grid_shape, kernel_size, pi=PI):
     """The truncated real-space Fresnel kernel of cnn_propagator/propagation.py:35-44 in separable form:
     K[p][q] = e * ky[p] * kx[q].  H on the (Y-1, X-1) mesh is e * outer(fv, fu), so its inverse FFT, fftshift and centre

@@ -44,9 +44,7 @@ def reconfigure(eng, ny, nx, s, bmax, flags):
     eng.ctx.check(eng.lib.bdof_configure(eng.h, ny, nx, s, bmax, flags))
     eng.ny, eng.nx, eng.n_slice, eng.batch_max = ny, nx, s, bmax
     eng.adjoint64, eng.recompute = bool(flags & A64), bool(flags & RECOMP)
-    for a in ('_probe_args', '_physics_args', '_tf64_args', '_conv_set', '_conv_kernel', '_field_shape'):
-        eng.__dict__.pop(a, None)
-    eng._keep = {}
+    eng._reset_host_state()
 
 
 def inputs(ny, nx, s, seed):

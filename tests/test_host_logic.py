@@ -239,3 +239,93 @@ def test_summary_columns_and_build_id(tmp_path):
     assert open(str(tmp_path / 'summary.txt')).read().splitlines()[0] == '{:<20}{}'.format('obj_size', '(8, 8, 8)')
     b = _lib.build_id()
     assert set(b) == {'source_sha256', 'flags', 'lib_sha256'} and len(b['source_sha256']) == 16
+
+
+def test_optics_record_hands_out_the_parent_expressions_bit_for_bit():
+    """util.Optics against the expressions the engine and the tiled propagator spelled out before it existed, written here from
+    get_kernel / get_kernel_tile / get_kernel_ir and ifftshift with dtype and transposition: np.array_equal, no tolerance.
+    Both forms of psize_cm, with and without field_shape, 'TF' and 'IR', free_prop_cm None / a distance / 'inf'."""
+    import itertools
+    import pytest
+    ifs, c64, c128 = np.fft.ifftshift, np.complex64, np.complex128
+    energy_ev, ny, nx = 5000., 12, 16
+    for psize_cm, fs, free_prop_cm, pi in itertools.product((1e-7, (1.5e-7, 2.5e-7, 2e-7)), (None, (40, 48)), (None, 1e-4, 'inf'),
+                                                            (util.PI, np.pi)):
+        o = util.Optics(energy_ev, psize_cm, free_prop_cm, pi, ny, nx, fs)
+        voxel_nm = np.array([psize_cm] * 3) * 1.e7 if np.isscalar(psize_cm) else np.array(psize_cm) * 1.e7
+        lmbda_nm = 1240. / energy_ev
+        delta_nm = voxel_nm[-1]
+        assert np.array_equal(o.voxel_nm, voxel_nm) and o.lmbda_nm == lmbda_nm and o.delta_nm == delta_nm == voxel_nm[2]
+        assert o.k == 2. * pi * delta_nm / lmbda_nm and o.pi == pi and o.field_shape == fs and (o.ny, o.nx) == (ny, nx)
+
+        def whole(d):
+            return util.get_kernel(d, lmbda_nm, voxel_nm, (ny, nx), pi=pi)
+
+        def tile(d):            # what a tile of the field applies; the field's own mesh without field_shape
+            return util.get_kernel_tile(d, lmbda_nm, voxel_nm, (ny, nx), fs, pi=pi) if fs is not None else whole(d)
+
+        # the slice step
+        assert np.array_equal(o.slice_kernel(tiled=True), tile(delta_nm))
+        assert np.array_equal(o.slice_kernel(tiled=False), whole(delta_nm))
+        hs64 = o.table(delta_nm, tiled=True, dtype=c128)                           # set_physics: bdof_set_transfer_f64
+        assert hs64.dtype == c128 and hs64.flags.c_contiguous
+        assert np.array_equal(hs64, np.ascontiguousarray((ifs(tile(delta_nm)) / float(nx * ny)).astype(c128)))
+        assert np.array_equal(hs64.astype(c64), np.ascontiguousarray((ifs(tile(delta_nm)) / float(nx * ny)).astype(c128)).astype(c64))
+        t = o.table(delta_nm, tiled=True)                                          # complex64 is the default
+        assert t.dtype == c64 and np.array_equal(t, (ifs(tile(delta_nm)) / float(nx * ny)).astype(c64))
+        t = o.table(delta_nm, tiled=True, transpose=True, dtype=c128)              # enable_tf_f64; the tiled propagator's [kx][ky]
+        assert t.flags.c_contiguous and np.array_equal(t, np.ascontiguousarray(hs64.T))
+        assert np.array_equal(t, np.ascontiguousarray((ifs(tile(delta_nm)) / float(nx * ny)).T.astype(c128)))
+        t = o.table(delta_nm * 7, tiled=True, dtype=c64)                           # tiling: 7 steps, the fused kernels' layout
+        assert np.array_equal(t, np.ascontiguousarray((ifs(tile(delta_nm * 7)) / float(nx * ny)).astype(c64)))
+        t = o.table(delta_nm, tiled=False, fold=False, dtype=c128)                 # the host's carrier stack
+        assert np.array_equal(t, ifs(whole(delta_nm)))
+        t = o.table(delta_nm, tiled=True, fold=False, transpose=True, dtype=c128)  # bdof_set_probe_field
+        assert t.flags.c_contiguous and np.array_equal(t, np.ascontiguousarray(ifs(tile(delta_nm)).T.astype(c128)))
+        dc = o.dc(delta_nm, tiled=True)
+        assert dc.shape == (2,) and complex(*dc) == complex(ifs(tile(delta_nm))[0, 0])
+        assert np.array_equal(dc, np.array(util.transfer_function_dc(delta_nm, lmbda_nm, voxel_nm, ny, nx, pi=pi, field_shape=fs)))
+
+        # the step to the detector
+        if free_prop_cm is None or free_prop_cm == 'inf':
+            assert o.det_nm is None
+            continue
+        dist = free_prop_cm * 1e7
+        assert o.det_nm == dist
+        ir = util.get_kernel_ir(dist, lmbda_nm, voxel_nm, (ny, nx), pi=pi)
+        assert np.array_equal(o.detector_kernel('TF'), whole(dist)) and np.array_equal(o.detector_kernel('TF', tiled=True), tile(dist))
+        assert np.array_equal(o.detector_kernel('IR'), ir)
+        for kind, centred in (('TF', whole(dist)), ('IR', ir)):
+            for dtype in (c64, c128):                                              # set_physics / its adjoint64 table
+                t = o.table(dist, kind, dtype=dtype)
+                assert t.dtype == dtype and np.array_equal(t, np.ascontiguousarray((ifs(centred) / float(nx * ny)).astype(dtype)))
+            t = o.table(dist, kind, transpose=True, dtype=c128)                    # enable_tf_f64 / enable_conv_f64
+            assert t.flags.c_contiguous
+            assert np.array_equal(t, np.ascontiguousarray(np.ascontiguousarray((ifs(centred) / float(nx * ny)).astype(c128)).T))
+            assert np.array_equal(o.table(dist, kind, fold=False, dtype=c128), ifs(centred))       # the carrier stacks on the host
+            t = o.table(dist, kind, fold=False, transpose=True, dtype=c128)
+            assert np.array_equal(t, np.ascontiguousarray(ifs(centred).T.astype(c128)))
+            assert complex(*o.dc(dist, kind)) == complex(ifs(centred)[0, 0])
+        t = o.table(dist, 'TF', tiled=True, fold=False, transpose=True, dtype=c128)                # bdof_set_probe_field, 'TF'
+        assert np.array_equal(t, np.ascontiguousarray(ifs(tile(dist)).T.astype(c128)))
+        if fs is not None:
+            with pytest.raises(ValueError):
+                o.detector_kernel('IR', tiled=True)                                # the impulse response is a whole field's
+    with pytest.raises(ValueError, match='free_prop_cm'):
+        util.Optics(energy_ev, 1e-7, 'far', util.PI, ny, nx)
+
+
+def test_engine_host_state_is_declared_and_the_loss_call_is_single():
+    """The static conditions of the host clean-up: the scalar-or-triple pixel size is converted in one place, the engine and the
+    solvers no longer ask their own objects what they hold, and each bdof_loss_grad* entry point is called from one place."""
+    import re
+    pkg = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'beyond_dof_amd')
+    src = {f: open(os.path.join(pkg, f)).read() for f in sorted(os.listdir(pkg)) if f.endswith('.py')}
+    assert sum(s.count('np.isscalar(psize_cm)') for s in src.values()) == 1 and 'np.isscalar(psize_cm)' in src['util.py']
+    assert 'getattr(self, ' not in src['engine.py'] and 'hasattr(self, ' not in src['engine.py']
+    assert 'getattr(self.eng, ' not in src['solver.py']
+    assert not any('_physics_args' in s or '_tf64_args' in s for s in src.values())
+    calls = [m for f, s in src.items() if f != '_lib.py' for m in re.findall(r'lib\.(bdof_loss_grad\w*)', s)]
+    assert sorted(calls) == ['bdof_loss_grad', 'bdof_loss_grad_conv', 'bdof_loss_grad_conv_f64', 'bdof_loss_grad_tf_f64']
+    from beyond_dof_amd.engine import MultisliceEngine
+    assert callable(MultisliceEngine._reset_host_state) and callable(MultisliceEngine.loss_grad_device)
