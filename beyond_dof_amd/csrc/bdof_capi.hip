@@ -164,6 +164,8 @@ struct bdof_ctx : Workspace {
     std::complex<double> c_p0{0.0, 0.0}, c_pS{0.0, 0.0};   // bdof_set_conv_probe_stack
     bool res_dirty = true, res_always = false;
     int meas_dev = 0;                           // bdof_set_meas_mode
+    int loss_kind = BDOF_LOSS_LSQ;              // bdof_set_loss: the data term of bdof_loss_grad / bdof_loss_grad_tf_f64 ...
+    double loss_mu = 0.0;                       // ... and, for BDOF_LOSS_POISSON, its photons per unit intensity
     bool generic = false;                       // generic-size engine (rocFFT)
     bool adj64 = false;                         // float64 adjoint sweep (BDOF_CFG_ADJOINT64; generic engine)
     int det_mode = BDOF_DET_NONE, variant = BDOF_VARIANT_NUMPY_SKIP_LAST;
@@ -221,6 +223,11 @@ static int check_batch(bdof_ctx* c, int B) {
 static int check_range(bdof_ctx* c, int z0, int nz) {
     return z0 < 0 || nz < 1 || z0 + nz > c->S ? fail(c, BDOF_ERR_ARG, "slice range outside [0, S)") : 0;
 }
+// the entry points that only know the least-squares data term
+static int need_lsq(bdof_ctx* c, const char* who) {
+    return c->loss_kind == BDOF_LOSS_LSQ ? 0 : fail(c, BDOF_ERR_STATE, std::string(who) + " computes the least-squares loss only: bdof_set_loss(BDOF_LOSS_LSQ) first");
+}
+static bool loss_is_poisson(const bdof_ctx* c) { return c->loss_kind == BDOF_LOSS_POISSON; }
 static int check_taper(bdof_ctx* c, int TX, int TY, int taper) {
     return taper < 0 || 2 * taper > TX || 2 * taper > TY ? fail(c, BDOF_ERR_ARG, "taper must fit the tile") : 0;
 }
@@ -561,11 +568,11 @@ static int launch_loss_real(bdof_ctx* c, int B, const cf* in, cf* out_hyb, bool 
     LossArgs a{sub_field(c, in), sub_field(c, out_hyb), sub_field(c, out_wave), sub_field(c, meas), c->partial + 2 * c->sub_part, B, c->NX,
                in_scale, out_scale, seed_scale, carrier, c->twY, pfield, c->meas_dev, nullptr, nullptr, make_double2(0.0, 0.0), make_double2(0.0, 0.0),
                c->meas_dev ? (dref_override ? *dref_override : meas_dref(c)) : 0.f,
-               pf64 ? pf64 : (pfield && pfield == c->pdet ? c->pdet64 : nullptr), pscale};
+               pf64 ? pf64 : (pfield && pfield == c->pdet ? c->pdet64 : nullptr), pscale, c->loss_mu};
     int grid = 0;
-    DISPATCH_N(c->NY, grid = rows_grid<N_>(c, B, c->NX); with_bool(tstore, [&](auto TSTORE) {
-        hipLaunchKernelGGL((k_row_loss<N_, false, TSTORE>), dim3(grid), dim3(BDOF_THREADS), 0, c->sub_stream, a);
-    }));
+    DISPATCH_N(c->NY, grid = rows_grid<N_>(c, B, c->NX); with_bool(tstore, [&](auto TSTORE) { with_bool(meas && loss_is_poisson(c), [&](auto PSN) {
+        hipLaunchKernelGGL((k_row_loss<N_, false, TSTORE, PSN>), dim3(grid), dim3(BDOF_THREADS), 0, c->sub_stream, a);
+    }); }));
     return grid;
 }
 
@@ -578,12 +585,11 @@ static int launch_loss_far(bdof_ctx* c, int B, const cf* in, cf* out_hyb, cf* ou
                in_scale, out_scale, seed_scale, carrier_det(c), c->twX, pfield, 0,
                gc ? c->gcar + c->sub_b0 : nullptr, gc ? c->gt0 + c->sub_b0 : nullptr,
                d2(carrier_end(c) * ((double)c->NX * (double)c->NY)), d2(carrier_end(c)), 0.f,
-               pf64 ? pf64 : (pfield && pfield == c->pdetT ? c->pdetT64 : nullptr), pscale};
+               pf64 ? pf64 : (pfield && pfield == c->pdetT ? c->pdetT64 : nullptr), pscale, c->loss_mu};
     int grid = 0;
-    DISPATCH_N(c->NX, {
-        grid = rows_grid<N_>(c, B, c->NY);
-        hipLaunchKernelGGL((k_row_loss<N_, true, true>), dim3(grid), dim3(BDOF_THREADS), 0, c->sub_stream, a);
-    });
+    DISPATCH_N(c->NX, grid = rows_grid<N_>(c, B, c->NY); with_bool(meas && loss_is_poisson(c), [&](auto PSN) {
+        hipLaunchKernelGGL((k_row_loss<N_, true, true, PSN>), dim3(grid), dim3(BDOF_THREADS), 0, c->sub_stream, a);
+    }));
     return grid;
 }
 
@@ -781,7 +787,7 @@ static int generic_forward(bdof_ctx* c, int B, void* out_wave, bool keep_tape) {
         GLossArgs la{c->bufA, (cf*)out_wave, nullptr, c->partial, B, c->NX, c->NY, c->det_mode == BDOF_DET_FAR,
                      make_float2((float)a.real(), (float)a.imag()), 0.f, c->pdet, 0, 0.f, nullptr, nullptr, make_double2(0.0, 0.0), make_double2(0.0, 0.0), nullptr,
                      nullptr, 0.0, make_double2(0.0, 0.0)};
-        hipLaunchKernelGGL(k_g_loss, dim3(g_elem_grid(c, n)), dim3(256), 0, c->stream, la);
+        hipLaunchKernelGGL(k_g_loss<false>, dim3(g_elem_grid(c, n)), dim3(256), 0, c->stream, la);
     }
     return 0;
 }
@@ -804,8 +810,8 @@ static int generic_loss_grad(bdof_ctx* c, int B, const float* meas, void* out_wa
         GLossArgs la{c->bufA, (cf*)out_wave, meas, c->partial, B, c->NX, c->NY, c->det_mode == BDOF_DET_FAR,
                      make_float2((float)a.real(), (float)a.imag()), 2.f / ((float)B * (float)c->NX * (float)c->NY), c->pdet, c->meas_dev,
                      c->meas_dev ? meas_dref(c) : 0.f, gc ? c->gcar : nullptr, gc ? c->gt0 : nullptr, d2(a), d2(carrier_end(c)), c->pdet ? c->pdet64 : nullptr,
-                     f64 ? c->g64 : nullptr, c->meas_dev ? std::abs(c->a0) : 0.0, make_double2(0.0, 0.0)};
-        hipLaunchKernelGGL(k_g_loss, dim3(egrid), dim3(256), 0, c->stream, la);
+                     f64 ? c->g64 : nullptr, c->meas_dev ? std::abs(c->a0) : 0.0, make_double2(0.0, 0.0), c->loss_mu};
+        with_bool(loss_is_poisson(c), [&](auto PSN) { hipLaunchKernelGGL(k_g_loss<PSN>, dim3(egrid), dim3(256), 0, c->stream, la); });
     }
     hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, c->stream, c->partial, egrid, 1.0 / ((double)B * c->NX * c->NY), c->loss_dev);
     if (f64) {
@@ -863,15 +869,15 @@ template <auto K> static int max_lds_once(bdof_ctx* c, int bytes) {
 }
 
 // ---- LDS-resident engine ---------------------------------------------------------------------------
-template <int N, int T, int WPE> static int resident_launch_t(bdof_ctx* c, const ResArgs& a, int grid, int* waves) {
+template <int N, int T, int WPE, bool PSN> static int resident_launch_t(bdof_ctx* c, const ResArgs& a, int grid, int* waves) {
     *waves = T / 64;
     const size_t lds = sizeof(cf) * ((size_t)N * (N | 1) + 2 * N) + sizeof(long long) * 3 * N;
-    if (int r = max_lds_once<k_resident<N, T, WPE>>(c, (int)lds)) return r;
-    hipLaunchKernelGGL((k_resident<N, T, WPE>), dim3(grid), dim3(T), lds, c->stream, a);
+    if (int r = max_lds_once<k_resident<N, T, WPE, PSN>>(c, (int)lds)) return r;
+    hipLaunchKernelGGL((k_resident<N, T, WPE, PSN>), dim3(grid), dim3(T), lds, c->stream, a);
     return 0;
 }
 template <int N> static int resident_launch(bdof_ctx* c, const ResArgs& a, int grid, int* waves) {
-    return resident_launch_t<N, ResPlan<N>::T, ResPlan<N>::WPE>(c, a, grid, waves);
+    return with_bool(a.meas && loss_is_poisson(c), [&](auto PSN) { return resident_launch_t<N, ResPlan<N>::T, ResPlan<N>::WPE, PSN>(c, a, grid, waves); });
 }
 
 // One workgroup per wavefield: against the streaming kernels (sizes with a fused plan) the resident engine wins once the
@@ -899,7 +905,7 @@ static int resident_run(bdof_ctx* c, int B, const float* meas, void* out_wave, b
     ResArgs a{c->probe, hdith ? c->hsT_d : c->hsT, c->hdetT, grad ? c->tape : nullptr, (size_t)c->Bmax * c->NX * c->NY, c->grot, c->obj, c->res_carrier,
               carrier_det(c), c->pstack, c->pdet, meas, (cf*)out_wave, c->partial, c->twR, B, c->S, c->det_mode,
               c->variant == BDOF_VARIANT_TF_ALL ? 1 : 0, grad ? 1 : 0, c->k, 2.f / ((float)B * (float)c->NX * (float)c->NY), c->meas_dev,
-              hdith ? c->hs_copies : 0, c->meas_dev ? meas_dref(c) : 0.f, grad ? c->gpsi0 : nullptr, c->pdet ? c->pdet64 : nullptr};
+              hdith ? c->hs_copies : 0, c->meas_dev ? meas_dref(c) : 0.f, grad ? c->gpsi0 : nullptr, c->pdet ? c->pdet64 : nullptr, c->loss_mu};
     const int grid = B < c->npartial ? B : c->npartial;
     int r = 0, waves = 1;
     switch (c->NX) {
@@ -1277,6 +1283,15 @@ int bdof_set_meas_mode(bdof_ctx* c, int mode) {
     return 0;
 }
 
+int bdof_set_loss(bdof_ctx* c, int kind, double multiplier) {
+    if (!c) return BDOF_ERR_ARG;
+    if (kind != BDOF_LOSS_LSQ && kind != BDOF_LOSS_POISSON) return fail(c, BDOF_ERR_ARG, "bdof_set_loss: kind must be BDOF_LOSS_LSQ or BDOF_LOSS_POISSON");
+    if (!(multiplier > 0.0)) return fail(c, BDOF_ERR_ARG, "bdof_set_loss: multiplier must be > 0");
+    c->loss_kind = kind;
+    c->loss_mu = multiplier;
+    return 0;
+}
+
 int bdof_probe_stack_supported(bdof_ctx* c) {
     // every engine of the transfer-function path carries it (the real-space propagator of bdof_set_conv does not)
     return c && c->NY > 0 ? 1 : 0;
@@ -1595,12 +1610,13 @@ int bdof_adjoint_range(bdof_ctx* c, int B, const int* angle_of_b, const int* xof
 int bdof_field_loss_seed(bdof_ctx* c, void* field, const float* meas, int FX, int FY) {
     if (!c || !field || !meas || FX < 1 || FY < 1) return BDOF_ERR_ARG;
     if (!c->partial) return fail(c, BDOF_ERR_STATE, "bdof_configure has not been called");
+    if (int r = need_lsq(c, "bdof_field_loss_seed")) return r;
     HIPC(c, hipSetDevice(c->device));
     const size_t n = (size_t)FX * FY;
     const int egrid = g_elem_grid(c, n);
     GLossArgs la{(cf*)field, nullptr, meas, c->partial, 1, FX, FY, 0, make_float2(0.f, 0.f), (float)(2.0 / (double)n), nullptr, 0, 0.f,
                  nullptr, nullptr, make_double2(0.0, 0.0), make_double2(0.0, 0.0), nullptr, nullptr, 0.0, make_double2(0.0, 0.0)};
-    hipLaunchKernelGGL(k_g_loss, dim3(egrid), dim3(256), 0, c->stream, la);
+    hipLaunchKernelGGL(k_g_loss<false>, dim3(egrid), dim3(256), 0, c->stream, la);
     hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, c->stream, c->partial, egrid, 1.0 / (double)n, c->loss_dev);
     return launched(c);
 }
@@ -1889,6 +1905,7 @@ int bdof_set_conv_f64_detector(bdof_ctx* c, const double* hdetT) {
 int bdof_loss_grad_conv_f64(bdof_ctx* c, int B, const int* angle_of_b, const int* xoff, const int* yoff, const float* meas, double meas_ref) {
     if (!c || !meas) return BDOF_ERR_ARG;
     if (!c->c64_ks || c->c64_tf) return fail(c, BDOF_ERR_STATE, "bdof_set_conv_f64 has not been called");
+    if (int rl = need_lsq(c, "bdof_loss_grad_conv_f64")) return rl;
     if (!c->obj_src) return fail(c, BDOF_ERR_STATE, "bdof_set_object (with (delta, beta) rows) has not been called");
     if (!c->grot || !c->partial) return fail(c, BDOF_ERR_STATE, "bdof_configure(with_grad = 1) needed");
     int r;
@@ -1927,7 +1944,7 @@ int bdof_loss_grad_conv_f64(bdof_ctx* c, int B, const int* angle_of_b, const int
     if (far) RFC(c, rocfft_execute(pf, buf, nullptr, c->fft.info));           // un-shifted, un-normalised fft2 (propagation.py:114-115)
     else if (near) { if ((r = bdof_fields_free_step(c, psi, B, N, N, c->c64_hdet, 0, 1))) return r; }      // propagation.py:122-124
     const int lgrid = std::min(eg, c->npartial);
-    hipLaunchKernelGGL(k_c64_loss, dim3(lgrid), dim3(256), 0, c->stream, psi, meas, c->partial, B, N, N, far ? 1 : 0, meas_ref, 2.0 / (double)n);
+    hipLaunchKernelGGL(k_c64_loss<false>, dim3(lgrid), dim3(256), 0, c->stream, psi, meas, c->partial, B, N, N, far ? 1 : 0, meas_ref, 2.0 / (double)n, 0.0);
     hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, c->stream, c->partial, lgrid, 1.0 / (double)n, c->loss_dev);
     if (far) RFC(c, rocfft_execute(pi, buf, nullptr, c->fft.info));           // G(q) = N^2 ifft2(G(d)): the un-normalised inverse
     else if (near) { if ((r = bdof_fields_free_step(c, psi, B, N, N, c->c64_hdet, 1, 1))) return r; }
@@ -2005,7 +2022,9 @@ int bdof_loss_grad_tf_f64(bdof_ctx* c, int B, const int* angle_of_b, const int* 
     if (c->det_mode == BDOF_DET_NEAR) { if ((r = bdof_fields_free_step(c, psi, B, NX, NY, c->c64_hdet, 0, 1))) return r; }
     else if (far) RFC(c, rocfft_execute(pf, buf, nullptr, c->fft.info));       // un-shifted, un-normalised fft2
     const int lgrid = std::min(eg, c->npartial);
-    hipLaunchKernelGGL(k_c64_loss, dim3(lgrid), dim3(256), 0, c->stream, psi, meas, c->partial, B, NX, NY, far ? 1 : 0, meas_ref, 2.0 / (double)n);
+    with_bool(loss_is_poisson(c), [&](auto PSN) {
+        hipLaunchKernelGGL(k_c64_loss<PSN>, dim3(lgrid), dim3(256), 0, c->stream, psi, meas, c->partial, B, NX, NY, far ? 1 : 0, meas_ref, 2.0 / (double)n, c->loss_mu);
+    });
     hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, c->stream, c->partial, lgrid, 1.0 / (double)n, c->loss_dev);
     if (c->det_mode == BDOF_DET_NEAR) { if ((r = bdof_fields_free_step(c, psi, B, NX, NY, c->c64_hdet, 1, 1))) return r; }
     else if (far) RFC(c, rocfft_execute(pi, buf, nullptr, c->fft.info));       // F^H: the un-normalised inverse
@@ -2368,6 +2387,7 @@ int bdof_loss_grad_conv(bdof_ctx* c, int B, const int* angle_of_b, const int* xo
     int r = conv_check(c, B, angle_of_b);
     if (r) return r;
     if (!meas) return BDOF_ERR_ARG;
+    if ((r = need_lsq(c, "bdof_loss_grad_conv"))) return r;
     // residual splitting at the detector (bdof_set_meas_mode(1): meas holds m - |a_0|), real-space detectors: the renormalised
     // wave is kept as A + e', A = s a_S a float64 scalar formed on the host from the corner pixel, and |A + e'| - m is
     // evaluated without the cancellation of two numbers of size one (loss_seed_dev) — as on the transfer-function path
@@ -2414,7 +2434,7 @@ int bdof_loss_grad_conv(bdof_ctx* c, int B, const int* angle_of_b, const int* xo
         hipLaunchKernelGGL((k_conv_final<0>), dim3(egrid), dim3(256), 0, c->stream, fa);
         GLossArgs la{c->bufA, (cf*)out_wave, meas, c->partial, B, c->NX, c->NY, 0, zero, (float)seed_scale, c->cstack + (size_t)c->S * plane, 0, 0.f,
                      nullptr, nullptr, make_double2(0.0, 0.0), make_double2(0.0, 0.0), c->cdet64, nullptr, 0.0, s64};
-        hipLaunchKernelGGL(k_g_loss, dim3(egrid), dim3(256), 0, c->stream, la);
+        hipLaunchKernelGGL(k_g_loss<false>, dim3(egrid), dim3(256), 0, c->stream, la);
         hipLaunchKernelGGL(k_conv_scale_seed, dim3(egrid), dim3(256), 0, c->stream, c->bufA, c->conv_scal, n);
         npart = egrid;
         gp = c->bufA;

@@ -59,8 +59,10 @@ __global__ __launch_bounds__(256) void k_c64_scale(double2* f, size_t n, const d
 }
 // loss partials and seed in place: d [B][NX][NY]; far: d is [b][kx][ky] and meas [b][ky][kx] (un-shifted), else both [b][x][y].
 // meas holds m - meas_ref (residual splitting of the float32 path); G = 2 (|d| - m) d / |d| * seed_scale
+// PSN: the Poisson data term with mu photons per unit intensity (poisson_weight, bdof_kernels.h)
+template <bool PSN>
 __global__ __launch_bounds__(256) void k_c64_loss(double2* d, const float* __restrict__ meas, double* partial, int B, int NX, int NY, int far,
-                                                 double meas_ref, double seed_scale) {
+                                                 double meas_ref, double seed_scale, double mu) {
     const size_t n = (size_t)B * NX * NY;
     double acc = 0.0, acc2 = 0.0;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
@@ -71,10 +73,15 @@ __global__ __launch_bounds__(256) void k_c64_loss(double2* d, const float* __res
         const double2 v = d[i];
         const double a = sqrt(v.x * v.x + v.y * v.y);
         const double res = a - m;
-        acc += res * res;
-        acc2 += res * a;
-        const double f = a > 0.0 ? seed_scale * res / a : 0.0;
-        d[i] = make_double2(v.x * f, v.y * f);
+        if constexpr (PSN) {
+            const double f = seed_scale * poisson_weight(res, a, m, mu, acc, acc2);
+            d[i] = make_double2(v.x * f, v.y * f);
+        } else {
+            acc += res * res;
+            acc2 += res * a;
+            const double f = a > 0.0 ? seed_scale * res / a : 0.0;
+            d[i] = make_double2(v.x * f, v.y * f);
+        }
     }
     __shared__ double w[2][4];
     acc = wave_reduce_sum(acc);

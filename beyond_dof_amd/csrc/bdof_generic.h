@@ -69,8 +69,11 @@ struct GLossArgs {
     double2* seed64;         // nullable [B][NX][NY]: float64 adjoint sweep (bdof_configure flag 64) — detector wave, residual and
     double meas_ref;         // seed all formed in float64 and left here un-rounded; meas_ref: what the host subtracted (meas_dev)
     double2 pscale;          // complex factor on pdet64 (the real-space propagator's renormalisation s; 0, 0 means 1)
+    double mu;               // PSN (bdof_set_loss): photons per unit intensity
 };
 
+// PSN: the Poisson data term (poisson_weight, bdof_kernels.h)
+template <bool PSN>
 __global__ __launch_bounds__(256) void k_g_loss(GLossArgs a) {
     const size_t n = (size_t)a.B * a.NX * a.NY;
     double acc = 0.0, acc2 = 0.0;
@@ -88,18 +91,22 @@ __global__ __launch_bounds__(256) void k_g_loss(GLossArgs a) {
             const size_t oi = a.far ? ((size_t)b * a.NY + y) * a.NX + x : idx;
             const double dx = p.x + (double)d.x, dy = p.y + (double)d.y;
             const double ab = sqrt(dx * dx + dy * dy), rr = ab - ((double)a.meas[oi] + a.meas_ref);
-            acc += rr * rr;
-            acc2 += rr * ab;
-            const double f = ab > 0.0 ? (double)a.seed_scale * rr / ab : 0.0;
-            a.seed64[idx] = make_double2(dx * f, dy * f);
+            if constexpr (PSN) {
+                a.seed64[idx] = poisson_seed64(dx, dy, ab, rr, (double)a.seed_scale, a.mu, acc, acc2);
+            } else {
+                acc += rr * rr;
+                acc2 += rr * ab;
+                const double f = ab > 0.0 ? (double)a.seed_scale * rr / ab : 0.0;
+                a.seed64[idx] = make_double2(dx * f, dy * f);
+            }
             if (a.out_wave) a.out_wave[oi] = make_float2((float)dx, (float)dy);
             continue;
         }
         if (a.meas_dev && a.meas && !a.far && !a.pdet) {
             const size_t oidx = idx;
             if (a.out_wave) a.out_wave[oidx] = cadd(d, a.carrier);
-            a.field[idx] = loss_seed_dev(d, a.carrier, sqrtf(a.carrier.x * a.carrier.x + a.carrier.y * a.carrier.y), a.meas[oidx],
-                                         a.seed_scale, acc, acc2, a.dref);
+            a.field[idx] = loss_seed_dev_k<PSN>(d, a.carrier, sqrtf(a.carrier.x * a.carrier.x + a.carrier.y * a.carrier.y), a.meas[oidx],
+                                                a.seed_scale, a.mu, acc, acc2, a.dref);
             continue;
         }
         const cf e0 = d;
@@ -108,7 +115,7 @@ __global__ __launch_bounds__(256) void k_g_loss(GLossArgs a) {
             cf dw;
             double2 p = a.pdet64[(size_t)x * a.NY + y];
             if (a.pscale.x != 0.0 || a.pscale.y != 0.0) p = make_double2(p.x * a.pscale.x - p.y * a.pscale.y, p.x * a.pscale.y + p.y * a.pscale.x);
-            a.field[idx] = loss_seed_f64(d, p, a.meas[oi], a.seed_scale, acc, acc2, dw);
+            a.field[idx] = loss_seed_f64_k<PSN>(d, p, a.meas[oi], a.seed_scale, a.mu, acc, acc2, dw);
             if (a.out_wave) a.out_wave[oi] = dw;
             continue;
         }
@@ -120,16 +127,21 @@ __global__ __launch_bounds__(256) void k_g_loss(GLossArgs a) {
             // DC bin in float64, its seed kept out of the transforms (AdjCarrier)
             const double dx = a.carrier_dd.x + (double)e0.x, dy = a.carrier_dd.y + (double)e0.y;
             const double ab = sqrt(dx * dx + dy * dy), rr = ab - (double)a.meas[oidx];
-            acc += rr * rr;
-            acc2 += rr * ab;
-            const double f = ab > 0.0 ? (double)a.seed_scale * rr / ab : 0.0;
-            const double2 s0 = make_double2(dx * f, dy * f);
+            double2 s0;
+            if constexpr (PSN) {
+                s0 = poisson_seed64(dx, dy, ab, rr, (double)a.seed_scale, a.mu, acc, acc2);
+            } else {
+                acc += rr * rr;
+                acc2 += rr * ab;
+                const double f = ab > 0.0 ? (double)a.seed_scale * rr / ab : 0.0;
+                s0 = make_double2(dx * f, dy * f);
+            }
             a.gcar[b] = s0;
             a.gt0[b] = make_double2(a.a_end.x * s0.x + a.a_end.y * s0.y, a.a_end.x * s0.y - a.a_end.y * s0.x);
             a.field[idx] = make_float2(0.f, 0.f);
             continue;
         }
-        if (a.meas) a.field[idx] = loss_seed(d, a.meas[oidx], a.seed_scale, acc, acc2);
+        if (a.meas) a.field[idx] = loss_seed_k<PSN>(d, a.meas[oidx], a.seed_scale, a.mu, acc, acc2);
     }
     if (a.meas) {
         __shared__ double w1[4], w2[4];

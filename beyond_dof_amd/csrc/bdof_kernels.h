@@ -416,6 +416,7 @@ struct LossArgs {
     float dref;          // meas_dev: |carrier| - reference subtracted by the host (loss_seed_dev)
     const double2* pfield64;   // nullable: `pfield` in float64 — the residual is then formed in float64 (loss_seed_f64)
     double2 pscale;            // complex factor on pfield64 (the real-space propagator's renormalisation s, else 1)
+    double mu;                 // PSN instantiations (bdof_set_loss): photons per unit intensity
 };
 
 // Adjoint carrier.  With a plane-wave probe and a far-field detector nearly all of the detector wave sits in ONE bin (DC,
@@ -480,8 +481,65 @@ __device__ __forceinline__ cf loss_seed_f64(cf e, double2 p, float m, float seed
     return make_float2((float)(dx * f), (float)(dy * f));
 }
 
-// FAR = false: inverse FFT first (rows of L1); FAR = true: forward FFT first (rows of L2).
-template <int N, bool FAR, bool TSTORE>
+// ---- Poisson (photon-counting) data term: bdof_set_loss(BDOF_LOSS_POISSON, mu), include/bdof.h ---------------------------
+// Per pixel, with a = |d|, m the measured amplitude, r = a - m and mu photons per unit intensity, the deviance
+//     L = mu (a^2 - m^2 - 2 m^2 ln(a / m)) = mu (r (a + m) - 2 m^2 log1p(r / m))          (m = 0: mu a^2)
+// — the reference's commented mu a^2 - mu m^2 ln(mu a^2) minus its value at a = m (same gradient, zero at the fit, ~ 2 mu r^2
+// near it; the raw form is a constant of order mu ln mu per pixel, which costs the sum its digits and blinds a stopping rule that
+// looks at the relative change).  The two first-order parts of the term cancel, so it is evaluated in float64 from r — which
+// every site forms without cancellation, exactly as for least squares (loss_seed_dev / loss_seed_f64 / the float64 DC bin).
+// Seed G(d) = seed_scale w d with w = mu r (a + m) / a^2: the least-squares weight r / a times mu (a + m) / a.
+// Second sum (k_conv_finish's meaning, sum Re(conj(d) G) / seed_scale): mu r (a + m).  a = 0: nothing, and no epsilon.
+// The ONE place the five detector kernels take the Poisson term from; least squares stays where it was, instruction by
+// instruction (the kernels carry the kind as a template parameter).
+__device__ __forceinline__ double poisson_weight(double r, double a, double m, double mu, double& acc, double& acc2) {
+    if (!(a > 0.0)) return 0.0;
+    const double s = r * (a + m);
+    acc += mu * (m > 0.0 ? s - 2.0 * m * m * log1p(r / m) : s);
+    acc2 += mu * s;
+    return mu * s / (a * a);
+}
+// the three seed forms above under either loss kind (PSN: Poisson).  Where the amplitude itself is not in hand (residual
+// splitting) m = a - r is accurate enough for the factor.
+template <bool PSN> __device__ __forceinline__ cf loss_seed_k(cf d, float m, float seed_scale, double mu, double& acc, double& acc2) {
+    if constexpr (!PSN) return loss_seed(d, m, seed_scale, acc, acc2);
+    else {
+        const float a = sqrtf(d.x * d.x + d.y * d.y);
+        const float f = (float)((double)seed_scale * poisson_weight((double)(a - m), (double)a, (double)m, mu, acc, acc2));
+        return make_float2(d.x * f, d.y * f);
+    }
+}
+template <bool PSN>
+__device__ __forceinline__ cf loss_seed_dev_k(cf e, cf a, float abs_a, float mdev, float seed_scale, double mu, double& acc, double& acc2, float dref) {
+    if constexpr (!PSN) return loss_seed_dev(e, a, abs_a, mdev, seed_scale, acc, acc2, dref);
+    else {
+        const cf d = cadd(a, e);
+        const float ab = sqrtf(d.x * d.x + d.y * d.y);
+        const float q = fmaf(2.f * a.x, e.x, fmaf(2.f * a.y, e.y, fmaf(e.x, e.x, e.y * e.y)));
+        const float r = q / (ab + abs_a) - (mdev - dref);
+        const float f = (float)((double)seed_scale * poisson_weight((double)r, (double)ab, (double)ab - (double)r, mu, acc, acc2));
+        return make_float2(d.x * f, d.y * f);
+    }
+}
+template <bool PSN>
+__device__ __forceinline__ cf loss_seed_f64_k(cf e, double2 p, float m, float seed_scale, double mu, double& acc, double& acc2, cf& d_out) {
+    if constexpr (!PSN) return loss_seed_f64(e, p, m, seed_scale, acc, acc2, d_out);
+    else {
+        const double dx = p.x + (double)e.x, dy = p.y + (double)e.y;
+        const double ab = sqrt(dx * dx + dy * dy);
+        const double f = (double)seed_scale * poisson_weight(ab - (double)m, ab, (double)m, mu, acc, acc2);
+        d_out = make_float2((float)dx, (float)dy);
+        return make_float2((float)(dx * f), (float)(dy * f));
+    }
+}
+// a float64 site's own residual rr of a wave (dx, dy) of modulus ab: its Poisson seed (the least-squares lines stay at the sites)
+__device__ __forceinline__ double2 poisson_seed64(double dx, double dy, double ab, double rr, double seed_scale, double mu, double& acc, double& acc2) {
+    const double f = seed_scale * poisson_weight(rr, ab, ab - rr, mu, acc, acc2);
+    return make_double2(dx * f, dy * f);
+}
+
+// FAR = false: inverse FFT first (rows of L1); FAR = true: forward FFT first (rows of L2).  PSN: the Poisson data term.
+template <int N, bool FAR, bool TSTORE, bool PSN = false>
 __global__ __launch_bounds__(BDOF_THREADS, RowCfg<N>::MIN_WAVES) void k_row_loss(LossArgs a) {
     typedef RowCfg<N> C;
     constexpr int S1 = FAR ? -1 : +1;     // direction of the first transform; the second is the opposite
@@ -522,7 +580,7 @@ __global__ __launch_bounds__(BDOF_THREADS, RowCfg<N>::MIN_WAVES) void k_row_loss
                     const double2 q = pf[tid + m * C::T];
                     const double2 p = make_double2(q.x * a.pscale.x - q.y * a.pscale.y, q.x * a.pscale.y + q.y * a.pscale.x);
                     cf dw;
-                    if (a.meas) u[m] = loss_seed_f64(u[m], p, mm[m], a.seed_scale, acc, acc2, dw);
+                    if (a.meas) u[m] = loss_seed_f64_k<PSN>(u[m], p, mm[m], a.seed_scale, a.mu, acc, acc2, dw);
                     else dw = u[m] = make_float2((float)(p.x + (double)u[m].x), (float)(p.y + (double)u[m].y));
                     if (a.out_wave) a.out_wave[off + tid + m * C::T] = dw;
                 }
@@ -534,7 +592,7 @@ __global__ __launch_bounds__(BDOF_THREADS, RowCfg<N>::MIN_WAVES) void k_row_loss
                     for (int m = 0; m < 8; ++m) a.out_wave[off + tid + m * C::T] = cadd(u[m], a.carrier);
                 }
 #pragma unroll
-                for (int m = 0; m < 8; ++m) u[m] = loss_seed_dev(u[m], a.carrier, abs_a, mm[m], a.seed_scale, acc, acc2, a.dref);
+                for (int m = 0; m < 8; ++m) u[m] = loss_seed_dev_k<PSN>(u[m], a.carrier, abs_a, mm[m], a.seed_scale, a.mu, acc, acc2, a.dref);
             } else {
                 if (a.pfield) {
                     const cf* pf = a.pfield + (size_t)(r0 + r) * N;
@@ -557,17 +615,22 @@ __global__ __launch_bounds__(BDOF_THREADS, RowCfg<N>::MIN_WAVES) void k_row_loss
                             // float32 path below contribute exactly nothing for this bin.
                             const double dx = a.carrier_dd.x + (double)e0.x, dy = a.carrier_dd.y + (double)e0.y;
                             const double ab = sqrt(dx * dx + dy * dy), rr = ab - (double)mm[0];
-                            acc += rr * rr;
-                            acc2 += rr * ab;
-                            const double f = ab > 0.0 ? (double)a.seed_scale * rr / ab : 0.0;
-                            const double2 s0 = make_double2(dx * f, dy * f);
+                            double2 s0;
+                            if constexpr (PSN) {
+                                s0 = poisson_seed64(dx, dy, ab, rr, (double)a.seed_scale, a.mu, acc, acc2);
+                            } else {
+                                acc += rr * rr;
+                                acc2 += rr * ab;
+                                const double f = ab > 0.0 ? (double)a.seed_scale * rr / ab : 0.0;
+                                s0 = make_double2(dx * f, dy * f);
+                            }
                             a.gcar[b] = s0;
                             a.gt0[b] = make_double2(a.a_end.x * s0.x + a.a_end.y * s0.y, a.a_end.x * s0.y - a.a_end.y * s0.x);
                             u[0] = make_float2(mm[0], 0.f);
                         }
                     }
 #pragma unroll
-                    for (int m = 0; m < 8; ++m) u[m] = loss_seed(u[m], mm[m], a.seed_scale, acc, acc2);
+                    for (int m = 0; m < 8; ++m) u[m] = loss_seed_k<PSN>(u[m], mm[m], a.seed_scale, a.mu, acc, acc2);
                 }
             }
             if (a.out_hyb) {

@@ -313,6 +313,7 @@ struct ResArgs {
     float dref;
     cf* gpsi0;             // nullable [B][N][N]: G(psi_0), the probe gradient per wavefield
     const double2* pdet64; // nullable: `pdet` in float64 — the residual |d| - m is then formed in float64 (loss_seed_f64)
+    double mu;             // PSN instantiations (bdof_set_loss): photons per unit intensity
 };
 
 // transfer-function multiply folded into the last pass of the forward transform: the thread writing element (kx, ky)
@@ -530,7 +531,9 @@ template <int N, int T> struct ResPoint {
 };
 
 // WPE = waves per SIMD the register allocation must leave room for (two workgroups per CU where the LDS image allows)
-template <int N, int T, int WPE>
+// PSN: the Poisson data term (poisson_weight, bdof_kernels.h) — a template parameter, so that the least-squares kernels are
+// the instructions they were
+template <int N, int T, int WPE, bool PSN = false>
 __global__ __launch_bounds__(T, WPE) void k_resident(ResArgs a) {
     typedef ResPipe<N, T> Pipe;
     typedef ResPoint<N, T> Point;
@@ -627,17 +630,17 @@ __global__ __launch_bounds__(T, WPE) void k_resident(ResArgs a) {
                     const size_t o = b * fsz + (far ? y * N + x : e);
                     cf d = f[x * P + y], seed;
                     if (mode == 1) {               // plane-wave carrier, real-space detector, residual splitting (loss_seed_dev)
-                        seed = loss_seed_dev(d, a.carrier_det, abs_car, a.meas[o], a.seed_scale, acc, acc2, a.dref);
+                        seed = loss_seed_dev_k<PSN>(d, a.carrier_det, abs_car, a.meas[o], a.seed_scale, a.mu, acc, acc2, a.dref);
                         d = cadd(d, a.carrier_det);
                     } else if (mode == 2) {        // carrier field in float64: |d| - m in float64 (loss_seed_f64)
                         cf dw;
-                        seed = loss_seed_f64(d, a.pdet64[e], a.meas[o], a.seed_scale, acc, acc2, dw);
+                        seed = loss_seed_f64_k<PSN>(d, a.pdet64[e], a.meas[o], a.seed_scale, a.mu, acc, acc2, dw);
                         d = dw;
                     } else {
                         if (a.pdet) d = cadd(d, a.pdet[e]);
                         else if (!far || e == 0) d = cadd(d, a.carrier_det);
                         seed = d;
-                        if (mode == 3) seed = loss_seed(d, a.meas[o], a.seed_scale, acc, acc2);
+                        if (mode == 3) seed = loss_seed_k<PSN>(d, a.meas[o], a.seed_scale, a.mu, acc, acc2);
                     }
                     if (a.out_wave) a.out_wave[o] = d;
                     if (mode != 0) f[x * P + y] = seed;

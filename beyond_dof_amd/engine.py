@@ -11,6 +11,22 @@ from ._lib import DeviceBuffer
 from . import util
 
 _VARIANT = {'numpy_skip_last': _lib.VARIANT_NUMPY_SKIP_LAST, 'tf_all': _lib.VARIANT_TF_ALL}
+_LOSS = {'lsq': _lib.LOSS_LSQ, 'poisson': _lib.LOSS_POISSON}
+
+
+def check_loss(loss_type, poisson_multiplier):
+    """The data term's two keywords as every layer takes them (raises ValueError)."""
+    if loss_type not in _LOSS:
+        raise ValueError("loss_type must be 'lsq' or 'poisson'")
+    if not float(poisson_multiplier) > 0:
+        raise ValueError('poisson_multiplier must be > 0')
+
+
+def check_poisson_path(loss_type, poisson_multiplier, propagator):
+    """check_loss, and that 'poisson' goes with the transfer-function propagator — the only one whose detector kernels carry it."""
+    check_loss(loss_type, poisson_multiplier)
+    if loss_type == 'poisson' and propagator != 'fft':
+        raise ValueError("loss_type='poisson' runs on the transfer-function propagator (propagator='fft') only")
 
 
 def _hp(arr):
@@ -45,7 +61,7 @@ class MultisliceEngine(object):
             | (_lib.CFG_NO_RESIDENT if engine == 'streaming' else 0) | (_lib.CFG_ALWAYS_RESIDENT if engine == 'resident' else 0) \
             | (_lib.CFG_RECOMPUTE if self.recompute else 0) | (_lib.CFG_NO_GROT if no_grot else 0) | (_lib.CFG_ADJOINT64 if self.adjoint64 else 0)
         self.ctx.check(self.lib.bdof_configure(self.h, self.ny, self.nx, self.n_slice, self.batch_max, flags))
-        self._reset_host_state()
+        self._reset_host_state()        # after bdof_configure, never before: it puts the ctx's data term back through the library (set_loss)
 
     # Host state: what the setters below record on the instance; before that, and after _reset_host_state(), as declared here.
     optics = None               # util.Optics of set_physics
@@ -60,11 +76,23 @@ class MultisliceEngine(object):
     tf_f64 = conv_f64 = False
     _gprobe = None              # enable_probe_grad
     residual_split = True       # False: amplitudes go to the device as they are (a probe that changes between steps)
+    loss_type, poisson_multiplier = 'lsq', 2e6      # set_loss
 
     def _reset_host_state(self):
         for name in set(vars(self)) & set(vars(MultisliceEngine)):
             delattr(self, name)
         self._keep = {}         # device buffers that must outlive the calls that registered them
+        self.set_loss()         # the one setting that is sticky on the ctx itself (it survives bdof_configure): as declared, too
+
+    # ---- data term -----------------------------------------------------------------------------
+    def set_loss(self, kind='lsq', multiplier=2e6):
+        """The data term loss_grad minimises (bdof_set_loss, include/bdof.h): 'lsq', mean((|d| - m)^2), or 'poisson', the
+        photon-counting likelihood's deviance mean(mu (|d|^2 - m^2 - 2 m^2 ln(|d| / m))) with mu = multiplier photons per unit
+        intensity (tensorflow_recon/ptychography.py's poisson_multiplier).  Transfer-function propagator only: under 'poisson'
+        loss_grad(conv=True) and the tiled propagator's field loss raise."""
+        check_loss(kind, multiplier)
+        self.ctx.check(self.lib.bdof_set_loss(self.h, _LOSS[kind], float(multiplier)))
+        self.loss_type, self.poisson_multiplier = kind, float(multiplier)
 
     # ---- physics -------------------------------------------------------------------------------
     def set_physics(self, energy_ev, psize_cm, free_prop_cm=None, variant='numpy_skip_last', pi=util.PI, field_shape=None,

@@ -23,6 +23,7 @@ import numpy as np
 from . import h5io, tiffio, util
 from .comm import get_comm, minibatch_schedule
 from .misc import create_summary
+from .engine import check_poisson_path
 from .solver import FullfieldSolver
 from .util import print_flush
 
@@ -60,7 +61,7 @@ def reconstruct_fullfield(fname, theta_st=0, theta_end=PI, n_epochs='auto', crit
                           multiscale_level=1, n_epoch_final_pass=None, initial_guess=None, n_batch_per_update=5,
                           dynamic_rate=True, probe_type='plane', probe_initial=None, probe_learning_rate=1e-3,
                           pupil_function=None, theta_downsample=None, forward_algorithm='fresnel', random_theta=True,
-                          object_type='normal', kernel_size=17, debug=False, **kwargs):
+                          object_type='normal', kernel_size=17, debug=False, loss_type='lsq', poisson_multiplier=2e6, **kwargs):
     """Reconstruct a beyond-depth-of-focus object from full-field projections (see the module docstring and
     cnn_propagator/fullfield.py:28-77 for the parameters).  Returns (obj_delta, obj_beta) of the finest level."""
     t_zero = time.time()
@@ -78,6 +79,10 @@ def reconstruct_fullfield(fname, theta_st=0, theta_end=PI, n_epochs='auto', crit
     adjoint_precision = kwargs.get('adjoint_precision', 'float32')
     if adjoint_precision not in ('float32', 'float64', 'first-step'):
         raise ValueError("adjoint_precision must be 'float32', 'float64' or 'first-step'")
+    # 'lsq': mean((|d| - m)^2), the reference's active line; 'poisson': the photon-counting likelihood next to it in
+    # tensorflow_recon/ptychography.py, as its deviance (include/bdof.h, bdof_set_loss), with poisson_multiplier photons per unit
+    # intensity.  Near the fit it is ~ 2 poisson_multiplier times the least-squares term: rescale alpha_d / alpha_b / gamma with it.
+    check_poisson_path(loss_type, poisson_multiplier, propagator)
     # gradient accumulation over n_batch_per_update minibatches exists only in the TF twin (tensorflow_recon/fullfield.py:
     # 413-425); the cnn variant accepts the keyword and ignores it (default 5!), so it is opt-in here
     accumulate = bool(kwargs.get('accumulate_gradients', False))
@@ -178,7 +183,8 @@ def reconstruct_fullfield(fname, theta_st=0, theta_end=PI, n_epochs='auto', crit
                                  free_prop_cm=free_prop_cm, probe_real=probe_real, probe_imag=probe_imag, variant=variant,
                                  comm=comm, device=comm.local_rank, coord_ls=coord_ls, propagator=propagator, kernel_size=kernel_size,
                                  rotation=rotation, theta=theta, adjoint64={'float32': None, 'float64': True, 'first-step': 'first'}[adjoint_precision],
-                                 detector_kernel=kwargs.get('detector_kernel', 'TF'))   # 'IR' / 'auto': np_funcs.py:51-61
+                                 detector_kernel=kwargs.get('detector_kernel', 'TF'),   # 'IR' / 'auto': np_funcs.py:51-61
+                                 loss_type=loss_type, poisson_multiplier=poisson_multiplier)
         solver.set_volume(obj_delta, obj_beta)
         solver.set_mask(mask)
         solver.set_measurements(np.abs(prj))

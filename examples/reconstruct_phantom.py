@@ -7,6 +7,10 @@ the far field with a plane probe (one bright bin) it does not converge — prope
 reference.
 
     python examples/reconstruct_phantom.py [n=128] [n_theta=60] [n_epochs=100] [learning_rate=2e-8] [free_prop_cm=1e-3] [minibatch=10]
+                                           [propagator=fft] [--loss lsq|poisson] [--poisson-multiplier 2e6]
+
+--loss poisson minimises the photon-counting likelihood (loss_type='poisson'); its data term is ~ 2 * multiplier times the
+least-squares one, and the L1 weights are scaled with it here.
 """
 import os
 import sys
@@ -32,7 +36,7 @@ def phantom(n, rng):
     return d
 
 
-def run(n=128, n_theta=60, n_epochs=100, lr=2e-8, fp=1e-3, quiet=False, mb=10, propagator='fft'):
+def run(n=128, n_theta=60, n_epochs=100, lr=2e-8, fp=1e-3, quiet=False, mb=10, propagator='fft', loss='lsq', multiplier=2e6):
     """Simulate, write exchange/data, reconstruct, compare with the phantom: returns the figures main() prints
     (tests/test_gpu_convergence.py asserts them)."""
     import contextlib
@@ -48,12 +52,14 @@ def run(n=128, n_theta=60, n_epochs=100, lr=2e-8, fp=1e-3, quiet=False, mb=10, p
         del s
         os.makedirs('case')
         h5io.write_dataset('case/data.h5', 'exchange/data', prj.astype(np.complex64))
+        reg = 2 * multiplier if loss == 'poisson' else 1.0      # the regulariser keeps its weight beside the data term
         t0 = time.time()
         with (contextlib.redirect_stdout(io.StringIO()) if quiet else contextlib.nullcontext()):
             rd, rb = reconstruct_fullfield('data.h5', theta_st=0, theta_end=2 * np.pi, n_epochs=n_epochs, learning_rate=lr,
                                            minibatch_size=mb, energy_ev=5000, psize_cm=1e-7, free_prop_cm=fp, save_path='case',
-                                           output_folder='out', shrink_cycle=None, seed=3, alpha_d=1e-9, alpha_b=1e-10, gamma=0,
-                                           initial_guess=[np.zeros_like(d), np.zeros_like(d)], propagator=propagator)
+                                           output_folder='out', shrink_cycle=None, seed=3, alpha_d=1e-9 * reg, alpha_b=1e-10 * reg, gamma=0,
+                                           initial_guess=[np.zeros_like(d), np.zeros_like(d)], propagator=propagator,
+                                           loss_type=loss, poisson_multiplier=multiplier)
         dt = time.time() - t0
         os.chdir(cwd)
     inner = (slice(n // 4, -n // 4),) * 3
@@ -64,7 +70,19 @@ def run(n=128, n_theta=60, n_epochs=100, lr=2e-8, fp=1e-3, quiet=False, mb=10, p
             'beta_corr': float(np.corrcoef(rb.ravel(), 0.1 * d.ravel())[0, 1])}
 
 
+def _option(name, default):
+    """--name value, taken out of sys.argv (the positional arguments keep their places)."""
+    if name not in sys.argv:
+        return default
+    i = sys.argv.index(name)
+    value = sys.argv[i + 1]
+    del sys.argv[i:i + 2]
+    return value
+
+
 def main():
+    loss = _option('--loss', 'lsq')
+    multiplier = float(_option('--poisson-multiplier', 2e6))
     n = int(sys.argv[1]) if len(sys.argv) > 1 else 128
     n_theta = int(sys.argv[2]) if len(sys.argv) > 2 else 60
     n_epochs = int(sys.argv[3]) if len(sys.argv) > 3 else 100
@@ -73,9 +91,9 @@ def main():
     fp = 'inf' if fp == 'inf' else float(fp)
     mb = int(sys.argv[6]) if len(sys.argv) > 6 else 10
     propagator = sys.argv[7] if len(sys.argv) > 7 else 'fft'
-    r = run(n, n_theta, n_epochs, lr, fp, mb=mb, propagator=propagator)
-    print('reconstruct_fullfield (propagator {}) {}^3, {} angles, {} epochs in minibatches of {}: {:.1f} s ({:.1f} ms per Adam step, entry point to files)'.format(
-        propagator, n, n_theta, n_epochs, mb, r['seconds'], 1e3 * r['seconds'] / (n_epochs * max(1, n_theta // mb))))
+    r = run(n, n_theta, n_epochs, lr, fp, mb=mb, propagator=propagator, loss=loss, multiplier=multiplier)
+    print('reconstruct_fullfield (propagator {}, loss {}) {}^3, {} angles, {} epochs in minibatches of {}: {:.1f} s ({:.1f} ms per Adam step, entry point to files)'.format(
+        propagator, loss, n, n_theta, n_epochs, mb, r['seconds'], 1e3 * r['seconds'] / (n_epochs * max(1, n_theta // mb))))
     print('delta: correlation with the phantom {:.4f} (central half {:.4f}); relative L2 error {:.3f}; peak {:.3e} vs {:.3e}'.format(
         r['delta_corr'], r['delta_corr_inner'], r['delta_rel_l2'], r['delta_peak'], r['phantom_peak']))
     print('beta : correlation {:.4f}'.format(r['beta_corr']))

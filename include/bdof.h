@@ -260,6 +260,19 @@ int bdof_probe_grad(bdof_ctx* ctx, void* out, int accumulate);
  * only; mode 0 (default): plain amplitudes.  bdof_loss_grad_conv honours it too: there the constant part of the detector
  * wave is A = s a_S with s the corner-pixel renormalisation of propagation.py:79,109-110, formed in float64 per call. */
 int bdof_set_meas_mode(bdof_ctx* ctx, int mode);
+/* The data term bdof_loss_grad and bdof_loss_grad_tf_f64 minimise (sticky on the ctx; default BDOF_LOSS_LSQ, whose results this
+ * call does not move by a bit).  BDOF_LOSS_POISSON: the photon-counting likelihood of amplitudes m measured with `multiplier`
+ * photons per unit intensity (mu; tensorflow_recon/ptychography.py's poisson_multiplier), as its deviance, per pixel with a = |d|
+ *     L = mean( mu (a^2 - m^2 - 2 m^2 ln(a / m)) )          (m = 0: mu a^2)
+ * — the reference's commented mu a^2 - mu m^2 ln(mu a^2) minus its value at a perfect fit: the same gradient, zero at a = m and
+ * ~ 2 mu (a - m)^2 near it, where the raw form carries a constant of order mu ln mu per pixel that hides the loss's relative
+ * change.  Seed G(d) = (2 mu / n) (1 - m^2 / a^2) d: the least-squares seed times mu (a + m) / a, so the residual a - m is
+ * formed exactly as for BDOF_LOSS_LSQ (residual splitting, float64 carrier field, float64 DC bin).  Pixels with a = 0 contribute
+ * nothing; there is no epsilon.  bdof_get_loss returns L.  multiplier must be > 0 (it is ignored by BDOF_LOSS_LSQ).
+ * With BDOF_LOSS_POISSON set, bdof_loss_grad_conv, bdof_loss_grad_conv_f64 and bdof_field_loss_seed fail (bdof_last_error). */
+#define BDOF_LOSS_LSQ 0
+#define BDOF_LOSS_POISSON 1
+int bdof_set_loss(bdof_ctx* ctx, int kind, double multiplier);
 
 /* Real-space truncated-kernel propagator: replaces multislice_propagate_cnn (cnn_propagator/propagation.py:18-133), the
  * forward model cnn_propagator/fullfield.py:87,102 and ptychography.py:74 literally call.  The cropped kernel is separable,
