@@ -936,21 +936,20 @@ static int check_ready(bdof_ctx* c, int B) {
 }
 
 // ---- the tile family: tiles cut out of a field / written back into it, and the adjoints ---------------------------------------
-// Every entry point fills its argument struct and hands it to launch_tiles: shapes, taper (gathers) and halo (scatters) are
+// Every entry point fills the TileArgs of its precision pairing and hands it to launch_tiles: shapes, taper (gathers) and halo (scatters) are
 // checked — the one an entry point does not take is 0 and passes — then one launch of 256-thread workgroups on the ctx stream,
 // over the tiles' rows (TILE_GRID: y blocks of 256, up to 64 workgroups along x, one z per tile) or over the field's rows
 // (FIELD_GRID: the adjoints that sum the tiles into the field).
 enum TileGrid { TILE_GRID, FIELD_GRID };
-template <class Args, class... Rest>
-static int launch_tiles(bdof_ctx* c, const void* field, const void* tiles, TileGrid shape, void (*kernel)(Args, Rest...), const Args& a,
-                        Rest... rest) {
+template <class Args>
+static int launch_tiles(bdof_ctx* c, const void* field, const void* tiles, TileGrid shape, void (*kernel)(Args), const Args& a) {
     if (!c || !field || !tiles || !a.x0 || !a.y0) return BDOF_ERR_ARG;
     if (a.B < 1 || a.FX < 1 || a.FY < 1 || a.TX < 1 || a.TY < 1) return fail(c, BDOF_ERR_ARG, "bad tile / field shape");
     int r;
     if ((r = check_taper(c, a.TX, a.TY, a.taper)) || (r = check_halo(c, a.TX, a.TY, a.hx, a.hy))) return r;
     HIPC(c, hipSetDevice(c->device));
     const dim3 grid = shape == TILE_GRID ? dim3((a.TY + 255) / 256, std::min(a.TX, 64), a.B) : dim3(std::min(a.FX, c->ncu * 8));
-    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, c->stream, a, rest...);
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, c->stream, a);
     return launched(c);
 }
 
@@ -1623,24 +1622,24 @@ int bdof_field_loss_seed(bdof_ctx* c, void* field, const float* meas, int FX, in
 
 int bdof_tiles_gather(bdof_ctx* c, const void* field, int FX, int FY, void* tiles, int B, int TX, int TY, const int* x0, const int* y0,
                       int taper) {
-    return launch_tiles(c, field, tiles, TILE_GRID, k_tiles_gather, TileArgs{(cf*)field, (cf*)tiles, x0, y0, B, FX, FY, TX, TY, 0, 0, taper}, 0);
+    return launch_tiles(c, field, tiles, TILE_GRID, k_tiles_cut<cf, cf>, TileArgs<cf, cf>{(cf*)field, (cf*)tiles, nullptr, x0, y0, B, FX, FY, TX, TY, 0, 0, taper, 0});
 }
 
 int bdof_tiles_scatter(bdof_ctx* c, const void* tiles, void* field, int FX, int FY, int B, int TX, int TY, const int* x0, const int* y0,
                        int halo_x, int halo_y) {
-    return launch_tiles(c, field, tiles, TILE_GRID, k_tiles_scatter, TileArgs{(cf*)field, (cf*)tiles, x0, y0, B, FX, FY, TX, TY, halo_x, halo_y, 0});
+    return launch_tiles(c, field, tiles, TILE_GRID, k_tiles_put<cf, cf>, TileArgs<cf, cf>{(cf*)field, (cf*)tiles, nullptr, x0, y0, B, FX, FY, TX, TY, halo_x, halo_y, 0, 0});
 }
 
 // adjoint of bdof_tiles_scatter: tiles = the field on every tile's core, zero elsewhere
 int bdof_tiles_scatter_adjoint(bdof_ctx* c, const void* field, int FX, int FY, void* tiles, int B, int TX, int TY, const int* x0, const int* y0,
                                int halo_x, int halo_y) {
-    return launch_tiles(c, field, tiles, TILE_GRID, k_tiles_gather, TileArgs{(cf*)field, (cf*)tiles, x0, y0, B, FX, FY, TX, TY, halo_x, halo_y, 0}, 1);
+    return launch_tiles(c, field, tiles, TILE_GRID, k_tiles_put_adjoint<cf, cf>, TileArgs<cf, cf>{(cf*)field, (cf*)tiles, nullptr, x0, y0, B, FX, FY, TX, TY, halo_x, halo_y, 0, 0});
 }
 
 // adjoint of bdof_tiles_gather: field = sum of the tiles' pixels, weighted with the taper, at the positions they were cut from
 int bdof_tiles_gather_adjoint(bdof_ctx* c, const void* tiles, void* field, int FX, int FY, int B, int TX, int TY, const int* x0, const int* y0,
                               int taper) {
-    return launch_tiles(c, field, tiles, FIELD_GRID, k_tiles_gather_adjoint, TileArgs{(cf*)field, (cf*)tiles, x0, y0, B, FX, FY, TX, TY, 0, 0, taper});
+    return launch_tiles(c, field, tiles, FIELD_GRID, k_tiles_cut_adjoint<cf, cf>, TileArgs<cf, cf>{(cf*)field, (cf*)tiles, nullptr, x0, y0, B, FX, FY, TX, TY, 0, 0, taper, 0});
 }
 
 // object gradient of a slice range of tiles, added into the volume gradient rows (see k_tiles_grad_add)
@@ -1767,42 +1766,43 @@ int bdof_c_convert(bdof_ctx* c, void* dst, const void* src, size_t n, int to_dou
 
 int bdof_tiles_gather_f64(bdof_ctx* c, const void* field, int FX, int FY, void* tiles, int B, int TX, int TY, const int* x0, const int* y0,
                           int taper) {
-    return launch_tiles(c, field, tiles, TILE_GRID, k_tiles_gather64, Tile64Args{(double2*)field, (double2*)tiles, x0, y0, B, FX, FY, TX, TY, 0, 0, taper});
+    return launch_tiles(c, field, tiles, TILE_GRID, k_tiles_cut<double2, double2>,
+                        TileArgs<double2, double2>{(double2*)field, (double2*)tiles, nullptr, x0, y0, B, FX, FY, TX, TY, 0, 0, taper, 0});
 }
 
 int bdof_tiles_scatter_f64(bdof_ctx* c, const void* tiles, void* field, int FX, int FY, int B, int TX, int TY, const int* x0, const int* y0,
                            int halo_x, int halo_y) {
-    return launch_tiles(c, field, tiles, TILE_GRID, k_tiles_scatter64,
-                        Tile64Args{(double2*)field, (double2*)tiles, x0, y0, B, FX, FY, TX, TY, halo_x, halo_y, 0});
+    return launch_tiles(c, field, tiles, TILE_GRID, k_tiles_put<double2, double2>,
+                        TileArgs<double2, double2>{(double2*)field, (double2*)tiles, nullptr, x0, y0, B, FX, FY, TX, TY, halo_x, halo_y, 0, 0});
 }
 
 // complex64 tiles cut out of a complex128 field (tapered, periodic) / written back into it:
 // field[core] = (accumulate ? field[core] : 0) + tiles_a - tiles_b (tiles_b nullable), the sum formed in float64
 int bdof_tiles_gather_mixed(bdof_ctx* c, const void* field64, int FX, int FY, void* tiles, int B, int TX, int TY, const int* x0, const int* y0,
                             int taper) {
-    return launch_tiles(c, field64, tiles, TILE_GRID, k_tiles_gather_mixed,
-                        TileMixArgs{(double2*)field64, nullptr, nullptr, (cf*)tiles, x0, y0, B, FX, FY, TX, TY, 0, 0, taper, 0}, 0);
+    return launch_tiles(c, field64, tiles, TILE_GRID, k_tiles_cut<double2, cf>,
+                        TileArgs<double2, cf>{(double2*)field64, (cf*)tiles, nullptr, x0, y0, B, FX, FY, TX, TY, 0, 0, taper, 0});
 }
 
 // adjoint of bdof_tiles_scatter_diff64 w.r.t. tiles_a: complex64 tiles = the complex128 field on every tile's core, zero elsewhere
 int bdof_tiles_scatter_adjoint_mixed(bdof_ctx* c, const void* field64, int FX, int FY, void* tiles, int B, int TX, int TY, const int* x0,
                                      const int* y0, int halo_x, int halo_y) {
-    return launch_tiles(c, field64, tiles, TILE_GRID, k_tiles_gather_mixed,
-                        TileMixArgs{(double2*)field64, nullptr, nullptr, (cf*)tiles, x0, y0, B, FX, FY, TX, TY, halo_x, halo_y, 0, 0}, 1);
+    return launch_tiles(c, field64, tiles, TILE_GRID, k_tiles_put_adjoint<double2, cf>,
+                        TileArgs<double2, cf>{(double2*)field64, (cf*)tiles, nullptr, x0, y0, B, FX, FY, TX, TY, halo_x, halo_y, 0, 0});
 }
 
 // adjoint of bdof_tiles_gather_mixed, on a difference of tiles: field64 (+)= sum of the tapered (tiles_a - tiles_b) pixels at the
 // positions they were cut from (periodically); tiles_b nullable
 int bdof_tiles_gather_adjoint_diff64(bdof_ctx* c, const void* tiles_a, const void* tiles_b, void* field64, int FX, int FY, int B, int TX, int TY,
                                      const int* x0, const int* y0, int taper, int accumulate) {
-    return launch_tiles(c, field64, tiles_a, FIELD_GRID, k_tiles_gather_adjoint_diff64,
-                        TileMixArgs{(double2*)field64, (const cf*)tiles_a, (const cf*)tiles_b, nullptr, x0, y0, B, FX, FY, TX, TY, 0, 0, taper, accumulate});
+    return launch_tiles(c, field64, tiles_a, FIELD_GRID, k_tiles_cut_adjoint<double2, cf>,
+                        TileArgs<double2, cf>{(double2*)field64, (cf*)tiles_a, (const cf*)tiles_b, x0, y0, B, FX, FY, TX, TY, 0, 0, taper, accumulate});
 }
 
 int bdof_tiles_scatter_diff64(bdof_ctx* c, const void* tiles_a, const void* tiles_b, void* field64, int FX, int FY, int B, int TX, int TY,
                               const int* x0, const int* y0, int halo_x, int halo_y, int accumulate) {
-    return launch_tiles(c, field64, tiles_a, TILE_GRID, k_tiles_scatter_diff64,
-                        TileMixArgs{(double2*)field64, (const cf*)tiles_a, (const cf*)tiles_b, nullptr, x0, y0, B, FX, FY, TX, TY, halo_x, halo_y, 0, accumulate});
+    return launch_tiles(c, field64, tiles_a, TILE_GRID, k_tiles_put<double2, cf>,
+                        TileArgs<double2, cf>{(double2*)field64, (cf*)tiles_a, (const cf*)tiles_b, x0, y0, B, FX, FY, TX, TY, halo_x, halo_y, 0, accumulate});
 }
 
 // bdof_forward_range in float64 on caller-owned complex128 fields [B][NX][NY], in place: slices z0 .. z0+nz-1 of the bound object

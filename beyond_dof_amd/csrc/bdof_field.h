@@ -6,7 +6,8 @@
 //  * the float64 tile path (TiledPropagator(precision='float64')): the reference's arithmetic is float64
 //    (cnn_propagator/np_funcs.py:20-42, quirk Q2) and a 1024-slice stack run through float32 transforms carries 1.5e-5 of
 //    rounding; here modulation, transforms (rocFFT double) and the transfer-function product are float64, unfused;
-//  * tile cut-out / write-back and axpy in float64.
+//  * the tile family: tiles cut out of a field / written back into it, and the adjoints, for every pairing of field and tile
+//    precision; axpy and conversions in float64.
 #pragma once
 #include "bdof_generic.h"
 
@@ -39,110 +40,111 @@ __global__ __launch_bounds__(256) void k_f_to_float(const double2* __restrict__ 
         dst[i] = make_float2((float)src[i].x, (float)src[i].y);
 }
 
-// ---- tiles in float64: the same cut-out / write-back as k_tiles_gather (mode 0) / k_tiles_scatter (bdof_kernels.h) ----------
-struct Tile64Args {
-    double2* field;     // [FX][FY]
-    double2* tiles;     // [B][TX][TY]
+// ---------------------------------------------------------------------------------------------
+// The tile family.  Tiled ("pfft") propagation: a field too large for one fused plan is cut into overlapping tiles that run
+// through the per-slice kernels as a batch; every few slices the tiles' cores are stitched back and the halos refilled
+// (README.md:1-11 of the reference: "tiling-based Fresnel multislice propagation"; its source is on a branch that is not in the
+// checkout).  Field [FX][FY] complex; tile b covers field rows x0[b] .. x0[b] + TX - 1 and columns y0[b] .. + TY - 1,
+// PERIODICALLY (the whole-field FFT propagator it stands in for is periodic).  Four linear operators, each written once for a
+// field of complex type F and tiles of complex type T (cf / cf, double2 / double2, and float32 tiles of a float64 field: the
+// field of the float32 tiled path with the long-range correction stays in float64 — its bulk is carried by the whole-field
+// free-space step in double, the tiles add the object's part); the arithmetic is done in the FIELD's real type:
+//   cut    tiles_a = periodic window of the field x taper                                          k_tiles_cut
+//   cut^H  field (+)= sum of the tapered (tiles_a - tiles_b) pixels at the places they were cut from  k_tiles_cut_adjoint
+//   put    field[core] = (field[core] +) tiles_a (- tiles_b); pixels beyond the field's edge are dropped  k_tiles_put
+//   put^H  tiles_a = the field on the tile's core, zero on the halo and beyond the field's edge    k_tiles_put_adjoint
+// ---------------------------------------------------------------------------------------------
+template <class F, class T>
+struct TileArgs {
+    F* field;           // [FX][FY]
+    T* tiles_a;         // [B][TX][TY]: written by cut / put^H, read by cut^H / put
+    const T* tiles_b;   // nullable: cut^H / put take tiles_a - tiles_b
     const int* x0;
     const int* y0;
-    int B, FX, FY, TX, TY, hx, hy, taper;
+    int B, FX, FY, TX, TY, hx, hy;      // put, put^H: only the core [hx, TX - hx) x [hy, TY - hy) of a tile is written back
+    int taper;                          // cut, cut^H: the outermost `taper` pixels of a tile are ramped to zero (raised cosine)
+    int accumulate;                     // cut^H / put: add to the field instead of overwriting it
 };
-__device__ __forceinline__ double taper_weight64(int i, int n, int taper) {
+template <class C> using real_of = decltype(C::x);
+template <class C, class R>
+__device__ __forceinline__ C make_c(R x, R y) { C c; c.x = (real_of<C>)x; c.y = (real_of<C>)y; return c; }
+
+// A tile is propagated with its own periodic FFT: left and right edge meet, and a jump there diffracts into the tile with a
+// 1/distance tail (Fresnel edge fringes) — 7e-4 of error at a 16-pixel halo.  Ramping the outer part of the halo to zero
+// removes the jump; what is left travels inwards at the geometric rate only (3e-5 at the same halo, 3e-6 at 32 pixels).
+template <class R> __device__ __forceinline__ R taper_weight(int i, int n, int taper);
+template <> __device__ __forceinline__ float taper_weight<float>(int i, int n, int taper) {
+    const int e = min(i, n - 1 - i);
+    return e < taper ? 0.5f - 0.5f * __cosf(3.14159265358979f * ((float)e + 0.5f) / (float)taper) : 1.f;
+}
+template <> __device__ __forceinline__ double taper_weight<double>(int i, int n, int taper) {
     const int e = min(i, n - 1 - i);
     return e < taper ? 0.5 - 0.5 * cos(3.14159265358979323846 * ((double)e + 0.5) / (double)taper) : 1.0;
 }
-__global__ __launch_bounds__(256) void k_tiles_gather64(Tile64Args a) {
-    const int b = blockIdx.z;
-    const int ox = a.x0[b], oy = a.y0[b];
-    for (int x = blockIdx.y; x < a.TX; x += gridDim.y) {
-        double2* dst = a.tiles + ((size_t)b * a.TX + x) * a.TY;
-        const double2* src = a.field + (size_t)wrap_idx(ox + x, a.FX) * a.FY;
-        const double wx = taper_weight64(x, a.TX, a.taper);
-        for (int y = blockIdx.x * blockDim.x + threadIdx.x; y < a.TY; y += gridDim.x * blockDim.x) {
-            const double w = wx * taper_weight64(y, a.TY, a.taper);
-            const double2 v = src[wrap_idx(oy + y, a.FY)];
-            dst[y] = make_double2(v.x * w, v.y * w);
-        }
-    }
-}
-__global__ __launch_bounds__(256) void k_tiles_scatter64(Tile64Args a) {
-    const int b = blockIdx.z;
-    const int ox = a.x0[b], oy = a.y0[b];
-    for (int x = a.hx + blockIdx.y; x < a.TX - a.hx; x += gridDim.y) {
-        const int xg = ox + x;
-        if (xg < 0 || xg >= a.FX) continue;
-        double2* dst = a.field + (size_t)xg * a.FY;
-        const double2* src = a.tiles + ((size_t)b * a.TX + x) * a.TY;
-        for (int y = a.hy + blockIdx.x * blockDim.x + threadIdx.x; y < a.TY - a.hy; y += gridDim.x * blockDim.x) {
-            const int yg = oy + y;
-            if (yg >= 0 && yg < a.FY) dst[yg] = src[y];
-        }
-    }
-}
+__device__ __forceinline__ int wrap_idx(int i, int n) { i %= n; return i < 0 ? i + n : i; }
 
-// float32 tiles of a float64 field (the field of the float32 tiled path with the long-range correction stays in float64: its
-// bulk is carried by the whole-field free-space step in double, the tiles add the object's part)
-struct TileMixArgs {
-    double2* field;       // [FX][FY]
-    const cf* ta;         // [B][TX][TY]
-    const cf* tb;         // nullable
-    cf* tiles;            // gather target
-    const int* x0;
-    const int* y0;
-    int B, FX, FY, TX, TY, hx, hy, taper, accumulate;
-};
-// mode 0: tile = field (periodic) x taper window.  mode 1: tile = the field on the tile's CORE, zero on the halo and beyond the
-// field's edge — the adjoint of the write-back (k_tiles_gather's two modes, from a float64 field)
-__global__ __launch_bounds__(256) void k_tiles_gather_mixed(TileMixArgs a, int mode) {
+template <class F, class T>
+__global__ __launch_bounds__(256) void k_tiles_cut(TileArgs<F, T> a) {
+    using R = real_of<F>;
     const int b = blockIdx.z;
     const int ox = a.x0[b], oy = a.y0[b];
     for (int x = blockIdx.y; x < a.TX; x += gridDim.y) {
-        cf* dst = a.tiles + ((size_t)b * a.TX + x) * a.TY;
-        if (mode == 1) {
-            const int xg = ox + x;
-            const bool xin = x >= a.hx && x < a.TX - a.hx && xg >= 0 && xg < a.FX;
-            const double2* srow = a.field + (size_t)(xin ? xg : 0) * a.FY;
-            for (int y = blockIdx.x * blockDim.x + threadIdx.x; y < a.TY; y += gridDim.x * blockDim.x) {
-                const int yg = oy + y;
-                const bool in = xin && y >= a.hy && y < a.TY - a.hy && yg >= 0 && yg < a.FY;
-                const double2 v = srow[in ? yg : 0];
-                dst[y] = in ? make_float2((float)v.x, (float)v.y) : make_float2(0.f, 0.f);
-            }
-            continue;
-        }
-        const double2* src = a.field + (size_t)wrap_idx(ox + x, a.FX) * a.FY;
-        const double wx = taper_weight64(x, a.TX, a.taper);
+        T* dst = a.tiles_a + ((size_t)b * a.TX + x) * a.TY;
+        const F* src = a.field + (size_t)wrap_idx(ox + x, a.FX) * a.FY;
+        const R wx = taper_weight<R>(x, a.TX, a.taper);
         for (int y = blockIdx.x * blockDim.x + threadIdx.x; y < a.TY; y += gridDim.x * blockDim.x) {
-            const double w = wx * taper_weight64(y, a.TY, a.taper);
-            const double2 v = src[wrap_idx(oy + y, a.FY)];
-            dst[y] = make_float2((float)(v.x * w), (float)(v.y * w));
+            const R w = wx * taper_weight<R>(y, a.TY, a.taper);
+            const F v = src[wrap_idx(oy + y, a.FY)];
+            dst[y] = make_c<T>(v.x * w, v.y * w);
         }
     }
 }
-// field[core] = (accumulate ? field[core] : 0) + ta - tb   on the cores of the tiles, in float64
-__global__ __launch_bounds__(256) void k_tiles_scatter_diff64(TileMixArgs a) {
+// the adjoint of k_tiles_put (which writes cores, without wrapping)
+template <class F, class T>
+__global__ __launch_bounds__(256) void k_tiles_put_adjoint(TileArgs<F, T> a) {
+    const int b = blockIdx.z;
+    const int ox = a.x0[b], oy = a.y0[b];
+    for (int x = blockIdx.y; x < a.TX; x += gridDim.y) {
+        T* dst = a.tiles_a + ((size_t)b * a.TX + x) * a.TY;
+        const int xg = ox + x;
+        const bool xin = x >= a.hx && x < a.TX - a.hx && xg >= 0 && xg < a.FX;
+        const F* src = a.field + (size_t)(xin ? xg : 0) * a.FY;
+        for (int y = blockIdx.x * blockDim.x + threadIdx.x; y < a.TY; y += gridDim.x * blockDim.x) {
+            const int yg = oy + y;
+            const bool in = xin && y >= a.hy && y < a.TY - a.hy && yg >= 0 && yg < a.FY;
+            const F v = src[in ? yg : 0];
+            dst[y] = in ? make_c<T>(v.x, v.y) : make_c<T>(0.f, 0.f);
+        }
+    }
+}
+// cores back into the field; a core pixel beyond the field's edge is dropped (cores tile the field from 0, the last ones
+// overhang), so every field pixel has exactly one writer
+template <class F, class T>
+__global__ __launch_bounds__(256) void k_tiles_put(TileArgs<F, T> a) {
+    using R = real_of<F>;
     const int b = blockIdx.z;
     const int ox = a.x0[b], oy = a.y0[b];
     for (int x = a.hx + blockIdx.y; x < a.TX - a.hx; x += gridDim.y) {
         const int xg = ox + x;
         if (xg < 0 || xg >= a.FX) continue;
-        double2* dst = a.field + (size_t)xg * a.FY;
+        F* dst = a.field + (size_t)xg * a.FY;
         const size_t row = ((size_t)b * a.TX + x) * a.TY;
         for (int y = a.hy + blockIdx.x * blockDim.x + threadIdx.x; y < a.TY - a.hy; y += gridDim.x * blockDim.x) {
             const int yg = oy + y;
             if (yg < 0 || yg >= a.FY) continue;
-            const cf va = a.ta[row + y];
-            double dx = (double)va.x, dy = (double)va.y;
-            if (a.tb) { const cf vb = a.tb[row + y]; dx -= (double)vb.x; dy -= (double)vb.y; }
-            if (a.accumulate) { const double2 o = dst[yg]; dx += o.x; dy += o.y; }
-            dst[yg] = make_double2(dx, dy);
+            const T va = a.tiles_a[row + y];
+            R dx = (R)va.x, dy = (R)va.y;
+            if (a.tiles_b) { const T vb = a.tiles_b[row + y]; dx -= (R)vb.x; dy -= (R)vb.y; }
+            if (a.accumulate) { const F o = dst[yg]; dx += o.x; dy += o.y; }
+            dst[yg] = make_c<F>(dx, dy);
         }
     }
 }
-
-// Adjoint of the tapered periodic cut-out, accumulated into a float64 field: field[xg][yg] += sum over the tiles b and tile
-// pixels (x, y) cut from (xg, yg) — periodically — of w(x) w(y) (ta - tb)[b][x][y].  One workgroup per field row, fixed order.
-__global__ __launch_bounds__(256) void k_tiles_gather_adjoint_diff64(TileMixArgs a) {
+// One workgroup per field row; it first lists the (tile, x) pairs that map onto its row, then every thread sums its columns
+// over the list in a fixed order (deterministic, no atomics).
+template <class F, class T>
+__global__ __launch_bounds__(256) void k_tiles_cut_adjoint(TileArgs<F, T> a) {
+    using R = real_of<F>;
     __shared__ int lb[BDOF_TILE_MAXLIST], lx[BDOF_TILE_MAXLIST];
     __shared__ int nlist;
     for (int xg = blockIdx.x; xg < a.FX; xg += gridDim.x) {
@@ -150,6 +152,7 @@ __global__ __launch_bounds__(256) void k_tiles_gather_adjoint_diff64(TileMixArgs
         if (threadIdx.x == 0) {
             int n = 0;
             for (int b = 0; b < a.B; ++b) {
+                // tile rows x with (x0[b] + x) mod FX == xg
                 int x = wrap_idx(xg - a.x0[b], a.FX);
                 for (; x < a.TX && n < BDOF_TILE_MAXLIST; x += a.FX) { lb[n] = b; lx[n] = x; ++n; }
             }
@@ -158,23 +161,23 @@ __global__ __launch_bounds__(256) void k_tiles_gather_adjoint_diff64(TileMixArgs
         __syncthreads();
         const int n = nlist;
         for (int yg = threadIdx.x; yg < a.FY; yg += blockDim.x) {
-            double sx = 0.0, sy = 0.0;
+            R sx = 0, sy = 0;
             for (int e = 0; e < n; ++e) {
                 const int b = lb[e], x = lx[e];
-                const double wx = taper_weight64(x, a.TX, a.taper);
+                const R wx = taper_weight<R>(x, a.TX, a.taper);
                 for (int y = wrap_idx(yg - a.y0[b], a.FY); y < a.TY; y += a.FY) {
-                    const double w = wx * taper_weight64(y, a.TY, a.taper);
+                    const R w = wx * taper_weight<R>(y, a.TY, a.taper);
                     const size_t o = ((size_t)b * a.TX + x) * a.TY + y;
-                    const cf va = a.ta[o];
-                    double dx = (double)va.x, dy = (double)va.y;
-                    if (a.tb) { const cf vb = a.tb[o]; dx -= (double)vb.x; dy -= (double)vb.y; }
-                    sx += w * dx;
-                    sy += w * dy;
+                    const T va = a.tiles_a[o];
+                    R dx = (R)va.x, dy = (R)va.y;
+                    if (a.tiles_b) { const T vb = a.tiles_b[o]; dx -= (R)vb.x; dy -= (R)vb.y; }
+                    sx = fma(w, dx, sx);
+                    sy = fma(w, dy, sy);
                 }
             }
-            double2* dst = a.field + (size_t)xg * a.FY + yg;
+            F* dst = a.field + (size_t)xg * a.FY + yg;
             if (a.accumulate) { sx += dst->x; sy += dst->y; }
-            *dst = make_double2(sx, sy);
+            *dst = make_c<F>(sx, sy);
         }
     }
 }

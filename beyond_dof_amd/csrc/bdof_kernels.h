@@ -990,105 +990,9 @@ __global__ __launch_bounds__(256) void k_adam(AdamArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// Tiled ("pfft") propagation: a field too large for one fused plan is cut into overlapping tiles that run through the
-// per-slice kernels as a batch; every few slices the tiles' cores are stitched back and the halos refilled (README.md:1-11
-// of the reference: "tiling-based Fresnel multislice propagation"; its source is on a branch that is not in the checkout).
-// Field [FX][FY] complex; tile b covers field rows x0[b] .. x0[b] + TX - 1 and columns y0[b] .. + TY - 1, PERIODICALLY
-// (the whole-field FFT propagator it stands in for is periodic).
+// Tiled ("pfft") propagation: the tile family (cut, put and their adjoints) is in bdof_field.h; here, the object gradient.
 // ---------------------------------------------------------------------------------------------
-struct TileArgs {
-    cf* field;
-    cf* tiles;          // [B][TX][TY]
-    const int* x0;
-    const int* y0;
-    int B, FX, FY, TX, TY, hx, hy;      // scatter: only the core [hx, TX - hx) x [hy, TY - hy) of a tile is written back
-    int taper;                          // gather: the outermost `taper` pixels of a tile are ramped to zero (raised cosine)
-};
-// A tile is propagated with its own periodic FFT: left and right edge meet, and a jump there diffracts into the tile with a
-// 1/distance tail (Fresnel edge fringes) — 7e-4 of error at a 16-pixel halo.  Ramping the outer part of the halo to zero
-// removes the jump; what is left travels inwards at the geometric rate only (3e-5 at the same halo, 3e-6 at 32 pixels).
-__device__ __forceinline__ float taper_weight(int i, int n, int taper) {
-    const int e = min(i, n - 1 - i);
-    return e < taper ? 0.5f - 0.5f * __cosf(3.14159265358979f * ((float)e + 0.5f) / (float)taper) : 1.f;
-}
-__device__ __forceinline__ int wrap_idx(int i, int n) { i %= n; return i < 0 ? i + n : i; }
-
-// mode 0: tile = field (periodic) x taper window.  mode 1: tile = field on the tile's CORE, zero on the halo and beyond the
-// field's edge — the adjoint of k_tiles_scatter (which writes cores, without wrapping).
-__global__ __launch_bounds__(256) void k_tiles_gather(TileArgs a, int mode) {
-    const int b = blockIdx.z;
-    const int ox = a.x0[b], oy = a.y0[b];
-    for (int x = blockIdx.y; x < a.TX; x += gridDim.y) {
-        cf* dst = a.tiles + ((size_t)b * a.TX + x) * a.TY;
-        if (mode == 1) {
-            const int xg = ox + x;
-            const bool xin = x >= a.hx && x < a.TX - a.hx && xg >= 0 && xg < a.FX;
-            const cf* src = a.field + (size_t)(xin ? xg : 0) * a.FY;
-            for (int y = blockIdx.x * blockDim.x + threadIdx.x; y < a.TY; y += gridDim.x * blockDim.x) {
-                const int yg = oy + y;
-                const bool in = xin && y >= a.hy && y < a.TY - a.hy && yg >= 0 && yg < a.FY;
-                dst[y] = in ? src[yg] : make_float2(0.f, 0.f);
-            }
-            continue;
-        }
-        const cf* src = a.field + (size_t)wrap_idx(ox + x, a.FX) * a.FY;
-        const float wx = taper_weight(x, a.TX, a.taper);
-        for (int y = blockIdx.x * blockDim.x + threadIdx.x; y < a.TY; y += gridDim.x * blockDim.x)
-            dst[y] = cscale(src[wrap_idx(oy + y, a.FY)], wx * taper_weight(y, a.TY, a.taper));
-    }
-}
-// cores back into the field; a core pixel beyond the field's edge is dropped (cores tile the field from 0, the last ones
-// overhang), so every field pixel has exactly one writer
-__global__ __launch_bounds__(256) void k_tiles_scatter(TileArgs a) {
-    const int b = blockIdx.z;
-    const int ox = a.x0[b], oy = a.y0[b];
-    for (int x = a.hx + blockIdx.y; x < a.TX - a.hx; x += gridDim.y) {
-        const int xg = ox + x;
-        if (xg < 0 || xg >= a.FX) continue;
-        cf* dst = a.field + (size_t)xg * a.FY;
-        const cf* src = a.tiles + ((size_t)b * a.TX + x) * a.TY;
-        for (int y = a.hy + blockIdx.x * blockDim.x + threadIdx.x; y < a.TY - a.hy; y += gridDim.x * blockDim.x) {
-            const int yg = oy + y;
-            if (yg >= 0 && yg < a.FY) dst[yg] = src[y];
-        }
-    }
-}
-// Adjoint of the tapered periodic gather: field[xg][yg] = sum over the tiles b and tile pixels (x, y) that were cut from
-// (xg, yg) — periodically — of w(x) w(y) tiles[b][x][y].  One workgroup per field row; it first lists the (tile, x) pairs
-// that map onto its row, then every thread sums its columns over the list in a fixed order (deterministic, no atomics).
-#define BDOF_TILE_MAXLIST 1024
-__global__ __launch_bounds__(256) void k_tiles_gather_adjoint(TileArgs a) {
-    __shared__ int lb[BDOF_TILE_MAXLIST], lx[BDOF_TILE_MAXLIST];
-    __shared__ int nlist;
-    for (int xg = blockIdx.x; xg < a.FX; xg += gridDim.x) {
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            int n = 0;
-            for (int b = 0; b < a.B; ++b) {
-                // tile rows x with (x0[b] + x) mod FX == xg
-                int x = wrap_idx(xg - a.x0[b], a.FX);
-                for (; x < a.TX && n < BDOF_TILE_MAXLIST; x += a.FX) { lb[n] = b; lx[n] = x; ++n; }
-            }
-            nlist = n;
-        }
-        __syncthreads();
-        const int n = nlist;
-        for (int yg = threadIdx.x; yg < a.FY; yg += blockDim.x) {
-            float sx = 0.f, sy = 0.f;
-            for (int e = 0; e < n; ++e) {
-                const int b = lb[e], x = lx[e];
-                const float wx = taper_weight(x, a.TX, a.taper);
-                for (int y = wrap_idx(yg - a.y0[b], a.FY); y < a.TY; y += a.FY) {
-                    const float w = wx * taper_weight(y, a.TY, a.taper);
-                    const cf v = a.tiles[((size_t)b * a.TX + x) * a.TY + y];
-                    sx = fmaf(w, v.x, sx);
-                    sy = fmaf(w, v.y, sy);
-                }
-            }
-            a.field[(size_t)xg * a.FY + yg] = make_float2(sx, sy);
-        }
-    }
-}
+#define BDOF_TILE_MAXLIST 1024      // (tile, row) pairs a workgroup lists for its field row / volume column (also bdof_field.h)
 // Object gradient of a slice range of the tiled propagation: the window-frame gradient rows grot[b][z - z0][x][y] of every
 // tile are added into the volume gradient rows gvol[tab[z][xg]][yg], xg = x0[b] + x, yg = y0[b] + y (the object is not
 // periodic: tile pixels beyond the volume saw vacuum and contribute nothing).  One workgroup per volume column xg; a thread

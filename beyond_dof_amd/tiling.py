@@ -42,6 +42,20 @@ from .comm import PseudoComm
 from .engine import MultisliceEngine
 
 
+C64, C128 = np.dtype(np.complex64), np.dtype(np.complex128)
+
+
+class TileSelection(object):
+    """A selection of tiles on the device: the count n and one [6][n] int32 table — angle, x origin, y origin of the tiles' object
+    windows (a, xo, yo) and of windows beyond the volume, which see vacuum whatever the object (va, vx, vy: the fused T_free)."""
+
+    def __init__(self, ctx, x0, y0):
+        self.n, x0, y0 = len(x0), np.asarray(x0, dtype=np.int32), np.asarray(y0, dtype=np.int32)
+        self._buf = DeviceBuffer.from_host(ctx, np.stack([0 * x0, x0, y0, 0 * x0, 0 * x0 + (1 << 28), y0])) if self.n else None
+
+    a, xo, yo, va, vx, vy = (property(lambda self, r=r: self._buf.ptr + 4 * r * self.n) for r in range(6))
+
+
 class TiledPropagator(object):
     def __init__(self, field_shape, n_slice, energy_ev, psize_cm, tile=512, halo='auto', slices_per_exchange=None, safety=0.5,
                  taper=None, variant='numpy_skip_last', device=0, pi=util.PI, with_grad=False, comm=None, long_range='auto',
@@ -121,17 +135,15 @@ class TiledPropagator(object):
         self.comm.attach(self.ctx)
         self.eng.set_physics(energy_ev, psize_cm, None, variant=variant, pi=pi, field_shape=(self.fy, self.fx))
         self.eng.set_probe_none()
-        self.idx = DeviceBuffer.from_host(self.ctx, np.stack([np.zeros(self.n_tiles, dtype=np.int32), self.x0, self.y0]))
         self.skip_vacuum = bool(skip_vacuum)
         self._carrier_arg = carrier
         self._active = None               # per stitch range: indices of the tiles whose window holds any object (set_object*)
-        self._active_bufs = {}
+        self._active_bufs = {}           # selections of active tiles, by the active set
         self._ends = self._grot = self._gvol = None      # the gradient's per-range buffers (_range_buffers)
         self._obj_shape = None            # row layout of the object the engine holds (set_object*)
         n = self.n_tiles * self.tile * self.tile
         self.dbl = precision == 'float64'
-        ctype = np.complex128 if self.dbl else np.complex64
-        cb = 16 if self.dbl else 8
+        ctype, cb = (C128, 16) if self.dbl else (C64, 8)
         self.tiles_in = DeviceBuffer(self.ctx, n * cb, ctype, (self.n_tiles, self.tile, self.tile))
         self.tiles_out = None if self.dbl else DeviceBuffer(self.ctx, n * 8, np.complex64, (self.n_tiles, self.tile, self.tile))
         self.field = DeviceBuffer(self.ctx, self.fx * self.fy * cb, ctype, (self.fx, self.fy))
@@ -144,10 +156,14 @@ class TiledPropagator(object):
             self.tiles_free = DeviceBuffer(self.ctx, n * cb, ctype, (self.n_tiles, self.tile, self.tile))
             self.whole64 = DeviceBuffer(self.ctx, self.fx * self.fy * 16, np.complex128, (self.fx, self.fy))
             self.field64 = self.field if self.dbl else DeviceBuffer(self.ctx, self.fx * self.fy * 16, np.complex128, (self.fx, self.fy))
-            # tiles that see vacuum whatever the object: window origins beyond the volume (the fused free-space step)
-            self.vac = DeviceBuffer.from_host(self.ctx, np.stack([np.zeros(self.n_tiles, dtype=np.int32),
-                                                                  np.full(self.n_tiles, 1 << 28, dtype=np.int32), self.y0]))
             self._conj_tables = {}
+        self.all = TileSelection(self.ctx, self.x0, self.y0)            # every tile of this rank
+        lib, c64, mixed, c128 = self.lib, (C64, C64), (C128, C64), (C128, C128)
+        self._tile_ops = {      # operator -> (field dtype, tiles dtype) -> entry point
+            'cut': {c64: lib.bdof_tiles_gather, c128: lib.bdof_tiles_gather_f64, mixed: lib.bdof_tiles_gather_mixed},
+            'cut_adjoint': {c64: lib.bdof_tiles_gather_adjoint, mixed: lib.bdof_tiles_gather_adjoint_diff64},
+            'put': {c64: lib.bdof_tiles_scatter, c128: lib.bdof_tiles_scatter_f64, mixed: lib.bdof_tiles_scatter_diff64},
+            'put_adjoint': {c64: lib.bdof_tiles_scatter_adjoint, mixed: lib.bdof_tiles_scatter_adjoint_mixed}}
         self.carrier = (self.long_range and not self.dbl and not self.with_grad) if self._carrier_arg == 'auto' else bool(self._carrier_arg)
         if self.carrier and not (self.long_range and not self.dbl and not self.with_grad):
             raise ValueError('carrier fields per tile run in the forward model with the long-range correction and float32 tiles')
@@ -209,51 +225,71 @@ class TiledPropagator(object):
             self._active = [self._tiles_with_object(np.any(d[:, :, z0:z0 + nz] != 0, axis=2) | np.any(b[:, :, z0:z0 + nz] != 0, axis=2))
                             for z0, nz in self.segments()]
 
-    def _scattered_range(self, f, w, B, a, xo, yo, z0, nz, prop_last, before_scatter=None):
-        """stitch(T psi - T_free psi) of one range added into w (prop_last) / the modulation's scattered part added into f (a last
+    def _tile_op(self, op, field, tiles, sel, edge, minus=None, accumulate=False):
+        """One launch of `op`'s entry point for the two buffers' dtypes; edge: the taper (cut, cut^H) or the halos (put, put^H)."""
+        fn = self._tile_ops[op].get((field.dtype, tiles.dtype))
+        diff = op in ('cut_adjoint', 'put') and (field.dtype, tiles.dtype) == (C128, C64)      # (*_diff64: tiles_a - tiles_b, accumulate)
+        if fn is None or ((minus is not None or accumulate) and not diff):
+            raise ValueError('no {} between a {} field and {} tiles{}'.format(op, field.dtype, tiles.dtype, ' with minus= / accumulate=' if fn else ''))
+        batch = (sel.n, self.tile, self.tile, sel.xo, sel.yo) + edge + ((int(accumulate),) if diff else ())
+        into = (tiles.ptr,) + ((getattr(minus, 'ptr', None),) if diff else ()) + (field.ptr, self.fx, self.fy)
+        self.ctx.check(fn(self.h, *((field.ptr, self.fx, self.fy, tiles.ptr) if op in ('cut', 'put_adjoint') else into) + batch))
+
+    def _cut(self, field, tiles, sel):
+        """tiles = periodic windows of the field x taper"""
+        self._tile_op('cut', field, tiles, sel, (self.taper,))
+
+    def _cut_adjoint(self, tiles, field, sel, minus=None, accumulate=False):
+        """field (+)= sum of the tapered (tiles - minus) pixels at the places they were cut from"""
+        self._tile_op('cut_adjoint', field, tiles, sel, (self.taper,), minus, accumulate)
+
+    def _put(self, tiles, field, sel, minus=None, accumulate=False):
+        """field[cores] = (field[cores] +) tiles (- minus); core pixels beyond the field's edge are dropped"""
+        self._tile_op('put', field, tiles, sel, (self.halo, self.halo), minus, accumulate)
+
+    def _put_adjoint(self, field, tiles, sel):
+        """tiles = the field on their cores, zero elsewhere"""
+        self._tile_op('put_adjoint', field, tiles, sel, (self.halo, self.halo))
+
+    def _sweep(self, sel, z0, nz, prop_last, out=None):
+        """T: the tiles in tiles_in through slices z0 .. z0 + nz - 1, into `out` (float64 tiles: in place); returns the result's buffer."""
+        head = (self.h, sel.n, sel.a, sel.xo, sel.yo, z0, nz, self.tiles_in.ptr)
+        if self.dbl:
+            self.ctx.check(self.lib.bdof_forward_range_f64(*head, self.h64.ptr, self.k64, prop_last))
+            return self.tiles_in
+        out = out or self.tiles_out
+        self.ctx.check(self.lib.bdof_forward_range(*head, out.ptr, prop_last))
+        return out
+
+    def _scattered_range(self, f, w, sel, z0, nz, prop_last, before_put=lambda: None):
+        """Stitch(T psi - T_free psi) of one range added into w (prop_last) / the modulation's scattered part added into f (a last
         single slice without a step), the tiles riding on their own free-space propagation in double."""
-        lib, h, T = self.lib, self.h, self.tile
-        px = B * T * T
+        lib, h, T, B, px = self.lib, self.h, self.tile, sel.n, sel.n * self.tile * self.tile
         if self._car64 is None or self._car64.nbytes < px * 16:
             self._car64 = DeviceBuffer(self.ctx, px * 16, np.complex128, (B, T, T))
         if self._car_stack is None or self._car_stack.nbytes < px * 8 * nz:
             self._car_stack = DeviceBuffer(self.ctx, px * 8 * max(nz, self.seg), np.complex64, (max(nz, self.seg), B, T, T))
-        car, stack = self._car64, self._car_stack
-        self.ctx.check(lib.bdof_tiles_gather_f64(h, f.ptr, self.fx, self.fy, car.ptr, B, T, T, xo, yo, self.taper))
+        self._cut(f, self._car64, sel)
         # p_z = F^-1(H^z F p_0), z = 0 .. nz - 1, in double: one forward transform, one batched inverse one (bdof_range_carrier_build)
-        self.ctx.check(lib.bdof_range_carrier_build(h, car.ptr, stack.ptr, B, T, T, self._h64_tile.ptr, nz))
+        self.ctx.check(lib.bdof_range_carrier_build(h, self._car64.ptr, self._car_stack.ptr, B, T, T, self._h64_tile.ptr, nz))
         self.ctx.check(lib.bdof_memset(h, self.tiles_in.ptr, 0, px * 8))              # the scattered part entering the range: none
-        self.ctx.check(lib.bdof_set_range_carrier(h, stack.ptr, B, z0, nz))
+        self.ctx.check(lib.bdof_set_range_carrier(h, self._car_stack.ptr, B, z0, nz))
         try:
-            self.ctx.check(lib.bdof_forward_range(h, B, a, xo, yo, z0, nz, self.tiles_in.ptr, self.tiles_out.ptr, prop_last))
+            self._sweep(sel, z0, nz, prop_last)
         finally:
             lib.bdof_set_range_carrier(h, None, 0, 0, 0)
-        dst = w if prop_last or nz > 1 else f
-        if before_scatter is not None:
-            before_scatter()
-        self.ctx.check(lib.bdof_tiles_scatter_diff64(h, self.tiles_out.ptr, None, dst.ptr, self.fx, self.fy, B, T, T, xo, yo,
-                                                     self.halo, self.halo, 1))
+        before_put()
+        self._put(self.tiles_out, w if prop_last or nz > 1 else f, sel, accumulate=True)
 
     def _range_tiles(self, i_range):
-        """(B, a, xo, yo, va, vx, vy) of stitch range i_range: every tile, or only those that see any object (skip_vacuum)."""
-        p, v, B = self.idx.ptr, self.vac.ptr, self.n_tiles
-        every = (B, p, p + 4 * B, p + 8 * B, v, v + 4 * B, v + 8 * B)
-        if not self.skip_vacuum or self._active is None or self.dbl or self.with_grad:
-            return every
-        act = self._active[i_range]
-        if len(act) == B:
-            return every
-        if len(act) == 0:
-            return (0,) * 7
+        """The tiles of stitch range i_range: every tile, or only those that see any object (skip_vacuum)."""
+        act = None if not self.skip_vacuum or self._active is None or self.dbl or self.with_grad else self._active[i_range]
+        if act is None or len(act) == self.n_tiles:
+            return self.all
         key = act.tobytes()
         if key not in self._active_bufs:
-            n = len(act)
-            zeros = np.zeros(n, dtype=np.int32)
-            self._active_bufs[key] = (DeviceBuffer.from_host(self.ctx, np.stack([zeros, self.x0[act], self.y0[act]])),
-                                      DeviceBuffer.from_host(self.ctx, np.stack([zeros, np.full(n, 1 << 28, dtype=np.int32), self.y0[act]])))
-        ib, vb = self._active_bufs[key]
-        n = len(act)
-        return (n, ib.ptr, ib.ptr + 4 * n, ib.ptr + 8 * n, vb.ptr, vb.ptr + 4 * n, vb.ptr + 8 * n)
+            self._active_bufs[key] = TileSelection(self.ctx, self.x0[act], self.y0[act])
+        return self._active_bufs[key]
 
     # ---- forward -------------------------------------------------------------------------------
     @staticmethod
@@ -283,27 +319,16 @@ class TiledPropagator(object):
     def forward_device(self):
         """Propagate the device field in place through all slices (np_funcs.py:36-43: no step after the last slice unless
         variant == 'tf_all')."""
-        lib, h, p = self.lib, self.h, self.idx.ptr
-        a, xo, yo = p, p + 4 * self.n_tiles, p + 8 * self.n_tiles
-        B, T = self.n_tiles, self.tile
+        lib, h, T = self.lib, self.h, self.tile
         if not self.long_range:
-            gather = lib.bdof_tiles_gather_f64 if self.dbl else lib.bdof_tiles_gather
-            for z0, nz in self.segments():
-                prop_last = int(z0 + nz < self.n_slice or self.variant == 'tf_all')
-                self.ctx.check(gather(h, self.field.ptr, self.fx, self.fy, self.tiles_in.ptr, B, T, T, xo, yo, self.taper))
-                if self.dbl:
-                    self.ctx.check(lib.bdof_forward_range_f64(h, B, a, xo, yo, z0, nz, self.tiles_in.ptr, self.h64.ptr, self.k64, prop_last))
-                    self._stitch(self.tiles_in)
-                else:
-                    self.ctx.check(lib.bdof_forward_range(h, B, a, xo, yo, z0, nz, self.tiles_in.ptr, self.tiles_out.ptr, prop_last))
-                    self._stitch(self.tiles_out)
+            for z0, nz in self.segments():                   # psi_out = Stitch(T Cut psi_in)
+                self._cut(self.field, self.tiles_in, self.all)
+                self._stitch(self._sweep(self.all, z0, nz, int(z0 + nz < self.n_slice or self.variant == 'tf_all')))
             return
-        # Long-range correction: psi_out = P_field^n psi_in + stitch(T psi_in - T_free psi_in) per range — the field's own
+        # Long-range correction: psi_out = P_field^n psi_in + Stitch(T Cut psi_in - T_free Cut psi_in) per range — the field's own
         # free-space step over the range (one transform pair of the whole field, in double) carries the wave, the tiles add what
         # the object does to it; T_free is the tiles' own free-space step, so what the tiles miss of the field's propagator
         # (its long-range tails) drops out to first order in the object's phase over one range.
-        v = self.vac.ptr
-        va, vx, vy = v, v + 4 * B, v + 8 * B
         npx = self.fx * self.fy
         if not self.dbl:
             self.ctx.check(lib.bdof_c_convert(h, self.field64.ptr, self.field.ptr, npx, 1))
@@ -311,58 +336,45 @@ class TiledPropagator(object):
         for i_range, (z0, nz) in enumerate(self.segments()):
             prop_last = int(z0 + nz < self.n_slice or self.variant == 'tf_all')
             nprop = nz - 1 + prop_last                       # transfer-function steps of this range
-            B, a, xo, yo, va, vx, vy = self._range_tiles(i_range)      # (tiles whose window is vacuum over the range add nothing)
-            if B == 0:
+            sel = self._range_tiles(i_range)                 # (tiles whose window is vacuum over the range add nothing)
+            t_tab, f_tab = self._tables(nprop) if nprop else (None, None)
+            if sel.n == 0:
                 if nprop:
-                    _, f_tab = self._tables(nprop)
                     self.ctx.check(lib.bdof_fields_free_step(h, f.ptr, 1, self.fx, self.fy, f_tab.ptr, 0, 1))
                 continue
             # per-tile carriers cost one double-precision transform pair per slice and tile: 'auto' takes them where few tiles see
             # the object (a padded field), and sweeps the full wave in float32 where most do (4 x the time for 2.4 x the accuracy)
-            if self.carrier and (self._carrier_arg is True or 4 * B <= self.n_tiles):
+            if self.carrier and (self._carrier_arg is True or 4 * sel.n <= self.n_tiles):
                 if nprop == 0:                               # a last single slice without a step: f += (c - 1) psi on the cores
-                    self._scattered_range(f, f, B, a, xo, yo, z0, nz, 0)
+                    self._scattered_range(f, f, sel, z0, nz, 0)
                     continue
                 # the field's own step (one double transform pair of the whole field) on the auxiliary stream, beside the few
                 # tiles' carrier steps and sweeps: the one saturates HBM, the others are small launches
-                _, f_tab = self._tables(nprop)
                 self.ctx.check(lib.bdof_fields_free_step_aux(h, w.ptr, f.ptr, 1, self.fx, self.fy, f_tab.ptr, 0, 1))
                 try:
-                    self._scattered_range(f, w, B, a, xo, yo, z0, nz, prop_last, before_scatter=lambda: self.ctx.check(lib.bdof_aux_join(h)))
+                    self._scattered_range(f, w, sel, z0, nz, prop_last, before_put=lambda: self.ctx.check(lib.bdof_aux_join(h)))
                 finally:
                     lib.bdof_aux_join(h)                     # (a no-op after the join above; an error on the way must not leave it open)
                 f, w = w, f
                 continue
-            if self.dbl:
-                self.ctx.check(lib.bdof_tiles_gather_f64(h, f.ptr, self.fx, self.fy, self.tiles_in.ptr, B, T, T, xo, yo, self.taper))
-            else:
-                self.ctx.check(lib.bdof_tiles_gather_mixed(h, f.ptr, self.fx, self.fy, self.tiles_in.ptr, B, T, T, xo, yo, self.taper))
+            self._cut(f, self.tiles_in, sel)
             if nprop == 0:                                   # a last single slice without a step: nothing to correct
-                if self.dbl:
-                    self.ctx.check(lib.bdof_forward_range_f64(h, B, a, xo, yo, z0, nz, self.tiles_in.ptr, self.h64.ptr, self.k64, 0))
-                    self.ctx.check(lib.bdof_tiles_scatter_f64(h, self.tiles_in.ptr, f.ptr, self.fx, self.fy, B, T, T, xo, yo, self.halo, self.halo))
-                else:
-                    self.ctx.check(lib.bdof_forward_range(h, B, a, xo, yo, z0, nz, self.tiles_in.ptr, self.tiles_out.ptr, 0))
-                    self.ctx.check(lib.bdof_tiles_scatter_diff64(h, self.tiles_out.ptr, None, f.ptr, self.fx, self.fy, B, T, T, xo, yo,
-                                                                 self.halo, self.halo, 0))
+                self._put(self._sweep(sel, z0, nz, 0), f, sel)
                 continue
-            t_tab, f_tab = self._tables(nprop)
             self.ctx.check(lib.bdof_memcpy_d2d(h, w.ptr, f.ptr, npx * 16))
             self.ctx.check(lib.bdof_fields_free_step(h, w.ptr, 1, self.fx, self.fy, f_tab.ptr, 0, 1))
             if self.dbl:
                 self.ctx.check(lib.bdof_memcpy_d2d(h, self.tiles_free.ptr, self.tiles_in.ptr, self.tiles_in.nbytes))
-                self.ctx.check(lib.bdof_fields_free_step(h, self.tiles_free.ptr, B, T, T, t_tab.ptr, 0, 1))
-                self.ctx.check(lib.bdof_forward_range_f64(h, B, a, xo, yo, z0, nz, self.tiles_in.ptr, self.h64.ptr, self.k64, prop_last))
-                self.ctx.check(lib.bdof_caxpy(h, self.tiles_in.ptr, self.tiles_free.ptr, -1.0, B * T * T, 1))
-                self.ctx.check(lib.bdof_tiles_scatter_f64(h, self.tiles_in.ptr, f.ptr, self.fx, self.fy, B, T, T, xo, yo, self.halo, self.halo))
+                self.ctx.check(lib.bdof_fields_free_step(h, self.tiles_free.ptr, sel.n, T, T, t_tab.ptr, 0, 1))
+                self._sweep(sel, z0, nz, prop_last)
+                self.ctx.check(lib.bdof_caxpy(h, self.tiles_in.ptr, self.tiles_free.ptr, -1.0, sel.n * T * T, 1))
+                self._put(self.tiles_in, f, sel)
                 self.ctx.check(lib.bdof_caxpy(h, w.ptr, f.ptr, 1.0, npx, 1))        # (f holds the difference on every core = everywhere)
             else:
                 # T_free through the SAME fused kernels (one vacuum slice stepped with H^n): both terms of the difference carry
                 # the same dithered constants, and no rocFFT float32 drift enters
-                self.ctx.check(lib.bdof_forward_range_h(h, B, va, vx, vy, z0, 1, self.tiles_in.ptr, self.tiles_free.ptr, 1, t_tab.ptr))
-                self.ctx.check(lib.bdof_forward_range(h, B, a, xo, yo, z0, nz, self.tiles_in.ptr, self.tiles_out.ptr, prop_last))
-                self.ctx.check(lib.bdof_tiles_scatter_diff64(h, self.tiles_out.ptr, self.tiles_free.ptr, w.ptr, self.fx, self.fy, B, T, T, xo, yo,
-                                                             self.halo, self.halo, 1))
+                self.ctx.check(lib.bdof_forward_range_h(h, sel.n, sel.va, sel.vx, sel.vy, z0, 1, self.tiles_in.ptr, self.tiles_free.ptr, 1, t_tab.ptr))
+                self._put(self._sweep(sel, z0, nz, prop_last), w, sel, minus=self.tiles_free, accumulate=True)
             f, w = w, f
         if f is not self.field64:                            # an odd number of swaps: the result sits in the other buffer
             self.ctx.check(lib.bdof_memcpy_d2d(h, self.field64.ptr, f.ptr, npx * 16))
@@ -375,12 +387,9 @@ class TiledPropagator(object):
 
     def _stitch(self, tiles):
         """Cores of this rank's tiles -> field; with several ranks the other ranks' cores arrive by summation."""
-        p = self.idx.ptr
         if self.comm.size > 1:
             self.ctx.check(self.lib.bdof_memset(self.h, self.field.ptr, 0, self.field.nbytes))
-        scatter = self.lib.bdof_tiles_scatter_f64 if self.dbl else self.lib.bdof_tiles_scatter
-        self.ctx.check(scatter(self.h, tiles.ptr, self.field.ptr, self.fx, self.fy, self.n_tiles, self.tile, self.tile,
-                               p + 4 * self.n_tiles, p + 8 * self.n_tiles, self.halo, self.halo))
+        self._put(tiles, self.field, self.all)
         self._sum_over_ranks(self.field)
 
     def forward(self, probe_real, probe_imag):
@@ -400,23 +409,20 @@ class TiledPropagator(object):
             raise RuntimeError('TiledPropagator(with_grad=True) needed')
         if self.long_range:
             return self._loss_and_grad_long_range(meas_dev)
-        lib, h, p = self.lib, self.h, self.idx.ptr
-        a, xo, yo = p, p + 4 * self.n_tiles, p + 8 * self.n_tiles
-        T, B = self.tile, self.n_tiles
+        lib, h, sel, T, B = self.lib, self.h, self.all, self.tile, self.n_tiles
         segs = self.segments()
         self._range_buffers(segs)
         for (z0, nz), end in zip(segs, self._ends):
-            self.ctx.check(lib.bdof_tiles_gather(h, self.field.ptr, self.fx, self.fy, self.tiles_in.ptr, B, T, T, xo, yo, self.taper))
-            self.ctx.check(lib.bdof_forward_range(h, B, a, xo, yo, z0, nz, self.tiles_in.ptr, end.ptr, 1))
-            self._stitch(end)
+            self._cut(self.field, self.tiles_in, sel)
+            self._stitch(self._sweep(sel, z0, nz, 1, end))
         self.ctx.check(lib.bdof_field_loss_seed(h, self.field.ptr, _lib._ptr(meas_dev), self.fx, self.fy))
         gvol = self._gvol
         self.ctx.check(lib.bdof_memset(h, gvol.ptr, 0, gvol.nbytes))
         for (z0, nz), end in reversed(list(zip(segs, self._ends))):
-            self.ctx.check(lib.bdof_tiles_scatter_adjoint(h, self.field.ptr, self.fx, self.fy, self.tiles_in.ptr, B, T, T, xo, yo, self.halo, self.halo))
-            self.ctx.check(lib.bdof_adjoint_range(h, B, a, xo, yo, z0, nz, end.ptr, self.tiles_in.ptr, self.tiles_out.ptr, self._grot.ptr))
-            self.ctx.check(lib.bdof_tiles_grad_add(h, self._grot.ptr, gvol.ptr, B, T, T, xo, yo, z0, nz))
-            self.ctx.check(lib.bdof_tiles_gather_adjoint(h, self.tiles_out.ptr, self.field.ptr, self.fx, self.fy, B, T, T, xo, yo, self.taper))
+            self._put_adjoint(self.field, self.tiles_in, sel)
+            self.ctx.check(lib.bdof_adjoint_range(h, B, sel.a, sel.xo, sel.yo, z0, nz, end.ptr, self.tiles_in.ptr, self.tiles_out.ptr, self._grot.ptr))
+            self.ctx.check(lib.bdof_tiles_grad_add(h, self._grot.ptr, gvol.ptr, B, T, T, sel.xo, sel.yo, z0, nz))
+            self._cut_adjoint(self.tiles_out, self.field, sel)
             self._sum_over_ranks(self.field)
         self._sum_over_ranks(gvol)
         return self.eng.get_loss(), gvol
@@ -443,24 +449,18 @@ class TiledPropagator(object):
             G_in = W^H G_out + Cut^H ( T^H - F^H ) Stitch^H G_out ,
         T^H by bdof_adjoint_range (which also leaves the object-gradient rows), F^H the fused free-space step with conj(H^n),
         W^H bdof_fields_free_step(conj_h = 1); the field-level adjoint stays in complex128 like the field."""
-        lib, h, p = self.lib, self.h, self.idx.ptr
-        a, xo, yo = p, p + 4 * self.n_tiles, p + 8 * self.n_tiles
-        v = self.vac.ptr
-        va, vx, vy = v, v + 4 * self.n_tiles, v + 8 * self.n_tiles
-        T, B, npx = self.tile, self.n_tiles, self.fx * self.fy
+        lib, h, sel, T, B, npx = self.lib, self.h, self.all, self.tile, self.n_tiles, self.fx * self.fy
         segs = self.segments()
         self._range_buffers(segs)
         f, w = self.field64, self.whole64
         self.ctx.check(lib.bdof_c_convert(h, f.ptr, self.field.ptr, npx, 1))
         for (z0, nz), end in zip(segs, self._ends):
             t_tab, f_tab = self._tables(nz)                   # tf_all: a step after every slice
-            self.ctx.check(lib.bdof_tiles_gather_mixed(h, f.ptr, self.fx, self.fy, self.tiles_in.ptr, B, T, T, xo, yo, self.taper))
+            self._cut(f, self.tiles_in, sel)
             self.ctx.check(lib.bdof_memcpy_d2d(h, w.ptr, f.ptr, npx * 16))
             self.ctx.check(lib.bdof_fields_free_step(h, w.ptr, 1, self.fx, self.fy, f_tab.ptr, 0, 1))
-            self.ctx.check(lib.bdof_forward_range_h(h, B, va, vx, vy, z0, 1, self.tiles_in.ptr, self.tiles_free.ptr, 1, t_tab.ptr))
-            self.ctx.check(lib.bdof_forward_range(h, B, a, xo, yo, z0, nz, self.tiles_in.ptr, end.ptr, 1))
-            self.ctx.check(lib.bdof_tiles_scatter_diff64(h, end.ptr, self.tiles_free.ptr, w.ptr, self.fx, self.fy, B, T, T, xo, yo,
-                                                         self.halo, self.halo, 1))
+            self.ctx.check(lib.bdof_forward_range_h(h, B, sel.va, sel.vx, sel.vy, z0, 1, self.tiles_in.ptr, self.tiles_free.ptr, 1, t_tab.ptr))
+            self._put(self._sweep(sel, z0, nz, 1, end), w, sel, minus=self.tiles_free, accumulate=True)
             f, w = w, f
         self.ctx.check(lib.bdof_c_convert(h, self.field.ptr, f.ptr, npx, 0))
         self.ctx.check(lib.bdof_field_loss_seed(h, self.field.ptr, _lib._ptr(meas_dev), self.fx, self.fy))
@@ -469,17 +469,16 @@ class TiledPropagator(object):
         gvol = self._gvol
         self.ctx.check(lib.bdof_memset(h, gvol.ptr, 0, gvol.nbytes))
         for (z0, nz), end in reversed(list(zip(segs, self._ends))):
-            _, f_tab = self._tables(nz)
-            self.ctx.check(lib.bdof_tiles_scatter_adjoint_mixed(h, g.ptr, self.fx, self.fy, self.tiles_in.ptr, B, T, T, xo, yo, self.halo, self.halo))
+            f_tab, c_tab = self._tables(nz)[1], self._conj_table(nz)
+            self._put_adjoint(g, self.tiles_in, sel)
             # F^H Stitch^H G: vacuum, conj(H^n)
-            self.ctx.check(lib.bdof_forward_range_h(h, B, va, vx, vy, z0, 1, self.tiles_in.ptr, self.tiles_free.ptr, 1, self._conj_table(nz).ptr))
+            self.ctx.check(lib.bdof_forward_range_h(h, B, sel.va, sel.vx, sel.vy, z0, 1, self.tiles_in.ptr, self.tiles_free.ptr, 1, c_tab.ptr))
             # T^H Stitch^H G, and the object gradient of the range
-            self.ctx.check(lib.bdof_adjoint_range(h, B, a, xo, yo, z0, nz, end.ptr, self.tiles_in.ptr, self.tiles_out.ptr, self._grot.ptr))
-            self.ctx.check(lib.bdof_tiles_grad_add(h, self._grot.ptr, gvol.ptr, B, T, T, xo, yo, z0, nz))
+            self.ctx.check(lib.bdof_adjoint_range(h, B, sel.a, sel.xo, sel.yo, z0, nz, end.ptr, self.tiles_in.ptr, self.tiles_out.ptr, self._grot.ptr))
+            self.ctx.check(lib.bdof_tiles_grad_add(h, self._grot.ptr, gvol.ptr, B, T, T, sel.xo, sel.yo, z0, nz))
             # W^H G in place, then += Cut^H (T^H - F^H) ...
             self.ctx.check(lib.bdof_fields_free_step(h, g.ptr, 1, self.fx, self.fy, f_tab.ptr, 1, 1))
-            self.ctx.check(lib.bdof_tiles_gather_adjoint_diff64(h, self.tiles_out.ptr, self.tiles_free.ptr, g.ptr, self.fx, self.fy, B, T, T, xo, yo,
-                                                                self.taper, 1))
+            self._cut_adjoint(self.tiles_out, g, sel, minus=self.tiles_free, accumulate=True)
         self.ctx.check(lib.bdof_c_convert(h, self.field.ptr, g.ptr, npx, 0))            # G(probe), as the plain path leaves it
         return self.eng.get_loss(), gvol
 
@@ -517,7 +516,7 @@ class WholeFieldPropagator(object):
         self.h64 = DeviceBuffer.from_host(self.ctx, o.table(o.delta_nm, transpose=True, dtype=np.complex128))      # [kx][ky]
         self.skip_vacuum, self._obj_shape = False, None      # (set_object* are TiledPropagator's: no tiles here to leave out)
         self.field = DeviceBuffer(self.ctx, self.fx * self.fy * 16, np.complex128, (self.fx, self.fy))
-        self.idx = DeviceBuffer.from_host(self.ctx, np.zeros(3, dtype=np.int32))
+        self.all = TileSelection(self.ctx, [0], [0])          # one "tile": the field
 
     set_object_slab = TiledPropagator.set_object_slab
     set_object = TiledPropagator.set_object
@@ -525,8 +524,8 @@ class WholeFieldPropagator(object):
     def forward(self, probe_real, probe_imag):
         probe = (np.asarray(probe_real) + 1j * np.asarray(probe_imag)) * np.ones((self.fy, self.fx))
         self.field.upload(np.ascontiguousarray(probe.T.astype(np.complex64).astype(np.complex128)))
-        p = self.idx.ptr
-        self.ctx.check(self.lib.bdof_forward_range_f64(self.h, 1, p, p + 4, p + 8, 0, self.n_slice, self.field.ptr, self.h64.ptr, self.k64,
-                                                       int(self.variant == 'tf_all')))
+        sel = self.all
+        self.ctx.check(self.lib.bdof_forward_range_f64(self.h, sel.n, sel.a, sel.xo, sel.yo, 0, self.n_slice, self.field.ptr, self.h64.ptr,
+                                                       self.k64, int(self.variant == 'tf_all')))
         self.ctx.sync()
         return np.ascontiguousarray(self.field.download().T)

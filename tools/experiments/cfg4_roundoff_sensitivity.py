@@ -23,7 +23,8 @@ for sets in ([A, A, A], [A2, A2, A2]):
     tp.forward(probe, zero)
     f64 = tp.field64.download().copy()
     tp._active = [np.ascontiguousarray(A)] * 3
-    B, a, xo, yo, va, vx, vy = tp._range_tiles(0)
+    sel = tp._range_tiles(0)
+    B, a, xo, yo, va, vx, vy = sel.n, sel.a, sel.xo, sel.yo, sel.va, sel.vx, sel.vy
     tp.ctx.check(lib.bdof_tiles_gather_mixed(h, tp.field64.ptr, n, n, tp.tiles_in.ptr, B, T, T, xo, yo, tp.taper))
     tin = tp.tiles_in.download()[:B].copy()
     t_tab, _ = tp._tables(16)

@@ -15,8 +15,8 @@ meas = np.ones((n, n), dtype=np.float32)
 for _ in range(2):
     print(tp.loss_and_grad(pr, np.zeros_like(pr), meas)[0])
 import time
-lib, h, p = tp.lib, tp.h, tp.idx.ptr
-a, xo, yo = p, p + 4 * tp.n_tiles, p + 8 * tp.n_tiles
+lib, h = tp.lib, tp.h
+a, xo, yo = tp.all.a, tp.all.xo, tp.all.yo
 T, B = tp.tile, tp.n_tiles
 def timed(name, f):
     tp.ctx.sync(); t0 = time.perf_counter(); f(); tp.ctx.sync(); print('%-28s %8.1f ms' % (name, (time.perf_counter() - t0) * 1e3))
