@@ -249,13 +249,11 @@ static std::complex<double> carrier_end(const bdof_ctx* c) {
     if (c->det_mode == BDOF_DET_NEAR) a *= c->hdet00;
     return a;
 }
-static cf carrier_det(const bdof_ctx* c) {
+static std::complex<double> carrier_det(const bdof_ctx* c) {
     std::complex<double> a = carrier_end(c);
     if (c->det_mode == BDOF_DET_FAR) a *= (double)c->NX * (double)c->NY;
-    return make_float2((float)a.real(), (float)a.imag());
+    return a;
 }
-// bdof_set_meas_mode(1): the host subtracted |a_0| from the amplitudes; the detector carrier has modulus |a_0| |cbar|^S
-static float meas_dref(const bdof_ctx* c) { return (float)(std::abs(carrier_end(c)) - std::abs(c->a0)); }
 // the object's mean modulation factor rides on the carrier when the carrier is a scalar of the transfer-function path
 static bool want_cbar(const bdof_ctx* c) { return std::abs(c->a0) > 0.0 && !c->pstack && !c->have_conv; }
 
@@ -268,6 +266,40 @@ static double2 d2(std::complex<double> v) { return make_double2(v.real(), v.imag
 static AdjCarrier adj_carrier_at(const bdof_ctx* c, int steps_back) {
     if (!use_adj_carrier(c)) return AdjCarrier{nullptr, nullptr, make_double2(1.0, 0.0), make_float2(0.f, 0.f)};
     return AdjCarrier{c->gcar + c->sub_b0, c->gt0 + c->sub_b0, d2(std::pow(std::conj((1.0 + c->cbm1) * c->h00), steps_back)), cfl(c->cbm1)};
+}
+
+// ---- the detector plane (DetPlane, bdof_kernels.h) ------------------------------------------------------------------------
+static void set_carrier(DetPlane& d, std::complex<double> a) {
+    d.carrier = cfl(a);
+    d.carrier_dd = d2(a);
+    d.abs_carrier = sqrtf(fmaf(d.carrier.x, d.carrier.x, d.carrier.y * d.carrier.y));      // of the float32 carrier, in float32
+}
+// a plane to write a wave out at: a carrier (scalar, or one of the ctx's fields and then its float64 twin) and nothing to fit
+static DetPlane wave_plane(const bdof_ctx* c, std::complex<double> carrier, const cf* pfield = nullptr) {
+    DetPlane d;
+    set_carrier(d, carrier);
+    d.pfield = pfield;
+    d.pfield64 = !pfield ? nullptr : pfield == c->pdet ? c->pdet64 : pfield == c->pdetT ? c->pdetT64 : nullptr;
+    return d;
+}
+// The detector plane and data term of the transfer-function engines for a batch of B wavefields (the current sub-batch's
+// adjoint carriers); pfield: the carrier field at the detector in the layout of the kernel that gets the plane, or null.
+static DetPlane det_plane(const bdof_ctx* c, int B, const cf* pfield) {
+    DetPlane d = wave_plane(c, carrier_det(c), pfield);
+    d.a_end = d2(carrier_end(c));
+    d.meas_dev = c->meas_dev;
+    if (c->meas_dev) {
+        // bdof_set_meas_mode(1): the host subtracted |a_0| from the amplitudes; the detector carrier has modulus |a_0| |cbar|^S
+        d.meas_ref = std::abs(c->a0);
+        d.dref = (float)(std::abs(carrier_end(c)) - std::abs(c->a0));
+    }
+    d.seed_scale = 2.f / ((float)B * (float)c->NX * (float)c->NY);
+    d.mu = c->loss_mu;
+    // Set whenever the ctx carries an adjoint carrier, whatever the launch does: the kernels write them only where they fit
+    // (a.meas) and reach the DC bin's test (k_row_loss<FAR>; k_g_loss, after its seed64 branch has taken every bin of a float64
+    // adjoint), and nothing reads them unless an adjoint sweep follows.
+    if (use_adj_carrier(c)) { d.gcar = c->gcar + c->sub_b0; d.gt0 = c->gt0 + c->sub_b0; }
+    return d;
 }
 
 static bool supported_n(int n) { return n == 64 || n == 128 || n == 256 || n == 512 || n == 1024; }
@@ -557,18 +589,29 @@ static void launch_row_bwd(bdof_ctx* c, int B, int z, const cf* gin, const cf* t
     }); }));
 }
 
-// Real-space detector on L1 rows.  Returns the grid (= number of partial sums when meas != null).
-// pf64 / pscale: a float64 carrier field of the caller's own and its complex factor (the real-space propagator's planes and
-// renormalisation); by default the ctx's pdet64 goes with pfield == pdet
-static const double2 kOne = {1.0, 0.0};
-static int launch_loss_real(bdof_ctx* c, int B, const cf* in, cf* out_hyb, bool tstore, cf* out_wave, const float* meas,
-                            float in_scale, float out_scale, float seed_scale, cf carrier, const cf* pfield = nullptr,
-                            const float* dref_override = nullptr, const double2* pf64 = nullptr, double2 pscale = kOne) {
+// The detector kernels of the streaming engine; B wavefields of the current sub-batch.  Return the grid (= number of partial
+// sums when meas != null).
+static LossArgs loss_args(bdof_ctx* c, int B, const DetPlane& det, const cf* in, cf* out_hyb, cf* out_wave, const float* meas,
+                          float in_scale, float out_scale) {
+    LossArgs a{};
+    a.in = sub_field(c, in);
+    a.out_hyb = sub_field(c, out_hyb);
+    a.out_wave = sub_field(c, out_wave);
+    a.meas = sub_field(c, meas);
+    a.partial = c->partial + 2 * c->sub_part;
+    a.B = B;
+    a.in_scale = in_scale;
+    a.out_scale = out_scale;
+    a.det = det;
+    return a;
+}
+// Real-space detector on L1 rows.
+static int launch_loss_real(bdof_ctx* c, int B, const DetPlane& det, const cf* in, cf* out_hyb, bool tstore, cf* out_wave, const float* meas,
+                            float in_scale, float out_scale) {
     ProfScope ps(c, BDOF_K_LOSS);
-    LossArgs a{sub_field(c, in), sub_field(c, out_hyb), sub_field(c, out_wave), sub_field(c, meas), c->partial + 2 * c->sub_part, B, c->NX,
-               in_scale, out_scale, seed_scale, carrier, c->twY, pfield, c->meas_dev, nullptr, nullptr, make_double2(0.0, 0.0), make_double2(0.0, 0.0),
-               c->meas_dev ? (dref_override ? *dref_override : meas_dref(c)) : 0.f,
-               pf64 ? pf64 : (pfield && pfield == c->pdet ? c->pdet64 : nullptr), pscale, c->loss_mu};
+    LossArgs a = loss_args(c, B, det, in, out_hyb, out_wave, meas, in_scale, out_scale);
+    a.R = c->NX;
+    a.twiddle = c->twY;
     int grid = 0;
     DISPATCH_N(c->NY, grid = rows_grid<N_>(c, B, c->NX); with_bool(tstore, [&](auto TSTORE) { with_bool(meas && loss_is_poisson(c), [&](auto PSN) {
         hipLaunchKernelGGL((k_row_loss<N_, false, TSTORE, PSN>), dim3(grid), dim3(BDOF_THREADS), 0, c->sub_stream, a);
@@ -577,15 +620,12 @@ static int launch_loss_real(bdof_ctx* c, int B, const cf* in, cf* out_hyb, bool 
 }
 
 // Far-field detector on L2 rows; the seed goes back transposed into L1.
-static int launch_loss_far(bdof_ctx* c, int B, const cf* in, cf* out_hyb, cf* out_wave, const float* meas, float in_scale,
-                           float out_scale, float seed_scale, const cf* pfield = nullptr, const double2* pf64 = nullptr, double2 pscale = kOne) {
+static int launch_loss_far(bdof_ctx* c, int B, const DetPlane& det, const cf* in, cf* out_hyb, cf* out_wave, const float* meas,
+                           float in_scale, float out_scale) {
     ProfScope ps(c, BDOF_K_LOSS);
-    const bool gc = meas && out_hyb && use_adj_carrier(c);
-    LossArgs a{sub_field(c, in), sub_field(c, out_hyb), sub_field(c, out_wave), sub_field(c, meas), c->partial + 2 * c->sub_part, B, c->NY,
-               in_scale, out_scale, seed_scale, carrier_det(c), c->twX, pfield, 0,
-               gc ? c->gcar + c->sub_b0 : nullptr, gc ? c->gt0 + c->sub_b0 : nullptr,
-               d2(carrier_end(c) * ((double)c->NX * (double)c->NY)), d2(carrier_end(c)), 0.f,
-               pf64 ? pf64 : (pfield && pfield == c->pdetT ? c->pdetT64 : nullptr), pscale, c->loss_mu};
+    LossArgs a = loss_args(c, B, det, in, out_hyb, out_wave, meas, in_scale, out_scale);
+    a.R = c->NY;
+    a.twiddle = c->twX;
     int grid = 0;
     DISPATCH_N(c->NX, grid = rows_grid<N_>(c, B, c->NY); with_bool(meas && loss_is_poisson(c), [&](auto PSN) {
         hipLaunchKernelGGL((k_row_loss<N_, true, true, PSN>), dim3(grid), dim3(BDOF_THREADS), 0, c->sub_stream, a);
@@ -776,6 +816,21 @@ static int generic_forward_sweep(bdof_ctx* c, int B, bool tape, rocfft_plan pf, 
     return 0;
 }
 
+// k_g_loss on a [B][NX][NY] field (the ctx's detector kind decides the layout of meas / out_wave)
+static GLossArgs g_loss_args(bdof_ctx* c, int B, const DetPlane& det, cf* field, cf* out_wave, const float* meas) {
+    GLossArgs la{};
+    la.field = field;
+    la.out_wave = out_wave;
+    la.meas = meas;
+    la.partial = c->partial;
+    la.B = B;
+    la.NX = c->NX;
+    la.NY = c->NY;
+    la.far = c->det_mode == BDOF_DET_FAR;
+    la.det = det;
+    return la;
+}
+
 static int generic_forward(bdof_ctx* c, int B, void* out_wave, bool keep_tape) {
     rocfft_plan pf, pi;
     int r = field_plans(c, c->NX, c->NY, B, false, &pf, &pi);
@@ -784,9 +839,7 @@ static int generic_forward(bdof_ctx* c, int B, void* out_wave, bool keep_tape) {
     if ((r = generic_forward_sweep(c, B, keep_tape, pf, pi, &a))) return r;
     if (out_wave) {
         const size_t n = (size_t)B * c->NX * c->NY;
-        GLossArgs la{c->bufA, (cf*)out_wave, nullptr, c->partial, B, c->NX, c->NY, c->det_mode == BDOF_DET_FAR,
-                     make_float2((float)a.real(), (float)a.imag()), 0.f, c->pdet, 0, 0.f, nullptr, nullptr, make_double2(0.0, 0.0), make_double2(0.0, 0.0), nullptr,
-                     nullptr, 0.0, make_double2(0.0, 0.0)};
+        const GLossArgs la = g_loss_args(c, B, wave_plane(c, a, c->pdet), c->bufA, (cf*)out_wave, nullptr);
         hipLaunchKernelGGL(k_g_loss<false>, dim3(g_elem_grid(c, n)), dim3(256), 0, c->stream, la);
     }
     return 0;
@@ -806,11 +859,10 @@ static int generic_loss_grad(bdof_ctx* c, int B, const float* meas, void* out_wa
     if (f64 && !c->have_h64) return fail(c, BDOF_ERR_STATE, "float64 adjoint: bdof_set_physics_f64 has not been called");
     {
         ProfScope ps(c, BDOF_K_LOSS);
-        const bool gc = use_adj_carrier(c) && !f64;
-        GLossArgs la{c->bufA, (cf*)out_wave, meas, c->partial, B, c->NX, c->NY, c->det_mode == BDOF_DET_FAR,
-                     make_float2((float)a.real(), (float)a.imag()), 2.f / ((float)B * (float)c->NX * (float)c->NY), c->pdet, c->meas_dev,
-                     c->meas_dev ? meas_dref(c) : 0.f, gc ? c->gcar : nullptr, gc ? c->gt0 : nullptr, d2(a), d2(carrier_end(c)), c->pdet ? c->pdet64 : nullptr,
-                     f64 ? c->g64 : nullptr, c->meas_dev ? std::abs(c->a0) : 0.0, make_double2(0.0, 0.0), c->loss_mu};
+        DetPlane det = det_plane(c, B, c->pdet);
+        set_carrier(det, a);                       // the carrier as the sweep's own recurrence left it
+        GLossArgs la = g_loss_args(c, B, det, c->bufA, (cf*)out_wave, meas);
+        la.seed64 = f64 ? c->g64 : nullptr;        // float64 adjoint: every bin's seed stays in float64, no adjoint carrier to split off
         with_bool(loss_is_poisson(c), [&](auto PSN) { hipLaunchKernelGGL(k_g_loss<PSN>, dim3(egrid), dim3(256), 0, c->stream, la); });
     }
     hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, c->stream, c->partial, egrid, 1.0 / ((double)B * c->NX * c->NY), c->loss_dev);
@@ -902,10 +954,29 @@ static int resident_run(bdof_ctx* c, int B, const float* meas, void* out_wave, b
     ProfScope ps(c, BDOF_K_ROW_FWD);
     const bool grad = do_grad && meas;
     const bool hdith = c->hs_copies > 0 && c->hsT_d;
-    ResArgs a{c->probe, hdith ? c->hsT_d : c->hsT, c->hdetT, grad ? c->tape : nullptr, (size_t)c->Bmax * c->NX * c->NY, c->grot, c->obj, c->res_carrier,
-              carrier_det(c), c->pstack, c->pdet, meas, (cf*)out_wave, c->partial, c->twR, B, c->S, c->det_mode,
-              c->variant == BDOF_VARIANT_TF_ALL ? 1 : 0, grad ? 1 : 0, c->k, 2.f / ((float)B * (float)c->NX * (float)c->NY), c->meas_dev,
-              hdith ? c->hs_copies : 0, c->meas_dev ? meas_dref(c) : 0.f, grad ? c->gpsi0 : nullptr, c->pdet ? c->pdet64 : nullptr, c->loss_mu};
+    ResArgs a{};
+    a.probe = c->probe;
+    a.hsT = hdith ? c->hsT_d : c->hsT;
+    a.hD = hdith ? c->hs_copies : 0;
+    a.hdetT = c->hdetT;
+    a.tape = grad ? c->tape : nullptr;
+    a.tape_stride = (size_t)c->Bmax * c->NX * c->NY;
+    a.grot = c->grot;
+    a.gpsi0 = grad ? c->gpsi0 : nullptr;
+    a.obj = c->obj;
+    a.carrier = c->res_carrier;
+    a.pstack = c->pstack;
+    a.meas = meas;
+    a.out_wave = (cf*)out_wave;
+    a.partial = c->partial;
+    a.twiddle = c->twR;
+    a.B = B;
+    a.S = c->S;
+    a.det_mode = c->det_mode;
+    a.tf_all = c->variant == BDOF_VARIANT_TF_ALL ? 1 : 0;
+    a.do_grad = grad ? 1 : 0;
+    a.k = c->k;
+    a.det = det_plane(c, B, c->pdet);
     const int grid = B < c->npartial ? B : c->npartial;
     int r = 0, waves = 1;
     switch (c->NX) {
@@ -1373,7 +1444,7 @@ int bdof_set_probe_field(bdof_ctx* c, const double* probe, const double* hT, con
     }
     hipLaunchKernelGGL(k_d_to_f, dim3(grid), dim3(256), 0, c->stream, dp, c->pdet, c->NX, c->NY, 0);
     hipLaunchKernelGGL(k_d_to_f, dim3(grid), dim3(256), 0, c->stream, dp, c->pdetT, c->NX, c->NY, 1);
-    // ... and unrounded: the detector kernels add the scattered wave to these and take |d| - m in float64 (loss_seed_f64)
+    // ... and unrounded: the detector kernels add the scattered wave to these and take |d| - m in float64 (seed_f64)
     hipLaunchKernelGGL(k_d_copy, dim3(grid), dim3(256), 0, c->stream, dp, c->pdet64, c->NX, c->NY, 0);
     hipLaunchKernelGGL(k_d_copy, dim3(grid), dim3(256), 0, c->stream, dp, c->pdetT64, c->NX, c->NY, 1);
     HIPC(c, hipGetLastError());
@@ -1458,11 +1529,11 @@ int bdof_forward(bdof_ctx* c, int B, const int* angle_of_b, const int* xoff, con
     c->last_valid = false;
     if (out_wave) {
         if (c->det_mode == BDOF_DET_FAR)
-            launch_loss_far(c, B, c->bufA, nullptr, (cf*)out_wave, nullptr, 1.f, 1.f, 0.f, c->pdetT);
+            launch_loss_far(c, B, wave_plane(c, carrier_det(c), c->pdetT), c->bufA, nullptr, (cf*)out_wave, nullptr, 1.f, 1.f);
         else if (c->det_mode == BDOF_DET_NONE && !tf_all)
-            launch_loss_real(c, B, c->bufA, nullptr, false, (cf*)out_wave, nullptr, 1.f / c->NY, 1.f, 0.f, carrier_det(c), c->pdet);
+            launch_loss_real(c, B, wave_plane(c, carrier_det(c), c->pdet), c->bufA, nullptr, false, (cf*)out_wave, nullptr, 1.f / c->NY, 1.f);
         else
-            launch_loss_real(c, B, c->bufB, nullptr, false, (cf*)out_wave, nullptr, 1.f, 1.f, 0.f, carrier_det(c), c->pdet);
+            launch_loss_real(c, B, wave_plane(c, carrier_det(c), c->pdet), c->bufB, nullptr, false, (cf*)out_wave, nullptr, 1.f, 1.f);
     }
     if (keep_tape && !tf_all) {
         // probe_array[S-1] = phi_{S-1} (np_funcs.py:41-43): keep R phi_{S-1} in L1 order in bufA
@@ -1511,11 +1582,11 @@ int bdof_forward_range(bdof_ctx* c, int B, const int* angle_of_b, const int* xof
     for (int gi = 0; gi < ng; ++gi) {
         use_group(c, groups[gi]);
         if (prop_last)
-            launch_loss_real(c, groups[gi].B, c->bufB, nullptr, false, (cf*)out_real, nullptr, 1.f, 1.f, 0.f, carrier_at(c, zl + 1),
-                             zl + 1 < c->S ? slice_carrier_field(c, zl + 1) : c->pdet);
+            launch_loss_real(c, groups[gi].B, wave_plane(c, carrier_z(c, zl + 1), zl + 1 < c->S ? slice_carrier_field(c, zl + 1) : c->pdet),
+                             c->bufB, nullptr, false, (cf*)out_real, nullptr, 1.f, 1.f);
         else
-            launch_loss_real(c, groups[gi].B, c->bufA, nullptr, false, (cf*)out_real, nullptr, 1.f / c->NY, 1.f, 0.f, carrier_phi_at(c, zl),
-                             slice_carrier_field(c, zl));
+            launch_loss_real(c, groups[gi].B, wave_plane(c, carrier_z(c, zl) * (1.0 + c->cbm1), slice_carrier_field(c, zl)),
+                             c->bufA, nullptr, false, (cf*)out_real, nullptr, 1.f / c->NY, 1.f);
     }
     if ((r = join_streams(c, ng))) return r;
     c->tape_valid = c->last_valid = false;
@@ -1613,8 +1684,12 @@ int bdof_field_loss_seed(bdof_ctx* c, void* field, const float* meas, int FX, in
     HIPC(c, hipSetDevice(c->device));
     const size_t n = (size_t)FX * FY;
     const int egrid = g_elem_grid(c, n);
-    GLossArgs la{(cf*)field, nullptr, meas, c->partial, 1, FX, FY, 0, make_float2(0.f, 0.f), (float)(2.0 / (double)n), nullptr, 0, 0.f,
-                 nullptr, nullptr, make_double2(0.0, 0.0), make_double2(0.0, 0.0), nullptr, nullptr, 0.0, make_double2(0.0, 0.0)};
+    DetPlane det;                               // no carrier: the field is the whole wave
+    det.seed_scale = (float)(2.0 / (double)n);
+    GLossArgs la = g_loss_args(c, 1, det, (cf*)field, nullptr, meas);
+    la.NX = FX;                                 // a field of its own shape, in real space
+    la.NY = FY;
+    la.far = 0;
     hipLaunchKernelGGL(k_g_loss<false>, dim3(egrid), dim3(256), 0, c->stream, la);
     hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, c->stream, c->partial, egrid, 1.0 / (double)n, c->loss_dev);
     return launched(c);
@@ -2047,13 +2122,13 @@ int bdof_tape_to_real(bdof_ctx* c, int i, int B, void* out) {
     if (i < 0 || i >= c->S) return fail(c, BDOF_ERR_ARG, "slice index outside [0, S)");
     const size_t fld = (size_t)c->Bmax * c->NX * c->NY;
     if (i < c->S - 1) {
-        launch_loss_real(c, B, c->tape + (size_t)i * fld, nullptr, false, (cf*)out, nullptr, 1.f, 1.f, 0.f, carrier_at(c, i + 1),
-                         slice_carrier_field(c, i + 1));
+        launch_loss_real(c, B, wave_plane(c, carrier_z(c, i + 1), slice_carrier_field(c, i + 1)), c->tape + (size_t)i * fld, nullptr, false,
+                         (cf*)out, nullptr, 1.f, 1.f);
     } else {
         if (!c->last_valid)
             return fail(c, BDOF_ERR_STATE, "the last slice's wave is only kept after bdof_forward(keep_tape=1) with the numpy_skip_last variant");
-        launch_loss_real(c, B, c->bufA, nullptr, false, (cf*)out, nullptr, 1.f / c->NY, 1.f, 0.f, carrier_phi_at(c, c->S - 1),
-                         slice_carrier_field(c, c->S - 1));
+        launch_loss_real(c, B, wave_plane(c, carrier_z(c, c->S - 1) * (1.0 + c->cbm1), slice_carrier_field(c, c->S - 1)), c->bufA, nullptr, false,
+                         (cf*)out, nullptr, 1.f / c->NY, 1.f);
     }
     return launched(c);
 }
@@ -2095,20 +2170,20 @@ int bdof_loss_grad(bdof_ctx* c, int B, const int* angle_of_b, const int* xoff, c
     forward_sweep(c, groups, ng, recompute ? TAPE_LAST : TAPE_HISTORY);
     c->tape_valid = false;      // the tape holds an incomplete history (or phi_{S-1} alone), not what bdof_tape_to_real expects
     c->last_valid = false;
-    const float seed_scale = 2.f / ((float)B * (float)c->NX * (float)c->NY);
     int npart = 0;
     // Detector + seed.  Afterwards bufB holds g_hat(phi_{S-1}) (L1 order, normalised hybrid).
     for (int gi = 0; gi < ng; ++gi) {
         const int Bg = groups[gi].B;
         use_group(c, groups[gi], npart);
+        const DetPlane det = det_plane(c, B, c->det_mode == BDOF_DET_FAR ? c->pdetT : c->pdet);      // the whole batch's seed scale
         if (c->det_mode == BDOF_DET_FAR) {
-            npart += launch_loss_far(c, Bg, c->bufA, c->bufB, (cf*)out_wave, meas, 1.f, 1.f, seed_scale, c->pdetT);
+            npart += launch_loss_far(c, Bg, det, c->bufA, c->bufB, (cf*)out_wave, meas, 1.f, 1.f);
         } else if (c->det_mode == BDOF_DET_NONE && !tf_all) {
-            npart += launch_loss_real(c, Bg, c->bufA, c->bufB, false, (cf*)out_wave, meas, 1.f / NYf, 1.f / NYf, seed_scale, carrier_det(c), c->pdet);
+            npart += launch_loss_real(c, Bg, det, c->bufA, c->bufB, false, (cf*)out_wave, meas, 1.f / NYf, 1.f / NYf);
         } else {
             // the detector wave came out of a transfer-function step: seed -> R (transposed) -> adjoint step
             const cf* h = c->det_mode == BDOF_DET_NONE ? c->hs : (tf_all ? c->hcomb : c->hdet);
-            npart += launch_loss_real(c, Bg, c->bufB, c->bufA, true, (cf*)out_wave, meas, 1.f, 1.f, seed_scale, carrier_det(c), c->pdet);
+            npart += launch_loss_real(c, Bg, det, c->bufB, c->bufA, true, (cf*)out_wave, meas, 1.f, 1.f);
             launch_row_prop(c, Bg, c->bufA, c->bufB, h, 1.f, 1, c->S - 1);
         }
     }
@@ -2320,6 +2395,19 @@ static int conv_check(bdof_ctx* c, int B, const int* angle_of_b) {
     return need_angles(c, angle_of_b);
 }
 
+// k_conv_final over B wavefields: q = s (a_S + eps) into `out`.  With a carrier field, or residual splitting (`split`), the
+// constant a_S stays out and only the scattered part s eps is formed.
+static ConvFinalArgs conv_final_args(bdof_ctx* c, int B, const cf* psi_eps, cf* out, bool split) {
+    ConvFinalArgs fa{};
+    fa.psi_eps = psi_eps;
+    fa.out = out;
+    fa.scal = c->conv_scal;
+    fa.carrier_end = (split || c->cstack) ? make_float2(0.f, 0.f) : conv_carrier(c, c->S);
+    fa.plane = (size_t)c->NX * c->NY;
+    fa.n = (size_t)B * fa.plane;
+    return fa;
+}
+
 
 extern "C" {
 
@@ -2354,30 +2442,26 @@ int bdof_forward_conv(bdof_ctx* c, int B, const int* angle_of_b, const int* xoff
     c->tape_valid = c->last_valid = false;
     const size_t n = (size_t)B * c->NX * c->NY;
     const int egrid = (int)std::min<size_t>((n + 255) / 256, (size_t)c->ncu * 16);
-    const cf zero = make_float2(0.f, 0.f);
     const bool cs = c->cstack != nullptr;
-    const size_t plane = (size_t)c->NX * c->NY;
-    const cf* pS = cs ? c->cstack + (size_t)c->S * plane : nullptr;
     if (c->det_mode == BDOF_DET_NONE) {
-        ConvFinalArgs fa{c->bufB, (cf*)out_wave, nullptr, nullptr, nullptr, c->conv_scal, cs ? zero : conv_carrier(c, c->S), n, 0.f, 0, zero, 0.f, 0.f, pS, plane};
+        ConvFinalArgs fa = conv_final_args(c, B, c->bufB, (cf*)out_wave, false);
+        fa.pfield = cs ? c->cstack + (size_t)c->S * fa.plane : nullptr;
         hipLaunchKernelGGL((k_conv_final<0>), dim3(egrid), dim3(256), 0, c->stream, fa);
     } else {
-        // carrier field: only the scattered part s eps_S goes through the float32 detector transforms; the carrier's detector
-        // plane comes in float64, times s (conv_scale64)
-        double2 s64 = kOne;
-        if (cs && (r = conv_scale64(c, &s64))) return r;
-        ConvFinalArgs fa{c->bufB, c->bufA, nullptr, nullptr, nullptr, c->conv_scal, cs ? zero : conv_carrier(c, c->S), n, 0.f, 0, zero, 0.f, 0.f, nullptr, plane};
+        // the detector transforms see no scalar carrier (the renormalised wave carries its own).  Carrier field: only the
+        // scattered part s eps_S goes through them in float32; the carrier's detector plane comes in float64, times s
+        DetPlane det;
+        if (cs && (r = conv_scale64(c, &det.pscale))) return r;
+        det.pfield64 = cs ? c->cdet64 : nullptr;
+        const ConvFinalArgs fa = conv_final_args(c, B, c->bufB, c->bufA, false);
         hipLaunchKernelGGL((k_conv_final<0>), dim3(egrid), dim3(256), 0, c->stream, fa);
         RealToHybArgs ra{c->bufA, c->bufC, B, c->NX, c->twY};
         DISPATCH_N(c->NY, { hipLaunchKernelGGL((k_row_real_to_hyb<N_>), dim3(rows_grid<N_>(c, B, c->NX)), dim3(BDOF_THREADS), 0, c->stream, ra); });
         if (c->det_mode == BDOF_DET_NEAR) {
             launch_row_prop(c, B, c->bufC, c->bufA, c->hdet, 1.f, 0);
-            launch_loss_real(c, B, c->bufA, nullptr, false, (cf*)out_wave, nullptr, 1.f, 1.f, 0.f, zero, nullptr, nullptr, cs ? c->cdet64 : nullptr, s64);
+            launch_loss_real(c, B, det, c->bufA, nullptr, false, (cf*)out_wave, nullptr, 1.f, 1.f);
         } else {
-            const std::complex<double> keep = c->a0;      // the far-field kernel adds the carrier's DC bin: none here
-            c->a0 = 0.0;
-            launch_loss_far(c, B, c->bufC, nullptr, (cf*)out_wave, nullptr, 1.f, 1.f, 0.f, nullptr, cs ? c->cdet64 : nullptr, s64);
-            c->a0 = keep;
+            launch_loss_far(c, B, det, c->bufC, nullptr, (cf*)out_wave, nullptr, 1.f, 1.f);
         }
     }
     return launched(c);
@@ -2390,7 +2474,7 @@ int bdof_loss_grad_conv(bdof_ctx* c, int B, const int* angle_of_b, const int* xo
     if ((r = need_lsq(c, "bdof_loss_grad_conv"))) return r;
     // residual splitting at the detector (bdof_set_meas_mode(1): meas holds m - |a_0|), real-space detectors: the renormalised
     // wave is kept as A + e', A = s a_S a float64 scalar formed on the host from the corner pixel, and |A + e'| - m is
-    // evaluated without the cancellation of two numbers of size one (loss_seed_dev) — as on the transfer-function path
+    // evaluated without the cancellation of two numbers of size one (seed_split) — as on the transfer-function path
     const bool split = c->meas_dev != 0;
     if (split && (c->det_mode == BDOF_DET_FAR || std::abs(c->a0) == 0.0))
         return fail(c, BDOF_ERR_STATE, "bdof_set_meas_mode(1) needs a plane-wave carrier and a real-space detector");
@@ -2408,8 +2492,15 @@ int bdof_loss_grad_conv(bdof_ctx* c, int B, const int* angle_of_b, const int* xo
     const cf zero = make_float2(0.f, 0.f);
     cf* gp;
     int npart;
-    cf carA = zero;                 // split: A (times Hdet[0,0] for the near detector), the constant part of the detector wave
-    float absA = 0.f, dref = 0.f;
+    // The detector plane of the renormalised wave.  From the ctx (det_plane) it keeps the data term only: meas_dev, meas_ref, mu.
+    // Everything about the carrier is this path's own — the transfer-function recurrence behind det_plane's carrier, a_end and
+    // dref does not describe this wave — and is set or cleared here by name.
+    DetPlane det = det_plane(c, B, nullptr);
+    det.seed_scale = (float)seed_scale;
+    det.gcar = det.gt0 = nullptr;       // the far-field kernel adds no DC carrier here, so there is no adjoint carrier either
+    det.a_end = make_double2(0.0, 0.0);
+    det.dref = 0.f;
+    set_carrier(det, 0.0);              // split: A (times Hdet[0,0] for the near detector), the constant part of the detector wave
     if (split) {
         cf e0, p0;                  // corner pixel of batch element 0: scattered part of psi_S and of the probe
         HIPC(c, hipMemcpyAsync(&e0, c->bufB, sizeof(cf), hipMemcpyDeviceToHost, c->stream));
@@ -2419,48 +2510,48 @@ int bdof_loss_grad_conv(bdof_ctx* c, int B, const int* angle_of_b, const int* xo
         const std::complex<double> sd = (c->a0 + std::complex<double>(p0.x, p0.y)) / (aS + std::complex<double>(e0.x, e0.y));
         std::complex<double> A = sd * aS;
         if (c->det_mode == BDOF_DET_NEAR) A *= c->hdet00;
-        carA = make_float2((float)A.real(), (float)A.imag());
-        absA = (float)std::abs(A);
-        dref = (float)(std::abs(A) - std::abs(c->a0));
+        set_carrier(det, A);
+        if (c->det_mode == BDOF_DET_NONE) det.abs_carrier = (float)std::abs(A);      // k_conv_final: |A| rounded once, from float64
+        det.dref = (float)(std::abs(A) - std::abs(c->a0));
     }
     const bool cs = c->cstack != nullptr;
     const size_t plane = (size_t)c->NX * c->NY;
-    double2 s64 = kOne;
-    if (cs && (r = conv_scale64(c, &s64))) return r;
-    const cf car_end = (split || cs) ? zero : conv_carrier(c, c->S);       // split / carrier field: only the scattered part s eps goes on
+    if (cs) {
+        if ((r = conv_scale64(c, &det.pscale))) return r;
+        det.pfield64 = c->cdet64;
+    }
     if (c->det_mode == BDOF_DET_NONE && cs) {
-        // q = s (p_S + eps_S): the scattered part in float32, the residual against s p_S in float64 (loss_seed_f64), seed in place
-        ConvFinalArgs fa{c->bufB, c->bufA, nullptr, nullptr, nullptr, c->conv_scal, zero, n, 0.f, 0, zero, 0.f, 0.f, nullptr, plane};
+        // q = s (p_S + eps_S): the scattered part in float32, the residual against s p_S in float64 (seed_f64), seed in place
+        const ConvFinalArgs fa = conv_final_args(c, B, c->bufB, c->bufA, split);
         hipLaunchKernelGGL((k_conv_final<0>), dim3(egrid), dim3(256), 0, c->stream, fa);
-        GLossArgs la{c->bufA, (cf*)out_wave, meas, c->partial, B, c->NX, c->NY, 0, zero, (float)seed_scale, c->cstack + (size_t)c->S * plane, 0, 0.f,
-                     nullptr, nullptr, make_double2(0.0, 0.0), make_double2(0.0, 0.0), c->cdet64, nullptr, 0.0, s64};
+        det.pfield = c->cstack + (size_t)c->S * plane;
+        const GLossArgs la = g_loss_args(c, B, det, c->bufA, (cf*)out_wave, meas);
         hipLaunchKernelGGL(k_g_loss<false>, dim3(egrid), dim3(256), 0, c->stream, la);
         hipLaunchKernelGGL(k_conv_scale_seed, dim3(egrid), dim3(256), 0, c->stream, c->bufA, c->conv_scal, n);
         npart = egrid;
         gp = c->bufA;
     } else if (c->det_mode == BDOF_DET_NONE) {
-        ConvFinalArgs fa{c->bufB, (cf*)out_wave, c->bufA, meas, c->partial, c->conv_scal, car_end, n, (float)seed_scale, split ? 1 : 0, carA, absA, dref, nullptr, plane};
+        ConvFinalArgs fa = conv_final_args(c, B, c->bufB, (cf*)out_wave, split);
+        fa.out2 = c->bufA;
+        fa.meas = meas;
+        fa.partial = c->partial;
+        fa.det = det;
         hipLaunchKernelGGL((k_conv_final<1>), dim3(egrid), dim3(256), 0, c->stream, fa);
         npart = egrid;
         gp = c->bufA;
     } else {
-        ConvFinalArgs fa{c->bufB, c->bufA, nullptr, nullptr, nullptr, c->conv_scal, car_end, n, 0.f, 0, zero, 0.f, 0.f, nullptr, plane};
+        const ConvFinalArgs fa = conv_final_args(c, B, c->bufB, c->bufA, split);
         hipLaunchKernelGGL((k_conv_final<0>), dim3(egrid), dim3(256), 0, c->stream, fa);
         RealToHybArgs ra{c->bufA, c->bufC, B, c->NX, c->twY};
         DISPATCH_N(c->NY, { hipLaunchKernelGGL((k_row_real_to_hyb<N_>), dim3(rows_grid<N_>(c, B, c->NX)), dim3(BDOF_THREADS), 0, c->stream, ra); });
         if (c->det_mode == BDOF_DET_NEAR) {
             launch_row_prop(c, B, c->bufC, c->bufA, c->hdet, 1.f, 0);                                     // d_hat (L1)
-            npart = launch_loss_real(c, B, c->bufA, c->bufC, true, (cf*)out_wave, meas, 1.f, 1.f, (float)seed_scale, carA, nullptr,
-                                     split ? &dref : nullptr, cs ? c->cdet64 : nullptr, s64);
+            npart = launch_loss_real(c, B, det, c->bufA, c->bufC, true, (cf*)out_wave, meas, 1.f, 1.f);
             launch_row_prop(c, B, c->bufC, c->bufA, c->hdet, 1.f, 1);                                     // g_hat(q) (L1)
         } else {
-            const std::complex<double> keep = c->a0;
-            c->a0 = 0.0;
-            npart = launch_loss_far(c, B, c->bufC, c->bufA, (cf*)out_wave, meas, 1.f, 1.f, (float)seed_scale, nullptr,
-                                    cs ? c->cdet64 : nullptr, s64);                                           // g_hat(q) (L1)
-            c->a0 = keep;
+            npart = launch_loss_far(c, B, det, c->bufC, c->bufA, (cf*)out_wave, meas, 1.f, 1.f);          // g_hat(q) (L1)
         }
-        launch_loss_real(c, B, c->bufA, nullptr, false, c->bufC, nullptr, 1.f, 1.f, 0.f, zero);            // G(q), real space
+        launch_loss_real(c, B, DetPlane{}, c->bufA, nullptr, false, c->bufC, nullptr, 1.f, 1.f);          // G(q), real space
         hipLaunchKernelGGL(k_conv_scale_seed, dim3(egrid), dim3(256), 0, c->stream, c->bufC, c->conv_scal, n);
         gp = c->bufC;
     }

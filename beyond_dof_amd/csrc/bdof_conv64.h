@@ -59,7 +59,7 @@ __global__ __launch_bounds__(256) void k_c64_scale(double2* f, size_t n, const d
 }
 // loss partials and seed in place: d [B][NX][NY]; far: d is [b][kx][ky] and meas [b][ky][kx] (un-shifted), else both [b][x][y].
 // meas holds m - meas_ref (residual splitting of the float32 path); G = 2 (|d| - m) d / |d| * seed_scale
-// PSN: the Poisson data term with mu photons per unit intensity (poisson_weight, bdof_kernels.h)
+// PSN: the Poisson data term with mu photons per unit intensity (seed_weight, bdof_kernels.h)
 template <bool PSN>
 __global__ __launch_bounds__(256) void k_c64_loss(double2* d, const float* __restrict__ meas, double* partial, int B, int NX, int NY, int far,
                                                  double meas_ref, double seed_scale, double mu) {
@@ -70,28 +70,9 @@ __global__ __launch_bounds__(256) void k_c64_loss(double2* d, const float* __res
         const size_t r = i / NY;
         const int x = r % NX, b = r / NX;
         const double m = (double)meas[far ? ((size_t)b * NY + y) * NX + x : i] + meas_ref;
-        const double2 v = d[i];
-        const double a = sqrt(v.x * v.x + v.y * v.y);
-        const double res = a - m;
-        if constexpr (PSN) {
-            const double f = seed_scale * poisson_weight(res, a, m, mu, acc, acc2);
-            d[i] = make_double2(v.x * f, v.y * f);
-        } else {
-            acc += res * res;
-            acc2 += res * a;
-            const double f = a > 0.0 ? seed_scale * res / a : 0.0;
-            d[i] = make_double2(v.x * f, v.y * f);
-        }
+        d[i] = seed_f64<PSN>(d[i], m, seed_scale, mu, acc, acc2);
     }
-    __shared__ double w[2][4];
-    acc = wave_reduce_sum(acc);
-    acc2 = wave_reduce_sum(acc2);
-    if ((threadIdx.x & 63) == 0) { w[0][threadIdx.x >> 6] = acc; w[1][threadIdx.x >> 6] = acc2; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        partial[2 * blockIdx.x] = w[0][0] + w[0][1] + w[0][2] + w[0][3];
-        partial[2 * blockIdx.x + 1] = w[1][0] + w[1][1] + w[1][2] + w[1][3];
-    }
+    block_store_sum2<256>(acc, acc2, partial + 2 * blockIdx.x);
 }
 // per-workgroup partial sums of G conj(q) (complex), then the renormalisation's adjoint: G <- conj(s) G, G[0] -= T / conj(P000)
 __global__ __launch_bounds__(256) void k_c64_dot(const double2* __restrict__ G, const double2* __restrict__ q, size_t n, double2* part) {
@@ -101,12 +82,7 @@ __global__ __launch_bounds__(256) void k_c64_dot(const double2* __restrict__ G, 
         sx += g.x * v.x + g.y * v.y;
         sy += g.y * v.x - g.x * v.y;
     }
-    __shared__ double w[2][4];
-    sx = wave_reduce_sum(sx);
-    sy = wave_reduce_sum(sy);
-    if ((threadIdx.x & 63) == 0) { w[0][threadIdx.x >> 6] = sx; w[1][threadIdx.x >> 6] = sy; }
-    __syncthreads();
-    if (threadIdx.x == 0) part[blockIdx.x] = make_double2(w[0][0] + w[0][1] + w[0][2] + w[0][3], w[1][0] + w[1][1] + w[1][2] + w[1][3]);
+    block_store_sum2<256>(sx, sy, reinterpret_cast<double*>(part + blockIdx.x));
 }
 __global__ void k_c64_corner_adj(double2* G, const double2* part, int npart, const double2* scal) {
     double tx = 0.0, ty = 0.0;

@@ -57,103 +57,58 @@ struct GLossArgs {
     const float* meas;   // nullable; same order as out_wave
     double* partial;     // [2 * gridDim.x]
     int B, NX, NY, far;
-    cf carrier;          // real detectors: added everywhere; far: added to the DC bin of every batch element
-    float seed_scale;
-    const cf* pdet;      // nullable: carrier field at the detector, [x][y] / far field [kx][ky] (replaces `carrier`)
-    int meas_dev;        // `meas` holds m - |carrier| (loss_seed_dev, bdof_kernels.h)
-    float dref;
-    double2* gcar;       // nullable [B]: adjoint carrier (AdjCarrier, bdof_kernels.h) — far field with a plane-wave carrier
-    double2* gt0;
-    double2 carrier_dd, a_end;
-    const double2* pdet64;   // nullable: `pdet` in float64 (loss_seed_f64)
-    double2* seed64;         // nullable [B][NX][NY]: float64 adjoint sweep (bdof_configure flag 64) — detector wave, residual and
-    double meas_ref;         // seed all formed in float64 and left here un-rounded; meas_ref: what the host subtracted (meas_dev)
-    double2 pscale;          // complex factor on pdet64 (the real-space propagator's renormalisation s; 0, 0 means 1)
-    double mu;               // PSN (bdof_set_loss): photons per unit intensity
+    double2* seed64;     // nullable [B][NX][NY]: float64 adjoint sweep (bdof_configure flag 64) — detector wave, residual and
+                         // seed all formed in float64 and left here un-rounded
+    DetPlane det;        // bdof_kernels.h; pfield / pfield64 [x][y], far field [kx][ky]
 };
 
-// PSN: the Poisson data term (poisson_weight, bdof_kernels.h)
+// PSN: the Poisson data term (seed_weight, bdof_kernels.h)
 template <bool PSN>
 __global__ __launch_bounds__(256) void k_g_loss(GLossArgs a) {
     const size_t n = (size_t)a.B * a.NX * a.NY;
+    const DetPlane& det = a.det;
     double acc = 0.0, acc2 = 0.0;
     for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < n; idx += (size_t)gridDim.x * blockDim.x) {
         const int y = idx % a.NY;
         const size_t r = idx / a.NY;
         const int x = r % a.NX, b = r / a.NX;
+        const size_t pi = (size_t)x * a.NY + y;                                    // in the carrier field's plane
+        const size_t oi = a.far ? ((size_t)b * a.NY + y) * a.NX + x : idx;         // in meas / out_wave
+        const bool dc = x == 0 && y == 0;
         cf d = a.field[idx];
         if (a.seed64 && a.meas) {
-            const bool dc = x == 0 && y == 0;
             double2 p = make_double2(0.0, 0.0);
-            if (a.pdet64) p = a.pdet64[(size_t)x * a.NY + y];
-            else if (a.pdet) { const cf q = a.pdet[(size_t)x * a.NY + y]; p = make_double2((double)q.x, (double)q.y); }
-            else if (!a.far || dc) p = a.carrier_dd;
-            const size_t oi = a.far ? ((size_t)b * a.NY + y) * a.NX + x : idx;
-            const double dx = p.x + (double)d.x, dy = p.y + (double)d.y;
-            const double ab = sqrt(dx * dx + dy * dy), rr = ab - ((double)a.meas[oi] + a.meas_ref);
-            if constexpr (PSN) {
-                a.seed64[idx] = poisson_seed64(dx, dy, ab, rr, (double)a.seed_scale, a.mu, acc, acc2);
-            } else {
-                acc += rr * rr;
-                acc2 += rr * ab;
-                const double f = ab > 0.0 ? (double)a.seed_scale * rr / ab : 0.0;
-                a.seed64[idx] = make_double2(dx * f, dy * f);
-            }
-            if (a.out_wave) a.out_wave[oi] = make_float2((float)dx, (float)dy);
+            if (det.pfield64) p = det.pfield64[pi];
+            else if (det.pfield) { const cf q = det.pfield[pi]; p = make_double2((double)q.x, (double)q.y); }
+            else if (!a.far || dc) p = det.carrier_dd;
+            p = make_double2(p.x + (double)d.x, p.y + (double)d.y);
+            a.seed64[idx] = seed_f64<PSN>(p, (double)a.meas[oi] + det.meas_ref, (double)det.seed_scale, det.mu, acc, acc2);
+            if (a.out_wave) a.out_wave[oi] = make_float2((float)p.x, (float)p.y);
             continue;
         }
-        if (a.meas_dev && a.meas && !a.far && !a.pdet) {
-            const size_t oidx = idx;
-            if (a.out_wave) a.out_wave[oidx] = cadd(d, a.carrier);
-            a.field[idx] = loss_seed_dev_k<PSN>(d, a.carrier, sqrtf(a.carrier.x * a.carrier.x + a.carrier.y * a.carrier.y), a.meas[oidx],
-                                                a.seed_scale, a.mu, acc, acc2, a.dref);
+        if (det.meas_dev && a.meas && !a.far && !det.pfield) {
+            if (a.out_wave) a.out_wave[idx] = cadd(d, det.carrier);
+            a.field[idx] = seed_split<PSN>(d, a.meas[idx], det, acc, acc2);
             continue;
         }
-        const cf e0 = d;
-        if (a.pdet64 && a.meas) {
-            const size_t oi = a.far ? ((size_t)b * a.NY + y) * a.NX + x : idx;
+        if (det.pfield64 && a.meas) {
             cf dw;
-            double2 p = a.pdet64[(size_t)x * a.NY + y];
-            if (a.pscale.x != 0.0 || a.pscale.y != 0.0) p = make_double2(p.x * a.pscale.x - p.y * a.pscale.y, p.x * a.pscale.y + p.y * a.pscale.x);
-            a.field[idx] = loss_seed_f64_k<PSN>(d, p, a.meas[oi], a.seed_scale, a.mu, acc, acc2, dw);
+            a.field[idx] = seed_f64<PSN>(d, det_field64(det, pi), a.meas[oi], det, acc, acc2, dw);
             if (a.out_wave) a.out_wave[oi] = dw;
             continue;
         }
-        if (a.pdet) d = cadd(d, a.pdet[(size_t)x * a.NY + y]);
-        else if (!a.far || (x == 0 && y == 0)) d = cadd(d, a.carrier);
-        const size_t oidx = a.far ? ((size_t)b * a.NY + y) * a.NX + x : idx;
-        if (a.out_wave) a.out_wave[oidx] = d;
-        if (a.meas && a.gcar && a.far && x == 0 && y == 0) {
-            // DC bin in float64, its seed kept out of the transforms (AdjCarrier)
-            const double dx = a.carrier_dd.x + (double)e0.x, dy = a.carrier_dd.y + (double)e0.y;
-            const double ab = sqrt(dx * dx + dy * dy), rr = ab - (double)a.meas[oidx];
-            double2 s0;
-            if constexpr (PSN) {
-                s0 = poisson_seed64(dx, dy, ab, rr, (double)a.seed_scale, a.mu, acc, acc2);
-            } else {
-                acc += rr * rr;
-                acc2 += rr * ab;
-                const double f = ab > 0.0 ? (double)a.seed_scale * rr / ab : 0.0;
-                s0 = make_double2(dx * f, dy * f);
-            }
-            a.gcar[b] = s0;
-            a.gt0[b] = make_double2(a.a_end.x * s0.x + a.a_end.y * s0.y, a.a_end.x * s0.y - a.a_end.y * s0.x);
-            a.field[idx] = make_float2(0.f, 0.f);
+        const cf e0 = d;
+        if (det.pfield) d = cadd(d, det.pfield[pi]);
+        else if (!a.far || dc) d = cadd(d, det.carrier);
+        if (a.out_wave) a.out_wave[oi] = d;
+        if (a.meas && det.gcar && a.far && dc) {
+            seed_dc_bin<PSN>(det, b, e0, a.meas[oi], acc, acc2);
+            a.field[idx] = make_float2(0.f, 0.f);       // nothing of this bin goes through the transform back
             continue;
         }
-        if (a.meas) a.field[idx] = loss_seed_k<PSN>(d, a.meas[oidx], a.seed_scale, a.mu, acc, acc2);
+        if (a.meas) a.field[idx] = seed_plain<PSN>(d, a.meas[oi], det, acc, acc2);
     }
-    if (a.meas) {
-        __shared__ double w1[4], w2[4];
-        acc = wave_reduce_sum(acc);
-        acc2 = wave_reduce_sum(acc2);
-        if ((threadIdx.x & 63) == 0) { w1[threadIdx.x >> 6] = acc; w2[threadIdx.x >> 6] = acc2; }
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            a.partial[2 * blockIdx.x] = w1[0] + w1[1] + w1[2] + w1[3];
-            a.partial[2 * blockIdx.x + 1] = w2[0] + w2[1] + w2[2] + w2[3];
-        }
-    }
+    if (a.meas) block_store_sum2<256>(acc, acc2, a.partial + 2 * blockIdx.x);
 }
 
 struct GBwdArgs {

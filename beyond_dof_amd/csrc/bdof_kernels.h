@@ -371,52 +371,67 @@ __device__ __forceinline__ double wave_reduce_sum(double v) {
     return v;
 }
 
-// two sums at once: dst[0] = sum v, dst[1] = sum v2
-__device__ __forceinline__ void block_store_sum2(double v, double v2, double* dst) {
-    __shared__ double wsum[2][BDOF_THREADS / 64];
+// two sums at once over a workgroup of T threads: true in thread 0, where v and v2 then hold the totals (the waves' sums added
+// in wave order)
+template <int T> __device__ __forceinline__ bool block_sum2(double& v, double& v2) {
+    __shared__ double wsum[2][T / 64];
     v = wave_reduce_sum(v);
     v2 = wave_reduce_sum(v2);
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    if (lane == 0) { wsum[0][wid] = v; wsum[1][wid] = v2; }
+    if ((threadIdx.x & 63) == 0) { wsum[0][threadIdx.x >> 6] = v; wsum[1][threadIdx.x >> 6] = v2; }
     __syncthreads();
-    if (threadIdx.x == 0) {
-        double s = 0, s2 = 0;
-        for (int j = 0; j < BDOF_THREADS / 64; ++j) { s += wsum[0][j]; s2 += wsum[1][j]; }
-        dst[0] = s;
-        dst[1] = s2;
-    }
+    if (threadIdx.x != 0) return false;
+    v = wsum[0][0];
+    v2 = wsum[1][0];
+#pragma unroll
+    for (int j = 1; j < T / 64; ++j) { v += wsum[0][j]; v2 += wsum[1][j]; }
+    return true;
+}
+// dst[0] = sum v, dst[1] = sum v2
+template <int T = BDOF_THREADS> __device__ __forceinline__ void block_store_sum2(double v, double v2, double* dst) {
+    if (block_sum2<T>(v, v2)) { dst[0] = v; dst[1] = v2; }
 }
 
 // ---------------------------------------------------------------------------------------------
 // Detector plane: magnitude loss + adjoint seed.
 //   loss: cnn_propagator/fullfield.py:106 ; seed G(d) = 2 (|d| - |m|) d/|d| / n   
-// k_row_loss   (free_prop_cm None / distance): rows of L1, d = R^-1' in * in_scale (real space).
-// k_row_loss_far (free_prop_cm 'inf'):         rows of L2, d = C in * in_scale  = un-shifted fft2;
-//   the fftshift of np_funcs.py:48 is folded into the order in which the host lays out `meas`.
+// Every engine ends its forward sweep here: carrier + scattered wave, residual against the measurement, two sums, seed.
+// DetPlane says what the plane and the data term ARE (the host fills it: det_plane, bdof_capi.hip); layout and transforms
+// stay with each kernel's own arguments.  The per-pixel arithmetic is seed_weight (the data term) under three residual
+// forms — seed_plain, seed_split, seed_f64 — and seed_dc_bin for the far field's adjoint carrier.
 // ---------------------------------------------------------------------------------------------
-struct LossArgs {
-    const cf* in;
-    cf* out_hyb;         // nullable: seed transformed back (* out_scale); layout by TSTORE
-    cf* out_wave;        // nullable: detector wave, same row layout as `in`
-    const float* meas;   // nullable: |measured|, same row layout as `in`
-    double* partial;     // [2 * gridDim.x] per-workgroup sums of (|d|-|m|)^2 and of (|d|-|m|) |d|
-    int B, R;            // R rows per batch element
-    float in_scale, out_scale, seed_scale;
-    cf carrier;          // constant part of the detector wave (far field: its DC bin value a*NX*NY)
-    const cf* twiddle;
-    const cf* pfield;    // nullable: carrier field at this plane in the row layout of `in` ([R][N], the same for every batch
-                         // element); replaces `carrier`
-    int meas_dev;        // `meas` holds m - |carrier| (loss_seed_dev); real-space detectors with a scalar carrier only
-    // Adjoint carrier (far field + plane-wave carrier, see AdjCarrier below): the DC bin is evaluated in float64 and its seed
-    // is NOT sent through the transforms; it is left in gcar[b] (and conj(a_end) * seed in gt0[b]) for the adjoint kernels.
-    double2* gcar;       // nullable [B]
-    double2* gt0;        // [B]
-    double2 carrier_dd;  // a_end * NX * NY in float64 (= `carrier`)
-    double2 a_end;       // a_end: constant part of phi_{S-1}
-    float dref;          // meas_dev: |carrier| - reference subtracted by the host (loss_seed_dev)
-    const double2* pfield64;   // nullable: `pfield` in float64 — the residual is then formed in float64 (loss_seed_f64)
-    double2 pscale;            // complex factor on pfield64 (the real-space propagator's renormalisation s, else 1)
-    double mu;                 // PSN instantiations (bdof_set_loss): photons per unit intensity
+struct DetPlane {
+    // Field order: what every engine reads comes first and lies together, the float64 / far-field-only members after it — a
+    // kernel that reads only the head (k_resident) then fetches it in one piece and keeps its scalar-register footprint.
+    // ---- carrier: the part of the detector wave that is known exactly and never goes through the float32 transforms
+    cf carrier = {0.f, 0.f};             // scalar (plane-wave probe).  Real-space detectors: added everywhere; far field: the DC
+                                         // bin value a_end NX NY, added to that bin of every wavefield
+    float abs_carrier = 0.f;             // |carrier|
+    // ---- measurement.  Residual splitting (bdof_set_meas_mode 1): with the wave held as d = a + e (a the plane-wave part, known
+    // exactly) the residual |d| - m is the difference of two float32 numbers of size one and carries 7e-8 of absolute error,
+    // i.e. 3e-6 of a 2 % residual.  |a + e| - |a| = (2 Re(conj(a) e) + |e|^2) / (|a + e| + |a|) has no cancellation, and the host
+    // hands the measurement over as mdev = m - |a| (float64 subtraction, then float32): r = (|d| - |a|) - mdev is as accurate
+    // as the scattered wave e itself (seed_split).
+    float dref = 0.f;                    // |carrier| - meas_ref: the host subtracts |a_0|, the carrier at the detector has modulus
+                                         // |a_0| |cbar|^S (mean-refraction carrier), the difference (float64 on the host) is added back
+    int meas_dev = 0;                    // `meas` holds m - meas_ref; real-space detectors with a scalar carrier only
+    // ---- data term
+    float seed_scale = 0.f;              // 2 / (number of pixels of the batch)
+    double mu = 0.0;                     // PSN instantiations (bdof_set_loss): photons per unit intensity
+    // Carrier FIELD (localised probe): the wave is d = p + e with p the probe's own propagation, known in float64
+    // (bdof_set_probe_field), and e the scattered part that came through the float32 transforms.  Rounding p to float32 first
+    // costs 6e-8 |d| — 3e-6 of a 2 % residual, the largest single term of the gradient's error in far-field ptychography
+    // (tools/precision_model.py) — so with pfield64 |d| - m is formed in float64 and only the finished seed is rounded (seed_f64).
+    const cf* pfield = nullptr;          // nullable: replaces `carrier`; one plane in the kernel's own layout, shared by the batch
+    const double2* pfield64 = nullptr;   // nullable: `pfield` in float64
+    // ---- read by the streaming, generic and real-space-propagator launches only
+    double2 pscale = {1.0, 0.0};         // complex factor on pfield64: the real-space propagator's renormalisation s; (1, 0): none
+    double meas_ref = 0.0;               // what the host subtracted (meas_dev), for the sites that form the wave in float64 (seed64)
+    double2 carrier_dd = {0.0, 0.0};     // `carrier` in float64
+    double2 a_end = {0.0, 0.0};          // constant part of phi_{S-1} (far field: carrier = a_end NX NY)
+    // adjoint carrier (far field + plane-wave carrier, AdjCarrier below): the DC bin is evaluated in float64 and its seed
+    // is NOT sent through the transforms; it is left in gcar[b] (and conj(a_end) * seed in gt0[b]) for the adjoint kernels
+    double2* gcar = nullptr;             // nullable [B]
+    double2* gt0 = nullptr;              // [B]
 };
 
 // Adjoint carrier.  With a plane-wave probe and a far-field detector nearly all of the detector wave sits in ONE bin (DC,
@@ -440,58 +455,15 @@ __device__ __forceinline__ void adj_carrier_load(const AdjCarrier& ac, int b, cf
     t0 = make_float2((float)t.x, (float)t.y);
 }
 
-__device__ __forceinline__ cf loss_seed(cf d, float m, float seed_scale, double& acc, double& acc2) {
-    const float a = sqrtf(d.x * d.x + d.y * d.y);
-    const float r = a - m;
-    acc += (double)r * (double)r;
-    acc2 += (double)r * (double)a;
-    const float f = a > 0.f ? seed_scale * r / a : 0.f;
-    return make_float2(d.x * f, d.y * f);
-}
-
-// Residual splitting at the detector (bdof_set_meas_mode 1): with the wave held as d = a + e (a the plane-wave part, known
-// exactly) the residual |d| - m is the difference of two float32 numbers of size one and carries 7e-8 of absolute error,
-// i.e. 3e-6 of a 2 % residual.  |a + e| - |a| = (2 Re(conj(a) e) + |e|^2) / (|a + e| + |a|) has no cancellation, and the host
-// hands the measurement over as mdev = m - |a| (float64 subtraction, then float32): r = (|d| - |a|) - mdev is as accurate
-// as the scattered wave e itself.
-// dref = |a| - (the reference the host subtracted): the host subtracts |a_0|, the carrier at the detector has modulus
-// |a_0| |cbar|^S (mean-refraction carrier), the difference (float64 on the host) is added back here.
-__device__ __forceinline__ cf loss_seed_dev(cf e, cf a, float abs_a, float mdev, float seed_scale, double& acc, double& acc2, float dref = 0.f) {
-    const cf d = cadd(a, e);
-    const float ab = sqrtf(d.x * d.x + d.y * d.y);
-    const float q = fmaf(2.f * a.x, e.x, fmaf(2.f * a.y, e.y, fmaf(e.x, e.x, e.y * e.y)));
-    const float r = q / (ab + abs_a) - (mdev - dref);
-    acc += (double)r * (double)r;
-    acc2 += (double)r * (double)ab;
-    const float f = ab > 0.f ? seed_scale * r / ab : 0.f;
-    return make_float2(d.x * f, d.y * f);
-}
-
-// Carrier FIELD at the detector (localised probe): the wave is d = p + e with p the probe's own propagation, known in float64
-// (bdof_set_probe_field), and e the scattered part that came through the float32 transforms.  Rounding p to float32 first
-// costs 6e-8 |d| — 3e-6 of a 2 % residual, the largest single term of the gradient's error in far-field ptychography
-// (tools/precision_model.py) — so |d| - m is formed here in float64 and only the finished seed is rounded.
-__device__ __forceinline__ cf loss_seed_f64(cf e, double2 p, float m, float seed_scale, double& acc, double& acc2, cf& d_out) {
-    const double dx = p.x + (double)e.x, dy = p.y + (double)e.y;
-    const double ab = sqrt(dx * dx + dy * dy), r = ab - (double)m;
-    acc += r * r;
-    acc2 += r * ab;
-    const double f = ab > 0.0 ? (double)seed_scale * r / ab : 0.0;
-    d_out = make_float2((float)dx, (float)dy);
-    return make_float2((float)(dx * f), (float)(dy * f));
-}
-
 // ---- Poisson (photon-counting) data term: bdof_set_loss(BDOF_LOSS_POISSON, mu), include/bdof.h ---------------------------
 // Per pixel, with a = |d|, m the measured amplitude, r = a - m and mu photons per unit intensity, the deviance
 //     L = mu (a^2 - m^2 - 2 m^2 ln(a / m)) = mu (r (a + m) - 2 m^2 log1p(r / m))          (m = 0: mu a^2)
 // — the reference's commented mu a^2 - mu m^2 ln(mu a^2) minus its value at a = m (same gradient, zero at the fit, ~ 2 mu r^2
 // near it; the raw form is a constant of order mu ln mu per pixel, which costs the sum its digits and blinds a stopping rule that
 // looks at the relative change).  The two first-order parts of the term cancel, so it is evaluated in float64 from r — which
-// every site forms without cancellation, exactly as for least squares (loss_seed_dev / loss_seed_f64 / the float64 DC bin).
+// every residual form below hands over without cancellation, exactly as for least squares.
 // Seed G(d) = seed_scale w d with w = mu r (a + m) / a^2: the least-squares weight r / a times mu (a + m) / a.
 // Second sum (k_conv_finish's meaning, sum Re(conj(d) G) / seed_scale): mu r (a + m).  a = 0: nothing, and no epsilon.
-// The ONE place the five detector kernels take the Poisson term from; least squares stays where it was, instruction by
-// instruction (the kernels carry the kind as a template parameter).
 __device__ __forceinline__ double poisson_weight(double r, double a, double m, double mu, double& acc, double& acc2) {
     if (!(a > 0.0)) return 0.0;
     const double s = r * (a + m);
@@ -499,44 +471,80 @@ __device__ __forceinline__ double poisson_weight(double r, double a, double m, d
     acc2 += mu * s;
     return mu * s / (a * a);
 }
-// the three seed forms above under either loss kind (PSN: Poisson).  Where the amplitude itself is not in hand (residual
-// splitting) m = a - r is accurate enough for the factor.
-template <bool PSN> __device__ __forceinline__ cf loss_seed_k(cf d, float m, float seed_scale, double mu, double& acc, double& acc2) {
-    if constexpr (!PSN) return loss_seed(d, m, seed_scale, acc, acc2);
-    else {
-        const float a = sqrtf(d.x * d.x + d.y * d.y);
-        const float f = (float)((double)seed_scale * poisson_weight((double)(a - m), (double)a, (double)m, mu, acc, acc2));
-        return make_float2(d.x * f, d.y * f);
+// The data term of one pixel, the ONE place every detector kernel takes it from: residual r, modulus a = |d| and measured
+// amplitude m in; the two sums accumulated (always in double); the factor f of the seed G(d) = f d out, in the precision the
+// residual was formed in.  The kernels carry the kind as a template parameter (PSN: Poisson), so least squares never sees mu or
+// m.  m is a double because the split form only has it as a - r, which is formed in double.
+template <bool PSN, class Real>
+__device__ __forceinline__ Real seed_weight(Real r, Real a, double m, Real seed_scale, double mu, double& acc, double& acc2) {
+    if constexpr (PSN) {
+        return (Real)((double)seed_scale * poisson_weight((double)r, (double)a, m, mu, acc, acc2));
+    } else {
+        acc += (double)r * (double)r;
+        acc2 += (double)r * (double)a;
+        return a > (Real)0 ? seed_scale * r / a : (Real)0;
     }
 }
+
+// plain: d is the whole detector wave in float32, r = |d| - m
+template <bool PSN> __device__ __forceinline__ cf seed_plain(cf d, float m, const DetPlane& p, double& acc, double& acc2) {
+    const float a = sqrtf(d.x * d.x + d.y * d.y);
+    const float f = seed_weight<PSN>(a - m, a, (double)m, p.seed_scale, p.mu, acc, acc2);
+    return make_float2(d.x * f, d.y * f);
+}
+// split (DetPlane::meas_dev): e is the scattered part, d = carrier + e, r = (|d| - |carrier|) - (mdev - dref)
+template <bool PSN> __device__ __forceinline__ cf seed_split(cf e, float mdev, const DetPlane& p, double& acc, double& acc2) {
+    const cf a = p.carrier;
+    const cf d = cadd(a, e);
+    const float ab = sqrtf(d.x * d.x + d.y * d.y);
+    const float q = fmaf(2.f * a.x, e.x, fmaf(2.f * a.y, e.y, fmaf(e.x, e.x, e.y * e.y)));
+    const float r = q / (ab + p.abs_carrier) - (mdev - p.dref);
+    const float f = seed_weight<PSN>(r, ab, (double)ab - (double)r, p.seed_scale, p.mu, acc, acc2);
+    return make_float2(d.x * f, d.y * f);
+}
+// float64: the wave d = (float64 carrier) + e in double, r = |d| - m in double; the seed is returned un-rounded
 template <bool PSN>
-__device__ __forceinline__ cf loss_seed_dev_k(cf e, cf a, float abs_a, float mdev, float seed_scale, double mu, double& acc, double& acc2, float dref) {
-    if constexpr (!PSN) return loss_seed_dev(e, a, abs_a, mdev, seed_scale, acc, acc2, dref);
-    else {
-        const cf d = cadd(a, e);
-        const float ab = sqrtf(d.x * d.x + d.y * d.y);
-        const float q = fmaf(2.f * a.x, e.x, fmaf(2.f * a.y, e.y, fmaf(e.x, e.x, e.y * e.y)));
-        const float r = q / (ab + abs_a) - (mdev - dref);
-        const float f = (float)((double)seed_scale * poisson_weight((double)r, (double)ab, (double)ab - (double)r, mu, acc, acc2));
-        return make_float2(d.x * f, d.y * f);
-    }
+__device__ __forceinline__ double2 seed_f64(double2 d, double m, double seed_scale, double mu, double& acc, double& acc2) {
+    const double ab = sqrt(d.x * d.x + d.y * d.y);
+    const double f = seed_weight<PSN>(ab - m, ab, m, seed_scale, mu, acc, acc2);
+    return make_double2(d.x * f, d.y * f);
 }
+// ... against a float64 carrier-field value c (DetPlane::pfield64): seed and detector wave c + e rounded once, at the end
 template <bool PSN>
-__device__ __forceinline__ cf loss_seed_f64_k(cf e, double2 p, float m, float seed_scale, double mu, double& acc, double& acc2, cf& d_out) {
-    if constexpr (!PSN) return loss_seed_f64(e, p, m, seed_scale, acc, acc2, d_out);
-    else {
-        const double dx = p.x + (double)e.x, dy = p.y + (double)e.y;
-        const double ab = sqrt(dx * dx + dy * dy);
-        const double f = (double)seed_scale * poisson_weight(ab - (double)m, ab, (double)m, mu, acc, acc2);
-        d_out = make_float2((float)dx, (float)dy);
-        return make_float2((float)(dx * f), (float)(dy * f));
-    }
+__device__ __forceinline__ cf seed_f64(cf e, double2 c, float m, const DetPlane& p, double& acc, double& acc2, cf& d_out) {
+    const double2 d = make_double2(c.x + (double)e.x, c.y + (double)e.y);
+    const double2 s = seed_f64<PSN>(d, (double)m, (double)p.seed_scale, p.mu, acc, acc2);
+    d_out = make_float2((float)d.x, (float)d.y);
+    return make_float2((float)s.x, (float)s.y);
 }
-// a float64 site's own residual rr of a wave (dx, dy) of modulus ab: its Poisson seed (the least-squares lines stay at the sites)
-__device__ __forceinline__ double2 poisson_seed64(double dx, double dy, double ab, double rr, double seed_scale, double mu, double& acc, double& acc2) {
-    const double f = seed_scale * poisson_weight(rr, ab, ab - rr, mu, acc, acc2);
-    return make_double2(dx * f, dy * f);
+__device__ __forceinline__ double2 det_field64(const DetPlane& p, size_t i) {
+    const double2 q = p.pfield64[i];
+    return make_double2(q.x * p.pscale.x - q.y * p.pscale.y, q.x * p.pscale.y + q.y * p.pscale.x);
 }
+// far field + plane-wave carrier: the DC bin of wavefield b, scattered part e0, evaluated in float64; its seed stays out of the
+// transforms (AdjCarrier).  The caller takes the bin out of its float32 path.
+template <bool PSN> __device__ __forceinline__ void seed_dc_bin(const DetPlane& p, int b, cf e0, float m, double& acc, double& acc2) {
+    const double2 d = make_double2(p.carrier_dd.x + (double)e0.x, p.carrier_dd.y + (double)e0.y);
+    const double2 s0 = seed_f64<PSN>(d, (double)m, (double)p.seed_scale, p.mu, acc, acc2);
+    p.gcar[b] = s0;
+    p.gt0[b] = make_double2(p.a_end.x * s0.x + p.a_end.y * s0.y, p.a_end.x * s0.y - p.a_end.y * s0.x);
+}
+
+// Detector kernels of the streaming engine:
+// k_row_loss   (free_prop_cm None / distance): rows of L1, d = R^-1' in * in_scale (real space).
+// k_row_loss_far (free_prop_cm 'inf'):         rows of L2, d = C in * in_scale  = un-shifted fft2;
+//   the fftshift of np_funcs.py:48 is folded into the order in which the host lays out `meas`.
+struct LossArgs {
+    const cf* in;
+    cf* out_hyb;         // nullable: seed transformed back (* out_scale); layout by TSTORE
+    cf* out_wave;        // nullable: detector wave, same row layout as `in`
+    const float* meas;   // nullable: |measured|, same row layout as `in`
+    double* partial;     // [2 * gridDim.x] per-workgroup sums of (|d|-|m|)^2 and of (|d|-|m|) |d|
+    int B, R;            // R rows per batch element
+    float in_scale, out_scale;
+    const cf* twiddle;
+    DetPlane det;        // pfield / pfield64 in the row layout of `in` ([R][N])
+};
 
 // FAR = false: inverse FFT first (rows of L1); FAR = true: forward FFT first (rows of L2).  PSN: the Poisson data term.
 template <int N, bool FAR, bool TSTORE, bool PSN = false>
@@ -571,38 +579,36 @@ __global__ __launch_bounds__(BDOF_THREADS, RowCfg<N>::MIN_WAVES) void k_row_loss
             line_fft<N, S1, 1, EX>(u, tw, tid, lds);
 #pragma unroll
             for (int m = 0; m < 8; ++m) u[m] = cscale(u[m], a.in_scale);
-            const bool dev = !FAR && a.meas_dev && a.meas && !a.pfield;
+            const DetPlane& det = a.det;
+            const bool dev = !FAR && det.meas_dev && a.meas && !det.pfield;
             cf e0 = make_float2(0.f, 0.f);        // FAR: scattered part of the DC bin
-            if (a.pfield64) {
-                const double2* pf = a.pfield64 + (size_t)(r0 + r) * N;
+            if (det.pfield64) {
 #pragma unroll
                 for (int m = 0; m < 8; ++m) {
-                    const double2 q = pf[tid + m * C::T];
-                    const double2 p = make_double2(q.x * a.pscale.x - q.y * a.pscale.y, q.x * a.pscale.y + q.y * a.pscale.x);
+                    const double2 p = det_field64(det, (size_t)(r0 + r) * N + tid + m * C::T);
                     cf dw;
-                    if (a.meas) u[m] = loss_seed_f64_k<PSN>(u[m], p, mm[m], a.seed_scale, a.mu, acc, acc2, dw);
+                    if (a.meas) u[m] = seed_f64<PSN>(u[m], p, mm[m], det, acc, acc2, dw);
                     else dw = u[m] = make_float2((float)(p.x + (double)u[m].x), (float)(p.y + (double)u[m].y));
                     if (a.out_wave) a.out_wave[off + tid + m * C::T] = dw;
                 }
             } else if (dev) {
                 // u is still the scattered part: the seed comes from (e, a) directly, the detector wave is a + e
-                const float abs_a = sqrtf(a.carrier.x * a.carrier.x + a.carrier.y * a.carrier.y);
                 if (a.out_wave) {
 #pragma unroll
-                    for (int m = 0; m < 8; ++m) a.out_wave[off + tid + m * C::T] = cadd(u[m], a.carrier);
+                    for (int m = 0; m < 8; ++m) a.out_wave[off + tid + m * C::T] = cadd(u[m], det.carrier);
                 }
 #pragma unroll
-                for (int m = 0; m < 8; ++m) u[m] = loss_seed_dev_k<PSN>(u[m], a.carrier, abs_a, mm[m], a.seed_scale, a.mu, acc, acc2, a.dref);
+                for (int m = 0; m < 8; ++m) u[m] = seed_split<PSN>(u[m], mm[m], det, acc, acc2);
             } else {
-                if (a.pfield) {
-                    const cf* pf = a.pfield + (size_t)(r0 + r) * N;
+                if (det.pfield) {
+                    const cf* pf = det.pfield + (size_t)(r0 + r) * N;
 #pragma unroll
                     for (int m = 0; m < 8; ++m) u[m] = cadd(u[m], pf[tid + m * C::T]);
                 } else if constexpr (FAR) {
-                    if (r0 + r == 0 && tid == 0) { e0 = u[0]; u[0] = cadd(u[0], a.carrier); }       // DC bin of the un-shifted fft2
+                    if (r0 + r == 0 && tid == 0) { e0 = u[0]; u[0] = cadd(u[0], det.carrier); }     // DC bin of the un-shifted fft2
                 } else {
 #pragma unroll
-                    for (int m = 0; m < 8; ++m) u[m] = cadd(u[m], a.carrier);
+                    for (int m = 0; m < 8; ++m) u[m] = cadd(u[m], det.carrier);
                 }
                 if (a.out_wave) {
 #pragma unroll
@@ -610,27 +616,15 @@ __global__ __launch_bounds__(BDOF_THREADS, RowCfg<N>::MIN_WAVES) void k_row_loss
                 }
                 if (a.meas) {
                     if constexpr (FAR) {
-                        if (a.gcar && r0 + r == 0 && tid == 0) {
-                            // DC bin in float64; its seed stays out of the transforms (AdjCarrier).  u[0] = (m, 0) makes the
-                            // float32 path below contribute exactly nothing for this bin.
-                            const double dx = a.carrier_dd.x + (double)e0.x, dy = a.carrier_dd.y + (double)e0.y;
-                            const double ab = sqrt(dx * dx + dy * dy), rr = ab - (double)mm[0];
-                            double2 s0;
-                            if constexpr (PSN) {
-                                s0 = poisson_seed64(dx, dy, ab, rr, (double)a.seed_scale, a.mu, acc, acc2);
-                            } else {
-                                acc += rr * rr;
-                                acc2 += rr * ab;
-                                const double f = ab > 0.0 ? (double)a.seed_scale * rr / ab : 0.0;
-                                s0 = make_double2(dx * f, dy * f);
-                            }
-                            a.gcar[b] = s0;
-                            a.gt0[b] = make_double2(a.a_end.x * s0.x + a.a_end.y * s0.y, a.a_end.x * s0.y - a.a_end.y * s0.x);
+                        if (det.gcar && r0 + r == 0 && tid == 0) {
+                            // u[0] = (m, 0) makes the float32 path below contribute exactly nothing for this bin (the row
+                            // still goes through the transform back)
+                            seed_dc_bin<PSN>(det, b, e0, mm[0], acc, acc2);
                             u[0] = make_float2(mm[0], 0.f);
                         }
                     }
 #pragma unroll
-                    for (int m = 0; m < 8; ++m) u[m] = loss_seed_k<PSN>(u[m], mm[m], a.seed_scale, a.mu, acc, acc2);
+                    for (int m = 0; m < 8; ++m) u[m] = seed_plain<PSN>(u[m], mm[m], det, acc, acc2);
                 }
             }
             if (a.out_hyb) {
@@ -1698,16 +1692,13 @@ struct ConvFinalArgs {
     const float* meas;   // MODE 1
     double* partial;     // MODE 1: [2 * gridDim.x]: sum r^2, sum r |d|
     const cf* scal;
-    cf carrier_end;      // a_S; zero when `split` (only the scattered part e' = s eps is formed)
+    cf carrier_end;      // a_S; zero when det.meas_dev (only the scattered part e' = s eps is formed)
     size_t n;
-    float seed_scale;
-    // MODE 1 with residual splitting (bdof_set_meas_mode(1)): d = A + e', A = s a_S from the host in float64, meas = m - |a_0|,
-    // dref = |A| - |a_0|
-    int split;
-    cf A;
-    float absA, dref;
     const cf* pfield;    // nullable [plane]: carrier FIELD p_S added to every wavefield (MODE 0 outputs of the full wave)
     size_t plane;
+    // MODE 1: seed_scale, and with residual splitting (meas_dev) d = A + e' with carrier = A = s a_S and abs_carrier = |A| from
+    // the host in float64, meas = m - |a_0|, dref = |A| - |a_0|
+    DetPlane det;
 };
 template <int MODE>
 __global__ __launch_bounds__(256) void k_conv_final(ConvFinalArgs a) {
@@ -1718,33 +1709,16 @@ __global__ __launch_bounds__(256) void k_conv_final(ConvFinalArgs a) {
         if (a.pfield) full = cadd(full, a.pfield[idx % a.plane]);
         const cf q = cmul(full, s);
         if constexpr (MODE == 1) {
-            if (a.split) {
-                if (a.out) a.out[idx] = cadd(q, a.A);
-                a.out2[idx] = cmulc(loss_seed_dev(q, a.A, a.absA, a.meas[idx], a.seed_scale, acc, acc2, a.dref), s);
+            if (a.det.meas_dev) {
+                if (a.out) a.out[idx] = cadd(q, a.det.carrier);
+                a.out2[idx] = cmulc(seed_split<false>(q, a.meas[idx], a.det, acc, acc2), s);
                 continue;
             }
         }
         if (a.out) a.out[idx] = q;
-        if constexpr (MODE == 1) {
-            const float ab = sqrtf(q.x * q.x + q.y * q.y);
-            const float r = ab - a.meas[idx];
-            acc += (double)r * r;
-            acc2 += (double)r * ab;
-            const float f = ab > 0.f ? a.seed_scale * r / ab : 0.f;
-            a.out2[idx] = cmulc(cscale(q, f), s);                         // conj(s) G(d)
-        }
+        if constexpr (MODE == 1) a.out2[idx] = cmulc(seed_plain<false>(q, a.meas[idx], a.det, acc, acc2), s);      // conj(s) G(d)
     }
-    if constexpr (MODE == 1) {
-        __shared__ double w1[4], w2[4];
-        acc = wave_reduce_sum(acc);
-        acc2 = wave_reduce_sum(acc2);
-        if ((threadIdx.x & 63) == 0) { w1[threadIdx.x >> 6] = acc; w2[threadIdx.x >> 6] = acc2; }
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            a.partial[2 * blockIdx.x] = w1[0] + w1[1] + w1[2] + w1[3];
-            a.partial[2 * blockIdx.x + 1] = w2[0] + w2[1] + w2[2] + w2[3];
-        }
-    }
+    if constexpr (MODE == 1) block_store_sum2<256>(acc, acc2, a.partial + 2 * blockIdx.x);
 }
 
 // Gp = conj(s) G(q) for detectors that went through the FFT machinery (G(q) arrives in real space)
@@ -1760,14 +1734,9 @@ __global__ void k_conv_finish(const double* partial, int nblocks, int stride, do
                               cf* gp, const cf* scal) {
     double v = 0.0, v2 = 0.0;
     for (int j = threadIdx.x; j < nblocks; j += blockDim.x) { v += partial[stride * j]; v2 += partial[stride * j + 1]; }
-    __shared__ double w1[4], w2[4];
-    v = wave_reduce_sum(v);
-    v2 = wave_reduce_sum(v2);
-    if ((threadIdx.x & 63) == 0) { w1[threadIdx.x >> 6] = v; w2[threadIdx.x >> 6] = v2; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        loss[0] = (w1[0] + w1[1] + w1[2] + w1[3]) * inv_n;
-        const double rsum = (w2[0] + w2[1] + w2[2] + w2[3]) * seed_scale;
+    if (block_sum2<256>(v, v2)) {
+        loss[0] = v * inv_n;
+        const double rsum = v2 * seed_scale;
         const cf p = scal[1];
         const double den = (double)p.x * p.x + (double)p.y * p.y;
         // rsum / conj(p) = rsum * p / |p|^2

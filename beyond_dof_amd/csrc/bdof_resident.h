@@ -295,25 +295,21 @@ struct ResArgs {
     float2* grot;          // [B][S][N][N]
     ObjView obj;
     const cf* carrier;     // device [2 S]: a_z, then a_z (cbar - 1) (mean-refraction carrier, modulate_eps_s)
-    cf carrier_det;        // constant part of the detector wave (far field: DC bin value)
     // Carrier FIELD (bdof_set_probe_stack): the probe propagated through free space, p_z [S][N][N] at the entrance of every
-    // slice and pdet [N][N] at the detector (far field: its un-normalised fft2, [kx][ky]), computed by the host in
+    // slice and det.pfield [N][N] at the detector (far field: its un-normalised fft2, [kx][ky]), computed by the host in
     // float64.  The wave is then held as psi_z = p_z + eps_z and only the SCATTERED part eps goes through the float32
-    // transforms — the generalisation of the scalar carrier to a localised probe.  nullptr: scalar carrier above.
+    // transforms — the generalisation of the scalar carrier to a localised probe.  nullptr: scalar carriers (`carrier`, det.carrier).
     const cf* pstack;
-    const cf* pdet;
     const float* meas;     // nullable; real detectors [b][x][y], far field [b][ky][kx]
     cf* out_wave;          // nullable; same order as meas
     double* partial;       // [2 * gridDim.x * T / 64]: per workgroup and wave, (sum r^2, sum r |d|)
     const cf* twiddle;     // [N] exp(-2 pi i k / N)
     int B, S, det_mode, tf_all, do_grad;
-    float k, seed_scale;
-    int meas_dev;          // `meas` holds m - |carrier_det| (loss_seed_dev, bdof_kernels.h)
+    float k;
     int hD;                // dithered copies of hsT (0: one table)
-    float dref;
     cf* gpsi0;             // nullable [B][N][N]: G(psi_0), the probe gradient per wavefield
-    const double2* pdet64; // nullable: `pdet` in float64 — the residual |d| - m is then formed in float64 (loss_seed_f64)
-    double mu;             // PSN instantiations (bdof_set_loss): photons per unit intensity
+    DetPlane det;          // bdof_kernels.h; pfield / pfield64 [x][y], far field [kx][ky], used as they are (pscale is 1 on the
+                           // transfer-function path); no adjoint carrier (use_resident, bdof_capi.hip)
 };
 
 // transfer-function multiply folded into the last pass of the forward transform: the thread writing element (kx, ky)
@@ -531,7 +527,7 @@ template <int N, int T> struct ResPoint {
 };
 
 // WPE = waves per SIMD the register allocation must leave room for (two workgroups per CU where the LDS image allows)
-// PSN: the Poisson data term (poisson_weight, bdof_kernels.h) — a template parameter, so that the least-squares kernels are
+// PSN: the Poisson data term (seed_weight, bdof_kernels.h) — a template parameter, so that the least-squares kernels are
 // the instructions they were
 template <int N, int T, int WPE, bool PSN = false>
 __global__ __launch_bounds__(T, WPE) void k_resident(ResArgs a) {
@@ -618,8 +614,7 @@ __global__ __launch_bounds__(T, WPE) void k_resident(ResArgs a) {
         // with register allocation, like the spill; the structured form has nothing for it to act on).
         double acc = 0.0, acc2 = 0.0;
         {
-            const int mode = !a.meas ? 0 : ((a.meas_dev && !far && !a.pdet) ? 1 : (a.pdet64 ? 2 : 3));
-            const float abs_car = sqrtf(a.carrier_det.x * a.carrier_det.x + a.carrier_det.y * a.carrier_det.y);
+            const int mode = !a.meas ? 0 : ((a.det.meas_dev && !far && !a.det.pfield) ? 1 : (a.det.pfield64 ? 2 : 3));
             int t0 = tid;
             asm volatile("" : "+v"(t0));
 #pragma nounroll
@@ -629,18 +624,18 @@ __global__ __launch_bounds__(T, WPE) void k_resident(ResArgs a) {
                     const int x = res_div<N>(e), y = e - x * N;
                     const size_t o = b * fsz + (far ? y * N + x : e);
                     cf d = f[x * P + y], seed;
-                    if (mode == 1) {               // plane-wave carrier, real-space detector, residual splitting (loss_seed_dev)
-                        seed = loss_seed_dev_k<PSN>(d, a.carrier_det, abs_car, a.meas[o], a.seed_scale, a.mu, acc, acc2, a.dref);
-                        d = cadd(d, a.carrier_det);
-                    } else if (mode == 2) {        // carrier field in float64: |d| - m in float64 (loss_seed_f64)
+                    if (mode == 1) {               // plane-wave carrier, real-space detector, residual splitting
+                        seed = seed_split<PSN>(d, a.meas[o], a.det, acc, acc2);
+                        d = cadd(d, a.det.carrier);
+                    } else if (mode == 2) {        // carrier field in float64: |d| - m in float64
                         cf dw;
-                        seed = loss_seed_f64_k<PSN>(d, a.pdet64[e], a.meas[o], a.seed_scale, a.mu, acc, acc2, dw);
+                        seed = seed_f64<PSN>(d, a.det.pfield64[e], a.meas[o], a.det, acc, acc2, dw);
                         d = dw;
                     } else {
-                        if (a.pdet) d = cadd(d, a.pdet[e]);
-                        else if (!far || e == 0) d = cadd(d, a.carrier_det);
+                        if (a.det.pfield) d = cadd(d, a.det.pfield[e]);
+                        else if (!far || e == 0) d = cadd(d, a.det.carrier);
                         seed = d;
-                        if (mode == 3) seed = loss_seed_k<PSN>(d, a.meas[o], a.seed_scale, a.mu, acc, acc2);
+                        if (mode == 3) seed = seed_plain<PSN>(d, a.meas[o], a.det, acc, acc2);
                     }
                     if (a.out_wave) a.out_wave[o] = d;
                     if (mode != 0) f[x * P + y] = seed;

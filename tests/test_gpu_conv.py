@@ -66,6 +66,41 @@ def test_conv_forward_and_gradient(engine_mod, fp, ks, probe):
         assert rel(gd, rgd) <= 1e-5 and rel(gb, rgb) <= 1e-5
 
 
+def test_conv_plain_residual_form(engine_mod):
+    """Real-space propagator, no free propagation, scalar carrier with residual splitting switched off: k_conv_final<1> takes
+    |q| - m in float32 (seed_plain), which test_conv_forward_and_gradient does not reach (its probes either make the engine split or
+    ride on a carrier field).  64 x 64, ks = 5, B = 2, S = 2.  Loss to 1e-5; gradients as in test_conv_forward_and_gradient: 2e-4 away from
+    the renormalisation's corner block, 2e-2 inside it."""
+    rng = np.random.default_rng(7)
+    B, Y, X, S, ks, fp = 2, 64, 64, 2, 5, None
+    delta = rng.uniform(0, 2e-5, size=(B, Y, X, S))
+    beta = 0.1 * delta
+    pr, pi = np.ones((Y, X)), np.zeros((Y, X))          # a plane wave: a scalar carrier, no carrier field
+    psize = [1e-7] * 3
+    eng = engine_mod.MultisliceEngine(Y, X, S, B, with_grad=True)
+    eng.residual_split = False
+    eng.set_physics(5000., 1e-7, fp)
+    eng.set_conv(5000., psize, ks)
+    eng.set_probe(pr, pi)
+    eng.set_object_batch(delta, beta)
+    assert eng.meas_ref == 0.0
+    ref = orc.multislice_propagate_cnn(delta, beta, pr.astype(np.complex64).real, pi.astype(np.float32), 5000., psize,
+                                       kernel_size=ks, free_prop_cm=fp)
+    meas = np.abs(ref) * (1 + 0.05 * rng.normal(size=ref.shape))
+    loss = eng.loss_grad(B, meas, conv=True)
+    gd, gb = eng.grad_batch_to_host(B)
+    rl, rgd, rgb = orc.cnn_loss_and_grad(delta, beta, pr.astype(np.float32), pi.astype(np.float32), 5000., psize, meas,
+                                         kernel_size=ks, free_prop_cm=fp)
+    away = np.ones(gd.shape, dtype=bool)
+    away[0, :ks, :ks, :] = False
+    e = (abs(loss - rl) / abs(rl), rel(gd[away], rgd[away]), rel(gb[away], rgb[away]), rel(gd[~away], rgd[~away]), rel(gb[~away], rgb[~away]),
+         rel(gd, rgd), rel(gb, rgb))
+    print('conv plain form: loss, g_delta / g_beta away from the corner, in it, whole', e)
+    assert e[0] <= 1e-5
+    assert e[1] <= 2e-4 and e[2] <= 2e-4
+    assert e[3] <= 2e-2 and e[4] <= 2e-2
+
+
 def test_drop_in_multislice_propagate_cnn(engine_mod):
     from beyond_dof_amd.propagation import multislice_propagate_cnn
     rng = np.random.default_rng(4)

@@ -44,7 +44,9 @@ def _case(engine_mod, B, Y, X, S, fp, variant, probe, seed=0, **eng_kw):
     delta = rng.uniform(0, 2e-5, size=(B, Y, X, S))
     beta = 0.1 * delta
     pr, pi = _probe(probe, Y, X, rng)
+    residual_split = eng_kw.pop('residual_split', True)
     eng = engine_mod.MultisliceEngine(Y, X, S, B, with_grad=True, **eng_kw)
+    eng.residual_split = residual_split
     eng.set_physics(5000., 1e-7, fp, variant=variant)
     eng.set_probe(pr, pi)
     eng.set_object_batch(delta, beta)
@@ -72,6 +74,24 @@ def test_poisson_loss_and_gradient_vs_reference(engine_mod, engine, Y, X, fp, pr
     rl, rgd, rgb, _ = pref.poisson_loss_and_grad(delta, beta, pr, pi, 5000., 1e-7, meas, MU, fp, variant)
     e = (abs(loss - rl) / abs(rl), rel(gd, rgd), rel(gb, rgb))
     print('poisson parity', engine, (Y, X), fp, probe, variant, 'loss / g_delta / g_beta rel err', e)
+    assert e[0] <= 1e-5, e
+    assert e[1] <= 2e-4 and e[2] <= 2e-4, e
+
+
+@pytest.mark.parametrize('fp,variant', [(None, 'numpy_skip_last'), (1e-4, 'tf_all')])
+def test_poisson_plain_residual_form_on_the_resident_engine(engine_mod, fp, variant):
+    """Scalar carrier with residual splitting off: the resident engine's float32 |d| - m (seed_plain) under the Poisson kind, which
+    the cases above do not reach (their real-space detectors split, their far-field ones carry a float64 field).  The engine's
+    smallest shape; bounds of test_poisson_loss_and_gradient_vs_reference."""
+    B, S, n = 2, 2, 32
+    eng, delta, beta, pr, pi, meas = _case(engine_mod, B, n, n, S, fp, variant, 'plane', seed=5, engine='resident', residual_split=False)
+    assert eng.meas_ref == 0.0 and not eng.probe_stack
+    eng.set_loss('poisson', MU)
+    loss = eng.loss_grad(B, meas)
+    gd, gb = eng.grad_batch_to_host(B)
+    rl, rgd, rgb, _ = pref.poisson_loss_and_grad(delta, beta, pr, pi, 5000., 1e-7, meas, MU, fp, variant)
+    e = (abs(loss - rl) / abs(rl), rel(gd, rgd), rel(gb, rgb))
+    print('poisson resident plain form', fp, variant, 'loss / g_delta / g_beta rel err', e)
     assert e[0] <= 1e-5, e
     assert e[1] <= 2e-4 and e[2] <= 2e-4, e
 

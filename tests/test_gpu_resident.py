@@ -86,6 +86,32 @@ def test_resident_agrees_with_the_other_device_engines(engine_mod, n, other):
     assert rel(a[2], b[2]) <= 2e-4 and rel(a[3], b[3]) <= 2e-4
 
 
+@pytest.mark.parametrize('fp,variant', [(None, 'numpy_skip_last'), (1e-4, 'tf_all')])
+def test_resident_plain_residual_form(engine_mod, fp, variant):
+    """Scalar carrier with residual splitting switched off (what the solvers do for an optimisable probe): the detector block adds
+    the carrier and takes |d| - m in float32 (seed_plain) — the one residual form the other resident tests do not reach, at the
+    engine's smallest shape.  Bounds of test_resident_sizes_vs_oracle."""
+    n, B, S = 32, 2, 2
+    rng, delta, beta, _, _ = _inputs(n, B, S, fp, 11)
+    pr, pi = np.ones((n, n)), np.zeros((n, n))          # a plane wave: a scalar carrier whatever the seed
+    eng = engine_mod.MultisliceEngine(n, n, S, B, with_grad=True, engine='resident')
+    eng.residual_split = False
+    eng.set_physics(5000., 1e-7, fp, variant=variant)
+    eng.set_probe(pr, pi)
+    eng.set_object_batch(delta, beta)
+    assert eng.meas_ref == 0.0 and not eng.probe_stack
+    ref, _ = orc.multislice_propagate_batch_numpy(delta, beta, pr, pi, 5000., 1e-7, fp, delta.shape, variant=variant,
+                                                  return_probe_array=False)
+    meas = np.abs(ref) * (1 + 0.05 * rng.normal(size=ref.shape))
+    loss = eng.loss_grad(B, meas)
+    gd, gb = eng.grad_batch_to_host(B)
+    rl, rgd, rgb = orc.multislice_loss_and_grad(delta, beta, pr, pi, 5000., 1e-7, meas, fp, variant)
+    e = (abs(loss - rl) / abs(rl), rel(gd, rgd), rel(gb, rgb))
+    print('resident plain form', fp, variant, 'loss / g_delta / g_beta rel err', e)
+    assert e[0] <= 1e-5
+    assert e[1] <= 2e-4 and e[2] <= 2e-4
+
+
 def test_resident_batch_larger_than_the_grid_and_auto_selection(engine_mod):
     """More wavefields than workgroups the launch may have (the kernel loops), and the automatic choice: a 64^2 field has a
     fused plan, so small batches stream and large ones (>= CUs / 4 wavefields) go resident — same numbers either way."""
