@@ -1018,6 +1018,9 @@ static int launch_tiles(bdof_ctx* c, const void* field, const void* tiles, TileG
     if (a.B < 1 || a.FX < 1 || a.FY < 1 || a.TX < 1 || a.TY < 1) return fail(c, BDOF_ERR_ARG, "bad tile / field shape");
     int r;
     if ((r = check_taper(c, a.TX, a.TY, a.taper)) || (r = check_halo(c, a.TX, a.TY, a.hx, a.hy))) return r;
+    // the field-row kernels list whole tiles, BDOF_TILE_MAXLIST (tile, row) pairs at a time (any B): one tile alone must fit
+    if (shape == FIELD_GRID && (a.TX + a.FX - 1) / a.FX > BDOF_TILE_MAXLIST)
+        return fail(c, BDOF_ERR_SIZE, "a tile wraps onto one field row more often than a workgroup lists (TX <= 1024 FX)");
     HIPC(c, hipSetDevice(c->device));
     const dim3 grid = shape == TILE_GRID ? dim3((a.TY + 255) / 256, std::min(a.TX, 64), a.B) : dim3(std::min(a.FX, c->ncu * 8));
     hipLaunchKernelGGL(kernel, grid, dim3(256), 0, c->stream, a);

@@ -141,43 +141,52 @@ __global__ __launch_bounds__(256) void k_tiles_put(TileArgs<F, T> a) {
     }
 }
 // One workgroup per field row; it first lists the (tile, x) pairs that map onto its row, then every thread sums its columns
-// over the list in a fixed order (deterministic, no atomics).
+// over the list in a fixed order (deterministic, no atomics).  The list holds BDOF_TILE_MAXLIST pairs; a row with more is summed
+// in chunks of whole tiles, in ascending tile order: thread 0 lists from the resume index and publishes where the next chunk
+// starts, so the trip count is uniform across the workgroup; the first chunk honours `accumulate`, the later ones add to the
+// field.  Any B; up to the list limit that is one chunk.  (The host sees to it that one tile alone fits: ceil(TX / FX) pairs.)
 template <class F, class T>
 __global__ __launch_bounds__(256) void k_tiles_cut_adjoint(TileArgs<F, T> a) {
     using R = real_of<F>;
     __shared__ int lb[BDOF_TILE_MAXLIST], lx[BDOF_TILE_MAXLIST];
-    __shared__ int nlist;
+    __shared__ int nlist, resume;
     for (int xg = blockIdx.x; xg < a.FX; xg += gridDim.x) {
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            int n = 0;
-            for (int b = 0; b < a.B; ++b) {
-                // tile rows x with (x0[b] + x) mod FX == xg
-                int x = wrap_idx(xg - a.x0[b], a.FX);
-                for (; x < a.TX && n < BDOF_TILE_MAXLIST; x += a.FX) { lb[n] = b; lx[n] = x; ++n; }
-            }
-            nlist = n;
-        }
-        __syncthreads();
-        const int n = nlist;
-        for (int yg = threadIdx.x; yg < a.FY; yg += blockDim.x) {
-            R sx = 0, sy = 0;
-            for (int e = 0; e < n; ++e) {
-                const int b = lb[e], x = lx[e];
-                const R wx = taper_weight<R>(x, a.TX, a.taper);
-                for (int y = wrap_idx(yg - a.y0[b], a.FY); y < a.TY; y += a.FY) {
-                    const R w = wx * taper_weight<R>(y, a.TY, a.taper);
-                    const size_t o = ((size_t)b * a.TX + x) * a.TY + y;
-                    const T va = a.tiles_a[o];
-                    R dx = (R)va.x, dy = (R)va.y;
-                    if (a.tiles_b) { const T vb = a.tiles_b[o]; dx -= (R)vb.x; dy -= (R)vb.y; }
-                    sx = fma(w, dx, sx);
-                    sy = fma(w, dy, sy);
+        for (int b_next = 0; b_next < a.B;) {
+            const bool first = b_next == 0;
+            __syncthreads();
+            if (threadIdx.x == 0) {
+                int n = 0, b = b_next;
+                for (; b < a.B; ++b) {
+                    // tile rows x with (x0[b] + x) mod FX == xg
+                    int x = wrap_idx(xg - a.x0[b], a.FX);
+                    if (x < a.TX && n + (a.TX - 1 - x) / a.FX + 1 > BDOF_TILE_MAXLIST) break;      // the next chunk starts with this tile
+                    for (; x < a.TX; x += a.FX) { lb[n] = b; lx[n] = x; ++n; }
                 }
+                nlist = n;
+                resume = b;
             }
-            F* dst = a.field + (size_t)xg * a.FY + yg;
-            if (a.accumulate) { sx += dst->x; sy += dst->y; }
-            *dst = make_c<F>(sx, sy);
+            __syncthreads();
+            const int n = nlist;
+            b_next = resume;
+            for (int yg = threadIdx.x; yg < a.FY; yg += blockDim.x) {
+                R sx = 0, sy = 0;
+                for (int e = 0; e < n; ++e) {
+                    const int b = lb[e], x = lx[e];
+                    const R wx = taper_weight<R>(x, a.TX, a.taper);
+                    for (int y = wrap_idx(yg - a.y0[b], a.FY); y < a.TY; y += a.FY) {
+                        const R w = wx * taper_weight<R>(y, a.TY, a.taper);
+                        const size_t o = ((size_t)b * a.TX + x) * a.TY + y;
+                        const T va = a.tiles_a[o];
+                        R dx = (R)va.x, dy = (R)va.y;
+                        if (a.tiles_b) { const T vb = a.tiles_b[o]; dx -= (R)vb.x; dy -= (R)vb.y; }
+                        sx = fma(w, dx, sx);
+                        sy = fma(w, dy, sy);
+                    }
+                }
+                F* dst = a.field + (size_t)xg * a.FY + yg;
+                if (a.accumulate || !first) { sx += dst->x; sy += dst->y; }
+                *dst = make_c<F>(sx, sy);
+            }
         }
     }
 }

@@ -986,7 +986,7 @@ __global__ __launch_bounds__(256) void k_adam(AdamArgs a) {
 // ---------------------------------------------------------------------------------------------
 // Tiled ("pfft") propagation: the tile family (cut, put and their adjoints) is in bdof_field.h; here, the object gradient.
 // ---------------------------------------------------------------------------------------------
-#define BDOF_TILE_MAXLIST 1024      // (tile, row) pairs a workgroup lists for its field row / volume column (also bdof_field.h)
+#define BDOF_TILE_MAXLIST 1024      // (tile, row) pairs a workgroup lists AT A TIME for its field row / volume column (also bdof_field.h)
 // Object gradient of a slice range of the tiled propagation: the window-frame gradient rows grot[b][z - z0][x][y] of every
 // tile are added into the volume gradient rows gvol[tab[z][xg]][yg], xg = x0[b] + x, yg = y0[b] + y (the object is not
 // periodic: tile pixels beyond the volume saw vacuum and contribute nothing).  One workgroup per volume column xg; a thread
@@ -1002,64 +1002,72 @@ struct TileGradArgs {
 };
 __global__ __launch_bounds__(256) void k_tiles_grad_add(TileGradArgs a) {
     __shared__ int lb[BDOF_TILE_MAXLIST];
-    __shared__ int nlist;
+    __shared__ int nlist, resume;
     for (int xg = blockIdx.x; xg < a.volNX; xg += gridDim.x) {
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            int n = 0;
-            for (int b = 0; b < a.B && n < BDOF_TILE_MAXLIST; ++b) {
-                const int x = xg - a.x0[b];
-                if (x >= 0 && x < a.TX) lb[n++] = b;
-            }
-            nlist = n;
-        }
-        __syncthreads();
-        const int n = nlist;
-        for (int yg = threadIdx.x; yg < a.volNY; yg += blockDim.x) {
-            // the tiles that cover (xg, yg): found once, outside the slice loop (a handful: (T / core)^2)
-            constexpr int MAXM = 9;
-            size_t moff[MAXM];
-            int nm = 0, spill_from = n;
-            for (int e = 0; e < n; ++e) {
-                const int b = lb[e];
-                const int y = yg - a.y0[b];
-                if (y < 0 || y >= a.TY) continue;
-                if (nm == MAXM) { spill_from = e; break; }
-                moff[nm++] = (((size_t)b * a.nz) * a.TX + (xg - a.x0[b])) * a.TY + y;
-            }
-            const size_t zstride = (size_t)a.TX * a.TY;
-            int cur = -1;
-            float2 acc = make_float2(0.f, 0.f);
-            for (int zr = 0; zr < a.nz; ++zr) {
-                const int dest = a.tab[(size_t)(a.z0 + zr) * a.volNX + xg];
-                if (dest != cur) {
-                    if (cur >= 0) {
-                        float2* d = a.gvol + (size_t)cur * a.volNY + yg;
-                        *d = make_float2(d->x + acc.x, d->y + acc.y);
-                    }
-                    cur = dest;
-                    acc = make_float2(0.f, 0.f);
+        // the tiles covering xg, in ascending order, BDOF_TILE_MAXLIST at a time: thread 0 lists from the resume index and publishes
+        // where the next chunk starts, so the trip count is uniform across the workgroup (any B; up to the list limit, one chunk)
+        for (int b_next = 0; b_next < a.B;) {
+            __syncthreads();
+            if (threadIdx.x == 0) {
+                int n = 0, b = b_next;
+                for (; b < a.B; ++b) {
+                    const int x = xg - a.x0[b];
+                    if (x < 0 || x >= a.TX) continue;
+                    if (n == BDOF_TILE_MAXLIST) break;          // the next chunk starts with this tile
+                    lb[n++] = b;
                 }
+                nlist = n;
+                resume = b;
+            }
+            __syncthreads();
+            const int n = nlist;
+            b_next = resume;
+            for (int yg = threadIdx.x; yg < a.volNY; yg += blockDim.x) {
+                // the tiles that cover (xg, yg): found once, outside the slice loop (a handful: (T / core)^2)
+                constexpr int MAXM = 9;
+                size_t moff[MAXM];
+                int nm = 0, spill_from = n;
+                for (int e = 0; e < n; ++e) {
+                    const int b = lb[e];
+                    const int y = yg - a.y0[b];
+                    if (y < 0 || y >= a.TY) continue;
+                    if (nm == MAXM) { spill_from = e; break; }
+                    moff[nm++] = (((size_t)b * a.nz) * a.TX + (xg - a.x0[b])) * a.TY + y;
+                }
+                const size_t zstride = (size_t)a.TX * a.TY;
+                int cur = -1;
+                float2 acc = make_float2(0.f, 0.f);
+                for (int zr = 0; zr < a.nz; ++zr) {
+                    const int dest = a.tab[(size_t)(a.z0 + zr) * a.volNX + xg];
+                    if (dest != cur) {
+                        if (cur >= 0) {
+                            float2* d = a.gvol + (size_t)cur * a.volNY + yg;
+                            *d = make_float2(d->x + acc.x, d->y + acc.y);
+                        }
+                        cur = dest;
+                        acc = make_float2(0.f, 0.f);
+                    }
 #pragma unroll
-                for (int m = 0; m < MAXM; ++m) {
-                    if (m < nm) {
-                        const float2 g = a.grot[moff[m] + zr * zstride];
+                    for (int m = 0; m < MAXM; ++m) {
+                        if (m < nm) {
+                            const float2 g = a.grot[moff[m] + zr * zstride];
+                            acc.x += g.x;
+                            acc.y += g.y;
+                        }
+                    }
+                    for (int e = spill_from; e < n; ++e) {          // more than MAXM covering tiles (very large halos)
+                        const int b = lb[e];
+                        const int y = yg - a.y0[b];
+                        if (y < 0 || y >= a.TY) continue;
+                        const float2 g = a.grot[(((size_t)b * a.nz + zr) * a.TX + (xg - a.x0[b])) * a.TY + y];
                         acc.x += g.x;
                         acc.y += g.y;
                     }
                 }
-                for (int e = spill_from; e < n; ++e) {          // more than MAXM covering tiles (very large halos)
-                    const int b = lb[e];
-                    const int y = yg - a.y0[b];
-                    if (y < 0 || y >= a.TY) continue;
-                    const float2 g = a.grot[(((size_t)b * a.nz + zr) * a.TX + (xg - a.x0[b])) * a.TY + y];
-                    acc.x += g.x;
-                    acc.y += g.y;
+                if (cur >= 0) {
+                    float2* d = a.gvol + (size_t)cur * a.volNY + yg;
+                    *d = make_float2(d->x + acc.x, d->y + acc.y);
                 }
-            }
-            if (cur >= 0) {
-                float2* d = a.gvol + (size_t)cur * a.volNY + yg;
-                *d = make_float2(d->x + acc.x, d->y + acc.y);
             }
         }
     }

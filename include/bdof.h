@@ -156,6 +156,9 @@ int bdof_tiles_scatter(bdof_ctx* ctx, const void* tiles, void* field, int FX, in
  * bdof_tiles_scatter_adjoint / bdof_tiles_gather_adjoint: adjoints of the two stitching steps; bdof_tiles_grad_add: the
  * range's gradient rows added into the volume gradient gvol (rows of volNY pairs, the object's own layout) through the table
  * of bdof_set_object — which must be injective in x for every slice (no rotation: the tiled path runs one pre-rotated object).
+ * bdof_tiles_gather_adjoint (and bdof_tiles_gather_adjoint_diff64) and bdof_tiles_grad_add take any number of tiles B, however
+ * many of them meet on one field row or volume column: the kernels sum them in ascending tile order, 1024 (tile, row) pairs at
+ * a time.  Only a single tile that wraps onto one field row more than 1024 times (TX > 1024 FX) is refused, BDOF_ERR_SIZE (-3).
  * bdof_field_loss_seed: loss mean((|field| - meas)^2) (bdof_get_loss) and, in place, its seed — fullfield.py:106 on a field. */
 int bdof_adjoint_range(bdof_ctx* ctx, int B, const int* angle_of_b, const int* xoff, const int* yoff, int z0, int nz,
                        const void* end_real, const void* g_end_real, void* g_start_real, void* grot_range);
