@@ -33,6 +33,7 @@ _SIGNATURES = {
     'bdof_timer_mark': (ctypes.c_int, [_vp, ctypes.c_int]),
     'bdof_timer_elapsed': (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_double)]),
     'bdof_configure': (ctypes.c_int, [_vp] + [ctypes.c_int] * 5),
+    'bdof_set_slice_binning': (ctypes.c_int, [_vp, ctypes.c_int]),
     'bdof_set_physics': (ctypes.c_int, [_vp, ctypes.c_double, _vp, _vp, _vp, _vp, ctypes.c_int, ctypes.c_int]),
     'bdof_set_physics_f64': (ctypes.c_int, [_vp, _vp, _vp]),
     'bdof_set_probe': (ctypes.c_int, [_vp, _vp, ctypes.c_double, ctypes.c_double]),

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../../include/bdof.h"
+#include "bdof_steps.h"
 #include "bdof_kernels.h"
 #include "bdof_conv2.h"
 #include "bdof_generic.h"
@@ -88,6 +89,7 @@ struct Workspace {
     DevBuf<cf> hs_d;               // bdof_set_transfer_f64: hs_copies dithered float32 copies of the slice step's table (bdof_field.h)
     int hs_copies = 0;
     DevBuf<cf> bufA, bufB, tape;
+    int bin = 1;                   // bdof_set_slice_binning: voxel slices per propagation step (1 after every bdof_configure)
     DevBuf<float2> grot;
     DevBuf<double2> gcar, gt0;                   // adjoint carrier per wavefield (AdjCarrier, bdof_kernels.h)
     DevBuf<cf> gpsi0;                            // [Bmax][NX][NY] G(psi_0) per wavefield (bdof_enable_probe_grad)
@@ -227,6 +229,13 @@ static int check_range(bdof_ctx* c, int z0, int nz) {
 static int need_lsq(bdof_ctx* c, const char* who) {
     return c->loss_kind == BDOF_LOSS_LSQ ? 0 : fail(c, BDOF_ERR_STATE, std::string(who) + " computes the least-squares loss only: bdof_set_loss(BDOF_LOSS_LSQ) first");
 }
+// the entry points that take one propagation step per voxel slice only (bdof_set_slice_binning names them)
+static int need_unbinned(bdof_ctx* c, const char* who) {
+    return !c || c->bin == 1 ? 0 : fail(c, BDOF_ERR_STATE, std::string(who) + " does not carry slice binning: it would run the unbinned model (bdof_set_slice_binning)");
+}
+// propagation steps of a sweep: the voxel depth over the slice binning
+static StepIndex steps(const bdof_ctx* c) { return StepIndex{c->S, c->bin}; }
+static int n_steps(const bdof_ctx* c) { return steps(c).n(); }
 static bool loss_is_poisson(const bdof_ctx* c) { return c->loss_kind == BDOF_LOSS_POISSON; }
 static int check_taper(bdof_ctx* c, int TX, int TY, int taper) {
     return taper < 0 || 2 * taper > TX || 2 * taper > TY ? fail(c, BDOF_ERR_ARG, "taper must fit the tile") : 0;
@@ -236,7 +245,8 @@ static int check_halo(bdof_ctx* c, int TX, int TY, int halo_x, int halo_y) {
 }
 
 // Mean-refraction carrier (modulate_eps_s): constant part of the wave entering slice z, a_z = a_0 (cbar H00)^z
-// (H00 = DC value of the transfer function, cbar = mean modulation factor of the object)
+// (H00 = DC value of the transfer function, cbar = mean modulation factor of the object).  With slice binning z counts
+// propagation steps, cbar is that of a bin (modulation_done) and H00 that of the bin's step.
 static std::complex<double> carrier_z(const bdof_ctx* c, int z) { return c->a0 * std::pow((1.0 + c->cbm1) * c->h00, z); }
 static cf cfl(std::complex<double> a) { return make_float2((float)a.real(), (float)a.imag()); }
 static cf carrier_at(const bdof_ctx* c, int z) { return cfl(carrier_z(c, z)); }
@@ -244,7 +254,7 @@ static cf cshift_at(const bdof_ctx* c, int z) { return cfl(carrier_z(c, z) * c->
 static cf carrier_phi_at(const bdof_ctx* c, int z) { return cfl(carrier_z(c, z) * (1.0 + c->cbm1)); }      // constant part of phi_z
 // constant part of the detector wave (real-space detectors) / of the wave whose fft2 is the far field
 static std::complex<double> carrier_end(const bdof_ctx* c) {
-    std::complex<double> a = carrier_z(c, c->S - 1) * (1.0 + c->cbm1);
+    std::complex<double> a = carrier_z(c, n_steps(c) - 1) * (1.0 + c->cbm1);
     if (c->det_mode != BDOF_DET_FAR && c->variant == BDOF_VARIANT_TF_ALL) a *= c->h00;
     if (c->det_mode == BDOF_DET_NEAR) a *= c->hdet00;
     return a;
@@ -529,7 +539,9 @@ static void launch_row_fwd(bdof_ctx* c, int B, int z, const cf* in, cf* out, boo
     }
     c->tw_tick = (unsigned)z;
     DISPATCH_N(c->NY, with_bool(z == 0 || start, [&](auto FIRST) { with_bool(tstore, [&](auto TSTORE) { with_bool(a.pz != nullptr, [&](auto PF) {
-        BDOF_LAUNCH(ps, (k_row_fwd<N_, FIRST, TSTORE, PF>), dim3(rows_grid<N_>(c, B, c->NX)), dim3(BDOF_THREADS), 0, c->sub_stream, a);
+        with_bool(c->bin > 1, [&](auto BIN) {
+            BDOF_LAUNCH(ps, (k_row_fwd<N_, FIRST, TSTORE, PF, false, BIN>), dim3(rows_grid<N_>(c, B, c->NX)), dim3(BDOF_THREADS), 0, c->sub_stream, a);
+        });
     }); }); }));
 }
 
@@ -577,13 +589,19 @@ static void launch_row_bwd(bdof_ctx* c, int B, int z, const cf* gin, const cf* t
     float2* grot = gt && gt->grot ? gt->grot + (size_t)c->sub_b0 * gt->S_ * c->NX * c->NY : c->grot + (size_t)c->sub_b0 * c->S * c->NX * c->NY;
     RowBwdArgs a{sub_field(c, gin), hist == 2 ? c->probe : sub_field(c, tape), sub_field(c, gout),
                  grot, sub_obj(c), B, c->NX, z, c->k, carrier_at(c, z), tw_of(c, c->twY, c->NY, (unsigned)z),
-                 slice_carrier_field(c, z), adj_carrier_at(c, c->S - 1 - z), cshift_at(c, z), carrier_phi_at(c, z), tape_scale,
+                 slice_carrier_field(c, z), adj_carrier_at(c, steps(c).steps_back(z)), cshift_at(c, z), carrier_phi_at(c, z), tape_scale,
                  gt && gt->gpsi ? sub_field(c, gt->gpsi) : (z == 0 && c->gpsi0 ? c->gpsi0 + (size_t)c->sub_b0 * c->NX * c->NY : nullptr),
-                 gt && gt->grot ? gt->S_ : c->S, gt && gt->grot ? gt->z_ : z};
+                 gt && gt->grot ? gt->S_ : c->S, gt && gt->grot ? gt->z_ : steps(c).first_slice(z)};
     sq_of(c, (unsigned)z, a.sq);
     c->tw_tick = (unsigned)z;
     // carrier form: 0 scalar, 1 field (PF), 2 far field + plane-wave carrier (GC; never together with a carrier field)
     const int form = a.ac.gcar ? 2 : a.pz ? 1 : 0;
+    if (c->bin > 1) {            // slice binning: the history-mode sweep's two forms (HIST 1, and 2 at step 0) — the only ones it launches
+        DISPATCH_N(c->NY, with_bool(hist == 2, [&](auto H2) { with_int<3>(form, [&](auto FORM) {
+            BDOF_LAUNCH(ps, (k_row_bwd<N_, H2 ? 2 : 1, FORM == 1, FORM == 2, true>), dim3(rows_grid<N_>(c, B, c->NX)), dim3(BDOF_THREADS), 0, c->sub_stream, a);
+        }); }));
+        return;
+    }
     DISPATCH_N(c->NY, with_int<4>(hist, [&](auto HIST) { with_int<3>(form, [&](auto FORM) {
         BDOF_LAUNCH(ps, (k_row_bwd<N_, HIST, FORM == 1, FORM == 2>), dim3(rows_grid<N_>(c, B, c->NX)), dim3(BDOF_THREADS), 0, c->sub_stream, a);
     }); }));
@@ -647,17 +665,18 @@ enum { TAPE_NONE = 0, TAPE_HISTORY = 1, TAPE_LAST = 2 };
 static void forward_sweep(bdof_ctx* c, const Group* groups, int ngroups, int tape_mode) {
     const size_t fld = (size_t)c->Bmax * c->NX * c->NY;
     const bool tf_all = c->variant == BDOF_VARIANT_TF_ALL;
-    for (int z = 0; z < c->S; ++z) {
+    const int nz = n_steps(c);
+    for (int z = 0; z < nz; ++z) {
         const cf* in = nullptr;
-        if (z > 0) in = tape_mode == TAPE_HISTORY ? c->tape + (size_t)(z - 1) * fld : c->bufB;
-        const bool last = z == c->S - 1;
+        if (z > 0) in = tape_mode == TAPE_HISTORY ? c->tape + (size_t)steps(c).tape_read(z) * fld : c->bufB;
+        const bool last = z == nz - 1;
         cf* phi = tape_mode == TAPE_LAST && last ? c->tape : nullptr;
         for (int gi = 0; gi < ngroups; ++gi) {
             const int B = groups[gi].B;
             use_group(c, groups[gi]);
             if (!last) {
                 launch_row_fwd(c, B, z, in, c->bufA, true, phi);
-                launch_row_prop(c, B, c->bufA, tape_mode == TAPE_HISTORY ? c->tape + (size_t)z * fld : c->bufB, c->hs, 1.f, 0);
+                launch_row_prop(c, B, c->bufA, tape_mode == TAPE_HISTORY ? c->tape + (size_t)steps(c).tape_write(z) * fld : c->bufB, c->hs, 1.f, 0);
             } else if (c->det_mode == BDOF_DET_NONE && !tf_all) {
                 launch_row_fwd(c, B, z, in, c->bufA, false, phi);
             } else {
@@ -687,6 +706,8 @@ static int modulation_done(bdof_ctx* c, size_t n, int grid, bool mean) {
         HIPC(c, hipMemcpyAsync(&m, c->cbar_dev + grid, sizeof(double2), hipMemcpyDeviceToHost, c->stream));
         HIPC(c, hipStreamSynchronize(c->stream));
         cb = std::complex<double>(m.x, m.y);
+        // slice binning: a step's carrier picks up the mean factor of its whole bin, cbar^bin (exact algebra for any cbar)
+        if (c->bin > 1) cb = std::pow(1.0 + cb, c->bin) - 1.0;
     }
     if (cb != c->cbm1) { c->cbm1 = cb; c->res_dirty = true; }
     c->obj.vol = c->mod;
@@ -789,16 +810,17 @@ static int generic_forward_sweep(bdof_ctx* c, int B, bool tape, rocfft_plan pf, 
     const bool tf_all = c->variant == BDOF_VARIANT_TF_ALL;
     std::complex<double> a = c->a0;
     int r;
-    for (int z = 0; z < c->S; ++z) {
+    const int nz = n_steps(c);
+    for (int z = 0; z < nz; ++z) {
         {
             ProfScope ps(c, BDOF_K_ROW_FWD);
             GModArgs m{c->bufA, z == 0 ? c->probe : nullptr, tape ? c->tape + (size_t)z * fld : nullptr, c->obj, B, c->NX, c->NY, z,
                        make_float2((float)a.real(), (float)a.imag()), c->pstack ? c->pstack + (size_t)z * c->NX * c->NY : nullptr,
                        cfl(a * c->cbm1)};
-            hipLaunchKernelGGL(k_g_modulate, dim3(g_elem_grid(c, n)), dim3(256), 0, c->stream, m);
+            with_bool(c->bin > 1, [&](auto BIN) { hipLaunchKernelGGL(k_g_modulate<BIN>, dim3(g_elem_grid(c, n)), dim3(256), 0, c->stream, m); });
             a *= 1.0 + c->cbm1;                  // mean-refraction carrier: phi_z rides on cbar a_z
         }
-        const bool last = z == c->S - 1;
+        const bool last = z == nz - 1;
         if (!last || (tf_all && c->det_mode != BDOF_DET_FAR)) {
             if ((r = generic_prop(c, B, pf, pi, c->bufA, hs_slice(c, z), 0))) return r;      // the slice's dithered copy of H
             a *= c->h00;
@@ -899,13 +921,14 @@ static int generic_loss_grad(bdof_ctx* c, int B, const float* meas, void* out_wa
     } else if (c->det_mode == BDOF_DET_FAR) {
         RFC(c, rocfft_execute(pi, buf, nullptr, c->fft.info));            // F^H = unnormalised inverse
     }
-    for (int z = c->S - 1; z >= 0; --z) {
-        const bool prop_after = z < c->S - 1 || (tf_all && c->det_mode != BDOF_DET_FAR);
+    const int nz = n_steps(c);
+    for (int z = nz - 1; z >= 0; --z) {
+        const bool prop_after = z < nz - 1 || (tf_all && c->det_mode != BDOF_DET_FAR);
         if (prop_after && (r = generic_prop(c, B, pf, pi, c->bufA, hs_slice(c, z), 1))) return r;      // conj of the forward step's copy
         ProfScope ps(c, BDOF_K_ROW_BWD);
         GBwdArgs ba{c->bufA, c->tape + (size_t)z * fld, c->grot, c->obj, B, c->NX, c->NY, z, c->k, carrier_phi_at(c, z), c->pstack ? 1 : 0,
-                    adj_carrier_at(c, c->S - 1 - z)};
-        hipLaunchKernelGGL(k_g_bwd, dim3(egrid), dim3(256), 0, c->stream, ba);
+                    adj_carrier_at(c, steps(c).steps_back(z))};
+        with_bool(c->bin > 1, [&](auto BIN) { hipLaunchKernelGGL(k_g_bwd<BIN>, dim3(egrid), dim3(256), 0, c->stream, ba); });
     }
     return 0;
 }
@@ -936,7 +959,7 @@ template <int N> static int resident_launch(bdof_ctx* c, const ResArgs& a, int g
 // batch fills a good part of the chip (measured at 64^2 / 128^2: 400 / 100 wavefields 4.6x / 1.5x faster, 25 slower);
 // sizes without a fused plan always take it (the alternative is the unfused rocFFT engine).
 static bool use_resident(const bdof_ctx* c, int B) {
-    if (!c->resident || c->recompute) return false;
+    if (!c->resident || c->recompute || c->bin > 1) return false;      // slice binning: the streaming and generic engines only
     // far field + plane-wave carrier needs the adjoint carrier (AdjCarrier), which the resident kernel does not carry: the
     // streaming / generic engines take that case (plane-wave full-field at a resident-plan size)
     if (c->det_mode == BDOF_DET_FAR && !c->pstack && std::abs(c->a0) > 0.0) return false;
@@ -1173,6 +1196,7 @@ int bdof_configure(bdof_ctx* c, int NY, int NX, int S, int Bmax, int with_grad) 
     HIPC(c, hipStreamSynchronize(c->stream));
     static_cast<Workspace&>(*c) = Workspace{};       // the previous configuration's buffers, plans and flags go before the new ones come
     c->NY = NY; c->NX = NX; c->S = S; c->Bmax = Bmax; c->with_grad = (with_grad & BDOF_CFG_GRAD) != 0;
+    c->obj.bin = 1;                                  // slice binning is not sticky: bdof_set_slice_binning follows, or there is none
     c->generic = generic;
     // dithered transform constants (bdof_fft.h): 64 copies of each table by default, BDOF_TW_DITHER=0 for one plain table
     { const char* e = std::getenv("BDOF_TW_DITHER"); c->tw_dither = e ? std::max(0, std::min(256, atoi(e))) : 64; if (c->tw_dither == 1) c->tw_dither = 0; }
@@ -1221,6 +1245,26 @@ int bdof_configure(bdof_ctx* c, int NY, int NX, int S, int Bmax, int with_grad) 
     HIPC(c, c->partial.alloc((size_t)2 * c->npartial * (c->resident ? 16 : 1)));
     HIPC(c, c->loss_dev.alloc(1));
     HIPC(c, hipMemsetAsync(c->loss_dev, 0, sizeof(double), c->stream));
+    return 0;
+}
+
+int bdof_set_slice_binning(bdof_ctx* c, int bin) {
+    if (!c) return BDOF_ERR_ARG;
+    if (int r = need_configured(c)) return r;
+    if (!StepIndex::valid(c->S, bin)) return fail(c, BDOF_ERR_ARG, "bdof_set_slice_binning: bin must be >= 1 and divide S (a shorter last bin is not carried)");
+    if (c->have_physics || c->have_probe)
+        return fail(c, BDOF_ERR_STATE, "bdof_set_slice_binning comes right after bdof_configure: the tables of bdof_set_physics and the carrier fields are per propagation step");
+    if (bin > 1) {
+        const char* why = c->res_always ? "the LDS-resident engine (BDOF_CFG_ALWAYS_RESIDENT)" : c->recompute ? "the tape-free adjoint (BDOF_CFG_RECOMPUTE)"
+                        : c->adj64 ? "the float64 adjoint sweep (BDOF_CFG_ADJOINT64)" : c->with_grad && !c->grot ? "a ctx without the gradient workspace (BDOF_CFG_NO_GROT)" : nullptr;
+        if (why) return fail(c, BDOF_ERR_STATE, std::string("bdof_set_slice_binning: ") + why + " does not carry slice binning");
+    }
+    HIPC(c, hipSetDevice(c->device));
+    HIPC(c, hipStreamSynchronize(c->stream));
+    if (c->with_grad && bin != c->bin) HIPC(c, c->tape.alloc((size_t)c->Bmax * c->NX * c->NY * StepIndex{c->S, bin}.tape_fields()));     // one field per step
+    c->bin = c->obj.bin = bin;
+    c->mod_dirty = c->res_dirty = true;
+    c->tape_valid = c->last_valid = false;
     return 0;
 }
 
@@ -1381,9 +1425,9 @@ int bdof_set_probe_stack(bdof_ctx* c, const float* stack, const float* det) {
     if (!stack && !det) return 0;
     if (!stack || !det) return fail(c, BDOF_ERR_ARG, "bdof_set_probe_stack: both arrays or neither");
     const size_t n = (size_t)c->NX * c->NY, fld = sizeof(cf) * n;
-    HIPC(c, c->pstack.alloc(n * (size_t)c->S));
+    HIPC(c, c->pstack.alloc(n * steps(c).stack_planes()));       // one plane per propagation step
     HIPC(c, c->pdet.alloc(n));
-    HIPC(c, hipMemcpy(c->pstack, stack, fld * (size_t)c->S, hipMemcpyHostToDevice));
+    HIPC(c, hipMemcpy(c->pstack, stack, fld * (size_t)n_steps(c), hipMemcpyHostToDevice));
     HIPC(c, hipMemcpy(c->pdet, det, fld, hipMemcpyHostToDevice));
     // the streaming far-field detector works on rows [ky][kx]: the same field transposed
     std::vector<float> t((size_t)2 * c->NX * c->NY);
@@ -1422,7 +1466,8 @@ int bdof_set_probe_field(bdof_ctx* c, const double* probe, const double* hT, con
     }
     c->pstack.reset(); c->pdet.reset(); c->pdetT.reset();
     c->pdet64.reset(); c->pdetT64.reset();
-    HIPC(c, c->pstack.alloc(n * (size_t)c->S));
+    const int nz = n_steps(c);                                   // one plane per propagation step (hT: the step's own table)
+    HIPC(c, c->pstack.alloc(n * (size_t)nz));
     HIPC(c, c->pdet.alloc(n));
     HIPC(c, c->pdetT.alloc(n));
     HIPC(c, c->pdet64.alloc(n));
@@ -1435,9 +1480,9 @@ int bdof_set_probe_field(bdof_ctx* c, const double* probe, const double* hT, con
         if (rocfft_execute(pi, buf, nullptr, c->fft.info) != rocfft_status_success) return fail(c, BDOF_ERR_STATE, "rocfft_execute (double) failed");
         return 0;
     };
-    for (int z = 0; z < c->S; ++z) {
+    for (int z = 0; z < nz; ++z) {
         hipLaunchKernelGGL(k_d_to_f, dim3(grid), dim3(256), 0, c->stream, dp, c->pstack + (size_t)z * n, c->NX, c->NY, 0);
-        if (z < c->S - 1 && (r = step(dh))) return r;
+        if (z < nz - 1 && (r = step(dh))) return r;
     }
     if (c->det_mode == BDOF_DET_FAR) {
         if (rocfft_execute(pf, buf, nullptr, c->fft.info) != rocfft_status_success) return fail(c, BDOF_ERR_STATE, "rocfft_execute (double) failed");
@@ -1476,6 +1521,7 @@ int bdof_set_object(bdof_ctx* c, const void* vol, long long n_rows, int volNY, c
     c->obj.tab = tab;
     c->obj.volNX = tab ? volNX : c->NX;
     c->obj.S = c->S;
+    c->obj.bin = c->bin;
     c->n_angles = tab ? n_angles : 0;
     return 0;
 }
@@ -1542,8 +1588,9 @@ int bdof_forward(bdof_ctx* c, int B, const int* angle_of_b, const int* xoff, con
         // probe_array[S-1] = phi_{S-1} (np_funcs.py:41-43): keep R phi_{S-1} in L1 order in bufA
         if (!(c->det_mode == BDOF_DET_NONE)) {
             const size_t fld = (size_t)c->Bmax * c->NX * c->NY;
-            const cf* in = c->S > 1 ? c->tape + (size_t)(c->S - 2) * fld : nullptr;   // psi_hat_{S-1}
-            launch_row_fwd(c, B, c->S - 1, in, c->bufA, false);
+            const int nz = n_steps(c);
+            const cf* in = nz > 1 ? c->tape + (size_t)(nz - 2) * fld : nullptr;   // psi_hat_{S-1}
+            launch_row_fwd(c, B, nz - 1, in, c->bufA, false);
         }
         c->last_valid = true;
     }
@@ -1552,6 +1599,7 @@ int bdof_forward(bdof_ctx* c, int B, const int* angle_of_b, const int* xoff, con
 
 int bdof_forward_range(bdof_ctx* c, int B, const int* angle_of_b, const int* xoff, const int* yoff, int z0, int nz,
                        const void* in_real, void* out_real, int prop_last) {
+    if (int rb = need_unbinned(c, "bdof_forward_range")) return rb;
     int r = check_ready(c, B);
     if (r) return r;
     if (!in_real || !out_real) return BDOF_ERR_ARG;
@@ -1602,6 +1650,7 @@ int bdof_forward_range(bdof_ctx* c, int B, const int* angle_of_b, const int* xof
 // carrier IS the incoming wave) and `out_real` receives the scattered part leaving it — for the tiles of a corrected stitch range
 // exactly T psi - T_free psi, without the round-off of two full-amplitude sweeps.  NULL removes the stack.
 int bdof_set_range_carrier(bdof_ctx* c, const void* stack, int B, int z0, int nz) {
+    if (int rb = need_unbinned(c, "bdof_set_range_carrier")) return rb;
     if (!c) return BDOF_ERR_ARG;
     if (!stack) { c->range_car = nullptr; c->range_car_B = 0; return 0; }
     if (int r = need_configured(c)) return r;
@@ -1616,6 +1665,7 @@ int bdof_set_range_carrier(bdof_ctx* c, const void* stack, int B, int z0, int nz
 
 int bdof_forward_range_h(bdof_ctx* c, int B, const int* angle_of_b, const int* xoff, const int* yoff, int z0, int nz,
                          const void* in_real, void* out_real, int prop_last, const void* h) {
+    if (int rb = need_unbinned(c, "bdof_forward_range_h")) return rb;
     if (!c || !h) return BDOF_ERR_ARG;
     c->hs_override = (const cf*)h;
     const int r = bdof_forward_range(c, B, angle_of_b, xoff, yoff, z0, nz, in_real, out_real, prop_last);
@@ -1628,6 +1678,7 @@ int bdof_forward_range_h(bdof_ctx* c, int B, const int* angle_of_b, const int* x
 // g_start_real receives G(psi_{z0}); the gradient rows of the range go to grot_range [B][nz][NX][NY] (pairs).
 int bdof_adjoint_range(bdof_ctx* c, int B, const int* angle_of_b, const int* xoff, const int* yoff, int z0, int nz,
                        const void* end_real, const void* g_end_real, void* g_start_real, void* grot_range) {
+    if (int rb = need_unbinned(c, "bdof_adjoint_range")) return rb;
     int r = check_ready(c, B);
     if (r) return r;
     if (!end_real || !g_end_real || !g_start_real || !grot_range) return BDOF_ERR_ARG;
@@ -1788,6 +1839,7 @@ int bdof_fields_free_step_aux(bdof_ctx* c, void* fields, const void* src, int B,
 // spectra s_hat H^z by a running product, ONE batched inverse transform of all of them, one conversion.  h: complex128 [kx][ky],
 // ifftshift(H) / (NX NY).
 int bdof_range_carrier_build(bdof_ctx* c, void* p0, void* stack, int B, int NX, int NY, const void* h, int nz) {
+    if (int rb = need_unbinned(c, "bdof_range_carrier_build")) return rb;
     if (!c || !p0 || !stack || !h || B < 1 || NX < 1 || NY < 1 || nz < 1) return BDOF_ERR_ARG;
     HIPC(c, hipSetDevice(c->device));
     const size_t per = (size_t)NX * NY, n = per * B;
@@ -1888,6 +1940,7 @@ int bdof_tiles_scatter_diff64(bdof_ctx* c, const void* tiles_a, const void* tile
 // rocFFT in double precision, h[kx][ky] = the transfer function / (NX NY) in float64.  cnn_propagator/np_funcs.py:36-43.
 int bdof_forward_range_f64(bdof_ctx* c, int B, const int* angle_of_b, const int* xoff, const int* yoff, int z0, int nz, void* fields,
                            const void* h, double k, int prop_last) {
+    if (int rb = need_unbinned(c, "bdof_forward_range_f64")) return rb;
     if (!c || !fields || !h) return BDOF_ERR_ARG;
     if (int r = need_configured(c)) return r;
     if (!c->obj_src) return fail(c, BDOF_ERR_STATE, "bdof_set_object (with (delta, beta) rows) has not been called");
@@ -1937,6 +1990,7 @@ static int c64_room(bdof_ctx* c, int B, bool tf, size_t M) {
 // kernel zero-padded to M x M, transposed to [kx][ky] and divided by M^2; ksum = sum of the kernel's taps (the padding constant's
 // recursion, propagation.py:91,99); k = 2 pi dz / lambda with numpy's pi (propagation.py:25)
 int bdof_set_conv_f64(bdof_ctx* c, const double* probe, const double* khat, int ks, double ksum_re, double ksum_im, double k) {
+    if (int rb = need_unbinned(c, "bdof_set_conv_f64")) return rb;
     if (!c || !probe || !khat) return BDOF_ERR_ARG;
     if (int r = need_configured(c)) return r;
     if (c->NX != c->NY) return fail(c, BDOF_ERR_SIZE, "the float64 real-space path takes square wavefields");
@@ -1964,6 +2018,7 @@ int bdof_set_conv_f64(bdof_ctx* c, const double* probe, const double* khat, int 
 // the step to a detector at a finite distance for the float64 real-space path (propagation.py:122-127: one transfer-function
 // step of the renormalised exit wave): hdetT host complex128 [kx][ky], ifftshift(H_det) / (NX NY); NULL removes it
 int bdof_set_conv_f64_detector(bdof_ctx* c, const double* hdetT) {
+    if (int rb = need_unbinned(c, "bdof_set_conv_f64_detector")) return rb;
     if (!c) return BDOF_ERR_ARG;
     if (int r = need_configured(c)) return r;
     HIPC(c, hipSetDevice(c->device));
@@ -1981,6 +2036,7 @@ int bdof_set_conv_f64_detector(bdof_ctx* c, const double* hdetT) {
 // the host subtracted from the amplitudes (bdof_set_meas_mode 1), 0 otherwise.  Detector: none, far field, or near field after
 // bdof_set_conv_f64_detector.
 int bdof_loss_grad_conv_f64(bdof_ctx* c, int B, const int* angle_of_b, const int* xoff, const int* yoff, const float* meas, double meas_ref) {
+    if (int rb = need_unbinned(c, "bdof_loss_grad_conv_f64")) return rb;
     if (!c || !meas) return BDOF_ERR_ARG;
     if (!c->c64_ks || c->c64_tf) return fail(c, BDOF_ERR_STATE, "bdof_set_conv_f64 has not been called");
     if (int rl = need_lsq(c, "bdof_loss_grad_conv_f64")) return rl;
@@ -2048,6 +2104,7 @@ int bdof_loss_grad_conv_f64(bdof_ctx* c, int B, const int* angle_of_b, const int
 // probe: host complex128 [NX][NY]; hT / hdetT (nullable: no near-field detector step): host complex128 [kx][ky], the
 // ifftshift-ed transfer functions / (NX NY); k = 2 pi dz / lambda as bdof_set_physics has it
 int bdof_set_tf_f64(bdof_ctx* c, const double* probe, const double* hT, const double* hdetT, double k) {
+    if (int rb = need_unbinned(c, "bdof_set_tf_f64")) return rb;
     if (!c || !probe || !hT) return BDOF_ERR_ARG;
     if (int r = need_configured(c)) return r;
     if (c->det_mode == BDOF_DET_NEAR && !hdetT) return fail(c, BDOF_ERR_ARG, "a near-field detector needs its transfer function in float64 too");
@@ -2071,6 +2128,7 @@ int bdof_set_tf_f64(bdof_ctx* c, const double* probe, const double* hT, const do
 // gradient rows in bdof_grot.  Unfused — the accuracy path of the first minibatch of an epoch, and a float64 twin of the fused
 // kernels on the device.  meas: device float, laid out as for bdof_loss_grad (+ meas_ref under bdof_set_meas_mode(1)).
 int bdof_loss_grad_tf_f64(bdof_ctx* c, int B, const int* angle_of_b, const int* xoff, const int* yoff, const float* meas, double meas_ref) {
+    if (int rb = need_unbinned(c, "bdof_loss_grad_tf_f64")) return rb;
     if (!c || !meas) return BDOF_ERR_ARG;
     if (!c->c64_tf) return fail(c, BDOF_ERR_STATE, "bdof_set_tf_f64 has not been called");
     if (!c->obj_src) return fail(c, BDOF_ERR_STATE, "bdof_set_object (with (delta, beta) rows) has not been called");
@@ -2122,15 +2180,16 @@ int bdof_tape_to_real(bdof_ctx* c, int i, int B, void* out) {
     if (r) return r;
     if (!out) return BDOF_ERR_ARG;
     if (!c->tape_valid) return fail(c, BDOF_ERR_STATE, "no history: run bdof_forward(keep_tape=1) first");
-    if (i < 0 || i >= c->S) return fail(c, BDOF_ERR_ARG, "slice index outside [0, S)");
+    const int nz = n_steps(c);
+    if (i < 0 || i >= nz) return fail(c, BDOF_ERR_ARG, "slice index outside [0, S / slice binning)");
     const size_t fld = (size_t)c->Bmax * c->NX * c->NY;
-    if (i < c->S - 1) {
+    if (i < nz - 1) {
         launch_loss_real(c, B, wave_plane(c, carrier_z(c, i + 1), slice_carrier_field(c, i + 1)), c->tape + (size_t)i * fld, nullptr, false,
                          (cf*)out, nullptr, 1.f, 1.f);
     } else {
         if (!c->last_valid)
             return fail(c, BDOF_ERR_STATE, "the last slice's wave is only kept after bdof_forward(keep_tape=1) with the numpy_skip_last variant");
-        launch_loss_real(c, B, wave_plane(c, carrier_z(c, c->S - 1) * (1.0 + c->cbm1), slice_carrier_field(c, c->S - 1)), c->bufA, nullptr, false,
+        launch_loss_real(c, B, wave_plane(c, carrier_z(c, nz - 1) * (1.0 + c->cbm1), slice_carrier_field(c, nz - 1)), c->bufA, nullptr, false,
                          (cf*)out, nullptr, 1.f / c->NY, 1.f);
     }
     return launched(c);
@@ -2170,6 +2229,7 @@ int bdof_loss_grad(bdof_ctx* c, int B, const int* angle_of_b, const int* xoff, c
     // it (one more transform per launch, no tape write in A_z: 104 instead of 112 B per pixel per slice-step, 67.6 -> 65.3 ms
     // per step at 512^3 x 25).
     const bool recompute = c->recompute;
+    const int nz = n_steps(c);
     forward_sweep(c, groups, ng, recompute ? TAPE_LAST : TAPE_HISTORY);
     c->tape_valid = false;      // the tape holds an incomplete history (or phi_{S-1} alone), not what bdof_tape_to_real expects
     c->last_valid = false;
@@ -2187,7 +2247,7 @@ int bdof_loss_grad(bdof_ctx* c, int B, const int* angle_of_b, const int* xoff, c
             // the detector wave came out of a transfer-function step: seed -> R (transposed) -> adjoint step
             const cf* h = c->det_mode == BDOF_DET_NONE ? c->hs : (tf_all ? c->hcomb : c->hdet);
             npart += launch_loss_real(c, Bg, det, c->bufB, c->bufA, true, (cf*)out_wave, meas, 1.f, 1.f);
-            launch_row_prop(c, Bg, c->bufA, c->bufB, h, 1.f, 1, c->S - 1);
+            launch_row_prop(c, Bg, c->bufA, c->bufB, h, 1.f, 1, nz - 1);
         }
     }
     // backward sweep: A'_z (L1 -> L2), then the adjoint transfer-function step (L2 -> L1)
@@ -2199,11 +2259,11 @@ int bdof_loss_grad(bdof_ctx* c, int B, const int* angle_of_b, const int* xoff, c
     cf* const rc_last = c->tape;
     cf* const rc1 = c->tape + fld;
     cf* const rc2 = c->tape + 2 * fld;
-    for (int z = c->S - 1; z >= 0; --z) {
+    for (int z = nz - 1; z >= 0; --z) {
         for (int gi = 0; gi < ng; ++gi) {
             use_group(c, groups[gi]);
             if (recompute) {
-                const bool top = z == c->S - 1;
+                const bool top = z == nz - 1;
                 if (z == 0) launch_row_bwd(c, groups[gi].B, z, c->bufB, nullptr, nullptr, 2);
                 else if (top) launch_row_bwd(c, groups[gi].B, z, c->bufB, rc_last, c->bufA, 0);
                 else launch_row_bwd(c, groups[gi].B, z, c->bufB, rc1, c->bufA, 3, 1.f);
@@ -2214,7 +2274,7 @@ int bdof_loss_grad(bdof_ctx* c, int B, const int* angle_of_b, const int* xoff, c
                 }
                 continue;
             }
-            launch_row_bwd(c, groups[gi].B, z, c->bufB, z > 0 ? c->tape + (size_t)(z - 1) * fld : nullptr, z > 0 ? c->bufA : nullptr,
+            launch_row_bwd(c, groups[gi].B, z, c->bufB, z > 0 ? c->tape + (size_t)steps(c).tape_read(z) * fld : nullptr, z > 0 ? c->bufA : nullptr,
                            z > 0 ? 1 : 2);
             if (z > 0) launch_row_prop(c, groups[gi].B, c->bufA, c->bufB, c->hs, 1.f, 1, z - 1);
         }
@@ -2231,6 +2291,7 @@ int bdof_loss_grad(bdof_ctx* c, int B, const int* angle_of_b, const int* xoff, c
 // =================================================================================================
 int bdof_set_conv(bdof_ctx* c, const float* ky, const float* kx, int ks, double e_re, double e_im, double ksum_re,
                   double ksum_im, double k) {
+    if (int rb = need_unbinned(c, "bdof_set_conv")) return rb;
     if (!c || !ky || !kx) return BDOF_ERR_ARG;
     if (int r = need_configured(c)) return r;
     if (ks < 1 || ks > BDOF_CONV_MAXK || ks % 2 == 0) return fail(c, BDOF_ERR_ARG, "kernel_size must be odd and <= 33");
@@ -2260,6 +2321,7 @@ int bdof_set_conv(bdof_ctx* c, const float* ky, const float* kx, int ks, double 
 }
 
 int bdof_set_conv_taps_f64(bdof_ctx* c, const double* ky, const double* kx, double e_re, double e_im) {
+    if (int rb = need_unbinned(c, "bdof_set_conv_taps_f64")) return rb;
     if (!c || !ky || !kx) return BDOF_ERR_ARG;
     if (!c->have_conv) return fail(c, BDOF_ERR_STATE, "bdof_set_conv has not been called");
     const int D = c->tw_dither;
@@ -2415,6 +2477,7 @@ static ConvFinalArgs conv_final_args(bdof_ctx* c, int B, const cf* psi_eps, cf* 
 extern "C" {
 
 int bdof_set_conv_probe_stack(bdof_ctx* c, const float* stack, const double* det64, double p0_re, double p0_im, double pS_re, double pS_im) {
+    if (int rb = need_unbinned(c, "bdof_set_conv_probe_stack")) return rb;
     if (!c) return BDOF_ERR_ARG;
     if (int r = need_configured(c)) return r;
     HIPC(c, hipSetDevice(c->device));
@@ -2435,6 +2498,7 @@ int bdof_set_conv_probe_stack(bdof_ctx* c, const float* stack, const double* det
 }
 
 int bdof_forward_conv(bdof_ctx* c, int B, const int* angle_of_b, const int* xoff, const int* yoff, void* out_wave) {
+    if (int rb = need_unbinned(c, "bdof_forward_conv")) return rb;
     int r = conv_check(c, B, angle_of_b);
     if (r) return r;
     if (!out_wave) return BDOF_ERR_ARG;
@@ -2471,6 +2535,7 @@ int bdof_forward_conv(bdof_ctx* c, int B, const int* angle_of_b, const int* xoff
 }
 
 int bdof_loss_grad_conv(bdof_ctx* c, int B, const int* angle_of_b, const int* xoff, const int* yoff, const float* meas, void* out_wave) {
+    if (int rb = need_unbinned(c, "bdof_loss_grad_conv")) return rb;
     int r = conv_check(c, B, angle_of_b);
     if (r) return r;
     if (!meas) return BDOF_ERR_ARG;
@@ -2729,6 +2794,7 @@ int bdof_rotate_bilinear(bdof_ctx* c, const void* vol, int NXv, int NZv, int NYv
 // bdof_rotate_bilinear + bdof_set_object in one pass: the B rotated objects are written straight into the ctx's modulation
 // table as factors c - 1 (no rotated (delta, beta) copy, no second pass over B volumes) and bound as the batch's objects.
 int bdof_set_object_bilinear(bdof_ctx* c, const void* vol, int NXv, int NZv, int NYv, const double* prm, int B, int conv) {
+    if (int rb = need_unbinned(c, "bdof_set_object_bilinear")) return rb;
     if (!c || !vol || !prm || B < 1) return BDOF_ERR_ARG;
     if (int r = need_configured(c)) return r;
     if (NXv < 1 || NZv < 1 || NYv < 2 || NYv % 2) return fail(c, BDOF_ERR_SIZE, "bdof_set_object_bilinear needs an even NY");

@@ -25,6 +25,18 @@ __device__ __forceinline__ float2 g_mod_value(const ObjView& o, int b, int x, in
     return make_float2(in ? v.x : 0.f, in ? v.y : 0.f);
 }
 
+// slice binning: c - 1 of step z's bin, the o.bin voxel slices combined as in load_obj_row_bin (bdof_kernels.h)
+__device__ __forceinline__ float2 g_mod_value_bin(const ObjView& o, int b, int x, int y, int z, int NX) {
+    float2 t = g_mod_value(o, b, x, y, z * o.bin, NX);
+    for (int j = 1; j < o.bin; ++j) {
+        const float2 u = g_mod_value(o, b, x, y, z * o.bin + j, NX);
+        t = make_float2(t.x + u.x + (t.x * u.x - t.y * u.y), t.y + u.y + (t.x * u.y + t.y * u.x));
+    }
+    return t;
+}
+
+// BIN (here and in k_g_bwd): slice binning, a.z counts propagation steps
+template <bool BIN>
 __global__ __launch_bounds__(256) void k_g_modulate(GModArgs a) {
     const size_t n = (size_t)a.B * a.NX * a.NY;
     for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < n; idx += (size_t)gridDim.x * blockDim.x) {
@@ -33,7 +45,8 @@ __global__ __launch_bounds__(256) void k_g_modulate(GModArgs a) {
         const int x = r % a.NX, b = r / a.NX;
         const cf e = a.probe ? a.probe[(size_t)x * a.NY + y] : a.field[idx];
         const cf pc = a.pz ? a.pz[(size_t)x * a.NY + y] : a.carrier;
-        const cf phi = modulate_eps_s(e, pc, g_mod_value(a.obj, b, x, y, a.z, a.NX), a.cshift);
+        const float2 m1 = BIN ? g_mod_value_bin(a.obj, b, x, y, a.z, a.NX) : g_mod_value(a.obj, b, x, y, a.z, a.NX);
+        const cf phi = modulate_eps_s(e, pc, m1, a.cshift);
         a.field[idx] = phi;
         if (a.tape) a.tape[idx] = a.pz ? cadd(phi, pc) : phi;
     }
@@ -123,6 +136,7 @@ struct GBwdArgs {
     AdjCarrier ac;       // gcar nullable
 };
 
+template <bool BIN>
 __global__ __launch_bounds__(256) void k_g_bwd(GBwdArgs a) {
     const size_t n = (size_t)a.B * a.NX * a.NY;
     for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < n; idx += (size_t)gridDim.x * blockDim.x) {
@@ -133,7 +147,7 @@ __global__ __launch_bounds__(256) void k_g_bwd(GBwdArgs a) {
         const cf e = a.tape[idx];
         const cf phi = a.full_tape ? e : cadd(e, a.carrier);
         cf t = cmulc(G, phi);
-        const float2 m1 = g_mod_value(a.obj, b, x, y, a.z, a.NX);
+        const float2 m1 = BIN ? g_mod_value_bin(a.obj, b, x, y, a.z, a.NX) : g_mod_value(a.obj, b, x, y, a.z, a.NX);
         cf Gn = cmulc(G, make_float2(1.f + m1.x, m1.y));
         if (a.ac.gcar) {
             cf gam, t0;
@@ -143,7 +157,12 @@ __global__ __launch_bounds__(256) void k_g_bwd(GBwdArgs a) {
             // the sweep ends at slice 0: leave the FULL G(psi_0) = scattered part + conj(cbar) gamma for bdof_probe_grad
             if (a.z == 0) Gn = cadd(Gn, cmulc(gam, make_float2(1.f + a.ac.cbm1.x, a.ac.cbm1.y)));
         }
-        a.grot[(((size_t)b * a.obj.S + a.z) * a.NX + x) * a.NY + y] = make_float2(a.k * t.y, -a.k * t.x);
+        const float2 gv = make_float2(a.k * t.y, -a.k * t.x);
+        if constexpr (BIN) {                  // the bin's one gradient value to each of its voxel slices
+            for (int j = 0; j < a.obj.bin; ++j) a.grot[(((size_t)b * a.obj.S + a.z * a.obj.bin + j) * a.NX + x) * a.NY + y] = gv;
+        } else {
+            a.grot[(((size_t)b * a.obj.S + a.z) * a.NX + x) * a.NY + y] = gv;
+        }
         a.g[idx] = Gn;
     }
 }

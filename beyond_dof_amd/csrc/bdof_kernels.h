@@ -81,6 +81,7 @@ struct ObjView {
     const int* xoff;         // nullable [B]: window origin in x (ptychography, K11)
     const int* yoff;         // nullable [B]: window origin in y
     int S, volNX, volNY;
+    int bin = 1;             // slice binning (bdof_set_slice_binning): voxel slices per propagation step; S stays the voxel depth
 };
 
 __device__ __forceinline__ long long obj_src_row(const ObjView& o, int b, int x, int z, int NX) {
@@ -198,6 +199,25 @@ __device__ __forceinline__ void load_obj_row(const ObjView& o, long long srow, i
     }
 }
 
+// Slice binning (bdof_set_slice_binning): step z modulates by the product of the o.bin voxel slices z bin .. z bin + bin - 1.
+// The table holds c - 1, and (1 + t)(1 + u) - 1 = t + u + t u combines two entries without ever forming 1 + small: the
+// bin's c - 1 keeps the digits of its slices'.  A row outside the volume or a y outside it is u = 0, a factor of 1.  The
+// loads of one voxel slice are unconditional and independent of each other and of the running product (load_obj_row).
+// (The view comes by value: with a reference into the kernel's argument block hipcc kept the whole block in scratch.)
+__device__ __forceinline__ void load_obj_row_bin(const ObjView o, int b, int x, int z, int NX, int y0, int tid, int T, float2 (&db)[8]) {
+    load_obj_row(o, obj_src_row(o, b, x, z * o.bin, NX), y0, tid, T, db);
+#pragma nounroll
+    for (int j = 1; j < o.bin; ++j) {
+        float2 u[8];
+        load_obj_row(o, obj_src_row(o, b, x, z * o.bin + j, NX), y0, tid, T, u);
+#pragma unroll
+        for (int m = 0; m < 8; ++m) {
+            const float2 t = db[m];
+            db[m] = make_float2(t.x + u[m].x + (t.x * u[m].x - t.y * u[m].y), t.y + u[m].y + (t.x * u[m].y + t.y * u[m].x));
+        }
+    }
+}
+
 // ---------------------------------------------------------------------------------------------
 // A: forward row kernel.                              cnn_propagator/np_funcs.py:37-40 (+ FFT along y)
 // ---------------------------------------------------------------------------------------------
@@ -233,7 +253,9 @@ __device__ __forceinline__ cf unmodulate_eps(cf epsp, cf carrier, cf cm1, cf csh
 // PF: the carrier is a field (localised probe), one more coalesced 8-B read per pixel; the plane-wave instances are untouched
 // INV: A_z^-1 — rows of the hybrid (or, real_in, real-space) scattered part of phi_z in, R eps(psi_z) out: the first half
 // of the step phi_z -> phi_{z-1} = P^H (phi_z / c_z) that marches the forward wave back beside the adjoint field.
-template <int NY, bool FIRST, bool TSTORE, bool PF = false, bool INV = false>
+// BIN: slice binning — a.z counts propagation steps and the modulation is the bin's (load_obj_row_bin); the BIN = false
+// instances are what they were without the option.
+template <int NY, bool FIRST, bool TSTORE, bool PF = false, bool INV = false, bool BIN = false>
 __global__ __launch_bounds__(BDOF_THREADS, RowCfg<NY>::MIN_WAVES) void k_row_fwd(RowFwdArgs a) {
     typedef RowCfg<NY> C;
     __shared__ cf smem[C::LDS_CF];
@@ -259,7 +281,8 @@ __global__ __launch_bounds__(BDOF_THREADS, RowCfg<NY>::MIN_WAVES) void k_row_fwd
             const cf* src = FIRST ? a.probe + (a.probe_batched ? (size_t)(row0 + r) : (size_t)x) * NY : a.in + (size_t)(row0 + r) * NY;
 #pragma unroll
             for (int m = 0; m < 8; ++m) u[m] = src[tid + m * C::T];
-            load_obj_row(a.obj, obj_src_row(a.obj, b, x, a.z, a.NX), y0, tid, C::T, db);
+            if constexpr (BIN) load_obj_row_bin(a.obj, b, x, a.z, a.NX, y0, tid, C::T, db);
+            else load_obj_row(a.obj, obj_src_row(a.obj, b, x, a.z, a.NX), y0, tid, C::T, db);
             if constexpr (PF) {
                 cf pc[8];
 #pragma unroll
@@ -681,7 +704,8 @@ struct RowBwdArgs {
     cf* gpsi0;         // nullable: G(psi_z) in real space, [B][NX][NY] — at z = 0 the gradient w.r.t. the probe per wavefield
                        // (probe_real / probe_imag of tensorflow_recon/fullfield.py:311-327 as optimisation variables)
     int grot_S, grot_z;  // gradient rows go to grot[b][grot_z][x][y] of a [B][grot_S][NX][NY] buffer (= obj.S, z unless the
-                         // sweep covers a slice range with a buffer of its own, bdof_adjoint_range)
+                         // sweep covers a slice range with a buffer of its own, bdof_adjoint_range; BIN kernels: z bin, the
+                         // first voxel slice of step z's bin)
     float sq[2];         // sqrt(1/2) of this launch (RowFwdArgs)
 };
 
@@ -691,7 +715,9 @@ struct RowBwdArgs {
 // HIST = 2: slice 0 of that mode, phi_0 from the probe (no transform).
 // HIST = 3: tape-free adjoint — `tape` is the hybrid scattered part of phi_z itself, marched back by A_{z+1}^-1 and the
 // adjoint transfer-function step (one inverse transform here, no modulation); tape_scale multiplies it.
-template <int NY, int HIST, bool PF = false, bool GC = false>
+// BIN: slice binning (HIST 1 / 2) — the bin's modulation, and the one gradient row goes to each of the bin's a.obj.bin voxel
+// slices grot[b][grot_z + j], j < bin: d c_bin / d delta_j = i k c_bin whichever slice of the bin delta_j belongs to.
+template <int NY, int HIST, bool PF = false, bool GC = false, bool BIN = false>
 __global__ __launch_bounds__(BDOF_THREADS, RowCfg<NY>::MIN_WAVES) void k_row_bwd(RowBwdArgs a) {
     typedef RowCfg<NY> C;
     __shared__ cf smem[C::LDS_CF];
@@ -701,7 +727,8 @@ __global__ __launch_bounds__(BDOF_THREADS, RowCfg<NY>::MIN_WAVES) void k_row_bwd
     FftTw<NY> tw;
     __shared__ cf smem_tail[7 * C::T * (EX ? 2 : 1)];
     tw.template load<EX>(a.twiddle, tid, smem_tw, smem_tail);
-    tw.sq = a.sq;
+    const float sq_bin[2] = {a.sq[0], a.sq[1]};      // BIN: a copy, so that no pointer into the argument block keeps it in memory
+    tw.sq = BIN ? sq_bin : a.sq;
     const int ntiles = a.B * a.NX / C::TILE;
     for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         const int row0 = tile * C::TILE;
@@ -709,6 +736,7 @@ __global__ __launch_bounds__(BDOF_THREADS, RowCfg<NY>::MIN_WAVES) void k_row_bwd
         const int y0 = a.obj.yoff ? a.obj.yoff[b] : 0;
         cf gam = make_float2(0.f, 0.f), t0 = make_float2(0.f, 0.f);
         if constexpr (GC) adj_carrier_load(a.ac, b, gam, t0);
+        const int nbin = BIN ? a.obj.bin : 1;
 #pragma nounroll
         for (int pass = 0; pass < C::PASSES; ++pass) {
             const int r = pass * C::RPP + rl;
@@ -717,12 +745,13 @@ __global__ __launch_bounds__(BDOF_THREADS, RowCfg<NY>::MIN_WAVES) void k_row_bwd
             const size_t off = (size_t)(row0 + r) * NY;
             cf g[8], p[8];
             float2 db[8];
+            if constexpr (BIN) load_obj_row_bin(a.obj, b, x, a.z, a.NX, y0, tid, C::T, db);     // (first: its loop runs with nothing else live)
 #pragma unroll
             for (int m = 0; m < 8; ++m) g[m] = a.gin[off + tid + m * C::T];
             const cf* psrc = HIST == 2 ? a.tape + (size_t)x * NY : a.tape + off;      // HIST 2: `tape` is the probe [NX][NY]
 #pragma unroll
             for (int m = 0; m < 8; ++m) p[m] = psrc[tid + m * C::T];
-            load_obj_row(a.obj, obj_src_row(a.obj, b, x, a.z, a.NX), y0, tid, C::T, db);
+            if constexpr (!BIN) load_obj_row(a.obj, obj_src_row(a.obj, b, x, a.z, a.NX), y0, tid, C::T, db);
             cf pc[PF ? 8 : 1];
             if constexpr (PF) {
 #pragma unroll
@@ -744,9 +773,18 @@ __global__ __launch_bounds__(BDOF_THREADS, RowCfg<NY>::MIN_WAVES) void k_row_bwd
                 const cf phi = cadd(p[m], PF ? pc[m] : a.carrier_phi);
                 cf t = cmulc(g[m], phi);                             // G * conj(phi)
                 if constexpr (GC) t = cadd(cadd(t, cmulc(gam, p[m])), t0);      // + gamma conj(e) + gamma conj(a)
-                gdst[tid + m * C::T] = make_float2(a.k * t.y, -a.k * t.x);
+                const float2 gv = make_float2(a.k * t.y, -a.k * t.x);
+                if constexpr (BIN) p[m] = gv;                        // (phi is done with: the row waits here for its bin's slices)
+                else gdst[tid + m * C::T] = gv;
                 g[m] = cmulc(g[m], make_float2(1.f + db[m].x, db[m].y));    // conj(c) G,  c = 1 + (c - 1)
                 if constexpr (GC) g[m] = cadd(g[m], cmulc(gam, csub(db[m], a.ac.cbm1)));   // + conj(c - cbar) gamma (conj(cbar) gamma rides on)
+            }
+            if constexpr (BIN) {
+#pragma nounroll
+                for (int j = 0; j < nbin; ++j, gdst += (size_t)a.NX * NY) {
+#pragma unroll
+                    for (int m = 0; m < 8; ++m) gdst[tid + m * C::T] = p[m];
+                }
             }
             if (a.gpsi0) {
                 cf* pd = a.gpsi0 + off;
@@ -758,7 +796,7 @@ __global__ __launch_bounds__(BDOF_THREADS, RowCfg<NY>::MIN_WAVES) void k_row_bwd
         }
         if (a.gout) {
             __syncthreads();
-            transposed_tail<NY, -1, 1, EX>(smem, a.gout + (size_t)b * NY * a.NX + x0, a.NX, 1.f, smem_tail, a.sq);
+            transposed_tail<NY, -1, 1, EX>(smem, a.gout + (size_t)b * NY * a.NX + x0, a.NX, 1.f, smem_tail, tw.sq);
             __syncthreads();
         }
     }

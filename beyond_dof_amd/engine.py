@@ -29,6 +29,27 @@ def check_poisson_path(loss_type, poisson_multiplier, propagator):
         raise ValueError("loss_type='poisson' runs on the transfer-function propagator (propagator='fft') only")
 
 
+def check_slice_binning(slice_binning):
+    """The slice_binning keyword as every layer takes it: an integer >= 1 (raises ValueError)."""
+    if isinstance(slice_binning, bool) or not isinstance(slice_binning, (int, np.integer)) or slice_binning < 1:
+        raise ValueError('slice_binning must be an integer >= 1')
+
+
+def check_binning_path(slice_binning, propagator='fft', adjoint_precision=None, rotation='nearest'):
+    """check_slice_binning, and with slice_binning > 1 that the call stays on what carries it: the transfer-function
+    propagator, the float32 sweeps (an explicit adjoint_precision other than 'float32' raises; None: not given) and the
+    nearest-neighbour rotation tables."""
+    check_slice_binning(slice_binning)
+    if slice_binning == 1:
+        return
+    if propagator != 'fft':
+        raise ValueError("slice_binning > 1 runs on the transfer-function propagator (propagator='fft') only")
+    if adjoint_precision not in (None, 'float32'):
+        raise ValueError("slice_binning > 1 has no float64 twin: adjoint_precision must be 'float32'")
+    if rotation != 'nearest':
+        raise ValueError("slice_binning > 1 runs on the rotation tables (rotation='nearest') only")
+
+
 def _hp(arr):
     """Host pointer of a numpy array for a library call (None stays None)."""
     return None if arr is None else arr.ctypes.data
@@ -41,13 +62,23 @@ class MultisliceEngine(object):
     """One wavefield geometry (NY x NX x S) on one GPU."""
 
     def __init__(self, ny, nx, n_slice, batch_max, with_grad=True, device=0, stream=None, force_generic=False, engine='auto',
-                 recompute=False, no_grot=False, adjoint64=False):
+                 recompute=False, no_grot=False, adjoint64=False, slice_binning=1):
         """Engines (include/bdof.h, bdof_configure): powers of two in 64..1024 run on the fused streaming kernels; small
         square fields (32..128, e.g. the 72 x 72 ptychography probe) on the LDS-resident kernel when there is no fused plan
         or the batch is large; every other size on the generic engine (rocFFT).  engine='generic' (= force_generic=True),
         'streaming' (never resident) or 'resident' (resident for every batch size) pin the choice for cross-checks.
         adjoint64=True: the adjoint sweep in float64 (bdof_configure flag 64; generic engine) — the
-        accuracy option for reconstructions that must follow the reference's float64 loop voxel by voxel."""
+        accuracy option for reconstructions that must follow the reference's float64 loop voxel by voxel.
+        slice_binning=b: one propagation step per b voxel slices (bdof_set_slice_binning, include/bdof.h) — the modulation
+        factors of a bin are multiplied, one transfer-function step of b * delta_nm follows, n_steps = n_slice / b steps in
+        all; streaming and generic engines, float32 sweeps with the tape."""
+        check_slice_binning(slice_binning)
+        b = int(slice_binning)
+        if int(n_slice) % b:
+            raise ValueError('slice_binning must divide n_slice ({} % {} != 0)'.format(int(n_slice), b))
+        if b > 1 and (engine == 'resident' or recompute or adjoint64 or no_grot):
+            raise ValueError("slice_binning > 1 runs on the streaming and generic engines with the tape: not engine='resident', "
+                             'recompute, adjoint64 or no_grot')
         if engine not in ('auto', 'generic', 'streaming', 'resident'):
             raise ValueError('engine must be auto, generic, streaming or resident')
         force_generic = force_generic or engine == 'generic'
@@ -57,10 +88,13 @@ class MultisliceEngine(object):
         self.lib, self.h = self.ctx.lib, self.ctx.handle
         self.ny, self.nx, self.n_slice, self.batch_max = int(ny), int(nx), int(n_slice), int(batch_max)
         self.with_grad = bool(with_grad)
+        self.slice_binning, self.n_steps = b, self.n_slice // b
         flags = (_lib.CFG_GRAD if with_grad else 0) | (_lib.CFG_GENERIC if force_generic else 0) \
             | (_lib.CFG_NO_RESIDENT if engine == 'streaming' else 0) | (_lib.CFG_ALWAYS_RESIDENT if engine == 'resident' else 0) \
             | (_lib.CFG_RECOMPUTE if self.recompute else 0) | (_lib.CFG_NO_GROT if no_grot else 0) | (_lib.CFG_ADJOINT64 if self.adjoint64 else 0)
         self.ctx.check(self.lib.bdof_configure(self.h, self.ny, self.nx, self.n_slice, self.batch_max, flags))
+        if b > 1:           # (1 is what bdof_configure leaves)
+            self.ctx.check(self.lib.bdof_set_slice_binning(self.h, b))
         self._reset_host_state()        # after bdof_configure, never before: it puts the ctx's data term back through the library (set_loss)
 
     # Host state: what the setters below record on the instance; before that, and after _reset_host_state(), as declared here.
@@ -108,9 +142,9 @@ class MultisliceEngine(object):
             det_kernel = util.detector_kernel_kind(detector_kernel, o.det_nm, o.lmbda_nm, o.voxel_nm, (self.ny, self.nx))
         self.optics, self.variant, self.k = o, variant, o.k       # (a refused argument has raised by now: the old physics stay whole)
         self.det_mode, self.det_kernel = det_mode, det_kernel
-        hs64 = o.table(o.delta_nm, tiled=True, dtype=np.complex128)       # the slice step honours field_shape ...
+        hs64 = o.table(self._step_nm(), tiled=True, dtype=np.complex128)  # the slice step (of slice_binning voxels) honours field_shape ...
         hs = hs64.astype(np.complex64)
-        h00 = o.dc(o.delta_nm, tiled=True)
+        h00 = o.dc(self._step_nm(), tiled=True)
         hdet00 = o.dc(o.det_nm, det_kernel) if det_mode == _lib.DET_NEAR else None
         hdet = self._detector_table(np.complex64)                          # ... the detector step does not
         self.tf_f64 = self.conv_f64 = False     # a float64 twin bound before this call held the previous tables
@@ -128,6 +162,14 @@ class MultisliceEngine(object):
             self.ctx.check(self.lib.bdof_set_physics_f64(self.h, hs64.ctypes.data, _hp(hd64)))
         if self._probe_args is not None:
             self.set_probe(*self._probe_args)      # the carrier (field, calibration) of the probe depends on the physics
+
+    def _step_nm(self):
+        """Length of one propagation step: slice_binning voxel slices."""
+        return self.optics.delta_nm * self.slice_binning
+
+    def _need_unbinned(self, what):
+        if self.slice_binning > 1:
+            raise ValueError('{} does not carry slice_binning > 1'.format(what))
 
     def _detector_table(self, dtype, fold=True, transpose=False, tiled=False):
         """The un-shifted multiplier of the step to a near-field detector (None without one): the one place it is built.
@@ -149,12 +191,12 @@ class MultisliceEngine(object):
         """The probe propagated through free space to the entrance of every slice and to the detector, in float64 on the
         host (np_funcs.py:42-61 without an object) — the carrier field of bdof_set_probe_stack (include/bdof.h)."""
         o = self.optics
-        h = o.table(o.delta_nm, tiled=False, fold=False, dtype=np.complex128)      # this cross-check: the (ny, nx) mesh's own get_kernel
+        h = o.table(self._step_nm(), tiled=False, fold=False, dtype=np.complex128)      # this cross-check: the (ny, nx) mesh's own get_kernel
         p = probe_c64.astype(np.complex128)
-        stack = np.empty((self.n_slice, self.nx, self.ny), dtype=np.complex64)
-        for z in range(self.n_slice):
+        stack = np.empty((self.n_steps, self.nx, self.ny), dtype=np.complex64)
+        for z in range(self.n_steps):
             stack[z] = p.T
-            if z < self.n_slice - 1:
+            if z < self.n_steps - 1:
                 p = np.fft.ifft2(np.fft.fft2(p) * h)
         if self.det_mode == _lib.DET_FAR:
             det = np.fft.fft2(p)                      # un-shifted, un-normalised; a tf_all step before it is applied on the host
@@ -170,7 +212,7 @@ class MultisliceEngine(object):
         """The same carrier field computed by the library on the device in float64 (bdof_set_probe_field): the host only forms
         the two transfer functions (float64, transposed to [kx][ky]); both honour field_shape."""
         o = self.optics
-        hT = o.table(o.delta_nm, tiled=True, fold=False, transpose=True, dtype=np.complex128)
+        hT = o.table(self._step_nm(), tiled=True, fold=False, transpose=True, dtype=np.complex128)
         hdT = self._detector_table(np.complex128, fold=False, transpose=True, tiled=True)
         p = np.ascontiguousarray(probe_c64.T.astype(np.complex128))
         self.ctx.check(self.lib.bdof_set_probe_field(self.h, p.ctypes.data, hT.ctypes.data, _hp(hdT)))
@@ -192,7 +234,7 @@ class MultisliceEngine(object):
                 return
         use_stack = (a0 == 0 and self.optics is not None and not os.environ.get('BDOF_NO_PROBE_STACK')
                      and self._conv_kernel is None                          # the real-space propagator has its own carrier
-                     and self.n_slice * self.nx * self.ny <= (1 << 32)      # 32 GiB of stack at most
+                     and self.n_steps * self.nx * self.ny <= (1 << 32)      # 32 GiB of stack at most
                      and self.lib.bdof_probe_stack_supported(self.h) == 1)
         if use_stack:
             if os.environ.get('BDOF_HOST_PROBE_STACK'):                     # cross-check: the float64 propagation on the host
@@ -281,6 +323,7 @@ class MultisliceEngine(object):
     def set_conv(self, energy_ev, psize_cm, kernel_size=17):
         """Switch the slice-to-slice step to the truncated real-space kernel of multislice_propagate_cnn
         (cnn_propagator/propagation.py:18-44): k uses numpy's pi there (:25), the kernel the reference's PI literal."""
+        self._need_unbinned('the real-space propagator (set_conv)')
         o = util.Optics(energy_ev, psize_cm, None, np.pi, self.ny, self.nx)         # o.k: numpy's pi, unlike set_physics
         ky, kx, e = util.conv_kernel_separable(o.delta_nm, o.lmbda_nm, o.voxel_nm, (self.ny, self.nx), kernel_size)   # pi=util.PI
         ksum = e * ky.sum() * kx.sum()
@@ -301,6 +344,7 @@ class MultisliceEngine(object):
         accuracy path of the first minibatch of an epoch (adjoint_precision='first-step') — no second engine — and a float64 twin
         of the fused kernels for tests.  Hands the probe and the transfer function(s) over in float64; call again after
         set_physics / set_probe."""
+        self._need_unbinned('the float64 twin (enable_tf_f64)')
         if self.optics is None or self._probe_args is None:
             raise RuntimeError('set_physics and set_probe first')
         o = self.optics
@@ -316,6 +360,7 @@ class MultisliceEngine(object):
         f64=True)): the accuracy path for the first minibatch of an epoch (adjoint_precision='first-step' / 'float64' with
         propagator='conv').  Square fields.  Hands the probe and the transform of the zero-padded
         ks x ks kernel over in float64 (overlap-save on the padded (N + ks - 1)^2 grid)."""
+        self._need_unbinned('the float64 twin (enable_conv_f64)')
         if self._conv_kernel is None or self._probe_args is None:
             raise RuntimeError('set_conv and set_probe first')
         if self.nx != self.ny:
@@ -392,10 +437,10 @@ class MultisliceEngine(object):
         return self._wave_to_host(out, B) if to_host else out
 
     def probe_array(self, B):
-        """Per-slice wavefields, (S, B, Y, X) — the second return value of np_funcs.py:65."""
+        """Per-step wavefields, (n_steps, B, Y, X) — the second return value of np_funcs.py:65 (n_steps = S without binning)."""
         out = DeviceBuffer(self.ctx, B * self.nx * self.ny * 8, np.complex64, (B, self.nx, self.ny))
-        res = np.empty((self.n_slice, B, self.ny, self.nx), dtype=np.complex64)
-        for i in range(self.n_slice):
+        res = np.empty((self.n_steps, B, self.ny, self.nx), dtype=np.complex64)
+        for i in range(self.n_steps):
             self.ctx.check(self.lib.bdof_tape_to_real(self.h, i, B, out.ptr))
             res[i] = out.download((B, self.nx, self.ny), np.complex64).transpose(0, 2, 1)
         return res

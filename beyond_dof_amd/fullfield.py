@@ -23,7 +23,7 @@ import numpy as np
 from . import h5io, tiffio, util
 from .comm import get_comm, minibatch_schedule
 from .misc import create_summary
-from .engine import check_poisson_path
+from .engine import check_poisson_path, check_binning_path
 from .solver import FullfieldSolver
 from .util import print_flush
 
@@ -61,7 +61,7 @@ def reconstruct_fullfield(fname, theta_st=0, theta_end=PI, n_epochs='auto', crit
                           multiscale_level=1, n_epoch_final_pass=None, initial_guess=None, n_batch_per_update=5,
                           dynamic_rate=True, probe_type='plane', probe_initial=None, probe_learning_rate=1e-3,
                           pupil_function=None, theta_downsample=None, forward_algorithm='fresnel', random_theta=True,
-                          object_type='normal', kernel_size=17, debug=False, loss_type='lsq', poisson_multiplier=2e6, **kwargs):
+                          object_type='normal', kernel_size=17, debug=False, loss_type='lsq', poisson_multiplier=2e6, slice_binning=1, **kwargs):
     """Reconstruct a beyond-depth-of-focus object from full-field projections (see the module docstring and
     cnn_propagator/fullfield.py:28-77 for the parameters).  Returns (obj_delta, obj_beta) of the finest level."""
     t_zero = time.time()
@@ -83,6 +83,10 @@ def reconstruct_fullfield(fname, theta_st=0, theta_end=PI, n_epochs='auto', crit
     # tensorflow_recon/ptychography.py, as its deviance (include/bdof.h, bdof_set_loss), with poisson_multiplier photons per unit
     # intensity.  Near the fit it is ~ 2 poisson_multiplier times the least-squares term: rescale alpha_d / alpha_b / gamma with it.
     check_poisson_path(loss_type, poisson_multiplier, propagator)
+    # slice_binning=b: one propagation step per b voxel slices (include/bdof.h, bdof_set_slice_binning) — a step only has to stay
+    # below the depth of focus.  Transfer-function propagator, lookup-table rotation and float32 sweeps; every multiscale
+    # level's depth must divide by b.
+    check_binning_path(slice_binning, propagator, kwargs.get('adjoint_precision'), kwargs.get('rotation', 'nearest'))
     # gradient accumulation over n_batch_per_update minibatches exists only in the TF twin (tensorflow_recon/fullfield.py:
     # 413-425); the cnn variant accepts the keyword and ignores it (default 5!), so it is opt-in here
     accumulate = bool(kwargs.get('accumulate_gradients', False))
@@ -115,6 +119,10 @@ def reconstruct_fullfield(fname, theta_st=0, theta_end=PI, n_epochs='auto', crit
     # regulariser weights: the alpha branch of fullfield.py:109-111 counts delta twice and never beta (quirk Q6)
     reg_d, reg_b = (2 * alpha, 0.0) if alpha_d is None else (alpha_d, alpha_b)
 
+    for lv in range(multiscale_level):          # the depths without a mask, before any level has run (a mask's are checked per level)
+        if len(range(0, prj_0.shape[-1], 2 ** lv)) % slice_binning:
+            raise ValueError('slice_binning={} does not divide the depth of multiscale level {}'.format(slice_binning, 2 ** lv))
+
     obj_delta = obj_beta = None
     first_level = True
     for ds_level in range(multiscale_level - 1, -1, -1):
@@ -131,6 +139,8 @@ def reconstruct_fullfield(fname, theta_st=0, theta_end=PI, n_epochs='auto', crit
         if mask is not None and ds_level > 1:
             mask = mask[::ds_level, ::ds_level, ::ds_level]
         dim_z = mask.shape[-1] if mask is not None else dim_x
+        if dim_z % slice_binning:
+            raise ValueError('slice_binning={} does not divide the depth {} of multiscale level {}'.format(slice_binning, dim_z, ds_level))
 
         np.random.seed(seed)          # same seed on every rank (fullfield.py:242-245)
         if first_level:
@@ -184,7 +194,7 @@ def reconstruct_fullfield(fname, theta_st=0, theta_end=PI, n_epochs='auto', crit
                                  comm=comm, device=comm.local_rank, coord_ls=coord_ls, propagator=propagator, kernel_size=kernel_size,
                                  rotation=rotation, theta=theta, adjoint64={'float32': None, 'float64': True, 'first-step': 'first'}[adjoint_precision],
                                  detector_kernel=kwargs.get('detector_kernel', 'TF'),   # 'IR' / 'auto': np_funcs.py:51-61
-                                 loss_type=loss_type, poisson_multiplier=poisson_multiplier)
+                                 loss_type=loss_type, poisson_multiplier=poisson_multiplier, slice_binning=slice_binning)
         solver.set_volume(obj_delta, obj_beta)
         solver.set_mask(mask)
         solver.set_measurements(np.abs(prj))

@@ -7,10 +7,12 @@ SUMMARY_PRESET_PTYCHO = ['obj_size', 'probe_size', 'output_folder', 'theta_downs
                          # not in the reference's preset: the precision the adjoint sweep was ASKED to run in and the one it runs in
                          'adjoint_precision', 'adjoint_precision_effective',
                          # ... and the data term (tensorflow_recon/ptychography.py prints its poisson_multiplier)
-                         'loss_type', 'poisson_multiplier']
+                         'loss_type', 'poisson_multiplier',
+                         # ... and the voxel slices per propagation step
+                         'slice_binning']
 SUMMARY_PRESET_FF = ['obj_size', 'output_folder', 'theta_downsample', 'n_theta', 'n_epochs', 'learning_rate', 'alpha_d',
                      'alpha_b', 'gamma', 'minibatch_size', 'free_prop_cm', 'psize_cm', 'energy_ev', 'fname', 'object_type',
-                     'loss_type', 'poisson_multiplier']
+                     'loss_type', 'poisson_multiplier', 'slice_binning']
 
 
 def create_summary(save_path, locals_dict, var_list=None, preset=None):

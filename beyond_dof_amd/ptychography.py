@@ -17,7 +17,7 @@ from . import h5io, tiffio, util
 from .comm import get_comm
 from .fullfield import create_probe_initial_guess, upsample_2x
 from .misc import create_summary
-from .engine import check_poisson_path
+from .engine import check_poisson_path, check_binning_path
 from .solver import PtychoSolver
 from ._lib import BdofError
 from .util import print_flush, split_tasks
@@ -69,7 +69,7 @@ def reconstruct_ptychography(fname, probe_pos, probe_size, obj_size, theta_st=0,
                              dynamic_rate=True, probe_type='gaussian', probe_initial=None, probe_learning_rate=1e-3,
                              pupil_function=None, probe_circ_mask=0.9, finite_support_mask=None,
                              forward_algorithm='fresnel', dynamic_dropping=True, dropping_threshold=8e-5,
-                             n_dp_batch=20, object_type='normal', loss_type='lsq', poisson_multiplier=2e6, **kwargs):
+                             n_dp_batch=20, object_type='normal', loss_type='lsq', poisson_multiplier=2e6, slice_binning=1, **kwargs):
     t_zero = time.time()
     comm = kwargs.get('comm') or get_comm()
     size, rank = comm.size, comm.rank
@@ -92,6 +92,15 @@ def reconstruct_ptychography(fname, probe_pos, probe_size, obj_size, theta_st=0,
     # keyword, as its deviance (include/bdof.h, bdof_set_loss).  The bare likelihood is unbounded where the model intensity goes
     # to zero under a measured count, which far-field data with noise has: there is no epsilon.
     check_poisson_path(loss_type, poisson_multiplier, propagator)
+    # slice_binning=b: one propagation step per b voxel slices (include/bdof.h, bdof_set_slice_binning).  Transfer-function
+    # propagator and float32 sweeps only — the float64 twin of 'first-step' does not carry it, so the DEFAULT becomes 'float32'
+    # and an explicit other choice raises; every multiscale level's depth must divide by b.
+    check_binning_path(slice_binning, propagator, kwargs.get('adjoint_precision'))
+    if slice_binning > 1:
+        adjoint_precision = 'float32'
+    for lv in range(multiscale_level):
+        if (int(obj_size[2] / 2 ** lv) if lv else int(obj_size[2])) % slice_binning:
+            raise ValueError('slice_binning={} does not divide the depth of multiscale level {}'.format(slice_binning, 2 ** lv))
 
     print_flush('Reading data...', 0, rank)
     f = h5io.File(os.path.join(save_path, fname))
@@ -168,7 +177,7 @@ def reconstruct_ptychography(fname, probe_pos, probe_size, obj_size, theta_st=0,
                                        psize_cm * ds_level, probe_real, probe_imag, variant=variant, comm=comm, device=comm.local_rank,
                                        coord_ls=coord_ls, propagator=propagator, kernel_size=kwargs.get('kernel_size', 17),
                                        adjoint64={'float32': None, 'float64': True, 'first-step': 'first'}[prec],
-                                       loss_type=loss_type, poisson_multiplier=poisson_multiplier)
+                                       loss_type=loss_type, poisson_multiplier=poisson_multiplier, slice_binning=slice_binning)
         # the DEFAULT's float64 path (first minibatch of an epoch) is an accuracy refinement with buffers of its own (wave + tape in
         # complex128, allocated when the solver is built): where they do not fit beside the engine's the run goes on in float32,
         # SAYS so and records it (summary.txt: adjoint_precision_effective); an explicit request fails.  The retry runs outside the

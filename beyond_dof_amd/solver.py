@@ -22,7 +22,7 @@ from . import _lib
 from ._lib import DeviceBuffer
 from . import util
 from .comm import PseudoComm
-from .engine import MultisliceEngine, RESIDENT_SIZES, check_poisson_path
+from .engine import MultisliceEngine, RESIDENT_SIZES, check_poisson_path, check_binning_path
 
 
 class _VolumeSolver(object):
@@ -349,8 +349,10 @@ class FullfieldSolver(_VolumeSolver):
     def __init__(self, dim_y, dim_x, dim_z, n_theta, minibatch_size, energy_ev, psize_cm, free_prop_cm=None,
                  probe_real=None, probe_imag=None, variant='numpy_skip_last', comm=None, device=0, stream=None,
                  coord_ls=None, propagator='fft', kernel_size=17, recompute=False, rotation='nearest', theta=None, adjoint64=None,
-                 detector_kernel='TF', loss_type='lsq', poisson_multiplier=2e6):
+                 detector_kernel='TF', loss_type='lsq', poisson_multiplier=2e6, slice_binning=1):
         """loss_type / poisson_multiplier: the data term (MultisliceEngine.set_loss; 'poisson' with propagator='fft' only).
+        slice_binning: voxel slices per propagation step (MultisliceEngine); > 1 with propagator='fft', rotation='nearest' and
+        no adjoint64 only.
         propagator='fft': the transfer-function step of np_funcs.py (north-star path); 'conv': the truncated real-space
         kernel of propagation.py, what cnn_propagator/fullfield.py:87,102 calls (kernel_size taps per axis).
         rotation='nearest': the cnn variant's lookup tables, fused into the kernels (cnn_propagator/util.py:294-402);
@@ -358,6 +360,7 @@ class FullfieldSolver(_VolumeSolver):
         `theta` (radians, one per projection): the minibatch's rotated objects are materialised per step
         (bdof_rotate_bilinear), its adjoint is a gather (bdof_rotate_bilinear_adjoint)."""
         check_poisson_path(loss_type, poisson_multiplier, propagator)
+        check_binning_path(slice_binning, propagator, 'float64' if adjoint64 else None, rotation if rotation == 'bilinear' else 'nearest')
         self.conv = propagator == 'conv'
         self.bilinear = rotation == 'bilinear'
         if adjoint64 not in (None, False, True, 'first'):
@@ -377,7 +380,7 @@ class FullfieldSolver(_VolumeSolver):
         self.n_theta, self.mb = int(n_theta), int(minibatch_size)
         self.comm = comm or PseudoComm()
         self.eng = MultisliceEngine(self.dim_y, self.dim_x, self.dim_z, self.mb, with_grad=True, device=device, stream=stream,
-                                    recompute=recompute, adjoint64=adjoint64)
+                                    recompute=recompute, adjoint64=adjoint64, slice_binning=slice_binning)
         self.ctx = self.eng.ctx
         self.eng.set_loss(loss_type, poisson_multiplier)
         self.eng.set_physics(energy_ev, psize_cm, free_prop_cm, variant=variant, detector_kernel=detector_kernel)
@@ -530,11 +533,14 @@ class PtychoSolver(_VolumeSolver):
 
     def __init__(self, obj_size, probe_size, probe_pos, n_theta, minibatch_size, energy_ev, psize_cm, probe_real, probe_imag,
                  variant='numpy_skip_last', comm=None, device=0, stream=None, coord_ls=None, propagator='fft', kernel_size=17,
-                 adjoint64=None, engine=None, loss_type='lsq', poisson_multiplier=2e6):
+                 adjoint64=None, engine=None, loss_type='lsq', poisson_multiplier=2e6, slice_binning=1):
         """loss_type / poisson_multiplier: the data term (MultisliceEngine.set_loss; 'poisson' with propagator='fft' only).
+        slice_binning: voxel slices per propagation step (MultisliceEngine); > 1 with propagator='fft' and no adjoint64 only, and
+        engine=None then takes 'auto' (the resident engine does not carry it).
         engine: None picks the LDS-resident engine for small square probes (below) and the automatic choice otherwise; 'auto',
         'generic', 'streaming' or 'resident' go to MultisliceEngine(engine=...) as they are."""
         check_poisson_path(loss_type, poisson_multiplier, propagator)
+        check_binning_path(slice_binning, propagator, 'float64' if adjoint64 else None)
         self.conv = propagator == 'conv'
         self.dim_y, self.dim_x, self.dim_z = [int(s) for s in obj_size]
         self.py, self.px = int(probe_size[0]), int(probe_size[1])
@@ -545,9 +551,9 @@ class PtychoSolver(_VolumeSolver):
         # small square probes: the LDS-resident engine (one launch per minibatch) also for the minibatches of ~20 positions the
         # drivers use, where the automatic choice would take the launch-bound streaming kernels for 64^2 / 128^2
         if engine is None:
-            engine = 'resident' if self.py == self.px and self.py in RESIDENT_SIZES and not self.conv else 'auto'
+            engine = 'resident' if self.py == self.px and self.py in RESIDENT_SIZES and not self.conv and slice_binning == 1 else 'auto'
         self.eng = MultisliceEngine(self.py, self.px, self.dim_z, self.mb, with_grad=True, device=device, stream=stream, engine=engine,
-                                    adjoint64=adjoint64 is True and not self.conv)
+                                    adjoint64=adjoint64 is True and not self.conv, slice_binning=slice_binning)
         self.ctx = self.eng.ctx
         self.eng.set_loss(loss_type, poisson_multiplier)
         self.eng.set_physics(energy_ev, psize_cm, 'inf', variant=variant)   # free_prop_cm='inf', ptychography.py:76

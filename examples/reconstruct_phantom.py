@@ -7,10 +7,12 @@ the far field with a plane probe (one bright bin) it does not converge — prope
 reference.
 
     python examples/reconstruct_phantom.py [n=128] [n_theta=60] [n_epochs=100] [learning_rate=2e-8] [free_prop_cm=1e-3] [minibatch=10]
-                                           [propagator=fft] [--loss lsq|poisson] [--poisson-multiplier 2e6]
+                                           [propagator=fft] [--loss lsq|poisson] [--poisson-multiplier 2e6] [--slice-binning 1]
 
 --loss poisson minimises the photon-counting likelihood (loss_type='poisson'); its data term is ~ 2 * multiplier times the
 least-squares one, and the L1 weights are scaled with it here.
+--slice-binning b reconstructs with one propagation step per b voxel slices (slice_binning=b); the data are always simulated
+with one step per voxel slice.
 """
 import os
 import sys
@@ -36,7 +38,7 @@ def phantom(n, rng):
     return d
 
 
-def run(n=128, n_theta=60, n_epochs=100, lr=2e-8, fp=1e-3, quiet=False, mb=10, propagator='fft', loss='lsq', multiplier=2e6):
+def run(n=128, n_theta=60, n_epochs=100, lr=2e-8, fp=1e-3, quiet=False, mb=10, propagator='fft', loss='lsq', multiplier=2e6, slice_binning=1):
     """Simulate, write exchange/data, reconstruct, compare with the phantom: returns the figures main() prints
     (tests/test_gpu_convergence.py asserts them)."""
     import contextlib
@@ -59,7 +61,7 @@ def run(n=128, n_theta=60, n_epochs=100, lr=2e-8, fp=1e-3, quiet=False, mb=10, p
                                            minibatch_size=mb, energy_ev=5000, psize_cm=1e-7, free_prop_cm=fp, save_path='case',
                                            output_folder='out', shrink_cycle=None, seed=3, alpha_d=1e-9 * reg, alpha_b=1e-10 * reg, gamma=0,
                                            initial_guess=[np.zeros_like(d), np.zeros_like(d)], propagator=propagator,
-                                           loss_type=loss, poisson_multiplier=multiplier)
+                                           loss_type=loss, poisson_multiplier=multiplier, slice_binning=slice_binning)
         dt = time.time() - t0
         os.chdir(cwd)
     inner = (slice(n // 4, -n // 4),) * 3
@@ -83,6 +85,7 @@ def _option(name, default):
 def main():
     loss = _option('--loss', 'lsq')
     multiplier = float(_option('--poisson-multiplier', 2e6))
+    slice_binning = int(_option('--slice-binning', 1))
     n = int(sys.argv[1]) if len(sys.argv) > 1 else 128
     n_theta = int(sys.argv[2]) if len(sys.argv) > 2 else 60
     n_epochs = int(sys.argv[3]) if len(sys.argv) > 3 else 100
@@ -91,7 +94,9 @@ def main():
     fp = 'inf' if fp == 'inf' else float(fp)
     mb = int(sys.argv[6]) if len(sys.argv) > 6 else 10
     propagator = sys.argv[7] if len(sys.argv) > 7 else 'fft'
-    r = run(n, n_theta, n_epochs, lr, fp, mb=mb, propagator=propagator, loss=loss, multiplier=multiplier)
+    r = run(n, n_theta, n_epochs, lr, fp, mb=mb, propagator=propagator, loss=loss, multiplier=multiplier, slice_binning=slice_binning)
+    if slice_binning > 1:
+        print('slice_binning {}: {} propagation steps per angle'.format(slice_binning, n // slice_binning))
     print('reconstruct_fullfield (propagator {}, loss {}) {}^3, {} angles, {} epochs in minibatches of {}: {:.1f} s ({:.1f} ms per Adam step, entry point to files)'.format(
         propagator, loss, n, n_theta, n_epochs, mb, r['seconds'], 1e3 * r['seconds'] / (n_epochs * max(1, n_theta // mb))))
     print('delta: correlation with the phantom {:.4f} (central half {:.4f}); relative L2 error {:.3f}; peak {:.3e} vs {:.3e}'.format(

@@ -74,6 +74,27 @@ int bdof_timer_elapsed(bdof_ctx* ctx, int slot_a, int slot_b, double* ms);
  * (cnn_propagator/np_funcs.py:20,43) and of autograd's tape (cnn_propagator/fullfield.py:329). */
 int bdof_configure(bdof_ctx* ctx, int NY, int NX, int S, int Bmax, int with_grad);
 
+/* Slice binning: one propagation step per `bin` voxel slices (Adorym's `binning`; a step only has to stay below the depth of
+ * focus).  S of bdof_configure stays the VOXEL depth — the stride of tab[angle][z][x], of the rows (b*S+z)*NX+x and of the
+ * rotated-frame gradient [B][S][NX][NY] — and n = S / bin steps are taken: for step i = 0 .. n-1
+ *     c_i = prod_j exp(i k delta[i bin + j] - k beta[i bin + j]), j < bin   (k per voxel, unchanged; exact for phase and absorption)
+ *     phi_i = c_i psi_i ;  psi_{i+1} = P_bin phi_i,  P_bin the transfer-function step of get_kernel(bin * delta_nm, ...)
+ * with the step taken for i < n-1 (numpy_skip_last) or every i (tf_all) as without binning; detector step, loss and seed are
+ * unchanged.  Every voxel slice of a bin receives the bin's one gradient row, g_delta[i bin + j] = k Im(conj(phi_i) G(phi_i)),
+ * g_beta[i bin + j] = -k Re(conj(phi_i) G(phi_i)).  bin = 1 is the model without the option, bit for bit.
+ * Call order: bdof_configure, bdof_set_slice_binning, bdof_set_physics (hs, h00 and the tables of bdof_set_transfer_f64 /
+ * bdof_set_probe_field built for bin * delta_nm; k and the detector tables as before), then probe and object as usual.
+ * bdof_configure puts bin back to 1 (not sticky, unlike bdof_set_loss).  bin >= 1 and S % bin == 0, else an argument error (a
+ * shorter last bin is not carried); after bdof_set_physics / bdof_set_probe a state error.  The call sizes the tape to n fields
+ * per wavefield; the carrier-field stack of bdof_set_probe_stack has n planes, bdof_tape_to_real takes i < n, the carrier
+ * scalars and the dithered constants run over the steps.
+ * With bin > 1 only the streaming and the generic-size engine run (never the LDS-resident one), and what does not carry the
+ * option returns a state error instead of running the unbinned model: a ctx configured with BDOF_CFG_ALWAYS_RESIDENT,
+ * BDOF_CFG_RECOMPUTE, BDOF_CFG_ADJOINT64 or BDOF_CFG_NO_GROT (refused here), bdof_set_conv and every *_conv* call, bdof_set_tf_f64 /
+ * bdof_loss_grad_tf_f64, bdof_forward_range*, bdof_adjoint_range, bdof_set_range_carrier / bdof_range_carrier_build and
+ * bdof_set_object_bilinear. */
+int bdof_set_slice_binning(bdof_ctx* ctx, int bin);
+
 /* Physics.  k = 2*PI*delta_nm/lambda_nm (np_funcs.py:32).  hs / hs_det: HOST arrays [NX][NY] complex,
  * hs[kx][ky] = ifftshift(get_kernel(...))[ky][kx] / (NX*NY)   (cnn_propagator/util.py:82-102, np_funcs.py:42);
  * the host computes them in float64 exactly as the reference does and rounds once to float32.
