@@ -88,6 +88,7 @@ _SIGNATURES = {
     'bdof_enable_probe_grad': (ctypes.c_int, [_vp, ctypes.c_int]),
     'bdof_probe_grad': (ctypes.c_int, [_vp, _vp, ctypes.c_int]),
     'bdof_grot': (_vp, [_vp]),
+    'bdof_modulation_table': (ctypes.c_int, [_vp, ctypes.POINTER(_vp), ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_double)]),
     'bdof_rotation_adjoint': (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp, ctypes.c_int, ctypes.c_float]),
     'bdof_rotation_adjoint_rows': (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_float]),
     'bdof_rotate_bilinear': (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int, _vp]),

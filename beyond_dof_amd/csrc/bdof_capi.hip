@@ -2681,6 +2681,19 @@ int bdof_get_loss(bdof_ctx* c, double* loss) {
 
 void* bdof_grot(bdof_ctx* c) { return c ? (void*)c->grot : nullptr; }
 
+int bdof_modulation_table(bdof_ctx* c, const void** table, size_t* n, double* mean_m1) {
+    if (!c || !table || !n) return BDOF_ERR_ARG;
+    if (int r = need_configured(c)) return r;
+    if (!c->have_physics) return fail(c, BDOF_ERR_STATE, "bdof_set_physics has not been called");
+    if (!c->obj_src && !c->obj_bound_mod) return fail(c, BDOF_ERR_STATE, "bdof_set_object has not been called");
+    HIPC(c, hipSetDevice(c->device));
+    if (int r = ensure_modulation(c)) return r;
+    *table = (const float2*)c->mod;
+    *n = c->obj_rows * (size_t)c->obj.volNY;
+    if (mean_m1) { mean_m1[0] = c->cbm1.real(); mean_m1[1] = c->cbm1.imag(); }
+    return 0;
+}
+
 int bdof_rotation_adjoint_rows(bdof_ctx* c, int B, const int* angle_of_b, void* gvol, int row0, int n_rows, int accumulate,
                                float scale) {
     if (!c || !gvol || !angle_of_b) return BDOF_ERR_ARG;

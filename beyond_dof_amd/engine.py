@@ -395,6 +395,17 @@ class MultisliceEngine(object):
         self._keep['tab'] = tab_buf
         self.ctx.check(self.lib.bdof_set_object(self.h, _lib._ptr(vol_buf), int(n_rows), int(vol_ny), _lib._ptr(tab_buf), int(vol_nx), int(n_angles)))
 
+    def modulation_table(self):
+        """The table of modulation factors c - 1 the sweeps read (bdof_modulation_table, include/bdof.h), built if stale:
+        (complex64 array of one entry per (delta, beta) pair in the bound object's order, complex mean c - 1 as the host
+        carries it — of a bin with slice_binning > 1, 0 when no mean rides on the carrier)."""
+        table, n, mean = _lib._vp(), ctypes.c_size_t(0), (ctypes.c_double * 2)()
+        self.ctx.check(self.lib.bdof_modulation_table(self.h, ctypes.byref(table), ctypes.byref(n), mean))
+        self.ctx.sync()
+        out = np.empty(n.value, dtype=np.complex64)
+        self.ctx.check(self.lib.bdof_memcpy_d2h(self.h, out.ctypes.data, table.value, out.nbytes))
+        return out, complex(mean[0], mean[1])
+
     def set_rotation_adjoint(self, off_buf, order_buf, n_dest):
         self._keep['off'] = off_buf
         self._keep['order'] = order_buf
@@ -409,8 +420,24 @@ class MultisliceEngine(object):
             return np.ascontiguousarray(np.fft.fftshift(w, axes=(1, 2)))   # np_funcs.py:48
         return np.ascontiguousarray(buf.download((B, self.nx, self.ny), np.complex64).transpose(0, 2, 1))
 
+    def choose_residual_split(self, meas_abs):
+        """Decide, for the amplitudes about to be handed over, whether the residual stays split (bdof_set_meas_mode), and return
+        meas_ref.  float32(m - |a0|) is finer than float32(m) only while the amplitudes stay near |a0|.  Behind an object that
+        takes most of the wave away (|cbar|^S << 1: the carrier has died out, m << |a0|) it is coarser — at m = 1e-4 |a0| by
+        three digits, which is then the error of every residual — so for amplitudes that lie closer to 0 than to |a0| on average
+        the splitting is switched off, until the next set_probe.  Called where amplitudes are bound: loss_grad for an array it
+        uploads itself, FullfieldSolver.set_measurements for the resident stack.  Everything laid out earlier with the other
+        reference must be laid out again (meas_layout) after the mode changed."""
+        if self.meas_ref:
+            m64 = np.asarray(meas_abs, dtype=np.float64)
+            if m64.size and np.abs(m64 - self.meas_ref).mean() > np.abs(m64).mean():
+                self.meas_ref = 0.0
+                self.ctx.check(self.lib.bdof_set_meas_mode(self.h, 0))
+        return self.meas_ref
+
     def meas_layout(self, meas_abs):
-        """|measured| (n, Y, X) in the index order libbdof's loss kernels read it."""
+        """|measured| (n, Y, X) as libbdof's loss kernels read it under the mode in force: m - meas_ref (residual splitting; 0
+        without it) rounded once to float32, in the kernels' index order.  Changes nothing on the engine."""
         if self.meas_ref:
             m = (np.asarray(meas_abs, dtype=np.float64) - self.meas_ref).astype(np.float32)      # subtract in float64, round once
         else:
@@ -420,6 +447,7 @@ class MultisliceEngine(object):
         return np.ascontiguousarray(m.transpose(0, 2, 1))
 
     def _meas_to_device(self, meas_abs):
+        self.choose_residual_split(meas_abs)
         return DeviceBuffer.from_host(self.ctx, self.meas_layout(meas_abs))
 
     def _idx_bufs(self, *lists):

@@ -426,7 +426,9 @@ class FullfieldSolver(_VolumeSolver):
                                                     int(self.conv)))
 
     def set_measurements(self, prj_abs):
-        """|prj| for every angle, (n_theta, Y, X) (loss uses np.abs(this_prj_batch), fullfield.py:106)."""
+        """|prj| for every angle, (n_theta, Y, X) (loss uses np.abs(this_prj_batch), fullfield.py:106).  The residual stays split
+        or not by what these amplitudes are (MultisliceEngine.choose_residual_split)."""
+        self.eng.choose_residual_split(prj_abs)
         self.meas = DeviceBuffer.from_host(self.ctx, self.eng.meas_layout(prj_abs))
 
     # ---- one Adam iteration ------------------------------------------------------------------

@@ -351,6 +351,15 @@ int bdof_loss_grad_tf_f64(bdof_ctx* ctx, int B, const int* angle_of_b, const int
 int bdof_forward_conv(bdof_ctx* ctx, int B, const int* angle_of_b, const int* xoff, const int* yoff, void* out_wave);
 int bdof_loss_grad_conv(bdof_ctx* ctx, int B, const int* angle_of_b, const int* xoff, const int* yoff, const float* meas, void* out_wave);
 void* bdof_grot(bdof_ctx* ctx);      /* device [B][S][NX][NY] pairs */
+/* Read-only view of the table of modulation factors c - 1 = exp(i k delta) exp(-k beta) - 1 that every sweep reads: one entry per
+ * (delta, beta) pair of the bound object, in the object's own order.  Builds the table if it is stale (the pass the sweeps run),
+ * with the k of bdof_set_physics or of the last sweep (the real-space propagator's differs).  table: the device address, n: its
+ * length in float2 entries; mean_m1 (nullable, [2]): the mean factor minus one that the host forms the carrier scalars from —
+ * with slice binning that of a bin, cbar^bin - 1; (0, 0) when no mean rides on the carrier (no plane-wave part in the probe, a
+ * carrier field, the real-space propagator).  Valid until the object, the physics or the probe change.  BDOF_ERR_STATE without
+ * an object or without physics, and when the object was bound by bdof_set_object_bilinear and the physics or the probe changed
+ * since (there are no (delta, beta) rows to build the table from: bind it again).  Domain and accuracy of the factors: DESIGN §5. */
+int bdof_modulation_table(bdof_ctx* ctx, const void** table, size_t* n, double* mean_m1);
 
 /* Adjoint of the rotation gather: gvol[dest][y] (+)= scale * sum over the batch of the rows gathered
  * from dest.  gvol: device [n_dest][NY] pairs. */
