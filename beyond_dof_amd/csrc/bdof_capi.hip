@@ -177,6 +177,15 @@ struct bdof_ctx : Workspace {
     size_t obj_rows = 0;
     DevBuf<float2> mod;                         // c - 1 table of those rows (k_modulation_table)
     bool mod_dirty = true;
+    // bdof_rotation_adjoint_adam left the table of ANOTHER volume (its x_new) in c->mod, with the row sums of the factors in
+    // cbar_dev[0, mod_for_rows) and their mean at cbar_dev[mod_for_mean_at]: the next bdof_set_object takes the table over if it binds exactly
+    // that volume (the record is good for that one call; everything that writes c->mod or cbar_dev drops it)
+    const float2* mod_for = nullptr;
+    size_t mod_for_rows = 0;
+    int mod_for_NY = 0;
+    bool mod_for_mean = false;                  // want_cbar when the table was written
+    size_t mod_for_mean_at = 0;                 // where in cbar_dev the mean is
+    bool mod_mean_pending = false;              // the table was taken over: its mean is still on the device (ensure_modulation)
     int n_angles = 0;
     int adj_ndest = 0;
     DevBuf<float2> winpad;                      // [S][volNX][volNY] rotated-frame gradient of the ptychography windows
@@ -696,14 +705,13 @@ static int modulation_room(bdof_ctx* c, size_t n, bool mean) {
     return 0;
 }
 // after a pass that left c - 1 in c->mod (and `grid` partial sums in cbar_dev if mean): mean to the host, object bound
-static int modulation_done(bdof_ctx* c, size_t n, int grid, bool mean) {
-    HIPC(c, hipGetLastError());
+// c - 1 is in c->mod and, if mean, its mean in cbar_dev[at]: mean to the host, object bound
+static int modulation_bound(bdof_ctx* c, size_t at, bool mean) {
     std::complex<double> cb(0.0, 0.0);
     if (mean) {
         // cbar is needed by the HOST (it forms the carrier scalars in float64): one small read-back per object update
-        hipLaunchKernelGGL(k_sum_mean, dim3(1), dim3(256), 0, c->stream, c->cbar_dev, grid, 1.0 / (double)n, c->cbar_dev + grid);
         double2 m;
-        HIPC(c, hipMemcpyAsync(&m, c->cbar_dev + grid, sizeof(double2), hipMemcpyDeviceToHost, c->stream));
+        HIPC(c, hipMemcpyAsync(&m, c->cbar_dev + at, sizeof(double2), hipMemcpyDeviceToHost, c->stream));
         HIPC(c, hipStreamSynchronize(c->stream));
         cb = std::complex<double>(m.x, m.y);
         // slice binning: a step's carrier picks up the mean factor of its whole bin, cbar^bin (exact algebra for any cbar)
@@ -712,11 +720,20 @@ static int modulation_done(bdof_ctx* c, size_t n, int grid, bool mean) {
     if (cb != c->cbm1) { c->cbm1 = cb; c->res_dirty = true; }
     c->obj.vol = c->mod;
     c->mod_dirty = false;
+    c->mod_mean_pending = false;
     return 0;
+}
+static int modulation_done(bdof_ctx* c, size_t n, int grid, bool mean) {
+    HIPC(c, hipGetLastError());
+    c->mod_for = nullptr;
+    if (mean) hipLaunchKernelGGL(k_sum_mean, dim3(1), dim3(256), 0, c->stream, c->cbar_dev, grid, 1.0 / (double)n, c->cbar_dev + grid);
+    return modulation_bound(c, grid, mean);
 }
 
 static int ensure_modulation(bdof_ctx* c) {
-    if (!c->mod_dirty) return 0;
+    // (a table taken over from bdof_rotation_adjoint_adam stands only while the mean rides on the carrier as it did then)
+    if (!c->mod_dirty && c->mod_mean_pending && c->mod_for_mean != want_cbar(c)) c->mod_dirty = true;
+    if (!c->mod_dirty) return c->mod_mean_pending ? modulation_bound(c, c->mod_for_mean_at, c->mod_for_mean) : 0;
     if (!c->obj_src) return fail(c, BDOF_ERR_STATE, "the object was bound as modulation factors (bdof_set_object_bilinear): bind it again for this propagator");
     const size_t n = c->obj_rows * (size_t)c->obj.volNY;
     const bool mean = want_cbar(c);
@@ -1512,10 +1529,14 @@ int bdof_set_object(bdof_ctx* c, const void* vol, long long n_rows, int volNY, c
     if (volNY < 1) return fail(c, BDOF_ERR_ARG, "volNY must be >= 1");
     if (tab && (volNX < 1 || n_angles < 1)) return fail(c, BDOF_ERR_ARG, "volNX and n_angles must be >= 1 with a table");
     if (!tab && volNY != c->NY) return fail(c, BDOF_ERR_ARG, "without a rotation table volNY must equal NY");
+    // the volume bdof_rotation_adjoint_adam has just left the table of: nothing to rebuild
+    const bool current = c->mod_for && vol == (const void*)c->mod_for && (size_t)n_rows == c->mod_for_rows && volNY == c->mod_for_NY;
+    c->mod_for = nullptr;
     c->obj_src = (const float2*)vol;
     c->obj_bound_mod = false;
     c->obj_rows = (size_t)n_rows;
-    c->mod_dirty = true;
+    c->mod_dirty = !current;
+    c->mod_mean_pending = current;
     c->obj.vol = nullptr;
     c->obj.volNY = volNY;
     c->obj.tab = tab;
@@ -2705,13 +2726,14 @@ int bdof_rotation_adjoint_rows(bdof_ctx* c, int B, const int* angle_of_b, void* 
     if (n_rows == 0) return 0;
     HIPC(c, hipSetDevice(c->device));
     ProfScope ps(c, BDOF_K_ROT_ADJ);
-    RotAdjArgs a{c->grot, (float2*)gvol, c->adj_off, c->adj_order, angle_of_b, B, c->S * c->NX, c->adj_ndest, c->NY, accumulate, scale,
-                 c->heavy, c->heavy + 1, row0, row0 + n_rows};
+    RotAdjK<false> a;
+    static_cast<RotAdjArgs&>(a) = RotAdjArgs{c->grot, (float2*)gvol, c->adj_off, c->adj_order, angle_of_b, B, c->S * c->NX, c->adj_ndest, c->NY,
+                                             accumulate, scale, c->heavy, c->heavy + 1, row0, row0 + n_rows};
     HIPC(c, hipMemsetAsync(c->heavy, 0, sizeof(int), c->stream));
     int need = (n_rows + 3) / 4;
     int grid = need < c->ncu * 8 ? need : c->ncu * 8;
-    hipLaunchKernelGGL(k_rot_adjoint, dim3(grid), dim3(256), 0, c->stream, a);
-    hipLaunchKernelGGL(k_rot_adjoint_heavy, dim3(c->ncu * 8), dim3(256), 0, c->stream, a);
+    hipLaunchKernelGGL(k_rot_adjoint<false>, dim3(grid), dim3(256), 0, c->stream, a);
+    hipLaunchKernelGGL(k_rot_adjoint_heavy<false>, dim3(c->ncu * 8), dim3(256), 0, c->stream, a);
     return launched(c);
 }
 
@@ -2751,13 +2773,27 @@ int bdof_window_rotation_adjoint(bdof_ctx* c, int B, int angle, const int* xoff,
     hipLaunchKernelGGL(k_window_overlap_add, dim3(c->obj.volNX, (c->S + z_per_wg - 1) / z_per_wg), dim3(256), 0, c->stream, a,
                        c->winpad, z_per_wg);
     // stage 2: rotated frame -> volume (the full-field rotation adjoint with a batch of one)
-    RotAdjArgs r{c->winpad, (float2*)gvol, c->adj_off, c->adj_order, c->win_angle, 1, n_src, c->adj_ndest, c->obj.volNY, accumulate,
-                 scale, c->heavy, c->heavy + 1, 0, c->adj_ndest};
+    RotAdjK<false> r;
+    static_cast<RotAdjArgs&>(r) = RotAdjArgs{c->winpad, (float2*)gvol, c->adj_off, c->adj_order, c->win_angle, 1, n_src, c->adj_ndest, c->obj.volNY,
+                                             accumulate, scale, c->heavy, c->heavy + 1, 0, c->adj_ndest};
     HIPC(c, hipMemsetAsync(c->heavy, 0, sizeof(int), c->stream));
     const int needwg = (c->adj_ndest + 3) / 4;
-    hipLaunchKernelGGL(k_rot_adjoint, dim3(needwg < c->ncu * 8 ? needwg : c->ncu * 8), dim3(256), 0, c->stream, r);
-    hipLaunchKernelGGL(k_rot_adjoint_heavy, dim3(c->ncu * 8), dim3(256), 0, c->stream, r);
+    hipLaunchKernelGGL(k_rot_adjoint<false>, dim3(needwg < c->ncu * 8 ? needwg : c->ncu * 8), dim3(256), 0, c->stream, r);
+    hipLaunchKernelGGL(k_rot_adjoint_heavy<false>, dim3(c->ncu * 8), dim3(256), 0, c->stream, r);
     return launched(c);
+}
+
+static AdamArgs adam_args(const void* x_old, void* x_new, const void* g, void* m, void* v, const float* mask, int NXv, int NZv, int NYv,
+                          float g_scale, float alpha_d, float alpha_b, float gamma, float lr, float b1, float b2, float eps, int i_batch,
+                          int clip, int x0, int nx) {
+    // b1, b2 arrive as float32 (0.999f = 0.99900001287...); the reference's are Python floats.  The decimal the caller meant is
+    // recovered (7 significant digits) so that 1 - b and the bias corrections are those of the float64 reference.
+    const double b1d = std::round((double)b1 * 1e7) / 1e7, b2d = std::round((double)b2 * 1e7) / 1e7;
+    const double bc1 = 1.0 - std::pow(b1d, (double)(i_batch + 1));
+    const double bc2 = 1.0 - std::pow(b2d, (double)(i_batch + 1));
+    return AdamArgs{(const float2*)x_old, (float2*)x_new, (const float2*)g, (float2*)m, (float2*)v, mask, NXv, NZv, NYv,
+                    g_scale, alpha_d, alpha_b, gamma, lr, (float)b1d, (float)b2d, eps, (float)(1.0 / bc1), (float)(1.0 / bc2),
+                    (float)(1.0 - b1d), (float)(1.0 - b2d), clip, x0, x0 + nx};
 }
 
 int bdof_adam_step_slab(bdof_ctx* c, const void* x_old, void* x_new, const void* g, void* m, void* v, const float* mask,
@@ -2770,14 +2806,8 @@ int bdof_adam_step_slab(bdof_ctx* c, const void* x_old, void* x_new, const void*
     if (nx == 0) return 0;
     HIPC(c, hipSetDevice(c->device));
     ProfScope ps(c, BDOF_K_ADAM);
-    // b1, b2 arrive as float32 (0.999f = 0.99900001287...); the reference's are Python floats.  The decimal the caller meant is
-    // recovered (7 significant digits) so that 1 - b and the bias corrections are those of the float64 reference.
-    const double b1d = std::round((double)b1 * 1e7) / 1e7, b2d = std::round((double)b2 * 1e7) / 1e7;
-    const double bc1 = 1.0 - std::pow(b1d, (double)(i_batch + 1));
-    const double bc2 = 1.0 - std::pow(b2d, (double)(i_batch + 1));
-    AdamArgs a{(const float2*)x_old, (float2*)x_new, (const float2*)g, (float2*)m, (float2*)v, mask, NXv, NZv, NYv,
-               g_scale, alpha_d, alpha_b, gamma, lr, (float)b1d, (float)b2d, eps, (float)(1.0 / bc1), (float)(1.0 / bc2),
-               (float)(1.0 - b1d), (float)(1.0 - b2d), clip, x0, x0 + nx};
+    const AdamArgs a = adam_args(x_old, x_new, g, m, v, mask, NXv, NZv, NYv, g_scale, alpha_d, alpha_b, gamma, lr, b1, b2, eps, i_batch, clip,
+                                 x0, nx);
     const size_t n = (size_t)nx * NZv * NYv;
     size_t need = (n + 255) / 256;
     int grid = need < (size_t)c->ncu * 16 ? (int)need : c->ncu * 16;
@@ -2791,6 +2821,65 @@ int bdof_adam_step(bdof_ctx* c, const void* x_old, void* x_new, const void* g, v
                    float lr, float b1, float b2, float eps, int i_batch, int clip) {
     return bdof_adam_step_slab(c, x_old, x_new, g, m, v, mask, NXv, NZv, NYv, g_scale, alpha_d, alpha_b, gamma, lr, b1, b2, eps,
                                i_batch, clip, 0, NXv);
+}
+
+// The tail of a step on one rank in one pass over the volume: bdof_rotation_adjoint_rows + bdof_adam_step + the modulation
+// table of x_new (k_rot_adjoint<true>, k_rot_adjoint_heavy<true>, k_sum_chunks + k_sum_mean over the row sums).
+int bdof_rotation_adjoint_adam(bdof_ctx* c, int B, const int* angle_of_b, void* gvol, int row0, int n_rows, int accumulate, float scale,
+                               const void* x_old, void* x_new, void* m, void* v, const float* mask, int NXv, int NZv, int NYv,
+                               float g_scale, float alpha_d, float alpha_b, float gamma, float lr, float b1, float b2, float eps,
+                               int i_batch, int clip) {
+    if (!c || !angle_of_b || !x_old || !x_new || !m || !v) return BDOF_ERR_ARG;
+    if (int r = need_configured(c)) return r;
+    const char* who = "bdof_rotation_adjoint_adam";
+    if (accumulate) return fail(c, BDOF_ERR_STATE, std::string(who) + " does not carry accumulate: the update needs the whole gradient (bdof_rotation_adjoint_rows, then bdof_adam_step)");
+    if (c->obj_bound_mod) return fail(c, BDOF_ERR_STATE, std::string(who) + " does not carry the bilinear rotation (bdof_set_object_bilinear): bdof_rotate_bilinear_adjoint, then bdof_adam_step");
+    if (!c->obj_src) return fail(c, BDOF_ERR_STATE, std::string(who) + " needs an object bound as (delta, beta) rows (bdof_set_object)");
+    if (!c->grot) return fail(c, BDOF_ERR_STATE, "no gradient workspace (configure with_grad=1)");
+    if (!c->adj_off) return fail(c, BDOF_ERR_STATE, "bdof_set_rotation_adjoint has not been called");
+    if (row0 != 0 || n_rows != c->adj_ndest) return fail(c, BDOF_ERR_STATE, std::string(who) + " does not carry a row range: it updates the whole volume (bdof_rotation_adjoint_rows, then bdof_adam_step_slab)");
+    if (int r = check_batch(c, B)) return r;
+    if (c->NY % 2) return fail(c, BDOF_ERR_SIZE, "the rotation adjoint needs an even NY");
+    if (x_old == x_new) return fail(c, BDOF_ERR_ARG, "x_new must not alias x_old (the TV stencil reads pre-update neighbours)");
+    if (NXv < 1 || NZv < 1 || NYv < 1 || i_batch < 0) return fail(c, BDOF_ERR_ARG, "bad volume shape / i_batch");
+    if (NYv != c->NY || (long long)NXv * NZv != c->adj_ndest || c->obj_rows != (size_t)c->adj_ndest || c->obj.volNY != NYv)
+        return fail(c, BDOF_ERR_ARG, "the volume must be the bound object's: [NXv][NZv] = the rotation adjoint's destination rows, of NY pairs");
+    if (!c->have_physics) return fail(c, BDOF_ERR_STATE, "bdof_set_physics has not been called");
+    HIPC(c, hipSetDevice(c->device));
+    const size_t n = (size_t)c->adj_ndest * NYv;
+    const bool mean = want_cbar(c);
+    HIPC(c, c->mod.room(n));
+    // row sums [n_dest], their sums chunk by chunk [n_chunks], the mean
+    const int chunk = 1024, n_chunks = (c->adj_ndest + chunk - 1) / chunk;
+    const size_t mean_at = (size_t)c->adj_ndest + n_chunks;
+    if (mean) HIPC(c, c->cbar_dev.room(std::max((size_t)c->ncu * 16, mean_at) + 1));
+    // c->mod stops being the bound object's table here
+    c->mod_dirty = true;
+    c->mod_mean_pending = false;
+    c->mod_for = nullptr;
+    ProfScope ps(c, BDOF_K_ROT_ADJ);
+    RotAdjK<true> a;
+    static_cast<RotAdjArgs&>(a) = RotAdjArgs{c->grot, (float2*)gvol, c->adj_off, c->adj_order, angle_of_b, B, c->S * c->NX, c->adj_ndest, c->NY,
+                                             0, scale, c->heavy, c->heavy + 1, 0, c->adj_ndest};
+    a.adam = adam_args(x_old, x_new, nullptr, m, v, mask, NXv, NZv, NYv, g_scale, alpha_d, alpha_b, gamma, lr, b1, b2, eps, i_batch, clip, 0, NXv);
+    a.mod = c->mod;
+    a.rowsum = mean ? (double2*)c->cbar_dev : nullptr;
+    a.k = c->k;
+    HIPC(c, hipMemsetAsync(c->heavy, 0, sizeof(int), c->stream));
+    const int need = (c->adj_ndest + 3) / 4;
+    hipLaunchKernelGGL(k_rot_adjoint<true>, dim3(need < c->ncu * 8 ? need : c->ncu * 8), dim3(256), 0, c->stream, a);
+    hipLaunchKernelGGL(k_rot_adjoint_heavy<true>, dim3(c->ncu * 8), dim3(256), 0, c->stream, a);
+    if (mean) {
+        hipLaunchKernelGGL(k_sum_chunks, dim3(n_chunks), dim3(256), 0, c->stream, c->cbar_dev, c->adj_ndest, chunk, c->cbar_dev + c->adj_ndest);
+        hipLaunchKernelGGL(k_sum_mean, dim3(1), dim3(256), 0, c->stream, c->cbar_dev + c->adj_ndest, n_chunks, 1.0 / (double)n, c->cbar_dev + mean_at);
+    }
+    if (int r = launched(c)) return r;
+    c->mod_for = (const float2*)x_new;
+    c->mod_for_rows = (size_t)c->adj_ndest;
+    c->mod_for_NY = NYv;
+    c->mod_for_mean = mean;
+    c->mod_for_mean_at = mean_at;
+    return 0;
 }
 
 int bdof_rotate_bilinear(bdof_ctx* c, const void* vol, int NXv, int NZv, int NYv, const double* prm, int B, void* out_rows) {
@@ -2817,6 +2906,8 @@ int bdof_set_object_bilinear(bdof_ctx* c, const void* vol, int NXv, int NZv, int
     HIPC(c, hipSetDevice(c->device));
     const size_t nrows = (size_t)B * NZv * NXv, n = nrows * NYv;
     // set the binding first: want_cbar looks at the physics and probe only
+    c->mod_for = nullptr;
+    c->mod_mean_pending = false;
     c->obj_src = nullptr;
     c->obj_bound_mod = true;
     c->obj_rows = nrows;
@@ -2949,8 +3040,16 @@ int bdof_ctx_malloc(bdof_ctx* c, void** ptr, size_t bytes) {
     return 0;
 }
 int bdof_free(void* ptr) { return (int)hipFree(ptr); }
+// the caller writes device memory through the ctx: a table bdof_rotation_adjoint_adam left for that memory is no longer its table
+static void wrote(bdof_ctx* c, const void* dst, size_t bytes) {
+    if (!c->mod_for) return;
+    const char *d = (const char*)dst, *t = (const char*)c->mod_for;
+    if (d < t + c->mod_for_rows * c->mod_for_NY * sizeof(float2) && t < d + bytes) c->mod_for = nullptr;
+}
+
 int bdof_memcpy_h2d(bdof_ctx* c, void* dst, const void* src, size_t bytes) {
     if (!c) return BDOF_ERR_ARG;
+    wrote(c, dst, bytes);
     HIPC(c, hipSetDevice(c->device));
     HIPC(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->stream));
     HIPC(c, hipStreamSynchronize(c->stream));
@@ -2965,6 +3064,7 @@ int bdof_memcpy_d2h(bdof_ctx* c, void* dst, const void* src, size_t bytes) {
 }
 int bdof_memset(bdof_ctx* c, void* dst, int value, size_t bytes) {
     if (!c) return BDOF_ERR_ARG;
+    wrote(c, dst, bytes);
     HIPC(c, hipSetDevice(c->device));
     HIPC(c, hipMemsetAsync(dst, value, bytes, c->stream));
     return 0;
@@ -2972,6 +3072,7 @@ int bdof_memset(bdof_ctx* c, void* dst, int value, size_t bytes) {
 
 int bdof_memcpy_d2d(bdof_ctx* c, void* dst, const void* src, size_t bytes) {
     if (!c) return BDOF_ERR_ARG;
+    wrote(c, dst, bytes);
     HIPC(c, hipSetDevice(c->device));
     HIPC(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, c->stream));
     return 0;

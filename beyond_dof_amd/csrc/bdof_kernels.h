@@ -183,6 +183,24 @@ __global__ __launch_bounds__(256) void k_sum_mean(const double2* partial, int n,
     if (threadIdx.x == 0) out[0] = make_double2(sx[0] * inv_count, sy[0] * inv_count);
 }
 
+// First level over many partial sums (the per-row sums of the one-pass tail, bdof_rotation_adjoint_adam): workgroup b adds
+// partial[b chunk, (b + 1) chunk) in k_sum_mean's fixed order (thread t: t, t + 256, ...; then the tree) into out[b]; k_sum_mean
+// finishes over the gridDim.x results.  (k_sum_mean alone over the 262144 rows of a 512^3 volume took 0.36 ms.)
+__global__ __launch_bounds__(256) void k_sum_chunks(const double2* partial, int n, int chunk, double2* out) {
+    __shared__ double sx[256], sy[256];
+    const int lo = blockIdx.x * chunk, hi = min(n, lo + chunk);
+    double ax = 0.0, ay = 0.0;
+    for (int j = lo + threadIdx.x; j < hi; j += 256) { ax += partial[j].x; ay += partial[j].y; }
+    sx[threadIdx.x] = ax;
+    sy[threadIdx.x] = ay;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) { sx[threadIdx.x] += sx[threadIdx.x + w]; sy[threadIdx.x] += sy[threadIdx.x + w]; }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) out[blockIdx.x] = make_double2(sx[0], sy[0]);
+}
+
 // Loads are unconditional (clamped address) and zeroed afterwards: a branch around each load makes hipcc wait
 // vmcnt(0) per element, i.e. eight dependent memory round trips per row.
 __device__ __forceinline__ void load_obj_row(const ObjView& o, long long srow, int y0, int tid, int T, float2 (&db)[8]) {
@@ -801,6 +819,68 @@ __global__ __launch_bounds__(BDOF_THREADS, RowCfg<NY>::MIN_WAVES) void k_row_bwd
 }
 
 // ---------------------------------------------------------------------------------------------
+// Fused regulariser gradient + Adam + finite-support mask + non-negativity (K9 + K10).
+//   cnn_propagator/fullfield.py:109-118,352-362 ; cnn_propagator/util.py:61-70,280-291
+// Volume layout [X][Z][Y] of (delta, beta) pairs.  Reads x_old, writes x_new (the TV stencil
+// needs the neighbours' pre-update values).
+// ---------------------------------------------------------------------------------------------
+struct AdamArgs {
+    const float2* x_old;
+    float2* x_new;
+    const float2* g;       // data-term gradient (already summed over ranks)
+    float2* m;
+    float2* v;
+    const float* mask;     // nullable [X][Z][Y]
+    int NXv, NZv, NYv;
+    float g_scale;         // 1/size                       cnn_propagator/fullfield.py:351
+    float alpha_d, alpha_b, gamma;
+    float lr, b1, b2, eps, inv_bc1, inv_bc2;   // inv_bc = 1 / (1 - b^(i_batch+1))
+    float om_b1, om_b2;                        // 1 - b1, 1 - b2 formed in float64 on the host (1 - 0.999f is 1.3e-5 off 1e-3)
+    int clip;              // max(x, 0)
+    int x0, x1;            // slab of the volume updated by this launch: x in [x0, x1)  (the stencil reads beyond it)
+};
+
+__device__ __forceinline__ float sgn(float v) { return (v > 0.f) - (v < 0.f); }
+
+// One voxel of the update: L1 + 7-point TV term on x_old (neighbours from global memory), moments (stored here), step, mask,
+// clip.  idx = (x NZv + z) NYv + y; grad() gives the voxel's data-term gradient (a load in k_adam, registers in the fused tail:
+// called where k_adam has always loaded it, so that kernel's code stays what it was).  Leaves the new (delta, beta) in (nd, nb);
+// the caller stores them.  STORE_MV: the moments are stored here, where k_adam has always stored them; else they come back in
+// (m, v) and the caller stores them (the fused tail: two voxels' worth in one 16-byte store).  k_adam and the fused tail of the rotation adjoint (k_rot_adjoint<true>) both run exactly this: the same bits.
+template <bool STORE_MV, class G>
+__device__ __forceinline__ void adam_voxel(const AdamArgs& a, size_t idx, int x, int z, int y, G grad, float& nd, float& nb, float2& m, float2& v) {
+    const float2 xv = a.x_old[idx];
+    const float2 g = grad();
+    float gd = g.x * a.g_scale + a.alpha_d * sgn(xv.x);
+    float gb = g.y * a.g_scale + a.alpha_b * sgn(xv.y);
+    if (a.gamma != 0.f) {
+        const size_t sy = 1, sz = a.NYv, sx = (size_t)a.NZv * a.NYv;
+        const float ym = a.x_old[idx - y * sy + ((y + a.NYv - 1) % a.NYv) * sy].x;
+        const float yp = a.x_old[idx - y * sy + ((y + 1) % a.NYv) * sy].x;
+        const float zm = a.x_old[idx - z * sz + ((z + a.NZv - 1) % a.NZv) * sz].x;
+        const float zp = a.x_old[idx - z * sz + ((z + 1) % a.NZv) * sz].x;
+        const float xm = a.x_old[idx - x * sx + ((x + a.NXv - 1) % a.NXv) * sx].x;
+        const float xp = a.x_old[idx - x * sx + ((x + 1) % a.NXv) * sx].x;
+        const float c = xv.x;
+        gd += a.gamma * (sgn(c - ym) - sgn(yp - c) + sgn(c - zm) - sgn(zp - c) + sgn(c - xm) - sgn(xp - c));
+    }
+    m = a.m[idx];
+    v = a.v[idx];
+    m.x = a.om_b1 * gd + a.b1 * m.x;
+    m.y = a.om_b1 * gb + a.b1 * m.y;
+    v.x = a.om_b2 * gd * gd + a.b2 * v.x;
+    v.y = a.om_b2 * gb * gb + a.b2 * v.y;
+    if constexpr (STORE_MV) {
+        a.m[idx] = m;
+        a.v[idx] = v;
+    }
+    nd = xv.x - a.lr * (m.x * a.inv_bc1) / (sqrtf(v.x * a.inv_bc2) + a.eps);
+    nb = xv.y - a.lr * (m.y * a.inv_bc1) / (sqrtf(v.y * a.inv_bc2) + a.eps);
+    if (a.mask) { const float mk = a.mask[idx]; nd *= mk; nb *= mk; }
+    if (a.clip) { nd = fmaxf(nd, 0.f); nb = fmaxf(nb, 0.f); }
+}
+
+// ---------------------------------------------------------------------------------------------
 // Adjoint of the rotation gather (K1^T), atomics-free and deterministic: every destination row of
 // the volume gradient sums the rotated-frame gradient rows that were gathered from it, through a
 // per-angle inverse (CSR) table.                  adjoint of cnn_propagator/util.py:377-402
@@ -824,10 +904,44 @@ struct RotAdjArgs {
 
 __device__ __forceinline__ void f4acc(float4& a, const float4 s) { a.x += s.x; a.y += s.y; a.z += s.z; a.w += s.w; }
 
+// The one-pass tail of a step on one rank (bdof_rotation_adjoint_adam): the summed gradient row is not stored and read back,
+// the lanes that hold it run Adam on it and leave the new volume's modulation factors as well.  What the kernels get beside
+// RotAdjArgs then (n_dest = NXv NZv, NY = NYv, the whole volume; a.gvol may be null: the gradient itself is not kept):
+template <bool FUSED> struct RotAdjK : RotAdjArgs {};
+template <> struct RotAdjK<true> : RotAdjArgs {
+    AdamArgs adam;            // (adam.g is not read: the gradient arrives in registers)
+    float2* mod;              // [n_dest][NY] modulation factors c - 1 of x_new (what k_modulation_table would make of it)
+    double2* rowsum;          // nullable [n_dest]: per destination row, the float64 sum of its NY factors (for their mean)
+    float k;
+};
+
+// Two voxels of destination row d (the float4 at pair index v) whose gradient is o: Adam, then x_new's modulation factors;
+// their sum is added to (sx, sy).  o has the bits the unfused kernels store, adam_voxel and slice_modulation_m1 are the
+// functions k_adam and k_modulation_table run, so m, v, x_new and the table come out bit for bit.
+__device__ __forceinline__ void rot_adjoint_tail(const RotAdjK<true>& a, int d, int v, float4 o, double& sx, double& sy) {
+    const size_t idx = (size_t)d * a.NY + 2 * (size_t)v;
+    const int x = d / a.adam.NZv, z = d % a.adam.NZv;
+    if (a.gvol) reinterpret_cast<float4*>(a.gvol)[idx >> 1] = o;
+    float2 n0, n1, m0, m1, v0, v1;
+    adam_voxel<false>(a.adam, idx, x, z, 2 * v, [&] { return make_float2(o.x, o.y); }, n0.x, n0.y, m0, v0);
+    adam_voxel<false>(a.adam, idx + 1, x, z, 2 * v + 1, [&] { return make_float2(o.z, o.w); }, n1.x, n1.y, m1, v1);
+    reinterpret_cast<float4*>(a.adam.m)[idx >> 1] = make_float4(m0.x, m0.y, m1.x, m1.y);
+    reinterpret_cast<float4*>(a.adam.v)[idx >> 1] = make_float4(v0.x, v0.y, v1.x, v1.y);
+    reinterpret_cast<float4*>(a.adam.x_new)[idx >> 1] = make_float4(n0.x, n0.y, n1.x, n1.y);
+    const float2 c0 = slice_modulation_m1(n0, a.k), c1 = slice_modulation_m1(n1, a.k);
+    reinterpret_cast<float4*>(a.mod)[idx >> 1] = make_float4(c0.x, c0.y, c1.x, c1.y);
+    sx += (double)c0.x;
+    sy += (double)c0.y;
+    sx += (double)c1.x;
+    sy += (double)c1.y;
+}
+
 // One WAVE per destination row (4 rows per workgroup, no workgroup barrier): lane b looks up batch element b's CSR
 // range, a wave scan places the (batch, source-row) pairs into the wave's LDS list in a fixed order, then the 64 lanes
 // stream the listed 4-KB rows with 16-byte loads, several rows in flight.
-__global__ __launch_bounds__(256) void k_rot_adjoint(RotAdjArgs a) {
+// FUSED: the row's lanes go on with rot_adjoint_tail instead of storing it; lane l's sum of factors runs over its pairs in
+// ascending v, the lanes' sums are added by wave_reduce_sum, lane 0 writes the row's sum.
+template <bool FUSED> __global__ __launch_bounds__(256) void k_rot_adjoint(RotAdjK<FUSED> a) {
     __shared__ int lists[4][BDOF_ROTADJ_MAXLIST];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     int* list = lists[wave];
@@ -868,6 +982,7 @@ __global__ __launch_bounds__(256) void k_rot_adjoint(RotAdjArgs a) {
             continue;
         }
         float4* drow = reinterpret_cast<float4*>(a.gvol + (size_t)d * a.NY);
+        double sx = 0.0, sy = 0.0;
         for (int v0 = 0; v0 < nv; v0 += 256) {
             float4 acc[4];
             bool ok[4];
@@ -892,9 +1007,20 @@ __global__ __launch_bounds__(256) void k_rot_adjoint(RotAdjArgs a) {
             for (int c = 0; c < 4; ++c) {
                 if (!ok[c]) continue;
                 float4 o = make_float4(acc[c].x * a.scale, acc[c].y * a.scale, acc[c].z * a.scale, acc[c].w * a.scale);
-                float4* dst = drow + v0 + c * 64 + lane;
-                if (a.accumulate) f4acc(o, *dst);
-                *dst = o;
+                if constexpr (FUSED) {
+                    rot_adjoint_tail(a, d, v0 + c * 64 + lane, o, sx, sy);
+                } else {
+                    float4* dst = drow + v0 + c * 64 + lane;
+                    if (a.accumulate) f4acc(o, *dst);
+                    *dst = o;
+                }
+            }
+        }
+        if constexpr (FUSED) {
+            if (a.rowsum) {
+                sx = wave_reduce_sum(sx);
+                sy = wave_reduce_sum(sy);
+                if (lane == 0) a.rowsum[d] = make_double2(sx, sy);
             }
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -905,12 +1031,14 @@ __global__ __launch_bounds__(256) void k_rot_adjoint(RotAdjArgs a) {
 
 // Heavy destination rows: one workgroup per row; the source indices are staged through LDS 256 at a time and all
 // threads stream the rows (16 B per lane, 4 rows in flight).  Fixed summation order -> deterministic.
-__global__ __launch_bounds__(256) void k_rot_adjoint_heavy(RotAdjArgs a) {
+// FUSED: as k_rot_adjoint<true>; a thread's sum of factors runs over its pairs in ascending v, block_sum2 adds the threads'.
+template <bool FUSED> __global__ __launch_bounds__(256) void k_rot_adjoint_heavy(RotAdjK<FUSED> a) {
     __shared__ int stage[256];
     const int nheavy = *a.heavy_count;
     const int nv = a.NY / 2;
     for (int i = blockIdx.x; i < nheavy; i += gridDim.x) {
         const int d = a.heavy_rows[i];
+        double sx = 0.0, sy = 0.0;
         for (int v0 = 0; v0 < nv; v0 += 256) {
             const int v = v0 + threadIdx.x;
             float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -940,37 +1068,24 @@ __global__ __launch_bounds__(256) void k_rot_adjoint_heavy(RotAdjArgs a) {
             if (v < nv) {
                 float4* dst = reinterpret_cast<float4*>(a.gvol + (size_t)d * a.NY) + v;
                 float4 o = make_float4(acc.x * a.scale, acc.y * a.scale, acc.z * a.scale, acc.w * a.scale);
-                if (a.accumulate) f4acc(o, *dst);
-                *dst = o;
+                if constexpr (FUSED) {
+                    rot_adjoint_tail(a, d, v, o, sx, sy);
+                } else {
+                    if (a.accumulate) f4acc(o, *dst);
+                    *dst = o;
+                }
+            }
+        }
+        if constexpr (FUSED) {
+            if (a.rowsum) {
+                if (block_sum2<256>(sx, sy)) a.rowsum[d] = make_double2(sx, sy);
+                __syncthreads();                // (block_sum2's LDS slots are written again for the workgroup's next row)
             }
         }
     }
 }
 
-// ---------------------------------------------------------------------------------------------
-// Fused regulariser gradient + Adam + finite-support mask + non-negativity (K9 + K10).
-//   cnn_propagator/fullfield.py:109-118,352-362 ; cnn_propagator/util.py:61-70,280-291
-// Volume layout [X][Z][Y] of (delta, beta) pairs.  Reads x_old, writes x_new (the TV stencil
-// needs the neighbours' pre-update values).
-// ---------------------------------------------------------------------------------------------
-struct AdamArgs {
-    const float2* x_old;
-    float2* x_new;
-    const float2* g;       // data-term gradient (already summed over ranks)
-    float2* m;
-    float2* v;
-    const float* mask;     // nullable [X][Z][Y]
-    int NXv, NZv, NYv;
-    float g_scale;         // 1/size                       cnn_propagator/fullfield.py:351
-    float alpha_d, alpha_b, gamma;
-    float lr, b1, b2, eps, inv_bc1, inv_bc2;   // inv_bc = 1 / (1 - b^(i_batch+1))
-    float om_b1, om_b2;                        // 1 - b1, 1 - b2 formed in float64 on the host (1 - 0.999f is 1.3e-5 off 1e-3)
-    int clip;              // max(x, 0)
-    int x0, x1;            // slab of the volume updated by this launch: x in [x0, x1)  (the stencil reads beyond it)
-};
-
-__device__ __forceinline__ float sgn(float v) { return (v > 0.f) - (v < 0.f); }
-
+// The sweep over the volume with the gradient in memory (several ranks, accumulation, bilinear rotation, ptychography).
 // (Round 3 measured the alternative the round-2 review suggested — one thread per (z, y) column walking x with the x-neighbours
 // of the TV stencil in registers: L2 <-> fabric traffic of a 512^3 step 10.2 -> 8.7 GB as intended, kernel time 1.58 -> 1.97 ms:
 // every workgroup then reads 2-KB pieces 2 MB apart, and what the stencil's re-fetches cost in bytes the linear walk below wins
@@ -990,31 +1105,9 @@ __global__ __launch_bounds__(256) void k_adam(AdamArgs a) {
         const size_t r = idx / a.NYv;
         const int z = r % a.NZv;
         const int x = r / a.NZv;
-        const float2 xv = a.x_old[idx];
-        float gd = a.g[idx].x * a.g_scale + a.alpha_d * sgn(xv.x);
-        float gb = a.g[idx].y * a.g_scale + a.alpha_b * sgn(xv.y);
-        if (a.gamma != 0.f) {
-            const size_t sy = 1, sz = a.NYv, sx = (size_t)a.NZv * a.NYv;
-            const float ym = a.x_old[idx - y * sy + ((y + a.NYv - 1) % a.NYv) * sy].x;
-            const float yp = a.x_old[idx - y * sy + ((y + 1) % a.NYv) * sy].x;
-            const float zm = a.x_old[idx - z * sz + ((z + a.NZv - 1) % a.NZv) * sz].x;
-            const float zp = a.x_old[idx - z * sz + ((z + 1) % a.NZv) * sz].x;
-            const float xm = a.x_old[idx - x * sx + ((x + a.NXv - 1) % a.NXv) * sx].x;
-            const float xp = a.x_old[idx - x * sx + ((x + 1) % a.NXv) * sx].x;
-            const float c = xv.x;
-            gd += a.gamma * (sgn(c - ym) - sgn(yp - c) + sgn(c - zm) - sgn(zp - c) + sgn(c - xm) - sgn(xp - c));
-        }
-        float2 m = a.m[idx], v = a.v[idx];
-        m.x = a.om_b1 * gd + a.b1 * m.x;
-        m.y = a.om_b1 * gb + a.b1 * m.y;
-        v.x = a.om_b2 * gd * gd + a.b2 * v.x;
-        v.y = a.om_b2 * gb * gb + a.b2 * v.y;
-        a.m[idx] = m;
-        a.v[idx] = v;
-        float nd = xv.x - a.lr * (m.x * a.inv_bc1) / (sqrtf(v.x * a.inv_bc2) + a.eps);
-        float nb = xv.y - a.lr * (m.y * a.inv_bc1) / (sqrtf(v.y * a.inv_bc2) + a.eps);
-        if (a.mask) { const float mk = a.mask[idx]; nd *= mk; nb *= mk; }
-        if (a.clip) { nd = fmaxf(nd, 0.f); nb = fmaxf(nb, 0.f); }
+        float nd, nb;
+        float2 m, v;
+        adam_voxel<true>(a, idx, x, z, y, [&] { return a.g[idx]; }, nd, nb, m, v);
         a.x_new[idx] = make_float2(nd, nb);
     }
 }

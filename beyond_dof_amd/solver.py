@@ -9,6 +9,8 @@ One Adam iteration (`step`):
       gradient exchange of slab c across ranks                            bdof_reduce_scatter_grad | bdof_allreduce_grad
       regulariser + Adam + mask + clip on slab c (sharded: on this rank's 1/N of it)   bdof_adam_step_slab
       sharded: all-gather of the updated slab                             bdof_allgather_volume
+    On one rank with the lookup-table rotation there is nothing between the rotation adjoint and Adam, and FullfieldSolver.step
+    runs the tail as one pass over the volume that also leaves the new volume's modulation table   bdof_rotation_adjoint_adam
 The collectives run on the communicator's stream; the ctx stream only waits for slab c two slabs later, so the producer
 of the next slabs and the consumer of the previous ones run while a slab is on the wire.  The TV stencil reads the
 pre-update volume (x_old), which no slab overwrites: slab-wise, sharded and whole-volume execution give identical results.
@@ -44,6 +46,7 @@ class _VolumeSolver(object):
         self._acc = 0              # minibatches accumulated in self.g since the last update (n_batch_per_update)
         self._epoch_plan = None    # shard layout of the Adam moments since the last reset_moments (None: none taken yet)
         self._g_shards = None      # slabs whose gradient is reduced on this rank's 1/size only (after a sharded step)
+        self._g_stale = False      # the last step ran the one-pass tail, which does not write self.g (_g_refresh)
         self.probe = None          # enable_probe_optimization
         self._pgrad = None         # the engine's device accumulator of the probe gradient (_probe_collect)
         self.meas = None           # FullfieldSolver.set_measurements
@@ -101,6 +104,14 @@ class _VolumeSolver(object):
         """self.g is about to be rewritten whole with this rank's own, unreduced gradient: the shard layout a sharded step
         left behind no longer describes it (gradient_to_host would otherwise gather stale parts over it)."""
         self._g_shards = None
+        self._g_stale = False
+
+    def _g_refresh(self):
+        """After a one-pass tail self.g was not written: the rotation adjoint of the rotated-frame gradient, which stays in the
+        ctx until the next gradient sweep, with the scale the step used — the bits the separate kernels would have left."""
+        if self._g_stale:
+            self._produce()(0, self.dim_x)
+            self._g_stale = False
 
     def gradient_to_host(self):
         """The gradient of the last step / loss_and_grad as (g_delta, g_beta), each (Y, X, Z).  After a sharded step every rank
@@ -111,6 +122,7 @@ class _VolumeSolver(object):
             for x0, nx in self._g_shards:
                 self.comm.wait(self.ctx, self.comm.start_allgather(self.ctx, self.g, x0 * per_x, (nx // self.comm.size) * per_x))
             self._g_shards = None
+        self._g_refresh()
         self.ctx.sync()
         return util.rows_to_volume(self.g.download())
 
@@ -180,25 +192,30 @@ class _VolumeSolver(object):
         return ms.value
 
     def _tail(self, produce, i_update, learning_rate, alpha_d=0.0, alpha_b=0.0, gamma=0.0, clip=True, use_mask=True,
-              n_slabs=None, sharded=None, flip=True, n_acc=1):
+              n_slabs=None, sharded=None, flip=True, n_acc=1, one_pass=None):
         if not self.time_tail:
-            return self._tail_run(produce, i_update, learning_rate, alpha_d, alpha_b, gamma, clip, use_mask, n_slabs, sharded, flip, n_acc)
+            return self._tail_run(produce, i_update, learning_rate, alpha_d, alpha_b, gamma, clip, use_mask, n_slabs, sharded, flip, n_acc,
+                                  one_pass)
         lib, h = self.ctx.lib, self.ctx.handle
         self.ctx.check(lib.bdof_timer_mark(h, 0))
-        self._tail_run(produce, i_update, learning_rate, alpha_d, alpha_b, gamma, clip, use_mask, n_slabs, sharded, flip, n_acc)
+        self._tail_run(produce, i_update, learning_rate, alpha_d, alpha_b, gamma, clip, use_mask, n_slabs, sharded, flip, n_acc, one_pass)
         self.ctx.check(lib.bdof_timer_mark(h, 1))
 
     def _tail_run(self, produce, i_update, learning_rate, alpha_d=0.0, alpha_b=0.0, gamma=0.0, clip=True, use_mask=True,
-                  n_slabs=None, sharded=None, flip=True, n_acc=1):
+                  n_slabs=None, sharded=None, flip=True, n_acc=1, one_pass=None):
         """produce(x0, nx): enqueue the kernels that leave this rank's gradient of x-planes [x0, x0+nx) in self.g.
         Then exchange + regulariser + Adam (+ mask, clip), slab by slab.  g_scale = 1 / (size * n_acc)
-        (grads /= size, fullfield.py:351; accumulated minibatches are averaged, tensorflow_recon/fullfield.py:424)."""
+        (grads /= size, fullfield.py:351; accumulated minibatches are averaged, tensorflow_recon/fullfield.py:424).
+        one_pass(*args, g_scale): what to run in place of produce + Adam when nothing is exchanged (FullfieldSolver._one_pass_tail)."""
         comm, ctx = self.comm, self.ctx
         g_scale = 1.0 / (comm.size * n_acc)
         args = (i_update, learning_rate, alpha_d, alpha_b, gamma, clip, use_mask)
         if not self._reduces():
-            produce(0, self.dim_x)
-            self._adam_slab(*args, slab=None, g_scale=g_scale)
+            if one_pass is not None:
+                one_pass(*args, g_scale=g_scale)
+            else:
+                produce(0, self.dim_x)
+                self._adam_slab(*args, slab=None, g_scale=g_scale)
             if flip:
                 self._flip()
             return
@@ -481,8 +498,22 @@ class FullfieldSolver(_VolumeSolver):
     def adam_update(self, i_batch, learning_rate, alpha_d=0.0, alpha_b=0.0, gamma=0.0, clip=True, use_mask=True):
         """Regulariser + Adam on the gradient in self.g (whole volume, no exchange)."""
         self._whole_volume_guard()
+        self._g_refresh()
         self._adam_slab(i_batch, learning_rate, alpha_d, alpha_b, gamma, clip, use_mask, None, 1.0 / self.comm.size)
         self._flip()
+
+    def _one_pass_tail(self, i_update, learning_rate, alpha_d, alpha_b, gamma, clip, use_mask, g_scale):
+        """The tail of a step that exchanges nothing, in one pass (bdof_rotation_adjoint_adam): the volume gradient is not written
+        (self.g is stale until _g_refresh), and the new volume's modulation table is in the ctx when _flip binds it."""
+        lib, h = self.ctx.lib, self.ctx.handle
+        new = 1 - self.cur
+        mask = self.mask if use_mask else None
+        self.ctx.check(lib.bdof_rotation_adjoint_adam(h, self.mb, self.angle_buf.ptr, None, 0, self.dim_x * self.dim_z, 0, 1.0,
+                                                      self.x[self.cur].ptr, self.x[new].ptr, self.m.ptr, self.v.ptr, _lib._ptr(mask),
+                                                      self.dim_x, self.dim_z, self.dim_y, g_scale, alpha_d, alpha_b, gamma,
+                                                      learning_rate, 0.9, 0.999, 1e-8, int(i_update), int(clip)))
+        self._g_shards = None
+        self._g_stale = True
 
     def _dry_tail(self, n_slabs, sharded):
         self.angle_buf.upload(np.arange(self.mb, dtype=np.int32) % self.n_theta)
@@ -511,7 +542,9 @@ class FullfieldSolver(_VolumeSolver):
                            sharded, n_acc=n_acc)
                 self._probe_apply()
         else:
-            self._tail(self._produce(), i_batch, learning_rate, alpha_d, alpha_b, gamma, clip, use_mask, n_slabs, sharded)
+            # one rank, lookup-table rotation: nothing happens between the rotation adjoint and Adam
+            one_pass = self._one_pass_tail if not self._reduces() and not self.bilinear else None
+            self._tail(self._produce(), i_batch, learning_rate, alpha_d, alpha_b, gamma, clip, use_mask, n_slabs, sharded, one_pass=one_pass)
             self._probe_apply()
         return self._get_loss() if want_loss else None          # the loss of THIS minibatch stays on the device until the next one
 

@@ -403,6 +403,29 @@ int bdof_adam_step_slab(bdof_ctx* ctx, const void* x_old, void* x_new, const voi
                         int NXv, int NZv, int NYv, float g_scale, float alpha_d, float alpha_b, float gamma,
                         float lr, float b1, float b2, float eps, int i_batch, int clip, int x0, int nx);
 
+/* The tail of a step on ONE rank in one pass over the volume: bdof_rotation_adjoint_rows, bdof_adam_step and the table of
+ * modulation factors of x_new, without writing the volume gradient and reading it and x_new back.  The arguments are those of
+ * the two calls; gvol may be NULL (the gradient is then not kept; otherwise it is stored as well, the bits of
+ * bdof_rotation_adjoint_rows).  m, v, x_new come out bit for bit as from the two calls, the table as from the pass
+ * bdof_set_object(x_new) would trigger; its mean is summed in another (fixed) order: per destination row over its lanes, then over
+ * chunks of 1024 rows, then over the chunks; longest addition chain D = max(2 ceil(NY / 128) + 6, 2 ceil(NY / 512) + 9) + 4 + 8 +
+ * ceil(ceil(n_dest / 1024) / 256) + 8 (35 for 512^3), so it
+ * may differ from that pass's in the last bits of a double (by at most (D + 2) 2^-53 mean|factor|).
+ * BDOF_ERR_STATE for what the call does not carry: accumulate != 0, a row range other than the whole volume, the bilinear
+ * rotation (an object bound by bdof_set_object_bilinear), no object bound as (delta, beta) rows; BDOF_ERR_ARG when x_new aliases
+ * x_old or [NXv][NZv][NYv] is not the bound object's shape.
+ * Whose table the ctx holds afterwards: the ctx records the address x_new (with its row count and NY).  The object bound before
+ * stays bound but its table is stale (a sweep without rebinding rebuilds it).  The NEXT bdof_set_object consumes the record: if
+ * it binds exactly that address, row count and NY, the table is taken over and the next sweep builds none (it only reads the
+ * mean back); any other bdof_set_object, and every later one on the same address, rebuilds as always — so "call again whenever
+ * that memory has been modified" keeps holding.  The record is dropped by bdof_memcpy_h2d / bdof_memset / bdof_memcpy_d2d into
+ * that memory, bdof_set_object_bilinear and any rebuild of the table; a taken-over table is rebuilt when k changes or the probe /
+ * propagator change whether the mean rides on the carrier. */
+int bdof_rotation_adjoint_adam(bdof_ctx* ctx, int B, const int* angle_of_b, void* gvol, int row0, int n_rows, int accumulate, float scale,
+                               const void* x_old, void* x_new, void* m, void* v, const float* mask, int NXv, int NZv, int NYv,
+                               float g_scale, float alpha_d, float alpha_b, float gamma, float lr, float b1, float b2, float eps,
+                               int i_batch, int clip);
+
 /* dst[b] = src[idx[b]] for B fields of bytes_per_field bytes (a multiple of 4; 16-byte copies when it is a multiple of 16;
  * idx: device int32 [B]) in one launch:
  * this_prj_batch = prj[this_ind_batch] (cnn_propagator/fullfield.py:344) on the device-resident stack of amplitudes. */
