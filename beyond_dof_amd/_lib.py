@@ -88,6 +88,7 @@ _SIGNATURES = {
     'bdof_enable_probe_grad': (ctypes.c_int, [_vp, ctypes.c_int]),
     'bdof_probe_grad': (ctypes.c_int, [_vp, _vp, ctypes.c_int]),
     'bdof_grot': (_vp, [_vp]),
+    'bdof_tape_slot': (_vp, [_vp, ctypes.c_int]),
     'bdof_modulation_table': (ctypes.c_int, [_vp, ctypes.POINTER(_vp), ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_double)]),
     'bdof_rotation_adjoint': (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp, ctypes.c_int, ctypes.c_float]),
     'bdof_rotation_adjoint_rows': (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_float]),
@@ -107,6 +108,8 @@ _SIGNATURES = {
     'bdof_gather_fields': (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_int, ctypes.c_size_t]),
     'bdof_set_streams': (ctypes.c_int, [_vp, ctypes.c_int]),
     'bdof_batch_groups': (ctypes.c_int, [_vp, ctypes.c_int]),
+    'bdof_set_sweep_fusion': (ctypes.c_int, [_vp, ctypes.c_int]),
+    'bdof_sweep_fused': (ctypes.c_int, [_vp]),
     'bdof_profile_enable': (ctypes.c_int, [_vp, ctypes.c_int]),
     'bdof_profile_read': (ctypes.c_int, [_vp, ctypes.c_int, _c_int_p, ctypes.POINTER(ctypes.c_double)]),
     'bdof_malloc': (ctypes.c_int, [ctypes.POINTER(_vp), ctypes.c_size_t]),

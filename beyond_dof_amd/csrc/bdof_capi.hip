@@ -88,6 +88,11 @@ struct Workspace {
     DevBuf<cf> hsT_d;              // the same copies in the LDS-resident kernel's [kx][ky] order
     DevBuf<cf> hs_d;               // bdof_set_transfer_f64: hs_copies dithered float32 copies of the slice step's table (bdof_field.h)
     int hs_copies = 0;
+    // Fused forward sweep (bdof_set_sweep_fusion; k_slice_y / k_slice_x): the separable factors of the slice step, hy[ky] hx[kx] =
+    // the table above, in sep_copies dithered float32 copies each ([copy][k]; 0: the table is not separable, or there is no float64
+    // table to take them from), and the [NY][NX] table whose every row is hx of step S-2 (the hand-over to the unfused last slice)
+    DevBuf<cf> hx_d, hy_d, hx_rows;
+    int sep_copies = 0;
     DevBuf<cf> bufA, bufB, tape;
     int bin = 1;                   // bdof_set_slice_binning: voxel slices per propagation step (1 after every bdof_configure)
     DevBuf<float2> grot;
@@ -128,6 +133,8 @@ struct bdof_ctx : Workspace {
     hipEvent_t ev_fork = nullptr, ev_join[BDOF_MAX_GROUPS - 1] = {};
     hipEvent_t timer[BDOF_N_TIMERS] = {};        // bdof_timer_mark
     int n_streams = -1;                          // -1 auto (1 or 2), else the number of groups to split a batch in
+    int fusion = 0;                              // bdof_set_sweep_fusion: 0 never (a new ctx), 1 the forward sweep where the configuration is eligible
+    int fused_last = 0;                          // what the last bdof_loss_grad ran (bdof_sweep_fused)
     int sub_b0 = 0, sub_part = 0;
     hipStream_t sub_stream = nullptr;
     int ncu = 256;
@@ -571,8 +578,8 @@ static void launch_row_unmod(bdof_ctx* c, int B, int z, const cf* in, cf* out, b
 // key: the slice whose copy of the dithered constants the launch takes (tw_of); -1 = that of the last A / A' launch.  The step
 // between slices z-1 and z runs with copy z-1 in the forward sweep (it follows A_{z-1}); its adjoint, which follows A'_z, is
 // handed z-1 explicitly, so that the adjoint step is the transpose of the very operator the forward sweep applied.
-static void launch_row_prop(bdof_ctx* c, int B, const cf* in, cf* out, const cf* h, float scale, int conj_h, int key = -1) {
-    ProfScope ps(c, BDOF_K_COL_PROP, true);
+static void launch_row_prop(bdof_ctx* c, int B, const cf* in, cf* out, const cf* h, float scale, int conj_h, int key = -1, int cls = BDOF_K_COL_PROP) {
+    ProfScope ps(c, cls, true);
     const unsigned tick = key >= 0 ? (unsigned)key : c->tw_tick;
     if (h == c->hs) {
         if (c->hs_override) h = c->hs_override;
@@ -583,6 +590,48 @@ static void launch_row_prop(bdof_ctx* c, int B, const cf* in, cf* out, const cf*
     DISPATCH_N(c->NX, {
         BDOF_LAUNCH(ps, (k_row_prop<N_, false>), dim3(rows_grid<N_>(c, B, c->NY)), dim3(BDOF_THREADS), 0, c->sub_stream, a);
     });
+}
+
+// ---- the fused forward sweep (k_slice_y / k_slice_x, bdof_kernels.h) ------------------------------------------------------------
+#define DISPATCH_FUSED_N(n, ...)                                      \
+    switch (n) {                                                      \
+        case 64: { constexpr int N_ = 64; __VA_ARGS__; } break;       \
+        case 128: { constexpr int N_ = 128; __VA_ARGS__; } break;     \
+        case 256: { constexpr int N_ = 256; __VA_ARGS__; } break;     \
+        case 512: { constexpr int N_ = 512; __VA_ARGS__; } break;     \
+        default: break;                                               \
+    }
+// Which sweep bdof_loss_grad runs: 1 = the fused forward sweep, 0 = the two-kernel sweep.  Eligible: the streaming engine with the
+// tape, one voxel slice per step, a scalar carrier, a real-space or no detector, no window offsets, no probe gradient, a separable
+// slice step (build_separable), S even and >= 4, lines of at most 512 points (at 1024 a line spans two waves and the transposed
+// phase would hold 64 values per thread).
+static int fused_mode(const bdof_ctx* c) {
+    if (c->fusion < 1 || c->sep_copies < 1 || c->recompute || c->bin != 1 || c->pstack || c->range_car || c->hs_override) return 0;
+    if (c->det_mode == BDOF_DET_FAR || c->obj.xoff || c->obj.yoff || c->gpsi0) return 0;
+    if (c->S < 4 || (c->S & 1) || c->NX > 512 || c->NY > 512) return 0;
+    return 1;
+}
+// Slice z of the fused forward sweep: even z on y-lines ([b][x][y] -> [b][y][x]), odd z on x-lines (back); phi_z goes to `phi`.
+// The leading step takes copy z-1 of every dithered constant, the trailing one copy z.
+static void launch_slice(bdof_ctx* c, int B, int z, const cf* in, cf* out, cf* phi) {
+    ProfScope ps(c, BDOF_K_ROW_FWD, true);
+    const bool xl = (z & 1) != 0;
+    const int N = xl ? c->NX : c->NY, R = xl ? c->NY : c->NX;
+    const cf* tw = xl ? c->twX : c->twY;
+    const cf* h = xl ? c->hx_d : c->hy_d;
+    const unsigned lead = (unsigned)(z > 0 ? z - 1 : 0), trail = (unsigned)z, D = (unsigned)c->sep_copies;
+    SliceArgs a{sub_field(c, in), c->probe, sub_field(c, out), sub_field(c, phi), sub_obj(c), B, R, z, carrier_at(c, z), cshift_at(c, z),
+                tw_of(c, tw, N, lead), tw_of(c, tw, N, trail), h + (size_t)(lead % D) * N, h + (size_t)(trail % D) * N};
+    sq_of(c, lead, a.sq_lead);
+    sq_of(c, trail, a.sq_trail);
+    c->tw_tick = trail;
+    if (xl) {
+        DISPATCH_FUSED_N(N, BDOF_LAUNCH(ps, (k_slice_x<N_>), dim3(rows_grid<N_>(c, B, R)), dim3(BDOF_THREADS), 0, c->sub_stream, a));
+    } else {
+        DISPATCH_FUSED_N(N, with_bool(z == 0, [&](auto FIRST) { with_bool(z == c->S - 2, [&](auto TAIL) {
+            BDOF_LAUNCH(ps, (k_slice_y<N_, FIRST, TAIL>), dim3(rows_grid<N_>(c, B, R)), dim3(BDOF_THREADS), 0, c->sub_stream, a);
+        }); }));
+    }
 }
 
 // A'_z: L1 (g) + phi tape -> L2 (g)
@@ -671,7 +720,10 @@ static int launch_loss_far(bdof_ctx* c, int B, const DetPlane& det, const cf* in
 enum { TAPE_NONE = 0, TAPE_HISTORY = 1, TAPE_LAST = 2 };
 // TAPE_LAST (tape-free adjoint): only the real-space phi_{S-1} is kept (tape slot 0); the adjoint sweep marches it back.
 // TAPE_HISTORY keeps psi_hat_{z+1} (the transfer-function step's output) per slice: probe_array of np_funcs.py:43.
-static void forward_sweep(bdof_ctx* c, const Group* groups, int ngroups, int tape_mode) {
+// fused (fused_mode; TAPE_HISTORY only): slices 0 .. S-2 run as one k_slice_y / k_slice_x launch each, ping-ponging bufA / bufB in
+// real space; tape slot z holds the scattered part of phi_z (z <= S-2) and slot S-1 psi_hat_{S-1}, which one k_row_prop launch with
+// the hx-only table makes of the ky-domain lines k_slice_y<TAIL> left in bufA.  The last slice and the detector run as always.
+static void forward_sweep(bdof_ctx* c, const Group* groups, int ngroups, int tape_mode, bool fused = false) {
     const size_t fld = (size_t)c->Bmax * c->NX * c->NY;
     const bool tf_all = c->variant == BDOF_VARIANT_TF_ALL;
     const int nz = n_steps(c);
@@ -679,6 +731,15 @@ static void forward_sweep(bdof_ctx* c, const Group* groups, int ngroups, int tap
         const cf* in = nullptr;
         if (z > 0) in = tape_mode == TAPE_HISTORY ? c->tape + (size_t)steps(c).tape_read(z) * fld : c->bufB;
         const bool last = z == nz - 1;
+        if (fused && last) in = c->tape + (size_t)z * fld;
+        if (fused && !last) {
+            for (int gi = 0; gi < ngroups; ++gi) {
+                use_group(c, groups[gi]);
+                launch_slice(c, groups[gi].B, z, (z & 1) ? c->bufA : c->bufB, (z & 1) ? c->bufB : c->bufA, c->tape + (size_t)z * fld);
+                if (z == nz - 2) launch_row_prop(c, groups[gi].B, c->bufA, c->tape + (size_t)(nz - 1) * fld, c->hx_rows, 1.f, 0, z, BDOF_K_LOSS);
+            }
+            continue;
+        }
         cf* phi = tape_mode == TAPE_LAST && last ? c->tape : nullptr;
         for (int gi = 0; gi < ngroups; ++gi) {
             const int B = groups[gi].B;
@@ -690,8 +751,10 @@ static void forward_sweep(bdof_ctx* c, const Group* groups, int ngroups, int tap
                 launch_row_fwd(c, B, z, in, c->bufA, false, phi);
             } else {
                 launch_row_fwd(c, B, z, in, c->bufA, true, phi);
-                if (c->det_mode == BDOF_DET_NONE) launch_row_prop(c, B, c->bufA, c->bufB, c->hs, 1.f, 0);
-                else if (c->det_mode == BDOF_DET_NEAR) launch_row_prop(c, B, c->bufA, c->bufB, tf_all ? c->hcomb : c->hdet, 1.f, 0);
+                // (fused route: the step's few remaining transfer-function launches outside the adjoint sweep are filed with the detector)
+                const int cls = fused ? BDOF_K_LOSS : BDOF_K_COL_PROP;
+                if (c->det_mode == BDOF_DET_NONE) launch_row_prop(c, B, c->bufA, c->bufB, c->hs, 1.f, 0, -1, cls);
+                else if (c->det_mode == BDOF_DET_NEAR) launch_row_prop(c, B, c->bufA, c->bufB, tf_all ? c->hcomb : c->hdet, 1.f, 0, -1, cls);
             }
         }
     }
@@ -1331,7 +1394,52 @@ int bdof_set_physics(bdof_ctx* c, double k, const float* hs, const float* hs_det
     c->have_physics = true;
     c->have_h64 = false;             // float64 adjoint: the caller follows up with bdof_set_physics_f64
     c->hs_copies = 0;                // dithered copies of the old table: the caller follows up with bdof_set_transfer_f64
+    c->sep_copies = 0;               // ... and so do its separable factors
     c->mod_dirty = true;
+    return 0;
+}
+
+// The separable factors of the slice step for the fused forward sweep, from the float64 table H[ky][kx] (1 / (NX NY) folded in):
+//     hx[kx] = H[0][kx] / H[0][0] / NX,   hy[ky] = H[ky][0] NX      =>  hy[ky] hx[kx] = H[ky][kx],
+// so that Fx^-1 hx Fx is Px with its normalisation (a constant passes unchanged) and Fy^-1 hy Fy is Py with 1 / NY and the step's
+// phase H00.  Separability is checked here, in float64: max |H[ky][kx] H00 - H[ky][0] H[0][kx]| <= 1e-14 |H00|^2; a table that
+// fails (an impulse-response kernel, anything set by hand) leaves sep_copies = 0 and the sweep unfused.  D copies of each, dithered
+// over the slices exactly as the 2-D table is (k_dither_copies: the entry's golden-ratio phase, up in a fraction p of the copies).
+static int build_separable(bdof_ctx* c, const double* hs64, int D) {
+    typedef std::complex<double> cd;
+    c->sep_copies = 0;
+    const int NX = c->NX, NY = c->NY;
+    if (c->generic || NX > 512 || NY > 512 || c->S < 2 || D < 1) return 0;
+    auto H = [&](int ky, int kx) { const size_t i = (size_t)ky * NX + kx; return cd(hs64[2 * i], hs64[2 * i + 1]); };
+    const cd h00 = H(0, 0);
+    const double tol = 1e-14 * std::norm(h00);
+    if (!(std::norm(h00) > 0.0)) return 0;
+    for (int ky = 0; ky < NY; ++ky) {
+        const cd hy0 = H(ky, 0);
+        for (int kx = 0; kx < NX; ++kx)
+            if (!(std::abs(H(ky, kx) * h00 - hy0 * H(0, kx)) <= tol)) return 0;
+    }
+    auto copies = [&](int n, auto value, std::vector<cf>& t) {
+        t.resize((size_t)D * n);
+        for (int i = 0; i < n; ++i) {
+            const cd v = value(i);
+            const double g = (double)(i % 1048573) * 0.6180339887498949;
+            const double ph = g - std::floor(g), ph2 = ph + 0.5 - std::floor(ph + 0.5);
+            for (int d = 0; d < D; ++d) t[(size_t)d * n + i] = make_float2(dither_pick(v.real(), d, ph), dither_pick(v.imag(), d, ph2));
+        }
+    };
+    std::vector<cf> hx, hy, rows((size_t)NX * NY);
+    copies(NX, [&](int kx) { return H(0, kx) / h00 / (double)NX; }, hx);
+    copies(NY, [&](int ky) { return H(ky, 0) * (double)NX; }, hy);
+    const cf* hx_top = hx.data() + (size_t)((c->S - 2) % D) * NX;
+    for (int ky = 0; ky < NY; ++ky) std::copy(hx_top, hx_top + NX, rows.begin() + (size_t)ky * NX);
+    HIPC(c, c->hx_d.alloc(hx.size()));
+    HIPC(c, c->hy_d.alloc(hy.size()));
+    HIPC(c, c->hx_rows.alloc(rows.size()));
+    HIPC(c, hipMemcpy(c->hx_d, hx.data(), sizeof(cf) * hx.size(), hipMemcpyHostToDevice));
+    HIPC(c, hipMemcpy(c->hy_d, hy.data(), sizeof(cf) * hy.size(), hipMemcpyHostToDevice));
+    HIPC(c, hipMemcpy(c->hx_rows, rows.data(), sizeof(cf) * rows.size(), hipMemcpyHostToDevice));
+    c->sep_copies = D;
     return 0;
 }
 
@@ -1347,6 +1455,7 @@ int bdof_set_transfer_f64(bdof_ctx* c, const double* hs64) {
     const size_t n = (size_t)c->NX * c->NY;
     int D = env ? std::max(0, std::min(256, atoi(env))) : 64;
     while (D > 1 && (size_t)D * n * sizeof(cf) > ((size_t)256 << 20)) D /= 2;
+    c->sep_copies = 0;
     if (D < 2) { c->hs_copies = 0; return 0; }
     HIPC(c, hipSetDevice(c->device));
     HIPC(c, hipStreamSynchronize(c->stream));
@@ -1380,7 +1489,7 @@ int bdof_set_transfer_f64(bdof_ctx* c, const double* hs64) {
     }
     if (e != hipSuccess) return fail(c, (int)e, "building the dithered transfer-function copies failed");
     c->hs_copies = D;
-    return 0;
+    return build_separable(c, hs64, D);
 }
 
 int bdof_set_physics_f64(bdof_ctx* c, const double* hs, const double* hs_det) {
@@ -2229,6 +2338,7 @@ int bdof_loss_grad(bdof_ctx* c, int B, const int* angle_of_b, const int* xoff, c
     if ((r = ensure_modulation_k(c, c->k_fft))) return r;
     c->gpsi_src = c->gpsi0;
     c->gpsi_B = B;
+    c->fused_last = 0;
     if (use_resident(c, B)) {
         if ((r = resident_run(c, B, meas, out_wave, true))) return r;
         c->tape_valid = c->last_valid = false;
@@ -2251,7 +2361,9 @@ int bdof_loss_grad(bdof_ctx* c, int B, const int* angle_of_b, const int* xoff, c
     // per step at 512^3 x 25).
     const bool recompute = c->recompute;
     const int nz = n_steps(c);
-    forward_sweep(c, groups, ng, recompute ? TAPE_LAST : TAPE_HISTORY);
+    const bool fused = fused_mode(c) != 0;
+    c->fused_last = fused ? 1 : 0;
+    forward_sweep(c, groups, ng, recompute ? TAPE_LAST : TAPE_HISTORY, fused);
     c->tape_valid = false;      // the tape holds an incomplete history (or phi_{S-1} alone), not what bdof_tape_to_real expects
     c->last_valid = false;
     int npart = 0;
@@ -2268,7 +2380,7 @@ int bdof_loss_grad(bdof_ctx* c, int B, const int* angle_of_b, const int* xoff, c
             // the detector wave came out of a transfer-function step: seed -> R (transposed) -> adjoint step
             const cf* h = c->det_mode == BDOF_DET_NONE ? c->hs : (tf_all ? c->hcomb : c->hdet);
             npart += launch_loss_real(c, Bg, det, c->bufB, c->bufA, true, (cf*)out_wave, meas, 1.f, 1.f);
-            launch_row_prop(c, Bg, c->bufA, c->bufB, h, 1.f, 1, nz - 1);
+            launch_row_prop(c, Bg, c->bufA, c->bufB, h, 1.f, 1, nz - 1, fused ? BDOF_K_LOSS : BDOF_K_COL_PROP);
         }
     }
     // backward sweep: A'_z (L1 -> L2), then the adjoint transfer-function step (L2 -> L1)
@@ -2295,8 +2407,13 @@ int bdof_loss_grad(bdof_ctx* c, int B, const int* angle_of_b, const int* xoff, c
                 }
                 continue;
             }
-            launch_row_bwd(c, groups[gi].B, z, c->bufB, z > 0 ? c->tape + (size_t)steps(c).tape_read(z) * fld : nullptr, z > 0 ? c->bufA : nullptr,
-                           z > 0 ? 1 : 2);
+            if (fused) {
+                // after the fused forward sweep the tape holds phi_z itself (HIST 0) below the last slice, whose psi_hat sits in slot S-1
+                launch_row_bwd(c, groups[gi].B, z, c->bufB, c->tape + (size_t)z * fld, z > 0 ? c->bufA : nullptr, z == nz - 1 ? 1 : 0);
+            } else {
+                launch_row_bwd(c, groups[gi].B, z, c->bufB, z > 0 ? c->tape + (size_t)steps(c).tape_read(z) * fld : nullptr, z > 0 ? c->bufA : nullptr,
+                               z > 0 ? 1 : 2);
+            }
             if (z > 0) launch_row_prop(c, groups[gi].B, c->bufA, c->bufB, c->hs, 1.f, 1, z - 1);
         }
     }
@@ -2701,6 +2818,11 @@ int bdof_get_loss(bdof_ctx* c, double* loss) {
 }
 
 void* bdof_grot(bdof_ctx* c) { return c ? (void*)c->grot : nullptr; }
+void* bdof_tape_slot(bdof_ctx* c, int slot) {
+    if (!c || !c->tape || slot < 0) return nullptr;
+    const size_t fld = (size_t)c->Bmax * c->NX * c->NY;
+    return (size_t)(slot + 1) * fld <= c->tape.size() ? (void*)(c->tape + (size_t)slot * fld) : nullptr;
+}
 
 int bdof_modulation_table(bdof_ctx* c, const void** table, size_t* n, double* mean_m1) {
     if (!c || !table || !n) return BDOF_ERR_ARG;
@@ -2988,6 +3110,14 @@ int bdof_gather_fields(bdof_ctx* c, void* dst, const void* src, const int* idx, 
     hipLaunchKernelGGL(k_gather_fields, dim3(gx, B < 1024 ? B : 1024), dim3(256), 0, c->stream, (float4*)dst, (const float4*)src, idx, B, n16);
     return launched(c);
 }
+
+int bdof_set_sweep_fusion(bdof_ctx* c, int mode) {
+    if (!c) return BDOF_ERR_ARG;
+    if (mode < 0 || mode > 2) return fail(c, BDOF_ERR_ARG, "bdof_set_sweep_fusion: mode must be 0, 1 or 2");
+    c->fusion = std::min(mode, 1);      // the highest stage this library carries
+    return 0;
+}
+int bdof_sweep_fused(bdof_ctx* c) { return c ? c->fused_last : 0; }
 
 int bdof_set_streams(bdof_ctx* c, int n) {
     if (!c) return -1;

@@ -237,6 +237,30 @@ __device__ __forceinline__ void line_fft(cf (&u)[8], const FftTw<N>& tw, int tid
     }
 }
 
+// line_fft after its first stage: the first stage's outputs are already in the line's LDS image, written by stage_write<N, R0, 1>
+// (the fused slice kernels run that stage in the transposed mapping, straight on last_stage's registers; the caller's workgroup
+// barrier orders those stores before the loads here).  u[m] <-> position tid + m*T on exit.
+template <int N, int SIGN, int ROUND = 1, bool EX = false, class L>
+__device__ __forceinline__ void line_fft_rest(cf (&u)[8], const FftTw<N>& tw, int tid, L& lds) {
+    typedef FftPlan<N> P;
+    stage_read<N, P::R1>(u, tid, lds);
+    stage_compute<N, SIGN, P::R1, P::R0, (P::NS == 2 ? 3 : 1), ROUND, EX>(u, tw, tid);
+    if constexpr (P::NS > 2) {
+        lds.sync_r2w();
+        stage_write<N, P::R1, P::R0>(u, tid, lds);
+        lds.sync_w2r();
+        stage_read<N, P::R2>(u, tid, lds);
+        stage_compute<N, SIGN, P::R2, P::R0 * P::R1, (P::NS == 3 ? 3 : 2), ROUND, EX>(u, tw, tid);
+    }
+    if constexpr (P::NS > 3) {
+        lds.sync_r2w();
+        stage_write<N, P::R2, P::R0 * P::R1>(u, tid, lds);
+        lds.sync_w2r();
+        stage_read<N, P::R3>(u, tid, lds);
+        stage_compute<N, SIGN, P::R3, P::R0 * P::R1 * P::R2, 3, ROUND, EX>(u, tw, tid);
+    }
+}
+
 // All stages but the last; the last stage's inputs are left in the line's LDS image (no sync after the
 // final store: the caller's workgroup barrier orders it before the transposed readers).
 template <int N, int SIGN, int ROUND = 1, bool EX = false, class L>

@@ -10,6 +10,9 @@
 // stage of each kernel's final FFT is executed with a transposed thread mapping (16 rows x N/8
 // butterflies), so the transposition costs no extra LDS pass and only one workgroup barrier per
 // 16-row tile, and the stores are 128-byte segments.  B's output is directly the tape entry.
+// The fused forward sweep of bdof_loss_grad (k_slice_y / k_slice_x, below A') replaces A + B by one kernel per slice that works
+// on lines of one direction, through the separable Fresnel step; between its kernels the field is in real space, [b][x][y] or
+// [b][y][x], and the tape holds phi_z:                                                                              32 B/px
 #pragma once
 #include "bdof_fft.h"
 
@@ -815,6 +818,274 @@ __global__ __launch_bounds__(BDOF_THREADS, RowCfg<NY>::MIN_WAVES) void k_row_bwd
             transposed_tail<NY, -1, 1, EX>(smem, a.gout + (size_t)b * NY * a.NX + x0, a.NX, 1.f, smem_tail, tw.sq);
             __syncthreads();
         }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// Fused slice kernels of the forward sweep (bdof_set_sweep_fusion): one launch and one trip of the field through memory per
+// slice.  The Fresnel transfer function is separable, H(u, v) = Hx(u) Hy(v), so one step is P = Px Py with Px = Fx^-1 hx Fx on
+// x-lines and Py = Fy^-1 hy Fy on y-lines, the two commute, and the slice chain regroups so that a kernel works on lines of
+// ONE direction:        ... c_z Py | Px c_{z+1} Px | Py c_{z+2} Py | Px ...        (| = kernel boundary = one transposed store)
+// Between the kernels the field is in REAL space, [b][x][y] in front of a y-line kernel and [b][y][x] in front of an x-line one.
+//   k_slice_y (even z): rows of [b][x][y]; Py of step z-1, modulation c_z (table row from load_obj_row, as A), phi_z to the
+//       tape, Py of step z with the transposed tail -> [b][y][x].  FIRST: no leading step, input = probe.  TAIL: stops after
+//       the trailing Fy and hy — the tail stores the ky-domain lines hy Fy phi_z into L2 [b][ky][x], from where one ordinary
+//       k_row_prop launch with an hx-only table leaves psi_hat_{z+1} in L1 for the unfused last slice and detector.
+//   k_slice_x (odd z): rows of [b][y][x]; Px of step z-1 up to its last stage, which runs in the transposed mapping (16 rows x
+//       N/8 butterflies: a thread sits on x = j + m T, y = y0 + r with its 16 neighbours along y) — there the table and the phi
+//       tape are 128-byte segments along y — modulation, then the FIRST stage of the next Fx on the same registers (it takes
+//       exactly the points j + m T), the rest of Px of step z in the row mapping, transposed tail -> [b][x][y].
+// Every transform takes the dithered constants of the step it belongs to (twiddles, sqrt(1/2), hx / hy): copy z-1 for the
+// leading step, copy z for the trailing one.  32 B per pixel (8 in + 8 table + 8 phi + 8 out) where A + B move 40.
+// ---------------------------------------------------------------------------------------------
+struct SliceArgs {
+    const cf* in;        // k_slice_y: [B][NX][NY]; k_slice_x: [B][NY][NX]; real space, scattered part
+    const cf* probe;     // k_slice_y<FIRST>: [NX][NY]
+    cf* out;             // k_slice_y: [B][NY][NX] (TAIL: [B][ky][NX]); k_slice_x: [B][NX][NY]
+    cf* phi_out;         // tape slot of slice z: real-space scattered part of phi_z, [B][NX][NY] (what k_row_bwd<HIST 0> reads)
+    ObjView obj;
+    int B, R, z;         // R: lines per wavefield (k_slice_y: NX, k_slice_x: NY)
+    cf carrier;          // a_z
+    cf cshift;           // a_z (cbar - 1)
+    const cf* tw_lead;   // twiddle table of the line length, copy of step z-1 ...
+    const cf* tw_trail;  // ... and of step z
+    const cf* h_lead;    // hx (k_slice_x) or hy (k_slice_y) of step z-1, normalisation folded in ...
+    const cf* h_trail;   // ... and of step z
+    float sq_lead[2], sq_trail[2];
+};
+
+// transposed_tail with a factor per position: dst[pos * ld + r] = h[pos] * out(row r, position pos)
+template <int N, int SIGN, int ROUND = 1>
+__device__ __forceinline__ void transposed_tail_mul(cf* smem, cf* __restrict__ dst, size_t ld, const cf* __restrict__ h, const cf* tail, const float* sq) {
+    typedef RowCfg<N> C;
+#pragma nounroll
+    for (int pass = 0; pass < C::PASSES; ++pass) {
+        const int q = threadIdx.x + pass * BDOF_THREADS;
+        const int r = q % C::TILE, j = q / C::TILE;
+        RowLds<C::T> lds{smem + r * C::RS};
+        cf u[8], hv[8];
+#pragma unroll
+        for (int m = 0; m < 8; ++m) hv[m] = h[j + m * C::T];
+        last_stage<N, SIGN, ROUND, false>(u, j, lds, tail, sq);
+#pragma unroll
+        for (int m = 0; m < 8; ++m) dst[(size_t)(j + m * C::T) * ld + r] = cmul(u[m], hv[m]);
+    }
+}
+
+// obj_src_row for the x-line kernel, whose tile needs the source row of EVERY x of its wavefield: the part that is the same for
+// the whole tile (the rotation table's row of (angle, z), or the first row of a plain batch's slice) once, then per x one
+// unconditional 4-byte load from a base that is valid either way — no branch around a load (load_obj_row).
+struct ObjRows {
+    const int* look;     // the table row [volNX] of (angle_of_b[b], z); without a table: any readable address
+    long long plain0;    // without a table: source row of x = 0 (0 with one)
+    int imax;            // last index of `look` that may be read (0 without a table)
+    int xmax;            // last x that has a source row (without a table: every x)
+    int mask;            // -1 with a table, 0 without: what is read counts / x itself counts
+};
+__device__ __forceinline__ ObjRows obj_rows_of(const ObjView o, int b, int z, int NX) {
+    ObjRows r;
+    r.look = o.tab ? o.tab + ((long long)o.angle_of_b[b] * o.S + z) * o.volNX : (const int*)o.vol;
+    r.plain0 = o.tab ? 0 : ((long long)b * o.S + z) * NX;
+    r.imax = o.tab ? o.volNX - 1 : 0;
+    r.xmax = o.tab ? o.volNX - 1 : 0x7fffffff;
+    r.mask = o.tab ? -1 : 0;
+    return r;
+}
+// the source row of x less plain0, or -1.  Arithmetic only: a select on the (uniform) "is there a table" became a branch around every load
+__device__ __forceinline__ int obj_rows_rel(const ObjRows r, int x) {
+    const int s = r.look[(unsigned)min(x, r.imax)] & r.mask;
+    return x <= r.xmax ? s + (x & ~r.mask) : -1;
+}
+
+// The tables of a transform's constants into LDS without the barrier and the per-lane part of FftTw::load: the slice kernels fill
+// the sets of both their steps in front of ONE barrier (a workgroup runs two tiles: every round trip at its start counts).
+template <int N> __device__ __forceinline__ void tw_fill(const cf* __restrict__ table, cf* lds_mid, cf* lds_tail) {
+    typedef FftTw<N> TW;
+    constexpr int T = N / 8;
+    for (int e = threadIdx.x; e < 7 * T; e += blockDim.x) {
+        const int m = e / T + 1, j = e - (m - 1) * T;
+        lds_tail[e] = table[m * j];
+    }
+    for (int e = threadIdx.x; e < TW::M1_CNT + TW::M2_CNT; e += blockDim.x) {
+        int k, m, step;
+        if (e < TW::M1_CNT) { k = e / TW::D1; m = e % TW::D1 + 1; step = N / (TW::M1_P * TW::M1_R); }
+        else { const int f = e - TW::M1_CNT; k = f / TW::D2; m = f % TW::D2 + 1; step = N / (TW::M2_P * TW::M2_R); }
+        lds_mid[e] = table[m * k * step];
+    }
+}
+
+// Point tw at the constants of one of the two steps a slice kernel belongs to (both sets are in LDS).  The lane's last-stage
+// twiddles are re-read from LDS at every switch — behind a compiler barrier, or hipcc hoists the loads out of the tile loop and
+// keeps both sets, 28 registers, live through the kernel (measured: 356 bytes of scratch in k_slice_x<512>).
+template <int N> __device__ __forceinline__ void tw_select(FftTw<N>& tw, const cf* mid, const cf* tail, const float* sq, int tid) {
+    asm volatile("" ::: "memory");
+    tw.mid = mid;
+    tw.tail = tail;
+    tw.sq = sq;
+#pragma unroll
+    for (int m = 1; m < 8; ++m) tw.w[m - 1] = tail[(m - 1) * (N / 8) + tid];
+}
+
+template <int NY, bool FIRST, bool TAIL>
+__global__ __launch_bounds__(BDOF_THREADS, RowCfg<NY>::MIN_WAVES) void k_slice_y(SliceArgs a) {
+    typedef RowCfg<NY> C;
+    __shared__ cf smem[C::LDS_CF];
+    __shared__ cf smem_tw[2][FftTw<NY>::LDS_CNT];
+    __shared__ cf smem_tail[2][7 * C::T];
+    const int tid = threadIdx.x % C::T, rl = threadIdx.x / C::T;
+    const float sql[2] = {a.sq_lead[0], a.sq_lead[1]}, sqt[2] = {a.sq_trail[0], a.sq_trail[1]};     // copies: no pointer into the argument block
+    FftTw<NY> tw;
+    if constexpr (!FIRST) tw_fill<NY>(a.tw_lead, smem_tw[0], smem_tail[0]);
+    tw_fill<NY>(a.tw_trail, smem_tw[1], smem_tail[1]);
+    __syncthreads();
+    const int NX = a.R;
+    const int ntiles = a.B * NX / C::TILE;
+    for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        const int row0 = tile * C::TILE;
+        const int b = row0 / NX, x0 = row0 - b * NX;
+#pragma nounroll
+        for (int pass = 0; pass < C::PASSES; ++pass) {
+            const int r = pass * C::RPP + rl;
+            const int x = x0 + r;
+            RowLds<C::T> lds{smem + r * C::RS};
+            cf u[8], hv[8];
+            float2 db[8];
+            const cf* src = FIRST ? a.probe + (size_t)x * NY : a.in + (size_t)(row0 + r) * NY;
+#pragma unroll
+            for (int m = 0; m < 8; ++m) u[m] = src[tid + m * C::T];
+            load_obj_row(a.obj, obj_src_row(a.obj, b, x, a.z, NX), 0, tid, C::T, db);
+            if constexpr (!FIRST) {                       // Py of step z-1
+#pragma unroll
+                for (int m = 0; m < 8; ++m) hv[m] = a.h_lead[tid + m * C::T];
+                tw_select(tw, smem_tw[0], smem_tail[0], sql, tid);
+                line_fft<NY, -1, 1, false>(u, tw, tid, lds);
+#pragma unroll
+                for (int m = 0; m < 8; ++m) u[m] = cmul(u[m], hv[m]);
+                line_fft<NY, +1, 2, false>(u, tw, tid, lds);
+            }
+#pragma unroll
+            for (int m = 0; m < 8; ++m) u[m] = modulate_eps_s(u[m], a.carrier, db[m], a.cshift);
+            cf* pdst = a.phi_out + (size_t)(row0 + r) * NY;
+#pragma unroll
+            for (int m = 0; m < 8; ++m) pdst[tid + m * C::T] = u[m];
+            tw_select(tw, smem_tw[1], smem_tail[1], sqt, tid);
+            if constexpr (TAIL) {                         // Fy of step z; its last stage and hy in the tail
+                line_fft_partial<NY, -1, 1, false>(u, tw, tid, lds);
+            } else {                                      // Py of step z
+#pragma unroll
+                for (int m = 0; m < 8; ++m) hv[m] = a.h_trail[tid + m * C::T];
+                line_fft<NY, -1, 1, false>(u, tw, tid, lds);
+#pragma unroll
+                for (int m = 0; m < 8; ++m) u[m] = cmul(u[m], hv[m]);
+                line_fft_partial<NY, +1, 2, false>(u, tw, tid, lds);
+            }
+        }
+        __syncthreads();
+        cf* dst = a.out + (size_t)b * NY * NX + x0;
+        if constexpr (TAIL) transposed_tail_mul<NY, -1, 1>(smem, dst, NX, a.h_trail, smem_tail[1], sqt);
+        else transposed_tail<NY, +1, 2, false>(smem, dst, NX, 1.f, smem_tail[1], sqt);
+        __syncthreads();
+    }
+}
+
+template <int NX>
+__global__ __launch_bounds__(BDOF_THREADS, RowCfg<NX>::MIN_WAVES) void k_slice_x(SliceArgs a) {
+    typedef RowCfg<NX> C;
+    typedef FftPlan<NX> P;
+    __shared__ cf smem[C::LDS_CF];
+    __shared__ cf smem_tw[2][FftTw<NX>::LDS_CNT];
+    __shared__ cf smem_tail[2][7 * C::T];
+    const int tid = threadIdx.x % C::T, rl = threadIdx.x / C::T;
+    const float sql[2] = {a.sq_lead[0], a.sq_lead[1]}, sqt[2] = {a.sq_trail[0], a.sq_trail[1]};
+    __shared__ int s_src[NX];                             // source row of every x of the tile's wavefield at this slice (less plain0)
+    FftTw<NX> tw;
+    tw_fill<NX>(a.tw_lead, smem_tw[0], smem_tail[0]);
+    tw_fill<NX>(a.tw_trail, smem_tw[1], smem_tail[1]);
+    __syncthreads();
+    const ObjView o = a.obj;                              // by value (load_obj_row_bin)
+    const int NY = a.R;
+    const int ntiles = a.B * NY / C::TILE;
+    for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        const int row0 = tile * C::TILE;
+        const int b = row0 / NY, y0 = row0 - b * NY;
+        const ObjRows rows = obj_rows_of(o, b, a.z, NX);
+        cf* const pdst = a.phi_out + (size_t)b * NX * NY;
+        // The rotation lookup of the tile, one x per thread, on its way while the first phase runs; it goes through LDS to the
+        // transposed phase, which would otherwise wait for it and THEN for the table rows it points to (two round trips in a row)
+        const int src_mine = (int)threadIdx.x < NX ? obj_rows_rel(rows, threadIdx.x) : -1;
+        // Px of step z-1 up to its last stage, row mapping
+#pragma nounroll
+        for (int pass = 0; pass < C::PASSES; ++pass) {
+            const int r = pass * C::RPP + rl;
+            RowLds<C::T> lds{smem + r * C::RS};
+            cf u[8], hv[8];
+            const cf* src = a.in + (size_t)(row0 + r) * NX;
+#pragma unroll
+            for (int m = 0; m < 8; ++m) u[m] = src[tid + m * C::T];
+#pragma unroll
+            for (int m = 0; m < 8; ++m) hv[m] = a.h_lead[tid + m * C::T];
+            tw_select(tw, smem_tw[0], smem_tail[0], sql, tid);
+            line_fft<NX, -1, 1, false>(u, tw, tid, lds);
+#pragma unroll
+            for (int m = 0; m < 8; ++m) u[m] = cmul(u[m], hv[m]);
+            line_fft_partial<NX, +1, 2, false>(u, tw, tid, lds);
+        }
+        if ((int)threadIdx.x < NX) s_src[threadIdx.x] = src_mine;
+        __syncthreads();
+        // Transposed mapping: last stage of Fx^-1, modulation, first stage of the next Fx.  The first stage's stores go to
+        // positions 8 j + q of row image r, which other threads' last stages still read (another wave, another pass): every
+        // read of the tile is done, with a workgroup barrier, before any write — the PASSES x 8 values wait in registers.
+        cf v[C::PASSES][8];
+#pragma unroll
+        for (int pass = 0; pass < C::PASSES; ++pass) {
+            const int q = threadIdx.x + pass * BDOF_THREADS;
+            const int r = q % C::TILE, j = q / C::TILE;
+            RowLds<C::T> lds{smem + r * C::RS};
+            // lookups and table loads first, unconditional and clamped (load_obj_row), consumed after the last stage
+            const int yg = y0 + r, yc = min(max(yg, 0), o.volNY - 1);
+            float2 db[8];
+#pragma unroll
+            for (int m = 0; m < 8; ++m) {
+                const int srel = s_src[j + m * C::T];
+                const float2 t = o.vol[(size_t)(rows.plain0 + max(srel, 0)) * o.volNY + yc];
+                const bool in = srel >= 0 && yg == yc;
+                db[m] = make_float2(in ? t.x : 0.f, in ? t.y : 0.f);
+            }
+            last_stage<NX, +1, 2, false>(v[pass], j, lds, smem_tail[0], sql);
+#pragma unroll
+            for (int m = 0; m < 8; ++m) {
+                v[pass][m] = modulate_eps_s(v[pass][m], a.carrier, db[m], a.cshift);
+                pdst[(unsigned)((j + m * C::T) * NY + yg)] = v[pass][m];      // (32-bit offsets inside one wavefield)
+            }
+            tw.sq = sqt;                                  // (the first stage takes no twiddles, only the step's sqrt(1/2))
+            stage_compute<NX, -1, P::R0, 1, 0, 1, false>(v[pass], tw, j);
+        }
+        __syncthreads();
+#pragma unroll
+        for (int pass = 0; pass < C::PASSES; ++pass) {
+            const int q = threadIdx.x + pass * BDOF_THREADS;
+            const int r = q % C::TILE, j = q / C::TILE;
+            RowLds<C::T> lds{smem + r * C::RS};
+            stage_write<NX, P::R0, 1>(v[pass], j, lds);
+        }
+        __syncthreads();
+        // the rest of Px of step z, row mapping
+#pragma nounroll
+        for (int pass = 0; pass < C::PASSES; ++pass) {
+            const int r = pass * C::RPP + rl;
+            RowLds<C::T> lds{smem + r * C::RS};
+            cf u[8], hv[8];
+#pragma unroll
+            for (int m = 0; m < 8; ++m) hv[m] = a.h_trail[tid + m * C::T];
+            tw_select(tw, smem_tw[1], smem_tail[1], sqt, tid);
+            line_fft_rest<NX, -1, 1, false>(u, tw, tid, lds);
+#pragma unroll
+            for (int m = 0; m < 8; ++m) u[m] = cmul(u[m], hv[m]);
+            line_fft_partial<NX, +1, 2, false>(u, tw, tid, lds);
+        }
+        __syncthreads();
+        transposed_tail<NX, +1, 2, false>(smem, a.out + (size_t)b * NX * NY + y0, NY, 1.f, smem_tail[1], sqt);
+        __syncthreads();
     }
 }
 

@@ -536,6 +536,17 @@ class MultisliceEngine(object):
     def batch_groups(self, B):
         return int(self.lib.bdof_batch_groups(self.h, int(B)))
 
+    def set_sweep_fusion(self, mode):
+        """Fused forward sweep of loss_grad (bdof_set_sweep_fusion, include/bdof.h): 0 never, 1 the forward sweep, 2 both sweeps
+        (runs the highest stage the library carries).  An engine starts at 0, so that its results stay bit for bit those of the
+        tape-free adjoint's forward sweep; FullfieldSolver switches to 2.  Ineligible configurations run the two-kernel sweep."""
+        self.ctx.check(self.lib.bdof_set_sweep_fusion(self.h, int(mode)))
+
+    @property
+    def sweep_fused(self):
+        """The mode the last loss_grad actually ran (bdof_sweep_fused): 0 = the two-kernel sweep."""
+        return int(self.lib.bdof_sweep_fused(self.h))
+
     def profile_enable(self, on=True, stride=1):
         self.ctx.check(self.lib.bdof_profile_enable(self.h, int(stride) if on else 0))
 

@@ -62,6 +62,15 @@ class _VolumeSolver(object):
     def _bind_volume(self):
         self.eng.set_volume(self.x[self.cur], self.dim_x * self.dim_z, self.dim_y, self.tab, self.dim_x, self.n_theta)
 
+    # ---- the streaming engine's fused forward sweep (MultisliceEngine.set_sweep_fusion) ---------
+    def set_sweep_fusion(self, mode):
+        self.eng.set_sweep_fusion(mode)
+
+    @property
+    def sweep_fused(self):
+        """The mode the last loss + gradient actually ran (0: the two-kernel sweep)."""
+        return self.eng.sweep_fused
+
     # ---- state -------------------------------------------------------------------------------
     def set_volume(self, obj_delta, obj_beta):
         self.x[self.cur].upload(util.volume_to_rows(obj_delta, obj_beta))
@@ -399,6 +408,7 @@ class FullfieldSolver(_VolumeSolver):
         self.eng = MultisliceEngine(self.dim_y, self.dim_x, self.dim_z, self.mb, with_grad=True, device=device, stream=stream,
                                     recompute=recompute, adjoint64=adjoint64, slice_binning=slice_binning)
         self.ctx = self.eng.ctx
+        self.eng.set_sweep_fusion(1)        # the fused forward sweep (a ctx of its own starts at 0); a later stage is a decision to take here
         self.eng.set_loss(loss_type, poisson_multiplier)
         self.eng.set_physics(energy_ev, psize_cm, free_prop_cm, variant=variant, detector_kernel=detector_kernel)
         if self.conv:

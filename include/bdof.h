@@ -351,6 +351,11 @@ int bdof_loss_grad_tf_f64(bdof_ctx* ctx, int B, const int* angle_of_b, const int
 int bdof_forward_conv(bdof_ctx* ctx, int B, const int* angle_of_b, const int* xoff, const int* yoff, void* out_wave);
 int bdof_loss_grad_conv(bdof_ctx* ctx, int B, const int* angle_of_b, const int* xoff, const int* yoff, const float* meas, void* out_wave);
 void* bdof_grot(bdof_ctx* ctx);      /* device [B][S][NX][NY] pairs */
+/* Field `slot` of the ctx's tape, device [Bmax][NX][NY] complex64 (NULL: no tape, or no such slot), as the last sweep left it; for
+ * inspection and tests.  After a bdof_loss_grad that ran the fused forward sweep (bdof_sweep_fused) slot z <= S-2 holds the
+ * real-space scattered part of phi_z, the wave behind slice z of np_funcs.py:37-40 less its constant part, and slot S-1 psi_hat_{S-1};
+ * after the two-kernel sweep slot z holds psi_hat_{z+1}. */
+void* bdof_tape_slot(bdof_ctx* ctx, int slot);
 /* Read-only view of the table of modulation factors c - 1 = exp(i k delta) exp(-k beta) - 1 that every sweep reads: one entry per
  * (delta, beta) pair of the bound object, in the object's own order.  Builds the table if it is stale (the pass the sweeps run),
  * with the k of bdof_set_physics or of the last sweep (the real-space propagator's differs).  table: the device address, n: its
@@ -446,6 +451,22 @@ int bdof_mask_shrink(bdof_ctx* ctx, const void* x, float* mask, size_t n, float 
  * 1..4 fixed.  bdof_batch_groups returns the number of groups a batch of B wavefields runs as. */
 int bdof_set_streams(bdof_ctx* ctx, int n);
 int bdof_batch_groups(bdof_ctx* ctx, int B);
+
+/* Fused forward sweep of bdof_loss_grad (streaming engine).  The Fresnel transfer function of np_funcs.py:42 (cnn_propagator/
+ * util.py:73-102) is separable, H(u, v) = Hx(u) Hy(v), so the slice chain of np_funcs.py:37-43 regroups into kernels that work on
+ * lines of one direction — "finish the previous step along my lines, modulate, start the next step along my lines" — one launch and
+ * one trip of the wavefield through memory per slice where the two-kernel sweep takes two (32 instead of 40 B per pixel and slice).
+ * mode: 0 never, 1 the forward sweep (the adjoint sweep reads the phi tape it leaves), 2 both sweeps; a mode above the highest
+ * stage the library carries (1) runs that stage.  A new ctx starts at 0: the two routes agree to float32 rounding, not bit for
+ * bit, and callers of this ABI compare bdof_loss_grad bit for bit with the tape-free adjoint (BDOF_CFG_RECOMPUTE), whose forward
+ * sweep is not fused; the full-field solver of the Python host switches to the highest stage.  The fused route is taken where the configuration is
+ * eligible: tape (not BDOF_CFG_RECOMPUTE), no slice binning, scalar carrier, BDOF_DET_NONE / BDOF_DET_NEAR, no window offsets, no
+ * probe gradient, S even and >= 4, NX, NY <= 512, and a transfer function that bdof_set_transfer_f64 found separable in float64
+ * while it built its dithered copies (BDOF_H_DITHER below 2 builds none: no fused route then)
+ * (max |H[ky][kx] H[0][0] - H[ky][0] H[0][kx]| <= 1e-14 |H[0][0]|^2).  Everything else runs the two-kernel sweep, as does every
+ * other entry point.  bdof_sweep_fused: the mode the last bdof_loss_grad actually ran (0 before the first). */
+int bdof_set_sweep_fusion(bdof_ctx* ctx, int mode);
+int bdof_sweep_fused(bdof_ctx* ctx);
 
 /* Per-kernel-class timing with HIP events on the stream of each launch (bench.py roofline leg).  enable = 0 off, 1 every launch,
  * n > 1 every n-th launch of the per-slice kernel classes (two event records per launch cost ~9 us of stream time). */
