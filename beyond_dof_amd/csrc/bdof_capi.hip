@@ -126,7 +126,7 @@ struct bdof_ctx : Workspace {
     int device = 0;
     hipStream_t stream = nullptr;               // borrowed from the caller unless own_stream
     bool own_stream = false;
-    // dual-stream split of a batch (see batch_groups): the sub-batch the launchers currently work on
+    // split of a batch over streams (Split)
     hipStream_t side[BDOF_MAX_GROUPS - 1] = {};   // side streams PROVEN to run concurrently with the ctx stream (probe_side_streams)
     int n_side = -1;                             // -1: not probed yet
     std::vector<hipStream_t> side_all;           // every candidate created (kept until the ctx dies)
@@ -135,8 +135,6 @@ struct bdof_ctx : Workspace {
     int n_streams = -1;                          // -1 auto (1 or 2), else the number of groups to split a batch in
     int fusion = 0;                              // bdof_set_sweep_fusion: 0 never (a new ctx), 1 the forward sweep where the configuration is eligible
     int fused_last = 0;                          // what the last bdof_loss_grad ran (bdof_sweep_fused)
-    int sub_b0 = 0, sub_part = 0;
-    hipStream_t sub_stream = nullptr;
     int ncu = 256;
     int NY = 0, NX = 0, S = 0, Bmax = 0;
     bool with_grad = false;
@@ -144,12 +142,10 @@ struct bdof_ctx : Workspace {
     // dithered twiddle tables (bdof_fft.h; BDOF_TW_DITHER=D, default 64): D copies of each table, entry j of copy d rounded up or
     // down so that the mean over the D copies is the float64 value to ulp / D; the launches of slice z take copy z mod D
     int tw_dither = 0;
-    unsigned tw_tick = 0;          // the slice of the last A / A' launch: the transfer-function launch that follows takes the same copy
     // borrowed: the caller's memory, which the caller keeps alive and releases (with the caller's stream above, and gpsi_src,
     // which points into the Workspace and is reset with it)
     const float2* obj_src = nullptr;            // caller's (delta, beta) rows
     const int *adj_off = nullptr, *adj_order = nullptr;
-    const cf* hs_override = nullptr;            // bdof_forward_range_h: the table of this call's transfer-function steps
     const cf* range_car = nullptr;              // bdof_set_range_carrier: [nz][B][NX][NY] carrier fields of the range being swept
     int range_car_B = 0, range_car_z0 = 0;
     DevBuf<double2> car_scratch;                // bdof_range_carrier_build: [nz - 1][B][NX][NY] complex128
@@ -260,6 +256,12 @@ static int check_halo(bdof_ctx* c, int TX, int TY, int halo_x, int halo_y) {
     return halo_x < 0 || halo_y < 0 || 2 * halo_x >= TX || 2 * halo_y >= TY ? fail(c, BDOF_ERR_ARG, "halo must leave a core") : 0;
 }
 
+// A sub-batch: wavefields b0 .. b0 + B - 1 of the call's batch, launched on stream st.  Every launcher of the streaming and conv
+// engines takes the sub-batch it works on; the ctx's buffers hold the whole batch and the launchers offset into them.
+struct Group { int b0, B; hipStream_t st; };
+// the whole batch on the ctx stream: the launches that run without a split, or after its join
+static Group whole(const bdof_ctx* c, int B) { return Group{0, B, c->stream}; }
+
 // Mean-refraction carrier (modulate_eps_s): constant part of the wave entering slice z, a_z = a_0 (cbar H00)^z
 // (H00 = DC value of the transfer function, cbar = mean modulation factor of the object).  With slice binning z counts
 // propagation steps, cbar is that of a bin (modulation_done) and H00 that of the bin's step.
@@ -289,9 +291,9 @@ static bool use_adj_carrier(const bdof_ctx* c) {
 }
 static double2 d2(std::complex<double> v) { return make_double2(v.real(), v.imag()); }
 // conj(H00)^n: what the adjoint carrier picks up in n adjoint transfer-function steps
-static AdjCarrier adj_carrier_at(const bdof_ctx* c, int steps_back) {
+static AdjCarrier adj_carrier_at(const bdof_ctx* c, const Group& g, int steps_back) {
     if (!use_adj_carrier(c)) return AdjCarrier{nullptr, nullptr, make_double2(1.0, 0.0), make_float2(0.f, 0.f)};
-    return AdjCarrier{c->gcar + c->sub_b0, c->gt0 + c->sub_b0, d2(std::pow(std::conj((1.0 + c->cbm1) * c->h00), steps_back)), cfl(c->cbm1)};
+    return AdjCarrier{c->gcar + g.b0, c->gt0 + g.b0, d2(std::pow(std::conj((1.0 + c->cbm1) * c->h00), steps_back)), cfl(c->cbm1)};
 }
 
 // ---- the detector plane (DetPlane, bdof_kernels.h) ------------------------------------------------------------------------
@@ -308,9 +310,9 @@ static DetPlane wave_plane(const bdof_ctx* c, std::complex<double> carrier, cons
     d.pfield64 = !pfield ? nullptr : pfield == c->pdet ? c->pdet64 : pfield == c->pdetT ? c->pdetT64 : nullptr;
     return d;
 }
-// The detector plane and data term of the transfer-function engines for a batch of B wavefields (the current sub-batch's
-// adjoint carriers); pfield: the carrier field at the detector in the layout of the kernel that gets the plane, or null.
-static DetPlane det_plane(const bdof_ctx* c, int B, const cf* pfield) {
+// The detector plane and data term of the transfer-function engines for a batch of B wavefields, with the adjoint carriers of
+// its sub-batch g; pfield: the carrier field at the detector in the layout of the kernel that gets the plane, or null.
+static DetPlane det_plane(const bdof_ctx* c, const Group& g, int B, const cf* pfield) {
     DetPlane d = wave_plane(c, carrier_det(c), pfield);
     d.a_end = d2(carrier_end(c));
     d.meas_dev = c->meas_dev;
@@ -324,7 +326,7 @@ static DetPlane det_plane(const bdof_ctx* c, int B, const cf* pfield) {
     // Set whenever the ctx carries an adjoint carrier, whatever the launch does: the kernels write them only where they fit
     // (a.meas) and reach the DC bin's test (k_row_loss<FAR>; k_g_loss, after its seed64 branch has taken every bin of a float64
     // adjoint), and nothing reads them unless an adjoint sweep follows.
-    if (use_adj_carrier(c)) { d.gcar = c->gcar + c->sub_b0; d.gt0 = c->gt0 + c->sub_b0; }
+    if (use_adj_carrier(c)) { d.gcar = c->gcar + g.b0; d.gt0 = c->gt0 + g.b0; }
     return d;
 }
 
@@ -334,10 +336,11 @@ static bool supported_n(int n) { return n == 64 || n == 128 || n == 256 || n == 
 struct ProfScope {
     bdof_ctx* c;
     int cls;
+    hipStream_t st;       // the stream the launch goes to
     bool on;
     bool ext;             // the launch itself carries the events (BDOF_LAUNCH -> hipExtLaunchKernelGGL): nothing is recorded here
     size_t idx = 0;
-    ProfScope(bdof_ctx* c_, int cls_, bool ext_ = false) : c(c_), cls(cls_), on(c_->prof), ext(ext_) {
+    ProfScope(bdof_ctx* c_, int cls_, hipStream_t st_, bool ext_ = false) : c(c_), cls(cls_), st(st_), on(c_->prof), ext(ext_) {
         if (on && c->prof_stride > 1 && cls <= BDOF_K_ROW_BWD) on = (c->prof_seen[cls]++ % (unsigned)c->prof_stride) == 0;
         if (!on) return;
         if (c->ev_next + 2 > c->ev_pool.size()) {
@@ -347,13 +350,13 @@ struct ProfScope {
         }
         idx = c->ev_next;
         c->ev_next += 2;
-        if (!ext) (void)hipEventRecord(c->ev_pool[idx], c->sub_stream ? c->sub_stream : c->stream);
+        if (!ext) (void)hipEventRecord(c->ev_pool[idx], st);
     }
     hipEvent_t e0() const { return c->ev_pool[idx]; }
     hipEvent_t e1() const { return c->ev_pool[idx + 1]; }
     ~ProfScope() {
         if (!on) return;
-        if (!ext) (void)hipEventRecord(c->ev_pool[idx + 1], c->sub_stream ? c->sub_stream : c->stream);
+        if (!ext) (void)hipEventRecord(c->ev_pool[idx + 1], st);
         c->ev_used.emplace_back(cls, (int)idx);
     }
 };
@@ -390,15 +393,11 @@ template <int N> static int rows_grid(const bdof_ctx* c, int B, int R) {
     return balanced_grid(c, B * R / RowCfg<N>::TILE, N >= 1024 ? 1 : 2);
 }
 
-#define DISPATCH_N(n, ...)                                            \
-    switch (n) {                                                      \
-        case 64: { constexpr int N_ = 64; __VA_ARGS__; } break;       \
-        case 128: { constexpr int N_ = 128; __VA_ARGS__; } break;     \
-        case 256: { constexpr int N_ = 256; __VA_ARGS__; } break;     \
-        case 512: { constexpr int N_ = 512; __VA_ARGS__; } break;     \
-        case 1024: { constexpr int N_ = 1024; __VA_ARGS__; } break;   \
-        default: break;                                               \
-    }
+// Line length -> template argument N_: every size of the streaming engine, or those of at most 512 points (the fused sweep's)
+#define N_CASE(v, ...) case v: { constexpr int N_ = v; __VA_ARGS__; } break;
+#define N_CASES_512(...) N_CASE(64, __VA_ARGS__) N_CASE(128, __VA_ARGS__) N_CASE(256, __VA_ARGS__) N_CASE(512, __VA_ARGS__)
+#define DISPATCH_N(n, ...) switch (n) { N_CASES_512(__VA_ARGS__) N_CASE(1024, __VA_ARGS__) default: break; }
+#define DISPATCH_N_512(n, ...) switch (n) { N_CASES_512(__VA_ARGS__) default: break; }
 
 // Runtime choice -> template argument: f(std::integral_constant<int, v>) for v in [0, N) (values from N - 1 up take N - 1),
 // f(std::true_type / false_type) for a bool; the constant converts to its value where a template argument is expected.
@@ -412,8 +411,7 @@ template <class F> static auto with_bool(bool v, F&& f) { return v ? f(std::true
 // A batch whose tile count fills the chip's workgroup slots badly (25 wavefields of 512 rows = 800 tiles on 512 slots:
 // every launch runs as two rounds at 78 % occupancy) is split in two groups that run the same kernel sequence on two
 // streams: the groups have no dependencies on each other, so one group's kernels fill the slots the other leaves idle
-// and the per-launch round quantisation disappears.  Launchers address the current group through c->sub_*.
-struct Group { int b0, B; hipStream_t st; };
+// and the per-launch round quantisation disappears.  Split holds the groups of one call; every launcher takes its Group.
 
 // HIP maps streams onto a small pool of hardware queues (4 per process by default, GPU_MAX_HW_QUEUES): two streams that
 // share a queue run their kernels one after the other, and which streams collide depends on every other stream in the
@@ -481,30 +479,31 @@ static int batch_groups(bdof_ctx* c, int B, int rows_per_b, int tile, Group (&g)
     }
     return n;
 }
-static void use_group(bdof_ctx* c, const Group& g, int part_off = 0) {
-    c->sub_b0 = g.b0;
-    c->sub_stream = g.st;
-    c->sub_part = part_off;
-}
-static void use_whole(bdof_ctx* c) { c->sub_b0 = 0; c->sub_stream = c->stream; c->sub_part = 0; }
-static int fork_streams(bdof_ctx* c, int ngroups) {
-    if (ngroups < 2) return 0;
-    HIPC(c, hipEventRecord(c->ev_fork, c->stream));
-    for (int i = 1; i < ngroups; ++i) HIPC(c, hipStreamWaitEvent(c->side[i - 1], c->ev_fork, 0));
-    return 0;
-}
-static int join_streams(bdof_ctx* c, int ngroups) {
-    use_whole(c);
-    for (int i = 1; i < ngroups; ++i) {
-        HIPC(c, hipEventRecord(c->ev_join[i - 1], c->side[i - 1]));
-        HIPC(c, hipStreamWaitEvent(c->stream, c->ev_join[i - 1], 0));
+// The split of one call's batch: open() forms the groups and makes the side streams wait for what the ctx stream has queued,
+// `for (const Group& g : split)` visits them, close() makes the ctx stream wait for every side stream.
+struct Split {
+    Group g[BDOF_MAX_GROUPS];
+    int n = 0;
+    const Group* begin() const { return g; }
+    const Group* end() const { return g + n; }
+    int open(bdof_ctx* c, int B, int rows_per_b, int tile) {
+        n = batch_groups(c, B, rows_per_b, tile, g);
+        if (n > 1) HIPC(c, hipEventRecord(c->ev_fork, c->stream));
+        for (int i = 1; i < n; ++i) HIPC(c, hipStreamWaitEvent(g[i].st, c->ev_fork, 0));
+        return 0;
     }
-    return 0;
-}
+    int close(bdof_ctx* c) const {
+        for (int i = 1; i < n; ++i) {
+            HIPC(c, hipEventRecord(c->ev_join[i - 1], g[i].st));
+            HIPC(c, hipStreamWaitEvent(c->stream, c->ev_join[i - 1], 0));
+        }
+        return 0;
+    }
+};
 
-static ObjView sub_obj(const bdof_ctx* c) {
+static ObjView sub_obj(const bdof_ctx* c, const Group& g) {
     ObjView o = c->obj;
-    const int b0 = c->sub_b0;
+    const int b0 = g.b0;
     if (b0) {
         if (o.tab) { o.angle_of_b += b0; }
         else { o.vol += (size_t)b0 * c->S * c->NX * o.volNY; }
@@ -536,100 +535,86 @@ static const cf* tw_of(bdof_ctx* c, const cf* base, int N, unsigned key) {
     return c->tw_dither > 0 ? base + (size_t)(key % (unsigned)c->tw_dither) * 2 * N : base;
 }
 
-template <class T> static T* sub_field(const bdof_ctx* c, T* p) { return p ? p + (size_t)c->sub_b0 * c->NX * c->NY : p; }
+template <class T> static T* sub_field(const bdof_ctx* c, const Group& g, T* p) { return p ? p + (size_t)g.b0 * c->NX * c->NY : p; }
 
 // A_z: L1 (or the probe) -> L2 (tstore) or L1 (plain)
 static const cf* slice_carrier_field(const bdof_ctx* c, int z) { return c->pstack ? c->pstack + (size_t)z * c->NX * c->NY : nullptr; }
 
 // start != nullptr: slice z starts from the real-space fields start[b] (scattered part) instead of the hybrid `in` — the
 // first slice of a range (bdof_forward_range); z == 0 without `start` starts from the probe shared by the batch.
-static void launch_row_fwd(bdof_ctx* c, int B, int z, const cf* in, cf* out, bool tstore, cf* phi_out = nullptr, const cf* start = nullptr) {
-    ProfScope ps(c, BDOF_K_ROW_FWD, true);
-    RowFwdArgs a{sub_field(c, in), start ? sub_field(c, start) : c->probe, sub_field(c, out), sub_field(c, phi_out), sub_obj(c), B, c->NX, z,
+static void launch_row_fwd(bdof_ctx* c, const Group& g, int z, const cf* in, cf* out, bool tstore, cf* phi_out = nullptr, const cf* start = nullptr) {
+    ProfScope ps(c, BDOF_K_ROW_FWD, g.st, true);
+    RowFwdArgs a{sub_field(c, g, in), start ? sub_field(c, g, start) : c->probe, sub_field(c, g, out), sub_field(c, g, phi_out), sub_obj(c, g), g.B, c->NX, z,
                  c->k, carrier_at(c, z), tw_of(c, c->twY, c->NY, (unsigned)z), slice_carrier_field(c, z), cshift_at(c, z), 0, 1.f, start ? 1 : 0};
     sq_of(c, (unsigned)z, a.sq);
     a.pz_b = 0;
     if (c->range_car) {          // every wavefield of the range rides on its own carrier field
-        a.pz = c->range_car + ((size_t)(z - c->range_car_z0) * c->range_car_B + c->sub_b0) * c->NX * c->NY;
+        a.pz = c->range_car + ((size_t)(z - c->range_car_z0) * c->range_car_B + g.b0) * c->NX * c->NY;
         a.pz_b = c->NX;
     }
-    c->tw_tick = (unsigned)z;
     DISPATCH_N(c->NY, with_bool(z == 0 || start, [&](auto FIRST) { with_bool(tstore, [&](auto TSTORE) { with_bool(a.pz != nullptr, [&](auto PF) {
         with_bool(c->bin > 1, [&](auto BIN) {
-            BDOF_LAUNCH(ps, (k_row_fwd<N_, FIRST, TSTORE, PF, false, BIN>), dim3(rows_grid<N_>(c, B, c->NX)), dim3(BDOF_THREADS), 0, c->sub_stream, a);
+            BDOF_LAUNCH(ps, (k_row_fwd<N_, FIRST, TSTORE, PF, false, BIN>), dim3(rows_grid<N_>(c, g.B, c->NX)), dim3(BDOF_THREADS), 0, g.st, a);
         });
     }); }); }));
 }
 
 // A_z^-1 (tape-free adjoint): scattered part of phi_z (L1 hybrid, or real space) -> R eps(psi_z) in L2
-static void launch_row_unmod(bdof_ctx* c, int B, int z, const cf* in, cf* out, bool real_in, float in_scale) {
-    ProfScope ps(c, BDOF_K_ROW_FWD, true);
-    RowFwdArgs a{sub_field(c, in), c->probe, sub_field(c, out), nullptr, sub_obj(c), B, c->NX, z, c->k, carrier_at(c, z), tw_of(c, c->twY, c->NY, (unsigned)z),
+static void launch_row_unmod(bdof_ctx* c, const Group& g, int z, const cf* in, cf* out, bool real_in, float in_scale) {
+    ProfScope ps(c, BDOF_K_ROW_FWD, g.st, true);
+    RowFwdArgs a{sub_field(c, g, in), c->probe, sub_field(c, g, out), nullptr, sub_obj(c, g), g.B, c->NX, z, c->k, carrier_at(c, z), tw_of(c, c->twY, c->NY, (unsigned)z),
                  slice_carrier_field(c, z), cshift_at(c, z), real_in ? 1 : 0, in_scale, 0};
     a.pz_b = 0;
     sq_of(c, (unsigned)z, a.sq);
-    c->tw_tick = (unsigned)z;
     DISPATCH_N(c->NY, with_bool(a.pz != nullptr, [&](auto PF) {
-        BDOF_LAUNCH(ps, (k_row_fwd<N_, false, true, PF, true>), dim3(rows_grid<N_>(c, B, c->NX)), dim3(BDOF_THREADS), 0, c->sub_stream, a);
+        BDOF_LAUNCH(ps, (k_row_fwd<N_, false, true, PF, true>), dim3(rows_grid<N_>(c, g.B, c->NX)), dim3(BDOF_THREADS), 0, g.st, a);
     }));
 }
 
 // B: L2 -> L1
-// key: the slice whose copy of the dithered constants the launch takes (tw_of); -1 = that of the last A / A' launch.  The step
-// between slices z-1 and z runs with copy z-1 in the forward sweep (it follows A_{z-1}); its adjoint, which follows A'_z, is
-// handed z-1 explicitly, so that the adjoint step is the transpose of the very operator the forward sweep applied.
-static void launch_row_prop(bdof_ctx* c, int B, const cf* in, cf* out, const cf* h, float scale, int conj_h, int key = -1, int cls = BDOF_K_COL_PROP) {
-    ProfScope ps(c, cls, true);
-    const unsigned tick = key >= 0 ? (unsigned)key : c->tw_tick;
-    if (h == c->hs) {
-        if (c->hs_override) h = c->hs_override;
-        else if (c->hs_copies > 0) h = c->hs_d + (size_t)(tick % (unsigned)c->hs_copies) * c->NX * c->NY;      // the slice's dithered copy
-    }
-    RowPropArgs a{sub_field(c, in), sub_field(c, out), h, B, c->NY, scale, conj_h, tw_of(c, c->twX, c->NX, tick)};
+// key: the slice whose copy of the dithered constants the launch takes (tw_of, sq_of, and of the slice step's table when h is
+// c->hs).  The step between slices z-1 and z runs with copy z-1 in the forward sweep (it follows A_{z-1}); its adjoint, which
+// follows A'_z, is handed z-1 too, so that the adjoint step is the transpose of the very operator the forward sweep applied.
+static void launch_row_prop(bdof_ctx* c, const Group& g, const cf* in, cf* out, const cf* h, float scale, int conj_h, int key, int cls = BDOF_K_COL_PROP) {
+    ProfScope ps(c, cls, g.st, true);
+    const unsigned tick = (unsigned)key;
+    if (h == c->hs && c->hs_copies > 0) h = c->hs_d + (size_t)(tick % (unsigned)c->hs_copies) * c->NX * c->NY;      // the slice's dithered copy
+    RowPropArgs a{sub_field(c, g, in), sub_field(c, g, out), h, g.B, c->NY, scale, conj_h, tw_of(c, c->twX, c->NX, tick)};
     sq_of(c, tick, a.sq);
     DISPATCH_N(c->NX, {
-        BDOF_LAUNCH(ps, (k_row_prop<N_, false>), dim3(rows_grid<N_>(c, B, c->NY)), dim3(BDOF_THREADS), 0, c->sub_stream, a);
+        BDOF_LAUNCH(ps, (k_row_prop<N_, false>), dim3(rows_grid<N_>(c, g.B, c->NY)), dim3(BDOF_THREADS), 0, g.st, a);
     });
 }
 
 // ---- the fused forward sweep (k_slice_y / k_slice_x, bdof_kernels.h) ------------------------------------------------------------
-#define DISPATCH_FUSED_N(n, ...)                                      \
-    switch (n) {                                                      \
-        case 64: { constexpr int N_ = 64; __VA_ARGS__; } break;       \
-        case 128: { constexpr int N_ = 128; __VA_ARGS__; } break;     \
-        case 256: { constexpr int N_ = 256; __VA_ARGS__; } break;     \
-        case 512: { constexpr int N_ = 512; __VA_ARGS__; } break;     \
-        default: break;                                               \
-    }
 // Which sweep bdof_loss_grad runs: 1 = the fused forward sweep, 0 = the two-kernel sweep.  Eligible: the streaming engine with the
 // tape, one voxel slice per step, a scalar carrier, a real-space or no detector, no window offsets, no probe gradient, a separable
 // slice step (build_separable), S even and >= 4, lines of at most 512 points (at 1024 a line spans two waves and the transposed
 // phase would hold 64 values per thread).
 static int fused_mode(const bdof_ctx* c) {
-    if (c->fusion < 1 || c->sep_copies < 1 || c->recompute || c->bin != 1 || c->pstack || c->range_car || c->hs_override) return 0;
+    if (c->fusion < 1 || c->sep_copies < 1 || c->recompute || c->bin != 1 || c->pstack || c->range_car) return 0;
     if (c->det_mode == BDOF_DET_FAR || c->obj.xoff || c->obj.yoff || c->gpsi0) return 0;
     if (c->S < 4 || (c->S & 1) || c->NX > 512 || c->NY > 512) return 0;
     return 1;
 }
 // Slice z of the fused forward sweep: even z on y-lines ([b][x][y] -> [b][y][x]), odd z on x-lines (back); phi_z goes to `phi`.
 // The leading step takes copy z-1 of every dithered constant, the trailing one copy z.
-static void launch_slice(bdof_ctx* c, int B, int z, const cf* in, cf* out, cf* phi) {
-    ProfScope ps(c, BDOF_K_ROW_FWD, true);
+static void launch_slice(bdof_ctx* c, const Group& g, int z, const cf* in, cf* out, cf* phi) {
+    ProfScope ps(c, BDOF_K_ROW_FWD, g.st, true);
     const bool xl = (z & 1) != 0;
     const int N = xl ? c->NX : c->NY, R = xl ? c->NY : c->NX;
     const cf* tw = xl ? c->twX : c->twY;
     const cf* h = xl ? c->hx_d : c->hy_d;
     const unsigned lead = (unsigned)(z > 0 ? z - 1 : 0), trail = (unsigned)z, D = (unsigned)c->sep_copies;
-    SliceArgs a{sub_field(c, in), c->probe, sub_field(c, out), sub_field(c, phi), sub_obj(c), B, R, z, carrier_at(c, z), cshift_at(c, z),
+    SliceArgs a{sub_field(c, g, in), c->probe, sub_field(c, g, out), sub_field(c, g, phi), sub_obj(c, g), g.B, R, z, carrier_at(c, z), cshift_at(c, z),
                 tw_of(c, tw, N, lead), tw_of(c, tw, N, trail), h + (size_t)(lead % D) * N, h + (size_t)(trail % D) * N};
     sq_of(c, lead, a.sq_lead);
     sq_of(c, trail, a.sq_trail);
-    c->tw_tick = trail;
     if (xl) {
-        DISPATCH_FUSED_N(N, BDOF_LAUNCH(ps, (k_slice_x<N_>), dim3(rows_grid<N_>(c, B, R)), dim3(BDOF_THREADS), 0, c->sub_stream, a));
+        DISPATCH_N_512(N, BDOF_LAUNCH(ps, (k_slice_x<N_>), dim3(rows_grid<N_>(c, g.B, R)), dim3(BDOF_THREADS), 0, g.st, a));
     } else {
-        DISPATCH_FUSED_N(N, with_bool(z == 0, [&](auto FIRST) { with_bool(z == c->S - 2, [&](auto TAIL) {
-            BDOF_LAUNCH(ps, (k_slice_y<N_, FIRST, TAIL>), dim3(rows_grid<N_>(c, B, R)), dim3(BDOF_THREADS), 0, c->sub_stream, a);
+        DISPATCH_N_512(N, with_bool(z == 0, [&](auto FIRST) { with_bool(z == c->S - 2, [&](auto TAIL) {
+            BDOF_LAUNCH(ps, (k_slice_y<N_, FIRST, TAIL>), dim3(rows_grid<N_>(c, g.B, R)), dim3(BDOF_THREADS), 0, g.st, a);
         }); }));
     }
 }
@@ -641,91 +626,106 @@ struct GradTarget {            // where A'_z leaves the gradient rows / G(psi_z)
     int S_ = 0, z_ = 0;
     cf* gpsi = nullptr;        // real-space G(psi_z), [B][NX][NY]
 };
-static void launch_row_bwd(bdof_ctx* c, int B, int z, const cf* gin, const cf* tape, cf* gout, int hist = 0, float tape_scale = 1.f,
+static void launch_row_bwd(bdof_ctx* c, const Group& g, int z, const cf* gin, const cf* tape, cf* gout, int hist = 0, float tape_scale = 1.f,
                            const GradTarget* gt = nullptr) {
-    ProfScope ps(c, BDOF_K_ROW_BWD, true);
-    float2* grot = gt && gt->grot ? gt->grot + (size_t)c->sub_b0 * gt->S_ * c->NX * c->NY : c->grot + (size_t)c->sub_b0 * c->S * c->NX * c->NY;
-    RowBwdArgs a{sub_field(c, gin), hist == 2 ? c->probe : sub_field(c, tape), sub_field(c, gout),
-                 grot, sub_obj(c), B, c->NX, z, c->k, carrier_at(c, z), tw_of(c, c->twY, c->NY, (unsigned)z),
-                 slice_carrier_field(c, z), adj_carrier_at(c, steps(c).steps_back(z)), cshift_at(c, z), carrier_phi_at(c, z), tape_scale,
-                 gt && gt->gpsi ? sub_field(c, gt->gpsi) : (z == 0 && c->gpsi0 ? c->gpsi0 + (size_t)c->sub_b0 * c->NX * c->NY : nullptr),
+    ProfScope ps(c, BDOF_K_ROW_BWD, g.st, true);
+    float2* grot = gt && gt->grot ? gt->grot + (size_t)g.b0 * gt->S_ * c->NX * c->NY : c->grot + (size_t)g.b0 * c->S * c->NX * c->NY;
+    RowBwdArgs a{sub_field(c, g, gin), hist == 2 ? c->probe : sub_field(c, g, tape), sub_field(c, g, gout),
+                 grot, sub_obj(c, g), g.B, c->NX, z, c->k, carrier_at(c, z), tw_of(c, c->twY, c->NY, (unsigned)z),
+                 slice_carrier_field(c, z), adj_carrier_at(c, g, steps(c).steps_back(z)), cshift_at(c, z), carrier_phi_at(c, z), tape_scale,
+                 gt && gt->gpsi ? sub_field(c, g, gt->gpsi) : (z == 0 ? sub_field<cf>(c, g, c->gpsi0) : nullptr),
                  gt && gt->grot ? gt->S_ : c->S, gt && gt->grot ? gt->z_ : steps(c).first_slice(z)};
     sq_of(c, (unsigned)z, a.sq);
-    c->tw_tick = (unsigned)z;
     // carrier form: 0 scalar, 1 field (PF), 2 far field + plane-wave carrier (GC; never together with a carrier field)
     const int form = a.ac.gcar ? 2 : a.pz ? 1 : 0;
     if (c->bin > 1) {            // slice binning: the history-mode sweep's two forms (HIST 1, and 2 at step 0) — the only ones it launches
         DISPATCH_N(c->NY, with_bool(hist == 2, [&](auto H2) { with_int<3>(form, [&](auto FORM) {
-            BDOF_LAUNCH(ps, (k_row_bwd<N_, H2 ? 2 : 1, FORM == 1, FORM == 2, true>), dim3(rows_grid<N_>(c, B, c->NX)), dim3(BDOF_THREADS), 0, c->sub_stream, a);
+            BDOF_LAUNCH(ps, (k_row_bwd<N_, H2 ? 2 : 1, FORM == 1, FORM == 2, true>), dim3(rows_grid<N_>(c, g.B, c->NX)), dim3(BDOF_THREADS), 0, g.st, a);
         }); }));
         return;
     }
     DISPATCH_N(c->NY, with_int<4>(hist, [&](auto HIST) { with_int<3>(form, [&](auto FORM) {
-        BDOF_LAUNCH(ps, (k_row_bwd<N_, HIST, FORM == 1, FORM == 2>), dim3(rows_grid<N_>(c, B, c->NX)), dim3(BDOF_THREADS), 0, c->sub_stream, a);
+        BDOF_LAUNCH(ps, (k_row_bwd<N_, HIST, FORM == 1, FORM == 2>), dim3(rows_grid<N_>(c, g.B, c->NX)), dim3(BDOF_THREADS), 0, g.st, a);
     }); }));
 }
 
-// The detector kernels of the streaming engine; B wavefields of the current sub-batch.  Return the grid (= number of partial
-// sums when meas != null).
-static LossArgs loss_args(bdof_ctx* c, int B, const DetPlane& det, const cf* in, cf* out_hyb, cf* out_wave, const float* meas,
-                          float in_scale, float out_scale) {
+// The detector kernels of the streaming engine on sub-batch g; with meas they leave their partial sums from slot `part` on and
+// return how many (= the grid).
+static LossArgs loss_args(bdof_ctx* c, const Group& g, const DetPlane& det, const cf* in, cf* out_hyb, cf* out_wave, const float* meas,
+                          float in_scale, float out_scale, int part) {
     LossArgs a{};
-    a.in = sub_field(c, in);
-    a.out_hyb = sub_field(c, out_hyb);
-    a.out_wave = sub_field(c, out_wave);
-    a.meas = sub_field(c, meas);
-    a.partial = c->partial + 2 * c->sub_part;
-    a.B = B;
+    a.in = sub_field(c, g, in);
+    a.out_hyb = sub_field(c, g, out_hyb);
+    a.out_wave = sub_field(c, g, out_wave);
+    a.meas = sub_field(c, g, meas);
+    a.partial = c->partial + 2 * part;
+    a.B = g.B;
     a.in_scale = in_scale;
     a.out_scale = out_scale;
     a.det = det;
     return a;
 }
 // Real-space detector on L1 rows.
-static int launch_loss_real(bdof_ctx* c, int B, const DetPlane& det, const cf* in, cf* out_hyb, bool tstore, cf* out_wave, const float* meas,
-                            float in_scale, float out_scale) {
-    ProfScope ps(c, BDOF_K_LOSS);
-    LossArgs a = loss_args(c, B, det, in, out_hyb, out_wave, meas, in_scale, out_scale);
+static int launch_loss_real(bdof_ctx* c, const Group& g, const DetPlane& det, const cf* in, cf* out_hyb, bool tstore, cf* out_wave, const float* meas,
+                            float in_scale, float out_scale, int part = 0) {
+    ProfScope ps(c, BDOF_K_LOSS, g.st);
+    LossArgs a = loss_args(c, g, det, in, out_hyb, out_wave, meas, in_scale, out_scale, part);
     a.R = c->NX;
     a.twiddle = c->twY;
     int grid = 0;
-    DISPATCH_N(c->NY, grid = rows_grid<N_>(c, B, c->NX); with_bool(tstore, [&](auto TSTORE) { with_bool(meas && loss_is_poisson(c), [&](auto PSN) {
-        hipLaunchKernelGGL((k_row_loss<N_, false, TSTORE, PSN>), dim3(grid), dim3(BDOF_THREADS), 0, c->sub_stream, a);
+    DISPATCH_N(c->NY, grid = rows_grid<N_>(c, g.B, c->NX); with_bool(tstore, [&](auto TSTORE) { with_bool(meas && loss_is_poisson(c), [&](auto PSN) {
+        hipLaunchKernelGGL((k_row_loss<N_, false, TSTORE, PSN>), dim3(grid), dim3(BDOF_THREADS), 0, g.st, a);
     }); }));
     return grid;
 }
 
 // Far-field detector on L2 rows; the seed goes back transposed into L1.
-static int launch_loss_far(bdof_ctx* c, int B, const DetPlane& det, const cf* in, cf* out_hyb, cf* out_wave, const float* meas,
-                           float in_scale, float out_scale) {
-    ProfScope ps(c, BDOF_K_LOSS);
-    LossArgs a = loss_args(c, B, det, in, out_hyb, out_wave, meas, in_scale, out_scale);
+static int launch_loss_far(bdof_ctx* c, const Group& g, const DetPlane& det, const cf* in, cf* out_hyb, cf* out_wave, const float* meas,
+                           float in_scale, float out_scale, int part = 0) {
+    ProfScope ps(c, BDOF_K_LOSS, g.st);
+    LossArgs a = loss_args(c, g, det, in, out_hyb, out_wave, meas, in_scale, out_scale, part);
     a.R = c->NY;
     a.twiddle = c->twX;
     int grid = 0;
-    DISPATCH_N(c->NX, grid = rows_grid<N_>(c, B, c->NY); with_bool(meas && loss_is_poisson(c), [&](auto PSN) {
-        hipLaunchKernelGGL((k_row_loss<N_, true, true, PSN>), dim3(grid), dim3(BDOF_THREADS), 0, c->sub_stream, a);
+    DISPATCH_N(c->NX, grid = rows_grid<N_>(c, g.B, c->NY); with_bool(meas && loss_is_poisson(c), [&](auto PSN) {
+        hipLaunchKernelGGL((k_row_loss<N_, true, true, PSN>), dim3(grid), dim3(BDOF_THREADS), 0, g.st, a);
     }));
     return grid;
 }
 
-// ---- the forward sweep ---------------------------------------------------------------------------
+// ---- the sweeps of the streaming engine ---------------------------------------------------------------------------
 // bufA is the L2-type scratch (row kernels' transposed output), bufB the L1-type scratch.
-// On return the field the detector step starts from is
-//   DET_NONE, numpy_skip_last : bufA = R phi_{S-1} in L1 order (plain store), un-normalised
-//   DET_NONE, tf_all          : bufB = psi_hat_S (L1)
+// Where the forward sweep leaves the field the detector step starts from, and how that step reads it:
+//   DET_NONE, numpy_skip_last : bufA = R phi_{S-1} in L1 order (plain store), un-normalised (scale 1 / NY)
+//   DET_NONE, tf_all          : bufB = psi_hat_S (L1), made with the slice step's table
 //   DET_NEAR                  : bufB = d_hat (L1)    (tf_all: one step with the combined transfer function)
 //   DET_FAR                   : bufA = R phi_{S-1} in L2 order, un-normalised (|fft2| is unchanged by the
 //                               unit-modulus transfer function, so tf_all needs no extra step here)
+struct DetRoute {
+    bool far;              // the far-field kernel on L2 rows (launch_loss_far), else the real-space one on L1 rows
+    const cf* in;          // the buffer the detector kernel reads
+    float in_scale;
+    const cf* h;           // table of the transfer-function step that makes `in` of the last slice's R phi_{S-1}; null: none
+    const cf* pfield;      // the carrier field at the detector (probe stack) in the kernel's layout
+};
+static DetRoute det_route(const bdof_ctx* c) {
+    const bool tf_all = c->variant == BDOF_VARIANT_TF_ALL;
+    if (c->det_mode == BDOF_DET_FAR) return DetRoute{true, c->bufA, 1.f, nullptr, c->pdetT};
+    if (c->det_mode == BDOF_DET_NONE && !tf_all) return DetRoute{false, c->bufA, 1.f / (float)c->NY, nullptr, c->pdet};
+    return DetRoute{false, c->bufB, 1.f, c->det_mode == BDOF_DET_NONE ? c->hs : tf_all ? c->hcomb : c->hdet, c->pdet};
+}
+
 enum { TAPE_NONE = 0, TAPE_HISTORY = 1, TAPE_LAST = 2 };
+// Every group of the split runs A_z then the transfer-function step, slice by slice, on its own stream; each launch is handed
+// its group and the slice z whose copy of the dithered constants it takes (the step after A_z takes copy z, as A_z does).
 // TAPE_LAST (tape-free adjoint): only the real-space phi_{S-1} is kept (tape slot 0); the adjoint sweep marches it back.
 // TAPE_HISTORY keeps psi_hat_{z+1} (the transfer-function step's output) per slice: probe_array of np_funcs.py:43.
 // fused (fused_mode; TAPE_HISTORY only): slices 0 .. S-2 run as one k_slice_y / k_slice_x launch each, ping-ponging bufA / bufB in
 // real space; tape slot z holds the scattered part of phi_z (z <= S-2) and slot S-1 psi_hat_{S-1}, which one k_row_prop launch with
 // the hx-only table makes of the ky-domain lines k_slice_y<TAIL> left in bufA.  The last slice and the detector run as always.
-static void forward_sweep(bdof_ctx* c, const Group* groups, int ngroups, int tape_mode, bool fused = false) {
+static void forward_sweep(bdof_ctx* c, const Split& split, int tape_mode, bool fused = false) {
     const size_t fld = (size_t)c->Bmax * c->NX * c->NY;
-    const bool tf_all = c->variant == BDOF_VARIANT_TF_ALL;
+    const DetRoute dr = det_route(c);
     const int nz = n_steps(c);
     for (int z = 0; z < nz; ++z) {
         const cf* in = nullptr;
@@ -733,29 +733,61 @@ static void forward_sweep(bdof_ctx* c, const Group* groups, int ngroups, int tap
         const bool last = z == nz - 1;
         if (fused && last) in = c->tape + (size_t)z * fld;
         if (fused && !last) {
-            for (int gi = 0; gi < ngroups; ++gi) {
-                use_group(c, groups[gi]);
-                launch_slice(c, groups[gi].B, z, (z & 1) ? c->bufA : c->bufB, (z & 1) ? c->bufB : c->bufA, c->tape + (size_t)z * fld);
-                if (z == nz - 2) launch_row_prop(c, groups[gi].B, c->bufA, c->tape + (size_t)(nz - 1) * fld, c->hx_rows, 1.f, 0, z, BDOF_K_LOSS);
+            for (const Group& g : split) {
+                launch_slice(c, g, z, (z & 1) ? c->bufA : c->bufB, (z & 1) ? c->bufB : c->bufA, c->tape + (size_t)z * fld);
+                if (z == nz - 2) launch_row_prop(c, g, c->bufA, c->tape + (size_t)(nz - 1) * fld, c->hx_rows, 1.f, 0, z, BDOF_K_LOSS);
             }
             continue;
         }
         cf* phi = tape_mode == TAPE_LAST && last ? c->tape : nullptr;
-        for (int gi = 0; gi < ngroups; ++gi) {
-            const int B = groups[gi].B;
-            use_group(c, groups[gi]);
+        for (const Group& g : split) {
             if (!last) {
-                launch_row_fwd(c, B, z, in, c->bufA, true, phi);
-                launch_row_prop(c, B, c->bufA, tape_mode == TAPE_HISTORY ? c->tape + (size_t)steps(c).tape_write(z) * fld : c->bufB, c->hs, 1.f, 0);
-            } else if (c->det_mode == BDOF_DET_NONE && !tf_all) {
-                launch_row_fwd(c, B, z, in, c->bufA, false, phi);
+                launch_row_fwd(c, g, z, in, c->bufA, true, phi);
+                launch_row_prop(c, g, c->bufA, tape_mode == TAPE_HISTORY ? c->tape + (size_t)steps(c).tape_write(z) * fld : c->bufB, c->hs, 1.f, 0, z);
             } else {
-                launch_row_fwd(c, B, z, in, c->bufA, true, phi);
+                launch_row_fwd(c, g, z, in, c->bufA, dr.far || dr.h, phi);
                 // (fused route: the step's few remaining transfer-function launches outside the adjoint sweep are filed with the detector)
-                const int cls = fused ? BDOF_K_LOSS : BDOF_K_COL_PROP;
-                if (c->det_mode == BDOF_DET_NONE) launch_row_prop(c, B, c->bufA, c->bufB, c->hs, 1.f, 0, -1, cls);
-                else if (c->det_mode == BDOF_DET_NEAR) launch_row_prop(c, B, c->bufA, c->bufB, tf_all ? c->hcomb : c->hdet, 1.f, 0, -1, cls);
+                if (dr.h) launch_row_prop(c, g, c->bufA, c->bufB, dr.h, 1.f, 0, z, fused ? BDOF_K_LOSS : BDOF_K_COL_PROP);
             }
+        }
+    }
+}
+
+// One step of the tape-free march back (BDOF_CFG_RECOMPUTE): P is unitary and c_z is invertible, so the forward
+// wave is marched BACK beside the adjoint field instead of being stored per slice, phi_{z-1} = P^H (phi_z / c_z).
+// A'_z of form `hist` on the adjoint field (bufB -> bufA) with phi_z from `phi` (real space: phi_real); `step`: the adjoint
+// transfer-function step to the slice below (bufA -> bufB); `march`: phi_{z-1} into rc1 (L1), through R eps(psi_z) in rc2 (L2).
+static void march_back(bdof_ctx* c, const Group& g, int z, int hist, const cf* phi, bool phi_real, bool step, bool march, cf* rc1, cf* rc2,
+                       const GradTarget* gt = nullptr) {
+    launch_row_bwd(c, g, z, c->bufB, phi, step ? c->bufA : nullptr, hist, 1.f, gt);
+    if (step) launch_row_prop(c, g, c->bufA, c->bufB, c->hs, 1.f, 1, z - 1);
+    if (march) {
+        launch_row_unmod(c, g, z, phi, rc2, phi_real, 1.f);
+        launch_row_prop(c, g, rc2, rc1, c->hs, 1.f, 1, z - 1);
+    }
+}
+
+// The backward sweep of bdof_loss_grad from the seed g_hat(phi_{S-1}) in bufB: A'_z (L1 -> L2), then the adjoint
+// transfer-function step (L2 -> L1), in the form that matches what the forward sweep left on the tape.
+//   history  : A'_z recomputes phi_z from psi_hat_z, which the transfer-function kernel writes anyway (one more transform per
+//              launch, no tape write in A_z: 104 instead of 112 B per pixel per slice-step, 67.6 -> 65.3 ms per step at 512^3 x 25)
+//   fused    : the tape holds phi_z itself (HIST 0) below the last slice, whose psi_hat sits in slot S-1
+//   tape-free: one A_z^-1 launch and one more adjoint transfer-function launch per slice (+40 B per pixel per slice-step), S - 3
+//              fields per wavefield less memory.  phi_{S-1} is kept by the forward sweep (real space, tape slot 0); slots 1 / 2
+//              hold the marched-back wave in L1 / L2 order; slice 0 takes phi_0 from the probe as the history form does.
+static void adjoint_sweep(bdof_ctx* c, const Split& split, bool fused) {
+    const size_t fld = (size_t)c->Bmax * c->NX * c->NY;
+    const int nz = n_steps(c);
+    for (int z = nz - 1; z >= 0; --z) {
+        const bool top = z == nz - 1;
+        for (const Group& g : split) {
+            if (c->recompute) {
+                march_back(c, g, z, z == 0 ? 2 : top ? 0 : 3, top ? c->tape : c->tape + fld, top, z > 0, z > 1, c->tape + fld, c->tape + 2 * fld);
+                continue;
+            }
+            if (fused) launch_row_bwd(c, g, z, c->bufB, c->tape + (size_t)z * fld, z > 0 ? c->bufA : nullptr, top ? 1 : 0);
+            else launch_row_bwd(c, g, z, c->bufB, z > 0 ? c->tape + (size_t)steps(c).tape_read(z) * fld : nullptr, z > 0 ? c->bufA : nullptr, z > 0 ? 1 : 2);
+            if (z > 0) launch_row_prop(c, g, c->bufA, c->bufB, c->hs, 1.f, 1, z - 1);
         }
     }
 }
@@ -874,7 +906,7 @@ static int g_elem_grid(const bdof_ctx* c, size_t n) { return (int)std::min<size_
 
 // one transfer-function step in place: field <- F^-1' ( h * F field )
 static int generic_prop(bdof_ctx* c, int B, rocfft_plan pf, rocfft_plan pi, cf* field, const cf* h, int conj_h) {
-    ProfScope ps(c, BDOF_K_COL_PROP);
+    ProfScope ps(c, BDOF_K_COL_PROP, c->stream);
     void* buf[1] = {field};
     RFC(c, rocfft_execute(pf, buf, nullptr, c->fft.info));
     const size_t n = (size_t)B * c->NX * c->NY;
@@ -893,7 +925,7 @@ static int generic_forward_sweep(bdof_ctx* c, int B, bool tape, rocfft_plan pf, 
     const int nz = n_steps(c);
     for (int z = 0; z < nz; ++z) {
         {
-            ProfScope ps(c, BDOF_K_ROW_FWD);
+            ProfScope ps(c, BDOF_K_ROW_FWD, c->stream);
             GModArgs m{c->bufA, z == 0 ? c->probe : nullptr, tape ? c->tape + (size_t)z * fld : nullptr, c->obj, B, c->NX, c->NY, z,
                        make_float2((float)a.real(), (float)a.imag()), c->pstack ? c->pstack + (size_t)z * c->NX * c->NY : nullptr,
                        cfl(a * c->cbm1)};
@@ -960,8 +992,8 @@ static int generic_loss_grad(bdof_ctx* c, int B, const float* meas, void* out_wa
     const bool f64 = c->adj64;
     if (f64 && !c->have_h64) return fail(c, BDOF_ERR_STATE, "float64 adjoint: bdof_set_physics_f64 has not been called");
     {
-        ProfScope ps(c, BDOF_K_LOSS);
-        DetPlane det = det_plane(c, B, c->pdet);
+        ProfScope ps(c, BDOF_K_LOSS, c->stream);
+        DetPlane det = det_plane(c, whole(c, B), B, c->pdet);
         set_carrier(det, a);                       // the carrier as the sweep's own recurrence left it
         GLossArgs la = g_loss_args(c, B, det, c->bufA, (cf*)out_wave, meas);
         la.seed64 = f64 ? c->g64 : nullptr;        // float64 adjoint: every bin's seed stays in float64, no adjoint carrier to split off
@@ -974,7 +1006,7 @@ static int generic_loss_grad(bdof_ctx* c, int B, const float* meas, void* out_wa
         if ((r = field_plans(c, c->NX, c->NY, B, true, &pf64, &pi64))) return r;
         void* b64[1] = {c->g64};
         auto prop64 = [&](const double2* h) -> int {
-            ProfScope ps(c, BDOF_K_COL_PROP);
+            ProfScope ps(c, BDOF_K_COL_PROP, c->stream);
             RFC(c, rocfft_execute(pf64, b64, nullptr, c->fft.info));
             hipLaunchKernelGGL(k_g_hmul64, dim3(egrid), dim3(256), 0, c->stream, c->g64, h, B, c->NX, c->NY, 1);
             RFC(c, rocfft_execute(pi64, b64, nullptr, c->fft.info));
@@ -985,7 +1017,7 @@ static int generic_loss_grad(bdof_ctx* c, int B, const float* meas, void* out_wa
         for (int z = c->S - 1; z >= 0; --z) {
             const bool prop_after = z < c->S - 1 || (tf_all && c->det_mode != BDOF_DET_FAR);
             if (prop_after && (r = prop64(c->hs64))) return r;
-            ProfScope ps(c, BDOF_K_ROW_BWD);
+            ProfScope ps(c, BDOF_K_ROW_BWD, c->stream);
             GBwd64Args ba{c->g64, c->tape + (size_t)z * fld, c->grot, c->obj, B, c->NX, c->NY, z, (double)c->k,
                           d2(carrier_z(c, z) * (1.0 + c->cbm1)), c->pstack ? 1 : 0};
             hipLaunchKernelGGL(k_g_bwd64, dim3(egrid), dim3(256), 0, c->stream, ba);
@@ -1005,9 +1037,9 @@ static int generic_loss_grad(bdof_ctx* c, int B, const float* meas, void* out_wa
     for (int z = nz - 1; z >= 0; --z) {
         const bool prop_after = z < nz - 1 || (tf_all && c->det_mode != BDOF_DET_FAR);
         if (prop_after && (r = generic_prop(c, B, pf, pi, c->bufA, hs_slice(c, z), 1))) return r;      // conj of the forward step's copy
-        ProfScope ps(c, BDOF_K_ROW_BWD);
+        ProfScope ps(c, BDOF_K_ROW_BWD, c->stream);
         GBwdArgs ba{c->bufA, c->tape + (size_t)z * fld, c->grot, c->obj, B, c->NX, c->NY, z, c->k, carrier_phi_at(c, z), c->pstack ? 1 : 0,
-                    adj_carrier_at(c, steps(c).steps_back(z))};
+                    adj_carrier_at(c, whole(c, B), steps(c).steps_back(z))};
         with_bool(c->bin > 1, [&](auto BIN) { hipLaunchKernelGGL(k_g_bwd<BIN>, dim3(egrid), dim3(256), 0, c->stream, ba); });
     }
     return 0;
@@ -1054,7 +1086,7 @@ static int resident_run(bdof_ctx* c, int B, const float* meas, void* out_wave, b
         HIPC(c, hipMemcpy(c->res_carrier, car.data(), sizeof(cf) * car.size(), hipMemcpyHostToDevice));
         c->res_dirty = false;
     }
-    ProfScope ps(c, BDOF_K_ROW_FWD);
+    ProfScope ps(c, BDOF_K_ROW_FWD, c->stream);
     const bool grad = do_grad && meas;
     const bool hdith = c->hs_copies > 0 && c->hsT_d;
     ResArgs a{};
@@ -1079,7 +1111,7 @@ static int resident_run(bdof_ctx* c, int B, const float* meas, void* out_wave, b
     a.tf_all = c->variant == BDOF_VARIANT_TF_ALL ? 1 : 0;
     a.do_grad = grad ? 1 : 0;
     a.k = c->k;
-    a.det = det_plane(c, B, c->pdet);
+    a.det = det_plane(c, whole(c, B), B, c->pdet);
     const int grid = B < c->npartial ? B : c->npartial;
     int r = 0, waves = 1;
     switch (c->NX) {
@@ -1183,7 +1215,6 @@ int bdof_ctx_create(bdof_ctx** out, int device, void* stream) {
     }
     (void)hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming);
     for (int i = 0; i < BDOF_MAX_GROUPS - 1; ++i) (void)hipEventCreateWithFlags(&c->ev_join[i], hipEventDisableTiming);
-    c->sub_stream = c->stream;
     if (const char* e = std::getenv("BDOF_STREAMS")) c->n_streams = std::atoi(e);
     *out = c;
     return 0;
@@ -1669,6 +1700,12 @@ static void set_batch_views(bdof_ctx* c, const int* angle_of_b, const int* xoff,
     c->obj.xoff = xoff;
     c->obj.yoff = yoff;
 }
+// What every batch call does once its arguments have passed: the device, the batch's index arrays, the modulation table for k
+static int begin_batch(bdof_ctx* c, const int* angle_of_b, const int* xoff, const int* yoff, float k) {
+    HIPC(c, hipSetDevice(c->device));
+    set_batch_views(c, angle_of_b, xoff, yoff);
+    return ensure_modulation_k(c, k);
+}
 // the batch's view of the caller's (delta, beta) rows: the float64 paths modulate from the rows, not from the table c->mod
 static ObjView rows_view(const bdof_ctx* c, const int* angle_of_b, const int* xoff, const int* yoff) {
     ObjView o = c->obj;
@@ -1684,9 +1721,7 @@ int bdof_forward(bdof_ctx* c, int B, const int* angle_of_b, const int* xoff, con
     if ((r = check_ready(c, B)) || (r = need_angles(c, angle_of_b))) return r;
     if (keep_tape && !c->with_grad) return fail(c, BDOF_ERR_STATE, "keep_tape needs bdof_configure(with_grad=1)");
     if (keep_tape && c->recompute) return fail(c, BDOF_ERR_STATE, "the per-slice history is not kept in tape-free (recompute) mode");
-    HIPC(c, hipSetDevice(c->device));
-    set_batch_views(c, angle_of_b, xoff, yoff);
-    if ((r = ensure_modulation_k(c, c->k_fft))) return r;
+    if ((r = begin_batch(c, angle_of_b, xoff, yoff, c->k_fft))) return r;
     if (use_resident(c, B) && !keep_tape) {
         if ((r = resident_run(c, B, nullptr, out_wave, false))) return r;
         c->tape_valid = c->last_valid = false;
@@ -1698,38 +1733,36 @@ int bdof_forward(bdof_ctx* c, int B, const int* angle_of_b, const int* xoff, con
         c->tape_valid = c->last_valid = false;
         return launched(c);
     }
-    const bool tf_all = c->variant == BDOF_VARIANT_TF_ALL;
-    Group groups[BDOF_MAX_GROUPS];
-    const int ng = batch_groups(c, B, c->NX, 16, groups);
-    if ((r = fork_streams(c, ng))) return r;
-    forward_sweep(c, groups, ng, keep_tape ? TAPE_HISTORY : TAPE_NONE);
-    if ((r = join_streams(c, ng))) return r;
+    Split split;
+    if ((r = split.open(c, B, c->NX, 16))) return r;
+    forward_sweep(c, split, keep_tape ? TAPE_HISTORY : TAPE_NONE);
+    if ((r = split.close(c))) return r;
     c->tape_valid = keep_tape != 0;
     c->last_valid = false;
+    const DetRoute dr = det_route(c);
+    const Group all = whole(c, B);
     if (out_wave) {
-        if (c->det_mode == BDOF_DET_FAR)
-            launch_loss_far(c, B, wave_plane(c, carrier_det(c), c->pdetT), c->bufA, nullptr, (cf*)out_wave, nullptr, 1.f, 1.f);
-        else if (c->det_mode == BDOF_DET_NONE && !tf_all)
-            launch_loss_real(c, B, wave_plane(c, carrier_det(c), c->pdet), c->bufA, nullptr, false, (cf*)out_wave, nullptr, 1.f / c->NY, 1.f);
-        else
-            launch_loss_real(c, B, wave_plane(c, carrier_det(c), c->pdet), c->bufB, nullptr, false, (cf*)out_wave, nullptr, 1.f, 1.f);
+        const DetPlane det = wave_plane(c, carrier_det(c), dr.pfield);
+        if (dr.far) launch_loss_far(c, all, det, dr.in, nullptr, (cf*)out_wave, nullptr, 1.f, 1.f);
+        else launch_loss_real(c, all, det, dr.in, nullptr, false, (cf*)out_wave, nullptr, dr.in_scale, 1.f);
     }
-    if (keep_tape && !tf_all) {
+    if (keep_tape && c->variant != BDOF_VARIANT_TF_ALL) {
         // probe_array[S-1] = phi_{S-1} (np_funcs.py:41-43): keep R phi_{S-1} in L1 order in bufA
         if (!(c->det_mode == BDOF_DET_NONE)) {
             const size_t fld = (size_t)c->Bmax * c->NX * c->NY;
             const int nz = n_steps(c);
             const cf* in = nz > 1 ? c->tape + (size_t)(nz - 2) * fld : nullptr;   // psi_hat_{S-1}
-            launch_row_fwd(c, B, nz - 1, in, c->bufA, false);
+            launch_row_fwd(c, all, nz - 1, in, c->bufA, false);
         }
         c->last_valid = true;
     }
     return launched(c);
 }
 
-int bdof_forward_range(bdof_ctx* c, int B, const int* angle_of_b, const int* xoff, const int* yoff, int z0, int nz,
-                       const void* in_real, void* out_real, int prop_last) {
-    if (int rb = need_unbinned(c, "bdof_forward_range")) return rb;
+// The range sweep behind bdof_forward_range (h = c->hs: the ctx's slice step, in its dithered copies) and bdof_forward_range_h
+// (h: the caller's table for every transfer-function step of the range).
+static int forward_range(bdof_ctx* c, int B, const int* angle_of_b, const int* xoff, const int* yoff, int z0, int nz,
+                         const void* in_real, void* out_real, int prop_last, const cf* h) {
     int r = check_ready(c, B);
     if (r) return r;
     if (!in_real || !out_real) return BDOF_ERR_ARG;
@@ -1738,40 +1771,36 @@ int bdof_forward_range(bdof_ctx* c, int B, const int* angle_of_b, const int* xof
     if ((r = need_angles(c, angle_of_b))) return r;
     if (c->range_car && (B != c->range_car_B || z0 != c->range_car_z0))
         return fail(c, BDOF_ERR_ARG, "the range carriers (bdof_set_range_carrier) were handed over for another batch / first slice");
-    HIPC(c, hipSetDevice(c->device));
-    set_batch_views(c, angle_of_b, xoff, yoff);
-    if ((r = ensure_modulation_k(c, c->k_fft))) return r;
-    Group groups[BDOF_MAX_GROUPS];
-    const int ng = batch_groups(c, B, c->NX, 16, groups);
-    if ((r = fork_streams(c, ng))) return r;
+    if ((r = begin_batch(c, angle_of_b, xoff, yoff, c->k_fft))) return r;
+    Split split;
+    if ((r = split.open(c, B, c->NX, 16))) return r;
     for (int z = z0; z < z0 + nz; ++z) {
-        const bool last = z == z0 + nz - 1;
-        for (int gi = 0; gi < ng; ++gi) {
-            const int Bg = groups[gi].B;
-            use_group(c, groups[gi]);
-            const cf* start = z == z0 ? (const cf*)in_real : nullptr;
-            if (!last || prop_last) {
-                launch_row_fwd(c, Bg, z, c->bufB, c->bufA, true, nullptr, start);
-                launch_row_prop(c, Bg, c->bufA, c->bufB, c->hs, 1.f, 0);
-            } else {
-                launch_row_fwd(c, Bg, z, c->bufB, c->bufA, false, nullptr, start);
-            }
+        const bool step = z < z0 + nz - 1 || prop_last;
+        for (const Group& g : split) {
+            launch_row_fwd(c, g, z, c->bufB, c->bufA, step, nullptr, z == z0 ? (const cf*)in_real : nullptr);
+            if (step) launch_row_prop(c, g, c->bufA, c->bufB, h, 1.f, 0, z);
         }
     }
     // real-space wave after the range: psi_{z0+nz} (prop_last) or phi_{z0+nz-1}
     const int zl = z0 + nz - 1;
-    for (int gi = 0; gi < ng; ++gi) {
-        use_group(c, groups[gi]);
+    for (const Group& g : split) {
         if (prop_last)
-            launch_loss_real(c, groups[gi].B, wave_plane(c, carrier_z(c, zl + 1), zl + 1 < c->S ? slice_carrier_field(c, zl + 1) : c->pdet),
+            launch_loss_real(c, g, wave_plane(c, carrier_z(c, zl + 1), zl + 1 < c->S ? slice_carrier_field(c, zl + 1) : c->pdet),
                              c->bufB, nullptr, false, (cf*)out_real, nullptr, 1.f, 1.f);
         else
-            launch_loss_real(c, groups[gi].B, wave_plane(c, carrier_z(c, zl) * (1.0 + c->cbm1), slice_carrier_field(c, zl)),
+            launch_loss_real(c, g, wave_plane(c, carrier_z(c, zl) * (1.0 + c->cbm1), slice_carrier_field(c, zl)),
                              c->bufA, nullptr, false, (cf*)out_real, nullptr, 1.f / c->NY, 1.f);
     }
-    if ((r = join_streams(c, ng))) return r;
+    if ((r = split.close(c))) return r;
     c->tape_valid = c->last_valid = false;
     return launched(c);
+}
+
+int bdof_forward_range(bdof_ctx* c, int B, const int* angle_of_b, const int* xoff, const int* yoff, int z0, int nz,
+                       const void* in_real, void* out_real, int prop_last) {
+    if (int rb = need_unbinned(c, "bdof_forward_range")) return rb;
+    if (!c) return BDOF_ERR_ARG;
+    return forward_range(c, B, angle_of_b, xoff, yoff, z0, nz, in_real, out_real, prop_last, c->hs);
 }
 
 // Carrier fields for the NEXT bdof_forward_range calls over slices z0 .. z0 + nz - 1 of B wavefields: stack [nz][B][NX][NY] complex64
@@ -1797,10 +1826,15 @@ int bdof_forward_range_h(bdof_ctx* c, int B, const int* angle_of_b, const int* x
                          const void* in_real, void* out_real, int prop_last, const void* h) {
     if (int rb = need_unbinned(c, "bdof_forward_range_h")) return rb;
     if (!c || !h) return BDOF_ERR_ARG;
-    c->hs_override = (const cf*)h;
-    const int r = bdof_forward_range(c, B, angle_of_b, xoff, yoff, z0, nz, in_real, out_real, prop_last);
-    c->hs_override = nullptr;
-    return r;
+    return forward_range(c, B, angle_of_b, xoff, yoff, z0, nz, in_real, out_real, prop_last, (const cf*)h);
+}
+
+// real-space fields [b][x][y] -> R (transposed, L2): what a transfer-function launch takes
+// (defined at the kernel's first use in the file, where the inline launches stood: templates are instantiated in the order of
+// first use, and hipcc commutes a few additions in six kernels when that order changes — MEASUREMENTS.md, device-code check)
+static void launch_real_to_hyb(bdof_ctx* c, const Group& g, const cf* in, cf* out) {
+    RealToHybArgs a{sub_field(c, g, in), sub_field(c, g, out), g.B, c->NX, c->twY};
+    DISPATCH_N(c->NY, { hipLaunchKernelGGL((k_row_real_to_hyb<N_>), dim3(rows_grid<N_>(c, g.B, c->NX)), dim3(BDOF_THREADS), 0, g.st, a); });
 }
 
 // Adjoint of bdof_forward_range(prop_last = 1) in the tape-free form: the forward wave is marched back from the range's end
@@ -1817,43 +1851,29 @@ int bdof_adjoint_range(bdof_ctx* c, int B, const int* angle_of_b, const int* xof
     if (!c->with_grad || !c->tape) return fail(c, BDOF_ERR_STATE, "bdof_adjoint_range needs bdof_configure(with_grad=1)");
     if (c->S < 2) return fail(c, BDOF_ERR_SIZE, "bdof_adjoint_range needs at least two tape fields (S >= 2)");
     if ((r = need_angles(c, angle_of_b))) return r;
-    HIPC(c, hipSetDevice(c->device));
-    set_batch_views(c, angle_of_b, xoff, yoff);
-    if ((r = ensure_modulation_k(c, c->k_fft))) return r;
+    if ((r = begin_batch(c, angle_of_b, xoff, yoff, c->k_fft))) return r;
     const size_t fld = (size_t)c->Bmax * c->NX * c->NY;
     cf* const rc1 = c->tape;                       // marched-back phi_hat_z (L1)
     cf* const rc2 = c->tape + fld;                 // R eps(psi_z) (L2)
-    Group groups[BDOF_MAX_GROUPS];
-    const int ng = batch_groups(c, B, c->NX, 16, groups);
-    if ((r = fork_streams(c, ng))) return r;
+    Split split;
+    if ((r = split.open(c, B, c->NX, 16))) return r;
     const int zt = z0 + nz - 1;
-    for (int gi = 0; gi < ng; ++gi) {
-        const int Bg = groups[gi].B;
-        use_group(c, groups[gi]);
+    for (const Group& g : split) {
         // phi_{zt} = P^H psi_{zt+1} and G(phi_{zt}) = P^H G(psi_{zt+1}): real space -> R (transposed) -> adjoint step
-        RealToHybArgs ra{sub_field(c, (const cf*)end_real), sub_field<cf>(c, c->bufA), Bg, c->NX, c->twY};
-        DISPATCH_N(c->NY, { hipLaunchKernelGGL((k_row_real_to_hyb<N_>), dim3(rows_grid<N_>(c, Bg, c->NX)), dim3(BDOF_THREADS), 0, c->sub_stream, ra); });
-        launch_row_prop(c, Bg, c->bufA, rc1, c->hs, 1.f, 1, zt);
-        RealToHybArgs rg{sub_field(c, (const cf*)g_end_real), sub_field<cf>(c, c->bufA), Bg, c->NX, c->twY};
-        DISPATCH_N(c->NY, { hipLaunchKernelGGL((k_row_real_to_hyb<N_>), dim3(rows_grid<N_>(c, Bg, c->NX)), dim3(BDOF_THREADS), 0, c->sub_stream, rg); });
-        launch_row_prop(c, Bg, c->bufA, c->bufB, c->hs, 1.f, 1, zt);
+        launch_real_to_hyb(c, g, (const cf*)end_real, c->bufA);
+        launch_row_prop(c, g, c->bufA, rc1, c->hs, 1.f, 1, zt);
+        launch_real_to_hyb(c, g, (const cf*)g_end_real, c->bufA);
+        launch_row_prop(c, g, c->bufA, c->bufB, c->hs, 1.f, 1, zt);
     }
     for (int z = zt; z >= z0; --z) {
-        for (int gi = 0; gi < ng; ++gi) {
-            const int Bg = groups[gi].B;
-            use_group(c, groups[gi]);
+        for (const Group& g : split) {
             GradTarget gt;
             gt.grot = (float2*)grot_range; gt.S_ = nz; gt.z_ = z - z0;
             gt.gpsi = z == z0 ? (cf*)g_start_real : nullptr;
-            launch_row_bwd(c, Bg, z, c->bufB, rc1, z > z0 ? c->bufA : nullptr, 3, 1.f, &gt);
-            if (z > z0) {
-                launch_row_prop(c, Bg, c->bufA, c->bufB, c->hs, 1.f, 1, z - 1);
-                launch_row_unmod(c, Bg, z, rc1, rc2, false, 1.f);
-                launch_row_prop(c, Bg, rc2, rc1, c->hs, 1.f, 1, z - 1);
-            }
+            march_back(c, g, z, 3, rc1, false, z > z0, z > z0, rc1, rc2, &gt);
         }
     }
-    if ((r = join_streams(c, ng))) return r;
+    if ((r = split.close(c))) return r;
     c->tape_valid = c->last_valid = false;
     c->gpsi_src = nullptr;
     return launched(c);
@@ -2314,12 +2334,12 @@ int bdof_tape_to_real(bdof_ctx* c, int i, int B, void* out) {
     if (i < 0 || i >= nz) return fail(c, BDOF_ERR_ARG, "slice index outside [0, S / slice binning)");
     const size_t fld = (size_t)c->Bmax * c->NX * c->NY;
     if (i < nz - 1) {
-        launch_loss_real(c, B, wave_plane(c, carrier_z(c, i + 1), slice_carrier_field(c, i + 1)), c->tape + (size_t)i * fld, nullptr, false,
+        launch_loss_real(c, whole(c, B), wave_plane(c, carrier_z(c, i + 1), slice_carrier_field(c, i + 1)), c->tape + (size_t)i * fld, nullptr, false,
                          (cf*)out, nullptr, 1.f, 1.f);
     } else {
         if (!c->last_valid)
             return fail(c, BDOF_ERR_STATE, "the last slice's wave is only kept after bdof_forward(keep_tape=1) with the numpy_skip_last variant");
-        launch_loss_real(c, B, wave_plane(c, carrier_z(c, nz - 1) * (1.0 + c->cbm1), slice_carrier_field(c, nz - 1)), c->bufA, nullptr, false,
+        launch_loss_real(c, whole(c, B), wave_plane(c, carrier_z(c, nz - 1) * (1.0 + c->cbm1), slice_carrier_field(c, nz - 1)), c->bufA, nullptr, false,
                          (cf*)out, nullptr, 1.f / c->NY, 1.f);
     }
     return launched(c);
@@ -2333,9 +2353,7 @@ int bdof_loss_grad(bdof_ctx* c, int B, const int* angle_of_b, const int* xoff, c
         return fail(c, BDOF_ERR_STATE, "bdof_set_meas_mode(1) needs a real-space detector and a scalar carrier");
     if (!c->with_grad || !c->grot) return fail(c, BDOF_ERR_STATE, "bdof_loss_grad needs bdof_configure(with_grad=1) with the gradient workspace (not flag 32)");
     if ((r = need_angles(c, angle_of_b))) return r;
-    HIPC(c, hipSetDevice(c->device));
-    set_batch_views(c, angle_of_b, xoff, yoff);
-    if ((r = ensure_modulation_k(c, c->k_fft))) return r;
+    if ((r = begin_batch(c, angle_of_b, xoff, yoff, c->k_fft))) return r;
     c->gpsi_src = c->gpsi0;
     c->gpsi_B = B;
     c->fused_last = 0;
@@ -2350,74 +2368,30 @@ int bdof_loss_grad(bdof_ctx* c, int B, const int* angle_of_b, const int* xoff, c
         c->gpsi_src = c->bufA;                  // the adjoint sweep ends with G(psi_0) in the field buffer, [b][x][y]
         return launched(c);
     }
-    const size_t fld = (size_t)c->Bmax * c->NX * c->NY;
-    const float NYf = (float)c->NY;
-    const bool tf_all = c->variant == BDOF_VARIANT_TF_ALL;
-    Group groups[BDOF_MAX_GROUPS];
-    const int ng = batch_groups(c, B, c->NX, 16, groups);
-    if ((r = fork_streams(c, ng))) return r;
-    // The tape is the per-slice history psi_hat_z that the transfer-function kernel writes anyway; A'_z recomputes phi_z from
-    // it (one more transform per launch, no tape write in A_z: 104 instead of 112 B per pixel per slice-step, 67.6 -> 65.3 ms
-    // per step at 512^3 x 25).
-    const bool recompute = c->recompute;
-    const int nz = n_steps(c);
+    Split split;
+    if ((r = split.open(c, B, c->NX, 16))) return r;
     const bool fused = fused_mode(c) != 0;
     c->fused_last = fused ? 1 : 0;
-    forward_sweep(c, groups, ng, recompute ? TAPE_LAST : TAPE_HISTORY, fused);
+    forward_sweep(c, split, c->recompute ? TAPE_LAST : TAPE_HISTORY, fused);
     c->tape_valid = false;      // the tape holds an incomplete history (or phi_{S-1} alone), not what bdof_tape_to_real expects
     c->last_valid = false;
     int npart = 0;
     // Detector + seed.  Afterwards bufB holds g_hat(phi_{S-1}) (L1 order, normalised hybrid).
-    for (int gi = 0; gi < ng; ++gi) {
-        const int Bg = groups[gi].B;
-        use_group(c, groups[gi], npart);
-        const DetPlane det = det_plane(c, B, c->det_mode == BDOF_DET_FAR ? c->pdetT : c->pdet);      // the whole batch's seed scale
-        if (c->det_mode == BDOF_DET_FAR) {
-            npart += launch_loss_far(c, Bg, det, c->bufA, c->bufB, (cf*)out_wave, meas, 1.f, 1.f);
-        } else if (c->det_mode == BDOF_DET_NONE && !tf_all) {
-            npart += launch_loss_real(c, Bg, det, c->bufA, c->bufB, false, (cf*)out_wave, meas, 1.f / NYf, 1.f / NYf);
+    const DetRoute dr = det_route(c);
+    for (const Group& g : split) {
+        const DetPlane det = det_plane(c, g, B, dr.pfield);      // the whole batch's seed scale
+        if (dr.far) {
+            npart += launch_loss_far(c, g, det, dr.in, c->bufB, (cf*)out_wave, meas, 1.f, 1.f, npart);
+        } else if (!dr.h) {
+            npart += launch_loss_real(c, g, det, dr.in, c->bufB, false, (cf*)out_wave, meas, dr.in_scale, dr.in_scale, npart);
         } else {
             // the detector wave came out of a transfer-function step: seed -> R (transposed) -> adjoint step
-            const cf* h = c->det_mode == BDOF_DET_NONE ? c->hs : (tf_all ? c->hcomb : c->hdet);
-            npart += launch_loss_real(c, Bg, det, c->bufB, c->bufA, true, (cf*)out_wave, meas, 1.f, 1.f);
-            launch_row_prop(c, Bg, c->bufA, c->bufB, h, 1.f, 1, nz - 1, fused ? BDOF_K_LOSS : BDOF_K_COL_PROP);
+            npart += launch_loss_real(c, g, det, dr.in, c->bufA, true, (cf*)out_wave, meas, 1.f, 1.f, npart);
+            launch_row_prop(c, g, c->bufA, c->bufB, dr.h, 1.f, 1, n_steps(c) - 1, fused ? BDOF_K_LOSS : BDOF_K_COL_PROP);
         }
     }
-    // backward sweep: A'_z (L1 -> L2), then the adjoint transfer-function step (L2 -> L1)
-    // Tape-free form (BDOF_CFG_RECOMPUTE): P is unitary and c_z is invertible, so the forward wave is marched
-    // BACK beside the adjoint field instead of being stored per slice: phi_{z-1} = P^H (phi_z / c_z) — one A_z^-1 launch and
-    // one more adjoint transfer-function launch per slice (+40 B per pixel per slice-step), S - 3 fields per wavefield less
-    // memory.  phi_{S-1} is kept by the forward sweep (real space, tape slot 0); slots 1 / 2 hold the marched-back wave in L1 /
-    // L2 order; slice 0 takes phi_0 from the probe as the history form does.
-    cf* const rc_last = c->tape;
-    cf* const rc1 = c->tape + fld;
-    cf* const rc2 = c->tape + 2 * fld;
-    for (int z = nz - 1; z >= 0; --z) {
-        for (int gi = 0; gi < ng; ++gi) {
-            use_group(c, groups[gi]);
-            if (recompute) {
-                const bool top = z == nz - 1;
-                if (z == 0) launch_row_bwd(c, groups[gi].B, z, c->bufB, nullptr, nullptr, 2);
-                else if (top) launch_row_bwd(c, groups[gi].B, z, c->bufB, rc_last, c->bufA, 0);
-                else launch_row_bwd(c, groups[gi].B, z, c->bufB, rc1, c->bufA, 3, 1.f);
-                if (z > 0) launch_row_prop(c, groups[gi].B, c->bufA, c->bufB, c->hs, 1.f, 1, z - 1);
-                if (z > 1) {
-                    launch_row_unmod(c, groups[gi].B, z, top ? rc_last : rc1, rc2, top, 1.f);
-                    launch_row_prop(c, groups[gi].B, rc2, rc1, c->hs, 1.f, 1, z - 1);
-                }
-                continue;
-            }
-            if (fused) {
-                // after the fused forward sweep the tape holds phi_z itself (HIST 0) below the last slice, whose psi_hat sits in slot S-1
-                launch_row_bwd(c, groups[gi].B, z, c->bufB, c->tape + (size_t)z * fld, z > 0 ? c->bufA : nullptr, z == nz - 1 ? 1 : 0);
-            } else {
-                launch_row_bwd(c, groups[gi].B, z, c->bufB, z > 0 ? c->tape + (size_t)steps(c).tape_read(z) * fld : nullptr, z > 0 ? c->bufA : nullptr,
-                               z > 0 ? 1 : 2);
-            }
-            if (z > 0) launch_row_prop(c, groups[gi].B, c->bufA, c->bufB, c->hs, 1.f, 1, z - 1);
-        }
-    }
-    if ((r = join_streams(c, ng))) return r;
+    adjoint_sweep(c, split, fused);
+    if ((r = split.close(c))) return r;
     hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, c->stream, c->partial, npart,
                        1.0 / ((double)B * c->NX * c->NY), c->loss_dev);
     return launched(c);
@@ -2508,7 +2482,7 @@ static int conv_tiling() {
     return e && e[0] == '1' ? 1 : 2;
 }
 
-template <bool BWD, int H, bool PF> static int launch_conv_hp(bdof_ctx* c, ConvArgs& a, ProfScope& ps) {
+template <bool BWD, int H, bool PF> static int launch_conv_hp(bdof_ctx* c, ConvArgs& a, ProfScope& ps) {      // on ps.st
     if constexpr (H == 2 || H == 4 || H == 8) {
         // second tiling (bdof_conv2.h): 64 x 32 tiles by LDS-DMA, static LDS, two workgroups per CU by registers
         if (conv_tiling() != 1 && a.NX % Conv2Cfg<H>::TX == 0 && a.NY % Conv2Cfg<H>::TY == 0) {
@@ -2521,19 +2495,20 @@ template <bool BWD, int H, bool PF> static int launch_conv_hp(bdof_ctx* c, ConvA
                 const int rounds = (run_tiles + slots - 1) / slots;
                 return 8 * ((run_tiles + rounds - 1) / rounds);
             };
-            BDOF_LAUNCH(ps, (k_conv2<BWD, H, PF>), dim3(plan(Conv2Cfg<H>::TX, 2)), dim3(Conv2Cfg<H>::THREADS), 0, c->sub_stream, a);
+            BDOF_LAUNCH(ps, (k_conv2<BWD, H, PF>), dim3(plan(Conv2Cfg<H>::TX, 2)), dim3(Conv2Cfg<H>::THREADS), 0, ps.st, a);
             return 0;
         }
     }
     if (int r = max_lds_once<k_conv<BWD, H, PF>>(c, 160 * 1024 - 1024)) return r;
     const int tiles = a.B * (a.NX / BDOF_CONV_TX) * (a.NY / BDOF_CONV_TY);
     const int grid = balanced_grid(c, tiles, 2);
-    BDOF_LAUNCH(ps, (k_conv<BWD, H, PF>), dim3(grid), dim3(BDOF_CONV_THREADS), conv_lds_bytes(c), c->sub_stream, a);
+    BDOF_LAUNCH(ps, (k_conv<BWD, H, PF>), dim3(grid), dim3(BDOF_CONV_THREADS), conv_lds_bytes(c), ps.st, a);
     return 0;
 }
 
-template <bool BWD> static int launch_conv(bdof_ctx* c, ConvArgs& a) {
-    ProfScope ps(c, BWD ? BDOF_K_ROW_BWD : BDOF_K_ROW_FWD, true);
+// one slice of the conv sweeps on g's stream; `a` addresses g's wavefields already
+template <bool BWD> static int launch_conv(bdof_ctx* c, const Group& g, ConvArgs& a) {
+    ProfScope ps(c, BWD ? BDOF_K_ROW_BWD : BDOF_K_ROW_FWD, g.st, true);
     // register-window fast paths for the common kernel sizes 5, 9, 17, 33 (H = 2, 4, 8, 16 = 2^L), the generic window H = 0 otherwise
     const int h = (c->taps.ks - 1) / 2;
     const int log_h = h == 2 ? 1 : h == 4 ? 2 : h == 8 ? 3 : h == 16 ? 4 : 0;
@@ -2554,28 +2529,26 @@ static int conv_forward_sweep(bdof_ctx* c, int B, bool tape) {
     ConvInitArgs ia{c->probe, cur, obj, B, c->NX, c->NY, conv_carrier(c, 0), cs ? c->cstack : nullptr};
     hipLaunchKernelGGL(k_conv_init, dim3(egrid), dim3(256), 0, c->stream, ia);
     int r;
-    // sub-batches on streams of their own, as on the transfer-function path (batch_groups): the ramp and tail of one group's
+    // sub-batches on streams of their own, as on the transfer-function path (Split): the ramp and tail of one group's
     // launch are filled by the other's; the slices of a group follow each other on its stream, the groups meet again at the
     // detector (the renormalisation reads batch element 0)
-    Group groups[BDOF_MAX_GROUPS];
-    const int ng = batch_groups(c, B, (c->NX / 32) * (c->NY / 32), 2, groups);
-    if ((r = fork_streams(c, ng))) return r;
-    for (int gi = 0; gi < ng; ++gi) {
-        use_group(c, groups[gi]);
-        const size_t off = (size_t)groups[gi].b0 * plane;
-        const ObjView gobj = sub_obj(c);
+    Split split;
+    if ((r = split.open(c, B, (c->NX / 32) * (c->NY / 32), 2))) return r;
+    for (const Group& g : split) {
+        const size_t off = (size_t)g.b0 * plane;
+        const ObjView gobj = sub_obj(c, g);
         cf* gcur = cur;
         for (int z = 0; z < c->S; ++z) {
             const bool last = z == c->S - 1;
             cf* out = last ? c->bufB : (tape ? c->tape + (size_t)(z + 1) * fld : (gcur == c->bufA ? c->bufC : c->bufA));
-            ConvArgs a{gcur + off, out + off, nullptr, nullptr, gobj, groups[gi].B, c->NX, c->NY, last ? -1 : z + 1, cs ? zero : conv_pad(c, z),
+            ConvArgs a{gcur + off, out + off, nullptr, nullptr, gobj, g.B, c->NX, c->NY, last ? -1 : z + 1, cs ? zero : conv_pad(c, z),
                        conv_carrier(c, z + 1), c->k_conv, c->taps_dev + z % c->taps_copies, c->taps.ks,
                        cs && !last ? c->cstack + (size_t)(z + 1) * plane : nullptr};
-            if ((r = launch_conv<false>(c, a))) { use_whole(c); return r; }
+            if ((r = launch_conv<false>(c, g, a))) return r;
             gcur = out;
         }
     }
-    if ((r = join_streams(c, ng))) return r;
+    if ((r = split.close(c))) return r;
     hipLaunchKernelGGL(k_conv_scalars, dim3(1), dim3(64), 0, c->stream, c->bufB, cs ? cfl(c->c_pS) : conv_carrier(c, c->S), c->probe,
                        cs ? cfl(c->c_p0) : conv_carrier(c, 0), c->conv_scal);
     return 0;
@@ -2640,9 +2613,7 @@ int bdof_forward_conv(bdof_ctx* c, int B, const int* angle_of_b, const int* xoff
     int r = conv_check(c, B, angle_of_b);
     if (r) return r;
     if (!out_wave) return BDOF_ERR_ARG;
-    HIPC(c, hipSetDevice(c->device));
-    set_batch_views(c, angle_of_b, xoff, yoff);
-    if ((r = ensure_modulation_k(c, c->k_conv))) return r;
+    if ((r = begin_batch(c, angle_of_b, xoff, yoff, c->k_conv))) return r;
     if ((r = conv_forward_sweep(c, B, false))) return r;
     c->tape_valid = c->last_valid = false;
     const size_t n = (size_t)B * c->NX * c->NY;
@@ -2660,13 +2631,13 @@ int bdof_forward_conv(bdof_ctx* c, int B, const int* angle_of_b, const int* xoff
         det.pfield64 = cs ? c->cdet64 : nullptr;
         const ConvFinalArgs fa = conv_final_args(c, B, c->bufB, c->bufA, false);
         hipLaunchKernelGGL((k_conv_final<0>), dim3(egrid), dim3(256), 0, c->stream, fa);
-        RealToHybArgs ra{c->bufA, c->bufC, B, c->NX, c->twY};
-        DISPATCH_N(c->NY, { hipLaunchKernelGGL((k_row_real_to_hyb<N_>), dim3(rows_grid<N_>(c, B, c->NX)), dim3(BDOF_THREADS), 0, c->stream, ra); });
+        const Group all = whole(c, B);
+        launch_real_to_hyb(c, all, c->bufA, c->bufC);
         if (c->det_mode == BDOF_DET_NEAR) {
-            launch_row_prop(c, B, c->bufC, c->bufA, c->hdet, 1.f, 0);
-            launch_loss_real(c, B, det, c->bufA, nullptr, false, (cf*)out_wave, nullptr, 1.f, 1.f);
+            launch_row_prop(c, all, c->bufC, c->bufA, c->hdet, 1.f, 0, 0);      // the detector step takes copy 0 of the dithered constants
+            launch_loss_real(c, all, det, c->bufA, nullptr, false, (cf*)out_wave, nullptr, 1.f, 1.f);
         } else {
-            launch_loss_far(c, B, det, c->bufC, nullptr, (cf*)out_wave, nullptr, 1.f, 1.f);
+            launch_loss_far(c, all, det, c->bufC, nullptr, (cf*)out_wave, nullptr, 1.f, 1.f);
         }
     }
     return launched(c);
@@ -2686,9 +2657,7 @@ int bdof_loss_grad_conv(bdof_ctx* c, int B, const int* angle_of_b, const int* xo
         return fail(c, BDOF_ERR_STATE, "bdof_set_meas_mode(1) needs a plane-wave carrier and a real-space detector");
     if (!c->with_grad) return fail(c, BDOF_ERR_STATE, "bdof_loss_grad_conv needs bdof_configure(with_grad=1)");
     c->gpsi_src = nullptr;                   // the real-space propagator does not export the probe gradient
-    HIPC(c, hipSetDevice(c->device));
-    set_batch_views(c, angle_of_b, xoff, yoff);
-    if ((r = ensure_modulation_k(c, c->k_conv))) return r;
+    if ((r = begin_batch(c, angle_of_b, xoff, yoff, c->k_conv))) return r;
     if ((r = conv_forward_sweep(c, B, true))) return r;
     c->tape_valid = c->last_valid = false;
     const size_t fld = (size_t)c->Bmax * c->NX * c->NY;
@@ -2701,7 +2670,7 @@ int bdof_loss_grad_conv(bdof_ctx* c, int B, const int* angle_of_b, const int* xo
     // The detector plane of the renormalised wave.  From the ctx (det_plane) it keeps the data term only: meas_dev, meas_ref, mu.
     // Everything about the carrier is this path's own — the transfer-function recurrence behind det_plane's carrier, a_end and
     // dref does not describe this wave — and is set or cleared here by name.
-    DetPlane det = det_plane(c, B, nullptr);
+    DetPlane det = det_plane(c, whole(c, B), B, nullptr);
     det.seed_scale = (float)seed_scale;
     det.gcar = det.gt0 = nullptr;       // the far-field kernel adds no DC carrier here, so there is no adjoint carrier either
     det.a_end = make_double2(0.0, 0.0);
@@ -2748,39 +2717,38 @@ int bdof_loss_grad_conv(bdof_ctx* c, int B, const int* angle_of_b, const int* xo
     } else {
         const ConvFinalArgs fa = conv_final_args(c, B, c->bufB, c->bufA, split);
         hipLaunchKernelGGL((k_conv_final<0>), dim3(egrid), dim3(256), 0, c->stream, fa);
-        RealToHybArgs ra{c->bufA, c->bufC, B, c->NX, c->twY};
-        DISPATCH_N(c->NY, { hipLaunchKernelGGL((k_row_real_to_hyb<N_>), dim3(rows_grid<N_>(c, B, c->NX)), dim3(BDOF_THREADS), 0, c->stream, ra); });
+        const Group all = whole(c, B);
+        launch_real_to_hyb(c, all, c->bufA, c->bufC);
         if (c->det_mode == BDOF_DET_NEAR) {
-            launch_row_prop(c, B, c->bufC, c->bufA, c->hdet, 1.f, 0);                                     // d_hat (L1)
-            npart = launch_loss_real(c, B, det, c->bufA, c->bufC, true, (cf*)out_wave, meas, 1.f, 1.f);
-            launch_row_prop(c, B, c->bufC, c->bufA, c->hdet, 1.f, 1);                                     // g_hat(q) (L1)
+            // the detector step and its adjoint take copy 0 of the dithered constants, whatever ran on the ctx before
+            launch_row_prop(c, all, c->bufC, c->bufA, c->hdet, 1.f, 0, 0);                                  // d_hat (L1)
+            npart = launch_loss_real(c, all, det, c->bufA, c->bufC, true, (cf*)out_wave, meas, 1.f, 1.f);
+            launch_row_prop(c, all, c->bufC, c->bufA, c->hdet, 1.f, 1, 0);                                  // g_hat(q) (L1)
         } else {
-            npart = launch_loss_far(c, B, det, c->bufC, c->bufA, (cf*)out_wave, meas, 1.f, 1.f);          // g_hat(q) (L1)
+            npart = launch_loss_far(c, all, det, c->bufC, c->bufA, (cf*)out_wave, meas, 1.f, 1.f);        // g_hat(q) (L1)
         }
-        launch_loss_real(c, B, DetPlane{}, c->bufA, nullptr, false, c->bufC, nullptr, 1.f, 1.f);          // G(q), real space
+        launch_loss_real(c, all, DetPlane{}, c->bufA, nullptr, false, c->bufC, nullptr, 1.f, 1.f);        // G(q), real space
         hipLaunchKernelGGL(k_conv_scale_seed, dim3(egrid), dim3(256), 0, c->stream, c->bufC, c->conv_scal, n);
         gp = c->bufC;
     }
     hipLaunchKernelGGL(k_conv_finish, dim3(1), dim3(256), 0, c->stream, c->partial, npart, 2, 1.0 / ((double)B * c->NX * c->NY),
                        seed_scale, c->loss_dev, gp, c->conv_scal);
     // backward sweep, in the same sub-batches
-    Group groups[BDOF_MAX_GROUPS];
-    const int ng = batch_groups(c, B, (c->NX / 32) * (c->NY / 32), 2, groups);
-    if ((r = fork_streams(c, ng))) return r;
-    for (int gi = 0; gi < ng; ++gi) {
-        use_group(c, groups[gi]);
-        const size_t off = (size_t)groups[gi].b0 * plane;
-        const ObjView gobj = sub_obj(c);
+    Split groups;
+    if ((r = groups.open(c, B, (c->NX / 32) * (c->NY / 32), 2))) return r;
+    for (const Group& g : groups) {
+        const size_t off = (size_t)g.b0 * plane;
+        const ObjView gobj = sub_obj(c, g);
         cf* gcur = gp;
         for (int z = c->S - 1; z >= 0; --z) {
             cf* gout = gcur == c->bufB ? c->bufA : c->bufB;
-            ConvArgs a{gcur + off, gout + off, c->tape + (size_t)z * fld + off, c->grot + (size_t)groups[gi].b0 * c->S * plane, gobj, groups[gi].B, c->NX, c->NY, z,
+            ConvArgs a{gcur + off, gout + off, c->tape + (size_t)z * fld + off, c->grot + (size_t)g.b0 * c->S * plane, gobj, g.B, c->NX, c->NY, z,
                        zero, conv_carrier(c, z), c->k_conv, c->taps_dev + z % c->taps_copies, c->taps.ks, cs ? c->cstack + (size_t)z * plane : nullptr};
-            if ((r = launch_conv<true>(c, a))) { use_whole(c); return r; }
+            if ((r = launch_conv<true>(c, g, a))) return r;
             gcur = gout;
         }
     }
-    if ((r = join_streams(c, ng))) return r;
+    if ((r = groups.close(c))) return r;
     return launched(c);
 }
 
@@ -2847,7 +2815,7 @@ int bdof_rotation_adjoint_rows(bdof_ctx* c, int B, const int* angle_of_b, void* 
     if (row0 < 0 || n_rows < 0 || (long long)row0 + n_rows > c->adj_ndest) return fail(c, BDOF_ERR_ARG, "destination rows outside the volume");
     if (n_rows == 0) return 0;
     HIPC(c, hipSetDevice(c->device));
-    ProfScope ps(c, BDOF_K_ROT_ADJ);
+    ProfScope ps(c, BDOF_K_ROT_ADJ, c->stream);
     RotAdjK<false> a;
     static_cast<RotAdjArgs&>(a) = RotAdjArgs{c->grot, (float2*)gvol, c->adj_off, c->adj_order, angle_of_b, B, c->S * c->NX, c->adj_ndest, c->NY,
                                              accumulate, scale, c->heavy, c->heavy + 1, row0, row0 + n_rows};
@@ -2873,7 +2841,7 @@ int bdof_window_rotation_adjoint(bdof_ctx* c, int B, int angle, const int* xoff,
     if (angle < 0 || angle >= c->n_angles) return fail(c, BDOF_ERR_ARG, "angle index outside the rotation tables");
     HIPC(c, hipSetDevice(c->device));
     if (c->obj.volNY % 2) return fail(c, BDOF_ERR_SIZE, "the rotation adjoint needs an even volume NY");
-    ProfScope ps(c, BDOF_K_ROT_ADJ);
+    ProfScope ps(c, BDOF_K_ROT_ADJ, c->stream);
     const int n_src = c->S * c->obj.volNX;
     WinAdjArgs a{c->grot, (float2*)gvol, c->adj_off + (size_t)angle * (c->adj_ndest + 1), c->adj_order + (size_t)angle * n_src,
                  xoff, yoff, B, c->S, c->NX, c->NY, c->obj.volNX, c->obj.volNY, c->adj_ndest, accumulate, scale};
@@ -2927,7 +2895,7 @@ int bdof_adam_step_slab(bdof_ctx* c, const void* x_old, void* x_new, const void*
     if (x0 < 0 || nx < 0 || (long long)x0 + nx > NXv) return fail(c, BDOF_ERR_ARG, "slab outside the volume");
     if (nx == 0) return 0;
     HIPC(c, hipSetDevice(c->device));
-    ProfScope ps(c, BDOF_K_ADAM);
+    ProfScope ps(c, BDOF_K_ADAM, c->stream);
     const AdamArgs a = adam_args(x_old, x_new, g, m, v, mask, NXv, NZv, NYv, g_scale, alpha_d, alpha_b, gamma, lr, b1, b2, eps, i_batch, clip,
                                  x0, nx);
     const size_t n = (size_t)nx * NZv * NYv;
@@ -2979,7 +2947,7 @@ int bdof_rotation_adjoint_adam(bdof_ctx* c, int B, const int* angle_of_b, void* 
     c->mod_dirty = true;
     c->mod_mean_pending = false;
     c->mod_for = nullptr;
-    ProfScope ps(c, BDOF_K_ROT_ADJ);
+    ProfScope ps(c, BDOF_K_ROT_ADJ, c->stream);
     RotAdjK<true> a;
     static_cast<RotAdjArgs&>(a) = RotAdjArgs{c->grot, (float2*)gvol, c->adj_off, c->adj_order, angle_of_b, B, c->S * c->NX, c->adj_ndest, c->NY,
                                              0, scale, c->heavy, c->heavy + 1, 0, c->adj_ndest};
@@ -3055,7 +3023,7 @@ int bdof_rotate_bilinear_adjoint(bdof_ctx* c, const void* grot, int NXv, int NZv
     if (row0 < 0 || n_rows < 0 || (long long)row0 + n_rows > (long long)NXv * NZv) return fail(c, BDOF_ERR_ARG, "destination rows outside the volume");
     if (n_rows == 0) return 0;
     HIPC(c, hipSetDevice(c->device));
-    ProfScope ps(c, BDOF_K_ROT_ADJ);
+    ProfScope ps(c, BDOF_K_ROT_ADJ, c->stream);
     RotBilinArgs a{nullptr, (float2*)grot, (float2*)gvol, (const double4*)prm, B, NXv, NZv, NYv, row0, row0 + n_rows, accumulate, scale};
     const int grid = std::min((n_rows + 3) / 4, c->ncu * 16);
     const int nv4 = (NYv / 2 + 63) / 64;

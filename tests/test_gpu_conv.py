@@ -321,3 +321,31 @@ def test_second_tiling_equals_the_first(engine_mod, monkeypatch, ks, probe, shap
     # sub-batches on two streams: the same kernels on the same fields — the same bits
     for a, b in zip(out['2'], out['2s']):
         assert np.array_equal(a, b)
+
+
+def test_conv_results_do_not_depend_on_earlier_calls(engine_mod):
+    """The near-field detector step of bdof_loss_grad_conv (one transfer-function launch and its adjoint) takes copy 0 of the
+    dithered twiddles and of sqrt(1/2), whatever ran on the context before: loss_grad(conv=True) on a fresh context, and on a
+    second one that first ran the transfer-function forward(conv=False) over the same object (S = 4 slices: its last launch took
+    copy 3), give the same bits.  64 x 64, S = 4, B = 2, ks = 5, detector at 1e-4 cm."""
+    rng = np.random.default_rng(41)
+    B, n, S, ks = 2, 64, 4, 5
+    delta = rng.uniform(0, 2e-5, size=(B, n, n, S))
+    beta = 0.1 * delta
+    meas = np.abs(1 + 0.05 * rng.normal(size=(B, n, n)))
+    res = []
+    for tf_first in (False, True):
+        eng = engine_mod.MultisliceEngine(n, n, S, B, with_grad=True, engine='streaming')
+        eng.set_physics(5000., 1e-7, 1e-4)
+        eng.set_conv(5000., [1e-7] * 3, ks)
+        eng.set_probe(np.ones((n, n)), np.zeros((n, n)))
+        eng.set_object_batch(delta, beta)
+        if tf_first:
+            eng.forward(B, conv=False)
+        loss = eng.loss_grad(B, meas, conv=True)
+        res.append((loss,) + tuple(eng.grad_batch_to_host(B)))
+    print('conv after a transfer-function call: loss', res[0][0], res[1][0], ' gradient values that differ',
+          int(np.sum(res[0][1] != res[1][1]) + np.sum(res[0][2] != res[1][2])))
+    assert np.isfinite(res[0][0]) and res[0][0] > 0 and np.abs(res[0][1]).max() > 0
+    assert res[0][0] == res[1][0]
+    assert np.array_equal(res[0][1], res[1][1]) and np.array_equal(res[0][2], res[1][2])
