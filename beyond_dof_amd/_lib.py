@@ -110,6 +110,8 @@ _SIGNATURES = {
     'bdof_batch_groups': (ctypes.c_int, [_vp, ctypes.c_int]),
     'bdof_set_sweep_fusion': (ctypes.c_int, [_vp, ctypes.c_int]),
     'bdof_sweep_fused': (ctypes.c_int, [_vp]),
+    'bdof_set_adjoint_fusion': (ctypes.c_int, [_vp, ctypes.c_int]),
+    'bdof_adjoint_fused': (ctypes.c_int, [_vp]),
     'bdof_profile_enable': (ctypes.c_int, [_vp, ctypes.c_int]),
     'bdof_profile_read': (ctypes.c_int, [_vp, ctypes.c_int, _c_int_p, ctypes.POINTER(ctypes.c_double)]),
     'bdof_malloc': (ctypes.c_int, [ctypes.POINTER(_vp), ctypes.c_size_t]),

@@ -135,6 +135,8 @@ struct bdof_ctx : Workspace {
     int n_streams = -1;                          // -1 auto (1 or 2), else the number of groups to split a batch in
     int fusion = 0;                              // bdof_set_sweep_fusion: 0 never (a new ctx), 1 the forward sweep where the configuration is eligible
     int fused_last = 0;                          // what the last bdof_loss_grad ran (bdof_sweep_fused)
+    int adj_fusion = 0;                          // bdof_set_adjoint_fusion: the fused adjoint sweep wherever the fused forward sweep runs
+    int adj_fused_last = 0;                      // what the last bdof_loss_grad ran (bdof_adjoint_fused)
     int ncu = 256;
     int NY = 0, NX = 0, S = 0, Bmax = 0;
     bool with_grad = false;
@@ -599,7 +601,8 @@ static int fused_mode(const bdof_ctx* c) {
 }
 // Slice z of the fused forward sweep: even z on y-lines ([b][x][y] -> [b][y][x]), odd z on x-lines (back); phi_z goes to `phi`.
 // The leading step takes copy z-1 of every dithered constant, the trailing one copy z.
-static void launch_slice(bdof_ctx* c, const Group& g, int z, const cf* in, cf* out, cf* phi) {
+// blk (the fused adjoint sweep will read the tape): an odd slot takes the tile-block layout of k_slice_x<BLK>.
+static void launch_slice(bdof_ctx* c, const Group& g, int z, const cf* in, cf* out, cf* phi, bool blk = false) {
     ProfScope ps(c, BDOF_K_ROW_FWD, g.st, true);
     const bool xl = (z & 1) != 0;
     const int N = xl ? c->NX : c->NY, R = xl ? c->NY : c->NX;
@@ -611,10 +614,35 @@ static void launch_slice(bdof_ctx* c, const Group& g, int z, const cf* in, cf* o
     sq_of(c, lead, a.sq_lead);
     sq_of(c, trail, a.sq_trail);
     if (xl) {
-        DISPATCH_N_512(N, BDOF_LAUNCH(ps, (k_slice_x<N_>), dim3(rows_grid<N_>(c, g.B, R)), dim3(BDOF_THREADS), 0, g.st, a));
+        DISPATCH_N_512(N, with_bool(blk, [&](auto BLK) {
+            BDOF_LAUNCH(ps, (k_slice_x<N_, BLK>), dim3(rows_grid<N_>(c, g.B, R)), dim3(BDOF_THREADS), 0, g.st, a);
+        }));
     } else {
         DISPATCH_N_512(N, with_bool(z == 0, [&](auto FIRST) { with_bool(z == c->S - 2, [&](auto TAIL) {
             BDOF_LAUNCH(ps, (k_slice_y<N_, FIRST, TAIL>), dim3(rows_grid<N_>(c, g.B, R)), dim3(BDOF_THREADS), 0, g.st, a);
+        }); }));
+    }
+}
+
+// Slice z <= S-2 of the fused adjoint sweep (k_slice_y_adj / k_slice_x_adj): even z on y-lines ([b][x][y] -> [b][y][x]; at S-2 from
+// g_hat in L1 order), odd z on x-lines (back), phi_z from `phi` (odd z: the blocked slot).  The leading step takes copy z of every
+// dithered constant, the trailing one copy z-1: the transposes of the steps launch_slice applied.
+static void launch_slice_adj(bdof_ctx* c, const Group& g, int z, const cf* in, cf* out, const cf* phi) {
+    ProfScope ps(c, BDOF_K_ROW_BWD, g.st, true);
+    const bool xl = (z & 1) != 0;
+    const int N = xl ? c->NX : c->NY, R = xl ? c->NY : c->NX;
+    const cf* tw = xl ? c->twX : c->twY;
+    const cf* h = xl ? c->hx_d : c->hy_d;
+    const unsigned lead = (unsigned)z, trail = (unsigned)(z > 0 ? z - 1 : 0), D = (unsigned)c->sep_copies;
+    SliceAdjArgs a{sub_field(c, g, in), sub_field(c, g, phi), sub_field(c, g, out), c->grot + (size_t)g.b0 * c->S * c->NX * c->NY, sub_obj(c, g), g.B, R, z,
+                   c->k, carrier_phi_at(c, z), tw_of(c, tw, N, lead), tw_of(c, tw, N, trail), h + (size_t)(lead % D) * N, h + (size_t)(trail % D) * N};
+    sq_of(c, lead, a.sq_lead);
+    sq_of(c, trail, a.sq_trail);
+    if (xl) {
+        DISPATCH_N_512(N, BDOF_LAUNCH(ps, (k_slice_x_adj<N_>), dim3(rows_grid<N_>(c, g.B, R)), dim3(BDOF_THREADS), 0, g.st, a));
+    } else {
+        DISPATCH_N_512(N, with_bool(z == c->S - 2, [&](auto HEAD) { with_bool(z == 0, [&](auto LAST) {
+            BDOF_LAUNCH(ps, (k_slice_y_adj<N_, HEAD, LAST>), dim3(rows_grid<N_>(c, g.B, R)), dim3(BDOF_THREADS), 0, g.st, a);
         }); }));
     }
 }
@@ -723,7 +751,8 @@ enum { TAPE_NONE = 0, TAPE_HISTORY = 1, TAPE_LAST = 2 };
 // fused (fused_mode; TAPE_HISTORY only): slices 0 .. S-2 run as one k_slice_y / k_slice_x launch each, ping-ponging bufA / bufB in
 // real space; tape slot z holds the scattered part of phi_z (z <= S-2) and slot S-1 psi_hat_{S-1}, which one k_row_prop launch with
 // the hx-only table makes of the ky-domain lines k_slice_y<TAIL> left in bufA.  The last slice and the detector run as always.
-static void forward_sweep(bdof_ctx* c, const Split& split, int tape_mode, bool fused = false) {
+// adj_fused: the fused adjoint sweep follows — the odd slots take k_slice_x<BLK>'s tile blocks, which only k_slice_x_adj reads.
+static void forward_sweep(bdof_ctx* c, const Split& split, int tape_mode, bool fused = false, bool adj_fused = false) {
     const size_t fld = (size_t)c->Bmax * c->NX * c->NY;
     const DetRoute dr = det_route(c);
     const int nz = n_steps(c);
@@ -734,7 +763,7 @@ static void forward_sweep(bdof_ctx* c, const Split& split, int tape_mode, bool f
         if (fused && last) in = c->tape + (size_t)z * fld;
         if (fused && !last) {
             for (const Group& g : split) {
-                launch_slice(c, g, z, (z & 1) ? c->bufA : c->bufB, (z & 1) ? c->bufB : c->bufA, c->tape + (size_t)z * fld);
+                launch_slice(c, g, z, (z & 1) ? c->bufA : c->bufB, (z & 1) ? c->bufB : c->bufA, c->tape + (size_t)z * fld, adj_fused);
                 if (z == nz - 2) launch_row_prop(c, g, c->bufA, c->tape + (size_t)(nz - 1) * fld, c->hx_rows, 1.f, 0, z, BDOF_K_LOSS);
             }
             continue;
@@ -772,10 +801,12 @@ static void march_back(bdof_ctx* c, const Group& g, int z, int hist, const cf* p
 //   history  : A'_z recomputes phi_z from psi_hat_z, which the transfer-function kernel writes anyway (one more transform per
 //              launch, no tape write in A_z: 104 instead of 112 B per pixel per slice-step, 67.6 -> 65.3 ms per step at 512^3 x 25)
 //   fused    : the tape holds phi_z itself (HIST 0) below the last slice, whose psi_hat sits in slot S-1
+//   adj_fused: below the top slice (A'_{S-1} and its adjoint step, as above) one launch_slice_adj per slice, ping-ponging bufB / bufA
+//              in real space as the forward sweep does: 1 + 1 + (S - 1) launches where the other forms take 2 S - 1
 //   tape-free: one A_z^-1 launch and one more adjoint transfer-function launch per slice (+40 B per pixel per slice-step), S - 3
 //              fields per wavefield less memory.  phi_{S-1} is kept by the forward sweep (real space, tape slot 0); slots 1 / 2
 //              hold the marched-back wave in L1 / L2 order; slice 0 takes phi_0 from the probe as the history form does.
-static void adjoint_sweep(bdof_ctx* c, const Split& split, bool fused) {
+static void adjoint_sweep(bdof_ctx* c, const Split& split, bool fused, bool adj_fused = false) {
     const size_t fld = (size_t)c->Bmax * c->NX * c->NY;
     const int nz = n_steps(c);
     for (int z = nz - 1; z >= 0; --z) {
@@ -783,6 +814,10 @@ static void adjoint_sweep(bdof_ctx* c, const Split& split, bool fused) {
         for (const Group& g : split) {
             if (c->recompute) {
                 march_back(c, g, z, z == 0 ? 2 : top ? 0 : 3, top ? c->tape : c->tape + fld, top, z > 0, z > 1, c->tape + fld, c->tape + 2 * fld);
+                continue;
+            }
+            if (adj_fused && !top) {
+                launch_slice_adj(c, g, z, (z & 1) ? c->bufA : c->bufB, (z & 1) ? c->bufB : c->bufA, c->tape + (size_t)z * fld);
                 continue;
             }
             if (fused) launch_row_bwd(c, g, z, c->bufB, c->tape + (size_t)z * fld, z > 0 ? c->bufA : nullptr, top ? 1 : 0);
@@ -2356,7 +2391,7 @@ int bdof_loss_grad(bdof_ctx* c, int B, const int* angle_of_b, const int* xoff, c
     if ((r = begin_batch(c, angle_of_b, xoff, yoff, c->k_fft))) return r;
     c->gpsi_src = c->gpsi0;
     c->gpsi_B = B;
-    c->fused_last = 0;
+    c->fused_last = c->adj_fused_last = 0;
     if (use_resident(c, B)) {
         if ((r = resident_run(c, B, meas, out_wave, true))) return r;
         c->tape_valid = c->last_valid = false;
@@ -2371,8 +2406,10 @@ int bdof_loss_grad(bdof_ctx* c, int B, const int* angle_of_b, const int* xoff, c
     Split split;
     if ((r = split.open(c, B, c->NX, 16))) return r;
     const bool fused = fused_mode(c) != 0;
+    const bool adj_fused = fused && c->adj_fusion != 0;
     c->fused_last = fused ? 1 : 0;
-    forward_sweep(c, split, c->recompute ? TAPE_LAST : TAPE_HISTORY, fused);
+    c->adj_fused_last = adj_fused ? 1 : 0;
+    forward_sweep(c, split, c->recompute ? TAPE_LAST : TAPE_HISTORY, fused, adj_fused);
     c->tape_valid = false;      // the tape holds an incomplete history (or phi_{S-1} alone), not what bdof_tape_to_real expects
     c->last_valid = false;
     int npart = 0;
@@ -2390,7 +2427,7 @@ int bdof_loss_grad(bdof_ctx* c, int B, const int* angle_of_b, const int* xoff, c
             launch_row_prop(c, g, c->bufA, c->bufB, dr.h, 1.f, 1, n_steps(c) - 1, fused ? BDOF_K_LOSS : BDOF_K_COL_PROP);
         }
     }
-    adjoint_sweep(c, split, fused);
+    adjoint_sweep(c, split, fused, adj_fused);
     if ((r = split.close(c))) return r;
     hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, c->stream, c->partial, npart,
                        1.0 / ((double)B * c->NX * c->NY), c->loss_dev);
@@ -3086,6 +3123,14 @@ int bdof_set_sweep_fusion(bdof_ctx* c, int mode) {
     return 0;
 }
 int bdof_sweep_fused(bdof_ctx* c) { return c ? c->fused_last : 0; }
+
+int bdof_set_adjoint_fusion(bdof_ctx* c, int on) {
+    if (!c) return BDOF_ERR_ARG;
+    if (on < 0 || on > 1) return fail(c, BDOF_ERR_ARG, "bdof_set_adjoint_fusion: on must be 0 or 1");
+    c->adj_fusion = on;
+    return 0;
+}
+int bdof_adjoint_fused(bdof_ctx* c) { return c ? c->adj_fused_last : 0; }
 
 int bdof_set_streams(bdof_ctx* c, int n) {
     if (!c) return -1;

@@ -13,6 +13,7 @@
 // The fused forward sweep of bdof_loss_grad (k_slice_y / k_slice_x, below A') replaces A + B by one kernel per slice that works
 // on lines of one direction, through the separable Fresnel step; between its kernels the field is in real space, [b][x][y] or
 // [b][y][x], and the tape holds phi_z:                                                                              32 B/px
+// The fused adjoint sweep (k_slice_y_adj / k_slice_x_adj, below them) replaces A' + B' the same way:                40 B/px
 #pragma once
 #include "bdof_fft.h"
 
@@ -988,7 +989,10 @@ __global__ __launch_bounds__(BDOF_THREADS, RowCfg<NY>::MIN_WAVES) void k_slice_y
     }
 }
 
-template <int NX>
+// BLK: phi_z goes to the tape in tile blocks, [b][NY / TILE][NX][TILE] (TILE = RowCfg<NX>::TILE rows along y): the transposed
+// mapping's stores are then contiguous over the workgroup (one wave instruction covers 512 bytes, a tile's phi is one block of
+// NX TILE entries) instead of 128-byte segments at a stride of one y-row.  Only k_slice_x_adj reads such a slot.
+template <int NX, bool BLK = false>
 __global__ __launch_bounds__(BDOF_THREADS, RowCfg<NX>::MIN_WAVES) void k_slice_x(SliceArgs a) {
     typedef RowCfg<NX> C;
     typedef FftPlan<NX> P;
@@ -1009,7 +1013,7 @@ __global__ __launch_bounds__(BDOF_THREADS, RowCfg<NX>::MIN_WAVES) void k_slice_x
         const int row0 = tile * C::TILE;
         const int b = row0 / NY, y0 = row0 - b * NY;
         const ObjRows rows = obj_rows_of(o, b, a.z, NX);
-        cf* const pdst = a.phi_out + (size_t)b * NX * NY;
+        cf* const pdst = a.phi_out + (BLK ? (size_t)row0 * NX : (size_t)b * NX * NY);      // BLK: the tile's block (row0 = b NY + y0)
         // The rotation lookup of the tile, one x per thread, on its way while the first phase runs; it goes through LDS to the
         // transposed phase, which would otherwise wait for it and THEN for the table rows it points to (two round trips in a row)
         const int src_mine = (int)threadIdx.x < NX ? obj_rows_rel(rows, threadIdx.x) : -1;
@@ -1055,7 +1059,8 @@ __global__ __launch_bounds__(BDOF_THREADS, RowCfg<NX>::MIN_WAVES) void k_slice_x
 #pragma unroll
             for (int m = 0; m < 8; ++m) {
                 v[pass][m] = modulate_eps_s(v[pass][m], a.carrier, db[m], a.cshift);
-                pdst[(unsigned)((j + m * C::T) * NY + yg)] = v[pass][m];      // (32-bit offsets inside one wavefield)
+                if constexpr (BLK) pdst[(unsigned)(q + m * C::T * C::TILE)] = v[pass][m];      // (x TILE + r, x = j + m T: q = j TILE + r)
+                else pdst[(unsigned)((j + m * C::T) * NY + yg)] = v[pass][m];      // (32-bit offsets inside one wavefield)
             }
             tw.sq = sqt;                                  // (the first stage takes no twiddles, only the step's sqrt(1/2))
             stage_compute<NX, -1, P::R0, 1, 0, 1, false>(v[pass], tw, j);
@@ -1081,6 +1086,215 @@ __global__ __launch_bounds__(BDOF_THREADS, RowCfg<NX>::MIN_WAVES) void k_slice_x
             line_fft_rest<NX, -1, 1, false>(u, tw, tid, lds);
 #pragma unroll
             for (int m = 0; m < 8; ++m) u[m] = cmul(u[m], hv[m]);
+            line_fft_partial<NX, +1, 2, false>(u, tw, tid, lds);
+        }
+        __syncthreads();
+        transposed_tail<NX, +1, 2, false>(smem, a.out + (size_t)b * NX * NY + y0, NY, 1.f, smem_tail[1], sqt);
+        __syncthreads();
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// Fused slice kernels of the adjoint sweep (bdof_set_adjoint_fusion): the transposed chain, regrouped the same way.  Px^H and Py^H
+// commute, P_z^H = Px_z^H Py_z^H with Px^H = Fx^-1 conj(hx) Fx, so a kernel again works on lines of one direction:
+//        ... | Py_{z-1}^H conj(c_z) Py_z^H | Px_z^H conj(c_{z+1}) Px_{z+1}^H | ...        (read right to left)
+// Between the kernels the adjoint field is in real space, [b][x][y] in front of a y-line kernel and [b][y][x] in front of an x-line one.
+//   k_slice_y_adj (even z): rows of [b][x][y]; k_row_bwd<HIST 0>'s body between two steps: Py_z^H (leading, copy z of every
+//       dithered constant, hy conjugated as k_row_prop conjugates h), phi_z from the tape, t = G conj(phi), the gradient row
+//       (k Im t, -k Re t), G <- conj(c) G, Py_{z-1}^H (trailing, copy z-1) with the transposed tail -> [b][y][x].
+//       HEAD (z = S-2): the input is g_hat in L1 order [b][x][ky], what the unfused top of the sweep leaves (k_row_bwd<HIST 1> at
+//       S-1, then k_row_prop with the conjugated 2-D table of copy S-2): the leading step is the inverse transform along y alone.
+//       LAST (z = 0): no trailing step, no output.
+//   k_slice_x_adj (odd z): rows of [b][y][x]; k_slice_x's structure — Px_z^H up to its last stage in the row mapping, the last
+//       stage in the transposed mapping, where phi_z (a blocked tape slot, k_slice_x<BLK>: contiguous) and the table entries
+//       are loaded and the gradient values go to grot as 128-byte segments along y, G <- conj(c) G, the first stage of Px_{z-1}^H
+//       on the same registers, its rest in the row mapping, transposed tail -> [b][x][y].
+// 40 B per pixel (8 in + 8 phi + 8 table + 8 gradient + 8 out) where A' + B' move 56.
+// ---------------------------------------------------------------------------------------------
+struct SliceAdjArgs {
+    const cf* in;        // k_slice_y_adj: [B][NX][NY] (HEAD: L1 [B][NX][ky]); k_slice_x_adj: [B][NY][NX]
+    const cf* phi;       // tape slot z: scattered part of phi_z; k_slice_y_adj [B][NX][NY], k_slice_x_adj [B][NY / TILE][NX][TILE]
+    cf* out;             // k_slice_y_adj: [B][NY][NX] (LAST: unused); k_slice_x_adj: [B][NX][NY]
+    float2* grot;        // [B][obj.S][NX][NY]: the gradient rows of slice z go to grot[b][z]
+    ObjView obj;
+    int B, R, z;         // R: lines per wavefield (k_slice_y_adj: NX, k_slice_x_adj: NY)
+    float k;
+    cf carrier_phi;      // cbar a_z: constant part of phi_z
+    const cf* tw_lead;   // twiddle table of the line length, copy of step z ...
+    const cf* tw_trail;  // ... and of step z-1
+    const cf* h_lead;    // hx (k_slice_x_adj) or hy (k_slice_y_adj) of step z (conjugated in the kernel) ...
+    const cf* h_trail;   // ... and of step z-1
+    float sq_lead[2], sq_trail[2];
+};
+
+template <int NY, bool HEAD, bool LAST>
+__global__ __launch_bounds__(BDOF_THREADS, RowCfg<NY>::MIN_WAVES) void k_slice_y_adj(SliceAdjArgs a) {
+    typedef RowCfg<NY> C;
+    __shared__ cf smem[C::LDS_CF];
+    __shared__ cf smem_tw[2][FftTw<NY>::LDS_CNT];
+    __shared__ cf smem_tail[2][7 * C::T];
+    const int tid = threadIdx.x % C::T, rl = threadIdx.x / C::T;
+    const float sql[2] = {a.sq_lead[0], a.sq_lead[1]}, sqt[2] = {a.sq_trail[0], a.sq_trail[1]};     // copies: no pointer into the argument block
+    FftTw<NY> tw;
+    tw_fill<NY>(a.tw_lead, smem_tw[0], smem_tail[0]);
+    if constexpr (!LAST) tw_fill<NY>(a.tw_trail, smem_tw[1], smem_tail[1]);
+    __syncthreads();
+    const int NX = a.R;
+    const int ntiles = a.B * NX / C::TILE;
+    for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        const int row0 = tile * C::TILE;
+        const int b = row0 / NX, x0 = row0 - b * NX;
+#pragma nounroll
+        for (int pass = 0; pass < C::PASSES; ++pass) {
+            const int r = pass * C::RPP + rl;
+            const int x = x0 + r;
+            RowLds<C::T> lds{smem + r * C::RS};
+            const size_t off = (size_t)(row0 + r) * NY;
+            cf g[8], p[8], hv[8];
+            float2 db[8];
+#pragma unroll
+            for (int m = 0; m < 8; ++m) g[m] = a.in[off + tid + m * C::T];
+            if constexpr (!HEAD) {
+#pragma unroll
+                for (int m = 0; m < 8; ++m) hv[m] = a.h_lead[tid + m * C::T];
+            }
+            // phi_z and the table row are asked for once hv is done with, and arrive under the inverse transform: all four rows in
+            // flight at once spilled (12 .. 76 bytes of scratch in the plain instances)
+            auto load_phi_and_table = [&]() {
+#pragma unroll
+                for (int m = 0; m < 8; ++m) p[m] = a.phi[off + tid + m * C::T];
+                load_obj_row(a.obj, obj_src_row(a.obj, b, x, a.z, NX), 0, tid, C::T, db);
+            };
+            tw_select(tw, smem_tw[0], smem_tail[0], sql, tid);
+            if constexpr (HEAD) {                         // g_hat -> G(phi_z): the inverse transform of Py_z^H, the rest was done in the ky domain
+                load_phi_and_table();
+                line_fft<NY, +1, 1, false>(g, tw, tid, lds);
+            } else {                                      // Py_z^H
+                line_fft<NY, -1, 1, false>(g, tw, tid, lds);
+#pragma unroll
+                for (int m = 0; m < 8; ++m) g[m] = cmulc(g[m], hv[m]);
+                load_phi_and_table();
+                line_fft<NY, +1, 2, false>(g, tw, tid, lds);
+            }
+            float2* gdst = a.grot + (((size_t)b * a.obj.S + a.z) * NX + x) * NY;
+#pragma unroll
+            for (int m = 0; m < 8; ++m) {
+                const cf t = cmulc(g[m], cadd(p[m], a.carrier_phi));                // G * conj(phi)
+                gdst[tid + m * C::T] = make_float2(a.k * t.y, -a.k * t.x);
+                g[m] = cmulc(g[m], make_float2(1.f + db[m].x, db[m].y));            // conj(c) G,  c = 1 + (c - 1)
+            }
+            if constexpr (!LAST) {                        // Py_{z-1}^H
+#pragma unroll
+                for (int m = 0; m < 8; ++m) hv[m] = a.h_trail[tid + m * C::T];
+                tw_select(tw, smem_tw[1], smem_tail[1], sqt, tid);
+                line_fft<NY, -1, 1, false>(g, tw, tid, lds);
+#pragma unroll
+                for (int m = 0; m < 8; ++m) g[m] = cmulc(g[m], hv[m]);
+                line_fft_partial<NY, +1, 2, false>(g, tw, tid, lds);
+            }
+        }
+        if constexpr (!LAST) {
+            __syncthreads();
+            transposed_tail<NY, +1, 2, false>(smem, a.out + (size_t)b * NY * NX + x0, NX, 1.f, smem_tail[1], sqt);
+            __syncthreads();
+        }
+    }
+}
+
+template <int NX>
+__global__ __launch_bounds__(BDOF_THREADS, RowCfg<NX>::MIN_WAVES) void k_slice_x_adj(SliceAdjArgs a) {
+    typedef RowCfg<NX> C;
+    typedef FftPlan<NX> P;
+    __shared__ cf smem[C::LDS_CF];
+    __shared__ cf smem_tw[2][FftTw<NX>::LDS_CNT];
+    __shared__ cf smem_tail[2][7 * C::T];
+    const int tid = threadIdx.x % C::T, rl = threadIdx.x / C::T;
+    const float sql[2] = {a.sq_lead[0], a.sq_lead[1]}, sqt[2] = {a.sq_trail[0], a.sq_trail[1]};
+    __shared__ int s_src[NX];                             // source row of every x of the tile's wavefield at this slice (less plain0)
+    FftTw<NX> tw;
+    tw_fill<NX>(a.tw_lead, smem_tw[0], smem_tail[0]);
+    tw_fill<NX>(a.tw_trail, smem_tw[1], smem_tail[1]);
+    __syncthreads();
+    const ObjView o = a.obj;                              // by value (load_obj_row_bin)
+    const int NY = a.R;
+    const int ntiles = a.B * NY / C::TILE;
+    for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        const int row0 = tile * C::TILE;
+        const int b = row0 / NY, y0 = row0 - b * NY;
+        const ObjRows rows = obj_rows_of(o, b, a.z, NX);
+        const cf* const psrc = a.phi + (size_t)row0 * NX;                              // the tile's block of the tape slot (k_slice_x<BLK>)
+        float2* const gdst = a.grot + ((size_t)b * o.S + a.z) * NX * NY;
+        const int src_mine = (int)threadIdx.x < NX ? obj_rows_rel(rows, threadIdx.x) : -1;       // (k_slice_x: on its way during the first phase)
+        // Px_z^H up to its last stage, row mapping
+#pragma nounroll
+        for (int pass = 0; pass < C::PASSES; ++pass) {
+            const int r = pass * C::RPP + rl;
+            RowLds<C::T> lds{smem + r * C::RS};
+            cf u[8], hv[8];
+            const cf* src = a.in + (size_t)(row0 + r) * NX;
+#pragma unroll
+            for (int m = 0; m < 8; ++m) u[m] = src[tid + m * C::T];
+#pragma unroll
+            for (int m = 0; m < 8; ++m) hv[m] = a.h_lead[tid + m * C::T];
+            tw_select(tw, smem_tw[0], smem_tail[0], sql, tid);
+            line_fft<NX, -1, 1, false>(u, tw, tid, lds);
+#pragma unroll
+            for (int m = 0; m < 8; ++m) u[m] = cmulc(u[m], hv[m]);
+            line_fft_partial<NX, +1, 2, false>(u, tw, tid, lds);
+        }
+        if ((int)threadIdx.x < NX) s_src[threadIdx.x] = src_mine;
+        __syncthreads();
+        // Transposed mapping: last stage of Fx^-1, gradient values, conj(c), first stage of the next Fx.  As in k_slice_x every read
+        // of the tile's row images is done, with a workgroup barrier, before any write — the PASSES x 8 values wait in registers.
+        cf v[C::PASSES][8];
+#pragma unroll
+        for (int pass = 0; pass < C::PASSES; ++pass) {
+            const int q = threadIdx.x + pass * BDOF_THREADS;
+            const int r = q % C::TILE, j = q / C::TILE;
+            RowLds<C::T> lds{smem + r * C::RS};
+            const int yg = y0 + r, yc = min(max(yg, 0), o.volNY - 1);
+            float2 db[8];
+            cf p[8];
+#pragma unroll
+            for (int m = 0; m < 8; ++m) {
+                const int srel = s_src[j + m * C::T];
+                const float2 t = o.vol[(size_t)(rows.plain0 + max(srel, 0)) * o.volNY + yc];
+                const bool in = srel >= 0 && yg == yc;
+                db[m] = make_float2(in ? t.x : 0.f, in ? t.y : 0.f);
+            }
+#pragma unroll
+            for (int m = 0; m < 8; ++m) p[m] = psrc[(unsigned)(q + m * C::T * C::TILE)];      // (x TILE + r, x = j + m T: q = j TILE + r)
+            last_stage<NX, +1, 2, false>(v[pass], j, lds, smem_tail[0], sql);
+#pragma unroll
+            for (int m = 0; m < 8; ++m) {
+                const cf t = cmulc(v[pass][m], cadd(p[m], a.carrier_phi));              // G * conj(phi)
+                gdst[(unsigned)((j + m * C::T) * NY + yg)] = make_float2(a.k * t.y, -a.k * t.x);      // (32-bit offsets inside one wavefield)
+                v[pass][m] = cmulc(v[pass][m], make_float2(1.f + db[m].x, db[m].y));    // conj(c) G
+            }
+            tw.sq = sqt;                                  // (the first stage takes no twiddles, only the step's sqrt(1/2))
+            stage_compute<NX, -1, P::R0, 1, 0, 1, false>(v[pass], tw, j);
+        }
+        __syncthreads();
+#pragma unroll
+        for (int pass = 0; pass < C::PASSES; ++pass) {
+            const int q = threadIdx.x + pass * BDOF_THREADS;
+            const int r = q % C::TILE, j = q / C::TILE;
+            RowLds<C::T> lds{smem + r * C::RS};
+            stage_write<NX, P::R0, 1>(v[pass], j, lds);
+        }
+        __syncthreads();
+        // the rest of Px_{z-1}^H, row mapping
+#pragma nounroll
+        for (int pass = 0; pass < C::PASSES; ++pass) {
+            const int r = pass * C::RPP + rl;
+            RowLds<C::T> lds{smem + r * C::RS};
+            cf u[8], hv[8];
+#pragma unroll
+            for (int m = 0; m < 8; ++m) hv[m] = a.h_trail[tid + m * C::T];
+            tw_select(tw, smem_tw[1], smem_tail[1], sqt, tid);
+            line_fft_rest<NX, -1, 1, false>(u, tw, tid, lds);
+#pragma unroll
+            for (int m = 0; m < 8; ++m) u[m] = cmulc(u[m], hv[m]);
             line_fft_partial<NX, +1, 2, false>(u, tw, tid, lds);
         }
         __syncthreads();

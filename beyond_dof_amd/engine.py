@@ -537,10 +537,21 @@ class MultisliceEngine(object):
         return int(self.lib.bdof_batch_groups(self.h, int(B)))
 
     def set_sweep_fusion(self, mode):
-        """Fused forward sweep of loss_grad (bdof_set_sweep_fusion, include/bdof.h): 0 never, 1 the forward sweep, 2 both sweeps
-        (runs the highest stage the library carries).  An engine starts at 0, so that its results stay bit for bit those of the
-        tape-free adjoint's forward sweep; FullfieldSolver switches to 2.  Ineligible configurations run the two-kernel sweep."""
+        """Fused forward sweep of loss_grad (bdof_set_sweep_fusion, include/bdof.h): 0 never, 1 the forward sweep; 2 is accepted and
+        runs 1, the highest stage this switch carries (the fused adjoint sweep has a switch of its own, set_adjoint_fusion).  An
+        engine starts at 0, so that its results stay bit for bit those of the tape-free adjoint's forward sweep; FullfieldSolver
+        switches to 1.  Ineligible configurations run the two-kernel sweep."""
         self.ctx.check(self.lib.bdof_set_sweep_fusion(self.h, int(mode)))
+
+    def set_adjoint_fusion(self, on=True):
+        """Fused adjoint sweep of loss_grad (bdof_set_adjoint_fusion): one kernel per slice below the top one, wherever the fused
+        forward sweep runs (set_sweep_fusion(1) and an eligible configuration).  An engine starts with it off."""
+        self.ctx.check(self.lib.bdof_set_adjoint_fusion(self.h, 1 if on else 0))
+
+    @property
+    def adjoint_fused(self):
+        """1 if the last loss_grad ran the fused adjoint sweep (bdof_adjoint_fused)."""
+        return int(self.lib.bdof_adjoint_fused(self.h))
 
     @property
     def sweep_fused(self):

@@ -71,6 +71,14 @@ class _VolumeSolver(object):
         """The mode the last loss + gradient actually ran (0: the two-kernel sweep)."""
         return self.eng.sweep_fused
 
+    def set_adjoint_fusion(self, on=True):
+        self.eng.set_adjoint_fusion(on)
+
+    @property
+    def adjoint_fused(self):
+        """1 if the last loss + gradient ran the fused adjoint sweep."""
+        return self.eng.adjoint_fused
+
     # ---- state -------------------------------------------------------------------------------
     def set_volume(self, obj_delta, obj_beta):
         self.x[self.cur].upload(util.volume_to_rows(obj_delta, obj_beta))
@@ -408,7 +416,8 @@ class FullfieldSolver(_VolumeSolver):
         self.eng = MultisliceEngine(self.dim_y, self.dim_x, self.dim_z, self.mb, with_grad=True, device=device, stream=stream,
                                     recompute=recompute, adjoint64=adjoint64, slice_binning=slice_binning)
         self.ctx = self.eng.ctx
-        self.eng.set_sweep_fusion(1)        # the fused forward sweep (a ctx of its own starts at 0); a later stage is a decision to take here
+        self.eng.set_sweep_fusion(1)        # the fused forward sweep (a ctx of its own starts at 0)
+        self.eng.set_adjoint_fusion(True)   # ... and the fused adjoint sweep behind it (MEASUREMENTS.md: the step-time criterion)
         self.eng.set_loss(loss_type, poisson_multiplier)
         self.eng.set_physics(energy_ev, psize_cm, free_prop_cm, variant=variant, detector_kernel=detector_kernel)
         if self.conv:

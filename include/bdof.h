@@ -354,7 +354,9 @@ void* bdof_grot(bdof_ctx* ctx);      /* device [B][S][NX][NY] pairs */
 /* Field `slot` of the ctx's tape, device [Bmax][NX][NY] complex64 (NULL: no tape, or no such slot), as the last sweep left it; for
  * inspection and tests.  After a bdof_loss_grad that ran the fused forward sweep (bdof_sweep_fused) slot z <= S-2 holds the
  * real-space scattered part of phi_z, the wave behind slice z of np_funcs.py:37-40 less its constant part, and slot S-1 psi_hat_{S-1};
- * after the two-kernel sweep slot z holds psi_hat_{z+1}. */
+ * after the two-kernel sweep slot z holds psi_hat_{z+1}.  When the fused adjoint sweep ran too (bdof_adjoint_fused) the odd slots
+ * z <= S-3 hold the same values in tile blocks, [b][NY / T][NX][T] with T = max(16, 4096 / NX) rows of y per tile: entry
+ * ((b NY / T + y / T) NX + x) T + y % T is phi_z[b][x][y].  Even slots keep [b][x][y]. */
 void* bdof_tape_slot(bdof_ctx* ctx, int slot);
 /* Read-only view of the table of modulation factors c - 1 = exp(i k delta) exp(-k beta) - 1 that every sweep reads: one entry per
  * (delta, beta) pair of the bound object, in the object's own order.  Builds the table if it is stale (the pass the sweeps run),
@@ -456,8 +458,8 @@ int bdof_batch_groups(bdof_ctx* ctx, int B);
  * util.py:73-102) is separable, H(u, v) = Hx(u) Hy(v), so the slice chain of np_funcs.py:37-43 regroups into kernels that work on
  * lines of one direction — "finish the previous step along my lines, modulate, start the next step along my lines" — one launch and
  * one trip of the wavefield through memory per slice where the two-kernel sweep takes two (32 instead of 40 B per pixel and slice).
- * mode: 0 never, 1 the forward sweep (the adjoint sweep reads the phi tape it leaves), 2 both sweeps; a mode above the highest
- * stage the library carries (1) runs that stage.  A new ctx starts at 0: the two routes agree to float32 rounding, not bit for
+ * mode: 0 never, 1 the forward sweep (the adjoint sweep reads the phi tape it leaves); 2 is accepted and runs 1, the highest
+ * stage this switch carries (the fused adjoint sweep has a switch of its own, bdof_set_adjoint_fusion below).  A new ctx starts at 0: the two routes agree to float32 rounding, not bit for
  * bit, and callers of this ABI compare bdof_loss_grad bit for bit with the tape-free adjoint (BDOF_CFG_RECOMPUTE), whose forward
  * sweep is not fused; the full-field solver of the Python host switches to the highest stage.  The fused route is taken where the configuration is
  * eligible: tape (not BDOF_CFG_RECOMPUTE), no slice binning, scalar carrier, BDOF_DET_NONE / BDOF_DET_NEAR, no window offsets, no
@@ -467,6 +469,15 @@ int bdof_batch_groups(bdof_ctx* ctx, int B);
  * other entry point.  bdof_sweep_fused: the mode the last bdof_loss_grad actually ran (0 before the first). */
 int bdof_set_sweep_fusion(bdof_ctx* ctx, int mode);
 int bdof_sweep_fused(bdof_ctx* ctx);
+/* The fused adjoint sweep of bdof_loss_grad: below the top slice one kernel per slice, on lines of alternating direction, through
+ * the transposes of the separable steps (40 B per pixel and slice where the two-kernel adjoint moves 56).  A switch of its own
+ * beside bdof_set_sweep_fusion, whose modes and query stay what they were: on = 1 takes the route wherever the fused forward sweep
+ * runs (bdof_set_sweep_fusion(1) and an eligible configuration), on = 0 (a new ctx) never.  The forward sweep then leaves its odd
+ * tape slots in tile blocks (bdof_tape_slot); its arithmetic, the loss and the detector wave do not change.  The gradient rows
+ * agree with the two-kernel adjoint's to float32 rounding.  bdof_adjoint_fused: 1 if the last bdof_loss_grad ran the fused adjoint
+ * sweep (0 before the first, and after every other configuration). */
+int bdof_set_adjoint_fusion(bdof_ctx* ctx, int on);
+int bdof_adjoint_fused(bdof_ctx* ctx);
 
 /* Per-kernel-class timing with HIP events on the stream of each launch (bench.py roofline leg).  enable = 0 off, 1 every launch,
  * n > 1 every n-th launch of the per-slice kernel classes (two event records per launch cost ~9 us of stream time). */
