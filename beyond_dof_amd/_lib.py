@@ -39,6 +39,8 @@ _SIGNATURES = {
     'bdof_set_probe': (ctypes.c_int, [_vp, _vp, ctypes.c_double, ctypes.c_double]),
     'bdof_set_meas_mode': (ctypes.c_int, [_vp, ctypes.c_int]),
     'bdof_set_loss': (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_double]),
+    'bdof_set_detector_weights': (ctypes.c_int, [_vp, _vp]),
+    'bdof_adjoint_carrier': (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp]),
     'bdof_probe_stack_supported': (ctypes.c_int, [_vp]),
     'bdof_set_probe_field': (ctypes.c_int, [_vp, _vp, _vp, _vp]),
     'bdof_set_probe_stack': (ctypes.c_int, [_vp, _vp, _vp]),

@@ -100,6 +100,7 @@ struct Workspace {
     DevBuf<cf> gpsi0;                            // [Bmax][NX][NY] G(psi_0) per wavefield (bdof_enable_probe_grad)
     const cf* gpsi_src = nullptr;                // borrowed from this workspace: where the last bdof_loss_grad left it (gpsi0, or the generic engine's field)
     DevBuf<double> partial, loss_dev;
+    DevBuf<float> wgt;                           // [NX][NY] detector weights in the order of one wavefield of meas; none: no weights (bdof_set_detector_weights)
     // real-space truncated-kernel propagator (bdof_set_conv)
     bool have_conv = false;
     DevBuf<ConvTaps> taps_dev;
@@ -243,6 +244,10 @@ static int check_range(bdof_ctx* c, int z0, int nz) {
 static int need_lsq(bdof_ctx* c, const char* who) {
     return c->loss_kind == BDOF_LOSS_LSQ ? 0 : fail(c, BDOF_ERR_STATE, std::string(who) + " computes the least-squares loss only: bdof_set_loss(BDOF_LOSS_LSQ) first");
 }
+// ... and no detector weights (bdof_set_detector_weights names them)
+static int need_unweighted(bdof_ctx* c, const char* who) {
+    return !c->wgt ? 0 : fail(c, BDOF_ERR_STATE, std::string(who) + " does not carry detector weights: bdof_set_detector_weights(ctx, NULL) first");
+}
 // the entry points that take one propagation step per voxel slice only (bdof_set_slice_binning names them)
 static int need_unbinned(bdof_ctx* c, const char* who) {
     return !c || c->bin == 1 ? 0 : fail(c, BDOF_ERR_STATE, std::string(who) + " does not carry slice binning: it would run the unbinned model (bdof_set_slice_binning)");
@@ -325,6 +330,7 @@ static DetPlane det_plane(const bdof_ctx* c, const Group& g, int B, const cf* pf
     }
     d.seed_scale = 2.f / ((float)B * (float)c->NX * (float)c->NY);
     d.mu = c->loss_mu;
+    d.wgt = c->wgt;
     // Set whenever the ctx carries an adjoint carrier, whatever the launch does: the kernels write them only where they fit
     // (a.meas) and reach the DC bin's test (k_row_loss<FAR>; k_g_loss, after its seed64 branch has taken every bin of a float64
     // adjoint), and nothing reads them unless an adjoint sweep follows.
@@ -702,7 +708,7 @@ static int launch_loss_real(bdof_ctx* c, const Group& g, const DetPlane& det, co
     a.twiddle = c->twY;
     int grid = 0;
     DISPATCH_N(c->NY, grid = rows_grid<N_>(c, g.B, c->NX); with_bool(tstore, [&](auto TSTORE) { with_bool(meas && loss_is_poisson(c), [&](auto PSN) {
-        hipLaunchKernelGGL((k_row_loss<N_, false, TSTORE, PSN>), dim3(grid), dim3(BDOF_THREADS), 0, g.st, a);
+        with_bool(meas && det.wgt, [&](auto WGT) { hipLaunchKernelGGL((k_row_loss<N_, false, TSTORE, PSN, WGT>), dim3(grid), dim3(BDOF_THREADS), 0, g.st, a); });
     }); }));
     return grid;
 }
@@ -716,7 +722,7 @@ static int launch_loss_far(bdof_ctx* c, const Group& g, const DetPlane& det, con
     a.twiddle = c->twX;
     int grid = 0;
     DISPATCH_N(c->NX, grid = rows_grid<N_>(c, g.B, c->NY); with_bool(meas && loss_is_poisson(c), [&](auto PSN) {
-        hipLaunchKernelGGL((k_row_loss<N_, true, true, PSN>), dim3(grid), dim3(BDOF_THREADS), 0, g.st, a);
+        with_bool(meas && det.wgt, [&](auto WGT) { hipLaunchKernelGGL((k_row_loss<N_, true, true, PSN, WGT>), dim3(grid), dim3(BDOF_THREADS), 0, g.st, a); });
     }));
     return grid;
 }
@@ -1032,7 +1038,9 @@ static int generic_loss_grad(bdof_ctx* c, int B, const float* meas, void* out_wa
         set_carrier(det, a);                       // the carrier as the sweep's own recurrence left it
         GLossArgs la = g_loss_args(c, B, det, c->bufA, (cf*)out_wave, meas);
         la.seed64 = f64 ? c->g64 : nullptr;        // float64 adjoint: every bin's seed stays in float64, no adjoint carrier to split off
-        with_bool(loss_is_poisson(c), [&](auto PSN) { hipLaunchKernelGGL(k_g_loss<PSN>, dim3(egrid), dim3(256), 0, c->stream, la); });
+        with_bool(loss_is_poisson(c), [&](auto PSN) { with_bool(meas && det.wgt, [&](auto WGT) {
+            hipLaunchKernelGGL((k_g_loss<PSN, WGT>), dim3(egrid), dim3(256), 0, c->stream, la);
+        }); });
     }
     hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, c->stream, c->partial, egrid, 1.0 / ((double)B * c->NX * c->NY), c->loss_dev);
     if (f64) {
@@ -1091,15 +1099,17 @@ template <auto K> static int max_lds_once(bdof_ctx* c, int bytes) {
 }
 
 // ---- LDS-resident engine ---------------------------------------------------------------------------
-template <int N, int T, int WPE, bool PSN> static int resident_launch_t(bdof_ctx* c, const ResArgs& a, int grid, int* waves) {
+template <int N, int T, int WPE, bool PSN, bool WGT> static int resident_launch_t(bdof_ctx* c, const ResArgs& a, int grid, int* waves) {
     *waves = T / 64;
     const size_t lds = sizeof(cf) * ((size_t)N * (N | 1) + 2 * N) + sizeof(long long) * 3 * N;
-    if (int r = max_lds_once<k_resident<N, T, WPE, PSN>>(c, (int)lds)) return r;
-    hipLaunchKernelGGL((k_resident<N, T, WPE, PSN>), dim3(grid), dim3(T), lds, c->stream, a);
+    if (int r = max_lds_once<k_resident<N, T, WPE, PSN, WGT>>(c, (int)lds)) return r;
+    hipLaunchKernelGGL((k_resident<N, T, WPE, PSN, WGT>), dim3(grid), dim3(T), lds, c->stream, a);
     return 0;
 }
 template <int N> static int resident_launch(bdof_ctx* c, const ResArgs& a, int grid, int* waves) {
-    return with_bool(a.meas && loss_is_poisson(c), [&](auto PSN) { return resident_launch_t<N, ResPlan<N>::T, ResPlan<N>::WPE, PSN>(c, a, grid, waves); });
+    return with_bool(a.meas && loss_is_poisson(c), [&](auto PSN) { return with_bool(a.meas && a.det.wgt, [&](auto WGT) {
+        return resident_launch_t<N, ResPlan<N>::T, ResPlan<N>::WPE, PSN, WGT>(c, a, grid, waves);
+    }); });
 }
 
 // One workgroup per wavefield: against the streaming kernels (sizes with a fused plan) the resident engine wins once the
@@ -1601,6 +1611,31 @@ int bdof_set_loss(bdof_ctx* c, int kind, double multiplier) {
     return 0;
 }
 
+int bdof_set_detector_weights(bdof_ctx* c, const float* w) {
+    if (!c) return BDOF_ERR_ARG;
+    if (int r = need_configured(c)) return r;
+    HIPC(c, hipSetDevice(c->device));
+    // launches in flight may still read the plane that goes
+    HIPC(c, hipStreamSynchronize(c->stream));
+    if (!w) { c->wgt.reset(); return 0; }
+    const size_t n = (size_t)c->NX * c->NY;
+    HIPC(c, c->wgt.room(n));
+    HIPC(c, hipMemcpy(c->wgt, w, n * sizeof(float), hipMemcpyHostToDevice));
+    return 0;
+}
+
+int bdof_adjoint_carrier(bdof_ctx* c, int B, double* gcar, double* gt0) {
+    if (!c || !gcar || !gt0) return BDOF_ERR_ARG;
+    int r;
+    if ((r = need_configured(c)) || (r = check_batch(c, B))) return r;
+    if (!use_adj_carrier(c) || c->adj64) return 0;      // (the float64 adjoint keeps every bin's seed in its own field)
+    HIPC(c, hipSetDevice(c->device));
+    HIPC(c, hipStreamSynchronize(c->stream));
+    HIPC(c, hipMemcpy(gcar, c->gcar, sizeof(double2) * B, hipMemcpyDeviceToHost));
+    HIPC(c, hipMemcpy(gt0, c->gt0, sizeof(double2) * B, hipMemcpyDeviceToHost));
+    return 1;
+}
+
 int bdof_probe_stack_supported(bdof_ctx* c) {
     // every engine of the transfer-function path carries it (the real-space propagator of bdof_set_conv does not)
     return c && c->NY > 0 ? 1 : 0;
@@ -1920,6 +1955,7 @@ int bdof_field_loss_seed(bdof_ctx* c, void* field, const float* meas, int FX, in
     if (!c || !field || !meas || FX < 1 || FY < 1) return BDOF_ERR_ARG;
     if (!c->partial) return fail(c, BDOF_ERR_STATE, "bdof_configure has not been called");
     if (int r = need_lsq(c, "bdof_field_loss_seed")) return r;
+    if (int r = need_unweighted(c, "bdof_field_loss_seed")) return r;
     HIPC(c, hipSetDevice(c->device));
     const size_t n = (size_t)FX * FY;
     const int egrid = g_elem_grid(c, n);
@@ -2225,6 +2261,7 @@ int bdof_loss_grad_conv_f64(bdof_ctx* c, int B, const int* angle_of_b, const int
     if (!c || !meas) return BDOF_ERR_ARG;
     if (!c->c64_ks || c->c64_tf) return fail(c, BDOF_ERR_STATE, "bdof_set_conv_f64 has not been called");
     if (int rl = need_lsq(c, "bdof_loss_grad_conv_f64")) return rl;
+    if (int rw = need_unweighted(c, "bdof_loss_grad_conv_f64")) return rw;
     if (!c->obj_src) return fail(c, BDOF_ERR_STATE, "bdof_set_object (with (delta, beta) rows) has not been called");
     if (!c->grot || !c->partial) return fail(c, BDOF_ERR_STATE, "bdof_configure(with_grad = 1) needed");
     int r;
@@ -2263,7 +2300,7 @@ int bdof_loss_grad_conv_f64(bdof_ctx* c, int B, const int* angle_of_b, const int
     if (far) RFC(c, rocfft_execute(pf, buf, nullptr, c->fft.info));           // un-shifted, un-normalised fft2 (propagation.py:114-115)
     else if (near) { if ((r = bdof_fields_free_step(c, psi, B, N, N, c->c64_hdet, 0, 1))) return r; }      // propagation.py:122-124
     const int lgrid = std::min(eg, c->npartial);
-    hipLaunchKernelGGL(k_c64_loss<false>, dim3(lgrid), dim3(256), 0, c->stream, psi, meas, c->partial, B, N, N, far ? 1 : 0, meas_ref, 2.0 / (double)n, 0.0);
+    hipLaunchKernelGGL(k_c64_loss<false>, dim3(lgrid), dim3(256), 0, c->stream, psi, meas, c->partial, B, N, N, far ? 1 : 0, meas_ref, 2.0 / (double)n, 0.0, (const float*)nullptr);
     hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, c->stream, c->partial, lgrid, 1.0 / (double)n, c->loss_dev);
     if (far) RFC(c, rocfft_execute(pi, buf, nullptr, c->fft.info));           // G(q) = N^2 ifft2(G(d)): the un-normalised inverse
     else if (near) { if ((r = bdof_fields_free_step(c, psi, B, N, N, c->c64_hdet, 1, 1))) return r; }
@@ -2343,9 +2380,10 @@ int bdof_loss_grad_tf_f64(bdof_ctx* c, int B, const int* angle_of_b, const int* 
     if (c->det_mode == BDOF_DET_NEAR) { if ((r = bdof_fields_free_step(c, psi, B, NX, NY, c->c64_hdet, 0, 1))) return r; }
     else if (far) RFC(c, rocfft_execute(pf, buf, nullptr, c->fft.info));       // un-shifted, un-normalised fft2
     const int lgrid = std::min(eg, c->npartial);
-    with_bool(loss_is_poisson(c), [&](auto PSN) {
-        hipLaunchKernelGGL(k_c64_loss<PSN>, dim3(lgrid), dim3(256), 0, c->stream, psi, meas, c->partial, B, NX, NY, far ? 1 : 0, meas_ref, 2.0 / (double)n, c->loss_mu);
-    });
+    with_bool(loss_is_poisson(c), [&](auto PSN) { with_bool((bool)c->wgt, [&](auto WGT) {
+        hipLaunchKernelGGL((k_c64_loss<PSN, WGT>), dim3(lgrid), dim3(256), 0, c->stream, psi, meas, c->partial, B, NX, NY, far ? 1 : 0, meas_ref, 2.0 / (double)n,
+                           c->loss_mu, (const float*)c->wgt);
+    }); });
     hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, c->stream, c->partial, lgrid, 1.0 / (double)n, c->loss_dev);
     if (c->det_mode == BDOF_DET_NEAR) { if ((r = bdof_fields_free_step(c, psi, B, NX, NY, c->c64_hdet, 1, 1))) return r; }
     else if (far) RFC(c, rocfft_execute(pi, buf, nullptr, c->fft.info));       // F^H: the un-normalised inverse
@@ -2686,6 +2724,7 @@ int bdof_loss_grad_conv(bdof_ctx* c, int B, const int* angle_of_b, const int* xo
     if (r) return r;
     if (!meas) return BDOF_ERR_ARG;
     if ((r = need_lsq(c, "bdof_loss_grad_conv"))) return r;
+    if ((r = need_unweighted(c, "bdof_loss_grad_conv"))) return r;
     // residual splitting at the detector (bdof_set_meas_mode(1): meas holds m - |a_0|), real-space detectors: the renormalised
     // wave is kept as A + e', A = s a_S a float64 scalar formed on the host from the corner pixel, and |A + e'| - m is
     // evaluated without the cancellation of two numbers of size one (seed_split) — as on the transfer-function path

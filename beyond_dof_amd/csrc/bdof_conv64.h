@@ -60,9 +60,10 @@ __global__ __launch_bounds__(256) void k_c64_scale(double2* f, size_t n, const d
 // loss partials and seed in place: d [B][NX][NY]; far: d is [b][kx][ky] and meas [b][ky][kx] (un-shifted), else both [b][x][y].
 // meas holds m - meas_ref (residual splitting of the float32 path); G = 2 (|d| - m) d / |d| * seed_scale
 // PSN: the Poisson data term with mu photons per unit intensity (seed_weight, bdof_kernels.h)
-template <bool PSN>
+// WGT: detector weights, wgt [NX][NY] in the order of one wavefield of meas (bdof_set_detector_weights)
+template <bool PSN, bool WGT = false>
 __global__ __launch_bounds__(256) void k_c64_loss(double2* d, const float* __restrict__ meas, double* partial, int B, int NX, int NY, int far,
-                                                 double meas_ref, double seed_scale, double mu) {
+                                                 double meas_ref, double seed_scale, double mu, const float* __restrict__ wgt) {
     const size_t n = (size_t)B * NX * NY;
     double acc = 0.0, acc2 = 0.0;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
@@ -70,7 +71,9 @@ __global__ __launch_bounds__(256) void k_c64_loss(double2* d, const float* __res
         const size_t r = i / NY;
         const int x = r % NX, b = r / NX;
         const double m = (double)meas[far ? ((size_t)b * NY + y) * NX + x : i] + meas_ref;
-        d[i] = seed_f64<PSN>(d[i], m, seed_scale, mu, acc, acc2);
+        float w = 1.f;
+        if constexpr (WGT) w = wgt[far ? (size_t)y * NX + x : (size_t)x * NY + y];
+        d[i] = seed_f64<PSN, WGT>(d[i], m, seed_scale, mu, acc, acc2, w);
     }
     block_store_sum2<256>(acc, acc2, partial + 2 * blockIdx.x);
 }

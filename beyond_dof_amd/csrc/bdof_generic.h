@@ -75,8 +75,8 @@ struct GLossArgs {
     DetPlane det;        // bdof_kernels.h; pfield / pfield64 [x][y], far field [kx][ky]
 };
 
-// PSN: the Poisson data term (seed_weight, bdof_kernels.h)
-template <bool PSN>
+// PSN: the Poisson data term (seed_weight, bdof_kernels.h); WGT: detector weights, det.wgt in the order of one wavefield of meas
+template <bool PSN, bool WGT = false>
 __global__ __launch_bounds__(256) void k_g_loss(GLossArgs a) {
     const size_t n = (size_t)a.B * a.NX * a.NY;
     const DetPlane& det = a.det;
@@ -88,6 +88,7 @@ __global__ __launch_bounds__(256) void k_g_loss(GLossArgs a) {
         const size_t pi = (size_t)x * a.NY + y;                                    // in the carrier field's plane
         const size_t oi = a.far ? ((size_t)b * a.NY + y) * a.NX + x : idx;         // in meas / out_wave
         const bool dc = x == 0 && y == 0;
+        const float w = a.meas ? det_weight<WGT>(det, a.far ? (size_t)y * a.NX + x : pi) : 1.f;
         cf d = a.field[idx];
         if (a.seed64 && a.meas) {
             double2 p = make_double2(0.0, 0.0);
@@ -95,18 +96,18 @@ __global__ __launch_bounds__(256) void k_g_loss(GLossArgs a) {
             else if (det.pfield) { const cf q = det.pfield[pi]; p = make_double2((double)q.x, (double)q.y); }
             else if (!a.far || dc) p = det.carrier_dd;
             p = make_double2(p.x + (double)d.x, p.y + (double)d.y);
-            a.seed64[idx] = seed_f64<PSN>(p, (double)a.meas[oi] + det.meas_ref, (double)det.seed_scale, det.mu, acc, acc2);
+            a.seed64[idx] = seed_f64<PSN, WGT>(p, (double)a.meas[oi] + det.meas_ref, (double)det.seed_scale, det.mu, acc, acc2, w);
             if (a.out_wave) a.out_wave[oi] = make_float2((float)p.x, (float)p.y);
             continue;
         }
         if (det.meas_dev && a.meas && !a.far && !det.pfield) {
             if (a.out_wave) a.out_wave[idx] = cadd(d, det.carrier);
-            a.field[idx] = seed_split<PSN>(d, a.meas[idx], det, acc, acc2);
+            a.field[idx] = seed_split<PSN, WGT>(d, a.meas[idx], det, acc, acc2, w);
             continue;
         }
         if (det.pfield64 && a.meas) {
             cf dw;
-            a.field[idx] = seed_f64<PSN>(d, det_field64(det, pi), a.meas[oi], det, acc, acc2, dw);
+            a.field[idx] = seed_f64<PSN, WGT>(d, det_field64(det, pi), a.meas[oi], det, acc, acc2, dw, w);
             if (a.out_wave) a.out_wave[oi] = dw;
             continue;
         }
@@ -115,11 +116,11 @@ __global__ __launch_bounds__(256) void k_g_loss(GLossArgs a) {
         else if (!a.far || dc) d = cadd(d, det.carrier);
         if (a.out_wave) a.out_wave[oi] = d;
         if (a.meas && det.gcar && a.far && dc) {
-            seed_dc_bin<PSN>(det, b, e0, a.meas[oi], acc, acc2);
+            seed_dc_bin<PSN, WGT>(det, b, e0, a.meas[oi], acc, acc2);
             a.field[idx] = make_float2(0.f, 0.f);       // nothing of this bin goes through the transform back
             continue;
         }
-        if (a.meas) a.field[idx] = seed_plain<PSN>(d, a.meas[oi], det, acc, acc2);
+        if (a.meas) a.field[idx] = seed_plain<PSN, WGT>(d, a.meas[oi], det, acc, acc2, w);
     }
     if (a.meas) block_store_sum2<256>(acc, acc2, a.partial + 2 * blockIdx.x);
 }

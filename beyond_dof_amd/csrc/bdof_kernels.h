@@ -469,6 +469,10 @@ struct DetPlane {
     // ---- read by the streaming, generic and real-space-propagator launches only
     double2 pscale = {1.0, 0.0};         // complex factor on pfield64: the real-space propagator's renormalisation s; (1, 0): none
     double meas_ref = 0.0;               // what the host subtracted (meas_dev), for the sites that form the wave in float64 (seed64)
+    // Detector weights (bdof_set_detector_weights; WGT instantiations only): L = sum w l / (number of pixels), G(d) = w (the seed
+    // below).  Here, in the 8 bytes the alignment of carrier_dd left empty: the head above stays one piece and every other member
+    // keeps its offset, so the kernels without WGT are the instructions they were; a WGT kernel fetches this one pointer beside the head.
+    const float* wgt = nullptr;          // nullable: one plane in the index order of one wavefield of `meas`, shared by the batch
     double2 carrier_dd = {0.0, 0.0};     // `carrier` in float64
     double2 a_end = {0.0, 0.0};          // constant part of phi_{S-1} (far field: carrier = a_end NX NY)
     // adjoint carrier (far field + plane-wave carrier, AdjCarrier below): the DC bin is evaluated in float64 and its seed
@@ -518,45 +522,58 @@ __device__ __forceinline__ double poisson_weight(double r, double a, double m, d
 // amplitude m in; the two sums accumulated (always in double); the factor f of the seed G(d) = f d out, in the precision the
 // residual was formed in.  The kernels carry the kind as a template parameter (PSN: Poisson), so least squares never sees mu or
 // m.  m is a double because the split form only has it as a - r, which is formed in double.
-template <bool PSN, class Real>
-__device__ __forceinline__ Real seed_weight(Real r, Real a, double m, Real seed_scale, double mu, double& acc, double& acc2) {
+// WGT: the pixel's detector weight w (DetPlane::wgt) on both sums and on the seed.  All three are linear in one factor of the
+// term — mu for Poisson, one of the two r of least squares — and w goes onto that factor, so every operation after it is the
+// operation of the unweighted form: w = 1 gives its bits, w = 0 gives 0 for any finite m.  Without WGT w is not read.
+template <bool PSN, bool WGT, class Real>
+__device__ __forceinline__ Real seed_weight(Real r, Real a, double m, Real seed_scale, double mu, float w, double& acc, double& acc2) {
     if constexpr (PSN) {
+        if constexpr (WGT) mu *= (double)w;
         return (Real)((double)seed_scale * poisson_weight((double)r, (double)a, m, mu, acc, acc2));
     } else {
-        acc += (double)r * (double)r;
-        acc2 += (double)r * (double)a;
-        return a > (Real)0 ? seed_scale * r / a : (Real)0;
+        Real rw = r;
+        if constexpr (WGT) rw *= (Real)w;
+        acc += (double)rw * (double)r;
+        acc2 += (double)rw * (double)a;
+        return a > (Real)0 ? seed_scale * rw / a : (Real)0;
     }
+}
+// the weight of plane index i (the index of `meas` within its wavefield)
+template <bool WGT> __device__ __forceinline__ float det_weight(const DetPlane& p, size_t i) {
+    if constexpr (WGT) return p.wgt[i];
+    else return 1.f;
 }
 
 // plain: d is the whole detector wave in float32, r = |d| - m
-template <bool PSN> __device__ __forceinline__ cf seed_plain(cf d, float m, const DetPlane& p, double& acc, double& acc2) {
+template <bool PSN, bool WGT = false>
+__device__ __forceinline__ cf seed_plain(cf d, float m, const DetPlane& p, double& acc, double& acc2, float w = 1.f) {
     const float a = sqrtf(d.x * d.x + d.y * d.y);
-    const float f = seed_weight<PSN>(a - m, a, (double)m, p.seed_scale, p.mu, acc, acc2);
+    const float f = seed_weight<PSN, WGT>(a - m, a, (double)m, p.seed_scale, p.mu, w, acc, acc2);
     return make_float2(d.x * f, d.y * f);
 }
 // split (DetPlane::meas_dev): e is the scattered part, d = carrier + e, r = (|d| - |carrier|) - (mdev - dref)
-template <bool PSN> __device__ __forceinline__ cf seed_split(cf e, float mdev, const DetPlane& p, double& acc, double& acc2) {
+template <bool PSN, bool WGT = false>
+__device__ __forceinline__ cf seed_split(cf e, float mdev, const DetPlane& p, double& acc, double& acc2, float w = 1.f) {
     const cf a = p.carrier;
     const cf d = cadd(a, e);
     const float ab = sqrtf(d.x * d.x + d.y * d.y);
     const float q = fmaf(2.f * a.x, e.x, fmaf(2.f * a.y, e.y, fmaf(e.x, e.x, e.y * e.y)));
     const float r = q / (ab + p.abs_carrier) - (mdev - p.dref);
-    const float f = seed_weight<PSN>(r, ab, (double)ab - (double)r, p.seed_scale, p.mu, acc, acc2);
+    const float f = seed_weight<PSN, WGT>(r, ab, (double)ab - (double)r, p.seed_scale, p.mu, w, acc, acc2);
     return make_float2(d.x * f, d.y * f);
 }
 // float64: the wave d = (float64 carrier) + e in double, r = |d| - m in double; the seed is returned un-rounded
-template <bool PSN>
-__device__ __forceinline__ double2 seed_f64(double2 d, double m, double seed_scale, double mu, double& acc, double& acc2) {
+template <bool PSN, bool WGT = false>
+__device__ __forceinline__ double2 seed_f64(double2 d, double m, double seed_scale, double mu, double& acc, double& acc2, float w = 1.f) {
     const double ab = sqrt(d.x * d.x + d.y * d.y);
-    const double f = seed_weight<PSN>(ab - m, ab, m, seed_scale, mu, acc, acc2);
+    const double f = seed_weight<PSN, WGT>(ab - m, ab, m, seed_scale, mu, w, acc, acc2);
     return make_double2(d.x * f, d.y * f);
 }
 // ... against a float64 carrier-field value c (DetPlane::pfield64): seed and detector wave c + e rounded once, at the end
-template <bool PSN>
-__device__ __forceinline__ cf seed_f64(cf e, double2 c, float m, const DetPlane& p, double& acc, double& acc2, cf& d_out) {
+template <bool PSN, bool WGT = false>
+__device__ __forceinline__ cf seed_f64(cf e, double2 c, float m, const DetPlane& p, double& acc, double& acc2, cf& d_out, float w = 1.f) {
     const double2 d = make_double2(c.x + (double)e.x, c.y + (double)e.y);
-    const double2 s = seed_f64<PSN>(d, (double)m, (double)p.seed_scale, p.mu, acc, acc2);
+    const double2 s = seed_f64<PSN, WGT>(d, (double)m, (double)p.seed_scale, p.mu, acc, acc2, w);
     d_out = make_float2((float)d.x, (float)d.y);
     return make_float2((float)s.x, (float)s.y);
 }
@@ -565,10 +582,12 @@ __device__ __forceinline__ double2 det_field64(const DetPlane& p, size_t i) {
     return make_double2(q.x * p.pscale.x - q.y * p.pscale.y, q.x * p.pscale.y + q.y * p.pscale.x);
 }
 // far field + plane-wave carrier: the DC bin of wavefield b, scattered part e0, evaluated in float64; its seed stays out of the
-// transforms (AdjCarrier).  The caller takes the bin out of its float32 path.
-template <bool PSN> __device__ __forceinline__ void seed_dc_bin(const DetPlane& p, int b, cf e0, float m, double& acc, double& acc2) {
+// transforms (AdjCarrier).  The caller takes the bin out of its float32 path.  WGT: the bin's weight is wgt[0] (un-shifted), and a
+// beamstop (w = 0) leaves gcar and gt0 exactly 0.
+template <bool PSN, bool WGT = false>
+__device__ __forceinline__ void seed_dc_bin(const DetPlane& p, int b, cf e0, float m, double& acc, double& acc2) {
     const double2 d = make_double2(p.carrier_dd.x + (double)e0.x, p.carrier_dd.y + (double)e0.y);
-    const double2 s0 = seed_f64<PSN>(d, (double)m, (double)p.seed_scale, p.mu, acc, acc2);
+    const double2 s0 = seed_f64<PSN, WGT>(d, (double)m, (double)p.seed_scale, p.mu, acc, acc2, det_weight<WGT>(p, 0));
     p.gcar[b] = s0;
     p.gt0[b] = make_double2(p.a_end.x * s0.x + p.a_end.y * s0.y, p.a_end.x * s0.y - p.a_end.y * s0.x);
 }
@@ -589,8 +608,21 @@ struct LossArgs {
     DetPlane det;        // pfield / pfield64 in the row layout of `in` ([R][N])
 };
 
+// p[i], fetched where it is used: the scheduling barrier keeps a run of these loads from being gathered in front of the code
+// between them.  A 32-bit index off a wave-uniform base: no address pair to keep per lane.
+__device__ __forceinline__ float load_here(const float* p, unsigned i) {
+    const float v = p[i];
+    __builtin_amdgcn_sched_barrier(0);
+    return v;
+}
+// k_row_loss, WGT: amplitude and weight of element m (u[m]) of the row — off the tile's first row of `meas` (an index below
+// TILE N) and off the plane (below NX NY <= 2^20)
+#define MEAS_OF(m) (WGT ? load_here(a.meas + (size_t)row0 * N, (unsigned)(r * N + tid + (m) * C::T)) : mm[m])
+#define WGT_OF(m) (WGT ? load_here(det.wgt, (unsigned)((r0 + r) * N + tid + (m) * C::T)) : 1.f)
+
 // FAR = false: inverse FFT first (rows of L1); FAR = true: forward FFT first (rows of L2).  PSN: the Poisson data term.
-template <int N, bool FAR, bool TSTORE, bool PSN = false>
+// WGT: detector weights (det.wgt, rows as `meas`), a template parameter as PSN is: the unweighted kernels do not change.
+template <int N, bool FAR, bool TSTORE, bool PSN = false, bool WGT = false>
 __global__ __launch_bounds__(BDOF_THREADS, RowCfg<N>::MIN_WAVES) void k_row_loss(LossArgs a) {
     typedef RowCfg<N> C;
     constexpr int S1 = FAR ? -1 : +1;     // direction of the first transform; the second is the opposite
@@ -615,7 +647,7 @@ __global__ __launch_bounds__(BDOF_THREADS, RowCfg<N>::MIN_WAVES) void k_row_loss
             float mm[8];
 #pragma unroll
             for (int m = 0; m < 8; ++m) u[m] = a.in[off + tid + m * C::T];
-            if (a.meas) {
+            if (!WGT && a.meas) {          // (WGT: MEAS_OF)
 #pragma unroll
                 for (int m = 0; m < 8; ++m) mm[m] = a.meas[off + tid + m * C::T];
             }
@@ -623,6 +655,11 @@ __global__ __launch_bounds__(BDOF_THREADS, RowCfg<N>::MIN_WAVES) void k_row_loss
 #pragma unroll
             for (int m = 0; m < 8; ++m) u[m] = cscale(u[m], a.in_scale);
             const DetPlane& det = a.det;
+            // WGT: amplitude and weight of element m are fetched where its seed is formed, one element after the other (MEAS_OF,
+            // WGT_OF).  These kernels sit at their 128 registers: eight more live values, beside mm[] across line_fft or behind
+            // it, or one more address pair per lane, spill in instances that did not (MEASUREMENTS.md, "detector weights").  The
+            // weight plane is cache-resident: one for the whole batch.  The conditions are constants: the instances without WGT
+            // read mm[] and nothing else, as they did.
             const bool dev = !FAR && det.meas_dev && a.meas && !det.pfield;
             cf e0 = make_float2(0.f, 0.f);        // FAR: scattered part of the DC bin
             if (det.pfield64) {
@@ -630,7 +667,7 @@ __global__ __launch_bounds__(BDOF_THREADS, RowCfg<N>::MIN_WAVES) void k_row_loss
                 for (int m = 0; m < 8; ++m) {
                     const double2 p = det_field64(det, (size_t)(r0 + r) * N + tid + m * C::T);
                     cf dw;
-                    if (a.meas) u[m] = seed_f64<PSN>(u[m], p, mm[m], det, acc, acc2, dw);
+                    if (a.meas) u[m] = seed_f64<PSN, WGT>(u[m], p, MEAS_OF(m), det, acc, acc2, dw, WGT_OF(m));
                     else dw = u[m] = make_float2((float)(p.x + (double)u[m].x), (float)(p.y + (double)u[m].y));
                     if (a.out_wave) a.out_wave[off + tid + m * C::T] = dw;
                 }
@@ -641,7 +678,7 @@ __global__ __launch_bounds__(BDOF_THREADS, RowCfg<N>::MIN_WAVES) void k_row_loss
                     for (int m = 0; m < 8; ++m) a.out_wave[off + tid + m * C::T] = cadd(u[m], det.carrier);
                 }
 #pragma unroll
-                for (int m = 0; m < 8; ++m) u[m] = seed_split<PSN>(u[m], mm[m], det, acc, acc2);
+                for (int m = 0; m < 8; ++m) u[m] = seed_split<PSN, WGT>(u[m], MEAS_OF(m), det, acc, acc2, WGT_OF(m));
             } else {
                 if (det.pfield) {
                     const cf* pf = det.pfield + (size_t)(r0 + r) * N;
@@ -662,12 +699,12 @@ __global__ __launch_bounds__(BDOF_THREADS, RowCfg<N>::MIN_WAVES) void k_row_loss
                         if (det.gcar && r0 + r == 0 && tid == 0) {
                             // u[0] = (m, 0) makes the float32 path below contribute exactly nothing for this bin (the row
                             // still goes through the transform back)
-                            seed_dc_bin<PSN>(det, b, e0, mm[0], acc, acc2);
-                            u[0] = make_float2(mm[0], 0.f);
+                            seed_dc_bin<PSN, WGT>(det, b, e0, MEAS_OF(0), acc, acc2);
+                            u[0] = make_float2(MEAS_OF(0), 0.f);
                         }
                     }
 #pragma unroll
-                    for (int m = 0; m < 8; ++m) u[m] = seed_plain<PSN>(u[m], mm[m], det, acc, acc2);
+                    for (int m = 0; m < 8; ++m) u[m] = seed_plain<PSN, WGT>(u[m], MEAS_OF(m), det, acc, acc2, WGT_OF(m));
                 }
             }
             if (a.out_hyb) {
@@ -690,6 +727,9 @@ __global__ __launch_bounds__(BDOF_THREADS, RowCfg<N>::MIN_WAVES) void k_row_loss
     }
     if (a.meas) block_store_sum2(acc, acc2, a.partial + 2 * blockIdx.x);
 }
+
+#undef MEAS_OF
+#undef WGT_OF
 
 __global__ void k_sum_partials(const double* partial, int n, double scale, double* out) {
     double v = 0.0;

@@ -528,8 +528,8 @@ template <int N, int T> struct ResPoint {
 
 // WPE = waves per SIMD the register allocation must leave room for (two workgroups per CU where the LDS image allows)
 // PSN: the Poisson data term (seed_weight, bdof_kernels.h) — a template parameter, so that the least-squares kernels are
-// the instructions they were
-template <int N, int T, int WPE, bool PSN = false>
+// the instructions they were.  WGT: detector weights (DetPlane::wgt), carried the same way.
+template <int N, int T, int WPE, bool PSN = false, bool WGT = false>
 __global__ __launch_bounds__(T, WPE) void k_resident(ResArgs a) {
     typedef ResPipe<N, T> Pipe;
     typedef ResPoint<N, T> Point;
@@ -624,18 +624,20 @@ __global__ __launch_bounds__(T, WPE) void k_resident(ResArgs a) {
                     const int x = res_div<N>(e), y = e - x * N;
                     const size_t o = b * fsz + (far ? y * N + x : e);
                     cf d = f[x * P + y], seed;
+                    float w = 1.f;                 // WGT: the weight at the index of meas within its wavefield
+                    if constexpr (WGT) { if (mode != 0) w = a.det.wgt[far ? y * N + x : e]; }
                     if (mode == 1) {               // plane-wave carrier, real-space detector, residual splitting
-                        seed = seed_split<PSN>(d, a.meas[o], a.det, acc, acc2);
+                        seed = seed_split<PSN, WGT>(d, a.meas[o], a.det, acc, acc2, w);
                         d = cadd(d, a.det.carrier);
                     } else if (mode == 2) {        // carrier field in float64: |d| - m in float64
                         cf dw;
-                        seed = seed_f64<PSN>(d, a.det.pfield64[e], a.meas[o], a.det, acc, acc2, dw);
+                        seed = seed_f64<PSN, WGT>(d, a.det.pfield64[e], a.meas[o], a.det, acc, acc2, dw, w);
                         d = dw;
                     } else {
                         if (a.det.pfield) d = cadd(d, a.det.pfield[e]);
                         else if (!far || e == 0) d = cadd(d, a.det.carrier);
                         seed = d;
-                        if (mode == 3) seed = seed_plain<PSN>(d, a.meas[o], a.det, acc, acc2);
+                        if (mode == 3) seed = seed_plain<PSN, WGT>(d, a.meas[o], a.det, acc, acc2, w);
                     }
                     if (a.out_wave) a.out_wave[o] = d;
                     if (mode != 0) f[x * P + y] = seed;

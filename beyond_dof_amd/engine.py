@@ -29,6 +29,43 @@ def check_poisson_path(loss_type, poisson_multiplier, propagator):
         raise ValueError("loss_type='poisson' runs on the transfer-function propagator (propagator='fft') only")
 
 
+def check_weights_path(detector_weights, propagator):
+    """Detector weights go with the transfer-function propagator — the only one whose detector kernels carry them."""
+    if detector_weights is not None and propagator != 'fft':
+        raise ValueError("detector_weights run on the transfer-function propagator (propagator='fft') only")
+
+
+def check_detector_weights(w, ny, nx):
+    """One (ny, nx) plane of finite weights >= 0, not all of them 0, as float32 (raises ValueError('detector_weights ...'))."""
+    w = np.asarray(w)
+    if w.shape != (ny, nx):
+        raise ValueError('detector_weights must have the shape of one measured frame, {}, not {}'.format((ny, nx), w.shape))
+    if w.dtype.kind not in 'fiub':
+        raise ValueError('detector_weights must be real numbers')
+    w = np.ascontiguousarray(w, dtype=np.float32)
+    if not np.isfinite(w).all():
+        raise ValueError('detector_weights must be finite')
+    if (w < 0).any():
+        raise ValueError('detector_weights must be >= 0')
+    if not (w > 0).any():
+        raise ValueError('detector_weights must leave at least one pixel with a weight > 0')
+    return w
+
+
+def read_detector_weights(detector_weights, data_path, frame_shape):
+    """The detector_weights keyword of the entry points as a checked (Y, X) float32 plane, or None: an array, or the name of a
+    dataset of the data file (for instance 'exchange/weights')."""
+    if detector_weights is None:
+        return None
+    if isinstance(detector_weights, str):
+        from . import h5io
+        try:
+            detector_weights = h5io.read_dataset(data_path, detector_weights)
+        except KeyError as e:
+            raise ValueError('detector_weights: {}'.format(e))
+    return check_detector_weights(detector_weights, int(frame_shape[0]), int(frame_shape[1]))
+
+
 def check_slice_binning(slice_binning):
     """The slice_binning keyword as every layer takes it: an integer >= 1 (raises ValueError)."""
     if isinstance(slice_binning, bool) or not isinstance(slice_binning, (int, np.integer)) or slice_binning < 1:
@@ -111,6 +148,7 @@ class MultisliceEngine(object):
     _gprobe = None              # enable_probe_grad
     residual_split = True       # False: amplitudes go to the device as they are (a probe that changes between steps)
     loss_type, poisson_multiplier = 'lsq', 2e6      # set_loss
+    detector_weights = None     # set_detector_weights: the (Y, X) float32 plane; None: every pixel counts alike
 
     def _reset_host_state(self):
         for name in set(vars(self)) & set(vars(MultisliceEngine)):
@@ -127,6 +165,30 @@ class MultisliceEngine(object):
         check_loss(kind, multiplier)
         self.ctx.check(self.lib.bdof_set_loss(self.h, _LOSS[kind], float(multiplier)))
         self.loss_type, self.poisson_multiplier = kind, float(multiplier)
+
+    def set_detector_weights(self, w):
+        """Detector weights (bdof_set_detector_weights, include/bdof.h): one plane w >= 0 for every measurement of the run, in
+        L = sum(w l) / (number of pixels) and G(d) = w (the seed) — 0 for dead and hot pixels, a beamstop, module gaps.  w is
+        (Y, X) in the orientation of one measured frame (the far field fftshifted, as the data are) and is laid out as
+        meas_layout lays out a frame; None clears the weights, and w == 1 everywhere gives the bits of no weights.  Where
+        w == 0 meas_layout puts the amplitude to 0, whatever the data hold there (NaN, inf, a saturated count), and
+        choose_residual_split looks at the other pixels only: amplitudes laid out BEFORE this call must be laid out again
+        (meas_layout) after it.  Call it after set_physics (the detector decides the layout).  Transfer-function propagator
+        only: with weights set loss_grad(conv=True) and the tiled propagator's field loss raise."""
+        if w is None:
+            self.ctx.check(self.lib.bdof_set_detector_weights(self.h, None))
+            self.detector_weights = None
+            return
+        w = check_detector_weights(w, self.ny, self.nx)
+        laid_out = self._plane_layout(w)            # (named: it has to outlive the call that reads its address)
+        self.ctx.check(self.lib.bdof_set_detector_weights(self.h, _hp(laid_out)))
+        self.detector_weights = w
+
+    def _plane_layout(self, p):
+        """(..., Y, X) planes in the index order of the loss kernels: transposed, or un-shifted in the far field."""
+        if self.det_mode == _lib.DET_FAR:
+            return np.ascontiguousarray(np.fft.ifftshift(p, axes=(-2, -1)))
+        return np.ascontiguousarray(np.swapaxes(p, -2, -1))
 
     # ---- physics -------------------------------------------------------------------------------
     def set_physics(self, energy_ev, psize_cm, free_prop_cm=None, variant='numpy_skip_last', pi=util.PI, field_shape=None,
@@ -162,6 +224,8 @@ class MultisliceEngine(object):
             self.ctx.check(self.lib.bdof_set_physics_f64(self.h, hs64.ctypes.data, _hp(hd64)))
         if self._probe_args is not None:
             self.set_probe(*self._probe_args)      # the carrier (field, calibration) of the probe depends on the physics
+        if self.detector_weights is not None:
+            self.set_detector_weights(self.detector_weights)      # the detector decides the plane's index order
 
     def _step_nm(self):
         """Length of one propagation step: slice_binning voxel slices."""
@@ -430,6 +494,8 @@ class MultisliceEngine(object):
         reference must be laid out again (meas_layout) after the mode changed."""
         if self.meas_ref:
             m64 = np.asarray(meas_abs, dtype=np.float64)
+            if self.detector_weights is not None:
+                m64 = m64.reshape(-1, self.ny, self.nx)[:, self.detector_weights > 0]      # the pixels that count
             if m64.size and np.abs(m64 - self.meas_ref).mean() > np.abs(m64).mean():
                 self.meas_ref = 0.0
                 self.ctx.check(self.lib.bdof_set_meas_mode(self.h, 0))
@@ -437,14 +503,16 @@ class MultisliceEngine(object):
 
     def meas_layout(self, meas_abs):
         """|measured| (n, Y, X) as libbdof's loss kernels read it under the mode in force: m - meas_ref (residual splitting; 0
-        without it) rounded once to float32, in the kernels' index order.  Changes nothing on the engine."""
+        without it) rounded once to float32, in the kernels' index order.  Under detector weights the amplitude is 0 wherever
+        w == 0, before anything else looks at it (0 NaN is NaN: the kernels could not keep such a pixel out).  Changes nothing
+        on the engine."""
+        if self.detector_weights is not None:
+            meas_abs = np.where(self.detector_weights > 0, meas_abs, 0)
         if self.meas_ref:
             m = (np.asarray(meas_abs, dtype=np.float64) - self.meas_ref).astype(np.float32)      # subtract in float64, round once
         else:
             m = np.asarray(meas_abs, dtype=np.float32)
-        if self.det_mode == _lib.DET_FAR:
-            return np.ascontiguousarray(np.fft.ifftshift(m, axes=(1, 2)))
-        return np.ascontiguousarray(m.transpose(0, 2, 1))
+        return self._plane_layout(m)
 
     def _meas_to_device(self, meas_abs):
         self.choose_residual_split(meas_abs)
@@ -503,6 +571,15 @@ class MultisliceEngine(object):
         loss = self.get_loss()
         self._keep['last_idx'] = (a, xo, yo, m)
         return loss
+
+    def adjoint_carrier(self, B):
+        """(gcar, gt0), complex128 [B]: the float64 DC-bin seed per wavefield and conj(a_end) times it, as the last loss_grad left
+        them (bdof_adjoint_carrier) — or None where the configuration does not carry the DC seed as a scalar."""
+        gcar, gt0 = np.zeros(B, dtype=np.complex128), np.zeros(B, dtype=np.complex128)
+        r = self.lib.bdof_adjoint_carrier(self.h, int(B), _hp(gcar), _hp(gt0))
+        if r < 0:
+            self.ctx.check(r)
+        return (gcar, gt0) if r == 1 else None
 
     def grad_batch_to_host(self, B):
         """Gradient w.r.t. the rotated object batch: (g_delta, g_beta), each (B, Y, X, S)."""

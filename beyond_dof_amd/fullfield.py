@@ -23,7 +23,7 @@ import numpy as np
 from . import h5io, tiffio, util
 from .comm import get_comm, minibatch_schedule
 from .misc import create_summary
-from .engine import check_poisson_path, check_binning_path
+from .engine import check_poisson_path, check_binning_path, check_weights_path, read_detector_weights
 from .solver import FullfieldSolver
 from .util import print_flush
 
@@ -61,7 +61,8 @@ def reconstruct_fullfield(fname, theta_st=0, theta_end=PI, n_epochs='auto', crit
                           multiscale_level=1, n_epoch_final_pass=None, initial_guess=None, n_batch_per_update=5,
                           dynamic_rate=True, probe_type='plane', probe_initial=None, probe_learning_rate=1e-3,
                           pupil_function=None, theta_downsample=None, forward_algorithm='fresnel', random_theta=True,
-                          object_type='normal', kernel_size=17, debug=False, loss_type='lsq', poisson_multiplier=2e6, slice_binning=1, **kwargs):
+                          object_type='normal', kernel_size=17, debug=False, loss_type='lsq', poisson_multiplier=2e6, slice_binning=1,
+                          detector_weights=None, **kwargs):
     """Reconstruct a beyond-depth-of-focus object from full-field projections (see the module docstring and
     cnn_propagator/fullfield.py:28-77 for the parameters).  Returns (obj_delta, obj_beta) of the finest level."""
     t_zero = time.time()
@@ -83,6 +84,10 @@ def reconstruct_fullfield(fname, theta_st=0, theta_end=PI, n_epochs='auto', crit
     # tensorflow_recon/ptychography.py, as its deviance (include/bdof.h, bdof_set_loss), with poisson_multiplier photons per unit
     # intensity.  Near the fit it is ~ 2 poisson_multiplier times the least-squares term: rescale alpha_d / alpha_b / gamma with it.
     check_poisson_path(loss_type, poisson_multiplier, propagator)
+    # detector_weights: one (Y, X) plane w >= 0 shared by every projection — 0 for dead or hot pixels and module gaps — as an array or
+    # as the name of a dataset of the data file ('exchange/weights').  L = sum(w l) / (number of pixels), and a pixel with w = 0
+    # takes no part whatever the file holds there (MultisliceEngine.set_detector_weights).  Transfer-function propagator only.
+    check_weights_path(detector_weights, propagator)
     # slice_binning=b: one propagation step per b voxel slices (include/bdof.h, bdof_set_slice_binning) — a step only has to stay
     # below the depth of focus.  Transfer-function propagator, lookup-table rotation and float32 sweeps; every multiscale
     # level's depth must divide by b.
@@ -98,6 +103,7 @@ def reconstruct_fullfield(fname, theta_st=0, theta_end=PI, n_epochs='auto', crit
     t0 = time.time()
     prj_0 = np.asarray(h5io.read_dataset(os.path.join(save_path, fname))).astype('complex64')
     theta = -np.linspace(theta_st, theta_end, prj_0.shape[0], dtype='float32')
+    weights_0 = read_detector_weights(detector_weights, os.path.join(save_path, fname), prj_0.shape[-2:])
     if theta_downsample is not None:
         prj_0 = prj_0[::theta_downsample]
         theta = theta[::theta_downsample]
@@ -130,6 +136,7 @@ def reconstruct_fullfield(fname, theta_st=0, theta_end=PI, n_epochs='auto', crit
         print_flush('Multiscale downsampling level: {}'.format(ds_level), 0, rank)
         prj = prj_0[:, ::ds_level, ::ds_level] if ds_level > 1 else prj_0
         dim_y, dim_x = prj.shape[-2:]
+        weights = weights_0 if weights_0 is None or ds_level == 1 else weights_0[::ds_level, ::ds_level]      # strided as the data are
         if minibatch_size is None:
             minibatch_size = n_theta
         if n_epochs_mask_release is None:
@@ -194,7 +201,8 @@ def reconstruct_fullfield(fname, theta_st=0, theta_end=PI, n_epochs='auto', crit
                                  comm=comm, device=comm.local_rank, coord_ls=coord_ls, propagator=propagator, kernel_size=kernel_size,
                                  rotation=rotation, theta=theta, adjoint64={'float32': None, 'float64': True, 'first-step': 'first'}[adjoint_precision],
                                  detector_kernel=kwargs.get('detector_kernel', 'TF'),   # 'IR' / 'auto': np_funcs.py:51-61
-                                 loss_type=loss_type, poisson_multiplier=poisson_multiplier, slice_binning=slice_binning)
+                                 loss_type=loss_type, poisson_multiplier=poisson_multiplier, slice_binning=slice_binning,
+                                 detector_weights=weights)
         solver.set_volume(obj_delta, obj_beta)
         solver.set_mask(mask)
         solver.set_measurements(np.abs(prj))

@@ -263,52 +263,79 @@ def _object_header(messages):
 
 def write_dataset(path, name, array):
     """Write `array` (float32/float64/complex64/complex128) as the only dataset `name` ('group/data')."""
-    array = np.ascontiguousarray(array)
-    parts = name.strip('/').split('/')
-    if len(parts) != 2:
-        raise ValueError("name must look like 'exchange/data'")
-    gname, dname = parts
+    write_datasets(path, {name: array})
+
+
+def write_datasets(path, arrays):
+    """Write the arrays of {'group/name': array} (float32/float64/complex64/complex128; one group, at most 8 members — for
+    instance 'exchange/data' and the detector weights 'exchange/weights') as the datasets of one file.  Every object header comes
+    before the first array's data, where the reader looks for them."""
     LEAF_K, INT_K = 4, 16
+    names = sorted(arrays)          # a symbol table node lists its members in the order of their names
+    parts = [n.strip('/').split('/') for n in names]
+    if not names or any(len(q) != 2 for q in parts):
+        raise ValueError("names must look like 'exchange/data'")
+    if len(set(q[0] for q in parts)) != 1 or len(names) > 2 * LEAF_K:
+        raise ValueError('the datasets of a file share one group, at most {} of them'.format(2 * LEAF_K))
+    gname = parts[0][0]
+    dnames = [q[1] for q in parts]
+    data = [np.ascontiguousarray(arrays[n]) for n in names]
     btree_size = 24 + (2 * INT_K + 1) * 8 + 2 * INT_K * 8
     snod_size = 8 + 2 * LEAF_K * 40
-    heap_data_size = 88
 
-    def group_blocks(ohdr_addr, child_name, child_ohdr):
-        """object header + B-tree + heap + SNOD of a group with one member; returns (bytes, end address)."""
+    def group_blocks(ohdr_addr, child_names, child_ohdrs):
+        """object header + B-tree + heap + SNOD of a group with these members; returns (bytes, end address)."""
+        heap_names, offs = b'\0' * 8, []
+        for nm in child_names:
+            offs.append(len(heap_names))
+            heap_names += (nm.encode() + b'\0').ljust(((len(nm) + 1 + 7) // 8) * 8, b'\0')
+        free_off = len(heap_names)
+        heap_data_size = max(88, free_off + 16)
         ohdr = _object_header([(0x0011, b'\0' * 16)])          # patched below
         bt = ohdr_addr + len(ohdr)
         hp = bt + btree_size
         hd = hp + 32
         sn = hd + heap_data_size
         ohdr = _object_header([(0x0011, struct.pack('<QQ', bt, hp))])
-        name_off = 8
-        heap_data = (b'\0' * 8 + child_name.encode() + b'\0').ljust(heap_data_size, b'\0')
-        free_off = 8 + ((len(child_name) + 1 + 7) // 8) * 8
+        heap_data = heap_names.ljust(heap_data_size, b'\0')
         heap_data = heap_data[:free_off] + struct.pack('<QQ', 1, heap_data_size - free_off) + heap_data[free_off + 16:]
-        tree = b'TREE' + struct.pack('<BBHQQ', 0, 0, 1, _UNDEF, _UNDEF) + struct.pack('<QQQ', 0, sn, name_off)
+        tree = b'TREE' + struct.pack('<BBHQQ', 0, 0, 1, _UNDEF, _UNDEF) + struct.pack('<QQQ', 0, sn, offs[-1])
         tree = tree.ljust(btree_size, b'\0')
         heap = b'HEAP' + struct.pack('<B3xQQQ', 0, heap_data_size, free_off, hd)
-        snod = (b'SNOD' + struct.pack('<BxH', 1, 1) + struct.pack('<QQII16x', name_off, child_ohdr, 0, 0)).ljust(snod_size, b'\0')
-        return ohdr, bt, hp, ohdr + tree + heap + heap_data + snod, sn + snod_size
+        snod = b'SNOD' + struct.pack('<BxH', 1, len(child_names))
+        for off, child in zip(offs, child_ohdrs):
+            snod += struct.pack('<QQII16x', off, child, 0, 0)
+        return ohdr, bt, hp, ohdr + tree + heap + heap_data + snod.ljust(snod_size, b'\0'), sn + snod_size
+
+    def dataset_msgs(array, data_addr):
+        dspace = struct.pack('<BBB5x', 1, array.ndim, 0) + struct.pack('<{}Q'.format(array.ndim), *array.shape)
+        fill = struct.pack('<BBBB', 2, 2, 2, 0)
+        return [(0x0001, dspace), (0x0003, _dtype_message(array.dtype)), (0x0005, fill), (0x0008, struct.pack('<BBQQ', 3, 1, data_addr, array.nbytes))]
 
     root_addr = 96
     # two-pass: sizes do not depend on addresses, so lay out with dummy child addresses first
-    _, _, _, blob, g_addr = group_blocks(root_addr, gname, 0)
-    _, _, _, gblob, d_addr = group_blocks(g_addr, dname, 0)
-    dspace = struct.pack('<BBB5x', 1, array.ndim, 0) + struct.pack('<{}Q'.format(array.ndim), *array.shape)
-    fill = struct.pack('<BBBB', 2, 2, 2, 0)
-    msgs = [(0x0001, dspace), (0x0003, _dtype_message(array.dtype)), (0x0005, fill), (0x0008, b'\0' * 18)]
-    data_addr = d_addr + len(_object_header(msgs))
-    data_addr += -data_addr % 8
-    msgs[3] = (0x0008, struct.pack('<BBQQ', 3, 1, data_addr, array.nbytes))
-    dhdr = _object_header(msgs).ljust(data_addr - d_addr, b'\0')
-    rohdr, rbt, rhp, blob, _ = group_blocks(root_addr, gname, g_addr)
-    _, _, _, gblob, _ = group_blocks(g_addr, dname, d_addr)
-    eof = data_addr + array.nbytes
+    _, _, _, blob, g_addr = group_blocks(root_addr, [gname], [0])
+    _, _, _, gblob, addr = group_blocks(g_addr, dnames, [0] * len(dnames))
+    d_addrs = []
+    for a in data:
+        d_addrs.append(addr)
+        addr += len(_object_header(dataset_msgs(a, 0)))
+        addr += -addr % 8
+    data_addrs = []
+    for a in data:
+        data_addrs.append(addr)
+        addr += a.nbytes
+        addr += -addr % 8
+    eof = data_addrs[-1] + data[-1].nbytes
+    ends = d_addrs[1:] + [data_addrs[0]]
+    dhdrs = b''.join(_object_header(dataset_msgs(a, da)).ljust(end - d, b'\0') for a, da, d, end in zip(data, data_addrs, d_addrs, ends))
+    rohdr, rbt, rhp, blob, _ = group_blocks(root_addr, [gname], [g_addr])
+    _, _, _, gblob, _ = group_blocks(g_addr, dnames, d_addrs)
     sb = _SIG + struct.pack('<BBBxBBBxHHI', 0, 0, 0, 0, 8, 8, LEAF_K, INT_K, 0)
     sb += struct.pack('<QQQQ', 0, _UNDEF, eof, _UNDEF)
     sb += struct.pack('<QQII', 0, root_addr, 1, 0) + struct.pack('<QQ', rbt, rhp)
     assert len(sb) == root_addr
     with open(path, 'wb') as f:
-        f.write(sb + blob + gblob + dhdr)
-        f.write(array.tobytes())
+        f.write(sb + blob + gblob + dhdrs)
+        for a, da, nxt in zip(data, data_addrs, data_addrs[1:] + [eof]):
+            f.write(a.tobytes().ljust(nxt - da, b'\0'))

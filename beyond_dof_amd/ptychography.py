@@ -17,7 +17,7 @@ from . import h5io, tiffio, util
 from .comm import get_comm
 from .fullfield import create_probe_initial_guess, upsample_2x
 from .misc import create_summary
-from .engine import check_poisson_path, check_binning_path
+from .engine import check_poisson_path, check_binning_path, check_weights_path, read_detector_weights
 from .solver import PtychoSolver
 from ._lib import BdofError
 from .util import print_flush, split_tasks
@@ -69,7 +69,8 @@ def reconstruct_ptychography(fname, probe_pos, probe_size, obj_size, theta_st=0,
                              dynamic_rate=True, probe_type='gaussian', probe_initial=None, probe_learning_rate=1e-3,
                              pupil_function=None, probe_circ_mask=0.9, finite_support_mask=None,
                              forward_algorithm='fresnel', dynamic_dropping=True, dropping_threshold=8e-5,
-                             n_dp_batch=20, object_type='normal', loss_type='lsq', poisson_multiplier=2e6, slice_binning=1, **kwargs):
+                             n_dp_batch=20, object_type='normal', loss_type='lsq', poisson_multiplier=2e6, slice_binning=1,
+                             detector_weights=None, **kwargs):
     t_zero = time.time()
     comm = kwargs.get('comm') or get_comm()
     size, rank = comm.size, comm.rank
@@ -92,6 +93,11 @@ def reconstruct_ptychography(fname, probe_pos, probe_size, obj_size, theta_st=0,
     # keyword, as its deviance (include/bdof.h, bdof_set_loss).  The bare likelihood is unbounded where the model intensity goes
     # to zero under a measured count, which far-field data with noise has: there is no epsilon.
     check_poisson_path(loss_type, poisson_multiplier, propagator)
+    # detector_weights: one (py, px) plane w >= 0 shared by every diffraction pattern, fftshifted as the patterns are — 0 behind the
+    # beamstop, for dead or hot pixels and module gaps — as an array or as the name of a dataset of the data file
+    # ('exchange/weights').  L = sum(w l) / (number of pixels), and a pixel with w = 0 takes no part whatever the file holds there
+    # (MultisliceEngine.set_detector_weights).  Transfer-function propagator only.
+    check_weights_path(detector_weights, propagator)
     # slice_binning=b: one propagation step per b voxel slices (include/bdof.h, bdof_set_slice_binning).  Transfer-function
     # propagator and float32 sweeps only — the float64 twin of 'first-step' does not carry it, so the DEFAULT becomes 'float32'
     # and an explicit other choice raises; every multiscale level's depth must divide by b.
@@ -106,6 +112,7 @@ def reconstruct_ptychography(fname, probe_pos, probe_size, obj_size, theta_st=0,
     f = h5io.File(os.path.join(save_path, fname))
     prj = f['exchange/data']                               # kept open, read per minibatch (ptychography.py:91-92,295)
     n_theta = prj.shape[0]
+    weights_0 = read_detector_weights(detector_weights, os.path.join(save_path, fname), prj.shape[-2:])
     prj_theta_ind = np.arange(n_theta, dtype=int)
     if theta_downsample is not None:
         prj_theta_ind = prj_theta_ind[::theta_downsample]
@@ -131,6 +138,7 @@ def reconstruct_ptychography(fname, probe_pos, probe_size, obj_size, theta_st=0,
         this_obj_size = [int(x / ds_level) for x in obj_size] if ds_level > 1 else list(obj_size)
         this_probe_size = [int(x / ds_level) for x in probe_size] if ds_level > 1 else list(probe_size)
         this_probe_pos = (probe_pos / ds_level).astype(int) if ds_level > 1 else probe_pos
+        weights = weights_0 if weights_0 is None or ds_level == 1 else weights_0[::ds_level, ::ds_level]      # strided as the data are
         if minibatch_size is None:
             minibatch_size = n_pos
 
@@ -177,7 +185,8 @@ def reconstruct_ptychography(fname, probe_pos, probe_size, obj_size, theta_st=0,
                                        psize_cm * ds_level, probe_real, probe_imag, variant=variant, comm=comm, device=comm.local_rank,
                                        coord_ls=coord_ls, propagator=propagator, kernel_size=kwargs.get('kernel_size', 17),
                                        adjoint64={'float32': None, 'float64': True, 'first-step': 'first'}[prec],
-                                       loss_type=loss_type, poisson_multiplier=poisson_multiplier, slice_binning=slice_binning)
+                                       loss_type=loss_type, poisson_multiplier=poisson_multiplier, slice_binning=slice_binning,
+                                       detector_weights=weights)
         # the DEFAULT's float64 path (first minibatch of an epoch) is an accuracy refinement with buffers of its own (wave + tape in
         # complex128, allocated when the solver is built): where they do not fit beside the engine's the run goes on in float32,
         # SAYS so and records it (summary.txt: adjoint_precision_effective); an explicit request fails.  The retry runs outside the

@@ -24,7 +24,7 @@ from . import _lib
 from ._lib import DeviceBuffer
 from . import util
 from .comm import PseudoComm
-from .engine import MultisliceEngine, RESIDENT_SIZES, check_poisson_path, check_binning_path
+from .engine import MultisliceEngine, RESIDENT_SIZES, check_poisson_path, check_binning_path, check_weights_path
 
 
 class _VolumeSolver(object):
@@ -383,8 +383,10 @@ class FullfieldSolver(_VolumeSolver):
     def __init__(self, dim_y, dim_x, dim_z, n_theta, minibatch_size, energy_ev, psize_cm, free_prop_cm=None,
                  probe_real=None, probe_imag=None, variant='numpy_skip_last', comm=None, device=0, stream=None,
                  coord_ls=None, propagator='fft', kernel_size=17, recompute=False, rotation='nearest', theta=None, adjoint64=None,
-                 detector_kernel='TF', loss_type='lsq', poisson_multiplier=2e6, slice_binning=1):
+                 detector_kernel='TF', loss_type='lsq', poisson_multiplier=2e6, slice_binning=1, detector_weights=None):
         """loss_type / poisson_multiplier: the data term (MultisliceEngine.set_loss; 'poisson' with propagator='fft' only).
+        detector_weights: one (Y, X) plane of weights >= 0 for every projection (MultisliceEngine.set_detector_weights; 0: the
+        pixel takes no part), set before any measurement is bound; propagator='fft' only.
         slice_binning: voxel slices per propagation step (MultisliceEngine); > 1 with propagator='fft', rotation='nearest' and
         no adjoint64 only.
         propagator='fft': the transfer-function step of np_funcs.py (north-star path); 'conv': the truncated real-space
@@ -394,6 +396,7 @@ class FullfieldSolver(_VolumeSolver):
         `theta` (radians, one per projection): the minibatch's rotated objects are materialised per step
         (bdof_rotate_bilinear), its adjoint is a gather (bdof_rotate_bilinear_adjoint)."""
         check_poisson_path(loss_type, poisson_multiplier, propagator)
+        check_weights_path(detector_weights, propagator)
         check_binning_path(slice_binning, propagator, 'float64' if adjoint64 else None, rotation if rotation == 'bilinear' else 'nearest')
         self.conv = propagator == 'conv'
         self.bilinear = rotation == 'bilinear'
@@ -420,6 +423,7 @@ class FullfieldSolver(_VolumeSolver):
         self.eng.set_adjoint_fusion(True)   # ... and the fused adjoint sweep behind it (MEASUREMENTS.md: the step-time criterion)
         self.eng.set_loss(loss_type, poisson_multiplier)
         self.eng.set_physics(energy_ev, psize_cm, free_prop_cm, variant=variant, detector_kernel=detector_kernel)
+        self.eng.set_detector_weights(detector_weights)
         if self.conv:
             self.eng.set_conv(energy_ev, psize_cm, kernel_size)
         if probe_real is None:
@@ -587,13 +591,16 @@ class PtychoSolver(_VolumeSolver):
 
     def __init__(self, obj_size, probe_size, probe_pos, n_theta, minibatch_size, energy_ev, psize_cm, probe_real, probe_imag,
                  variant='numpy_skip_last', comm=None, device=0, stream=None, coord_ls=None, propagator='fft', kernel_size=17,
-                 adjoint64=None, engine=None, loss_type='lsq', poisson_multiplier=2e6, slice_binning=1):
+                 adjoint64=None, engine=None, loss_type='lsq', poisson_multiplier=2e6, slice_binning=1, detector_weights=None):
         """loss_type / poisson_multiplier: the data term (MultisliceEngine.set_loss; 'poisson' with propagator='fft' only).
+        detector_weights: one (py, px) plane of weights >= 0 for every diffraction pattern, fftshifted as the patterns are
+        (MultisliceEngine.set_detector_weights; 0: dead pixel, beamstop), set before any measurement is bound; propagator='fft' only.
         slice_binning: voxel slices per propagation step (MultisliceEngine); > 1 with propagator='fft' and no adjoint64 only, and
         engine=None then takes 'auto' (the resident engine does not carry it).
         engine: None picks the LDS-resident engine for small square probes (below) and the automatic choice otherwise; 'auto',
         'generic', 'streaming' or 'resident' go to MultisliceEngine(engine=...) as they are."""
         check_poisson_path(loss_type, poisson_multiplier, propagator)
+        check_weights_path(detector_weights, propagator)
         check_binning_path(slice_binning, propagator, 'float64' if adjoint64 else None)
         self.conv = propagator == 'conv'
         self.dim_y, self.dim_x, self.dim_z = [int(s) for s in obj_size]
@@ -611,6 +618,7 @@ class PtychoSolver(_VolumeSolver):
         self.ctx = self.eng.ctx
         self.eng.set_loss(loss_type, poisson_multiplier)
         self.eng.set_physics(energy_ev, psize_cm, 'inf', variant=variant)   # free_prop_cm='inf', ptychography.py:76
+        self.eng.set_detector_weights(detector_weights)
         if self.conv:
             self.eng.set_conv(energy_ev, psize_cm, kernel_size)
         self.eng.set_probe(probe_real, probe_imag)

@@ -298,6 +298,27 @@ int bdof_set_meas_mode(bdof_ctx* ctx, int mode);
 #define BDOF_LOSS_POISSON 1
 int bdof_set_loss(bdof_ctx* ctx, int kind, double multiplier);
 
+/* Detector weights: one plane w >= 0 (finite, float32) shared by every measurement of the run — a property of the detector: dead
+ * and hot pixels, a beamstop, module gaps (w = 0), or a per-pixel confidence.  With l the per-pixel term of the data term set by
+ * bdof_set_loss (least squares: (|d| - m)^2; Poisson: the deviance above) and B wavefields of NX NY pixels
+ *     L    = sum(w l) / (B NX NY)          — the divisor stays the pixel count, NOT sum(w)
+ *     G(d) = w (the unweighted seed)
+ * for bdof_loss_grad (every engine) and bdof_loss_grad_tf_f64; the far field's float64 DC bin carries w as well (a beamstop on it
+ * leaves exactly no adjoint carrier).  w == 1 everywhere gives the results of no weights bit for bit, and so does clearing them.
+ * w: HOST pointer to [NX][NY] floats in the index order of ONE wavefield of `meas` — real-space detectors [x][y], far field the
+ * un-shifted [ky][kx]; the library copies it into a buffer the ctx owns.  NULL clears the weights; bdof_configure clears them too
+ * (the shape may change), and before bdof_configure the call is a state error.
+ * A pixel with w = 0 takes no part only if its amplitude is finite (0 NaN is NaN): the caller zeroes `meas` where w == 0 before
+ * it uploads (MultisliceEngine.meas_layout does).
+ * With weights set, bdof_loss_grad_conv, bdof_loss_grad_conv_f64 and bdof_field_loss_seed fail (bdof_last_error). */
+int bdof_set_detector_weights(bdof_ctx* ctx, const float* w);
+
+/* The adjoint carrier the last bdof_loss_grad left (far-field detector under a plane-wave probe on the streaming and generic
+ * engines): per wavefield the float64 seed of the DC bin, gcar[b], and conj(a_end) gcar[b], gt0[b] — HOST arrays of B complex
+ * doubles (re, im).  Returns 1 and fills them where the configuration carries the DC seed that way, 0 (nothing written) where it
+ * does not, < 0 on an error.  For checks: a detector weight of 0 on the DC bin (a beamstop) leaves both exactly 0. */
+int bdof_adjoint_carrier(bdof_ctx* ctx, int B, double* gcar, double* gt0);
+
 /* Real-space truncated-kernel propagator: replaces multislice_propagate_cnn (cnn_propagator/propagation.py:18-133), the
  * forward model cnn_propagator/fullfield.py:87,102 and ptychography.py:74 literally call.  The cropped kernel is separable,
  * K[p][q] = e * ky[p] * kx[q] (ky, kx: HOST complex arrays of ks taps, ks odd <= 33); ksum = sum of K (the factor of the
