@@ -101,6 +101,14 @@ struct Workspace {
     const cf* gpsi_src = nullptr;                // borrowed from this workspace: where the last bdof_loss_grad left it (gpsi0, or the generic engine's field)
     DevBuf<double> partial, loss_dev;
     DevBuf<float> wgt;                           // [NX][NY] detector weights in the order of one wavefield of meas; none: no weights (bdof_set_detector_weights)
+    // Detector planes (bdof_set_detector_planes): D > 1 near-field planes behind the exit wave; 1 (after every bdof_configure and
+    // bdof_set_physics): the one plane of bdof_set_physics, on bufA / bufB alone
+    int planes = 1;
+    DevBuf<cf> hdet_pl, hcomb_pl;                // [D][ky][kx] tables of the planes: the detector step's, and under tf_all combined with the slice step's
+    std::vector<std::complex<double>> hdet00_pl; // [D] their DC values
+    // the 2 D detector / seed fields per wavefield.  Streaming engine: [Bmax][D][NX][NY] each, det_pl the detector fields in L1
+    // order and seed_pl the seeds in L2 order.  Generic engine: det_pl alone, [D][Bmax][NX][NY] real-space fields.
+    DevBuf<cf> det_pl, seed_pl;
     // real-space truncated-kernel propagator (bdof_set_conv)
     bool have_conv = false;
     DevBuf<ConvTaps> taps_dev;
@@ -252,6 +260,16 @@ static int need_unweighted(bdof_ctx* c, const char* who) {
 static int need_unbinned(bdof_ctx* c, const char* who) {
     return !c || c->bin == 1 ? 0 : fail(c, BDOF_ERR_STATE, std::string(who) + " does not carry slice binning: it would run the unbinned model (bdof_set_slice_binning)");
 }
+// the entry points that know one detector plane only (bdof_set_detector_planes names them)
+static int need_one_plane(bdof_ctx* c, const char* who) {
+    return !c || c->planes == 1 ? 0 : fail(c, BDOF_ERR_STATE, std::string(who) + " does not carry detector planes: bdof_set_detector_planes(ctx, 1, NULL, NULL) first");
+}
+// back to the one plane of bdof_set_physics: tables and the planes' fields go
+static void drop_planes(bdof_ctx* c) {
+    c->planes = 1;
+    c->hdet_pl.reset(); c->hcomb_pl.reset(); c->det_pl.reset(); c->seed_pl.reset();
+    c->hdet00_pl.clear();
+}
 // propagation steps of a sweep: the voxel depth over the slice binning
 static StepIndex steps(const bdof_ctx* c) { return StepIndex{c->S, c->bin}; }
 static int n_steps(const bdof_ctx* c) { return steps(c).n(); }
@@ -278,14 +296,15 @@ static cf carrier_at(const bdof_ctx* c, int z) { return cfl(carrier_z(c, z)); }
 static cf cshift_at(const bdof_ctx* c, int z) { return cfl(carrier_z(c, z) * c->cbm1); }                  // a_z (cbar - 1)
 static cf carrier_phi_at(const bdof_ctx* c, int z) { return cfl(carrier_z(c, z) * (1.0 + c->cbm1)); }      // constant part of phi_z
 // constant part of the detector wave (real-space detectors) / of the wave whose fft2 is the far field
-static std::complex<double> carrier_end(const bdof_ctx* c) {
+// plane: which of the detector planes (bdof_set_detector_planes; 0 with one plane)
+static std::complex<double> carrier_end(const bdof_ctx* c, int plane = 0) {
     std::complex<double> a = carrier_z(c, n_steps(c) - 1) * (1.0 + c->cbm1);
     if (c->det_mode != BDOF_DET_FAR && c->variant == BDOF_VARIANT_TF_ALL) a *= c->h00;
-    if (c->det_mode == BDOF_DET_NEAR) a *= c->hdet00;
+    if (c->det_mode == BDOF_DET_NEAR) a *= c->planes > 1 ? c->hdet00_pl[plane] : c->hdet00;
     return a;
 }
-static std::complex<double> carrier_det(const bdof_ctx* c) {
-    std::complex<double> a = carrier_end(c);
+static std::complex<double> carrier_det(const bdof_ctx* c, int plane = 0) {
+    std::complex<double> a = carrier_end(c, plane);
     if (c->det_mode == BDOF_DET_FAR) a *= (double)c->NX * (double)c->NY;
     return a;
 }
@@ -319,16 +338,17 @@ static DetPlane wave_plane(const bdof_ctx* c, std::complex<double> carrier, cons
 }
 // The detector plane and data term of the transfer-function engines for a batch of B wavefields, with the adjoint carriers of
 // its sub-batch g; pfield: the carrier field at the detector in the layout of the kernel that gets the plane, or null.
-static DetPlane det_plane(const bdof_ctx* c, const Group& g, int B, const cf* pfield) {
-    DetPlane d = wave_plane(c, carrier_det(c), pfield);
-    d.a_end = d2(carrier_end(c));
+// plane: which of the ctx's detector planes.  They share the data term: its mean runs over the B * planes frames of the batch.
+static DetPlane det_plane(const bdof_ctx* c, const Group& g, int B, const cf* pfield, int plane = 0) {
+    DetPlane d = wave_plane(c, carrier_det(c, plane), pfield);
+    d.a_end = d2(carrier_end(c, plane));
     d.meas_dev = c->meas_dev;
     if (c->meas_dev) {
         // bdof_set_meas_mode(1): the host subtracted |a_0| from the amplitudes; the detector carrier has modulus |a_0| |cbar|^S
         d.meas_ref = std::abs(c->a0);
-        d.dref = (float)(std::abs(carrier_end(c)) - std::abs(c->a0));
+        d.dref = (float)(std::abs(carrier_end(c, plane)) - std::abs(c->a0));
     }
-    d.seed_scale = 2.f / ((float)B * (float)c->NX * (float)c->NY);
+    d.seed_scale = 2.f / ((float)(B * c->planes) * (float)c->NX * (float)c->NY);
     d.mu = c->loss_mu;
     d.wgt = c->wgt;
     // Set whenever the ctx carries an adjoint carrier, whatever the launch does: the kernels write them only where they fit
@@ -594,6 +614,25 @@ static void launch_row_prop(bdof_ctx* c, const Group& g, const cf* in, cf* out, 
     });
 }
 
+// Detector planes (bdof_set_detector_planes).  The planes' fields of sub-batch g: D fields per wavefield.
+template <class T> static T* sub_planes(const bdof_ctx* c, const Group& g, T* p) { return p ? p + (size_t)g.b0 * c->planes * c->NX * c->NY : p; }
+// the tables the streaming engine steps to the planes with: from R phi_{S-1}, so under tf_all combined with the slice step's
+static const cf* plane_tables(const bdof_ctx* c) { return c->variant == BDOF_VARIANT_TF_ALL ? c->hcomb_pl : c->hdet_pl; }
+// fan-out: L2 lines of bufA -> det_pl (L1, one field per plane); fan-in: the planes' seeds in seed_pl (L2) -> g_hat(phi_{S-1}) in
+// bufB (L1).  key: as launch_row_prop's — the last step's, which the one plane's detector step takes too.
+static void launch_row_planes(bdof_ctx* c, const Group& g, bool gather, int key, int cls) {
+    ProfScope ps(c, cls, g.st, true);
+    const unsigned tick = (unsigned)key;
+    RowPlanesArgs a{gather ? sub_planes<const cf>(c, g, c->seed_pl) : sub_field<const cf>(c, g, c->bufA),
+                    gather ? sub_field<cf>(c, g, c->bufB) : sub_planes<cf>(c, g, c->det_pl), plane_tables(c), g.B, c->NY, c->planes,
+                    tw_of(c, c->twX, c->NX, tick)};
+    sq_of(c, tick, a.sq);
+    DISPATCH_N(c->NX, {
+        if (gather) BDOF_LAUNCH(ps, (k_row_prop_gather<N_>), dim3(rows_grid<N_>(c, g.B, c->NY)), dim3(BDOF_THREADS), 0, g.st, a);
+        else BDOF_LAUNCH(ps, (k_row_prop_fan<N_>), dim3(rows_grid<N_>(c, g.B, c->NY)), dim3(BDOF_THREADS), 0, g.st, a);
+    });
+}
+
 // ---- the fused forward sweep (k_slice_y / k_slice_x, bdof_kernels.h) ------------------------------------------------------------
 // Which sweep bdof_loss_grad runs: 1 = the fused forward sweep, 0 = the two-kernel sweep.  Eligible: the streaming engine with the
 // tape, one voxel slice per step, a scalar carrier, a real-space or no detector, no window offsets, no probe gradient, a separable
@@ -713,6 +752,28 @@ static int launch_loss_real(bdof_ctx* c, const Group& g, const DetPlane& det, co
     return grid;
 }
 
+// Plane j of the detector planes on the L1 rows of det_pl: the real-space detector once per plane, each launch with its own
+// DetPlane.  Frames (meas, out_wave) and fields are [B][D][NX][NY], so a launch strides D fields from wavefield to wavefield
+// (k_row_loss<PL>); with meas the seed goes transposed to seed_pl.
+static int launch_loss_plane(bdof_ctx* c, const Group& g, const DetPlane& det, int j, cf* out_wave, const float* meas, int part = 0) {
+    ProfScope ps(c, BDOF_K_LOSS, g.st);
+    const size_t pl = (size_t)c->NX * c->NY;
+    LossPlaneArgs a;
+    static_cast<LossArgs&>(a) = loss_args(c, g, det, nullptr, nullptr, nullptr, nullptr, 1.f, 1.f, part);
+    a.in = sub_planes<const cf>(c, g, c->det_pl) + j * pl;
+    a.out_hyb = meas ? sub_planes<cf>(c, g, c->seed_pl) + j * pl : nullptr;
+    a.out_wave = out_wave ? sub_planes(c, g, out_wave) + j * pl : nullptr;
+    a.meas = meas ? sub_planes(c, g, meas) + j * pl : nullptr;
+    a.fstride = c->planes;
+    a.R = c->NX;
+    a.twiddle = c->twY;
+    int grid = 0;
+    DISPATCH_N(c->NY, grid = rows_grid<N_>(c, g.B, c->NX); with_bool(meas && loss_is_poisson(c), [&](auto PSN) {
+        with_bool(meas && det.wgt, [&](auto WGT) { hipLaunchKernelGGL((k_row_loss<N_, false, true, PSN, WGT, true>), dim3(grid), dim3(BDOF_THREADS), 0, g.st, a); });
+    }));
+    return grid;
+}
+
 // Far-field detector on L2 rows; the seed goes back transposed into L1.
 static int launch_loss_far(bdof_ctx* c, const Group& g, const DetPlane& det, const cf* in, cf* out_hyb, cf* out_wave, const float* meas,
                            float in_scale, float out_scale, int part = 0) {
@@ -733,6 +794,7 @@ static int launch_loss_far(bdof_ctx* c, const Group& g, const DetPlane& det, con
 //   DET_NONE, numpy_skip_last : bufA = R phi_{S-1} in L1 order (plain store), un-normalised (scale 1 / NY)
 //   DET_NONE, tf_all          : bufB = psi_hat_S (L1), made with the slice step's table
 //   DET_NEAR                  : bufB = d_hat (L1)    (tf_all: one step with the combined transfer function)
+//   DET_NEAR, D > 1 planes    : det_pl = d_hat_j (L1), [B][D] fields (launch_row_planes; bdof_set_detector_planes)
 //   DET_FAR                   : bufA = R phi_{S-1} in L2 order, un-normalised (|fft2| is unchanged by the
 //                               unit-modulus transfer function, so tf_all needs no extra step here)
 struct DetRoute {
@@ -782,7 +844,8 @@ static void forward_sweep(bdof_ctx* c, const Split& split, int tape_mode, bool f
             } else {
                 launch_row_fwd(c, g, z, in, c->bufA, dr.far || dr.h, phi);
                 // (fused route: the step's few remaining transfer-function launches outside the adjoint sweep are filed with the detector)
-                if (dr.h) launch_row_prop(c, g, c->bufA, c->bufB, dr.h, 1.f, 0, z, fused ? BDOF_K_LOSS : BDOF_K_COL_PROP);
+                if (c->planes > 1) launch_row_planes(c, g, false, z, fused ? BDOF_K_LOSS : BDOF_K_COL_PROP);      // the fan-out to det_pl
+                else if (dr.h) launch_row_prop(c, g, c->bufA, c->bufB, dr.h, 1.f, 0, z, fused ? BDOF_K_LOSS : BDOF_K_COL_PROP);
             }
         }
     }
@@ -979,7 +1042,9 @@ static int generic_forward_sweep(bdof_ctx* c, int B, bool tape, rocfft_plan pf, 
             a *= c->h00;
         }
     }
-    if (c->det_mode == BDOF_DET_NEAR) {
+    if (c->det_mode == BDOF_DET_NEAR && c->planes > 1) {
+        // detector planes: the sweep ends in front of the detector step (generic_to_planes takes it from here)
+    } else if (c->det_mode == BDOF_DET_NEAR) {
         if ((r = generic_prop(c, B, pf, pi, c->bufA, c->hdet, 0))) return r;
         a *= c->hdet00;
     } else if (c->det_mode == BDOF_DET_FAR) {
@@ -1006,13 +1071,33 @@ static GLossArgs g_loss_args(bdof_ctx* c, int B, const DetPlane& det, cf* field,
     return la;
 }
 
+// Detector planes on the generic engine: plane j's field of the batch, [D][Bmax][NX][NY] in det_pl
+static cf* generic_plane(const bdof_ctx* c, int j) { return c->det_pl + (size_t)j * c->Bmax * c->NX * c->NY; }
+// the wave in front of the detector step (bufA) stepped to every plane: one copy and one generic_prop per plane
+static int generic_to_planes(bdof_ctx* c, int B, rocfft_plan pf, rocfft_plan pi) {
+    const size_t n = (size_t)B * c->NX * c->NY;
+    for (int j = 0; j < c->planes; ++j) {
+        HIPC(c, hipMemcpyAsync(generic_plane(c, j), c->bufA, n * sizeof(cf), hipMemcpyDeviceToDevice, c->stream));
+        if (int r = generic_prop(c, B, pf, pi, generic_plane(c, j), c->hdet_pl + (size_t)j * c->NX * c->NY, 0)) return r;
+    }
+    return 0;
+}
+
 static int generic_forward(bdof_ctx* c, int B, void* out_wave, bool keep_tape) {
     rocfft_plan pf, pi;
     int r = field_plans(c, c->NX, c->NY, B, false, &pf, &pi);
     if (r) return r;
     std::complex<double> a;
     if ((r = generic_forward_sweep(c, B, keep_tape, pf, pi, &a))) return r;
-    if (out_wave) {
+    if (out_wave && c->planes > 1) {
+        if ((r = generic_to_planes(c, B, pf, pi))) return r;
+        const size_t n = (size_t)B * c->NX * c->NY;
+        for (int j = 0; j < c->planes; ++j) {
+            GLossArgs la = g_loss_args(c, B, wave_plane(c, a * c->hdet00_pl[j]), generic_plane(c, j), (cf*)out_wave + (size_t)j * c->NX * c->NY, nullptr);
+            la.fstride = c->planes;
+            hipLaunchKernelGGL((k_g_loss<false, false, true>), dim3(g_elem_grid(c, n)), dim3(256), 0, c->stream, la);
+        }
+    } else if (out_wave) {
         const size_t n = (size_t)B * c->NX * c->NY;
         const GLossArgs la = g_loss_args(c, B, wave_plane(c, a, c->pdet), c->bufA, (cf*)out_wave, nullptr);
         hipLaunchKernelGGL(k_g_loss<false>, dim3(g_elem_grid(c, n)), dim3(256), 0, c->stream, la);
@@ -1032,7 +1117,29 @@ static int generic_loss_grad(bdof_ctx* c, int B, const float* meas, void* out_wa
     const int egrid = g_elem_grid(c, n);
     const bool f64 = c->adj64;
     if (f64 && !c->have_h64) return fail(c, BDOF_ERR_STATE, "float64 adjoint: bdof_set_physics_f64 has not been called");
-    {
+    if (c->planes > 1) {
+        // Detector planes: the data term once per plane on its own field (the carrier as the sweep's recurrence left it, times
+        // the plane's DC value), the adjoint detector step per plane, and the sum of the D results in bufA
+        if ((r = generic_to_planes(c, B, pf, pi))) return r;
+        const size_t pl = (size_t)c->NX * c->NY;
+        const int lgrid = std::min(egrid, c->npartial);
+        for (int j = 0; j < c->planes; ++j) {
+            ProfScope ps(c, BDOF_K_LOSS, c->stream);
+            DetPlane det = det_plane(c, whole(c, B), B, nullptr, j);
+            set_carrier(det, a * c->hdet00_pl[j]);
+            GLossArgs la = g_loss_args(c, B, det, generic_plane(c, j), out_wave ? (cf*)out_wave + j * pl : nullptr, meas + j * pl);
+            la.fstride = c->planes;
+            la.partial = c->partial + (size_t)2 * j * lgrid;
+            with_bool(loss_is_poisson(c), [&](auto PSN) { with_bool(det.wgt != nullptr, [&](auto WGT) {
+                hipLaunchKernelGGL((k_g_loss<PSN, WGT, true>), dim3(lgrid), dim3(256), 0, c->stream, la);
+            }); });
+        }
+        hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, c->stream, c->partial, lgrid * c->planes, 1.0 / ((double)B * c->planes * c->NX * c->NY), c->loss_dev);
+        for (int j = 0; j < c->planes; ++j) {
+            if ((r = generic_prop(c, B, pf, pi, generic_plane(c, j), c->hdet_pl + j * pl, 1))) return r;
+            hipLaunchKernelGGL(k_g_accumulate, dim3(egrid), dim3(256), 0, c->stream, c->bufA, generic_plane(c, j), n, j == 0 ? 1 : 0);
+        }
+    } else {
         ProfScope ps(c, BDOF_K_LOSS, c->stream);
         DetPlane det = det_plane(c, whole(c, B), B, c->pdet);
         set_carrier(det, a);                       // the carrier as the sweep's own recurrence left it
@@ -1042,7 +1149,8 @@ static int generic_loss_grad(bdof_ctx* c, int B, const float* meas, void* out_wa
             hipLaunchKernelGGL((k_g_loss<PSN, WGT>), dim3(egrid), dim3(256), 0, c->stream, la);
         }); });
     }
-    hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, c->stream, c->partial, egrid, 1.0 / ((double)B * c->NX * c->NY), c->loss_dev);
+    if (c->planes == 1)
+        hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, c->stream, c->partial, egrid, 1.0 / ((double)B * c->NX * c->NY), c->loss_dev);
     if (f64) {
         // float64 adjoint sweep: g64 holds the seed G(d)
         rocfft_plan pf64, pi64;
@@ -1071,7 +1179,9 @@ static int generic_loss_grad(bdof_ctx* c, int B, const float* meas, void* out_wa
     }
     // adjoint of the detector step: bufA now holds the seed G(d)
     void* buf[1] = {c->bufA};
-    if (c->det_mode == BDOF_DET_NEAR) {
+    if (c->det_mode == BDOF_DET_NEAR && c->planes > 1) {
+        // (detector planes: done above, plane by plane)
+    } else if (c->det_mode == BDOF_DET_NEAR) {
         if ((r = generic_prop(c, B, pf, pi, c->bufA, c->hdet, 1))) return r;
     } else if (c->det_mode == BDOF_DET_FAR) {
         RFC(c, rocfft_execute(pi, buf, nullptr, c->fft.info));            // F^H = unnormalised inverse
@@ -1116,7 +1226,7 @@ template <int N> static int resident_launch(bdof_ctx* c, const ResArgs& a, int g
 // batch fills a good part of the chip (measured at 64^2 / 128^2: 400 / 100 wavefields 4.6x / 1.5x faster, 25 slower);
 // sizes without a fused plan always take it (the alternative is the unfused rocFFT engine).
 static bool use_resident(const bdof_ctx* c, int B) {
-    if (!c->resident || c->recompute || c->bin > 1) return false;      // slice binning: the streaming and generic engines only
+    if (!c->resident || c->recompute || c->bin > 1 || c->planes > 1) return false;      // slice binning, detector planes: the streaming and generic engines only
     // far field + plane-wave carrier needs the adjoint carrier (AdjCarrier), which the resident kernel does not carry: the
     // streaming / generic engines take that case (plane-wave full-field at a resident-plan size)
     if (c->det_mode == BDOF_DET_FAR && !c->pstack && std::abs(c->a0) > 0.0) return false;
@@ -1432,6 +1542,10 @@ int bdof_set_physics(bdof_ctx* c, double k, const float* hs, const float* hs_det
     if (det_mode == BDOF_DET_NEAR && !hs_det) return fail(c, BDOF_ERR_ARG, "hs_det required for BDOF_DET_NEAR");
     const size_t bytes = sizeof(cf) * c->NX * c->NY;
     c->c64_tf = false; c->c64_ks = 0;     // a float64 twin handed over before (bdof_set_tf_f64 / bdof_set_conv_f64) held the previous model
+    if (c->planes > 1) {                  // detector planes belong to the physics that go: bdof_set_detector_planes follows, or there is one plane
+        HIPC(c, hipStreamSynchronize(c->stream));
+        drop_planes(c);
+    }
     HIPC(c, hipMemcpyAsync(c->hs, hs, bytes, hipMemcpyHostToDevice, c->stream));
     if (hs_det) {
         HIPC(c, hipMemcpyAsync(c->hdet, hs_det, bytes, hipMemcpyHostToDevice, c->stream));
@@ -1624,6 +1738,45 @@ int bdof_set_detector_weights(bdof_ctx* c, const float* w) {
     return 0;
 }
 
+int bdof_set_detector_planes(bdof_ctx* c, int D, const float* hs_det, const double* hdet00) {
+    if (!c) return BDOF_ERR_ARG;
+    if (int r = need_configured(c)) return r;
+    if (D < 1 || D > BDOF_MAX_PLANES) return fail(c, BDOF_ERR_ARG, "bdof_set_detector_planes: the number of detector planes must be in [1, BDOF_MAX_PLANES]");
+    HIPC(c, hipSetDevice(c->device));
+    HIPC(c, hipStreamSynchronize(c->stream));         // launches in flight may still read the tables and fields that go
+    if (D == 1 || !hs_det) { drop_planes(c); return 0; }
+    if (!hdet00) return fail(c, BDOF_ERR_ARG, "bdof_set_detector_planes: hdet00 required with the tables");
+    if (!c->have_physics) return fail(c, BDOF_ERR_STATE, "bdof_set_detector_planes comes after bdof_set_physics");
+    const char* why = c->det_mode != BDOF_DET_NEAR ? "a detector mode other than BDOF_DET_NEAR" : c->recompute ? "the tape-free adjoint (BDOF_CFG_RECOMPUTE)"
+                    : c->adj64 ? "the float64 adjoint sweep (BDOF_CFG_ADJOINT64)" : c->have_conv ? "the real-space propagator (bdof_set_conv)"
+                    : c->pstack ? "a carrier field (bdof_set_probe_stack / bdof_set_probe_field)" : c->range_car ? "range carriers (bdof_set_range_carrier)" : nullptr;
+    if (why) return fail(c, BDOF_ERR_STATE, std::string("bdof_set_detector_planes: ") + why + " does not carry detector planes");
+    drop_planes(c);
+    const size_t n = (size_t)c->NX * c->NY, fields = (size_t)c->Bmax * D * n;
+    // the combined tables of tf_all, formed as bdof_set_physics forms its one: from the float32 slice step the ctx holds
+    std::vector<float> hs(2 * n), comb(2 * n * D);
+    HIPC(c, hipMemcpy(hs.data(), c->hs, sizeof(cf) * n, hipMemcpyDeviceToHost));
+    const double nn = (double)c->NX * c->NY;
+    for (int j = 0; j < D; ++j)
+        for (size_t i = 0; i < n; ++i) {
+            const double ar = hs[2 * i], ai = hs[2 * i + 1], br = hs_det[2 * (j * n + i)], bi = hs_det[2 * (j * n + i) + 1];
+            comb[2 * (j * n + i)] = (float)((ar * br - ai * bi) * nn);
+            comb[2 * (j * n + i) + 1] = (float)((ar * bi + ai * br) * nn);
+        }
+    HIPC(c, c->hdet_pl.alloc(n * D));
+    HIPC(c, c->hcomb_pl.alloc(n * D));
+    HIPC(c, hipMemcpy(c->hdet_pl, hs_det, sizeof(cf) * n * D, hipMemcpyHostToDevice));
+    HIPC(c, hipMemcpy(c->hcomb_pl, comb.data(), sizeof(cf) * n * D, hipMemcpyHostToDevice));
+    HIPC(c, c->det_pl.alloc(fields));
+    if (c->with_grad && !c->generic) HIPC(c, c->seed_pl.alloc(fields));
+    // every plane's launch leaves its own partial sums: room for D times those of one plane
+    HIPC(c, c->partial.room((size_t)2 * c->npartial * D * (c->resident ? 16 : 1)));
+    for (int j = 0; j < D; ++j) c->hdet00_pl.push_back(std::complex<double>(hdet00[2 * j], hdet00[2 * j + 1]));
+    c->planes = D;
+    c->tape_valid = c->last_valid = false;
+    return 0;
+}
+
 int bdof_adjoint_carrier(bdof_ctx* c, int B, double* gcar, double* gt0) {
     if (!c || !gcar || !gt0) return BDOF_ERR_ARG;
     int r;
@@ -1651,6 +1804,7 @@ int bdof_set_probe_stack(bdof_ctx* c, const float* stack, const float* det) {
     c->mod_dirty = true;
     if (!stack && !det) return 0;
     if (!stack || !det) return fail(c, BDOF_ERR_ARG, "bdof_set_probe_stack: both arrays or neither");
+    if (int r = need_one_plane(c, "a carrier field (bdof_set_probe_stack)")) return r;
     const size_t n = (size_t)c->NX * c->NY, fld = sizeof(cf) * n;
     HIPC(c, c->pstack.alloc(n * steps(c).stack_planes()));       // one plane per propagation step
     HIPC(c, c->pdet.alloc(n));
@@ -1676,6 +1830,7 @@ int bdof_set_probe_field(bdof_ctx* c, const double* probe, const double* hT, con
     if (!c || !probe || !hT) return BDOF_ERR_ARG;
     if (!c->have_physics) return fail(c, BDOF_ERR_STATE, "bdof_set_physics has not been called");
     if (c->det_mode == BDOF_DET_NEAR && !hdetT) return fail(c, BDOF_ERR_ARG, "hdetT required for BDOF_DET_NEAR");
+    if (int r = need_one_plane(c, "a carrier field (bdof_set_probe_field)")) return r;
     HIPC(c, hipSetDevice(c->device));
     HIPC(c, hipStreamSynchronize(c->stream));
     const size_t n = (size_t)c->NX * c->NY, fld = sizeof(cf) * n, dbytes = sizeof(double2) * n;
@@ -1811,7 +1966,9 @@ int bdof_forward(bdof_ctx* c, int B, const int* angle_of_b, const int* xoff, con
     c->last_valid = false;
     const DetRoute dr = det_route(c);
     const Group all = whole(c, B);
-    if (out_wave) {
+    if (out_wave && c->planes > 1) {
+        for (int j = 0; j < c->planes; ++j) launch_loss_plane(c, all, wave_plane(c, carrier_det(c, j)), j, (cf*)out_wave, nullptr);
+    } else if (out_wave) {
         const DetPlane det = wave_plane(c, carrier_det(c), dr.pfield);
         if (dr.far) launch_loss_far(c, all, det, dr.in, nullptr, (cf*)out_wave, nullptr, 1.f, 1.f);
         else launch_loss_real(c, all, det, dr.in, nullptr, false, (cf*)out_wave, nullptr, dr.in_scale, 1.f);
@@ -1869,6 +2026,7 @@ static int forward_range(bdof_ctx* c, int B, const int* angle_of_b, const int* x
 int bdof_forward_range(bdof_ctx* c, int B, const int* angle_of_b, const int* xoff, const int* yoff, int z0, int nz,
                        const void* in_real, void* out_real, int prop_last) {
     if (int rb = need_unbinned(c, "bdof_forward_range")) return rb;
+    if (int rp = need_one_plane(c, "bdof_forward_range")) return rp;
     if (!c) return BDOF_ERR_ARG;
     return forward_range(c, B, angle_of_b, xoff, yoff, z0, nz, in_real, out_real, prop_last, c->hs);
 }
@@ -1880,6 +2038,7 @@ int bdof_forward_range(bdof_ctx* c, int B, const int* angle_of_b, const int* xof
 // exactly T psi - T_free psi, without the round-off of two full-amplitude sweeps.  NULL removes the stack.
 int bdof_set_range_carrier(bdof_ctx* c, const void* stack, int B, int z0, int nz) {
     if (int rb = need_unbinned(c, "bdof_set_range_carrier")) return rb;
+    if (int rp = need_one_plane(c, "bdof_set_range_carrier")) return rp;
     if (!c) return BDOF_ERR_ARG;
     if (!stack) { c->range_car = nullptr; c->range_car_B = 0; return 0; }
     if (int r = need_configured(c)) return r;
@@ -1895,6 +2054,7 @@ int bdof_set_range_carrier(bdof_ctx* c, const void* stack, int B, int z0, int nz
 int bdof_forward_range_h(bdof_ctx* c, int B, const int* angle_of_b, const int* xoff, const int* yoff, int z0, int nz,
                          const void* in_real, void* out_real, int prop_last, const void* h) {
     if (int rb = need_unbinned(c, "bdof_forward_range_h")) return rb;
+    if (int rp = need_one_plane(c, "bdof_forward_range_h")) return rp;
     if (!c || !h) return BDOF_ERR_ARG;
     return forward_range(c, B, angle_of_b, xoff, yoff, z0, nz, in_real, out_real, prop_last, (const cf*)h);
 }
@@ -1913,6 +2073,7 @@ static void launch_real_to_hyb(bdof_ctx* c, const Group& g, const cf* in, cf* ou
 int bdof_adjoint_range(bdof_ctx* c, int B, const int* angle_of_b, const int* xoff, const int* yoff, int z0, int nz,
                        const void* end_real, const void* g_end_real, void* g_start_real, void* grot_range) {
     if (int rb = need_unbinned(c, "bdof_adjoint_range")) return rb;
+    if (int rp = need_one_plane(c, "bdof_adjoint_range")) return rp;
     int r = check_ready(c, B);
     if (r) return r;
     if (!end_real || !g_end_real || !g_start_real || !grot_range) return BDOF_ERR_ARG;
@@ -2061,6 +2222,7 @@ int bdof_fields_free_step_aux(bdof_ctx* c, void* fields, const void* src, int B,
 // ifftshift(H) / (NX NY).
 int bdof_range_carrier_build(bdof_ctx* c, void* p0, void* stack, int B, int NX, int NY, const void* h, int nz) {
     if (int rb = need_unbinned(c, "bdof_range_carrier_build")) return rb;
+    if (int rp = need_one_plane(c, "bdof_range_carrier_build")) return rp;
     if (!c || !p0 || !stack || !h || B < 1 || NX < 1 || NY < 1 || nz < 1) return BDOF_ERR_ARG;
     HIPC(c, hipSetDevice(c->device));
     const size_t per = (size_t)NX * NY, n = per * B;
@@ -2162,6 +2324,7 @@ int bdof_tiles_scatter_diff64(bdof_ctx* c, const void* tiles_a, const void* tile
 int bdof_forward_range_f64(bdof_ctx* c, int B, const int* angle_of_b, const int* xoff, const int* yoff, int z0, int nz, void* fields,
                            const void* h, double k, int prop_last) {
     if (int rb = need_unbinned(c, "bdof_forward_range_f64")) return rb;
+    if (int rp = need_one_plane(c, "bdof_forward_range_f64")) return rp;
     if (!c || !fields || !h) return BDOF_ERR_ARG;
     if (int r = need_configured(c)) return r;
     if (!c->obj_src) return fail(c, BDOF_ERR_STATE, "bdof_set_object (with (delta, beta) rows) has not been called");
@@ -2212,6 +2375,7 @@ static int c64_room(bdof_ctx* c, int B, bool tf, size_t M) {
 // recursion, propagation.py:91,99); k = 2 pi dz / lambda with numpy's pi (propagation.py:25)
 int bdof_set_conv_f64(bdof_ctx* c, const double* probe, const double* khat, int ks, double ksum_re, double ksum_im, double k) {
     if (int rb = need_unbinned(c, "bdof_set_conv_f64")) return rb;
+    if (int rp = need_one_plane(c, "bdof_set_conv_f64")) return rp;
     if (!c || !probe || !khat) return BDOF_ERR_ARG;
     if (int r = need_configured(c)) return r;
     if (c->NX != c->NY) return fail(c, BDOF_ERR_SIZE, "the float64 real-space path takes square wavefields");
@@ -2240,6 +2404,7 @@ int bdof_set_conv_f64(bdof_ctx* c, const double* probe, const double* khat, int 
 // step of the renormalised exit wave): hdetT host complex128 [kx][ky], ifftshift(H_det) / (NX NY); NULL removes it
 int bdof_set_conv_f64_detector(bdof_ctx* c, const double* hdetT) {
     if (int rb = need_unbinned(c, "bdof_set_conv_f64_detector")) return rb;
+    if (int rp = need_one_plane(c, "bdof_set_conv_f64_detector")) return rp;
     if (!c) return BDOF_ERR_ARG;
     if (int r = need_configured(c)) return r;
     HIPC(c, hipSetDevice(c->device));
@@ -2258,6 +2423,7 @@ int bdof_set_conv_f64_detector(bdof_ctx* c, const double* hdetT) {
 // bdof_set_conv_f64_detector.
 int bdof_loss_grad_conv_f64(bdof_ctx* c, int B, const int* angle_of_b, const int* xoff, const int* yoff, const float* meas, double meas_ref) {
     if (int rb = need_unbinned(c, "bdof_loss_grad_conv_f64")) return rb;
+    if (int rp = need_one_plane(c, "bdof_loss_grad_conv_f64")) return rp;
     if (!c || !meas) return BDOF_ERR_ARG;
     if (!c->c64_ks || c->c64_tf) return fail(c, BDOF_ERR_STATE, "bdof_set_conv_f64 has not been called");
     if (int rl = need_lsq(c, "bdof_loss_grad_conv_f64")) return rl;
@@ -2327,6 +2493,7 @@ int bdof_loss_grad_conv_f64(bdof_ctx* c, int B, const int* angle_of_b, const int
 // ifftshift-ed transfer functions / (NX NY); k = 2 pi dz / lambda as bdof_set_physics has it
 int bdof_set_tf_f64(bdof_ctx* c, const double* probe, const double* hT, const double* hdetT, double k) {
     if (int rb = need_unbinned(c, "bdof_set_tf_f64")) return rb;
+    if (int rp = need_one_plane(c, "bdof_set_tf_f64")) return rp;
     if (!c || !probe || !hT) return BDOF_ERR_ARG;
     if (int r = need_configured(c)) return r;
     if (c->det_mode == BDOF_DET_NEAR && !hdetT) return fail(c, BDOF_ERR_ARG, "a near-field detector needs its transfer function in float64 too");
@@ -2351,6 +2518,7 @@ int bdof_set_tf_f64(bdof_ctx* c, const double* probe, const double* hT, const do
 // kernels on the device.  meas: device float, laid out as for bdof_loss_grad (+ meas_ref under bdof_set_meas_mode(1)).
 int bdof_loss_grad_tf_f64(bdof_ctx* c, int B, const int* angle_of_b, const int* xoff, const int* yoff, const float* meas, double meas_ref) {
     if (int rb = need_unbinned(c, "bdof_loss_grad_tf_f64")) return rb;
+    if (int rp = need_one_plane(c, "bdof_loss_grad_tf_f64")) return rp;
     if (!c || !meas) return BDOF_ERR_ARG;
     if (!c->c64_tf) return fail(c, BDOF_ERR_STATE, "bdof_set_tf_f64 has not been called");
     if (!c->obj_src) return fail(c, BDOF_ERR_STATE, "bdof_set_object (with (delta, beta) rows) has not been called");
@@ -2454,6 +2622,13 @@ int bdof_loss_grad(bdof_ctx* c, int B, const int* angle_of_b, const int* xoff, c
     // Detector + seed.  Afterwards bufB holds g_hat(phi_{S-1}) (L1 order, normalised hybrid).
     const DetRoute dr = det_route(c);
     for (const Group& g : split) {
+        if (c->planes > 1) {
+            // one real-space detector launch per plane on det_pl, the seeds (transposed) to seed_pl, then the fan-in to bufB
+            for (int j = 0; j < c->planes; ++j)
+                npart += launch_loss_plane(c, g, det_plane(c, g, B, nullptr, j), j, (cf*)out_wave, meas, npart);
+            launch_row_planes(c, g, true, n_steps(c) - 1, fused ? BDOF_K_LOSS : BDOF_K_COL_PROP);
+            continue;
+        }
         const DetPlane det = det_plane(c, g, B, dr.pfield);      // the whole batch's seed scale
         if (dr.far) {
             npart += launch_loss_far(c, g, det, dr.in, c->bufB, (cf*)out_wave, meas, 1.f, 1.f, npart);
@@ -2468,7 +2643,7 @@ int bdof_loss_grad(bdof_ctx* c, int B, const int* angle_of_b, const int* xoff, c
     adjoint_sweep(c, split, fused, adj_fused);
     if ((r = split.close(c))) return r;
     hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, c->stream, c->partial, npart,
-                       1.0 / ((double)B * c->NX * c->NY), c->loss_dev);
+                       1.0 / ((double)B * c->planes * c->NX * c->NY), c->loss_dev);
     return launched(c);
 }
 
@@ -2479,6 +2654,7 @@ int bdof_loss_grad(bdof_ctx* c, int B, const int* angle_of_b, const int* xoff, c
 int bdof_set_conv(bdof_ctx* c, const float* ky, const float* kx, int ks, double e_re, double e_im, double ksum_re,
                   double ksum_im, double k) {
     if (int rb = need_unbinned(c, "bdof_set_conv")) return rb;
+    if (int rp = need_one_plane(c, "bdof_set_conv")) return rp;
     if (!c || !ky || !kx) return BDOF_ERR_ARG;
     if (int r = need_configured(c)) return r;
     if (ks < 1 || ks > BDOF_CONV_MAXK || ks % 2 == 0) return fail(c, BDOF_ERR_ARG, "kernel_size must be odd and <= 33");
@@ -2509,6 +2685,7 @@ int bdof_set_conv(bdof_ctx* c, const float* ky, const float* kx, int ks, double 
 
 int bdof_set_conv_taps_f64(bdof_ctx* c, const double* ky, const double* kx, double e_re, double e_im) {
     if (int rb = need_unbinned(c, "bdof_set_conv_taps_f64")) return rb;
+    if (int rp = need_one_plane(c, "bdof_set_conv_taps_f64")) return rp;
     if (!c || !ky || !kx) return BDOF_ERR_ARG;
     if (!c->have_conv) return fail(c, BDOF_ERR_STATE, "bdof_set_conv has not been called");
     const int D = c->tw_dither;
@@ -2664,6 +2841,7 @@ extern "C" {
 
 int bdof_set_conv_probe_stack(bdof_ctx* c, const float* stack, const double* det64, double p0_re, double p0_im, double pS_re, double pS_im) {
     if (int rb = need_unbinned(c, "bdof_set_conv_probe_stack")) return rb;
+    if (int rp = need_one_plane(c, "bdof_set_conv_probe_stack")) return rp;
     if (!c) return BDOF_ERR_ARG;
     if (int r = need_configured(c)) return r;
     HIPC(c, hipSetDevice(c->device));
@@ -2685,6 +2863,7 @@ int bdof_set_conv_probe_stack(bdof_ctx* c, const float* stack, const double* det
 
 int bdof_forward_conv(bdof_ctx* c, int B, const int* angle_of_b, const int* xoff, const int* yoff, void* out_wave) {
     if (int rb = need_unbinned(c, "bdof_forward_conv")) return rb;
+    if (int rp = need_one_plane(c, "bdof_forward_conv")) return rp;
     int r = conv_check(c, B, angle_of_b);
     if (r) return r;
     if (!out_wave) return BDOF_ERR_ARG;
@@ -2720,6 +2899,7 @@ int bdof_forward_conv(bdof_ctx* c, int B, const int* angle_of_b, const int* xoff
 
 int bdof_loss_grad_conv(bdof_ctx* c, int B, const int* angle_of_b, const int* xoff, const int* yoff, const float* meas, void* out_wave) {
     if (int rb = need_unbinned(c, "bdof_loss_grad_conv")) return rb;
+    if (int rp = need_one_plane(c, "bdof_loss_grad_conv")) return rp;
     int r = conv_check(c, B, angle_of_b);
     if (r) return r;
     if (!meas) return BDOF_ERR_ARG;

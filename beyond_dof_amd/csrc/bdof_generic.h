@@ -72,11 +72,20 @@ struct GLossArgs {
     int B, NX, NY, far;
     double2* seed64;     // nullable [B][NX][NY]: float64 adjoint sweep (bdof_configure flag 64) — detector wave, residual and
                          // seed all formed in float64 and left here un-rounded
+    int fstride = 1;     // PL instantiations only (in the bytes the alignment of `det` left empty): wavefield b of `field` is frame
+                         // b * fstride of meas / out_wave — one detector plane of D, frames [B][D][NX][NY] (bdof_set_detector_planes)
     DetPlane det;        // bdof_kernels.h; pfield / pfield64 [x][y], far field [kx][ky]
 };
 
+// dst (+)= src, n complex numbers: the fan-in of the detector planes' adjoint steps
+__global__ __launch_bounds__(256) void k_g_accumulate(cf* __restrict__ dst, const cf* __restrict__ src, size_t n, int first) {
+    for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < n; idx += (size_t)gridDim.x * blockDim.x)
+        dst[idx] = first ? src[idx] : cadd(dst[idx], src[idx]);
+}
+
 // PSN: the Poisson data term (seed_weight, bdof_kernels.h); WGT: detector weights, det.wgt in the order of one wavefield of meas
-template <bool PSN, bool WGT = false>
+// PL: one detector plane of several (GLossArgs::fstride; real-space detectors)
+template <bool PSN, bool WGT = false, bool PL = false>
 __global__ __launch_bounds__(256) void k_g_loss(GLossArgs a) {
     const size_t n = (size_t)a.B * a.NX * a.NY;
     const DetPlane& det = a.det;
@@ -86,7 +95,8 @@ __global__ __launch_bounds__(256) void k_g_loss(GLossArgs a) {
         const size_t r = idx / a.NY;
         const int x = r % a.NX, b = r / a.NX;
         const size_t pi = (size_t)x * a.NY + y;                                    // in the carrier field's plane
-        const size_t oi = a.far ? ((size_t)b * a.NY + y) * a.NX + x : idx;         // in meas / out_wave
+        const size_t oi = PL ? idx + (size_t)b * (a.fstride - 1) * a.NX * a.NY
+                             : a.far ? ((size_t)b * a.NY + y) * a.NX + x : idx;         // in meas / out_wave
         const bool dc = x == 0 && y == 0;
         const float w = a.meas ? det_weight<WGT>(det, a.far ? (size_t)y * a.NX + x : pi) : 1.f;
         cf d = a.field[idx];
@@ -101,8 +111,9 @@ __global__ __launch_bounds__(256) void k_g_loss(GLossArgs a) {
             continue;
         }
         if (det.meas_dev && a.meas && !a.far && !det.pfield) {
-            if (a.out_wave) a.out_wave[idx] = cadd(d, det.carrier);
-            a.field[idx] = seed_split<PSN, WGT>(d, a.meas[idx], det, acc, acc2, w);
+            const size_t si = PL ? oi : idx;        // (real-space detector: without PL the frame index is the field's)
+            if (a.out_wave) a.out_wave[si] = cadd(d, det.carrier);
+            a.field[idx] = seed_split<PSN, WGT>(d, a.meas[si], det, acc, acc2, w);
             continue;
         }
         if (det.pfield64 && a.meas) {

@@ -15,6 +15,7 @@
 // [b][y][x], and the tape holds phi_z:                                                                              32 B/px
 // The fused adjoint sweep (k_slice_y_adj / k_slice_x_adj, below them) replaces A' + B' the same way:                40 B/px
 #pragma once
+#include <type_traits>
 #include "bdof_fft.h"
 
 #define BDOF_THREADS 512
@@ -406,6 +407,126 @@ __global__ __launch_bounds__(BDOF_THREADS, RowCfg<NX>::MIN_WAVES) void k_row_pro
 }
 
 // ---------------------------------------------------------------------------------------------
+// Detector planes (bdof_set_detector_planes): the step between the exit wave and D > 1 detector planes, and its adjoint.
+//   fan-out (k_row_prop_fan)   : L2 -> D x L1   out_j = C^-1'( h_j * C in )                          8 (1 + D) B/px
+//   fan-in  (k_row_prop_gather): D x L2 -> L1   out   = C^-1'( sum_j conj(h_j) * C in_j )            8 (D + 1) B/px
+// Both are k_row_prop with a loop over the planes inside the tile; the planes of wavefield b lie one after the other,
+// [B][D][..][..], as the measurements do, and the tables are [D][ky][kx].  One launch per sub-batch each.
+// ---------------------------------------------------------------------------------------------
+struct RowPlanesArgs {
+    const cf* in;    // fan: L2 [B][NY][NX]         gather: L2 [B][D][NY][NX]
+    cf* out;         // fan: L1 [B][D][NX][NY]      gather: L1 [B][NX][NY]
+    const cf* h;     // [D][ky][kx], as RowPropArgs::h
+    int B, NY, D;
+    const cf* twiddle;
+    float sq[2];     // sqrt(1/2) of this launch (RowFwdArgs)
+};
+
+// The line is read and transformed once where a tile is one pass (NX <= 256): its spectrum stays in registers across the planes.
+// Where a tile takes several passes (NX >= 512) the spectra of all its passes would have to stay (16 registers per pass), which
+// these kernels do not have: there the line is read again per plane — from L2, the tile was read a moment ago — and transformed
+// again, inside the same launch.
+template <int NX>
+__global__ __launch_bounds__(BDOF_THREADS, RowCfg<NX>::MIN_WAVES) void k_row_prop_fan(RowPlanesArgs a) {
+    typedef RowCfg<NX> C;
+    constexpr bool HOLD = C::PASSES == 1;
+    __shared__ cf smem[C::LDS_CF];
+    const int tid = threadIdx.x % C::T, rl = threadIdx.x / C::T;
+    __shared__ cf smem_tw[FftTw<NX>::LDS_CNT];
+    FftTw<NX> tw;
+    __shared__ cf smem_tail[7 * C::T];
+    tw.template load<false>(a.twiddle, tid, smem_tw, smem_tail);
+    tw.sq = a.sq;
+    const int ntiles = a.B * a.NY / C::TILE;
+    for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        const int row0 = tile * C::TILE;
+        const int b = row0 / a.NY, ky0 = row0 - b * a.NY;
+        cf s[8];
+        if constexpr (HOLD) {
+            RowLds<C::T> lds{smem + rl * C::RS};
+            const cf* src = a.in + (size_t)(row0 + rl) * NX;
+#pragma unroll
+            for (int m = 0; m < 8; ++m) s[m] = src[tid + m * C::T];
+            line_fft<NX, -1, 1, false>(s, tw, tid, lds);
+        }
+#pragma nounroll
+        for (int j = 0; j < a.D; ++j) {
+            const cf* hj = a.h + (size_t)j * a.NY * NX;
+#pragma nounroll
+            for (int pass = 0; pass < C::PASSES; ++pass) {
+                const int r = pass * C::RPP + rl;
+                RowLds<C::T> lds{smem + r * C::RS};
+                const cf* hrow = hj + (size_t)(ky0 + r) * NX;
+                cf u[8], hv[8];
+                if constexpr (!HOLD) {
+                    const cf* src = a.in + (size_t)(row0 + r) * NX;
+#pragma unroll
+                    for (int m = 0; m < 8; ++m) u[m] = src[tid + m * C::T];
+#pragma unroll
+                    for (int m = 0; m < 8; ++m) hv[m] = hrow[tid + m * C::T];
+                    line_fft<NX, -1, 1, false>(u, tw, tid, lds);
+                } else {
+#pragma unroll
+                    for (int m = 0; m < 8; ++m) hv[m] = hrow[tid + m * C::T];
+#pragma unroll
+                    for (int m = 0; m < 8; ++m) u[m] = s[m];
+                }
+#pragma unroll
+                for (int m = 0; m < 8; ++m) u[m] = cmul(u[m], hv[m]);
+                line_fft_partial<NX, +1, 2, false>(u, tw, tid, lds);
+            }
+            __syncthreads();
+            transposed_tail<NX, +1, 2, false>(smem, a.out + ((size_t)b * a.D + j) * NX * a.NY + ky0, a.NY, 1.f, smem_tail, a.sq);
+            __syncthreads();
+        }
+    }
+}
+
+template <int NX>
+__global__ __launch_bounds__(BDOF_THREADS, RowCfg<NX>::MIN_WAVES) void k_row_prop_gather(RowPlanesArgs a) {
+    typedef RowCfg<NX> C;
+    __shared__ cf smem[C::LDS_CF];
+    const int tid = threadIdx.x % C::T, rl = threadIdx.x / C::T;
+    __shared__ cf smem_tw[FftTw<NX>::LDS_CNT];
+    FftTw<NX> tw;
+    __shared__ cf smem_tail[7 * C::T];
+    tw.template load<false>(a.twiddle, tid, smem_tw, smem_tail);
+    tw.sq = a.sq;
+    const int ntiles = a.B * a.NY / C::TILE;
+    for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        const int row0 = tile * C::TILE;
+        const int b = row0 / a.NY, ky0 = row0 - b * a.NY;
+#pragma nounroll
+        for (int pass = 0; pass < C::PASSES; ++pass) {
+            const int r = pass * C::RPP + rl;
+            RowLds<C::T> lds{smem + r * C::RS};
+            cf acc[8];
+#pragma unroll
+            for (int m = 0; m < 8; ++m) acc[m] = make_float2(0.f, 0.f);
+#pragma nounroll
+            for (int j = 0; j < a.D; ++j) {
+                const cf* src = a.in + (((size_t)b * a.D + j) * a.NY + ky0 + r) * NX;
+                const cf* hrow = a.h + ((size_t)j * a.NY + ky0 + r) * NX;
+                cf u[8];
+#pragma unroll
+                for (int m = 0; m < 8; ++m) u[m] = src[tid + m * C::T];
+                line_fft<NX, -1, 1, false>(u, tw, tid, lds);
+#pragma unroll
+                for (int m = 0; m < 8; ++m) {
+                    cf t = hrow[tid + m * C::T];
+                    t.y = -t.y;
+                    acc[m] = cadd(acc[m], cmul(u[m], t));
+                }
+            }
+            line_fft_partial<NX, +1, 2, false>(acc, tw, tid, lds);
+        }
+        __syncthreads();
+        transposed_tail<NX, +1, 2, false>(smem, a.out + (size_t)b * NX * a.NY + ky0, a.NY, 1.f, smem_tail, a.sq);
+        __syncthreads();
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
 // block reduction of a per-thread double: wavefront shuffles, then one LDS hop
 // ---------------------------------------------------------------------------------------------
 __device__ __forceinline__ double wave_reduce_sum(double v) {
@@ -607,6 +728,12 @@ struct LossArgs {
     const cf* twiddle;
     DetPlane det;        // pfield / pfield64 in the row layout of `in` ([R][N])
 };
+// The arguments of the PL instantiations (one detector plane of D, bdof_set_detector_planes): wavefield b of the launch is field
+// b * fstride of in / out_hyb / out_wave / meas, which lie [B][D][R][N].  A struct of its own, so that the kernels without PL
+// keep their argument block to the byte.
+struct LossPlaneArgs : LossArgs {
+    int fstride = 1;
+};
 
 // p[i], fetched where it is used: the scheduling barrier keeps a run of these loads from being gathered in front of the code
 // between them.  A 32-bit index off a wave-uniform base: no address pair to keep per lane.
@@ -617,13 +744,14 @@ __device__ __forceinline__ float load_here(const float* p, unsigned i) {
 }
 // k_row_loss, WGT: amplitude and weight of element m (u[m]) of the row — off the tile's first row of `meas` (an index below
 // TILE N) and off the plane (below NX NY <= 2^20)
-#define MEAS_OF(m) (WGT ? load_here(a.meas + (size_t)row0 * N, (unsigned)(r * N + tid + (m) * C::T)) : mm[m])
+#define MEAS_OF(m) (WGT ? load_here(a.meas + (PL ? tile_off : (size_t)row0 * N), (unsigned)(r * N + tid + (m) * C::T)) : mm[m])
 #define WGT_OF(m) (WGT ? load_here(det.wgt, (unsigned)((r0 + r) * N + tid + (m) * C::T)) : 1.f)
 
 // FAR = false: inverse FFT first (rows of L1); FAR = true: forward FFT first (rows of L2).  PSN: the Poisson data term.
 // WGT: detector weights (det.wgt, rows as `meas`), a template parameter as PSN is: the unweighted kernels do not change.
-template <int N, bool FAR, bool TSTORE, bool PSN = false, bool WGT = false>
-__global__ __launch_bounds__(BDOF_THREADS, RowCfg<N>::MIN_WAVES) void k_row_loss(LossArgs a) {
+// PL: one detector plane of several (LossPlaneArgs), a template parameter for the same reason.
+template <int N, bool FAR, bool TSTORE, bool PSN = false, bool WGT = false, bool PL = false>
+__global__ __launch_bounds__(BDOF_THREADS, RowCfg<N>::MIN_WAVES) void k_row_loss(std::conditional_t<PL, LossPlaneArgs, LossArgs> a) {
     typedef RowCfg<N> C;
     constexpr int S1 = FAR ? -1 : +1;     // direction of the first transform; the second is the opposite
     __shared__ cf smem[C::LDS_CF];
@@ -638,11 +766,14 @@ __global__ __launch_bounds__(BDOF_THREADS, RowCfg<N>::MIN_WAVES) void k_row_loss
     for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         const int row0 = tile * C::TILE;
         const int b = row0 / a.R, r0 = row0 - b * a.R;
+        size_t fields = 1, tile_off = 0;  // PL: fields from one wavefield of the launch to the next; the tile's first row in in / out_wave / meas
+        if constexpr (PL) { fields = (size_t)a.fstride; tile_off = ((size_t)b * fields * a.R + r0) * N; }
 #pragma nounroll
         for (int pass = 0; pass < C::PASSES; ++pass) {
             const int r = pass * C::RPP + rl;
             RowLds<C::T> lds{smem + r * C::RS};
-            const size_t off = (size_t)(row0 + r) * N;
+            size_t off;
+            if constexpr (PL) off = tile_off + (size_t)r * N; else off = (size_t)(row0 + r) * N;
             cf u[8];
             float mm[8];
 #pragma unroll
@@ -720,7 +851,7 @@ __global__ __launch_bounds__(BDOF_THREADS, RowCfg<N>::MIN_WAVES) void k_row_loss
         if constexpr (TSTORE) {
             if (a.out_hyb) {
                 __syncthreads();
-                transposed_tail<N, -S1, 1, EX>(smem, a.out_hyb + (size_t)b * N * a.R + r0, a.R, a.out_scale, smem_tail);
+                transposed_tail<N, -S1, 1, EX>(smem, a.out_hyb + (size_t)b * fields * N * a.R + r0, a.R, a.out_scale, smem_tail);
                 __syncthreads();
             }
         }

@@ -87,6 +87,28 @@ def check_binning_path(slice_binning, propagator='fft', adjoint_precision=None, 
         raise ValueError("slice_binning > 1 runs on the rotation tables (rotation='nearest') only")
 
 
+def check_planes_path(free_prop_cm, propagator='fft', adjoint_precision=None, rotation='nearest', recompute=False, adjoint64=False,
+                      detector_kernel='TF'):
+    """The free_prop_cm keyword as every layer takes it (util.detector_distances raises ValueError for a bad one), and with more
+    than one detector plane that the call stays on what carries them: the transfer-function propagator, the float32 sweeps
+    with the tape (an explicit adjoint_precision other than 'float32' raises; None: not given), the nearest-neighbour rotation
+    tables and one kernel kind, 'TF' or 'IR', for all planes.  Returns the number of frames per angle (1 without planes)."""
+    planes = util.detector_distances(free_prop_cm)[1]
+    if planes is None:
+        return 1
+    if propagator != 'fft':
+        raise ValueError("several detector planes (free_prop_cm as a sequence) run on the transfer-function propagator (propagator='fft') only")
+    if adjoint_precision not in (None, 'float32') or adjoint64:
+        raise ValueError("several detector planes have no float64 twin: adjoint_precision must be 'float32' (no adjoint64)")
+    if recompute:
+        raise ValueError('several detector planes run with the tape: not recompute')
+    if rotation != 'nearest':
+        raise ValueError("several detector planes run on the rotation tables (rotation='nearest') only")
+    if detector_kernel not in ('TF', 'IR'):
+        raise ValueError("several detector planes share one detector_kernel, 'TF' or 'IR': not {!r}".format(detector_kernel))
+    return len(planes)
+
+
 def _hp(arr):
     """Host pointer of a numpy array for a library call (None stays None)."""
     return None if arr is None else arr.ctypes.data
@@ -149,6 +171,7 @@ class MultisliceEngine(object):
     residual_split = True       # False: amplitudes go to the device as they are (a probe that changes between steps)
     loss_type, poisson_multiplier = 'lsq', 2e6      # set_loss
     detector_weights = None     # set_detector_weights: the (Y, X) float32 plane; None: every pixel counts alike
+    n_planes = 1                # detector planes per wavefield (set_physics with a sequence of distances)
 
     def _reset_host_state(self):
         for name in set(vars(self)) & set(vars(MultisliceEngine)):
@@ -196,14 +219,25 @@ class MultisliceEngine(object):
         """k and H exactly as cnn_propagator/np_funcs.py:19-32,45-57 derive them from energy / pixel size.  field_shape: this
         engine's wavefields are tiles of a (FY, FX) field and apply that field's propagator (util.get_kernel_tile).
         detector_kernel: 'TF' (what np_funcs.py:55 forces), 'IR' (get_kernel_ir, np_funcs.py:59-61) or 'auto' (the sampling
-        criterion of np_funcs.py:51-53) for the step to a detector at a finite distance."""
+        criterion of np_funcs.py:51-53) for the step to a detector at a finite distance.
+        free_prop_cm as a sequence of D distances: D detector planes per wavefield (bdof_set_detector_planes, include/bdof.h),
+        each with the table of its own distance and the one detector_kernel, 'TF' or 'IR'.  forward then returns (B, D, Y, X)
+        and loss_grad takes amplitudes of that shape; n_planes = D.  A sequence of one is its scalar.  Streaming and generic
+        engines with the tape, scalar-carrier probes."""
+        n_planes = check_planes_path(free_prop_cm, 'fft' if self._conv_kernel is None else 'conv', recompute=self.recompute,
+                                     adjoint64=self.adjoint64, detector_kernel=detector_kernel)
         o = util.Optics(energy_ev, psize_cm, free_prop_cm, pi, self.ny, self.nx, field_shape)
+        if n_planes > 1:
+            if field_shape is not None:
+                raise ValueError('several detector planes: not for the tiles of a larger field (field_shape)')
+            if self._probe_args is not None and self._wants_probe_stack(self._scalar_carrier(self._probe_field(), n_planes), o):
+                raise ValueError('several detector planes run with a scalar carrier: this probe rides on a carrier field (set_probe)')
         det_mode = _lib.DET_NONE if free_prop_cm is None else _lib.DET_FAR if o.det_nm is None else _lib.DET_NEAR
         det_kernel = 'TF'
         if det_mode == _lib.DET_NEAR:
             det_kernel = util.detector_kernel_kind(detector_kernel, o.det_nm, o.lmbda_nm, o.voxel_nm, (self.ny, self.nx))
         self.optics, self.variant, self.k = o, variant, o.k       # (a refused argument has raised by now: the old physics stay whole)
-        self.det_mode, self.det_kernel = det_mode, det_kernel
+        self.det_mode, self.det_kernel, self.n_planes = det_mode, det_kernel, n_planes
         hs64 = o.table(self._step_nm(), tiled=True, dtype=np.complex128)  # the slice step (of slice_binning voxels) honours field_shape ...
         hs = hs64.astype(np.complex64)
         h00 = o.dc(self._step_nm(), tiled=True)
@@ -219,6 +253,12 @@ class MultisliceEngine(object):
                                                  self.det_mode, _VARIANT[variant]))
         # the same table in float64: the streaming kernels multiply by dithered float32 copies of it (bdof_set_transfer_f64)
         self.ctx.check(self.lib.bdof_set_transfer_f64(self.h, hs64.ctypes.data))
+        if n_planes > 1:        # (bdof_set_physics has put the ctx back to one plane)
+            tables = np.ascontiguousarray(np.stack([o.table(d, det_kernel) for d in o.det_planes_nm]))
+            dcs = np.ascontiguousarray(np.stack([o.dc(d, det_kernel) for d in o.det_planes_nm]))
+            if self.lib.bdof_probe_stack_supported(self.h) == 1:
+                self.ctx.check(self.lib.bdof_set_probe_stack(self.h, None, None))      # the re-issued probe below rides on a scalar
+            self.ctx.check(self.lib.bdof_set_detector_planes(self.h, n_planes, tables.ctypes.data, dcs.ctypes.data))
         if self.adjoint64:
             hd64 = self._detector_table(np.complex128)
             self.ctx.check(self.lib.bdof_set_physics_f64(self.h, hs64.ctypes.data, _hp(hd64)))
@@ -234,6 +274,10 @@ class MultisliceEngine(object):
     def _need_unbinned(self, what):
         if self.slice_binning > 1:
             raise ValueError('{} does not carry slice_binning > 1'.format(what))
+
+    def _need_one_plane(self, what):
+        if self.n_planes > 1:
+            raise ValueError('{} does not carry several detector planes'.format(what))
 
     def _detector_table(self, dtype, fold=True, transpose=False, tiled=False):
         """The un-shifted multiplier of the step to a near-field detector (None without one): the one place it is built.
@@ -282,24 +326,23 @@ class MultisliceEngine(object):
         self.ctx.check(self.lib.bdof_set_probe_field(self.h, p.ctypes.data, hT.ctypes.data, _hp(hdT)))
 
     def set_probe(self, probe_real, probe_imag):
-        self._probe_args = (np.array(probe_real, copy=True), np.array(probe_imag, copy=True))
-        self.tf_f64 = self.conv_f64 = False     # the float64 twins (enable_tf_f64 / enable_conv_f64) hold the previous probe
+        previous, self._probe_args = self._probe_args, (np.array(probe_real, copy=True), np.array(probe_imag, copy=True))
         probe = self._probe_field()
         # Carrier splitting: the wave is held as carrier + eps and only eps runs through the float32 transforms.
         #  - a (nearly) uniform probe rides on its mean a0, propagated exactly as a scalar inside the library;
         #  - a localised probe rides on its own free-space propagation, a carrier FIELD per slice, which the library computes
         #    on the device in float64 (bdof_set_probe_field): eps is the scattered wave alone;
         #  - otherwise (BDOF_NO_PROBE_STACK, the real-space propagator) a0 = 0 and the whole wave is float32.
-        mean = complex(probe.astype(np.complex128).mean())
-        a0 = mean if np.abs(probe - mean).max() <= 0.25 * abs(mean) else 0j
+        a0 = self._scalar_carrier(probe, self.n_planes)
+        use_stack = self._wants_probe_stack(a0, self.optics)
+        if use_stack and self.n_planes > 1:        # (nothing has changed: the engine keeps the probe it had)
+            self._probe_args = previous
+            raise ValueError('several detector planes run with a scalar carrier: this probe rides on a carrier field')
+        self.tf_f64 = self.conv_f64 = False     # the float64 twins (enable_tf_f64 / enable_conv_f64) hold the previous probe
         self.probe_stack = False
         if self._conv_kernel is not None and self.optics is not None:
             if self._set_conv_probe_stack(probe, a0):
                 return
-        use_stack = (a0 == 0 and self.optics is not None and not os.environ.get('BDOF_NO_PROBE_STACK')
-                     and self._conv_kernel is None                          # the real-space propagator has its own carrier
-                     and self.n_steps * self.nx * self.ny <= (1 << 32)      # 32 GiB of stack at most
-                     and self.lib.bdof_probe_stack_supported(self.h) == 1)
         if use_stack:
             if os.environ.get('BDOF_HOST_PROBE_STACK'):                     # cross-check: the float64 propagation on the host
                 stack, det = self._probe_stack(probe)
@@ -316,6 +359,25 @@ class MultisliceEngine(object):
         eps = np.ascontiguousarray((probe.astype(np.complex128) - a0).T.astype(np.complex64))
         self.ctx.check(self.lib.bdof_set_probe(self.h, eps.ctypes.data, a0.real, a0.imag))
         self._set_meas_mode(a0)
+
+    @staticmethod
+    def _scalar_carrier(probe, n_planes=1):
+        """The scalar a (nearly) uniform probe rides on, its mean; 0 for any other probe.  Nearly uniform: no pixel further from
+        the mean than a quarter of it.  With several detector planes, which have no carrier field to fall back on, the deviation
+        is taken in RMS: a structured probe around a dominant mean (noise of 10 % on a plane wave, whose extreme pixels pass
+        the quarter) still rides on its mean — exact algebra for any scalar, and the part left to the float32 transforms is
+        small against the wave — and only a probe without a dominant mean (a localised one, a Gaussian) comes back as 0."""
+        mean = complex(probe.astype(np.complex128).mean())
+        dev = np.abs(probe - mean)
+        spread = dev.max() if n_planes == 1 else float(np.sqrt(np.mean(dev.astype(np.float64) ** 2)))
+        return mean if spread <= 0.25 * abs(mean) else 0j
+
+    def _wants_probe_stack(self, a0, optics):
+        """Whether set_probe puts a probe of scalar carrier a0 on a carrier FIELD under these optics."""
+        return (a0 == 0 and optics is not None and not os.environ.get('BDOF_NO_PROBE_STACK')
+                and self._conv_kernel is None                          # the real-space propagator has its own carrier
+                and self.n_steps * self.nx * self.ny <= (1 << 32)      # 32 GiB of stack at most
+                and self.lib.bdof_probe_stack_supported(self.h) == 1)
 
     def _set_zero_probe(self):
         """bdof_set_probe with nothing in it: the wave is a carrier field's, or a caller's."""
@@ -388,6 +450,7 @@ class MultisliceEngine(object):
         """Switch the slice-to-slice step to the truncated real-space kernel of multislice_propagate_cnn
         (cnn_propagator/propagation.py:18-44): k uses numpy's pi there (:25), the kernel the reference's PI literal."""
         self._need_unbinned('the real-space propagator (set_conv)')
+        self._need_one_plane('the real-space propagator (set_conv)')
         o = util.Optics(energy_ev, psize_cm, None, np.pi, self.ny, self.nx)         # o.k: numpy's pi, unlike set_physics
         ky, kx, e = util.conv_kernel_separable(o.delta_nm, o.lmbda_nm, o.voxel_nm, (self.ny, self.nx), kernel_size)   # pi=util.PI
         ksum = e * ky.sum() * kx.sum()
@@ -409,6 +472,7 @@ class MultisliceEngine(object):
         of the fused kernels for tests.  Hands the probe and the transfer function(s) over in float64; call again after
         set_physics / set_probe."""
         self._need_unbinned('the float64 twin (enable_tf_f64)')
+        self._need_one_plane('the float64 twin (enable_tf_f64)')
         if self.optics is None or self._probe_args is None:
             raise RuntimeError('set_physics and set_probe first')
         o = self.optics
@@ -482,7 +546,17 @@ class MultisliceEngine(object):
             if self._far_phase is not None:
                 w = w * self._far_phase
             return np.ascontiguousarray(np.fft.fftshift(w, axes=(1, 2)))   # np_funcs.py:48
+        if self.n_planes > 1:
+            return np.ascontiguousarray(buf.download((B, self.n_planes, self.nx, self.ny), np.complex64).transpose(0, 1, 3, 2))
         return np.ascontiguousarray(buf.download((B, self.nx, self.ny), np.complex64).transpose(0, 2, 1))
+
+    def _check_frames(self, meas_abs):
+        """Amplitudes are (n, Y, X) frames, or (n, D, Y, X) with D == n_planes detector planes (D = 1: both forms)."""
+        shape = np.shape(meas_abs)
+        ok = shape[-2:] == (self.ny, self.nx) and (len(shape) == 4 and shape[1] == self.n_planes or len(shape) == 3 and self.n_planes == 1)
+        if not ok:
+            raise ValueError('amplitudes of shape {} do not fit {} detector plane(s) of {}: (n, {}Y, X)'.format(
+                tuple(shape), self.n_planes, (self.ny, self.nx), 'D, ' if self.n_planes > 1 else ''))
 
     def choose_residual_split(self, meas_abs):
         """Decide, for the amplitudes about to be handed over, whether the residual stays split (bdof_set_meas_mode), and return
@@ -492,6 +566,7 @@ class MultisliceEngine(object):
         the splitting is switched off, until the next set_probe.  Called where amplitudes are bound: loss_grad for an array it
         uploads itself, FullfieldSolver.set_measurements for the resident stack.  Everything laid out earlier with the other
         reference must be laid out again (meas_layout) after the mode changed."""
+        self._check_frames(meas_abs)
         if self.meas_ref:
             m64 = np.asarray(meas_abs, dtype=np.float64)
             if self.detector_weights is not None:
@@ -505,7 +580,8 @@ class MultisliceEngine(object):
         """|measured| (n, Y, X) as libbdof's loss kernels read it under the mode in force: m - meas_ref (residual splitting; 0
         without it) rounded once to float32, in the kernels' index order.  Under detector weights the amplitude is 0 wherever
         w == 0, before anything else looks at it (0 NaN is NaN: the kernels could not keep such a pixel out).  Changes nothing
-        on the engine."""
+        on the engine.  With D detector planes the frames are (n, D, Y, X) and every plane shares the weights."""
+        self._check_frames(meas_abs)
         if self.detector_weights is not None:
             meas_abs = np.where(self.detector_weights > 0, meas_abs, 0)
         if self.meas_ref:
@@ -523,9 +599,12 @@ class MultisliceEngine(object):
         return [None if v is None else DeviceBuffer.from_host(self.ctx, np.asarray(v, dtype=np.int32)) for v in lists]
 
     def forward(self, B, angle_idx=None, xoff=None, yoff=None, keep_tape=False, to_host=True, conv=False):
-        out = DeviceBuffer(self.ctx, B * self.nx * self.ny * 8, np.complex64, (B, self.nx, self.ny))
+        """The detector waves of B wavefields, (B, Y, X) — with D detector planes (B, D, Y, X), in the order of the distances."""
+        D = self.n_planes
+        out = DeviceBuffer(self.ctx, B * D * self.nx * self.ny * 8, np.complex64, (B, self.nx, self.ny) if D == 1 else (B, D, self.nx, self.ny))
         a, xo, yo = self._idx_bufs(angle_idx, xoff, yoff)
         if conv:
+            self._need_one_plane('the real-space propagator (forward(conv=True))')
             self.ctx.check(self.lib.bdof_forward_conv(self.h, B, _lib._ptr(a), _lib._ptr(xo), _lib._ptr(yo), out.ptr))
         else:
             self.ctx.check(self.lib.bdof_forward(self.h, B, _lib._ptr(a), _lib._ptr(xo), _lib._ptr(yo), out.ptr, int(keep_tape)))
@@ -546,6 +625,8 @@ class MultisliceEngine(object):
         """Enqueue forward + loss + adjoint of B wavefields; every array argument is a device pointer (or None).  The one
         place that picks among the four entry points: conv — the real-space propagator; f64 — the model's float64 path on
         this context, which takes the residual-splitting reference as a number."""
+        if conv or f64:
+            self._need_one_plane('the real-space propagator / the float64 twin (loss_grad(conv=True / f64=True))')
         if f64:
             if conv and not self.conv_f64:
                 raise RuntimeError('the real-space propagator\'s float64 path: enable_conv_f64() first')

@@ -23,7 +23,7 @@ import numpy as np
 from . import h5io, tiffio, util
 from .comm import get_comm, minibatch_schedule
 from .misc import create_summary
-from .engine import check_poisson_path, check_binning_path, check_weights_path, read_detector_weights
+from .engine import check_poisson_path, check_binning_path, check_planes_path, check_weights_path, read_detector_weights
 from .solver import FullfieldSolver
 from .util import print_flush
 
@@ -92,6 +92,13 @@ def reconstruct_fullfield(fname, theta_st=0, theta_end=PI, n_epochs='auto', crit
     # below the depth of focus.  Transfer-function propagator, lookup-table rotation and float32 sweeps; every multiscale
     # level's depth must divide by b.
     check_binning_path(slice_binning, propagator, kwargs.get('adjoint_precision'), kwargs.get('rotation', 'nearest'))
+    # free_prop_cm=[z_0, ..]: D detector planes per angle (holotomography; include/bdof.h, bdof_set_detector_planes).  The file's
+    # exchange/data is then (n_theta, D, Y, X), in the order of the distances.  Transfer-function propagator, lookup-table
+    # rotation, float32 sweeps, one detector_kernel ('TF' or 'IR') for all planes; a sequence of one is its scalar.
+    n_planes = check_planes_path(free_prop_cm, propagator, kwargs.get('adjoint_precision'), kwargs.get('rotation', 'nearest'),
+                                 detector_kernel=kwargs.get('detector_kernel', 'TF'))
+    if n_planes > 1 and probe_type == 'optimizable' and probe_initial is None:
+        raise ValueError("several detector planes with probe_type='optimizable' need probe_initial: the initial guess back-propagates one plane")
     # gradient accumulation over n_batch_per_update minibatches exists only in the TF twin (tensorflow_recon/fullfield.py:
     # 413-425); the cnn variant accepts the keyword and ignores it (default 5!), so it is opt-in here
     accumulate = bool(kwargs.get('accumulate_gradients', False))
@@ -102,6 +109,11 @@ def reconstruct_fullfield(fname, theta_st=0, theta_end=PI, n_epochs='auto', crit
     print_flush('Reading data...', 0, rank)
     t0 = time.time()
     prj_0 = np.asarray(h5io.read_dataset(os.path.join(save_path, fname))).astype('complex64')
+    if n_planes > 1 and (prj_0.ndim != 4 or prj_0.shape[1] != n_planes):
+        raise ValueError('free_prop_cm holds {} detector planes: exchange/data must have the shape (n_theta, {}, Y, X), not {}'.format(
+            n_planes, n_planes, prj_0.shape))
+    if n_planes == 1 and prj_0.ndim == 4 and prj_0.shape[1] == 1:
+        prj_0 = prj_0[:, 0]                    # one plane written as (n_theta, 1, Y, X)
     theta = -np.linspace(theta_st, theta_end, prj_0.shape[0], dtype='float32')
     weights_0 = read_detector_weights(detector_weights, os.path.join(save_path, fname), prj_0.shape[-2:])
     if theta_downsample is not None:
@@ -116,7 +128,7 @@ def reconstruct_fullfield(fname, theta_st=0, theta_end=PI, n_epochs='auto', crit
         output_folder = ('recon_360_minibatch_{}_mskrls_{}_shrink_{}_iter_{}_alphad_{}_alphab_{}_gamma_{}_rate_{}_energy_{}_'
                          'size_{}_ntheta_{}_prop_{}_ms_{}_cpu_{}').format(
             minibatch_size, n_epochs_mask_release, shrink_cycle, n_epochs, alpha_d, alpha_b, gamma, learning_rate, energy_ev,
-            prj_0.shape[-1], prj_0.shape[0], free_prop_cm, multiscale_level, cpu_only)
+            prj_0.shape[-1], prj_0.shape[0], free_prop_cm if n_planes == 1 else '_'.join(str(z) for z in free_prop_cm), multiscale_level, cpu_only)
         if abs(PI - theta_end) < 1e-3:
             output_folder += '_180'
     if save_path != '.':
@@ -134,7 +146,7 @@ def reconstruct_fullfield(fname, theta_st=0, theta_end=PI, n_epochs='auto', crit
     for ds_level in range(multiscale_level - 1, -1, -1):
         ds_level = 2 ** ds_level
         print_flush('Multiscale downsampling level: {}'.format(ds_level), 0, rank)
-        prj = prj_0[:, ::ds_level, ::ds_level] if ds_level > 1 else prj_0
+        prj = prj_0[..., ::ds_level, ::ds_level] if ds_level > 1 else prj_0
         dim_y, dim_x = prj.shape[-2:]
         weights = weights_0 if weights_0 is None or ds_level == 1 else weights_0[::ds_level, ::ds_level]      # strided as the data are
         if minibatch_size is None:
@@ -142,7 +154,7 @@ def reconstruct_fullfield(fname, theta_st=0, theta_end=PI, n_epochs='auto', crit
         if n_epochs_mask_release is None:
             n_epochs_mask_release = np.inf
 
-        mask = _read_mask(save_path, prj_0.shape[1])
+        mask = _read_mask(save_path, prj_0.shape[-2])
         if mask is not None and ds_level > 1:
             mask = mask[::ds_level, ::ds_level, ::ds_level]
         dim_z = mask.shape[-1] if mask is not None else dim_x

@@ -25,12 +25,15 @@ def multislice_propagate_batch_numpy(grid_delta_batch, grid_beta_batch, probe_re
     """cnn_propagator/np_funcs.py:15-65.  Returns (wavefront[B,Y,X] complex64, probe_array[S,B,Y,X]).
 
     `variant` and `return_probe_array` are extensions: 'tf_all' propagates after the last slice too
-    (tensorflow_recon/util.py:465-483); return_probe_array=False skips the per-slice history."""
+    (tensorflow_recon/util.py:465-483); return_probe_array=False skips the per-slice history.  free_prop_cm as a sequence of D
+    distances (several detector planes, MultisliceEngine.set_physics): the wavefront is [B,D,Y,X], in the order of the distances."""
     if obj_batch_shape is None:
         obj_batch_shape = grid_delta_batch.shape
     B, ny, nx, n_slice = [int(s) for s in obj_batch_shape]
     want_tape = bool(return_probe_array) and variant == 'numpy_skip_last'
     eng = _engine(ny, nx, n_slice, B, with_grad=want_tape)
+    if util.detector_distances(free_prop_cm)[1] is not None:
+        eng.set_probe_none()        # the cached engine's last probe (it may ride on a carrier field) is not this call's
     eng.set_physics(energy_ev, psize_cm, free_prop_cm, variant=variant)
     eng.set_probe(probe_real, probe_imag)
     eng.set_object_batch(np.asarray(grid_delta_batch)[:B], np.asarray(grid_beta_batch)[:B])

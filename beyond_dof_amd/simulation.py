@@ -12,6 +12,7 @@ from scipy.ndimage import gaussian_filter
 from scipy.ndimage import rotate as sp_rotate
 
 from . import h5io, tiffio, util
+from .engine import check_planes_path
 from .np_funcs import multislice_propagate_batch_numpy
 
 PI = util.PI
@@ -48,7 +49,9 @@ def _check_target(path, overwrite):
 def create_fullfield_data_numpy(energy_ev, psize_cm, free_prop_cm, n_theta, phantom_path, save_folder, fname, batch_size=1,
                                 probe_type='plane', wavefront_initial=None, theta_st=0, theta_end=2 * PI,
                                 monitor_output=False, overwrite=False, **kwargs):
-    """cnn_propagator/simulation.py:80-161.  Writes (n_theta, Y, X) complex64 to save_folder/fname."""
+    """cnn_propagator/simulation.py:80-161.  Writes (n_theta, Y, X) complex64 to save_folder/fname — with free_prop_cm a sequence
+    of D distances (several detector planes per angle) (n_theta, D, Y, X), in the order of the distances."""
+    n_planes = check_planes_path(free_prop_cm)
     obj = _load_phantom(phantom_path)
     img_dim = obj.shape[:3]
     path = os.path.join(save_folder, fname)
@@ -64,7 +67,7 @@ def create_fullfield_data_numpy(energy_ev, psize_cm, free_prop_cm, n_theta, phan
         raise ValueError("Invalid wavefront type. Choose from 'plane', 'fixed' or 'gaussian'.")
     theta_ls = -np.linspace(theta_st, theta_end, n_theta) / np.pi * 180
     theta_batch = np.array_split(theta_ls, int(np.ceil(float(n_theta) / batch_size)))
-    dat = np.zeros((n_theta, img_dim[0], img_dim[1]), dtype=np.complex64)
+    dat = np.zeros((n_theta,) + ((n_planes,) if n_planes > 1 else ()) + (img_dim[0], img_dim[1]), dtype=np.complex64)
     pos = 0
     for i_batch, this_theta_batch in enumerate(theta_batch):
         rot = np.array([sp_rotate(obj, theta, reshape=False, axes=(1, 2)) for theta in this_theta_batch])
@@ -72,7 +75,7 @@ def create_fullfield_data_numpy(energy_ev, psize_cm, free_prop_cm, n_theta, phan
                                                        free_prop_cm=free_prop_cm, obj_batch_shape=rot.shape[:-1],
                                                        return_probe_array=False)
         if monitor_output:
-            tiffio.write_tiff(np.abs(wave_out), os.path.join(save_folder, 'monitor_output', 'prj_{}'.format(i_batch)),
+            tiffio.write_tiff(np.abs(wave_out).reshape((-1,) + wave_out.shape[-2:]), os.path.join(save_folder, 'monitor_output', 'prj_{}'.format(i_batch)),
                               dtype='float32', overwrite=True)
         dat[pos:pos + len(this_theta_batch)] = wave_out
         pos += len(this_theta_batch)

@@ -24,7 +24,7 @@ from . import _lib
 from ._lib import DeviceBuffer
 from . import util
 from .comm import PseudoComm
-from .engine import MultisliceEngine, RESIDENT_SIZES, check_poisson_path, check_binning_path, check_weights_path
+from .engine import MultisliceEngine, RESIDENT_SIZES, check_poisson_path, check_binning_path, check_planes_path, check_weights_path
 
 
 class _VolumeSolver(object):
@@ -389,6 +389,8 @@ class FullfieldSolver(_VolumeSolver):
         pixel takes no part), set before any measurement is bound; propagator='fft' only.
         slice_binning: voxel slices per propagation step (MultisliceEngine); > 1 with propagator='fft', rotation='nearest' and
         no adjoint64 only.
+        free_prop_cm as a sequence of D distances: D detector planes per angle (MultisliceEngine.set_physics) — measurements and
+        forward_angles are then (n, D, Y, X); with propagator='fft', rotation='nearest', the tape and no adjoint64 only.
         propagator='fft': the transfer-function step of np_funcs.py (north-star path); 'conv': the truncated real-space
         kernel of propagation.py, what cnn_propagator/fullfield.py:87,102 calls (kernel_size taps per axis).
         rotation='nearest': the cnn variant's lookup tables, fused into the kernels (cnn_propagator/util.py:294-402);
@@ -398,6 +400,8 @@ class FullfieldSolver(_VolumeSolver):
         check_poisson_path(loss_type, poisson_multiplier, propagator)
         check_weights_path(detector_weights, propagator)
         check_binning_path(slice_binning, propagator, 'float64' if adjoint64 else None, rotation if rotation == 'bilinear' else 'nearest')
+        self.n_planes = check_planes_path(free_prop_cm, propagator, 'float64' if adjoint64 else None, rotation if rotation == 'bilinear' else 'nearest',
+                                          recompute=recompute, detector_kernel=detector_kernel)
         self.conv = propagator == 'conv'
         self.bilinear = rotation == 'bilinear'
         if adjoint64 not in (None, False, True, 'first'):
@@ -444,8 +448,8 @@ class FullfieldSolver(_VolumeSolver):
             # rotation lookup tables (cnn_propagator/util.py:294-347), uploaded once
             self._upload_rotation_tables(coord_ls)
         self._init_volume()
-        self.meas_stage = DeviceBuffer(self.ctx, self.mb * self.dim_x * self.dim_y * 4, np.float32,
-                                       (self.mb, self.dim_x, self.dim_y))
+        self.meas_stage = DeviceBuffer(self.ctx, self.mb * self.n_planes * self.dim_x * self.dim_y * 4, np.float32,
+                                       (self.mb, self.dim_x, self.dim_y) if self.n_planes == 1 else (self.mb, self.n_planes, self.dim_x, self.dim_y))
         self.angle_buf = DeviceBuffer(self.ctx, self.mb * 4, np.int32, (self.mb,))
         self._bind_volume()
         if not self.bilinear:
@@ -466,7 +470,8 @@ class FullfieldSolver(_VolumeSolver):
                                                     int(self.conv)))
 
     def set_measurements(self, prj_abs):
-        """|prj| for every angle, (n_theta, Y, X) (loss uses np.abs(this_prj_batch), fullfield.py:106).  The residual stays split
+        """|prj| for every angle, (n_theta, Y, X) — with D detector planes (n_theta, D, Y, X) — (loss uses np.abs(this_prj_batch),
+        fullfield.py:106).  The residual stays split
         or not by what these amplitudes are (MultisliceEngine.choose_residual_split)."""
         self.eng.choose_residual_split(prj_abs)
         self.meas = DeviceBuffer.from_host(self.ctx, self.eng.meas_layout(prj_abs))
@@ -477,9 +482,9 @@ class FullfieldSolver(_VolumeSolver):
         idx = np.asarray(angle_idx, dtype=np.int32)
         assert len(idx) == self.mb
         self.angle_buf.upload(idx)
-        # this_prj_batch = prj[this_ind_batch] (fullfield.py:344): one gather launch on the resident stack
+        # this_prj_batch = prj[this_ind_batch] (fullfield.py:344): one gather launch on the resident stack (an angle's planes are one item)
         self.ctx.check(lib.bdof_gather_fields(h, self.meas_stage.ptr, self.meas.ptr, self.angle_buf.ptr, self.mb,
-                                              self.dim_x * self.dim_y * 4))
+                                              self.n_planes * self.dim_x * self.dim_y * 4))
 
     def _rot_loss_grad(self, angle_idx, f64=False):
         """Forward + adjoint sweeps of this rank's angles: the gradient w.r.t. the rotated objects stays in the ctx.
@@ -572,7 +577,8 @@ class FullfieldSolver(_VolumeSolver):
         return self._get_loss() if want_loss else None          # the loss of THIS minibatch stays on the device until the next one
 
     def forward_angles(self, angle_idx):
-        """Detector waves (len(idx), Y, X) of the current volume — the forward_pass of fullfield.py:79-91."""
+        """Detector waves (len(idx), Y, X) of the current volume — the forward_pass of fullfield.py:79-91; with D detector planes
+        (len(idx), D, Y, X)."""
         idx = np.asarray(angle_idx, dtype=np.int32)
         out = []
         for i in range(0, len(idx), self.mb):

@@ -112,14 +112,45 @@ def transfer_function_dc(dist_nm, lmbda_nm, voxel_nm, ny, nx, pi=PI, field_shape
     return v.real, v.imag
 
 
+MAX_DETECTOR_PLANES = 8      # BDOF_MAX_PLANES (include/bdof.h): detector planes per wavefield
+
+
+def detector_distances(free_prop_cm):
+    """free_prop_cm as every layer takes it -> (free_prop_cm, planes): None, 'inf' or a distance pass as they are, with planes
+    None; a sequence of D finite positive distances in cm (several detector planes per angle, bdof_set_detector_planes) comes
+    back as a tuple of floats with planes = that tuple — except a sequence of one, which IS its scalar (planes None).  Raises
+    ValueError for anything else inside a sequence (None, 'inf', zero, negative, non-finite) and for more than
+    MAX_DETECTOR_PLANES entries."""
+    if isinstance(free_prop_cm, str):
+        if free_prop_cm != 'inf':
+            raise ValueError("free_prop_cm must be None, a distance in cm, a sequence of distances or 'inf'")
+        return free_prop_cm, None
+    if free_prop_cm is None or np.ndim(free_prop_cm) == 0:
+        return free_prop_cm, None
+    seq = list(free_prop_cm) if np.ndim(free_prop_cm) == 1 else None
+    if not seq:
+        raise ValueError('free_prop_cm as a sequence holds one distance per detector plane: at least one, in one dimension')
+    if len(seq) > MAX_DETECTOR_PLANES:
+        raise ValueError('free_prop_cm holds {} detector planes, more than the {} that are carried'.format(len(seq), MAX_DETECTOR_PLANES))
+    for d in seq:
+        if isinstance(d, (str, bool)) or d is None or not isinstance(d, (int, float, np.integer, np.floating)) or not np.isfinite(d) or not d > 0:
+            raise ValueError('free_prop_cm as a sequence of detector planes takes finite distances > 0 in cm, not {!r}'.format(d))
+    if len(seq) == 1:
+        return seq[0], None
+    return tuple(float(d) for d in seq), tuple(float(d) for d in seq)
+
+
 class Optics(object):
     """Units and propagation multipliers of one (ny, nx) wavefield geometry: what the engine and the tiled propagator take
-    every wavelength, voxel size, k and transfer-function table from.  free_prop_cm: None (no detector step), a distance in cm
-    or 'inf' (far field); field_shape: the wavefield is a tile of a (FY, FX) field (get_kernel_tile)."""
+    every wavelength, voxel size, k and transfer-function table from.  free_prop_cm: None (no detector step), a distance in cm,
+    a sequence of distances (detector planes, detector_distances: det_planes_nm holds them and det_nm the first; a sequence of
+    one is its scalar) or 'inf' (far field); field_shape: the wavefield is a tile of a (FY, FX) field (get_kernel_tile)."""
 
     def __init__(self, energy_ev, psize_cm, free_prop_cm, pi, ny, nx, field_shape=None):
-        if isinstance(free_prop_cm, str) and free_prop_cm != 'inf':
-            raise ValueError("free_prop_cm must be None, a distance in cm or 'inf'")
+        free_prop_cm, planes = detector_distances(free_prop_cm)
+        self.det_planes_nm = None if planes is None else tuple(d * 1e7 for d in planes)
+        if planes is not None:
+            free_prop_cm = planes[0]
         self.voxel_nm = np.array([psize_cm] * 3) * 1.e7 if np.isscalar(psize_cm) else np.array(psize_cm) * 1.e7
         self.lmbda_nm = 1240. / energy_ev
         self.delta_nm = self.voxel_nm[-1]                      # slice thickness
@@ -127,6 +158,7 @@ class Optics(object):
         self.k = 2. * pi * self.delta_nm / self.lmbda_nm
         self.det_nm = None if free_prop_cm is None or isinstance(free_prop_cm, str) else free_prop_cm * 1e7
         self.ny, self.nx, self.field_shape = int(ny), int(nx), field_shape
+        self.n_planes = 1 if self.det_planes_nm is None else len(self.det_planes_nm)      # frames per wavefield at the detector
 
     def _args(self, tiled, kernel='TF'):
         return self.lmbda_nm, self.voxel_nm, self.ny, self.nx, self.pi, self.field_shape if tiled else None, kernel

@@ -11,6 +11,8 @@ reference.
 
 --loss poisson minimises the photon-counting likelihood (loss_type='poisson'); its data term is ~ 2 * multiplier times the
 least-squares one, and the L1 weights are scaled with it here.
+free_prop_cm=5e-4,1e-3,2e-3 (distances separated by commas) simulates and fits several detector planes per angle: the data file
+is then (n_theta, D, Y, X) and run(..., fp=(5e-4, 1e-3, 2e-3)) is the same from Python.
 --slice-binning b reconstructs with one propagation step per b voxel slices (slice_binning=b); the data are always simulated
 with one step per voxel slice.
 """
@@ -91,7 +93,7 @@ def main():
     n_epochs = int(sys.argv[3]) if len(sys.argv) > 3 else 100
     lr = float(sys.argv[4]) if len(sys.argv) > 4 else 2e-8
     fp = sys.argv[5] if len(sys.argv) > 5 else '1e-3'
-    fp = 'inf' if fp == 'inf' else float(fp)
+    fp = 'inf' if fp == 'inf' else tuple(float(z) for z in fp.split(',')) if ',' in fp else float(fp)
     mb = int(sys.argv[6]) if len(sys.argv) > 6 else 10
     propagator = sys.argv[7] if len(sys.argv) > 7 else 'fft'
     r = run(n, n_theta, n_epochs, lr, fp, mb=mb, propagator=propagator, loss=loss, multiplier=multiplier, slice_binning=slice_binning)

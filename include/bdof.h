@@ -313,6 +313,27 @@ int bdof_set_loss(bdof_ctx* ctx, int kind, double multiplier);
  * With weights set, bdof_loss_grad_conv, bdof_loss_grad_conv_f64 and bdof_field_loss_seed fail (bdof_last_error). */
 int bdof_set_detector_weights(bdof_ctx* ctx, const float* w);
 
+/* Detector planes: D >= 1 near-field planes per wavefield, at distances z_0 .. z_{D-1} behind the exit wave (propagation-based
+ * phase contrast recorded at several distances, holotomography).  With psi the wave that enters the detector step — phi_{S-1}
+ * under numpy_skip_last, P phi_{S-1} under tf_all — and P(z_j) the step with plane j's transfer function
+ *     d_j  = P(z_j) psi                                    j = 0 .. D-1, in the order given
+ *     L    = sum_j sum(l(d_j, m_j)) / (B D NX NY)          — the data term of bdof_set_loss as the mean over B D frames;
+ *                                                            the seed scale is 2 / (B D NX NY)
+ *     G(psi) = sum_j P(z_j)^H G(d_j)                       — the sweep back through the object is unchanged
+ * hs_det: HOST [D][ky][kx] complex64 tables, each as bdof_set_physics takes its one hs_det (un-shifted, 1/(NX NY) folded in);
+ * hdet00: HOST [D] complex128 DC values (re, im) of the un-folded tables.  Valid after bdof_set_physics with BDOF_DET_NEAR.
+ * With D > 1 set, `meas` of bdof_loss_grad and `out_wave` of bdof_forward / bdof_loss_grad are [B][D][NX][NY]; detector
+ * weights stay one plane, shared by all D; residual splitting carries over (every transfer function has unit modulus at DC).
+ * D = 1, or hs_det = NULL, goes back to the one plane of bdof_set_physics, whose results this call does not move by a bit; so
+ * do bdof_configure and bdof_set_physics (the planes do not survive them).  D outside [1, BDOF_MAX_PLANES]: BDOF_ERR_ARG.
+ * Carried by the streaming engine (two-kernel and fused sweeps, slice binning) and the generic engine; the resident engine is
+ * not taken.  Everything else refuses, with "detector planes" in bdof_last_error: BDOF_CFG_RECOMPUTE, BDOF_CFG_ADJOINT64 and
+ * bdof_loss_grad_tf_f64, the real-space propagator (bdof_*_conv*), a carrier field (bdof_set_probe_stack /
+ * bdof_set_probe_field), the range calls (bdof_forward_range*, bdof_adjoint_range, bdof_set_range_carrier), and a detector
+ * mode other than BDOF_DET_NEAR. */
+#define BDOF_MAX_PLANES 8
+int bdof_set_detector_planes(bdof_ctx* ctx, int D, const float* hs_det, const double* hdet00);
+
 /* The adjoint carrier the last bdof_loss_grad left (far-field detector under a plane-wave probe on the streaming and generic
  * engines): per wavefield the float64 seed of the DC bin, gcar[b], and conj(a_end) gcar[b], gt0[b] — HOST arrays of B complex
  * doubles (re, im).  Returns 1 and fills them where the configuration carries the DC seed that way, 0 (nothing written) where it
