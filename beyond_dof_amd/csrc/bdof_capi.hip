@@ -248,21 +248,43 @@ static int check_batch(bdof_ctx* c, int B) {
 static int check_range(bdof_ctx* c, int z0, int nz) {
     return z0 < 0 || nz < 1 || z0 + nz > c->S ? fail(c, BDOF_ERR_ARG, "slice range outside [0, S)") : 0;
 }
-// the entry points that only know the least-squares data term
-static int need_lsq(bdof_ctx* c, const char* who) {
-    return c->loss_kind == BDOF_LOSS_LSQ ? 0 : fail(c, BDOF_ERR_STATE, std::string(who) + " computes the least-squares loss only: bdof_set_loss(BDOF_LOSS_LSQ) first");
+// ---- the model's options: which entry point carries which ----------------------------------------------------------------------
+// An option is in force on a ctx (`on`) or not; an entry point states the options it carries and admit() refuses it under any
+// other one that is in force, in the order of the table.  bdof_loss_grad, bdof_forward and the rest of the main path carry all
+// four and make no call.
+enum { CARRIES_NOTHING = 0, CARRIES_BINNING = 1, CARRIES_PLANES = 2, CARRIES_POISSON = 4, CARRIES_WEIGHTS = 8,
+       NO_DATA_TERM = CARRIES_POISSON | CARRIES_WEIGHTS };       // an entry point that computes no loss: the data term's options pass
+struct ModelOption { int bit; bool (*on)(const bdof_ctx*); const char* refusal; };       // (the refusal follows the caller's name)
+static const ModelOption MODEL_OPTIONS[] = {
+    {CARRIES_BINNING, [](const bdof_ctx* c) { return c->bin > 1; }, " does not carry slice binning: it would run the unbinned model (bdof_set_slice_binning)"},
+    {CARRIES_PLANES, [](const bdof_ctx* c) { return c->planes > 1; }, " does not carry detector planes: bdof_set_detector_planes(ctx, 1, NULL, NULL) first"},
+    {CARRIES_POISSON, [](const bdof_ctx* c) { return c->loss_kind != BDOF_LOSS_LSQ; }, " computes the least-squares loss only: bdof_set_loss(BDOF_LOSS_LSQ) first"},
+    {CARRIES_WEIGHTS, [](const bdof_ctx* c) { return (bool)c->wgt; }, " does not carry detector weights: bdof_set_detector_weights(ctx, NULL) first"},
+};
+// (no ctx: passes, and the entry point's own argument check answers)
+static int admit(bdof_ctx* c, const char* who, int carries) {
+    if (!c) return 0;
+    for (const ModelOption& o : MODEL_OPTIONS)
+        if (!(carries & o.bit) && o.on(c)) return fail(c, BDOF_ERR_STATE, std::string(who) + o.refusal);
+    return 0;
 }
-// ... and no detector weights (bdof_set_detector_weights names them)
-static int need_unweighted(bdof_ctx* c, const char* who) {
-    return !c->wgt ? 0 : fail(c, BDOF_ERR_STATE, std::string(who) + " does not carry detector weights: bdof_set_detector_weights(ctx, NULL) first");
-}
-// the entry points that take one propagation step per voxel slice only (bdof_set_slice_binning names them)
-static int need_unbinned(bdof_ctx* c, const char* who) {
-    return !c || c->bin == 1 ? 0 : fail(c, BDOF_ERR_STATE, std::string(who) + " does not carry slice binning: it would run the unbinned model (bdof_set_slice_binning)");
-}
-// the entry points that know one detector plane only (bdof_set_detector_planes names them)
-static int need_one_plane(bdof_ctx* c, const char* who) {
-    return !c || c->planes == 1 ? 0 : fail(c, BDOF_ERR_STATE, std::string(who) + " does not carry detector planes: bdof_set_detector_planes(ctx, 1, NULL, NULL) first");
+
+// The reverse direction: the modes of a ctx that an option can collide with.  A setter names the ones that do not carry its
+// option, in the order it reports them.
+struct CtxMode { bool (*on)(const bdof_ctx*); const char* name; };
+static const CtxMode MODE_RESIDENT = {[](const bdof_ctx* c) { return c->res_always; }, "the LDS-resident engine (BDOF_CFG_ALWAYS_RESIDENT)"};
+static const CtxMode MODE_RECOMPUTE = {[](const bdof_ctx* c) { return c->recompute; }, "the tape-free adjoint (BDOF_CFG_RECOMPUTE)"};
+static const CtxMode MODE_ADJOINT64 = {[](const bdof_ctx* c) { return c->adj64; }, "the float64 adjoint sweep (BDOF_CFG_ADJOINT64)"};
+static const CtxMode MODE_NO_GROT = {[](const bdof_ctx* c) { return c->with_grad && !c->grot; }, "a ctx without the gradient workspace (BDOF_CFG_NO_GROT)"};
+static const CtxMode MODE_NOT_NEAR = {[](const bdof_ctx* c) { return c->det_mode != BDOF_DET_NEAR; }, "a detector mode other than BDOF_DET_NEAR"};
+static const CtxMode MODE_CONV = {[](const bdof_ctx* c) { return c->have_conv; }, "the real-space propagator (bdof_set_conv)"};
+static const CtxMode MODE_CARRIER_FIELD = {[](const bdof_ctx* c) { return (bool)c->pstack; }, "a carrier field (bdof_set_probe_stack / bdof_set_probe_field)"};
+static const CtxMode MODE_RANGE_CARRIER = {[](const bdof_ctx* c) { return c->range_car != nullptr; }, "range carriers (bdof_set_range_carrier)"};
+// "<setter>: <mode> does not carry <option>" for the first of `refused` that is on
+static int refuse_modes(bdof_ctx* c, const char* setter, const char* option, std::initializer_list<const CtxMode*> refused) {
+    for (const CtxMode* m : refused)
+        if (m->on(c)) return fail(c, BDOF_ERR_STATE, std::string(setter) + ": " + m->name + " does not carry " + option);
+    return 0;
 }
 // back to the one plane of bdof_set_physics: tables and the planes' fields go
 static void drop_planes(bdof_ctx* c) {
@@ -1520,11 +1542,8 @@ int bdof_set_slice_binning(bdof_ctx* c, int bin) {
     if (!StepIndex::valid(c->S, bin)) return fail(c, BDOF_ERR_ARG, "bdof_set_slice_binning: bin must be >= 1 and divide S (a shorter last bin is not carried)");
     if (c->have_physics || c->have_probe)
         return fail(c, BDOF_ERR_STATE, "bdof_set_slice_binning comes right after bdof_configure: the tables of bdof_set_physics and the carrier fields are per propagation step");
-    if (bin > 1) {
-        const char* why = c->res_always ? "the LDS-resident engine (BDOF_CFG_ALWAYS_RESIDENT)" : c->recompute ? "the tape-free adjoint (BDOF_CFG_RECOMPUTE)"
-                        : c->adj64 ? "the float64 adjoint sweep (BDOF_CFG_ADJOINT64)" : c->with_grad && !c->grot ? "a ctx without the gradient workspace (BDOF_CFG_NO_GROT)" : nullptr;
-        if (why) return fail(c, BDOF_ERR_STATE, std::string("bdof_set_slice_binning: ") + why + " does not carry slice binning");
-    }
+    if (bin > 1)
+        if (int r = refuse_modes(c, "bdof_set_slice_binning", "slice binning", {&MODE_RESIDENT, &MODE_RECOMPUTE, &MODE_ADJOINT64, &MODE_NO_GROT})) return r;
     HIPC(c, hipSetDevice(c->device));
     HIPC(c, hipStreamSynchronize(c->stream));
     if (c->with_grad && bin != c->bin) HIPC(c, c->tape.alloc((size_t)c->Bmax * c->NX * c->NY * StepIndex{c->S, bin}.tape_fields()));     // one field per step
@@ -1747,10 +1766,8 @@ int bdof_set_detector_planes(bdof_ctx* c, int D, const float* hs_det, const doub
     if (D == 1 || !hs_det) { drop_planes(c); return 0; }
     if (!hdet00) return fail(c, BDOF_ERR_ARG, "bdof_set_detector_planes: hdet00 required with the tables");
     if (!c->have_physics) return fail(c, BDOF_ERR_STATE, "bdof_set_detector_planes comes after bdof_set_physics");
-    const char* why = c->det_mode != BDOF_DET_NEAR ? "a detector mode other than BDOF_DET_NEAR" : c->recompute ? "the tape-free adjoint (BDOF_CFG_RECOMPUTE)"
-                    : c->adj64 ? "the float64 adjoint sweep (BDOF_CFG_ADJOINT64)" : c->have_conv ? "the real-space propagator (bdof_set_conv)"
-                    : c->pstack ? "a carrier field (bdof_set_probe_stack / bdof_set_probe_field)" : c->range_car ? "range carriers (bdof_set_range_carrier)" : nullptr;
-    if (why) return fail(c, BDOF_ERR_STATE, std::string("bdof_set_detector_planes: ") + why + " does not carry detector planes");
+    if (int r = refuse_modes(c, "bdof_set_detector_planes", "detector planes",
+                             {&MODE_NOT_NEAR, &MODE_RECOMPUTE, &MODE_ADJOINT64, &MODE_CONV, &MODE_CARRIER_FIELD, &MODE_RANGE_CARRIER})) return r;
     drop_planes(c);
     const size_t n = (size_t)c->NX * c->NY, fields = (size_t)c->Bmax * D * n;
     // the combined tables of tf_all, formed as bdof_set_physics forms its one: from the float32 slice step the ctx holds
@@ -1804,7 +1821,7 @@ int bdof_set_probe_stack(bdof_ctx* c, const float* stack, const float* det) {
     c->mod_dirty = true;
     if (!stack && !det) return 0;
     if (!stack || !det) return fail(c, BDOF_ERR_ARG, "bdof_set_probe_stack: both arrays or neither");
-    if (int r = need_one_plane(c, "a carrier field (bdof_set_probe_stack)")) return r;
+    if (int r = admit(c, "a carrier field (bdof_set_probe_stack)", CARRIES_BINNING | NO_DATA_TERM)) return r;
     const size_t n = (size_t)c->NX * c->NY, fld = sizeof(cf) * n;
     HIPC(c, c->pstack.alloc(n * steps(c).stack_planes()));       // one plane per propagation step
     HIPC(c, c->pdet.alloc(n));
@@ -1830,7 +1847,7 @@ int bdof_set_probe_field(bdof_ctx* c, const double* probe, const double* hT, con
     if (!c || !probe || !hT) return BDOF_ERR_ARG;
     if (!c->have_physics) return fail(c, BDOF_ERR_STATE, "bdof_set_physics has not been called");
     if (c->det_mode == BDOF_DET_NEAR && !hdetT) return fail(c, BDOF_ERR_ARG, "hdetT required for BDOF_DET_NEAR");
-    if (int r = need_one_plane(c, "a carrier field (bdof_set_probe_field)")) return r;
+    if (int r = admit(c, "a carrier field (bdof_set_probe_field)", CARRIES_BINNING | NO_DATA_TERM)) return r;
     HIPC(c, hipSetDevice(c->device));
     HIPC(c, hipStreamSynchronize(c->stream));
     const size_t n = (size_t)c->NX * c->NY, fld = sizeof(cf) * n, dbytes = sizeof(double2) * n;
@@ -2025,8 +2042,7 @@ static int forward_range(bdof_ctx* c, int B, const int* angle_of_b, const int* x
 
 int bdof_forward_range(bdof_ctx* c, int B, const int* angle_of_b, const int* xoff, const int* yoff, int z0, int nz,
                        const void* in_real, void* out_real, int prop_last) {
-    if (int rb = need_unbinned(c, "bdof_forward_range")) return rb;
-    if (int rp = need_one_plane(c, "bdof_forward_range")) return rp;
+    if (int r = admit(c, "bdof_forward_range", NO_DATA_TERM)) return r;
     if (!c) return BDOF_ERR_ARG;
     return forward_range(c, B, angle_of_b, xoff, yoff, z0, nz, in_real, out_real, prop_last, c->hs);
 }
@@ -2037,8 +2053,7 @@ int bdof_forward_range(bdof_ctx* c, int B, const int* angle_of_b, const int* xof
 // carrier IS the incoming wave) and `out_real` receives the scattered part leaving it — for the tiles of a corrected stitch range
 // exactly T psi - T_free psi, without the round-off of two full-amplitude sweeps.  NULL removes the stack.
 int bdof_set_range_carrier(bdof_ctx* c, const void* stack, int B, int z0, int nz) {
-    if (int rb = need_unbinned(c, "bdof_set_range_carrier")) return rb;
-    if (int rp = need_one_plane(c, "bdof_set_range_carrier")) return rp;
+    if (int r = admit(c, "bdof_set_range_carrier", NO_DATA_TERM)) return r;
     if (!c) return BDOF_ERR_ARG;
     if (!stack) { c->range_car = nullptr; c->range_car_B = 0; return 0; }
     if (int r = need_configured(c)) return r;
@@ -2053,8 +2068,7 @@ int bdof_set_range_carrier(bdof_ctx* c, const void* stack, int B, int z0, int nz
 
 int bdof_forward_range_h(bdof_ctx* c, int B, const int* angle_of_b, const int* xoff, const int* yoff, int z0, int nz,
                          const void* in_real, void* out_real, int prop_last, const void* h) {
-    if (int rb = need_unbinned(c, "bdof_forward_range_h")) return rb;
-    if (int rp = need_one_plane(c, "bdof_forward_range_h")) return rp;
+    if (int r = admit(c, "bdof_forward_range_h", NO_DATA_TERM)) return r;
     if (!c || !h) return BDOF_ERR_ARG;
     return forward_range(c, B, angle_of_b, xoff, yoff, z0, nz, in_real, out_real, prop_last, (const cf*)h);
 }
@@ -2072,8 +2086,7 @@ static void launch_real_to_hyb(bdof_ctx* c, const Group& g, const cf* in, cf* ou
 // g_start_real receives G(psi_{z0}); the gradient rows of the range go to grot_range [B][nz][NX][NY] (pairs).
 int bdof_adjoint_range(bdof_ctx* c, int B, const int* angle_of_b, const int* xoff, const int* yoff, int z0, int nz,
                        const void* end_real, const void* g_end_real, void* g_start_real, void* grot_range) {
-    if (int rb = need_unbinned(c, "bdof_adjoint_range")) return rb;
-    if (int rp = need_one_plane(c, "bdof_adjoint_range")) return rp;
+    if (int r = admit(c, "bdof_adjoint_range", NO_DATA_TERM)) return r;
     int r = check_ready(c, B);
     if (r) return r;
     if (!end_real || !g_end_real || !g_start_real || !grot_range) return BDOF_ERR_ARG;
@@ -2115,8 +2128,7 @@ int bdof_adjoint_range(bdof_ctx* c, int B, const int* angle_of_b, const int* xof
 int bdof_field_loss_seed(bdof_ctx* c, void* field, const float* meas, int FX, int FY) {
     if (!c || !field || !meas || FX < 1 || FY < 1) return BDOF_ERR_ARG;
     if (!c->partial) return fail(c, BDOF_ERR_STATE, "bdof_configure has not been called");
-    if (int r = need_lsq(c, "bdof_field_loss_seed")) return r;
-    if (int r = need_unweighted(c, "bdof_field_loss_seed")) return r;
+    if (int r = admit(c, "bdof_field_loss_seed", CARRIES_BINNING | CARRIES_PLANES)) return r;      // (a whole field: no sweep, no detector step)
     HIPC(c, hipSetDevice(c->device));
     const size_t n = (size_t)FX * FY;
     const int egrid = g_elem_grid(c, n);
@@ -2221,8 +2233,7 @@ int bdof_fields_free_step_aux(bdof_ctx* c, void* fields, const void* src, int B,
 // spectra s_hat H^z by a running product, ONE batched inverse transform of all of them, one conversion.  h: complex128 [kx][ky],
 // ifftshift(H) / (NX NY).
 int bdof_range_carrier_build(bdof_ctx* c, void* p0, void* stack, int B, int NX, int NY, const void* h, int nz) {
-    if (int rb = need_unbinned(c, "bdof_range_carrier_build")) return rb;
-    if (int rp = need_one_plane(c, "bdof_range_carrier_build")) return rp;
+    if (int r = admit(c, "bdof_range_carrier_build", NO_DATA_TERM)) return r;
     if (!c || !p0 || !stack || !h || B < 1 || NX < 1 || NY < 1 || nz < 1) return BDOF_ERR_ARG;
     HIPC(c, hipSetDevice(c->device));
     const size_t per = (size_t)NX * NY, n = per * B;
@@ -2323,8 +2334,7 @@ int bdof_tiles_scatter_diff64(bdof_ctx* c, const void* tiles_a, const void* tile
 // rocFFT in double precision, h[kx][ky] = the transfer function / (NX NY) in float64.  cnn_propagator/np_funcs.py:36-43.
 int bdof_forward_range_f64(bdof_ctx* c, int B, const int* angle_of_b, const int* xoff, const int* yoff, int z0, int nz, void* fields,
                            const void* h, double k, int prop_last) {
-    if (int rb = need_unbinned(c, "bdof_forward_range_f64")) return rb;
-    if (int rp = need_one_plane(c, "bdof_forward_range_f64")) return rp;
+    if (int r = admit(c, "bdof_forward_range_f64", NO_DATA_TERM)) return r;
     if (!c || !fields || !h) return BDOF_ERR_ARG;
     if (int r = need_configured(c)) return r;
     if (!c->obj_src) return fail(c, BDOF_ERR_STATE, "bdof_set_object (with (delta, beta) rows) has not been called");
@@ -2374,8 +2384,7 @@ static int c64_room(bdof_ctx* c, int B, bool tf, size_t M) {
 // kernel zero-padded to M x M, transposed to [kx][ky] and divided by M^2; ksum = sum of the kernel's taps (the padding constant's
 // recursion, propagation.py:91,99); k = 2 pi dz / lambda with numpy's pi (propagation.py:25)
 int bdof_set_conv_f64(bdof_ctx* c, const double* probe, const double* khat, int ks, double ksum_re, double ksum_im, double k) {
-    if (int rb = need_unbinned(c, "bdof_set_conv_f64")) return rb;
-    if (int rp = need_one_plane(c, "bdof_set_conv_f64")) return rp;
+    if (int r = admit(c, "bdof_set_conv_f64", NO_DATA_TERM)) return r;
     if (!c || !probe || !khat) return BDOF_ERR_ARG;
     if (int r = need_configured(c)) return r;
     if (c->NX != c->NY) return fail(c, BDOF_ERR_SIZE, "the float64 real-space path takes square wavefields");
@@ -2403,8 +2412,7 @@ int bdof_set_conv_f64(bdof_ctx* c, const double* probe, const double* khat, int 
 // the step to a detector at a finite distance for the float64 real-space path (propagation.py:122-127: one transfer-function
 // step of the renormalised exit wave): hdetT host complex128 [kx][ky], ifftshift(H_det) / (NX NY); NULL removes it
 int bdof_set_conv_f64_detector(bdof_ctx* c, const double* hdetT) {
-    if (int rb = need_unbinned(c, "bdof_set_conv_f64_detector")) return rb;
-    if (int rp = need_one_plane(c, "bdof_set_conv_f64_detector")) return rp;
+    if (int r = admit(c, "bdof_set_conv_f64_detector", NO_DATA_TERM)) return r;
     if (!c) return BDOF_ERR_ARG;
     if (int r = need_configured(c)) return r;
     HIPC(c, hipSetDevice(c->device));
@@ -2422,12 +2430,9 @@ int bdof_set_conv_f64_detector(bdof_ctx* c, const double* hdetT) {
 // the host subtracted from the amplitudes (bdof_set_meas_mode 1), 0 otherwise.  Detector: none, far field, or near field after
 // bdof_set_conv_f64_detector.
 int bdof_loss_grad_conv_f64(bdof_ctx* c, int B, const int* angle_of_b, const int* xoff, const int* yoff, const float* meas, double meas_ref) {
-    if (int rb = need_unbinned(c, "bdof_loss_grad_conv_f64")) return rb;
-    if (int rp = need_one_plane(c, "bdof_loss_grad_conv_f64")) return rp;
+    if (int r = admit(c, "bdof_loss_grad_conv_f64", CARRIES_NOTHING)) return r;
     if (!c || !meas) return BDOF_ERR_ARG;
     if (!c->c64_ks || c->c64_tf) return fail(c, BDOF_ERR_STATE, "bdof_set_conv_f64 has not been called");
-    if (int rl = need_lsq(c, "bdof_loss_grad_conv_f64")) return rl;
-    if (int rw = need_unweighted(c, "bdof_loss_grad_conv_f64")) return rw;
     if (!c->obj_src) return fail(c, BDOF_ERR_STATE, "bdof_set_object (with (delta, beta) rows) has not been called");
     if (!c->grot || !c->partial) return fail(c, BDOF_ERR_STATE, "bdof_configure(with_grad = 1) needed");
     int r;
@@ -2492,8 +2497,7 @@ int bdof_loss_grad_conv_f64(bdof_ctx* c, int B, const int* angle_of_b, const int
 // probe: host complex128 [NX][NY]; hT / hdetT (nullable: no near-field detector step): host complex128 [kx][ky], the
 // ifftshift-ed transfer functions / (NX NY); k = 2 pi dz / lambda as bdof_set_physics has it
 int bdof_set_tf_f64(bdof_ctx* c, const double* probe, const double* hT, const double* hdetT, double k) {
-    if (int rb = need_unbinned(c, "bdof_set_tf_f64")) return rb;
-    if (int rp = need_one_plane(c, "bdof_set_tf_f64")) return rp;
+    if (int r = admit(c, "bdof_set_tf_f64", NO_DATA_TERM)) return r;
     if (!c || !probe || !hT) return BDOF_ERR_ARG;
     if (int r = need_configured(c)) return r;
     if (c->det_mode == BDOF_DET_NEAR && !hdetT) return fail(c, BDOF_ERR_ARG, "a near-field detector needs its transfer function in float64 too");
@@ -2517,8 +2521,7 @@ int bdof_set_tf_f64(bdof_ctx* c, const double* probe, const double* hT, const do
 // gradient rows in bdof_grot.  Unfused — the accuracy path of the first minibatch of an epoch, and a float64 twin of the fused
 // kernels on the device.  meas: device float, laid out as for bdof_loss_grad (+ meas_ref under bdof_set_meas_mode(1)).
 int bdof_loss_grad_tf_f64(bdof_ctx* c, int B, const int* angle_of_b, const int* xoff, const int* yoff, const float* meas, double meas_ref) {
-    if (int rb = need_unbinned(c, "bdof_loss_grad_tf_f64")) return rb;
-    if (int rp = need_one_plane(c, "bdof_loss_grad_tf_f64")) return rp;
+    if (int r = admit(c, "bdof_loss_grad_tf_f64", NO_DATA_TERM)) return r;
     if (!c || !meas) return BDOF_ERR_ARG;
     if (!c->c64_tf) return fail(c, BDOF_ERR_STATE, "bdof_set_tf_f64 has not been called");
     if (!c->obj_src) return fail(c, BDOF_ERR_STATE, "bdof_set_object (with (delta, beta) rows) has not been called");
@@ -2653,8 +2656,7 @@ int bdof_loss_grad(bdof_ctx* c, int B, const int* angle_of_b, const int* xoff, c
 // =================================================================================================
 int bdof_set_conv(bdof_ctx* c, const float* ky, const float* kx, int ks, double e_re, double e_im, double ksum_re,
                   double ksum_im, double k) {
-    if (int rb = need_unbinned(c, "bdof_set_conv")) return rb;
-    if (int rp = need_one_plane(c, "bdof_set_conv")) return rp;
+    if (int r = admit(c, "bdof_set_conv", NO_DATA_TERM)) return r;
     if (!c || !ky || !kx) return BDOF_ERR_ARG;
     if (int r = need_configured(c)) return r;
     if (ks < 1 || ks > BDOF_CONV_MAXK || ks % 2 == 0) return fail(c, BDOF_ERR_ARG, "kernel_size must be odd and <= 33");
@@ -2684,8 +2686,7 @@ int bdof_set_conv(bdof_ctx* c, const float* ky, const float* kx, int ks, double 
 }
 
 int bdof_set_conv_taps_f64(bdof_ctx* c, const double* ky, const double* kx, double e_re, double e_im) {
-    if (int rb = need_unbinned(c, "bdof_set_conv_taps_f64")) return rb;
-    if (int rp = need_one_plane(c, "bdof_set_conv_taps_f64")) return rp;
+    if (int r = admit(c, "bdof_set_conv_taps_f64", NO_DATA_TERM)) return r;
     if (!c || !ky || !kx) return BDOF_ERR_ARG;
     if (!c->have_conv) return fail(c, BDOF_ERR_STATE, "bdof_set_conv has not been called");
     const int D = c->tw_dither;
@@ -2840,8 +2841,7 @@ static ConvFinalArgs conv_final_args(bdof_ctx* c, int B, const cf* psi_eps, cf* 
 extern "C" {
 
 int bdof_set_conv_probe_stack(bdof_ctx* c, const float* stack, const double* det64, double p0_re, double p0_im, double pS_re, double pS_im) {
-    if (int rb = need_unbinned(c, "bdof_set_conv_probe_stack")) return rb;
-    if (int rp = need_one_plane(c, "bdof_set_conv_probe_stack")) return rp;
+    if (int r = admit(c, "bdof_set_conv_probe_stack", NO_DATA_TERM)) return r;
     if (!c) return BDOF_ERR_ARG;
     if (int r = need_configured(c)) return r;
     HIPC(c, hipSetDevice(c->device));
@@ -2862,8 +2862,7 @@ int bdof_set_conv_probe_stack(bdof_ctx* c, const float* stack, const double* det
 }
 
 int bdof_forward_conv(bdof_ctx* c, int B, const int* angle_of_b, const int* xoff, const int* yoff, void* out_wave) {
-    if (int rb = need_unbinned(c, "bdof_forward_conv")) return rb;
-    if (int rp = need_one_plane(c, "bdof_forward_conv")) return rp;
+    if (int r = admit(c, "bdof_forward_conv", NO_DATA_TERM)) return r;
     int r = conv_check(c, B, angle_of_b);
     if (r) return r;
     if (!out_wave) return BDOF_ERR_ARG;
@@ -2898,13 +2897,10 @@ int bdof_forward_conv(bdof_ctx* c, int B, const int* angle_of_b, const int* xoff
 }
 
 int bdof_loss_grad_conv(bdof_ctx* c, int B, const int* angle_of_b, const int* xoff, const int* yoff, const float* meas, void* out_wave) {
-    if (int rb = need_unbinned(c, "bdof_loss_grad_conv")) return rb;
-    if (int rp = need_one_plane(c, "bdof_loss_grad_conv")) return rp;
+    if (int r = admit(c, "bdof_loss_grad_conv", CARRIES_NOTHING)) return r;
     int r = conv_check(c, B, angle_of_b);
     if (r) return r;
     if (!meas) return BDOF_ERR_ARG;
-    if ((r = need_lsq(c, "bdof_loss_grad_conv"))) return r;
-    if ((r = need_unweighted(c, "bdof_loss_grad_conv"))) return r;
     // residual splitting at the detector (bdof_set_meas_mode(1): meas holds m - |a_0|), real-space detectors: the renormalised
     // wave is kept as A + e', A = s a_S a float64 scalar formed on the host from the corner pixel, and |A + e'| - m is
     // evaluated without the cancellation of two numbers of size one (seed_split) — as on the transfer-function path
@@ -3242,7 +3238,7 @@ int bdof_rotate_bilinear(bdof_ctx* c, const void* vol, int NXv, int NZv, int NYv
 // bdof_rotate_bilinear + bdof_set_object in one pass: the B rotated objects are written straight into the ctx's modulation
 // table as factors c - 1 (no rotated (delta, beta) copy, no second pass over B volumes) and bound as the batch's objects.
 int bdof_set_object_bilinear(bdof_ctx* c, const void* vol, int NXv, int NZv, int NYv, const double* prm, int B, int conv) {
-    if (int rb = need_unbinned(c, "bdof_set_object_bilinear")) return rb;
+    if (int r = admit(c, "bdof_set_object_bilinear", CARRIES_PLANES | NO_DATA_TERM)) return r;
     if (!c || !vol || !prm || B < 1) return BDOF_ERR_ARG;
     if (int r = need_configured(c)) return r;
     if (NXv < 1 || NZv < 1 || NYv < 2 || NYv % 2) return fail(c, BDOF_ERR_SIZE, "bdof_set_object_bilinear needs an even NY");

@@ -22,19 +22,6 @@ def check_loss(loss_type, poisson_multiplier):
         raise ValueError('poisson_multiplier must be > 0')
 
 
-def check_poisson_path(loss_type, poisson_multiplier, propagator):
-    """check_loss, and that 'poisson' goes with the transfer-function propagator — the only one whose detector kernels carry it."""
-    check_loss(loss_type, poisson_multiplier)
-    if loss_type == 'poisson' and propagator != 'fft':
-        raise ValueError("loss_type='poisson' runs on the transfer-function propagator (propagator='fft') only")
-
-
-def check_weights_path(detector_weights, propagator):
-    """Detector weights go with the transfer-function propagator — the only one whose detector kernels carry them."""
-    if detector_weights is not None and propagator != 'fft':
-        raise ValueError("detector_weights run on the transfer-function propagator (propagator='fft') only")
-
-
 def check_detector_weights(w, ny, nx):
     """One (ny, nx) plane of finite weights >= 0, not all of them 0, as float32 (raises ValueError('detector_weights ...'))."""
     w = np.asarray(w)
@@ -72,40 +59,73 @@ def check_slice_binning(slice_binning):
         raise ValueError('slice_binning must be an integer >= 1')
 
 
-def check_binning_path(slice_binning, propagator='fft', adjoint_precision=None, rotation='nearest'):
-    """check_slice_binning, and with slice_binning > 1 that the call stays on what carries it: the transfer-function
-    propagator, the float32 sweeps (an explicit adjoint_precision other than 'float32' raises; None: not given) and the
-    nearest-neighbour rotation tables."""
+# ---- the model's options against the path of a call ------------------------------------------------------------------------------
+# The path: what a call runs on, by the keyword that chooses it, with the value that carries every option.  `method` is an
+# engine method that steps off the main path, by the words its refusal begins with.
+PATH = dict(propagator='fft', adjoint_precision=None, rotation='nearest', engine='auto', recompute=False, adjoint64=False,
+            no_grot=False, detector_kernel='TF', method=None)
+_SET_CONV = 'the real-space propagator (set_conv)'
+_TF_F64 = 'the float64 twin (enable_tf_f64)'
+_CONV_F64 = 'the float64 twin (enable_conv_f64)'
+_FORWARD_CONV = 'the real-space propagator (forward(conv=True))'
+_LOSS_GRAD_OFF = 'the real-space propagator / the float64 twin (loss_grad(conv=True / f64=True))'
+_BINNING_ENGINES = "slice_binning > 1 runs on the streaming and generic engines with the tape: not engine='resident', recompute, adjoint64 or no_grot"
+_PLANES_F32 = "several detector planes have no float64 twin: adjoint_precision must be 'float32' (no adjoint64)"
+_F32 = (None, 'float32')
+
+# option -> what it needs of the path: (keyword of the path, test of its value, text of the ValueError; {} is the value), in the
+# order in which they are reported.  An explicit adjoint_precision other than 'float32' is refused; None: not given.
+OPTION_NEEDS = {
+    'poisson': (('propagator', lambda v: v == 'fft', "loss_type='poisson' runs on the transfer-function propagator (propagator='fft') only"),),
+    'weights': (('propagator', lambda v: v == 'fft', "detector_weights run on the transfer-function propagator (propagator='fft') only"),),
+    'binning': (
+        ('propagator', lambda v: v == 'fft', "slice_binning > 1 runs on the transfer-function propagator (propagator='fft') only"),
+        ('adjoint_precision', lambda v: v in _F32, "slice_binning > 1 has no float64 twin: adjoint_precision must be 'float32'"),
+        ('rotation', lambda v: v == 'nearest', "slice_binning > 1 runs on the rotation tables (rotation='nearest') only"),
+        ('engine', lambda v: v != 'resident', _BINNING_ENGINES),
+        ('recompute', lambda v: not v, _BINNING_ENGINES),
+        ('adjoint64', lambda v: not v, _BINNING_ENGINES),
+        ('no_grot', lambda v: not v, _BINNING_ENGINES),
+        ('method', lambda v: v not in (_SET_CONV, _TF_F64, _CONV_F64), '{} does not carry slice_binning > 1'),
+    ),
+    'planes': (
+        ('propagator', lambda v: v == 'fft', "several detector planes (free_prop_cm as a sequence) run on the transfer-function propagator (propagator='fft') only"),
+        ('adjoint_precision', lambda v: v in _F32, _PLANES_F32),
+        ('adjoint64', lambda v: not v, _PLANES_F32),
+        ('recompute', lambda v: not v, 'several detector planes run with the tape: not recompute'),
+        ('rotation', lambda v: v == 'nearest', "several detector planes run on the rotation tables (rotation='nearest') only"),
+        ('detector_kernel', lambda v: v in ('TF', 'IR'), "several detector planes share one detector_kernel, 'TF' or 'IR': not {!r}"),
+        ('method', lambda v: v not in (_SET_CONV, _TF_F64, _FORWARD_CONV, _LOSS_GRAD_OFF), '{} does not carry several detector planes'),
+    ),
+}
+
+
+def check_option_path(option, path):
+    """Raise the ValueError of the first thing `option` needs that `path` (PATH with some keywords replaced) does not give."""
+    for key, carries, text in OPTION_NEEDS[option]:
+        if not carries(path[key]):
+            raise ValueError(text.format(path[key]))
+
+
+def check_model_options(loss_type='lsq', poisson_multiplier=2e6, detector_weights=None, slice_binning=1, free_prop_cm=None, **path):
+    """The option keywords as every layer takes them (check_loss, check_slice_binning and util.detector_distances raise ValueError
+    for a bad one), and for every option that is on that the call stays on what carries it (OPTION_NEEDS); **path: the
+    keywords of PATH the caller has.  Returns the number of frames per angle (1 without detector planes)."""
+    path = dict(PATH, **path)
+    if len(path) != len(PATH):
+        raise TypeError('not of the path: {}'.format(sorted(set(path) - set(PATH))))
+    check_loss(loss_type, poisson_multiplier)
+    if loss_type == 'poisson':
+        check_option_path('poisson', path)
+    if detector_weights is not None:
+        check_option_path('weights', path)
     check_slice_binning(slice_binning)
-    if slice_binning == 1:
-        return
-    if propagator != 'fft':
-        raise ValueError("slice_binning > 1 runs on the transfer-function propagator (propagator='fft') only")
-    if adjoint_precision not in (None, 'float32'):
-        raise ValueError("slice_binning > 1 has no float64 twin: adjoint_precision must be 'float32'")
-    if rotation != 'nearest':
-        raise ValueError("slice_binning > 1 runs on the rotation tables (rotation='nearest') only")
-
-
-def check_planes_path(free_prop_cm, propagator='fft', adjoint_precision=None, rotation='nearest', recompute=False, adjoint64=False,
-                      detector_kernel='TF'):
-    """The free_prop_cm keyword as every layer takes it (util.detector_distances raises ValueError for a bad one), and with more
-    than one detector plane that the call stays on what carries them: the transfer-function propagator, the float32 sweeps
-    with the tape (an explicit adjoint_precision other than 'float32' raises; None: not given), the nearest-neighbour rotation
-    tables and one kernel kind, 'TF' or 'IR', for all planes.  Returns the number of frames per angle (1 without planes)."""
+    if slice_binning > 1:
+        check_option_path('binning', path)
     planes = util.detector_distances(free_prop_cm)[1]
     if planes is None:
         return 1
-    if propagator != 'fft':
-        raise ValueError("several detector planes (free_prop_cm as a sequence) run on the transfer-function propagator (propagator='fft') only")
-    if adjoint_precision not in (None, 'float32') or adjoint64:
-        raise ValueError("several detector planes have no float64 twin: adjoint_precision must be 'float32' (no adjoint64)")
-    if recompute:
-        raise ValueError('several detector planes run with the tape: not recompute')
-    if rotation != 'nearest':
-        raise ValueError("several detector planes run on the rotation tables (rotation='nearest') only")
-    if detector_kernel not in ('TF', 'IR'):
-        raise ValueError("several detector planes share one detector_kernel, 'TF' or 'IR': not {!r}".format(detector_kernel))
+    check_option_path('planes', path)
     return len(planes)
 
 
@@ -135,9 +155,7 @@ class MultisliceEngine(object):
         b = int(slice_binning)
         if int(n_slice) % b:
             raise ValueError('slice_binning must divide n_slice ({} % {} != 0)'.format(int(n_slice), b))
-        if b > 1 and (engine == 'resident' or recompute or adjoint64 or no_grot):
-            raise ValueError("slice_binning > 1 runs on the streaming and generic engines with the tape: not engine='resident', "
-                             'recompute, adjoint64 or no_grot')
+        check_model_options(slice_binning=b, engine=engine, recompute=recompute, adjoint64=adjoint64, no_grot=no_grot)
         if engine not in ('auto', 'generic', 'streaming', 'resident'):
             raise ValueError('engine must be auto, generic, streaming or resident')
         force_generic = force_generic or engine == 'generic'
@@ -224,8 +242,8 @@ class MultisliceEngine(object):
         each with the table of its own distance and the one detector_kernel, 'TF' or 'IR'.  forward then returns (B, D, Y, X)
         and loss_grad takes amplitudes of that shape; n_planes = D.  A sequence of one is its scalar.  Streaming and generic
         engines with the tape, scalar-carrier probes."""
-        n_planes = check_planes_path(free_prop_cm, 'fft' if self._conv_kernel is None else 'conv', recompute=self.recompute,
-                                     adjoint64=self.adjoint64, detector_kernel=detector_kernel)
+        n_planes = check_model_options(free_prop_cm=free_prop_cm, propagator='fft' if self._conv_kernel is None else 'conv',
+                                       recompute=self.recompute, adjoint64=self.adjoint64, detector_kernel=detector_kernel)
         o = util.Optics(energy_ev, psize_cm, free_prop_cm, pi, self.ny, self.nx, field_shape)
         if n_planes > 1:
             if field_shape is not None:
@@ -271,13 +289,12 @@ class MultisliceEngine(object):
         """Length of one propagation step: slice_binning voxel slices."""
         return self.optics.delta_nm * self.slice_binning
 
-    def _need_unbinned(self, what):
+    def _admit(self, method):
+        """A method that steps off the main path, under the options this engine runs with (OPTION_NEEDS, 'method')."""
         if self.slice_binning > 1:
-            raise ValueError('{} does not carry slice_binning > 1'.format(what))
-
-    def _need_one_plane(self, what):
+            check_option_path('binning', dict(PATH, method=method))
         if self.n_planes > 1:
-            raise ValueError('{} does not carry several detector planes'.format(what))
+            check_option_path('planes', dict(PATH, method=method))
 
     def _detector_table(self, dtype, fold=True, transpose=False, tiled=False):
         """The un-shifted multiplier of the step to a near-field detector (None without one): the one place it is built.
@@ -449,8 +466,7 @@ class MultisliceEngine(object):
     def set_conv(self, energy_ev, psize_cm, kernel_size=17):
         """Switch the slice-to-slice step to the truncated real-space kernel of multislice_propagate_cnn
         (cnn_propagator/propagation.py:18-44): k uses numpy's pi there (:25), the kernel the reference's PI literal."""
-        self._need_unbinned('the real-space propagator (set_conv)')
-        self._need_one_plane('the real-space propagator (set_conv)')
+        self._admit(_SET_CONV)
         o = util.Optics(energy_ev, psize_cm, None, np.pi, self.ny, self.nx)         # o.k: numpy's pi, unlike set_physics
         ky, kx, e = util.conv_kernel_separable(o.delta_nm, o.lmbda_nm, o.voxel_nm, (self.ny, self.nx), kernel_size)   # pi=util.PI
         ksum = e * ky.sum() * kx.sum()
@@ -471,8 +487,7 @@ class MultisliceEngine(object):
         accuracy path of the first minibatch of an epoch (adjoint_precision='first-step') — no second engine — and a float64 twin
         of the fused kernels for tests.  Hands the probe and the transfer function(s) over in float64; call again after
         set_physics / set_probe."""
-        self._need_unbinned('the float64 twin (enable_tf_f64)')
-        self._need_one_plane('the float64 twin (enable_tf_f64)')
+        self._admit(_TF_F64)
         if self.optics is None or self._probe_args is None:
             raise RuntimeError('set_physics and set_probe first')
         o = self.optics
@@ -488,7 +503,7 @@ class MultisliceEngine(object):
         f64=True)): the accuracy path for the first minibatch of an epoch (adjoint_precision='first-step' / 'float64' with
         propagator='conv').  Square fields.  Hands the probe and the transform of the zero-padded
         ks x ks kernel over in float64 (overlap-save on the padded (N + ks - 1)^2 grid)."""
-        self._need_unbinned('the float64 twin (enable_conv_f64)')
+        self._admit(_CONV_F64)
         if self._conv_kernel is None or self._probe_args is None:
             raise RuntimeError('set_conv and set_probe first')
         if self.nx != self.ny:
@@ -604,7 +619,7 @@ class MultisliceEngine(object):
         out = DeviceBuffer(self.ctx, B * D * self.nx * self.ny * 8, np.complex64, (B, self.nx, self.ny) if D == 1 else (B, D, self.nx, self.ny))
         a, xo, yo = self._idx_bufs(angle_idx, xoff, yoff)
         if conv:
-            self._need_one_plane('the real-space propagator (forward(conv=True))')
+            self._admit(_FORWARD_CONV)
             self.ctx.check(self.lib.bdof_forward_conv(self.h, B, _lib._ptr(a), _lib._ptr(xo), _lib._ptr(yo), out.ptr))
         else:
             self.ctx.check(self.lib.bdof_forward(self.h, B, _lib._ptr(a), _lib._ptr(xo), _lib._ptr(yo), out.ptr, int(keep_tape)))
@@ -626,7 +641,7 @@ class MultisliceEngine(object):
         place that picks among the four entry points: conv — the real-space propagator; f64 — the model's float64 path on
         this context, which takes the residual-splitting reference as a number."""
         if conv or f64:
-            self._need_one_plane('the real-space propagator / the float64 twin (loss_grad(conv=True / f64=True))')
+            self._admit(_LOSS_GRAD_OFF)
         if f64:
             if conv and not self.conv_f64:
                 raise RuntimeError('the real-space propagator\'s float64 path: enable_conv_f64() first')

@@ -23,7 +23,7 @@ import numpy as np
 from . import h5io, tiffio, util
 from .comm import get_comm, minibatch_schedule
 from .misc import create_summary
-from .engine import check_poisson_path, check_binning_path, check_planes_path, check_weights_path, read_detector_weights
+from .engine import check_model_options, read_detector_weights
 from .solver import FullfieldSolver
 from .util import print_flush
 
@@ -83,20 +83,17 @@ def reconstruct_fullfield(fname, theta_st=0, theta_end=PI, n_epochs='auto', crit
     # 'lsq': mean((|d| - m)^2), the reference's active line; 'poisson': the photon-counting likelihood next to it in
     # tensorflow_recon/ptychography.py, as its deviance (include/bdof.h, bdof_set_loss), with poisson_multiplier photons per unit
     # intensity.  Near the fit it is ~ 2 poisson_multiplier times the least-squares term: rescale alpha_d / alpha_b / gamma with it.
-    check_poisson_path(loss_type, poisson_multiplier, propagator)
     # detector_weights: one (Y, X) plane w >= 0 shared by every projection — 0 for dead or hot pixels and module gaps — as an array or
     # as the name of a dataset of the data file ('exchange/weights').  L = sum(w l) / (number of pixels), and a pixel with w = 0
-    # takes no part whatever the file holds there (MultisliceEngine.set_detector_weights).  Transfer-function propagator only.
-    check_weights_path(detector_weights, propagator)
+    # takes no part whatever the file holds there (MultisliceEngine.set_detector_weights).
     # slice_binning=b: one propagation step per b voxel slices (include/bdof.h, bdof_set_slice_binning) — a step only has to stay
-    # below the depth of focus.  Transfer-function propagator, lookup-table rotation and float32 sweeps; every multiscale
-    # level's depth must divide by b.
-    check_binning_path(slice_binning, propagator, kwargs.get('adjoint_precision'), kwargs.get('rotation', 'nearest'))
+    # below the depth of focus; every multiscale level's depth must divide by b.
     # free_prop_cm=[z_0, ..]: D detector planes per angle (holotomography; include/bdof.h, bdof_set_detector_planes).  The file's
-    # exchange/data is then (n_theta, D, Y, X), in the order of the distances.  Transfer-function propagator, lookup-table
-    # rotation, float32 sweeps, one detector_kernel ('TF' or 'IR') for all planes; a sequence of one is its scalar.
-    n_planes = check_planes_path(free_prop_cm, propagator, kwargs.get('adjoint_precision'), kwargs.get('rotation', 'nearest'),
-                                 detector_kernel=kwargs.get('detector_kernel', 'TF'))
+    # exchange/data is then (n_theta, D, Y, X), in the order of the distances; a sequence of one is its scalar.
+    # What each of the four needs of propagator, adjoint precision, rotation and detector kernel: engine.OPTION_NEEDS.
+    n_planes = check_model_options(loss_type, poisson_multiplier, detector_weights, slice_binning, free_prop_cm, propagator=propagator,
+                                   adjoint_precision=kwargs.get('adjoint_precision'), rotation=kwargs.get('rotation', 'nearest'),
+                                   detector_kernel=kwargs.get('detector_kernel', 'TF'))
     if n_planes > 1 and probe_type == 'optimizable' and probe_initial is None:
         raise ValueError("several detector planes with probe_type='optimizable' need probe_initial: the initial guess back-propagates one plane")
     # gradient accumulation over n_batch_per_update minibatches exists only in the TF twin (tensorflow_recon/fullfield.py:

@@ -17,7 +17,7 @@ from . import h5io, tiffio, util
 from .comm import get_comm
 from .fullfield import create_probe_initial_guess, upsample_2x
 from .misc import create_summary
-from .engine import check_poisson_path, check_binning_path, check_weights_path, read_detector_weights
+from .engine import check_model_options, read_detector_weights
 from .solver import PtychoSolver
 from ._lib import BdofError
 from .util import print_flush, split_tasks
@@ -92,16 +92,15 @@ def reconstruct_ptychography(fname, probe_pos, probe_size, obj_size, theta_st=0,
     # the data term: 'lsq', or 'poisson' — the likelihood tensorflow_recon/ptychography.py writes out beside its poisson_multiplier
     # keyword, as its deviance (include/bdof.h, bdof_set_loss).  The bare likelihood is unbounded where the model intensity goes
     # to zero under a measured count, which far-field data with noise has: there is no epsilon.
-    check_poisson_path(loss_type, poisson_multiplier, propagator)
     # detector_weights: one (py, px) plane w >= 0 shared by every diffraction pattern, fftshifted as the patterns are — 0 behind the
     # beamstop, for dead or hot pixels and module gaps — as an array or as the name of a dataset of the data file
     # ('exchange/weights').  L = sum(w l) / (number of pixels), and a pixel with w = 0 takes no part whatever the file holds there
-    # (MultisliceEngine.set_detector_weights).  Transfer-function propagator only.
-    check_weights_path(detector_weights, propagator)
-    # slice_binning=b: one propagation step per b voxel slices (include/bdof.h, bdof_set_slice_binning).  Transfer-function
-    # propagator and float32 sweeps only — the float64 twin of 'first-step' does not carry it, so the DEFAULT becomes 'float32'
-    # and an explicit other choice raises; every multiscale level's depth must divide by b.
-    check_binning_path(slice_binning, propagator, kwargs.get('adjoint_precision'))
+    # (MultisliceEngine.set_detector_weights).
+    # slice_binning=b: one propagation step per b voxel slices (include/bdof.h, bdof_set_slice_binning).  The float64 twin of
+    # 'first-step' does not carry it, so the DEFAULT becomes 'float32' and an explicit other choice raises; every multiscale
+    # level's depth must divide by b.  What each of the three needs of propagator and adjoint precision: engine.OPTION_NEEDS.
+    check_model_options(loss_type, poisson_multiplier, detector_weights, slice_binning, propagator=propagator,
+                        adjoint_precision=kwargs.get('adjoint_precision'))
     if slice_binning > 1:
         adjoint_precision = 'float32'
     for lv in range(multiscale_level):

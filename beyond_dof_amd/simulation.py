@@ -12,7 +12,7 @@ from scipy.ndimage import gaussian_filter
 from scipy.ndimage import rotate as sp_rotate
 
 from . import h5io, tiffio, util
-from .engine import check_planes_path
+from .engine import check_model_options
 from .np_funcs import multislice_propagate_batch_numpy
 
 PI = util.PI
@@ -51,7 +51,7 @@ def create_fullfield_data_numpy(energy_ev, psize_cm, free_prop_cm, n_theta, phan
                                 monitor_output=False, overwrite=False, **kwargs):
     """cnn_propagator/simulation.py:80-161.  Writes (n_theta, Y, X) complex64 to save_folder/fname — with free_prop_cm a sequence
     of D distances (several detector planes per angle) (n_theta, D, Y, X), in the order of the distances."""
-    n_planes = check_planes_path(free_prop_cm)
+    n_planes = check_model_options(free_prop_cm=free_prop_cm)
     obj = _load_phantom(phantom_path)
     img_dim = obj.shape[:3]
     path = os.path.join(save_folder, fname)

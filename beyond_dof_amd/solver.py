@@ -24,7 +24,12 @@ from . import _lib
 from ._lib import DeviceBuffer
 from . import util
 from .comm import PseudoComm
-from .engine import MultisliceEngine, RESIDENT_SIZES, check_poisson_path, check_binning_path, check_planes_path, check_weights_path
+from .engine import MultisliceEngine, RESIDENT_SIZES, check_model_options
+
+
+def _check_options(propagator, adjoint64, *options, **path):
+    """check_model_options with a solver's keywords: any adjoint64 that is on stands for the float64 path."""
+    return check_model_options(*options, propagator=propagator, adjoint_precision='float64' if adjoint64 else None, **path)
 
 
 class _VolumeSolver(object):
@@ -397,11 +402,8 @@ class FullfieldSolver(_VolumeSolver):
         'bilinear': the TF twin's tf_rotate(obj, theta[i], 'BILINEAR') (tensorflow_recon/fullfield.py:96) with the true angles
         `theta` (radians, one per projection): the minibatch's rotated objects are materialised per step
         (bdof_rotate_bilinear), its adjoint is a gather (bdof_rotate_bilinear_adjoint)."""
-        check_poisson_path(loss_type, poisson_multiplier, propagator)
-        check_weights_path(detector_weights, propagator)
-        check_binning_path(slice_binning, propagator, 'float64' if adjoint64 else None, rotation if rotation == 'bilinear' else 'nearest')
-        self.n_planes = check_planes_path(free_prop_cm, propagator, 'float64' if adjoint64 else None, rotation if rotation == 'bilinear' else 'nearest',
-                                          recompute=recompute, detector_kernel=detector_kernel)
+        self.n_planes = _check_options(propagator, adjoint64, loss_type, poisson_multiplier, detector_weights, slice_binning, free_prop_cm,
+                                       rotation=rotation if rotation == 'bilinear' else 'nearest', recompute=recompute, detector_kernel=detector_kernel)
         self.conv = propagator == 'conv'
         self.bilinear = rotation == 'bilinear'
         if adjoint64 not in (None, False, True, 'first'):
@@ -605,9 +607,7 @@ class PtychoSolver(_VolumeSolver):
         engine=None then takes 'auto' (the resident engine does not carry it).
         engine: None picks the LDS-resident engine for small square probes (below) and the automatic choice otherwise; 'auto',
         'generic', 'streaming' or 'resident' go to MultisliceEngine(engine=...) as they are."""
-        check_poisson_path(loss_type, poisson_multiplier, propagator)
-        check_weights_path(detector_weights, propagator)
-        check_binning_path(slice_binning, propagator, 'float64' if adjoint64 else None)
+        _check_options(propagator, adjoint64, loss_type, poisson_multiplier, detector_weights, slice_binning)
         self.conv = propagator == 'conv'
         self.dim_y, self.dim_x, self.dim_z = [int(s) for s in obj_size]
         self.py, self.px = int(probe_size[0]), int(probe_size[1])

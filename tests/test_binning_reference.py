@@ -1,4 +1,4 @@
-"""Slice binning off the GPU: the float64 reference the GPU tests compare against (tests/binning_reference.py) is pinned to the
+"""Slice binning off the GPU: the float64 reference the GPU tests compare against (tests/reference_model.py) is pinned to the
 oracle where the two models coincide (b = 1; objects that leave all but one slice of a bin empty), its gradient is checked
 against central differences of its own loss, and the keyword surface of the two entry points and the C symbol are checked."""
 import numpy as np
@@ -6,23 +6,15 @@ import pytest
 
 from oracle import bdof_oracle as orc
 
-import binning_reference as bref
+import reference_model as ref_model
+from reference_model import rel
 
 E, PS = 5000., 1e-7
 DETECTORS = [None, 1e-4, 'inf']
 
 
-def rel(a, b):
-    return np.linalg.norm(np.asarray(a) - np.asarray(b)) / max(np.linalg.norm(b), 1e-300)
-
-
-def _setup(B=2, Y=16, X=16, S=12, seed=0):
-    rng = np.random.default_rng(seed)
-    delta = rng.uniform(0, 2e-3, size=(B, Y, X, S))
-    beta = rng.uniform(0, 2e-4, size=(B, Y, X, S))
-    pr = 1 + 0.1 * rng.normal(size=(Y, X))
-    pi = 0.1 * rng.normal(size=(Y, X))
-    return delta, beta, pr, pi, rng
+def _setup():
+    return ref_model.setup(S=12)
 
 
 @pytest.mark.parametrize('fp', DETECTORS)
@@ -30,11 +22,11 @@ def _setup(B=2, Y=16, X=16, S=12, seed=0):
 def test_binning_one_is_the_oracle_exactly(fp, variant):
     delta, beta, pr, pi, rng = _setup()
     ref, ref_after = orc.multislice_propagate_batch_numpy(delta, beta, pr, pi, E, PS, fp, delta.shape, variant=variant)
-    d, after = bref.forward(delta, beta, pr, pi, E, PS, fp, variant, b=1)
+    d, after = ref_model.forward(delta, beta, pr, pi, E, PS, fp, variant, b=1)
     assert np.array_equal(d, ref) and np.array_equal(after, ref_after)
     meas = np.abs(ref) * np.abs(1 + 0.05 * rng.normal(size=ref.shape))
     rl, rgd, rgb, rgp = orc.multislice_loss_and_grad(delta, beta, pr, pi, E, PS, meas, fp, variant, return_probe_grad=True)
-    loss, gd, gb, gp, _ = bref.loss_and_grad(delta, beta, pr, pi, E, PS, meas, fp, variant, b=1)
+    loss, gd, gb, gp, _ = ref_model.loss_and_grad(delta, beta, pr, pi, E, PS, meas, fp, variant, b=1)
     diffs = (abs(loss - rl), np.abs(gd - rgd).max(), np.abs(gb - rgb).max(), np.abs(gp - rgp).max())
     print('b = 1 against the oracle: differences', fp, variant, diffs)
     assert diffs == (0.0, 0.0, 0.0, 0.0), diffs
@@ -50,7 +42,7 @@ def test_first_slice_of_each_bin_only_gives_the_unbinned_wave(b, fp):
     keep[::b] = 1
     delta, beta = delta * keep, beta * keep
     ref, _ = orc.multislice_propagate_batch_numpy(delta, beta, pr, pi, E, PS, fp, delta.shape, variant='tf_all')
-    d, _ = bref.forward(delta, beta, pr, pi, E, PS, fp, 'tf_all', b=b)
+    d, _ = ref_model.forward(delta, beta, pr, pi, E, PS, fp, 'tf_all', b=b)
     e = rel(d, ref)
     print('identity 1 (first slice of each bin, tf_all)', b, fp, e)
     assert e <= 1e-13
@@ -68,7 +60,7 @@ def test_last_slice_of_each_bin_only_gives_the_unbinned_amplitudes(b, fp):
     keep[b - 1::b] = 1
     delta, beta = delta * keep, beta * keep
     ref, _ = orc.multislice_propagate_batch_numpy(delta, beta, pr, pi, E, PS, fp, delta.shape)
-    d, _ = bref.forward(delta, beta, pr, pi, E, PS, fp, 'numpy_skip_last', b=b)
+    d, _ = ref_model.forward(delta, beta, pr, pi, E, PS, fp, 'numpy_skip_last', b=b)
     e = rel(np.abs(d), np.abs(ref))
     print('identity 2 (last slice of each bin, numpy_skip_last, plane probe)', b, fp, e)
     assert e <= 1e-13
@@ -80,7 +72,7 @@ def test_binned_and_unbinned_models_differ_for_a_general_object(b):
     any bound they assert (1e-5)."""
     delta, beta, pr, pi, _ = _setup()
     ref, _ = orc.multislice_propagate_batch_numpy(delta, beta, pr, pi, E, PS, 1e-4, delta.shape)
-    d, _ = bref.forward(delta, beta, pr, pi, E, PS, 1e-4, 'numpy_skip_last', b=b)
+    d, _ = ref_model.forward(delta, beta, pr, pi, E, PS, 1e-4, 'numpy_skip_last', b=b)
     e = rel(np.abs(d), np.abs(ref))
     print('binned against unbinned |d|, random object', b, e)
     assert e >= 1e-3
@@ -97,10 +89,10 @@ def test_reference_gradient_against_central_differences(b, fp, variant):
     difference quotient's own truncation error, (1e-7)^2 D^3 L / 6, is then divided by a number that cancelled towards zero —
     and is drawn again.  The criterion looks at the direction alone, never at the error."""
     delta, beta, pr, pi, rng = _setup()
-    ref, _ = bref.forward(delta, beta, pr, pi, E, PS, fp, variant, b)
+    ref, _ = ref_model.forward(delta, beta, pr, pi, E, PS, fp, variant, b)
     meas = np.abs(ref) * np.abs(1 + 0.05 * rng.normal(size=ref.shape))
-    loss, gd, gb, gp, _ = bref.loss_and_grad(delta, beta, pr, pi, E, PS, meas, fp, variant, b)
-    assert abs(loss - bref.loss_only(delta, beta, pr, pi, E, PS, meas, fp, variant, b)) <= 1e-14 * abs(loss)
+    loss, gd, gb, gp, _ = ref_model.loss_and_grad(delta, beta, pr, pi, E, PS, meas, fp, variant, b)
+    assert abs(loss - ref_model.loss_only(delta, beta, pr, pi, E, PS, meas, fp, variant, b)) <= 1e-14 * abs(loss)
     assert gp.shape == ref.shape
     for i in range(delta.shape[-1] // b):                   # the slices of a bin share their row
         for j in range(1, b):
@@ -114,11 +106,11 @@ def test_reference_gradient_against_central_differences(b, fp, variant):
             while abs(np.sum(g * v)) < 0.1 * np.linalg.norm(g):
                 v = rng.choice([-1.0, 1.0], size=delta.shape)
             if which == 0:
-                lp = bref.loss_only(delta + eps * v, beta, pr, pi, E, PS, meas, fp, variant, b)
-                lm = bref.loss_only(delta - eps * v, beta, pr, pi, E, PS, meas, fp, variant, b)
+                lp = ref_model.loss_only(delta + eps * v, beta, pr, pi, E, PS, meas, fp, variant, b)
+                lm = ref_model.loss_only(delta - eps * v, beta, pr, pi, E, PS, meas, fp, variant, b)
             else:
-                lp = bref.loss_only(delta, beta + eps * v, pr, pi, E, PS, meas, fp, variant, b)
-                lm = bref.loss_only(delta, beta - eps * v, pr, pi, E, PS, meas, fp, variant, b)
+                lp = ref_model.loss_only(delta, beta + eps * v, pr, pi, E, PS, meas, fp, variant, b)
+                lm = ref_model.loss_only(delta, beta - eps * v, pr, pi, E, PS, meas, fp, variant, b)
             an = float(np.sum(g * v))
             errs.append(abs((lp - lm) / (2 * eps) - an) / abs(an))
     print('binned reference, directional derivatives rel err', b, fp, variant, errs)

@@ -147,3 +147,33 @@ def test_counted_wait_scanner_flags_a_wait_not_backed_by_stores():
     assert len(bad) == 1 and 'only 1' in bad[0][2]
     none = head + '\tglobal_store_dwordx2 v[0:1], v[2:3], off\n\ts_endpgm\n'
     assert check_spills.scan_counted_waits(none)[0] == [('_Z7k_conv2ILb0ELi8ELb0ELi64EEv8ConvArgs', 0, 'no counted wait found')]
+
+
+def test_isa_listing_does_not_depend_on_the_width_of_label_numbers():
+    """tools/isa_kernels.kernels on two made-up listings of one kernel at positions 9 and 10 of a file: the label numbers differ in
+    width, and with them the column of the assembler's trailing comments and the labels those comments name; the text that is
+    hashed is the same.  A changed instruction still shows."""
+    import sys
+    sys.path.insert(0, os.path.join(ROOT, 'tools'))
+    import isa_kernels
+
+    def listing(pos, op='v_add_u32_e32 v0, v1, v2'):
+        label = '.LBB{}_2:'.format(pos)
+        return ('_Z6k_demoPf:                            ; @_Z6k_demoPf\n'
+                '; %bb.0:\n'
+                '\ts_load_dwordx2 s[0:1], s[4:5], 0x0\n'
+                + label + ' ' * (40 - len(label)) + '; =>This Inner Loop Header: Depth=1\n'
+                '\t' + op + '\n'
+                '\ts_cbranch_scc1 .LBB{0}_2                      ; encoding: [0xfb,0xff,0x85,0xbf]   \n'.format(pos)
+                + '; %bb.3:                                ; %for.end, after BB{}_2\n'.format(pos)
+                + '\ts_endpgm\n'
+                '.Lfunc_end{0}:\n'
+                '\t.size\t_Z6k_demoPf, .Lfunc_end{0}-_Z6k_demoPf\n'
+                '\t.amdhsa_kernel _Z6k_demoPf\n'
+                '\t\t.amdhsa_next_free_vgpr 3\n'
+                '\t.end_amdhsa_kernel\n').format(pos)
+
+    nine, ten = isa_kernels.kernels(listing(9)), isa_kernels.kernels(listing(10))
+    assert list(nine) == ['_Z6k_demoPf'] and nine == ten
+    assert '.LBB_2:\n' in nine['_Z6k_demoPf'] and 's_cbranch_scc1 .LBB_2\n' in nine['_Z6k_demoPf'] and '.amdhsa_next_free_vgpr 3' in nine['_Z6k_demoPf']
+    assert isa_kernels.kernels(listing(10, 'v_sub_u32_e32 v0, v1, v2')) != nine

@@ -1,5 +1,5 @@
 """Slice binning (bdof_set_slice_binning, MultisliceEngine(slice_binning=b), the solvers' and entry points' keyword) on the device,
-through the two engines that carry it, against the float64 reference of tests/binning_reference.py.
+through the two engines that carry it, against the float64 reference of tests/reference_model.py.
 
 Bounds: the ones tests/test_gpu_parity.py asserts for the identical unbinned cases — forward intensities relative L2 1e-5, wave
 5e-6, loss relative 1e-5, gradients relative L2 2e-4 — because binning changes which table rows are multiplied into a step's
@@ -16,8 +16,8 @@ pytestmark = pytest.mark.gpu
 
 from oracle import bdof_oracle as orc
 
-import binning_reference as bref
 import poisson_reference as pref
+import reference_model as ref_model
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 E, PS, MU = 5000., 1e-7, 2e6
@@ -43,8 +43,7 @@ def _probe(kind, Y, X, rng):
     return 1 + 0.1 * rng.normal(size=(Y, X)), 0.1 * rng.normal(size=(Y, X))
 
 
-def _poisson_term(d, meas):
-    return pref.poisson_loss(d, meas, MU), pref.poisson_seed(d, meas, MU)
+POISSON = ref_model.data_term(pref.poisson_loss, pref.poisson_seed, MU)
 
 
 @functools.lru_cache(maxsize=None)
@@ -59,10 +58,10 @@ def _reference(B, Y, X, S, fp, variant, probe, b, loss='lsq', seed=0, first_only
         delta = delta * keep
     beta = 0.1 * delta
     pr, pi = _probe(probe, Y, X, rng)
-    ref, _ = bref.forward(delta, beta, pr, pi, E, PS, fp, variant, b)
+    ref, _ = ref_model.forward(delta, beta, pr, pi, E, PS, fp, variant, b)
     meas = np.abs(ref) * np.abs(1 + 0.05 * rng.normal(size=ref.shape))
-    rl, rgd, rgb, _, _ = bref.loss_and_grad(delta, beta, pr, pi, E, PS, meas, fp, variant, b,
-                                            loss_and_seed=_poisson_term if loss == 'poisson' else bref.lsq_loss_and_seed)
+    rl, rgd, rgb, _, _ = ref_model.loss_and_grad(delta, beta, pr, pi, E, PS, meas, fp, variant, b,
+                                                 term=POISSON if loss == 'poisson' else ref_model.lsq)
     out = (delta, beta, pr, pi, meas, ref, rl, rgd, rgb)
     for a in out[:-3] + out[-2:]:
         a.setflags(write=False)
@@ -193,7 +192,7 @@ def test_fullfield_solver_rotation_table_path(engine_mod, b):
     idx = np.sort(rng.choice(n_theta, mb, replace=False))
     one, zero = np.ones((n, n)), np.zeros((n, n))
     rot = np.stack([orc.apply_rotation(np.stack([od, ob], axis=3), coords[j]) for j in idx])
-    ref, _ = bref.forward(rot[..., 0], rot[..., 1], one, zero, E, PS, fp, 'numpy_skip_last', b)
+    ref, _ = ref_model.forward(rot[..., 0], rot[..., 1], one, zero, E, PS, fp, 'numpy_skip_last', b)
     prj = np.zeros((n_theta, n, n))
     prj[idx] = (np.abs(ref) * np.abs(1 + 0.05 * rng.normal(size=ref.shape))).astype(np.float32)
     s = FullfieldSolver(n, n, n, n_theta, mb, E, PS, free_prop_cm=fp, coord_ls=coords, slice_binning=b)
@@ -203,7 +202,7 @@ def test_fullfield_solver_rotation_table_path(engine_mod, b):
     w = s.forward_angles(idx)
     loss = s.loss_and_grad(idx)
     gd, gb = s.gradient_to_host()
-    rl, rgd, rgb = bref.fullfield_loss_and_grad(od, ob, coords, idx, prj[idx], one, zero, E, PS, fp, b=b)
+    rl, rgd, rgb, _ = ref_model.fullfield_loss_and_grad(od, ob, coords, idx, prj[idx], one, zero, E, PS, fp, b=b)
     e = (rel(np.abs(w) ** 2, np.abs(ref) ** 2), abs(loss - rl) / abs(rl), rel(gd, rgd), rel(gb, rgb))
     print('binning, full-field solver 64^3', 'b', b, 'intensity / loss / g_delta / g_beta rel err', e)
     assert e[0] <= 1e-5 and e[1] <= 1e-5 and e[2] <= 2e-4 and e[3] <= 2e-4, e
@@ -231,7 +230,7 @@ def test_ptycho_solver_window_path(engine_mod, psz, pos):
     meas = np.abs(w).astype(np.float64) * np.abs(1 + 0.05 * rng.normal(size=w.shape))
     loss = s.loss_and_grad(i_theta, sel, meas)
     gd, gb = s.gradient_to_host()
-    rl, rgd, rgb = bref.ptycho_loss_and_grad(od, ob, coords[i_theta], pos, pos[sel], meas, prr, pii, psz, E, PS, b=b)
+    rl, rgd, rgb = ref_model.ptycho_loss_and_grad(od, ob, coords[i_theta], pos, pos[sel], meas, prr, pii, psz, E, PS, b=b)
     e = (abs(loss - rl) / abs(rl), rel(gd, rgd), rel(gb, rgb))
     print('binning, ptychography solver', psz, 'b', b, 'loss / g_delta / g_beta rel err', e)
     assert e[0] <= 1e-5 and e[1] <= 2e-4 and e[2] <= 2e-4, e

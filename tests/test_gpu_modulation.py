@@ -21,7 +21,7 @@ pytestmark = pytest.mark.gpu
 
 from oracle import bdof_oracle as orc
 
-import binning_reference as bref
+import reference_model as ref_model
 import modulation_reference as mref
 
 E, PS = mref.E_EV, mref.PSIZE_CM
@@ -310,13 +310,13 @@ def test_tape_free_adjoint(engine_mod, name):
 @pytest.mark.parametrize('engine,Y,X', [('streaming', 64, 64), ('generic', 72, 72)])
 @pytest.mark.parametrize('b', [2, 3])
 def test_slice_binning(engine_mod, engine, Y, X, b):
-    """The binning product of the table's factors, against tests/binning_reference.py at test_gpu_binning.py's bounds."""
+    """The binning product of the table's factors, against tests/reference_model.py at test_gpu_binning.py's bounds."""
     fp = 1e-4
     c = mref.engine_case(Y, X, 'pi', fp)
     de, be, pr, pi = c['delta_eff'], c['beta_eff'], c['pr'], c['pi']
-    ref, _ = bref.forward(de, be, pr, pi, E, PS, fp, 'numpy_skip_last', b)
+    ref, _ = ref_model.forward(de, be, pr, pi, E, PS, fp, 'numpy_skip_last', b)
     meas = mref.measurement(ref)
-    rl, rgd, rgb, _, _ = bref.loss_and_grad(de, be, pr, pi, E, PS, meas, fp, 'numpy_skip_last', b)
+    rl, rgd, rgb, _, _ = ref_model.loss_and_grad(de, be, pr, pi, E, PS, meas, fp, 'numpy_skip_last', b)
     eng = engine_mod.MultisliceEngine(Y, X, S, B, with_grad=True, engine=engine, slice_binning=b)
     eng.set_physics(E, PS, fp)
     eng.set_probe(pr, pi)

@@ -1,6 +1,6 @@
 """Several detector planes per wavefield (bdof_set_detector_planes; free_prop_cm as a sequence of distances through MultisliceEngine,
 FullfieldSolver, reconstruct_fullfield and the simulator) on the device, through the two engines that carry them, against the float64
-reference of tests/multidistance_reference.py.
+reference of tests/reference_model.py.
 
 Bounds: the ones tests/test_gpu_parity.py and tests/test_gpu_binning.py assert for the same single-plane cases — forward
 intensities relative L2 1e-5, wave 5e-6, loss relative 1e-5, gradients relative L2 2e-4.  The planes run the same float32 line
@@ -18,8 +18,8 @@ pytestmark = pytest.mark.gpu
 
 from oracle import bdof_oracle as orc
 
-import multidistance_reference as mref
 import poisson_reference as pref
+import reference_model as ref_model
 import weights_reference as wref
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -47,8 +47,7 @@ def _probe(kind, Y, X, rng):
     return 1 + 0.1 * rng.normal(size=(Y, X)), 0.1 * rng.normal(size=(Y, X))
 
 
-def _poisson_term(d, meas):
-    return pref.poisson_loss(d, meas, MU), pref.poisson_seed(d, meas, MU)
+POISSON = ref_model.data_term(pref.poisson_loss, pref.poisson_seed, MU)
 
 
 @functools.lru_cache(maxsize=None)
@@ -58,10 +57,10 @@ def _reference(B, Y, X, S, dist, variant, probe, b=1, loss='lsq', seed=0):
     delta = rng.uniform(0, 2e-5, size=(B, Y, X, S))
     beta = 0.1 * delta
     pr, pi = _probe(probe, Y, X, rng)
-    ref = mref.forward(delta, beta, pr, pi, E, PS, dist, variant, b)
+    ref, _ = ref_model.forward(delta, beta, pr, pi, E, PS, dist, variant, b)
     meas = np.abs(ref) * np.abs(1 + 0.05 * rng.normal(size=ref.shape))
-    rl, rgd, rgb, _, _ = mref.loss_and_grad(delta, beta, pr, pi, E, PS, meas, dist, variant, b,
-                                            loss_and_seed=_poisson_term if loss == 'poisson' else mref.lsq_loss_and_seed)
+    rl, rgd, rgb, _, _ = ref_model.loss_and_grad(delta, beta, pr, pi, E, PS, meas, dist, variant, b,
+                                                 term=POISSON if loss == 'poisson' else ref_model.lsq)
     out = (delta, beta, pr, pi, meas, ref, rl, rgd, rgb)
     for a in out[:6] + out[7:]:
         a.setflags(write=False)
@@ -164,8 +163,8 @@ def test_planes_with_detector_weights(engine_mod, engine, Y, X, loss):
     rng = np.random.default_rng(5)
     w = rng.uniform(0.25, 1.75, size=(Y, X))
     w[10:20, 30:45] = 0
-    term = lambda d, m: (wref.weighted_loss(d, m, w, loss, MU), wref.weighted_seed(d, m, w, loss, MU))      # noqa: E731
-    rl, rgd, rgb, _, _ = mref.loss_and_grad(delta, beta, pr, pi, E, PS, meas, dist, loss_and_seed=term)
+    term = ref_model.data_term(wref.weighted_loss, wref.weighted_seed, w, loss, MU)
+    rl, rgd, rgb, _, _ = ref_model.loss_and_grad(delta, beta, pr, pi, E, PS, meas, dist, term=term)
     eng = engine_mod.MultisliceEngine(Y, X, S, B, with_grad=True, engine=engine)
     eng.set_loss(loss, MU)
     eng.set_physics(E, PS, list(dist))
@@ -286,7 +285,7 @@ def test_fullfield_solver_with_two_planes(engine_mod):
     idx = np.sort(rng.choice(n_theta, mb, replace=False))
     one, zero = np.ones((n, n)), np.zeros((n, n))
     rot = np.stack([orc.apply_rotation(np.stack([od, ob], axis=3), coords[j]) for j in idx])
-    ref = mref.forward(rot[..., 0], rot[..., 1], one, zero, E, PS, dist)
+    ref, _ = ref_model.forward(rot[..., 0], rot[..., 1], one, zero, E, PS, dist)
     prj = np.zeros((n_theta, 2, n, n))
     prj[idx] = (np.abs(ref) * np.abs(1 + 0.05 * rng.normal(size=ref.shape))).astype(np.float32)
     s = FullfieldSolver(n, n, n, n_theta, mb, E, PS, free_prop_cm=list(dist), coord_ls=coords)
@@ -297,7 +296,7 @@ def test_fullfield_solver_with_two_planes(engine_mod):
     assert w.shape == (mb, 2, n, n)
     loss = s.loss_and_grad(idx)
     gd, gb = s.gradient_to_host()
-    rl, rgd, rgb, _ = mref.fullfield_loss_and_grad(od, ob, coords, idx, prj[idx], one, zero, E, PS, dist)
+    rl, rgd, rgb, _ = ref_model.fullfield_loss_and_grad(od, ob, coords, idx, prj[idx], one, zero, E, PS, dist)
     e = (rel(np.abs(w) ** 2, np.abs(ref) ** 2), abs(loss - rl) / abs(rl), rel(gd, rgd), rel(gb, rgb))
     print('planes, full-field solver 64^3, D = 2: intensity / loss / g_delta / g_beta rel err', e)
     assert e[0] <= 1e-5 and e[1] <= 1e-5 and e[2] <= 2e-4 and e[3] <= 2e-4, e

@@ -1,5 +1,5 @@
 """The Poisson (photon-counting) data term (bdof_set_loss, MultisliceEngine.set_loss, loss_type='poisson') on the device, through
-every engine that forms a seed on the transfer-function path, against the float64 reference of tests/poisson_reference.py.
+every engine that forms a seed on the transfer-function path, against the float64 reference of tests/reference_model.py under tests/poisson_reference.py's data term.
 
 Bounds: the ones tests/test_gpu_parity.py asserts for the identical least-squares cases — loss relative 1e-5, gradients relative L2
 2e-4 — because the Poisson seed is the least-squares seed times mu (a + m) / a, a factor good to 1e-7; the float64 twin at the
@@ -14,8 +14,10 @@ pytestmark = pytest.mark.gpu
 from oracle import bdof_oracle as orc
 
 import poisson_reference as pref
+import reference_model as ref_model
 
 MU = 2e6
+POISSON = ref_model.data_term(pref.poisson_loss, pref.poisson_seed, MU)
 
 
 def rel(a, b):
@@ -50,7 +52,7 @@ def _case(engine_mod, B, Y, X, S, fp, variant, probe, seed=0, **eng_kw):
     eng.set_physics(5000., 1e-7, fp, variant=variant)
     eng.set_probe(pr, pi)
     eng.set_object_batch(delta, beta)
-    ref, _ = pref.forward(delta, beta, pr, pi, 5000., 1e-7, fp, variant)
+    ref, _ = ref_model.forward(delta, beta, pr, pi, 5000., 1e-7, fp, variant)
     meas = np.abs(ref) * np.abs(1 + 0.05 * rng.normal(size=ref.shape))
     return eng, delta, beta, pr, pi, meas
 
@@ -71,7 +73,7 @@ def test_poisson_loss_and_gradient_vs_reference(engine_mod, engine, Y, X, fp, pr
     eng.set_loss('poisson', MU)
     loss = eng.loss_grad(B, meas)
     gd, gb = eng.grad_batch_to_host(B)
-    rl, rgd, rgb, _ = pref.poisson_loss_and_grad(delta, beta, pr, pi, 5000., 1e-7, meas, MU, fp, variant)
+    rl, rgd, rgb, _, _ = ref_model.loss_and_grad(delta, beta, pr, pi, 5000., 1e-7, meas, fp, variant, term=POISSON)
     e = (abs(loss - rl) / abs(rl), rel(gd, rgd), rel(gb, rgb))
     print('poisson parity', engine, (Y, X), fp, probe, variant, 'loss / g_delta / g_beta rel err', e)
     assert e[0] <= 1e-5, e
@@ -89,7 +91,7 @@ def test_poisson_plain_residual_form_on_the_resident_engine(engine_mod, fp, vari
     eng.set_loss('poisson', MU)
     loss = eng.loss_grad(B, meas)
     gd, gb = eng.grad_batch_to_host(B)
-    rl, rgd, rgb, _ = pref.poisson_loss_and_grad(delta, beta, pr, pi, 5000., 1e-7, meas, MU, fp, variant)
+    rl, rgd, rgb, _, _ = ref_model.loss_and_grad(delta, beta, pr, pi, 5000., 1e-7, meas, fp, variant, term=POISSON)
     e = (abs(loss - rl) / abs(rl), rel(gd, rgd), rel(gb, rgb))
     print('poisson resident plain form', fp, variant, 'loss / g_delta / g_beta rel err', e)
     assert e[0] <= 1e-5, e
@@ -113,9 +115,9 @@ def test_poisson_float64_twin_vs_reference(engine_mod, Y, X, fp, variant):
     eng.set_physics(5000., 1e-7, fp, variant=variant)
     eng.set_probe(pr, pi)
     eng.set_object_batch(delta, beta)
-    ref, _ = pref.forward(delta, beta, pr64, pi64, 5000., 1e-7, fp, variant)
+    ref, _ = ref_model.forward(delta, beta, pr64, pi64, 5000., 1e-7, fp, variant)
     meas = (np.abs(ref) * np.abs(1 + 0.05 * rng.normal(size=ref.shape))).astype(np.float32).astype(np.float64)
-    rl, rgd, rgb, _ = pref.poisson_loss_and_grad(delta, beta, pr64, pi64, 5000., 1e-7, meas, MU, fp, variant)
+    rl, rgd, rgb, _, _ = ref_model.loss_and_grad(delta, beta, pr64, pi64, 5000., 1e-7, meas, fp, variant, term=POISSON)
     eng.set_loss('poisson', MU)
     eng.enable_tf_f64()
     loss = eng.loss_grad(B, meas, f64=True)
@@ -136,7 +138,7 @@ def test_poisson_seed_only_settings(engine_mod, setting):
         eng.enable_probe_grad(True)
     loss = eng.loss_grad(B, meas)
     gd, gb = eng.grad_batch_to_host(B)
-    rl, rgd, rgb, g0 = pref.poisson_loss_and_grad(delta, beta, pr, pi, 5000., 1e-7, meas, MU, fp)
+    rl, rgd, rgb, g0, _ = ref_model.loss_and_grad(delta, beta, pr, pi, 5000., 1e-7, meas, fp, term=POISSON)
     e = [abs(loss - rl) / abs(rl), rel(gd, rgd), rel(gb, rgb)]
     if setting == 'probe_grad':
         e.append(rel(eng.probe_grad(), g0.sum(axis=0)))
@@ -156,7 +158,7 @@ def test_poisson_solver_parity_64_cubed(engine_mod):
     one, zero = np.ones((n, n)), np.zeros((n, n))
     idx = [1, 3]
     rot = np.stack([orc.apply_rotation(np.stack([od, ob], axis=3), coords[j]) for j in idx])
-    ref, _ = pref.forward(rot[..., 0], rot[..., 1], one, zero, 5000., 1e-7, fp)
+    ref, _ = ref_model.forward(rot[..., 0], rot[..., 1], one, zero, 5000., 1e-7, fp)
     meas = np.ones((n_theta, n, n))
     meas[idx] = np.abs(ref) * np.abs(1 + 0.05 * rng.normal(size=ref.shape))
     s = FullfieldSolver(n, n, n, n_theta, 2, 5000., 1e-7, free_prop_cm=fp, coord_ls=coords, loss_type='poisson', poisson_multiplier=MU)
@@ -164,7 +166,7 @@ def test_poisson_solver_parity_64_cubed(engine_mod):
     s.set_volume(od, ob)
     loss = s.loss_and_grad(idx)
     gd, gb = s.gradient_to_host()
-    rl, rgd, rgb, _ = pref.poisson_loss_and_grad(rot[..., 0], rot[..., 1], one, zero, 5000., 1e-7, meas[idx], MU, fp)
+    rl, rgd, rgb, _, _ = ref_model.loss_and_grad(rot[..., 0], rot[..., 1], one, zero, 5000., 1e-7, meas[idx], fp, term=POISSON)
     wd = sum(orc.apply_rotation_adjoint(rgd[k], coords[j]) for k, j in enumerate(idx))
     wb = sum(orc.apply_rotation_adjoint(rgb[k], coords[j]) for k, j in enumerate(idx))
     e = (abs(loss - rl) / abs(rl), rel(gd, wd), rel(gb, wb))
@@ -257,7 +259,7 @@ def _e2e_run(noise_seed, loss_type, tmp):
     if not os.path.exists(os.path.join(case, 'noisy.h5')):
         os.makedirs(case)
         rot = np.stack([orc.apply_rotation(np.stack([true_d, true_b], axis=3), c) for c in coords])
-        prj, _ = pref.forward(rot[..., 0], rot[..., 1], one, zero, 5000., 1e-7, fp)
+        prj, _ = ref_model.forward(rot[..., 0], rot[..., 1], one, zero, 5000., 1e-7, fp)
         h5io.write_dataset(os.path.join(case, 'clean.h5'), 'exchange/data', prj.astype(np.complex64))
         # n_ph_tx / n_sample_pixel photons per unit intensity (simulation.create_noisy_data): E2E_MU of them
         simulation.create_noisy_data(os.path.join(case, 'clean.h5'), os.path.join(case, 'noisy.h5'), E2E_MU, n_sample_pixel=1,
@@ -316,7 +318,7 @@ def test_poisson_ptychography_lowers_its_loss(engine_mod, tmp_path, monkeypatch)
         obj_pad = np.pad(rot, ((pad[0, 0], pad[0, 1]), (pad[1, 0], pad[1, 1]), (0, 0), (0, 0)), mode='constant')
         subs = np.stack([obj_pad[p[0] + pad[0, 0] - half[0]:p[0] + pad[0, 0] - half[0] + psz[0],
                                  p[1] + pad[1, 0] - half[1]:p[1] + pad[1, 0] - half[1] + psz[1]] for p in pos])
-        data[t], _ = pref.forward(subs[..., 0], subs[..., 1], prr, pii, 5000., 1e-7, 'inf')
+        data[t], _ = ref_model.forward(subs[..., 0], subs[..., 1], prr, pii, 5000., 1e-7, 'inf')
     os.makedirs('case')
     h5io.write_dataset('case/data.h5', 'exchange/data', data)
     init_d, init_b = np.full((n, n, n), 8e-6), np.full((n, n, n), 8e-7)

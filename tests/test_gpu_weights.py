@@ -1,5 +1,5 @@
 """Detector weights (bdof_set_detector_weights, MultisliceEngine.set_detector_weights, detector_weights=...) on the device, through
-every engine that forms a seed on the transfer-function path, against the float64 reference of tests/weights_reference.py.
+every engine that forms a seed on the transfer-function path, against the float64 reference of tests/reference_model.py under tests/weights_reference.py's data term.
 
 Bounds: those of tests/test_gpu_poisson.py — loss relative 1e-5, gradients relative L2 2e-4 — because a weight is one exact
 float32 factor on a seed and on two sums whose error those bounds already cover; the float64 twin at 1e-8 / 2e-7.  Under a
@@ -17,7 +17,7 @@ pytestmark = pytest.mark.gpu
 
 from oracle import bdof_oracle as orc
 
-import poisson_reference as pref
+import reference_model as ref_model
 import weights_reference as wref
 
 MU = 2e6
@@ -58,7 +58,7 @@ def _data(Y, X, fp, probe, seed=0, f32=False):
         delta, beta = delta.astype(np.float32).astype(np.float64), beta.astype(np.float32).astype(np.float64)
         p = (np.asarray(pr) + 1j * np.asarray(pi)).astype(np.complex64)
         pr, pi = p.real.astype(np.float64), p.imag.astype(np.float64)
-    ref, _ = pref.forward(delta, beta, pr, pi, E, PS, fp)
+    ref, _ = ref_model.forward(delta, beta, pr, pi, E, PS, fp)
     meas = np.abs(ref) * np.abs(1 + 0.05 * rng.normal(size=ref.shape))
     if f32:
         meas = meas.astype(np.float32).astype(np.float64)
@@ -68,12 +68,16 @@ def _data(Y, X, fp, probe, seed=0, f32=False):
     return delta, beta, pr, pi, meas, w
 
 
+def _term(w, loss_type):
+    return ref_model.data_term(wref.weighted_loss, wref.weighted_seed, w, loss_type, MU)
+
+
 @functools.lru_cache(maxsize=None)
 def _reference(Y, X, fp, probe, loss_type, weights='random', seed=0, f32=False):
     """The reference's (loss, g_delta, g_beta, g_probe) of a _data case: computed once, shared, never written to."""
     delta, beta, pr, pi, meas, w = _data(Y, X, fp, probe, seed, f32)
     w = {'random': w, 'beamstop': wref.beamstop((Y, X)), 'none': np.ones((Y, X), dtype=np.float32)}[weights]
-    out = wref.loss_and_grad(delta, beta, pr, pi, E, PS, meas, w, loss_type, MU, fp)
+    out = ref_model.loss_and_grad(delta, beta, pr, pi, E, PS, meas, fp, term=_term(w, loss_type))[:4]
     for a in out[1:]:
         a.setflags(write=False)
     return out
@@ -309,7 +313,7 @@ def test_fullfield_solver_with_weights_64_cubed(engine_mod, loss_type):
     one, zero = np.ones((n, n)), np.zeros((n, n))
     idx = [1, 3]
     rot = np.stack([orc.apply_rotation(np.stack([od, ob], axis=3), coords[j]) for j in idx])
-    ref, _ = pref.forward(rot[..., 0], rot[..., 1], one, zero, E, PS, fp)
+    ref, _ = ref_model.forward(rot[..., 0], rot[..., 1], one, zero, E, PS, fp)
     w = wref.random_weights((n, n), rng)
     meas = np.ones((n_theta, n, n))
     meas[idx] = np.abs(ref) * np.abs(1 + 0.05 * rng.normal(size=ref.shape))
@@ -320,7 +324,7 @@ def test_fullfield_solver_with_weights_64_cubed(engine_mod, loss_type):
     s.set_volume(od, ob)
     loss = s.loss_and_grad(idx)
     gd, gb = s.gradient_to_host()
-    rl, rgd, rgb, _ = wref.loss_and_grad(rot[..., 0], rot[..., 1], one, zero, E, PS, meas[idx], w, loss_type, MU, fp)
+    rl, rgd, rgb, _, _ = ref_model.loss_and_grad(rot[..., 0], rot[..., 1], one, zero, E, PS, meas[idx], fp, term=_term(w, loss_type))
     wd = sum(orc.apply_rotation_adjoint(rgd[k], coords[j]) for k, j in enumerate(idx))
     wb = sum(orc.apply_rotation_adjoint(rgb[k], coords[j]) for k, j in enumerate(idx))
     e = (abs(loss - rl) / abs(rl), rel(gd, wd), rel(gb, wb))
@@ -350,7 +354,8 @@ def test_ptycho_solver_with_beamstop_and_dead_pixels(engine_mod, loss_type):
     meas[:, w == 0] = 1e6           # the direct beam behind the stop, hot pixels
     loss = s.loss_and_grad(i_theta, sel, meas)
     gd, gb = s.gradient_to_host()
-    rl, rgd, rgb = wref.ptycho_loss_and_grad(od, ob, coords[i_theta], PTY_POS, PTY_POS[sel], meas, prr, pii, psz, E, PS, w, loss_type, MU)
+    rl, rgd, rgb = ref_model.ptycho_loss_and_grad(od, ob, coords[i_theta], PTY_POS, PTY_POS[sel], meas, prr, pii, psz, E, PS,
+                                                  term=_term(w, loss_type))
     e = (abs(loss - rl) / abs(rl), rel(gd, rgd), rel(gb, rgb))
     print('weights, ptychography solver', loss_type, 'loss / g_delta / g_beta rel err', e)
     assert e[0] <= 1e-5 and e[1] <= 2e-4 and e[2] <= 2e-4, e
@@ -387,7 +392,7 @@ def test_reconstruct_ptychography_with_weights(engine_mod, tmp_path, monkeypatch
         obj_pad = np.pad(rot, ((pad[0, 0], pad[0, 1]), (pad[1, 0], pad[1, 1]), (0, 0), (0, 0)), mode='constant')
         subs = np.stack([obj_pad[p[0] + pad[0, 0] - half[0]:p[0] + pad[0, 0] - half[0] + psz[0],
                                  p[1] + pad[1, 0] - half[1]:p[1] + pad[1, 0] - half[1] + psz[1]] for p in pos])
-        data[t], _ = pref.forward(subs[..., 0], subs[..., 1], prr, pii, E, PS, 'inf')
+        data[t], _ = ref_model.forward(subs[..., 0], subs[..., 1], prr, pii, E, PS, 'inf')
     w = (wref.beamstop(psz) * (wref.random_weights(psz, rng) > 0)).astype(np.float32)
     dirty = data.copy()
     zero = np.argwhere(w == 0)
@@ -442,7 +447,7 @@ def test_reconstruct_fullfield_with_weights(engine_mod, tmp_path, monkeypatch, c
     coords = orc.rotation_lookup([n, n, n], n_theta)
     one, zero = np.ones((n, n)), np.zeros((n, n))
     rot = np.stack([orc.apply_rotation(np.stack([true_d, true_b], axis=3), c) for c in coords])
-    prj, _ = pref.forward(rot[..., 0], rot[..., 1], one, zero, E, PS, fp)
+    prj, _ = ref_model.forward(rot[..., 0], rot[..., 1], one, zero, E, PS, fp)
     data = prj.astype(np.complex64)
     w = wref.random_weights((n, n), rng)
     dirty = data.copy()

@@ -1,42 +1,33 @@
 """Several detector planes per wavefield off the GPU: the float64 reference the GPU tests compare against
-(tests/multidistance_reference.py) is pinned to tests/binning_reference.py where the two models coincide (one plane; two equal
+(tests/reference_model.py) is pinned to its own single distance where the two detector stages coincide (one plane; two equal
 planes), its gradient is checked against central differences of its own loss, the planes of the GPU tests' object are shown to
 differ by far more than the GPU tests' bounds, and the keyword surface of every layer and the C symbol are checked."""
 import numpy as np
 import pytest
 
-import binning_reference as bref
-import multidistance_reference as mref
+import reference_model as ref_model
+from reference_model import rel
 
 E, PS = 5000., 1e-7
 DIST = (5e-5, 1e-4, 2e-4)
 
 
-def rel(a, b):
-    return np.linalg.norm(np.asarray(a) - np.asarray(b)) / max(np.linalg.norm(b), 1e-300)
-
-
-def _setup(B=2, Y=16, X=16, S=12, seed=0):
-    rng = np.random.default_rng(seed)
-    delta = rng.uniform(0, 2e-3, size=(B, Y, X, S))
-    beta = rng.uniform(0, 2e-4, size=(B, Y, X, S))
-    pr = 1 + 0.1 * rng.normal(size=(Y, X))
-    pi = 0.1 * rng.normal(size=(Y, X))
-    return delta, beta, pr, pi, rng
+def _setup():
+    return ref_model.setup(S=12)
 
 
 @pytest.mark.parametrize('b', [1, 2])
 @pytest.mark.parametrize('variant', ['numpy_skip_last', 'tf_all'])
 def test_one_plane_is_the_single_distance_reference_exactly(variant, b):
     delta, beta, pr, pi, rng = _setup()
-    ref, _ = bref.forward(delta, beta, pr, pi, E, PS, 1e-4, variant, b)
-    d = mref.forward(delta, beta, pr, pi, E, PS, [1e-4], variant, b)
+    ref, _ = ref_model.forward(delta, beta, pr, pi, E, PS, 1e-4, variant, b)
+    d, _ = ref_model.forward(delta, beta, pr, pi, E, PS, [1e-4], variant, b)
     assert d.shape == (2, 1, 16, 16) and np.array_equal(d[:, 0], ref)
     meas = np.abs(ref) * np.abs(1 + 0.05 * rng.normal(size=ref.shape))
-    rl, rgd, rgb, rgp, rd = bref.loss_and_grad(delta, beta, pr, pi, E, PS, meas, 1e-4, variant, b)
-    loss, gd, gb, gp, dd = mref.loss_and_grad(delta, beta, pr, pi, E, PS, meas[:, None], [1e-4], variant, b)
+    rl, rgd, rgb, rgp, rd = ref_model.loss_and_grad(delta, beta, pr, pi, E, PS, meas, 1e-4, variant, b)
+    loss, gd, gb, gp, dd = ref_model.loss_and_grad(delta, beta, pr, pi, E, PS, meas[:, None], [1e-4], variant, b)
     diffs = (abs(loss - rl), np.abs(gd - rgd).max(), np.abs(gb - rgb).max(), np.abs(gp - rgp).max(), np.abs(dd[:, 0] - rd).max())
-    print('D = 1 against binning_reference: differences', variant, b, diffs)
+    print('D = 1 against the single distance: differences', variant, b, diffs)
     assert diffs == (0.0, 0.0, 0.0, 0.0, 0.0), diffs
 
 
@@ -46,10 +37,10 @@ def test_two_equal_planes_are_one_plane(variant, b):
     """Two planes at the same distance with the same amplitudes: the mean over 2 B frames is the mean over B, and the two seeds,
     each half of the one plane's, add up to it."""
     delta, beta, pr, pi, rng = _setup()
-    ref, _ = bref.forward(delta, beta, pr, pi, E, PS, 1e-4, variant, b)
+    ref, _ = ref_model.forward(delta, beta, pr, pi, E, PS, 1e-4, variant, b)
     meas = np.abs(ref) * np.abs(1 + 0.05 * rng.normal(size=ref.shape))
-    rl, rgd, rgb, _, _ = bref.loss_and_grad(delta, beta, pr, pi, E, PS, meas, 1e-4, variant, b)
-    loss, gd, gb, _, d = mref.loss_and_grad(delta, beta, pr, pi, E, PS, np.stack([meas, meas], axis=1), [1e-4, 1e-4], variant, b)
+    rl, rgd, rgb, _, _ = ref_model.loss_and_grad(delta, beta, pr, pi, E, PS, meas, 1e-4, variant, b)
+    loss, gd, gb, _, d = ref_model.loss_and_grad(delta, beta, pr, pi, E, PS, np.stack([meas, meas], axis=1), [1e-4, 1e-4], variant, b)
     e = (abs(loss - rl) / abs(rl), rel(gd, rgd), rel(gb, rgb))
     print('two equal planes against one: loss / g_delta / g_beta rel', variant, b, e)
     assert np.array_equal(d[:, 0], d[:, 1])
@@ -64,11 +55,11 @@ def test_reference_gradient_against_central_differences(variant, b):
     test_binning_reference.py (a direction nearly orthogonal to the gradient measures nothing and is drawn again; the criterion
     looks at the direction alone)."""
     delta, beta, pr, pi, rng = _setup()
-    ref = mref.forward(delta, beta, pr, pi, E, PS, DIST, variant, b)
+    ref, _ = ref_model.forward(delta, beta, pr, pi, E, PS, DIST, variant, b)
     assert ref.shape == (2, 3, 16, 16)
     meas = np.abs(ref) * np.abs(1 + 0.05 * rng.normal(size=ref.shape))
-    loss, gd, gb, gp, d = mref.loss_and_grad(delta, beta, pr, pi, E, PS, meas, DIST, variant, b)
-    assert abs(loss - mref.loss_only(delta, beta, pr, pi, E, PS, meas, DIST, variant, b)) <= 1e-14 * abs(loss)
+    loss, gd, gb, gp, d = ref_model.loss_and_grad(delta, beta, pr, pi, E, PS, meas, DIST, variant, b)
+    assert abs(loss - ref_model.loss_only(delta, beta, pr, pi, E, PS, meas, DIST, variant, b)) <= 1e-14 * abs(loss)
     assert rel(d, ref) <= 1e-15
     errs = []
     eps = 1e-7
@@ -79,11 +70,11 @@ def test_reference_gradient_against_central_differences(variant, b):
             while abs(np.sum(g * v)) < 0.1 * np.linalg.norm(g):
                 v = rng.choice([-1.0, 1.0], size=delta.shape)
             if which == 0:
-                lp = mref.loss_only(delta + eps * v, beta, pr, pi, E, PS, meas, DIST, variant, b)
-                lm = mref.loss_only(delta - eps * v, beta, pr, pi, E, PS, meas, DIST, variant, b)
+                lp = ref_model.loss_only(delta + eps * v, beta, pr, pi, E, PS, meas, DIST, variant, b)
+                lm = ref_model.loss_only(delta - eps * v, beta, pr, pi, E, PS, meas, DIST, variant, b)
             else:
-                lp = mref.loss_only(delta, beta + eps * v, pr, pi, E, PS, meas, DIST, variant, b)
-                lm = mref.loss_only(delta, beta - eps * v, pr, pi, E, PS, meas, DIST, variant, b)
+                lp = ref_model.loss_only(delta, beta + eps * v, pr, pi, E, PS, meas, DIST, variant, b)
+                lm = ref_model.loss_only(delta, beta - eps * v, pr, pi, E, PS, meas, DIST, variant, b)
             an = float(np.sum(g * v))
             errs.append(abs((lp - lm) / (2 * eps) - an) / abs(an))
     print('multi-distance reference, directional derivatives rel err', variant, b, errs)
@@ -96,12 +87,12 @@ def test_planes_of_the_gpu_tests_object_differ():
     rng = np.random.default_rng(0)
     delta = rng.uniform(0, 2e-5, size=(2, 64, 64, 6))
     beta = 0.1 * delta
-    d = mref.forward(delta, beta, np.ones((64, 64)), np.zeros((64, 64)), E, PS, DIST)
+    d, _ = ref_model.forward(delta, beta, np.ones((64, 64)), np.zeros((64, 64)), E, PS, DIST)
     e = [rel(np.abs(d[:, j]), np.abs(d[:, j + 1])) for j in range(2)]
     ei = [rel(np.abs(d[:, j]) ** 2, np.abs(d[:, j + 1]) ** 2) for j in range(2)]
     meas = np.abs(d) * np.abs(1 + 0.05 * rng.normal(size=d.shape))
-    _, gd3, _, _, _ = mref.loss_and_grad(delta, beta, np.ones((64, 64)), np.zeros((64, 64)), E, PS, meas, DIST)
-    _, gd1, _, _, _ = mref.loss_and_grad(delta, beta, np.ones((64, 64)), np.zeros((64, 64)), E, PS, meas[:, 1:2], DIST[1:2])
+    _, gd3, _, _, _ = ref_model.loss_and_grad(delta, beta, np.ones((64, 64)), np.zeros((64, 64)), E, PS, meas, DIST)
+    _, gd1, _, _, _ = ref_model.loss_and_grad(delta, beta, np.ones((64, 64)), np.zeros((64, 64)), E, PS, meas[:, 1:2], DIST[1:2])
     print('weak object, neighbouring planes: |d| rel', e, 'intensity rel', ei, 'three-plane gradient against the middle plane alone', rel(gd3, gd1))
     assert min(e) >= 1e-4, e
     assert rel(gd3, gd1) >= 1e-2
@@ -123,7 +114,10 @@ def test_distances_keyword():
 
 
 def test_planes_keywords_are_checked_before_anything_touches_a_file_or_a_gpu(tmp_path):
-    from beyond_dof_amd.engine import check_planes_path
+    from beyond_dof_amd.engine import check_model_options
+
+    def check_planes_path(free_prop_cm, **path):
+        return check_model_options(free_prop_cm=free_prop_cm, **path)
     from beyond_dof_amd.fullfield import reconstruct_fullfield
     from beyond_dof_amd.simulation import create_fullfield_data_numpy
     from beyond_dof_amd.solver import FullfieldSolver

@@ -1,23 +1,15 @@
 """The Poisson (photon-counting) data term off the GPU: the float64 reference the GPU tests compare against
-(tests/poisson_reference.py) is itself checked against central differences of its own loss through the oracle's unmodified
-forward model; the loss's defining properties; the keyword surface of the two entry points; the C symbol."""
+(tests/reference_model.py under tests/poisson_reference.py's data term) is itself checked against central differences of its
+own loss; the loss's defining properties; the keyword surface of the two entry points; the C symbol."""
 import numpy as np
 import pytest
 
-from oracle import bdof_oracle as orc
-
 import poisson_reference as pref
+import reference_model as ref_model
+from reference_model import setup as _setup
 
 MU = 2e6
-
-
-def _setup(B=2, Y=16, X=16, S=6, seed=0):
-    rng = np.random.default_rng(seed)
-    delta = rng.uniform(0, 2e-3, size=(B, Y, X, S))
-    beta = rng.uniform(0, 2e-4, size=(B, Y, X, S))
-    pr = 1 + 0.1 * rng.normal(size=(Y, X))
-    pi = 0.1 * rng.normal(size=(Y, X))
-    return delta, beta, pr, pi, rng
+POISSON = ref_model.data_term(pref.poisson_loss, pref.poisson_seed, MU)
 
 
 @pytest.mark.parametrize('fp', [None, 1e-4, 'inf'])
@@ -27,10 +19,10 @@ def test_reference_gradient_against_central_differences(fp, variant):
     takes directional derivatives) against central differences of poisson_loss over orc.multislice_propagate_batch_numpy, to the
     1e-6 the oracle's own gradient is held to there."""
     delta, beta, pr, pi, rng = _setup()
-    ref, _ = pref.forward(delta, beta, pr, pi, 5000., 1e-7, fp, variant)
+    ref, _ = ref_model.forward(delta, beta, pr, pi, 5000., 1e-7, fp, variant)
     meas = np.abs(ref) * np.abs(1 + 0.05 * rng.normal(size=ref.shape))
-    loss, gd, gb, gp = pref.poisson_loss_and_grad(delta, beta, pr, pi, 5000., 1e-7, meas, MU, fp, variant)
-    assert abs(loss - pref.loss_only(delta, beta, pr, pi, 5000., 1e-7, meas, MU, fp, variant)) <= 1e-14 * abs(loss)
+    loss, gd, gb, gp = ref_model.loss_and_grad(delta, beta, pr, pi, 5000., 1e-7, meas, fp, variant, term=POISSON)[:4]
+    assert abs(loss - ref_model.loss_only(delta, beta, pr, pi, 5000., 1e-7, meas, fp, variant, term=POISSON)) <= 1e-14 * abs(loss)
     assert gp.shape == ref.shape
     errs = []
     for which in (0, 1):
@@ -38,11 +30,11 @@ def test_reference_gradient_against_central_differences(fp, variant):
             v = rng.choice([-1.0, 1.0], size=delta.shape)
             eps = 1e-7
             if which == 0:
-                lp = pref.loss_only(delta + eps * v, beta, pr, pi, 5000., 1e-7, meas, MU, fp, variant)
-                lm = pref.loss_only(delta - eps * v, beta, pr, pi, 5000., 1e-7, meas, MU, fp, variant)
+                lp = ref_model.loss_only(delta + eps * v, beta, pr, pi, 5000., 1e-7, meas, fp, variant, term=POISSON)
+                lm = ref_model.loss_only(delta - eps * v, beta, pr, pi, 5000., 1e-7, meas, fp, variant, term=POISSON)
             else:
-                lp = pref.loss_only(delta, beta + eps * v, pr, pi, 5000., 1e-7, meas, MU, fp, variant)
-                lm = pref.loss_only(delta, beta - eps * v, pr, pi, 5000., 1e-7, meas, MU, fp, variant)
+                lp = ref_model.loss_only(delta, beta + eps * v, pr, pi, 5000., 1e-7, meas, fp, variant, term=POISSON)
+                lm = ref_model.loss_only(delta, beta - eps * v, pr, pi, 5000., 1e-7, meas, fp, variant, term=POISSON)
             fd = (lp - lm) / (2 * eps)
             an = float(np.sum((gd if which == 0 else gb) * v))
             errs.append(abs(fd - an) / abs(an))
@@ -55,17 +47,17 @@ def test_reference_probe_gradient_against_central_differences():
     model rounds the probe to complex64 (np_funcs.py:20-21), so the differences step between float32 numbers."""
     delta, beta, pr, pi, rng = _setup(seed=2)
     pr, pi = pr.astype(np.float32).astype(np.float64), pi.astype(np.float32).astype(np.float64)
-    ref, _ = pref.forward(delta, beta, pr, pi, 5000., 1e-7, 1e-4)
+    ref, _ = ref_model.forward(delta, beta, pr, pi, 5000., 1e-7, 1e-4)
     meas = np.abs(ref) * np.abs(1 + 0.05 * rng.normal(size=ref.shape))
-    _, _, _, gp = pref.poisson_loss_and_grad(delta, beta, pr, pi, 5000., 1e-7, meas, MU, 1e-4)
+    _, _, _, gp = ref_model.loss_and_grad(delta, beta, pr, pi, 5000., 1e-7, meas, 1e-4, term=POISSON)[:4]
     g = gp.sum(axis=0)
     step = np.float32(2.0 ** -10)               # exactly representable beside values of size one: no rounding of the stepped probe
     for part in (0, 1):
         v = rng.choice([-1.0, 1.0], size=pr.shape) * float(step)
         args_p = (pr + v, pi) if part == 0 else (pr, pi + v)
         args_m = (pr - v, pi) if part == 0 else (pr, pi - v)
-        lp = pref.loss_only(delta, beta, *args_p, 5000., 1e-7, meas, MU, 1e-4)
-        lm = pref.loss_only(delta, beta, *args_m, 5000., 1e-7, meas, MU, 1e-4)
+        lp = ref_model.loss_only(delta, beta, *args_p, 5000., 1e-7, meas, 1e-4, term=POISSON)
+        lm = ref_model.loss_only(delta, beta, *args_m, 5000., 1e-7, meas, 1e-4, term=POISSON)
         an = float(np.sum((g.real if part == 0 else g.imag) * v))
         # central differences with a step of 1e-3: their own truncation error is (step)^2 ~ 1e-6 relative
         assert abs((lp - lm) / 2 - an) <= 1e-4 * abs(an), (part, (lp - lm) / 2, an)

@@ -1,4 +1,5 @@
-"""Detector weights off the GPU: the float64 reference the GPU tests compare against (tests/weights_reference.py) against the
+"""Detector weights off the GPU: the float64 reference the GPU tests compare against (tests/reference_model.py under
+tests/weights_reference.py's data term) against the
 oracle and the Poisson reference at w = 1, against central differences of its own weighted loss, and for what w = 0 means; the
 keyword surface of the two entry points; the checks of a weight plane; the HDF5 writer that puts a weight plane beside the data;
 the C symbol."""
@@ -8,23 +9,17 @@ import pytest
 from oracle import bdof_oracle as orc
 
 import poisson_reference as pref
+import reference_model as ref_model
 import weights_reference as wref
+from reference_model import rel, setup as _setup
 
+loss_only = ref_model.loss_only
 MU = 2e6
 EPS = np.finfo(np.float64).eps
 
 
-def _setup(B=2, Y=16, X=16, S=6, seed=0):
-    rng = np.random.default_rng(seed)
-    delta = rng.uniform(0, 2e-3, size=(B, Y, X, S))
-    beta = rng.uniform(0, 2e-4, size=(B, Y, X, S))
-    pr = 1 + 0.1 * rng.normal(size=(Y, X))
-    pi = 0.1 * rng.normal(size=(Y, X))
-    return delta, beta, pr, pi, rng
-
-
-def rel(a, b):
-    return np.linalg.norm(np.asarray(a) - np.asarray(b)) / np.linalg.norm(b)
+def _weighted(w, loss_type):
+    return ref_model.data_term(wref.weighted_loss, wref.weighted_seed, w, loss_type, MU)
 
 
 @pytest.mark.parametrize('fp', [None, 1e-4, 'inf'])
@@ -37,16 +32,17 @@ def test_unit_weights_reproduce_the_unweighted_references(fp, variant):
     gradient is linear in a residual that is 5 % of the amplitude, which divides that by 0.05: 64 eps on the loss and 4096 eps
     (9e-13) on a gradient's relative L2 error leave an order of magnitude over both."""
     delta, beta, pr, pi, rng = _setup()
-    ref, _ = pref.forward(delta, beta, pr, pi, 5000., 1e-7, fp, variant)
+    ref, _ = ref_model.forward(delta, beta, pr, pi, 5000., 1e-7, fp, variant)
     meas = np.abs(ref) * np.abs(1 + 0.05 * rng.normal(size=ref.shape))
     one = np.ones(ref.shape[1:])
-    l, gd, gb, gp = wref.loss_and_grad(delta, beta, pr, pi, 5000., 1e-7, meas, one, 'lsq', MU, fp, variant)
+    l, gd, gb, gp = ref_model.loss_and_grad(delta, beta, pr, pi, 5000., 1e-7, meas, fp, variant, term=_weighted(one, 'lsq'))[:4]
     rl, rgd, rgb, rgp = orc.multislice_loss_and_grad(delta, beta, pr, pi, 5000., 1e-7, meas, fp, variant, return_probe_grad=True)
     e = (abs(l - rl) / rl, rel(gd, rgd), rel(gb, rgb), rel(gp, rgp))
     print('unit weights against the oracle (lsq)', fp, variant, e)
     assert e[0] <= 64 * EPS and max(e[1:]) <= 4096 * EPS, e
-    l, gd, gb, gp = wref.loss_and_grad(delta, beta, pr, pi, 5000., 1e-7, meas, one, 'poisson', MU, fp, variant)
-    rl, rgd, rgb, rgp = pref.poisson_loss_and_grad(delta, beta, pr, pi, 5000., 1e-7, meas, MU, fp, variant)
+    l, gd, gb, gp = ref_model.loss_and_grad(delta, beta, pr, pi, 5000., 1e-7, meas, fp, variant, term=_weighted(one, 'poisson'))[:4]
+    rl, rgd, rgb, rgp = ref_model.loss_and_grad(delta, beta, pr, pi, 5000., 1e-7, meas, fp, variant,
+                                                term=ref_model.data_term(pref.poisson_loss, pref.poisson_seed, MU))[:4]
     e = (abs(l - rl) / rl, rel(gd, rgd), rel(gb, rgb), rel(gp, rgp))
     print('unit weights against poisson_reference', fp, variant, e)
     assert e[0] <= 8 * EPS and max(e[1:]) <= 8 * EPS, e          # the same forward sweep and the same seed, times 1.0
@@ -62,13 +58,14 @@ def test_weighted_gradient_against_central_differences(loss_type, fp, variant):
     a directional derivative that happens to come out at 0.33 where its neighbours are 23 and -1.8.  At 2e-8 the two terms are
     3e-8 and 2e-8."""
     delta, beta, pr, pi, rng = _setup()
-    ref, _ = pref.forward(delta, beta, pr, pi, 5000., 1e-7, fp, variant)
+    ref, _ = ref_model.forward(delta, beta, pr, pi, 5000., 1e-7, fp, variant)
     meas = np.abs(ref) * np.abs(1 + 0.05 * rng.normal(size=ref.shape))
     w = wref.random_weights(ref.shape[1:], rng)
     assert (w == 0).sum() > 5
-    args = (5000., 1e-7, meas, w, loss_type, MU, fp, variant)
-    loss, gd, gb, gp = wref.loss_and_grad(delta, beta, pr, pi, *args)
-    assert abs(loss - wref.loss_only(delta, beta, pr, pi, *args)) <= 1e-14 * abs(loss)
+    args = (5000., 1e-7, meas, fp, variant)
+    term = _weighted(w, loss_type)
+    loss, gd, gb, gp = ref_model.loss_and_grad(delta, beta, pr, pi, *args, term=term)[:4]
+    assert abs(loss - loss_only(delta, beta, pr, pi, *args, term=term)) <= 1e-14 * abs(loss)
     assert gp.shape == ref.shape
     errs = []
     for which in (0, 1):
@@ -76,9 +73,9 @@ def test_weighted_gradient_against_central_differences(loss_type, fp, variant):
             v = rng.choice([-1.0, 1.0], size=delta.shape)
             eps = 2e-8
             if which == 0:
-                lp, lm = wref.loss_only(delta + eps * v, beta, pr, pi, *args), wref.loss_only(delta - eps * v, beta, pr, pi, *args)
+                lp, lm = loss_only(delta + eps * v, beta, pr, pi, *args, term=term), loss_only(delta - eps * v, beta, pr, pi, *args, term=term)
             else:
-                lp, lm = wref.loss_only(delta, beta + eps * v, pr, pi, *args), wref.loss_only(delta, beta - eps * v, pr, pi, *args)
+                lp, lm = loss_only(delta, beta + eps * v, pr, pi, *args, term=term), loss_only(delta, beta - eps * v, pr, pi, *args, term=term)
             fd = (lp - lm) / (2 * eps)
             an = float(np.sum((gd if which == 0 else gb) * v))
             errs.append(abs(fd - an) / abs(an))
@@ -91,17 +88,17 @@ def test_weighted_probe_gradient_against_central_differences(loss_type):
     """As test_reference_probe_gradient_against_central_differences: steps between float32 numbers, 1e-4."""
     delta, beta, pr, pi, rng = _setup(seed=2)
     pr, pi = pr.astype(np.float32).astype(np.float64), pi.astype(np.float32).astype(np.float64)
-    ref, _ = pref.forward(delta, beta, pr, pi, 5000., 1e-7, 1e-4)
+    ref, _ = ref_model.forward(delta, beta, pr, pi, 5000., 1e-7, 1e-4)
     meas = np.abs(ref) * np.abs(1 + 0.05 * rng.normal(size=ref.shape))
     w = wref.random_weights(ref.shape[1:], rng)
-    tail = (5000., 1e-7, meas, w, loss_type, MU, 1e-4)
-    g = wref.loss_and_grad(delta, beta, pr, pi, *tail)[3].sum(axis=0)
+    tail, term = (5000., 1e-7, meas, 1e-4), _weighted(w, loss_type)
+    g = ref_model.loss_and_grad(delta, beta, pr, pi, *tail, term=term)[3].sum(axis=0)
     step = np.float32(2.0 ** -10)
     for part in (0, 1):
         v = rng.choice([-1.0, 1.0], size=pr.shape) * float(step)
         args_p = (pr + v, pi) if part == 0 else (pr, pi + v)
         args_m = (pr - v, pi) if part == 0 else (pr, pi - v)
-        lp, lm = wref.loss_only(delta, beta, *args_p, *tail), wref.loss_only(delta, beta, *args_m, *tail)
+        lp, lm = loss_only(delta, beta, *args_p, *tail, term=term), loss_only(delta, beta, *args_m, *tail, term=term)
         an = float(np.sum((g.real if part == 0 else g.imag) * v))
         assert abs((lp - lm) / 2 - an) <= 1e-4 * abs(an), (part, (lp - lm) / 2, an)
 
@@ -111,20 +108,20 @@ def test_weighted_probe_gradient_against_central_differences(loss_type):
 def test_amplitudes_under_a_zero_weight_take_no_part(loss_type, fp):
     """Whatever m holds where w = 0 — NaN, inf, a saturated count, a negative number — loss and gradients do not move by a bit."""
     delta, beta, pr, pi, rng = _setup(seed=3)
-    ref, _ = pref.forward(delta, beta, pr, pi, 5000., 1e-7, fp)
+    ref, _ = ref_model.forward(delta, beta, pr, pi, 5000., 1e-7, fp)
     meas = np.abs(ref) * np.abs(1 + 0.05 * rng.normal(size=ref.shape))
     w = wref.random_weights(ref.shape[1:], rng)
     dirty = meas.copy()
     junk = np.array([np.nan, np.inf, 65535.0, -1.0, 1e30])
     dirty[:, w == 0] = junk[rng.integers(0, len(junk), size=dirty[:, w == 0].shape)]
     assert np.isnan(dirty).any() and np.isinf(dirty).any()
-    a = wref.loss_and_grad(delta, beta, pr, pi, 5000., 1e-7, meas, w, loss_type, MU, fp)
-    b = wref.loss_and_grad(delta, beta, pr, pi, 5000., 1e-7, dirty, w, loss_type, MU, fp)
+    a = ref_model.loss_and_grad(delta, beta, pr, pi, 5000., 1e-7, meas, fp, term=_weighted(w, loss_type))[:4]
+    b = ref_model.loss_and_grad(delta, beta, pr, pi, 5000., 1e-7, dirty, fp, term=_weighted(w, loss_type))[:4]
     assert a[0] == b[0] and np.isfinite(a[0])
     for x, y in zip(a[1:], b[1:]):
         assert np.array_equal(x, y) and np.isfinite(x).all()
     # ... and the divisor is the pixel count: halving every weight halves the loss, masking pixels does not renormalise it
-    half = wref.loss_and_grad(delta, beta, pr, pi, 5000., 1e-7, meas, 0.5 * w, loss_type, MU, fp)
+    half = ref_model.loss_and_grad(delta, beta, pr, pi, 5000., 1e-7, meas, fp, term=_weighted(0.5 * w, loss_type))
     assert abs(half[0] - 0.5 * a[0]) <= 4 * EPS * a[0]
 
 

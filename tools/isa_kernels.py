@@ -4,7 +4,8 @@
 A host-code refactor must leave the device code alone.  The order in which hipcc emits template instantiations follows the host
 code, so two builds are compared per symbol, not per file: run this on both trees and `diff` the outputs.  The hash covers the
 function's instructions and its kernel descriptor (registers, LDS, scratch); the local labels, which carry the function's position
-in the file (.LBB12_3, .Lfunc_end12, and BB12_3 in the comments), are renumbered out.
+in the file (.LBB12_3, .Lfunc_end12), are renumbered out, and the assembler's trailing `; ...` comments are dropped: they
+name such labels too, and the column they start in depends on how many digits the label's number had.
 
 usage: python tools/isa_kernels.py [extra hipcc flags] > kernels.txt
 """
@@ -16,6 +17,7 @@ from check_spills import KERNEL, device_isa
 
 LOCAL = re.compile(r'(?:\.L|\b)(BB|func_begin|func_end|tmp|JTI)\d+')
 DESC = re.compile(r'^\s*\.amdhsa_kernel\s+(\w+)')
+COMMENT = re.compile(r'\s*;.*$')
 
 
 def kernels(isa):
@@ -29,7 +31,7 @@ def kernels(isa):
         d = DESC.match(line)
         if d:
             desc = d.group(1)
-        line = LOCAL.sub(lambda g: '.L' + g.group(1), line)
+        line = LOCAL.sub(lambda g: '.L' + g.group(1), COMMENT.sub('', line)).rstrip()
         if desc is not None:
             out.setdefault(desc, []).append(line)
             if line.strip() == '.end_amdhsa_kernel':
