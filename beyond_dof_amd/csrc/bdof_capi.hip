@@ -21,6 +21,8 @@
 #include "bdof_comm.h"
 #include <rocfft/rocfft.h>
 #include <map>
+#include <optional>
+#include <functional>
 #include <array>
 
 #define BDOF_ERR_ARG (-1)
@@ -317,11 +319,14 @@ static cf cfl(std::complex<double> a) { return make_float2((float)a.real(), (flo
 static cf carrier_at(const bdof_ctx* c, int z) { return cfl(carrier_z(c, z)); }
 static cf cshift_at(const bdof_ctx* c, int z) { return cfl(carrier_z(c, z) * c->cbm1); }                  // a_z (cbar - 1)
 static cf carrier_phi_at(const bdof_ctx* c, int z) { return cfl(carrier_z(c, z) * (1.0 + c->cbm1)); }      // constant part of phi_z
+// a transfer-function step follows the last slice: variant tf_all, except in front of a far-field detector
+// (|F P phi| = |H F phi| = |F phi|)
+static bool step_after_last(const bdof_ctx* c) { return c->variant == BDOF_VARIANT_TF_ALL && c->det_mode != BDOF_DET_FAR; }
 // constant part of the detector wave (real-space detectors) / of the wave whose fft2 is the far field
 // plane: which of the detector planes (bdof_set_detector_planes; 0 with one plane)
 static std::complex<double> carrier_end(const bdof_ctx* c, int plane = 0) {
     std::complex<double> a = carrier_z(c, n_steps(c) - 1) * (1.0 + c->cbm1);
-    if (c->det_mode != BDOF_DET_FAR && c->variant == BDOF_VARIANT_TF_ALL) a *= c->h00;
+    if (step_after_last(c)) a *= c->h00;
     if (c->det_mode == BDOF_DET_NEAR) a *= c->planes > 1 ? c->hdet00_pl[plane] : c->hdet00;
     return a;
 }
@@ -1030,22 +1035,39 @@ static const cf* hs_slice(const bdof_ctx* c, int z) {
 
 static int g_elem_grid(const bdof_ctx* c, size_t n) { return (int)std::min<size_t>((n + 255) / 256, (size_t)c->ncu * 16); }
 
-// one transfer-function step in place: field <- F^-1' ( h * F field )
-static int generic_prop(bdof_ctx* c, int B, rocfft_plan pf, rocfft_plan pi, cf* field, const cf* h, int conj_h) {
-    ProfScope ps(c, BDOF_K_COL_PROP, c->stream);
-    void* buf[1] = {field};
-    RFC(c, rocfft_execute(pf, buf, nullptr, c->fft.info));
-    const size_t n = (size_t)B * c->NX * c->NY;
-    hipLaunchKernelGGL(k_g_hmul, dim3(g_elem_grid(c, n)), dim3(256), 0, c->stream, field, h, B, c->NX, c->NY, conj_h);
-    RFC(c, rocfft_execute(pi, buf, nullptr, c->fft.info));
+// The one free-space step of the rocFFT paths, in place on B fields [NX][NY] of either precision: fields <- F^-1' ( h * F fields ),
+// queued on stream st, whose execution info x is (c->fft and c->stream, or the auxiliary pair once bdof_fields_free_step_aux has
+// given it room).  The table is h[kx][ky], or the fused engine's h[ky][kx]; it carries the transforms' 1 / (NX NY), unless
+// scale says otherwise (float64 [kx][ky] tables only).  prof_cls: the profiling class the step is filed under, if any.
+enum TableOrder { H_KXKY, H_KYKX };
+static int free_step(bdof_ctx* c, FftExec& x, hipStream_t st, void* fields, int B, int NX, int NY, const void* h, TableOrder order, int conj_h,
+                     bool dbl, int prof_cls = -1, double scale = 1.0) {
+    rocfft_plan pf, pi;
+    if (int r = field_plans(c, NX, NY, B, dbl, &pf, &pi)) return r;
+    std::optional<ProfScope> ps;
+    if (prof_cls >= 0) ps.emplace(c, prof_cls, st);
+    void* buf[1] = {fields};
+    const size_t n = (size_t)B * NX * NY;
+    const dim3 grid(g_elem_grid(c, n));
+    RFC(c, rocfft_execute(pf, buf, nullptr, x.info));
+    if (scale != 1.0)
+        hipLaunchKernelGGL((k_hmul<double2, false, true>), grid, dim3(256), 0, st, (double2*)fields, (const double2*)h, NX, NY, n, conj_h, scale);
+    else with_bool(order == H_KYKX, [&](auto KYKX) {
+        if (dbl) hipLaunchKernelGGL((k_hmul<double2, KYKX>), grid, dim3(256), 0, st, (double2*)fields, (const double2*)h, NX, NY, n, conj_h, 1.0);
+        else hipLaunchKernelGGL((k_hmul<float2, KYKX>), grid, dim3(256), 0, st, (float2*)fields, (const float2*)h, NX, NY, n, conj_h, 1.f);
+    });
+    RFC(c, rocfft_execute(pi, buf, nullptr, x.info));
     return 0;
+}
+// a transfer-function step of the generic engine's ctx fields (tables in the fused engine's order), filed under BDOF_K_COL_PROP
+static int generic_prop(bdof_ctx* c, int B, void* field, const void* h, int conj_h, bool dbl = false) {
+    return free_step(c, c->fft, c->stream, field, B, c->NX, c->NY, h, H_KYKX, conj_h, dbl, BDOF_K_COL_PROP);
 }
 
 // Forward sweep; leaves the field the detector starts from in bufA (eps part) and returns its carrier.
-static int generic_forward_sweep(bdof_ctx* c, int B, bool tape, rocfft_plan pf, rocfft_plan pi, std::complex<double>* carrier_out) {
+static int generic_forward_sweep(bdof_ctx* c, int B, bool tape, rocfft_plan pf, std::complex<double>* carrier_out) {
     const size_t fld = (size_t)c->Bmax * c->NX * c->NY;
     const size_t n = (size_t)B * c->NX * c->NY;
-    const bool tf_all = c->variant == BDOF_VARIANT_TF_ALL;
     std::complex<double> a = c->a0;
     int r;
     const int nz = n_steps(c);
@@ -1058,16 +1080,15 @@ static int generic_forward_sweep(bdof_ctx* c, int B, bool tape, rocfft_plan pf, 
             with_bool(c->bin > 1, [&](auto BIN) { hipLaunchKernelGGL(k_g_modulate<BIN>, dim3(g_elem_grid(c, n)), dim3(256), 0, c->stream, m); });
             a *= 1.0 + c->cbm1;                  // mean-refraction carrier: phi_z rides on cbar a_z
         }
-        const bool last = z == nz - 1;
-        if (!last || (tf_all && c->det_mode != BDOF_DET_FAR)) {
-            if ((r = generic_prop(c, B, pf, pi, c->bufA, hs_slice(c, z), 0))) return r;      // the slice's dithered copy of H
+        if (z < nz - 1 || step_after_last(c)) {
+            if ((r = generic_prop(c, B, c->bufA, hs_slice(c, z), 0))) return r;      // the slice's dithered copy of H
             a *= c->h00;
         }
     }
     if (c->det_mode == BDOF_DET_NEAR && c->planes > 1) {
         // detector planes: the sweep ends in front of the detector step (generic_to_planes takes it from here)
     } else if (c->det_mode == BDOF_DET_NEAR) {
-        if ((r = generic_prop(c, B, pf, pi, c->bufA, c->hdet, 0))) return r;
+        if ((r = generic_prop(c, B, c->bufA, c->hdet, 0))) return r;
         a *= c->hdet00;
     } else if (c->det_mode == BDOF_DET_FAR) {
         void* buf[1] = {c->bufA};
@@ -1096,11 +1117,11 @@ static GLossArgs g_loss_args(bdof_ctx* c, int B, const DetPlane& det, cf* field,
 // Detector planes on the generic engine: plane j's field of the batch, [D][Bmax][NX][NY] in det_pl
 static cf* generic_plane(const bdof_ctx* c, int j) { return c->det_pl + (size_t)j * c->Bmax * c->NX * c->NY; }
 // the wave in front of the detector step (bufA) stepped to every plane: one copy and one generic_prop per plane
-static int generic_to_planes(bdof_ctx* c, int B, rocfft_plan pf, rocfft_plan pi) {
+static int generic_to_planes(bdof_ctx* c, int B) {
     const size_t n = (size_t)B * c->NX * c->NY;
     for (int j = 0; j < c->planes; ++j) {
         HIPC(c, hipMemcpyAsync(generic_plane(c, j), c->bufA, n * sizeof(cf), hipMemcpyDeviceToDevice, c->stream));
-        if (int r = generic_prop(c, B, pf, pi, generic_plane(c, j), c->hdet_pl + (size_t)j * c->NX * c->NY, 0)) return r;
+        if (int r = generic_prop(c, B, generic_plane(c, j), c->hdet_pl + (size_t)j * c->NX * c->NY, 0)) return r;
     }
     return 0;
 }
@@ -1110,9 +1131,9 @@ static int generic_forward(bdof_ctx* c, int B, void* out_wave, bool keep_tape) {
     int r = field_plans(c, c->NX, c->NY, B, false, &pf, &pi);
     if (r) return r;
     std::complex<double> a;
-    if ((r = generic_forward_sweep(c, B, keep_tape, pf, pi, &a))) return r;
+    if ((r = generic_forward_sweep(c, B, keep_tape, pf, &a))) return r;
     if (out_wave && c->planes > 1) {
-        if ((r = generic_to_planes(c, B, pf, pi))) return r;
+        if ((r = generic_to_planes(c, B))) return r;
         const size_t n = (size_t)B * c->NX * c->NY;
         for (int j = 0; j < c->planes; ++j) {
             GLossArgs la = g_loss_args(c, B, wave_plane(c, a * c->hdet00_pl[j]), generic_plane(c, j), (cf*)out_wave + (size_t)j * c->NX * c->NY, nullptr);
@@ -1133,16 +1154,15 @@ static int generic_loss_grad(bdof_ctx* c, int B, const float* meas, void* out_wa
     if (r) return r;
     const size_t fld = (size_t)c->Bmax * c->NX * c->NY;
     const size_t n = (size_t)B * c->NX * c->NY;
-    const bool tf_all = c->variant == BDOF_VARIANT_TF_ALL;
     std::complex<double> a;
-    if ((r = generic_forward_sweep(c, B, true, pf, pi, &a))) return r;
+    if ((r = generic_forward_sweep(c, B, true, pf, &a))) return r;
     const int egrid = g_elem_grid(c, n);
     const bool f64 = c->adj64;
     if (f64 && !c->have_h64) return fail(c, BDOF_ERR_STATE, "float64 adjoint: bdof_set_physics_f64 has not been called");
     if (c->planes > 1) {
         // Detector planes: the data term once per plane on its own field (the carrier as the sweep's recurrence left it, times
         // the plane's DC value), the adjoint detector step per plane, and the sum of the D results in bufA
-        if ((r = generic_to_planes(c, B, pf, pi))) return r;
+        if ((r = generic_to_planes(c, B))) return r;
         const size_t pl = (size_t)c->NX * c->NY;
         const int lgrid = std::min(egrid, c->npartial);
         for (int j = 0; j < c->planes; ++j) {
@@ -1158,7 +1178,7 @@ static int generic_loss_grad(bdof_ctx* c, int B, const float* meas, void* out_wa
         }
         hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, c->stream, c->partial, lgrid * c->planes, 1.0 / ((double)B * c->planes * c->NX * c->NY), c->loss_dev);
         for (int j = 0; j < c->planes; ++j) {
-            if ((r = generic_prop(c, B, pf, pi, generic_plane(c, j), c->hdet_pl + j * pl, 1))) return r;
+            if ((r = generic_prop(c, B, generic_plane(c, j), c->hdet_pl + j * pl, 1))) return r;
             hipLaunchKernelGGL(k_g_accumulate, dim3(egrid), dim3(256), 0, c->stream, c->bufA, generic_plane(c, j), n, j == 0 ? 1 : 0);
         }
     } else {
@@ -1178,18 +1198,10 @@ static int generic_loss_grad(bdof_ctx* c, int B, const float* meas, void* out_wa
         rocfft_plan pf64, pi64;
         if ((r = field_plans(c, c->NX, c->NY, B, true, &pf64, &pi64))) return r;
         void* b64[1] = {c->g64};
-        auto prop64 = [&](const double2* h) -> int {
-            ProfScope ps(c, BDOF_K_COL_PROP, c->stream);
-            RFC(c, rocfft_execute(pf64, b64, nullptr, c->fft.info));
-            hipLaunchKernelGGL(k_g_hmul64, dim3(egrid), dim3(256), 0, c->stream, c->g64, h, B, c->NX, c->NY, 1);
-            RFC(c, rocfft_execute(pi64, b64, nullptr, c->fft.info));
-            return 0;
-        };
-        if (c->det_mode == BDOF_DET_NEAR) { if ((r = prop64(c->hdet64))) return r; }
+        if (c->det_mode == BDOF_DET_NEAR) { if ((r = generic_prop(c, B, c->g64, c->hdet64, 1, true))) return r; }
         else if (c->det_mode == BDOF_DET_FAR) RFC(c, rocfft_execute(pi64, b64, nullptr, c->fft.info));
         for (int z = c->S - 1; z >= 0; --z) {
-            const bool prop_after = z < c->S - 1 || (tf_all && c->det_mode != BDOF_DET_FAR);
-            if (prop_after && (r = prop64(c->hs64))) return r;
+            if ((z < c->S - 1 || step_after_last(c)) && (r = generic_prop(c, B, c->g64, c->hs64, 1, true))) return r;
             ProfScope ps(c, BDOF_K_ROW_BWD, c->stream);
             GBwd64Args ba{c->g64, c->tape + (size_t)z * fld, c->grot, c->obj, B, c->NX, c->NY, z, (double)c->k,
                           d2(carrier_z(c, z) * (1.0 + c->cbm1)), c->pstack ? 1 : 0};
@@ -1204,14 +1216,13 @@ static int generic_loss_grad(bdof_ctx* c, int B, const float* meas, void* out_wa
     if (c->det_mode == BDOF_DET_NEAR && c->planes > 1) {
         // (detector planes: done above, plane by plane)
     } else if (c->det_mode == BDOF_DET_NEAR) {
-        if ((r = generic_prop(c, B, pf, pi, c->bufA, c->hdet, 1))) return r;
+        if ((r = generic_prop(c, B, c->bufA, c->hdet, 1))) return r;
     } else if (c->det_mode == BDOF_DET_FAR) {
         RFC(c, rocfft_execute(pi, buf, nullptr, c->fft.info));            // F^H = unnormalised inverse
     }
     const int nz = n_steps(c);
     for (int z = nz - 1; z >= 0; --z) {
-        const bool prop_after = z < nz - 1 || (tf_all && c->det_mode != BDOF_DET_FAR);
-        if (prop_after && (r = generic_prop(c, B, pf, pi, c->bufA, hs_slice(c, z), 1))) return r;      // conj of the forward step's copy
+        if ((z < nz - 1 || step_after_last(c)) && (r = generic_prop(c, B, c->bufA, hs_slice(c, z), 1))) return r;      // conj of the forward step's copy
         ProfScope ps(c, BDOF_K_ROW_BWD, c->stream);
         GBwdArgs ba{c->bufA, c->tape + (size_t)z * fld, c->grot, c->obj, B, c->NX, c->NY, z, c->k, carrier_phi_at(c, z), c->pstack ? 1 : 0,
                     adj_carrier_at(c, whole(c, B), steps(c).steps_back(z))};
@@ -1873,22 +1884,15 @@ int bdof_set_probe_field(bdof_ctx* c, const double* probe, const double* hT, con
     HIPC(c, c->pdetT64.alloc(n));
     const int grid = g_elem_grid(c, n);
     void* buf[1] = {dp};
-    auto step = [&](const double2* h) -> int {
-        if (rocfft_execute(pf, buf, nullptr, c->fft.info) != rocfft_status_success) return fail(c, BDOF_ERR_STATE, "rocfft_execute (double) failed");
-        hipLaunchKernelGGL(k_d_mul, dim3(grid), dim3(256), 0, c->stream, dp, h, n, 1.0 / (double)n);
-        if (rocfft_execute(pi, buf, nullptr, c->fft.info) != rocfft_status_success) return fail(c, BDOF_ERR_STATE, "rocfft_execute (double) failed");
-        return 0;
+    auto step = [&](const double2* h) {      // the caller's tables come without the transforms' 1 / n
+        return free_step(c, c->fft, c->stream, dp, 1, c->NX, c->NY, h, H_KXKY, 0, true, -1, 1.0 / (double)n);
     };
     for (int z = 0; z < nz; ++z) {
         hipLaunchKernelGGL(k_d_to_f, dim3(grid), dim3(256), 0, c->stream, dp, c->pstack + (size_t)z * n, c->NX, c->NY, 0);
-        if (z < nz - 1 && (r = step(dh))) return r;
+        if ((z < nz - 1 || step_after_last(c)) && (r = step(dh))) return r;
     }
-    if (c->det_mode == BDOF_DET_FAR) {
-        if (rocfft_execute(pf, buf, nullptr, c->fft.info) != rocfft_status_success) return fail(c, BDOF_ERR_STATE, "rocfft_execute (double) failed");
-    } else {
-        if (c->variant == BDOF_VARIANT_TF_ALL && (r = step(dh))) return r;
-        if (c->det_mode == BDOF_DET_NEAR && (r = step(dhd))) return r;
-    }
+    if (c->det_mode == BDOF_DET_FAR) RFC(c, rocfft_execute(pf, buf, nullptr, c->fft.info));
+    else if (c->det_mode == BDOF_DET_NEAR && (r = step(dhd))) return r;
     hipLaunchKernelGGL(k_d_to_f, dim3(grid), dim3(256), 0, c->stream, dp, c->pdet, c->NX, c->NY, 0);
     hipLaunchKernelGGL(k_d_to_f, dim3(grid), dim3(256), 0, c->stream, dp, c->pdetT, c->NX, c->NY, 1);
     // ... and unrounded: the detector kernels add the scattered wave to these and take |d| - m in float64 (seed_f64)
@@ -2182,15 +2186,7 @@ int bdof_tiles_grad_add(bdof_ctx* c, const void* grot_range, void* gvol, int B, 
 int bdof_fields_free_step(bdof_ctx* c, void* fields, int B, int NX, int NY, const void* h, int conj_h, int is_double) {
     if (!c || !fields || !h || B < 1 || NX < 1 || NY < 1) return BDOF_ERR_ARG;
     HIPC(c, hipSetDevice(c->device));
-    rocfft_plan pf, pi;
-    int r = field_plans(c, NX, NY, B, is_double != 0, &pf, &pi);
-    if (r) return r;
-    void* buf[1] = {fields};
-    const size_t per = (size_t)NX * NY, n = per * B;
-    RFC(c, rocfft_execute(pf, buf, nullptr, c->fft.info));
-    if (is_double) hipLaunchKernelGGL(k_f_hmul<double2>, dim3(g_elem_grid(c, n)), dim3(256), 0, c->stream, (double2*)fields, (const double2*)h, per, n, conj_h);
-    else hipLaunchKernelGGL(k_f_hmul<float2>, dim3(g_elem_grid(c, n)), dim3(256), 0, c->stream, (float2*)fields, (const float2*)h, per, n, conj_h);
-    RFC(c, rocfft_execute(pi, buf, nullptr, c->fft.info));
+    if (int r = free_step(c, c->fft, c->stream, fields, B, NX, NY, h, H_KXKY, conj_h, is_double != 0)) return r;
     return launched(c);
 }
 
@@ -2214,16 +2210,12 @@ int bdof_fields_free_step_aux(bdof_ctx* c, void* fields, const void* src, int B,
     RFC(c, rocfft_plan_get_work_buffer_size(pf, &w1));
     RFC(c, rocfft_plan_get_work_buffer_size(pi, &w2));
     if ((r = fft_exec_room(c, c->fft_aux, c->aux, std::max(w1, w2)))) return r;
-    const size_t per = (size_t)NX * NY, n = per * B, esz = is_double ? sizeof(double2) : sizeof(float2);
+    const size_t n = (size_t)NX * NY * B, esz = is_double ? sizeof(double2) : sizeof(float2);
     HIPC(c, hipEventRecord(c->ev_aux_fork, c->stream));
     HIPC(c, hipStreamWaitEvent(c->aux, c->ev_aux_fork, 0));
     c->aux_pending = true;
     if (src) HIPC(c, hipMemcpyAsync(fields, src, n * esz, hipMemcpyDeviceToDevice, c->aux));
-    void* buf[1] = {fields};
-    RFC(c, rocfft_execute(pf, buf, nullptr, c->fft_aux.info));
-    if (is_double) hipLaunchKernelGGL(k_f_hmul<double2>, dim3(g_elem_grid(c, n)), dim3(256), 0, c->aux, (double2*)fields, (const double2*)h, per, n, conj_h);
-    else hipLaunchKernelGGL(k_f_hmul<float2>, dim3(g_elem_grid(c, n)), dim3(256), 0, c->aux, (float2*)fields, (const float2*)h, per, n, conj_h);
-    RFC(c, rocfft_execute(pi, buf, nullptr, c->fft_aux.info));
+    if ((r = free_step(c, c->fft_aux, c->aux, fields, B, NX, NY, h, H_KXKY, conj_h, is_double != 0))) return r;
     return launched(c);
 }
 
@@ -2245,10 +2237,10 @@ int bdof_range_carrier_build(bdof_ctx* c, void* p0, void* stack, int B, int NX, 
             HIPC(c, c->car_scratch.alloc(need));
         }
         rocfft_plan pf, pi, qf, qi;
+        // the two plan pairs share c->fft's work area, which only grows: after the second call it has room for both
         int r = field_plans(c, NX, NY, B, true, &pf, &pi);
         if (r) return r;
-        if ((r = field_plans(c, NX, NY, B * (nz - 1), true, &qf, &qi))) return r;       // (sizes the shared work buffer for both)
-        if ((r = field_plans(c, NX, NY, B, true, &pf, &pi))) return r;
+        if ((r = field_plans(c, NX, NY, B * (nz - 1), true, &qf, &qi))) return r;
         void* b0[1] = {p0};
         RFC(c, rocfft_execute(pf, b0, nullptr, c->fft.info));
         hipLaunchKernelGGL(k_carrier_spectra, dim3(g_elem_grid(c, n)), dim3(256), 0, c->stream, (const double2*)p0, (const double2*)h, c->car_scratch,
@@ -2329,6 +2321,57 @@ int bdof_tiles_scatter_diff64(bdof_ctx* c, const void* tiles_a, const void* tile
                         TileArgs<double2, cf>{(double2*)field64, (cf*)tiles_a, (const cf*)tiles_b, x0, y0, B, FX, FY, TX, TY, halo_x, halo_y, 0, accumulate});
 }
 
+// ---- the float64 model: one sweep under bdof_forward_range_f64 and the two twins ------------------------------------------------
+// What the models that run it differ in: the step behind a slice, and what the real-space model does to the exit wave in front
+// of the detector.  Each hook runs forward on the wave or, adj, as its adjoint on the wave's gradient, in place.
+struct Model64 {
+    double k;                                  // 2 pi dz / lambda
+    bool step_last;                            // a step follows the last slice of the range as well
+    std::function<int(bool adj)> step;
+    std::function<int(bool adj)> exit_wave;    // (empty: none)
+};
+// psi [B][NX][NY] complex128 on the ctx's stream (first the probe broadcast into it, if given) through slices z0 .. z0 + nz - 1 of
+// the object seen through o; tape (nullable): [nz][B][NX][NY], receives the modulated waves.  meas == null: that is all.  Else the
+// ctx's detector and data term follow (loss for bdof_get_loss) and the adjoint sweep down the tape: gradient rows in bdof_grot.
+static int sweep_f64(bdof_ctx* c, const Model64& m, const ObjView& o, int B, double2* psi, const double2* probe, int z0, int nz, double2* tape,
+                     const float* meas, double meas_ref) {
+    const int NX = c->NX, NY = c->NY;
+    const size_t per = (size_t)NX * NY, n = per * B;
+    const int eg = g_elem_grid(c, n);
+    int r;
+    rocfft_plan pf = nullptr, pi = nullptr;                                    // the far-field detector's transforms
+    if (meas && (r = field_plans(c, NX, NY, B, true, &pf, &pi))) return r;
+    if (probe) hipLaunchKernelGGL(k_c64_bcast, dim3(eg), dim3(256), 0, c->stream, probe, psi, B, per);
+    for (int z = z0; z < z0 + nz; ++z) {
+        Mod64Args ma{psi, o, B, NX, NY, z, m.k, tape ? tape + (size_t)(z - z0) * n : nullptr};
+        hipLaunchKernelGGL(k_f64_modulate, dim3(eg), dim3(256), 0, c->stream, ma);
+        if ((z < z0 + nz - 1 || m.step_last) && (r = m.step(false))) return r;
+    }
+    if (!meas) return 0;
+    if (m.exit_wave && (r = m.exit_wave(false))) return r;
+    const bool far = c->det_mode == BDOF_DET_FAR, near = c->det_mode == BDOF_DET_NEAR;
+    void* buf[1] = {psi};
+    if (near) { if ((r = free_step(c, c->fft, c->stream, psi, B, NX, NY, c->c64_hdet, H_KXKY, 0, true))) return r; }
+    else if (far) RFC(c, rocfft_execute(pf, buf, nullptr, c->fft.info));       // un-shifted, un-normalised fft2
+    const int lgrid = std::min(eg, c->npartial);
+    with_bool(loss_is_poisson(c), [&](auto PSN) { with_bool((bool)c->wgt, [&](auto WGT) {
+        hipLaunchKernelGGL((k_c64_loss<PSN, WGT>), dim3(lgrid), dim3(256), 0, c->stream, psi, meas, c->partial, B, NX, NY, far ? 1 : 0, meas_ref, 2.0 / (double)n,
+                           c->loss_mu, (const float*)c->wgt);
+    }); });
+    hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, c->stream, c->partial, lgrid, 1.0 / (double)n, c->loss_dev);
+    if (near) { if ((r = free_step(c, c->fft, c->stream, psi, B, NX, NY, c->c64_hdet, H_KXKY, 1, true))) return r; }
+    else if (far) RFC(c, rocfft_execute(pi, buf, nullptr, c->fft.info));       // F^H: the un-normalised inverse
+    if (m.exit_wave && (r = m.exit_wave(true))) return r;
+    for (int z = z0 + nz - 1; z >= z0; --z) {
+        if ((z < z0 + nz - 1 || m.step_last) && (r = m.step(true))) return r;
+        C64BwdArgs ba{psi, tape + (size_t)(z - z0) * n, c->grot, o, B, NX, NY, c->S, z, m.k};
+        hipLaunchKernelGGL(k_c64_bwd, dim3(eg), dim3(256), 0, c->stream, ba);
+    }
+    c->tape_valid = c->last_valid = false;
+    c->gpsi_src = nullptr;
+    return 0;
+}
+
 // bdof_forward_range in float64 on caller-owned complex128 fields [B][NX][NY], in place: slices z0 .. z0+nz-1 of the bound object
 // seen through the windows (xoff, yoff); modulation from the caller's (delta, beta) rows with k in float64, transforms by
 // rocFFT in double precision, h[kx][ky] = the transfer function / (NX NY) in float64.  cnn_propagator/np_funcs.py:36-43.
@@ -2342,20 +2385,8 @@ int bdof_forward_range_f64(bdof_ctx* c, int B, const int* angle_of_b, const int*
     int r;
     if ((r = check_range(c, z0, nz)) || (r = need_angles(c, angle_of_b))) return r;
     HIPC(c, hipSetDevice(c->device));
-    rocfft_plan pf, pi;
-    if ((r = field_plans(c, c->NX, c->NY, B, true, &pf, &pi))) return r;
-    const ObjView o = rows_view(c, angle_of_b, xoff, yoff);
-    const size_t per = (size_t)c->NX * c->NY, n = per * B;
-    void* buf[1] = {fields};
-    for (int z = z0; z < z0 + nz; ++z) {
-        Mod64Args m{(double2*)fields, o, B, c->NX, c->NY, z, k, nullptr};
-        hipLaunchKernelGGL(k_f64_modulate, dim3(g_elem_grid(c, n)), dim3(256), 0, c->stream, m);
-        if (z < z0 + nz - 1 || prop_last) {
-            RFC(c, rocfft_execute(pf, buf, nullptr, c->fft.info));
-            hipLaunchKernelGGL(k_f_hmul<double2>, dim3(g_elem_grid(c, n)), dim3(256), 0, c->stream, (double2*)fields, (const double2*)h, per, n, 0);
-            RFC(c, rocfft_execute(pi, buf, nullptr, c->fft.info));
-        }
-    }
+    const Model64 m{k, prop_last != 0, [&](bool) { return free_step(c, c->fft, c->stream, fields, B, c->NX, c->NY, h, H_KXKY, 0, true); }, nullptr};
+    if ((r = sweep_f64(c, m, rows_view(c, angle_of_b, xoff, yoff), B, (double2*)fields, nullptr, z0, nz, nullptr, nullptr, 0.0))) return r;
     return launched(c);
 }
 
@@ -2440,56 +2471,39 @@ int bdof_loss_grad_conv_f64(bdof_ctx* c, int B, const int* angle_of_b, const int
     if (c->det_mode == BDOF_DET_NEAR && !c->c64_hdet)
         return fail(c, BDOF_ERR_STATE, "near-field detector: bdof_set_conv_f64_detector has not been called");
     HIPC(c, hipSetDevice(c->device));
-    const int N = c->NX, ks = c->c64_ks, p = (ks - 1) / 2, M = N + ks - 1, S = c->S;
-    const size_t per = (size_t)N * N, n = per * B, nbig = (size_t)M * M * B;
+    const int N = c->NX, ks = c->c64_ks, p = (ks - 1) / 2, M = N + ks - 1;
+    const size_t n = (size_t)N * N * B, nbig = (size_t)M * M * B;
     if ((r = c64_room(c, B, false, (size_t)M))) return r;
-    rocfft_plan pf, pi;
-    if ((r = field_plans(c, N, N, B, true, &pf, &pi))) return r;           // detector transforms
-    const ObjView o = rows_view(c, angle_of_b, xoff, yoff);
     const int eg = g_elem_grid(c, n), egb = g_elem_grid(c, nbig);
     double2 *psi = c->c64_psi, *big = c->c64_big;
-    hipLaunchKernelGGL(k_c64_bcast, dim3(eg), dim3(256), 0, c->stream, c->c64_probe, psi, B, per);
     std::complex<double> edge(1.0, 0.0);
-    for (int z = 0; z < S; ++z) {
-        Mod64Args m{psi, o, B, N, N, z, c->c64_k, c->c64_tape + (size_t)z * n};
-        hipLaunchKernelGGL(k_f64_modulate, dim3(eg), dim3(256), 0, c->stream, m);
-        hipLaunchKernelGGL(k_c64_pad, dim3(egb), dim3(256), 0, c->stream, psi, big, B, N, M, p, make_double2(edge.real(), edge.imag()));
-        if ((r = bdof_fields_free_step(c, big, B, M, M, c->c64_khat, 0, 1))) return r;
-        hipLaunchKernelGGL(k_c64_crop, dim3(eg), dim3(256), 0, c->stream, big, psi, B, N, M, ks - 1);
-        edge *= c->c64_ksum;
-    }
-    // q = s P, s = psi_0[0,0,0] / P[0,0,0] (one scalar for the batch)
-    double2 init;
-    HIPC(c, hipMemcpyAsync(&init, c->c64_probe, sizeof(double2), hipMemcpyDeviceToHost, c->stream));
-    HIPC(c, hipStreamSynchronize(c->stream));
-    hipLaunchKernelGGL(k_c64_corner, dim3(1), dim3(1), 0, c->stream, psi, init, c->c64_scal);
-    hipLaunchKernelGGL(k_c64_scale, dim3(eg), dim3(256), 0, c->stream, psi, n, c->c64_scal, 0);
-    HIPC(c, hipMemcpyAsync(c->c64_q, psi, n * sizeof(double2), hipMemcpyDeviceToDevice, c->stream));
-    const bool far = c->det_mode == BDOF_DET_FAR;
-    void* buf[1] = {psi};
-    const bool near = c->det_mode == BDOF_DET_NEAR;
-    if (far) RFC(c, rocfft_execute(pf, buf, nullptr, c->fft.info));           // un-shifted, un-normalised fft2 (propagation.py:114-115)
-    else if (near) { if ((r = bdof_fields_free_step(c, psi, B, N, N, c->c64_hdet, 0, 1))) return r; }      // propagation.py:122-124
-    const int lgrid = std::min(eg, c->npartial);
-    hipLaunchKernelGGL(k_c64_loss<false>, dim3(lgrid), dim3(256), 0, c->stream, psi, meas, c->partial, B, N, N, far ? 1 : 0, meas_ref, 2.0 / (double)n, 0.0, (const float*)nullptr);
-    hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, c->stream, c->partial, lgrid, 1.0 / (double)n, c->loss_dev);
-    if (far) RFC(c, rocfft_execute(pi, buf, nullptr, c->fft.info));           // G(q) = N^2 ifft2(G(d)): the un-normalised inverse
-    else if (near) { if ((r = bdof_fields_free_step(c, psi, B, N, N, c->c64_hdet, 1, 1))) return r; }
-    // adjoint of the renormalisation through the corner pixel
-    const int dgrid = std::min(eg, c->ncu * 16);
-    hipLaunchKernelGGL(k_c64_dot, dim3(dgrid), dim3(256), 0, c->stream, psi, c->c64_q, n, c->c64_part);
-    hipLaunchKernelGGL(k_c64_scale, dim3(eg), dim3(256), 0, c->stream, psi, n, c->c64_scal, 1);
-    hipLaunchKernelGGL(k_c64_corner_adj, dim3(1), dim3(1), 0, c->stream, psi, c->c64_part, dgrid, c->c64_scal);
-    for (int z = S - 1; z >= 0; --z) {
-        // adjoint of (constant pad, valid convolution): embed, circular correlation, crop to the un-padded pixels
-        hipLaunchKernelGGL(k_c64_pad, dim3(egb), dim3(256), 0, c->stream, psi, big, B, N, M, ks - 1, make_double2(0.0, 0.0));
-        if ((r = bdof_fields_free_step(c, big, B, M, M, c->c64_khat, 1, 1))) return r;
-        hipLaunchKernelGGL(k_c64_crop, dim3(eg), dim3(256), 0, c->stream, big, psi, B, N, M, p);
-        C64BwdArgs ba{psi, c->c64_tape + (size_t)z * n, c->grot, o, B, N, N, S, z, c->c64_k};
-        hipLaunchKernelGGL(k_c64_bwd, dim3(eg), dim3(256), 0, c->stream, ba);
-    }
-    c->tape_valid = c->last_valid = false;
-    c->gpsi_src = nullptr;
+    Model64 m{c->c64_k, true};
+    // constant pad, valid convolution on the padded grid, crop; adjoint: embed, circular correlation, crop to the un-padded pixels
+    m.step = [&](bool adj) -> int {
+        hipLaunchKernelGGL(k_c64_pad, dim3(egb), dim3(256), 0, c->stream, psi, big, B, N, M, adj ? ks - 1 : p, adj ? make_double2(0.0, 0.0) : d2(edge));
+        if (int e = free_step(c, c->fft, c->stream, big, B, M, M, c->c64_khat, H_KXKY, adj, true)) return e;
+        hipLaunchKernelGGL(k_c64_crop, dim3(eg), dim3(256), 0, c->stream, big, psi, B, N, M, adj ? p : ks - 1);
+        if (!adj) edge *= c->c64_ksum;
+        return 0;
+    };
+    // q = s P, s = psi_0[0,0,0] / P[0,0,0] (one scalar for the batch), kept in c64_q; adjoint: through the corner pixel
+    m.exit_wave = [&](bool adj) -> int {
+        const int dgrid = std::min(eg, c->ncu * 16);
+        if (adj) {
+            hipLaunchKernelGGL(k_c64_dot, dim3(dgrid), dim3(256), 0, c->stream, psi, c->c64_q, n, c->c64_part);
+            hipLaunchKernelGGL(k_c64_scale, dim3(eg), dim3(256), 0, c->stream, psi, n, c->c64_scal, 1);
+            hipLaunchKernelGGL(k_c64_corner_adj, dim3(1), dim3(1), 0, c->stream, psi, c->c64_part, dgrid, c->c64_scal);
+            return 0;
+        }
+        double2 init;
+        HIPC(c, hipMemcpyAsync(&init, c->c64_probe, sizeof(double2), hipMemcpyDeviceToHost, c->stream));
+        HIPC(c, hipStreamSynchronize(c->stream));
+        hipLaunchKernelGGL(k_c64_corner, dim3(1), dim3(1), 0, c->stream, psi, init, c->c64_scal);
+        hipLaunchKernelGGL(k_c64_scale, dim3(eg), dim3(256), 0, c->stream, psi, n, c->c64_scal, 0);
+        HIPC(c, hipMemcpyAsync(c->c64_q, psi, n * sizeof(double2), hipMemcpyDeviceToDevice, c->stream));
+        return 0;
+    };
+    if ((r = sweep_f64(c, m, rows_view(c, angle_of_b, xoff, yoff), B, psi, c->c64_probe, 0, c->S, c->c64_tape, meas, meas_ref))) return r;
     return launched(c);
 }
 
@@ -2529,43 +2543,11 @@ int bdof_loss_grad_tf_f64(bdof_ctx* c, int B, const int* angle_of_b, const int* 
     int r;
     if ((r = check_batch(c, B)) || (r = need_angles(c, angle_of_b))) return r;
     HIPC(c, hipSetDevice(c->device));
-    const int NX = c->NX, NY = c->NY, S = c->S;
-    const size_t per = (size_t)NX * NY, n = per * B;
     if ((r = c64_room(c, B, true, 0))) return r;
-    rocfft_plan pf, pi;
-    if ((r = field_plans(c, NX, NY, B, true, &pf, &pi))) return r;
-    const ObjView o = rows_view(c, angle_of_b, xoff, yoff);
-    const int eg = g_elem_grid(c, n);
-    const bool far = c->det_mode == BDOF_DET_FAR;
-    // a step after the last slice: variant tf_all, except in front of a far-field detector (|F P phi| = |H F phi| = |F phi|)
-    const bool prop_last = c->variant == BDOF_VARIANT_TF_ALL && !far;
     double2* psi = c->c64_psi;
-    hipLaunchKernelGGL(k_c64_bcast, dim3(eg), dim3(256), 0, c->stream, c->c64_probe, psi, B, per);
-    for (int z = 0; z < S; ++z) {
-        Mod64Args m{psi, o, B, NX, NY, z, c->c64_k, c->c64_tape + (size_t)z * n};
-        hipLaunchKernelGGL(k_f64_modulate, dim3(eg), dim3(256), 0, c->stream, m);
-        if (z < S - 1 || prop_last)
-            if ((r = bdof_fields_free_step(c, psi, B, NX, NY, c->c64_h, 0, 1))) return r;
-    }
-    void* buf[1] = {psi};
-    if (c->det_mode == BDOF_DET_NEAR) { if ((r = bdof_fields_free_step(c, psi, B, NX, NY, c->c64_hdet, 0, 1))) return r; }
-    else if (far) RFC(c, rocfft_execute(pf, buf, nullptr, c->fft.info));       // un-shifted, un-normalised fft2
-    const int lgrid = std::min(eg, c->npartial);
-    with_bool(loss_is_poisson(c), [&](auto PSN) { with_bool((bool)c->wgt, [&](auto WGT) {
-        hipLaunchKernelGGL((k_c64_loss<PSN, WGT>), dim3(lgrid), dim3(256), 0, c->stream, psi, meas, c->partial, B, NX, NY, far ? 1 : 0, meas_ref, 2.0 / (double)n,
-                           c->loss_mu, (const float*)c->wgt);
-    }); });
-    hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, c->stream, c->partial, lgrid, 1.0 / (double)n, c->loss_dev);
-    if (c->det_mode == BDOF_DET_NEAR) { if ((r = bdof_fields_free_step(c, psi, B, NX, NY, c->c64_hdet, 1, 1))) return r; }
-    else if (far) RFC(c, rocfft_execute(pi, buf, nullptr, c->fft.info));       // F^H: the un-normalised inverse
-    for (int z = S - 1; z >= 0; --z) {
-        if (z < S - 1 || prop_last)
-            if ((r = bdof_fields_free_step(c, psi, B, NX, NY, c->c64_h, 1, 1))) return r;
-        C64BwdArgs ba{psi, c->c64_tape + (size_t)z * n, c->grot, o, B, NX, NY, S, z, c->c64_k};
-        hipLaunchKernelGGL(k_c64_bwd, dim3(eg), dim3(256), 0, c->stream, ba);
-    }
-    c->tape_valid = c->last_valid = false;
-    c->gpsi_src = nullptr;
+    const Model64 m{c->c64_k, step_after_last(c),
+                    [&](bool adj) { return free_step(c, c->fft, c->stream, psi, B, c->NX, c->NY, c->c64_h, H_KXKY, adj, true); }, nullptr};
+    if ((r = sweep_f64(c, m, rows_view(c, angle_of_b, xoff, yoff), B, psi, c->c64_probe, 0, c->S, c->c64_tape, meas, meas_ref))) return r;
     return launched(c);
 }
 

@@ -11,20 +11,6 @@
 #pragma once
 #include "bdof_generic.h"
 
-// f[i] *= h[i mod per_field]     (C2 = float2 / double2)
-template <class C2>
-__global__ __launch_bounds__(256) void k_f_hmul(C2* __restrict__ f, const C2* __restrict__ h, size_t per_field, size_t n, int conj_h) {
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        const C2 a = f[i];
-        C2 t = h[i % per_field];
-        if (conj_h) t.y = -t.y;
-        C2 o;
-        o.x = a.x * t.x - a.y * t.y;
-        o.y = a.x * t.y + a.y * t.x;
-        f[i] = o;
-    }
-}
-
 // y += alpha x on n real numbers
 template <class R>
 __global__ __launch_bounds__(256) void k_f_axpy(R* __restrict__ y, const R* __restrict__ x, R alpha, size_t n) {

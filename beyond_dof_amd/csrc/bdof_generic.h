@@ -52,15 +52,26 @@ __global__ __launch_bounds__(256) void k_g_modulate(GModArgs a) {
     }
 }
 
-// field[b][kx][ky] *= h[ky][kx] (the transfer-function table is kept in the fused engine's [ky][kx] order)
-__global__ __launch_bounds__(256) void k_g_hmul(cf* field, const cf* h, int B, int NX, int NY, int conj_h) {
-    const size_t n = (size_t)B * NX * NY;
-    for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < n; idx += (size_t)gridDim.x * blockDim.x) {
-        const int ky = idx % NY;
-        const int kx = (idx / NY) % NX;
-        cf t = h[(size_t)ky * NX + kx];
+// The product of every rocFFT step: f[b][kx][ky] *= h (or its conjugate) on n = B NX NY numbers, C2 = float2 / double2.
+// KYKX: the table is h[ky][kx], the fused engine's order, else h[kx][ky]; SCALED: the product times `scale` (a table that does
+// not carry the transforms' 1 / (NX NY)).
+// The order of the two loads is part of the arithmetic: hipcc contracts a.x t.y + a.y t.x into one product and one fma, and
+// which of the two products it rounds follows the order in which a and t were loaded.  The [ky][kx] instances read the table
+// first and the [kx][ky] ones the field first, as the kernels they replace did: the bits of either engine stay what they were
+// (MEASUREMENTS.md, "rocFFT paths").
+template <class C2, bool KYKX, bool SCALED = false>
+__global__ __launch_bounds__(256) void k_hmul(C2* __restrict__ f, const C2* __restrict__ h, int NX, int NY, size_t n, int conj_h, decltype(C2::x) scale) {
+    const size_t per_field = (size_t)NX * NY;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        C2 a, t;
+        if (KYKX) { t = h[(i % NY) * (size_t)NX + (i / NY) % NX]; a = f[i]; }
+        else { a = f[i]; t = h[i % per_field]; }
         if (conj_h) t.y = -t.y;
-        field[idx] = cmul(field[idx], t);
+        C2 o;
+        o.x = a.x * t.x - a.y * t.y;
+        o.y = a.x * t.y + a.y * t.x;
+        if (SCALED) { o.x *= scale; o.y *= scale; }
+        f[i] = o;
     }
 }
 
@@ -212,30 +223,12 @@ __global__ __launch_bounds__(256) void k_g_bwd64(GBwd64Args a) {
         a.g[idx] = make_double2(G.x * cx + G.y * cy, G.y * cx - G.x * cy);           // G conj(c)
     }
 }
-// field[b][kx][ky] *= h[ky][kx] (or its conjugate), float64
-__global__ __launch_bounds__(256) void k_g_hmul64(double2* field, const double2* h, int B, int NX, int NY, int conj_h) {
-    const size_t n = (size_t)B * NX * NY;
-    for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < n; idx += (size_t)gridDim.x * blockDim.x) {
-        const int ky = idx % NY;
-        const int kx = (idx / NY) % NX;
-        double2 t = h[(size_t)ky * NX + kx];
-        if (conj_h) t.y = -t.y;
-        const double2 v = field[idx];
-        field[idx] = make_double2(v.x * t.x - v.y * t.y, v.x * t.y + v.y * t.x);
-    }
-}
 __global__ __launch_bounds__(256) void k_d_scale(double2* f, size_t n, double s) {
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
         f[i] = make_double2(f[i].x * s, f[i].y * s);
 }
 
 // ---- float64 helpers of bdof_set_probe_field: the carrier field of a localised probe, propagated on the device ------------
-__global__ __launch_bounds__(256) void k_d_mul(double2* __restrict__ f, const double2* __restrict__ h, size_t n, double scale) {
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        const double2 a = f[i], b = h[i];
-        f[i] = make_double2((a.x * b.x - a.y * b.y) * scale, (a.x * b.y + a.y * b.x) * scale);
-    }
-}
 __global__ __launch_bounds__(256) void k_d_copy(const double2* __restrict__ src, double2* __restrict__ dst, int n0, int n1, int transposed) {
     const size_t n = (size_t)n0 * n1;
     for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < n; idx += (size_t)gridDim.x * blockDim.x)
