@@ -294,6 +294,106 @@ static void drop_planes(bdof_ctx* c) {
     c->hdet_pl.reset(); c->hcomb_pl.reset(); c->det_pl.reset(); c->seed_pl.reset();
     c->hdet00_pl.clear();
 }
+
+// ---- what a change voids ---------------------------------------------------------------------------------------------------
+// State the ctx derives from what it is handed, by the flag that says whether it still holds ...
+enum { V_TWIN64 = 1,        // c64_tf, c64_ks: the float64 twin handed over (bdof_set_tf_f64 / bdof_set_conv_f64) held the previous model
+       V_RESIDENT = 2,      // res_dirty: the resident engine's carrier constants (resident_run uploads them again)
+       V_MODULATION = 4,    // mod_dirty, mod_mean_pending: the table c - 1 in c->mod and its mean (ensure_modulation rebuilds them)
+       V_MOD_RECORD = 8,    // mod_for: the table bdof_rotation_adjoint_adam left for another volume
+       V_HISTORY = 16,      // tape_valid: the per-slice history of bdof_forward(keep_tape)
+       V_LAST_WAVE = 32,    // last_valid: ... and its last slice's wave in bufA
+       V_COPIES = 64,       // hs_copies, sep_copies: dithered copies of the slice step and of its separable factors (bdof_set_transfer_f64 follows)
+       V_H64 = 128,         // have_h64: the float64 adjoint's tables (bdof_set_physics_f64 follows)
+       V_PLANES = 256,      // planes: detector planes belong to the physics that go (drop_planes; bdof_set_detector_planes follows)
+       V_GPSI = 512 };      // gpsi_src: where the last bdof_loss_grad left G(psi_0)
+// ... and the one statement of which cause voids what (DESIGN §4 has the same table).  No setter or entry point assigns these
+// flags itself.  It records what the code did when it was written down, uneven places included (MEASUREMENTS.md lists them).
+enum Cause { CHANGED_CONFIGURATION, CHANGED_BINNING, CHANGED_PHYSICS, CHANGED_SLICE_STEP_F64, CHANGED_PROBE, CHANGED_CARRIER_FIELD,
+             CHANGED_CARRIER_FIELD_F64, CHANGED_CONV_TAPS, CHANGED_CONV_CARRIER_FIELD, CHANGED_OBJECT, CHANGED_DETECTOR_PLANES,
+             CHANGED_MODULATION_K, CHANGED_MOD_OVERWRITTEN, CHANGED_MEAN_MODULATION, TAPE_OVERWRITTEN, PROBE_GRADIENT_GONE };
+static const struct { Cause cause; int voids; } VOIDS[] = {
+    {CHANGED_CONFIGURATION, V_RESIDENT | V_HISTORY},             // bdof_configure (beside the fresh Workspace, which resets what it holds)
+    {CHANGED_BINNING, V_MODULATION | V_RESIDENT | V_HISTORY | V_LAST_WAVE},                     // bdof_set_slice_binning
+    {CHANGED_PHYSICS, V_TWIN64 | V_PLANES | V_RESIDENT | V_H64 | V_COPIES | V_MODULATION},      // bdof_set_physics
+    {CHANGED_SLICE_STEP_F64, V_COPIES | V_RESIDENT},             // bdof_set_transfer_f64: the previous table's copies go before the new ones come
+    {CHANGED_PROBE, V_TWIN64 | V_RESIDENT | V_MODULATION},       // bdof_set_probe: whether the mean modulation rides on the carrier depends on a0 (want_cbar)
+    {CHANGED_CARRIER_FIELD, V_MODULATION},                       // bdof_set_probe_stack, set or cleared
+    {CHANGED_CARRIER_FIELD_F64, V_RESIDENT | V_MODULATION},      // bdof_set_probe_field: a carrier field that also zeroes the probe and a0
+    {CHANGED_CONV_TAPS, V_TWIN64 | V_MODULATION},                // bdof_set_conv
+    {CHANGED_CONV_CARRIER_FIELD, 0},                             // bdof_set_conv_probe_stack: the sweeps read the stack itself, nothing derived is kept
+    {CHANGED_OBJECT, V_MODULATION | V_MOD_RECORD},               // bdof_set_object, bdof_set_object_bilinear — see changed()
+    {CHANGED_DETECTOR_PLANES, V_PLANES | V_HISTORY | V_LAST_WAVE},      // bdof_set_detector_planes with D > 1 tables
+    {CHANGED_MODULATION_K, V_MODULATION},                        // the table was built with another k, or with the mean riding differently
+    {CHANGED_MOD_OVERWRITTEN, V_MODULATION | V_MOD_RECORD},      // c->mod or cbar_dev is being written for something else than the bound object
+    {CHANGED_MEAN_MODULATION, V_RESIDENT},                       // cbar came out different: the carrier scalars move
+    {TAPE_OVERWRITTEN, V_HISTORY | V_LAST_WAVE},                 // a sweep has overwritten the tape
+    {PROBE_GRADIENT_GONE, V_GPSI},                               // a sweep that leaves no G(psi_0), or its buffer went
+};
+static void changed(bdof_ctx* c, Cause cause) {
+    int v = 0;
+    for (const auto& row : VOIDS) if (row.cause == cause) v = row.voids;
+    // a new binding of the volume bdof_rotation_adjoint_adam has just left the table of: nothing to rebuild, its mean to fetch
+    const bool taken_over = cause == CHANGED_OBJECT && c->mod_for && c->obj_src == c->mod_for && c->obj_rows == c->mod_for_rows && c->obj.volNY == c->mod_for_NY;
+    if (v & V_TWIN64) { c->c64_tf = false; c->c64_ks = 0; }
+    if (v & V_RESIDENT) c->res_dirty = true;
+    if (v & V_MODULATION) { c->mod_dirty = !taken_over; c->mod_mean_pending = taken_over; }
+    if (v & V_MOD_RECORD) c->mod_for = nullptr;
+    if (v & V_HISTORY) c->tape_valid = false;
+    if (v & V_LAST_WAVE) c->last_valid = false;
+    if (v & V_COPIES) c->hs_copies = c->sep_copies = 0;
+    if (v & V_H64) c->have_h64 = false;
+    if (v & V_PLANES) drop_planes(c);
+    if (v & V_GPSI) c->gpsi_src = nullptr;
+}
+// what makes it good again: the tape after bdof_forward(keep_tape), the table in c->mod, the resident engine's constants, a twin handed over
+static void tape_holds(bdof_ctx* c, bool history, bool last) { c->tape_valid = history; c->last_valid = last; }
+static void modulation_current(bdof_ctx* c) { c->mod_dirty = false; c->mod_mean_pending = false; }
+static void resident_current(bdof_ctx* c) { c->res_dirty = false; }
+static void twin64_holds(bdof_ctx* c, bool tf, int ks) { c->c64_tf = tf; c->c64_ks = ks; }
+
+// ---- the setters' opening and their uploads ----------------------------------------------------------------------------------
+// Every setter opens in one order: a ctx, a configuration, the ctx's device (a process may hold ctxs on several), and — drain —
+// the ctx stream drained, because launches in flight may still read what the setter is about to free or overwrite.
+static int enter_setter(bdof_ctx* c, bool drain) {
+    if (!c) return BDOF_ERR_ARG;
+    if (int r = need_configured(c)) return r;
+    HIPC(c, hipSetDevice(c->device));
+    if (drain) HIPC(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+// n elements of a host table into buf, which is allocated FRESH (what it held goes first: DevBuf::alloc), only GROWn, or KEPT
+// where it holds something already.  A blocking copy: the host table may go when this returns.
+enum Room { FRESH, GROW, KEEP };
+template <class T> static int upload(bdof_ctx* c, DevBuf<T>& buf, const void* host, size_t n, Room room) {
+    if (room == FRESH || (room == KEEP && !buf)) HIPC(c, buf.alloc(n));
+    else if (room == GROW) HIPC(c, buf.room(n));
+    HIPC(c, hipMemcpy(buf, host, n * sizeof(T), hipMemcpyHostToDevice));
+    return 0;
+}
+// an interleaved complex table [rows][cols] as [cols][rows]
+template <class T> static std::vector<T> transposed(const T* t, int rows, int cols) {
+    std::vector<T> out((size_t)2 * rows * cols);
+    for (int i = 0; i < rows; ++i)
+        for (int j = 0; j < cols; ++j) {
+            out[2 * ((size_t)j * rows + i)] = t[2 * ((size_t)i * cols + j)];
+            out[2 * ((size_t)j * rows + i) + 1] = t[2 * ((size_t)i * cols + j) + 1];
+        }
+    return out;
+}
+// tf_all + near detector: the two consecutive steps F^-1 hdet_j F F^-1 hs F collapse into one with the table hs hdet_j n, formed
+// in double and rounded once; D tables [D][n] of the detector steps, n = NX NY (the transforms' 1 / n sits in both factors)
+static std::vector<float> combined(const float* hs, const float* hs_det, size_t n, int D) {
+    std::vector<float> comb(2 * n * D);
+    const double nn = (double)n;
+    for (int j = 0; j < D; ++j)
+        for (size_t i = 0; i < n; ++i) {
+            const double ar = hs[2 * i], ai = hs[2 * i + 1], br = hs_det[2 * (j * n + i)], bi = hs_det[2 * (j * n + i) + 1];
+            comb[2 * (j * n + i)] = (float)((ar * br - ai * bi) * nn);
+            comb[2 * (j * n + i) + 1] = (float)((ar * bi + ai * br) * nn);
+        }
+    return comb;
+}
 // propagation steps of a sweep: the voxel depth over the slice binning
 static StepIndex steps(const bdof_ctx* c) { return StepIndex{c->S, c->bin}; }
 static int n_steps(const bdof_ctx* c) { return steps(c).n(); }
@@ -444,6 +544,8 @@ static int balanced_grid(const bdof_ctx* c, int tiles, int per_cu) {
     const int rounds = (tiles + cap - 1) / cap;
     return (tiles + rounds - 1) / rounds;
 }
+// element-wise kernels: 256 elements per workgroup, at most 16 workgroups per CU (they stride over the rest)
+static int g_elem_grid(const bdof_ctx* c, size_t n) { return (int)std::min<size_t>((n + 255) / 256, (size_t)c->ncu * 16); }
 template <int N> static int rows_grid(const bdof_ctx* c, int B, int R) {
     return balanced_grid(c, B * R / RowCfg<N>::TILE, N >= 1024 ? 1 : 2);
 }
@@ -943,37 +1045,35 @@ static int modulation_bound(bdof_ctx* c, size_t at, bool mean) {
         // slice binning: a step's carrier picks up the mean factor of its whole bin, cbar^bin (exact algebra for any cbar)
         if (c->bin > 1) cb = std::pow(1.0 + cb, c->bin) - 1.0;
     }
-    if (cb != c->cbm1) { c->cbm1 = cb; c->res_dirty = true; }
+    if (cb != c->cbm1) { c->cbm1 = cb; changed(c, CHANGED_MEAN_MODULATION); }
     c->obj.vol = c->mod;
-    c->mod_dirty = false;
-    c->mod_mean_pending = false;
+    modulation_current(c);
     return 0;
 }
 static int modulation_done(bdof_ctx* c, size_t n, int grid, bool mean) {
     HIPC(c, hipGetLastError());
-    c->mod_for = nullptr;
+    changed(c, CHANGED_MOD_OVERWRITTEN);
     if (mean) hipLaunchKernelGGL(k_sum_mean, dim3(1), dim3(256), 0, c->stream, c->cbar_dev, grid, 1.0 / (double)n, c->cbar_dev + grid);
     return modulation_bound(c, grid, mean);
 }
 
 static int ensure_modulation(bdof_ctx* c) {
     // (a table taken over from bdof_rotation_adjoint_adam stands only while the mean rides on the carrier as it did then)
-    if (!c->mod_dirty && c->mod_mean_pending && c->mod_for_mean != want_cbar(c)) c->mod_dirty = true;
+    if (!c->mod_dirty && c->mod_mean_pending && c->mod_for_mean != want_cbar(c)) changed(c, CHANGED_MODULATION_K);
     if (!c->mod_dirty) return c->mod_mean_pending ? modulation_bound(c, c->mod_for_mean_at, c->mod_for_mean) : 0;
     if (!c->obj_src) return fail(c, BDOF_ERR_STATE, "the object was bound as modulation factors (bdof_set_object_bilinear): bind it again for this propagator");
     const size_t n = c->obj_rows * (size_t)c->obj.volNY;
     const bool mean = want_cbar(c);
     int r = modulation_room(c, n, mean);
     if (r) return r;
-    size_t need = (n + 255) / 256;
-    int grid = need < (size_t)c->ncu * 16 ? (int)need : c->ncu * 16;
+    const int grid = g_elem_grid(c, n);
     hipLaunchKernelGGL(k_modulation_table, dim3(grid), dim3(256), 0, c->stream, c->obj_src, c->mod, n, c->k, mean ? c->cbar_dev : nullptr);
     return modulation_done(c, n, grid, mean);
 }
 
 static int ensure_modulation_k(bdof_ctx* c, float k) {
     // the conv propagator's k uses numpy's pi, the FFT path's the reference's literal (quirk Q1): one table per k
-    if (c->k != k) { c->k = k; c->mod_dirty = true; }
+    if (c->k != k) { c->k = k; changed(c, CHANGED_MODULATION_K); }
     return ensure_modulation(c);
 }
 
@@ -1032,8 +1132,6 @@ static int field_plans(bdof_ctx* c, int NX, int NY, int B, bool dbl, rocfft_plan
 static const cf* hs_slice(const bdof_ctx* c, int z) {
     return c->hs_copies > 0 ? c->hs_d + (size_t)((unsigned)z % (unsigned)c->hs_copies) * c->NX * c->NY : c->hs;
 }
-
-static int g_elem_grid(const bdof_ctx* c, size_t n) { return (int)std::min<size_t>((n + 255) / 256, (size_t)c->ncu * 16); }
 
 // The one free-space step of the rocFFT paths, in place on B fields [NX][NY] of either precision: fields <- F^-1' ( h * F fields ),
 // queued on stream st, whose execution info x is (c->fft and c->stream, or the auxiliary pair once bdof_fields_free_step_aux has
@@ -1271,8 +1369,8 @@ static int resident_run(bdof_ctx* c, int B, const float* meas, void* out_wave, b
         std::vector<cf> car(2 * (size_t)c->S);
         for (int z = 0; z < c->S; ++z) { car[z] = carrier_at(c, z); car[c->S + z] = cshift_at(c, z); }
         HIPC(c, hipStreamSynchronize(c->stream));
-        HIPC(c, hipMemcpy(c->res_carrier, car.data(), sizeof(cf) * car.size(), hipMemcpyHostToDevice));
-        c->res_dirty = false;
+        if (int r = upload(c, c->res_carrier, car.data(), car.size(), KEEP)) return r;
+        resident_current(c);
     }
     ProfScope ps(c, BDOF_K_ROW_FWD, c->stream);
     const bool grad = do_grad && meas;
@@ -1503,8 +1601,8 @@ int bdof_configure(bdof_ctx* c, int NY, int NX, int S, int Bmax, int with_grad) 
     c->adj64 = (with_grad & BDOF_CFG_ADJOINT64) != 0 && c->with_grad;
     c->resident = (with_grad & (BDOF_CFG_GENERIC | BDOF_CFG_NO_RESIDENT | BDOF_CFG_ADJOINT64)) == 0 && NX == NY && resident_supported(NX);
     c->res_always = (with_grad & BDOF_CFG_ALWAYS_RESIDENT) != 0;
-    c->res_dirty = true;
-    c->have_physics = c->have_probe = c->tape_valid = false;
+    changed(c, CHANGED_CONFIGURATION);
+    c->have_physics = c->have_probe = false;
     int r;
     if (c->resident) {
         if ((r = upload_twiddle(c, NX, c->twR, false))) return r;       // one launch runs all slices: one table
@@ -1548,74 +1646,47 @@ int bdof_configure(bdof_ctx* c, int NY, int NX, int S, int Bmax, int with_grad) 
 }
 
 int bdof_set_slice_binning(bdof_ctx* c, int bin) {
-    if (!c) return BDOF_ERR_ARG;
-    if (int r = need_configured(c)) return r;
+    if (int r = enter_setter(c, true)) return r;
     if (!StepIndex::valid(c->S, bin)) return fail(c, BDOF_ERR_ARG, "bdof_set_slice_binning: bin must be >= 1 and divide S (a shorter last bin is not carried)");
     if (c->have_physics || c->have_probe)
         return fail(c, BDOF_ERR_STATE, "bdof_set_slice_binning comes right after bdof_configure: the tables of bdof_set_physics and the carrier fields are per propagation step");
     if (bin > 1)
         if (int r = refuse_modes(c, "bdof_set_slice_binning", "slice binning", {&MODE_RESIDENT, &MODE_RECOMPUTE, &MODE_ADJOINT64, &MODE_NO_GROT})) return r;
-    HIPC(c, hipSetDevice(c->device));
-    HIPC(c, hipStreamSynchronize(c->stream));
     if (c->with_grad && bin != c->bin) HIPC(c, c->tape.alloc((size_t)c->Bmax * c->NX * c->NY * StepIndex{c->S, bin}.tape_fields()));     // one field per step
     c->bin = c->obj.bin = bin;
-    c->mod_dirty = c->res_dirty = true;
-    c->tape_valid = c->last_valid = false;
+    changed(c, CHANGED_BINNING);
     return 0;
 }
 
 int bdof_set_physics(bdof_ctx* c, double k, const float* hs, const float* hs_det, const double* h00, const double* hdet00,
                      int det_mode, int variant) {
     if (!c || !hs || !h00) return BDOF_ERR_ARG;
-    if (int r = need_configured(c)) return r;
+    if (int r = enter_setter(c, false)) return r;
     if (det_mode < 0 || det_mode > 2 || variant < 0 || variant > 1) return fail(c, BDOF_ERR_ARG, "bad det_mode / variant");
     if (det_mode == BDOF_DET_NEAR && !hs_det) return fail(c, BDOF_ERR_ARG, "hs_det required for BDOF_DET_NEAR");
-    const size_t bytes = sizeof(cf) * c->NX * c->NY;
-    c->c64_tf = false; c->c64_ks = 0;     // a float64 twin handed over before (bdof_set_tf_f64 / bdof_set_conv_f64) held the previous model
-    if (c->planes > 1) {                  // detector planes belong to the physics that go: bdof_set_detector_planes follows, or there is one plane
-        HIPC(c, hipStreamSynchronize(c->stream));
-        drop_planes(c);
-    }
+    const size_t n = (size_t)c->NX * c->NY, bytes = sizeof(cf) * n;
+    if (c->planes > 1) HIPC(c, hipStreamSynchronize(c->stream));      // launches in flight may still read the planes that go
+    changed(c, CHANGED_PHYSICS);
     HIPC(c, hipMemcpyAsync(c->hs, hs, bytes, hipMemcpyHostToDevice, c->stream));
     if (hs_det) {
         HIPC(c, hipMemcpyAsync(c->hdet, hs_det, bytes, hipMemcpyHostToDevice, c->stream));
-        // tf_all + near detector: the two consecutive steps F^-1 hdet F F^-1 hs F collapse into one
-        std::vector<float> comb((size_t)2 * c->NX * c->NY);
-        const double n = (double)c->NX * c->NY;
-        for (size_t i = 0; i < (size_t)c->NX * c->NY; ++i) {
-            const double ar = hs[2 * i], ai = hs[2 * i + 1], br = hs_det[2 * i], bi = hs_det[2 * i + 1];
-            comb[2 * i] = (float)((ar * br - ai * bi) * n);
-            comb[2 * i + 1] = (float)((ar * bi + ai * br) * n);
-        }
+        const std::vector<float> comb = combined(hs, hs_det, n, 1);
         HIPC(c, hipMemcpyAsync(c->hcomb, comb.data(), bytes, hipMemcpyHostToDevice, c->stream));
         HIPC(c, hipStreamSynchronize(c->stream));
     }
     if (c->resident) {
         // the resident kernel multiplies the field image [kx][ky] element by element: tables in that order
-        const int N = c->NX;
-        std::vector<float> t((size_t)2 * N * N);
-        for (int pass = 0; pass < (hs_det ? 2 : 1); ++pass) {
-            const float* src = pass ? hs_det : hs;
-            for (int ky = 0; ky < N; ++ky)
-                for (int kx = 0; kx < N; ++kx) {
-                    t[2 * ((size_t)kx * N + ky)] = src[2 * ((size_t)ky * N + kx)];
-                    t[2 * ((size_t)kx * N + ky) + 1] = src[2 * ((size_t)ky * N + kx) + 1];
-                }
-            HIPC(c, hipMemcpy(pass ? c->hdetT : c->hsT, t.data(), bytes, hipMemcpyHostToDevice));
-        }
+        if (int r = upload(c, c->hsT, transposed(hs, c->NY, c->NX).data(), n, KEEP)) return r;
+        if (hs_det)
+            if (int r = upload(c, c->hdetT, transposed(hs_det, c->NY, c->NX).data(), n, KEEP)) return r;
     }
     HIPC(c, hipStreamSynchronize(c->stream));
-    c->res_dirty = true;
     c->k = c->k_fft = (float)k;
     c->h00 = std::complex<double>(h00[0], h00[1]);
     c->hdet00 = hdet00 ? std::complex<double>(hdet00[0], hdet00[1]) : std::complex<double>(1.0, 0.0);
     c->det_mode = det_mode;
     c->variant = variant;
     c->have_physics = true;
-    c->have_h64 = false;             // float64 adjoint: the caller follows up with bdof_set_physics_f64
-    c->hs_copies = 0;                // dithered copies of the old table: the caller follows up with bdof_set_transfer_f64
-    c->sep_copies = 0;               // ... and so do its separable factors
-    c->mod_dirty = true;
     return 0;
 }
 
@@ -1653,14 +1724,24 @@ static int build_separable(bdof_ctx* c, const double* hs64, int D) {
     copies(NY, [&](int ky) { return H(ky, 0) * (double)NX; }, hy);
     const cf* hx_top = hx.data() + (size_t)((c->S - 2) % D) * NX;
     for (int ky = 0; ky < NY; ++ky) std::copy(hx_top, hx_top + NX, rows.begin() + (size_t)ky * NX);
-    HIPC(c, c->hx_d.alloc(hx.size()));
-    HIPC(c, c->hy_d.alloc(hy.size()));
-    HIPC(c, c->hx_rows.alloc(rows.size()));
-    HIPC(c, hipMemcpy(c->hx_d, hx.data(), sizeof(cf) * hx.size(), hipMemcpyHostToDevice));
-    HIPC(c, hipMemcpy(c->hy_d, hy.data(), sizeof(cf) * hy.size(), hipMemcpyHostToDevice));
-    HIPC(c, hipMemcpy(c->hx_rows, rows.data(), sizeof(cf) * rows.size(), hipMemcpyHostToDevice));
+    int r;
+    if ((r = upload(c, c->hx_d, hx.data(), hx.size(), FRESH)) || (r = upload(c, c->hy_d, hy.data(), hy.size(), FRESH)) ||
+        (r = upload(c, c->hx_rows, rows.data(), rows.size(), FRESH))) return r;
     c->sep_copies = D;
     return 0;
+}
+
+// D dithered float32 copies of a float64 table of n complex entries into dst (k_dither_copies, bdof_field.h), through the device
+// scratch tmp of n entries; drains the ctx stream, so the host table and tmp may go when this returns
+static int dither_copies(bdof_ctx* c, DevBuf<cf>& dst, const double* host64, size_t n, int D, DevBuf<double2>& tmp) {
+    hipError_t e = dst.alloc((size_t)D * n);
+    if (e != hipSuccess) return fail(c, (int)e, "hipMalloc of the dithered transfer-function copies failed");
+    e = hipMemcpy(tmp, host64, n * sizeof(double2), hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(k_dither_copies, dim3(g_elem_grid(c, n)), dim3(256), 0, c->stream, tmp, dst, n, D);
+        e = hipStreamSynchronize(c->stream);
+    }
+    return e == hipSuccess ? 0 : fail(c, (int)e, "building the dithered transfer-function copies failed");
 }
 
 // The slice step's transfer function in float64 ([ky][kx], 1 / (NX NY) folded in — what bdof_set_physics' hs was rounded from):
@@ -1675,39 +1756,17 @@ int bdof_set_transfer_f64(bdof_ctx* c, const double* hs64) {
     const size_t n = (size_t)c->NX * c->NY;
     int D = env ? std::max(0, std::min(256, atoi(env))) : 64;
     while (D > 1 && (size_t)D * n * sizeof(cf) > ((size_t)256 << 20)) D /= 2;
-    c->sep_copies = 0;
-    if (D < 2) { c->hs_copies = 0; return 0; }
-    HIPC(c, hipSetDevice(c->device));
-    HIPC(c, hipStreamSynchronize(c->stream));
+    changed(c, CHANGED_SLICE_STEP_F64);
+    if (D < 2) return 0;
+    if (int r = enter_setter(c, true)) return r;
     c->hs_d.reset();
     c->hsT_d.reset();
-    c->hs_copies = 0;
     DevBuf<double2> tmp;
     HIPC(c, tmp.alloc(n));
-    hipError_t e = c->hs_d.alloc((size_t)D * n);
-    if (e != hipSuccess) return fail(c, (int)e, "hipMalloc of the dithered transfer-function copies failed");
-    e = hipMemcpy(tmp, hs64, n * sizeof(double2), hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_dither_copies, dim3(g_elem_grid(c, n)), dim3(256), 0, c->stream, tmp, c->hs_d, n, D);
-        e = hipStreamSynchronize(c->stream);
-    }
-    if (e == hipSuccess && c->resident) {
-        // the LDS-resident kernel multiplies its field image [kx][ky] element by element: the same copies, transposed
-        std::vector<double> t(2 * n);
-        for (int ky = 0; ky < c->NY; ++ky)
-            for (int kx = 0; kx < c->NX; ++kx) {
-                t[2 * ((size_t)kx * c->NY + ky)] = hs64[2 * ((size_t)ky * c->NX + kx)];
-                t[2 * ((size_t)kx * c->NY + ky) + 1] = hs64[2 * ((size_t)ky * c->NX + kx) + 1];
-            }
-        e = c->hsT_d.alloc((size_t)D * n);
-        if (e == hipSuccess) e = hipMemcpy(tmp, t.data(), n * sizeof(double2), hipMemcpyHostToDevice);
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(k_dither_copies, dim3(g_elem_grid(c, n)), dim3(256), 0, c->stream, tmp, c->hsT_d, n, D);
-            e = hipStreamSynchronize(c->stream);
-        }
-        c->res_dirty = true;
-    }
-    if (e != hipSuccess) return fail(c, (int)e, "building the dithered transfer-function copies failed");
+    if (int r = dither_copies(c, c->hs_d, hs64, n, D, tmp)) return r;
+    // the LDS-resident kernel multiplies its field image [kx][ky] element by element: the same copies, transposed
+    if (c->resident)
+        if (int r = dither_copies(c, c->hsT_d, transposed(hs64, c->NY, c->NX).data(), n, D, tmp)) return r;
     c->hs_copies = D;
     return build_separable(c, hs64, D);
 }
@@ -1717,24 +1776,21 @@ int bdof_set_physics_f64(bdof_ctx* c, const double* hs, const double* hs_det) {
     if (!c->adj64) return fail(c, BDOF_ERR_STATE, "bdof_set_physics_f64 needs bdof_configure with flag 64 (float64 adjoint sweep)");
     if (!c->have_physics) return fail(c, BDOF_ERR_STATE, "bdof_set_physics has not been called");
     if (c->det_mode == BDOF_DET_NEAR && !hs_det) return fail(c, BDOF_ERR_ARG, "hs_det required for BDOF_DET_NEAR");
-    HIPC(c, hipSetDevice(c->device));
-    HIPC(c, hipStreamSynchronize(c->stream));
-    const size_t bytes = sizeof(double2) * (size_t)c->NX * c->NY;
-    HIPC(c, hipMemcpy(c->hs64, hs, bytes, hipMemcpyHostToDevice));
-    if (hs_det) HIPC(c, hipMemcpy(c->hdet64, hs_det, bytes, hipMemcpyHostToDevice));
+    int r = enter_setter(c, true);
+    if (r) return r;
+    const size_t n = (size_t)c->NX * c->NY;
+    if ((r = upload(c, c->hs64, hs, n, KEEP)) || (hs_det && (r = upload(c, c->hdet64, hs_det, n, KEEP)))) return r;
     c->have_h64 = true;
     return 0;
 }
 
 int bdof_set_probe(bdof_ctx* c, const float* probe, double a0_re, double a0_im) {
     if (!c || !probe) return BDOF_ERR_ARG;
-    if (int r = need_configured(c)) return r;
+    if (int r = enter_setter(c, false)) return r;
+    changed(c, CHANGED_PROBE);
     HIPC(c, hipMemcpyAsync(c->probe, probe, sizeof(cf) * c->NX * c->NY, hipMemcpyHostToDevice, c->stream));
-    c->c64_tf = false; c->c64_ks = 0;     // a float64 twin handed over before (bdof_set_tf_f64 / bdof_set_conv_f64) held the previous model
     HIPC(c, hipStreamSynchronize(c->stream));
     c->a0 = std::complex<double>(a0_re, a0_im);
-    c->res_dirty = true;
-    c->mod_dirty = true;            // whether the mean modulation rides on the carrier depends on a0 (want_cbar)
     c->have_probe = true;
     return 0;
 }
@@ -1756,52 +1812,32 @@ int bdof_set_loss(bdof_ctx* c, int kind, double multiplier) {
 }
 
 int bdof_set_detector_weights(bdof_ctx* c, const float* w) {
-    if (!c) return BDOF_ERR_ARG;
-    if (int r = need_configured(c)) return r;
-    HIPC(c, hipSetDevice(c->device));
-    // launches in flight may still read the plane that goes
-    HIPC(c, hipStreamSynchronize(c->stream));
+    if (int r = enter_setter(c, true)) return r;       // launches in flight may still read the plane that goes
     if (!w) { c->wgt.reset(); return 0; }
-    const size_t n = (size_t)c->NX * c->NY;
-    HIPC(c, c->wgt.room(n));
-    HIPC(c, hipMemcpy(c->wgt, w, n * sizeof(float), hipMemcpyHostToDevice));
-    return 0;
+    return upload(c, c->wgt, w, (size_t)c->NX * c->NY, GROW);
 }
 
 int bdof_set_detector_planes(bdof_ctx* c, int D, const float* hs_det, const double* hdet00) {
-    if (!c) return BDOF_ERR_ARG;
-    if (int r = need_configured(c)) return r;
+    if (int r = enter_setter(c, true)) return r;      // launches in flight may still read the tables and fields that go
     if (D < 1 || D > BDOF_MAX_PLANES) return fail(c, BDOF_ERR_ARG, "bdof_set_detector_planes: the number of detector planes must be in [1, BDOF_MAX_PLANES]");
-    HIPC(c, hipSetDevice(c->device));
-    HIPC(c, hipStreamSynchronize(c->stream));         // launches in flight may still read the tables and fields that go
     if (D == 1 || !hs_det) { drop_planes(c); return 0; }
     if (!hdet00) return fail(c, BDOF_ERR_ARG, "bdof_set_detector_planes: hdet00 required with the tables");
     if (!c->have_physics) return fail(c, BDOF_ERR_STATE, "bdof_set_detector_planes comes after bdof_set_physics");
     if (int r = refuse_modes(c, "bdof_set_detector_planes", "detector planes",
                              {&MODE_NOT_NEAR, &MODE_RECOMPUTE, &MODE_ADJOINT64, &MODE_CONV, &MODE_CARRIER_FIELD, &MODE_RANGE_CARRIER})) return r;
-    drop_planes(c);
+    changed(c, CHANGED_DETECTOR_PLANES);
     const size_t n = (size_t)c->NX * c->NY, fields = (size_t)c->Bmax * D * n;
     // the combined tables of tf_all, formed as bdof_set_physics forms its one: from the float32 slice step the ctx holds
-    std::vector<float> hs(2 * n), comb(2 * n * D);
+    std::vector<float> hs(2 * n);
     HIPC(c, hipMemcpy(hs.data(), c->hs, sizeof(cf) * n, hipMemcpyDeviceToHost));
-    const double nn = (double)c->NX * c->NY;
-    for (int j = 0; j < D; ++j)
-        for (size_t i = 0; i < n; ++i) {
-            const double ar = hs[2 * i], ai = hs[2 * i + 1], br = hs_det[2 * (j * n + i)], bi = hs_det[2 * (j * n + i) + 1];
-            comb[2 * (j * n + i)] = (float)((ar * br - ai * bi) * nn);
-            comb[2 * (j * n + i) + 1] = (float)((ar * bi + ai * br) * nn);
-        }
-    HIPC(c, c->hdet_pl.alloc(n * D));
-    HIPC(c, c->hcomb_pl.alloc(n * D));
-    HIPC(c, hipMemcpy(c->hdet_pl, hs_det, sizeof(cf) * n * D, hipMemcpyHostToDevice));
-    HIPC(c, hipMemcpy(c->hcomb_pl, comb.data(), sizeof(cf) * n * D, hipMemcpyHostToDevice));
+    int r;
+    if ((r = upload(c, c->hdet_pl, hs_det, n * D, FRESH)) || (r = upload(c, c->hcomb_pl, combined(hs.data(), hs_det, n, D).data(), n * D, FRESH))) return r;
     HIPC(c, c->det_pl.alloc(fields));
     if (c->with_grad && !c->generic) HIPC(c, c->seed_pl.alloc(fields));
     // every plane's launch leaves its own partial sums: room for D times those of one plane
     HIPC(c, c->partial.room((size_t)2 * c->npartial * D * (c->resident ? 16 : 1)));
     for (int j = 0; j < D; ++j) c->hdet00_pl.push_back(std::complex<double>(hdet00[2 * j], hdet00[2 * j + 1]));
     c->planes = D;
-    c->tape_valid = c->last_valid = false;
     return 0;
 }
 
@@ -1823,31 +1859,19 @@ int bdof_probe_stack_supported(bdof_ctx* c) {
 }
 
 int bdof_set_probe_stack(bdof_ctx* c, const float* stack, const float* det) {
-    if (!c) return BDOF_ERR_ARG;
-    if (int r = need_configured(c)) return r;
-    HIPC(c, hipSetDevice(c->device));
-    HIPC(c, hipStreamSynchronize(c->stream));
+    int r = enter_setter(c, true);
+    if (r) return r;
     c->pstack.reset(); c->pdet.reset(); c->pdetT.reset();
     c->pdet64.reset(); c->pdetT64.reset();                     // a host-supplied stack comes in float32 only
-    c->mod_dirty = true;
+    changed(c, CHANGED_CARRIER_FIELD);
     if (!stack && !det) return 0;
     if (!stack || !det) return fail(c, BDOF_ERR_ARG, "bdof_set_probe_stack: both arrays or neither");
-    if (int r = admit(c, "a carrier field (bdof_set_probe_stack)", CARRIES_BINNING | NO_DATA_TERM)) return r;
-    const size_t n = (size_t)c->NX * c->NY, fld = sizeof(cf) * n;
-    HIPC(c, c->pstack.alloc(n * steps(c).stack_planes()));       // one plane per propagation step
-    HIPC(c, c->pdet.alloc(n));
-    HIPC(c, hipMemcpy(c->pstack, stack, fld * (size_t)n_steps(c), hipMemcpyHostToDevice));
-    HIPC(c, hipMemcpy(c->pdet, det, fld, hipMemcpyHostToDevice));
+    if ((r = admit(c, "a carrier field (bdof_set_probe_stack)", CARRIES_BINNING | NO_DATA_TERM))) return r;
+    const size_t n = (size_t)c->NX * c->NY;
+    if ((r = upload(c, c->pstack, stack, n * steps(c).stack_planes(), FRESH))) return r;       // one plane per propagation step
+    if ((r = upload(c, c->pdet, det, n, FRESH))) return r;
     // the streaming far-field detector works on rows [ky][kx]: the same field transposed
-    std::vector<float> t((size_t)2 * c->NX * c->NY);
-    for (int i = 0; i < c->NX; ++i)
-        for (int j = 0; j < c->NY; ++j) {
-            t[2 * ((size_t)j * c->NX + i)] = det[2 * ((size_t)i * c->NY + j)];
-            t[2 * ((size_t)j * c->NX + i) + 1] = det[2 * ((size_t)i * c->NY + j) + 1];
-        }
-    HIPC(c, c->pdetT.alloc(n));
-    HIPC(c, hipMemcpy(c->pdetT, t.data(), fld, hipMemcpyHostToDevice));
-    return 0;
+    return upload(c, c->pdetT, transposed(det, c->NX, c->NY).data(), n, FRESH);
 }
 
 // The carrier field of a localised probe (bdof_set_probe_stack) computed ON THE DEVICE in float64: S - 1 transfer-function steps
@@ -1858,22 +1882,13 @@ int bdof_set_probe_field(bdof_ctx* c, const double* probe, const double* hT, con
     if (!c || !probe || !hT) return BDOF_ERR_ARG;
     if (!c->have_physics) return fail(c, BDOF_ERR_STATE, "bdof_set_physics has not been called");
     if (c->det_mode == BDOF_DET_NEAR && !hdetT) return fail(c, BDOF_ERR_ARG, "hdetT required for BDOF_DET_NEAR");
-    if (int r = admit(c, "a carrier field (bdof_set_probe_field)", CARRIES_BINNING | NO_DATA_TERM)) return r;
-    HIPC(c, hipSetDevice(c->device));
-    HIPC(c, hipStreamSynchronize(c->stream));
-    const size_t n = (size_t)c->NX * c->NY, fld = sizeof(cf) * n, dbytes = sizeof(double2) * n;
+    int r = admit(c, "a carrier field (bdof_set_probe_field)", CARRIES_BINNING | NO_DATA_TERM);
+    if (r || (r = enter_setter(c, true))) return r;
+    const size_t n = (size_t)c->NX * c->NY;
     rocfft_plan pf, pi;
-    int r = field_plans(c, c->NX, c->NY, 1, true, &pf, &pi);       // fields are [x][y]
-    if (r) return r;
+    if ((r = field_plans(c, c->NX, c->NY, 1, true, &pf, &pi))) return r;       // fields are [x][y]
     DevBuf<double2> dp, dh, dhd;
-    HIPC(c, dp.alloc(n));
-    HIPC(c, dh.alloc(n));
-    HIPC(c, hipMemcpy(dp, probe, dbytes, hipMemcpyHostToDevice));
-    HIPC(c, hipMemcpy(dh, hT, dbytes, hipMemcpyHostToDevice));
-    if (hdetT) {
-        HIPC(c, dhd.alloc(n));
-        HIPC(c, hipMemcpy(dhd, hdetT, dbytes, hipMemcpyHostToDevice));
-    }
+    if ((r = upload(c, dp, probe, n, FRESH)) || (r = upload(c, dh, hT, n, FRESH)) || (hdetT && (r = upload(c, dhd, hdetT, n, FRESH)))) return r;
     c->pstack.reset(); c->pdet.reset(); c->pdetT.reset();
     c->pdet64.reset(); c->pdetT64.reset();
     const int nz = n_steps(c);                                   // one plane per propagation step (hT: the step's own table)
@@ -1901,10 +1916,9 @@ int bdof_set_probe_field(bdof_ctx* c, const double* probe, const double* hT, con
     HIPC(c, hipGetLastError());
     HIPC(c, hipStreamSynchronize(c->stream));         // the temporaries go when this returns: nothing queued may still read them
     // the wave is carried as p_z + eps_z with eps_0 = 0: no probe of its own, no scalar carrier
-    HIPC(c, hipMemsetAsync(c->probe, 0, fld, c->stream));
+    HIPC(c, hipMemsetAsync(c->probe, 0, sizeof(cf) * n, c->stream));
     c->a0 = 0.0;
-    c->res_dirty = true;
-    c->mod_dirty = true;
+    changed(c, CHANGED_CARRIER_FIELD_F64);
     c->have_probe = true;
     return 0;
 }
@@ -1915,16 +1929,12 @@ int bdof_set_object(bdof_ctx* c, const void* vol, long long n_rows, int volNY, c
     if (volNY < 1) return fail(c, BDOF_ERR_ARG, "volNY must be >= 1");
     if (tab && (volNX < 1 || n_angles < 1)) return fail(c, BDOF_ERR_ARG, "volNX and n_angles must be >= 1 with a table");
     if (!tab && volNY != c->NY) return fail(c, BDOF_ERR_ARG, "without a rotation table volNY must equal NY");
-    // the volume bdof_rotation_adjoint_adam has just left the table of: nothing to rebuild
-    const bool current = c->mod_for && vol == (const void*)c->mod_for && (size_t)n_rows == c->mod_for_rows && volNY == c->mod_for_NY;
-    c->mod_for = nullptr;
     c->obj_src = (const float2*)vol;
     c->obj_bound_mod = false;
     c->obj_rows = (size_t)n_rows;
-    c->mod_dirty = !current;
-    c->mod_mean_pending = current;
     c->obj.vol = nullptr;
     c->obj.volNY = volNY;
+    changed(c, CHANGED_OBJECT);
     c->obj.tab = tab;
     c->obj.volNX = tab ? volNX : c->NX;
     c->obj.S = c->S;
@@ -1970,21 +1980,20 @@ int bdof_forward(bdof_ctx* c, int B, const int* angle_of_b, const int* xoff, con
     if ((r = begin_batch(c, angle_of_b, xoff, yoff, c->k_fft))) return r;
     if (use_resident(c, B) && !keep_tape) {
         if ((r = resident_run(c, B, nullptr, out_wave, false))) return r;
-        c->tape_valid = c->last_valid = false;
+        changed(c, TAPE_OVERWRITTEN);
         return 0;
     }
     if (c->generic) {
         if (keep_tape) return fail(c, BDOF_ERR_STATE, "the per-slice history is not kept by the generic-size engine");
         if ((r = generic_forward(c, B, out_wave, false))) return r;
-        c->tape_valid = c->last_valid = false;
+        changed(c, TAPE_OVERWRITTEN);
         return launched(c);
     }
     Split split;
     if ((r = split.open(c, B, c->NX, 16))) return r;
     forward_sweep(c, split, keep_tape ? TAPE_HISTORY : TAPE_NONE);
     if ((r = split.close(c))) return r;
-    c->tape_valid = keep_tape != 0;
-    c->last_valid = false;
+    tape_holds(c, keep_tape != 0, false);
     const DetRoute dr = det_route(c);
     const Group all = whole(c, B);
     if (out_wave && c->planes > 1) {
@@ -2002,7 +2011,7 @@ int bdof_forward(bdof_ctx* c, int B, const int* angle_of_b, const int* xoff, con
             const cf* in = nz > 1 ? c->tape + (size_t)(nz - 2) * fld : nullptr;   // psi_hat_{S-1}
             launch_row_fwd(c, all, nz - 1, in, c->bufA, false);
         }
-        c->last_valid = true;
+        tape_holds(c, true, true);
     }
     return launched(c);
 }
@@ -2040,7 +2049,7 @@ static int forward_range(bdof_ctx* c, int B, const int* angle_of_b, const int* x
                              c->bufA, nullptr, false, (cf*)out_real, nullptr, 1.f / c->NY, 1.f);
     }
     if ((r = split.close(c))) return r;
-    c->tape_valid = c->last_valid = false;
+    changed(c, TAPE_OVERWRITTEN);
     return launched(c);
 }
 
@@ -2122,8 +2131,8 @@ int bdof_adjoint_range(bdof_ctx* c, int B, const int* angle_of_b, const int* xof
         }
     }
     if ((r = split.close(c))) return r;
-    c->tape_valid = c->last_valid = false;
-    c->gpsi_src = nullptr;
+    changed(c, TAPE_OVERWRITTEN);
+    changed(c, PROBE_GRADIENT_GONE);
     return launched(c);
 }
 
@@ -2367,8 +2376,8 @@ static int sweep_f64(bdof_ctx* c, const Model64& m, const ObjView& o, int B, dou
         C64BwdArgs ba{psi, tape + (size_t)(z - z0) * n, c->grot, o, B, NX, NY, c->S, z, m.k};
         hipLaunchKernelGGL(k_c64_bwd, dim3(eg), dim3(256), 0, c->stream, ba);
     }
-    c->tape_valid = c->last_valid = false;
-    c->gpsi_src = nullptr;
+    changed(c, TAPE_OVERWRITTEN);
+    changed(c, PROBE_GRADIENT_GONE);
     return 0;
 }
 
@@ -2388,6 +2397,17 @@ int bdof_forward_range_f64(bdof_ctx* c, int B, const int* angle_of_b, const int*
     const Model64 m{k, prop_last != 0, [&](bool) { return free_step(c, c->fft, c->stream, fields, B, c->NX, c->NY, h, H_KXKY, 0, true); }, nullptr};
     if ((r = sweep_f64(c, m, rows_view(c, angle_of_b, xoff, yoff), B, (double2*)fields, nullptr, z0, nz, nullptr, nullptr, 0.0))) return r;
     return launched(c);
+}
+
+// What the two float64 twins ask before they run: a batch of measurements, the twin's own model held (`held`, else `text`), the
+// object as (delta, beta) rows, the gradient workspace, a batch within Bmax and its angles
+static int ready_f64(bdof_ctx* c, int B, const int* angle_of_b, const float* meas, bool held, const char* text) {
+    if (!c || !meas) return BDOF_ERR_ARG;
+    if (!held) return fail(c, BDOF_ERR_STATE, text);
+    if (!c->obj_src) return fail(c, BDOF_ERR_STATE, "bdof_set_object (with (delta, beta) rows) has not been called");
+    if (!c->grot || !c->partial) return fail(c, BDOF_ERR_STATE, "bdof_configure(with_grad = 1) needed");
+    if (int r = check_batch(c, B)) return r;
+    return need_angles(c, angle_of_b);
 }
 
 // ---- the real-space propagator in float64 (bdof_conv64.h) -------------------------------------------------------------------
@@ -2417,24 +2437,19 @@ static int c64_room(bdof_ctx* c, int B, bool tf, size_t M) {
 int bdof_set_conv_f64(bdof_ctx* c, const double* probe, const double* khat, int ks, double ksum_re, double ksum_im, double k) {
     if (int r = admit(c, "bdof_set_conv_f64", NO_DATA_TERM)) return r;
     if (!c || !probe || !khat) return BDOF_ERR_ARG;
-    if (int r = need_configured(c)) return r;
+    int r = enter_setter(c, true);
+    if (r) return r;
     if (c->NX != c->NY) return fail(c, BDOF_ERR_SIZE, "the float64 real-space path takes square wavefields");
     if (ks < 1 || ks % 2 == 0 || ks >= c->NX) return fail(c, BDOF_ERR_ARG, "kernel_size must be odd and smaller than the field");
-    HIPC(c, hipSetDevice(c->device));
-    HIPC(c, hipStreamSynchronize(c->stream));
     const size_t n = (size_t)c->NX * c->NY, M = (size_t)c->NX + ks - 1;
     if (c->c64_ks != ks) {
         c->c64_khat.reset(); c->c64_big.reset();
         c->c64_B = 0;
     }
-    if (!c->c64_probe) HIPC(c, c->c64_probe.alloc(n));
-    if (!c->c64_khat) HIPC(c, c->c64_khat.alloc(M * M));
     if (!c->c64_scal) HIPC(c, c->c64_scal.alloc(2));
     if (!c->c64_part) HIPC(c, c->c64_part.alloc((size_t)c->ncu * 16));
-    HIPC(c, hipMemcpy(c->c64_probe, probe, n * sizeof(double2), hipMemcpyHostToDevice));
-    HIPC(c, hipMemcpy(c->c64_khat, khat, M * M * sizeof(double2), hipMemcpyHostToDevice));
-    c->c64_ks = ks;
-    c->c64_tf = false;
+    if ((r = upload(c, c->c64_probe, probe, n, KEEP)) || (r = upload(c, c->c64_khat, khat, M * M, KEEP))) return r;
+    twin64_holds(c, false, ks);
     c->c64_ksum = std::complex<double>(ksum_re, ksum_im);
     c->c64_k = k;
     return c64_room(c, c->Bmax, false, M);
@@ -2444,15 +2459,9 @@ int bdof_set_conv_f64(bdof_ctx* c, const double* probe, const double* khat, int 
 // step of the renormalised exit wave): hdetT host complex128 [kx][ky], ifftshift(H_det) / (NX NY); NULL removes it
 int bdof_set_conv_f64_detector(bdof_ctx* c, const double* hdetT) {
     if (int r = admit(c, "bdof_set_conv_f64_detector", NO_DATA_TERM)) return r;
-    if (!c) return BDOF_ERR_ARG;
-    if (int r = need_configured(c)) return r;
-    HIPC(c, hipSetDevice(c->device));
-    HIPC(c, hipStreamSynchronize(c->stream));
-    const size_t n = (size_t)c->NX * c->NY;
+    if (int r = enter_setter(c, true)) return r;
     if (!hdetT) { c->c64_hdet.reset(); return 0; }
-    if (!c->c64_hdet) HIPC(c, c->c64_hdet.alloc(n));
-    HIPC(c, hipMemcpy(c->c64_hdet, hdetT, n * sizeof(double2), hipMemcpyHostToDevice));
-    return 0;
+    return upload(c, c->c64_hdet, hdetT, (size_t)c->NX * c->NY, KEEP);
 }
 
 // bdof_loss_grad_conv with every quantity in float64: loss left for bdof_get_loss, gradient rows in the ctx's rotated-frame
@@ -2462,12 +2471,8 @@ int bdof_set_conv_f64_detector(bdof_ctx* c, const double* hdetT) {
 // bdof_set_conv_f64_detector.
 int bdof_loss_grad_conv_f64(bdof_ctx* c, int B, const int* angle_of_b, const int* xoff, const int* yoff, const float* meas, double meas_ref) {
     if (int r = admit(c, "bdof_loss_grad_conv_f64", CARRIES_NOTHING)) return r;
-    if (!c || !meas) return BDOF_ERR_ARG;
-    if (!c->c64_ks || c->c64_tf) return fail(c, BDOF_ERR_STATE, "bdof_set_conv_f64 has not been called");
-    if (!c->obj_src) return fail(c, BDOF_ERR_STATE, "bdof_set_object (with (delta, beta) rows) has not been called");
-    if (!c->grot || !c->partial) return fail(c, BDOF_ERR_STATE, "bdof_configure(with_grad = 1) needed");
-    int r;
-    if ((r = check_batch(c, B)) || (r = need_angles(c, angle_of_b))) return r;
+    int r = ready_f64(c, B, angle_of_b, meas, c && c->c64_ks && !c->c64_tf, "bdof_set_conv_f64 has not been called");
+    if (r) return r;
     if (c->det_mode == BDOF_DET_NEAR && !c->c64_hdet)
         return fail(c, BDOF_ERR_STATE, "near-field detector: bdof_set_conv_f64_detector has not been called");
     HIPC(c, hipSetDevice(c->device));
@@ -2513,19 +2518,13 @@ int bdof_loss_grad_conv_f64(bdof_ctx* c, int B, const int* angle_of_b, const int
 int bdof_set_tf_f64(bdof_ctx* c, const double* probe, const double* hT, const double* hdetT, double k) {
     if (int r = admit(c, "bdof_set_tf_f64", NO_DATA_TERM)) return r;
     if (!c || !probe || !hT) return BDOF_ERR_ARG;
-    if (int r = need_configured(c)) return r;
+    int r = enter_setter(c, true);
+    if (r) return r;
     if (c->det_mode == BDOF_DET_NEAR && !hdetT) return fail(c, BDOF_ERR_ARG, "a near-field detector needs its transfer function in float64 too");
-    HIPC(c, hipSetDevice(c->device));
-    HIPC(c, hipStreamSynchronize(c->stream));
     const size_t n = (size_t)c->NX * c->NY;
-    if (!c->c64_probe) HIPC(c, c->c64_probe.alloc(n));
-    if (!c->c64_h) HIPC(c, c->c64_h.alloc(n));
-    if (hdetT && !c->c64_hdet) HIPC(c, c->c64_hdet.alloc(n));
-    HIPC(c, hipMemcpy(c->c64_probe, probe, n * sizeof(double2), hipMemcpyHostToDevice));
-    HIPC(c, hipMemcpy(c->c64_h, hT, n * sizeof(double2), hipMemcpyHostToDevice));
-    if (hdetT) HIPC(c, hipMemcpy(c->c64_hdet, hdetT, n * sizeof(double2), hipMemcpyHostToDevice));
-    c->c64_tf = true;
-    c->c64_ks = 1;
+    if ((r = upload(c, c->c64_probe, probe, n, KEEP)) || (r = upload(c, c->c64_h, hT, n, KEEP)) ||
+        (hdetT && (r = upload(c, c->c64_hdet, hdetT, n, KEEP)))) return r;
+    twin64_holds(c, true, 1);
     c->c64_k = k;
     return c64_room(c, c->Bmax, true, 0);
 }
@@ -2536,12 +2535,8 @@ int bdof_set_tf_f64(bdof_ctx* c, const double* probe, const double* hT, const do
 // kernels on the device.  meas: device float, laid out as for bdof_loss_grad (+ meas_ref under bdof_set_meas_mode(1)).
 int bdof_loss_grad_tf_f64(bdof_ctx* c, int B, const int* angle_of_b, const int* xoff, const int* yoff, const float* meas, double meas_ref) {
     if (int r = admit(c, "bdof_loss_grad_tf_f64", NO_DATA_TERM)) return r;
-    if (!c || !meas) return BDOF_ERR_ARG;
-    if (!c->c64_tf) return fail(c, BDOF_ERR_STATE, "bdof_set_tf_f64 has not been called");
-    if (!c->obj_src) return fail(c, BDOF_ERR_STATE, "bdof_set_object (with (delta, beta) rows) has not been called");
-    if (!c->grot || !c->partial) return fail(c, BDOF_ERR_STATE, "bdof_configure(with_grad = 1) needed");
-    int r;
-    if ((r = check_batch(c, B)) || (r = need_angles(c, angle_of_b))) return r;
+    int r = ready_f64(c, B, angle_of_b, meas, c && c->c64_tf, "bdof_set_tf_f64 has not been called");
+    if (r) return r;
     HIPC(c, hipSetDevice(c->device));
     if ((r = c64_room(c, B, true, 0))) return r;
     double2* psi = c->c64_psi;
@@ -2585,12 +2580,12 @@ int bdof_loss_grad(bdof_ctx* c, int B, const int* angle_of_b, const int* xoff, c
     c->fused_last = c->adj_fused_last = 0;
     if (use_resident(c, B)) {
         if ((r = resident_run(c, B, meas, out_wave, true))) return r;
-        c->tape_valid = c->last_valid = false;
+        changed(c, TAPE_OVERWRITTEN);
         return 0;
     }
     if (c->generic) {
         if ((r = generic_loss_grad(c, B, meas, out_wave))) return r;
-        c->tape_valid = c->last_valid = false;
+        changed(c, TAPE_OVERWRITTEN);
         c->gpsi_src = c->bufA;                  // the adjoint sweep ends with G(psi_0) in the field buffer, [b][x][y]
         return launched(c);
     }
@@ -2601,8 +2596,7 @@ int bdof_loss_grad(bdof_ctx* c, int B, const int* angle_of_b, const int* xoff, c
     c->fused_last = fused ? 1 : 0;
     c->adj_fused_last = adj_fused ? 1 : 0;
     forward_sweep(c, split, c->recompute ? TAPE_LAST : TAPE_HISTORY, fused, adj_fused);
-    c->tape_valid = false;      // the tape holds an incomplete history (or phi_{S-1} alone), not what bdof_tape_to_real expects
-    c->last_valid = false;
+    changed(c, TAPE_OVERWRITTEN);      // the tape holds an incomplete history (or phi_{S-1} alone), not what bdof_tape_to_real expects
     int npart = 0;
     // Detector + seed.  Afterwards bufB holds g_hat(phi_{S-1}) (L1 order, normalised hybrid).
     const DetRoute dr = det_route(c);
@@ -2640,12 +2634,11 @@ int bdof_set_conv(bdof_ctx* c, const float* ky, const float* kx, int ks, double 
                   double ksum_im, double k) {
     if (int r = admit(c, "bdof_set_conv", NO_DATA_TERM)) return r;
     if (!c || !ky || !kx) return BDOF_ERR_ARG;
-    if (int r = need_configured(c)) return r;
+    if (int r = enter_setter(c, false)) return r;
     if (ks < 1 || ks > BDOF_CONV_MAXK || ks % 2 == 0) return fail(c, BDOF_ERR_ARG, "kernel_size must be odd and <= 33");
     if (c->generic || c->NX % BDOF_CONV_TX || c->NY % BDOF_CONV_TY)
         return fail(c, BDOF_ERR_SIZE, "the conv propagator needs power-of-two wavefields (tiles are 32 x 64)");
-    HIPC(c, hipSetDevice(c->device));
-    c->c64_tf = false; c->c64_ks = 0;     // a float64 twin handed over before (bdof_set_tf_f64 / bdof_set_conv_f64) held the previous model
+    changed(c, CHANGED_CONV_TAPS);
     for (int i = 0; i < ks; ++i) {
         c->taps.ky[i] = make_float2(ky[2 * i], ky[2 * i + 1]);
         c->taps.kx[i] = make_float2(kx[2 * i], kx[2 * i + 1]);
@@ -2659,11 +2652,9 @@ int bdof_set_conv(bdof_ctx* c, const float* ky, const float* kx, int ks, double 
     if (!c->conv_scal) HIPC(c, c->conv_scal.alloc(4));
     HIPC(c, hipStreamSynchronize(c->stream));                  // a sweep still in flight reads the previous taps
     if (c->taps_copies != 1) c->taps_dev.reset();
-    if (!c->taps_dev) HIPC(c, c->taps_dev.alloc(1));
     c->taps_copies = 1;
-    HIPC(c, hipMemcpy(c->taps_dev, &c->taps, sizeof(ConvTaps), hipMemcpyHostToDevice));
+    if (int r = upload(c, c->taps_dev, &c->taps, 1, KEEP)) return r;
     c->have_conv = true;
-    c->mod_dirty = true;
     return 0;
 }
 
@@ -2673,7 +2664,7 @@ int bdof_set_conv_taps_f64(bdof_ctx* c, const double* ky, const double* kx, doub
     if (!c->have_conv) return fail(c, BDOF_ERR_STATE, "bdof_set_conv has not been called");
     const int D = c->tw_dither;
     if (D < 2) return 0;                                       // BDOF_TW_DITHER=0: the nearest-rounded taps of bdof_set_conv stay
-    HIPC(c, hipSetDevice(c->device));
+    if (int r = enter_setter(c, false)) return r;
     std::vector<ConvTaps> t((size_t)D, c->taps);
     const int ks = c->taps.ks;
     for (int d = 0; d < D; ++d) {
@@ -2686,9 +2677,8 @@ int bdof_set_conv_taps_f64(bdof_ctx* c, const double* ky, const double* kx, doub
         }
         t[d].e = make_float2(dither_pick(e_re, d, 0.25), dither_pick(e_im, d, 0.75));
     }
-    HIPC(c, hipStreamSynchronize(c->stream));
-    HIPC(c, c->taps_dev.alloc((size_t)D));
-    HIPC(c, hipMemcpy(c->taps_dev, t.data(), sizeof(ConvTaps) * D, hipMemcpyHostToDevice));
+    HIPC(c, hipStreamSynchronize(c->stream));                  // a sweep still in flight reads the previous taps
+    if (int r = upload(c, c->taps_dev, t.data(), (size_t)D, FRESH)) return r;
     c->taps_copies = D;
     return 0;
 }
@@ -2752,11 +2742,14 @@ template <bool BWD> static int launch_conv(bdof_ctx* c, const Group& g, ConvArgs
     }); });
 }
 
+// the conv sweeps' sub-batches: tiles of 32 x 32 pixels, two workgroups per CU
+static int conv_split(bdof_ctx* c, int B, Split* split) { return split->open(c, B, (c->NX / 32) * (c->NY / 32), 2); }
+
 // forward sweep of the conv propagator; leaves psi_S (eps part) in bufB and the scalars in conv_scal
 static int conv_forward_sweep(bdof_ctx* c, int B, bool tape) {
     const size_t fld = (size_t)c->Bmax * c->NX * c->NY;
     const size_t n = (size_t)B * c->NX * c->NY, plane = (size_t)c->NX * c->NY;
-    const int egrid = (int)std::min<size_t>((n + 255) / 256, (size_t)c->ncu * 16);
+    const int egrid = g_elem_grid(c, n);
     const bool cs = c->cstack != nullptr;           // carrier field: eps is the scattered wave alone, padded with zeros
     const cf zero = make_float2(0.f, 0.f);
     ObjView obj = c->obj;
@@ -2768,7 +2761,7 @@ static int conv_forward_sweep(bdof_ctx* c, int B, bool tape) {
     // launch are filled by the other's; the slices of a group follow each other on its stream, the groups meet again at the
     // detector (the renormalisation reads batch element 0)
     Split split;
-    if ((r = split.open(c, B, (c->NX / 32) * (c->NY / 32), 2))) return r;
+    if ((r = conv_split(c, B, &split))) return r;
     for (const Group& g : split) {
         const size_t off = (size_t)g.b0 * plane;
         const ObjView gobj = sub_obj(c, g);
@@ -2789,12 +2782,21 @@ static int conv_forward_sweep(bdof_ctx* c, int B, bool tape) {
     return 0;
 }
 
-// carrier field: the renormalisation s = p_0[0,0] / (p_S[0,0] + eps_S[0,0,0]) in float64 (one 8-byte read-back)
-static int conv_scale64(bdof_ctx* c, double2* s64) {
-    cf e0;
-    HIPC(c, hipMemcpyAsync(&e0, c->bufB, sizeof(cf), hipMemcpyDeviceToHost, c->stream));
+// The one read-back of the conv path: the corner pixel (batch element 0) of each of the device fields `dev` (two at the most), to
+// float64 scalars on the host; 8 bytes each and one drain of the ctx stream for all of them
+static int conv_corner(bdof_ctx* c, std::initializer_list<const cf*> dev, std::complex<double>* out) {
+    cf px[2];
+    int i = 0;
+    for (const cf* d : dev) HIPC(c, hipMemcpyAsync(&px[i++], d, sizeof(cf), hipMemcpyDeviceToHost, c->stream));
     HIPC(c, hipStreamSynchronize(c->stream));
-    const std::complex<double> sd = c->c_p0 / (c->c_pS + std::complex<double>(e0.x, e0.y));
+    for (int j = 0; j < i; ++j) out[j] = std::complex<double>(px[j].x, px[j].y);
+    return 0;
+}
+// carrier field: the renormalisation s = p_0[0,0] / (p_S[0,0] + eps_S[0,0,0]) in float64
+static int conv_scale64(bdof_ctx* c, double2* s64) {
+    std::complex<double> e0;
+    if (int r = conv_corner(c, {c->bufB}, &e0)) return r;
+    const std::complex<double> sd = c->c_p0 / (c->c_pS + e0);
     *s64 = make_double2(sd.real(), sd.imag());
     return 0;
 }
@@ -2819,25 +2821,50 @@ static ConvFinalArgs conv_final_args(bdof_ctx* c, int B, const cf* psi_eps, cf* 
     return fa;
 }
 
+// The detector stage of the conv path behind a real-space (near) or far-field detector, from eps_S in bufB: the renormalised wave
+// through the detector transforms to out_wave and, with meas, the data term (returns the number of partial sums) and its seed
+// back to real space, scaled, in *seed.  bdof_forward_conv is bdof_loss_grad_conv without meas.  The detector transforms see no
+// scalar carrier (the renormalised wave carries its own; under residual splitting — meas with bdof_set_meas_mode(1) — det does).
+// Carrier field: only the scattered part s eps_S goes through them in float32; the carrier's detector plane comes in float64,
+// times s (det.pfield64, det.pscale).
+static int conv_detector(bdof_ctx* c, int B, const DetPlane& det, const float* meas, cf* out_wave, cf** seed) {
+    const size_t n = (size_t)B * c->NX * c->NY;
+    const int egrid = g_elem_grid(c, n);
+    const ConvFinalArgs fa = conv_final_args(c, B, c->bufB, c->bufA, meas && c->meas_dev != 0);
+    hipLaunchKernelGGL((k_conv_final<0>), dim3(egrid), dim3(256), 0, c->stream, fa);
+    const Group all = whole(c, B);
+    launch_real_to_hyb(c, all, c->bufA, c->bufC);
+    int npart;
+    if (c->det_mode == BDOF_DET_NEAR) {
+        // the detector step and its adjoint take copy 0 of the dithered constants, whatever ran on the ctx before
+        launch_row_prop(c, all, c->bufC, c->bufA, c->hdet, 1.f, 0, 0);                                               // d_hat (L1)
+        npart = launch_loss_real(c, all, det, c->bufA, meas ? (cf*)c->bufC : nullptr, meas != nullptr, out_wave, meas, 1.f, 1.f);
+        if (meas) launch_row_prop(c, all, c->bufC, c->bufA, c->hdet, 1.f, 1, 0);                                     // g_hat(q) (L1)
+    } else {
+        npart = launch_loss_far(c, all, det, c->bufC, meas ? (cf*)c->bufA : nullptr, out_wave, meas, 1.f, 1.f);      // g_hat(q) (L1)
+    }
+    if (!meas) return 0;
+    launch_loss_real(c, all, DetPlane{}, c->bufA, nullptr, false, c->bufC, nullptr, 1.f, 1.f);        // G(q), real space
+    hipLaunchKernelGGL(k_conv_scale_seed, dim3(egrid), dim3(256), 0, c->stream, c->bufC, c->conv_scal, n);
+    *seed = c->bufC;
+    return npart;
+}
+
 
 extern "C" {
 
 int bdof_set_conv_probe_stack(bdof_ctx* c, const float* stack, const double* det64, double p0_re, double p0_im, double pS_re, double pS_im) {
     if (int r = admit(c, "bdof_set_conv_probe_stack", NO_DATA_TERM)) return r;
-    if (!c) return BDOF_ERR_ARG;
-    if (int r = need_configured(c)) return r;
-    HIPC(c, hipSetDevice(c->device));
-    HIPC(c, hipStreamSynchronize(c->stream));
+    int r = enter_setter(c, true);
+    if (r) return r;
     c->cstack.reset();
     c->cdet64.reset();
+    changed(c, CHANGED_CONV_CARRIER_FIELD);
     if (!stack && !det64) return 0;
     if (!stack || !det64) return fail(c, BDOF_ERR_ARG, "bdof_set_conv_probe_stack: both arrays or neither");
     if (!c->have_conv) return fail(c, BDOF_ERR_STATE, "bdof_set_conv has not been called");
     const size_t plane = (size_t)c->NX * c->NY;
-    HIPC(c, c->cstack.alloc(plane * (size_t)(c->S + 1)));
-    HIPC(c, c->cdet64.alloc(plane));
-    HIPC(c, hipMemcpy(c->cstack, stack, sizeof(cf) * plane * (size_t)(c->S + 1), hipMemcpyHostToDevice));
-    HIPC(c, hipMemcpy(c->cdet64, det64, sizeof(double2) * plane, hipMemcpyHostToDevice));
+    if ((r = upload(c, c->cstack, stack, plane * (size_t)(c->S + 1), FRESH)) || (r = upload(c, c->cdet64, det64, plane, FRESH))) return r;
     c->c_p0 = std::complex<double>(p0_re, p0_im);
     c->c_pS = std::complex<double>(pS_re, pS_im);
     return 0;
@@ -2850,30 +2877,17 @@ int bdof_forward_conv(bdof_ctx* c, int B, const int* angle_of_b, const int* xoff
     if (!out_wave) return BDOF_ERR_ARG;
     if ((r = begin_batch(c, angle_of_b, xoff, yoff, c->k_conv))) return r;
     if ((r = conv_forward_sweep(c, B, false))) return r;
-    c->tape_valid = c->last_valid = false;
-    const size_t n = (size_t)B * c->NX * c->NY;
-    const int egrid = (int)std::min<size_t>((n + 255) / 256, (size_t)c->ncu * 16);
+    changed(c, TAPE_OVERWRITTEN);
     const bool cs = c->cstack != nullptr;
     if (c->det_mode == BDOF_DET_NONE) {
         ConvFinalArgs fa = conv_final_args(c, B, c->bufB, (cf*)out_wave, false);
         fa.pfield = cs ? c->cstack + (size_t)c->S * fa.plane : nullptr;
-        hipLaunchKernelGGL((k_conv_final<0>), dim3(egrid), dim3(256), 0, c->stream, fa);
+        hipLaunchKernelGGL((k_conv_final<0>), dim3(g_elem_grid(c, fa.n)), dim3(256), 0, c->stream, fa);
     } else {
-        // the detector transforms see no scalar carrier (the renormalised wave carries its own).  Carrier field: only the
-        // scattered part s eps_S goes through them in float32; the carrier's detector plane comes in float64, times s
         DetPlane det;
         if (cs && (r = conv_scale64(c, &det.pscale))) return r;
         det.pfield64 = cs ? c->cdet64 : nullptr;
-        const ConvFinalArgs fa = conv_final_args(c, B, c->bufB, c->bufA, false);
-        hipLaunchKernelGGL((k_conv_final<0>), dim3(egrid), dim3(256), 0, c->stream, fa);
-        const Group all = whole(c, B);
-        launch_real_to_hyb(c, all, c->bufA, c->bufC);
-        if (c->det_mode == BDOF_DET_NEAR) {
-            launch_row_prop(c, all, c->bufC, c->bufA, c->hdet, 1.f, 0, 0);      // the detector step takes copy 0 of the dithered constants
-            launch_loss_real(c, all, det, c->bufA, nullptr, false, (cf*)out_wave, nullptr, 1.f, 1.f);
-        } else {
-            launch_loss_far(c, all, det, c->bufC, nullptr, (cf*)out_wave, nullptr, 1.f, 1.f);
-        }
+        conv_detector(c, B, det, nullptr, (cf*)out_wave, nullptr);
     }
     return launched(c);
 }
@@ -2890,13 +2904,13 @@ int bdof_loss_grad_conv(bdof_ctx* c, int B, const int* angle_of_b, const int* xo
     if (split && (c->det_mode == BDOF_DET_FAR || std::abs(c->a0) == 0.0))
         return fail(c, BDOF_ERR_STATE, "bdof_set_meas_mode(1) needs a plane-wave carrier and a real-space detector");
     if (!c->with_grad) return fail(c, BDOF_ERR_STATE, "bdof_loss_grad_conv needs bdof_configure(with_grad=1)");
-    c->gpsi_src = nullptr;                   // the real-space propagator does not export the probe gradient
+    changed(c, PROBE_GRADIENT_GONE);         // the real-space propagator does not export the probe gradient
     if ((r = begin_batch(c, angle_of_b, xoff, yoff, c->k_conv))) return r;
     if ((r = conv_forward_sweep(c, B, true))) return r;
-    c->tape_valid = c->last_valid = false;
+    changed(c, TAPE_OVERWRITTEN);
     const size_t fld = (size_t)c->Bmax * c->NX * c->NY;
     const size_t n = (size_t)B * c->NX * c->NY;
-    const int egrid = (int)std::min<size_t>((n + 255) / 256, (size_t)c->ncu * 16);
+    const int egrid = g_elem_grid(c, n);
     const double seed_scale = 2.0 / ((double)B * c->NX * c->NY);
     const cf zero = make_float2(0.f, 0.f);
     cf* gp;
@@ -2911,12 +2925,10 @@ int bdof_loss_grad_conv(bdof_ctx* c, int B, const int* angle_of_b, const int* xo
     det.dref = 0.f;
     set_carrier(det, 0.0);              // split: A (times Hdet[0,0] for the near detector), the constant part of the detector wave
     if (split) {
-        cf e0, p0;                  // corner pixel of batch element 0: scattered part of psi_S and of the probe
-        HIPC(c, hipMemcpyAsync(&e0, c->bufB, sizeof(cf), hipMemcpyDeviceToHost, c->stream));
-        HIPC(c, hipMemcpyAsync(&p0, c->probe, sizeof(cf), hipMemcpyDeviceToHost, c->stream));
-        HIPC(c, hipStreamSynchronize(c->stream));
+        std::complex<double> px[2];     // corner pixel of batch element 0: scattered part of psi_S and of the probe
+        if ((r = conv_corner(c, {c->bufB, c->probe}, px))) return r;
         const std::complex<double> aS = c->a0 * std::pow(c->ksum, c->S);
-        const std::complex<double> sd = (c->a0 + std::complex<double>(p0.x, p0.y)) / (aS + std::complex<double>(e0.x, e0.y));
+        const std::complex<double> sd = (c->a0 + px[1]) / (aS + px[0]);
         std::complex<double> A = sd * aS;
         if (c->det_mode == BDOF_DET_NEAR) A *= c->hdet00;
         set_carrier(det, A);
@@ -2949,27 +2961,13 @@ int bdof_loss_grad_conv(bdof_ctx* c, int B, const int* angle_of_b, const int* xo
         npart = egrid;
         gp = c->bufA;
     } else {
-        const ConvFinalArgs fa = conv_final_args(c, B, c->bufB, c->bufA, split);
-        hipLaunchKernelGGL((k_conv_final<0>), dim3(egrid), dim3(256), 0, c->stream, fa);
-        const Group all = whole(c, B);
-        launch_real_to_hyb(c, all, c->bufA, c->bufC);
-        if (c->det_mode == BDOF_DET_NEAR) {
-            // the detector step and its adjoint take copy 0 of the dithered constants, whatever ran on the ctx before
-            launch_row_prop(c, all, c->bufC, c->bufA, c->hdet, 1.f, 0, 0);                                  // d_hat (L1)
-            npart = launch_loss_real(c, all, det, c->bufA, c->bufC, true, (cf*)out_wave, meas, 1.f, 1.f);
-            launch_row_prop(c, all, c->bufC, c->bufA, c->hdet, 1.f, 1, 0);                                  // g_hat(q) (L1)
-        } else {
-            npart = launch_loss_far(c, all, det, c->bufC, c->bufA, (cf*)out_wave, meas, 1.f, 1.f);        // g_hat(q) (L1)
-        }
-        launch_loss_real(c, all, DetPlane{}, c->bufA, nullptr, false, c->bufC, nullptr, 1.f, 1.f);        // G(q), real space
-        hipLaunchKernelGGL(k_conv_scale_seed, dim3(egrid), dim3(256), 0, c->stream, c->bufC, c->conv_scal, n);
-        gp = c->bufC;
+        npart = conv_detector(c, B, det, meas, (cf*)out_wave, &gp);
     }
     hipLaunchKernelGGL(k_conv_finish, dim3(1), dim3(256), 0, c->stream, c->partial, npart, 2, 1.0 / ((double)B * c->NX * c->NY),
                        seed_scale, c->loss_dev, gp, c->conv_scal);
     // backward sweep, in the same sub-batches
     Split groups;
-    if ((r = groups.open(c, B, (c->NX / 32) * (c->NY / 32), 2))) return r;
+    if ((r = conv_split(c, B, &groups))) return r;
     for (const Group& g : groups) {
         const size_t off = (size_t)g.b0 * plane;
         const ObjView gobj = sub_obj(c, g);
@@ -2987,9 +2985,7 @@ int bdof_loss_grad_conv(bdof_ctx* c, int B, const int* angle_of_b, const int* xo
 }
 
 int bdof_enable_probe_grad(bdof_ctx* c, int enable) {
-    if (!c) return BDOF_ERR_ARG;
-    if (int r = need_configured(c)) return r;
-    HIPC(c, hipSetDevice(c->device));
+    if (int r = enter_setter(c, false)) return r;
     if (enable && !c->gpsi0) {
         if (!c->with_grad) return fail(c, BDOF_ERR_STATE, "the probe gradient needs bdof_configure(with_grad=1)");
         HIPC(c, c->gpsi0.alloc((size_t)c->Bmax * c->NX * c->NY));
@@ -2997,7 +2993,7 @@ int bdof_enable_probe_grad(bdof_ctx* c, int enable) {
         HIPC(c, hipStreamSynchronize(c->stream));
         c->gpsi0.reset();
     }
-    c->gpsi_src = nullptr;
+    changed(c, PROBE_GRADIENT_GONE);
     return 0;
 }
 
@@ -3133,8 +3129,7 @@ int bdof_adam_step_slab(bdof_ctx* c, const void* x_old, void* x_new, const void*
     const AdamArgs a = adam_args(x_old, x_new, g, m, v, mask, NXv, NZv, NYv, g_scale, alpha_d, alpha_b, gamma, lr, b1, b2, eps, i_batch, clip,
                                  x0, nx);
     const size_t n = (size_t)nx * NZv * NYv;
-    size_t need = (n + 255) / 256;
-    int grid = need < (size_t)c->ncu * 16 ? (int)need : c->ncu * 16;
+    int grid = g_elem_grid(c, n);
     grid = (grid + 7) / 8 * 8;                       // k_adam deals the range to the 8 XCDs by blockIdx % 8
     hipLaunchKernelGGL(k_adam, dim3(grid), dim3(256), 0, c->stream, a);
     return launched(c);
@@ -3178,9 +3173,7 @@ int bdof_rotation_adjoint_adam(bdof_ctx* c, int B, const int* angle_of_b, void* 
     const size_t mean_at = (size_t)c->adj_ndest + n_chunks;
     if (mean) HIPC(c, c->cbar_dev.room(std::max((size_t)c->ncu * 16, mean_at) + 1));
     // c->mod stops being the bound object's table here
-    c->mod_dirty = true;
-    c->mod_mean_pending = false;
-    c->mod_for = nullptr;
+    changed(c, CHANGED_MOD_OVERWRITTEN);
     ProfScope ps(c, BDOF_K_ROT_ADJ, c->stream);
     RotAdjK<true> a;
     static_cast<RotAdjArgs&>(a) = RotAdjArgs{c->grot, (float2*)gvol, c->adj_off, c->adj_order, angle_of_b, B, c->S * c->NX, c->adj_ndest, c->NY,
@@ -3222,16 +3215,14 @@ int bdof_rotate_bilinear(bdof_ctx* c, const void* vol, int NXv, int NZv, int NYv
 int bdof_set_object_bilinear(bdof_ctx* c, const void* vol, int NXv, int NZv, int NYv, const double* prm, int B, int conv) {
     if (int r = admit(c, "bdof_set_object_bilinear", CARRIES_PLANES | NO_DATA_TERM)) return r;
     if (!c || !vol || !prm || B < 1) return BDOF_ERR_ARG;
-    if (int r = need_configured(c)) return r;
+    int r = enter_setter(c, false);
+    if (r) return r;
     if (NXv < 1 || NZv < 1 || NYv < 2 || NYv % 2) return fail(c, BDOF_ERR_SIZE, "bdof_set_object_bilinear needs an even NY");
     if (NYv != c->NY || NXv != c->NX || NZv != c->S) return fail(c, BDOF_ERR_ARG, "the volume must be (NX, S, NY) of the configured wavefields");
     if (B > c->Bmax) return fail(c, BDOF_ERR_ARG, "batch size outside [1, Bmax]");
     if (conv && !c->have_conv) return fail(c, BDOF_ERR_STATE, "bdof_set_conv has not been called");
-    HIPC(c, hipSetDevice(c->device));
     const size_t nrows = (size_t)B * NZv * NXv, n = nrows * NYv;
     // set the binding first: want_cbar looks at the physics and probe only
-    c->mod_for = nullptr;
-    c->mod_mean_pending = false;
     c->obj_src = nullptr;
     c->obj_bound_mod = true;
     c->obj_rows = nrows;
@@ -3241,9 +3232,9 @@ int bdof_set_object_bilinear(bdof_ctx* c, const void* vol, int NXv, int NZv, int
     c->obj.S = c->S;
     c->n_angles = 0;
     c->k = conv ? c->k_conv : c->k_fft;
+    changed(c, CHANGED_OBJECT);
     const bool mean = want_cbar(c);
-    int r = modulation_room(c, n, mean);
-    if (r) return r;
+    if ((r = modulation_room(c, n, mean))) return r;
     RotBilinArgs a{(const float2*)vol, c->mod, nullptr, (const double4*)prm, B, NXv, NZv, NYv, 0, 0, 0, 1.f};
     const int grid = (int)std::min<size_t>((nrows + 3) / 4, (size_t)c->ncu * 16);
     hipLaunchKernelGGL((k_rot_bilinear<true>), dim3(grid), dim3(256), 0, c->stream, a, c->k, mean ? c->cbar_dev : (double2*)nullptr);
@@ -3291,9 +3282,7 @@ void* bdof_stream(bdof_ctx* c) { return c ? (void*)c->stream : nullptr; }
 int bdof_mask_shrink(bdof_ctx* c, const void* x, float* mask, size_t n, float thresh) {
     if (!c || !x || !mask) return BDOF_ERR_ARG;
     HIPC(c, hipSetDevice(c->device));
-    size_t need = (n + 255) / 256;
-    int grid = need < (size_t)c->ncu * 16 ? (int)need : c->ncu * 16;
-    hipLaunchKernelGGL(k_mask_shrink, dim3(grid), dim3(256), 0, c->stream, (const float2*)x, mask, n, thresh);
+    hipLaunchKernelGGL(k_mask_shrink, dim3(g_elem_grid(c, n)), dim3(256), 0, c->stream, (const float2*)x, mask, n, thresh);
     return launched(c);
 }
 
