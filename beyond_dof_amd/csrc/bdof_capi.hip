@@ -773,6 +773,18 @@ static int fused_mode(const bdof_ctx* c) {
     if (c->S < 4 || (c->S & 1) || c->NX > 512 || c->NY > 512) return 0;
     return 1;
 }
+// The two steps of a slice kernel on x-lines (hx, twX) or y-lines (hy, twY): twiddles, h and sqrt(1/2) of copy `lead` of every
+// dithered constant for the leading step, of copy `trail` for the trailing one.
+static LineSteps line_steps(bdof_ctx* c, bool x_lines, unsigned lead, unsigned trail) {
+    const int N = x_lines ? c->NX : c->NY;
+    const cf* tw = x_lines ? c->twX : c->twY;
+    const cf* h = x_lines ? c->hx_d : c->hy_d;
+    const unsigned D = (unsigned)c->sep_copies;
+    LineSteps s{tw_of(c, tw, N, lead), tw_of(c, tw, N, trail), h + (size_t)(lead % D) * N, h + (size_t)(trail % D) * N};
+    sq_of(c, lead, s.sq_lead);
+    sq_of(c, trail, s.sq_trail);
+    return s;
+}
 // Slice z of the fused forward sweep: even z on y-lines ([b][x][y] -> [b][y][x]), odd z on x-lines (back); phi_z goes to `phi`.
 // The leading step takes copy z-1 of every dithered constant, the trailing one copy z.
 // blk (the fused adjoint sweep will read the tape): an odd slot takes the tile-block layout of k_slice_x<BLK>.
@@ -780,13 +792,8 @@ static void launch_slice(bdof_ctx* c, const Group& g, int z, const cf* in, cf* o
     ProfScope ps(c, BDOF_K_ROW_FWD, g.st, true);
     const bool xl = (z & 1) != 0;
     const int N = xl ? c->NX : c->NY, R = xl ? c->NY : c->NX;
-    const cf* tw = xl ? c->twX : c->twY;
-    const cf* h = xl ? c->hx_d : c->hy_d;
-    const unsigned lead = (unsigned)(z > 0 ? z - 1 : 0), trail = (unsigned)z, D = (unsigned)c->sep_copies;
     SliceArgs a{sub_field(c, g, in), c->probe, sub_field(c, g, out), sub_field(c, g, phi), sub_obj(c, g), g.B, R, z, carrier_at(c, z), cshift_at(c, z),
-                tw_of(c, tw, N, lead), tw_of(c, tw, N, trail), h + (size_t)(lead % D) * N, h + (size_t)(trail % D) * N};
-    sq_of(c, lead, a.sq_lead);
-    sq_of(c, trail, a.sq_trail);
+                line_steps(c, xl, (unsigned)(z > 0 ? z - 1 : 0), (unsigned)z)};
     if (xl) {
         DISPATCH_N_512(N, with_bool(blk, [&](auto BLK) {
             BDOF_LAUNCH(ps, (k_slice_x<N_, BLK>), dim3(rows_grid<N_>(c, g.B, R)), dim3(BDOF_THREADS), 0, g.st, a);
@@ -805,13 +812,8 @@ static void launch_slice_adj(bdof_ctx* c, const Group& g, int z, const cf* in, c
     ProfScope ps(c, BDOF_K_ROW_BWD, g.st, true);
     const bool xl = (z & 1) != 0;
     const int N = xl ? c->NX : c->NY, R = xl ? c->NY : c->NX;
-    const cf* tw = xl ? c->twX : c->twY;
-    const cf* h = xl ? c->hx_d : c->hy_d;
-    const unsigned lead = (unsigned)z, trail = (unsigned)(z > 0 ? z - 1 : 0), D = (unsigned)c->sep_copies;
     SliceAdjArgs a{sub_field(c, g, in), sub_field(c, g, phi), sub_field(c, g, out), c->grot + (size_t)g.b0 * c->S * c->NX * c->NY, sub_obj(c, g), g.B, R, z,
-                   c->k, carrier_phi_at(c, z), tw_of(c, tw, N, lead), tw_of(c, tw, N, trail), h + (size_t)(lead % D) * N, h + (size_t)(trail % D) * N};
-    sq_of(c, lead, a.sq_lead);
-    sq_of(c, trail, a.sq_trail);
+                   c->k, carrier_phi_at(c, z), line_steps(c, xl, (unsigned)z, (unsigned)(z > 0 ? z - 1 : 0))};
     if (xl) {
         DISPATCH_N_512(N, BDOF_LAUNCH(ps, (k_slice_x_adj<N_>), dim3(rows_grid<N_>(c, g.B, R)), dim3(BDOF_THREADS), 0, g.st, a));
     } else {

@@ -126,11 +126,12 @@ template <int N> struct FftTw {
     const float* sq = nullptr;      // dithered sqrt(1/2) of this launch (mul_sqrt_half); nullptr: the compiled-in constants
 
     // table[j] = exp(-2 pi i j / N), j in [0, N).  Must be called by every thread of the workgroup.
-    // lds_mid: LDS_CNT slots; lds_tail: 7*N/8 slots laid out [m-1][j] = table[m*j] (also the tail stage's twiddles):
-    // one cooperative fill, one barrier, and the per-lane last-stage factors are read back from LDS instead of being
-    // gathered from global memory by every wave (kernel start-up is amortised over only ~2 tiles per workgroup).
+    // lds_mid: LDS_CNT slots; lds_tail: 7*N/8 slots laid out [m-1][j] = table[m*j] (also the tail stage's twiddles).
+    // The cooperative fill alone, without the barrier and the per-lane part of load: the slice kernels fill the sets of both
+    // their steps in front of ONE barrier (a workgroup runs two tiles: every round trip at its start counts) and point tw
+    // at one of them per step (tw_select, bdof_kernels.h).
     template <bool LO = false>
-    __device__ __forceinline__ void load(const cf* __restrict__ table, int tid, cf* lds_mid, cf* lds_tail) {
+    static __device__ __forceinline__ void fill(const cf* __restrict__ table, cf* lds_mid, cf* lds_tail) {
         constexpr int T = N / 8;
         for (int e = threadIdx.x; e < 7 * T; e += blockDim.x) {
             const int m = e / T + 1, j = e - (m - 1) * T;
@@ -144,6 +145,13 @@ template <int N> struct FftTw {
             lds_mid[e] = table[m * k * step];
             if constexpr (LO) lds_mid[LDS_CNT + e] = table[N + m * k * step];
         }
+    }
+    // One cooperative fill, one barrier, and the per-lane last-stage factors are read back from LDS instead of being
+    // gathered from global memory by every wave (kernel start-up is amortised over only ~2 tiles per workgroup).
+    template <bool LO = false>
+    __device__ __forceinline__ void load(const cf* __restrict__ table, int tid, cf* lds_mid, cf* lds_tail) {
+        constexpr int T = N / 8;
+        fill<LO>(table, lds_mid, lds_tail);
         mid = lds_mid;
         tail = lds_tail;
         __syncthreads();

@@ -10,6 +10,11 @@
 // stage of each kernel's final FFT is executed with a transposed thread mapping (16 rows x N/8
 // butterflies), so the transposition costs no extra LDS pass and only one workgroup barrier per
 // 16-row tile, and the stores are 128-byte segments.  B's output is directly the tape entry.
+// What the row kernels share is stated once: the tile and transposed index maps (tile_at, transposed_at), the transposed tails
+// (transposed_tail, transposed_tail_mul), the object access (ObjView, load_obj_row), the transform constants (FftTw::load, and
+// FftTw::fill + tw_select for the two steps of a slice kernel) and, for the slice kernels, their two steps' constants (LineSteps).
+// The 8-point row access, the separable step and the gradient point are spelt out in each kernel: as functions they change the
+// kernels' registers, scratch or instruction counts under hipcc (MEASUREMENTS.md, "Row kernels: what can be stated once").
 // The fused forward sweep of bdof_loss_grad (k_slice_y / k_slice_x, below A') replaces A + B by one kernel per slice that works
 // on lines of one direction, through the separable Fresnel step; between its kernels the field is in real space, [b][x][y] or
 // [b][y][x], and the tape holds phi_z:                                                                              32 B/px
@@ -57,6 +62,24 @@ template <int T> struct RowLds {
 };
 
 // ---------------------------------------------------------------------------------------------
+// The two index maps of the skeleton the row kernels share.  A workgroup takes tiles of TILE rows; in the ROW mapping a row belongs
+// to T = N/8 lanes, lane tid holding its points tid + m T; in the TRANSPOSED mapping (last stage, tails) a thread holds the points
+// j + m T of row r of the tile, with its TILE neighbours along the tile's rows.
+// ---------------------------------------------------------------------------------------------
+// tile -> its first row among all B R rows, its wavefield, its first row within the wavefield
+struct TileAt { int row0, b, r0; };
+template <class C> __device__ __forceinline__ TileAt tile_at(int tile, int R) {
+    const int row0 = tile * C::TILE, b = row0 / R;
+    return {row0, b, row0 - b * R};
+}
+// transposed mapping of pass `pass`: q = j TILE + r
+struct TransposedAt { int q, r, j; };
+template <class C> __device__ __forceinline__ TransposedAt transposed_at(int pass) {
+    const int q = threadIdx.x + pass * BDOF_THREADS;
+    return {q, q % C::TILE, q / C::TILE};
+}
+
+// ---------------------------------------------------------------------------------------------
 // Transposed tail: last FFT stage of the TILE rows whose images are in `smem`, then
 //   dst[(pos) * ld + r] = scale * out(row r, position pos),  pos = j + q*T
 // Called by all threads between two workgroup barriers.
@@ -66,8 +89,7 @@ __device__ __forceinline__ void transposed_tail(cf* smem, cf* __restrict__ dst, 
     typedef RowCfg<N> C;
 #pragma nounroll
     for (int pass = 0; pass < C::PASSES; ++pass) {
-        const int q = threadIdx.x + pass * BDOF_THREADS;
-        const int r = q % C::TILE, j = q / C::TILE;
+        const auto [q, r, j] = transposed_at<C>(pass);
         RowLds<C::T> lds{smem + r * C::RS};
         cf u[8];
         last_stage<N, SIGN, ROUND, EX>(u, j, lds, tail, sq);
@@ -289,8 +311,7 @@ __global__ __launch_bounds__(BDOF_THREADS, RowCfg<NY>::MIN_WAVES) void k_row_fwd
     tw.sq = a.sq;
     const int ntiles = a.B * a.NX / C::TILE;
     for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        const int row0 = tile * C::TILE;
-        const int b = row0 / a.NX, x0 = row0 - b * a.NX;
+        const auto [row0, b, x0] = tile_at<C>(tile, a.NX);
         const int y0 = a.obj.yoff ? a.obj.yoff[b] : 0;
 #pragma nounroll
         for (int pass = 0; pass < C::PASSES; ++pass) {
@@ -378,8 +399,7 @@ __global__ __launch_bounds__(BDOF_THREADS, RowCfg<NX>::MIN_WAVES) void k_row_pro
     tw.sq = a.sq;
     const int ntiles = a.B * a.NY / C::TILE;
     for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        const int row0 = tile * C::TILE;
-        const int b = row0 / a.NY, ky0 = row0 - b * a.NY;
+        const auto [row0, b, ky0] = tile_at<C>(tile, a.NY);
 #pragma nounroll
         for (int pass = 0; pass < C::PASSES; ++pass) {
             const int r = pass * C::RPP + rl;
@@ -439,8 +459,7 @@ __global__ __launch_bounds__(BDOF_THREADS, RowCfg<NX>::MIN_WAVES) void k_row_pro
     tw.sq = a.sq;
     const int ntiles = a.B * a.NY / C::TILE;
     for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        const int row0 = tile * C::TILE;
-        const int b = row0 / a.NY, ky0 = row0 - b * a.NY;
+        const auto [row0, b, ky0] = tile_at<C>(tile, a.NY);
         cf s[8];
         if constexpr (HOLD) {
             RowLds<C::T> lds{smem + rl * C::RS};
@@ -494,8 +513,7 @@ __global__ __launch_bounds__(BDOF_THREADS, RowCfg<NX>::MIN_WAVES) void k_row_pro
     tw.sq = a.sq;
     const int ntiles = a.B * a.NY / C::TILE;
     for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        const int row0 = tile * C::TILE;
-        const int b = row0 / a.NY, ky0 = row0 - b * a.NY;
+        const auto [row0, b, ky0] = tile_at<C>(tile, a.NY);
 #pragma nounroll
         for (int pass = 0; pass < C::PASSES; ++pass) {
             const int r = pass * C::RPP + rl;
@@ -764,7 +782,7 @@ __global__ __launch_bounds__(BDOF_THREADS, RowCfg<N>::MIN_WAVES) void k_row_loss
     const int ntiles = a.B * a.R / C::TILE;
     double acc = 0.0, acc2 = 0.0;
     for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        const int row0 = tile * C::TILE;
+        const int row0 = tile * C::TILE;          // (tile_at, spelt out: through the helper hipcc orders these kernels' instructions differently)
         const int b = row0 / a.R, r0 = row0 - b * a.R;
         size_t fields = 1, tile_off = 0;  // PL: fields from one wavefield of the launch to the next; the tile's first row in in / out_wave / meas
         if constexpr (PL) { fields = (size_t)a.fstride; tile_off = ((size_t)b * fields * a.R + r0) * N; }
@@ -922,7 +940,7 @@ __global__ __launch_bounds__(BDOF_THREADS, RowCfg<NY>::MIN_WAVES) void k_row_bwd
     tw.sq = BIN ? sq_bin : a.sq;
     const int ntiles = a.B * a.NX / C::TILE;
     for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        const int row0 = tile * C::TILE;
+        const int row0 = tile * C::TILE;          // (tile_at, spelt out: through the helper the HIST 2 instances change their scalar arithmetic)
         const int b = row0 / a.NX, x0 = row0 - b * a.NX;
         const int y0 = a.obj.yoff ? a.obj.yoff[b] : 0;
         cf gam = make_float2(0.f, 0.f), t0 = make_float2(0.f, 0.f);
@@ -1010,6 +1028,16 @@ __global__ __launch_bounds__(BDOF_THREADS, RowCfg<NY>::MIN_WAVES) void k_row_bwd
 // Every transform takes the dithered constants of the step it belongs to (twiddles, sqrt(1/2), hx / hy): copy z-1 for the
 // leading step, copy z for the trailing one.  32 B per pixel (8 in + 8 table + 8 phi + 8 out) where A + B move 40.
 // ---------------------------------------------------------------------------------------------
+// The two separable steps a slice kernel belongs to, each with the copy of every dithered constant of its own slice step (the
+// host fills it: line_steps, bdof_capi.hip).  The last member of SliceArgs and SliceAdjArgs.
+struct LineSteps {
+    const cf* tw_lead;   // twiddle table of the line length, copy of the leading step ...
+    const cf* tw_trail;  // ... and of the trailing one
+    const cf* h_lead;    // hx (x-line kernels) or hy (y-line kernels) of the leading step, normalisation folded in ...
+    const cf* h_trail;   // ... and of the trailing one (the adjoint kernels conjugate both)
+    float sq_lead[2], sq_trail[2];
+};
+
 struct SliceArgs {
     const cf* in;        // k_slice_y: [B][NX][NY]; k_slice_x: [B][NY][NX]; real space, scattered part
     const cf* probe;     // k_slice_y<FIRST>: [NX][NY]
@@ -1019,12 +1047,9 @@ struct SliceArgs {
     int B, R, z;         // R: lines per wavefield (k_slice_y: NX, k_slice_x: NY)
     cf carrier;          // a_z
     cf cshift;           // a_z (cbar - 1)
-    const cf* tw_lead;   // twiddle table of the line length, copy of step z-1 ...
-    const cf* tw_trail;  // ... and of step z
-    const cf* h_lead;    // hx (k_slice_x) or hy (k_slice_y) of step z-1, normalisation folded in ...
-    const cf* h_trail;   // ... and of step z
-    float sq_lead[2], sq_trail[2];
+    LineSteps steps;     // lead: step z-1, trail: step z
 };
+static_assert(offsetof(SliceArgs, steps) == 120 && sizeof(SliceArgs) == 168, "SliceArgs: the byte layout it had with the six members spelt out");
 
 // transposed_tail with a factor per position: dst[pos * ld + r] = h[pos] * out(row r, position pos)
 template <int N, int SIGN, int ROUND = 1>
@@ -1032,8 +1057,7 @@ __device__ __forceinline__ void transposed_tail_mul(cf* smem, cf* __restrict__ d
     typedef RowCfg<N> C;
 #pragma nounroll
     for (int pass = 0; pass < C::PASSES; ++pass) {
-        const int q = threadIdx.x + pass * BDOF_THREADS;
-        const int r = q % C::TILE, j = q / C::TILE;
+        const auto [q, r, j] = transposed_at<C>(pass);
         RowLds<C::T> lds{smem + r * C::RS};
         cf u[8], hv[8];
 #pragma unroll
@@ -1069,26 +1093,10 @@ __device__ __forceinline__ int obj_rows_rel(const ObjRows r, int x) {
     return x <= r.xmax ? s + (x & ~r.mask) : -1;
 }
 
-// The tables of a transform's constants into LDS without the barrier and the per-lane part of FftTw::load: the slice kernels fill
-// the sets of both their steps in front of ONE barrier (a workgroup runs two tiles: every round trip at its start counts).
-template <int N> __device__ __forceinline__ void tw_fill(const cf* __restrict__ table, cf* lds_mid, cf* lds_tail) {
-    typedef FftTw<N> TW;
-    constexpr int T = N / 8;
-    for (int e = threadIdx.x; e < 7 * T; e += blockDim.x) {
-        const int m = e / T + 1, j = e - (m - 1) * T;
-        lds_tail[e] = table[m * j];
-    }
-    for (int e = threadIdx.x; e < TW::M1_CNT + TW::M2_CNT; e += blockDim.x) {
-        int k, m, step;
-        if (e < TW::M1_CNT) { k = e / TW::D1; m = e % TW::D1 + 1; step = N / (TW::M1_P * TW::M1_R); }
-        else { const int f = e - TW::M1_CNT; k = f / TW::D2; m = f % TW::D2 + 1; step = N / (TW::M2_P * TW::M2_R); }
-        lds_mid[e] = table[m * k * step];
-    }
-}
-
-// Point tw at the constants of one of the two steps a slice kernel belongs to (both sets are in LDS).  The lane's last-stage
-// twiddles are re-read from LDS at every switch — behind a compiler barrier, or hipcc hoists the loads out of the tile loop and
-// keeps both sets, 28 registers, live through the kernel (measured: 356 bytes of scratch in k_slice_x<512>).
+// Point tw at the constants of one of the two steps a slice kernel belongs to (both sets are in LDS: FftTw::fill, in front of ONE
+// barrier — a workgroup runs two tiles, every round trip at its start counts).  The lane's last-stage twiddles are re-read from
+// LDS at every switch — behind a compiler barrier, or hipcc hoists the loads out of the tile loop and keeps both sets, 28
+// registers, live through the kernel (measured: 356 bytes of scratch in k_slice_x<512>).
 template <int N> __device__ __forceinline__ void tw_select(FftTw<N>& tw, const cf* mid, const cf* tail, const float* sq, int tid) {
     asm volatile("" ::: "memory");
     tw.mid = mid;
@@ -1105,16 +1113,15 @@ __global__ __launch_bounds__(BDOF_THREADS, RowCfg<NY>::MIN_WAVES) void k_slice_y
     __shared__ cf smem_tw[2][FftTw<NY>::LDS_CNT];
     __shared__ cf smem_tail[2][7 * C::T];
     const int tid = threadIdx.x % C::T, rl = threadIdx.x / C::T;
-    const float sql[2] = {a.sq_lead[0], a.sq_lead[1]}, sqt[2] = {a.sq_trail[0], a.sq_trail[1]};     // copies: no pointer into the argument block
+    const float sql[2] = {a.steps.sq_lead[0], a.steps.sq_lead[1]}, sqt[2] = {a.steps.sq_trail[0], a.steps.sq_trail[1]};     // copies: no pointer into the argument block
     FftTw<NY> tw;
-    if constexpr (!FIRST) tw_fill<NY>(a.tw_lead, smem_tw[0], smem_tail[0]);
-    tw_fill<NY>(a.tw_trail, smem_tw[1], smem_tail[1]);
+    if constexpr (!FIRST) FftTw<NY>::fill(a.steps.tw_lead, smem_tw[0], smem_tail[0]);
+    FftTw<NY>::fill(a.steps.tw_trail, smem_tw[1], smem_tail[1]);
     __syncthreads();
     const int NX = a.R;
     const int ntiles = a.B * NX / C::TILE;
     for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        const int row0 = tile * C::TILE;
-        const int b = row0 / NX, x0 = row0 - b * NX;
+        const auto [row0, b, x0] = tile_at<C>(tile, NX);
 #pragma nounroll
         for (int pass = 0; pass < C::PASSES; ++pass) {
             const int r = pass * C::RPP + rl;
@@ -1128,7 +1135,7 @@ __global__ __launch_bounds__(BDOF_THREADS, RowCfg<NY>::MIN_WAVES) void k_slice_y
             load_obj_row(a.obj, obj_src_row(a.obj, b, x, a.z, NX), 0, tid, C::T, db);
             if constexpr (!FIRST) {                       // Py of step z-1
 #pragma unroll
-                for (int m = 0; m < 8; ++m) hv[m] = a.h_lead[tid + m * C::T];
+                for (int m = 0; m < 8; ++m) hv[m] = a.steps.h_lead[tid + m * C::T];
                 tw_select(tw, smem_tw[0], smem_tail[0], sql, tid);
                 line_fft<NY, -1, 1, false>(u, tw, tid, lds);
 #pragma unroll
@@ -1145,7 +1152,7 @@ __global__ __launch_bounds__(BDOF_THREADS, RowCfg<NY>::MIN_WAVES) void k_slice_y
                 line_fft_partial<NY, -1, 1, false>(u, tw, tid, lds);
             } else {                                      // Py of step z
 #pragma unroll
-                for (int m = 0; m < 8; ++m) hv[m] = a.h_trail[tid + m * C::T];
+                for (int m = 0; m < 8; ++m) hv[m] = a.steps.h_trail[tid + m * C::T];
                 line_fft<NY, -1, 1, false>(u, tw, tid, lds);
 #pragma unroll
                 for (int m = 0; m < 8; ++m) u[m] = cmul(u[m], hv[m]);
@@ -1154,7 +1161,7 @@ __global__ __launch_bounds__(BDOF_THREADS, RowCfg<NY>::MIN_WAVES) void k_slice_y
         }
         __syncthreads();
         cf* dst = a.out + (size_t)b * NY * NX + x0;
-        if constexpr (TAIL) transposed_tail_mul<NY, -1, 1>(smem, dst, NX, a.h_trail, smem_tail[1], sqt);
+        if constexpr (TAIL) transposed_tail_mul<NY, -1, 1>(smem, dst, NX, a.steps.h_trail, smem_tail[1], sqt);
         else transposed_tail<NY, +1, 2, false>(smem, dst, NX, 1.f, smem_tail[1], sqt);
         __syncthreads();
     }
@@ -1171,18 +1178,17 @@ __global__ __launch_bounds__(BDOF_THREADS, RowCfg<NX>::MIN_WAVES) void k_slice_x
     __shared__ cf smem_tw[2][FftTw<NX>::LDS_CNT];
     __shared__ cf smem_tail[2][7 * C::T];
     const int tid = threadIdx.x % C::T, rl = threadIdx.x / C::T;
-    const float sql[2] = {a.sq_lead[0], a.sq_lead[1]}, sqt[2] = {a.sq_trail[0], a.sq_trail[1]};
+    const float sql[2] = {a.steps.sq_lead[0], a.steps.sq_lead[1]}, sqt[2] = {a.steps.sq_trail[0], a.steps.sq_trail[1]};
     __shared__ int s_src[NX];                             // source row of every x of the tile's wavefield at this slice (less plain0)
     FftTw<NX> tw;
-    tw_fill<NX>(a.tw_lead, smem_tw[0], smem_tail[0]);
-    tw_fill<NX>(a.tw_trail, smem_tw[1], smem_tail[1]);
+    FftTw<NX>::fill(a.steps.tw_lead, smem_tw[0], smem_tail[0]);
+    FftTw<NX>::fill(a.steps.tw_trail, smem_tw[1], smem_tail[1]);
     __syncthreads();
     const ObjView o = a.obj;                              // by value (load_obj_row_bin)
     const int NY = a.R;
     const int ntiles = a.B * NY / C::TILE;
     for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        const int row0 = tile * C::TILE;
-        const int b = row0 / NY, y0 = row0 - b * NY;
+        const auto [row0, b, y0] = tile_at<C>(tile, NY);
         const ObjRows rows = obj_rows_of(o, b, a.z, NX);
         cf* const pdst = a.phi_out + (BLK ? (size_t)row0 * NX : (size_t)b * NX * NY);      // BLK: the tile's block (row0 = b NY + y0)
         // The rotation lookup of the tile, one x per thread, on its way while the first phase runs; it goes through LDS to the
@@ -1198,7 +1204,7 @@ __global__ __launch_bounds__(BDOF_THREADS, RowCfg<NX>::MIN_WAVES) void k_slice_x
 #pragma unroll
             for (int m = 0; m < 8; ++m) u[m] = src[tid + m * C::T];
 #pragma unroll
-            for (int m = 0; m < 8; ++m) hv[m] = a.h_lead[tid + m * C::T];
+            for (int m = 0; m < 8; ++m) hv[m] = a.steps.h_lead[tid + m * C::T];
             tw_select(tw, smem_tw[0], smem_tail[0], sql, tid);
             line_fft<NX, -1, 1, false>(u, tw, tid, lds);
 #pragma unroll
@@ -1213,8 +1219,7 @@ __global__ __launch_bounds__(BDOF_THREADS, RowCfg<NX>::MIN_WAVES) void k_slice_x
         cf v[C::PASSES][8];
 #pragma unroll
         for (int pass = 0; pass < C::PASSES; ++pass) {
-            const int q = threadIdx.x + pass * BDOF_THREADS;
-            const int r = q % C::TILE, j = q / C::TILE;
+            const auto [q, r, j] = transposed_at<C>(pass);
             RowLds<C::T> lds{smem + r * C::RS};
             // lookups and table loads first, unconditional and clamped (load_obj_row), consumed after the last stage
             const int yg = y0 + r, yc = min(max(yg, 0), o.volNY - 1);
@@ -1239,8 +1244,7 @@ __global__ __launch_bounds__(BDOF_THREADS, RowCfg<NX>::MIN_WAVES) void k_slice_x
         __syncthreads();
 #pragma unroll
         for (int pass = 0; pass < C::PASSES; ++pass) {
-            const int q = threadIdx.x + pass * BDOF_THREADS;
-            const int r = q % C::TILE, j = q / C::TILE;
+            const auto [q, r, j] = transposed_at<C>(pass);
             RowLds<C::T> lds{smem + r * C::RS};
             stage_write<NX, P::R0, 1>(v[pass], j, lds);
         }
@@ -1252,7 +1256,7 @@ __global__ __launch_bounds__(BDOF_THREADS, RowCfg<NX>::MIN_WAVES) void k_slice_x
             RowLds<C::T> lds{smem + r * C::RS};
             cf u[8], hv[8];
 #pragma unroll
-            for (int m = 0; m < 8; ++m) hv[m] = a.h_trail[tid + m * C::T];
+            for (int m = 0; m < 8; ++m) hv[m] = a.steps.h_trail[tid + m * C::T];
             tw_select(tw, smem_tw[1], smem_tail[1], sqt, tid);
             line_fft_rest<NX, -1, 1, false>(u, tw, tid, lds);
 #pragma unroll
@@ -1291,12 +1295,9 @@ struct SliceAdjArgs {
     int B, R, z;         // R: lines per wavefield (k_slice_y_adj: NX, k_slice_x_adj: NY)
     float k;
     cf carrier_phi;      // cbar a_z: constant part of phi_z
-    const cf* tw_lead;   // twiddle table of the line length, copy of step z ...
-    const cf* tw_trail;  // ... and of step z-1
-    const cf* h_lead;    // hx (k_slice_x_adj) or hy (k_slice_y_adj) of step z (conjugated in the kernel) ...
-    const cf* h_trail;   // ... and of step z-1
-    float sq_lead[2], sq_trail[2];
+    LineSteps steps;     // lead: step z, trail: step z-1, both conjugated in the kernel
 };
+static_assert(offsetof(SliceAdjArgs, steps) == 112 && sizeof(SliceAdjArgs) == 160, "SliceAdjArgs: the byte layout it had with the six members spelt out");
 
 template <int NY, bool HEAD, bool LAST>
 __global__ __launch_bounds__(BDOF_THREADS, RowCfg<NY>::MIN_WAVES) void k_slice_y_adj(SliceAdjArgs a) {
@@ -1305,16 +1306,15 @@ __global__ __launch_bounds__(BDOF_THREADS, RowCfg<NY>::MIN_WAVES) void k_slice_y
     __shared__ cf smem_tw[2][FftTw<NY>::LDS_CNT];
     __shared__ cf smem_tail[2][7 * C::T];
     const int tid = threadIdx.x % C::T, rl = threadIdx.x / C::T;
-    const float sql[2] = {a.sq_lead[0], a.sq_lead[1]}, sqt[2] = {a.sq_trail[0], a.sq_trail[1]};     // copies: no pointer into the argument block
+    const float sql[2] = {a.steps.sq_lead[0], a.steps.sq_lead[1]}, sqt[2] = {a.steps.sq_trail[0], a.steps.sq_trail[1]};     // copies: no pointer into the argument block
     FftTw<NY> tw;
-    tw_fill<NY>(a.tw_lead, smem_tw[0], smem_tail[0]);
-    if constexpr (!LAST) tw_fill<NY>(a.tw_trail, smem_tw[1], smem_tail[1]);
+    FftTw<NY>::fill(a.steps.tw_lead, smem_tw[0], smem_tail[0]);
+    if constexpr (!LAST) FftTw<NY>::fill(a.steps.tw_trail, smem_tw[1], smem_tail[1]);
     __syncthreads();
     const int NX = a.R;
     const int ntiles = a.B * NX / C::TILE;
     for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        const int row0 = tile * C::TILE;
-        const int b = row0 / NX, x0 = row0 - b * NX;
+        const auto [row0, b, x0] = tile_at<C>(tile, NX);
 #pragma nounroll
         for (int pass = 0; pass < C::PASSES; ++pass) {
             const int r = pass * C::RPP + rl;
@@ -1327,11 +1327,11 @@ __global__ __launch_bounds__(BDOF_THREADS, RowCfg<NY>::MIN_WAVES) void k_slice_y
             for (int m = 0; m < 8; ++m) g[m] = a.in[off + tid + m * C::T];
             if constexpr (!HEAD) {
 #pragma unroll
-                for (int m = 0; m < 8; ++m) hv[m] = a.h_lead[tid + m * C::T];
+                for (int m = 0; m < 8; ++m) hv[m] = a.steps.h_lead[tid + m * C::T];
             }
             // phi_z and the table row are asked for once hv is done with, and arrive under the inverse transform: all four rows in
             // flight at once spilled (12 .. 76 bytes of scratch in the plain instances)
-            auto load_phi_and_table = [&]() {
+            auto load_phi_and_table = [&, b = b]() {
 #pragma unroll
                 for (int m = 0; m < 8; ++m) p[m] = a.phi[off + tid + m * C::T];
                 load_obj_row(a.obj, obj_src_row(a.obj, b, x, a.z, NX), 0, tid, C::T, db);
@@ -1356,7 +1356,7 @@ __global__ __launch_bounds__(BDOF_THREADS, RowCfg<NY>::MIN_WAVES) void k_slice_y
             }
             if constexpr (!LAST) {                        // Py_{z-1}^H
 #pragma unroll
-                for (int m = 0; m < 8; ++m) hv[m] = a.h_trail[tid + m * C::T];
+                for (int m = 0; m < 8; ++m) hv[m] = a.steps.h_trail[tid + m * C::T];
                 tw_select(tw, smem_tw[1], smem_tail[1], sqt, tid);
                 line_fft<NY, -1, 1, false>(g, tw, tid, lds);
 #pragma unroll
@@ -1380,18 +1380,17 @@ __global__ __launch_bounds__(BDOF_THREADS, RowCfg<NX>::MIN_WAVES) void k_slice_x
     __shared__ cf smem_tw[2][FftTw<NX>::LDS_CNT];
     __shared__ cf smem_tail[2][7 * C::T];
     const int tid = threadIdx.x % C::T, rl = threadIdx.x / C::T;
-    const float sql[2] = {a.sq_lead[0], a.sq_lead[1]}, sqt[2] = {a.sq_trail[0], a.sq_trail[1]};
+    const float sql[2] = {a.steps.sq_lead[0], a.steps.sq_lead[1]}, sqt[2] = {a.steps.sq_trail[0], a.steps.sq_trail[1]};
     __shared__ int s_src[NX];                             // source row of every x of the tile's wavefield at this slice (less plain0)
     FftTw<NX> tw;
-    tw_fill<NX>(a.tw_lead, smem_tw[0], smem_tail[0]);
-    tw_fill<NX>(a.tw_trail, smem_tw[1], smem_tail[1]);
+    FftTw<NX>::fill(a.steps.tw_lead, smem_tw[0], smem_tail[0]);
+    FftTw<NX>::fill(a.steps.tw_trail, smem_tw[1], smem_tail[1]);
     __syncthreads();
     const ObjView o = a.obj;                              // by value (load_obj_row_bin)
     const int NY = a.R;
     const int ntiles = a.B * NY / C::TILE;
     for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        const int row0 = tile * C::TILE;
-        const int b = row0 / NY, y0 = row0 - b * NY;
+        const auto [row0, b, y0] = tile_at<C>(tile, NY);
         const ObjRows rows = obj_rows_of(o, b, a.z, NX);
         const cf* const psrc = a.phi + (size_t)row0 * NX;                              // the tile's block of the tape slot (k_slice_x<BLK>)
         float2* const gdst = a.grot + ((size_t)b * o.S + a.z) * NX * NY;
@@ -1406,7 +1405,7 @@ __global__ __launch_bounds__(BDOF_THREADS, RowCfg<NX>::MIN_WAVES) void k_slice_x
 #pragma unroll
             for (int m = 0; m < 8; ++m) u[m] = src[tid + m * C::T];
 #pragma unroll
-            for (int m = 0; m < 8; ++m) hv[m] = a.h_lead[tid + m * C::T];
+            for (int m = 0; m < 8; ++m) hv[m] = a.steps.h_lead[tid + m * C::T];
             tw_select(tw, smem_tw[0], smem_tail[0], sql, tid);
             line_fft<NX, -1, 1, false>(u, tw, tid, lds);
 #pragma unroll
@@ -1420,8 +1419,7 @@ __global__ __launch_bounds__(BDOF_THREADS, RowCfg<NX>::MIN_WAVES) void k_slice_x
         cf v[C::PASSES][8];
 #pragma unroll
         for (int pass = 0; pass < C::PASSES; ++pass) {
-            const int q = threadIdx.x + pass * BDOF_THREADS;
-            const int r = q % C::TILE, j = q / C::TILE;
+            const auto [q, r, j] = transposed_at<C>(pass);
             RowLds<C::T> lds{smem + r * C::RS};
             const int yg = y0 + r, yc = min(max(yg, 0), o.volNY - 1);
             float2 db[8];
@@ -1448,8 +1446,7 @@ __global__ __launch_bounds__(BDOF_THREADS, RowCfg<NX>::MIN_WAVES) void k_slice_x
         __syncthreads();
 #pragma unroll
         for (int pass = 0; pass < C::PASSES; ++pass) {
-            const int q = threadIdx.x + pass * BDOF_THREADS;
-            const int r = q % C::TILE, j = q / C::TILE;
+            const auto [q, r, j] = transposed_at<C>(pass);
             RowLds<C::T> lds{smem + r * C::RS};
             stage_write<NX, P::R0, 1>(v[pass], j, lds);
         }
@@ -1461,7 +1458,7 @@ __global__ __launch_bounds__(BDOF_THREADS, RowCfg<NX>::MIN_WAVES) void k_slice_x
             RowLds<C::T> lds{smem + r * C::RS};
             cf u[8], hv[8];
 #pragma unroll
-            for (int m = 0; m < 8; ++m) hv[m] = a.h_trail[tid + m * C::T];
+            for (int m = 0; m < 8; ++m) hv[m] = a.steps.h_trail[tid + m * C::T];
             tw_select(tw, smem_tw[1], smem_tail[1], sqt, tid);
             line_fft_rest<NX, -1, 1, false>(u, tw, tid, lds);
 #pragma unroll
@@ -2557,8 +2554,7 @@ __global__ __launch_bounds__(BDOF_THREADS, RowCfg<NY>::MIN_WAVES) void k_row_rea
     tw.template load<EX>(a.twiddle, tid, smem_tw, smem_tail);
     const int ntiles = a.B * a.NX / C::TILE;
     for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        const int row0 = tile * C::TILE;
-        const int b = row0 / a.NX, x0 = row0 - b * a.NX;
+        const auto [row0, b, x0] = tile_at<C>(tile, a.NX);
 #pragma nounroll
         for (int pass = 0; pass < C::PASSES; ++pass) {
             const int r = pass * C::RPP + rl;
