@@ -15,7 +15,9 @@ k_modulation_table, k_rot_bilinear<MOD>) — numpy, test side, shared by test_mo
                         `wrong` variants — that the cases below tell a subtly wrong kernel from a right one.
   sweep / switches / special   the cases.  Domain: |x| <= 1e5, -100 <= y <= 10.
   regime / oracle_inputs / c64_*   strong-phase objects for every engine, and a plain complex64 restatement of the oracle (scipy.fft,
-                        no carrier splitting): the error level a float32 engine can be asked for at these objects.
+                        no carrier splitting): the error level a float32 engine can be asked for at these objects.  With the
+                        options of tests/reference_model.py (slice binning, detector planes, a data term, the probe gradient) it
+                        also conditions the bounds of tests/gradient_cases.py.
 """
 import numpy as np
 import scipy.fft
@@ -239,54 +241,96 @@ def _c64_kernel(dist_nm, grid_shape):
     return np.fft.ifftshift(orc.get_kernel(dist_nm, 1240. / E_EV, voxel_nm, grid_shape)).astype(np.complex64)
 
 
-def c64_loss_and_grad(delta, beta, probe_real, probe_imag, meas_abs, free_prop_cm=None, variant='numpy_skip_last', k64=K64):
-    """orc.multislice_loss_and_grad operation for operation with every field, table and factor in complex64 / float32 (scipy.fft
-    keeps the type) and no carrier splitting: (detector wave, loss, g_delta, g_beta)."""
+def c64_term(loss_type='lsq', mu=2e6, w=None):
+    """A data term (d, meas_abs) -> (loss, G(d)) for c64_loss_and_grad: the seed of tests/reference_model.py's lsq, of
+    poisson_reference.poisson_seed or, with a weight plane w, of weights_reference.weighted_seed, every factor float32 /
+    complex64; the loss is summed in float64 from the float32 amplitudes.  Where w == 0 the amplitude takes no part."""
+    def term(d, meas_abs):
+        c8 = np.complex64
+        assert d.dtype == c8
+        absd = np.abs(d)
+        m = np.asarray(meas_abs, f32)
+        ww = None if w is None else np.asarray(w, f32)
+        if ww is not None:
+            m = np.where(ww > 0, m, f32(0))
+        with np.errstate(divide='ignore', invalid='ignore'):
+            if loss_type == 'lsq':
+                resid = absd - m
+                per_pixel = resid.astype(f64) ** 2
+                unit = np.where(absd > 0, d / absd, 0).astype(c8)
+                G = (f32(2.0 / d.size) * resid * unit).astype(c8)
+            else:
+                a64, m64 = absd.astype(f64), m.astype(f64)
+                log_term = np.where((m64 > 0) & (a64 > 0), 2.0 * m64 * m64 * np.log1p((a64 - m64) / np.where(m64 > 0, m64, 1.0)), 0.0)
+                per_pixel = np.where(a64 > 0, mu * ((a64 - m64) * (a64 + m64) - log_term), 0.0)
+                ratio = np.where(absd > 0, f32(1) - (m * m) / (absd * absd), f32(0)).astype(f32)
+                G = (f32(2.0 * mu / d.size) * ratio * d).astype(c8)
+        if ww is not None:
+            per_pixel, G = ww.astype(f64) * per_pixel, (ww * G).astype(c8)
+        return float(np.sum(per_pixel) / d.size), G
+    return term
+
+
+def c64_loss_and_grad(delta, beta, probe_real, probe_imag, meas_abs, free_prop_cm=None, variant='numpy_skip_last', k64=K64, b=1,
+                      term=None, probe_grad=False):
+    """tests/reference_model.py's loss_and_grad (b = 1, one detector, least squares: orc.multislice_loss_and_grad) operation for
+    operation with every field, table and factor in complex64 / float32 (scipy.fft keeps the type) and no carrier splitting:
+    (detector wave(s), loss, g_delta, g_beta) and, with probe_grad, G(psi_0) [B, Y, X] behind them.  b: slice binning;
+    free_prop_cm: None, 'inf', a distance or a sequence of distances; term: a data term of c64_term (None: least squares)."""
     B, Y, X, S = delta.shape
+    assert b >= 1 and S % b == 0
+    n = S // b
     c8 = np.complex64
-    h = _c64_kernel(1.0, (Y, X, S))
-    c = (np.exp(1j * k64 * delta) * np.exp(-k64 * beta)).astype(c8)                    # the factors themselves rounded once
+    term = term or c64_term()
+    h = _c64_kernel(1.0 * b, (Y, X, S))
+    c = np.stack([np.exp(1j * k64 * delta[..., i * b:(i + 1) * b].sum(axis=-1)) * np.exp(-k64 * beta[..., i * b:(i + 1) * b].sum(axis=-1))
+                  for i in range(n)], axis=-1).astype(c8)                               # the factors themselves rounded once
     psi = np.zeros((B, Y, X), dtype=c8) + (np.asarray(probe_real) + 1j * np.asarray(probe_imag)).astype(c8)
+    planes = isinstance(free_prop_cm, (list, tuple, np.ndarray))
 
     def step(f, hh):
         return scipy.fft.ifft2(scipy.fft.fft2(f, axes=(1, 2)) * hh, axes=(1, 2))
 
     phis = []
-    for i in range(S):
+    for i in range(n):
         phi = psi * c[..., i]
         phis.append(phi)
-        psi = step(phi, h) if (i < S - 1 or variant == 'tf_all') else phi
+        psi = step(phi, h) if (i < n - 1 or variant == 'tf_all') else phi
     if free_prop_cm is None:
         d = psi
+    elif planes:
+        hds = [_c64_kernel(z * 1e7, (Y, X, S)) for z in free_prop_cm]
+        d = np.stack([step(psi, hd) for hd in hds], axis=1)
     elif free_prop_cm == 'inf':
         d = scipy.fft.fftshift(scipy.fft.fft2(psi, axes=(1, 2)), axes=(1, 2))
     else:
         hd = _c64_kernel(free_prop_cm * 1e7, (Y, X, S))
         d = step(psi, hd)
     assert d.dtype == c8
-    absd = np.abs(d)
-    resid = absd - np.asarray(meas_abs, f32)
-    loss = float(np.mean(resid.astype(f64) ** 2))
-    with np.errstate(divide='ignore', invalid='ignore'):
-        unit = np.where(absd > 0, d / absd, 0).astype(c8)
-    G = (f32(2.0 / (B * Y * X)) * resid * unit).astype(c8)
+    loss, G = term(d, meas_abs)
     if free_prop_cm is None:
         pass
+    elif planes:
+        Gd = G
+        G = step(Gd[:, 0], np.conj(hds[0]))
+        for j in range(1, len(hds)):
+            G = G + step(Gd[:, j], np.conj(hds[j]))
     elif free_prop_cm == 'inf':
         G = f32(Y * X) * scipy.fft.ifft2(scipy.fft.ifftshift(G, axes=(1, 2)), axes=(1, 2))
     else:
         G = step(G, np.conj(hd))
     gd, gb = np.zeros((B, Y, X, S), f32), np.zeros((B, Y, X, S), f32)
     k = f32(k64)
-    for i in range(S - 1, -1, -1):
-        if i < S - 1 or variant == 'tf_all':
+    for i in range(n - 1, -1, -1):
+        if i < n - 1 or variant == 'tf_all':
             G = step(G, np.conj(h))
         t = np.conj(phis[i]) * G
-        gd[..., i] = k * t.imag
-        gb[..., i] = -k * t.real
+        for j in range(b):
+            gd[..., i * b + j] = k * t.imag
+            gb[..., i * b + j] = -k * t.real
         G = np.conj(c[..., i]) * G
     assert G.dtype == c8
-    return d, loss, gd, gb
+    return (d, loss, gd, gb, G) if probe_grad else (d, loss, gd, gb)
 
 
 # ---- the engine cases, shared by the CPU check of the bounds and the GPU file ------------------------------------------------------------

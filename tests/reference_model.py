@@ -24,6 +24,10 @@ and a sequence of one gives the numbers of its scalar exactly.
 The data term is an argument, (d, meas_abs) -> (loss, G(d)) with G(d) = dL/dRe d + i dL/dIm d over all pixels of d: `lsq` here,
 mean((|d| - m)^2), as multislice_loss_and_grad forms it; poisson_reference.py's and weights_reference.py's through `data_term`
 (a (Y, X) weight plane broadcasts over wavefields and planes).
+
+Two kinds of test data: `measurement_wide` here (amplitudes spread over [0, 2 |ref|]: the tight gradient bound of
+tests/gradient_cases.py) beside the 5 % noise of the other files.  `AdjointHook` lets a test put one defect into the adjoint
+sweep of loss_and_grad (tests/test_gradient_conditioning.py); without one the sweep is the model above.
 """
 import numpy as np
 
@@ -55,6 +59,46 @@ def lsq(d, meas_abs):
 def data_term(loss, seed, *args):
     """(d, meas_abs) -> (loss, G(d)) of a module's pair of functions, e.g. data_term(pref.poisson_loss, pref.poisson_seed, mu)."""
     return lambda d, meas_abs: (loss(d, meas_abs, *args), seed(d, meas_abs, *args))
+
+
+def measurement_wide(ref_wave, seed=0):
+    """Amplitudes m = |ref| U(0, 2) per pixel for a float64 detector wave `ref` (a generator of its own stream, deterministic).
+
+    Why not m = |ref| (1 + 0.05 N), the data of the other files.  The least-squares seed is G(d) = (2 / n) (1 - m / |d|) d and the
+    object gradient is g_delta = k Im(conj(phi) G(phi)), g_beta = -k Re(conj(phi) G(phi)).  With 5 % data 1 - m / |d| is the
+    difference of two float32 numbers that agree to 5 %, so a float32 engine's gradient error is its forward error divided by
+    0.05: that quotient, not the adjoint kernels, sets the 2e-4 of tests/test_gpu_parity.py, and an adjoint mistake of 1e-4
+    hides under it.
+
+    Why not scaled data, m = s |ref| (s = 3, or m = 0).  Then 1 - m / |d| = 1 - s is ONE number, G(d) is proportional to d,
+    the adjoint sweep carries it back to a multiple of phi (the sweep is the adjoint of a unitary step and of the modulation that
+    made phi), and conj(phi) G(phi) is proportional to |phi|^2: real.  g_delta, its imaginary part, is left with what absorption
+    breaks of that symmetry — 1.4e-5 of g_beta at a weak object, in float64 — which on a float32 device is all rounding: a relative
+    bound on it says nothing (tests/test_gradient_conditioning.py::test_scaled_data_leaves_g_delta_empty).
+
+    Only the pixel-to-pixel VARIATION of m / |d| feeds g_delta.  U(0, 2) makes that variation of order one: no cancellation in the
+    seed (|1 - m / |d|| is 0.5 on average), g_delta and g_beta of the same size, and the same forward noise gives a gradient error
+    7 to 9 times smaller than under the 5 % data.  The mean of m stays |ref|, so for a wave on a scalar carrier a0 the residual
+    split of MultisliceEngine.choose_residual_split stays on: mean|m - |a0|| is about |a0| / 2, below mean(m)."""
+    rng = np.random.default_rng([seed, 79])
+    return np.abs(ref_wave) * rng.uniform(0, 2, size=np.shape(ref_wave))
+
+
+class AdjointHook(object):
+    """What loss_and_grad's adjoint sweep asks at each place a kernel could go wrong; this one answers as the model does.  A test
+    subclasses it to restate ONE defect (step i counts propagation steps, 0 .. n-1; cs[i] is the bin's factor, phis[i] = cs[i] psi_i)."""
+
+    def row_field(self, i, phis, cs):
+        """The field whose conjugate multiplies G(phi_i) in the gradient row of step i."""
+        return phis[i]
+
+    def back_factor(self, i, cs):
+        """G(psi_i) = back_factor G(phi_i)."""
+        return np.conj(cs[i])
+
+    def plane_terms(self, terms):
+        """The list P(z_j)^H G(d_j) whose sum is G(psi) under several detector planes."""
+        return terms
 
 
 def _optics(shape, energy_ev, psize_cm, b, pi):
@@ -125,9 +169,11 @@ def loss_only(delta, beta, probe_real, probe_imag, energy_ev, psize_cm, meas_abs
 
 
 def loss_and_grad(delta, beta, probe_real, probe_imag, energy_ev, psize_cm, meas_abs, free_prop_cm=None, variant='numpy_skip_last',
-                  b=1, pi=orc.PI, term=lsq):
+                  b=1, pi=orc.PI, term=lsq, hook=None):
     """(loss, g_delta [B, Y, X, S], g_beta, g_probe [B, Y, X] complex = G(psi_0) per wavefield, detector wave(s)).
-    meas_abs has the shape of the detector waves; term(d, meas_abs) -> (loss, G(d)) is the data term."""
+    meas_abs has the shape of the detector waves; term(d, meas_abs) -> (loss, G(d)) is the data term.  hook: an AdjointHook
+    (test side: a defective adjoint sweep to measure a bound against); None is the model."""
+    hook = hook or AdjointHook()
     B, Y, X, S = delta.shape
     voxel_nm, lmbda_nm, h, k = _optics(delta.shape, energy_ev, psize_cm, b, pi)
     psi, phis, cs, _ = _sweep(delta, beta, probe_real, probe_imag, h, k, variant, b)
@@ -135,10 +181,10 @@ def loss_and_grad(delta, beta, probe_real, probe_imag, energy_ev, psize_cm, meas
     assert np.shape(meas_abs) == d.shape, (np.shape(meas_abs), d.shape)
     loss, G = term(d, meas_abs)
     if _planes(free_prop_cm):
-        Gd = G
-        G = prop_adj(Gd[:, 0], hd[0])
-        for j in range(1, len(hd)):
-            G = G + prop_adj(Gd[:, j], hd[j])
+        terms = hook.plane_terms([prop_adj(G[:, j], hd[j]) for j in range(len(hd))])
+        G = terms[0]
+        for t in terms[1:]:
+            G = G + t
     elif free_prop_cm == 'inf':
         G = (Y * X) * np.fft.ifft2(np.fft.ifftshift(G, axes=[1, 2]))
     elif free_prop_cm is not None:
@@ -148,11 +194,11 @@ def loss_and_grad(delta, beta, probe_real, probe_imag, energy_ev, psize_cm, meas
     for i in range(n - 1, -1, -1):
         if i < n - 1 or variant == 'tf_all':
             G = prop_adj(G, h)
-        t = np.conj(phis[i]) * G
+        t = np.conj(hook.row_field(i, phis, cs)) * G
         for j in range(b):                                  # the bin's one row to each of its voxel slices
             g_delta[..., i * b + j] = k * t.imag
             g_beta[..., i * b + j] = -k * t.real
-        G = np.conj(cs[i]) * G
+        G = hook.back_factor(i, cs) * G
     return loss, g_delta, g_beta, G, d
 
 
