@@ -19,6 +19,7 @@
 #include "bdof_conv64.h"
 #include "bdof_resident.h"
 #include "bdof_comm.h"
+#include "bdof_rigid.h"
 #include <rocfft/rocfft.h>
 #include <map>
 #include <optional>
@@ -3212,6 +3213,28 @@ int bdof_rotate_bilinear(bdof_ctx* c, const void* vol, int NXv, int NZv, int NYv
     return launched(c);
 }
 
+// What bdof_set_object_bilinear and bdof_set_object_rigid share once their own shape checks have passed: the B rotated objects of
+// a (NX, S, NY) volume are bound as modulation factors (there is no (delta, beta) source to rebuild the table from), with room for
+// the table and, if the mean-refraction carrier is in use (*mean), for the per-workgroup sums of the pass that fills it.
+static int bind_rotated_objects(bdof_ctx* c, int NXv, int NZv, int NYv, int B, int conv, bool* mean) {
+    if (NYv != c->NY || NXv != c->NX || NZv != c->S) return fail(c, BDOF_ERR_ARG, "the volume must be (NX, S, NY) of the configured wavefields");
+    if (B > c->Bmax) return fail(c, BDOF_ERR_ARG, "batch size outside [1, Bmax]");
+    if (conv && !c->have_conv) return fail(c, BDOF_ERR_STATE, "bdof_set_conv has not been called");
+    // set the binding first: want_cbar looks at the physics and probe only
+    c->obj_src = nullptr;
+    c->obj_bound_mod = true;
+    c->obj_rows = (size_t)B * NZv * NXv;
+    c->obj.volNY = NYv;
+    c->obj.tab = nullptr;
+    c->obj.volNX = c->NX;
+    c->obj.S = c->S;
+    c->n_angles = 0;
+    c->k = conv ? c->k_conv : c->k_fft;
+    changed(c, CHANGED_OBJECT);
+    *mean = want_cbar(c);
+    return modulation_room(c, c->obj_rows * NYv, *mean);
+}
+
 // bdof_rotate_bilinear + bdof_set_object in one pass: the B rotated objects are written straight into the ctx's modulation
 // table as factors c - 1 (no rotated (delta, beta) copy, no second pass over B volumes) and bound as the batch's objects.
 int bdof_set_object_bilinear(bdof_ctx* c, const void* vol, int NXv, int NZv, int NYv, const double* prm, int B, int conv) {
@@ -3220,23 +3243,9 @@ int bdof_set_object_bilinear(bdof_ctx* c, const void* vol, int NXv, int NZv, int
     int r = enter_setter(c, false);
     if (r) return r;
     if (NXv < 1 || NZv < 1 || NYv < 2 || NYv % 2) return fail(c, BDOF_ERR_SIZE, "bdof_set_object_bilinear needs an even NY");
-    if (NYv != c->NY || NXv != c->NX || NZv != c->S) return fail(c, BDOF_ERR_ARG, "the volume must be (NX, S, NY) of the configured wavefields");
-    if (B > c->Bmax) return fail(c, BDOF_ERR_ARG, "batch size outside [1, Bmax]");
-    if (conv && !c->have_conv) return fail(c, BDOF_ERR_STATE, "bdof_set_conv has not been called");
-    const size_t nrows = (size_t)B * NZv * NXv, n = nrows * NYv;
-    // set the binding first: want_cbar looks at the physics and probe only
-    c->obj_src = nullptr;
-    c->obj_bound_mod = true;
-    c->obj_rows = nrows;
-    c->obj.volNY = NYv;
-    c->obj.tab = nullptr;
-    c->obj.volNX = c->NX;
-    c->obj.S = c->S;
-    c->n_angles = 0;
-    c->k = conv ? c->k_conv : c->k_fft;
-    changed(c, CHANGED_OBJECT);
-    const bool mean = want_cbar(c);
-    if ((r = modulation_room(c, n, mean))) return r;
+    bool mean;
+    if ((r = bind_rotated_objects(c, NXv, NZv, NYv, B, conv, &mean))) return r;
+    const size_t nrows = c->obj_rows, n = nrows * NYv;
     RotBilinArgs a{(const float2*)vol, c->mod, nullptr, (const double4*)prm, B, NXv, NZv, NYv, 0, 0, 0, 1.f};
     const int grid = (int)std::min<size_t>((nrows + 3) / 4, (size_t)c->ncu * 16);
     hipLaunchKernelGGL((k_rot_bilinear<true>), dim3(grid), dim3(256), 0, c->stream, a, c->k, mean ? c->cbar_dev : (double2*)nullptr);
@@ -3259,6 +3268,58 @@ int bdof_rotate_bilinear_adjoint(bdof_ctx* c, const void* grot, int NXv, int NZv
     else if (nv4 <= 4) hipLaunchKernelGGL((k_rot_bilinear_adjoint<4>), dim3(grid), dim3(256), 0, c->stream, a);
     else if (nv4 <= 8) hipLaunchKernelGGL((k_rot_bilinear_adjoint<8>), dim3(grid), dim3(256), 0, c->stream, a);
     else return fail(c, BDOF_ERR_SIZE, "bdof_rotate_bilinear_adjoint: NY <= 1024");
+    return launched(c);
+}
+
+// ---- trilinear rotation under a rigid map per batch element (bdof_rigid.h): the three entry points mirror the bilinear ones ----
+// what all three ask of the shape: an even NY as for the bilinear pair (rotated rows are bound as rows of float4 pairs), and a
+// volume and a rotated batch whose voxel indices the kernels hold in an int
+static int rigid_shape(bdof_ctx* c, const char* who, int NXv, int NZv, int NYv, int B) {
+    if (NXv < 1 || NZv < 1 || NYv < 2 || NYv % 2) return fail(c, BDOF_ERR_SIZE, std::string(who) + " needs an even NY");
+    if ((long long)NXv * NZv * NYv > 0x7fffffffLL || (long long)B * NXv * NZv > 0x7fffffffLL)
+        return fail(c, BDOF_ERR_SIZE, std::string(who) + ": NX * NZ * NY and B * NX * NZ must be below 2^31");
+    return 0;
+}
+
+int bdof_rotate_rigid(bdof_ctx* c, const void* vol, int NXv, int NZv, int NYv, const double* prm, int B, void* out_rows) {
+    if (!c || !vol || !prm || !out_rows || B < 1) return BDOF_ERR_ARG;
+    if (int r = rigid_shape(c, "bdof_rotate_rigid", NXv, NZv, NYv, B)) return r;
+    HIPC(c, hipSetDevice(c->device));
+    RotRigidArgs a{(const float2*)vol, (float2*)out_rows, nullptr, prm, B, NXv, NZv, NYv, 0, 0, 0, 1.f};
+    const size_t nrows = (size_t)B * NZv * NXv;
+    const int grid = (int)std::min<size_t>((nrows + 3) / 4, (size_t)c->ncu * 16);
+    hipLaunchKernelGGL((k_rot_rigid<false>), dim3(grid), dim3(256), 0, c->stream, a, 0.f, (double2*)nullptr);
+    return launched(c);
+}
+
+// bdof_rotate_rigid + bdof_set_object in one pass, as bdof_set_object_bilinear: the factors c - 1 of the B rotated objects go
+// straight into the ctx's modulation table and are bound as the batch's objects.
+int bdof_set_object_rigid(bdof_ctx* c, const void* vol, int NXv, int NZv, int NYv, const double* prm, int B, int conv) {
+    if (int r = admit(c, "bdof_set_object_rigid", CARRIES_PLANES | NO_DATA_TERM)) return r;
+    if (!c || !vol || !prm || B < 1) return BDOF_ERR_ARG;
+    int r = enter_setter(c, false);
+    if (r) return r;
+    if ((r = rigid_shape(c, "bdof_set_object_rigid", NXv, NZv, NYv, B))) return r;
+    bool mean;
+    if ((r = bind_rotated_objects(c, NXv, NZv, NYv, B, conv, &mean))) return r;
+    const size_t nrows = c->obj_rows, n = nrows * NYv;
+    RotRigidArgs a{(const float2*)vol, c->mod, nullptr, prm, B, NXv, NZv, NYv, 0, 0, 0, 1.f};
+    const int grid = (int)std::min<size_t>((nrows + 3) / 4, (size_t)c->ncu * 16);
+    hipLaunchKernelGGL((k_rot_rigid<true>), dim3(grid), dim3(256), 0, c->stream, a, c->k, mean ? c->cbar_dev : (double2*)nullptr);
+    return modulation_done(c, n, grid, mean);
+}
+
+int bdof_rotate_rigid_adjoint(bdof_ctx* c, const void* grot, int NXv, int NZv, int NYv, const double* prm, int B, void* gvol, int row0,
+                              int n_rows, int accumulate, float scale) {
+    if (!c || !grot || !prm || !gvol || B < 1) return BDOF_ERR_ARG;
+    if (int r = rigid_shape(c, "bdof_rotate_rigid_adjoint", NXv, NZv, NYv, B)) return r;
+    if (row0 < 0 || n_rows < 0 || (long long)row0 + n_rows > (long long)NXv * NZv) return fail(c, BDOF_ERR_ARG, "destination rows outside the volume");
+    if (n_rows == 0) return 0;
+    HIPC(c, hipSetDevice(c->device));
+    ProfScope ps(c, BDOF_K_ROT_ADJ, c->stream);
+    RotRigidArgs a{nullptr, (float2*)grot, (float2*)gvol, prm, B, NXv, NZv, NYv, row0, row0 + n_rows, accumulate, scale};
+    const int grid = std::min((n_rows + 3) / 4, c->ncu * 16);
+    hipLaunchKernelGGL(k_rot_rigid_adjoint, dim3(grid), dim3(256), 0, c->stream, a);
     return launched(c);
 }
 

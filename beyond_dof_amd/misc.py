@@ -13,6 +13,9 @@ SUMMARY_PRESET_PTYCHO = ['obj_size', 'probe_size', 'output_folder', 'theta_downs
 SUMMARY_PRESET_FF = ['obj_size', 'output_folder', 'theta_downsample', 'n_theta', 'n_epochs', 'learning_rate', 'alpha_d',
                      'alpha_b', 'gamma', 'minibatch_size', 'free_prop_cm', 'psize_cm', 'energy_ev', 'fname', 'object_type',
                      'loss_type', 'poisson_multiplier', 'slice_binning']
+# rotation='trilinear' only: the geometry keywords behind a preset's lines (center as given, in pixels of the full-resolution data;
+# rotation_matrices as 'given' or None)
+SUMMARY_GEOMETRY = ['rotation', 'axis_tilt', 'axis_roll', 'center', 'rotation_matrices']
 
 
 def create_summary(save_path, locals_dict, var_list=None, preset=None):

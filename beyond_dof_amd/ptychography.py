@@ -16,7 +16,7 @@ import numpy as np
 from . import h5io, tiffio, util
 from .comm import get_comm
 from .fullfield import create_probe_initial_guess, upsample_2x
-from .misc import create_summary
+from .misc import create_summary, SUMMARY_PRESET_PTYCHO, SUMMARY_GEOMETRY
 from .engine import check_model_options, read_detector_weights
 from .solver import PtychoSolver
 from ._lib import BdofError
@@ -86,6 +86,14 @@ def reconstruct_ptychography(fname, probe_pos, probe_size, obj_size, theta_st=0,
     # (the default with the transfer-function propagator: reconstructed delta within 2.1e-6 of the reference's float64 loop on golden
     # vector G17, 7.0e-6 with 'float32' — both inside 1e-5 since the kernels take dithered copies of the transfer function;
     # one slower step per epoch)
+    # rotation='trilinear': a rigid map per angle, sampled trilinearly (PtychoSolver), with the true angles theta =
+    # -linspace(theta_st, theta_end, n_theta) and axis_tilt / axis_roll (radians), center (the detector column the axis projects
+    # onto, a pixel index of the full-resolution volume) or rotation_matrices (n_theta, 3, 4) in full-resolution voxels; no
+    # lookup-table files are written.  Any other value of the keyword stays ignored, as it always was, and the four with it.
+    trilinear = kwargs.get('rotation') == 'trilinear'
+    rotation = 'trilinear' if trilinear else 'nearest'
+    axis_tilt, axis_roll = float(kwargs.get('axis_tilt', 0.)), float(kwargs.get('axis_roll', 0.))
+    center, rotation_matrices = kwargs.get('center'), kwargs.get('rotation_matrices')
     adjoint_precision = kwargs.get('adjoint_precision', 'first-step')
     if adjoint_precision not in ('float32', 'float64', 'first-step'):
         raise ValueError("adjoint_precision must be 'float32', 'float64' or 'first-step'")
@@ -100,7 +108,7 @@ def reconstruct_ptychography(fname, probe_pos, probe_size, obj_size, theta_st=0,
     # 'first-step' does not carry it, so the DEFAULT becomes 'float32' and an explicit other choice raises; every multiscale
     # level's depth must divide by b.  What each of the three needs of propagator and adjoint precision: engine.OPTION_NEEDS.
     check_model_options(loss_type, poisson_multiplier, detector_weights, slice_binning, propagator=propagator,
-                        adjoint_precision=kwargs.get('adjoint_precision'))
+                        adjoint_precision=kwargs.get('adjoint_precision'), rotation=rotation)
     if slice_binning > 1:
         adjoint_precision = 'float32'
     for lv in range(multiscale_level):
@@ -116,6 +124,9 @@ def reconstruct_ptychography(fname, probe_pos, probe_size, obj_size, theta_st=0,
     if theta_downsample is not None:
         prj_theta_ind = prj_theta_ind[::theta_downsample]
         n_theta = len(prj_theta_ind)
+    theta = -np.linspace(theta_st, theta_end, prj.shape[0], dtype='float32')[prj_theta_ind]
+    if trilinear and rotation_matrices is not None:
+        rotation_matrices = util.check_rigid(np.asarray(rotation_matrices, dtype=np.float64)[prj_theta_ind], n_theta).reshape(-1, 3, 4)
     original_shape = [n_theta] + list(prj.shape[1:])
     print_flush('Data shape: {}'.format(original_shape), 0, rank)
 
@@ -141,7 +152,17 @@ def reconstruct_ptychography(fname, probe_pos, probe_size, obj_size, theta_st=0,
         if minibatch_size is None:
             minibatch_size = n_pos
 
-        coord_ls = util.rotation_lookup_files(this_obj_size, n_theta, comm)
+        coord_ls = None if trilinear else util.rotation_lookup_files(this_obj_size, n_theta, comm)
+        geometry = {}
+        if trilinear:
+            # the levels are strided: voxel i of this level is voxel i * ds_level of the full resolution, so an explicit centre
+            # and the translations divide by ds_level (the default centre is this level's own middle column)
+            geometry = dict(rotation=rotation, theta=theta, axis_tilt=axis_tilt, axis_roll=axis_roll,
+                            center=None if center is None else float(center) / ds_level)
+            if rotation_matrices is not None:
+                level = rotation_matrices.copy()
+                level[:, :, 3] /= ds_level
+                geometry['rotation_matrices'] = level
 
         np.random.seed(seed)                               # rank 0 initialises and broadcasts in the reference (:169-208)
         if first_level:
@@ -185,7 +206,7 @@ def reconstruct_ptychography(fname, probe_pos, probe_size, obj_size, theta_st=0,
                                        coord_ls=coord_ls, propagator=propagator, kernel_size=kwargs.get('kernel_size', 17),
                                        adjoint64={'float32': None, 'float64': True, 'first-step': 'first'}[prec],
                                        loss_type=loss_type, poisson_multiplier=poisson_multiplier, slice_binning=slice_binning,
-                                       detector_weights=weights)
+                                       detector_weights=weights, **geometry)
         # the DEFAULT's float64 path (first minibatch of an epoch) is an accuracy refinement with buffers of its own (wave + tape in
         # complex128, allocated when the solver is built): where they do not fit beside the engine's the run goes on in float32,
         # SAYS so and records it (summary.txt: adjoint_precision_effective); an explicit request fails.  The retry runs outside the
@@ -221,7 +242,11 @@ def reconstruct_ptychography(fname, probe_pos, probe_size, obj_size, theta_st=0,
             solver.enable_probe_optimization(probe_real, probe_imag, probe_learning_rate, pupil_function)
         print_flush('Optimizer started.', 0, rank)
         if rank == 0:
-            create_summary(output_folder, locals(), preset='ptycho')
+            if trilinear:                        # the geometry behind the preset's lines
+                create_summary(output_folder, dict(locals(), rotation_matrices=None if rotation_matrices is None else 'given'),
+                               var_list=SUMMARY_PRESET_PTYCHO + SUMMARY_GEOMETRY)
+            else:
+                create_summary(output_folder, locals(), preset='ptycho')
 
         rng = np.random.RandomState(seed)
         i_epoch, cont = 0, True

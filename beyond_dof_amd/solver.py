@@ -32,6 +32,18 @@ def _check_options(propagator, adjoint64, *options, **path):
     return check_model_options(*options, propagator=propagator, adjoint_precision='float64' if adjoint64 else None, **path)
 
 
+def _rigid_prm(n_theta, shape, theta, axis_tilt, axis_roll, center, rotation_matrices):
+    """(n_theta, 12) float64 rows of (M | t) for rotation='trilinear' from a solver's keywords (ValueError for what is missing, of
+    the wrong length or not rigid): rotation_matrices if given, else util.rigid_geometry of theta and the axis keywords."""
+    if theta is None and rotation_matrices is None:
+        raise ValueError("rotation='trilinear' needs the projection angles theta or rotation_matrices")
+    if rotation_matrices is not None:
+        return util.check_rigid(rotation_matrices, n_theta)
+    if len(np.atleast_1d(theta)) != int(n_theta):
+        raise ValueError('theta must hold n_theta = {} angles'.format(int(n_theta)))
+    return util.rigid_geometry(theta, shape, axis_tilt, axis_roll, center)
+
+
 class _VolumeSolver(object):
     """What the full-field and ptychography solvers share: volume double buffer, gradient, moments, the tail of the step."""
 
@@ -388,7 +400,8 @@ class FullfieldSolver(_VolumeSolver):
     def __init__(self, dim_y, dim_x, dim_z, n_theta, minibatch_size, energy_ev, psize_cm, free_prop_cm=None,
                  probe_real=None, probe_imag=None, variant='numpy_skip_last', comm=None, device=0, stream=None,
                  coord_ls=None, propagator='fft', kernel_size=17, recompute=False, rotation='nearest', theta=None, adjoint64=None,
-                 detector_kernel='TF', loss_type='lsq', poisson_multiplier=2e6, slice_binning=1, detector_weights=None):
+                 detector_kernel='TF', loss_type='lsq', poisson_multiplier=2e6, slice_binning=1, detector_weights=None,
+                 axis_tilt=0., axis_roll=0., center=None, rotation_matrices=None):
         """loss_type / poisson_multiplier: the data term (MultisliceEngine.set_loss; 'poisson' with propagator='fft' only).
         detector_weights: one (Y, X) plane of weights >= 0 for every projection (MultisliceEngine.set_detector_weights; 0: the
         pixel takes no part), set before any measurement is bound; propagator='fft' only.
@@ -401,24 +414,34 @@ class FullfieldSolver(_VolumeSolver):
         rotation='nearest': the cnn variant's lookup tables, fused into the kernels (cnn_propagator/util.py:294-402);
         'bilinear': the TF twin's tf_rotate(obj, theta[i], 'BILINEAR') (tensorflow_recon/fullfield.py:96) with the true angles
         `theta` (radians, one per projection): the minibatch's rotated objects are materialised per step
-        (bdof_rotate_bilinear), its adjoint is a gather (bdof_rotate_bilinear_adjoint)."""
+        (bdof_rotate_bilinear), its adjoint is a gather (bdof_rotate_bilinear_adjoint);
+        'trilinear': a rigid map per angle, sampled trilinearly (bdof_set_object_rigid / bdof_rotate_rigid_adjoint), on the same
+        path as 'bilinear' — util.rigid_geometry(theta, (Y, X, Z), axis_tilt, axis_roll, center): the axis tilted towards the
+        beam by axis_tilt (laminography), rolled about the beam by axis_roll (radians), projecting onto detector column `center`
+        (a pixel index, fractional if need be; None: the middle) — or rotation_matrices (n_theta, 3, 4), any rigid (M | t) per
+        angle (util.check_rigid), which then stands in place of theta and the three geometry keywords.  With any other rotation
+        these four keywords are ignored."""
         self.n_planes = _check_options(propagator, adjoint64, loss_type, poisson_multiplier, detector_weights, slice_binning, free_prop_cm,
-                                       rotation=rotation if rotation == 'bilinear' else 'nearest', recompute=recompute, detector_kernel=detector_kernel)
+                                       rotation=rotation if rotation in ('bilinear', 'trilinear') else 'nearest', recompute=recompute, detector_kernel=detector_kernel)
         self.conv = propagator == 'conv'
         self.bilinear = rotation == 'bilinear'
+        self.trilinear = rotation == 'trilinear'
+        self.materialised = self.bilinear or self.trilinear      # the minibatch's rotated objects are written out every step
         if adjoint64 not in (None, False, True, 'first'):
             raise ValueError("adjoint64 must be None, False, True or 'first'")
-        if adjoint64 and rotation == 'bilinear' and (self.conv or adjoint64 == 'first'):
+        if adjoint64 and self.materialised and (self.conv or adjoint64 == 'first'):
             raise ValueError("the float64 paths (adjoint64='first'; propagator='conv') run with the lookup-table rotation")
         # 'first': the first minibatch of every epoch through the model's float64 path on the same context (bdof_loss_grad_tf_f64 /
         # bdof_loss_grad_conv_f64), as PtychoSolver does it; True: every minibatch — the engine's float64 adjoint sweep
         # (transfer-function model) or the float64 path (real-space model, which has no such sweep)
         self.f64 = 'first' if adjoint64 == 'first' else (True if (adjoint64 is True and self.conv) else None)
         adjoint64 = adjoint64 is True and not self.conv
-        if rotation not in ('nearest', 'bilinear'):
-            raise ValueError("rotation must be 'nearest' or 'bilinear'")
+        if rotation not in ('nearest', 'bilinear', 'trilinear'):
+            raise ValueError("rotation must be 'nearest', 'bilinear' or 'trilinear'")
         if self.bilinear and theta is None:
             raise ValueError("rotation='bilinear' needs the projection angles theta")
+        if self.trilinear:       # (M | t) per angle, float64: checked here, before anything is allocated on the device
+            rot_prm = _rigid_prm(n_theta, (dim_y, dim_x, dim_z), theta, axis_tilt, axis_roll, center, rotation_matrices)
         self.dim_y, self.dim_x, self.dim_z = int(dim_y), int(dim_x), int(dim_z)
         self.n_theta, self.mb = int(n_theta), int(minibatch_size)
         self.comm = comm or PseudoComm()
@@ -444,7 +467,13 @@ class FullfieldSolver(_VolumeSolver):
             H, W = self.dim_x, self.dim_z
             c, sn = np.cos(th), np.sin(th)
             self.rot_prm = np.stack([c, sn, ((W - 1) - (c * (W - 1) - sn * (H - 1))) / 2.0, ((H - 1) - (sn * (W - 1) + c * (H - 1))) / 2.0], axis=1)
-            self.prm_buf = DeviceBuffer(self.ctx, self.mb * 32, np.float64, (self.mb, 4))
+        elif self.trilinear:
+            self.rot_prm = rot_prm
+        if self.materialised:
+            lib = self.ctx.lib
+            self._bind_rotated, self._rotation_adjoint = (lib.bdof_set_object_bilinear, lib.bdof_rotate_bilinear_adjoint) if self.bilinear \
+                else (lib.bdof_set_object_rigid, lib.bdof_rotate_rigid_adjoint)
+            self.prm_buf = DeviceBuffer(self.ctx, self.mb * self.rot_prm.shape[1] * 8, np.float64, (self.mb, self.rot_prm.shape[1]))
             self.tab = self.off = self.order = None
         else:
             # rotation lookup tables (cnn_propagator/util.py:294-347), uploaded once
@@ -454,22 +483,21 @@ class FullfieldSolver(_VolumeSolver):
                                        (self.mb, self.dim_x, self.dim_y) if self.n_planes == 1 else (self.mb, self.n_planes, self.dim_x, self.dim_y))
         self.angle_buf = DeviceBuffer(self.ctx, self.mb * 4, np.int32, (self.mb,))
         self._bind_volume()
-        if not self.bilinear:
+        if not self.materialised:
             self.eng.set_rotation_adjoint(self.off, self.order, self.dim_x * self.dim_z)
 
     def _bind_volume(self):
-        if not self.bilinear:        # (else the engine's object is the minibatch's rotated copy, rebuilt at every step: _rotate_batch)
+        if not self.materialised:    # (else the engine's object is the minibatch's rotated copy, rebuilt at every step: _rotate_batch)
             _VolumeSolver._bind_volume(self)
 
     def _rotate_batch(self, idx, B):
-        """Bilinear rotation of the current volume to the B angles idx, bound as a batch of rotated objects: one pass that
-        writes the rotated objects' modulation factors into the ctx (bdof_set_object_bilinear)."""
-        lib, h = self.ctx.lib, self.ctx.handle
-        prm = np.zeros((self.mb, 4))
+        """Materialised rotation (bilinear or trilinear) of the current volume to the B angles idx, bound as a batch of rotated
+        objects: one pass that writes the rotated objects' modulation factors into the ctx (bdof_set_object_bilinear / _rigid)."""
+        prm = np.zeros(self.prm_buf.shape)
         prm[:B] = self.rot_prm[np.asarray(idx)]
         self.prm_buf.upload(prm)
-        self.ctx.check(lib.bdof_set_object_bilinear(h, self.x[self.cur].ptr, self.dim_x, self.dim_z, self.dim_y, self.prm_buf.ptr, B,
-                                                    int(self.conv)))
+        self.ctx.check(self._bind_rotated(self.ctx.handle, self.x[self.cur].ptr, self.dim_x, self.dim_z, self.dim_y, self.prm_buf.ptr, B,
+                                          int(self.conv)))
 
     def set_measurements(self, prj_abs):
         """|prj| for every angle, (n_theta, Y, X) — with D detector planes (n_theta, D, Y, X) — (loss uses np.abs(this_prj_batch),
@@ -493,24 +521,24 @@ class FullfieldSolver(_VolumeSolver):
         f64: through the transfer-function model's float64 path on the same context (bdof_loss_grad_tf_f64)."""
         self._stage_batch(angle_idx)
         if f64:
-            if self.bilinear:
+            if self.materialised:
                 raise ValueError("f64: the float64 paths run with the lookup-table rotation")
             if self.conv and not self.eng.conv_f64:      # (a probe or physics set since the last call unbound the twin)
                 self.eng.enable_conv_f64()
             if not self.conv and not self.eng.tf_f64:
                 self.eng.enable_tf_f64()
-        elif self.bilinear:
+        elif self.materialised:
             self._rotate_batch(angle_idx, self.mb)
-        self.eng.loss_grad_device(self.mb, None if self.bilinear else self.angle_buf.ptr, None, None, self.meas_stage.ptr,
+        self.eng.loss_grad_device(self.mb, None if self.materialised else self.angle_buf.ptr, None, None, self.meas_stage.ptr,
                                   conv=self.conv, f64=f64)
 
     def _produce(self, accumulate=False):
         lib, h = self.ctx.lib, self.ctx.handle
 
         def produce(x0, nx):
-            if self.bilinear:
-                self.ctx.check(lib.bdof_rotate_bilinear_adjoint(h, lib.bdof_grot(h), self.dim_x, self.dim_z, self.dim_y, self.prm_buf.ptr,
-                                                                self.mb, self.g.ptr, x0 * self.dim_z, nx * self.dim_z, int(accumulate), 1.0))
+            if self.materialised:
+                self.ctx.check(self._rotation_adjoint(h, lib.bdof_grot(h), self.dim_x, self.dim_z, self.dim_y, self.prm_buf.ptr,
+                                                      self.mb, self.g.ptr, x0 * self.dim_z, nx * self.dim_z, int(accumulate), 1.0))
             else:
                 self.ctx.check(lib.bdof_rotation_adjoint_rows(h, self.mb, self.angle_buf.ptr, self.g.ptr, x0 * self.dim_z,
                                                               nx * self.dim_z, int(accumulate), 1.0))
@@ -547,7 +575,7 @@ class FullfieldSolver(_VolumeSolver):
 
     def _dry_tail(self, n_slabs, sharded):
         self.angle_buf.upload(np.arange(self.mb, dtype=np.int32) % self.n_theta)
-        if self.bilinear:
+        if self.materialised:
             prm = self.rot_prm[np.arange(self.mb) % self.n_theta]
             self.prm_buf.upload(np.ascontiguousarray(prm))
         self._tail(self._produce(), 0, 0.0, n_slabs=n_slabs, sharded=sharded, flip=False)
@@ -573,7 +601,7 @@ class FullfieldSolver(_VolumeSolver):
                 self._probe_apply()
         else:
             # one rank, lookup-table rotation: nothing happens between the rotation adjoint and Adam
-            one_pass = self._one_pass_tail if not self._reduces() and not self.bilinear else None
+            one_pass = self._one_pass_tail if not self._reduces() and not self.materialised else None
             self._tail(self._produce(), i_batch, learning_rate, alpha_d, alpha_b, gamma, clip, use_mask, n_slabs, sharded, one_pass=one_pass)
             self._probe_apply()
         return self._get_loss() if want_loss else None          # the loss of THIS minibatch stays on the device until the next one
@@ -585,7 +613,7 @@ class FullfieldSolver(_VolumeSolver):
         out = []
         for i in range(0, len(idx), self.mb):
             chunk = idx[i:i + self.mb]
-            if self.bilinear:
+            if self.materialised:
                 self._rotate_batch(chunk, len(chunk))
                 out.append(self.eng.forward(len(chunk), conv=self.conv))
             else:
@@ -599,17 +627,29 @@ class PtychoSolver(_VolumeSolver):
 
     def __init__(self, obj_size, probe_size, probe_pos, n_theta, minibatch_size, energy_ev, psize_cm, probe_real, probe_imag,
                  variant='numpy_skip_last', comm=None, device=0, stream=None, coord_ls=None, propagator='fft', kernel_size=17,
-                 adjoint64=None, engine=None, loss_type='lsq', poisson_multiplier=2e6, slice_binning=1, detector_weights=None):
-        """loss_type / poisson_multiplier: the data term (MultisliceEngine.set_loss; 'poisson' with propagator='fft' only).
+                 adjoint64=None, engine=None, loss_type='lsq', poisson_multiplier=2e6, slice_binning=1, detector_weights=None,
+                 rotation='nearest', theta=None, axis_tilt=0., axis_roll=0., center=None, rotation_matrices=None):
+        """rotation='nearest': the lookup tables.  'trilinear': the rigid map of FullfieldSolver(rotation='trilinear'), with the same
+        theta / axis_tilt / axis_roll / center / rotation_matrices (tilt 0: ptychography's interpolating rotation).  A minibatch has
+        one angle, so per step the volume is rotated once into a plain (delta, beta) copy (bdof_rotate_rigid, B = 1), the copy is
+        bound under a one-angle identity table, the windows run with angle 0 on whichever engine and precision was chosen, the
+        window adjoint fills a rotated-frame gradient through the identity's inverse tables and bdof_rotate_rigid_adjoint takes it
+        into the volume's.  slice_binning > 1 keeps to rotation='nearest'.
+        loss_type / poisson_multiplier: the data term (MultisliceEngine.set_loss; 'poisson' with propagator='fft' only).
         detector_weights: one (py, px) plane of weights >= 0 for every diffraction pattern, fftshifted as the patterns are
         (MultisliceEngine.set_detector_weights; 0: dead pixel, beamstop), set before any measurement is bound; propagator='fft' only.
         slice_binning: voxel slices per propagation step (MultisliceEngine); > 1 with propagator='fft' and no adjoint64 only, and
         engine=None then takes 'auto' (the resident engine does not carry it).
         engine: None picks the LDS-resident engine for small square probes (below) and the automatic choice otherwise; 'auto',
         'generic', 'streaming' or 'resident' go to MultisliceEngine(engine=...) as they are."""
-        _check_options(propagator, adjoint64, loss_type, poisson_multiplier, detector_weights, slice_binning)
+        if rotation not in ('nearest', 'trilinear'):
+            raise ValueError("rotation must be 'nearest' or 'trilinear'")
+        self.trilinear = rotation == 'trilinear'
+        _check_options(propagator, adjoint64, loss_type, poisson_multiplier, detector_weights, slice_binning, rotation=rotation)
         self.conv = propagator == 'conv'
         self.dim_y, self.dim_x, self.dim_z = [int(s) for s in obj_size]
+        if self.trilinear:
+            self.rot_prm = _rigid_prm(n_theta, (self.dim_y, self.dim_x, self.dim_z), theta, axis_tilt, axis_roll, center, rotation_matrices)
         self.py, self.px = int(probe_size[0]), int(probe_size[1])
         self.n_theta, self.mb = int(n_theta), int(minibatch_size)
         self.comm = comm or PseudoComm()
@@ -638,13 +678,35 @@ class PtychoSolver(_VolumeSolver):
             self.f64 = adjoint64
         elif adjoint64 not in (None, False, True):
             raise ValueError("adjoint64 must be None, False, True or 'first'")
-        self._upload_rotation_tables(coord_ls)
+        if self.trilinear:
+            # the rotated copy [z][x][y] and its gradient, and the identity tables of one angle: rotated row (z, x) is row z X + x
+            n_rows = self.dim_z * self.dim_x
+            self.rot_copy = DeviceBuffer.zeros(self.ctx, (self.dim_z, self.dim_x, self.dim_y, 2), np.float32)
+            self.g_rot = DeviceBuffer.zeros(self.ctx, (self.dim_z, self.dim_x, self.dim_y, 2), np.float32)
+            self.prm_buf = DeviceBuffer(self.ctx, 12 * 8, np.float64, (1, 12))
+            self.tab = DeviceBuffer.from_host(self.ctx, np.arange(n_rows, dtype=np.int32).reshape(1, self.dim_z, self.dim_x))
+            self.off = DeviceBuffer.from_host(self.ctx, np.arange(n_rows + 1, dtype=np.int32).reshape(1, -1))
+            self.order = DeviceBuffer.from_host(self.ctx, np.arange(n_rows, dtype=np.int32).reshape(1, -1))
+        else:
+            self._upload_rotation_tables(coord_ls)
         self._init_volume()
         self.meas_stage = DeviceBuffer(self.ctx, self.mb * self.py * self.px * 4, np.float32, (self.mb, self.py, self.px))
         self.idx_buf = DeviceBuffer(self.ctx, 4 * self.mb * 4, np.int32, (4, self.mb))
         self._bind_volume()
         self.eng.set_rotation_adjoint(self.off, self.order, self.dim_x * self.dim_z)
         self._last = None
+
+    def _bind_volume(self):
+        if not self.trilinear:       # (else the engine's object is the rotated copy of the step's angle: _rotate_to)
+            _VolumeSolver._bind_volume(self)
+
+    def _rotate_to(self, i_theta):
+        """rotation='trilinear': the current volume under angle i_theta's rigid map as plain (delta, beta) rows, bound with the
+        identity table (again at every call: that memory has changed)."""
+        lib, h = self.ctx.lib, self.ctx.handle
+        self.prm_buf.upload(np.ascontiguousarray(self.rot_prm[int(i_theta)][None]))
+        self.ctx.check(lib.bdof_rotate_rigid(h, self.x[self.cur].ptr, self.dim_x, self.dim_z, self.dim_y, self.prm_buf.ptr, 1, self.rot_copy.ptr))
+        self.eng.set_volume(self.rot_copy, self.dim_z * self.dim_x, self.dim_y, self.tab, self.dim_x, 1)
 
     def set_measurements(self, prj_abs_all):
         """All diffraction amplitudes |prj| (n_theta, n_pos, py, px) resident on the device (a cfg5-sized dataset is 0.75 GB):
@@ -657,7 +719,7 @@ class PtychoSolver(_VolumeSolver):
     def _stage(self, i_theta, pos_idx, prj_abs_batch):
         pos = self.probe_pos[np.asarray(pos_idx)]
         idx = np.empty((4, self.mb), dtype=np.int32)
-        idx[0] = i_theta
+        idx[0] = 0 if self.trilinear else i_theta      # trilinear: the bound copy is already rotated, its one table is the identity
         idx[1] = pos[:, 1] - self.half[1]            # window origin in x (axis 1), ptychography.py:68-70
         idx[2] = pos[:, 0] - self.half[0]            # window origin in y (axis 0)
         idx[3] = 0
@@ -677,13 +739,21 @@ class PtychoSolver(_VolumeSolver):
     def _win_loss_grad(self, i_theta, pos_idx, prj_abs_batch, use64=False):
         a, xo, yo = self._stage(i_theta, pos_idx, prj_abs_batch)
         f64 = self.f64 is True or (use64 and self.f64 == 'first')
+        if self.trilinear:
+            self._rotate_to(i_theta)
         self.eng.loss_grad_device(self.mb, a, xo, yo, self.meas_stage.ptr, conv=self.conv, f64=f64)
-        self._last = (int(i_theta), xo, yo)
+        self._last = (0 if self.trilinear else int(i_theta), xo, yo)
 
     def _produce_all(self):
         i_theta, xo, yo = self._last
         self._g_is_local()
-        self.ctx.check(self.ctx.lib.bdof_window_rotation_adjoint(self.ctx.handle, self.mb, i_theta, xo, yo, self.g.ptr, 0, 1.0))
+        lib, h = self.ctx.lib, self.ctx.handle
+        if self.trilinear:           # windows -> rotated frame (identity tables) -> volume frame (prm_buf still holds the step's angle)
+            self.ctx.check(lib.bdof_window_rotation_adjoint(h, self.mb, 0, xo, yo, self.g_rot.ptr, 0, 1.0))
+            self.ctx.check(lib.bdof_rotate_rigid_adjoint(h, self.g_rot.ptr, self.dim_x, self.dim_z, self.dim_y, self.prm_buf.ptr, 1,
+                                                         self.g.ptr, 0, self.dim_x * self.dim_z, 0, 1.0))
+        else:
+            self.ctx.check(lib.bdof_window_rotation_adjoint(h, self.mb, i_theta, xo, yo, self.g.ptr, 0, 1.0))
 
     def loss_and_grad(self, i_theta, pos_idx, prj_abs_batch=None, want_loss=True, f64=False):
         """prj_abs_batch: |this_prj_batch| (mb, py, px) for probe positions pos_idx at angle i_theta (None: from the resident
@@ -710,6 +780,9 @@ class PtychoSolver(_VolumeSolver):
 
     def forward(self, i_theta, pos_idx):
         pos = self.probe_pos[np.asarray(pos_idx)]
+        if self.trilinear:
+            self._rotate_to(i_theta)
+            i_theta = 0
         return self.eng.forward(len(pos), angle_idx=[i_theta] * len(pos), xoff=pos[:, 1] - self.half[1],
                                 yoff=pos[:, 0] - self.half[0], conv=self.conv)
 

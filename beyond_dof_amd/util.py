@@ -313,6 +313,49 @@ def device_rotation_tables(coords, nx, nz):
     return tab, off, order
 
 
+def rigid_geometry(theta, shape, axis_tilt=0., axis_roll=0., center=None):
+    """(n_theta, 12) float64: the rows of (M | t) of rotation='trilinear' for a volume of shape (Y, X, Z).  Output voxel
+    o = (x, z, y) of the beam frame samples the volume at p = M o + t in index coordinates (x', z', y'), with
+
+        M(theta) = M0(theta) T(axis_tilt) R(axis_roll),      t = c_v - M c_o
+        M0: x' =  cos x + sin z ; z' = -sin x + cos z ; y' = y       (the bilinear rotation's own map)
+        T : z' =  cos z + sin y ; y' = -sin z + cos y ; x' = x       (axis tilted towards the beam: laminography)
+        R : x' =  cos x + sin y ; y' = -sin x + cos y ; z' = z       (axis rolled about the beam)
+        c_v = ((X - 1) / 2, (Z - 1) / 2, (Y - 1) / 2),  c_o = c_v with its first entry replaced by `center` if given
+
+    center: the detector column the axis projects onto, as a (possibly fractional) pixel index.  Angles in radians."""
+    th = np.atleast_1d(np.asarray(theta, dtype=np.float64))
+    ny, nx, nz = [int(a) for a in shape]
+    ca, sa, cr, sr = np.cos(float(axis_tilt)), np.sin(float(axis_tilt)), np.cos(float(axis_roll)), np.sin(float(axis_roll))
+    T = np.array([[1., 0., 0.], [0., ca, sa], [0., -sa, ca]])
+    R = np.array([[cr, 0., sr], [0., 1., 0.], [-sr, 0., cr]])
+    c_v = np.array([(nx - 1) / 2., (nz - 1) / 2., (ny - 1) / 2.])
+    c_o = c_v.copy()
+    if center is not None:
+        c_o[0] = float(center)
+    out = np.empty((len(th), 3, 4))
+    for i, a in enumerate(th):
+        c, s = np.cos(a), np.sin(a)
+        M = np.array([[c, s, 0.], [-s, c, 0.], [0., 0., 1.]]) @ T @ R
+        out[i, :, :3] = M
+        out[i, :, 3] = c_v - M @ c_o
+    return out.reshape(len(th), 12)
+
+
+def check_rigid(rotation_matrices, n_theta):
+    """A user's rotation_matrices (n_theta, 3, 4) = (M | t) as the (n_theta, 12) float64 the kernels take.  ValueError unless
+    every M is orthonormal (|M^T M - I| <= 1e-9) with det > 0: the adjoint's candidate search relies on M preserving distances."""
+    m = np.array(rotation_matrices, dtype=np.float64)
+    if m.shape != (int(n_theta), 3, 4):
+        raise ValueError('rotation_matrices must have shape (n_theta, 3, 4) = ({}, 3, 4), not {}'.format(int(n_theta), m.shape))
+    M = m[:, :, :3]
+    dev = np.abs(np.einsum('nji,njk->nik', M, M) - np.eye(3)).max(axis=(1, 2))
+    if not np.all(np.isfinite(m)) or np.any(dev > 1e-9) or np.any(np.linalg.det(M) <= 0):
+        raise ValueError('rotation_matrices must be rigid: every 3 x 3 part orthonormal to 1e-9 with det > 0 '
+                         '(largest |M^T M - I| is {:.3g})'.format(float(np.nanmax(dev))))
+    return np.ascontiguousarray(m.reshape(len(m), 12))
+
+
 def split_tasks(arr, split_size):
     """cnn_propagator/util.py:271-277."""
     return [arr[i:i + split_size] for i in range(0, len(arr), split_size)]

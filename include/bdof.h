@@ -435,6 +435,26 @@ int bdof_set_object_bilinear(bdof_ctx* ctx, const void* vol, int NXv, int NZv, i
 int bdof_rotate_bilinear_adjoint(bdof_ctx* ctx, const void* grot, int NXv, int NZv, int NYv, const double* prm, int B, void* gvol, int row0,
                                  int n_rows, int accumulate, float scale);
 
+/* Trilinear rotation under an arbitrary rigid map per batch element (laminography tilt, axis roll, centre of rotation, per-angle
+ * wobble) and its exact adjoint: the 3-D counterpart of the three calls above, with the same semantics, layouts, admission rules
+ * and state.  vol: device [NXv][NZv][NYv] pairs; prm: DEVICE float64 [B][12], the rows of (M | t): output voxel o = (x, z, y) of
+ * rotated object b samples the volume at p = M o + t in index coordinates (x', z', y'), trilinearly over the 8 surrounding
+ * voxels, a tap outside the volume counting 0 (scipy.ndimage.affine_transform(order=1, mode='grid-constant', cval=0)).
+ * Coordinates are formed in float64, a weight is the float32 product of three float32 factors; the adjoint uses the forward's
+ * weights bit for bit and is a deterministic gather (no atomics: slab-wise, whole-volume and repeated calls give the same bits).
+ * PRECONDITION: M is orthonormal with det +1.  The adjoint finds the outputs that touch a voxel in the box |o - M^T (v' - t)|_i <
+ * sum_j |M_ji|, which holds because M preserves distances; prm is a device pointer, so the library cannot check it (the Python
+ * layer does, util.check_rigid).  With a sheared or scaled M the adjoint silently misses contributions.
+ * out_rows: device [B][NZv][NXv][NYv] pairs, as for bdof_rotate_bilinear.  bdof_set_object_rigid is bdof_rotate_rigid +
+ * bdof_set_object in one pass (the volume must be (NX, S, NY) of the configured wavefields; the object is bound as modulation
+ * factors, so bdof_rotation_adjoint_adam and, after a change of physics or probe, bdof_modulation_table refuse it exactly as
+ * they refuse bdof_set_object_bilinear's).  bdof_rotate_rigid_adjoint keeps the slab interface (row0, n_rows, accumulate, scale).
+ * BDOF_ERR_SIZE: an odd NY, NXv * NZv * NYv or B * NXv * NZv of 2^31 or more. */
+int bdof_rotate_rigid(bdof_ctx* ctx, const void* vol, int NXv, int NZv, int NYv, const double* prm, int B, void* out_rows);
+int bdof_set_object_rigid(bdof_ctx* ctx, const void* vol, int NXv, int NZv, int NYv, const double* prm, int B, int conv);
+int bdof_rotate_rigid_adjoint(bdof_ctx* ctx, const void* grot, int NXv, int NZv, int NYv, const double* prm, int B, void* gvol, int row0,
+                              int n_rows, int accumulate, float scale);
+
 /* Ptychography: adjoint of rotate + zero-pad + per-position window (cnn_propagator/ptychography.py:32-34,42-73) for a
  * batch whose elements all use rotation angle `angle` and windows at (xoff[b], yoff[b]); gvol: device [n_dest][volNY] pairs. */
 int bdof_window_rotation_adjoint(bdof_ctx* ctx, int B, int angle, const int* xoff, const int* yoff, void* gvol,
