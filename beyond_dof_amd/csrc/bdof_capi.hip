@@ -3202,18 +3202,12 @@ int bdof_rotation_adjoint_adam(bdof_ctx* c, int B, const int* angle_of_b, void* 
     return 0;
 }
 
-int bdof_rotate_bilinear(bdof_ctx* c, const void* vol, int NXv, int NZv, int NYv, const double* prm, int B, void* out_rows) {
-    if (!c || !vol || !prm || !out_rows || B < 1) return BDOF_ERR_ARG;
-    if (NXv < 1 || NZv < 1 || NYv < 2 || NYv % 2) return fail(c, BDOF_ERR_SIZE, "bdof_rotate_bilinear needs an even NY");
-    HIPC(c, hipSetDevice(c->device));
-    RotBilinArgs a{(const float2*)vol, (float2*)out_rows, nullptr, (const double4*)prm, B, NXv, NZv, NYv, 0, 0, 0, 1.f};
-    const size_t nrows = (size_t)B * NZv * NXv;
-    const int grid = (int)std::min<size_t>((nrows + 3) / 4, (size_t)c->ncu * 16);
-    hipLaunchKernelGGL((k_rot_bilinear<false>), dim3(grid), dim3(256), 0, c->stream, a, 0.f, (double2*)nullptr);
-    return launched(c);
-}
+}  // extern "C"  (the host paths below are templates)
 
-// What bdof_set_object_bilinear and bdof_set_object_rigid share once their own shape checks have passed: the B rotated objects of
+// ---- the materialised rotations: bilinear (k_rot_bilinear*) and trilinear under a rigid map per batch element (bdof_rigid.h) ----
+// One host path per operation — rotate, bind as modulation factors, adjoint — over a traits struct per kind: the entry points' names
+// for the messages, the prm type, the shape rule and the two launches.
+// What both kinds bind once their own shape checks have passed: the B rotated objects of
 // a (NX, S, NY) volume are bound as modulation factors (there is no (delta, beta) source to rebuild the table from), with room for
 // the table and, if the mean-refraction carrier is in use (*mean), for the per-workgroup sums of the pass that fills it.
 static int bind_rotated_objects(bdof_ctx* c, int NXv, int NZv, int NYv, int B, int conv, bool* mean) {
@@ -3235,92 +3229,108 @@ static int bind_rotated_objects(bdof_ctx* c, int NXv, int NZv, int NYv, int B, i
     return modulation_room(c, c->obj_rows * NYv, *mean);
 }
 
-// bdof_rotate_bilinear + bdof_set_object in one pass: the B rotated objects are written straight into the ctx's modulation
-// table as factors c - 1 (no rotated (delta, beta) copy, no second pass over B volumes) and bound as the batch's objects.
-int bdof_set_object_bilinear(bdof_ctx* c, const void* vol, int NXv, int NZv, int NYv, const double* prm, int B, int conv) {
-    if (int r = admit(c, "bdof_set_object_bilinear", CARRIES_PLANES | NO_DATA_TERM)) return r;
-    if (!c || !vol || !prm || B < 1) return BDOF_ERR_ARG;
-    int r = enter_setter(c, false);
-    if (r) return r;
-    if (NXv < 1 || NZv < 1 || NYv < 2 || NYv % 2) return fail(c, BDOF_ERR_SIZE, "bdof_set_object_bilinear needs an even NY");
-    bool mean;
-    if ((r = bind_rotated_objects(c, NXv, NZv, NYv, B, conv, &mean))) return r;
-    const size_t nrows = c->obj_rows, n = nrows * NYv;
-    RotBilinArgs a{(const float2*)vol, c->mod, nullptr, (const double4*)prm, B, NXv, NZv, NYv, 0, 0, 0, 1.f};
-    const int grid = (int)std::min<size_t>((nrows + 3) / 4, (size_t)c->ncu * 16);
-    hipLaunchKernelGGL((k_rot_bilinear<true>), dim3(grid), dim3(256), 0, c->stream, a, c->k, mean ? c->cbar_dev : (double2*)nullptr);
-    return modulation_done(c, n, grid, mean);
-}
+struct RotBilinear {
+    using Prm = double4;
+    static constexpr const char *rotate = "bdof_rotate_bilinear", *set_object = "bdof_set_object_bilinear", *adjoint = "bdof_rotate_bilinear_adjoint";
+    // an even NY: rotated rows are bound as rows of float4 pairs
+    static int shape(bdof_ctx* c, const char* who, int NXv, int NZv, int NYv, int) {
+        if (NXv < 1 || NZv < 1 || NYv < 2 || NYv % 2) return fail(c, BDOF_ERR_SIZE, std::string(who) + " needs an even NY");
+        return 0;
+    }
+    template <bool MOD> static void forward(bdof_ctx* c, int grid, const RotArgs<Prm>& a, float k, double2* partial) {
+        hipLaunchKernelGGL((k_rot_bilinear<MOD>), dim3(grid), dim3(256), 0, c->stream, a, k, partial);
+    }
+    static int back(bdof_ctx* c, int grid, const RotArgs<Prm>& a) {
+        const int nv4 = (a.NYv / 2 + 63) / 64;
+        if (nv4 <= 1) hipLaunchKernelGGL((k_rot_bilinear_adjoint<1>), dim3(grid), dim3(256), 0, c->stream, a);
+        else if (nv4 <= 2) hipLaunchKernelGGL((k_rot_bilinear_adjoint<2>), dim3(grid), dim3(256), 0, c->stream, a);
+        else if (nv4 <= 4) hipLaunchKernelGGL((k_rot_bilinear_adjoint<4>), dim3(grid), dim3(256), 0, c->stream, a);
+        else if (nv4 <= 8) hipLaunchKernelGGL((k_rot_bilinear_adjoint<8>), dim3(grid), dim3(256), 0, c->stream, a);
+        else return fail(c, BDOF_ERR_SIZE, "bdof_rotate_bilinear_adjoint: NY <= 1024");
+        return 0;
+    }
+};
+struct RotRigid {
+    using Prm = double;
+    static constexpr const char *rotate = "bdof_rotate_rigid", *set_object = "bdof_set_object_rigid", *adjoint = "bdof_rotate_rigid_adjoint";
+    // an even NY as for the bilinear kind, and a volume and a rotated batch whose voxel indices the kernels hold in an int
+    static int shape(bdof_ctx* c, const char* who, int NXv, int NZv, int NYv, int B) {
+        if (int r = RotBilinear::shape(c, who, NXv, NZv, NYv, B)) return r;
+        if ((long long)NXv * NZv * NYv > 0x7fffffffLL || (long long)B * NXv * NZv > 0x7fffffffLL)
+            return fail(c, BDOF_ERR_SIZE, std::string(who) + ": NX * NZ * NY and B * NX * NZ must be below 2^31");
+        return 0;
+    }
+    template <bool MOD> static void forward(bdof_ctx* c, int grid, const RotArgs<Prm>& a, float k, double2* partial) {
+        hipLaunchKernelGGL((k_rot_rigid<MOD>), dim3(grid), dim3(256), 0, c->stream, a, k, partial);
+    }
+    static int back(bdof_ctx* c, int grid, const RotArgs<Prm>& a) { hipLaunchKernelGGL(k_rot_rigid_adjoint, dim3(grid), dim3(256), 0, c->stream, a); return 0; }
+};
 
-int bdof_rotate_bilinear_adjoint(bdof_ctx* c, const void* grot, int NXv, int NZv, int NYv, const double* prm, int B, void* gvol, int row0,
-                                 int n_rows, int accumulate, float scale) {
-    if (!c || !grot || !prm || !gvol || B < 1) return BDOF_ERR_ARG;
-    if (NXv < 1 || NZv < 1 || NYv < 2 || NYv % 2) return fail(c, BDOF_ERR_SIZE, "bdof_rotate_bilinear_adjoint needs an even NY");
-    if (row0 < 0 || n_rows < 0 || (long long)row0 + n_rows > (long long)NXv * NZv) return fail(c, BDOF_ERR_ARG, "destination rows outside the volume");
-    if (n_rows == 0) return 0;
-    HIPC(c, hipSetDevice(c->device));
-    ProfScope ps(c, BDOF_K_ROT_ADJ, c->stream);
-    RotBilinArgs a{nullptr, (float2*)grot, (float2*)gvol, (const double4*)prm, B, NXv, NZv, NYv, row0, row0 + n_rows, accumulate, scale};
-    const int grid = std::min((n_rows + 3) / 4, c->ncu * 16);
-    const int nv4 = (NYv / 2 + 63) / 64;
-    if (nv4 <= 1) hipLaunchKernelGGL((k_rot_bilinear_adjoint<1>), dim3(grid), dim3(256), 0, c->stream, a);
-    else if (nv4 <= 2) hipLaunchKernelGGL((k_rot_bilinear_adjoint<2>), dim3(grid), dim3(256), 0, c->stream, a);
-    else if (nv4 <= 4) hipLaunchKernelGGL((k_rot_bilinear_adjoint<4>), dim3(grid), dim3(256), 0, c->stream, a);
-    else if (nv4 <= 8) hipLaunchKernelGGL((k_rot_bilinear_adjoint<8>), dim3(grid), dim3(256), 0, c->stream, a);
-    else return fail(c, BDOF_ERR_SIZE, "bdof_rotate_bilinear_adjoint: NY <= 1024");
-    return launched(c);
-}
-
-// ---- trilinear rotation under a rigid map per batch element (bdof_rigid.h): the three entry points mirror the bilinear ones ----
-// what all three ask of the shape: an even NY as for the bilinear pair (rotated rows are bound as rows of float4 pairs), and a
-// volume and a rotated batch whose voxel indices the kernels hold in an int
-static int rigid_shape(bdof_ctx* c, const char* who, int NXv, int NZv, int NYv, int B) {
-    if (NXv < 1 || NZv < 1 || NYv < 2 || NYv % 2) return fail(c, BDOF_ERR_SIZE, std::string(who) + " needs an even NY");
-    if ((long long)NXv * NZv * NYv > 0x7fffffffLL || (long long)B * NXv * NZv > 0x7fffffffLL)
-        return fail(c, BDOF_ERR_SIZE, std::string(who) + ": NX * NZ * NY and B * NX * NZ must be below 2^31");
-    return 0;
-}
-
-int bdof_rotate_rigid(bdof_ctx* c, const void* vol, int NXv, int NZv, int NYv, const double* prm, int B, void* out_rows) {
+template <class K>       // the B rotated objects as plain (delta, beta) rows
+static int rotate_rows(bdof_ctx* c, const void* vol, int NXv, int NZv, int NYv, const double* prm, int B, void* out_rows) {
     if (!c || !vol || !prm || !out_rows || B < 1) return BDOF_ERR_ARG;
-    if (int r = rigid_shape(c, "bdof_rotate_rigid", NXv, NZv, NYv, B)) return r;
+    if (int r = K::shape(c, K::rotate, NXv, NZv, NYv, B)) return r;
     HIPC(c, hipSetDevice(c->device));
-    RotRigidArgs a{(const float2*)vol, (float2*)out_rows, nullptr, prm, B, NXv, NZv, NYv, 0, 0, 0, 1.f};
+    RotArgs<typename K::Prm> a{(const float2*)vol, (float2*)out_rows, nullptr, (const typename K::Prm*)prm, B, NXv, NZv, NYv, 0, 0, 0, 1.f};
     const size_t nrows = (size_t)B * NZv * NXv;
     const int grid = (int)std::min<size_t>((nrows + 3) / 4, (size_t)c->ncu * 16);
-    hipLaunchKernelGGL((k_rot_rigid<false>), dim3(grid), dim3(256), 0, c->stream, a, 0.f, (double2*)nullptr);
+    K::template forward<false>(c, grid, a, 0.f, nullptr);
     return launched(c);
 }
 
-// bdof_rotate_rigid + bdof_set_object in one pass, as bdof_set_object_bilinear: the factors c - 1 of the B rotated objects go
-// straight into the ctx's modulation table and are bound as the batch's objects.
-int bdof_set_object_rigid(bdof_ctx* c, const void* vol, int NXv, int NZv, int NYv, const double* prm, int B, int conv) {
-    if (int r = admit(c, "bdof_set_object_rigid", CARRIES_PLANES | NO_DATA_TERM)) return r;
+// rotate_rows + bdof_set_object in one pass: the B rotated objects are written straight into the ctx's modulation
+// table as factors c - 1 (no rotated (delta, beta) copy, no second pass over B volumes) and bound as the batch's objects.
+template <class K>
+static int set_object_rotated(bdof_ctx* c, const void* vol, int NXv, int NZv, int NYv, const double* prm, int B, int conv) {
+    if (int r = admit(c, K::set_object, CARRIES_PLANES | NO_DATA_TERM)) return r;
     if (!c || !vol || !prm || B < 1) return BDOF_ERR_ARG;
     int r = enter_setter(c, false);
     if (r) return r;
-    if ((r = rigid_shape(c, "bdof_set_object_rigid", NXv, NZv, NYv, B))) return r;
+    if ((r = K::shape(c, K::set_object, NXv, NZv, NYv, B))) return r;
     bool mean;
     if ((r = bind_rotated_objects(c, NXv, NZv, NYv, B, conv, &mean))) return r;
     const size_t nrows = c->obj_rows, n = nrows * NYv;
-    RotRigidArgs a{(const float2*)vol, c->mod, nullptr, prm, B, NXv, NZv, NYv, 0, 0, 0, 1.f};
+    RotArgs<typename K::Prm> a{(const float2*)vol, c->mod, nullptr, (const typename K::Prm*)prm, B, NXv, NZv, NYv, 0, 0, 0, 1.f};
     const int grid = (int)std::min<size_t>((nrows + 3) / 4, (size_t)c->ncu * 16);
-    hipLaunchKernelGGL((k_rot_rigid<true>), dim3(grid), dim3(256), 0, c->stream, a, c->k, mean ? c->cbar_dev : (double2*)nullptr);
+    K::template forward<true>(c, grid, a, c->k, mean ? c->cbar_dev : (double2*)nullptr);
     return modulation_done(c, n, grid, mean);
 }
 
-int bdof_rotate_rigid_adjoint(bdof_ctx* c, const void* grot, int NXv, int NZv, int NYv, const double* prm, int B, void* gvol, int row0,
-                              int n_rows, int accumulate, float scale) {
+template <class K>
+static int rotate_adjoint(bdof_ctx* c, const void* grot, int NXv, int NZv, int NYv, const double* prm, int B, void* gvol, int row0,
+                          int n_rows, int accumulate, float scale) {
     if (!c || !grot || !prm || !gvol || B < 1) return BDOF_ERR_ARG;
-    if (int r = rigid_shape(c, "bdof_rotate_rigid_adjoint", NXv, NZv, NYv, B)) return r;
+    if (int r = K::shape(c, K::adjoint, NXv, NZv, NYv, B)) return r;
     if (row0 < 0 || n_rows < 0 || (long long)row0 + n_rows > (long long)NXv * NZv) return fail(c, BDOF_ERR_ARG, "destination rows outside the volume");
     if (n_rows == 0) return 0;
     HIPC(c, hipSetDevice(c->device));
     ProfScope ps(c, BDOF_K_ROT_ADJ, c->stream);
-    RotRigidArgs a{nullptr, (float2*)grot, (float2*)gvol, prm, B, NXv, NZv, NYv, row0, row0 + n_rows, accumulate, scale};
-    const int grid = std::min((n_rows + 3) / 4, c->ncu * 16);
-    hipLaunchKernelGGL(k_rot_rigid_adjoint, dim3(grid), dim3(256), 0, c->stream, a);
+    RotArgs<typename K::Prm> a{nullptr, (float2*)grot, (float2*)gvol, (const typename K::Prm*)prm, B, NXv, NZv, NYv, row0, row0 + n_rows, accumulate, scale};
+    if (int r = K::back(c, std::min((n_rows + 3) / 4, c->ncu * 16), a)) return r;
     return launched(c);
+}
+
+extern "C" {
+
+int bdof_rotate_bilinear(bdof_ctx* c, const void* vol, int NXv, int NZv, int NYv, const double* prm, int B, void* out_rows) {
+    return rotate_rows<RotBilinear>(c, vol, NXv, NZv, NYv, prm, B, out_rows);
+}
+int bdof_set_object_bilinear(bdof_ctx* c, const void* vol, int NXv, int NZv, int NYv, const double* prm, int B, int conv) {
+    return set_object_rotated<RotBilinear>(c, vol, NXv, NZv, NYv, prm, B, conv);
+}
+int bdof_rotate_bilinear_adjoint(bdof_ctx* c, const void* grot, int NXv, int NZv, int NYv, const double* prm, int B, void* gvol, int row0,
+                                 int n_rows, int accumulate, float scale) {
+    return rotate_adjoint<RotBilinear>(c, grot, NXv, NZv, NYv, prm, B, gvol, row0, n_rows, accumulate, scale);
+}
+int bdof_rotate_rigid(bdof_ctx* c, const void* vol, int NXv, int NZv, int NYv, const double* prm, int B, void* out_rows) {
+    return rotate_rows<RotRigid>(c, vol, NXv, NZv, NYv, prm, B, out_rows);
+}
+int bdof_set_object_rigid(bdof_ctx* c, const void* vol, int NXv, int NZv, int NYv, const double* prm, int B, int conv) {
+    return set_object_rotated<RotRigid>(c, vol, NXv, NZv, NYv, prm, B, conv);
+}
+int bdof_rotate_rigid_adjoint(bdof_ctx* c, const void* grot, int NXv, int NZv, int NYv, const double* prm, int B, void* gvol, int row0,
+                              int n_rows, int accumulate, float scale) {
+    return rotate_adjoint<RotRigid>(c, grot, NXv, NZv, NYv, prm, B, gvol, row0, n_rows, accumulate, scale);
 }
 
 int bdof_regularizer_value(bdof_ctx* c, const void* x, int NXv, int NZv, int NYv, double* sums) {

@@ -1895,29 +1895,51 @@ __global__ __launch_bounds__(256) void k_gather_fields4(float* __restrict__ dst,
 // rows.  prm[b] = (cos, sin, x_off, y_off) in float64 (coordinates are formed per ROW, so float64 costs nothing).
 // Output rows [b][z][x][y]: the layout of already rotated objects (bdof_set_object without a table).
 // ---------------------------------------------------------------------------------------------
-struct RotBilinArgs {
+// the arguments of a materialised rotation's kernels, bilinear (Prm = double4, prm [B]) or rigid (bdof_rigid.h: double, prm [B][12])
+template <class Prm>
+struct RotArgs {
     const float2* vol;      // [NXv][NZv][NYv]
     float2* rot;            // forward: out [B][NZv][NXv][NYv] ; adjoint: in, the rotated-frame gradient
     float2* gvol;           // adjoint: out [NXv][NZv][NYv]
-    const double4* prm;     // [B]
+    const Prm* prm;
     int B, NXv, NZv, NYv;
     int d0, d1, accumulate; // adjoint: destination rows [d0, d1)
     float scale;
 };
-// source point and the four (row index, weight) pairs of output row (h = x, w = z); rows outside the volume get weight 0
-__device__ __forceinline__ void bilin_taps(const double4 p, int h, int w, int H, int W, int (&row)[4], float (&wt)[4]) {
+using RotBilinArgs = RotArgs<double4>;
+// The source point of output row (h = x, w = z): the lower corner (h0, w0) of its cell and the fractions (ah, aw) rounded to
+// float32.  bilin_point and bilin_weight are the only place where a coordinate or a weight of the bilinear rotation is formed: the
+// forward kernel reaches them through bilin_taps, the adjoint directly, so the adjoint's weights are the forward's, bit for bit.
+__device__ __forceinline__ void bilin_point(const double4 p, int h, int w, int& h0, int& w0, float& ah, float& aw) {
     const double sw = p.x * w - p.y * h + p.z, sh = p.y * w + p.x * h + p.w;
     const double fw = floor(sw), fh = floor(sh);
-    const int w0 = (int)fw, h0 = (int)fh;
-    const float aw = (float)(sw - fw), ah = (float)(sh - fh);
-    const int hs[4] = {h0, h0, h0 + 1, h0 + 1}, ws[4] = {w0, w0 + 1, w0, w0 + 1};
-    const float cw[4] = {(1.f - ah) * (1.f - aw), (1.f - ah) * aw, ah * (1.f - aw), ah * aw};
+    w0 = (int)fw, h0 = (int)fh;
+    aw = (float)(sw - fw), ah = (float)(sh - fh);
+}
+// the weight of the cell's corner (h0 + ih, w0 + iw): the float32 product of two factors, the one along h first
+__device__ __forceinline__ float bilin_weight(float ah, float aw, int ih, int iw) { return (ih ? ah : 1.f - ah) * (iw ? aw : 1.f - aw); }
+// the four (row index, weight) pairs of output row (h, w): tap i = 2 ih + iw; rows outside the volume get index 0 and weight 0
+__device__ __forceinline__ void bilin_taps(const double4 p, int h, int w, int H, int W, int (&row)[4], float (&wt)[4]) {
+    int h0, w0;
+    float ah, aw;
+    bilin_point(p, h, w, h0, w0, ah, aw);
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-        const bool in = hs[i] >= 0 && hs[i] < H && ws[i] >= 0 && ws[i] < W;
-        row[i] = in ? hs[i] * W + ws[i] : 0;
-        wt[i] = in ? cw[i] : 0.f;
+        const int ih = i >> 1, iw = i & 1, hs = h0 + ih, ws = w0 + iw;
+        const bool in = hs >= 0 && hs < H && ws >= 0 && ws < W;
+        row[i] = in ? hs * W + ws : 0;
+        wt[i] = in ? bilin_weight(ah, aw, ih, iw) : 0.f;
     }
+}
+// The MOD epilogue of a forward rotation kernel of 4 waves (k_rot_bilinear<true>, k_rot_rigid<true>): the lanes' float64 sums of
+// c - 1 reduced over the wave, handed over through LDS and stored as the workgroup's entry of `partial`.
+__device__ __forceinline__ void rot_mod_partial(double sx, double sy, int wave, int lane, double2* __restrict__ partial) {
+    __shared__ double w[2][4];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) { sx += __shfl_down(sx, off, 64); sy += __shfl_down(sy, off, 64); }
+    if (lane == 0) { w[0][wave] = sx; w[1][wave] = sy; }
+    __syncthreads();
+    if (threadIdx.x == 0) partial[blockIdx.x] = make_double2(w[0][0] + w[0][1] + w[0][2] + w[0][3], w[1][0] + w[1][1] + w[1][2] + w[1][3]);
 }
 // one wave per output row (4 rows per workgroup).  MOD: the rows are written as modulation factors c - 1 of the interpolated
 // (delta, beta) (what k_modulation_table would make of them in a second pass over B volumes), with the per-workgroup
@@ -1956,14 +1978,7 @@ __global__ __launch_bounds__(256) void k_rot_bilinear(RotBilinArgs a, float k, d
         }
     }
     if constexpr (MOD) {
-        if (partial) {
-            __shared__ double w[2][4];
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) { sx += __shfl_down(sx, off, 64); sy += __shfl_down(sy, off, 64); }
-            if (lane == 0) { w[0][wave] = sx; w[1][wave] = sy; }
-            __syncthreads();
-            if (threadIdx.x == 0) partial[blockIdx.x] = make_double2(w[0][0] + w[0][1] + w[0][2] + w[0][3], w[1][0] + w[1][1] + w[1][2] + w[1][3]);
-        }
+        if (partial) rot_mod_partial(sx, sy, wave, lane, partial);
     }
 }
 // Adjoint, as a gather (deterministic, no atomics): volume row d = (x', z') collects w * rotated-frame rows (x, z) whose
@@ -1996,12 +2011,12 @@ __global__ __launch_bounds__(256) void k_rot_bilinear_adjoint(RotBilinArgs a) {
                 const double wi = p.x * dw + p.y * dh, hi = -p.y * dw + p.x * dh;
                 const int w = (int)floor(wi) - 1 + jw, h = (int)floor(hi) - 1 + jh;
                 if (h >= 0 && h < H && w >= 0 && w < W) {
-                    const double sw = p.x * w - p.y * h + p.z, sh = p.y * w + p.x * h + p.w;
-                    const double fw = floor(sw), fh = floor(sh);
-                    const int iw = wp - (int)fw, ih = hp - (int)fh;         // which of the 2 x 2 taps of (h, w) is (h', w'): 0 or 1
+                    int h0, w0;
+                    float ah, aw;
+                    bilin_point(p, h, w, h0, w0, ah, aw);
+                    const int iw = wp - w0, ih = hp - h0;                   // which of the 2 x 2 taps of (h, w) is (h', w'): 0 or 1
                     if (iw >= 0 && iw <= 1 && ih >= 0 && ih <= 1) {
-                        const float aw = (float)(sw - fw), ah = (float)(sh - fh);
-                        wgt = (ih ? ah : 1.f - ah) * (iw ? aw : 1.f - aw);
+                        wgt = bilin_weight(ah, aw, ih, iw);
                         row = (b * W + w) * H + h;
                     }
                 }

@@ -9,15 +9,7 @@
 #pragma once
 #include "bdof_kernels.h"
 
-struct RotRigidArgs {
-    const float2* vol;      // [NXv][NZv][NYv]
-    float2* rot;            // forward: out [B][NZv][NXv][NYv] ; adjoint: in, the rotated-frame gradient
-    float2* gvol;           // adjoint: out [NXv][NZv][NYv]
-    const double* prm;      // [B][12]
-    int B, NXv, NZv, NYv;
-    int d0, d1, accumulate; // adjoint: destination rows [d0, d1)
-    float scale;
-};
+using RotRigidArgs = RotArgs<double>;        // prm [B][12]
 
 // The source point of output voxel (x, z, y) under m = (M | t): the lower corner i0 of its cell and, per axis, the two factors
 // (one minus the fraction, the fraction) rounded to float32.  Coordinates in float64: the row's base point M (x, z, 0) + t, then
@@ -96,14 +88,7 @@ __global__ __launch_bounds__(256) void k_rot_rigid(RotRigidArgs a, float k, doub
         }
     }
     if constexpr (MOD) {
-        if (partial) {
-            __shared__ double w[2][4];
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) { sx += __shfl_down(sx, off, 64); sy += __shfl_down(sy, off, 64); }
-            if (lane == 0) { w[0][wave] = sx; w[1][wave] = sy; }
-            __syncthreads();
-            if (threadIdx.x == 0) partial[blockIdx.x] = make_double2(w[0][0] + w[0][1] + w[0][2] + w[0][3], w[1][0] + w[1][1] + w[1][2] + w[1][3]);
-        }
+        if (partial) rot_mod_partial(sx, sy, wave, lane, partial);
     }
 }
 

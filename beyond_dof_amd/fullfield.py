@@ -100,14 +100,10 @@ def reconstruct_fullfield(fname, theta_st=0, theta_end=PI, n_epochs='auto', crit
     # 413-425); the cnn variant accepts the keyword and ignores it (default 5!), so it is opt-in here
     accumulate = bool(kwargs.get('accumulate_gradients', False))
     # 'nearest': the cnn variant's lookup tables over linspace(0, 2 pi) (quirk Q5); 'bilinear': the TF twin's tf_rotate with the true
-    # angles theta = -linspace(theta_st, theta_end) (tensorflow_recon/fullfield.py:96,216)
-    # 'trilinear': a rigid map per angle, sampled trilinearly (FullfieldSolver): the same theta, with axis_tilt / axis_roll
-    # (radians), center (the detector column the axis projects onto, a pixel index of the full-resolution data) or
-    # rotation_matrices (n_theta, 3, 4) in voxels of the full-resolution volume.  With any other rotation the four are ignored.
-    rotation = kwargs.get('rotation', 'nearest')
-    trilinear = rotation == 'trilinear'
-    axis_tilt, axis_roll = float(kwargs.get('axis_tilt', 0.)), float(kwargs.get('axis_roll', 0.))
-    center, rotation_matrices = kwargs.get('center'), kwargs.get('rotation_matrices')
+    # angles theta = -linspace(theta_st, theta_end) (tensorflow_recon/fullfield.py:96,216); 'trilinear': a rigid map per angle
+    # (FullfieldSolver) with the same theta and the geometry keywords of util.RotationKeywords
+    geo = util.RotationKeywords(kwargs)
+    rotation, trilinear = geo.rotation, geo.trilinear
 
     print_flush('Reading data...', 0, rank)
     t0 = time.time()
@@ -123,11 +119,7 @@ def reconstruct_fullfield(fname, theta_st=0, theta_end=PI, n_epochs='auto', crit
         prj_0 = prj_0[::theta_downsample]
         theta = theta[::theta_downsample]
     n_theta = len(theta)
-    if trilinear and rotation_matrices is not None:
-        rotation_matrices = np.asarray(rotation_matrices, dtype=np.float64)
-        if theta_downsample is not None:
-            rotation_matrices = rotation_matrices[::theta_downsample]
-        rotation_matrices = util.check_rigid(rotation_matrices, n_theta).reshape(-1, 3, 4)
+    geo.select(n_theta, None if theta_downsample is None else slice(None, None, theta_downsample))
     original_shape = prj_0.shape
     print_flush('Data reading: {} s'.format(time.time() - t0), 0, rank)
     print_flush('Data shape: {}'.format(original_shape), 0, rank)
@@ -215,23 +207,13 @@ def reconstruct_fullfield(fname, theta_st=0, theta_end=PI, n_epochs='auto', crit
             raise ValueError("Invalid wavefront type. Choose from 'plane', 'fixed', 'optimizable'.")
 
         coord_ls = None if rotation in ('bilinear', 'trilinear') else util.rotation_lookup_files([dim_y, dim_x, dim_x], n_theta, comm)
-        geometry = {}
-        if trilinear:
-            # the data are strided, not binned: voxel i of this level is voxel i * ds_level of the full resolution, so an
-            # explicit centre and the translations divide by ds_level (the default centre is this level's own middle column)
-            geometry = dict(axis_tilt=axis_tilt, axis_roll=axis_roll, center=None if center is None else float(center) / ds_level)
-            if rotation_matrices is not None:
-                level = rotation_matrices.copy()
-                level[:, :, 3] /= ds_level
-                geometry['rotation_matrices'] = level
-
         solver = FullfieldSolver(dim_y, dim_x, dim_z, n_theta, minibatch_size, energy_ev, psize_cm * ds_level,
                                  free_prop_cm=free_prop_cm, probe_real=probe_real, probe_imag=probe_imag, variant=variant,
                                  comm=comm, device=comm.local_rank, coord_ls=coord_ls, propagator=propagator, kernel_size=kernel_size,
                                  rotation=rotation, theta=theta, adjoint64={'float32': None, 'float64': True, 'first-step': 'first'}[adjoint_precision],
                                  detector_kernel=kwargs.get('detector_kernel', 'TF'),   # 'IR' / 'auto': np_funcs.py:51-61
                                  loss_type=loss_type, poisson_multiplier=poisson_multiplier, slice_binning=slice_binning,
-                                 detector_weights=weights, **geometry)
+                                 detector_weights=weights, **geo.for_level(ds_level))
         solver.set_volume(obj_delta, obj_beta)
         solver.set_mask(mask)
         solver.set_measurements(np.abs(prj))
@@ -242,8 +224,7 @@ def reconstruct_fullfield(fname, theta_st=0, theta_end=PI, n_epochs='auto', crit
         print_flush('Optimizer started.', 0, rank)
         if rank == 0:
             if trilinear:                        # the geometry this level ran with, behind the preset's lines
-                create_summary(output_folder, dict(locals(), rotation_matrices=None if rotation_matrices is None else 'given'),
-                               var_list=SUMMARY_PRESET_FF + SUMMARY_GEOMETRY)
+                create_summary(output_folder, dict(locals(), **geo.summary()), var_list=SUMMARY_PRESET_FF + SUMMARY_GEOMETRY)
             else:
                 create_summary(output_folder, locals(), preset='fullfield')
 

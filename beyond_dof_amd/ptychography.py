@@ -23,6 +23,7 @@ from ._lib import BdofError
 from .util import print_flush, split_tasks
 
 PI = util.PI
+ROTATIONS = ('trilinear',)     # the values of the rotation keyword this entry point acts on; any other stays ignored, as it always was
 
 
 def epoch_schedule(n_theta, n_pos, minibatch_size, rng):
@@ -86,14 +87,10 @@ def reconstruct_ptychography(fname, probe_pos, probe_size, obj_size, theta_st=0,
     # (the default with the transfer-function propagator: reconstructed delta within 2.1e-6 of the reference's float64 loop on golden
     # vector G17, 7.0e-6 with 'float32' — both inside 1e-5 since the kernels take dithered copies of the transfer function;
     # one slower step per epoch)
-    # rotation='trilinear': a rigid map per angle, sampled trilinearly (PtychoSolver), with the true angles theta =
-    # -linspace(theta_st, theta_end, n_theta) and axis_tilt / axis_roll (radians), center (the detector column the axis projects
-    # onto, a pixel index of the full-resolution volume) or rotation_matrices (n_theta, 3, 4) in full-resolution voxels; no
-    # lookup-table files are written.  Any other value of the keyword stays ignored, as it always was, and the four with it.
-    trilinear = kwargs.get('rotation') == 'trilinear'
-    rotation = 'trilinear' if trilinear else 'nearest'
-    axis_tilt, axis_roll = float(kwargs.get('axis_tilt', 0.)), float(kwargs.get('axis_roll', 0.))
-    center, rotation_matrices = kwargs.get('center'), kwargs.get('rotation_matrices')
+    # rotation='trilinear': a rigid map per angle (PtychoSolver) with the true angles theta = -linspace(theta_st, theta_end, n_theta)
+    # and the geometry keywords of util.RotationKeywords; no lookup-table files are written
+    geo = util.RotationKeywords(kwargs, only=ROTATIONS)
+    rotation, trilinear = geo.rotation, geo.trilinear
     adjoint_precision = kwargs.get('adjoint_precision', 'first-step')
     if adjoint_precision not in ('float32', 'float64', 'first-step'):
         raise ValueError("adjoint_precision must be 'float32', 'float64' or 'first-step'")
@@ -125,8 +122,7 @@ def reconstruct_ptychography(fname, probe_pos, probe_size, obj_size, theta_st=0,
         prj_theta_ind = prj_theta_ind[::theta_downsample]
         n_theta = len(prj_theta_ind)
     theta = -np.linspace(theta_st, theta_end, prj.shape[0], dtype='float32')[prj_theta_ind]
-    if trilinear and rotation_matrices is not None:
-        rotation_matrices = util.check_rigid(np.asarray(rotation_matrices, dtype=np.float64)[prj_theta_ind], n_theta).reshape(-1, 3, 4)
+    geo.select(n_theta, prj_theta_ind)
     original_shape = [n_theta] + list(prj.shape[1:])
     print_flush('Data shape: {}'.format(original_shape), 0, rank)
 
@@ -153,16 +149,7 @@ def reconstruct_ptychography(fname, probe_pos, probe_size, obj_size, theta_st=0,
             minibatch_size = n_pos
 
         coord_ls = None if trilinear else util.rotation_lookup_files(this_obj_size, n_theta, comm)
-        geometry = {}
-        if trilinear:
-            # the levels are strided: voxel i of this level is voxel i * ds_level of the full resolution, so an explicit centre
-            # and the translations divide by ds_level (the default centre is this level's own middle column)
-            geometry = dict(rotation=rotation, theta=theta, axis_tilt=axis_tilt, axis_roll=axis_roll,
-                            center=None if center is None else float(center) / ds_level)
-            if rotation_matrices is not None:
-                level = rotation_matrices.copy()
-                level[:, :, 3] /= ds_level
-                geometry['rotation_matrices'] = level
+        geometry = dict(geo.for_level(ds_level), rotation=rotation, theta=theta) if trilinear else {}
 
         np.random.seed(seed)                               # rank 0 initialises and broadcasts in the reference (:169-208)
         if first_level:
@@ -243,8 +230,7 @@ def reconstruct_ptychography(fname, probe_pos, probe_size, obj_size, theta_st=0,
         print_flush('Optimizer started.', 0, rank)
         if rank == 0:
             if trilinear:                        # the geometry behind the preset's lines
-                create_summary(output_folder, dict(locals(), rotation_matrices=None if rotation_matrices is None else 'given'),
-                               var_list=SUMMARY_PRESET_PTYCHO + SUMMARY_GEOMETRY)
+                create_summary(output_folder, dict(locals(), **geo.summary()), var_list=SUMMARY_PRESET_PTYCHO + SUMMARY_GEOMETRY)
             else:
                 create_summary(output_folder, locals(), preset='ptycho')
 

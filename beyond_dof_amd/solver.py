@@ -22,6 +22,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import DeviceBuffer
+from . import rotation as rotations
 from . import util
 from .comm import PseudoComm
 from .engine import MultisliceEngine, RESIDENT_SIZES, check_model_options
@@ -30,18 +31,6 @@ from .engine import MultisliceEngine, RESIDENT_SIZES, check_model_options
 def _check_options(propagator, adjoint64, *options, **path):
     """check_model_options with a solver's keywords: any adjoint64 that is on stands for the float64 path."""
     return check_model_options(*options, propagator=propagator, adjoint_precision='float64' if adjoint64 else None, **path)
-
-
-def _rigid_prm(n_theta, shape, theta, axis_tilt, axis_roll, center, rotation_matrices):
-    """(n_theta, 12) float64 rows of (M | t) for rotation='trilinear' from a solver's keywords (ValueError for what is missing, of
-    the wrong length or not rigid): rotation_matrices if given, else util.rigid_geometry of theta and the axis keywords."""
-    if theta is None and rotation_matrices is None:
-        raise ValueError("rotation='trilinear' needs the projection angles theta or rotation_matrices")
-    if rotation_matrices is not None:
-        return util.check_rigid(rotation_matrices, n_theta)
-    if len(np.atleast_1d(theta)) != int(n_theta):
-        raise ValueError('theta must hold n_theta = {} angles'.format(int(n_theta)))
-    return util.rigid_geometry(theta, shape, axis_tilt, axis_roll, center)
 
 
 class _VolumeSolver(object):
@@ -70,14 +59,8 @@ class _VolumeSolver(object):
         self.meas_all = None       # PtychoSolver.set_measurements
         self.comm.attach(self.ctx)
 
-    def _upload_rotation_tables(self, coord_ls):
-        if coord_ls is None:
-            coord_ls = util.rotation_lookup([self.dim_y, self.dim_x, self.dim_z], self.n_theta)
-        tables = util.device_rotation_tables(coord_ls, self.dim_x, self.dim_z)
-        self.tab, self.off, self.order = [DeviceBuffer.from_host(self.ctx, t) for t in tables]
-
     def _bind_volume(self):
-        self.eng.set_volume(self.x[self.cur], self.dim_x * self.dim_z, self.dim_y, self.tab, self.dim_x, self.n_theta)
+        self.rot.bind_volume(self.eng, self.x[self.cur])
 
     # ---- the streaming engine's fused forward sweep (MultisliceEngine.set_sweep_fusion) ---------
     def set_sweep_fusion(self, mode):
@@ -424,12 +407,10 @@ class FullfieldSolver(_VolumeSolver):
         self.n_planes = _check_options(propagator, adjoint64, loss_type, poisson_multiplier, detector_weights, slice_binning, free_prop_cm,
                                        rotation=rotation if rotation in ('bilinear', 'trilinear') else 'nearest', recompute=recompute, detector_kernel=detector_kernel)
         self.conv = propagator == 'conv'
-        self.bilinear = rotation == 'bilinear'
-        self.trilinear = rotation == 'trilinear'
-        self.materialised = self.bilinear or self.trilinear      # the minibatch's rotated objects are written out every step
+        materialised = rotation in rotations.KINDS               # the minibatch's rotated objects are written out every step
         if adjoint64 not in (None, False, True, 'first'):
             raise ValueError("adjoint64 must be None, False, True or 'first'")
-        if adjoint64 and self.materialised and (self.conv or adjoint64 == 'first'):
+        if adjoint64 and materialised and (self.conv or adjoint64 == 'first'):
             raise ValueError("the float64 paths (adjoint64='first'; propagator='conv') run with the lookup-table rotation")
         # 'first': the first minibatch of every epoch through the model's float64 path on the same context (bdof_loss_grad_tf_f64 /
         # bdof_loss_grad_conv_f64), as PtychoSolver does it; True: every minibatch — the engine's float64 adjoint sweep
@@ -438,10 +419,8 @@ class FullfieldSolver(_VolumeSolver):
         adjoint64 = adjoint64 is True and not self.conv
         if rotation not in ('nearest', 'bilinear', 'trilinear'):
             raise ValueError("rotation must be 'nearest', 'bilinear' or 'trilinear'")
-        if self.bilinear and theta is None:
-            raise ValueError("rotation='bilinear' needs the projection angles theta")
-        if self.trilinear:       # (M | t) per angle, float64: checked here, before anything is allocated on the device
-            rot_prm = _rigid_prm(n_theta, (dim_y, dim_x, dim_z), theta, axis_tilt, axis_roll, center, rotation_matrices)
+        # the rotation's host side (for a materialised kind its float64 rows per angle): checked here, before anything is allocated
+        self.rot = rotations.choose(rotation, (dim_y, dim_x, dim_z), n_theta, coord_ls, theta, (axis_tilt, axis_roll, center, rotation_matrices))
         self.dim_y, self.dim_x, self.dim_z = int(dim_y), int(dim_x), int(dim_z)
         self.n_theta, self.mb = int(n_theta), int(minibatch_size)
         self.comm = comm or PseudoComm()
@@ -460,44 +439,13 @@ class FullfieldSolver(_VolumeSolver):
         self.eng.set_probe(probe_real, probe_imag)
         if self.f64:
             self._enable_f64()
-        if self.bilinear:
-            # per-angle projective transform of tf.contrib.image.rotate for images of height X and width Z, in float64
-            th = np.asarray(theta, dtype=np.float64)
-            assert len(th) == self.n_theta
-            H, W = self.dim_x, self.dim_z
-            c, sn = np.cos(th), np.sin(th)
-            self.rot_prm = np.stack([c, sn, ((W - 1) - (c * (W - 1) - sn * (H - 1))) / 2.0, ((H - 1) - (sn * (W - 1) + c * (H - 1))) / 2.0], axis=1)
-        elif self.trilinear:
-            self.rot_prm = rot_prm
-        if self.materialised:
-            lib = self.ctx.lib
-            self._bind_rotated, self._rotation_adjoint = (lib.bdof_set_object_bilinear, lib.bdof_rotate_bilinear_adjoint) if self.bilinear \
-                else (lib.bdof_set_object_rigid, lib.bdof_rotate_rigid_adjoint)
-            self.prm_buf = DeviceBuffer(self.ctx, self.mb * self.rot_prm.shape[1] * 8, np.float64, (self.mb, self.rot_prm.shape[1]))
-            self.tab = self.off = self.order = None
-        else:
-            # rotation lookup tables (cnn_propagator/util.py:294-347), uploaded once
-            self._upload_rotation_tables(coord_ls)
+        self.rot.allocate(self.ctx, self.mb)
         self._init_volume()
         self.meas_stage = DeviceBuffer(self.ctx, self.mb * self.n_planes * self.dim_x * self.dim_y * 4, np.float32,
                                        (self.mb, self.dim_x, self.dim_y) if self.n_planes == 1 else (self.mb, self.n_planes, self.dim_x, self.dim_y))
         self.angle_buf = DeviceBuffer(self.ctx, self.mb * 4, np.int32, (self.mb,))
         self._bind_volume()
-        if not self.materialised:
-            self.eng.set_rotation_adjoint(self.off, self.order, self.dim_x * self.dim_z)
-
-    def _bind_volume(self):
-        if not self.materialised:    # (else the engine's object is the minibatch's rotated copy, rebuilt at every step: _rotate_batch)
-            _VolumeSolver._bind_volume(self)
-
-    def _rotate_batch(self, idx, B):
-        """Materialised rotation (bilinear or trilinear) of the current volume to the B angles idx, bound as a batch of rotated
-        objects: one pass that writes the rotated objects' modulation factors into the ctx (bdof_set_object_bilinear / _rigid)."""
-        prm = np.zeros(self.prm_buf.shape)
-        prm[:B] = self.rot_prm[np.asarray(idx)]
-        self.prm_buf.upload(prm)
-        self.ctx.check(self._bind_rotated(self.ctx.handle, self.x[self.cur].ptr, self.dim_x, self.dim_z, self.dim_y, self.prm_buf.ptr, B,
-                                          int(self.conv)))
+        self.rot.attach(self.eng)
 
     def set_measurements(self, prj_abs):
         """|prj| for every angle, (n_theta, Y, X) — with D detector planes (n_theta, D, Y, X) — (loss uses np.abs(this_prj_batch),
@@ -521,28 +469,19 @@ class FullfieldSolver(_VolumeSolver):
         f64: through the transfer-function model's float64 path on the same context (bdof_loss_grad_tf_f64)."""
         self._stage_batch(angle_idx)
         if f64:
-            if self.materialised:
+            if not self.rot.float64_paths:
                 raise ValueError("f64: the float64 paths run with the lookup-table rotation")
             if self.conv and not self.eng.conv_f64:      # (a probe or physics set since the last call unbound the twin)
                 self.eng.enable_conv_f64()
             if not self.conv and not self.eng.tf_f64:
                 self.eng.enable_tf_f64()
-        elif self.materialised:
-            self._rotate_batch(angle_idx, self.mb)
-        self.eng.loss_grad_device(self.mb, None if self.materialised else self.angle_buf.ptr, None, None, self.meas_stage.ptr,
+        else:
+            self.rot.stage(self.eng, self.x[self.cur], angle_idx, self.mb, self.conv)
+        self.eng.loss_grad_device(self.mb, self.rot.angle_arg(self.angle_buf.ptr), None, None, self.meas_stage.ptr,
                                   conv=self.conv, f64=f64)
 
     def _produce(self, accumulate=False):
-        lib, h = self.ctx.lib, self.ctx.handle
-
-        def produce(x0, nx):
-            if self.materialised:
-                self.ctx.check(self._rotation_adjoint(h, lib.bdof_grot(h), self.dim_x, self.dim_z, self.dim_y, self.prm_buf.ptr,
-                                                      self.mb, self.g.ptr, x0 * self.dim_z, nx * self.dim_z, int(accumulate), 1.0))
-            else:
-                self.ctx.check(lib.bdof_rotation_adjoint_rows(h, self.mb, self.angle_buf.ptr, self.g.ptr, x0 * self.dim_z,
-                                                              nx * self.dim_z, int(accumulate), 1.0))
-        return produce
+        return lambda x0, nx: self.rot.adjoint(self.angle_buf, self.g, x0, nx, accumulate)
 
     def loss_and_grad(self, angle_idx, want_loss=True, f64=False):
         """Data-term loss and its gradient w.r.t. the volume for this rank's angles (left in self.g, not reduced).  f64: both
@@ -574,10 +513,9 @@ class FullfieldSolver(_VolumeSolver):
         self._g_stale = True
 
     def _dry_tail(self, n_slabs, sharded):
-        self.angle_buf.upload(np.arange(self.mb, dtype=np.int32) % self.n_theta)
-        if self.materialised:
-            prm = self.rot_prm[np.arange(self.mb) % self.n_theta]
-            self.prm_buf.upload(np.ascontiguousarray(prm))
+        idx = np.arange(self.mb, dtype=np.int32) % self.n_theta
+        self.angle_buf.upload(idx)
+        self.rot.stage_angles(idx)
         self._tail(self._produce(), 0, 0.0, n_slabs=n_slabs, sharded=sharded, flip=False)
 
     def step(self, i_batch, angle_idx, learning_rate, alpha_d=0.0, alpha_b=0.0, gamma=0.0, want_loss=False, n_slabs=None,
@@ -600,8 +538,8 @@ class FullfieldSolver(_VolumeSolver):
                            sharded, n_acc=n_acc)
                 self._probe_apply()
         else:
-            # one rank, lookup-table rotation: nothing happens between the rotation adjoint and Adam
-            one_pass = self._one_pass_tail if not self._reduces() and not self.materialised else None
+            # one rank, a rotation that carries it (the lookup tables): nothing happens between the rotation adjoint and Adam
+            one_pass = self._one_pass_tail if not self._reduces() and self.rot.one_pass_tail else None
             self._tail(self._produce(), i_batch, learning_rate, alpha_d, alpha_b, gamma, clip, use_mask, n_slabs, sharded, one_pass=one_pass)
             self._probe_apply()
         return self._get_loss() if want_loss else None          # the loss of THIS minibatch stays on the device until the next one
@@ -613,11 +551,8 @@ class FullfieldSolver(_VolumeSolver):
         out = []
         for i in range(0, len(idx), self.mb):
             chunk = idx[i:i + self.mb]
-            if self.materialised:
-                self._rotate_batch(chunk, len(chunk))
-                out.append(self.eng.forward(len(chunk), conv=self.conv))
-            else:
-                out.append(self.eng.forward(len(chunk), angle_idx=chunk, conv=self.conv))
+            self.rot.stage(self.eng, self.x[self.cur], chunk, len(chunk), self.conv)
+            out.append(self.eng.forward(len(chunk), angle_idx=self.rot.angle_arg(chunk), conv=self.conv))
         return np.concatenate(out, axis=0)
 
 
@@ -630,11 +565,8 @@ class PtychoSolver(_VolumeSolver):
                  adjoint64=None, engine=None, loss_type='lsq', poisson_multiplier=2e6, slice_binning=1, detector_weights=None,
                  rotation='nearest', theta=None, axis_tilt=0., axis_roll=0., center=None, rotation_matrices=None):
         """rotation='nearest': the lookup tables.  'trilinear': the rigid map of FullfieldSolver(rotation='trilinear'), with the same
-        theta / axis_tilt / axis_roll / center / rotation_matrices (tilt 0: ptychography's interpolating rotation).  A minibatch has
-        one angle, so per step the volume is rotated once into a plain (delta, beta) copy (bdof_rotate_rigid, B = 1), the copy is
-        bound under a one-angle identity table, the windows run with angle 0 on whichever engine and precision was chosen, the
-        window adjoint fills a rotated-frame gradient through the identity's inverse tables and bdof_rotate_rigid_adjoint takes it
-        into the volume's.  slice_binning > 1 keeps to rotation='nearest'.
+        theta / axis_tilt / axis_roll / center / rotation_matrices (tilt 0: ptychography's interpolating rotation), through a rotated
+        copy per step (rotation.RotatedCopy).  slice_binning > 1 keeps to rotation='nearest'.
         loss_type / poisson_multiplier: the data term (MultisliceEngine.set_loss; 'poisson' with propagator='fft' only).
         detector_weights: one (py, px) plane of weights >= 0 for every diffraction pattern, fftshifted as the patterns are
         (MultisliceEngine.set_detector_weights; 0: dead pixel, beamstop), set before any measurement is bound; propagator='fft' only.
@@ -644,12 +576,11 @@ class PtychoSolver(_VolumeSolver):
         'generic', 'streaming' or 'resident' go to MultisliceEngine(engine=...) as they are."""
         if rotation not in ('nearest', 'trilinear'):
             raise ValueError("rotation must be 'nearest' or 'trilinear'")
-        self.trilinear = rotation == 'trilinear'
         _check_options(propagator, adjoint64, loss_type, poisson_multiplier, detector_weights, slice_binning, rotation=rotation)
         self.conv = propagator == 'conv'
         self.dim_y, self.dim_x, self.dim_z = [int(s) for s in obj_size]
-        if self.trilinear:
-            self.rot_prm = _rigid_prm(n_theta, (self.dim_y, self.dim_x, self.dim_z), theta, axis_tilt, axis_roll, center, rotation_matrices)
+        self.rot = rotations.choose(rotation, obj_size, n_theta, coord_ls, theta, (axis_tilt, axis_roll, center, rotation_matrices),
+                                    materialised=rotations.RotatedCopy)
         self.py, self.px = int(probe_size[0]), int(probe_size[1])
         self.n_theta, self.mb = int(n_theta), int(minibatch_size)
         self.comm = comm or PseudoComm()
@@ -678,35 +609,13 @@ class PtychoSolver(_VolumeSolver):
             self.f64 = adjoint64
         elif adjoint64 not in (None, False, True):
             raise ValueError("adjoint64 must be None, False, True or 'first'")
-        if self.trilinear:
-            # the rotated copy [z][x][y] and its gradient, and the identity tables of one angle: rotated row (z, x) is row z X + x
-            n_rows = self.dim_z * self.dim_x
-            self.rot_copy = DeviceBuffer.zeros(self.ctx, (self.dim_z, self.dim_x, self.dim_y, 2), np.float32)
-            self.g_rot = DeviceBuffer.zeros(self.ctx, (self.dim_z, self.dim_x, self.dim_y, 2), np.float32)
-            self.prm_buf = DeviceBuffer(self.ctx, 12 * 8, np.float64, (1, 12))
-            self.tab = DeviceBuffer.from_host(self.ctx, np.arange(n_rows, dtype=np.int32).reshape(1, self.dim_z, self.dim_x))
-            self.off = DeviceBuffer.from_host(self.ctx, np.arange(n_rows + 1, dtype=np.int32).reshape(1, -1))
-            self.order = DeviceBuffer.from_host(self.ctx, np.arange(n_rows, dtype=np.int32).reshape(1, -1))
-        else:
-            self._upload_rotation_tables(coord_ls)
+        self.rot.allocate(self.ctx, self.mb)
         self._init_volume()
         self.meas_stage = DeviceBuffer(self.ctx, self.mb * self.py * self.px * 4, np.float32, (self.mb, self.py, self.px))
         self.idx_buf = DeviceBuffer(self.ctx, 4 * self.mb * 4, np.int32, (4, self.mb))
         self._bind_volume()
-        self.eng.set_rotation_adjoint(self.off, self.order, self.dim_x * self.dim_z)
+        self.rot.attach(self.eng)
         self._last = None
-
-    def _bind_volume(self):
-        if not self.trilinear:       # (else the engine's object is the rotated copy of the step's angle: _rotate_to)
-            _VolumeSolver._bind_volume(self)
-
-    def _rotate_to(self, i_theta):
-        """rotation='trilinear': the current volume under angle i_theta's rigid map as plain (delta, beta) rows, bound with the
-        identity table (again at every call: that memory has changed)."""
-        lib, h = self.ctx.lib, self.ctx.handle
-        self.prm_buf.upload(np.ascontiguousarray(self.rot_prm[int(i_theta)][None]))
-        self.ctx.check(lib.bdof_rotate_rigid(h, self.x[self.cur].ptr, self.dim_x, self.dim_z, self.dim_y, self.prm_buf.ptr, 1, self.rot_copy.ptr))
-        self.eng.set_volume(self.rot_copy, self.dim_z * self.dim_x, self.dim_y, self.tab, self.dim_x, 1)
 
     def set_measurements(self, prj_abs_all):
         """All diffraction amplitudes |prj| (n_theta, n_pos, py, px) resident on the device (a cfg5-sized dataset is 0.75 GB):
@@ -719,7 +628,7 @@ class PtychoSolver(_VolumeSolver):
     def _stage(self, i_theta, pos_idx, prj_abs_batch):
         pos = self.probe_pos[np.asarray(pos_idx)]
         idx = np.empty((4, self.mb), dtype=np.int32)
-        idx[0] = 0 if self.trilinear else i_theta      # trilinear: the bound copy is already rotated, its one table is the identity
+        idx[0] = self.rot.window_angle(i_theta)
         idx[1] = pos[:, 1] - self.half[1]            # window origin in x (axis 1), ptychography.py:68-70
         idx[2] = pos[:, 0] - self.half[0]            # window origin in y (axis 0)
         idx[3] = 0
@@ -739,21 +648,14 @@ class PtychoSolver(_VolumeSolver):
     def _win_loss_grad(self, i_theta, pos_idx, prj_abs_batch, use64=False):
         a, xo, yo = self._stage(i_theta, pos_idx, prj_abs_batch)
         f64 = self.f64 is True or (use64 and self.f64 == 'first')
-        if self.trilinear:
-            self._rotate_to(i_theta)
+        self.rot.stage(self.eng, self.x[self.cur], [int(i_theta)], 1, self.conv)
         self.eng.loss_grad_device(self.mb, a, xo, yo, self.meas_stage.ptr, conv=self.conv, f64=f64)
-        self._last = (0 if self.trilinear else int(i_theta), xo, yo)
+        self._last = (int(i_theta), xo, yo)
 
     def _produce_all(self):
         i_theta, xo, yo = self._last
         self._g_is_local()
-        lib, h = self.ctx.lib, self.ctx.handle
-        if self.trilinear:           # windows -> rotated frame (identity tables) -> volume frame (prm_buf still holds the step's angle)
-            self.ctx.check(lib.bdof_window_rotation_adjoint(h, self.mb, 0, xo, yo, self.g_rot.ptr, 0, 1.0))
-            self.ctx.check(lib.bdof_rotate_rigid_adjoint(h, self.g_rot.ptr, self.dim_x, self.dim_z, self.dim_y, self.prm_buf.ptr, 1,
-                                                         self.g.ptr, 0, self.dim_x * self.dim_z, 0, 1.0))
-        else:
-            self.ctx.check(lib.bdof_window_rotation_adjoint(h, self.mb, i_theta, xo, yo, self.g.ptr, 0, 1.0))
+        self.rot.window_adjoint(i_theta, xo, yo, self.g)
 
     def loss_and_grad(self, i_theta, pos_idx, prj_abs_batch=None, want_loss=True, f64=False):
         """prj_abs_batch: |this_prj_batch| (mb, py, px) for probe positions pos_idx at angle i_theta (None: from the resident
@@ -780,10 +682,8 @@ class PtychoSolver(_VolumeSolver):
 
     def forward(self, i_theta, pos_idx):
         pos = self.probe_pos[np.asarray(pos_idx)]
-        if self.trilinear:
-            self._rotate_to(i_theta)
-            i_theta = 0
-        return self.eng.forward(len(pos), angle_idx=[i_theta] * len(pos), xoff=pos[:, 1] - self.half[1],
+        self.rot.stage(self.eng, self.x[self.cur], [int(i_theta)], 1, self.conv)
+        return self.eng.forward(len(pos), angle_idx=[self.rot.window_angle(i_theta)] * len(pos), xoff=pos[:, 1] - self.half[1],
                                 yoff=pos[:, 0] - self.half[0], conv=self.conv)
 
     def adam_update(self, i_batch, learning_rate, clip=True):

@@ -356,6 +356,70 @@ def check_rigid(rotation_matrices, n_theta):
     return np.ascontiguousarray(m.reshape(len(m), 12))
 
 
+def rigid_prm(n_theta, shape, theta, axis_tilt=0., axis_roll=0., center=None, rotation_matrices=None):
+    """(n_theta, 12) float64 rows of (M | t) for rotation='trilinear' from a solver's keywords (ValueError for what is missing, of
+    the wrong length or not rigid): rotation_matrices if given, else rigid_geometry of theta and the axis keywords."""
+    if theta is None and rotation_matrices is None:
+        raise ValueError("rotation='trilinear' needs the projection angles theta or rotation_matrices")
+    if rotation_matrices is not None:
+        return check_rigid(rotation_matrices, n_theta)
+    if len(np.atleast_1d(theta)) != int(n_theta):
+        raise ValueError('theta must hold n_theta = {} angles'.format(int(n_theta)))
+    return rigid_geometry(theta, shape, axis_tilt, axis_roll, center)
+
+
+def bilinear_prm(n_theta, shape, theta, *ignored):
+    """(n_theta, 4) float64 rows (cos, sin, x_off, y_off) for rotation='bilinear': the per-angle projective transform of
+    tf.contrib.image.rotate for images of height X and width Z of a (Y, X, Z) volume; the geometry keywords are ignored."""
+    if theta is None:
+        raise ValueError("rotation='bilinear' needs the projection angles theta")
+    th = np.asarray(theta, dtype=np.float64)
+    assert len(th) == int(n_theta)
+    H, W = int(shape[1]), int(shape[2])
+    c, sn = np.cos(th), np.sin(th)
+    return np.stack([c, sn, ((W - 1) - (c * (W - 1) - sn * (H - 1))) / 2.0, ((H - 1) - (sn * (W - 1) + c * (H - 1))) / 2.0], axis=1)
+
+
+class RotationKeywords(object):
+    """The rotation keywords of an entry point's **kwargs.  rotation: the value as given ('nearest' if absent); with `only`, a
+    value outside it stays ignored and counts as 'nearest'.  For rotation='trilinear' — a rigid map per angle, sampled trilinearly —
+    the geometry: axis_tilt / axis_roll (radians), center (the detector column the axis projects onto, a pixel index of the
+    full-resolution data) or rotation_matrices (n_theta, 3, 4) in voxels of the full-resolution volume.  With any other rotation
+    the four are ignored and for_level gives no keyword."""
+
+    def __init__(self, kwargs, only=None):
+        self.rotation = kwargs.get('rotation', 'nearest')
+        if only is not None and self.rotation not in only:
+            self.rotation = 'nearest'
+        self.trilinear = self.rotation == 'trilinear'
+        self.axis_tilt, self.axis_roll = float(kwargs.get('axis_tilt', 0.)), float(kwargs.get('axis_roll', 0.))
+        self.center, self.rotation_matrices = kwargs.get('center'), kwargs.get('rotation_matrices')
+
+    def select(self, n_theta, index=None):
+        """Once the data are read: keep the rotation_matrices of the angles the run keeps (index: a slice or an index array, as
+        theta_downsample picks them) and hold them to check_rigid for the n_theta that are left."""
+        if self.trilinear and self.rotation_matrices is not None:
+            m = np.asarray(self.rotation_matrices, dtype=np.float64)
+            self.rotation_matrices = check_rigid(m if index is None else m[index], n_theta).reshape(-1, 3, 4)
+
+    def for_level(self, ds_level):
+        """The solver's geometry keywords at multiscale level ds_level.  The levels are strided, not binned: voxel i of a level is
+        voxel i * ds_level of the full resolution, so an explicit centre and the translations divide by ds_level (the default
+        centre is the level's own middle column)."""
+        if not self.trilinear:
+            return {}
+        geometry = dict(axis_tilt=self.axis_tilt, axis_roll=self.axis_roll, center=None if self.center is None else float(self.center) / ds_level)
+        if self.rotation_matrices is not None:
+            level = self.rotation_matrices.copy()
+            level[:, :, 3] /= ds_level
+            geometry['rotation_matrices'] = level
+        return geometry
+
+    def summary(self):
+        """The geometry as a run's summary records it (the matrices only as 'given')."""
+        return dict(self.for_level(1), center=self.center, rotation_matrices=None if self.rotation_matrices is None else 'given')
+
+
 def split_tasks(arr, split_size):
     """cnn_propagator/util.py:271-277."""
     return [arr[i:i + split_size] for i in range(0, len(arr), split_size)]

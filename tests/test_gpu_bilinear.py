@@ -51,7 +51,7 @@ def test_bilinear_rotation_forward_gradient_and_adam(fp):
     from beyond_dof_amd._lib import DeviceBuffer
     lib, h = s.ctx.lib, s.ctx.handle
     rows = DeviceBuffer(s.ctx, mb * n * n * n * 8, np.float32, (mb, n, n, n, 2))
-    prm = DeviceBuffer.from_host(s.ctx, np.ascontiguousarray(s.rot_prm[idx]))
+    prm = DeviceBuffer.from_host(s.ctx, np.ascontiguousarray(s.rot.prm[idx]))
     s.ctx.check(lib.bdof_rotate_bilinear(h, s.x[s.cur].ptr, n, n, n, prm.ptr, mb, rows.ptr))
     s.ctx.sync()
     got = rows.download()                                                 # [b][z][x][y][2]
@@ -123,7 +123,7 @@ def test_bilinear_binding_for_the_real_space_propagator():
     w = s.forward_angles(idx)                                             # fused binding, conv sweep
     lib, h = s.ctx.lib, s.ctx.handle
     rows = DeviceBuffer(s.ctx, mb * n * n * n * 8, np.float32, (mb, n, n, n, 2))
-    prm = DeviceBuffer.from_host(s.ctx, np.ascontiguousarray(s.rot_prm[idx]))
+    prm = DeviceBuffer.from_host(s.ctx, np.ascontiguousarray(s.rot.prm[idx]))
     s.ctx.check(lib.bdof_rotate_bilinear(h, s.x[s.cur].ptr, n, n, n, prm.ptr, mb, rows.ptr))
     s.eng.set_volume(rows, mb * n * n, n, None, 0, 0)
     assert np.array_equal(s.eng.forward(mb, conv=True), w)

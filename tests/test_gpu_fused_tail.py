@@ -203,7 +203,7 @@ def test_refusals(case):
     assert all(np.array_equal(p, q) for p, q in zip(before[0] + before[1:], after[0] + after[1:]))      # nothing ran
     bil = FullfieldSolver(N, N, N, 4, 2, E, PS, free_prop_cm=None, rotation='bilinear', theta=np.linspace(0, np.pi, 4, endpoint=False))
     bil.set_volume(case['od'], case['ob'])
-    bil._rotate_batch(np.array([0, 1]), 2)                            # the object is now bound as a batch of rotated factors
+    bil.rot.stage(bil.eng, bil.x[bil.cur], np.array([0, 1]), 2, bil.conv)                            # the object is now bound as a batch of rotated factors
     with pytest.raises(BdofError, match='does not carry the bilinear rotation'):
         _call_fused(bil)
 

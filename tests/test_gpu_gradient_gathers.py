@@ -119,7 +119,7 @@ BILIN_NXV, BILIN_NZV = 7, 10
 
 
 def bilinear_prm(theta, H, W):
-    """the solver's own expression (solver.py, rot_prm)"""
+    """the solver's own expression (util.bilinear_prm)"""
     th = np.asarray(theta, dtype=np.float64)
     c, sn = np.cos(th), np.sin(th)
     return np.stack([c, sn, ((W - 1) - (c * (W - 1) - sn * (H - 1))) / 2.0, ((H - 1) - (sn * (W - 1) + c * (H - 1))) / 2.0], axis=1)

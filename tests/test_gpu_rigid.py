@@ -37,11 +37,12 @@ def _geometry(how):
 
 @pytest.mark.parametrize('fp,how', [(1e-4, 'keywords'), (None, 'keywords'), (1e-4, 'matrices')])
 def test_trilinear_rotation_forward_gradient_and_adam(built, fp, how):
+    from beyond_dof_amd import rotation
     from beyond_dof_amd.solver import FullfieldSolver
     p = rr.solver_problem(fp)
     geo = _geometry(how)
     s = FullfieldSolver(N, N, N, N_THETA, MB, rr.E_EV, rr.PSIZE_CM, free_prop_cm=fp, rotation='trilinear', **geo)
-    assert s.materialised and s.trilinear and not s.bilinear
+    assert type(s.rot) is rotation.MaterialisedRotation and s.rot.kind is rotation.KINDS['trilinear'] and s.rot.kind is not rotation.KINDS['bilinear']
     s.set_volume(p['od'], p['ob'])
     w = s.forward_angles(IDX)
     e_int, e_wave = rel(np.abs(w) ** 2, np.abs(p['wave']) ** 2), rel(w, p['wave'])
@@ -87,7 +88,7 @@ def test_trilinear_binding_for_the_real_space_propagator(built):
     w = s.forward_angles(IDX)                                             # fused binding, conv sweep
     lib, h = s.ctx.lib, s.ctx.handle
     rows = DeviceBuffer(s.ctx, MB * N * N * N * 8, np.float32, (MB, N, N, N, 2))
-    prm = DeviceBuffer.from_host(s.ctx, np.ascontiguousarray(s.rot_prm[IDX]))
+    prm = DeviceBuffer.from_host(s.ctx, np.ascontiguousarray(s.rot.prm[IDX]))
     s.ctx.check(lib.bdof_rotate_rigid(h, s.x[s.cur].ptr, N, N, N, prm.ptr, MB, rows.ptr))
     s.eng.set_volume(rows, MB * N * N, N, None, 0, 0)
     assert np.any(np.abs(w - 1) > 1e-4) and np.array_equal(s.eng.forward(MB, conv=True), w)

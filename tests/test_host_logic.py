@@ -179,6 +179,61 @@ def test_adjoint_precision_values_are_checked_before_anything_touches_a_gpu(tmp_
                                  adjoint_precision='first')
 
 
+def test_rotation_keywords_of_the_entry_points():
+    """util.RotationKeywords, the one reader of rotation / axis_tilt / axis_roll / center / rotation_matrices for both entry points:
+    per multiscale level an explicit centre and column 3 of every (3, 4) matrix divide by ds_level, a None centre stays None; the
+    angle selection is applied before check_rigid; what is not rigid is a ValueError; each entry point's rule for the rotation
+    keyword is the one it always had."""
+    import pytest
+    from beyond_dof_amd import ptychography
+    from beyond_dof_amd.solver import FullfieldSolver, PtychoSolver
+    c, s = 0.6, 0.8                                                    # an exact rotation about y by a 3-4-5 angle
+    M = np.array([[c, s, 0.], [-s, c, 0.], [0., 0., 1.]])
+    mats = np.stack([np.concatenate([M if i % 2 else np.eye(3), [[8. * i + 4.], [-16.], [2.]]], axis=1) for i in range(4)])
+    geo = util.RotationKeywords(dict(rotation='trilinear', axis_tilt=0.5, axis_roll='0.25', center=30, rotation_matrices=mats.tolist()))
+    assert geo.rotation == 'trilinear' and geo.trilinear
+    with pytest.raises(ValueError, match=r'\(2, 3, 4\)'):            # four matrices for two angles: the selection comes first
+        util.RotationKeywords(dict(rotation='trilinear', rotation_matrices=mats)).select(2)
+    geo.select(2, slice(None, None, 2))                                # theta_downsample = 2 keeps angles 0 and 2
+    for ds, center, t0 in ((1, 30., [4., 20.]), (2, 15., [2., 10.]), (4, 7.5, [1., 5.])):
+        kw = geo.for_level(ds)
+        assert sorted(kw) == ['axis_roll', 'axis_tilt', 'center', 'rotation_matrices']
+        assert kw['axis_tilt'] == 0.5 and kw['axis_roll'] == 0.25 and kw['center'] == center
+        m = kw['rotation_matrices']
+        assert m.shape == (2, 3, 4) and np.array_equal(m[:, :, :3], np.stack([np.eye(3)] * 2))      # only column 3 is divided
+        assert np.array_equal(m[:, 0, 3], t0) and np.array_equal(m[:, 1, 3], [-16. / ds] * 2) and np.array_equal(m[:, 2, 3], [2. / ds] * 2)
+    assert np.array_equal(geo.for_level(1)['rotation_matrices'], mats[::2])                     # a level does not change the record
+    # an index array selects as a slice does (reconstruct_ptychography); no centre, no matrices
+    odd = util.RotationKeywords(dict(rotation='trilinear', rotation_matrices=mats))
+    odd.select(2, np.array([1, 3]))
+    assert np.array_equal(odd.for_level(2)['rotation_matrices'][:, :, :3], np.stack([M] * 2))
+    assert np.array_equal(odd.for_level(2)['rotation_matrices'][:, 0, 3], [6., 14.])
+    plain = util.RotationKeywords(dict(rotation='trilinear'))
+    plain.select(3)
+    assert all(plain.for_level(ds) == dict(axis_tilt=0., axis_roll=0., center=None) for ds in (1, 2, 4))
+    sheared = mats.copy()
+    sheared[1, 0, 1] += 1e-3
+    with pytest.raises(ValueError, match='rigid'):
+        util.RotationKeywords(dict(rotation='trilinear', rotation_matrices=sheared)).select(4)
+    util.RotationKeywords(dict(rotation='trilinear', rotation_matrices=sheared)).select(2, slice(None, None, 2))     # ... of a kept angle only
+    # the geometry is ignored with any other rotation, whatever it holds
+    for rot in ('nearest', 'bilinear'):
+        other = util.RotationKeywords(dict(rotation=rot, center=3, rotation_matrices=sheared))
+        other.select(2)
+        assert other.rotation == rot and other.for_level(2) == {}
+    # reconstruct_fullfield hands any value on (the solver refuses what it does not know); reconstruct_ptychography acts on
+    # 'trilinear' alone and ignores every other value
+    assert util.RotationKeywords({}).rotation == 'nearest' and util.RotationKeywords(dict(rotation='cubic')).rotation == 'cubic'
+    assert ptychography.ROTATIONS == ('trilinear',)
+    assert [util.RotationKeywords(dict(rotation=r), only=ptychography.ROTATIONS).rotation for r in ('trilinear', 'nearest', 'bilinear', 'cubic', None)] \
+        == ['trilinear', 'nearest', 'nearest', 'nearest', 'nearest']
+    assert util.RotationKeywords({}, only=ptychography.ROTATIONS).rotation == 'nearest'
+    with pytest.raises(ValueError, match="rotation must be 'nearest', 'bilinear' or 'trilinear'"):
+        FullfieldSolver(8, 8, 8, 2, 1, 5000., 1e-7, rotation='cubic')
+    with pytest.raises(ValueError, match="rotation must be 'nearest' or 'trilinear'"):
+        PtychoSolver((8, 8, 8), (4, 4), [(4, 4)], 2, 1, 5000., 1e-7, np.ones((4, 4)), np.zeros((4, 4)), rotation='bilinear')
+
+
 def test_tiled_propagator_auto_halo():
     """TiledPropagator(halo='auto') (host arithmetic only): 64 pixels for plain stitching; with the long-range correction twice the
     band edge's reach over one 16-slice range plus 16 pixels — 24 at 5 keV / 1 nm (81 tiles of 512^2 on the 4096^2 field) — or plus 40

@@ -53,7 +53,7 @@ def one_mode(mode, n, mb, steps, warmup):
     for i in range(warmup):
         s.step(i, idx, **hyper)
     out = {'step_ms': timed(lambda i: s.step(warmup + i, idx, **hyper), steps)}
-    out['bind_ms'] = timed(lambda i: s._rotate_batch(idx, mb), steps)
+    out['bind_ms'] = timed(lambda i: s.rot.stage(s.eng, s.x[s.cur], idx, mb, s.conv), steps)
     s._rot_loss_grad(idx)                       # a rotated-frame gradient for the adjoint to take back
     out['adjoint_ms'] = timed(lambda i: s._produce()(0, n), steps)
     return {k: round(v, 3) for k, v in out.items()}
