@@ -208,6 +208,7 @@ struct bdof_ctx : Workspace {
     DevBuf<float2> winpad;                      // [S][volNX][volNY] rotated-frame gradient of the ptychography windows
     DevBuf<int> win_angle;                      // device copy of the batch's angle index
     DevBuf<int> heavy;                          // [1 + n_dest]: counter + deferred rows of the rotation adjoint
+    DevBuf<double> prm_partial;                 // [B][P][12] per-workgroup records of bdof_rotate_rigid_param_grad (grown on demand)
     // profiling
     bool prof = false;
     int prof_stride = 1;                        // time every prof_stride-th launch of a class
@@ -3252,7 +3253,8 @@ struct RotBilinear {
 };
 struct RotRigid {
     using Prm = double;
-    static constexpr const char *rotate = "bdof_rotate_rigid", *set_object = "bdof_set_object_rigid", *adjoint = "bdof_rotate_rigid_adjoint";
+    static constexpr const char *rotate = "bdof_rotate_rigid", *set_object = "bdof_set_object_rigid", *adjoint = "bdof_rotate_rigid_adjoint",
+                                *param_grad = "bdof_rotate_rigid_param_grad";
     // an even NY as for the bilinear kind, and a volume and a rotated batch whose voxel indices the kernels hold in an int
     static int shape(bdof_ctx* c, const char* who, int NXv, int NZv, int NYv, int B) {
         if (int r = RotBilinear::shape(c, who, NXv, NZv, NYv, B)) return r;
@@ -3310,6 +3312,27 @@ static int rotate_adjoint(bdof_ctx* c, const void* grot, int NXv, int NZv, int N
     return launched(c);
 }
 
+// dL/d(M | t) of the rigid kind only (bdof_rigid.h): the shape rule of its other three calls, the rotated-frame gradient the
+// adjoint would take (grot; nullptr: the ctx's own), per-workgroup float64 records in the ctx's prm_partial, then their sum per b.
+static int rigid_param_grad(bdof_ctx* c, const void* vol, const void* grot, int NXv, int NZv, int NYv, const double* prm, int B, double* out,
+                            int accumulate) {
+    using K = RotRigid;
+    if (!c || !vol || !prm || !out || B < 1) return BDOF_ERR_ARG;
+    if (int r = K::shape(c, K::param_grad, NXv, NZv, NYv, B)) return r;
+    if (!grot) {
+        if (!c->grot) return fail(c, BDOF_ERR_STATE, std::string(K::param_grad) + ": the ctx holds no rotated-frame gradient (bdof_grot)");
+        if ((size_t)B * NXv * NZv * NYv > c->grot.size()) return fail(c, BDOF_ERR_ARG, std::string(K::param_grad) + ": B rotated objects do not fit bdof_grot");
+        grot = (const float2*)c->grot;
+    }
+    HIPC(c, hipSetDevice(c->device));
+    const int P = rigid_param_partials(NXv, NZv);
+    HIPC(c, c->prm_partial.room((size_t)B * P * 12));
+    RotArgs<K::Prm> a{(const float2*)vol, (float2*)grot, nullptr, prm, B, NXv, NZv, NYv, 0, 0, accumulate, 1.f};
+    hipLaunchKernelGGL(k_rot_rigid_param_grad, dim3((unsigned)((size_t)B * P)), dim3(256), 0, c->stream, a, P, (double*)c->prm_partial);
+    hipLaunchKernelGGL(k_rot_rigid_param_sum, dim3(B), dim3(64), 0, c->stream, (const double*)c->prm_partial, P, out, accumulate);
+    return launched(c);
+}
+
 extern "C" {
 
 int bdof_rotate_bilinear(bdof_ctx* c, const void* vol, int NXv, int NZv, int NYv, const double* prm, int B, void* out_rows) {
@@ -3331,6 +3354,10 @@ int bdof_set_object_rigid(bdof_ctx* c, const void* vol, int NXv, int NZv, int NY
 int bdof_rotate_rigid_adjoint(bdof_ctx* c, const void* grot, int NXv, int NZv, int NYv, const double* prm, int B, void* gvol, int row0,
                               int n_rows, int accumulate, float scale) {
     return rotate_adjoint<RotRigid>(c, grot, NXv, NZv, NYv, prm, B, gvol, row0, n_rows, accumulate, scale);
+}
+int bdof_rotate_rigid_param_grad(bdof_ctx* c, const void* vol, const void* grot, int NXv, int NZv, int NYv, const double* prm, int B, double* out,
+                                 int accumulate) {
+    return rigid_param_grad(c, vol, grot, NXv, NZv, NYv, prm, B, out, accumulate);
 }
 
 int bdof_regularizer_value(bdof_ctx* c, const void* x, int NXv, int NZv, int NYv, double* sums) {

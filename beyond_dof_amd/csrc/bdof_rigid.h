@@ -146,3 +146,97 @@ __global__ __launch_bounds__(256) void k_rot_rigid_adjoint(RotRigidArgs a) {
         }
     }
 }
+
+// ---- the derivative of a loss with respect to the map itself ---------------------------------------------------------------------------
+// dL/d prm[b][a][j] = sum_o q_a(o) (x, z, y, 1)_j,   q_a(o) = sum_c g_c(o) dV_c/dp_a (p(o)),   a in x', z', y':
+// g the rotated-frame gradient, dV/dp_a taken INSIDE the cell floor(p) that rigid_point gives: over the cell's 8 corners, (-1 or +1
+// by the corner's bit along a) times the product of the other two axes' factors times V(corner), a corner outside the volume counting
+// 0 as in rigid_taps.  A point on a lattice plane belongs to the cell floor gives it: the right-hand derivative (at zero tilt and
+// roll the y fraction is exactly 0 at every voxel, so the convention is the common case, not the edge).
+//
+// The partial count and the rows of a workgroup depend on (NXv, NZv) only — not on the CU count, not on B — and nothing is added
+// atomically: element b has the same bits alone, in a batch and twice.
+#define RIGID_PG_MAX_PARTIALS 512
+__host__ __device__ inline int rigid_param_partials(int NXv, int NZv) {
+    const long long groups = ((long long)NXv * NZv + 3) / 4;             // 4 rows (waves) per workgroup pass
+    return (int)(groups < RIGID_PG_MAX_PARTIALS ? groups : RIGID_PG_MAX_PARTIALS);
+}
+
+// One wave per output row (b, z, x), lanes along y as in k_rot_rigid; grid B P, workgroup p of element b takes the rows
+// 4 (p + i P) + wave, i = 0, 1, ....  Two-factor weights, tap sums and q_a in float32; the sums over voxels in float64: per row
+// the lanes keep sum q_a and sum q_a y (x and z are the row's), folded into the 12 running sums at the row's end.  Then the wave
+// (shuffles), the workgroup's waves in wave order (LDS), and one record of 12 per workgroup: partial [B][P][12].
+__global__ __launch_bounds__(256) void k_rot_rigid_param_grad(RotRigidArgs a, int P, double* __restrict__ partial) {
+    __shared__ double w[4][12];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int NX = a.NXv, NZ = a.NZv, NY = a.NYv;
+    const int b = blockIdx.x / P, p = blockIdx.x - b * P, nrows = NX * NZ;
+    const double* m = a.prm + 12 * (size_t)b;
+    double acc[3][4];
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[i][j] = 0.0;
+    for (int r = p * 4 + wave; r < nrows; r += P * 4) {
+        const int x = r % NX, z = r / NX;
+        const float2* grow = a.rot + ((size_t)b * nrows + r) * NY;
+        double s[3] = {0.0, 0.0, 0.0}, sy[3] = {0.0, 0.0, 0.0};
+        for (int y = lane; y < NY; y += 64) {
+            int i0[3];
+            float f[3][2];
+            rigid_point(m, x, z, y, NX, NZ, NY, i0, f);
+            float2 d[3] = {make_float2(0.f, 0.f), make_float2(0.f, 0.f), make_float2(0.f, 0.f)};      // dV/dp_a, both channels
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                const int ix = i >> 2, iz = (i >> 1) & 1, iy = i & 1;
+                const int px = i0[0] + ix, pz = i0[1] + iz, py = i0[2] + iy;
+                if (px >= 0 && px < NX && pz >= 0 && pz < NZ && py >= 0 && py < NY) {
+                    const float2 v = a.vol[(px * NZ + pz) * NY + py];
+                    const float fx = f[0][ix], fz = f[1][iz], fy = f[2][iy];
+                    const float wx = ix ? fz * fy : -(fz * fy), wz = iz ? fx * fy : -(fx * fy), wy = iy ? fx * fz : -(fx * fz);
+                    d[0].x = fmaf(wx, v.x, d[0].x);
+                    d[0].y = fmaf(wx, v.y, d[0].y);
+                    d[1].x = fmaf(wz, v.x, d[1].x);
+                    d[1].y = fmaf(wz, v.y, d[1].y);
+                    d[2].x = fmaf(wy, v.x, d[2].x);
+                    d[2].y = fmaf(wy, v.y, d[2].y);
+                }
+            }
+            const float2 g = grow[y];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                const double q = (double)fmaf(g.y, d[k].y, g.x * d[k].x);
+                s[k] += q;
+                sy[k] = fma(q, (double)y, sy[k]);
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            acc[k][0] = fma(s[k], (double)x, acc[k][0]);
+            acc[k][1] = fma(s[k], (double)z, acc[k][1]);
+            acc[k][2] += sy[k];
+            acc[k][3] += s[k];
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 12; ++i) {
+        double v = acc[i >> 2][i & 3];
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+        if (lane == 0) w[wave][i] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x < 12) {
+        const int i = threadIdx.x;
+        partial[(size_t)blockIdx.x * 12 + i] = ((w[0][i] + w[1][i]) + w[2][i]) + w[3][i];
+    }
+}
+
+// the P records of element b added in ascending order: out [B][12] (+= with accumulate); grid B, one wave
+__global__ __launch_bounds__(64) void k_rot_rigid_param_sum(const double* __restrict__ partial, int P, double* __restrict__ out, int accumulate) {
+    const int b = blockIdx.x, i = threadIdx.x;
+    if (i >= 12) return;
+    double s = 0.0;
+    for (int p = 0; p < P; ++p) s += partial[((size_t)b * P + p) * 12 + i];
+    out[12 * (size_t)b + i] = accumulate ? out[12 * (size_t)b + i] + s : s;
+}

@@ -24,6 +24,7 @@ from . import h5io, tiffio, util
 from .comm import get_comm, minibatch_schedule
 from .misc import create_summary, SUMMARY_PRESET_FF, SUMMARY_GEOMETRY
 from .engine import check_model_options, read_detector_weights
+from .rotation import check_refine
 from .solver import FullfieldSolver
 from .util import print_flush
 
@@ -104,6 +105,11 @@ def reconstruct_fullfield(fname, theta_st=0, theta_end=PI, n_epochs='auto', crit
     # (FullfieldSolver) with the same theta and the geometry keywords of util.RotationKeywords
     geo = util.RotationKeywords(kwargs)
     rotation, trilinear = geo.rotation, geo.trilinear
+    # refine_geometry=('center', 'axis_tilt', ...): the solver moves these with the volume (FullfieldSolver); what a multiscale level
+    # reaches is the next level's start, and geometry.npy / summary.txt record it in full-resolution units
+    check_refine(geo.refine, rotation, geo.rotation_matrices)
+    if geo.refine and accumulate and n_batch_per_update > 1:
+        raise ValueError('refine_geometry moves the geometry at every minibatch: not together with accumulate_gradients')
 
     print_flush('Reading data...', 0, rank)
     t0 = time.time()
@@ -214,6 +220,8 @@ def reconstruct_fullfield(fname, theta_st=0, theta_end=PI, n_epochs='auto', crit
                                  detector_kernel=kwargs.get('detector_kernel', 'TF'),   # 'IR' / 'auto': np_funcs.py:51-61
                                  loss_type=loss_type, poisson_multiplier=poisson_multiplier, slice_binning=slice_binning,
                                  detector_weights=weights, **geo.for_level(ds_level))
+        if geo.refine and geo.refined is not None:
+            solver.set_geometry(**geo.level_values(ds_level))
         solver.set_volume(obj_delta, obj_beta)
         solver.set_mask(mask)
         solver.set_measurements(np.abs(prj))
@@ -248,6 +256,8 @@ def reconstruct_fullfield(fname, theta_st=0, theta_end=PI, n_epochs='auto', crit
                 if save_intermediate and rank == 0:
                     d, _ = solver.get_volume()
                     tiffio.write_tiff(d, os.path.join(output_folder, 'intermediate', 'current'), dtype='float32', overwrite=True)
+                    if geo.refine:
+                        geo.record(solver.geometry(), ds_level, output_folder)
                 if shrink_cycle is not None and i_epoch >= shrink_cycle:
                     solver.shrink_wrap()
                 if debug:
@@ -275,6 +285,10 @@ def reconstruct_fullfield(fname, theta_st=0, theta_end=PI, n_epochs='auto', crit
                 cont = False
 
         obj_delta, obj_beta = solver.get_volume()
+        if geo.refine:                               # every rank holds the same values (the gradient was summed over the ranks)
+            geo.keep(solver.geometry(), ds_level)
+            if rank == 0:
+                geo.record(solver.geometry(), ds_level, output_folder, summary=True)
         if rank == 0:
             tiffio.write_tiff(obj_delta, os.path.join(output_folder, 'delta_ds_{}'.format(ds_level)), dtype='float32', overwrite=True)
             tiffio.write_tiff(obj_beta, os.path.join(output_folder, 'beta_ds_{}'.format(ds_level)), dtype='float32', overwrite=True)

@@ -18,6 +18,7 @@ from .comm import get_comm
 from .fullfield import create_probe_initial_guess, upsample_2x
 from .misc import create_summary, SUMMARY_PRESET_PTYCHO, SUMMARY_GEOMETRY
 from .engine import check_model_options, read_detector_weights
+from .rotation import check_refine
 from .solver import PtychoSolver
 from ._lib import BdofError
 from .util import print_flush, split_tasks
@@ -91,6 +92,8 @@ def reconstruct_ptychography(fname, probe_pos, probe_size, obj_size, theta_st=0,
     # and the geometry keywords of util.RotationKeywords; no lookup-table files are written
     geo = util.RotationKeywords(kwargs, only=ROTATIONS)
     rotation, trilinear = geo.rotation, geo.trilinear
+    # refine_geometry / geometry_learning_rate: as in reconstruct_fullfield (PtychoSolver moves the step's angle and the shared values)
+    check_refine(geo.refine, rotation, geo.rotation_matrices)
     adjoint_precision = kwargs.get('adjoint_precision', 'first-step')
     if adjoint_precision not in ('float32', 'float64', 'first-step'):
         raise ValueError("adjoint_precision must be 'float32', 'float64' or 'first-step'")
@@ -214,6 +217,8 @@ def reconstruct_ptychography(fname, probe_pos, probe_size, obj_size, theta_st=0,
                         "delta is then within ~7e-6 of a float64 run instead of ~2e-6 (golden vector G17; DESIGN.md, numerics)".format(
                             setup_error), 0, rank)
             solver = mk('float32')
+        if geo.refine and geo.refined is not None:
+            solver.set_geometry(**geo.level_values(ds_level))
         solver.set_volume(obj_delta, obj_beta)
         solver.tune_tail()
         # the diffraction amplitudes stay on the device when they fit (ptychography.py:295 reads them from the file per step)
@@ -251,6 +256,8 @@ def reconstruct_ptychography(fname, probe_pos, probe_size, obj_size, theta_st=0,
                 if save_intermediate and rank == 0:
                     d, _ = solver.get_volume()
                     tiffio.write_tiff(d, os.path.join(output_folder, 'intermediate', 'current'), dtype='float32', overwrite=True)
+                    if geo.refine:
+                        geo.record(solver.geometry(), ds_level, output_folder)
             i_epoch += 1
             this_loss = solver.loss_and_grad(this_i_theta, this_ind_rank, this_prj_batch, want_loss=True)
             print_flush('Epoch {} (rank {}); loss = {}; Delta-t = {} s; current time = {} s,'.format(
@@ -263,6 +270,10 @@ def reconstruct_ptychography(fname, probe_pos, probe_size, obj_size, theta_st=0,
             if rank == 0:
                 tiffio.write_tiff(obj_delta, os.path.join(output_folder, 'delta_ds_{}'.format(ds_level)), dtype='float32', overwrite=True)
                 tiffio.write_tiff(obj_beta, os.path.join(output_folder, 'beta_ds_{}'.format(ds_level)), dtype='float32', overwrite=True)
+        if geo.refine:
+            geo.keep(solver.geometry(), ds_level)
+            if rank == 0:
+                geo.record(solver.geometry(), ds_level, output_folder, summary=True)
         obj_delta, obj_beta = obj_delta.astype(float), obj_beta.astype(float)
         first_level = False
         del solver

@@ -14,11 +14,95 @@ KINDS = {'bilinear': Kind(util.bilinear_prm, 4, 'bdof_rotate_bilinear', 'bdof_se
          'trilinear': Kind(util.rigid_prm, 12, 'bdof_rotate_rigid', 'bdof_set_object_rigid', 'bdof_rotate_rigid_adjoint')}
 
 
-def choose(rotation, shape, n_theta, coord_ls, theta, geometry, materialised=None):
-    """shape = (Y, X, Z); geometry = (axis_tilt, axis_roll, center, rotation_matrices); materialised: the class for a kind of KINDS."""
+def choose(rotation, shape, n_theta, coord_ls, theta, geometry, materialised=None, refine=(), rate=0.05):
+    """shape = (Y, X, Z); geometry = (axis_tilt, axis_roll, center, rotation_matrices); materialised: the class for a kind of KINDS.
+    refine, rate: the solvers' refine_geometry and geometry_learning_rate (RigidGeometry; ValueError for what cannot be refined)."""
+    refine = check_refine(refine, rotation, geometry[3])
     if rotation == 'nearest':
         return LookupRotation(shape, n_theta, coord_ls)
-    return (materialised or MaterialisedRotation)(shape, n_theta, KINDS[rotation], KINDS[rotation].prm(n_theta, shape, theta, *geometry))
+    rot = (materialised or MaterialisedRotation)(shape, n_theta, KINDS[rotation], KINDS[rotation].prm(n_theta, shape, theta, *geometry))
+    if rotation == 'trilinear' and geometry[3] is None:
+        rot.geometry = RigidGeometry(shape, theta, geometry[0], geometry[1], geometry[2], refine, rate)
+    return rot
+
+
+def check_refine(refine, rotation, rotation_matrices):
+    """A solver's refine_geometry as a tuple of names of util.GEOMETRY_NAMES; ValueError for an unknown name, for a rotation
+    other than 'trilinear' and for raw rotation_matrices (which refinement could not keep rigid)."""
+    refine = (refine,) if isinstance(refine, str) else tuple(refine or ())
+    unknown = [n for n in refine if n not in util.GEOMETRY_NAMES]
+    if unknown:
+        raise ValueError('refine_geometry takes names out of {}, not {}'.format(util.GEOMETRY_NAMES, unknown))
+    if refine and rotation != 'trilinear':
+        raise ValueError("refine_geometry runs with rotation='trilinear' only")
+    if refine and rotation_matrices is not None:
+        raise ValueError('refine_geometry moves center, axis_tilt, axis_roll, theta and shifts: not together with rotation_matrices')
+    return refine
+
+
+class RigidGeometry(object):
+    """The numbers util.rigid_geometry builds rotation='trilinear' from, the chain rule from dL/d(M | t) back to them and, for
+    the names in `refine`, a host Adam (0.9 / 0.999 / 1e-8) on them.  rate: Adam's step as a displacement in pixels at the
+    volume's edge — center and shifts take it as it is, the three angles rate / (max(X, Z, Y) / 2).  A per-angle entry (theta,
+    shifts) keeps its own update counter and moves only in a step that lists its angle.
+    Gauge: the mean horizontal shift and center move the same rows, the mean vertical shift is a translation of the volume
+    along y; refining both members of a pair leaves their split to Adam's path."""
+
+    def __init__(self, shape, theta, axis_tilt, axis_roll, center, refine=(), rate=0.05):
+        self.shape = tuple(int(a) for a in shape)
+        n = len(np.atleast_1d(theta))
+        self.value = dict(center=np.array((self.shape[1] - 1) / 2. if center is None else float(center)), axis_tilt=np.array(float(axis_tilt)),
+                          axis_roll=np.array(float(axis_roll)), theta=np.array(np.atleast_1d(theta), dtype=np.float64), shifts=np.zeros((n, 2)))
+        self.refine, self.n_theta = tuple(refine), n
+        self.rate = {k: float(rate) / (1. if k in ('center', 'shifts') else max(self.shape) / 2.) for k in util.GEOMETRY_NAMES}
+        self.m = {k: np.zeros_like(self.value[k]) for k in self.refine}
+        self.v = {k: np.zeros_like(self.value[k]) for k in self.refine}
+        self.t = {k: np.zeros(self.value[k].shape, dtype=np.int64) for k in self.refine}
+
+    def values(self):
+        return {k: v.copy() for k, v in self.value.items()}
+
+    def set_values(self, **values):
+        for k, v in values.items():
+            self.value[k] = np.array(v, dtype=np.float64).reshape(self.value[k].shape)
+
+    def prm(self):
+        g = self.value
+        return util.rigid_geometry(g['theta'], self.shape, float(g['axis_tilt']), float(g['axis_roll']), float(g['center']), g['shifts'])
+
+    def gradient(self, dprm, index):
+        """dL/d(M | t) rows (len(index), 3, 4) of the angles index -> util.rigid_geometry_gradient's dict"""
+        g = self.value
+        return util.rigid_geometry_gradient(g['theta'], self.shape, float(g['axis_tilt']), float(g['axis_roll']), float(g['center']), g['shifts'],
+                                            np.reshape(dprm, (len(index), 12)), index)
+
+    def dense(self, grad, index):
+        """one vector for the ranks to add: per refined name its gradient scattered over all angles, then which angles it lists"""
+        parts = []
+        for k in self.refine:
+            full = np.zeros_like(self.value[k])
+            if full.ndim:
+                np.add.at(full, np.asarray(index), grad[k])
+            else:
+                full += grad[k]
+            parts.append(full.reshape(-1))
+        seen = np.zeros(self.n_theta)
+        seen[np.asarray(index)] = 1.
+        return np.concatenate(parts + [seen])
+
+    def update(self, dense, b1=0.9, b2=0.999, eps=1e-8):
+        """Adam on the refined names from dense()'s vector (already summed over the ranks and divided by their number)"""
+        seen, at = dense[-self.n_theta:] > 0, 0
+        for k in self.refine:
+            g = dense[at:at + self.value[k].size].reshape(self.value[k].shape)
+            at += self.value[k].size
+            move = np.ones(self.value[k].shape, dtype=bool) if self.value[k].ndim == 0 else (seen if g.ndim == 1 else np.repeat(seen[:, None], 2, axis=1))
+            self.t[k] = self.t[k] + move
+            self.m[k] = np.where(move, b1 * self.m[k] + (1 - b1) * g, self.m[k])
+            self.v[k] = np.where(move, b2 * self.v[k] + (1 - b2) * g * g, self.v[k])
+            t = np.maximum(self.t[k], 1)
+            step = self.rate[k] * (self.m[k] / (1 - b1 ** t)) / (np.sqrt(self.v[k] / (1 - b2 ** t)) + eps)
+            self.value[k] = np.where(move, self.value[k] - step, self.value[k])
 
 
 class LookupRotation(object):
@@ -74,9 +158,12 @@ class MaterialisedRotation(LookupRotation):
     step, straight into the ctx's modulation table, so no volume stays bound between steps; the adjoint is a gather with the same rows."""
     one_pass_tail = float64_paths = False
 
+    geometry = None            # rotation='trilinear' from theta and the axis keywords: their RigidGeometry (choose)
+
     def __init__(self, shape, n_theta, kind, prm):
         LookupRotation.__init__(self, shape, n_theta, None)
         self.kind, self.prm = kind, prm            # prm: (n_theta, kind.columns) float64
+        self.dprm_buf = None
 
     def allocate(self, ctx, mb):
         self.ctx, self.mb = ctx, int(mb)
@@ -107,6 +194,19 @@ class MaterialisedRotation(LookupRotation):
         """grot: the rotated-frame gradient (None: the ctx's own, bdof_grot)"""
         grot = self.ctx.lib.bdof_grot(self.ctx.handle) if grot is None else grot.ptr
         self._call(self.kind.adjoint, grot, self.mb, g.ptr, x0 * self.dim_z, nx * self.dim_z, int(accumulate), 1.0)
+
+    def param_gradient(self, x, grot=None):
+        """dL/d(M | t) of the staged angles, (B, 3, 4) float64 on the host (bdof_rotate_rigid_param_grad): x the volume that was
+        staged, grot the rotated-frame gradient (None: the ctx's own).  The download waits for the stream."""
+        if self.kind is not KINDS['trilinear']:
+            raise ValueError("param_gradient: rotation='trilinear' only")
+        if self.dprm_buf is None:
+            self.dprm_buf = DeviceBuffer(self.ctx, self.mb * 12 * 8, np.float64, (self.mb, 3, 4))
+        lib, h = self.ctx.lib, self.ctx.handle
+        self.ctx.check(lib.bdof_rotate_rigid_param_grad(h, x.ptr, None if grot is None else grot.ptr, self.dim_x, self.dim_z, self.dim_y,
+                                                        self.prm_buf.ptr, self.mb, self.dprm_buf.ptr, 0))
+        self.ctx.sync()
+        return self.dprm_buf.download()
 
 
 class RotatedCopy(MaterialisedRotation):
@@ -140,3 +240,6 @@ class RotatedCopy(MaterialisedRotation):
         """windows -> rotated frame (identity tables) -> volume frame (prm_buf still holds the step's angle)"""
         self.ctx.check(self.ctx.lib.bdof_window_rotation_adjoint(self.ctx.handle, self.n_windows, 0, xo, yo, self.g_rot.ptr, 0, 1.0))
         self.adjoint(None, g, 0, self.dim_x, 0, grot=self.g_rot)
+
+    def param_gradient(self, x, grot=None):
+        return MaterialisedRotation.param_gradient(self, x, self.g_rot if grot is None else grot)

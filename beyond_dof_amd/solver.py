@@ -143,6 +143,49 @@ class _VolumeSolver(object):
         self.ctx.sync()
         return util.rows_to_volume(self.g.download())
 
+    # ---- the geometry of rotation='trilinear' (rotation.RigidGeometry) --------------------------------------------------------
+    def _rigid_geometry(self):
+        geo = getattr(self.rot, 'geometry', None)
+        if geo is None:
+            raise ValueError("the geometry is that of rotation='trilinear' built from theta and the axis keywords (not rotation_matrices)")
+        return geo
+
+    def geometry(self):
+        """The current center, axis_tilt, axis_roll, theta (n_theta) and shifts (n_theta, 2): what refine_geometry has made of them."""
+        return self._rigid_geometry().values()
+
+    def set_geometry(self, **values):
+        """Replace values of geometry() (center, axis_tilt, axis_roll, theta, shifts): the next stage rotates with them."""
+        geo = self._rigid_geometry()
+        geo.set_values(**values)
+        self.rot.prm = geo.prm()
+
+    def geometry_gradient(self):
+        """dL/d(center, axis_tilt, axis_roll, theta_i, shift_i) of the data term for the angles of the last loss_and_grad (or, inside
+        step, of the step, before the tail flips the volume), not reduced over the ranks: the dict of util.rigid_geometry_gradient,
+        its per-angle entries in the order of those angles.  One reduction on the device over the volume that was staged, the
+        staged rows and the rotated-frame gradient (bdof_rotate_rigid_param_grad), then the chain rule on the host."""
+        geo, index = self._rigid_geometry(), self._step_angles()
+        if index is None:
+            raise RuntimeError('geometry_gradient() follows loss_and_grad() or runs inside step(): no angles have been staged yet')
+        return geo.gradient(self.rot.param_gradient(self.x[self.cur])[:len(index)], index)
+
+    def _refine_geometry(self):
+        """step, before the tail: gradient, sum over the ranks (/ size, as the volume gradient), host Adam, new rows for the next stage"""
+        geo = getattr(self.rot, 'geometry', None)
+        if geo is None or not geo.refine:
+            return
+        dense = geo.dense(self.geometry_gradient(), self._step_angles())
+        if self.comm.size > 1:
+            dense = self.comm.allreduce_sum_host(dense) / self.comm.size
+        geo.update(dense)
+        self.rot.prm = geo.prm()
+
+    def _refuse_accumulation(self, n_batch_per_update):
+        geo = getattr(self.rot, 'geometry', None)
+        if geo is not None and geo.refine and int(n_batch_per_update) > 1:
+            raise ValueError('refine_geometry moves the geometry at every minibatch: not together with n_batch_per_update > 1')
+
     def regularizer(self, alpha_d=0.0, alpha_b=0.0, gamma=0.0):
         """alpha_d sum|delta| + alpha_b sum|beta| + gamma TV(delta) of the current volume (fullfield.py:109-118), on the device."""
         sums = (ctypes.c_double * 3)()
@@ -384,7 +427,7 @@ class FullfieldSolver(_VolumeSolver):
                  probe_real=None, probe_imag=None, variant='numpy_skip_last', comm=None, device=0, stream=None,
                  coord_ls=None, propagator='fft', kernel_size=17, recompute=False, rotation='nearest', theta=None, adjoint64=None,
                  detector_kernel='TF', loss_type='lsq', poisson_multiplier=2e6, slice_binning=1, detector_weights=None,
-                 axis_tilt=0., axis_roll=0., center=None, rotation_matrices=None):
+                 axis_tilt=0., axis_roll=0., center=None, rotation_matrices=None, refine_geometry=(), geometry_learning_rate=0.05):
         """loss_type / poisson_multiplier: the data term (MultisliceEngine.set_loss; 'poisson' with propagator='fft' only).
         detector_weights: one (Y, X) plane of weights >= 0 for every projection (MultisliceEngine.set_detector_weights; 0: the
         pixel takes no part), set before any measurement is bound; propagator='fft' only.
@@ -403,7 +446,12 @@ class FullfieldSolver(_VolumeSolver):
         beam by axis_tilt (laminography), rolled about the beam by axis_roll (radians), projecting onto detector column `center`
         (a pixel index, fractional if need be; None: the middle) — or rotation_matrices (n_theta, 3, 4), any rigid (M | t) per
         angle (util.check_rigid), which then stands in place of theta and the three geometry keywords.  With any other rotation
-        these four keywords are ignored."""
+        these four keywords are ignored.
+        refine_geometry: names out of 'center', 'axis_tilt', 'axis_roll', 'theta', 'shifts' (a per-angle detector offset, util.rigid_geometry)
+        that every step() moves with the volume — geometry_gradient(), summed over the ranks, a host Adam whose step
+        geometry_learning_rate is a displacement in pixels at the volume's edge (rotation.RigidGeometry), new rows for the next
+        step; geometry() returns the current values.  rotation='trilinear' without rotation_matrices and without
+        n_batch_per_update > 1 only.  Empty: nothing of this runs."""
         self.n_planes = _check_options(propagator, adjoint64, loss_type, poisson_multiplier, detector_weights, slice_binning, free_prop_cm,
                                        rotation=rotation if rotation in ('bilinear', 'trilinear') else 'nearest', recompute=recompute, detector_kernel=detector_kernel)
         self.conv = propagator == 'conv'
@@ -420,7 +468,8 @@ class FullfieldSolver(_VolumeSolver):
         if rotation not in ('nearest', 'bilinear', 'trilinear'):
             raise ValueError("rotation must be 'nearest', 'bilinear' or 'trilinear'")
         # the rotation's host side (for a materialised kind its float64 rows per angle): checked here, before anything is allocated
-        self.rot = rotations.choose(rotation, (dim_y, dim_x, dim_z), n_theta, coord_ls, theta, (axis_tilt, axis_roll, center, rotation_matrices))
+        self.rot = rotations.choose(rotation, (dim_y, dim_x, dim_z), n_theta, coord_ls, theta, (axis_tilt, axis_roll, center, rotation_matrices),
+                                    refine=refine_geometry, rate=geometry_learning_rate)
         self.dim_y, self.dim_x, self.dim_z = int(dim_y), int(dim_x), int(dim_z)
         self.n_theta, self.mb = int(n_theta), int(minibatch_size)
         self.comm = comm or PseudoComm()
@@ -468,6 +517,7 @@ class FullfieldSolver(_VolumeSolver):
         """Forward + adjoint sweeps of this rank's angles: the gradient w.r.t. the rotated objects stays in the ctx.
         f64: through the transfer-function model's float64 path on the same context (bdof_loss_grad_tf_f64)."""
         self._stage_batch(angle_idx)
+        self._angles = np.asarray(angle_idx, dtype=np.int64)
         if f64:
             if not self.rot.float64_paths:
                 raise ValueError("f64: the float64 paths run with the lookup-table rotation")
@@ -482,6 +532,9 @@ class FullfieldSolver(_VolumeSolver):
 
     def _produce(self, accumulate=False):
         return lambda x0, nx: self.rot.adjoint(self.angle_buf, self.g, x0, nx, accumulate)
+
+    def _step_angles(self):
+        return getattr(self, '_angles', None)
 
     def loss_and_grad(self, angle_idx, want_loss=True, f64=False):
         """Data-term loss and its gradient w.r.t. the volume for this rank's angles (left in self.g, not reduced).  f64: both
@@ -525,8 +578,10 @@ class FullfieldSolver(_VolumeSolver):
         n_batch_per_update > 1 (tensorflow_recon/fullfield.py:413-425,512-530): the volume gradient of consecutive
         minibatches is accumulated and applied (averaged) every n-th minibatch or at the last one of the epoch; the Adam
         bias-correction exponent then counts updates, not minibatches."""
+        self._refuse_accumulation(n_batch_per_update)
         self._rot_loss_grad(angle_idx, f64=self.f64 is True or (self.f64 == 'first' and i_batch == 0 and self.probe is None))
         self._probe_collect()
+        self._refine_geometry()
         nb = max(1, int(n_batch_per_update))
         if nb > 1:
             self._g_is_local()
@@ -563,8 +618,10 @@ class PtychoSolver(_VolumeSolver):
     def __init__(self, obj_size, probe_size, probe_pos, n_theta, minibatch_size, energy_ev, psize_cm, probe_real, probe_imag,
                  variant='numpy_skip_last', comm=None, device=0, stream=None, coord_ls=None, propagator='fft', kernel_size=17,
                  adjoint64=None, engine=None, loss_type='lsq', poisson_multiplier=2e6, slice_binning=1, detector_weights=None,
-                 rotation='nearest', theta=None, axis_tilt=0., axis_roll=0., center=None, rotation_matrices=None):
-        """rotation='nearest': the lookup tables.  'trilinear': the rigid map of FullfieldSolver(rotation='trilinear'), with the same
+                 rotation='nearest', theta=None, axis_tilt=0., axis_roll=0., center=None, rotation_matrices=None, refine_geometry=(),
+                 geometry_learning_rate=0.05):
+        """refine_geometry / geometry_learning_rate: as for FullfieldSolver (the step's one angle moves).
+        rotation='nearest': the lookup tables.  'trilinear': the rigid map of FullfieldSolver(rotation='trilinear'), with the same
         theta / axis_tilt / axis_roll / center / rotation_matrices (tilt 0: ptychography's interpolating rotation), through a rotated
         copy per step (rotation.RotatedCopy).  slice_binning > 1 keeps to rotation='nearest'.
         loss_type / poisson_multiplier: the data term (MultisliceEngine.set_loss; 'poisson' with propagator='fft' only).
@@ -580,7 +637,7 @@ class PtychoSolver(_VolumeSolver):
         self.conv = propagator == 'conv'
         self.dim_y, self.dim_x, self.dim_z = [int(s) for s in obj_size]
         self.rot = rotations.choose(rotation, obj_size, n_theta, coord_ls, theta, (axis_tilt, axis_roll, center, rotation_matrices),
-                                    materialised=rotations.RotatedCopy)
+                                    materialised=rotations.RotatedCopy, refine=refine_geometry, rate=geometry_learning_rate)
         self.py, self.px = int(probe_size[0]), int(probe_size[1])
         self.n_theta, self.mb = int(n_theta), int(minibatch_size)
         self.comm = comm or PseudoComm()
@@ -657,6 +714,9 @@ class PtychoSolver(_VolumeSolver):
         self._g_is_local()
         self.rot.window_adjoint(i_theta, xo, yo, self.g)
 
+    def _step_angles(self):
+        return None if self._last is None else np.array([self._last[0]], dtype=np.int64)
+
     def loss_and_grad(self, i_theta, pos_idx, prj_abs_batch=None, want_loss=True, f64=False):
         """prj_abs_batch: |this_prj_batch| (mb, py, px) for probe positions pos_idx at angle i_theta (None: from the resident
         stack of set_measurements).  f64: through the model's float64 path (solver built with adjoint64='first')."""
@@ -676,6 +736,7 @@ class PtychoSolver(_VolumeSolver):
                             use64=self.f64 == 'first' and i_batch == 0 and self.probe is None)
         self._probe_collect()
         self._produce_all()
+        self._refine_geometry()          # (after the window adjoint: the rotated-frame gradient is the rotated copy's)
         self._tail(lambda x0, nx: None, i_batch, learning_rate, clip=clip, use_mask=False, n_slabs=n_slabs, sharded=sharded)
         self._probe_apply()
         return self._get_loss() if want_loss else None

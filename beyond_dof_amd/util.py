@@ -313,7 +313,33 @@ def device_rotation_tables(coords, nx, nz):
     return tab, off, order
 
 
-def rigid_geometry(theta, shape, axis_tilt=0., axis_roll=0., center=None):
+def _rigid_factors(shape, axis_tilt, axis_roll, center):
+    """T, R, c_v, c_o of rigid_geometry and the derivatives dT / d axis_tilt, dR / d axis_roll"""
+    ny, nx, nz = [int(a) for a in shape]
+    ca, sa, cr, sr = np.cos(float(axis_tilt)), np.sin(float(axis_tilt)), np.cos(float(axis_roll)), np.sin(float(axis_roll))
+    T = np.array([[1., 0., 0.], [0., ca, sa], [0., -sa, ca]])
+    R = np.array([[cr, 0., sr], [0., 1., 0.], [-sr, 0., cr]])
+    dT = np.array([[0., 0., 0.], [0., -sa, ca], [0., -ca, -sa]])
+    dR = np.array([[-sr, 0., cr], [0., 0., 0.], [-cr, 0., -sr]])
+    c_v = np.array([(nx - 1) / 2., (nz - 1) / 2., (ny - 1) / 2.])
+    c_o = c_v.copy()
+    if center is not None:
+        c_o[0] = float(center)
+    return T, R, dT, dR, c_v, c_o
+
+
+def _rigid_shifts(shifts, n):
+    """shifts (n, 2) = (horizontal, vertical) per angle as the (n, 3) offsets of c_o: (sx, 0, sy); None: zeros"""
+    off = np.zeros((n, 3))
+    if shifts is not None:
+        sh = np.asarray(shifts, dtype=np.float64)
+        if sh.shape != (n, 2):
+            raise ValueError('shifts must have shape (n_theta, 2) = ({}, 2), not {}'.format(n, sh.shape))
+        off[:, 0], off[:, 2] = sh[:, 0], sh[:, 1]
+    return off
+
+
+def rigid_geometry(theta, shape, axis_tilt=0., axis_roll=0., center=None, shifts=None):
     """(n_theta, 12) float64: the rows of (M | t) of rotation='trilinear' for a volume of shape (Y, X, Z).  Output voxel
     o = (x, z, y) of the beam frame samples the volume at p = M o + t in index coordinates (x', z', y'), with
 
@@ -321,25 +347,51 @@ def rigid_geometry(theta, shape, axis_tilt=0., axis_roll=0., center=None):
         M0: x' =  cos x + sin z ; z' = -sin x + cos z ; y' = y       (the bilinear rotation's own map)
         T : z' =  cos z + sin y ; y' = -sin z + cos y ; x' = x       (axis tilted towards the beam: laminography)
         R : x' =  cos x + sin y ; y' = -sin x + cos y ; z' = z       (axis rolled about the beam)
-        c_v = ((X - 1) / 2, (Z - 1) / 2, (Y - 1) / 2),  c_o = c_v with its first entry replaced by `center` if given
+        c_v = ((X - 1) / 2, (Z - 1) / 2, (Y - 1) / 2),  c_o = c_v with its first entry replaced by `center` if given,
+        plus (sx_i, 0, sy_i) for angle i if `shifts` is given
 
-    center: the detector column the axis projects onto, as a (possibly fractional) pixel index.  Angles in radians."""
+    center: the detector column the axis projects onto, as a (possibly fractional) pixel index.  Angles in radians.
+    shifts: (n_theta, 2), the detector offset (horizontal, vertical) of every angle in pixels; None and zeros give the same rows."""
     th = np.atleast_1d(np.asarray(theta, dtype=np.float64))
-    ny, nx, nz = [int(a) for a in shape]
-    ca, sa, cr, sr = np.cos(float(axis_tilt)), np.sin(float(axis_tilt)), np.cos(float(axis_roll)), np.sin(float(axis_roll))
-    T = np.array([[1., 0., 0.], [0., ca, sa], [0., -sa, ca]])
-    R = np.array([[cr, 0., sr], [0., 1., 0.], [-sr, 0., cr]])
-    c_v = np.array([(nx - 1) / 2., (nz - 1) / 2., (ny - 1) / 2.])
-    c_o = c_v.copy()
-    if center is not None:
-        c_o[0] = float(center)
+    T, R, _, _, c_v, c_o = _rigid_factors(shape, axis_tilt, axis_roll, center)
+    off = _rigid_shifts(shifts, len(th))
     out = np.empty((len(th), 3, 4))
     for i, a in enumerate(th):
         c, s = np.cos(a), np.sin(a)
         M = np.array([[c, s, 0.], [-s, c, 0.], [0., 0., 1.]]) @ T @ R
         out[i, :, :3] = M
-        out[i, :, 3] = c_v - M @ c_o
+        out[i, :, 3] = c_v - M @ (c_o + off[i])
     return out.reshape(len(th), 12)
+
+
+GEOMETRY_NAMES = ('center', 'axis_tilt', 'axis_roll', 'theta', 'shifts')
+
+
+def rigid_geometry_gradient(theta, shape, axis_tilt, axis_roll, center, shifts, dprm, index):
+    """The chain rule of rigid_geometry: dprm (len(index), 12) = dL/d(M | t) of the angles `index` of theta -> dict of
+    dL/d theta (len(index), of the listed angles), axis_tilt, axis_roll, center (scalars, summed over the listed angles) and
+    shifts (len(index), 2).  Analytic, float64: with G = (G_M | G_t) the row of an angle and a parameter moving M by dM,
+        dL = <G_M, dM> - G_t . (dM c_o),        dL/d c_o = -M^T G_t
+    (center is c_o's first entry for every angle, a shift the first and third of its own angle's)."""
+    th = np.atleast_1d(np.asarray(theta, dtype=np.float64))
+    index = np.atleast_1d(np.asarray(index, dtype=np.int64))
+    G = np.asarray(dprm, dtype=np.float64).reshape(len(index), 3, 4)
+    T, R, dT, dR, c_v, c_o = _rigid_factors(shape, axis_tilt, axis_roll, center)
+    off = _rigid_shifts(shifts, len(th))
+    out = dict(theta=np.zeros(len(index)), axis_tilt=0.0, axis_roll=0.0, center=0.0, shifts=np.zeros((len(index), 2)))
+    for k, i in enumerate(index):
+        c, s = np.cos(th[i]), np.sin(th[i])
+        M0 = np.array([[c, s, 0.], [-s, c, 0.], [0., 0., 1.]])
+        dM0 = np.array([[-s, c, 0.], [-c, -s, 0.], [0., 0., 0.]])
+        GM, Gt, co = G[k, :, :3], G[k, :, 3], c_o + off[i]
+        d = lambda dM: float(np.sum(GM * dM) - Gt @ (dM @ co))
+        out['theta'][k] = d(dM0 @ T @ R)
+        out['axis_tilt'] += d(M0 @ dT @ R)
+        out['axis_roll'] += d(M0 @ T @ dR)
+        dco = -(M0 @ T @ R).T @ Gt
+        out['center'] += float(dco[0])
+        out['shifts'][k] = dco[0], dco[2]
+    return out
 
 
 def check_rigid(rotation_matrices, n_theta):
@@ -356,7 +408,7 @@ def check_rigid(rotation_matrices, n_theta):
     return np.ascontiguousarray(m.reshape(len(m), 12))
 
 
-def rigid_prm(n_theta, shape, theta, axis_tilt=0., axis_roll=0., center=None, rotation_matrices=None):
+def rigid_prm(n_theta, shape, theta, axis_tilt=0., axis_roll=0., center=None, rotation_matrices=None, shifts=None):
     """(n_theta, 12) float64 rows of (M | t) for rotation='trilinear' from a solver's keywords (ValueError for what is missing, of
     the wrong length or not rigid): rotation_matrices if given, else rigid_geometry of theta and the axis keywords."""
     if theta is None and rotation_matrices is None:
@@ -365,7 +417,7 @@ def rigid_prm(n_theta, shape, theta, axis_tilt=0., axis_roll=0., center=None, ro
         return check_rigid(rotation_matrices, n_theta)
     if len(np.atleast_1d(theta)) != int(n_theta):
         raise ValueError('theta must hold n_theta = {} angles'.format(int(n_theta)))
-    return rigid_geometry(theta, shape, axis_tilt, axis_roll, center)
+    return rigid_geometry(theta, shape, axis_tilt, axis_roll, center, shifts)
 
 
 def bilinear_prm(n_theta, shape, theta, *ignored):
@@ -385,7 +437,9 @@ class RotationKeywords(object):
     value outside it stays ignored and counts as 'nearest'.  For rotation='trilinear' — a rigid map per angle, sampled trilinearly —
     the geometry: axis_tilt / axis_roll (radians), center (the detector column the axis projects onto, a pixel index of the
     full-resolution data) or rotation_matrices (n_theta, 3, 4) in voxels of the full-resolution volume.  With any other rotation
-    the four are ignored and for_level gives no keyword."""
+    the four are ignored and for_level gives no keyword.  refine_geometry / geometry_learning_rate go to the solver as they are
+    (which refuses them for another rotation); what a level has refined is kept in full-resolution units (keep) and handed to
+    the next level (level_values)."""
 
     def __init__(self, kwargs, only=None):
         self.rotation = kwargs.get('rotation', 'nearest')
@@ -394,6 +448,10 @@ class RotationKeywords(object):
         self.trilinear = self.rotation == 'trilinear'
         self.axis_tilt, self.axis_roll = float(kwargs.get('axis_tilt', 0.)), float(kwargs.get('axis_roll', 0.))
         self.center, self.rotation_matrices = kwargs.get('center'), kwargs.get('rotation_matrices')
+        refine = kwargs.get('refine_geometry', ())
+        self.refine = (refine,) if isinstance(refine, str) else tuple(refine or ())
+        self.rate = float(kwargs.get('geometry_learning_rate', 0.05))
+        self.refined = None                       # the last level's geometry() in full-resolution units
 
     def select(self, n_theta, index=None):
         """Once the data are read: keep the rotation_matrices of the angles the run keeps (index: a slice or an index array, as
@@ -413,7 +471,30 @@ class RotationKeywords(object):
             level = self.rotation_matrices.copy()
             level[:, :, 3] /= ds_level
             geometry['rotation_matrices'] = level
+        if self.refine:
+            geometry.update(refine_geometry=self.refine, geometry_learning_rate=self.rate)
         return geometry
+
+    def keep(self, values, ds_level):
+        """a solver's geometry() at level ds_level, in full-resolution units: center and shifts times ds_level"""
+        self.refined = dict(values, center=np.asarray(values['center']) * ds_level, shifts=np.asarray(values['shifts']) * ds_level)
+        return self.refined
+
+    def record(self, values, ds_level, output_folder, summary=False):
+        """keep(), written as geometry.npy (a dict of arrays; np.load(..., allow_pickle=True).item()) and, with summary, as
+        refined_<name> lines behind what summary.txt holds"""
+        refined = self.keep(values, ds_level)
+        np.save(os.path.join(output_folder, 'geometry.npy'), refined)
+        if summary:
+            with open(os.path.join(output_folder, 'summary.txt'), 'a') as f:
+                for name in GEOMETRY_NAMES:
+                    f.write('{:<20}{}\n'.format('refined_' + name, np.array2string(np.asarray(refined[name]), threshold=10 ** 6).replace('\n', ' ')))
+
+    def level_values(self, ds_level):
+        """what keep() holds, in the units of level ds_level (None: nothing refined yet)"""
+        if self.refined is None:
+            return None
+        return dict(self.refined, center=self.refined['center'] / ds_level, shifts=self.refined['shifts'] / ds_level)
 
     def summary(self):
         """The geometry as a run's summary records it (the matrices only as 'given')."""

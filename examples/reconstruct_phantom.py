@@ -8,6 +8,7 @@ reference.
 
     python examples/reconstruct_phantom.py [n=128] [n_theta=60] [n_epochs=100] [learning_rate=2e-8] [free_prop_cm=1e-3] [minibatch=10]
                                            [propagator=fft] [--loss lsq|poisson] [--poisson-multiplier 2e6] [--slice-binning 1]
+                                           [--refine-geometry center,axis_tilt]
 
 --loss poisson minimises the photon-counting likelihood (loss_type='poisson'); its data term is ~ 2 * multiplier times the
 least-squares one, and the L1 weights are scaled with it here.
@@ -15,6 +16,9 @@ free_prop_cm=5e-4,1e-3,2e-3 (distances separated by commas) simulates and fits s
 is then (n_theta, D, Y, X) and run(..., fp=(5e-4, 1e-3, 2e-3)) is the same from Python.
 --slice-binning b reconstructs with one propagation step per b voxel slices (slice_binning=b); the data are always simulated
 with one step per voxel slice.
+--refine-geometry names: the data are simulated with rotation='trilinear' about an axis that is OFFSET (OFFSET below: the centre
+1.5 pixels, the tilt 0.01 rad off the nominal geometry) and reconstructed from the nominal one with refine_geometry=names; the
+refined values (out/geometry.npy) are printed beside the truth.
 """
 import os
 import sys
@@ -40,7 +44,11 @@ def phantom(n, rng):
     return d
 
 
-def run(n=128, n_theta=60, n_epochs=100, lr=2e-8, fp=1e-3, quiet=False, mb=10, propagator='fft', loss='lsq', multiplier=2e6, slice_binning=1):
+OFFSET = dict(center=1.5, axis_tilt=0.01)
+
+
+def run(n=128, n_theta=60, n_epochs=100, lr=2e-8, fp=1e-3, quiet=False, mb=10, propagator='fft', loss='lsq', multiplier=2e6, slice_binning=1,
+        refine=()):
     """Simulate, write exchange/data, reconstruct, compare with the phantom: returns the figures main() prints
     (tests/test_gpu_convergence.py asserts them)."""
     import contextlib
@@ -50,7 +58,12 @@ def run(n=128, n_theta=60, n_epochs=100, lr=2e-8, fp=1e-3, quiet=False, mb=10, p
     cwd = os.getcwd()
     with tempfile.TemporaryDirectory() as td:
         os.chdir(td)
-        s = FullfieldSolver(n, n, n, n_theta, mb, 5000., 1e-7, free_prop_cm=fp, propagator=propagator)
+        nominal = dict(center=(n - 1) / 2., axis_tilt=0.)
+        truth = {k: v + OFFSET[k] for k, v in nominal.items()}
+        theta = -np.linspace(0, 2 * np.pi, n_theta, dtype='float32')          # the entry point's angles
+        sim = dict(rotation='trilinear', theta=theta, **truth) if refine else {}
+        fit = dict(rotation='trilinear', refine_geometry=tuple(refine), **nominal) if refine else {}
+        s = FullfieldSolver(n, n, n, n_theta, mb, 5000., 1e-7, free_prop_cm=fp, propagator=propagator, **sim)
         s.set_volume(d, 0.1 * d)
         prj = s.forward_angles(np.arange(n_theta))
         del s
@@ -63,11 +76,13 @@ def run(n=128, n_theta=60, n_epochs=100, lr=2e-8, fp=1e-3, quiet=False, mb=10, p
                                            minibatch_size=mb, energy_ev=5000, psize_cm=1e-7, free_prop_cm=fp, save_path='case',
                                            output_folder='out', shrink_cycle=None, seed=3, alpha_d=1e-9 * reg, alpha_b=1e-10 * reg, gamma=0,
                                            initial_guess=[np.zeros_like(d), np.zeros_like(d)], propagator=propagator,
-                                           loss_type=loss, poisson_multiplier=multiplier, slice_binning=slice_binning)
+                                           loss_type=loss, poisson_multiplier=multiplier, slice_binning=slice_binning, **fit)
         dt = time.time() - t0
+        refined = np.load(os.path.join('case', 'out', 'geometry.npy'), allow_pickle=True).item() if refine else {}
         os.chdir(cwd)
     inner = (slice(n // 4, -n // 4),) * 3
     return {'n': n, 'n_theta': n_theta, 'n_epochs': n_epochs, 'seconds': dt,
+            'geometry': {k: (nominal[k], float(refined[k]), truth[k]) for k in refine if k in nominal},
             'delta_corr': float(np.corrcoef(rd.ravel(), d.ravel())[0, 1]),
             'delta_corr_inner': float(np.corrcoef(rd[inner].ravel(), d[inner].ravel())[0, 1]),
             'delta_rel_l2': float(np.linalg.norm(rd - d) / np.linalg.norm(d)), 'delta_peak': float(rd.max()), 'phantom_peak': float(d.max()),
@@ -88,6 +103,7 @@ def main():
     loss = _option('--loss', 'lsq')
     multiplier = float(_option('--poisson-multiplier', 2e6))
     slice_binning = int(_option('--slice-binning', 1))
+    refine = tuple(k for k in _option('--refine-geometry', '').split(',') if k)
     n = int(sys.argv[1]) if len(sys.argv) > 1 else 128
     n_theta = int(sys.argv[2]) if len(sys.argv) > 2 else 60
     n_epochs = int(sys.argv[3]) if len(sys.argv) > 3 else 100
@@ -96,7 +112,10 @@ def main():
     fp = 'inf' if fp == 'inf' else tuple(float(z) for z in fp.split(',')) if ',' in fp else float(fp)
     mb = int(sys.argv[6]) if len(sys.argv) > 6 else 10
     propagator = sys.argv[7] if len(sys.argv) > 7 else 'fft'
-    r = run(n, n_theta, n_epochs, lr, fp, mb=mb, propagator=propagator, loss=loss, multiplier=multiplier, slice_binning=slice_binning)
+    r = run(n, n_theta, n_epochs, lr, fp, mb=mb, propagator=propagator, loss=loss, multiplier=multiplier, slice_binning=slice_binning,
+            refine=refine)
+    for k, (start, reached, truth) in r['geometry'].items():
+        print('{}: nominal {:.4f}, refined {:.4f}, simulated with {:.4f}'.format(k, start, reached, truth))
     if slice_binning > 1:
         print('slice_binning {}: {} propagation steps per angle'.format(slice_binning, n // slice_binning))
     print('reconstruct_fullfield (propagator {}, loss {}) {}^3, {} angles, {} epochs in minibatches of {}: {:.1f} s ({:.1f} ms per Adam step, entry point to files)'.format(

@@ -454,6 +454,18 @@ int bdof_rotate_rigid(bdof_ctx* ctx, const void* vol, int NXv, int NZv, int NYv,
 int bdof_set_object_rigid(bdof_ctx* ctx, const void* vol, int NXv, int NZv, int NYv, const double* prm, int B, int conv);
 int bdof_rotate_rigid_adjoint(bdof_ctx* ctx, const void* grot, int NXv, int NZv, int NYv, const double* prm, int B, void* gvol, int row0,
                               int n_rows, int accumulate, float scale);
+/* The derivative of the loss with respect to the map itself, from what the three calls above leave on the device: the volume, the
+ * rows prm and the rotated-frame gradient grot ([B][NZv][NXv][NYv] pairs; NULL: the ctx's own, bdof_grot()).  With o~ = (x, z, y, 1)
+ *     out[b][a][j] = sum_o q_a(o) o~_j,   q_a(o) = sum_c grot_c(o) dV_c/dp_a (p(o)),   a in (x', z', y'), j in 0..3,
+ * the layout of prm: DEVICE float64 [B][12] (accumulate != 0: added to what is there).  dV/dp_a is taken inside the cell floor(p)
+ * of the forward map — over its 8 corners, -1 or +1 by the corner's bit along a, times the other two axes' factors, times V(corner),
+ * a corner outside the volume counting 0.  A point ON a lattice plane belongs to the cell floor gives it, so it takes the
+ * RIGHT-HAND derivative; at zero tilt and roll that is every voxel's y.  Weights, tap sums and q_a in float32 (the forward's cell
+ * and fractions, bit for bit), the sums over voxels in float64, in per-workgroup records whose number and rows depend on
+ * (NXv, NZv) only, added in a fixed order without atomics: element b has the same bits alone, in a batch and in a repeated call.
+ * Shape rules and error codes are bdof_rotate_rigid_adjoint's (BDOF_ERR_SIZE: an odd NY, the 2^31 limits). */
+int bdof_rotate_rigid_param_grad(bdof_ctx* ctx, const void* vol, const void* grot, int NXv, int NZv, int NYv, const double* prm, int B,
+                                 double* out /* DEVICE [B][12] */, int accumulate);
 
 /* Ptychography: adjoint of rotate + zero-pad + per-position window (cnn_propagator/ptychography.py:32-34,42-73) for a
  * batch whose elements all use rotation angle `angle` and windows at (xoff[b], yoff[b]); gvol: device [n_dest][volNY] pairs. */

@@ -4,10 +4,13 @@ free_prop_cm = 1e-4, plane probe): ms of the forward binding (bdof_set_object_bi
     bilinear       rotation='bilinear' (the yardstick, same run)
     trilinear0     rotation='trilinear' at zero tilt (the same geometry as bilinear)
     trilinear30    rotation='trilinear' with the axis tilted 30 degrees towards the beam.
+--geometry: trilinear30 against trilinear30_refined, the same step with refine_geometry on all five names (per step: the
+parameter-gradient kernels, the download of B * 12 doubles, which waits for the stream, the chain rule and Adam on the host); both
+also time the kernels alone (param_grad_kernel_ms: launches only, one wait at the end) and with the download (param_grad_host_ms).
 Every mode runs in a child process of its own under `timeout`, one after another; the first one that fails ends the script with
 its status.  Prints one JSON line.
 
-usage: python tools/bench_rigid.py [--size 256] [--angles 50] [--steps 10] [--warmup 2] [--limit 240]
+usage: python tools/bench_rigid.py [--geometry] [--size 256] [--angles 50] [--steps 10] [--warmup 2] [--limit 240]
        python tools/bench_rigid.py --mode trilinear30 ...      (one mode, in this process)"""
 import argparse
 import json
@@ -22,7 +25,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 MODES = {'bilinear': dict(rotation='bilinear'), 'trilinear0': dict(rotation='trilinear'),
-         'trilinear30': dict(rotation='trilinear', axis_tilt=np.pi / 6)}
+         'trilinear30': dict(rotation='trilinear', axis_tilt=np.pi / 6),
+         'trilinear30_refined': dict(rotation='trilinear', axis_tilt=np.pi / 6, refine_geometry=('center', 'axis_tilt', 'axis_roll', 'theta', 'shifts'))}
 
 
 def one_mode(mode, n, mb, steps, warmup):
@@ -56,6 +60,13 @@ def one_mode(mode, n, mb, steps, warmup):
     out['bind_ms'] = timed(lambda i: s.rot.stage(s.eng, s.x[s.cur], idx, mb, s.conv), steps)
     s._rot_loss_grad(idx)                       # a rotated-frame gradient for the adjoint to take back
     out['adjoint_ms'] = timed(lambda i: s._produce()(0, n), steps)
+    if MODES[mode]['rotation'] == 'trilinear':
+        from beyond_dof_amd._lib import DeviceBuffer
+        dprm = DeviceBuffer.zeros(s.ctx, (mb, 12), np.float64)
+        launch = lambda i: s.ctx.check(s.ctx.lib.bdof_rotate_rigid_param_grad(s.ctx.handle, s.x[s.cur].ptr, None, n, n, n, s.rot.prm_buf.ptr, mb, dprm.ptr, 0))
+        launch(0)
+        out['param_grad_kernel_ms'] = timed(launch, steps)
+        out['param_grad_host_ms'] = timed(lambda i: s.rot.param_gradient(s.x[s.cur]), steps)
     return {k: round(v, 3) for k, v in out.items()}
 
 
@@ -67,12 +78,13 @@ def main():
     ap.add_argument('--warmup', type=int, default=2)
     ap.add_argument('--limit', type=int, default=240, help='seconds a mode may take')
     ap.add_argument('--mode', choices=sorted(MODES))
+    ap.add_argument('--geometry', action='store_true', help='the trilinear30 step without and with refine_geometry')
     args = ap.parse_args()
     if args.mode:
         print(json.dumps(one_mode(args.mode, args.size, args.angles, args.steps, args.warmup)))
         return 0
     res = {}
-    for mode in ('bilinear', 'trilinear0', 'trilinear30'):
+    for mode in (('trilinear30', 'trilinear30_refined') if args.geometry else ('bilinear', 'trilinear0', 'trilinear30')):
         cmd = ['timeout', '-k', '10', str(args.limit), sys.executable, os.path.abspath(__file__), '--mode', mode, '--size', str(args.size),
                '--angles', str(args.angles), '--steps', str(args.steps), '--warmup', str(args.warmup)]
         r = subprocess.run(cmd, stdout=subprocess.PIPE)
