@@ -20,6 +20,7 @@
 #include "bdof_resident.h"
 #include "bdof_comm.h"
 #include "bdof_rigid.h"
+#include "bdof_windows.h"
 #include <rocfft/rocfft.h>
 #include <map>
 #include <optional>
@@ -209,6 +210,7 @@ struct bdof_ctx : Workspace {
     DevBuf<int> win_angle;                      // device copy of the batch's angle index
     DevBuf<int> heavy;                          // [1 + n_dest]: counter + deferred rows of the rotation adjoint
     DevBuf<double> prm_partial;                 // [B][P][12] per-workgroup records of bdof_rotate_rigid_param_grad (grown on demand)
+    int win_volNX = 0, win_volNY = 0;           // the rotated frame of the last bdof_window_stack: what bdof_window_stack_adjoint scatters into
     // profiling
     bool prof = false;
     int prof_stride = 1;                        // time every prof_stride-th launch of a class
@@ -3066,6 +3068,26 @@ int bdof_rotation_adjoint(bdof_ctx* c, int B, const int* angle_of_b, void* gvol,
     return bdof_rotation_adjoint_rows(c, B, angle_of_b, gvol, 0, c->adj_ndest, accumulate, scale);
 }
 
+}  // extern "C"  (two steps that both window adjoints take)
+// the device copy of the batch's one angle, for stage 2
+static int window_pad_angle(bdof_ctx* c, int angle) {
+    if (!c->win_angle) HIPC(c, c->win_angle.alloc(1));
+    HIPC(c, hipMemsetD32Async((hipDeviceptr_t)c->win_angle, angle, 1, c->stream));
+    return 0;
+}
+// stage 2: rotated frame (c->winpad, n_src rows of volNY pairs) -> volume (the full-field rotation adjoint with a batch of one)
+static int window_pad_adjoint(bdof_ctx* c, int n_src, int volNY, void* gvol, int accumulate, float scale) {
+    RotAdjK<false> r;
+    static_cast<RotAdjArgs&>(r) = RotAdjArgs{c->winpad, (float2*)gvol, c->adj_off, c->adj_order, c->win_angle, 1, n_src, c->adj_ndest, volNY,
+                                             accumulate, scale, c->heavy, c->heavy + 1, 0, c->adj_ndest};
+    HIPC(c, hipMemsetAsync(c->heavy, 0, sizeof(int), c->stream));
+    const int needwg = (c->adj_ndest + 3) / 4;
+    hipLaunchKernelGGL(k_rot_adjoint<false>, dim3(needwg < c->ncu * 8 ? needwg : c->ncu * 8), dim3(256), 0, c->stream, r);
+    hipLaunchKernelGGL(k_rot_adjoint_heavy<false>, dim3(c->ncu * 8), dim3(256), 0, c->stream, r);
+    return launched(c);
+}
+extern "C" {
+
 int bdof_window_rotation_adjoint(bdof_ctx* c, int B, int angle, const int* xoff, const int* yoff, void* gvol,
                                  int accumulate, float scale) {
     if (!c || !gvol || !xoff || !yoff) return BDOF_ERR_ARG;
@@ -3090,21 +3112,12 @@ int bdof_window_rotation_adjoint(bdof_ctx* c, int B, int angle, const int* xoff,
         HIPC(c, hipStreamSynchronize(c->stream));
         HIPC(c, c->winpad.alloc(need));
     }
-    if (!c->win_angle) HIPC(c, c->win_angle.alloc(1));
-    HIPC(c, hipMemsetD32Async((hipDeviceptr_t)c->win_angle, angle, 1, c->stream));
+    if (int r = window_pad_angle(c, angle)) return r;
     // stage 1: windows -> rotated frame
     const int z_per_wg = 8;
     hipLaunchKernelGGL(k_window_overlap_add, dim3(c->obj.volNX, (c->S + z_per_wg - 1) / z_per_wg), dim3(256), 0, c->stream, a,
                        c->winpad, z_per_wg);
-    // stage 2: rotated frame -> volume (the full-field rotation adjoint with a batch of one)
-    RotAdjK<false> r;
-    static_cast<RotAdjArgs&>(r) = RotAdjArgs{c->winpad, (float2*)gvol, c->adj_off, c->adj_order, c->win_angle, 1, n_src, c->adj_ndest, c->obj.volNY,
-                                             accumulate, scale, c->heavy, c->heavy + 1, 0, c->adj_ndest};
-    HIPC(c, hipMemsetAsync(c->heavy, 0, sizeof(int), c->stream));
-    const int needwg = (c->adj_ndest + 3) / 4;
-    hipLaunchKernelGGL(k_rot_adjoint<false>, dim3(needwg < c->ncu * 8 ? needwg : c->ncu * 8), dim3(256), 0, c->stream, r);
-    hipLaunchKernelGGL(k_rot_adjoint_heavy<false>, dim3(c->ncu * 8), dim3(256), 0, c->stream, r);
-    return launched(c);
+    return window_pad_adjoint(c, n_src, c->obj.volNY, gvol, accumulate, scale);
 }
 
 static AdamArgs adam_args(const void* x_old, void* x_new, const void* g, void* m, void* v, const float* mask, int NXv, int NZv, int NYv,
@@ -3358,6 +3371,96 @@ int bdof_rotate_rigid_adjoint(bdof_ctx* c, const void* grot, int NXv, int NZv, i
 int bdof_rotate_rigid_param_grad(bdof_ctx* c, const void* vol, const void* grot, int NXv, int NZv, int NYv, const double* prm, int B, double* out,
                                  int accumulate) {
     return rigid_param_grad(c, vol, grot, NXv, NZv, NYv, prm, B, out, accumulate);
+}
+
+}  // extern "C"
+
+// ---- ptychography windows at fractional origins (bdof_windows.h) ------------------------------------------------------------------
+// The shape rule of the three calls: even NY of the windows and of the volume (rows are bound and summed as float4 pairs), and a
+// rotated frame and a window batch whose row indices the kernels hold in an int.
+static int window_shape(bdof_ctx* c, const char* who, int volNX, int volNY, int B) {
+    if (volNX < 1 || volNY < 1) return fail(c, BDOF_ERR_ARG, std::string(who) + ": bad volume shape");
+    if (c->NY % 2 || volNY % 2) return fail(c, BDOF_ERR_SIZE, std::string(who) + " needs an even NY of the windows and of the volume");
+    if ((long long)volNX * c->S * volNY > 0x7fffffffLL || (long long)B * c->S * c->NX > 0x7fffffffLL)
+        return fail(c, BDOF_ERR_SIZE, std::string(who) + ": volNX * S * volNY and B * S * NX must be below 2^31");
+    return 0;
+}
+// the window-frame gradient a call reads: the caller's, or the ctx's own
+static int window_grot(bdof_ctx* c, const char* who, const void*& grot, int B) {
+    if (grot) return 0;
+    if (!c->grot) return fail(c, BDOF_ERR_STATE, std::string(who) + ": the ctx holds no gradient workspace (bdof_grot)");
+    if ((size_t)B * c->S * c->NX * c->NY > c->grot.size()) return fail(c, BDOF_ERR_ARG, std::string(who) + ": B windows do not fit bdof_grot");
+    grot = (const float2*)c->grot;
+    return 0;
+}
+
+extern "C" {
+
+int bdof_window_stack(bdof_ctx* c, const void* vol, int volNX, int volNY, const int* tab, const double* origin, int B, void* out_rows) {
+    const char* who = "bdof_window_stack";
+    if (!c || !vol || !tab || !origin || !out_rows) return BDOF_ERR_ARG;
+    if (int r = need_configured(c)) return r;
+    if (int r = check_batch(c, B)) return r;
+    if (int r = window_shape(c, who, volNX, volNY, B)) return r;
+    HIPC(c, hipSetDevice(c->device));
+    WinStackArgs a{(const float2*)vol, tab, origin, (float2*)out_rows, B, c->S, c->NX, c->NY, volNX, volNY};
+    const size_t nrows = (size_t)B * c->S * c->NX;
+    hipLaunchKernelGGL(k_window_stack, dim3((unsigned)std::min<size_t>((nrows + 3) / 4, (size_t)c->ncu * 16)), dim3(256), 0, c->stream, a);
+    c->win_volNX = volNX;
+    c->win_volNY = volNY;
+    return launched(c);
+}
+
+int bdof_window_stack_adjoint(bdof_ctx* c, const void* grot, int angle, const double* origin, int B, void* gvol, int accumulate, float scale) {
+    const char* who = "bdof_window_stack_adjoint";
+    if (!c || !origin || !gvol) return BDOF_ERR_ARG;
+    if (int r = need_configured(c)) return r;
+    if (!c->adj_off) return fail(c, BDOF_ERR_STATE, std::string(who) + ": bdof_set_rotation_adjoint has not been called");
+    if (!c->win_volNX) return fail(c, BDOF_ERR_STATE, std::string(who) + ": no bdof_window_stack has been run (it sets the rotated frame the windows lie in)");
+    if (int r = check_batch(c, B)) return r;
+    if (angle < 0) return fail(c, BDOF_ERR_ARG, std::string(who) + ": angle index outside the rotation tables");
+    const int volNX = c->win_volNX, volNY = c->win_volNY;
+    if (int r = window_shape(c, who, volNX, volNY, B)) return r;
+    if (int r = window_grot(c, who, grot, B)) return r;
+    HIPC(c, hipSetDevice(c->device));
+    if (B > BDOF_WIN_MAXLIST) {
+        // only then can a column's list overflow: count on the host, refuse, never truncate
+        std::vector<double> host((size_t)2 * B);
+        HIPC(c, hipMemcpyAsync(host.data(), origin, sizeof(double) * host.size(), hipMemcpyDeviceToHost, c->stream));
+        HIPC(c, hipStreamSynchronize(c->stream));
+        if (win_max_per_column(host.data(), B, c->NX, c->NY, volNX, volNY) > BDOF_WIN_MAXLIST)
+            return fail(c, BDOF_ERR_SIZE, std::string(who) + ": more than BDOF_WIN_MAXLIST (1024) windows touch one column of the rotated frame");
+    }
+    ProfScope ps(c, BDOF_K_ROT_ADJ, c->stream);
+    const int n_src = c->S * volNX;
+    const size_t need = (size_t)n_src * volNY;
+    if (c->winpad.size() < need) {
+        HIPC(c, hipStreamSynchronize(c->stream));
+        HIPC(c, c->winpad.alloc(need));
+    }
+    if (int r = window_pad_angle(c, angle)) return r;
+    WinShiftAdjArgs a{(const float2*)grot, origin, B, c->S, c->NX, c->NY, volNX, volNY};
+    const int z_per_wg = 8;
+    hipLaunchKernelGGL(k_window_overlap_add_shifted, dim3(volNX, (c->S + z_per_wg - 1) / z_per_wg), dim3(256), 0, c->stream, a,
+                       (float2*)c->winpad, z_per_wg);
+    return window_pad_adjoint(c, n_src, volNY, gvol, accumulate, scale);
+}
+
+int bdof_window_position_grad(bdof_ctx* c, const void* vol, int volNX, int volNY, const int* tab, const void* grot, const double* origin, int B,
+                              double* out, int accumulate) {
+    const char* who = "bdof_window_position_grad";
+    if (!c || !vol || !tab || !origin || !out) return BDOF_ERR_ARG;
+    if (int r = need_configured(c)) return r;
+    if (int r = check_batch(c, B)) return r;
+    if (int r = window_shape(c, who, volNX, volNY, B)) return r;
+    if (int r = window_grot(c, who, grot, B)) return r;
+    HIPC(c, hipSetDevice(c->device));
+    const int P = win_position_partials(c->S, c->NX);
+    HIPC(c, c->prm_partial.room((size_t)B * P * 2));           // (shared with bdof_rotate_rigid_param_grad: the calls are stream-ordered)
+    WinStackArgs a{(const float2*)vol, tab, origin, (float2*)grot, B, c->S, c->NX, c->NY, volNX, volNY};
+    hipLaunchKernelGGL(k_window_position_grad, dim3((unsigned)((size_t)B * P)), dim3(256), 0, c->stream, a, P, (double*)c->prm_partial);
+    hipLaunchKernelGGL(k_window_position_sum, dim3(B), dim3(64), 0, c->stream, (const double*)c->prm_partial, P, out, accumulate);
+    return launched(c);
 }
 
 int bdof_regularizer_value(bdof_ctx* c, const void* x, int NXv, int NZv, int NYv, double* sums) {

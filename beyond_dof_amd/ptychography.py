@@ -14,6 +14,7 @@ import time
 import numpy as np
 
 from . import h5io, tiffio, util
+from . import positions as probe_positions
 from .comm import get_comm
 from .fullfield import create_probe_initial_guess, upsample_2x
 from .misc import create_summary, SUMMARY_PRESET_PTYCHO, SUMMARY_GEOMETRY
@@ -72,7 +73,7 @@ def reconstruct_ptychography(fname, probe_pos, probe_size, obj_size, theta_st=0,
                              pupil_function=None, probe_circ_mask=0.9, finite_support_mask=None,
                              forward_algorithm='fresnel', dynamic_dropping=True, dropping_threshold=8e-5,
                              n_dp_batch=20, object_type='normal', loss_type='lsq', poisson_multiplier=2e6, slice_binning=1,
-                             detector_weights=None, **kwargs):
+                             detector_weights=None, position_offsets=None, refine_positions=None, position_learning_rate=0.05, **kwargs):
     t_zero = time.time()
     comm = kwargs.get('comm') or get_comm()
     size, rank = comm.size, comm.rank
@@ -109,7 +110,14 @@ def reconstruct_ptychography(fname, probe_pos, probe_size, obj_size, theta_st=0,
     # level's depth must divide by b.  What each of the three needs of propagator and adjoint precision: engine.OPTION_NEEDS.
     check_model_options(loss_type, poisson_multiplier, detector_weights, slice_binning, propagator=propagator,
                         adjoint_precision=kwargs.get('adjoint_precision'), rotation=rotation)
-    if slice_binning > 1:
+    # position_offsets / refine_positions / position_learning_rate: sub-pixel probe positions and their refinement (PtychoSolver).
+    # Offsets are kept in full-resolution pixels: level ds runs with offsets / ds on top of (probe_pos / ds).astype(int), and what
+    # a level refined is the next level's start.  The float64 first step does not carry them, so the DEFAULT becomes 'float32' and
+    # an explicit other choice raises, as with slice_binning.  The result goes to positions.npy (the offsets, (n_theta, n_pos, 2))
+    # and as a refined_positions line into summary.txt.
+    offsets = probe_positions.check_positions(position_offsets, refine_positions, len(probe_pos), propagator=propagator, slice_binning=slice_binning,
+                                              adjoint_precision=kwargs.get('adjoint_precision'), n_batch_per_update=n_batch_per_update)
+    if slice_binning > 1 or offsets is not None:
         adjoint_precision = 'float32'
     for lv in range(multiscale_level):
         if (int(obj_size[2] / 2 ** lv) if lv else int(obj_size[2])) % slice_binning:
@@ -127,6 +135,9 @@ def reconstruct_ptychography(fname, probe_pos, probe_size, obj_size, theta_st=0,
     theta = -np.linspace(theta_st, theta_end, prj.shape[0], dtype='float32')[prj_theta_ind]
     geo.select(n_theta, prj_theta_ind)
     original_shape = [n_theta] + list(prj.shape[1:])
+    if offsets is not None:
+        offsets = probe_positions.check_positions(offsets, refine_positions, len(probe_pos), n_theta)           # (now against the angles)
+        offsets = offsets_start = np.array(np.broadcast_to(offsets, (n_theta, len(probe_pos), 2)))
     print_flush('Data shape: {}'.format(original_shape), 0, rank)
 
     if output_folder is None:
@@ -153,6 +164,9 @@ def reconstruct_ptychography(fname, probe_pos, probe_size, obj_size, theta_st=0,
 
         coord_ls = None if trilinear else util.rotation_lookup_files(this_obj_size, n_theta, comm)
         geometry = dict(geo.for_level(ds_level), rotation=rotation, theta=theta) if trilinear else {}
+        if offsets is not None:
+            geometry.update(position_offsets=probe_positions.to_level(offsets, ds_level), refine_positions=refine_positions,
+                            position_learning_rate=position_learning_rate)
 
         np.random.seed(seed)                               # rank 0 initialises and broadcasts in the reference (:169-208)
         if first_level:
@@ -274,6 +288,13 @@ def reconstruct_ptychography(fname, probe_pos, probe_size, obj_size, theta_st=0,
             geo.keep(solver.geometry(), ds_level)
             if rank == 0:
                 geo.record(solver.geometry(), ds_level, output_folder, summary=True)
+        if offsets is not None:
+            offsets = probe_positions.from_level(solver.positions(), ds_level)
+            if rank == 0:
+                np.save(os.path.join(output_folder, 'positions.npy'), offsets)
+                if ds_level == 1:
+                    with open(os.path.join(output_folder, 'summary.txt'), 'a') as f:
+                        f.write(probe_positions.summary_line(offsets_start, offsets))
         obj_delta, obj_beta = obj_delta.astype(float), obj_beta.astype(float)
         first_level = False
         del solver

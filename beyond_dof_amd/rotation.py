@@ -152,6 +152,14 @@ class LookupRotation(object):
         """ptychography: the window gradients in the ctx into the volume gradient g"""
         self.ctx.check(self.ctx.lib.bdof_window_rotation_adjoint(self.ctx.handle, self.mb, i_theta, xo, yo, g.ptr, 0, 1.0))
 
+    def window_source(self, x, i_theta):
+        """ptychography at fractional positions: (rows, table of the step's angle) bdof_window_stack gathers from — device addresses"""
+        return x.ptr, self.tab.ptr + int(i_theta) * self.dim_z * self.dim_x * 4
+
+    def window_stack_adjoint(self, i_theta, origin, g):
+        """... and the window gradients in the ctx, cut at the origins `origin`, into the volume gradient g"""
+        self.ctx.check(self.ctx.lib.bdof_window_stack_adjoint(self.ctx.handle, None, int(i_theta), origin.ptr, self.mb, g.ptr, 0, 1.0))
+
 
 class MaterialisedRotation(LookupRotation):
     """rotation='bilinear' / 'trilinear' (KINDS), behind the same methods: the minibatch's rotated objects are written out at every
@@ -243,3 +251,10 @@ class RotatedCopy(MaterialisedRotation):
 
     def param_gradient(self, x, grot=None):
         return MaterialisedRotation.param_gradient(self, x, self.g_rot if grot is None else grot)
+
+    def window_source(self, x, i_theta):
+        return self.copy.ptr, self.tab.ptr
+
+    def window_stack_adjoint(self, i_theta, origin, g):
+        self.ctx.check(self.ctx.lib.bdof_window_stack_adjoint(self.ctx.handle, None, 0, origin.ptr, self.n_windows, self.g_rot.ptr, 0, 1.0))
+        self.adjoint(None, g, 0, self.dim_x, 0, grot=self.g_rot)

@@ -23,6 +23,7 @@ import numpy as np
 from . import _lib
 from ._lib import DeviceBuffer
 from . import rotation as rotations
+from . import positions as probe_positions
 from . import util
 from .comm import PseudoComm
 from .engine import MultisliceEngine, RESIDENT_SIZES, check_model_options
@@ -619,8 +620,18 @@ class PtychoSolver(_VolumeSolver):
                  variant='numpy_skip_last', comm=None, device=0, stream=None, coord_ls=None, propagator='fft', kernel_size=17,
                  adjoint64=None, engine=None, loss_type='lsq', poisson_multiplier=2e6, slice_binning=1, detector_weights=None,
                  rotation='nearest', theta=None, axis_tilt=0., axis_roll=0., center=None, rotation_matrices=None, refine_geometry=(),
-                 geometry_learning_rate=0.05):
-        """refine_geometry / geometry_learning_rate: as for FullfieldSolver (the step's one angle moves).
+                 geometry_learning_rate=0.05, position_offsets=None, refine_positions=None, position_learning_rate=0.05):
+        """position_offsets: (n_pos, 2) or (n_theta, n_pos, 2) pixels in the order of probe_pos (y, x), added to probe_pos: the windows
+        are then cut at fractional origins.  refine_positions: None, 'shared' (one offset per position for all angles) or 'per_angle':
+        every step() also takes position_gradient() (bdof_window_position_grad), sums it over the ranks and moves the listed offsets
+        by a host Adam whose step position_learning_rate is in pixels (positions.ProbePositions); positions() returns them.  With
+        either keyword set a step cuts the minibatch's windows into a stack [mb][S][px][py] of (delta, beta) pairs
+        (bdof_window_stack), binds it as a batch of already rotated objects and sweeps without angle and window offsets; the window
+        adjoint is bdof_window_stack_adjoint.  MEMORY: the stack and the modulation table built from it take mb * S * px * py * 8
+        bytes EACH — 4.25 GB each for 400 windows of 72 x 72 over 256 slices.  Transfer-function propagator, float32 sweeps (no
+        adjoint64), slice_binning 1, every engine, both rotations; with neither keyword set nothing of this runs and a step has the
+        bits it had.  Gauge: the mean offset is a translation of the object against the scan and is not removed.
+        refine_geometry / geometry_learning_rate: as for FullfieldSolver (the step's one angle moves).
         rotation='nearest': the lookup tables.  'trilinear': the rigid map of FullfieldSolver(rotation='trilinear'), with the same
         theta / axis_tilt / axis_roll / center / rotation_matrices (tilt 0: ptychography's interpolating rotation), through a rotated
         copy per step (rotation.RotatedCopy).  slice_binning > 1 keeps to rotation='nearest'.
@@ -634,6 +645,9 @@ class PtychoSolver(_VolumeSolver):
         if rotation not in ('nearest', 'trilinear'):
             raise ValueError("rotation must be 'nearest' or 'trilinear'")
         _check_options(propagator, adjoint64, loss_type, poisson_multiplier, detector_weights, slice_binning, rotation=rotation)
+        offsets = probe_positions.check_positions(position_offsets, refine_positions, len(probe_pos), n_theta, propagator=propagator,
+                                                  slice_binning=slice_binning, adjoint_precision='float64' if adjoint64 else None)
+        self.pos = None if offsets is None else probe_positions.ProbePositions(n_theta, len(probe_pos), offsets, refine_positions, position_learning_rate)
         self.conv = propagator == 'conv'
         self.dim_y, self.dim_x, self.dim_z = [int(s) for s in obj_size]
         self.rot = rotations.choose(rotation, obj_size, n_theta, coord_ls, theta, (axis_tilt, axis_roll, center, rotation_matrices),
@@ -670,9 +684,15 @@ class PtychoSolver(_VolumeSolver):
         self._init_volume()
         self.meas_stage = DeviceBuffer(self.ctx, self.mb * self.py * self.px * 4, np.float32, (self.mb, self.py, self.px))
         self.idx_buf = DeviceBuffer(self.ctx, 4 * self.mb * 4, np.int32, (4, self.mb))
+        if self.pos is not None:
+            # the window stack [mb][S][px][py] of pairs, the origins (u, v) it is cut at and their derivative
+            self.stack = DeviceBuffer(self.ctx, self.mb * self.dim_z * self.px * self.py * 8, np.float32, (self.mb, self.dim_z, self.px, self.py, 2))
+            self.origin_buf = DeviceBuffer(self.ctx, self.mb * 16, np.float64, (self.mb, 2))
+            self.dpos_buf = DeviceBuffer(self.ctx, self.mb * 16, np.float64, (self.mb, 2))
         self._bind_volume()
         self.rot.attach(self.eng)
         self._last = None
+        self._last_pos = None
 
     def set_measurements(self, prj_abs_all):
         """All diffraction amplitudes |prj| (n_theta, n_pos, py, px) resident on the device (a cfg5-sized dataset is 0.75 GB):
@@ -702,17 +722,68 @@ class PtychoSolver(_VolumeSolver):
             self.meas_stage.upload(self.eng.meas_layout(prj_abs_batch))
         return p, p + 4 * self.mb, p + 8 * self.mb
 
+    def _stack_windows(self, i_theta, pos_idx):
+        """The windows of positions pos_idx (at most mb) at their fractional origins, cut from the volume under angle i_theta
+        into self.stack and bound as that many already rotated objects."""
+        pos_idx = np.asarray(pos_idx)
+        n = len(pos_idx)
+        at = self.probe_pos[pos_idx] + self.pos.of(i_theta, pos_idx)
+        origin = np.zeros((self.mb, 2))
+        origin[:n, 0] = at[:, 1] - self.half[1]          # u: along x (axis 1), as _stage's integer origins
+        origin[:n, 1] = at[:, 0] - self.half[0]          # v: along y (axis 0)
+        self.origin_buf.upload(origin)
+        self.rot.stage(self.eng, self.x[self.cur], [int(i_theta)], 1, self.conv)
+        self._source = self.rot.window_source(self.x[self.cur], i_theta)
+        self.ctx.check(self.ctx.lib.bdof_window_stack(self.ctx.handle, self._source[0], self.dim_x, self.dim_y, self._source[1], self.origin_buf.ptr,
+                                                      n, self.stack.ptr))
+        self.eng.set_volume(self.stack, n * self.dim_z * self.px, self.py, None, 0, 0)
+        self._last_pos = (int(i_theta), pos_idx.copy())
+
     def _win_loss_grad(self, i_theta, pos_idx, prj_abs_batch, use64=False):
         a, xo, yo = self._stage(i_theta, pos_idx, prj_abs_batch)
         f64 = self.f64 is True or (use64 and self.f64 == 'first')
-        self.rot.stage(self.eng, self.x[self.cur], [int(i_theta)], 1, self.conv)
-        self.eng.loss_grad_device(self.mb, a, xo, yo, self.meas_stage.ptr, conv=self.conv, f64=f64)
+        if self.pos is not None:
+            self._stack_windows(i_theta, pos_idx)
+            self.eng.loss_grad_device(self.mb, None, None, None, self.meas_stage.ptr)
+        else:
+            self.rot.stage(self.eng, self.x[self.cur], [int(i_theta)], 1, self.conv)
+            self.eng.loss_grad_device(self.mb, a, xo, yo, self.meas_stage.ptr, conv=self.conv, f64=f64)
         self._last = (int(i_theta), xo, yo)
 
     def _produce_all(self):
         i_theta, xo, yo = self._last
         self._g_is_local()
-        self.rot.window_adjoint(i_theta, xo, yo, self.g)
+        if self.pos is not None:
+            self.rot.window_stack_adjoint(i_theta, self.origin_buf, self.g)
+        else:
+            self.rot.window_adjoint(i_theta, xo, yo, self.g)
+
+    # ---- probe positions (positions.ProbePositions) ---------------------------------------------------------------------------
+    def positions(self):
+        """The current offsets (n_theta, n_pos, 2), pixels in the order of probe_pos (y, x): what refine_positions has made of them."""
+        if self.pos is None:
+            raise ValueError('positions(): the solver was built without position_offsets and refine_positions')
+        return self.pos.values()
+
+    def position_gradient(self):
+        """dL/d(offset) of the data term for the positions of the last loss_and_grad (or, inside step, of the step, before the tail
+        flips the volume), (mb, 2) in the order of probe_pos (y, x), not reduced over the ranks: one reduction on the device over the
+        volume that was cut, the origins and the window-frame gradient (bdof_window_position_grad).  The download waits for the stream."""
+        if self.pos is None or self._last_pos is None:
+            raise RuntimeError('position_gradient() follows loss_and_grad() or runs inside step() of a solver built with position_offsets or refine_positions')
+        self.ctx.check(self.ctx.lib.bdof_window_position_grad(self.ctx.handle, self._source[0], self.dim_x, self.dim_y, self._source[1], None,
+                                                              self.origin_buf.ptr, self.mb, self.dpos_buf.ptr, 0))
+        self.ctx.sync()
+        return self.dpos_buf.download()[:, ::-1].copy()           # (dL/du, dL/dv) = (x, y) -> (y, x)
+
+    def _refine_positions(self):
+        """step, before the tail: gradient, sum over the ranks (/ size, as the volume gradient), host Adam"""
+        if self.pos is None or not self.pos.refine:
+            return
+        dense = self.pos.dense(self.position_gradient(), *self._last_pos)
+        if self.comm.size > 1:
+            dense = self.comm.allreduce_sum_host(dense) / self.comm.size
+        self.pos.update(dense)
 
     def _step_angles(self):
         return None if self._last is None else np.array([self._last[0]], dtype=np.int64)
@@ -737,12 +808,17 @@ class PtychoSolver(_VolumeSolver):
         self._probe_collect()
         self._produce_all()
         self._refine_geometry()          # (after the window adjoint: the rotated-frame gradient is the rotated copy's)
+        self._refine_positions()
         self._tail(lambda x0, nx: None, i_batch, learning_rate, clip=clip, use_mask=False, n_slabs=n_slabs, sharded=sharded)
         self._probe_apply()
         return self._get_loss() if want_loss else None
 
     def forward(self, i_theta, pos_idx):
         pos = self.probe_pos[np.asarray(pos_idx)]
+        if self.pos is not None:
+            self._stack_windows(i_theta, pos_idx)
+            self._last_pos = None                    # (no gradient belongs to these windows)
+            return self.eng.forward(len(pos))
         self.rot.stage(self.eng, self.x[self.cur], [int(i_theta)], 1, self.conv)
         return self.eng.forward(len(pos), angle_idx=[self.rot.window_angle(i_theta)] * len(pos), xoff=pos[:, 1] - self.half[1],
                                 yoff=pos[:, 0] - self.half[0], conv=self.conv)

@@ -3,7 +3,13 @@ patterns of a gaussian probe scanned over a phantom at a set of angles (simulate
 as exchange/data (n_theta, n_pos, py, px), reconstructed with reconstruct_ptychography and compared with the phantom.  On one MI355X: 128^3, 121 positions x 30 angles,
 40 epochs at learning rate 5e-8 in 4.7 s — delta correlation 0.996, relative L2 error 0.09, beta correlation 0.88.
 
-    python examples/reconstruct_ptycho_phantom.py [n=128] [n_theta=30] [n_epochs=20] [learning_rate=1e-7]
+    python examples/reconstruct_ptycho_phantom.py [n=128] [n_theta=30] [n_epochs=20] [learning_rate=1e-7] [--refine-positions]
+
+--refine-positions: the patterns are simulated with every scan position jittered by U(-1, 1) pixel (position_offsets of the
+simulating solver) and reconstructed from the nominal positions with refine_positions='shared'; the rms distance of the refined
+offsets from the jitter is printed beside the figures above (the mean offset is a translation of the object and is taken out of
+that distance).  From an empty volume the offsets follow an object that is still forming: at the default size they end at 1.39 px
+rms from the truth after starting at 0.85 (delta correlation 0.988) — refinement wants a formed object first.
 """
 import os
 import sys
@@ -28,7 +34,7 @@ def phantom(n, rng):
     return d
 
 
-def run(n=128, n_theta=30, n_epochs=20, lr=1e-7, quiet=False):
+def run(n=128, n_theta=30, n_epochs=20, lr=1e-7, quiet=False, refine_positions=False):
     """Simulate, write exchange/data, reconstruct, compare with the phantom (tests/test_gpu_convergence.py asserts the figures)."""
     import contextlib
     import io
@@ -41,7 +47,8 @@ def run(n=128, n_theta=30, n_epochs=20, lr=1e-7, quiet=False):
     cwd = os.getcwd()
     with tempfile.TemporaryDirectory() as td:
         os.chdir(td)
-        s = PtychoSolver((n, n, n), psz, pos, n_theta, len(pos), 5000., 1e-7, prr, pii)
+        jitter = rng.uniform(-1, 1, size=(len(pos), 2)) if refine_positions else None
+        s = PtychoSolver((n, n, n), psz, pos, n_theta, len(pos), 5000., 1e-7, prr, pii, position_offsets=jitter)
         s.set_volume(d, 0.1 * d)
         data = np.stack([s.forward(t, np.arange(len(pos))) for t in range(n_theta)]).astype(np.complex64)
         del s
@@ -52,24 +59,33 @@ def run(n=128, n_theta=30, n_epochs=20, lr=1e-7, quiet=False):
             rd, rb = reconstruct_ptychography('data.h5', pos, psz, (n, n, n), theta_st=0, theta_end=2 * np.pi, n_epochs=n_epochs,
                                               learning_rate=lr, minibatch_size=len(pos), energy_ev=5000, psize_cm=1e-7, save_path='case',
                                               output_folder='out', initial_guess=[np.zeros_like(d), np.zeros_like(d)],
-                                              probe_type='gaussian', seed=3, n_dp_batch=len(pos), alpha_d=0, alpha_b=0, **kw)
+                                              probe_type='gaussian', seed=3, n_dp_batch=len(pos), alpha_d=0, alpha_b=0,
+                                              refine_positions='shared' if refine_positions else None, **kw)
         dt = time.time() - t0
+        moved = np.load(os.path.join('case', 'out', 'positions.npy'))[0] if refine_positions else None
         os.chdir(cwd)
-    return {'n': n, 'n_pos': len(pos), 'n_theta': n_theta, 'n_epochs': n_epochs, 'seconds': dt,
+    extra = {}
+    if refine_positions:
+        rms = lambda a: float(np.sqrt(np.mean(np.sum((a - a.mean(axis=0)) ** 2, axis=1))))
+        extra = {'position_rms_start': rms(jitter), 'position_rms_end': rms(moved - jitter)}
+    return {**extra, 'n': n, 'n_pos': len(pos), 'n_theta': n_theta, 'n_epochs': n_epochs, 'seconds': dt,
             'delta_corr': float(np.corrcoef(rd.ravel(), d.ravel())[0, 1]), 'delta_rel_l2': float(np.linalg.norm(rd - d) / np.linalg.norm(d)),
             'delta_peak': float(rd.max()), 'phantom_peak': float(d.max()), 'beta_corr': float(np.corrcoef(rb.ravel(), 0.1 * d.ravel())[0, 1])}
 
 
 def main():
-    n = int(sys.argv[1]) if len(sys.argv) > 1 else 128
-    n_theta = int(sys.argv[2]) if len(sys.argv) > 2 else 30
-    n_epochs = int(sys.argv[3]) if len(sys.argv) > 3 else 20
-    lr = float(sys.argv[4]) if len(sys.argv) > 4 else 1e-7
-    r = run(n, n_theta, n_epochs, lr)
+    argv = [a for a in sys.argv[1:] if a != '--refine-positions']
+    n = int(argv[0]) if len(argv) > 0 else 128
+    n_theta = int(argv[1]) if len(argv) > 1 else 30
+    n_epochs = int(argv[2]) if len(argv) > 2 else 20
+    lr = float(argv[3]) if len(argv) > 3 else 1e-7
+    r = run(n, n_theta, n_epochs, lr, refine_positions='--refine-positions' in sys.argv[1:])
     print('reconstruct_ptychography {}^3, {} positions x {} angles, {} epochs: {:.1f} s'.format(n, r['n_pos'], n_theta, n_epochs, r['seconds']))
     print('delta: correlation with the phantom {:.4f}; relative L2 error {:.3f}; peak {:.3e} vs {:.3e}'.format(
         r['delta_corr'], r['delta_rel_l2'], r['delta_peak'], r['phantom_peak']))
     print('beta : correlation {:.4f}'.format(r['beta_corr']))
+    if 'position_rms_end' in r:
+        print('positions: rms distance from the true offsets {:.3f} px at the start, {:.3f} px at the end'.format(r['position_rms_start'], r['position_rms_end']))
 
 
 if __name__ == '__main__':

@@ -472,6 +472,38 @@ int bdof_rotate_rigid_param_grad(bdof_ctx* ctx, const void* vol, const void* gro
 int bdof_window_rotation_adjoint(bdof_ctx* ctx, int B, int angle, const int* xoff, const int* yoff, void* gvol,
                                  int accumulate, float scale);
 
+/* Ptychography windows at FRACTIONAL origins (sub-pixel probe positions): the window stack, its exact adjoint and the derivative
+ * of the loss with respect to the origins.  Window size (NX, NY) and depth S are the configured wavefield's.  Rotated frame
+ * R[z][xg][y] = row tab[z][xg] of vol (rows of volNY pairs; tab: DEVICE [S][volNX], the table of the batch's ONE angle), zero
+ * outside.  origin: DEVICE float64 [B][2] = (u_b, v_b), the pixel coordinate of window b's first voxel along x and along y:
+ *     i0 = floor(u), fx = u - i0;  j0 = floor(v), fy = v - j0       (in float64; a negative origin floors downwards)
+ *     W_b[z][i][j] = sum_{a,c in {0,1}} wx_a wy_c R[z][i0 + i + a][j0 + j + c],   wx = (1 - fx, fx), wy = (1 - fy, fy)
+ * with the factors rounded to float32 and a weight their float32 product wx_a wy_c; a tap of weight 0 or outside the volume is
+ * skipped, so at fx = fy = 0 the window is the integer cut of the sweeps' index math, value for value.  All three calls form
+ * (i0, j0, weights) with one function: the same bits.
+ * bdof_window_stack writes out_rows, device [B][S][NX][NY] pairs — a batch of already rotated objects for
+ * bdof_set_object(ctx, out_rows, B S NX, NY, NULL, 0, 0) — and records (volNX, volNY) in the ctx as the rotated frame of the windows.
+ * bdof_window_stack_adjoint: grot (device [B][S][NX][NY] pairs; NULL: the ctx's own, bdof_grot()) -> gvol, device [n_dest][volNY]
+ * pairs, as bdof_window_rotation_adjoint: first pad[z][xg][y] = sum_b sum_{a,c} wx_a wy_c grot_b[z][xg - i0_b - a][y - j0_b - c], a
+ * deterministic gather in the fixed order (j0, then b, then a, then c), then the rotation adjoint of `pad` under angle `angle` of
+ * the tables of bdof_set_rotation_adjoint (which it needs; a bound table it does NOT need: the bound object is the stack).  The
+ * rotated frame is that of the last bdof_window_stack (BDOF_ERR_STATE without one).  gvol = scale * result (+ gvol with
+ * accumulate != 0).  More than BDOF_WIN_MAXLIST = 1024 windows on one column of the rotated frame (a window touches NX + 1
+ * columns): BDOF_ERR_SIZE, checked on the host before anything is launched — nothing is ever dropped silently.
+ * bdof_window_position_grad: out, DEVICE float64 [B][2] = (dL/du_b, dL/dv_b) (accumulate != 0: added to what is there),
+ *     dL/du_b = sum_{z,i,j} sum_channels grot_b[z][i][j] sum_c wy_c (R[z][i0+i+1][j0+j+c] - R[z][i0+i][j0+j+c])
+ * and the same with x and y exchanged for dL/dv_b, taken INSIDE the cell floor gives: an origin on a lattice line takes the
+ * RIGHT-HAND derivative, as bdof_rotate_rigid_param_grad does.  Taps and products in float32, sums over voxels in float64 in
+ * per-workgroup records whose number and rows depend on (S, NX) only, added in a fixed order without atomics: element b has the
+ * same bits alone, in a batch and in a repeated call.
+ * BDOF_ERR_SIZE: an odd NY (of the windows or of the volume), volNX * S * volNY or B * S * NX of 2^31 or more. */
+int bdof_window_stack(bdof_ctx* ctx, const void* vol, int volNX, int volNY, const int* tab, const double* origin /* DEVICE [B][2] */, int B,
+                      void* out_rows);
+int bdof_window_stack_adjoint(bdof_ctx* ctx, const void* grot, int angle, const double* origin, int B, void* gvol, int accumulate,
+                              float scale);
+int bdof_window_position_grad(bdof_ctx* ctx, const void* vol, int volNX, int volNY, const int* tab, const void* grot, const double* origin,
+                              int B, double* out /* DEVICE [B][2] */, int accumulate);
+
 /* Fused regulariser gradient + Adam + mask + clip on a volume [NXv][NZv][NYv] of pairs.
  * Replaces cnn_propagator/fullfield.py:109-118 (gradient of the L1 + TV terms), apply_gradient_adam
  * (cnn_propagator/util.py:280-291) and the constraints of fullfield.py:359-362.  g is the data-term
