@@ -13,6 +13,7 @@ DET_NONE, DET_NEAR, DET_FAR = 0, 1, 2
 VARIANT_NUMPY_SKIP_LAST, VARIANT_TF_ALL = 0, 1
 LOSS_LSQ, LOSS_POISSON = 0, 1
 MAX_PLANES = 8          # BDOF_MAX_PLANES: detector planes per wavefield (bdof_set_detector_planes)
+MAX_MODES = 8           # BDOF_MAX_MODES: probe modes per window (bdof_set_probe_modes)
 CFG_GRAD, CFG_GENERIC, CFG_NO_RESIDENT, CFG_ALWAYS_RESIDENT, CFG_RECOMPUTE, CFG_NO_GROT, CFG_ADJOINT64 = 1, 2, 4, 8, 16, 32, 64
 K_ROW_FWD, K_COL_PROP, K_ROW_BWD, K_LOSS, K_ROT_ADJ, K_ADAM = range(6)
 KERNEL_CLASS_NAMES = ['row_fwd', 'col_prop', 'row_bwd', 'loss', 'rot_adjoint', 'adam']
@@ -42,6 +43,8 @@ _SIGNATURES = {
     'bdof_set_loss': (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_double]),
     'bdof_set_detector_weights': (ctypes.c_int, [_vp, _vp]),
     'bdof_set_detector_planes': (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp]),
+    'bdof_set_probe_modes': (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp, _vp]),
+    'bdof_probe_grad_modes': (ctypes.c_int, [_vp, _vp, ctypes.c_int]),
     'bdof_adjoint_carrier': (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp]),
     'bdof_probe_stack_supported': (ctypes.c_int, [_vp]),
     'bdof_set_probe_field': (ctypes.c_int, [_vp, _vp, _vp, _vp]),

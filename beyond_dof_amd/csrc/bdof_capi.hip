@@ -18,6 +18,7 @@
 #include "bdof_field.h"
 #include "bdof_conv64.h"
 #include "bdof_resident.h"
+#include "bdof_modes.h"
 #include "bdof_comm.h"
 #include "bdof_rigid.h"
 #include "bdof_windows.h"
@@ -127,6 +128,14 @@ struct Workspace {
     DevBuf<cf> hsT, hdetT, twR, res_carrier;
     DevBuf<cf> pstack, pdet, pdetT;              // carrier field of a localised probe (bdof_set_probe_stack); pdetT = det transposed
     DevBuf<double2> pdet64, pdetT64;             // the same planes in float64 (bdof_set_probe_field): the residual |d| - m is formed in float64
+    // Probe modes (bdof_set_probe_modes; bdof_modes.h): M > 0 carrier fields, built as bdof_set_probe_field builds its one, mode m
+    // at plane m of each buffer: the [M][steps][NX][NY] stacks and the [M][NX][NY] float64 detector planes, [x][y] (far field
+    // [kx][ky]) — what the sweeps and k_modes_couple read; the float32 and the transposed detector planes of the single probe have
+    // no reader under modes and are not built.  0: no modes, the probe of bdof_set_probe*
+    int n_modes = 0;
+    DevBuf<cf> m_stack;
+    DevBuf<double2> m_det64;
+    DevBuf<cf> m_zero;                           // zeros, max(NX NY, 2 S): the modes' eps_0 and their scalar carriers
     // rocFFT (generic-size engine, float64 paths, whole-field steps): one plan pair per (NX, NY, B, double)
     std::map<std::array<int, 4>, PlanPair> plans;
     FftExec fft;                                 // of the ctx's stream
@@ -257,8 +266,8 @@ static int check_range(bdof_ctx* c, int z0, int nz) {
 // ---- the model's options: which entry point carries which ----------------------------------------------------------------------
 // An option is in force on a ctx (`on`) or not; an entry point states the options it carries and admit() refuses it under any
 // other one that is in force, in the order of the table.  bdof_loss_grad, bdof_forward and the rest of the main path carry all
-// four and make no call.
-enum { CARRIES_NOTHING = 0, CARRIES_BINNING = 1, CARRIES_PLANES = 2, CARRIES_POISSON = 4, CARRIES_WEIGHTS = 8,
+// five and make no call.
+enum { CARRIES_NOTHING = 0, CARRIES_BINNING = 1, CARRIES_PLANES = 2, CARRIES_POISSON = 4, CARRIES_WEIGHTS = 8, CARRIES_MODES = 16,
        NO_DATA_TERM = CARRIES_POISSON | CARRIES_WEIGHTS };       // an entry point that computes no loss: the data term's options pass
 struct ModelOption { int bit; bool (*on)(const bdof_ctx*); const char* refusal; };       // (the refusal follows the caller's name)
 static const ModelOption MODEL_OPTIONS[] = {
@@ -266,6 +275,7 @@ static const ModelOption MODEL_OPTIONS[] = {
     {CARRIES_PLANES, [](const bdof_ctx* c) { return c->planes > 1; }, " does not carry detector planes: bdof_set_detector_planes(ctx, 1, NULL, NULL) first"},
     {CARRIES_POISSON, [](const bdof_ctx* c) { return c->loss_kind != BDOF_LOSS_LSQ; }, " computes the least-squares loss only: bdof_set_loss(BDOF_LOSS_LSQ) first"},
     {CARRIES_WEIGHTS, [](const bdof_ctx* c) { return (bool)c->wgt; }, " does not carry detector weights: bdof_set_detector_weights(ctx, NULL) first"},
+    {CARRIES_MODES, [](const bdof_ctx* c) { return c->n_modes > 0; }, " does not carry probe modes: bdof_set_probe_modes(ctx, 0, NULL, NULL, NULL) first"},
 };
 // (no ctx: passes, and the entry point's own argument check answers)
 static int admit(bdof_ctx* c, const char* who, int carries) {
@@ -286,6 +296,8 @@ static const CtxMode MODE_NOT_NEAR = {[](const bdof_ctx* c) { return c->det_mode
 static const CtxMode MODE_CONV = {[](const bdof_ctx* c) { return c->have_conv; }, "the real-space propagator (bdof_set_conv)"};
 static const CtxMode MODE_CARRIER_FIELD = {[](const bdof_ctx* c) { return (bool)c->pstack; }, "a carrier field (bdof_set_probe_stack / bdof_set_probe_field)"};
 static const CtxMode MODE_RANGE_CARRIER = {[](const bdof_ctx* c) { return c->range_car != nullptr; }, "range carriers (bdof_set_range_carrier)"};
+static const CtxMode MODE_STREAMING_ONLY = {[](const bdof_ctx* c) { return !c->resident && !c->generic; }, "a ctx whose only engine is the streaming one"};
+static const CtxMode MODE_PROBE_MODES = {[](const bdof_ctx* c) { return c->n_modes > 0; }, "probe modes (bdof_set_probe_modes)"};
 // "<setter>: <mode> does not carry <option>" for the first of `refused` that is on
 static int refuse_modes(bdof_ctx* c, const char* setter, const char* option, std::initializer_list<const CtxMode*> refused) {
     for (const CtxMode* m : refused)
@@ -297,6 +309,11 @@ static void drop_planes(bdof_ctx* c) {
     c->planes = 1;
     c->hdet_pl.reset(); c->hcomb_pl.reset(); c->det_pl.reset(); c->seed_pl.reset();
     c->hdet00_pl.clear();
+}
+// back to the probe of bdof_set_probe*: the modes' carrier fields go
+static void drop_modes(bdof_ctx* c) {
+    c->n_modes = 0;
+    c->m_stack.reset(); c->m_det64.reset(); c->m_zero.reset();
 }
 
 // ---- what a change voids ---------------------------------------------------------------------------------------------------
@@ -310,16 +327,17 @@ enum { V_TWIN64 = 1,        // c64_tf, c64_ks: the float64 twin handed over (bdo
        V_COPIES = 64,       // hs_copies, sep_copies: dithered copies of the slice step and of its separable factors (bdof_set_transfer_f64 follows)
        V_H64 = 128,         // have_h64: the float64 adjoint's tables (bdof_set_physics_f64 follows)
        V_PLANES = 256,      // planes: detector planes belong to the physics that go (drop_planes; bdof_set_detector_planes follows)
-       V_GPSI = 512 };      // gpsi_src: where the last bdof_loss_grad left G(psi_0)
+       V_GPSI = 512,        // gpsi_src: where the last bdof_loss_grad left G(psi_0)
+       V_MODES = 1024 };    // n_modes: probe modes were propagated with the physics that go (drop_modes; bdof_set_probe_modes follows)
 // ... and the one statement of which cause voids what (DESIGN §4 has the same table).  No setter or entry point assigns these
 // flags itself.  It records what the code did when it was written down, uneven places included (MEASUREMENTS.md lists them).
 enum Cause { CHANGED_CONFIGURATION, CHANGED_BINNING, CHANGED_PHYSICS, CHANGED_SLICE_STEP_F64, CHANGED_PROBE, CHANGED_CARRIER_FIELD,
              CHANGED_CARRIER_FIELD_F64, CHANGED_CONV_TAPS, CHANGED_CONV_CARRIER_FIELD, CHANGED_OBJECT, CHANGED_DETECTOR_PLANES,
-             CHANGED_MODULATION_K, CHANGED_MOD_OVERWRITTEN, CHANGED_MEAN_MODULATION, TAPE_OVERWRITTEN, PROBE_GRADIENT_GONE };
+             CHANGED_MODULATION_K, CHANGED_MOD_OVERWRITTEN, CHANGED_MEAN_MODULATION, TAPE_OVERWRITTEN, PROBE_GRADIENT_GONE, CHANGED_PROBE_MODES };
 static const struct { Cause cause; int voids; } VOIDS[] = {
     {CHANGED_CONFIGURATION, V_RESIDENT | V_HISTORY},             // bdof_configure (beside the fresh Workspace, which resets what it holds)
     {CHANGED_BINNING, V_MODULATION | V_RESIDENT | V_HISTORY | V_LAST_WAVE},                     // bdof_set_slice_binning
-    {CHANGED_PHYSICS, V_TWIN64 | V_PLANES | V_RESIDENT | V_H64 | V_COPIES | V_MODULATION},      // bdof_set_physics
+    {CHANGED_PHYSICS, V_TWIN64 | V_PLANES | V_MODES | V_RESIDENT | V_H64 | V_COPIES | V_MODULATION},      // bdof_set_physics
     {CHANGED_SLICE_STEP_F64, V_COPIES | V_RESIDENT},             // bdof_set_transfer_f64: the previous table's copies go before the new ones come
     {CHANGED_PROBE, V_TWIN64 | V_RESIDENT | V_MODULATION},       // bdof_set_probe: whether the mean modulation rides on the carrier depends on a0 (want_cbar)
     {CHANGED_CARRIER_FIELD, V_MODULATION},                       // bdof_set_probe_stack, set or cleared
@@ -333,6 +351,7 @@ static const struct { Cause cause; int voids; } VOIDS[] = {
     {CHANGED_MEAN_MODULATION, V_RESIDENT},                       // cbar came out different: the carrier scalars move
     {TAPE_OVERWRITTEN, V_HISTORY | V_LAST_WAVE},                 // a sweep has overwritten the tape
     {PROBE_GRADIENT_GONE, V_GPSI},                               // a sweep that leaves no G(psi_0), or its buffer went
+    {CHANGED_PROBE_MODES, V_MODES | V_HISTORY | V_LAST_WAVE | V_GPSI},      // bdof_set_probe_modes, set or removed (bdof_configure: the fresh Workspace)
 };
 static void changed(bdof_ctx* c, Cause cause) {
     int v = 0;
@@ -349,6 +368,7 @@ static void changed(bdof_ctx* c, Cause cause) {
     if (v & V_H64) c->have_h64 = false;
     if (v & V_PLANES) drop_planes(c);
     if (v & V_GPSI) c->gpsi_src = nullptr;
+    if (v & V_MODES) drop_modes(c);
 }
 // what makes it good again: the tape after bdof_forward(keep_tape), the table in c->mod, the resident engine's constants, a twin handed over
 static void tape_holds(bdof_ctx* c, bool history, bool last) { c->tape_valid = history; c->last_valid = last; }
@@ -1346,14 +1366,16 @@ template <auto K> static int max_lds_once(bdof_ctx* c, int bytes) {
 }
 
 // ---- LDS-resident engine ---------------------------------------------------------------------------
-template <int N, int T, int WPE, bool PSN, bool WGT> static int resident_launch_t(bdof_ctx* c, const ResArgs& a, int grid, int* waves) {
+template <int N, int T, int WPE, bool PSN, bool WGT, bool SEEDED = false> static int resident_launch_t(bdof_ctx* c, const ResArgs& a, int grid, int* waves) {
     *waves = T / 64;
     const size_t lds = sizeof(cf) * ((size_t)N * (N | 1) + 2 * N) + sizeof(long long) * 3 * N;
-    if (int r = max_lds_once<k_resident<N, T, WPE, PSN, WGT>>(c, (int)lds)) return r;
-    hipLaunchKernelGGL((k_resident<N, T, WPE, PSN, WGT>), dim3(grid), dim3(T), lds, c->stream, a);
+    if (int r = max_lds_once<k_resident<N, T, WPE, PSN, WGT, SEEDED>>(c, (int)lds)) return r;
+    hipLaunchKernelGGL((k_resident<N, T, WPE, PSN, WGT, SEEDED>), dim3(grid), dim3(T), lds, c->stream, a);
     return 0;
 }
-template <int N> static int resident_launch(bdof_ctx* c, const ResArgs& a, int grid, int* waves) {
+// seeded: the adjoint sweep alone, from the seeds in a.out_wave (k_resident's SEEDED instance; the data term is outside it)
+template <int N> static int resident_launch(bdof_ctx* c, const ResArgs& a, int grid, int* waves, bool seeded) {
+    if (seeded) return resident_launch_t<N, ResPlan<N>::T, ResPlan<N>::WPE, false, false, true>(c, a, grid, waves);
     return with_bool(a.meas && loss_is_poisson(c), [&](auto PSN) { return with_bool(a.meas && a.det.wgt, [&](auto WGT) {
         return resident_launch_t<N, ResPlan<N>::T, ResPlan<N>::WPE, PSN, WGT>(c, a, grid, waves);
     }); });
@@ -1370,6 +1392,41 @@ static bool use_resident(const bdof_ctx* c, int B) {
     return c->generic || c->res_always || B * 4 >= c->ncu;
 }
 
+// What every launch of the resident kernel on B wavefields shares: tables, object, shapes.  The caller adds the probe and its
+// carriers, the tape, the detector plane and the buffers the launch reads and writes.
+static ResArgs resident_args(const bdof_ctx* c, int B) {
+    const bool hdith = c->hs_copies > 0 && c->hsT_d;
+    ResArgs a{};
+    a.hsT = hdith ? c->hsT_d : c->hsT;
+    a.hD = hdith ? c->hs_copies : 0;
+    a.hdetT = c->hdetT;
+    a.tape_stride = (size_t)c->Bmax * c->NX * c->NY;
+    a.obj = c->obj;
+    a.twiddle = c->twR;
+    a.B = B;
+    a.S = c->S;
+    a.det_mode = c->det_mode;
+    a.tf_all = c->variant == BDOF_VARIANT_TF_ALL ? 1 : 0;
+    a.k = c->k;
+    return a;
+}
+// the launch of the plan of the ctx's size; grid: the workgroups of the launch, *waves: the waves of each
+static int resident_grid(const bdof_ctx* c, int B) { return B < c->npartial ? B : c->npartial; }
+static int resident_dispatch(bdof_ctx* c, const ResArgs& a, int* waves, bool seeded = false) {
+    const int grid = resident_grid(c, a.B);
+    switch (c->NX) {
+        case 32: return resident_launch<32>(c, a, grid, waves, seeded);
+        case 36: return resident_launch<36>(c, a, grid, waves, seeded);
+        case 48: return resident_launch<48>(c, a, grid, waves, seeded);
+        case 64: return resident_launch<64>(c, a, grid, waves, seeded);
+        case 72: return resident_launch<72>(c, a, grid, waves, seeded);
+        case 80: return resident_launch<80>(c, a, grid, waves, seeded);
+        case 96: return resident_launch<96>(c, a, grid, waves, seeded);
+        case 128: return resident_launch<128>(c, a, grid, waves, seeded);
+        default: return fail(c, BDOF_ERR_SIZE, "no resident plan for this size");
+    }
+}
+
 static int resident_run(bdof_ctx* c, int B, const float* meas, void* out_wave, bool do_grad) {
     if (c->res_dirty) {
         std::vector<cf> car(2 * (size_t)c->S);
@@ -1380,47 +1437,161 @@ static int resident_run(bdof_ctx* c, int B, const float* meas, void* out_wave, b
     }
     ProfScope ps(c, BDOF_K_ROW_FWD, c->stream);
     const bool grad = do_grad && meas;
-    const bool hdith = c->hs_copies > 0 && c->hsT_d;
-    ResArgs a{};
+    ResArgs a = resident_args(c, B);
     a.probe = c->probe;
-    a.hsT = hdith ? c->hsT_d : c->hsT;
-    a.hD = hdith ? c->hs_copies : 0;
-    a.hdetT = c->hdetT;
     a.tape = grad ? c->tape : nullptr;
-    a.tape_stride = (size_t)c->Bmax * c->NX * c->NY;
     a.grot = c->grot;
     a.gpsi0 = grad ? c->gpsi0 : nullptr;
-    a.obj = c->obj;
     a.carrier = c->res_carrier;
     a.pstack = c->pstack;
     a.meas = meas;
     a.out_wave = (cf*)out_wave;
     a.partial = c->partial;
-    a.twiddle = c->twR;
-    a.B = B;
-    a.S = c->S;
-    a.det_mode = c->det_mode;
-    a.tf_all = c->variant == BDOF_VARIANT_TF_ALL ? 1 : 0;
     a.do_grad = grad ? 1 : 0;
-    a.k = c->k;
     a.det = det_plane(c, whole(c, B), B, c->pdet);
-    const int grid = B < c->npartial ? B : c->npartial;
-    int r = 0, waves = 1;
-    switch (c->NX) {
-        case 32: r = resident_launch<32>(c, a, grid, &waves); break;
-        case 36: r = resident_launch<36>(c, a, grid, &waves); break;
-        case 48: r = resident_launch<48>(c, a, grid, &waves); break;
-        case 64: r = resident_launch<64>(c, a, grid, &waves); break;
-        case 72: r = resident_launch<72>(c, a, grid, &waves); break;
-        case 80: r = resident_launch<80>(c, a, grid, &waves); break;
-        case 96: r = resident_launch<96>(c, a, grid, &waves); break;
-        case 128: r = resident_launch<128>(c, a, grid, &waves); break;
-        default: return fail(c, BDOF_ERR_SIZE, "no resident plan for this size");
-    }
-    if (r) return r;
+    const int grid = resident_grid(c, B);
+    int waves = 1;
+    if (int r = resident_dispatch(c, a, &waves)) return r;
     if (meas)
         hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, c->stream, c->partial, grid * waves, 1.0 / ((double)B * c->NX * c->NY),
                            c->loss_dev);
+    return launched(c);
+}
+
+// ---- probe modes (bdof_set_probe_modes; bdof_modes.h) -----------------------------------------------------------------------
+// Three phases per call, B windows and M modes, wavefield (m, j) at index m B + j of bufA, bufB, the tape, gpsi0 and — until the
+// last launch — of the gradient rows: (1) the forward sweep of every wavefield, which leaves the scattered part of its detector
+// wave; (2) k_modes_couple: the data term on sum_m |d_m|^2 and the M seeds; (3) the adjoint sweep of every wavefield into its own
+// rows [m B + j][S] of grot, then k_modes_sum_rows: [B][S][NX][NY] with the modes summed, what bdof_grot promises.  The rows fit:
+// grot holds Bmax wavefields and B M <= Bmax.  The object view and the offsets are per window, so every kernel that reads them
+// is launched per mode on its sub-batch of B; the transforms of the generic engine run batched over all B M fields.
+static bool modes_resident(const bdof_ctx* c) { return c->resident; }      // else the generic engine (MODE_STREAMING_ONLY is refused)
+static size_t modes_sub(const bdof_ctx* c, int B, int m) { return (size_t)m * B * c->NX * c->NY; }      // mode m's sub-batch in a field buffer
+
+// phase 1, resident: one launch per mode of the forward instance, the tape handed in when a gradient follows; a detector plane
+// without a carrier, so bufA receives the scattered parts alone, in the order of meas
+static int modes_resident_forward(bdof_ctx* c, int B, bool tape) {
+    ProfScope ps(c, BDOF_K_ROW_FWD, c->stream);
+    for (int m = 0; m < c->n_modes; ++m) {
+        ResArgs a = resident_args(c, B);
+        a.probe = c->m_zero;
+        a.carrier = c->m_zero;
+        a.pstack = c->m_stack + (size_t)m * c->S * c->NX * c->NY;
+        a.tape = tape ? c->tape + modes_sub(c, B, m) : nullptr;
+        a.out_wave = c->bufA + modes_sub(c, B, m);
+        int waves;
+        if (int r = resident_dispatch(c, a, &waves)) return r;
+    }
+    return 0;
+}
+// phase 3, resident: one launch per mode of the seeded instance, seeds in bufB
+static int modes_resident_adjoint(bdof_ctx* c, int B) {
+    ProfScope ps(c, BDOF_K_ROW_BWD, c->stream);
+    for (int m = 0; m < c->n_modes; ++m) {
+        ResArgs a = resident_args(c, B);
+        a.carrier = c->m_zero;
+        a.pstack = c->m_stack + (size_t)m * c->S * c->NX * c->NY;
+        a.tape = c->tape + modes_sub(c, B, m);
+        a.out_wave = c->bufB + modes_sub(c, B, m);
+        a.grot = c->grot + modes_sub(c, B, m) * c->S;
+        a.gpsi0 = c->gpsi0 ? c->gpsi0 + modes_sub(c, B, m) : nullptr;
+        a.do_grad = 1;
+        int waves;
+        if (int r = resident_dispatch(c, a, &waves, true)) return r;
+    }
+    return 0;
+}
+// phase 1, generic: the forward sweep of generic_forward_sweep with the modulation per mode; bufA ends as the scattered parts
+// of the detector waves, [x][y] (far field [kx][ky])
+static int modes_generic_forward(bdof_ctx* c, int B, bool tape) {
+    const int BM = B * c->n_modes, nz = n_steps(c);
+    const size_t fld = (size_t)c->Bmax * c->NX * c->NY, pl = (size_t)c->NX * c->NY, n = (size_t)B * pl;
+    const cf zero = make_float2(0.f, 0.f);
+    rocfft_plan pf, pi;
+    int r = field_plans(c, c->NX, c->NY, BM, false, &pf, &pi);
+    if (r) return r;
+    for (int z = 0; z < nz; ++z) {
+        for (int m = 0; m < c->n_modes; ++m) {
+            ProfScope ps(c, BDOF_K_ROW_FWD, c->stream);
+            GModArgs ma{c->bufA + modes_sub(c, B, m), z == 0 ? (const cf*)c->m_zero : nullptr, tape ? c->tape + (size_t)z * fld + modes_sub(c, B, m) : nullptr,
+                        c->obj, B, c->NX, c->NY, z, zero, c->m_stack + ((size_t)m * nz + z) * pl, zero};
+            hipLaunchKernelGGL(k_g_modulate<false>, dim3(g_elem_grid(c, n)), dim3(256), 0, c->stream, ma);
+        }
+        if ((z < nz - 1 || step_after_last(c)) && (r = generic_prop(c, BM, c->bufA, hs_slice(c, z), 0))) return r;
+    }
+    if (c->det_mode == BDOF_DET_NEAR) return generic_prop(c, BM, c->bufA, c->hdet, 0);
+    if (c->det_mode == BDOF_DET_FAR) {
+        void* buf[1] = {c->bufA};
+        RFC(c, rocfft_execute(pf, buf, nullptr, c->fft.info));
+    }
+    return 0;
+}
+// phase 3, generic: the adjoint loop of generic_loss_grad on the seeds in bufA, k_g_bwd per mode; G(psi_0) stays in bufA
+static int modes_generic_adjoint(bdof_ctx* c, int B) {
+    const int BM = B * c->n_modes, nz = n_steps(c);
+    const size_t fld = (size_t)c->Bmax * c->NX * c->NY, n = (size_t)B * c->NX * c->NY;
+    rocfft_plan pf, pi;
+    int r = field_plans(c, c->NX, c->NY, BM, false, &pf, &pi);
+    if (r) return r;
+    void* buf[1] = {c->bufA};
+    if (c->det_mode == BDOF_DET_NEAR) { if ((r = generic_prop(c, BM, c->bufA, c->hdet, 1))) return r; }
+    else if (c->det_mode == BDOF_DET_FAR) RFC(c, rocfft_execute(pi, buf, nullptr, c->fft.info));            // F^H = unnormalised inverse
+    const AdjCarrier none{nullptr, nullptr, make_double2(1.0, 0.0), make_float2(0.f, 0.f)};
+    for (int z = nz - 1; z >= 0; --z) {
+        if ((z < nz - 1 || step_after_last(c)) && (r = generic_prop(c, BM, c->bufA, hs_slice(c, z), 1))) return r;
+        for (int m = 0; m < c->n_modes; ++m) {
+            ProfScope ps(c, BDOF_K_ROW_BWD, c->stream);
+            GBwdArgs ba{c->bufA + modes_sub(c, B, m), c->tape + (size_t)z * fld + modes_sub(c, B, m), c->grot + modes_sub(c, B, m) * c->S, c->obj,
+                        B, c->NX, c->NY, z, c->k, make_float2(0.f, 0.f), 1, none};
+            hipLaunchKernelGGL(k_g_bwd<false>, dim3(g_elem_grid(c, n)), dim3(256), 0, c->stream, ba);
+        }
+    }
+    return 0;
+}
+// phase 2: meas == nullptr writes the detector waves alone (bdof_forward)
+static void modes_couple(bdof_ctx* c, int B, const float* meas, void* out_wave) {
+    ProfScope ps(c, BDOF_K_LOSS, c->stream);
+    const size_t n = (size_t)B * c->NX * c->NY;
+    const bool res = modes_resident(c);
+    ModesArgs a{};
+    a.e = c->bufA;
+    a.seed = res ? c->bufB : c->bufA;
+    a.out_wave = (cf*)out_wave;
+    a.meas = meas;
+    a.pdet64 = c->m_det64;
+    a.wgt = c->wgt;
+    a.partial = c->partial;
+    a.M = c->n_modes; a.B = B; a.NX = c->NX; a.NY = c->NY;
+    a.far = c->det_mode == BDOF_DET_FAR;
+    a.e_meas_order = res ? 1 : 0;
+    a.seed_scale = 2.0 / ((double)B * c->NX * c->NY);
+    a.mu = c->loss_mu;
+    const int grid = g_elem_grid(c, n);
+    with_bool(meas && loss_is_poisson(c), [&](auto PSN) { with_bool(meas && c->wgt, [&](auto WGT) {
+        hipLaunchKernelGGL((k_modes_couple<PSN, WGT>), dim3(grid), dim3(256), 0, c->stream, a);
+    }); });
+    if (meas) hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, c->stream, c->partial, grid, 1.0 / ((double)B * c->NX * c->NY), c->loss_dev);
+}
+static int check_modes_batch(bdof_ctx* c, int B) {
+    return (long long)B * c->n_modes > c->Bmax ? fail(c, BDOF_ERR_ARG, "probe modes: windows times modes must not exceed Bmax (B M <= Bmax)") : 0;
+}
+static int modes_forward(bdof_ctx* c, int B, void* out_wave) {
+    int r = modes_resident(c) ? modes_resident_forward(c, B, false) : modes_generic_forward(c, B, false);
+    if (r) return r;
+    if (out_wave) modes_couple(c, B, nullptr, out_wave);
+    return launched(c);
+}
+static int modes_loss_grad(bdof_ctx* c, int B, const float* meas, void* out_wave) {
+    const bool res = modes_resident(c);
+    int r = res ? modes_resident_forward(c, B, true) : modes_generic_forward(c, B, true);
+    if (r) return r;
+    modes_couple(c, B, meas, out_wave);
+    if ((r = res ? modes_resident_adjoint(c, B) : modes_generic_adjoint(c, B))) return r;
+    if (c->n_modes > 1) {
+        const size_t rows = (size_t)B * c->S * c->NX * c->NY;
+        hipLaunchKernelGGL(k_modes_sum_rows, dim3(g_elem_grid(c, rows)), dim3(256), 0, c->stream, c->grot, c->n_modes, rows);
+    }
+    c->gpsi_src = res ? (const cf*)c->gpsi0 : (const cf*)c->bufA;
     return launched(c);
 }
 
@@ -1428,7 +1599,7 @@ static int check_ready(bdof_ctx* c, int B) {
     if (!c) return BDOF_ERR_ARG;
     if (int r = need_configured(c)) return r;
     if (!c->have_physics) return fail(c, BDOF_ERR_STATE, "bdof_set_physics has not been called");
-    if (!c->have_probe) return fail(c, BDOF_ERR_STATE, "bdof_set_probe has not been called");
+    if (!c->have_probe && !c->n_modes) return fail(c, BDOF_ERR_STATE, "bdof_set_probe has not been called");
     if (!c->obj_src && !c->obj_bound_mod) return fail(c, BDOF_ERR_STATE, "bdof_set_object has not been called");
     return check_batch(c, B);
 }
@@ -1830,7 +2001,7 @@ int bdof_set_detector_planes(bdof_ctx* c, int D, const float* hs_det, const doub
     if (!hdet00) return fail(c, BDOF_ERR_ARG, "bdof_set_detector_planes: hdet00 required with the tables");
     if (!c->have_physics) return fail(c, BDOF_ERR_STATE, "bdof_set_detector_planes comes after bdof_set_physics");
     if (int r = refuse_modes(c, "bdof_set_detector_planes", "detector planes",
-                             {&MODE_NOT_NEAR, &MODE_RECOMPUTE, &MODE_ADJOINT64, &MODE_CONV, &MODE_CARRIER_FIELD, &MODE_RANGE_CARRIER})) return r;
+                             {&MODE_NOT_NEAR, &MODE_RECOMPUTE, &MODE_ADJOINT64, &MODE_CONV, &MODE_CARRIER_FIELD, &MODE_RANGE_CARRIER, &MODE_PROBE_MODES})) return r;
     changed(c, CHANGED_DETECTOR_PLANES);
     const size_t n = (size_t)c->NX * c->NY, fields = (size_t)c->Bmax * D * n;
     // the combined tables of tf_all, formed as bdof_set_physics forms its one: from the float32 slice step the ctx holds
@@ -1872,7 +2043,7 @@ int bdof_set_probe_stack(bdof_ctx* c, const float* stack, const float* det) {
     changed(c, CHANGED_CARRIER_FIELD);
     if (!stack && !det) return 0;
     if (!stack || !det) return fail(c, BDOF_ERR_ARG, "bdof_set_probe_stack: both arrays or neither");
-    if ((r = admit(c, "a carrier field (bdof_set_probe_stack)", CARRIES_BINNING | NO_DATA_TERM))) return r;
+    if ((r = admit(c, "a carrier field (bdof_set_probe_stack)", CARRIES_BINNING | CARRIES_MODES | NO_DATA_TERM))) return r;
     const size_t n = (size_t)c->NX * c->NY;
     if ((r = upload(c, c->pstack, stack, n * steps(c).stack_planes(), FRESH))) return r;       // one plane per propagation step
     if ((r = upload(c, c->pdet, det, n, FRESH))) return r;
@@ -1884,48 +2055,91 @@ int bdof_set_probe_stack(bdof_ctx* c, const float* stack, const float* det) {
 // of one field with rocFFT's double-precision plans (np_funcs.py:42 without an object), each plane rounded once into the
 // float32 stack.  A probe that changes every Adam step (probe_type='optimizable') then costs ~4 small launches per slice
 // instead of 2 S host FFTs and a 1-GiB upload.
-int bdof_set_probe_field(bdof_ctx* c, const double* probe, const double* hT, const double* hdetT) {
-    if (!c || !probe || !hT) return BDOF_ERR_ARG;
-    if (!c->have_physics) return fail(c, BDOF_ERR_STATE, "bdof_set_physics has not been called");
-    if (c->det_mode == BDOF_DET_NEAR && !hdetT) return fail(c, BDOF_ERR_ARG, "hdetT required for BDOF_DET_NEAR");
-    int r = admit(c, "a carrier field (bdof_set_probe_field)", CARRIES_BINNING | NO_DATA_TERM);
-    if (r || (r = enter_setter(c, true))) return r;
+// The carrier field of ONE probe, queued on the ctx stream: dp (device [NX][NY] complex128, overwritten) stepped through free
+// space with the tables dh / dhd ([kx][ky], without the transforms' 1 / n; dhd: the detector step, BDOF_DET_NEAR only); every
+// plane rounded once into `stack`, the detector plane into det / detT (transposed) and unrounded into det64 / detT64 — each of
+// the four where the caller has a reader for it (null: not written).
+struct CarrierField { cf *stack, *det, *detT; double2 *det64, *detT64; };
+static int build_carrier_field(bdof_ctx* c, double2* dp, const double2* dh, const double2* dhd, const CarrierField& out) {
     const size_t n = (size_t)c->NX * c->NY;
     rocfft_plan pf, pi;
+    int r;
     if ((r = field_plans(c, c->NX, c->NY, 1, true, &pf, &pi))) return r;       // fields are [x][y]
-    DevBuf<double2> dp, dh, dhd;
-    if ((r = upload(c, dp, probe, n, FRESH)) || (r = upload(c, dh, hT, n, FRESH)) || (hdetT && (r = upload(c, dhd, hdetT, n, FRESH)))) return r;
-    c->pstack.reset(); c->pdet.reset(); c->pdetT.reset();
-    c->pdet64.reset(); c->pdetT64.reset();
-    const int nz = n_steps(c);                                   // one plane per propagation step (hT: the step's own table)
-    HIPC(c, c->pstack.alloc(n * (size_t)nz));
-    HIPC(c, c->pdet.alloc(n));
-    HIPC(c, c->pdetT.alloc(n));
-    HIPC(c, c->pdet64.alloc(n));
-    HIPC(c, c->pdetT64.alloc(n));
+    const int nz = n_steps(c);                                   // one plane per propagation step (dh: the step's own table)
     const int grid = g_elem_grid(c, n);
     void* buf[1] = {dp};
     auto step = [&](const double2* h) {      // the caller's tables come without the transforms' 1 / n
         return free_step(c, c->fft, c->stream, dp, 1, c->NX, c->NY, h, H_KXKY, 0, true, -1, 1.0 / (double)n);
     };
     for (int z = 0; z < nz; ++z) {
-        hipLaunchKernelGGL(k_d_to_f, dim3(grid), dim3(256), 0, c->stream, dp, c->pstack + (size_t)z * n, c->NX, c->NY, 0);
+        hipLaunchKernelGGL(k_d_to_f, dim3(grid), dim3(256), 0, c->stream, dp, out.stack + (size_t)z * n, c->NX, c->NY, 0);
         if ((z < nz - 1 || step_after_last(c)) && (r = step(dh))) return r;
     }
     if (c->det_mode == BDOF_DET_FAR) RFC(c, rocfft_execute(pf, buf, nullptr, c->fft.info));
     else if (c->det_mode == BDOF_DET_NEAR && (r = step(dhd))) return r;
-    hipLaunchKernelGGL(k_d_to_f, dim3(grid), dim3(256), 0, c->stream, dp, c->pdet, c->NX, c->NY, 0);
-    hipLaunchKernelGGL(k_d_to_f, dim3(grid), dim3(256), 0, c->stream, dp, c->pdetT, c->NX, c->NY, 1);
+    if (out.det) hipLaunchKernelGGL(k_d_to_f, dim3(grid), dim3(256), 0, c->stream, dp, out.det, c->NX, c->NY, 0);
+    if (out.detT) hipLaunchKernelGGL(k_d_to_f, dim3(grid), dim3(256), 0, c->stream, dp, out.detT, c->NX, c->NY, 1);
     // ... and unrounded: the detector kernels add the scattered wave to these and take |d| - m in float64 (seed_f64)
-    hipLaunchKernelGGL(k_d_copy, dim3(grid), dim3(256), 0, c->stream, dp, c->pdet64, c->NX, c->NY, 0);
-    hipLaunchKernelGGL(k_d_copy, dim3(grid), dim3(256), 0, c->stream, dp, c->pdetT64, c->NX, c->NY, 1);
+    if (out.det64) hipLaunchKernelGGL(k_d_copy, dim3(grid), dim3(256), 0, c->stream, dp, out.det64, c->NX, c->NY, 0);
+    if (out.detT64) hipLaunchKernelGGL(k_d_copy, dim3(grid), dim3(256), 0, c->stream, dp, out.detT64, c->NX, c->NY, 1);
     HIPC(c, hipGetLastError());
+    return 0;
+}
+
+int bdof_set_probe_field(bdof_ctx* c, const double* probe, const double* hT, const double* hdetT) {
+    if (!c || !probe || !hT) return BDOF_ERR_ARG;
+    if (!c->have_physics) return fail(c, BDOF_ERR_STATE, "bdof_set_physics has not been called");
+    if (c->det_mode == BDOF_DET_NEAR && !hdetT) return fail(c, BDOF_ERR_ARG, "hdetT required for BDOF_DET_NEAR");
+    int r = admit(c, "a carrier field (bdof_set_probe_field)", CARRIES_BINNING | CARRIES_MODES | NO_DATA_TERM);
+    if (r || (r = enter_setter(c, true))) return r;
+    const size_t n = (size_t)c->NX * c->NY;
+    DevBuf<double2> dp, dh, dhd;
+    if ((r = upload(c, dp, probe, n, FRESH)) || (r = upload(c, dh, hT, n, FRESH)) || (hdetT && (r = upload(c, dhd, hdetT, n, FRESH)))) return r;
+    c->pstack.reset(); c->pdet.reset(); c->pdetT.reset();
+    c->pdet64.reset(); c->pdetT64.reset();
+    HIPC(c, c->pstack.alloc(n * (size_t)n_steps(c)));
+    HIPC(c, c->pdet.alloc(n));
+    HIPC(c, c->pdetT.alloc(n));
+    HIPC(c, c->pdet64.alloc(n));
+    HIPC(c, c->pdetT64.alloc(n));
+    if ((r = build_carrier_field(c, dp, dh, dhd, CarrierField{c->pstack, c->pdet, c->pdetT, c->pdet64, c->pdetT64}))) return r;
     HIPC(c, hipStreamSynchronize(c->stream));         // the temporaries go when this returns: nothing queued may still read them
     // the wave is carried as p_z + eps_z with eps_0 = 0: no probe of its own, no scalar carrier
     HIPC(c, hipMemsetAsync(c->probe, 0, sizeof(cf) * n, c->stream));
     c->a0 = 0.0;
     changed(c, CHANGED_CARRIER_FIELD_F64);
     c->have_probe = true;
+    return 0;
+}
+
+// Probe modes: M carrier fields, each built as bdof_set_probe_field builds its one.  They live beside the probe of
+// bdof_set_probe* (which M = 0 goes back to) and take its place in bdof_forward / bdof_loss_grad while they are in force.
+int bdof_set_probe_modes(bdof_ctx* c, int M, const double* probes, const double* hT, const double* hdetT) {
+    int r = enter_setter(c, true);
+    if (r) return r;
+    if (M == 0 || !probes) { changed(c, CHANGED_PROBE_MODES); return 0; }
+    if (M < 1 || M > BDOF_MAX_MODES) return fail(c, BDOF_ERR_ARG, "bdof_set_probe_modes: the number of probe modes must be in [1, BDOF_MAX_MODES]");
+    if (!hT) return fail(c, BDOF_ERR_ARG, "bdof_set_probe_modes: hT required with the probe modes");
+    if (!c->have_physics) return fail(c, BDOF_ERR_STATE, "bdof_set_probe_modes (probe modes) comes after bdof_set_physics");
+    if (c->det_mode == BDOF_DET_NEAR && !hdetT) return fail(c, BDOF_ERR_ARG, "bdof_set_probe_modes: hdetT required for BDOF_DET_NEAR");
+    if ((r = admit(c, "probe modes (bdof_set_probe_modes)", CARRIES_MODES | NO_DATA_TERM))) return r;
+    if ((r = refuse_modes(c, "bdof_set_probe_modes", "probe modes",
+                          {&MODE_STREAMING_ONLY, &MODE_RECOMPUTE, &MODE_ADJOINT64, &MODE_NO_GROT, &MODE_CONV, &MODE_RANGE_CARRIER}))) return r;
+    const size_t n = (size_t)c->NX * c->NY, nz = (size_t)n_steps(c);
+    DevBuf<double2> dp, dh, dhd;
+    if ((r = upload(c, dp, probes, n * M, FRESH)) || (r = upload(c, dh, hT, n, FRESH)) || (hdetT && (r = upload(c, dhd, hdetT, n, FRESH)))) return r;
+    changed(c, CHANGED_PROBE_MODES);
+    HIPC(c, c->m_stack.alloc(n * nz * M));
+    HIPC(c, c->m_det64.alloc(n * M));
+    const size_t nzero = std::max(n, (size_t)2 * c->S);
+    HIPC(c, c->m_zero.alloc(nzero));
+    HIPC(c, hipMemsetAsync(c->m_zero, 0, sizeof(cf) * nzero, c->stream));
+    for (int m = 0; m < M; ++m) {
+        const CarrierField out{c->m_stack + m * nz * n, nullptr, nullptr, c->m_det64 + m * n, nullptr};
+        if ((r = build_carrier_field(c, dp + m * n, dh, dhd, out))) { drop_modes(c); return r; }
+    }
+    HIPC(c, hipStreamSynchronize(c->stream));         // the temporaries go when this returns: nothing queued may still read them
+    c->n_modes = M;
     return 0;
 }
 
@@ -1983,7 +2197,13 @@ int bdof_forward(bdof_ctx* c, int B, const int* angle_of_b, const int* xoff, con
     if ((r = check_ready(c, B)) || (r = need_angles(c, angle_of_b))) return r;
     if (keep_tape && !c->with_grad) return fail(c, BDOF_ERR_STATE, "keep_tape needs bdof_configure(with_grad=1)");
     if (keep_tape && c->recompute) return fail(c, BDOF_ERR_STATE, "the per-slice history is not kept in tape-free (recompute) mode");
+    if (c->n_modes && keep_tape) return fail(c, BDOF_ERR_STATE, "the per-slice history is not kept under probe modes");
+    if (c->n_modes && (r = check_modes_batch(c, B))) return r;
     if ((r = begin_batch(c, angle_of_b, xoff, yoff, c->k_fft))) return r;
+    if (c->n_modes) {
+        changed(c, TAPE_OVERWRITTEN);
+        return modes_forward(c, B, out_wave);
+    }
     if (use_resident(c, B) && !keep_tape) {
         if ((r = resident_run(c, B, nullptr, out_wave, false))) return r;
         changed(c, TAPE_OVERWRITTEN);
@@ -2147,7 +2367,7 @@ int bdof_adjoint_range(bdof_ctx* c, int B, const int* angle_of_b, const int* xof
 int bdof_field_loss_seed(bdof_ctx* c, void* field, const float* meas, int FX, int FY) {
     if (!c || !field || !meas || FX < 1 || FY < 1) return BDOF_ERR_ARG;
     if (!c->partial) return fail(c, BDOF_ERR_STATE, "bdof_configure has not been called");
-    if (int r = admit(c, "bdof_field_loss_seed", CARRIES_BINNING | CARRIES_PLANES)) return r;      // (a whole field: no sweep, no detector step)
+    if (int r = admit(c, "bdof_field_loss_seed", CARRIES_BINNING | CARRIES_PLANES | CARRIES_MODES)) return r;      // (a whole field: no sweep, no detector step)
     HIPC(c, hipSetDevice(c->device));
     const size_t n = (size_t)FX * FY;
     const int egrid = g_elem_grid(c, n);
@@ -2576,14 +2796,19 @@ int bdof_loss_grad(bdof_ctx* c, int B, const int* angle_of_b, const int* xoff, c
     int r = check_ready(c, B);
     if (r) return r;
     if (!meas) return BDOF_ERR_ARG;
-    if (c->meas_dev && (c->det_mode == BDOF_DET_FAR || c->pstack))
-        return fail(c, BDOF_ERR_STATE, "bdof_set_meas_mode(1) needs a real-space detector and a scalar carrier");
+    if (c->meas_dev && (c->det_mode == BDOF_DET_FAR || c->pstack || c->n_modes))
+        return fail(c, BDOF_ERR_STATE, "bdof_set_meas_mode(1) needs a real-space detector and a scalar carrier (not a carrier field, not probe modes)");
     if (!c->with_grad || !c->grot) return fail(c, BDOF_ERR_STATE, "bdof_loss_grad needs bdof_configure(with_grad=1) with the gradient workspace (not flag 32)");
     if ((r = need_angles(c, angle_of_b))) return r;
+    if (c->n_modes && (r = check_modes_batch(c, B))) return r;
     if ((r = begin_batch(c, angle_of_b, xoff, yoff, c->k_fft))) return r;
     c->gpsi_src = c->gpsi0;
     c->gpsi_B = B;
     c->fused_last = c->adj_fused_last = 0;
+    if (c->n_modes) {
+        changed(c, TAPE_OVERWRITTEN);
+        return modes_loss_grad(c, B, meas, out_wave);
+    }
     if (use_resident(c, B)) {
         if ((r = resident_run(c, B, meas, out_wave, true))) return r;
         changed(c, TAPE_OVERWRITTEN);
@@ -3007,10 +3232,25 @@ int bdof_probe_grad(bdof_ctx* c, void* out, int accumulate) {
     if (!c || !out) return BDOF_ERR_ARG;
     if (!c->gpsi0) return fail(c, BDOF_ERR_STATE, "bdof_enable_probe_grad(1) has not been called");
     if (!c->gpsi_src) return fail(c, BDOF_ERR_STATE, "no gradient sweep since the probe gradient was enabled (bdof_loss_grad first)");
+    if (int r = admit(c, "bdof_probe_grad", CARRIES_BINNING | CARRIES_PLANES | NO_DATA_TERM)) return r;      // (bdof_probe_grad_modes)
     HIPC(c, hipSetDevice(c->device));
     const size_t n = (size_t)c->NX * c->NY;
     hipLaunchKernelGGL(k_sum_fields, dim3((unsigned)std::min<size_t>((n + 255) / 256, (size_t)c->ncu * 8)), dim3(256), 0, c->stream, c->gpsi_src,
                        (cf*)out, c->gpsi_B, n, accumulate);
+    return launched(c);
+}
+
+// the gradient w.r.t. mode m: its sub-batch of G(psi_0) summed over the windows, k_sum_fields per mode
+int bdof_probe_grad_modes(bdof_ctx* c, void* out, int accumulate) {
+    if (!c || !out) return BDOF_ERR_ARG;
+    if (!c->n_modes) return fail(c, BDOF_ERR_STATE, "bdof_probe_grad_modes: no probe modes are set (bdof_set_probe_modes)");
+    if (!c->gpsi0) return fail(c, BDOF_ERR_STATE, "bdof_enable_probe_grad(1) has not been called");
+    if (!c->gpsi_src) return fail(c, BDOF_ERR_STATE, "no gradient sweep since the probe gradient was enabled (bdof_loss_grad first)");
+    HIPC(c, hipSetDevice(c->device));
+    const size_t n = (size_t)c->NX * c->NY;
+    for (int m = 0; m < c->n_modes; ++m)
+        hipLaunchKernelGGL(k_sum_fields, dim3((unsigned)std::min<size_t>((n + 255) / 256, (size_t)c->ncu * 8)), dim3(256), 0, c->stream,
+                           c->gpsi_src + modes_sub(c, c->gpsi_B, m), (cf*)out + (size_t)m * n, c->gpsi_B, n, accumulate);
     return launched(c);
 }
 
@@ -3297,7 +3537,7 @@ static int rotate_rows(bdof_ctx* c, const void* vol, int NXv, int NZv, int NYv, 
 // table as factors c - 1 (no rotated (delta, beta) copy, no second pass over B volumes) and bound as the batch's objects.
 template <class K>
 static int set_object_rotated(bdof_ctx* c, const void* vol, int NXv, int NZv, int NYv, const double* prm, int B, int conv) {
-    if (int r = admit(c, K::set_object, CARRIES_PLANES | NO_DATA_TERM)) return r;
+    if (int r = admit(c, K::set_object, CARRIES_PLANES | CARRIES_MODES | NO_DATA_TERM)) return r;
     if (!c || !vol || !prm || B < 1) return BDOF_ERR_ARG;
     int r = enter_setter(c, false);
     if (r) return r;

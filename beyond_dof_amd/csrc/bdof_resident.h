@@ -529,7 +529,11 @@ template <int N, int T> struct ResPoint {
 // WPE = waves per SIMD the register allocation must leave room for (two workgroups per CU where the LDS image allows)
 // PSN: the Poisson data term (seed_weight, bdof_kernels.h) — a template parameter, so that the least-squares kernels are
 // the instructions they were.  WGT: detector weights (DetPlane::wgt), carried the same way.
-template <int N, int T, int WPE, bool PSN = false, bool WGT = false>
+// SEEDED: the adjoint sweep alone, from seeds formed outside the kernel (probe modes, bdof_modes.h): a.out_wave holds G(d) of
+// every wavefield, [B][N][N] in the image's own [x][y] order (far field [kx][ky]), and is READ; the tape is the one an earlier
+// launch of the forward instance left.  No forward sweep, no loss block, no sums: probe, meas, partial and det are not read,
+// and the data term's parameters with them — one such instance per size.
+template <int N, int T, int WPE, bool PSN = false, bool WGT = false, bool SEEDED = false>
 __global__ __launch_bounds__(T, WPE) void k_resident(ResArgs a) {
     typedef ResPipe<N, T> Pipe;
     typedef ResPoint<N, T> Point;
@@ -552,109 +556,114 @@ __global__ __launch_bounds__(T, WPE) void k_resident(ResArgs a) {
         res_sync();
         for (int e = tid; e < N * N; e += T) {
             const int x = res_div<N>(e), y = e - x * N;
-            f[x * P + y] = a.probe[e];
+            if constexpr (SEEDED) f[x * P + y] = a.out_wave[b * fsz + e];
+            else f[x * P + y] = a.probe[e];
         }
-        if (tid < N) {
-            rowbuf[tid] = Pipe::row_of(a, b, 0, tid);
-            rowbuf[N + tid] = Pipe::row_of(a, b, 1, tid);
+        if constexpr (!SEEDED) {
+            if (tid < N) {
+                rowbuf[tid] = Pipe::row_of(a, b, 0, tid);
+                rowbuf[N + tid] = Pipe::row_of(a, b, 1, tid);
+            }
         }
         res_sync();
 
-        // ---- forward sweep --------------------------------------------------------------------
         float2 m[EPT];
-        Pipe::load_factors(a, rowbuf, y0, tid, m);
-        if constexpr (FUSE) {
-            // slice 0 is modulated on its own; every later slice inside the propagation step that produces it (EpiMod)
-            Point::modulate(f, tape0, a.carrier[0], a.carrier[a.S], a.pstack, m, tid);
-            for (int z = 0; z < a.S; ++z) {
-                const long long r2 = Pipe::row_of(a, b, z + 2, tid);
-                if (z + 1 < a.S) {
-                    EpiMod<N, T> em;
-                    em.a = &a;
-                    em.rows = rowbuf + ((z + 1) % 3) * N;
-                    em.tape = tape0 ? tape0 + (size_t)(z + 1) * a.tape_stride : nullptr;
-                    em.car = a.carrier[z + 1];
-                    em.csh = a.carrier[a.S + z + 1];
-                    em.pz = a.pstack ? a.pstack + (size_t)(z + 1) * fsz : nullptr;
-                    em.y0 = y0;
-                    res_prop<N, T, false>(f, hs_of(z), tw, tid, em);
-                } else if (a.tf_all && !far) {
-                    res_prop<N, T, false>(f, hs_of(z), tw, tid);
-                }
-                if (tid < N) rowbuf[((z + 2) % 3) * N + tid] = r2;      // read two propagation steps from now
-            }
-        } else {
-            EpiNone none;
-            for (int z = 0; z < a.S; ++z) {
-                const long long r2 = Pipe::row_of(a, b, z + 2, tid);
-                Point::modulate(f, tape0 ? tape0 + (size_t)z * a.tape_stride : nullptr, a.carrier[z], a.carrier[a.S + z],
-                                a.pstack ? a.pstack + (size_t)z * fsz : nullptr, m, tid);
-                if (tid < N) rowbuf[((z + 2) % 3) * N + tid] = r2;
-                if (z + 1 < a.S) {
-                    // the next slice's factors: in flight during the last two passes of the step
-                    res_prop<N, T, false>(f, hs_of(z), tw, tid, none, [&]() { Pipe::load_factors(a, rowbuf + ((z + 1) % 3) * N, y0, tid, m); });
-                } else if (a.tf_all && !far) {
-                    res_prop<N, T, false>(f, hs_of(z), tw, tid);
-                }
-            }
-        }
-        if (a.det_mode == BDOF_DET_NEAR) res_prop<N, T, false>(f, a.hdetT, tw, tid);
-        else if (far) res_fft2<N, T, -1>(f, tw, tid);
-
-        // ---- detector wave, loss, seed --------------------------------------------------------
-        // The sums of this wavefield are reduced per wave right here and added to the wave's slot of `partial` in global memory
-        // (same lane every time: a plain read-modify-write, fixed order).  They used to be carried in registers to the end of
-        // the kernel — values that live across both sweeps get spilled, and hipcc 7.2 placed the spill of the zero-initialised
-        // accumulators in the flow block of an `if (tid < N)` region, BEFORE exec was restored: waves with no lane in that
-        // region never stored them and reloaded whatever an earlier kernel had left in that scratch slot (loss off by 5 % at
-        // N = 128, depending on what ran before).  tools/check_spills.py scans the ISA of every kernel for that pattern.
-        // The loop is counted and the kind of detector / carrier is one wave-uniform switch: the earlier form (`for (e = tid;
-        // e < N * N; e += T)` with a `continue` per case) compiled, at N = 72 after the change above, into code whose sums were
-        // wrong for most waves — and right again with a store added to the loop body (a code-generation problem that moved
-        // with register allocation, like the spill; the structured form has nothing for it to act on).
-        double acc = 0.0, acc2 = 0.0;
-        {
-            const int mode = !a.meas ? 0 : ((a.det.meas_dev && !far && !a.det.pfield) ? 1 : (a.det.pfield64 ? 2 : 3));
-            int t0 = tid;
-            asm volatile("" : "+v"(t0));
-#pragma nounroll
-            for (int i = 0; i < EPT; ++i) {
-                const int e = t0 + i * T;
-                if (EPT * T == N * N || e < N * N) {
-                    const int x = res_div<N>(e), y = e - x * N;
-                    const size_t o = b * fsz + (far ? y * N + x : e);
-                    cf d = f[x * P + y], seed;
-                    float w = 1.f;                 // WGT: the weight at the index of meas within its wavefield
-                    if constexpr (WGT) { if (mode != 0) w = a.det.wgt[far ? y * N + x : e]; }
-                    if (mode == 1) {               // plane-wave carrier, real-space detector, residual splitting
-                        seed = seed_split<PSN, WGT>(d, a.meas[o], a.det, acc, acc2, w);
-                        d = cadd(d, a.det.carrier);
-                    } else if (mode == 2) {        // carrier field in float64: |d| - m in float64
-                        cf dw;
-                        seed = seed_f64<PSN, WGT>(d, a.det.pfield64[e], a.meas[o], a.det, acc, acc2, dw, w);
-                        d = dw;
-                    } else {
-                        if (a.det.pfield) d = cadd(d, a.det.pfield[e]);
-                        else if (!far || e == 0) d = cadd(d, a.det.carrier);
-                        seed = d;
-                        if (mode == 3) seed = seed_plain<PSN, WGT>(d, a.meas[o], a.det, acc, acc2, w);
+        if constexpr (!SEEDED) {
+            // ---- forward sweep --------------------------------------------------------------------
+            Pipe::load_factors(a, rowbuf, y0, tid, m);
+            if constexpr (FUSE) {
+                // slice 0 is modulated on its own; every later slice inside the propagation step that produces it (EpiMod)
+                Point::modulate(f, tape0, a.carrier[0], a.carrier[a.S], a.pstack, m, tid);
+                for (int z = 0; z < a.S; ++z) {
+                    const long long r2 = Pipe::row_of(a, b, z + 2, tid);
+                    if (z + 1 < a.S) {
+                        EpiMod<N, T> em;
+                        em.a = &a;
+                        em.rows = rowbuf + ((z + 1) % 3) * N;
+                        em.tape = tape0 ? tape0 + (size_t)(z + 1) * a.tape_stride : nullptr;
+                        em.car = a.carrier[z + 1];
+                        em.csh = a.carrier[a.S + z + 1];
+                        em.pz = a.pstack ? a.pstack + (size_t)(z + 1) * fsz : nullptr;
+                        em.y0 = y0;
+                        res_prop<N, T, false>(f, hs_of(z), tw, tid, em);
+                    } else if (a.tf_all && !far) {
+                        res_prop<N, T, false>(f, hs_of(z), tw, tid);
                     }
-                    if (a.out_wave) a.out_wave[o] = d;
-                    if (mode != 0) f[x * P + y] = seed;
+                    if (tid < N) rowbuf[((z + 2) % 3) * N + tid] = r2;      // read two propagation steps from now
+                }
+            } else {
+                EpiNone none;
+                for (int z = 0; z < a.S; ++z) {
+                    const long long r2 = Pipe::row_of(a, b, z + 2, tid);
+                    Point::modulate(f, tape0 ? tape0 + (size_t)z * a.tape_stride : nullptr, a.carrier[z], a.carrier[a.S + z],
+                                    a.pstack ? a.pstack + (size_t)z * fsz : nullptr, m, tid);
+                    if (tid < N) rowbuf[((z + 2) % 3) * N + tid] = r2;
+                    if (z + 1 < a.S) {
+                        // the next slice's factors: in flight during the last two passes of the step
+                        res_prop<N, T, false>(f, hs_of(z), tw, tid, none, [&]() { Pipe::load_factors(a, rowbuf + ((z + 1) % 3) * N, y0, tid, m); });
+                    } else if (a.tf_all && !far) {
+                        res_prop<N, T, false>(f, hs_of(z), tw, tid);
+                    }
                 }
             }
-        }
-        if (a.meas) {
-            acc = wave_reduce_sum(acc);
-            acc2 = wave_reduce_sum(acc2);
-            if ((tid & 63) == 0) {
-                double* pw = a.partial + 2 * ((size_t)blockIdx.x * (T / 64) + (tid >> 6));
-                const bool first = b == (int)blockIdx.x;
-                pw[0] = (first ? 0.0 : pw[0]) + acc;
-                pw[1] = (first ? 0.0 : pw[1]) + acc2;
+            if (a.det_mode == BDOF_DET_NEAR) res_prop<N, T, false>(f, a.hdetT, tw, tid);
+            else if (far) res_fft2<N, T, -1>(f, tw, tid);
+
+            // ---- detector wave, loss, seed --------------------------------------------------------
+            // The sums of this wavefield are reduced per wave right here and added to the wave's slot of `partial` in global memory
+            // (same lane every time: a plain read-modify-write, fixed order).  They used to be carried in registers to the end of
+            // the kernel — values that live across both sweeps get spilled, and hipcc 7.2 placed the spill of the zero-initialised
+            // accumulators in the flow block of an `if (tid < N)` region, BEFORE exec was restored: waves with no lane in that
+            // region never stored them and reloaded whatever an earlier kernel had left in that scratch slot (loss off by 5 % at
+            // N = 128, depending on what ran before).  tools/check_spills.py scans the ISA of every kernel for that pattern.
+            // The loop is counted and the kind of detector / carrier is one wave-uniform switch: the earlier form (`for (e = tid;
+            // e < N * N; e += T)` with a `continue` per case) compiled, at N = 72 after the change above, into code whose sums were
+            // wrong for most waves — and right again with a store added to the loop body (a code-generation problem that moved
+            // with register allocation, like the spill; the structured form has nothing for it to act on).
+            double acc = 0.0, acc2 = 0.0;
+            {
+                const int mode = !a.meas ? 0 : ((a.det.meas_dev && !far && !a.det.pfield) ? 1 : (a.det.pfield64 ? 2 : 3));
+                int t0 = tid;
+                asm volatile("" : "+v"(t0));
+#pragma nounroll
+                for (int i = 0; i < EPT; ++i) {
+                    const int e = t0 + i * T;
+                    if (EPT * T == N * N || e < N * N) {
+                        const int x = res_div<N>(e), y = e - x * N;
+                        const size_t o = b * fsz + (far ? y * N + x : e);
+                        cf d = f[x * P + y], seed;
+                        float w = 1.f;                 // WGT: the weight at the index of meas within its wavefield
+                        if constexpr (WGT) { if (mode != 0) w = a.det.wgt[far ? y * N + x : e]; }
+                        if (mode == 1) {               // plane-wave carrier, real-space detector, residual splitting
+                            seed = seed_split<PSN, WGT>(d, a.meas[o], a.det, acc, acc2, w);
+                            d = cadd(d, a.det.carrier);
+                        } else if (mode == 2) {        // carrier field in float64: |d| - m in float64
+                            cf dw;
+                            seed = seed_f64<PSN, WGT>(d, a.det.pfield64[e], a.meas[o], a.det, acc, acc2, dw, w);
+                            d = dw;
+                        } else {
+                            if (a.det.pfield) d = cadd(d, a.det.pfield[e]);
+                            else if (!far || e == 0) d = cadd(d, a.det.carrier);
+                            seed = d;
+                            if (mode == 3) seed = seed_plain<PSN, WGT>(d, a.meas[o], a.det, acc, acc2, w);
+                        }
+                        if (a.out_wave) a.out_wave[o] = d;
+                        if (mode != 0) f[x * P + y] = seed;
+                    }
+                }
             }
-        }
-        if (!a.do_grad || !a.meas) continue;
+            if (a.meas) {
+                acc = wave_reduce_sum(acc);
+                acc2 = wave_reduce_sum(acc2);
+                if ((tid & 63) == 0) {
+                    double* pw = a.partial + 2 * ((size_t)blockIdx.x * (T / 64) + (tid >> 6));
+                    const bool first = b == (int)blockIdx.x;
+                    pw[0] = (first ? 0.0 : pw[0]) + acc;
+                    pw[1] = (first ? 0.0 : pw[1]) + acc2;
+                }
+            }
+            if (!a.do_grad || !a.meas) continue;
+        }   // !SEEDED
 
         // ---- adjoint sweep --------------------------------------------------------------------
         if (tid < N) {

@@ -9,6 +9,7 @@ import numpy as np
 from . import _lib
 from ._lib import DeviceBuffer
 from . import util
+from . import modes as probe_modes_mod
 
 _VARIANT = {'numpy_skip_last': _lib.VARIANT_NUMPY_SKIP_LAST, 'tf_all': _lib.VARIANT_TF_ALL}
 _LOSS = {'lsq': _lib.LOSS_LSQ, 'poisson': _lib.LOSS_POISSON}
@@ -186,6 +187,7 @@ class MultisliceEngine(object):
     meas_ref = 0.0
     tf_f64 = conv_f64 = False
     _gprobe = None              # enable_probe_grad
+    probe_modes = None          # set_probe_modes: the complex64 (M, Y, X) modes in force; None: the one probe of set_probe
     residual_split = True       # False: amplitudes go to the device as they are (a probe that changes between steps)
     loss_type, poisson_multiplier = 'lsq', 2e6      # set_loss
     detector_weights = None     # set_detector_weights: the (Y, X) float32 plane; None: every pixel counts alike
@@ -282,6 +284,8 @@ class MultisliceEngine(object):
             self.ctx.check(self.lib.bdof_set_physics_f64(self.h, hs64.ctypes.data, _hp(hd64)))
         if self._probe_args is not None:
             self.set_probe(*self._probe_args)      # the carrier (field, calibration) of the probe depends on the physics
+        if self.probe_modes is not None:           # (bdof_set_physics has dropped the modes: their carriers were the old physics')
+            self.set_probe_modes(self.probe_modes.real, self.probe_modes.imag)
         if self.detector_weights is not None:
             self.set_detector_weights(self.detector_weights)      # the detector decides the plane's index order
 
@@ -430,19 +434,62 @@ class MultisliceEngine(object):
         self._set_meas_mode(0j)
         return True
 
+    # ---- probe modes (bdof_set_probe_modes, include/bdof.h) --------------------------------------------------------------
+    def set_probe_modes(self, probe_real, probe_imag):
+        """M mutually incoherent probe modes, (M, Y, X) arrays: the data term then fits sqrt(sum_m |d_m|^2) (partial coherence;
+        modes.py).  They take the place of set_probe's probe until set_probe_modes(None, None) removes them.  With modes set B of
+        forward and loss_grad stays the number of windows and batch_max counts wavefields, B M <= batch_max; forward returns
+        (M, B, Y, X) and probe_grad (M, Y, X).  Resident and generic engines, transfer-function propagator, one step per voxel
+        slice, one detector plane, float32 sweeps with the tape; call it after set_physics."""
+        if probe_real is None:
+            self.ctx.check(self.lib.bdof_set_probe_modes(self.h, 0, None, None, None))
+            self.probe_modes = None
+            if self._probe_args is not None:
+                self.set_probe(*self._probe_args)      # (the residual splitting of a plane-wave probe comes back with it)
+            return
+        modes = probe_modes_mod.as_modes(probe_real, probe_imag)
+        if modes.shape[1:] != (self.ny, self.nx):
+            raise ValueError('probe modes must be (M, {}, {}), not {}'.format(self.ny, self.nx, modes.shape))
+        probe_modes_mod.check_probe_modes(modes.shape[0], propagator='fft' if self._conv_kernel is None else 'conv', slice_binning=self.slice_binning,
+                                          adjoint_precision='float64' if self.adjoint64 else None)
+        if self.optics is None:
+            raise RuntimeError('set_physics first')
+        if self.n_planes > 1:
+            raise ValueError('probe modes run with one detector plane')
+        o = self.optics
+        hT = o.table(self._step_nm(), tiled=True, fold=False, transpose=True, dtype=np.complex128)
+        hdT = self._detector_table(np.complex128, fold=False, transpose=True, tiled=True)
+        modes = modes.astype(np.complex64)             # as set_probe rounds its one (np_funcs.py:20-21)
+        p = np.ascontiguousarray(modes.transpose(0, 2, 1).astype(np.complex128))
+        self.ctx.check(self.lib.bdof_set_probe_modes(self.h, modes.shape[0], p.ctypes.data, hT.ctypes.data, _hp(hdT)))
+        self.probe_modes = modes
+        self._set_meas_mode(0j)                        # no scalar carrier under modes: plain amplitudes
+
+    @property
+    def n_modes(self):
+        return 0 if self.probe_modes is None else self.probe_modes.shape[0]
+
     # ---- gradient w.r.t. the probe (probe_type='optimizable', tensorflow_recon/fullfield.py:311-327) -------------------
     def enable_probe_grad(self, on=True):
         self.ctx.check(self.lib.bdof_enable_probe_grad(self.h, int(bool(on))))
         self._gprobe = DeviceBuffer.zeros(self.ctx, (self.nx, self.ny), np.complex64) if on else None
 
     def probe_grad(self, accumulate=False, to_host=True):
-        """dL/d(probe_real) + i dL/d(probe_imag) of the last loss_grad, summed over its wavefields: (Y, X) complex.
-        to_host=False: the device accumulator itself, [x][y]."""
-        self.ctx.check(self.lib.bdof_probe_grad(self.h, self._gprobe.ptr, int(bool(accumulate))))
+        """dL/d(probe_real) + i dL/d(probe_imag) of the last loss_grad, summed over its wavefields: (Y, X) complex — with probe
+        modes (M, Y, X), one gradient per mode.  to_host=False: the device accumulator itself, [x][y] per plane."""
+        if self.probe_modes is not None:
+            shape = (self.n_modes, self.nx, self.ny)
+            if self._gprobe.shape != shape:            # (enabled before the modes were set, or their number changed)
+                self._gprobe = DeviceBuffer.zeros(self.ctx, shape, np.complex64)
+            self.ctx.check(self.lib.bdof_probe_grad_modes(self.h, self._gprobe.ptr, int(bool(accumulate))))
+        else:
+            if self._gprobe.shape != (self.nx, self.ny):
+                self._gprobe = DeviceBuffer.zeros(self.ctx, (self.nx, self.ny), np.complex64)
+            self.ctx.check(self.lib.bdof_probe_grad(self.h, self._gprobe.ptr, int(bool(accumulate))))
         if not to_host:
             return self._gprobe
         self.ctx.sync()
-        return np.ascontiguousarray(self._gprobe.download().T)
+        return np.ascontiguousarray(np.swapaxes(self._gprobe.download(), -2, -1))
 
     def set_probe_none(self):
         """No probe of the ctx's own: every wavefield starts from a caller-supplied field (bdof_forward_range), no carrier."""
@@ -614,8 +661,16 @@ class MultisliceEngine(object):
         return [None if v is None else DeviceBuffer.from_host(self.ctx, np.asarray(v, dtype=np.int32)) for v in lists]
 
     def forward(self, B, angle_idx=None, xoff=None, yoff=None, keep_tape=False, to_host=True, conv=False):
-        """The detector waves of B wavefields, (B, Y, X) — with D detector planes (B, D, Y, X), in the order of the distances."""
+        """The detector waves of B wavefields, (B, Y, X) — with D detector planes (B, D, Y, X), in the order of the distances; with
+        M probe modes (set_probe_modes) of B windows (M, B, Y, X)."""
         D = self.n_planes
+        if self.probe_modes is not None and not conv:
+            M = self.n_modes                     # frames [M][B]: one detector wave per (mode, window)
+            a, xo, yo = self._idx_bufs(angle_idx, xoff, yoff)
+            out = DeviceBuffer(self.ctx, M * B * self.nx * self.ny * 8, np.complex64, (M * B, self.nx, self.ny))
+            self.ctx.check(self.lib.bdof_forward(self.h, B, _lib._ptr(a), _lib._ptr(xo), _lib._ptr(yo), out.ptr, int(keep_tape)))
+            self.ctx.sync()
+            return self._wave_to_host(out, M * B).reshape(M, B, self.ny, self.nx) if to_host else out
         out = DeviceBuffer(self.ctx, B * D * self.nx * self.ny * 8, np.complex64, (B, self.nx, self.ny) if D == 1 else (B, D, self.nx, self.ny))
         a, xo, yo = self._idx_bufs(angle_idx, xoff, yoff)
         if conv:

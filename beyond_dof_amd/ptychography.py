@@ -15,6 +15,7 @@ import numpy as np
 
 from . import h5io, tiffio, util
 from . import positions as probe_positions
+from . import modes as probe_modes
 from .comm import get_comm
 from .fullfield import create_probe_initial_guess, upsample_2x
 from .misc import create_summary, SUMMARY_PRESET_PTYCHO, SUMMARY_GEOMETRY
@@ -73,7 +74,8 @@ def reconstruct_ptychography(fname, probe_pos, probe_size, obj_size, theta_st=0,
                              pupil_function=None, probe_circ_mask=0.9, finite_support_mask=None,
                              forward_algorithm='fresnel', dynamic_dropping=True, dropping_threshold=8e-5,
                              n_dp_batch=20, object_type='normal', loss_type='lsq', poisson_multiplier=2e6, slice_binning=1,
-                             detector_weights=None, position_offsets=None, refine_positions=None, position_learning_rate=0.05, **kwargs):
+                             detector_weights=None, position_offsets=None, refine_positions=None, position_learning_rate=0.05,
+                             n_probe_modes=1, probe_mode_power=0.02, **kwargs):
     t_zero = time.time()
     comm = kwargs.get('comm') or get_comm()
     size, rank = comm.size, comm.rank
@@ -117,7 +119,22 @@ def reconstruct_ptychography(fname, probe_pos, probe_size, obj_size, theta_st=0,
     # and as a refined_positions line into summary.txt.
     offsets = probe_positions.check_positions(position_offsets, refine_positions, len(probe_pos), propagator=propagator, slice_binning=slice_binning,
                                               adjoint_precision=kwargs.get('adjoint_precision'), n_batch_per_update=n_batch_per_update)
-    if slice_binning > 1 or offsets is not None:
+    # n_probe_modes=M > 1: M mutually incoherent probe modes whose intensities add (partial coherence, fly scans; modes.py,
+    # bdof_set_probe_modes).  Every level's probe, whatever its probe_type, becomes modes.initial_modes(probe, M, probe_mode_power) —
+    # the probe, and M - 1 orthogonal modes of probe_mode_power of its power each — unless probe_initial already holds (M, py, px)
+    # arrays, which are taken as they are.  With probe_type='optimizable' the modes are orthogonalised at the end of every epoch.
+    # The float64 first step does not carry modes, so the DEFAULT becomes 'float32' and an explicit other choice raises, as with
+    # positions.  The result goes to probe_modes.npy (complex, (M, py, px)) and as a probe_mode_power line into summary.txt.
+    # n_probe_modes=1 is the run without the keyword.
+    n_probe_modes = probe_modes.check_probe_modes(n_probe_modes)
+    if n_probe_modes > 1:
+        probe_modes.check_probe_modes(n_probe_modes, propagator=propagator, slice_binning=slice_binning, adjoint_precision=kwargs.get('adjoint_precision'),
+                                      engine=kwargs.get('engine'))
+        if not float(probe_mode_power) > 0:
+            raise ValueError('probe_mode_power must be > 0')
+    if probe_initial is not None and np.ndim(probe_initial[0]) == 3 and np.shape(probe_initial[0])[0] != n_probe_modes:
+        raise ValueError('probe_initial holds {} probe modes: n_probe_modes must say so, not {}'.format(np.shape(probe_initial[0])[0], n_probe_modes))
+    if slice_binning > 1 or offsets is not None or n_probe_modes > 1:
         adjoint_precision = 'float32'
     for lv in range(multiscale_level):
         if (int(obj_size[2] / 2 ** lv) if lv else int(obj_size[2])) % slice_binning:
@@ -204,6 +221,9 @@ def reconstruct_ptychography(fname, probe_pos, probe_size, obj_size, theta_st=0,
             probe_real, probe_imag = util.mag_phase_to_real_imag(*probe_initial)
         else:
             raise ValueError("Invalid wavefront type. Choose from 'plane', 'fixed', 'optimizable'.")
+        if n_probe_modes > 1 and np.ndim(probe_real) == 2:
+            modes_0 = probe_modes.initial_modes(np.asarray(probe_real) + 1j * np.asarray(probe_imag), n_probe_modes, probe_mode_power)
+            probe_real, probe_imag = modes_0.real, modes_0.imag
 
         mk = lambda prec: PtychoSolver(this_obj_size, this_probe_size, this_probe_pos, n_theta, minibatch_size, energy_ev,
                                        psize_cm * ds_level, probe_real, probe_imag, variant=variant, comm=comm, device=comm.local_rank,
@@ -273,6 +293,8 @@ def reconstruct_ptychography(fname, probe_pos, probe_size, obj_size, theta_st=0,
                     if geo.refine:
                         geo.record(solver.geometry(), ds_level, output_folder)
             i_epoch += 1
+            if n_probe_modes > 1 and probe_type == 'optimizable':
+                solver.orthogonalize_probe_modes()          # the fit fixes the modes up to a unitary mix: keep the orthogonal one
             this_loss = solver.loss_and_grad(this_i_theta, this_ind_rank, this_prj_batch, want_loss=True)
             print_flush('Epoch {} (rank {}); loss = {}; Delta-t = {} s; current time = {} s,'.format(
                 i_epoch, rank, this_loss, time.time() - t0, time.time() - t_zero), 0, rank)
@@ -295,6 +317,13 @@ def reconstruct_ptychography(fname, probe_pos, probe_size, obj_size, theta_st=0,
                 if ds_level == 1:
                     with open(os.path.join(output_folder, 'summary.txt'), 'a') as f:
                         f.write(probe_positions.summary_line(offsets_start, offsets))
+        if n_probe_modes > 1 and rank == 0:
+            final = solver.get_probe() if probe_type == 'optimizable' else (probe_real, probe_imag)
+            final = np.asarray(final[0]) + 1j * np.asarray(final[1])
+            np.save(os.path.join(output_folder, 'probe_modes.npy'), final)
+            if ds_level == 1:
+                with open(os.path.join(output_folder, 'summary.txt'), 'a') as f:
+                    f.write(probe_modes.summary_line(final))
         obj_delta, obj_beta = obj_delta.astype(float), obj_beta.astype(float)
         first_level = False
         del solver

@@ -86,8 +86,11 @@ def create_fullfield_data_numpy(energy_ev, psize_cm, free_prop_cm, n_theta, phan
 def create_ptychography_data_batch_numpy(energy_ev, psize_cm, n_theta, phantom_path, save_folder, fname, probe_pos,
                                          probe_type='gaussian', probe_size=(72, 72), wavefront_initial=None,
                                          theta_st=0, theta_end=2 * PI, probe_circ_mask=0.9, minibatch_size=20,
-                                         overwrite=False, **kwargs):
-    """cnn_propagator/simulation.py:283-386.  Writes (n_theta, n_pos, py, px) complex64 far-field waves."""
+                                         overwrite=False, probe_modes=None, **kwargs):
+    """cnn_propagator/simulation.py:283-386.  Writes (n_theta, n_pos, py, px) complex64 far-field waves.
+    probe_modes: complex (M, py, px) mutually incoherent probe modes (modes.py) in place of the generated probe, taken as they
+    are (no circular mask on them).  The dataset then holds the amplitude sqrt(sum_m |d_m|^2) of the summed intensities, with a
+    zero imaginary part: a partially coherent measurement has no phase."""
     obj = _load_phantom(phantom_path)
     img_dim = obj.shape[:3]
     probe_pos = np.array(probe_pos)
@@ -97,13 +100,19 @@ def create_ptychography_data_batch_numpy(energy_ev, psize_cm, n_theta, phantom_p
     half = (np.array(probe_size) / 2).astype('int')
     path = os.path.join(save_folder, fname)
     _check_target(path, overwrite)
-    if probe_type != 'gaussian':
+    if probe_modes is not None:
+        probe_modes = np.asarray(probe_modes, dtype=np.complex128)
+        if probe_modes.ndim != 3 or probe_modes.shape[1:] != tuple(probe_size):
+            raise ValueError('probe_modes must be complex (M, {}, {}), not {}'.format(probe_size[0], probe_size[1], probe_modes.shape))
+    elif probe_type != 'gaussian':
         raise ValueError("only probe_type='gaussian' is generated here, as in the reference")
-    probe_real, probe_imag = util.gaussian_probe(probe_size, kwargs['probe_mag_sigma'], kwargs['probe_phase_sigma'],
-                                                 kwargs['probe_phase_max'])
+    else:
+        probe_real, probe_imag = util.gaussian_probe(probe_size, kwargs['probe_mag_sigma'], kwargs['probe_phase_sigma'],
+                                                     kwargs['probe_phase_max'])
     probe_mask = None
     if probe_circ_mask is not None:
-        probe_real, probe_imag = circ_mask(np.array([probe_real, probe_imag]), ratio=probe_circ_mask)
+        if probe_modes is None:
+            probe_real, probe_imag = circ_mask(np.array([probe_real, probe_imag]), ratio=probe_circ_mask)
         probe_mask = gaussian_filter(np.squeeze(circ_mask(np.ones((1,) + tuple(probe_size)), ratio=probe_circ_mask)), 3)
     pad = np.array([[0, 0], [0, 0]])
     if probe_pos[:, 0].min() - half[0] < 0:
@@ -124,12 +133,15 @@ def create_ptychography_data_batch_numpy(energy_ev, psize_cm, n_theta, phantom_p
             subs = np.array([obj_rot[int(p[0]) + pad[0, 0] - half[0]:int(p[0]) + pad[0, 0] - half[0] + probe_size[0],
                                      int(p[1]) + pad[1, 0] - half[1]:int(p[1]) + pad[1, 0] - half[1] + probe_size[1]]
                              for p in pos_batch])
-            exiting, _ = multislice_propagate_batch_numpy(subs[..., 0], subs[..., 1], probe_real, probe_imag, energy_ev, psize_cm,
-                                                          free_prop_cm='inf', obj_batch_shape=subs.shape[:-1],
-                                                          return_probe_array=False)
-            if probe_mask is not None:
-                exiting = exiting * probe_mask
-            out.append(exiting)
+            waves = []
+            for pr, pi in [(probe_real, probe_imag)] if probe_modes is None else [(p.real, p.imag) for p in probe_modes]:
+                exiting, _ = multislice_propagate_batch_numpy(subs[..., 0], subs[..., 1], pr, pi, energy_ev, psize_cm,
+                                                              free_prop_cm='inf', obj_batch_shape=subs.shape[:-1],
+                                                              return_probe_array=False)
+                if probe_mask is not None:
+                    exiting = exiting * probe_mask
+                waves.append(exiting)
+            out.append(waves[0] if probe_modes is None else np.sqrt(np.sum(np.abs(np.array(waves)) ** 2, axis=0)).astype(np.complex128))
         dat[ii] = np.vstack(out)
         tiffio.write_tiff(np.abs(dat[ii]), os.path.join(save_folder, 'diffraction_dat', 'mag_{:05d}'.format(ii)),
                           overwrite=True, dtype='float32')

@@ -24,6 +24,7 @@ from . import _lib
 from ._lib import DeviceBuffer
 from . import rotation as rotations
 from . import positions as probe_positions
+from . import modes as probe_modes
 from . import util
 from .comm import PseudoComm
 from .engine import MultisliceEngine, RESIDENT_SIZES, check_model_options
@@ -368,8 +369,15 @@ class _VolumeSolver(object):
         gradient w.r.t. the probe (bdof_probe_grad: G(psi_0) summed over the minibatch), averages it over the ranks,
         updates the probe on the host in float64 — it is one (Y, X) field — multiplies by the pupil function
         (tensorflow_recon/fullfield.py:546-548) and hands it back to the engine, which re-derives its carrier (scalar, or
-        the carrier field propagated on the device in float64)."""
+        the carrier field propagated on the device in float64).
+        Probe modes (PtychoSolver with (M, py, px) probes): the arrays are (M, py, px), every mode has its own Adam moments
+        (one step counter), the gradient is bdof_probe_grad_modes' and the pupil multiplies every mode."""
         self.probe = (np.asarray(probe_real, dtype=np.float64) + 1j * np.asarray(probe_imag, dtype=np.float64)) * np.ones((self.eng.ny, self.eng.nx))
+        n_modes = getattr(self, 'n_modes', 0)
+        if self.probe.ndim != (3 if n_modes else 2) or (n_modes and self.probe.shape[0] != n_modes):
+            self.probe = None
+            raise ValueError('enable_probe_optimization: the probe must have the shape the solver was built with ({})'.format(
+                '{} probe modes'.format(n_modes) if n_modes else 'one (Y, X) probe'))
         self.probe_lr = float(probe_learning_rate)
         self.pupil = None if pupil_function is None else np.asarray(pupil_function, dtype=np.float64)
         self.probe_m = np.zeros_like(self.probe)
@@ -383,10 +391,17 @@ class _VolumeSolver(object):
         # amplitudes that are already resident are put back to plain m.
         old_ref = self.eng.meas_ref
         self.eng.residual_split = False
-        self.eng.set_probe(self.probe.real, self.probe.imag)
+        self._probe_to_engine()
         if old_ref and self.meas is not None:
             self.ctx.sync()
             self.meas.upload((self.meas.download().astype(np.float64) + old_ref).astype(np.float32))
+
+    def _probe_to_engine(self):
+        """the probe — or, (M, py, px), the probe modes — handed to the engine"""
+        if self.probe.ndim == 3:
+            self.eng.set_probe_modes(self.probe.real, self.probe.imag)
+        else:
+            self.eng.set_probe(self.probe.real, self.probe.imag)
 
     def _probe_collect(self):
         """Add this minibatch's probe gradient to the device accumulator (call after every loss_grad)."""
@@ -400,7 +415,7 @@ class _VolumeSolver(object):
         if self.probe is None or self._pacc == 0:
             return
         self.ctx.sync()
-        g = np.ascontiguousarray(self._pgrad.download().T).astype(np.complex128) / self._pacc
+        g = np.ascontiguousarray(np.swapaxes(self._pgrad.download(), -2, -1)).astype(np.complex128) / self._pacc
         self._pacc = 0
         if self.comm.size > 1:
             g = self.comm.allreduce_sum_host(g) / self.comm.size
@@ -412,7 +427,7 @@ class _VolumeSolver(object):
         self.probe = self.probe - self.probe_lr * (mh.real / (np.sqrt(vh.real) + eps) + 1j * mh.imag / (np.sqrt(vh.imag) + eps))
         if self.pupil is not None:
             self.probe = self.probe * self.pupil
-        self.eng.set_probe(self.probe.real, self.probe.imag)
+        self._probe_to_engine()
 
     def get_probe(self):
         return self.probe.real.copy(), self.probe.imag.copy()
@@ -466,6 +481,8 @@ class FullfieldSolver(_VolumeSolver):
         # (transfer-function model) or the float64 path (real-space model, which has no such sweep)
         self.f64 = 'first' if adjoint64 == 'first' else (True if (adjoint64 is True and self.conv) else None)
         adjoint64 = adjoint64 is True and not self.conv
+        if probe_real is not None and np.ndim(probe_real) == 3:
+            raise ValueError("probe modes ((M, Y, X) probes) are ptychography's: FullfieldSolver takes one (Y, X) probe")
         if rotation not in ('nearest', 'bilinear', 'trilinear'):
             raise ValueError("rotation must be 'nearest', 'bilinear' or 'trilinear'")
         # the rotation's host side (for a materialised kind its float64 rows per angle): checked here, before anything is allocated
@@ -641,13 +658,24 @@ class PtychoSolver(_VolumeSolver):
         slice_binning: voxel slices per propagation step (MultisliceEngine); > 1 with propagator='fft' and no adjoint64 only, and
         engine=None then takes 'auto' (the resident engine does not carry it).
         engine: None picks the LDS-resident engine for small square probes (below) and the automatic choice otherwise; 'auto',
-        'generic', 'streaming' or 'resident' go to MultisliceEngine(engine=...) as they are."""
+        'generic', 'streaming' or 'resident' go to MultisliceEngine(engine=...) as they are.
+        probe_real / probe_imag of shape (M, py, px): M probe modes whose intensities add (partial coherence; modes.py,
+        bdof_set_probe_modes) — a 2-D probe takes the single-probe path and gives the bits it gave.  With modes engine=None picks
+        'resident' for the sizes with a resident plan and 'generic' otherwise ('streaming' raises), every minibatch sweeps mb * M
+        wavefields (the tape and the engine's batch are M times those of one probe), and propagator='conv', slice_binning > 1 and
+        adjoint64 raise (modes.check_probe_modes).  position_offsets / refine_positions, rotation='trilinear' and refine_geometry
+        work as they do with one probe: they read the window gradient, in which the modes are already summed."""
         if rotation not in ('nearest', 'trilinear'):
             raise ValueError("rotation must be 'nearest' or 'trilinear'")
         _check_options(propagator, adjoint64, loss_type, poisson_multiplier, detector_weights, slice_binning, rotation=rotation)
         offsets = probe_positions.check_positions(position_offsets, refine_positions, len(probe_pos), n_theta, propagator=propagator,
                                                   slice_binning=slice_binning, adjoint_precision='float64' if adjoint64 else None)
         self.pos = None if offsets is None else probe_positions.ProbePositions(n_theta, len(probe_pos), offsets, refine_positions, position_learning_rate)
+        self.n_modes = 0
+        if np.ndim(probe_real) == 3:
+            precision = None if not adjoint64 else 'first-step' if adjoint64 == 'first' else 'float64'
+            self.n_modes = probe_modes.check_probe_modes(int(np.shape(probe_real)[0]), propagator=propagator, slice_binning=slice_binning,
+                                                         adjoint_precision=precision, engine=engine)
         self.conv = propagator == 'conv'
         self.dim_y, self.dim_x, self.dim_z = [int(s) for s in obj_size]
         self.rot = rotations.choose(rotation, obj_size, n_theta, coord_ls, theta, (axis_tilt, axis_roll, center, rotation_matrices),
@@ -660,16 +688,20 @@ class PtychoSolver(_VolumeSolver):
         # small square probes: the LDS-resident engine (one launch per minibatch) also for the minibatches of ~20 positions the
         # drivers use, where the automatic choice would take the launch-bound streaming kernels for 64^2 / 128^2
         if engine is None:
-            engine = 'resident' if self.py == self.px and self.py in RESIDENT_SIZES and not self.conv and slice_binning == 1 else 'auto'
-        self.eng = MultisliceEngine(self.py, self.px, self.dim_z, self.mb, with_grad=True, device=device, stream=stream, engine=engine,
-                                    adjoint64=adjoint64 is True and not self.conv, slice_binning=slice_binning)
+            engine = 'resident' if self.py == self.px and self.py in RESIDENT_SIZES and not self.conv and slice_binning == 1 else \
+                'generic' if self.n_modes else 'auto'
+        self.eng = MultisliceEngine(self.py, self.px, self.dim_z, self.mb * max(self.n_modes, 1), with_grad=True, device=device, stream=stream,
+                                    engine=engine, adjoint64=adjoint64 is True and not self.conv, slice_binning=slice_binning)
         self.ctx = self.eng.ctx
         self.eng.set_loss(loss_type, poisson_multiplier)
         self.eng.set_physics(energy_ev, psize_cm, 'inf', variant=variant)   # free_prop_cm='inf', ptychography.py:76
         self.eng.set_detector_weights(detector_weights)
         if self.conv:
             self.eng.set_conv(energy_ev, psize_cm, kernel_size)
-        self.eng.set_probe(probe_real, probe_imag)
+        if self.n_modes:
+            self.eng.set_probe_modes(probe_real, probe_imag)
+        else:
+            self.eng.set_probe(probe_real, probe_imag)
         # adjoint64='first': the FIRST minibatch of every epoch runs through the model's float64 path on the SAME context
         # (bdof_loss_grad_tf_f64 / bdof_loss_grad_conv_f64: whole sweeps in double, no second engine) — Adam's first step after a
         # restart is lr g / (|g| + 1e-8), the only one in which a 1e-8 error of the gradient moves a voxel by a fraction of a
@@ -784,6 +816,17 @@ class PtychoSolver(_VolumeSolver):
         if self.comm.size > 1:
             dense = self.comm.allreduce_sum_host(dense) / self.comm.size
         self.pos.update(dense)
+
+    def orthogonalize_probe_modes(self):
+        """The optimised probe modes mixed into their orthogonal form, descending in power (modes.orthogonalize: a unitary mix, the
+        model's intensities do not change).  The probe's Adam moments and step counter start again: they belong to the basis
+        that went.  Returns the modes' relative powers."""
+        if self.probe is None or self.probe.ndim != 3:
+            raise ValueError('orthogonalize_probe_modes(): the solver optimises no probe modes (enable_probe_optimization with (M, py, px) probes)')
+        self.probe = probe_modes.orthogonalize(self.probe)
+        self.probe_m, self.probe_v, self.probe_t = np.zeros_like(self.probe), np.zeros_like(self.probe), 0
+        self._probe_to_engine()
+        return probe_modes.relative_power(self.probe)
 
     def _step_angles(self):
         return None if self._last is None else np.array([self._last[0]], dtype=np.int64)

@@ -334,6 +334,43 @@ int bdof_set_detector_weights(bdof_ctx* ctx, const float* w);
 #define BDOF_MAX_PLANES 8
 int bdof_set_detector_planes(bdof_ctx* ctx, int D, const float* hs_det, const double* hdet00);
 
+/* Probe modes (mixed states): a beam that is not fully coherent, or a fly scan smeared along its path, records the INCOHERENT sum
+ * of M >= 1 orthogonal probe modes P_0 .. P_{M-1} (Thibault & Menzel; Adorym's n_probe_modes).  For window j of a batch of B
+ *     psi_{j,m} = the multislice model under probe P_m          one sweep per (window, mode), the model of every other call
+ *     d_{j,m}   = the detector step of psi_{j,m}                none / near field / far field, as bdof_set_physics set it
+ *     a_j       = sqrt( sum_m |d_{j,m}|^2 )                     per pixel
+ *     L         = sum_j sum_pix w l(a_j, m_j) / (B NX NY)       l: the data term of bdof_set_loss, w: the detector weights; the
+ *                                                               divisor is the number of measured pixels, NOT times M
+ *     G(d_{j,m}) = f_j d_{j,m}                                  f_j: the data term's one factor per pixel (for least squares
+ *                                                               (2 / (B NX NY)) w (a_j - m_j) / a_j), formed once in float64 and shared
+ *                                                               by the modes; a_j = 0 gives 0, there is no epsilon
+ * The volume gradient is the sum over the modes of each sweep's k Im / -k Re (conj(phi) G(phi)); the gradient w.r.t. mode m is
+ * sum_j G(psi_{0; j,m}).  M = 1 is the model of bdof_set_probe_field.  A mode that is identically zero contributes nothing, and
+ * a unitary mix P'_m = sum_n U_mn P_n leaves L and the volume gradient unchanged.
+ * bdof_set_probe_modes: probes HOST [M][NX][NY] complex128; hT / hdetT as for bdof_set_probe_field.  The library builds, on the
+ * device in float64, M carrier stacks and M float64 detector carriers with the code bdof_set_probe_field builds its one with
+ * (the float32 and transposed detector planes of the single probe have no reader under modes and are not built); they live beside
+ * the probe of bdof_set_probe* and take its place while they are in force.  M = 0 or probes = NULL removes the modes and goes back
+ * to whatever bdof_set_probe* last set, whose results this call does not move by a bit; bdof_configure and bdof_set_physics drop
+ * the modes too (the carriers were propagated with the physics that go).  M outside [0, BDOF_MAX_MODES]: BDOF_ERR_ARG.
+ * With modes in force B of bdof_forward and bdof_loss_grad stays the number of WINDOWS: angle_of_b, xoff, yoff and meas stay [B];
+ * out_wave, where given, is [M][B][NX][NY] detector waves (frames in the order of meas); B M <= Bmax, else BDOF_ERR_ARG — a
+ * wavefield per (window, mode) is swept and taped, so the tape costs M times what it costs without modes.  After bdof_loss_grad
+ * bdof_grot holds [B][S][NX][NY] with the modes ALREADY SUMMED: bdof_rotation_adjoint, bdof_window_rotation_adjoint,
+ * bdof_window_stack_adjoint, bdof_window_position_grad and the rotate_*_adjoint / _param_grad calls run on it unchanged.
+ * bdof_probe_grad_modes: out device [M][NX][NY] complex, the sum over the windows of G(psi_0) per mode (accumulate != 0: added to
+ * what is there); needs bdof_enable_probe_grad(1) before the bdof_loss_grad.  bdof_probe_grad refuses under modes.
+ * Carried by the LDS-resident engine — at every batch size, whenever the size has a resident plan and the ctx allows the engine —
+ * and otherwise by the generic engine: both loss kinds, detector weights, both variants, all three detector modes.  Everything
+ * else refuses with BDOF_ERR_STATE and "probe modes" in bdof_last_error: a ctx whose only engine is the streaming one (a
+ * power-of-two size without a resident plan, or BDOF_CFG_NO_RESIDENT, unless BDOF_CFG_GENERIC), BDOF_CFG_RECOMPUTE,
+ * BDOF_CFG_ADJOINT64, BDOF_CFG_NO_GROT, slice binning, detector planes, the real-space propagator (bdof_*_conv*), the float64
+ * twins (bdof_set_tf_f64 / bdof_loss_grad_tf_f64), the range calls (bdof_forward_range*, bdof_adjoint_range,
+ * bdof_set_range_carrier / bdof_range_carrier_build), bdof_forward(keep_tape) and bdof_set_meas_mode(1). */
+#define BDOF_MAX_MODES 8
+int bdof_set_probe_modes(bdof_ctx* ctx, int M, const double* probes, const double* hT, const double* hdetT);
+int bdof_probe_grad_modes(bdof_ctx* ctx, void* out, int accumulate);
+
 /* The adjoint carrier the last bdof_loss_grad left (far-field detector under a plane-wave probe on the streaming and generic
  * engines): per wavefield the float64 seed of the DC bin, gcar[b], and conj(a_end) gcar[b], gt0[b] — HOST arrays of B complex
  * doubles (re, im).  Returns 1 and fills them where the configuration carries the DC seed that way, 0 (nothing written) where it
