@@ -877,8 +877,27 @@ static void launch_row_bwd(bdof_ctx* c, const Group& g, int z, const cf* gin, co
     }); }));
 }
 
+// The grid of a detector launch that leaves loss partials.  A workgroup leaves ONE float64 partial for all the tiles it runs, and
+// k_sum_partials adds the partials by their index: with the grid balanced over the sub-batch (rows_grid), which tiles share a
+// partial depends on how the batch was split, and the loss of one and of two sub-batch streams differed in its last bit (129
+// fields of 64 x 512).  per_tile: every workgroup takes one tile, so the partials are per tile and, the sub-batches coming in the
+// batch's order, in the batch's tile order whatever the split.  bdof_loss_grad asks for it where loss_tiles_fit says so: one
+// detector plane (with D planes the partials come sub-batch by sub-batch, plane by plane: that order does depend on the split)
+// and a batch whose tiles fit the partial buffer.  Beyond that, and in every other caller (bdof_loss, the float64 and the
+// real-space paths), the grid is the balanced one, as before: their partials group by launch, and a batch that large may still
+// differ in the last bit between splits.  A sub-batch of at most 2 ncu tiles (the flagship's) has one tile per workgroup either way.
+template <int N> static int loss_grid(const bdof_ctx* c, int B, int R, bool per_tile) {
+    return per_tile ? B * R / RowCfg<N>::TILE : rows_grid<N>(c, B, R);
+}
+static bool loss_tiles_fit(const bdof_ctx* c, int B, bool far) {
+    if (c->planes > 1) return false;
+    long long tiles = 0;
+    DISPATCH_N(far ? c->NX : c->NY, tiles = (long long)B * (far ? c->NY : c->NX) / RowCfg<N_>::TILE);
+    return tiles > 0 && tiles <= c->npartial;
+}
+
 // The detector kernels of the streaming engine on sub-batch g; with meas they leave their partial sums from slot `part` on and
-// return how many (= the grid).
+// return how many (= the grid; per_tile: loss_grid).
 static LossArgs loss_args(bdof_ctx* c, const Group& g, const DetPlane& det, const cf* in, cf* out_hyb, cf* out_wave, const float* meas,
                           float in_scale, float out_scale, int part) {
     LossArgs a{};
@@ -895,13 +914,13 @@ static LossArgs loss_args(bdof_ctx* c, const Group& g, const DetPlane& det, cons
 }
 // Real-space detector on L1 rows.
 static int launch_loss_real(bdof_ctx* c, const Group& g, const DetPlane& det, const cf* in, cf* out_hyb, bool tstore, cf* out_wave, const float* meas,
-                            float in_scale, float out_scale, int part = 0) {
+                            float in_scale, float out_scale, int part = 0, bool per_tile = false) {
     ProfScope ps(c, BDOF_K_LOSS, g.st);
     LossArgs a = loss_args(c, g, det, in, out_hyb, out_wave, meas, in_scale, out_scale, part);
     a.R = c->NX;
     a.twiddle = c->twY;
     int grid = 0;
-    DISPATCH_N(c->NY, grid = rows_grid<N_>(c, g.B, c->NX); with_bool(tstore, [&](auto TSTORE) { with_bool(meas && loss_is_poisson(c), [&](auto PSN) {
+    DISPATCH_N(c->NY, grid = loss_grid<N_>(c, g.B, c->NX, per_tile); with_bool(tstore, [&](auto TSTORE) { with_bool(meas && loss_is_poisson(c), [&](auto PSN) {
         with_bool(meas && det.wgt, [&](auto WGT) { hipLaunchKernelGGL((k_row_loss<N_, false, TSTORE, PSN, WGT>), dim3(grid), dim3(BDOF_THREADS), 0, g.st, a); });
     }); }));
     return grid;
@@ -931,13 +950,13 @@ static int launch_loss_plane(bdof_ctx* c, const Group& g, const DetPlane& det, i
 
 // Far-field detector on L2 rows; the seed goes back transposed into L1.
 static int launch_loss_far(bdof_ctx* c, const Group& g, const DetPlane& det, const cf* in, cf* out_hyb, cf* out_wave, const float* meas,
-                           float in_scale, float out_scale, int part = 0) {
+                           float in_scale, float out_scale, int part = 0, bool per_tile = false) {
     ProfScope ps(c, BDOF_K_LOSS, g.st);
     LossArgs a = loss_args(c, g, det, in, out_hyb, out_wave, meas, in_scale, out_scale, part);
     a.R = c->NY;
     a.twiddle = c->twX;
     int grid = 0;
-    DISPATCH_N(c->NX, grid = rows_grid<N_>(c, g.B, c->NY); with_bool(meas && loss_is_poisson(c), [&](auto PSN) {
+    DISPATCH_N(c->NX, grid = loss_grid<N_>(c, g.B, c->NY, per_tile); with_bool(meas && loss_is_poisson(c), [&](auto PSN) {
         with_bool(meas && det.wgt, [&](auto WGT) { hipLaunchKernelGGL((k_row_loss<N_, true, true, PSN, WGT>), dim3(grid), dim3(BDOF_THREADS), 0, g.st, a); });
     }));
     return grid;
@@ -2831,6 +2850,7 @@ int bdof_loss_grad(bdof_ctx* c, int B, const int* angle_of_b, const int* xoff, c
     int npart = 0;
     // Detector + seed.  Afterwards bufB holds g_hat(phi_{S-1}) (L1 order, normalised hybrid).
     const DetRoute dr = det_route(c);
+    const bool per_tile = loss_tiles_fit(c, B, dr.far);      // (loss_grid)
     for (const Group& g : split) {
         if (c->planes > 1) {
             // one real-space detector launch per plane on det_pl, the seeds (transposed) to seed_pl, then the fan-in to bufB
@@ -2841,12 +2861,12 @@ int bdof_loss_grad(bdof_ctx* c, int B, const int* angle_of_b, const int* xoff, c
         }
         const DetPlane det = det_plane(c, g, B, dr.pfield);      // the whole batch's seed scale
         if (dr.far) {
-            npart += launch_loss_far(c, g, det, dr.in, c->bufB, (cf*)out_wave, meas, 1.f, 1.f, npart);
+            npart += launch_loss_far(c, g, det, dr.in, c->bufB, (cf*)out_wave, meas, 1.f, 1.f, npart, per_tile);
         } else if (!dr.h) {
-            npart += launch_loss_real(c, g, det, dr.in, c->bufB, false, (cf*)out_wave, meas, dr.in_scale, dr.in_scale, npart);
+            npart += launch_loss_real(c, g, det, dr.in, c->bufB, false, (cf*)out_wave, meas, dr.in_scale, dr.in_scale, npart, per_tile);
         } else {
             // the detector wave came out of a transfer-function step: seed -> R (transposed) -> adjoint step
-            npart += launch_loss_real(c, g, det, dr.in, c->bufA, true, (cf*)out_wave, meas, 1.f, 1.f, npart);
+            npart += launch_loss_real(c, g, det, dr.in, c->bufA, true, (cf*)out_wave, meas, 1.f, 1.f, npart, per_tile);
             launch_row_prop(c, g, c->bufA, c->bufB, dr.h, 1.f, 1, n_steps(c) - 1, fused ? BDOF_K_LOSS : BDOF_K_COL_PROP);
         }
     }

@@ -1025,6 +1025,10 @@ __global__ __launch_bounds__(BDOF_THREADS, RowCfg<NY>::MIN_WAVES) void k_row_bwd
 //       N/8 butterflies: a thread sits on x = j + m T, y = y0 + r with its 16 neighbours along y) — there the table and the phi
 //       tape are 128-byte segments along y — modulation, then the FIRST stage of the next Fx on the same registers (it takes
 //       exactly the points j + m T), the rest of Px of step z in the row mapping, transposed tail -> [b][x][y].
+//       When the x-line kernels ask for their operands (a sub-batch of the flagship puts ONE tile on a workgroup, so nothing
+//       overlaps across tiles): the rotation lookups first, wave-private (WaveRows); pass 0's table segments between the two
+//       transforms of the row phase's last pass, so that they cross the phase barrier in registers; every other load of the
+//       transposed phase ahead of that phase's first store — no wait for an operand stands behind a store's acknowledgement.
 // Every transform takes the dithered constants of the step it belongs to (twiddles, sqrt(1/2), hx / hy): copy z-1 for the
 // leading step, copy z for the trailing one.  32 B per pixel (8 in + 8 table + 8 phi + 8 out) where A + B move 40.
 // ---------------------------------------------------------------------------------------------
@@ -1088,9 +1092,22 @@ __device__ __forceinline__ ObjRows obj_rows_of(const ObjView o, int b, int z, in
     return r;
 }
 // the source row of x less plain0, or -1.  Arithmetic only: a select on the (uniform) "is there a table" became a branch around every load
+// (and a select on "x has a source row" became a branch around THIS load, with the wait for it inside: the -1 is formed with a mask too)
 __device__ __forceinline__ int obj_rows_rel(const ObjRows r, int x) {
     const int s = r.look[(unsigned)min(x, r.imax)] & r.mask;
-    return x <= r.xmax ? s + (x & ~r.mask) : -1;
+    const int none = -(int)(x > r.xmax);                  // -1: no source row
+    return ((s + (x & ~r.mask)) & ~none) | none;
+}
+
+// Operands requested early are used from here on, not before: an empty statement the compiler cannot see through, so the selects
+// and additions that take a loaded value — and the wait for it — stay behind the work that is meant to cover the load.
+// This, the copy of threadIdx.x in k_slice_x_adj and the compiler barrier in front of its second phi request steer hipcc's
+// scheduler; they are not part of the language's contract.  k_slice_x_adj<512> sits at exactly 128 VGPRs.  On a toolchain change
+// check again: tools/check_spills.py (no scratch), the resource lines (<= 128 VGPRs) and, in the ISA listing of the two 512
+// instances, that the loads still stand where MEASUREMENTS.md ("x-line slice kernels: operands in flight") found them.
+__device__ __forceinline__ void use_from_here(float2 (&v)[8]) {
+#pragma unroll
+    for (int m = 0; m < 8; ++m) asm volatile("" : "+v"(v[m].x), "+v"(v[m].y));
 }
 
 // Point tw at the constants of one of the two steps a slice kernel belongs to (both sets are in LDS: FftTw::fill, in front of ONE
@@ -1167,6 +1184,28 @@ __global__ __launch_bounds__(BDOF_THREADS, RowCfg<NY>::MIN_WAVES) void k_slice_y
     }
 }
 
+// The rotation lookups of an x-line kernel's transposed phase, wave-private.  In the transposed mapping the lanes of one wave sit on
+// JW = 64 / TILE values of j per pass, so over all passes and its eight points j + m T a wave needs JW PASSES 8 <= 64 source rows
+// (at 512 points x = 4 w + i + 32 pass + 64 m).  Lane i + JW (pass + PASSES m) of the wave fetches that one at the top of the
+// tile (obj_rows_rel; the lanes beyond the count fetch a clamped entry nobody asks for) and the using lane takes it with a wave
+// shuffle: no LDS, no workgroup barrier, and nothing a workgroup's next tile could find stale.
+template <class C> struct WaveRows {
+    static_assert(C::TILE <= 64 && 64 % C::TILE == 0 && BDOF_THREADS % 64 == 0, "a wave covers whole values of j");
+    static constexpr int JW = 64 / C::TILE;                   // values of j a wave sits on in one pass
+    static constexpr int JP = BDOF_THREADS / C::TILE;         // values of j of one pass
+    static_assert(JW * C::PASSES * 8 <= 64, "one lookup per lane");
+    // the x whose lookup this lane fetches
+    static __device__ __forceinline__ int x_mine() {
+        const int lane = threadIdx.x % 64, w = threadIdx.x / 64;
+        const int i = lane % JW, t = lane / JW;
+        return w * JW + i + (t % C::PASSES) * JP + (t / C::PASSES) * C::T;
+    }
+    // the lookup of this thread's point j + m T in pass `pass`
+    static __device__ __forceinline__ int get(int mine, int pass, int m) {
+        return __shfl(mine, (int)(threadIdx.x % 64) / C::TILE + JW * (pass + C::PASSES * m), 64);
+    }
+};
+
 // BLK: phi_z goes to the tape in tile blocks, [b][NY / TILE][NX][TILE] (TILE = RowCfg<NX>::TILE rows along y): the transposed
 // mapping's stores are then contiguous over the workgroup (one wave instruction covers 512 bytes, a tile's phi is one block of
 // NX TILE entries) instead of 128-byte segments at a stride of one y-row.  Only k_slice_x_adj reads such a slot.
@@ -1179,23 +1218,42 @@ __global__ __launch_bounds__(BDOF_THREADS, RowCfg<NX>::MIN_WAVES) void k_slice_x
     __shared__ cf smem_tail[2][7 * C::T];
     const int tid = threadIdx.x % C::T, rl = threadIdx.x / C::T;
     const float sql[2] = {a.steps.sq_lead[0], a.steps.sq_lead[1]}, sqt[2] = {a.steps.sq_trail[0], a.steps.sq_trail[1]};
-    __shared__ int s_src[NX];                             // source row of every x of the tile's wavefield at this slice (less plain0)
+    typedef WaveRows<C> W;
     FftTw<NX> tw;
     FftTw<NX>::fill(a.steps.tw_lead, smem_tw[0], smem_tail[0]);
     FftTw<NX>::fill(a.steps.tw_trail, smem_tw[1], smem_tail[1]);
     __syncthreads();
     const ObjView o = a.obj;                              // by value (load_obj_row_bin)
+    const float2* const __restrict__ vol = o.vol;         // read-only while the kernel runs: its loads may pass the phi stores
     const int NY = a.R;
     const int ntiles = a.B * NY / C::TILE;
     for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         const auto [row0, b, y0] = tile_at<C>(tile, NY);
         const ObjRows rows = obj_rows_of(o, b, a.z, NX);
-        cf* const pdst = a.phi_out + (BLK ? (size_t)row0 * NX : (size_t)b * NX * NY);      // BLK: the tile's block (row0 = b NY + y0)
-        // The rotation lookup of the tile, one x per thread, on its way while the first phase runs; it goes through LDS to the
-        // transposed phase, which would otherwise wait for it and THEN for the table rows it points to (two round trips in a row)
-        const int src_mine = (int)threadIdx.x < NX ? obj_rows_rel(rows, threadIdx.x) : -1;
+        cf* const __restrict__ pdst = a.phi_out + (BLK ? (size_t)row0 * NX : (size_t)b * NX * NY);      // BLK: the tile's block (row0 = b NY + y0)
+        // The rotation lookups this wave's lanes need in the transposed phase, one per lane, requested before anything else (WaveRows)
+        const int src_mine = obj_rows_rel(rows, W::x_mine());
+        // The table segments of the transposed phase, unconditional and clamped (load_obj_row).  The transposed mapping's row
+        // (q % TILE, hence yg and yc) is the same in every pass.  Pass 0's segments are requested in the LAST pass of the row
+        // phase, once its row and h values are used up (the in-order memory counter then holds nothing back, and the 16 registers
+        // are h's: requested beside the row and h loads, every instance went to 126 .. 128 VGPRs and the 512 ones spilled), arrive
+        // under the inverse transform and cross the barrier in registers; the other passes' at the top of the transposed phase,
+        // ahead of its first store, where pass 0's arithmetic covers them.  inb: bit m says whether entry m counts (a source
+        // row, y inside the volume); the select waits with the value (use_from_here).
+        const int yg = y0 + (int)(threadIdx.x % C::TILE), yc = min(max(yg, 0), o.volNY - 1);
+        float2 db[C::PASSES][8];
+        unsigned inb[C::PASSES];
+        auto request_table = [&](int pass) {
+            inb[pass] = 0;
+#pragma unroll
+            for (int m = 0; m < 8; ++m) {
+                const int srel = W::get(src_mine, pass, m);
+                db[pass][m] = vol[(size_t)(rows.plain0 + max(srel, 0)) * o.volNY + yc];
+                inb[pass] |= (unsigned)(srel >= 0 && yg == yc) << m;
+            }
+        };
         // Px of step z-1 up to its last stage, row mapping
-#pragma nounroll
+#pragma unroll
         for (int pass = 0; pass < C::PASSES; ++pass) {
             const int r = pass * C::RPP + rl;
             RowLds<C::T> lds{smem + r * C::RS};
@@ -1209,32 +1267,26 @@ __global__ __launch_bounds__(BDOF_THREADS, RowCfg<NX>::MIN_WAVES) void k_slice_x
             line_fft<NX, -1, 1, false>(u, tw, tid, lds);
 #pragma unroll
             for (int m = 0; m < 8; ++m) u[m] = cmul(u[m], hv[m]);
+            if (pass == C::PASSES - 1) request_table(0);
             line_fft_partial<NX, +1, 2, false>(u, tw, tid, lds);
         }
-        if ((int)threadIdx.x < NX) s_src[threadIdx.x] = src_mine;
         __syncthreads();
         // Transposed mapping: last stage of Fx^-1, modulation, first stage of the next Fx.  The first stage's stores go to
         // positions 8 j + q of row image r, which other threads' last stages still read (another wave, another pass): every
         // read of the tile is done, with a workgroup barrier, before any write — the PASSES x 8 values wait in registers.
         cf v[C::PASSES][8];
 #pragma unroll
+        for (int pass = 1; pass < C::PASSES; ++pass) request_table(pass);
+#pragma unroll
         for (int pass = 0; pass < C::PASSES; ++pass) {
             const auto [q, r, j] = transposed_at<C>(pass);
             RowLds<C::T> lds{smem + r * C::RS};
-            // lookups and table loads first, unconditional and clamped (load_obj_row), consumed after the last stage
-            const int yg = y0 + r, yc = min(max(yg, 0), o.volNY - 1);
-            float2 db[8];
-#pragma unroll
-            for (int m = 0; m < 8; ++m) {
-                const int srel = s_src[j + m * C::T];
-                const float2 t = o.vol[(size_t)(rows.plain0 + max(srel, 0)) * o.volNY + yc];
-                const bool in = srel >= 0 && yg == yc;
-                db[m] = make_float2(in ? t.x : 0.f, in ? t.y : 0.f);
-            }
             last_stage<NX, +1, 2, false>(v[pass], j, lds, smem_tail[0], sql);
+            use_from_here(db[pass]);
 #pragma unroll
             for (int m = 0; m < 8; ++m) {
-                v[pass][m] = modulate_eps_s(v[pass][m], a.carrier, db[m], a.cshift);
+                const bool in = inb[pass] >> m & 1;
+                v[pass][m] = modulate_eps_s(v[pass][m], a.carrier, make_float2(in ? db[pass][m].x : 0.f, in ? db[pass][m].y : 0.f), a.cshift);
                 if constexpr (BLK) pdst[(unsigned)(q + m * C::T * C::TILE)] = v[pass][m];      // (x TILE + r, x = j + m T: q = j TILE + r)
                 else pdst[(unsigned)((j + m * C::T) * NY + yg)] = v[pass][m];      // (32-bit offsets inside one wavefield)
             }
@@ -1379,24 +1431,44 @@ __global__ __launch_bounds__(BDOF_THREADS, RowCfg<NX>::MIN_WAVES) void k_slice_x
     __shared__ cf smem[C::LDS_CF];
     __shared__ cf smem_tw[2][FftTw<NX>::LDS_CNT];
     __shared__ cf smem_tail[2][7 * C::T];
-    const int tid = threadIdx.x % C::T, rl = threadIdx.x / C::T;
     const float sql[2] = {a.steps.sq_lead[0], a.steps.sq_lead[1]}, sqt[2] = {a.steps.sq_trail[0], a.steps.sq_trail[1]};
-    __shared__ int s_src[NX];                             // source row of every x of the tile's wavefield at this slice (less plain0)
+    typedef WaveRows<C> W;
     FftTw<NX> tw;
     FftTw<NX>::fill(a.steps.tw_lead, smem_tw[0], smem_tail[0]);
     FftTw<NX>::fill(a.steps.tw_trail, smem_tw[1], smem_tail[1]);
     __syncthreads();
     const ObjView o = a.obj;                              // by value (load_obj_row_bin)
-    const int NY = a.R;
+    const float2* const __restrict__ vol = o.vol;         // table and tape are read-only while the kernel runs: their loads may pass
+    const int NY = a.R;                                   // the gradient stores
     const int ntiles = a.B * NY / C::TILE;
     for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         const auto [row0, b, y0] = tile_at<C>(tile, NY);
+        // The thread's indices are formed again for every tile, from a copy of threadIdx.x the compiler cannot see through: hoisted
+        // out of the tile loop, the row and transposed mappings' LDS and global offsets stayed in ~16 registers through the whole
+        // tile, and k_slice_x_adj<512>, with the operands below in flight, spilled 44 .. 104 bytes of them.  (Two passes only: the
+        // one-pass instances have the room, and forming the indices again cost them 4 .. 18 registers.)
+        int tx = threadIdx.x;
+        if constexpr (C::PASSES > 1) asm volatile("" : "+v"(tx));
+        const int tid = tx % C::T, rl = tx / C::T;
         const ObjRows rows = obj_rows_of(o, b, a.z, NX);
-        const cf* const psrc = a.phi + (size_t)row0 * NX;                              // the tile's block of the tape slot (k_slice_x<BLK>)
-        float2* const gdst = a.grot + ((size_t)b * o.S + a.z) * NX * NY;
-        const int src_mine = (int)threadIdx.x < NX ? obj_rows_rel(rows, threadIdx.x) : -1;       // (k_slice_x: on its way during the first phase)
+        const cf* const __restrict__ psrc = a.phi + (size_t)row0 * NX;                 // the tile's block of the tape slot (k_slice_x<BLK>)
+        float2* const __restrict__ gdst = a.grot + ((size_t)b * o.S + a.z) * NX * NY;
+        // lookups and table segments: as k_slice_x, wave-private lookups first, pass 0's segments from the last pass of the row phase
+        const int src_mine = obj_rows_rel(rows, W::x_mine());
+        const int yg = y0 + tx % C::TILE, yc = min(max(yg, 0), o.volNY - 1);
+        float2 db[C::PASSES][8];
+        unsigned inb[C::PASSES];
+        auto request_table = [&](int pass) {
+            inb[pass] = 0;
+#pragma unroll
+            for (int m = 0; m < 8; ++m) {
+                const int srel = W::get(src_mine, pass, m);
+                db[pass][m] = vol[(size_t)(rows.plain0 + max(srel, 0)) * o.volNY + yc];
+                inb[pass] |= (unsigned)(srel >= 0 && yg == yc) << m;
+            }
+        };
         // Px_z^H up to its last stage, row mapping
-#pragma nounroll
+#pragma unroll
         for (int pass = 0; pass < C::PASSES; ++pass) {
             const int r = pass * C::RPP + rl;
             RowLds<C::T> lds{smem + r * C::RS};
@@ -1410,43 +1482,52 @@ __global__ __launch_bounds__(BDOF_THREADS, RowCfg<NX>::MIN_WAVES) void k_slice_x
             line_fft<NX, -1, 1, false>(u, tw, tid, lds);
 #pragma unroll
             for (int m = 0; m < 8; ++m) u[m] = cmulc(u[m], hv[m]);
+            if (pass == C::PASSES - 1) request_table(0);
             line_fft_partial<NX, +1, 2, false>(u, tw, tid, lds);
         }
-        if ((int)threadIdx.x < NX) s_src[threadIdx.x] = src_mine;
         __syncthreads();
         // Transposed mapping: last stage of Fx^-1, gradient values, conj(c), first stage of the next Fx.  As in k_slice_x every read
         // of the tile's row images is done, with a workgroup barrier, before any write — the PASSES x 8 values wait in registers.
+        // Every load of the phase is requested ahead of its first store, so that no wait for an operand also waits for a store's
+        // acknowledgement: pass 0's phi block at the top; the next pass's table segments behind a pass's last stage (at the top,
+        // beside db[0], p[0], the last stage's 8 values and its 7 twiddles, k_slice_x_adj<512> spilled), the next pass's phi block
+        // once the pass has used its own, in front of its gradient stores (the 8 gradient values wait in registers).
         cf v[C::PASSES][8];
+        cf p[C::PASSES][8];
+        auto request_phi = [&](int pass) {
+#pragma unroll
+            for (int m = 0; m < 8; ++m) p[pass][m] = psrc[(unsigned)(tx + pass * BDOF_THREADS + m * C::T * C::TILE)];      // (x TILE + r, x = j + m T: q = j TILE + r)
+        };
+        request_phi(0);
 #pragma unroll
         for (int pass = 0; pass < C::PASSES; ++pass) {
-            const auto [q, r, j] = transposed_at<C>(pass);
+            const int q = tx + pass * BDOF_THREADS, r = q % C::TILE, j = q / C::TILE;
             RowLds<C::T> lds{smem + r * C::RS};
-            const int yg = y0 + r, yc = min(max(yg, 0), o.volNY - 1);
-            float2 db[8];
-            cf p[8];
-#pragma unroll
-            for (int m = 0; m < 8; ++m) {
-                const int srel = s_src[j + m * C::T];
-                const float2 t = o.vol[(size_t)(rows.plain0 + max(srel, 0)) * o.volNY + yc];
-                const bool in = srel >= 0 && yg == yc;
-                db[m] = make_float2(in ? t.x : 0.f, in ? t.y : 0.f);
-            }
-#pragma unroll
-            for (int m = 0; m < 8; ++m) p[m] = psrc[(unsigned)(q + m * C::T * C::TILE)];      // (x TILE + r, x = j + m T: q = j TILE + r)
             last_stage<NX, +1, 2, false>(v[pass], j, lds, smem_tail[0], sql);
+            if (pass + 1 < C::PASSES) request_table(pass + 1);
+            use_from_here(p[pass]);
+            use_from_here(db[pass]);
+            float2 gv[8];
 #pragma unroll
             for (int m = 0; m < 8; ++m) {
-                const cf t = cmulc(v[pass][m], cadd(p[m], a.carrier_phi));              // G * conj(phi)
-                gdst[(unsigned)((j + m * C::T) * NY + yg)] = make_float2(a.k * t.y, -a.k * t.x);      // (32-bit offsets inside one wavefield)
-                v[pass][m] = cmulc(v[pass][m], make_float2(1.f + db[m].x, db[m].y));    // conj(c) G
+                const bool in = inb[pass] >> m & 1;
+                const cf t = cmulc(v[pass][m], cadd(p[pass][m], a.carrier_phi));        // G * conj(phi)
+                gv[m] = make_float2(a.k * t.y, -a.k * t.x);
+                v[pass][m] = cmulc(v[pass][m], make_float2(1.f + (in ? db[pass][m].x : 0.f), in ? db[pass][m].y : 0.f));    // conj(c) G
             }
+            if (pass + 1 < C::PASSES) {
+                asm volatile("" ::: "memory");            // not before this pass's block is done with: both in flight at once spill
+                request_phi(pass + 1);
+            }
+#pragma unroll
+            for (int m = 0; m < 8; ++m) gdst[(unsigned)((j + m * C::T) * NY + yg)] = gv[m];      // (32-bit offsets inside one wavefield)
             tw.sq = sqt;                                  // (the first stage takes no twiddles, only the step's sqrt(1/2))
             stage_compute<NX, -1, P::R0, 1, 0, 1, false>(v[pass], tw, j);
         }
         __syncthreads();
 #pragma unroll
         for (int pass = 0; pass < C::PASSES; ++pass) {
-            const auto [q, r, j] = transposed_at<C>(pass);
+            const int q = tx + pass * BDOF_THREADS, r = q % C::TILE, j = q / C::TILE;
             RowLds<C::T> lds{smem + r * C::RS};
             stage_write<NX, P::R0, 1>(v[pass], j, lds);
         }
