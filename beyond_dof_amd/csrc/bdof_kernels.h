@@ -242,6 +242,28 @@ __device__ __forceinline__ void load_obj_row(const ObjView& o, long long srow, i
     }
 }
 
+// load_obj_row in two halves, for a kernel that asks for the row long before it uses it: the requests (unconditional, clamped; y0 = 0)
+// with the "entry m counts" bits, and the select, which waits with the values (use_from_here in between).
+__device__ __forceinline__ unsigned request_obj_row(const ObjView& o, long long srow, int tid, int T, float2 (&db)[8]) {
+    const float2* row = o.vol + (size_t)(srow >= 0 ? srow : 0) * o.volNY;
+    unsigned inb = 0;
+#pragma unroll
+    for (int m = 0; m < 8; ++m) {
+        const int yg = tid + m * T;
+        const int yc = min(max(yg, 0), o.volNY - 1);
+        db[m] = row[yc];
+        inb |= (unsigned)(srow >= 0 && yg == yc) << m;
+    }
+    return inb;
+}
+__device__ __forceinline__ void take_obj_row(unsigned inb, float2 (&db)[8]) {
+#pragma unroll
+    for (int m = 0; m < 8; ++m) {
+        const bool in = inb >> m & 1;
+        db[m] = make_float2(in ? db[m].x : 0.f, in ? db[m].y : 0.f);
+    }
+}
+
 // Slice binning (bdof_set_slice_binning): step z modulates by the product of the o.bin voxel slices z bin .. z bin + bin - 1.
 // The table holds c - 1, and (1 + t)(1 + u) - 1 = t + u + t u combines two entries without ever forming 1 + small: the
 // bin's c - 1 keeps the digits of its slices'.  A row outside the volume or a y outside it is u = 0, a factor of 1.  The
@@ -1123,22 +1145,47 @@ template <int N> __device__ __forceinline__ void tw_select(FftTw<N>& tw, const c
     for (int m = 1; m < 8; ++m) tw.w[m - 1] = tail[(m - 1) * (N / 8) + tid];
 }
 
+// The rotation lookups of a y-line kernel's tile.  A row of the tile belongs to T lanes, and thread (pass, rl) works on x = x0 + pass RPP
+// + rl: every lane fetches the PASSES lookups of its own rows at the top of the tile (obj_rows_rel; at 512 points a wave sits on one
+// row and the load is one address for the wave, at shorter lines the lanes of a row ask for the same entry), ahead of the first row
+// load, and keeps them in registers: no lookup, and no wait for one, inside the pass loop.  The fused route is never taken with
+// window offsets (fused_mode), so this is obj_src_row without its xoff term.
+template <class C> struct LineRows {
+    static_assert(C::PASSES <= 2, "src_row selects between two lookups");
+    static __device__ __forceinline__ void request(const ObjRows rows, int x_first, int (&srel)[C::PASSES]) {
+#pragma unroll
+        for (int pass = 0; pass < C::PASSES; ++pass) srel[pass] = obj_rows_rel(rows, x_first + pass * C::RPP);
+    }
+    // obj_src_row of the thread's row in pass `pass` (the pass loop is not unrolled: a select, not an index)
+    static __device__ __forceinline__ long long src_row(const ObjRows rows, const int (&srel)[C::PASSES], int pass) {
+        const int s = pass == 0 ? srel[0] : srel[C::PASSES - 1];
+        return s < 0 ? -1 : rows.plain0 + s;
+    }
+};
+
 template <int NY, bool FIRST, bool TAIL>
 __global__ __launch_bounds__(BDOF_THREADS, RowCfg<NY>::MIN_WAVES) void k_slice_y(SliceArgs a) {
     typedef RowCfg<NY> C;
     __shared__ cf smem[C::LDS_CF];
     __shared__ cf smem_tw[2][FftTw<NY>::LDS_CNT];
     __shared__ cf smem_tail[2][7 * C::T];
-    const int tid = threadIdx.x % C::T, rl = threadIdx.x / C::T;
     const float sql[2] = {a.steps.sq_lead[0], a.steps.sq_lead[1]}, sqt[2] = {a.steps.sq_trail[0], a.steps.sq_trail[1]};     // copies: no pointer into the argument block
     FftTw<NY> tw;
     if constexpr (!FIRST) FftTw<NY>::fill(a.steps.tw_lead, smem_tw[0], smem_tail[0]);
     FftTw<NY>::fill(a.steps.tw_trail, smem_tw[1], smem_tail[1]);
     __syncthreads();
+    const ObjView o = a.obj;                              // by value (load_obj_row_bin)
     const int NX = a.R;
     const int ntiles = a.B * NX / C::TILE;
     for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         const auto [row0, b, x0] = tile_at<C>(tile, NX);
+        const int tid = threadIdx.x % C::T, rl = threadIdx.x / C::T;
+        // The rotation lookups of this thread's rows, requested before anything else (LineRows): in the pass loop a table row's
+        // address is arithmetic on a value in hand, and its loads stand beside the row's and h's with no wait in front of them.
+        typedef LineRows<C> L;
+        const ObjRows rows = obj_rows_of(o, b, a.z, NX);
+        int srel[C::PASSES];
+        L::request(rows, x0 + rl, srel);
 #pragma nounroll
         for (int pass = 0; pass < C::PASSES; ++pass) {
             const int r = pass * C::RPP + rl;
@@ -1149,16 +1196,20 @@ __global__ __launch_bounds__(BDOF_THREADS, RowCfg<NY>::MIN_WAVES) void k_slice_y
             const cf* src = FIRST ? a.probe + (size_t)x * NY : a.in + (size_t)(row0 + r) * NY;
 #pragma unroll
             for (int m = 0; m < 8; ++m) u[m] = src[tid + m * C::T];
-            load_obj_row(a.obj, obj_src_row(a.obj, b, x, a.z, NX), 0, tid, C::T, db);
-            if constexpr (!FIRST) {                       // Py of step z-1
+            if constexpr (!FIRST) {
 #pragma unroll
                 for (int m = 0; m < 8; ++m) hv[m] = a.steps.h_lead[tid + m * C::T];
+            }
+            const unsigned inb = request_obj_row(o, L::src_row(rows, srel, pass), tid, C::T, db);
+            if constexpr (!FIRST) {                       // Py of step z-1
                 tw_select(tw, smem_tw[0], smem_tail[0], sql, tid);
                 line_fft<NY, -1, 1, false>(u, tw, tid, lds);
 #pragma unroll
                 for (int m = 0; m < 8; ++m) u[m] = cmul(u[m], hv[m]);
                 line_fft<NY, +1, 2, false>(u, tw, tid, lds);
             }
+            use_from_here(db);                            // the table row's select, and the wait for the row, not before this point
+            take_obj_row(inb, db);
 #pragma unroll
             for (int m = 0; m < 8; ++m) u[m] = modulate_eps_s(u[m], a.carrier, db[m], a.cshift);
             cf* pdst = a.phi_out + (size_t)(row0 + r) * NY;
