@@ -22,6 +22,7 @@
 #include "bdof_comm.h"
 #include "bdof_rigid.h"
 #include "bdof_windows.h"
+#include "bdof_shells.h"
 #include <rocfft/rocfft.h>
 #include <map>
 #include <optional>
@@ -138,6 +139,11 @@ struct Workspace {
     DevBuf<cf> m_zero;                           // zeros, max(NX NY, 2 S): the modes' eps_0 and their scalar carriers
     // rocFFT (generic-size engine, float64 paths, whole-field steps): one plan pair per (NX, NY, B, double)
     std::map<std::array<int, 4>, PlanPair> plans;
+    // bdof_shell_correlation (bdof_shells.h): the forward double-precision plan of a whole volume per (NX, NZ, NY), the complex128
+    // copies of the two volumes and the per-workgroup shell tables with their sum behind them — taken at first use
+    std::map<std::array<int, 3>, PlanPair> vol_plans;
+    DevBuf<double2> shell_a, shell_b;
+    DevBuf<double> shell_part;
     FftExec fft;                                 // of the ctx's stream
     // float64 adjoint sweep (BDOF_CFG_ADJOINT64; generic engine)
     bool have_h64 = false;
@@ -3737,6 +3743,93 @@ int bdof_regularizer_value(bdof_ctx* c, const void* x, int NXv, int NZv, int NYv
     HIPC(c, hipStreamSynchronize(c->stream));
     sums[0] = sums[1] = sums[2] = 0.0;
     for (int b = 0; b < grid; ++b) for (int j = 0; j < 3; ++j) sums[j] += p[3 * (size_t)b + j];
+    return 0;
+}
+
+// ---- Fourier shell correlation (bdof_shells.h) --------------------------------------------------------------------------------
+// the cached forward double-precision plan of one whole volume [NX][NZ][NY], over its axes longer than 1, in place; c->fft is ready
+static int volume_plan(bdof_ctx* c, int NX, int NZ, int NY, rocfft_plan* fwd) {
+    if (!g_rocfft_ready) { RFC(c, rocfft_setup()); g_rocfft_ready = true; }
+    const std::array<int, 3> key{NX, NZ, NY};
+    auto it = c->vol_plans.find(key);
+    size_t need = 0;                                                    // a cached plan's work area is there already
+    if (it == c->vol_plans.end()) {
+        size_t lengths[3], dims = 0;                                    // fastest dimension first
+        for (int n : {NY, NZ, NX}) if (n > 1) lengths[dims++] = (size_t)n;
+        PlanPair p;
+        RFC(c, rocfft_plan_create(&p.fwd, rocfft_placement_inplace, rocfft_transform_type_complex_forward, rocfft_precision_double, dims, lengths, 1, nullptr));
+        RFC(c, rocfft_plan_get_work_buffer_size(p.fwd, &need));
+        it = c->vol_plans.emplace(key, std::move(p)).first;
+    }
+    if (int r = fft_exec_room(c, c->fft, c->stream, need)) return r;
+    *fwd = it->second.fwd;
+    return 0;
+}
+
+// C = F (delta + i beta) of one volume in `spec`, unnormalised
+static int volume_spectrum(bdof_ctx* c, const void* vol, int NXv, int NZv, int NYv, DevBuf<double2>& spec) {
+    const size_t n = (size_t)NXv * NZv * NYv;
+    if (spec.size() < n) {
+        HIPC(c, hipStreamSynchronize(c->stream));
+        HIPC(c, spec.alloc(n));
+    }
+    rocfft_plan pf;
+    if (int r = volume_plan(c, NXv, NZv, NYv, &pf)) return r;
+    hipLaunchKernelGGL(k_shell_widen, dim3(g_elem_grid(c, n)), dim3(256), 0, c->stream, (const float2*)vol, (double2*)spec, n);
+    void* buf[1] = {(double2*)spec};
+    RFC(c, rocfft_execute(pf, buf, nullptr, c->fft.info));
+    return launched(c);
+}
+
+int bdof_shell_correlation(bdof_ctx* c, const void* vol_a, const void* vol_b, int NXv, int NZv, int NYv, int n_shells, double* out) {
+    const char* who = "bdof_shell_correlation";
+    if (!c || !vol_a || !vol_b || !out) return BDOF_ERR_ARG;
+    if (NXv < 1 || NZv < 1 || NYv < 1) return fail(c, BDOF_ERR_ARG, "bad volume shape");
+    if (n_shells < 1) return fail(c, BDOF_ERR_SIZE, std::string(who) + ": n_shells must be at least 1");
+    // Nref and L over the axes longer than 1
+    long long L = 1, Nref = 0;
+    int long_axes = 0;
+    for (long long n : {(long long)NXv, (long long)NZv, (long long)NYv}) {
+        if (n == 1) continue;
+        ++long_axes;
+        Nref = Nref ? std::min(Nref, n) : n;
+        long long a = L, b = n;
+        while (b) { const long long t = a % b; a = b; b = t; }
+        L = L / a * n;                                                  // at most 2^30 * (2^31 - 1) before the check
+        if (L > (1ll << 30)) return fail(c, BDOF_ERR_SIZE, std::string(who) + ": the least common multiple of the axes exceeds 2^30");
+    }
+    if (long_axes < 2) return fail(c, BDOF_ERR_SIZE, std::string(who) + ": fewer than two axes longer than 1");
+    if (Nref < 4) return fail(c, BDOF_ERR_SIZE, std::string(who) + ": the shortest axis must have at least 4 points");
+    HIPC(c, hipSetDevice(c->device));
+    if (int r = volume_spectrum(c, vol_a, NXv, NZv, NYv, c->shell_a)) return r;
+    if (vol_b != vol_a) if (int r = volume_spectrum(c, vol_b, NXv, NZv, NYv, c->shell_b)) return r;
+    const double2* Ca = c->shell_a;
+    const double2* Cb = vol_b != vol_a ? c->shell_b : c->shell_a;
+    ShellGeom g{NXv, NZv, NYv, (unsigned long long)(L / NXv), (unsigned long long)(L / NZv), (unsigned long long)(L / NYv), (unsigned long long)(L / Nref), 0, 0};
+    // A launch files as many shells as one wave's table holds in LDS; shells beyond that take further passes over the spectra.
+    // The grid depends on the shape and n_shells alone: the same call adds in the same order.
+    const int window = BDOF_SHELL_LDS_BYTES / (int)(BDOF_SHELL_TERMS * sizeof(double));
+    const long long rows = (long long)NXv * NZv;
+    std::vector<double> host((size_t)std::min(n_shells, window) * BDOF_SHELL_TERMS);
+    for (int s_lo = 0; s_lo < n_shells; s_lo += window) {
+        g.s_lo = s_lo;
+        g.s_n = std::min(n_shells - s_lo, window);
+        const int nent = g.s_n * BDOF_SHELL_TERMS;
+        const int waves = std::max(1, std::min(4, window / g.s_n));
+        const int blocks = (int)std::min<long long>((rows + waves - 1) / waves, (long long)c->ncu * 4);
+        const size_t need = ((size_t)blocks + 1) * nent;
+        if (c->shell_part.size() < need) {
+            HIPC(c, hipStreamSynchronize(c->stream));
+            HIPC(c, c->shell_part.alloc(need));
+        }
+        double* sum = (double*)c->shell_part + (size_t)blocks * nent;
+        hipLaunchKernelGGL(k_shell_sums, dim3(blocks), dim3(64 * waves), (size_t)waves * nent * sizeof(double), c->stream, Ca, Cb, g, (double*)c->shell_part);
+        hipLaunchKernelGGL(k_shell_blocks, dim3((nent + 255) / 256), dim3(256), 0, c->stream, (const double*)c->shell_part, blocks, nent, sum);
+        HIPC(c, hipGetLastError());
+        HIPC(c, hipMemcpyAsync(host.data(), sum, sizeof(double) * nent, hipMemcpyDeviceToHost, c->stream));
+        HIPC(c, hipStreamSynchronize(c->stream));
+        std::copy(host.begin(), host.begin() + nent, out + (size_t)s_lo * BDOF_SHELL_TERMS);
+    }
     return 0;
 }
 

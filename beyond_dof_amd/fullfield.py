@@ -20,7 +20,7 @@ import time
 
 import numpy as np
 
-from . import h5io, tiffio, util
+from . import h5io, resolution, tiffio, util
 from .comm import get_comm, minibatch_schedule
 from .misc import create_summary, SUMMARY_PRESET_FF, SUMMARY_GEOMETRY
 from .engine import check_model_options, read_detector_weights
@@ -63,7 +63,7 @@ def reconstruct_fullfield(fname, theta_st=0, theta_end=PI, n_epochs='auto', crit
                           dynamic_rate=True, probe_type='plane', probe_initial=None, probe_learning_rate=1e-3,
                           pupil_function=None, theta_downsample=None, forward_algorithm='fresnel', random_theta=True,
                           object_type='normal', kernel_size=17, debug=False, loss_type='lsq', poisson_multiplier=2e6, slice_binning=1,
-                          detector_weights=None, **kwargs):
+                          detector_weights=None, fsc_reference=None, fsc_threshold='half-bit', **kwargs):
     """Reconstruct a beyond-depth-of-focus object from full-field projections (see the module docstring and
     cnn_propagator/fullfield.py:28-77 for the parameters).  Returns (obj_delta, obj_beta) of the finest level."""
     t_zero = time.time()
@@ -146,6 +146,15 @@ def reconstruct_fullfield(fname, theta_st=0, theta_end=PI, n_epochs='auto', crit
     for lv in range(multiscale_level):          # the depths without a mask, before any level has run (a mask's are checked per level)
         if len(range(0, prj_0.shape[-1], 2 ** lv)) % slice_binning:
             raise ValueError('slice_binning={} does not divide the depth of multiscale level {}'.format(slice_binning, 2 ** lv))
+
+    # fsc_reference=(delta, beta), arrays or two .npy / TIFF paths: after the last level rank 0 compares the final resident volume
+    # with it by Fourier shell correlation (resolution.py; nothing but the shell sums leaves the device), writes fsc.npy and adds the
+    # lines resolution_delta / resolution_beta, at fsc_threshold ('half-bit', or a number such as 0.5 or 0.143), to summary.txt
+    if fsc_reference is not None:
+        resolution.threshold_curve(fsc_threshold, 1)
+        final_mask = _read_mask(save_path, prj_0.shape[-2])
+        fsc_reference = resolution.read_reference(fsc_reference, list(prj_0.shape[-2:]) + [final_mask.shape[-1] if final_mask is not None else prj_0.shape[-1]])
+        del final_mask
 
     obj_delta = obj_beta = None
     first_level = True
@@ -296,6 +305,8 @@ def reconstruct_fullfield(fname, theta_st=0, theta_end=PI, n_epochs='auto', crit
                 pr_f, pi_f = solver.get_probe()
                 tiffio.write_tiff(np.sqrt(pr_f ** 2 + pi_f ** 2), os.path.join(output_folder, 'probe_mag_ds_{}'.format(ds_level)), dtype='float32', overwrite=True)
                 tiffio.write_tiff(np.arctan2(pi_f, pr_f), os.path.join(output_folder, 'probe_phase_ds_{}'.format(ds_level)), dtype='float32', overwrite=True)
+        if fsc_reference is not None and ds_level == 1 and rank == 0:
+            resolution.write_report(solver.shell_correlation(fsc_reference, psize_cm), output_folder, fsc_threshold, psize_cm)
         obj_delta, obj_beta = obj_delta.astype(float), obj_beta.astype(float)
         first_level = False
         del solver

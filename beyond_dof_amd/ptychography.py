@@ -13,7 +13,7 @@ import time
 
 import numpy as np
 
-from . import h5io, tiffio, util
+from . import h5io, resolution, tiffio, util
 from . import positions as probe_positions
 from . import modes as probe_modes
 from .comm import get_comm
@@ -75,7 +75,7 @@ def reconstruct_ptychography(fname, probe_pos, probe_size, obj_size, theta_st=0,
                              forward_algorithm='fresnel', dynamic_dropping=True, dropping_threshold=8e-5,
                              n_dp_batch=20, object_type='normal', loss_type='lsq', poisson_multiplier=2e6, slice_binning=1,
                              detector_weights=None, position_offsets=None, refine_positions=None, position_learning_rate=0.05,
-                             n_probe_modes=1, probe_mode_power=0.02, **kwargs):
+                             n_probe_modes=1, probe_mode_power=0.02, fsc_reference=None, fsc_threshold='half-bit', **kwargs):
     t_zero = time.time()
     comm = kwargs.get('comm') or get_comm()
     size, rank = comm.size, comm.rank
@@ -139,6 +139,12 @@ def reconstruct_ptychography(fname, probe_pos, probe_size, obj_size, theta_st=0,
     for lv in range(multiscale_level):
         if (int(obj_size[2] / 2 ** lv) if lv else int(obj_size[2])) % slice_binning:
             raise ValueError('slice_binning={} does not divide the depth of multiscale level {}'.format(slice_binning, 2 ** lv))
+
+    # fsc_reference / fsc_threshold: as in reconstruct_fullfield — the final resident volume against a (delta, beta) reference by
+    # Fourier shell correlation (resolution.py): fsc.npy and the resolution_delta / resolution_beta lines of summary.txt
+    if fsc_reference is not None:
+        resolution.threshold_curve(fsc_threshold, 1)
+        fsc_reference = resolution.read_reference(fsc_reference, [int(n) for n in obj_size])
 
     print_flush('Reading data...', 0, rank)
     f = h5io.File(os.path.join(save_path, fname))
@@ -324,6 +330,8 @@ def reconstruct_ptychography(fname, probe_pos, probe_size, obj_size, theta_st=0,
             if ds_level == 1:
                 with open(os.path.join(output_folder, 'summary.txt'), 'a') as f:
                     f.write(probe_modes.summary_line(final))
+        if fsc_reference is not None and ds_level == 1 and rank == 0:
+            resolution.write_report(solver.shell_correlation(fsc_reference, psize_cm), output_folder, fsc_threshold, psize_cm)
         obj_delta, obj_beta = obj_delta.astype(float), obj_beta.astype(float)
         first_level = False
         del solver

@@ -194,6 +194,18 @@ class _VolumeSolver(object):
         self.ctx.check(self.ctx.lib.bdof_regularizer_value(self.ctx.handle, self.x[self.cur].ptr, self.dim_x, self.dim_z, self.dim_y, sums))
         return alpha_d * sums[0] + alpha_b * sums[1] + gamma * sums[2]
 
+    def shell_correlation(self, other, psize_cm=None):
+        """Fourier shell correlation (resolution.fourier_shell_correlation) of the resident volume with another solver's resident
+        volume, or with a host (delta, beta) pair in (y, x, z) order: nothing comes back from the device but the shell sums."""
+        from . import resolution
+        mine = self.x[self.cur]
+        if isinstance(other, _VolumeSolver):
+            if other.ctx is not self.ctx and other.ctx.device != self.ctx.device:
+                raise ValueError('the other solver lives on device {}, this one on {}'.format(other.ctx.device, self.ctx.device))
+            other.ctx.sync()
+            other = other.x[other.cur]
+        return resolution.fourier_shell_correlation(mine, other, psize_cm, ctx=self.ctx)
+
     # ---- the tail of the step ----------------------------------------------------------------
     def _reduces(self):
         return self.comm.size > 1 or getattr(self.comm, 'always_reduce', False)

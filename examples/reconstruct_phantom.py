@@ -8,7 +8,7 @@ reference.
 
     python examples/reconstruct_phantom.py [n=128] [n_theta=60] [n_epochs=100] [learning_rate=2e-8] [free_prop_cm=1e-3] [minibatch=10]
                                            [propagator=fft] [--loss lsq|poisson] [--poisson-multiplier 2e6] [--slice-binning 1]
-                                           [--refine-geometry center,axis_tilt]
+                                           [--refine-geometry center,axis_tilt] [--fsc]
 
 --loss poisson minimises the photon-counting likelihood (loss_type='poisson'); its data term is ~ 2 * multiplier times the
 least-squares one, and the L1 weights are scaled with it here.
@@ -19,6 +19,11 @@ with one step per voxel slice.
 --refine-geometry names: the data are simulated with rotation='trilinear' about an axis that is OFFSET (OFFSET below: the centre
 1.5 pixels, the tilt 0.01 rad off the nominal geometry) and reconstructed from the nominal one with refine_geometry=names; the
 refined values (out/geometry.npy) are printed beside the truth.
+--fsc: the resolution of the run by Fourier shell correlation (beyond_dof_amd/resolution.py).  The data are simulated and fitted
+with rotation='bilinear' (the true angles, so that a subset of them is a data set of its own).  Printed: the curve of the
+reconstruction against the phantom (fsc_reference=) with the half-bit resolution of delta and beta; then the even and the odd
+angles are reconstructed separately, each from its own data file with theta_st / theta_end at its first and last angle, and the
+half-bit resolution of the two halves against each other — the figure a user with measured data, who has no phantom, can get.
 """
 import os
 import sys
@@ -28,7 +33,7 @@ import time
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from beyond_dof_amd import h5io                                   # noqa: E402
+from beyond_dof_amd import h5io, resolution                       # noqa: E402
 from beyond_dof_amd.fullfield import reconstruct_fullfield       # noqa: E402
 from beyond_dof_amd.solver import FullfieldSolver                # noqa: E402
 
@@ -89,6 +94,46 @@ def run(n=128, n_theta=60, n_epochs=100, lr=2e-8, fp=1e-3, quiet=False, mb=10, p
             'beta_corr': float(np.corrcoef(rb.ravel(), 0.1 * d.ravel())[0, 1])}
 
 
+def _resolution_text(res):
+    return ', '.join('{} {}'.format(k, 'no crossing' if r is None else '{:.3g} nm half period (shell {:.2f})'.format(1e7 * r.half_period, r.shell))
+                     for k, r in sorted(res.items(), reverse=True))
+
+
+def run_fsc(n=128, n_theta=60, n_epochs=100, lr=2e-8, fp=1e-3, mb=10, propagator='fft', quiet=True, psize_cm=1e-7):
+    """The run of run() with rotation='bilinear', measured by Fourier shell correlation: against the phantom, and the even against
+    the odd angles.  Returns {'phantom': record, 'halves': record} (resolution.ShellRecord)."""
+    import contextlib
+    import io
+    rng = np.random.default_rng(0)
+    d = phantom(n, rng)
+    angles = np.linspace(0, 2 * np.pi, n_theta)
+    cwd = os.getcwd()
+    with tempfile.TemporaryDirectory() as td:
+        os.chdir(td)
+        try:
+            s = FullfieldSolver(n, n, n, n_theta, mb, 5000., psize_cm, free_prop_cm=fp, propagator=propagator, rotation='bilinear',
+                                theta=-angles.astype('float32'))
+            s.set_volume(d, 0.1 * d)
+            prj = s.forward_angles(np.arange(n_theta)).astype(np.complex64)
+            del s
+            os.makedirs('case')
+            sets = {'all': slice(None), 'even': slice(0, None, 2), 'odd': slice(1, None, 2)}
+            out = {}
+            for name, part in sets.items():
+                h5io.write_dataset('case/{}.h5'.format(name), 'exchange/data', prj[part])
+                with (contextlib.redirect_stdout(io.StringIO()) if quiet else contextlib.nullcontext()):
+                    out[name] = reconstruct_fullfield(
+                        name + '.h5', theta_st=angles[part][0], theta_end=angles[part][-1], n_epochs=n_epochs, learning_rate=lr,
+                        minibatch_size=min(mb, len(angles[part])), energy_ev=5000, psize_cm=psize_cm, free_prop_cm=fp, save_path='case',
+                        output_folder='out_' + name, shrink_cycle=None, seed=3, alpha_d=1e-9, alpha_b=1e-10, gamma=0,
+                        initial_guess=[np.zeros_like(d), np.zeros_like(d)], propagator=propagator, rotation='bilinear',
+                        fsc_reference=(d, 0.1 * d) if name == 'all' else None)
+            saved = np.load(os.path.join('case', 'out_all', 'fsc.npy'), allow_pickle=True).item()
+        finally:
+            os.chdir(cwd)
+    return {'phantom': resolution.ShellRecord(**saved), 'halves': resolution.fourier_shell_correlation(out['even'], out['odd'], psize_cm)}
+
+
 def _option(name, default):
     """--name value, taken out of sys.argv (the positional arguments keep their places)."""
     if name not in sys.argv:
@@ -104,6 +149,9 @@ def main():
     multiplier = float(_option('--poisson-multiplier', 2e6))
     slice_binning = int(_option('--slice-binning', 1))
     refine = tuple(k for k in _option('--refine-geometry', '').split(',') if k)
+    fsc = '--fsc' in sys.argv
+    if fsc:
+        sys.argv.remove('--fsc')
     n = int(sys.argv[1]) if len(sys.argv) > 1 else 128
     n_theta = int(sys.argv[2]) if len(sys.argv) > 2 else 60
     n_epochs = int(sys.argv[3]) if len(sys.argv) > 3 else 100
@@ -112,6 +160,16 @@ def main():
     fp = 'inf' if fp == 'inf' else tuple(float(z) for z in fp.split(',')) if ',' in fp else float(fp)
     mb = int(sys.argv[6]) if len(sys.argv) > 6 else 10
     propagator = sys.argv[7] if len(sys.argv) > 7 else 'fft'
+    if fsc:
+        r = run_fsc(n, n_theta, n_epochs, lr, fp, mb=mb, propagator=propagator)
+        rec = r['phantom']
+        print('Fourier shell correlation with the phantom, {}^3, {} angles, {} epochs:'.format(n, n_theta, n_epochs))
+        print('  shell  cycles/voxel  n_points  fsc_delta  fsc_beta  half-bit')
+        for row in zip(rec.shell, rec.frequency, rec.n_points, rec.fsc_delta, rec.fsc_beta, resolution.threshold_curve('half-bit', rec.n_points)):
+            print('  {:5d}  {:12.4f}  {:8d}  {:9.4f}  {:8.4f}  {:8.4f}'.format(*row))
+        print('resolution against the phantom (half-bit): ' + _resolution_text(resolution.resolution(rec, 'half-bit')))
+        print('resolution of the even against the odd angles (half-bit): ' + _resolution_text(resolution.resolution(r['halves'], 'half-bit')))
+        return
     r = run(n, n_theta, n_epochs, lr, fp, mb=mb, propagator=propagator, loss=loss, multiplier=multiplier, slice_binning=slice_binning,
             refine=refine)
     for k, (start, reached, truth) in r['geometry'].items():

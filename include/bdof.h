@@ -586,6 +586,26 @@ int bdof_gather_fields(bdof_ctx* ctx, void* dst, const void* src, const int* idx
  * The caller weights them (alpha_d, alpha_b, gamma).  Synchronous (three numbers come back). */
 int bdof_regularizer_value(bdof_ctx* ctx, const void* x, int NXv, int NZv, int NYv, double* sums);
 
+/* Fourier shell correlation of two volumes (tensorflow_recon/util.py:975-1048, fourier_shell_correlation / fourier_ring_correlation):
+ * the per-shell sums from which the host forms the curve and its thresholds.  vol_a, vol_b: DEVICE volumes [NXv][NZv][NYv] of
+ * (delta, beta) pairs, the solvers' layout; they may be the same pointer, neither is written.  out: HOST [n_shells][7], row s =
+ *   n_points of shell s,
+ *   sum Re(F_a conj F_b), sum |F_a|^2, sum |F_b|^2 of the delta channel,
+ *   the same three sums of the beta channel,
+ * F the unnormalised discrete Fourier transform over the axes longer than 1 (one of length 1: rings of 2-D arrays), computed in
+ * float64: each volume is widened to complex128 delta + i beta, one rocFFT transform C gives both channels, F_delta(k) =
+ * (C(k) + conj C(-k)) / 2 and F_beta(k) = (C(k) - conj C(-k)) / (2i).  Sums, not ratios: sum_s |F_a|^2 = N sum a^2 (Parseval).
+ * Shells are hard and exact.  With Nref the shortest and L the least common multiple of the axes longer than 1, w = L / Nref,
+ * and the signed index k_i = j for j < (N_i + 1) / 2, else j - N_i: u = 4 sum (k_i L / N_i)^2 in 64-bit integers, and the
+ * point lies in the shell s with (2s - 1)^2 w^2 <= u < (2s + 1)^2 w^2 (s = 0 for u < w^2) — s = floor(rho + 1/2), rho = Nref |f|,
+ * f in cycles per voxel; on a cube the rounded index radius.  The reference's shells have Gaussian-blurred edges around the same
+ * centre line; those are not reproduced.  Points of a shell >= n_shells are dropped.
+ * No floating-point atomics: the same call gives the same bits.  Synchronous (host numbers come back); needs no bdof_configure.
+ * The ctx keeps the complex128 workspace (16 bytes per voxel and distinct volume), the plan and rocFFT's work area from the first
+ * call until it is destroyed or configured again.
+ * BDOF_ERR_SIZE: L > 2^30, fewer than two axes longer than 1, Nref < 4, n_shells < 1. */
+int bdof_shell_correlation(bdof_ctx* ctx, const void* vol_a, const void* vol_b, int NXv, int NZv, int NYv, int n_shells, double* out);
+
 /* Shrink-wrap (cnn_propagator/fullfield.py:365-368): mask[i] *= (delta[i] > thresh) over n voxels. */
 int bdof_mask_shrink(bdof_ctx* ctx, const void* x, float* mask, size_t n, float thresh);
 
