@@ -34,6 +34,7 @@ class PseudoComm(object):
     local_rank = 0
     backend = 'none'
     sharded = False
+    always_reduce = False      # (RcclComm / TorchComm: BDOF_FORCE_COMM runs the collectives even with one rank)
 
     def attach(self, ctx):
         pass

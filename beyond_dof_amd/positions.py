@@ -9,6 +9,8 @@ Gauge: the mean offset is a translation of the object against the scan and is NO
 same time absorbs it, and Adam's path decides the split."""
 import numpy as np
 
+from . import hostopt
+
 MODES = (None, 'shared', 'per_angle')
 
 
@@ -63,8 +65,9 @@ class ProbePositions(object):
         self.n_theta, self.n_pos, self.mode, self.rate = int(n_theta), int(n_pos), mode, float(rate)
         off = np.zeros((self.n_pos, 2)) if offsets is None else np.asarray(offsets, dtype=np.float64)
         self.offset = np.array(np.broadcast_to(off, (self.n_theta, self.n_pos, 2)), dtype=np.float64)
-        shape = (self.n_pos, 2) if mode == 'shared' else (self.n_theta, self.n_pos, 2)
-        self.m, self.v, self.t = np.zeros(shape), np.zeros(shape), np.zeros(shape, dtype=np.int64)
+        self.shape = (self.n_pos, 2) if mode == 'shared' else (self.n_theta, self.n_pos, 2)
+        self.opt = hostopt.MaskedAdam(self.shape, self.rate)
+        self.m, self.v, self.t = self.opt.m, self.opt.v, self.opt.t           # (the optimiser's own arrays)
 
     @property
     def refine(self):
@@ -80,27 +83,18 @@ class ProbePositions(object):
     def dense(self, grad, i_theta, pos_idx):
         """one vector for the ranks to add: the gradient (len(pos_idx), 2) scattered over the entries (a position listed twice
         adds), then which entries it lists"""
-        full, seen = np.zeros(self.m.shape), np.zeros(self.m.shape[:-1])
         at = (np.asarray(pos_idx),) if self.mode == 'shared' else (np.full(len(pos_idx), int(i_theta)), np.asarray(pos_idx))
-        np.add.at(full, at, np.asarray(grad, dtype=np.float64))
-        seen[at] = 1.
-        return np.concatenate([full.reshape(-1), seen.reshape(-1)])
+        return hostopt.pack(self.shape[:-1], at, [grad], [self.shape])
 
     def split(self, dense):
         """dense()'s vector -> (gradient, listed) in the entries' shape"""
-        n = self.m.size
-        return dense[:n].reshape(self.m.shape), dense[n:].reshape(self.m.shape[:-1]) > 0
+        g, move = hostopt.unpack(dense, self.shape[:-1], [self.shape])[0]
+        return g, move[..., 0]
 
-    def update(self, dense, b1=0.9, b2=0.999, eps=1e-8):
+    def update(self, dense):
         """Adam on the listed entries from dense()'s vector (already summed over the ranks and divided by their number)"""
-        g, seen = self.split(dense)
-        move = np.repeat(seen[..., None], 2, axis=-1)
-        self.t = self.t + move
-        self.m = np.where(move, b1 * self.m + (1 - b1) * g, self.m)
-        self.v = np.where(move, b2 * self.v + (1 - b2) * g * g, self.v)
-        t = np.maximum(self.t, 1)
-        step = np.where(move, self.rate * (self.m / (1 - b1 ** t)) / (np.sqrt(self.v / (1 - b2 ** t)) + eps), 0.)
-        self.offset = self.offset - step            # ('shared': (n_pos, 2) against (n_theta, n_pos, 2) — every angle takes the step)
+        g, move = hostopt.unpack(dense, self.shape[:-1], [self.shape])[0]
+        self.offset = self.opt.step(self.offset, g, move)      # ('shared': (n_pos, 2) against (n_theta, n_pos, 2) — every angle takes the step)
 
 
 def summary_line(start, end):

@@ -5,7 +5,7 @@ import collections
 
 import numpy as np
 
-from . import util
+from . import hostopt, util
 from ._lib import DeviceBuffer
 
 # a materialised kind: the host builder of its float64 rows per angle, their width, and its three libbdof entry points
@@ -55,9 +55,9 @@ class RigidGeometry(object):
                           axis_roll=np.array(float(axis_roll)), theta=np.array(np.atleast_1d(theta), dtype=np.float64), shifts=np.zeros((n, 2)))
         self.refine, self.n_theta = tuple(refine), n
         self.rate = {k: float(rate) / (1. if k in ('center', 'shifts') else max(self.shape) / 2.) for k in util.GEOMETRY_NAMES}
-        self.m = {k: np.zeros_like(self.value[k]) for k in self.refine}
-        self.v = {k: np.zeros_like(self.value[k]) for k in self.refine}
-        self.t = {k: np.zeros(self.value[k].shape, dtype=np.int64) for k in self.refine}
+        self.opt = {k: hostopt.MaskedAdam(self.value[k].shape, self.rate[k]) for k in self.refine}
+        self.shapes = [self.value[k].shape for k in self.refine]
+        self.m, self.v, self.t = [{k: getattr(o, a) for k, o in self.opt.items()} for a in 'mvt']     # (the optimisers' own arrays)
 
     def values(self):
         return {k: v.copy() for k, v in self.value.items()}
@@ -77,37 +77,19 @@ class RigidGeometry(object):
                                             np.reshape(dprm, (len(index), 12)), index)
 
     def dense(self, grad, index):
-        """one vector for the ranks to add: per refined name its gradient scattered over all angles, then which angles it lists"""
-        parts = []
-        for k in self.refine:
-            full = np.zeros_like(self.value[k])
-            if full.ndim:
-                np.add.at(full, np.asarray(index), grad[k])
-            else:
-                full += grad[k]
-            parts.append(full.reshape(-1))
-        seen = np.zeros(self.n_theta)
-        seen[np.asarray(index)] = 1.
-        return np.concatenate(parts + [seen])
+        """one vector for the ranks to add (hostopt.pack): per refined name its gradient scattered over all angles, then which angles it lists"""
+        return hostopt.pack((self.n_theta,), (np.asarray(index),), [grad[k] for k in self.refine], self.shapes)
 
-    def update(self, dense, b1=0.9, b2=0.999, eps=1e-8):
+    def update(self, dense):
         """Adam on the refined names from dense()'s vector (already summed over the ranks and divided by their number)"""
-        seen, at = dense[-self.n_theta:] > 0, 0
-        for k in self.refine:
-            g = dense[at:at + self.value[k].size].reshape(self.value[k].shape)
-            at += self.value[k].size
-            move = np.ones(self.value[k].shape, dtype=bool) if self.value[k].ndim == 0 else (seen if g.ndim == 1 else np.repeat(seen[:, None], 2, axis=1))
-            self.t[k] = self.t[k] + move
-            self.m[k] = np.where(move, b1 * self.m[k] + (1 - b1) * g, self.m[k])
-            self.v[k] = np.where(move, b2 * self.v[k] + (1 - b2) * g * g, self.v[k])
-            t = np.maximum(self.t[k], 1)
-            step = self.rate[k] * (self.m[k] / (1 - b1 ** t)) / (np.sqrt(self.v[k] / (1 - b2 ** t)) + eps)
-            self.value[k] = np.where(move, self.value[k] - step, self.value[k])
+        for k, (g, move) in zip(self.refine, hostopt.unpack(dense, (self.n_theta,), self.shapes)):
+            self.value[k] = self.opt[k].step(self.value[k], g, move)
 
 
 class LookupRotation(object):
     """rotation='nearest': the lookup tables (cnn_propagator/util.py:294-402), uploaded once and fused into the kernels."""
     one_pass_tail = float64_paths = True       # bdof_rotation_adjoint_adam and the models' float64 twins go through the tables
+    geometry = None            # only rotation='trilinear' from theta and the axis keywords has one: its RigidGeometry (choose)
 
     def __init__(self, shape, n_theta, coord_ls):
         self.dim_y, self.dim_x, self.dim_z = [int(s) for s in shape]
@@ -165,8 +147,6 @@ class MaterialisedRotation(LookupRotation):
     """rotation='bilinear' / 'trilinear' (KINDS), behind the same methods: the minibatch's rotated objects are written out at every
     step, straight into the ctx's modulation table, so no volume stays bound between steps; the adjoint is a gather with the same rows."""
     one_pass_tail = float64_paths = False
-
-    geometry = None            # rotation='trilinear' from theta and the axis keywords: their RigidGeometry (choose)
 
     def __init__(self, shape, n_theta, kind, prm):
         LookupRotation.__init__(self, shape, n_theta, None)

@@ -15,6 +15,7 @@ The collectives run on the communicator's stream; the ctx stream only waits for 
 of the next slabs and the consumer of the previous ones run while a slab is on the wire.  The TV stencil reads the
 pre-update volume (x_old), which no slab overwrites: slab-wise, sharded and whole-volume execution give identical results.
 """
+import collections
 import ctypes
 import os
 
@@ -28,6 +29,10 @@ from . import modes as probe_modes
 from . import util
 from .comm import PseudoComm
 from .engine import MultisliceEngine, RESIDENT_SIZES, check_model_options
+from .hostopt import ProbeVariable
+
+# one update of the volume as the tail takes it: bias-correction exponent, step, regulariser (_VolumeSolver.regularizer), clip to >= 0, mask
+Update = collections.namedtuple('Update', 'i_update learning_rate alpha_d alpha_b gamma clip use_mask', defaults=(0.0, 0.0, 0.0, True, True))
 
 
 def _check_options(propagator, adjoint64, *options, **path):
@@ -39,26 +44,57 @@ class _VolumeSolver(object):
     """What the full-field and ptychography solvers share: volume double buffer, gradient, moments, the tail of the step."""
 
     lookahead = 2              # slabs in flight between a collective's start and the Adam pass that consumes it
+    n_modes = 0                # probe modes (PtychoSolver with (M, py, px) probes)
+
+    def _float64_paths(self, adjoint64, propagator):
+        """adjoint64, propagator -> self.conv, self.f64 and (returned) the engine's adjoint64, its float64 adjoint sweep (transfer-function
+        model).  f64 = 'first': the FIRST minibatch of every epoch runs through the model's float64 path on the same context (bdof_loss_grad_tf_f64
+        / _conv_f64: whole sweeps in double) — Adam's first step after a restart is lr g / (|g| + 1e-8), the only one in which a 1e-8 error of
+        the gradient moves a voxel by a fraction of a whole step; True: every minibatch (real-space model, which has no such sweep)."""
+        if adjoint64 not in (None, False, True, 'first'):
+            raise ValueError("adjoint64 must be None, False, True or 'first'")
+        self.conv = propagator == 'conv'
+        self.f64 = 'first' if adjoint64 == 'first' else (True if (adjoint64 is True and self.conv) else None)
+        return adjoint64 is True and not self.conv
+
+    def _set_up(self, energy_ev, psize_cm, kernel_size, loss, detector_weights, probe_real, probe_imag, **physics):
+        """The constructors' common tail, once self.eng and self.rot exist: the engine's model (loss: set_loss's arguments, physics:
+        set_physics' keywords), the float64 twin, then the buffers of the rotation, the volume and (_batch_buffers) the staged minibatch."""
+        self.ctx = self.eng.ctx
+        self.eng.set_loss(*loss)
+        self.eng.set_physics(energy_ev, psize_cm, **physics)
+        self.eng.set_detector_weights(detector_weights)
+        if self.conv:
+            self.eng.set_conv(energy_ev, psize_cm, kernel_size)
+        (self.eng.set_probe_modes if np.ndim(probe_real) == 3 else self.eng.set_probe)(probe_real, probe_imag)
+        if self.f64:
+            self._enable_f64()
+        self.rot.allocate(self.ctx, self.mb)
+        self._init_volume()
+        self._batch_buffers()
+        self._bind_volume()
+        self.rot.attach(self.eng)
 
     def _init_volume(self):
         shape = (self.dim_x, self.dim_z, self.dim_y, 2)
         self.x = [DeviceBuffer.zeros(self.ctx, shape, np.float32), DeviceBuffer.zeros(self.ctx, shape, np.float32)]
         self.cur = 0
-        self.g = DeviceBuffer.zeros(self.ctx, shape, np.float32)
-        self.m = DeviceBuffer.zeros(self.ctx, shape, np.float32)
-        self.v = DeviceBuffer.zeros(self.ctx, shape, np.float32)
+        self.g, self.m, self.v = [DeviceBuffer.zeros(self.ctx, shape, np.float32) for _ in range(3)]
         self.mask = None
         self.nvox = self.dim_x * self.dim_z * self.dim_y
-        self._plan = None
-        self.tuned = None
+        self._plan = self.tuned = None
         self._acc = 0              # minibatches accumulated in self.g since the last update (n_batch_per_update)
         self._epoch_plan = None    # shard layout of the Adam moments since the last reset_moments (None: none taken yet)
         self._g_shards = None      # slabs whose gradient is reduced on this rank's 1/size only (after a sharded step)
         self._g_stale = False      # the last step ran the one-pass tail, which does not write self.g (_g_refresh)
-        self.probe = None          # enable_probe_optimization
-        self._pgrad = None         # the engine's device accumulator of the probe gradient (_probe_collect)
+        self.pvar = None           # enable_probe_optimization: the probe as a variable (hostopt.ProbeVariable)
         self.meas = None           # FullfieldSolver.set_measurements
         self.meas_all = None       # PtychoSolver.set_measurements
+        # what a staged minibatch leaves behind, written by the staging functions only (_rot_loss_grad; _win_loss_grad, _stack_windows)
+        self._angles = None        # its angles, int64 (ptychography: the one)
+        self._last = None          # ptychography: (i_theta, xo, yo), xo / yo the device addresses of its window origins
+        self._last_pos = None      # ... at fractional positions: (i_theta, pos_idx) of the windows the window gradient belongs to
+        self._source = None        # ... and the (rows, table) they were cut from, device addresses (rotation's window_source)
         self.comm.attach(self.ctx)
 
     def _bind_volume(self):
@@ -147,10 +183,9 @@ class _VolumeSolver(object):
 
     # ---- the geometry of rotation='trilinear' (rotation.RigidGeometry) --------------------------------------------------------
     def _rigid_geometry(self):
-        geo = getattr(self.rot, 'geometry', None)
-        if geo is None:
+        if self.rot.geometry is None:
             raise ValueError("the geometry is that of rotation='trilinear' built from theta and the axis keywords (not rotation_matrices)")
-        return geo
+        return self.rot.geometry
 
     def geometry(self):
         """The current center, axis_tilt, axis_roll, theta (n_theta) and shifts (n_theta, 2): what refine_geometry has made of them."""
@@ -172,21 +207,24 @@ class _VolumeSolver(object):
             raise RuntimeError('geometry_gradient() follows loss_and_grad() or runs inside step(): no angles have been staged yet')
         return geo.gradient(self.rot.param_gradient(self.x[self.cur])[:len(index)], index)
 
-    def _refine_geometry(self):
-        """step, before the tail: gradient, sum over the ranks (/ size, as the volume gradient), host Adam, new rows for the next stage"""
-        geo = getattr(self.rot, 'geometry', None)
-        if geo is None or not geo.refine:
-            return
-        dense = geo.dense(self.geometry_gradient(), self._step_angles())
-        if self.comm.size > 1:
-            dense = self.comm.allreduce_sum_host(dense) / self.comm.size
-        geo.update(dense)
-        self.rot.prm = geo.prm()
+    def _step_angles(self):
+        return self._angles
 
-    def _refuse_accumulation(self, n_batch_per_update):
-        geo = getattr(self.rot, 'geometry', None)
-        if geo is not None and geo.refine and int(n_batch_per_update) > 1:
-            raise ValueError('refine_geometry moves the geometry at every minibatch: not together with n_batch_per_update > 1')
+    def _rank_mean(self, a):
+        """a host array summed over the ranks and divided by their number (grads /= size, as the volume gradient)"""
+        return self.comm.allreduce_sum_host(a) / self.comm.size if self.comm.size > 1 else a
+
+    def _refine(self, variable, gradient, *where):
+        """step, before the tail, for a variable with a host Adam (rotation.RigidGeometry, positions.ProbePositions) that is being
+        refined: its gradient() at the entries `where` of the minibatch, the mean over the ranks, the variable's Adam.  True: it moved."""
+        if variable is None or not variable.refine:
+            return False
+        variable.update(self._rank_mean(variable.dense(gradient(), *where)))
+        return True
+
+    def _refine_geometry(self):
+        if self._refine(self.rot.geometry, self.geometry_gradient, self._angles):
+            self.rot.prm = self.rot.geometry.prm()           # new rows for the next stage
 
     def regularizer(self, alpha_d=0.0, alpha_b=0.0, gamma=0.0):
         """alpha_d sum|delta| + alpha_b sum|beta| + gamma TV(delta) of the current volume (fullfield.py:109-118), on the device."""
@@ -208,7 +246,7 @@ class _VolumeSolver(object):
 
     # ---- the tail of the step ----------------------------------------------------------------
     def _reduces(self):
-        return self.comm.size > 1 or getattr(self.comm, 'always_reduce', False)
+        return self.comm.size > 1 or self.comm.always_reduce
 
     def slab_bounds(self, n_slabs):
         """x-plane ranges [(x0, nx)] of n_slabs nearly equal slabs of the [X][Z][Y] volume."""
@@ -227,7 +265,7 @@ class _VolumeSolver(object):
         if n_slabs is None:
             n_slabs = int(os.environ.get('BDOF_ALLREDUCE_SLABS', '8'))
         if sharded is None:
-            sharded = getattr(self.comm, 'sharded', False) and os.environ.get('BDOF_SHARDED_ADAM', '1') != '0'
+            sharded = self.comm.sharded and os.environ.get('BDOF_SHARDED_ADAM', '1') != '0'
         n_slabs = max(1, min(int(n_slabs), self.dim_x))
         if sharded:
             n = n_slabs
@@ -239,23 +277,27 @@ class _VolumeSolver(object):
                 sharded = False
         return n_slabs, bool(sharded)
 
-    def _adam_slab(self, i_update, learning_rate, alpha_d, alpha_b, gamma, clip, use_mask, slab, g_scale):
+    def _adam_slab(self, u, slab, g_scale):
         new = 1 - self.cur
-        self.eng.adam_step(self.x[self.cur], self.x[new], self.g, self.m, self.v, self.mask if use_mask else None,
-                           (self.dim_x, self.dim_z, self.dim_y), i_update, learning_rate, g_scale=g_scale,
-                           alpha_d=alpha_d, alpha_b=alpha_b, gamma=gamma, clip=clip, slab=slab)
+        self.eng.adam_step(self.x[self.cur], self.x[new], self.g, self.m, self.v, self.mask if u.use_mask else None,
+                           (self.dim_x, self.dim_z, self.dim_y), u.i_update, u.learning_rate, g_scale=g_scale,
+                           alpha_d=u.alpha_d, alpha_b=u.alpha_b, gamma=u.gamma, clip=u.clip, slab=slab)
 
     def _flip(self):
         self.cur = 1 - self.cur
         self._bind_volume()
 
-    def _whole_volume_guard(self):
-        """adam_update runs Adam on the whole volume with this rank's moments: wrong once a sharded step has left them valid
-        on 1/size of every slab only."""
+    def adam_update(self, i_batch, learning_rate, alpha_d=0.0, alpha_b=0.0, gamma=0.0, clip=True, use_mask=True):
+        """Regulariser + Adam on the gradient in self.g (whole volume, no exchange) with this rank's moments: wrong, and refused,
+        once a sharded step has left them valid on 1/size of every slab only."""
         if self._epoch_plan is not None and self._epoch_plan[1] is not None:
             raise RuntimeError('adam_update() after a sharded step(): the Adam moments of this epoch are sharded over the ranks '
                                '(call reset_moments() first, or keep using step())')
         self._epoch_plan = ('taken', None)
+        self._g_refresh()
+        u = Update(i_batch, learning_rate, alpha_d=alpha_d, alpha_b=alpha_b, gamma=gamma, clip=clip, use_mask=use_mask)
+        self._adam_slab(u, None, 1.0 / self.comm.size)
+        self._flip()
 
     time_tail = False          # True: every _tail is bracketed by stream-ordered time stamps (bdof_timer_mark slots 0 / 1)
 
@@ -265,75 +307,65 @@ class _VolumeSolver(object):
         self.ctx.check(self.ctx.lib.bdof_timer_elapsed(self.ctx.handle, 0, 1, ctypes.byref(ms)))
         return ms.value
 
-    def _tail(self, produce, i_update, learning_rate, alpha_d=0.0, alpha_b=0.0, gamma=0.0, clip=True, use_mask=True,
-              n_slabs=None, sharded=None, flip=True, n_acc=1, one_pass=None):
-        if not self.time_tail:
-            return self._tail_run(produce, i_update, learning_rate, alpha_d, alpha_b, gamma, clip, use_mask, n_slabs, sharded, flip, n_acc,
-                                  one_pass)
-        lib, h = self.ctx.lib, self.ctx.handle
-        self.ctx.check(lib.bdof_timer_mark(h, 0))
-        self._tail_run(produce, i_update, learning_rate, alpha_d, alpha_b, gamma, clip, use_mask, n_slabs, sharded, flip, n_acc, one_pass)
-        self.ctx.check(lib.bdof_timer_mark(h, 1))
-
-    def _tail_run(self, produce, i_update, learning_rate, alpha_d=0.0, alpha_b=0.0, gamma=0.0, clip=True, use_mask=True,
-                  n_slabs=None, sharded=None, flip=True, n_acc=1, one_pass=None):
+    def _tail(self, produce, u, n_slabs=None, sharded=None, flip=True, n_acc=1, one_pass=None):
         """produce(x0, nx): enqueue the kernels that leave this rank's gradient of x-planes [x0, x0+nx) in self.g.
-        Then exchange + regulariser + Adam (+ mask, clip), slab by slab.  g_scale = 1 / (size * n_acc)
+        Then exchange + regulariser + Adam (+ mask, clip) of the Update u, slab by slab.  g_scale = 1 / (size * n_acc)
         (grads /= size, fullfield.py:351; accumulated minibatches are averaged, tensorflow_recon/fullfield.py:424).
-        one_pass(*args, g_scale): what to run in place of produce + Adam when nothing is exchanged (FullfieldSolver._one_pass_tail)."""
+        one_pass(u, g_scale): what to run in place of produce + Adam when nothing is exchanged (FullfieldSolver._one_pass_tail)."""
         comm, ctx = self.comm, self.ctx
+        if self.time_tail:
+            ctx.check(ctx.lib.bdof_timer_mark(ctx.handle, 0))
         g_scale = 1.0 / (comm.size * n_acc)
-        args = (i_update, learning_rate, alpha_d, alpha_b, gamma, clip, use_mask)
         if not self._reduces():
             if one_pass is not None:
-                one_pass(*args, g_scale=g_scale)
+                one_pass(u, g_scale=g_scale)
             else:
                 produce(0, self.dim_x)
-                self._adam_slab(*args, slab=None, g_scale=g_scale)
-            if flip:
-                self._flip()
-            return
-        n_slabs, sharded = self.tail_plan(n_slabs, sharded)
-        # Sharded form: the Adam moments (and, after the reduce-scatter, the gradient) are valid on this rank's 1/size of every
-        # slab only, so the shard layout must not move while the moments live — i.e. until the next reset_moments().  The
-        # all-reduce form keeps them whole on every rank, whatever its slab count.
-        layout = (n_slabs, True) if sharded else None
-        if self._epoch_plan is None:
-            self._epoch_plan = ('taken', layout)
-        elif self._epoch_plan[1] != layout:
-            raise RuntimeError('the exchange plan changed from {} to {} inside an epoch: the Adam moments are sharded by the first one '
-                               '(call reset_moments() first)'.format(self._epoch_plan[1], layout))
-        slabs = self.slab_bounds(n_slabs)
-        self._g_shards = list(slabs) if sharded else None
-        per_x = self.dim_z * self.dim_y * 2                  # floats per x-plane of the gradient / volume
-        size, rank = comm.size, comm.rank
-        tickets, gathers = [None] * len(slabs), []
-        x_new = self.x[1 - self.cur]
+                self._adam_slab(u, None, g_scale)
+        else:
+            n_slabs, sharded = self.tail_plan(n_slabs, sharded)
+            # Sharded form: the Adam moments (and, after the reduce-scatter, the gradient) are valid on this rank's 1/size of every
+            # slab only, so the shard layout must not move while the moments live — i.e. until the next reset_moments().  The
+            # all-reduce form keeps them whole on every rank, whatever its slab count.
+            layout = (n_slabs, True) if sharded else None
+            if self._epoch_plan is None:
+                self._epoch_plan = ('taken', layout)
+            elif self._epoch_plan[1] != layout:
+                raise RuntimeError('the exchange plan changed from {} to {} inside an epoch: the Adam moments are sharded by the first one '
+                                   '(call reset_moments() first)'.format(self._epoch_plan[1], layout))
+            slabs = self.slab_bounds(n_slabs)
+            self._g_shards = list(slabs) if sharded else None
+            per_x = self.dim_z * self.dim_y * 2                  # floats per x-plane of the gradient / volume
+            size, rank = comm.size, comm.rank
+            tickets, gathers = [None] * len(slabs), []
+            x_new = self.x[1 - self.cur]
 
-        def finish(c):
-            x0, nx = slabs[c]
-            comm.wait(ctx, tickets[c])
-            if sharded:
-                w = nx // size
-                self._adam_slab(*args, slab=(x0 + rank * w, w), g_scale=g_scale)
-                gathers.append(comm.start_allgather(ctx, x_new, x0 * per_x, w * per_x))
-            else:
-                self._adam_slab(*args, slab=(x0, nx), g_scale=g_scale)
+            def finish(c):
+                x0, nx = slabs[c]
+                comm.wait(ctx, tickets[c])
+                if sharded:
+                    w = nx // size
+                    self._adam_slab(u, (x0 + rank * w, w), g_scale)
+                    gathers.append(comm.start_allgather(ctx, x_new, x0 * per_x, w * per_x))
+                else:
+                    self._adam_slab(u, (x0, nx), g_scale)
 
-        for c, (x0, nx) in enumerate(slabs):
-            produce(x0, nx)
-            if sharded:
-                tickets[c] = comm.start_reduce_scatter(ctx, self.g, x0 * per_x, (nx // size) * per_x)
-            else:
-                tickets[c] = comm.start_allreduce(ctx, self.g, x0 * per_x, (x0 + nx) * per_x)
-            if c >= self.lookahead:
-                finish(c - self.lookahead)
-        for c in range(max(0, len(slabs) - self.lookahead), len(slabs)):
-            finish(c)
-        for t in gathers:
-            comm.wait(ctx, t)
+            for c, (x0, nx) in enumerate(slabs):
+                produce(x0, nx)
+                if sharded:
+                    tickets[c] = comm.start_reduce_scatter(ctx, self.g, x0 * per_x, (nx // size) * per_x)
+                else:
+                    tickets[c] = comm.start_allreduce(ctx, self.g, x0 * per_x, (x0 + nx) * per_x)
+                if c >= self.lookahead:
+                    finish(c - self.lookahead)
+            for c in range(max(0, len(slabs) - self.lookahead), len(slabs)):
+                finish(c)
+            for t in gathers:
+                comm.wait(ctx, t)
         if flip:
             self._flip()
+        if self.time_tail:
+            ctx.check(ctx.lib.bdof_timer_mark(ctx.handle, 1))
 
     def tune_tail(self, candidates=(1, 8, 16, 32), reps=2):
         """Pick the number of slabs of the pipelined tail by timing it on this machine and process layout (the collective,
@@ -384,18 +416,12 @@ class _VolumeSolver(object):
         the carrier field propagated on the device in float64).
         Probe modes (PtychoSolver with (M, py, px) probes): the arrays are (M, py, px), every mode has its own Adam moments
         (one step counter), the gradient is bdof_probe_grad_modes' and the pupil multiplies every mode."""
-        self.probe = (np.asarray(probe_real, dtype=np.float64) + 1j * np.asarray(probe_imag, dtype=np.float64)) * np.ones((self.eng.ny, self.eng.nx))
-        n_modes = getattr(self, 'n_modes', 0)
-        if self.probe.ndim != (3 if n_modes else 2) or (n_modes and self.probe.shape[0] != n_modes):
-            self.probe = None
+        probe = (np.asarray(probe_real, dtype=np.float64) + 1j * np.asarray(probe_imag, dtype=np.float64)) * np.ones((self.eng.ny, self.eng.nx))
+        self.pvar = None
+        if probe.ndim != (3 if self.n_modes else 2) or (self.n_modes and probe.shape[0] != self.n_modes):
             raise ValueError('enable_probe_optimization: the probe must have the shape the solver was built with ({})'.format(
-                '{} probe modes'.format(n_modes) if n_modes else 'one (Y, X) probe'))
-        self.probe_lr = float(probe_learning_rate)
-        self.pupil = None if pupil_function is None else np.asarray(pupil_function, dtype=np.float64)
-        self.probe_m = np.zeros_like(self.probe)
-        self.probe_v = np.zeros_like(self.probe)
-        self.probe_t = 0
-        self._pacc = 0
+                '{} probe modes'.format(self.n_modes) if self.n_modes else 'one (Y, X) probe'))
+        self.pvar = ProbeVariable(probe, probe_learning_rate, pupil_function)
         self.eng.enable_probe_grad(True)
         # The resident amplitudes were laid out as m - |a0| for the probe in force at set_measurements (residual splitting,
         # MultisliceEngine.meas_layout).  A probe that moves every step would leave that reference behind — every residual biased by
@@ -403,46 +429,30 @@ class _VolumeSolver(object):
         # amplitudes that are already resident are put back to plain m.
         old_ref = self.eng.meas_ref
         self.eng.residual_split = False
-        self._probe_to_engine()
+        self.pvar.to_engine(self.eng)
         if old_ref and self.meas is not None:
             self.ctx.sync()
             self.meas.upload((self.meas.download().astype(np.float64) + old_ref).astype(np.float32))
 
-    def _probe_to_engine(self):
-        """the probe — or, (M, py, px), the probe modes — handed to the engine"""
-        if self.probe.ndim == 3:
-            self.eng.set_probe_modes(self.probe.real, self.probe.imag)
-        else:
-            self.eng.set_probe(self.probe.real, self.probe.imag)
+    def _of_probe(name):
+        return property(lambda self: None if self.pvar is None else getattr(self.pvar, name))
+    probe, probe_m, probe_v, probe_t = _of_probe('probe'), _of_probe('probe_m'), _of_probe('probe_v'), _of_probe('probe_t')
 
     def _probe_collect(self):
         """Add this minibatch's probe gradient to the device accumulator (call after every loss_grad)."""
-        if self.probe is None:
-            return
-        self._pgrad = self.eng.probe_grad(accumulate=self._pacc > 0, to_host=False)
-        self._pacc += 1
+        if self.pvar is not None:
+            self.pvar.collect(self.eng)
 
-    def _probe_apply(self, b1=0.9, b2=0.999, eps=1e-8):
+    def _probe_apply(self):
         """Adam on (probe_real, probe_imag) with the accumulated gradient (mean over accumulated minibatches and ranks)."""
-        if self.probe is None or self._pacc == 0:
+        if self.pvar is None or self.pvar.n_acc == 0:
             return
         self.ctx.sync()
-        g = np.ascontiguousarray(np.swapaxes(self._pgrad.download(), -2, -1)).astype(np.complex128) / self._pacc
-        self._pacc = 0
-        if self.comm.size > 1:
-            g = self.comm.allreduce_sum_host(g) / self.comm.size
-        self.probe_t += 1
-        self.probe_m = b1 * self.probe_m + (1 - b1) * g
-        self.probe_v = b2 * self.probe_v + (1 - b2) * (g.real ** 2 + 1j * g.imag ** 2)
-        mh = self.probe_m / (1 - b1 ** self.probe_t)
-        vh = self.probe_v / (1 - b2 ** self.probe_t)
-        self.probe = self.probe - self.probe_lr * (mh.real / (np.sqrt(vh.real) + eps) + 1j * mh.imag / (np.sqrt(vh.imag) + eps))
-        if self.pupil is not None:
-            self.probe = self.probe * self.pupil
-        self._probe_to_engine()
+        self.pvar.apply(self._rank_mean)
+        self.pvar.to_engine(self.eng)
 
     def get_probe(self):
-        return self.probe.real.copy(), self.probe.imag.copy()
+        return self.pvar.get()
 
     def shrink_wrap(self, thresh=1e-15):
         """mask = mask * (obj_delta > 1e-15)   (cnn_propagator/fullfield.py:365-368, intended behaviour, quirk Q8)."""
@@ -482,17 +492,9 @@ class FullfieldSolver(_VolumeSolver):
         n_batch_per_update > 1 only.  Empty: nothing of this runs."""
         self.n_planes = _check_options(propagator, adjoint64, loss_type, poisson_multiplier, detector_weights, slice_binning, free_prop_cm,
                                        rotation=rotation if rotation in ('bilinear', 'trilinear') else 'nearest', recompute=recompute, detector_kernel=detector_kernel)
-        self.conv = propagator == 'conv'
-        materialised = rotation in rotations.KINDS               # the minibatch's rotated objects are written out every step
-        if adjoint64 not in (None, False, True, 'first'):
-            raise ValueError("adjoint64 must be None, False, True or 'first'")
-        if adjoint64 and materialised and (self.conv or adjoint64 == 'first'):
+        engine64 = self._float64_paths(adjoint64, propagator)
+        if adjoint64 and rotation in rotations.KINDS and (self.conv or adjoint64 == 'first'):
             raise ValueError("the float64 paths (adjoint64='first'; propagator='conv') run with the lookup-table rotation")
-        # 'first': the first minibatch of every epoch through the model's float64 path on the same context (bdof_loss_grad_tf_f64 /
-        # bdof_loss_grad_conv_f64), as PtychoSolver does it; True: every minibatch — the engine's float64 adjoint sweep
-        # (transfer-function model) or the float64 path (real-space model, which has no such sweep)
-        self.f64 = 'first' if adjoint64 == 'first' else (True if (adjoint64 is True and self.conv) else None)
-        adjoint64 = adjoint64 is True and not self.conv
         if probe_real is not None and np.ndim(probe_real) == 3:
             raise ValueError("probe modes ((M, Y, X) probes) are ptychography's: FullfieldSolver takes one (Y, X) probe")
         if rotation not in ('nearest', 'bilinear', 'trilinear'):
@@ -504,27 +506,18 @@ class FullfieldSolver(_VolumeSolver):
         self.n_theta, self.mb = int(n_theta), int(minibatch_size)
         self.comm = comm or PseudoComm()
         self.eng = MultisliceEngine(self.dim_y, self.dim_x, self.dim_z, self.mb, with_grad=True, device=device, stream=stream,
-                                    recompute=recompute, adjoint64=adjoint64, slice_binning=slice_binning)
-        self.ctx = self.eng.ctx
+                                    recompute=recompute, adjoint64=engine64, slice_binning=slice_binning)
         self.eng.set_sweep_fusion(1)        # the fused forward sweep (a ctx of its own starts at 0)
         self.eng.set_adjoint_fusion(True)   # ... and the fused adjoint sweep behind it (MEASUREMENTS.md: the step-time criterion)
-        self.eng.set_loss(loss_type, poisson_multiplier)
-        self.eng.set_physics(energy_ev, psize_cm, free_prop_cm, variant=variant, detector_kernel=detector_kernel)
-        self.eng.set_detector_weights(detector_weights)
-        if self.conv:
-            self.eng.set_conv(energy_ev, psize_cm, kernel_size)
         if probe_real is None:
             probe_real, probe_imag = np.ones((dim_y, dim_x)), np.zeros((dim_y, dim_x))   # 'plane', fullfield.py:276-278
-        self.eng.set_probe(probe_real, probe_imag)
-        if self.f64:
-            self._enable_f64()
-        self.rot.allocate(self.ctx, self.mb)
-        self._init_volume()
+        self._set_up(energy_ev, psize_cm, kernel_size, (loss_type, poisson_multiplier), detector_weights, probe_real, probe_imag,
+                     free_prop_cm=free_prop_cm, variant=variant, detector_kernel=detector_kernel)
+
+    def _batch_buffers(self):
         self.meas_stage = DeviceBuffer(self.ctx, self.mb * self.n_planes * self.dim_x * self.dim_y * 4, np.float32,
                                        (self.mb, self.dim_x, self.dim_y) if self.n_planes == 1 else (self.mb, self.n_planes, self.dim_x, self.dim_y))
         self.angle_buf = DeviceBuffer(self.ctx, self.mb * 4, np.int32, (self.mb,))
-        self._bind_volume()
-        self.rot.attach(self.eng)
 
     def set_measurements(self, prj_abs):
         """|prj| for every angle, (n_theta, Y, X) — with D detector planes (n_theta, D, Y, X) — (loss uses np.abs(this_prj_batch),
@@ -534,19 +527,15 @@ class FullfieldSolver(_VolumeSolver):
         self.meas = DeviceBuffer.from_host(self.ctx, self.eng.meas_layout(prj_abs))
 
     # ---- one Adam iteration ------------------------------------------------------------------
-    def _stage_batch(self, angle_idx):
-        lib, h = self.ctx.lib, self.ctx.handle
+    def _rot_loss_grad(self, angle_idx, f64=False):
+        """Forward + adjoint sweeps of this rank's angles: the gradient w.r.t. the rotated objects stays in the ctx.
+        f64: through the transfer-function model's float64 path on the same context (bdof_loss_grad_tf_f64)."""
         idx = np.asarray(angle_idx, dtype=np.int32)
         assert len(idx) == self.mb
         self.angle_buf.upload(idx)
         # this_prj_batch = prj[this_ind_batch] (fullfield.py:344): one gather launch on the resident stack (an angle's planes are one item)
-        self.ctx.check(lib.bdof_gather_fields(h, self.meas_stage.ptr, self.meas.ptr, self.angle_buf.ptr, self.mb,
-                                              self.n_planes * self.dim_x * self.dim_y * 4))
-
-    def _rot_loss_grad(self, angle_idx, f64=False):
-        """Forward + adjoint sweeps of this rank's angles: the gradient w.r.t. the rotated objects stays in the ctx.
-        f64: through the transfer-function model's float64 path on the same context (bdof_loss_grad_tf_f64)."""
-        self._stage_batch(angle_idx)
+        self.ctx.check(self.ctx.lib.bdof_gather_fields(self.ctx.handle, self.meas_stage.ptr, self.meas.ptr, self.angle_buf.ptr, self.mb,
+                                                       self.n_planes * self.dim_x * self.dim_y * 4))
         self._angles = np.asarray(angle_idx, dtype=np.int64)
         if f64:
             if not self.rot.float64_paths:
@@ -563,9 +552,6 @@ class FullfieldSolver(_VolumeSolver):
     def _produce(self, accumulate=False):
         return lambda x0, nx: self.rot.adjoint(self.angle_buf, self.g, x0, nx, accumulate)
 
-    def _step_angles(self):
-        return getattr(self, '_angles', None)
-
     def loss_and_grad(self, angle_idx, want_loss=True, f64=False):
         """Data-term loss and its gradient w.r.t. the volume for this rank's angles (left in self.g, not reduced).  f64: both
         sweeps through the model's float64 path (a float64 twin of the fused kernels on the same context; the tests hold it to 3e-15 /
@@ -575,23 +561,16 @@ class FullfieldSolver(_VolumeSolver):
         self._produce()(0, self.dim_x)
         return self._get_loss() if want_loss else None
 
-    def adam_update(self, i_batch, learning_rate, alpha_d=0.0, alpha_b=0.0, gamma=0.0, clip=True, use_mask=True):
-        """Regulariser + Adam on the gradient in self.g (whole volume, no exchange)."""
-        self._whole_volume_guard()
-        self._g_refresh()
-        self._adam_slab(i_batch, learning_rate, alpha_d, alpha_b, gamma, clip, use_mask, None, 1.0 / self.comm.size)
-        self._flip()
-
-    def _one_pass_tail(self, i_update, learning_rate, alpha_d, alpha_b, gamma, clip, use_mask, g_scale):
+    def _one_pass_tail(self, u, g_scale):
         """The tail of a step that exchanges nothing, in one pass (bdof_rotation_adjoint_adam): the volume gradient is not written
         (self.g is stale until _g_refresh), and the new volume's modulation table is in the ctx when _flip binds it."""
         lib, h = self.ctx.lib, self.ctx.handle
         new = 1 - self.cur
-        mask = self.mask if use_mask else None
+        mask = self.mask if u.use_mask else None
         self.ctx.check(lib.bdof_rotation_adjoint_adam(h, self.mb, self.angle_buf.ptr, None, 0, self.dim_x * self.dim_z, 0, 1.0,
                                                       self.x[self.cur].ptr, self.x[new].ptr, self.m.ptr, self.v.ptr, _lib._ptr(mask),
-                                                      self.dim_x, self.dim_z, self.dim_y, g_scale, alpha_d, alpha_b, gamma,
-                                                      learning_rate, 0.9, 0.999, 1e-8, int(i_update), int(clip)))
+                                                      self.dim_x, self.dim_z, self.dim_y, g_scale, u.alpha_d, u.alpha_b, u.gamma,
+                                                      u.learning_rate, 0.9, 0.999, 1e-8, int(u.i_update), int(u.clip)))
         self._g_shards = None
         self._g_stale = True
 
@@ -599,7 +578,7 @@ class FullfieldSolver(_VolumeSolver):
         idx = np.arange(self.mb, dtype=np.int32) % self.n_theta
         self.angle_buf.upload(idx)
         self.rot.stage_angles(idx)
-        self._tail(self._produce(), 0, 0.0, n_slabs=n_slabs, sharded=sharded, flip=False)
+        self._tail(self._produce(), Update(0, 0.0), n_slabs=n_slabs, sharded=sharded, flip=False)
 
     def step(self, i_batch, angle_idx, learning_rate, alpha_d=0.0, alpha_b=0.0, gamma=0.0, want_loss=False, n_slabs=None,
              sharded=None, use_mask=True, clip=True, n_batch_per_update=1, last_of_epoch=False):
@@ -608,24 +587,25 @@ class FullfieldSolver(_VolumeSolver):
         n_batch_per_update > 1 (tensorflow_recon/fullfield.py:413-425,512-530): the volume gradient of consecutive
         minibatches is accumulated and applied (averaged) every n-th minibatch or at the last one of the epoch; the Adam
         bias-correction exponent then counts updates, not minibatches."""
-        self._refuse_accumulation(n_batch_per_update)
+        if self.rot.geometry is not None and self.rot.geometry.refine and int(n_batch_per_update) > 1:
+            raise ValueError('refine_geometry moves the geometry at every minibatch: not together with n_batch_per_update > 1')
         self._rot_loss_grad(angle_idx, f64=self.f64 is True or (self.f64 == 'first' and i_batch == 0 and self.probe is None))
         self._probe_collect()
         self._refine_geometry()
         nb = max(1, int(n_batch_per_update))
+        u = Update(i_batch // nb, learning_rate, alpha_d=alpha_d, alpha_b=alpha_b, gamma=gamma, clip=clip, use_mask=use_mask)
         if nb > 1:
             self._g_is_local()
             self._produce(accumulate=self._acc > 0)(0, self.dim_x)
             self._acc += 1
             if self._acc == nb or last_of_epoch:
                 n_acc, self._acc = self._acc, 0
-                self._tail(lambda x0, nx: None, i_batch // nb, learning_rate, alpha_d, alpha_b, gamma, clip, use_mask, n_slabs,
-                           sharded, n_acc=n_acc)
+                self._tail(lambda x0, nx: None, u, n_slabs, sharded, n_acc=n_acc)
                 self._probe_apply()
         else:
             # one rank, a rotation that carries it (the lookup tables): nothing happens between the rotation adjoint and Adam
             one_pass = self._one_pass_tail if not self._reduces() and self.rot.one_pass_tail else None
-            self._tail(self._produce(), i_batch, learning_rate, alpha_d, alpha_b, gamma, clip, use_mask, n_slabs, sharded, one_pass=one_pass)
+            self._tail(self._produce(), u, n_slabs, sharded, one_pass=one_pass)
             self._probe_apply()
         return self._get_loss() if want_loss else None          # the loss of THIS minibatch stays on the device until the next one
 
@@ -683,12 +663,11 @@ class PtychoSolver(_VolumeSolver):
         offsets = probe_positions.check_positions(position_offsets, refine_positions, len(probe_pos), n_theta, propagator=propagator,
                                                   slice_binning=slice_binning, adjoint_precision='float64' if adjoint64 else None)
         self.pos = None if offsets is None else probe_positions.ProbePositions(n_theta, len(probe_pos), offsets, refine_positions, position_learning_rate)
-        self.n_modes = 0
         if np.ndim(probe_real) == 3:
             precision = None if not adjoint64 else 'first-step' if adjoint64 == 'first' else 'float64'
             self.n_modes = probe_modes.check_probe_modes(int(np.shape(probe_real)[0]), propagator=propagator, slice_binning=slice_binning,
                                                          adjoint_precision=precision, engine=engine)
-        self.conv = propagator == 'conv'
+        engine64 = self._float64_paths(adjoint64, propagator)
         self.dim_y, self.dim_x, self.dim_z = [int(s) for s in obj_size]
         self.rot = rotations.choose(rotation, obj_size, n_theta, coord_ls, theta, (axis_tilt, axis_roll, center, rotation_matrices),
                                     materialised=rotations.RotatedCopy, refine=refine_geometry, rate=geometry_learning_rate)
@@ -703,29 +682,11 @@ class PtychoSolver(_VolumeSolver):
             engine = 'resident' if self.py == self.px and self.py in RESIDENT_SIZES and not self.conv and slice_binning == 1 else \
                 'generic' if self.n_modes else 'auto'
         self.eng = MultisliceEngine(self.py, self.px, self.dim_z, self.mb * max(self.n_modes, 1), with_grad=True, device=device, stream=stream,
-                                    engine=engine, adjoint64=adjoint64 is True and not self.conv, slice_binning=slice_binning)
-        self.ctx = self.eng.ctx
-        self.eng.set_loss(loss_type, poisson_multiplier)
-        self.eng.set_physics(energy_ev, psize_cm, 'inf', variant=variant)   # free_prop_cm='inf', ptychography.py:76
-        self.eng.set_detector_weights(detector_weights)
-        if self.conv:
-            self.eng.set_conv(energy_ev, psize_cm, kernel_size)
-        if self.n_modes:
-            self.eng.set_probe_modes(probe_real, probe_imag)
-        else:
-            self.eng.set_probe(probe_real, probe_imag)
-        # adjoint64='first': the FIRST minibatch of every epoch runs through the model's float64 path on the SAME context
-        # (bdof_loss_grad_tf_f64 / bdof_loss_grad_conv_f64: whole sweeps in double, no second engine) — Adam's first step after a
-        # restart is lr g / (|g| + 1e-8), the only one in which a 1e-8 error of the gradient moves a voxel by a fraction of a
-        # whole step; every later step runs on the fast engine.  f64 = 'first' / True says when it runs.
-        self.f64 = None
-        if adjoint64 == 'first' or (self.conv and adjoint64 is True):
-            self._enable_f64()
-            self.f64 = adjoint64
-        elif adjoint64 not in (None, False, True):
-            raise ValueError("adjoint64 must be None, False, True or 'first'")
-        self.rot.allocate(self.ctx, self.mb)
-        self._init_volume()
+                                    engine=engine, adjoint64=engine64, slice_binning=slice_binning)
+        self._set_up(energy_ev, psize_cm, kernel_size, (loss_type, poisson_multiplier), detector_weights, probe_real, probe_imag,
+                     free_prop_cm='inf', variant=variant)                        # ('inf': ptychography.py:76)
+
+    def _batch_buffers(self):
         self.meas_stage = DeviceBuffer(self.ctx, self.mb * self.py * self.px * 4, np.float32, (self.mb, self.py, self.px))
         self.idx_buf = DeviceBuffer(self.ctx, 4 * self.mb * 4, np.int32, (4, self.mb))
         if self.pos is not None:
@@ -733,10 +694,6 @@ class PtychoSolver(_VolumeSolver):
             self.stack = DeviceBuffer(self.ctx, self.mb * self.dim_z * self.px * self.py * 8, np.float32, (self.mb, self.dim_z, self.px, self.py, 2))
             self.origin_buf = DeviceBuffer(self.ctx, self.mb * 16, np.float64, (self.mb, 2))
             self.dpos_buf = DeviceBuffer(self.ctx, self.mb * 16, np.float64, (self.mb, 2))
-        self._bind_volume()
-        self.rot.attach(self.eng)
-        self._last = None
-        self._last_pos = None
 
     def set_measurements(self, prj_abs_all):
         """All diffraction amplitudes |prj| (n_theta, n_pos, py, px) resident on the device (a cfg5-sized dataset is 0.75 GB):
@@ -766,9 +723,9 @@ class PtychoSolver(_VolumeSolver):
             self.meas_stage.upload(self.eng.meas_layout(prj_abs_batch))
         return p, p + 4 * self.mb, p + 8 * self.mb
 
-    def _stack_windows(self, i_theta, pos_idx):
+    def _stack_windows(self, i_theta, pos_idx, for_gradient=True):
         """The windows of positions pos_idx (at most mb) at their fractional origins, cut from the volume under angle i_theta
-        into self.stack and bound as that many already rotated objects."""
+        into self.stack and bound as that many already rotated objects.  for_gradient: a window gradient will belong to them."""
         pos_idx = np.asarray(pos_idx)
         n = len(pos_idx)
         at = self.probe_pos[pos_idx] + self.pos.of(i_theta, pos_idx)
@@ -781,7 +738,7 @@ class PtychoSolver(_VolumeSolver):
         self.ctx.check(self.ctx.lib.bdof_window_stack(self.ctx.handle, self._source[0], self.dim_x, self.dim_y, self._source[1], self.origin_buf.ptr,
                                                       n, self.stack.ptr))
         self.eng.set_volume(self.stack, n * self.dim_z * self.px, self.py, None, 0, 0)
-        self._last_pos = (int(i_theta), pos_idx.copy())
+        self._last_pos = (int(i_theta), pos_idx.copy()) if for_gradient else None
 
     def _win_loss_grad(self, i_theta, pos_idx, prj_abs_batch, use64=False):
         a, xo, yo = self._stage(i_theta, pos_idx, prj_abs_batch)
@@ -793,6 +750,7 @@ class PtychoSolver(_VolumeSolver):
             self.rot.stage(self.eng, self.x[self.cur], [int(i_theta)], 1, self.conv)
             self.eng.loss_grad_device(self.mb, a, xo, yo, self.meas_stage.ptr, conv=self.conv, f64=f64)
         self._last = (int(i_theta), xo, yo)
+        self._angles = np.array([int(i_theta)], dtype=np.int64)
 
     def _produce_all(self):
         i_theta, xo, yo = self._last
@@ -820,28 +778,15 @@ class PtychoSolver(_VolumeSolver):
         self.ctx.sync()
         return self.dpos_buf.download()[:, ::-1].copy()           # (dL/du, dL/dv) = (x, y) -> (y, x)
 
-    def _refine_positions(self):
-        """step, before the tail: gradient, sum over the ranks (/ size, as the volume gradient), host Adam"""
-        if self.pos is None or not self.pos.refine:
-            return
-        dense = self.pos.dense(self.position_gradient(), *self._last_pos)
-        if self.comm.size > 1:
-            dense = self.comm.allreduce_sum_host(dense) / self.comm.size
-        self.pos.update(dense)
-
     def orthogonalize_probe_modes(self):
         """The optimised probe modes mixed into their orthogonal form, descending in power (modes.orthogonalize: a unitary mix, the
         model's intensities do not change).  The probe's Adam moments and step counter start again: they belong to the basis
         that went.  Returns the modes' relative powers."""
         if self.probe is None or self.probe.ndim != 3:
             raise ValueError('orthogonalize_probe_modes(): the solver optimises no probe modes (enable_probe_optimization with (M, py, px) probes)')
-        self.probe = probe_modes.orthogonalize(self.probe)
-        self.probe_m, self.probe_v, self.probe_t = np.zeros_like(self.probe), np.zeros_like(self.probe), 0
-        self._probe_to_engine()
+        self.pvar.restart(probe_modes.orthogonalize(self.probe))
+        self.pvar.to_engine(self.eng)
         return probe_modes.relative_power(self.probe)
-
-    def _step_angles(self):
-        return None if self._last is None else np.array([self._last[0]], dtype=np.int64)
 
     def loss_and_grad(self, i_theta, pos_idx, prj_abs_batch=None, want_loss=True, f64=False):
         """prj_abs_batch: |this_prj_batch| (mb, py, px) for probe positions pos_idx at angle i_theta (None: from the resident
@@ -853,7 +798,7 @@ class PtychoSolver(_VolumeSolver):
         return self._get_loss() if want_loss else None
 
     def _dry_tail(self, n_slabs, sharded):
-        self._tail(lambda x0, nx: None, 0, 0.0, n_slabs=n_slabs, sharded=sharded, flip=False, use_mask=False)
+        self._tail(lambda x0, nx: None, Update(0, 0.0, use_mask=False), n_slabs=n_slabs, sharded=sharded, flip=False)
 
     def step(self, i_batch, i_theta, pos_idx, prj_abs_batch=None, learning_rate=1.0, want_loss=False, n_slabs=None, sharded=None, clip=True):
         """One Adam iteration of ptychography.py:301-310: loss_grad, Allreduce, /size, Adam, clip (no regulariser, no mask).
@@ -863,22 +808,17 @@ class PtychoSolver(_VolumeSolver):
         self._probe_collect()
         self._produce_all()
         self._refine_geometry()          # (after the window adjoint: the rotated-frame gradient is the rotated copy's)
-        self._refine_positions()
-        self._tail(lambda x0, nx: None, i_batch, learning_rate, clip=clip, use_mask=False, n_slabs=n_slabs, sharded=sharded)
+        if self.pos is not None:
+            self._refine(self.pos, self.position_gradient, *self._last_pos)
+        self._tail(lambda x0, nx: None, Update(i_batch, learning_rate, clip=clip, use_mask=False), n_slabs=n_slabs, sharded=sharded)
         self._probe_apply()
         return self._get_loss() if want_loss else None
 
     def forward(self, i_theta, pos_idx):
         pos = self.probe_pos[np.asarray(pos_idx)]
         if self.pos is not None:
-            self._stack_windows(i_theta, pos_idx)
-            self._last_pos = None                    # (no gradient belongs to these windows)
+            self._stack_windows(i_theta, pos_idx, for_gradient=False)
             return self.eng.forward(len(pos))
         self.rot.stage(self.eng, self.x[self.cur], [int(i_theta)], 1, self.conv)
         return self.eng.forward(len(pos), angle_idx=[self.rot.window_angle(i_theta)] * len(pos), xoff=pos[:, 1] - self.half[1],
                                 yoff=pos[:, 0] - self.half[0], conv=self.conv)
-
-    def adam_update(self, i_batch, learning_rate, clip=True):
-        self._whole_volume_guard()
-        self._adam_slab(i_batch, learning_rate, 0.0, 0.0, 0.0, clip, False, None, 1.0 / self.comm.size)
-        self._flip()

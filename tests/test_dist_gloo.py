@@ -157,6 +157,90 @@ def test_solver_tail_plan_without_a_gpu():
     assert sum(nx for _, nx in s.slab_bounds(3)) == 512
 
 
+def _recorded_tail(size, rank, one_pass=False, **plan):
+    """The tail of a step (solver._VolumeSolver._tail) on an object without a device, 16 x-planes of 3 x 5 voxels (30 floats per
+    plane): what it asks of the communicator, the engine's Adam, the producer of the gradient and the rotation, in order."""
+    from beyond_dof_amd.solver import _VolumeSolver, Update
+    events = []
+
+    class Comm(object):
+        sharded, always_reduce = True, False
+
+        def _start(self, kind, buf, lo, n):
+            events.append(('start', kind, buf, lo, n))
+            return '{}{}'.format(kind, sum(e[:2] == ('start', kind) for e in events) - 1)      # the ticket: 'rs0', 'rs1', ...
+
+        def start_allreduce(self, ctx, buf, lo, hi):
+            return self._start('ar', buf, lo, hi)
+
+        def start_reduce_scatter(self, ctx, buf, lo, per):
+            return self._start('rs', buf, lo, per)
+
+        def start_allgather(self, ctx, buf, lo, per):
+            return self._start('ag', buf, lo, per)
+
+        def wait(self, ctx, ticket):
+            events.append(('wait', ticket))
+
+    class Engine(object):
+        def adam_step(self, x_old, x_new, g, m, v, mask, shape_xzy, i_batch, lr, g_scale=1.0, alpha_d=0.0, alpha_b=0.0, gamma=0.0, clip=True, slab=None):
+            assert (x_old, x_new, g, m, v, mask, shape_xzy) == ('x0', 'x1', 'g', 'm', 'v', 'mask', (16, 3, 5))
+            assert (i_batch, lr, alpha_d, alpha_b, gamma, clip) == (7, 0.25, 1e-3, 2e-3, 3e-3, False)
+            events.append(('adam', slab, g_scale))
+
+    class Rotation(object):
+        def bind_volume(self, eng, x):
+            events.append(('bind', x))
+
+    s = _VolumeSolver.__new__(_VolumeSolver)
+    s.comm, s.ctx, s.eng, s.rot = Comm(), object(), Engine(), Rotation()
+    s.comm.size, s.comm.rank = size, rank
+    s.dim_x, s.dim_z, s.dim_y = 16, 3, 5
+    s.x, s.cur, s.g, s.m, s.v, s.mask = ['x0', 'x1'], 0, 'g', 'm', 'v', 'mask'
+    s._plan = s._epoch_plan = s._g_shards = None
+    assert s.lookahead == 2 and not s.time_tail
+    update = Update(7, 0.25, alpha_d=1e-3, alpha_b=2e-3, gamma=3e-3, clip=False, use_mask=True)
+    if one_pass:
+        plan['one_pass'] = lambda u, g_scale: events.append(('one_pass', tuple(u), g_scale))
+    s._tail(lambda x0, nx: events.append(('produce', x0, nx)), update, **plan)
+    assert s.cur == 1
+    return events, s
+
+
+def test_the_tail_keeps_its_schedule():
+    """The order of launches, collectives and waits of the tail, written out by hand: a collective is started right behind the
+    producer of its slab and awaited two slabs later (lookahead), Adam follows the wait, the sharded form's all-gathers are awaited
+    at the end, the new volume is bound last."""
+    # sharded: reduce-scatter of this rank's half of each 4-plane slab (60 floats per rank), Adam on rank 1's two planes of it
+    events, s = _recorded_tail(2, 1, n_slabs=4, sharded=True)
+    assert events == [
+        ('produce', 0, 4), ('start', 'rs', 'g', 0, 60),
+        ('produce', 4, 4), ('start', 'rs', 'g', 120, 60),
+        ('produce', 8, 4), ('start', 'rs', 'g', 240, 60), ('wait', 'rs0'), ('adam', (2, 2), 0.5), ('start', 'ag', 'x1', 0, 60),
+        ('produce', 12, 4), ('start', 'rs', 'g', 360, 60), ('wait', 'rs1'), ('adam', (6, 2), 0.5), ('start', 'ag', 'x1', 120, 60),
+        ('wait', 'rs2'), ('adam', (10, 2), 0.5), ('start', 'ag', 'x1', 240, 60),
+        ('wait', 'rs3'), ('adam', (14, 2), 0.5), ('start', 'ag', 'x1', 360, 60),
+        ('wait', 'ag0'), ('wait', 'ag1'), ('wait', 'ag2'), ('wait', 'ag3'),
+        ('bind', 'x1')]
+    assert s._g_shards == [(0, 4), (4, 4), (8, 4), (12, 4)] and s._epoch_plan == ('taken', (4, True))
+    # all-reduce: floats [lo, hi) of every slab, Adam on the whole slab
+    events, s = _recorded_tail(2, 0, n_slabs=4, sharded=False)
+    assert events == [
+        ('produce', 0, 4), ('start', 'ar', 'g', 0, 120),
+        ('produce', 4, 4), ('start', 'ar', 'g', 120, 240),
+        ('produce', 8, 4), ('start', 'ar', 'g', 240, 360), ('wait', 'ar0'), ('adam', (0, 4), 0.5),
+        ('produce', 12, 4), ('start', 'ar', 'g', 360, 480), ('wait', 'ar1'), ('adam', (4, 4), 0.5),
+        ('wait', 'ar2'), ('adam', (8, 4), 0.5),
+        ('wait', 'ar3'), ('adam', (12, 4), 0.5),
+        ('bind', 'x1')]
+    assert s._g_shards is None and s._epoch_plan == ('taken', None)
+    # one rank: nothing is exchanged, whatever plan is asked for; accumulated minibatches are averaged
+    events, s = _recorded_tail(1, 0, n_slabs=4, sharded=True, n_acc=4)
+    assert events == [('produce', 0, 16), ('adam', None, 0.25), ('bind', 'x1')] and s._epoch_plan is None
+    events, s = _recorded_tail(1, 0, one_pass=True)
+    assert events == [('one_pass', (7, 0.25, 1e-3, 2e-3, 3e-3, False, True), 1.0), ('bind', 'x1')]
+
+
 def test_control_plane_messages_are_parsed_not_executed(tmp_path):
     """The rendezvous socket carries None / bytes / numpy arrays / JSON values in a typed encoding (no pickle), lives in a
     directory only this user can enter, and both ends check the peer's uid (round-2 advice)."""

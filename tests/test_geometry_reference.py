@@ -176,6 +176,69 @@ def test_two_ranks_hold_the_same_geometry_after_the_sum():
     assert np.isclose(va['center'], 6.0 - 0.05, rtol=0, atol=1e-9) and np.isclose(a.m['center'], 0.1 * 1.0)
 
 
+def _dense_before_hostopt(self, grad, index):
+    """RigidGeometry.dense as it stood before hostopt.pack, verbatim"""
+    parts = []
+    for k in self.refine:
+        full = np.zeros_like(self.value[k])
+        if full.ndim:
+            np.add.at(full, np.asarray(index), grad[k])
+        else:
+            full += grad[k]
+        parts.append(full.reshape(-1))
+    seen = np.zeros(self.n_theta)
+    seen[np.asarray(index)] = 1.
+    return np.concatenate(parts + [seen])
+
+
+def _update_before_hostopt(self, dense, b1=0.9, b2=0.999, eps=1e-8):
+    """RigidGeometry.update as it stood before hostopt.MaskedAdam, verbatim"""
+    seen, at = dense[-self.n_theta:] > 0, 0
+    for k in self.refine:
+        g = dense[at:at + self.value[k].size].reshape(self.value[k].shape)
+        at += self.value[k].size
+        move = np.ones(self.value[k].shape, dtype=bool) if self.value[k].ndim == 0 else (seen if g.ndim == 1 else np.repeat(seen[:, None], 2, axis=1))
+        self.t[k] = self.t[k] + move
+        self.m[k] = np.where(move, b1 * self.m[k] + (1 - b1) * g, self.m[k])
+        self.v[k] = np.where(move, b2 * self.v[k] + (1 - b2) * g * g, self.v[k])
+        t = np.maximum(self.t[k], 1)
+        step = self.rate[k] * (self.m[k] / (1 - b1 ** t)) / (np.sqrt(self.v[k] / (1 - b2 ** t)) + eps)
+        self.value[k] = np.where(move, self.value[k] - step, self.value[k])
+
+
+def test_masked_adam_has_the_bits_of_the_update_it_replaced():
+    """all five names — scalars, (n,) and (n, 2), each at its own rate — over six steps of random float64 gradients: angle 4 is
+    never listed, step 1 lists angle 3 twice, step 2 lists nothing (the scalars still move), steps 3 and 4 stand for a sum over two
+    ranks (/ 2).  Value, m, v and t are the same bits after every step, and so is the vector the ranks add."""
+    import types
+    from beyond_dof_amd import hostopt
+    rng = np.random.default_rng(11)
+    n, names = 5, util.GEOMETRY_NAMES
+    assert set(names) == {'center', 'axis_tilt', 'axis_roll', 'theta', 'shifts'}
+    theta = rng.uniform(-3, 3, size=n)
+    geo = rotation.RigidGeometry((16, 12, 10), theta, 0.1, -0.02, 5.25, refine=names, rate=0.05)
+    assert len({geo.rate[k] for k in ('center', 'theta')}) == 2 and all(isinstance(o, hostopt.MaskedAdam) for o in geo.opt.values())
+    old = types.SimpleNamespace(refine=names, n_theta=n, rate=dict(geo.rate), value=geo.values(), m={k: np.zeros_like(geo.value[k]) for k in names},
+                                v={k: np.zeros_like(geo.value[k]) for k in names}, t={k: np.zeros(geo.value[k].shape, dtype=np.int64) for k in names})
+    listed = [[1, 3], [3, 3], [], [0, 1, 3], [2], [1, 0]]
+    for step, index in enumerate(listed):
+        index = np.array(index, dtype=np.int64)
+        grad = dict(center=rng.normal(), axis_tilt=rng.normal(), axis_roll=rng.normal(), theta=rng.normal(size=len(index)),
+                    shifts=rng.normal(size=(len(index), 2)))
+        dense = _dense_before_hostopt(old, grad, index)
+        assert np.array_equal(geo.dense(grad, index), dense)
+        if step in (3, 4):
+            dense = (dense + _dense_before_hostopt(old, {k: 3 * g for k, g in grad.items()}, index)) / 2
+        _update_before_hostopt(old, dense)
+        geo.update(dense)
+        for k in names:
+            assert geo.value[k].shape == old.value[k].shape and geo.value[k].dtype == np.float64
+            assert np.array_equal(geo.value[k], old.value[k]) and np.array_equal(geo.m[k], old.m[k]), (step, k)
+            assert np.array_equal(geo.v[k], old.v[k]) and np.array_equal(geo.t[k], old.t[k]), (step, k)
+    assert list(geo.t['theta']) == [2, 3, 1, 3, 0] and geo.t['center'] == 6 and np.array_equal(geo.value['theta'][4], theta[4])
+    assert np.array_equal(geo.t['shifts'], np.repeat(geo.t['theta'][:, None], 2, axis=1))
+
+
 # ---- where the solver-level bounds come from ---------------------------------------------------------------------------------------------
 def test_where_the_geometry_gradient_bound_comes_from():
     """gradient_cases.bound_rule on the float32 / complex64 restatement of dL/d(M | t) of the composed 64^3 case, relative to every

@@ -3,6 +3,7 @@ captured from the reference and against the oracle.  No GPU needed."""
 import os
 
 import numpy as np
+import pytest
 
 from beyond_dof_amd import util
 from beyond_dof_amd.comm import minibatch_schedule, PseudoComm
@@ -384,3 +385,81 @@ def test_engine_host_state_is_declared_and_the_loss_call_is_single():
     assert sorted(calls) == ['bdof_loss_grad', 'bdof_loss_grad_conv', 'bdof_loss_grad_conv_f64', 'bdof_loss_grad_tf_f64']
     from beyond_dof_amd.engine import MultisliceEngine
     assert callable(MultisliceEngine._reset_host_state) and callable(MultisliceEngine.loss_grad_device)
+
+
+def _probe_apply_before_hostopt(self, b1=0.9, b2=0.999, eps=1e-8):
+    """_VolumeSolver._probe_apply as it stood before hostopt.ProbeVariable, verbatim"""
+    if self.probe is None or self._pacc == 0:
+        return
+    self.ctx.sync()
+    g = np.ascontiguousarray(np.swapaxes(self._pgrad.download(), -2, -1)).astype(np.complex128) / self._pacc
+    self._pacc = 0
+    if self.comm.size > 1:
+        g = self.comm.allreduce_sum_host(g) / self.comm.size
+    self.probe_t += 1
+    self.probe_m = b1 * self.probe_m + (1 - b1) * g
+    self.probe_v = b2 * self.probe_v + (1 - b2) * (g.real ** 2 + 1j * g.imag ** 2)
+    mh = self.probe_m / (1 - b1 ** self.probe_t)
+    vh = self.probe_v / (1 - b2 ** self.probe_t)
+    self.probe = self.probe - self.probe_lr * (mh.real / (np.sqrt(vh.real) + eps) + 1j * mh.imag / (np.sqrt(vh.imag) + eps))
+    if self.pupil is not None:
+        self.probe = self.probe * self.pupil
+    self._probe_to_engine()
+
+
+@pytest.mark.parametrize('pupil', [False, True], ids=['no_pupil', 'pupil'])
+@pytest.mark.parametrize('shape', [(8, 8), (3, 8, 8)], ids=['probe', 'modes'])
+def test_probe_variable_has_the_bits_of_the_update_it_replaced(shape, pupil):
+    """hostopt.ProbeVariable behind the solver's _probe_collect / _probe_apply, on an object without a device: four steps of two
+    accumulated minibatches each, the other of two ranks' gradients added by a stand-in communicator.  probe, probe_m, probe_v,
+    probe_t and what the engine is handed: the same bits as the complex Adam that stood in the solver."""
+    import types
+    from beyond_dof_amd.hostopt import ProbeVariable
+    from beyond_dof_amd.solver import _VolumeSolver
+    rng = np.random.default_rng(21)
+    cplx = lambda s: rng.normal(size=s) + 1j * rng.normal(size=s)
+    handed = []
+
+    class Comm(object):
+        size, other = 2, None
+
+        def allreduce_sum_host(self, a):
+            return a + self.other
+
+    class Engine(object):          # the device accumulator of the probe gradient, [x][y] per plane, complex64
+        acc = None
+
+        def probe_grad(self, accumulate, to_host):
+            assert not to_host
+            g = cplx(shape).astype(np.complex64)
+            self.acc = self.acc + g if accumulate else g
+            return types.SimpleNamespace(download=lambda: self.acc.copy())
+
+        def set_probe(self, re, im):
+            handed.append(('probe', re + 1j * im))
+
+        def set_probe_modes(self, re, im):
+            handed.append(('modes', re + 1j * im))
+
+    start = cplx(shape)
+    pupil = (rng.uniform(size=(8, 8)) > 0.3).astype(np.float64) if pupil else None
+    comm, ctx = Comm(), types.SimpleNamespace(sync=lambda: None)
+    s = _VolumeSolver.__new__(_VolumeSolver)
+    s.comm, s.ctx, s.eng, s.pvar = comm, ctx, Engine(), ProbeVariable(start.copy(), 2e-3, pupil)
+    old = types.SimpleNamespace(comm=comm, ctx=ctx, probe=start.copy(), probe_lr=2e-3, pupil=pupil, probe_m=np.zeros_like(start),
+                                probe_v=np.zeros_like(start), probe_t=0, _probe_to_engine=lambda: None)
+    s._probe_apply()                                    # nothing collected: nothing moves
+    assert s.probe_t == 0 and np.array_equal(s.probe, start) and not handed
+    for step in range(4):
+        s._probe_collect()
+        s._probe_collect()
+        old._pgrad, old._pacc = types.SimpleNamespace(download=lambda: s.eng.acc.copy()), 2
+        comm.other = cplx(shape)
+        _probe_apply_before_hostopt(old)
+        s._probe_apply()
+        assert s.pvar.n_acc == 0 and s.probe_t == old.probe_t == step + 1
+        assert np.array_equal(s.probe, old.probe) and np.array_equal(s.probe_m, old.probe_m) and np.array_equal(s.probe_v, old.probe_v), step
+        assert handed[-1][0] == ('modes' if len(shape) == 3 else 'probe') and np.array_equal(handed[-1][1], old.probe) and len(handed) == step + 1
+    assert all(np.array_equal(a, b) for a, b in zip(s.get_probe(), (old.probe.real, old.probe.imag)))
+    if pupil is not None:
+        assert not np.any(s.probe[..., pupil == 0]) and np.any(s.probe_m[..., pupil == 0])

@@ -111,6 +111,66 @@ def test_shared_sums_over_angles_and_moves_every_angle():
     assert np.allclose(step[:, 1], [0.1, -0.1], rtol=1e-6) and np.allclose(step[:, 2], [-0.1, 0.1], rtol=1e-6) and not np.any(step[:, [0, 3]])
 
 
+def _dense_before_hostopt(self, grad, i_theta, pos_idx):
+    """ProbePositions.dense as it stood before hostopt.pack, verbatim"""
+    full, seen = np.zeros(self.m.shape), np.zeros(self.m.shape[:-1])
+    at = (np.asarray(pos_idx),) if self.mode == 'shared' else (np.full(len(pos_idx), int(i_theta)), np.asarray(pos_idx))
+    np.add.at(full, at, np.asarray(grad, dtype=np.float64))
+    seen[at] = 1.
+    return np.concatenate([full.reshape(-1), seen.reshape(-1)])
+
+
+def _split_before_hostopt(self, dense):
+    n = self.m.size
+    return dense[:n].reshape(self.m.shape), dense[n:].reshape(self.m.shape[:-1]) > 0
+
+
+def _update_before_hostopt(self, dense, b1=0.9, b2=0.999, eps=1e-8):
+    """ProbePositions.update as it stood before hostopt.MaskedAdam, verbatim"""
+    g, seen = _split_before_hostopt(self, dense)
+    move = np.repeat(seen[..., None], 2, axis=-1)
+    self.t = self.t + move
+    self.m = np.where(move, b1 * self.m + (1 - b1) * g, self.m)
+    self.v = np.where(move, b2 * self.v + (1 - b2) * g * g, self.v)
+    t = np.maximum(self.t, 1)
+    step = np.where(move, self.rate * (self.m / (1 - b1 ** t)) / (np.sqrt(self.v / (1 - b2 ** t)) + eps), 0.)
+    self.offset = self.offset - step
+
+
+@pytest.mark.parametrize('mode', ['shared', 'per_angle'])
+def test_masked_adam_has_the_bits_of_the_update_it_replaced(mode):
+    """5 angles, 6 positions, six steps of random float64 gradients: position 5 is never listed, step 1 lists position 4 twice,
+    step 2 lists nothing, steps 3 and 4 stand for a sum over two ranks (/ 2) that list different angles.  'shared' holds (n_pos, 2)
+    entries against offsets (n_theta, n_pos, 2).  Offsets, m, v, t and the vector the ranks add: the same bits after every step."""
+    import types
+    from beyond_dof_amd import hostopt
+    from beyond_dof_amd.positions import ProbePositions
+    rng = np.random.default_rng(12)
+    n_theta, n_pos = 5, 6
+    start = rng.uniform(-0.9, 0.9, size=(n_theta, n_pos, 2))
+    p = ProbePositions(n_theta, n_pos, start, mode, rate=0.07)
+    shape = (n_pos, 2) if mode == 'shared' else (n_theta, n_pos, 2)
+    assert isinstance(p.opt, hostopt.MaskedAdam) and p.m.shape == shape
+    old = types.SimpleNamespace(mode=mode, rate=0.07, offset=start.copy(), m=np.zeros(shape), v=np.zeros(shape), t=np.zeros(shape, dtype=np.int64))
+    listed = [(1, [0, 3]), (2, [4, 4]), (0, []), (1, [0, 1, 2]), (4, [3]), (2, [4, 0])]
+    for step, (i_theta, pos_idx) in enumerate(listed):
+        pos_idx = np.array(pos_idx, dtype=np.int64)
+        grad = rng.normal(size=(len(pos_idx), 2))
+        dense = _dense_before_hostopt(old, grad, i_theta, pos_idx)
+        assert np.array_equal(p.dense(grad, i_theta, pos_idx), dense)
+        if step in (3, 4):
+            dense = (dense + _dense_before_hostopt(old, rng.normal(size=(2, 2)), 3, [2, 1 if step == 3 else 0])) / 2
+        for a, b in zip(p.split(dense), _split_before_hostopt(old, dense)):
+            assert np.array_equal(a, b)
+        _update_before_hostopt(old, dense)
+        p.update(dense)
+        assert p.values().shape == (n_theta, n_pos, 2) and p.values().dtype == np.float64
+        assert np.array_equal(p.values(), old.offset) and np.array_equal(p.m, old.m) and np.array_equal(p.v, old.v), step
+        assert np.array_equal(p.t, old.t) and p.t.dtype == np.int64, step
+    # steps that listed each position (under 'per_angle' summed over the angles, of which steps 3 and 4 list two)
+    assert list(p.t[..., 0]) == [4, 1, 2, 2, 2, 0] if mode == 'shared' else list(p.t[..., 0].sum(axis=0)) == [4, 2, 3, 2, 2, 0]
+
+
 def test_dense_vector_round_trip_and_level_units():
     from beyond_dof_amd import positions
     p = positions.ProbePositions(2, 3, None, 'per_angle')
