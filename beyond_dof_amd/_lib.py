@@ -119,6 +119,10 @@ _SIGNATURES = {
                                    + [ctypes.c_float] * 8 + [ctypes.c_int, ctypes.c_int]),
     'bdof_regularizer_value': (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_double)]),
     'bdof_shell_correlation': (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_double)]),
+    'bdof_ctf_retrieve': (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_double, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp]),
+    'bdof_backproject': (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int, _vp, _vp, ctypes.c_int, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                        ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_float]),
+    'bdof_volume_clip_mask': (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_size_t]),
     'bdof_mask_shrink': (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_size_t, ctypes.c_float]),
     'bdof_gather_fields': (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_int, ctypes.c_size_t]),
     'bdof_set_streams': (ctypes.c_int, [_vp, ctypes.c_int]),

@@ -23,6 +23,7 @@
 #include "bdof_rigid.h"
 #include "bdof_windows.h"
 #include "bdof_shells.h"
+#include "bdof_fbp.h"
 #include <rocfft/rocfft.h>
 #include <map>
 #include <optional>
@@ -144,6 +145,7 @@ struct Workspace {
     std::map<std::array<int, 3>, PlanPair> vol_plans;
     DevBuf<double2> shell_a, shell_b;
     DevBuf<double> shell_part;
+    DevBuf<double2> fbp_work;                    // bdof_ctf_retrieve (bdof_fbp.h): [D][B][NX][NY] complex128 contrast planes, grown on demand
     FftExec fft;                                 // of the ctx's stream
     // float64 adjoint sweep (BDOF_CFG_ADJOINT64; generic engine)
     bool have_h64 = false;
@@ -3831,6 +3833,52 @@ int bdof_shell_correlation(bdof_ctx* c, const void* vol_a, const void* vol_b, in
         std::copy(host.begin(), host.begin() + nent, out + (size_t)s_lo * BDOF_SHELL_TERMS);
     }
     return 0;
+}
+
+// ---- analytic starting volume (bdof_fbp.h) ----------------------------------------------------------------------------------------
+int bdof_ctf_retrieve(bdof_ctx* c, const void* meas, const void* wgt, double a0_sq, const void* filters, int B, int D, int NX, int NY, void* q) {
+    const char* who = "bdof_ctf_retrieve";
+    if (!c || !meas || !filters || !q || B < 1 || NX < 1 || NY < 1) return BDOF_ERR_ARG;
+    if (D < 1 || D > BDOF_MAX_PLANES) return fail(c, BDOF_ERR_ARG, std::string(who) + ": D outside [1, BDOF_MAX_PLANES]");
+    if (!(a0_sq > 0.0) || !std::isfinite(a0_sq)) return fail(c, BDOF_ERR_ARG, std::string(who) + ": |a0|^2 must be finite and > 0");
+    if (NX > 4096) return fail(c, BDOF_ERR_SIZE, std::string(who) + ": NX <= 4096 (the ramp kernel's tap table and column block share LDS)");
+    if ((long long)B * D * NX * NY > 0x7fffffffLL) return fail(c, BDOF_ERR_SIZE, std::string(who) + ": B * D * NX * NY must be below 2^31");
+    HIPC(c, hipSetDevice(c->device));
+    const size_t plane = (size_t)NX * NY, n = (size_t)B * D * plane;
+    if (c->fbp_work.size() < n) {
+        HIPC(c, hipStreamSynchronize(c->stream));
+        HIPC(c, c->fbp_work.alloc(n));
+    }
+    double2* work = c->fbp_work;
+    hipLaunchKernelGGL(k_fbp_contrast, dim3(g_elem_grid(c, n)), dim3(256), 0, c->stream, (const float*)meas, (const float*)wgt, a0_sq, work, B, D, plane);
+    for (int d = 0; d < D; ++d)
+        if (int r = free_step(c, c->fft, c->stream, work + (size_t)d * B * plane, B, NX, NY, (const double2*)filters + (size_t)d * plane, H_KXKY, 0, true)) return r;
+    const dim3 grid((NY + 63) / 64, (NX + FBP_RAMP_TILE - 1) / FBP_RAMP_TILE, B);
+    hipLaunchKernelGGL(k_fbp_ramp, grid, dim3(256), ((size_t)NX + FBP_RAMP_TILE * 64) * sizeof(double), c->stream, (const double2*)work, (float*)q, B, D, NX, NY);
+    return launched(c);
+}
+
+int bdof_backproject(bdof_ctx* c, const void* q, int NXd, int NYd, const double* prm, const float* w, int B, void* vol, int NXv, int NZv, int NYv,
+                     int row0, int n_rows, int accumulate, float scale_delta, float scale_beta) {
+    const char* who = "bdof_backproject";
+    if (!c || !q || !prm || !w || !vol || B < 1) return BDOF_ERR_ARG;
+    if (NXd < 1 || NYd < 1 || NXv < 1 || NZv < 1 || NYv < 1) return fail(c, BDOF_ERR_ARG, std::string(who) + ": bad shape");
+    if ((long long)NXv * NZv * NYv > 0x7fffffffLL || (long long)NXd * NYd > 0x7fffffffLL)
+        return fail(c, BDOF_ERR_SIZE, std::string(who) + ": NX * NZ * NY of the volume and NX * NY of a frame must be below 2^31");
+    if (row0 < 0 || n_rows < 0 || (long long)row0 + n_rows > (long long)NXv * NZv) return fail(c, BDOF_ERR_ARG, std::string(who) + ": destination rows outside the volume");
+    if (n_rows == 0) return 0;
+    HIPC(c, hipSetDevice(c->device));
+    FbpBackArgs a{(const float*)q, prm, w, (float2*)vol, B, NXd, NYd, NXv, NZv, NYv, row0, row0 + n_rows, accumulate, scale_delta, scale_beta};
+    hipLaunchKernelGGL(k_fbp_backproject, dim3(std::min((n_rows + 3) / 4, c->ncu * 16)), dim3(256), 0, c->stream, a);
+    return launched(c);
+}
+
+int bdof_volume_clip_mask(bdof_ctx* c, void* vol, const float* mask, size_t n) {
+    if (!c || !vol) return BDOF_ERR_ARG;
+    if (n == 0) return 0;
+    HIPC(c, hipSetDevice(c->device));
+    hipLaunchKernelGGL(k_fbp_clip_mask, dim3(g_elem_grid(c, n)), dim3(256), 0, c->stream, (float2*)vol, mask, n);
+    return launched(c);
 }
 
 void* bdof_stream(bdof_ctx* c) { return c ? (void*)c->stream : nullptr; }

@@ -316,6 +316,10 @@ class MultisliceEngine(object):
         probe = (np.asarray(pr) + 1j * np.asarray(pi)) * np.ones((self.ny, self.nx))
         return probe.astype(np.complex64) if round_c64 else probe
 
+    def probe_arrays(self):
+        """(real, imag) of the probe in force, as set_probe was given them; None before any set_probe"""
+        return None if self._probe_args is None else tuple(np.array(a, copy=True) for a in self._probe_args)
+
     def _probe_stack(self, probe_c64):
         """The probe propagated through free space to the entrance of every slice and to the detector, in float64 on the
         host (np_funcs.py:42-61 without an object) — the carrier field of bdof_set_probe_stack (include/bdof.h)."""

@@ -20,9 +20,9 @@ import time
 
 import numpy as np
 
-from . import h5io, resolution, tiffio, util
+from . import analytic, h5io, resolution, tiffio, util
 from .comm import get_comm, minibatch_schedule
-from .misc import create_summary, SUMMARY_PRESET_FF, SUMMARY_GEOMETRY
+from .misc import create_summary, SUMMARY_PRESET_FF, SUMMARY_GEOMETRY, SUMMARY_ANALYTIC
 from .engine import check_model_options, read_detector_weights
 from .rotation import check_refine
 from .solver import FullfieldSolver
@@ -63,10 +63,29 @@ def reconstruct_fullfield(fname, theta_st=0, theta_end=PI, n_epochs='auto', crit
                           dynamic_rate=True, probe_type='plane', probe_initial=None, probe_learning_rate=1e-3,
                           pupil_function=None, theta_downsample=None, forward_algorithm='fresnel', random_theta=True,
                           object_type='normal', kernel_size=17, debug=False, loss_type='lsq', poisson_multiplier=2e6, slice_binning=1,
-                          detector_weights=None, fsc_reference=None, fsc_threshold='half-bit', **kwargs):
+                          detector_weights=None, fsc_reference=None, fsc_threshold='half-bit', delta_beta_ratio=10.,
+                          ctf_regularization=1e-2, write_support_mask=None, **kwargs):
     """Reconstruct a beyond-depth-of-focus object from full-field projections (see the module docstring and
-    cnn_propagator/fullfield.py:28-77 for the parameters).  Returns (obj_delta, obj_beta) of the finest level."""
+    cnn_propagator/fullfield.py:28-77 for the parameters).  Returns (obj_delta, obj_beta) of the finest level.
+    initial_guess='ctf-fbp': the first (coarsest) multiscale level starts from the analytic volume of
+    FullfieldSolver.analytic_volume — CTF retrieval of all detector planes for a homogeneous object delta = delta_beta_ratio *
+    beta, regularised by ctf_regularization, and a filtered back-projection through the level's own rotation — formed from that
+    level's strided data with its voxel size; summary.txt gets the lines initial_guess, delta_beta_ratio and ctf_regularization.
+    write_support_mask=threshold: rank 0 also writes analytic.support_mask(delta, threshold) of that start, brought to the full
+    resolution, as <save_path>/fin_sup_mask/mask_*.tiff — after the last level and before the closing barrier, so no level of this
+    run reads it (a mask that was there serves this run and is then replaced): it is for the NEXT run.  Any other string raises."""
     t_zero = time.time()
+    analytic_start = isinstance(initial_guess, str)
+    if analytic_start and initial_guess != 'ctf-fbp':
+        raise ValueError("initial_guess takes None, the arrays [delta, beta] or 'ctf-fbp', not {!r}".format(initial_guess))
+    if write_support_mask is not None:           # on every rank, before anything runs: rank 0 alone writes it, in front of a barrier
+        if not analytic_start:
+            raise ValueError("write_support_mask is formed from the analytic start: initial_guess='ctf-fbp'")
+        if isinstance(write_support_mask, (str, bool)) or np.ndim(write_support_mask) != 0 or not np.isfinite(write_support_mask) \
+                or write_support_mask < 0:
+            raise ValueError('write_support_mask is a threshold on delta: one finite number >= 0, not {!r}'.format(write_support_mask))
+        if not os.path.isdir(save_path) or not os.access(save_path, os.W_OK | os.X_OK):
+            raise ValueError('write_support_mask: save_path {!r} is not a directory this run can write to'.format(save_path))
     comm = kwargs.get('comm') or get_comm()
     size, rank = comm.size, comm.rank
     seed = kwargs.get('seed', int(time.time() / 60))
@@ -100,6 +119,10 @@ def reconstruct_fullfield(fname, theta_st=0, theta_end=PI, n_epochs='auto', crit
     # gradient accumulation over n_batch_per_update minibatches exists only in the TF twin (tensorflow_recon/fullfield.py:
     # 413-425); the cnn variant accepts the keyword and ignores it (default 5!), so it is opt-in here
     accumulate = bool(kwargs.get('accumulate_gradients', False))
+    if analytic_start:                           # the host-side refusals, before the file is read (the probe's when the solver has it)
+        analytic.check_analytic(propagator, None, None, delta_beta_ratio, ctf_regularization, object_type, free_prop_cm)
+        if probe_type not in ('plane', 'fixed', 'optimizable'):
+            raise ValueError("initial_guess='ctf-fbp' assumes a plane-wave probe: not with probe_type={!r}".format(probe_type))
     # 'nearest': the cnn variant's lookup tables over linspace(0, 2 pi) (quirk Q5); 'bilinear': the TF twin's tf_rotate with the true
     # angles theta = -linspace(theta_st, theta_end) (tensorflow_recon/fullfield.py:96,216); 'trilinear': a rigid map per angle
     # (FullfieldSolver) with the same theta and the geometry keywords of util.RotationKeywords
@@ -156,7 +179,7 @@ def reconstruct_fullfield(fname, theta_st=0, theta_end=PI, n_epochs='auto', crit
         fsc_reference = resolution.read_reference(fsc_reference, list(prj_0.shape[-2:]) + [final_mask.shape[-1] if final_mask is not None else prj_0.shape[-1]])
         del final_mask
 
-    obj_delta = obj_beta = None
+    obj_delta = obj_beta = support_from = None
     first_level = True
     for ds_level in range(multiscale_level - 1, -1, -1):
         ds_level = 2 ** ds_level
@@ -170,6 +193,7 @@ def reconstruct_fullfield(fname, theta_st=0, theta_end=PI, n_epochs='auto', crit
             n_epochs_mask_release = np.inf
 
         mask = _read_mask(save_path, prj_0.shape[-2])
+        full_z = mask.shape[-1] if mask is not None else prj_0.shape[-1]      # the depth at full resolution
         if mask is not None and ds_level > 1:
             mask = mask[::ds_level, ::ds_level, ::ds_level]
         dim_z = mask.shape[-1] if mask is not None else dim_x
@@ -178,7 +202,10 @@ def reconstruct_fullfield(fname, theta_st=0, theta_end=PI, n_epochs='auto', crit
 
         np.random.seed(seed)          # same seed on every rank (fullfield.py:242-245)
         if first_level:
-            if initial_guess is None:
+            if analytic_start:
+                print_flush('Initializing with CTF retrieval and filtered back-projection.', 0, rank)
+                obj_delta = obj_beta = np.zeros([dim_y, dim_x, dim_z])        # until the solver, which forms it, exists
+            elif initial_guess is None:
                 print_flush('Initializing with Gaussian random.', 0, rank)
                 obj_delta = np.random.normal(size=[dim_y, dim_x, dim_z], loc=8.7e-7, scale=1e-7)
                 obj_beta = np.random.normal(size=[dim_y, dim_x, dim_z], loc=5.1e-8, scale=1e-8)
@@ -234,14 +261,22 @@ def reconstruct_fullfield(fname, theta_st=0, theta_end=PI, n_epochs='auto', crit
         solver.set_volume(obj_delta, obj_beta)
         solver.set_mask(mask)
         solver.set_measurements(np.abs(prj))
+        if analytic_start and first_level:
+            solver.analytic_volume(np.abs(prj), delta_beta_ratio, ctf_regularization, object_type)
+            if write_support_mask is not None and rank == 0:
+                coarse = solver.get_volume()[0]
+                for axis in range(3):            # the level's voxels are every ds_level-th of the full resolution's: repeated back
+                    coarse = np.repeat(coarse, ds_level, axis=axis)
+                support_from = coarse[:prj_0.shape[-2], :prj_0.shape[-1], :full_z]      # written after the LAST level: every level of this run reads the mask that was there
         solver.tune_tail()                       # N ranks: slab count of the exchange + Adam pipeline, by measurement; step() uses it
         if probe_type == 'optimizable':          # the probe is a variable too (tensorflow_recon/fullfield.py:311-327,442-455)
             solver.enable_probe_optimization(probe_real, probe_imag, probe_learning_rate, pupil_function)
 
         print_flush('Optimizer started.', 0, rank)
         if rank == 0:
-            if trilinear:                        # the geometry this level ran with, behind the preset's lines
-                create_summary(output_folder, dict(locals(), **geo.summary()), var_list=SUMMARY_PRESET_FF + SUMMARY_GEOMETRY)
+            lines = SUMMARY_PRESET_FF + (SUMMARY_GEOMETRY if trilinear else []) + (SUMMARY_ANALYTIC if analytic_start else [])
+            if lines != SUMMARY_PRESET_FF:       # the geometry this level ran with and the analytic start, behind the preset's lines
+                create_summary(output_folder, dict(locals(), **(geo.summary() if trilinear else {})), var_list=lines)
             else:
                 create_summary(output_folder, locals(), preset='fullfield')
 
@@ -311,5 +346,7 @@ def reconstruct_fullfield(fname, theta_st=0, theta_end=PI, n_epochs='auto', crit
         first_level = False
         del solver
         print_flush('Current iteration finished.', 0, rank)
-    comm.Barrier()
+    if support_from is not None:                 # rank 0 alone holds it; no level of this run reads fin_sup_mask after this point
+        analytic.support_mask(support_from, write_support_mask, save_path=save_path)
+    comm.Barrier()                               # (and no rank returns, to start a next run that reads the mask, before it is whole)
     return obj_delta, obj_beta

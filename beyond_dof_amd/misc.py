@@ -16,6 +16,8 @@ SUMMARY_PRESET_FF = ['obj_size', 'output_folder', 'theta_downsample', 'n_theta',
 # rotation='trilinear' only: the geometry keywords behind a preset's lines (center as given, in pixels of the full-resolution data;
 # rotation_matrices as 'given' or None)
 SUMMARY_GEOMETRY = ['rotation', 'axis_tilt', 'axis_roll', 'center', 'rotation_matrices']
+# initial_guess='ctf-fbp' only: the analytic start's keywords
+SUMMARY_ANALYTIC = ['initial_guess', 'delta_beta_ratio', 'ctf_regularization']
 
 
 def create_summary(save_path, locals_dict, var_list=None, preset=None):

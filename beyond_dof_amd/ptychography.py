@@ -77,6 +77,9 @@ def reconstruct_ptychography(fname, probe_pos, probe_size, obj_size, theta_st=0,
                              detector_weights=None, position_offsets=None, refine_positions=None, position_learning_rate=0.05,
                              n_probe_modes=1, probe_mode_power=0.02, fsc_reference=None, fsc_threshold='half-bit', **kwargs):
     t_zero = time.time()
+    if isinstance(initial_guess, str):
+        raise ValueError("initial_guess={!r}: the analytic start ('ctf-fbp') is full field's (reconstruct_fullfield); ptychography takes "
+                         "None or the arrays [delta, beta]".format(initial_guess))
     comm = kwargs.get('comm') or get_comm()
     size, rank = comm.size, comm.rank
     seed = kwargs.get('seed', int(time.time() / 60))

@@ -23,6 +23,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import DeviceBuffer
+from . import analytic
 from . import rotation as rotations
 from . import positions as probe_positions
 from . import modes as probe_modes
@@ -504,6 +505,9 @@ class FullfieldSolver(_VolumeSolver):
                                     refine=refine_geometry, rate=geometry_learning_rate)
         self.dim_y, self.dim_x, self.dim_z = int(dim_y), int(dim_x), int(dim_z)
         self.n_theta, self.mb = int(n_theta), int(minibatch_size)
+        # what analytic_volume builds its maps and filters from
+        self._rotation = (rotation, theta, axis_tilt, axis_roll, center, rotation_matrices)
+        self._analytic = dict(propagator=propagator, free_prop_cm=free_prop_cm, energy_ev=energy_ev, psize_cm=psize_cm)
         self.comm = comm or PseudoComm()
         self.eng = MultisliceEngine(self.dim_y, self.dim_x, self.dim_z, self.mb, with_grad=True, device=device, stream=stream,
                                     recompute=recompute, adjoint64=engine64, slice_binning=slice_binning)
@@ -525,6 +529,67 @@ class FullfieldSolver(_VolumeSolver):
         or not by what these amplitudes are (MultisliceEngine.choose_residual_split)."""
         self.eng.choose_residual_split(prj_abs)
         self.meas = DeviceBuffer.from_host(self.ctx, self.eng.meas_layout(prj_abs))
+
+    # ---- analytic starting volume (analytic.py; csrc/bdof_fbp.h) --------------------------------
+    def analytic_rows(self):
+        """(rows, angles) of analytic.rotation_rows for the rotation this solver runs with: for rotation='trilinear' built from theta
+        and the axis keywords the CURRENT geometry (set_geometry, refine_geometry), else what the constructor was given."""
+        rotation, theta, axis_tilt, axis_roll, center, rotation_matrices = self._rotation
+        shape = (self.dim_y, self.dim_x, self.dim_z)
+        if self.rot.geometry is not None:
+            g = self.rot.geometry.values()
+            return analytic.rotation_rows('trilinear', self.n_theta, shape, g['theta'], float(g['axis_tilt']), float(g['axis_roll']),
+                                          float(g['center']), None, g['shifts'])
+        return analytic.rotation_rows(rotation, self.n_theta, shape, theta, axis_tilt, axis_roll, center, rotation_matrices)
+
+    def analytic_volume(self, prj_abs, delta_beta_ratio=10., ctf_regularization=1e-2, object_type='normal'):
+        """Form the resident volume analytically from the measured amplitudes prj_abs (n_theta, Y, X) — with D detector planes
+        (n_theta, D, Y, X), all of which enter — and bind it: contrast-transfer-function retrieval of the projected absorption for
+        a homogeneous object delta = delta_beta_ratio * beta (regularised by ctf_regularization), a Ram-Lak filter and a
+        back-projection through the maps of this solver's rotation (bdof_ctf_retrieve, bdof_backproject; analytic.py has the
+        model), clipped at 0 and multiplied by the solver's mask.  No optimiser step; get_volume() returns the result.
+        object_type 'phase_only' / 'absorption_only': that channel alone is retrieved, the other is 0.  Detector weights of 0 take
+        their pixels out.  Every rank computes the whole volume from all angles, in batches of the minibatch size: identical bits
+        on every rank, nothing communicated.  ValueError: analytic.check_analytic's refusals (propagator='conv', a probe that is
+        not a plane wave, the far field, a negative ratio, a regularisation <= 0)."""
+        a = self._analytic
+        probe = self.pvar.get() if self.pvar is not None else self.eng.probe_arrays()
+        a0_sq = analytic.check_analytic(a['propagator'], probe[0], probe[1], delta_beta_ratio, ctf_regularization, object_type, a['free_prop_cm'])
+        D, nx, ny = self.n_planes, self.dim_x, self.dim_y
+        self.eng._check_frames(prj_abs)
+        prj_abs = np.asarray(prj_abs)
+        if len(prj_abs) != self.n_theta:
+            raise ValueError('analytic_volume takes the amplitudes of all {} angles'.format(self.n_theta))
+        rows, angles = self.analytic_rows()
+        weights = analytic.angle_weights(angles).astype(np.float32)
+        filters = DeviceBuffer.from_host(self.ctx, analytic.ctf_filters(nx, ny, a['energy_ev'], a['psize_cm'], a['free_prop_cm'], self.dim_z,
+                                                                        delta_beta_ratio, ctf_regularization, object_type))
+        wgt = None if self.eng.detector_weights is None else DeviceBuffer.from_host(
+            self.ctx, np.ascontiguousarray(np.asarray(self.eng.detector_weights, dtype=np.float32).T))
+        q = DeviceBuffer(self.ctx, self.mb * nx * ny * 4, np.float32, (self.mb, nx, ny))
+        prm = DeviceBuffer(self.ctx, self.mb * 12 * 8, np.float64, (self.mb, 12))
+        w = DeviceBuffer(self.ctx, self.mb * 4, np.float32, (self.mb,))
+        per_voxel = 1.0 / (float(a['psize_cm']) * 1e7)                # the projected quantity is in nm
+        scale = {'normal': (delta_beta_ratio * per_voxel, per_voxel), 'phase_only': (per_voxel, 0.), 'absorption_only': (0., per_voxel)}[object_type]
+        lib, h, vol = self.ctx.lib, self.ctx.handle, self.x[self.cur]
+        for i in range(0, self.n_theta, self.mb):
+            B = min(self.mb, self.n_theta - i)
+            frames = np.zeros((self.mb,) + (() if D == 1 else (D,)) + (nx, ny), dtype=np.float32)
+            frames[:B] = np.swapaxes(prj_abs[i:i + B], -2, -1)
+            r64, w32 = np.zeros((self.mb, 12)), np.zeros(self.mb, dtype=np.float32)
+            r64[:B], w32[:B] = rows[i:i + B], weights[i:i + B]
+            self.meas_stage.upload(frames)
+            prm.upload(r64)
+            w.upload(w32)
+            self.ctx.check(lib.bdof_ctf_retrieve(h, self.meas_stage.ptr, _lib._ptr(wgt), a0_sq, filters.ptr, B, D, nx, ny, q.ptr))
+            self.ctx.check(lib.bdof_backproject(h, q.ptr, nx, ny, prm.ptr, w.ptr, B, vol.ptr, self.dim_x, self.dim_z, self.dim_y,
+                                                0, self.dim_x * self.dim_z, int(i > 0), scale[0], scale[1]))
+        self.ctx.check(lib.bdof_volume_clip_mask(h, vol.ptr, _lib._ptr(self.mask), self.nvox))
+        self.ctx.sync()                                               # (the temporaries below go with this call)
+        for buf in (filters, wgt, q, prm, w):
+            if buf is not None:
+                buf.free()
+        self._bind_volume()
 
     # ---- one Adam iteration ------------------------------------------------------------------
     def _rot_loss_grad(self, angle_idx, f64=False):

@@ -8,7 +8,7 @@ reference.
 
     python examples/reconstruct_phantom.py [n=128] [n_theta=60] [n_epochs=100] [learning_rate=2e-8] [free_prop_cm=1e-3] [minibatch=10]
                                            [propagator=fft] [--loss lsq|poisson] [--poisson-multiplier 2e6] [--slice-binning 1]
-                                           [--refine-geometry center,axis_tilt] [--fsc]
+                                           [--refine-geometry center,axis_tilt] [--fsc] [--analytic-start]
 
 --loss poisson minimises the photon-counting likelihood (loss_type='poisson'); its data term is ~ 2 * multiplier times the
 least-squares one, and the L1 weights are scaled with it here.
@@ -19,6 +19,9 @@ with one step per voxel slice.
 --refine-geometry names: the data are simulated with rotation='trilinear' about an axis that is OFFSET (OFFSET below: the centre
 1.5 pixels, the tilt 0.01 rad off the nominal geometry) and reconstructed from the nominal one with refine_geometry=names; the
 refined values (out/geometry.npy) are printed beside the truth.
+--analytic-start: the run starts from initial_guess='ctf-fbp' (CTF retrieval and filtered back-projection on the device,
+FullfieldSolver.analytic_volume) instead of zeros; the correlation of that start itself with the phantom is printed first.  Combines
+with --refine-geometry: the start is then formed with the nominal (wrong) geometry the refinement begins from.
 --fsc: the resolution of the run by Fourier shell correlation (beyond_dof_amd/resolution.py).  The data are simulated and fitted
 with rotation='bilinear' (the true angles, so that a subset of them is a data set of its own).  Printed: the curve of the
 reconstruction against the phantom (fsc_reference=) with the half-bit resolution of delta and beta; then the even and the odd
@@ -53,7 +56,7 @@ OFFSET = dict(center=1.5, axis_tilt=0.01)
 
 
 def run(n=128, n_theta=60, n_epochs=100, lr=2e-8, fp=1e-3, quiet=False, mb=10, propagator='fft', loss='lsq', multiplier=2e6, slice_binning=1,
-        refine=()):
+        refine=(), analytic_start=False):
     """Simulate, write exchange/data, reconstruct, compare with the phantom: returns the figures main() prints
     (tests/test_gpu_convergence.py asserts them)."""
     import contextlib
@@ -75,18 +78,25 @@ def run(n=128, n_theta=60, n_epochs=100, lr=2e-8, fp=1e-3, quiet=False, mb=10, p
         os.makedirs('case')
         h5io.write_dataset('case/data.h5', 'exchange/data', prj.astype(np.complex64))
         reg = 2 * multiplier if loss == 'poisson' else 1.0      # the regulariser keeps its weight beside the data term
+        start_corr = None
+        if analytic_start:                                     # the start by itself, as the entry point will form it
+            a = FullfieldSolver(n, n, n, n_theta, mb, 5000., 1e-7, free_prop_cm=fp, propagator=propagator, slice_binning=slice_binning,
+                                **(dict(rotation='trilinear', theta=theta, **nominal) if refine else {}))
+            a.analytic_volume(np.abs(prj))
+            start_corr = float(np.corrcoef(a.get_volume()[0].ravel(), d.ravel())[0, 1])
+            del a
         t0 = time.time()
         with (contextlib.redirect_stdout(io.StringIO()) if quiet else contextlib.nullcontext()):
             rd, rb = reconstruct_fullfield('data.h5', theta_st=0, theta_end=2 * np.pi, n_epochs=n_epochs, learning_rate=lr,
                                            minibatch_size=mb, energy_ev=5000, psize_cm=1e-7, free_prop_cm=fp, save_path='case',
                                            output_folder='out', shrink_cycle=None, seed=3, alpha_d=1e-9 * reg, alpha_b=1e-10 * reg, gamma=0,
-                                           initial_guess=[np.zeros_like(d), np.zeros_like(d)], propagator=propagator,
-                                           loss_type=loss, poisson_multiplier=multiplier, slice_binning=slice_binning, **fit)
+                                           initial_guess='ctf-fbp' if analytic_start else [np.zeros_like(d), np.zeros_like(d)],
+                                           propagator=propagator, loss_type=loss, poisson_multiplier=multiplier, slice_binning=slice_binning, **fit)
         dt = time.time() - t0
         refined = np.load(os.path.join('case', 'out', 'geometry.npy'), allow_pickle=True).item() if refine else {}
         os.chdir(cwd)
     inner = (slice(n // 4, -n // 4),) * 3
-    return {'n': n, 'n_theta': n_theta, 'n_epochs': n_epochs, 'seconds': dt,
+    return {'n': n, 'n_theta': n_theta, 'n_epochs': n_epochs, 'seconds': dt, 'start_corr': start_corr,
             'geometry': {k: (nominal[k], float(refined[k]), truth[k]) for k in refine if k in nominal},
             'delta_corr': float(np.corrcoef(rd.ravel(), d.ravel())[0, 1]),
             'delta_corr_inner': float(np.corrcoef(rd[inner].ravel(), d[inner].ravel())[0, 1]),
@@ -152,6 +162,9 @@ def main():
     fsc = '--fsc' in sys.argv
     if fsc:
         sys.argv.remove('--fsc')
+    analytic_start = '--analytic-start' in sys.argv
+    if analytic_start:
+        sys.argv.remove('--analytic-start')
     n = int(sys.argv[1]) if len(sys.argv) > 1 else 128
     n_theta = int(sys.argv[2]) if len(sys.argv) > 2 else 60
     n_epochs = int(sys.argv[3]) if len(sys.argv) > 3 else 100
@@ -171,7 +184,9 @@ def main():
         print('resolution of the even against the odd angles (half-bit): ' + _resolution_text(resolution.resolution(r['halves'], 'half-bit')))
         return
     r = run(n, n_theta, n_epochs, lr, fp, mb=mb, propagator=propagator, loss=loss, multiplier=multiplier, slice_binning=slice_binning,
-            refine=refine)
+            refine=refine, analytic_start=analytic_start)
+    if analytic_start:
+        print('analytic start (CTF retrieval + filtered back-projection): delta correlation with the phantom {:.4f}'.format(r['start_corr']))
     for k, (start, reached, truth) in r['geometry'].items():
         print('{}: nominal {:.4f}, refined {:.4f}, simulated with {:.4f}'.format(k, start, reached, truth))
     if slice_binning > 1:

@@ -606,6 +606,39 @@ int bdof_regularizer_value(bdof_ctx* ctx, const void* x, int NXv, int NZv, int N
  * BDOF_ERR_SIZE: L > 2^30, fewer than two axes longer than 1, Nref < 4, n_shells < 1. */
 int bdof_shell_correlation(bdof_ctx* ctx, const void* vol_a, const void* vol_b, int NXv, int NZv, int NYv, int n_shells, double* out);
 
+/* ---- analytic starting volume for full field (csrc/bdof_fbp.h; DESIGN §3 "Analytic start") ----
+ * Contrast-transfer-function retrieval and Ram-Lak filter of B angles at once.  meas: DEVICE amplitudes [B][D][NX][NY] float32, D
+ * detector planes per angle in the layout the full-field solver stages; wgt: DEVICE [NX][NY] float32 weight plane or NULL — where
+ * it is 0 the contrast is 0 whatever meas holds there (NaN included); a0_sq = |a0|^2 of the plane-wave probe; filters: DEVICE
+ * complex128 [D][kx][ky] in the un-shifted index order of the transforms, G_d = conj(C_d) / (sum_d |C_d|^2 + regulariser) / (NX NY)
+ * with C_d the (in general complex, Hermitian) transfer of the projected quantity to the contrast of plane d (analytic.ctf_transfer).
+ *   g_d = m_d^2 / a0_sq - 1 (double, from the float32 amplitude),   P = sum_d Re F^-1(G_d F g_d)   (double-precision rocFFT, any NX, NY),
+ *   q[b][x][y] = sum_x' h[x - x'] P[b][x'][y],  h[0] = 1/4, h[m] = -1 / (pi^2 m^2) for odd m, 0 for even m != 0
+ * — the exact real-space Ram-Lak filter along x, the frame zero outside itself (no padding, no wrap-around), summed in float64 and
+ * rounded once: q is float32 [B][NX][NY].  The ctx keeps the complex128 work area (B D NX NY 16 bytes), grown on demand, until it
+ * is destroyed or configured again (it lies with the buffers bdof_configure replaces).  Needs no bdof_configure.
+ * BDOF_ERR_ARG: D outside [1, BDOF_MAX_PLANES], a0_sq not finite or <= 0.  BDOF_ERR_SIZE: NX > 4096, B D NX NY of 2^31 or more. */
+int bdof_ctf_retrieve(bdof_ctx* ctx, const void* meas, const void* wgt, double a0_sq, const void* filters, int B, int D, int NX, int NY,
+                      void* q);
+
+/* Back-projection of B filtered frames q [B][NXd][NYd] (float32) through rigid maps prm (DEVICE float64 [B][12], the rows of
+ * (M | t) of bdof_rotate_rigid: beam-frame voxel o = (x, z, y) samples the volume at p = M o + t) into destination rows
+ * [row0, row0 + n_rows) of the volume [NXv][NZv][NYv] of (delta, beta) pairs (row = x' NZv + z'; the slab interface of
+ * bdof_rotate_rigid_adjoint):
+ *   vol[p] (+)= (scale_delta, scale_beta) sum_b w_b bilinear(q_b; o_x, o_y),   o = M_b^T (p - t_b),   w: DEVICE float32 [B].
+ * The detector's size is independent of the volume's; a tap outside the detector counts 0.  Coordinates in float64, the two
+ * bilinear factors per axis, their product and the four-tap sum in float32; each channel's sum over b in float32 in ascending b as
+ * acc = fmaf(scale w_b, s_b, acc), from 0 or, with accumulate, from what the volume holds — so a call per batch of angles with
+ * accumulate from the second on forms the very sum of one call over all of them.  A gather without atomics: slab-wise,
+ * whole-volume and repeated calls give the same bits.  Needs no bdof_configure.
+ * BDOF_ERR_SIZE: NXv NZv NYv or NXd NYd of 2^31 or more.  BDOF_ERR_ARG: rows outside the volume. */
+int bdof_backproject(bdof_ctx* ctx, const void* q, int NXd, int NYd, const double* prm, const float* w, int B, void* vol, int NXv, int NZv,
+                     int NYv, int row0, int n_rows, int accumulate, float scale_delta, float scale_beta);
+
+/* vol = max(vol, 0) * mask over n voxels of (delta, beta) pairs, in place (mask: DEVICE float32 [n] or NULL): the clip and the
+ * finite-support mask every initial guess goes through (cnn_propagator/fullfield.py:258-262), for a volume formed on the device. */
+int bdof_volume_clip_mask(bdof_ctx* ctx, void* vol, const float* mask, size_t n);
+
 /* Shrink-wrap (cnn_propagator/fullfield.py:365-368): mask[i] *= (delta[i] > thresh) over n voxels. */
 int bdof_mask_shrink(bdof_ctx* ctx, const void* x, float* mask, size_t n, float thresh);
 
